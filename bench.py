@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — BASELINE.json metric: Mrays/s and ms/frame on the Sponza-class 1080p path trace.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   N > 1: either under a launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
   or plainly (python bench.py --gpus N): the script then starts its N ranks itself, as child processes under
   torch.distributed.run on 127.0.0.1, before anything has touched a GPU, and exits with their status.
@@ -70,7 +70,11 @@ def parse():
     ap.add_argument("--cook-torrance", action="store_true", help="extension (SURVEY 8f N2): the diffuse materials of configs 1-3 become Cook-Torrance (material type 4)")
     ap.add_argument("--cpu-sample", type=str, default="1920x1080x8", help="WxHx(max frames) rendered by the CPU oracle")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="the CPU baseline stops after the first frame that ends beyond this many seconds")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the images the timed region left on rank 0 (accumulation, output) as DIR/<name>.npy, float32")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def main():
@@ -246,6 +250,9 @@ def main():
         print(f"[debug] composition done at {time.perf_counter() - t0:.4f} s", file=sys.stderr)
     sync_all()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path reads after its last step (the runs below reset the accumulation)
+        dump_outputs(args.dump_outputs, {"accumulation": renderer.read_accumulation(), "output_bgra8": renderer.read_output_bgra8()})
 
     st = renderer.get_stats()
     my_rays = float(st.path_rays)
@@ -372,6 +379,29 @@ def main():
         rdzv.barrier()
         renderer.rccl_detach()
         rdzv.close()
+
+
+DUMP_BYTES = 64 * 10**6  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(directory, images, seed=0):
+    """--dump-outputs: every (H, W, C) image as directory/<name>.npy in float32. Images that together exceed DUMP_BYTES (two RGBA
+    images at 1080p do) are written as the same fixed, seeded sample of pixels, (N, C) each, beside sample_pixels.npy: the sample's
+    pixel indices y * W + x, float64."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    images = {k: np.asarray(v, dtype=np.float32) for k, v in images.items()}
+    h, w = next(iter(images.values())).shape[:2]
+    per_pixel = sum(a[0, 0].nbytes for a in images.values())
+    headers = 128 * (len(images) + 1)  # np.save's header per file
+    if h * w * per_pixel + headers > DUMP_BYTES:
+        n = (DUMP_BYTES - headers) // (per_pixel + 8)
+        pick = np.sort(np.random.default_rng(seed).choice(h * w, size=n, replace=False))
+        images = {k: a.reshape(h * w, -1)[pick] for k, a in images.items()}
+        images["sample_pixels"] = pick.astype(np.float64)
+    for k, a in images.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
 
 
 def signature(args, scene, W, H):

@@ -1,22 +1,23 @@
 #!/usr/bin/env python3
 """Makes tests/golden/jpeg_fixtures.npz: inputs and expected outputs for the two in-repo JPEG decoders (include/utopian_jpeg.hpp,
-rust-renderer_amd/jpeg_decode.py). Run here, where the reference checkout is mounted and Pillow (libjpeg-turbo) is installed;
-the tests themselves need neither.
+rust-renderer_amd/jpeg_decode.py). Run with Pillow (libjpeg-turbo) installed, on a reference checkout; the tests themselves need
+neither:  python tests/golden/make_jpeg_fixtures.py <reference checkout>
   * the reference's two small JPEG assets as data (utopian/data/textures/defaults/checker.jpg: baseline 4:2:0, 225 x 225;
     prototype/data/models/FlightHelmet/screenshot/screenshot.jpg: progressive 4:4:4, 130 x 130) with the RGB Pillow decodes;
   * for each of the 65 JPEG textures of prototype/data/models/Sponza/glTF (baseline 4:4:4, 1024 x 1024; too large to commit):
-    name, size, mean colour and CRC-32 of the RGB Pillow decodes - checked against the in-repo decoders where the checkout is mounted;
+    name, size, mean colour and CRC-32 of the RGB Pillow decodes - checked against the in-repo decoders on the four of them that
+    tests/golden/reference_files.npz holds;
   * synthetic JPEGs written by Pillow from a seeded image: every chroma layout it offers x baseline / progressive / optimised
     tables x awkward sizes, grey, restart intervals, low and high quality, RGB-in-JFIF-less Adobe files, and a CMYK file (refused)."""
 import glob
 import io
 import os
+import sys
 import zlib
 
 import numpy as np
 from PIL import Image
 
-REF = "/root/reference"
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "jpeg_fixtures.npz")
 
 
@@ -267,4 +268,7 @@ def main():
 
 
 if __name__ == "__main__":
+    if len(sys.argv) != 2:
+        sys.exit("usage: python tests/golden/make_jpeg_fixtures.py <reference checkout>")
+    REF = sys.argv[1]
     main()

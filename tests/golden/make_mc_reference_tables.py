@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """Makes tests/golden/mc_reference_tables.npz: the two constant lookup tables of the reference's marching cubes
 (utopian/shaders/marching_cubes/tables.glsl:4-293: edgeTable[256], triangleTable[256][16]) as plain integer arrays - the
-data the oracle's restatement of marching_cubes.comp:179-254 (oracle/oracle.cpp orc_marching_cubes) runs on. Numbers only; run
-where the reference checkout is mounted."""
+data the oracle's restatement of marching_cubes.comp:179-254 (oracle/oracle.cpp orc_marching_cubes) runs on. Numbers only:
+  python tests/golden/make_mc_reference_tables.py <reference checkout>"""
 import os
 import re
+import sys
 
 import numpy as np
 
-SRC = "/root/reference/utopian/shaders/marching_cubes/tables.glsl"
+if len(sys.argv) != 2:
+    sys.exit(__doc__)
+SRC = os.path.join(sys.argv[1], "utopian/shaders/marching_cubes/tables.glsl")
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "mc_reference_tables.npz")
 
 text = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(SRC).read(), flags=re.S)

@@ -106,3 +106,31 @@ def test_metric_names_the_real_step_count():
         assert key in src, key
     assert "camera and sun at rest" in src and "outside the timed region" in src  # the headline says what regime it is measured in
     assert "import torch" not in src, "a rank is a GPU process and imports no torch"
+
+
+def test_dump_outputs_stays_within_its_budget(bench, tmp_path):
+    """--dump-outputs: small images whole; two RGBA float32 images at 1080p (66 MB) as one seeded pixel sample within 64 MB,
+    the same pixels in every file and from run to run"""
+    import numpy as np
+
+    rng = np.random.default_rng(5)
+    small = {"accumulation": rng.random((6, 5, 4), dtype=np.float32), "output_bgra8": rng.integers(0, 256, (6, 5, 4), dtype=np.uint8)}
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    assert sorted(os.listdir(tmp_path / "small")) == ["accumulation.npy", "output_bgra8.npy"]
+    for k, v in small.items():
+        got = np.load(tmp_path / "small" / f"{k}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, v.astype(np.float32))
+    acc = np.arange(1080 * 1920 * 4, dtype=np.float32).reshape(1080, 1920, 4)
+    out = (np.arange(1080 * 1920 * 4) % 251).astype(np.uint8).reshape(1080, 1920, 4)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"accumulation": acc, "output_bgra8": out})
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["accumulation.npy", "output_bgra8.npy", "sample_pixels.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_BYTES
+    pix = np.load(tmp_path / "a" / "sample_pixels.npy")
+    assert pix.dtype == np.float64 and len(np.unique(pix)) == len(pix) > 1000000
+    idx = pix.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "accumulation.npy"), acc.reshape(-1, 4)[idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "output_bgra8.npy"), out.reshape(-1, 4)[idx].astype(np.float32))
+    for f in files:
+        assert open(tmp_path / "a" / f, "rb").read() == open(tmp_path / "b" / f, "rb").read(), f

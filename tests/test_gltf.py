@@ -1,7 +1,6 @@
 """CPU: glTF ingestion on the reference's own self-contained assets
-(read from the reference checkout where it is mounted; skipped elsewhere - nothing here runs on the
-GPU box), then the reference's Cornell scene script (prototype/src/scenes.rs:58-100, without the
-FlightHelmet whose textures are absent) rendered by the oracle."""
+(their bytes are committed in tests/golden/reference_files.npz), then the reference's Cornell scene script
+(prototype/src/scenes.rs:58-100, without the FlightHelmet whose textures are absent) rendered by the oracle."""
 import os
 
 import numpy as np
@@ -10,14 +9,19 @@ import pytest
 import oracle_api as oa
 import rust_renderer_amd as rr
 from rust_renderer_amd import gltf
-
-REF = "/root/reference/prototype/data/models"
-needs_ref = pytest.mark.skipif(not os.path.exists(os.path.join(REF, "sphere.gltf")), reason="reference assets not mounted")
+from util import reference_file
 
 
-@needs_ref
-def test_sphere_gltf_counts_and_geometry():
-    m = gltf.load_gltf(os.path.join(REF, "sphere.gltf"))
+@pytest.fixture(scope="module")
+def models(tmp_path_factory):
+    d = tmp_path_factory.mktemp("models")
+    for name in ("sphere.gltf", "CornellBox-Original.gltf"):
+        reference_file(name, d)
+    return str(d)
+
+
+def test_sphere_gltf_counts_and_geometry(models):
+    m = gltf.load_gltf(os.path.join(models, "sphere.gltf"))
     assert len(m.meshes) == 1 and m.meshes[0].num_triangles == 4512
     v = m.meshes[0].vertices
     assert np.allclose(np.linalg.norm(v["pos"][:, :3], axis=1), 1.0, atol=2e-3)
@@ -27,9 +31,8 @@ def test_sphere_gltf_counts_and_geometry():
     assert np.array_equal(m.meshes[0].transform, rr.identity3x4())
 
 
-@needs_ref
-def test_cornell_gltf_matches_the_asset_inventory():
-    m = gltf.load_gltf(os.path.join(REF, "CornellBox-Original.gltf"))
+def test_cornell_gltf_matches_the_asset_inventory(models):
+    m = gltf.load_gltf(os.path.join(models, "CornellBox-Original.gltf"))
     assert len(m.meshes) == 8 and sum(x.num_triangles for x in m.meshes) == 32 and not m.textures
     names = [x.name for x in m.meshes]
     assert names == ["floor", "ceiling", "backWall", "rightWall", "leftWall", "shortBox", "tallBox", "Light"]
@@ -58,9 +61,8 @@ def test_srt_round_trip_drops_shear():
     assert np.allclose(out[:, 3], [1, 2, 3])
 
 
-@needs_ref
-def test_reference_cornell_scene_script_renders():
-    cornell = gltf.load_gltf(os.path.join(REF, "CornellBox-Original.gltf"))
+def test_reference_cornell_scene_script_renders(models):
+    cornell = gltf.load_gltf(os.path.join(models, "CornellBox-Original.gltf"))
     light = gltf.load_cube()
     light.meshes[0].material_type = rr.DIFFUSE_LIGHT  # scenes.rs:79-80
     cam = rr.camera.Camera((0.0, 0.9, 2.0), (0.0, 0.5, 0.0), 60.0, 1.0, 0.01, 1000.0)  # scenes.rs:63-66

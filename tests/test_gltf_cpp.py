@@ -1,8 +1,8 @@
 """CPU: the C++ glTF loader (include/utopian_gltf.hpp, what the C++ host mirror uses) against the Python loader
 (rust-renderer_amd/gltf.py + image_decode.py, what the parity tests use) on glTF files written here - node hierarchies with
 matrices and TRS, strided buffer views, 8/16/32-bit indices, normalised integer attributes, data URIs and external
-files, PNG textures with every scanline filter, RGB / RGBA / palette - and, where the reference checkout is mounted, on
-the reference's own assets. Neither side needs a GPU."""
+files, PNG textures with every scanline filter, RGB / RGBA / palette - and on the reference's own assets (their bytes are
+committed in tests/golden/reference_files.npz). Neither side needs a GPU."""
 import base64
 import json
 import os
@@ -16,9 +16,9 @@ import pytest
 from rust_renderer_amd import gltf
 from rust_renderer_amd.image_decode import UnsupportedImage, load_image_rgba8
 from rust_renderer_amd.types import VERTEX_DTYPE
+from util import reference_file
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/prototype/data/models"
 
 
 @pytest.fixture(scope="module")
@@ -251,10 +251,9 @@ def test_both_loaders_refuse_what_the_reference_refuses(dump_exe, tmp_path, ctyp
     assert r.returncode == 1 and "Unsupported image format" in r.stdout
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "sphere.gltf")), reason="reference assets not mounted")
 @pytest.mark.parametrize("name", ["sphere.gltf", "CornellBox-Original.gltf"])
 def test_cpp_loader_equals_python_loader_on_the_reference_assets(dump_exe, tmp_path, name):
-    meshes, _ = compare(dump_exe, os.path.join(REF, name), tmp_path)
+    meshes, _ = compare(dump_exe, reference_file(name, tmp_path), tmp_path)
     assert sum(len(m["indices"]) // 3 for m in meshes) == (4512 if name == "sphere.gltf" else 32)
 
 

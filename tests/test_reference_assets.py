@@ -10,8 +10,8 @@ scripts restated here:
   create_sponza_scene         prototype/src/scenes.rs:102-150 camera (-10.28, 2.10, -0.18) -> (0, 0.5, 0); sphere.gltf twice, size 0.6:
                               Metal at (-3, 2.65, 0.7), Dielectric 1.5 at (-3, 0.65, 0.7)  [Sponza.bin is absent from the mount]
 
-CPU: the fixture equals what the loader reads from the reference checkout (where it is mounted), and the asset inventory of
-SURVEY.md section 2 row 22. GPU: the HIP path against the oracle on both scenes, every pass of the graph."""
+CPU: the fixture equals what the loader reads from the reference's files (their bytes: tests/golden/reference_files.npz), and
+the asset inventory of SURVEY.md section 2 row 22. GPU: the HIP path against the oracle on both scenes, every pass of the graph."""
 import os
 
 import numpy as np
@@ -22,10 +22,9 @@ import rust_renderer_amd as rr
 from rust_renderer_amd import gltf
 from rust_renderer_amd.scenes import Mesh, Model, Scene
 from rust_renderer_amd.types import VERTEX_DTYPE
-from util import L2_TOL, per_pixel_l2
+from util import L2_TOL, per_pixel_l2, reference_file
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference"
 
 
 @pytest.fixture(scope="module")
@@ -76,17 +75,16 @@ def test_fixture_matches_the_asset_inventory(assets):
     assert (np.abs(assets["default_flat_normal_map_unique"].astype(int) - [127, 127, 255, 255]) <= 2).all()  # a dithered (127.5, 127.5, 255) image
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "prototype/data/models/sphere.gltf")), reason="reference checkout not mounted")
-def test_loader_reproduces_the_fixture_from_the_reference_files(assets):
+def test_loader_reproduces_the_fixture_from_the_reference_files(assets, tmp_path):
     """pins rust-renderer_amd/gltf.py + image_decode.py against the files themselves"""
     for key, path in (("cornell", "CornellBox-Original.gltf"), ("sphere", "sphere.gltf")):
-        live, fix = gltf.load_gltf(os.path.join(REF, "prototype/data/models", path)), model_from(assets, key)
+        live, fix = gltf.load_gltf(reference_file(path, tmp_path)), model_from(assets, key)
         assert len(live.meshes) == len(fix.meshes)
         for a, b in zip(live.meshes, fix.meshes):
             assert a.vertices.tobytes() == b.vertices.tobytes() and np.array_equal(a.indices, b.indices)
             assert np.array_equal(np.asarray(a.transform, dtype=np.float32), b.transform) and a.name == b.name
     from rust_renderer_amd import image_decode
-    white = image_decode.load_image_rgba8(open(os.path.join(REF, "utopian/data/textures/defaults/white_texture.png"), "rb").read())
+    white = image_decode.load_image_rgba8(reference_file("white_texture.png"))
     assert white.shape == (128, 128, 4) and np.array_equal(white[:16, :16], assets["default_white_texture"])
 
 

@@ -1,11 +1,26 @@
 """Shared helpers for the parity tests: drive the HIP path (through the C ABI) and the CPU oracle
 through the same host calls on the same seeded scene."""
+import os
+
 import numpy as np
 
 import oracle_api as oa
 import rust_renderer_amd as rr
 
 L2_TOL = 1e-3  # BASELINE.json north_star: per-pixel L2 <= 1e-3 on linear radiance
+REFERENCE_FILES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_files.npz")
+
+
+def reference_file(name, directory=None):
+    """the bytes of one of the reference's own asset files, by file name (tests/golden/reference_files.npz, made by
+    tests/golden/make_reference_file_fixtures.py); with `directory`: the file written there, and its path"""
+    data = np.load(REFERENCE_FILES)[name].tobytes()
+    if directory is None:
+        return data
+    path = os.path.join(str(directory), name)
+    with open(path, "wb") as f:
+        f.write(data)
+    return path
 
 
 def make_pair(scene, W, H, **oracle_kw):

@@ -2,7 +2,7 @@
 # Same-box A/B of builds of the library: tools/ab.sh "<bench args>" lib1.so lib2.so ... ("-" = the default libutopian_hip.so), two rounds
 # interleaved. Per run: the timed rate, ms per frame, the serialised per-kernel times of the bench's calibration frames (ms per frame,
 # one 16-frame wavefront alone on the GPU) and the counted node / triangle visits per closest-hit ray.
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 cd $root
 args=$1; shift
 run() {

@@ -2,7 +2,7 @@
 # usage: tools/ab_bench.sh <tag> [bench.py args...]: the bench line of the in-tree library and of rust-renderer_amd/libutopian_hip_prev.so
 # (a build of an earlier commit, same box, back to back) -> gpurun_out/<tag>_new.json / <tag>_prev.json
 tag=$1; shift
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 cd $root
 for which in new prev new prev; do
   if [ $which = prev ]; then export UTOPIAN_HIP_LIB=$root/rust-renderer_amd/libutopian_hip_prev.so; else unset UTOPIAN_HIP_LIB; fi

@@ -1,6 +1,6 @@
 #!/bin/bash
 # same-box comparison of two builds of the library over the BASELINE configs: tools/ab_configs.sh [libA.so libB.so]
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 cd $root
 A=${1:-libutopian_hip_prev.so}; B=${2:-libutopian_hip.so}
 run() { lib=$1; shift; printf "%-26s %-58s" "$lib" "$*"; UTOPIAN_HIP_LIB=$root/rust-renderer_amd/$lib timeout -k 10 300 python bench.py --warmup 8 --no-cpu-baseline --no-alone --no-tree-walk "$@" 2>/dev/null | tail -1 | python -c "

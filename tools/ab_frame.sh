@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of one frame per call: tools/ab_frame.sh "<frame_timeline.py args>" lib1.so lib2.so ... ("-" = the default library), two
 # rounds interleaved; per run the interactive (a wait after every frame) and pipelined (four in flight) frame times.
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 cd $root
 args=$1; shift
 for rep in 1 2; do for lib in "$@"; do

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of library options: tools/ab_opt.sh "<bench args>" "name=a [name2=b ...]" "name=c" ...  ("-" = defaults), two rounds interleaved.
 # Per run: the timed rate, ms per frame, the serialised per-kernel times of the bench's calibration frames, one frame per call (waited for / in flight).
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 cd $root
 args=$1; shift
 run() {

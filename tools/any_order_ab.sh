@@ -2,7 +2,7 @@
 # child order for visibility walks: (A) triangles, then nodes by descending area, slots taken in ascending order (the product);
 # (B) the same tree walked from the highest slot down = smallest node first; (C) nodes in ascending area walked from the
 # highest slot down = largest node first, triangles last
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd $(cd "$(dirname "$0")/.." && pwd)
 visits() { python - <<'PY'
 import sys
 sys.path.insert(0, '.')

@@ -1,6 +1,6 @@
 #!/bin/bash
 # bench lines of configs 2-4 with their own bounded CPU-oracle sample
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd $(cd "$(dirname "$0")/.." && pwd)
 tag=r02
 timeout -k 10 300 python bench.py --config 2 --steps 32 --cpu-sample 1920x1080x4 > gpurun_out/${tag}_bench_config2.json 2>gpurun_out/c2.err
 timeout -k 10 400 python bench.py --config 3 --width 3840 --height 2160 --steps 16 --cpu-sample 3840x2160x1 > gpurun_out/${tag}_bench_config3_4k.json 2>gpurun_out/c3.err

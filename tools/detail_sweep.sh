@@ -1,6 +1,6 @@
 #!/bin/bash
 # frame rate against scene size (--detail scales the tessellation): how much of the frame time is the BVH working set missing the 4 MiB L2 of an XCD?
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd $(cd "$(dirname "$0")/.." && pwd)
 for d in 1.0 0.5 0.25 0.1 0.03; do
   printf "detail %-5s " $d
   timeout -k 10 200 python bench.py --steps 64 --warmup 8 --no-cpu-baseline --no-alone --detail $d --tex-size 64 2>/dev/null | tail -1 | python -c "

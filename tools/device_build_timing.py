@@ -1,6 +1,7 @@
 """Option "device_build": build time and traversal quality of the Morton-order tree against the host SAH tree."""
+import os
 import sys, time
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import rust_renderer_amd as rr
 W, H = 1920, 1080
 for cfg in (1, 3):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: tools/final_benches.sh <tag>: the bench lines DESIGN.md section 7 quotes -> gpurun_out/<tag>_bench_*.json (copy into profiles/)
 tag=$1
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 cd $root
 run() { name=$1; shift; timeout -k 10 280 python3 bench.py "$@" > gpurun_out/${tag}_bench_$name.json 2> gpurun_out/${tag}_bench_$name.err || echo "$name failed"; echo "$name done"; }
 run main --steps 64 --warmup 8

@@ -1,6 +1,6 @@
 #!/bin/bash
 # the round's committed evidence: default bench line, kernel trace + counter passes of the same command line, the other BASELINE configs
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 cd $root
 tag=${1:-r03}
 timeout -k 10 300 python bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err

@@ -1,5 +1,6 @@
+import os
 import sys
-sys.path.insert(0,'/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import rust_renderer_amd as rr
 for cfg,W,H in ((1,1920,1080),(2,1920,1080),(4,1920,1080),(0,256,256),(1,3840,2160),(3,1920,1080),(1,2560,1440)):

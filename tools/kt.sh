@@ -2,7 +2,7 @@
 # usage: tools/kt.sh <tag> [bench.py args...] : rocprofv3 --kernel-trace --stats of `python3 bench.py --no-cpu-baseline --no-alone <args>`;
 # prints the per-kernel summary (the CSV stays under gpurun_out/<tag>_kt)
 tag=$1; shift
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 export TMPDIR=/tmp
 cd $root
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $root/gpurun_out/${tag}_kt --output-format csv -- python3 bench.py --no-cpu-baseline --no-alone "$@" > gpurun_out/${tag}_bench_under_rocprof.json 2> gpurun_out/${tag}_kt.log || { echo "kernel trace failed"; tail -5 gpurun_out/${tag}_kt.log; }

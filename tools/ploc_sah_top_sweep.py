@@ -1,6 +1,7 @@
 """Option "ploc_sah_top": PLOC rounds stop at K clusters and a host SAH tree over them is the top - rebuild time, traversal quality, frame time."""
+import os
 import sys, time
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import rust_renderer_amd as rr
 W, H = 1920, 1080
 for cfg, tops in ((1, (0, 1024, 4096, 8192, 16384, 32768, 131072)), (3, (0, 8192, 65536))):

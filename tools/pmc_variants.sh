@@ -1,7 +1,7 @@
 #!/bin/bash
 # counters of k_trace_closest for builds of the library, on the same box: tools/pmc_variants.sh <tag prefix> lib1.so lib2.so ... ("-" = default)
 # (the raw bounce rays of tools/raw_trace_bench.py: 2.07 M diffuse bounce rays of the config-1 scene, the kernel alone on the GPU)
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 prefix=$1; shift
 for lib in "$@"; do
    name=$(basename $lib .so); [ "$lib" = "-" ] && name=base

@@ -5,7 +5,7 @@
 # (2) the counter passes of tools/pmc_passes.sh on `python3 bench.py --steps 48 --warmup 16 --no-cpu-baseline --no-alone <args>`.
 # Afterwards, off the GPU box: python tools/pmc_summary.py <tag> --bench ; cp gpurun_out/<tag>_kt/**/*kernel_stats.csv profiles/
 tag=$1; shift
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 export TMPDIR=/tmp
 export UH_BENCH_SIGNATURE=$root/gpurun_out/bench_signature.json
 cd $root

@@ -1,6 +1,6 @@
 #!/bin/bash
 # load balance of the tile partition: every rank's share of an 8-rank job, one after the other on one GPU
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 cd $root
 for tile in 64 32; do
 for r in 0 1 2 3 4 5 6 7; do

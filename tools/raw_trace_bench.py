@@ -1,9 +1,10 @@
 """Raw closest-hit traversal kernel on the config-1 scene at 1080p: primary rays once, then the 2.07 M diffuse
 bounce rays built from their hits, `reps` times (the profiling target of tools/pmc_passes.sh: the bounce-ray
 dispatches are the median of the per-kernel counters).  usage: raw_trace_bench.py [reps] [option=value ...]"""
+import os
 import sys
 import numpy as np
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import rust_renderer_amd as rr
 
 W, H = 1920, 1080

@@ -1,7 +1,8 @@
 """uh_refit_acceleration vs uh_build_acceleration on the config-2 scene, and what a refit after moving
 the two spheres costs the traversal (nodes/ray)."""
+import os
 import sys, time
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import rust_renderer_amd as rr
 W, H = 1920, 1080

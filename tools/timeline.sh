@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: tools/timeline.sh <tag> [frame_timeline.py args...] : the kernel trace of one-frame-per-call frames, then the last frame's timeline
 tag=$1; shift
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 export TMPDIR=/tmp
 cd $root
 rm -rf gpurun_out/${tag}_tl

@@ -1,6 +1,7 @@
 """Per-ray traversal statistics of the closest-hit kernel (diagnostic batch kernel: node / triangle visits per ray), config-1 scene."""
+import os
 import sys
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import rust_renderer_amd as rr
 W, H = 1920, 1080
 scene = rr.scenes.scene_for_config(1, tex_size=64)

@@ -10,9 +10,10 @@ XCDs (block b -> XCD b % 8) - so the ORDER of the rays decides which XCD traces 
              rays inside a region in random order
    regions+pixel   the same, rays inside a region in pixel order
 usage: xcd_locality_experiment.py [reps]"""
+import os
 import sys
 import numpy as np
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import rust_renderer_amd as rr
 
 W, H = 1920, 1080
