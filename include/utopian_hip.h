@@ -251,7 +251,9 @@ typedef struct uh_ctx uh_ctx;
  *   uh_add_texture_rgba8 uploads into a fresh allocation no frame in flight can reference (textures enter a frame's tables at the
  *        next uh_build_acceleration) and is complete on return;
  *   uh_trace_closest / uh_trace_any run on the context's first stream, in order with the frames of that stream, read the scene
- *        only, and are complete on return.
+ *        only, and are complete on return;
+ *   uh_render_hybrid enqueues like a frame, ordered behind the frames in flight and before those that follow (on the context's first
+ *        stream, after a wait for the others); uh_read_hybrid and uh_get_hybrid_stats wait and are complete on return.
  * The sun-direction grid and the camera grid are (re)built inside the first frame call that wants them, after a wait for the frames in flight. */
 
 /* ---- lifetime -------------------------------------------------------------------------- */
@@ -494,6 +496,61 @@ int uh_mgpu_reset_stats(uh_mgpu* group);
  * passes by bands of rows, one band per GPU (uh_set_restir_partition), the bands exchanged by peer copies after every
  * spatial pass; 0 = every GPU runs them for the whole frame */
 int uh_mgpu_set_option(uh_mgpu* group, const char* name, int value);
+
+/* ---- the hybrid graph's ray-traced passes (build_render_graph, utopian/src/renderers/mod.rs:61-186) -------------------------
+ * Per-context verbs: they have no uh_mgpu_ twin. The rasterized graph of the reference (key 2 of the prototype) traces rays in
+ * two passes over a G-buffer of four targets (create_gbuffer_textures, mod.rs:17-45):
+ *   UH_HYBRID_GBUFFER         gbuffer_pass (gbuffer.vert / gbuffer.frag) as a cast of the un-jittered primary rays - the same rays and
+ *                             the same traversal as UH_PASS_GBUFFER, so the position target equals gbuffer_position bit for bit - and
+ *                             a resolve of position RGBA32F, normal RGBA32F (normal-mapped where the tangent is not zero), albedo RGBA8
+ *                             (the diffuse map without base_color_factor, alpha 255) and pbr RGBA32F (metallic = the metallic-roughness
+ *                             map's b, roughness = its g, occlusion = the occlusion map's r, the material index: mesh i has material i)
+ *   UH_HYBRID_RT_SHADOWS      rt_shadows (rt_shadows.rgen): one any-hit ray per pixel toward normalize(view.sun_dir) from the G-buffer's
+ *                             texel corner; R8: 0 occluded, 255 not (sun_shadow_enabled / shadows_enabled are not read, as there)
+ *   UH_HYBRID_RT_REFLECTIONS  rt_reflections (rt_reflections.rgen/.rchit/.rmiss, IBL off): one closest-hit ray per pixel whose material
+ *                             is metal (raytrace_properties.x == 1), RGBA8 = 0.1 * diffuse texel * base colour on a hit, the sky
+ *                             (white under option "furnace") on a miss, alpha 0; every other pixel (0, 0, 0, 0)
+ * PASS ORDER is the reference's (rt_shadows is added to the graph before gbuffer_pass, mod.rs:100-119, and the graph runs passes in the
+ * order they were added, graph.rs:743): with UH_HYBRID_ALL, rt_shadows reads the G-buffer of the PREVIOUS hybrid call, then the G-buffer
+ * pass runs, then rt_reflections on the new G-buffer. A caller that wants this frame's shadows calls with UH_HYBRID_GBUFFER, then with
+ * UH_HYBRID_RT_SHADOWS.
+ * RESOURCES of its own, separate from the path-tracing graph's gbuffer_position (each graph of the reference creates its own): allocated by
+ * the first uh_render_hybrid (61 bytes per pixel with the reflection queue; UH_ERR_OUT_OF_MEMORY when that fails), cleared to
+ * (1, 1, 1, 0) - albedo (255, 255, 255, 0), rt_shadows 255, rt_reflections (255, 255, 255, 0) - and freed by uh_destroy. A context
+ * that never calls uh_render_hybrid allocates nothing for it.
+ * ISOLATION: a hybrid call changes nothing a path-traced frame reads or reports (accumulation, gbuffer_position, reservoirs, UhStats,
+ * the camera / sun grids' state); its rays and times go to UhHybridStats only. The passes are always full-frame:
+ * uh_set_tile_partition and uh_set_restir_partition do not apply to them.
+ * GATES: view->raytracing_supported == 0 skips both ray-traced passes and leaves their images as they are (mod.rs:107,134);
+ * UH_HYBRID_RT_REFLECTIONS with view->ibl_enabled == 1 is UH_ERR_INVALID_ARGUMENT - the IBL maps (irradiance, specular, BRDF LUT of
+ * ibl.rs) are not part of this library - and nothing runs; mask bits, UH_ERR_NOT_BUILT and moved instances with view->rebuild_tlas
+ * as for uh_render_frame (bits outside UH_HYBRID_ALL are ignored).
+ * STREAM ORDER: uh_render_hybrid enqueues like a frame (behind the frames in flight, ahead of those that follow); uh_read_hybrid and
+ * uh_get_hybrid_stats wait for all work of the context and are complete on return.
+ * Arithmetic: DESIGN.md section 2, "Hybrid passes". */
+enum { UH_HYBRID_RT_SHADOWS = 1u << 0, UH_HYBRID_GBUFFER = 1u << 1, UH_HYBRID_RT_REFLECTIONS = 1u << 2, UH_HYBRID_ALL = 7 };
+/* which image uh_read_hybrid copies out (W*H texels each) */
+enum {
+   UH_HYBRID_POSITION = 0,   /* RGBA32F */
+   UH_HYBRID_NORMAL = 1,     /* RGBA32F */
+   UH_HYBRID_ALBEDO = 2,     /* RGBA8 */
+   UH_HYBRID_PBR = 3,        /* RGBA32F */
+   UH_HYBRID_SHADOWS = 4,    /* R8 */
+   UH_HYBRID_REFLECTIONS = 5 /* RGBA8 */
+};
+/* the last uh_render_hybrid call: rays[0] G-buffer cast, rays[1] rt_shadows, rays[2] rt_reflections (= metal pixels); pass_ms the
+ * hipEvent time of each pass in the same order (0 for a pass that did not run) */
+typedef struct UhHybridStats {
+   uint64_t rays[3];
+   float pass_ms[3];
+   uint32_t reflection_pixels;
+   uint32_t reserved[2];
+} UhHybridStats;
+UH_LAYOUT_ASSERT(sizeof(UhHybridStats) == 48 && offsetof(UhHybridStats, pass_ms) == 24 && offsetof(UhHybridStats, reflection_pixels) == 36,
+                 "UhHybridStats (48 B)");
+int uh_render_hybrid(uh_ctx* ctx, const UhViewUniformData* view, uint32_t hybrid_mask);
+int uh_read_hybrid(uh_ctx* ctx, int which, void* out); /* UH_ERR_INVALID_ARGUMENT before the first uh_render_hybrid */
+int uh_get_hybrid_stats(uh_ctx* ctx, UhHybridStats* out);
 
 #ifdef __cplusplus
 }

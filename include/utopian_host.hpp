@@ -298,6 +298,21 @@ class Renderer {
       check(uh_get_stats(ctx_, &s), "get_stats");
       return s;
    }
+   // the hybrid graph's ray-traced passes (build_render_graph, renderers/mod.rs:61-186): rt_shadows on the previous G-buffer, the
+   // G-buffer pass, rt_reflections on the new one - for the bits of `mask` (utopian_hip.h "uh_render_hybrid")
+   void render_hybrid(const UhViewUniformData& view, uint32_t mask = UH_HYBRID_ALL) { check(uh_render_hybrid(ctx_, &view, mask), "render_hybrid"); }
+   // one image as bytes: W*H texels of 16 (position, normal, pbr), 4 (albedo, reflections) or 1 (shadows) bytes
+   std::vector<uint8_t> read_hybrid(int which) {
+      const size_t texel = (which == UH_HYBRID_SHADOWS) ? 1 : (which == UH_HYBRID_ALBEDO || which == UH_HYBRID_REFLECTIONS) ? 4 : 16;
+      std::vector<uint8_t> out((size_t)width_ * height_ * texel);
+      check(uh_read_hybrid(ctx_, which, out.data()), "read_hybrid");
+      return out;
+   }
+   UhHybridStats hybrid_stats() {
+      UhHybridStats s;
+      check(uh_get_hybrid_stats(ctx_, &s), "hybrid_stats");
+      return s;
+   }
    // uh_set_option: "device_build", "frames_in_flight", ... (DESIGN.md "Options")
    void set_option(const char* name, int value) { check(uh_set_option(ctx_, name, value), name); }
    // marching_cubes.rs:17-83 / marching_cubes.comp: the density field's iso-surface, extracted on the GPU and added

@@ -21,8 +21,16 @@ from .types import (
     RESERVOIR_DTYPE,
     RESTIR_EXCHANGE_FN,
     VERTEX_DTYPE,
+    HYBRID_ALBEDO,
+    HYBRID_ALL,
+    HYBRID_NORMAL,
+    HYBRID_POSITION,
+    HYBRID_PBR,
+    HYBRID_REFLECTIONS,
+    HYBRID_SHADOWS,
     GpuLight,
     GpuMaterial,
+    HybridStats,
     Reservoir,
     RestirRows,
     Stats,
@@ -68,10 +76,14 @@ class CApi:
             "set_restir_partition": [vp, u32, u32, vp, vp],
             "get_restir_rows": [vp, p(RestirRows)],
             "resolve_output": [vp, u32, u32],
+            "render_hybrid": [vp, p(ViewUniformData), u32],
+            "read_hybrid": [vp, C.c_int, vp],
+            "get_hybrid_stats": [vp, p(HybridStats)],
         }
+        hybrid = ("render_hybrid", "read_hybrid", "get_hybrid_stats")
         for name, argtypes in sig.items():
-            if not hasattr(lib, prefix + name) and (name == "render_frames" or prefix == "uh_mgpu_"):
-                continue  # the oracle renders frame by frame; the GPU group has no per-context queries
+            if not hasattr(lib, prefix + name) and (name == "render_frames" or name in hybrid or prefix == "uh_mgpu_"):
+                continue  # the oracle renders frame by frame and has no hybrid passes; the GPU group has no per-context queries
             fn = getattr(lib, prefix + name)
             fn.argtypes, fn.restype = argtypes, C.c_int
             setattr(self, name, fn)
@@ -400,6 +412,42 @@ class Renderer:
         out = np.empty((self.height, self.width, 4), dtype=np.float32)
         self._check(self._api.read_gbuffer_position(self._ctx, out.ctypes.data))
         return out
+
+    # -- the hybrid graph's ray-traced passes (uh_render_hybrid; include/utopian_hip.h) ----
+    def _hybrid_api(self):
+        if self.backend != "hip" or not hasattr(self._api, "render_hybrid"):
+            raise NotImplementedError(f"the hybrid passes (rt_shadows / rt_reflections) are per-context verbs of the HIP library; backend {self.backend!r} has none")
+        return self._api
+
+    def render_hybrid(self, view, mask=HYBRID_ALL):
+        """rt_shadows (previous G-buffer), gbuffer, rt_reflections (this one) - the reference's pass order - for the bits of `mask`"""
+        api = self._hybrid_api()
+        self._check(api.render_hybrid(self._ctx, C.byref(view), int(mask)))
+
+    _HYBRID_IMAGES = {
+        HYBRID_POSITION: (np.float32, 4),
+        HYBRID_NORMAL: (np.float32, 4),
+        HYBRID_ALBEDO: (np.uint8, 4),
+        HYBRID_PBR: (np.float32, 4),
+        HYBRID_SHADOWS: (np.uint8, 1),
+        HYBRID_REFLECTIONS: (np.uint8, 4),
+    }
+
+    def read_hybrid(self, which):
+        """one image of the hybrid graph: (H, W, 4) float32 position / normal / pbr, (H, W, 4) uint8 albedo / reflections, (H, W) uint8 shadows"""
+        api = self._hybrid_api()
+        if which not in self._HYBRID_IMAGES:
+            raise ValueError(f"hybrid image index {which} (0..5)")
+        dtype, ch = self._HYBRID_IMAGES[which]
+        out = np.empty((self.height, self.width, ch) if ch > 1 else (self.height, self.width), dtype=dtype)
+        self._check(api.read_hybrid(self._ctx, int(which), out.ctypes.data))
+        return out
+
+    def hybrid_stats(self):
+        api = self._hybrid_api()
+        s = HybridStats()
+        self._check(api.get_hybrid_stats(self._ctx, C.byref(s)))
+        return s
 
     # -- stand-alone ray queries ----------------------------------------------------------
     def trace_closest(self, rays):

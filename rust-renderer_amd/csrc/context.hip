@@ -311,6 +311,22 @@ struct uh_ctx {
    // tail waits for it like for a frame's (last_acc)
    DevBuf<float4> tile_send, tile_recv;
    hipEvent_t ev_compose = nullptr;
+
+   // the hybrid graph's passes (uh_render_hybrid): images, the metal-pixel queue and a copy of the scene's meshes as gbuffer.vert
+   // reads them, all allocated by the first call
+   struct Hybrid {
+      DevBuf<float4> pos, nrm, pbr;
+      DevBuf<uchar4> alb, refl;
+      DevBuf<uint8_t> shadow;
+      DevBuf<uint32_t> queue, counter;
+      DevBuf<HybridMesh> meshes;
+      DevBuf<UhVertex> vertices;
+      DevBuf<uint32_t> indices;
+      uint64_t geom = 0;                       // geom_version the mesh tables were made for
+      hipEvent_t waits[2 * kMaxSlots + 1] = {};  // behind the frames in flight
+      hipEvent_t ev[4] = {};                   // pass boundaries of the last call (timing)
+      bool ran[3] = {false, false, false};     // G-buffer, rt_shadows, rt_reflections in the last call
+   } hy;
 };
 
 namespace {
@@ -562,6 +578,22 @@ void uh_destroy(uh_ctx* c) {
    c->output.release();
    for (auto& r : c->reservoirs) r.release();
    c->dstats.release();
+   {  // (its events were recorded on the slots' streams: they go first)
+      uh_ctx::Hybrid& h = c->hy;
+      for (auto* b : {&h.pos, &h.nrm, &h.pbr}) b->release();
+      h.alb.release();
+      h.refl.release();
+      h.shadow.release();
+      h.queue.release();
+      h.counter.release();
+      h.meshes.release();
+      h.vertices.release();
+      h.indices.release();
+      for (hipEvent_t ev : h.waits)
+         if (ev) (void)hipEventDestroy(ev);
+      for (hipEvent_t ev : h.ev)
+         if (ev) (void)hipEventDestroy(ev);
+   }
    for (auto& s : c->slots) s.destroy();
    for (hipEvent_t ev : c->ev_band)
       if (ev) (void)hipEventDestroy(ev);
@@ -2503,6 +2535,187 @@ int uh_read_mesh(uh_ctx* c, uint32_t mesh_index, UhVertex* vertices, uint32_t* i
    const HostMesh& m = c->meshes[mesh_index];
    if (vertices && !m.vertices.empty()) std::memcpy(vertices, m.vertices.data(), m.vertices.size() * sizeof(UhVertex));
    if (indices && !m.indices.empty()) std::memcpy(indices, m.indices.data(), m.indices.size() * sizeof(uint32_t));
+   return UH_OK;
+}
+
+// ---- the hybrid graph's ray-traced passes (utopian_hip.h "uh_render_hybrid") ----
+static int hybrid_alloc(uh_ctx* c) {
+   uh_ctx::Hybrid& h = c->hy;
+   if (h.counter.p) return UH_OK;
+   const size_t n = (size_t)c->W * c->H;
+   HIP_TRY(c, h.pos.alloc(n));
+   HIP_TRY(c, h.nrm.alloc(n));
+   HIP_TRY(c, h.pbr.alloc(n));
+   HIP_TRY(c, h.alb.alloc(n));
+   HIP_TRY(c, h.refl.alloc(n));
+   HIP_TRY(c, h.shadow.alloc(n));
+   HIP_TRY(c, h.queue.alloc(n));
+   for (hipEvent_t& ev : h.waits)
+      if (!ev) HIP_TRY(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+   for (hipEvent_t& ev : h.ev)
+      if (!ev) HIP_TRY(c, hipEventCreate(&ev));
+   HIP_TRY(c, h.counter.alloc(1));  // last: its pointer says "allocated"
+   return UH_OK;
+}
+
+// the meshes as the vertex and fragment shaders read them: vertices, indices, the instance's world matrix and the material's maps
+static int hybrid_tables(uh_ctx* c) {
+   uh_ctx::Hybrid& h = c->hy;
+   if (h.geom == c->geom_version && h.meshes.p) return UH_OK;
+   std::vector<HybridMesh> ms(c->meshes.size());
+   size_t nv = 0, ni = 0;
+   for (size_t i = 0; i < c->meshes.size(); i++) {
+      const HostMesh& m = c->meshes[i];
+      HybridMesh& d = ms[i];
+      for (int r = 0; r < 3; r++)
+         for (int k = 0; k < 3; k++) d.o2w[3 * r + k] = m.o2w[4 * r + k];
+      std::memcpy(d.w2o, m.w2o, sizeof(d.w2o));
+      d.vertex_base = (uint32_t)nv;
+      d.index_base = (uint32_t)ni;
+      d.diffuse_map = m.material.diffuse_map;
+      d.normal_map = m.material.normal_map;
+      d.metallic_roughness_map = m.material.metallic_roughness_map;
+      d.occlusion_map = m.material.occlusion_map;
+      nv += m.vertices.size();
+      ni += m.indices.size();
+   }
+   if (nv >= (1ull << 32) || ni >= (1ull << 32)) return fail(c, UH_ERR_CAPACITY, "uh_render_hybrid: more than 2^32 vertices or indices");
+   std::vector<UhVertex> verts;
+   std::vector<uint32_t> idx;
+   verts.reserve(nv);
+   idx.reserve(ni);
+   for (const HostMesh& m : c->meshes) {
+      verts.insert(verts.end(), m.vertices.begin(), m.vertices.end());
+      idx.insert(idx.end(), m.indices.begin(), m.indices.end());
+   }
+   HIP_TRY(c, h.meshes.alloc(ms.size()));
+   HIP_TRY(c, h.vertices.alloc(verts.size()));
+   HIP_TRY(c, h.indices.alloc(idx.size()));
+   if (!ms.empty()) HIP_TRY(c, hipMemcpyAsync(h.meshes.p, ms.data(), ms.size() * sizeof(HybridMesh), hipMemcpyHostToDevice, c->stream));
+   if (!verts.empty()) HIP_TRY(c, hipMemcpyAsync(h.vertices.p, verts.data(), verts.size() * sizeof(UhVertex), hipMemcpyHostToDevice, c->stream));
+   if (!idx.empty()) HIP_TRY(c, hipMemcpyAsync(h.indices.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+   HIP_TRY(c, hipStreamSynchronize(c->stream));  // the host vectors go out of scope
+   h.geom = c->geom_version;
+   return UH_OK;
+}
+
+int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!view) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_render_hybrid: null view");
+   if ((mask & UH_HYBRID_RT_REFLECTIONS) && view->ibl_enabled == 1)
+      return fail(c, UH_ERR_INVALID_ARGUMENT,
+                  "uh_render_hybrid: rt_reflections with view.ibl_enabled = 1 needs the IBL maps (irradiance, specular, BRDF LUT of ibl.rs), "
+                  "which are not part of this library; set ibl_enabled = 0 for the reflection pass's non-IBL branch");
+   if (!c->built && c->topology_valid && view->rebuild_tlas == 1)
+      if (int st = uh_refit_acceleration(c)) return st;
+   if (!c->built) return fail(c, UH_ERR_NOT_BUILT, "uh_render_hybrid before uh_build_acceleration");
+   HIP_TRY(c, hipSetDevice(c->device));
+   uh_ctx::Hybrid& h = c->hy;
+   const bool first = !h.counter.p;
+   if (int st = hybrid_alloc(c)) return st;
+   if (int st = hybrid_tables(c)) return st;
+   const FrameParams fp = make_params(c, *view);
+   HybridDev hd{};
+   hd.pos = h.pos.p;
+   hd.nrm = h.nrm.p;
+   hd.alb = h.alb.p;
+   hd.pbr = h.pbr.p;
+   hd.shadow = h.shadow.p;
+   hd.refl = h.refl.p;
+   hd.queue = h.queue.p;
+   hd.counter = h.counter.p;
+   hd.meshes = h.meshes.p;
+   hd.vertices = h.vertices.p;
+   hd.indices = h.indices.p;
+   for (int a = 0; a < 3; a++) {
+      hd.sun_dir[a] = fp.sun_dir[a];
+      hd.eye[a] = view->eye_pos[a];
+   }
+   hd.W = c->W;
+   hd.H = c->H;
+   hd.furnace = c->furnace ? 1u : 0u;
+   // behind every frame in flight: the context's first stream (slot 0's, where this call runs) waits for the others
+   int w = 0;
+   for (uint32_t i = 1; i < kMaxSlots; i++) {
+      const Slot& s = c->slots[i];
+      if (!s.ready) continue;
+      for (hipStream_t st : {s.stream, s.side}) {
+         HIP_TRY(c, hipEventRecord(h.waits[w], st));
+         HIP_TRY(c, hipStreamWaitEvent(c->stream, h.waits[w++], 0));
+      }
+   }
+   if (c->restir_stream) {
+      HIP_TRY(c, hipEventRecord(h.waits[w], c->restir_stream));
+      HIP_TRY(c, hipStreamWaitEvent(c->stream, h.waits[w++], 0));
+   }
+   if (c->slots[0].ready) {
+      HIP_TRY(c, hipEventRecord(h.waits[w], c->slots[0].side));
+      HIP_TRY(c, hipStreamWaitEvent(c->stream, h.waits[w++], 0));
+   }
+   LaunchCfg lc = cfg(c);
+   lc.count_visits = false;  // nothing of this call goes to UhStats
+   if (first) launch_hybrid_clear(lc, hd);
+   // the camera grid when the path tracer's is built for this camera and geometry (read only: the grid's state is the path tracer's)
+   float mats[32];
+   std::memcpy(mats, fp.inv_view, sizeof(float) * 16);
+   std::memcpy(mats + 16, fp.inv_proj, sizeof(float) * 16);
+   const bool grid = c->cam_grid_enabled && c->cam_valid && c->cam_geom == c->geom_version && std::memcmp(mats, c->cam_mats, sizeof(mats)) == 0;
+   const bool rt = view->raytracing_supported != 0;
+   h.ran[0] = (mask & UH_HYBRID_GBUFFER) != 0;
+   h.ran[1] = rt && (mask & UH_HYBRID_RT_SHADOWS);
+   h.ran[2] = rt && (mask & UH_HYBRID_RT_REFLECTIONS);
+   // pass order of build_render_graph (mod.rs:100-134, graph.rs:743): rt_shadows, gbuffer, rt_reflections
+   HIP_TRY(c, hipEventRecord(h.ev[0], c->stream));
+   if (h.ran[1]) launch_hybrid_shadows(lc, c->scene, hd);
+   HIP_TRY(c, hipEventRecord(h.ev[1], c->stream));
+   if (h.ran[0]) launch_hybrid_gbuffer(lc, fp, c->scene, hd, grid ? &c->cam_dev : nullptr);
+   HIP_TRY(c, hipEventRecord(h.ev[2], c->stream));
+   if (h.ran[2]) {
+      HIP_TRY(c, hipMemsetAsync(h.counter.p, 0, sizeof(uint32_t), c->stream));
+      launch_hybrid_reflections(lc, c->scene, hd);
+   }
+   HIP_TRY(c, hipEventRecord(h.ev[3], c->stream));
+   HIP_TRY(c, hipGetLastError());
+   return UH_OK;
+}
+
+int uh_read_hybrid(uh_ctx* c, int which, void* out) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   const uh_ctx::Hybrid& h = c->hy;
+   if (!h.counter.p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid before the first uh_render_hybrid");
+   const size_t n = (size_t)c->W * c->H;
+   switch (which) {
+   case UH_HYBRID_POSITION: return read_back(c, out, h.pos.p, n * sizeof(float4));
+   case UH_HYBRID_NORMAL: return read_back(c, out, h.nrm.p, n * sizeof(float4));
+   case UH_HYBRID_ALBEDO: return read_back(c, out, h.alb.p, n * sizeof(uchar4));
+   case UH_HYBRID_PBR: return read_back(c, out, h.pbr.p, n * sizeof(float4));
+   case UH_HYBRID_SHADOWS: return read_back(c, out, h.shadow.p, n);
+   case UH_HYBRID_REFLECTIONS: return read_back(c, out, h.refl.p, n * sizeof(uchar4));
+   default: return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..5");
+   }
+}
+
+int uh_get_hybrid_stats(uh_ctx* c, UhHybridStats* out) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_hybrid_stats: null destination");
+   std::memset(out, 0, sizeof(*out));
+   const uh_ctx::Hybrid& h = c->hy;
+   if (!h.counter.p) return UH_OK;
+   HIP_TRY(c, hipSetDevice(c->device));
+   if (int st = sync_all(c)) return st;
+   uint32_t metal = 0;
+   if (h.ran[2]) HIP_TRY(c, hipMemcpy(&metal, h.counter.p, sizeof(metal), hipMemcpyDeviceToHost));
+   const uint64_t n = (uint64_t)c->W * c->H;
+   out->rays[0] = h.ran[0] ? n : 0;
+   out->rays[1] = h.ran[1] ? n : 0;
+   out->rays[2] = metal;
+   out->reflection_pixels = metal;
+   const int from[3] = {1, 0, 2};  // G-buffer between events 1 and 2, rt_shadows 0 and 1, rt_reflections 2 and 3
+   for (int k = 0; k < 3; k++) {
+      float ms = 0.0f;
+      if (h.ran[k]) HIP_TRY(c, hipEventElapsedTime(&ms, h.ev[from[k]], h.ev[from[k] + 1]));
+      out->pass_ms[k] = ms;
+   }
    return UH_OK;
 }
 

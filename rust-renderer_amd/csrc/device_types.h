@@ -194,6 +194,31 @@ struct RowSpans {
 };
 inline RowSpans whole_frame(uint32_t W, uint32_t H) { return RowSpans{{0, 0}, {H, 0}, W}; }
 
+// The hybrid (rasterized) graph's ray-traced passes (uh_render_hybrid; renderers/mod.rs:61-186): its own G-buffer of four targets
+// and the two images rt_shadows / rt_reflections write. Full-frame, pixel = y * W + x everywhere.
+struct HybridMesh {           // what gbuffer.vert / gbuffer.frag read per mesh (push constants + Material)
+   float o2w[9];              // mat3(world): row-major upper 3x3 of the object-to-world 3x4
+   float w2o[9];              // its inverse (= MeshShade::w2o): mat3(transpose(inverse(world))) * n reads it by columns
+   uint32_t vertex_base, index_base;  // the mesh's first vertex / index in HybridDev::vertices / indices
+   uint32_t diffuse_map, normal_map, metallic_roughness_map, occlusion_map;
+};
+struct HybridDev {
+   float4* pos;       // gbuffer_position RGBA32F
+   float4* nrm;       // gbuffer_normal RGBA32F
+   uchar4* alb;       // gbuffer_albedo RGBA8
+   float4* pbr;       // gbuffer_pbr RGBA32F (metallic, roughness, occlusion, material index)
+   uint8_t* shadow;   // rt_shadows output R8
+   uchar4* refl;      // rt_reflections output RGBA8
+   uint32_t* queue;   // metal pixels, compacted (rt_reflections)
+   uint32_t* counter; // [0]: entries of `queue`
+   const HybridMesh* meshes;
+   const UhVertex* vertices;
+   const uint32_t* indices;
+   float sun_dir[3];  // normalize(view.sun_dir), as FrameParams::sun_dir
+   float eye[3];      // view.eye_pos
+   uint32_t W, H, furnace;
+};
+
 // launch wrappers implemented in kernels.hip --------------------------------------------------
 struct LaunchCfg {
    hipStream_t stream;
@@ -232,6 +257,13 @@ void launch_spatial_reuse(const LaunchCfg&, const FrameParams&, const SceneDev&,
 // stand-alone queries (n rays in ray_o/ray_d[0..n), identity queue)
 void launch_trace_closest_raw(const LaunchCfg&, const SceneDev&, const float4* ray_o, const float4* ray_d, float4* hit, uint32_t n);
 void launch_trace_any_raw(const LaunchCfg&, const SceneDev&, const float4* ray_o, const float4* ray_d, uint32_t* occluded, uint32_t n);
+// the hybrid graph's passes (uh_render_hybrid): every pixel of the frame
+void launch_hybrid_clear(const LaunchCfg&, const HybridDev&);
+// the G-buffer cast of launch_gbuffer (same rays, same traversal choice) and the resolve of all four targets; the cast's ray and hit
+// records live in the targets themselves until the resolve (ray_o = normal, ray_d = pbr, hit = position target)
+void launch_hybrid_gbuffer(const LaunchCfg&, const FrameParams&, const SceneDev&, const HybridDev&, const SunGridDev* camera_grid);
+void launch_hybrid_shadows(const LaunchCfg&, const SceneDev&, const HybridDev&);
+void launch_hybrid_reflections(const LaunchCfg&, const SceneDev&, const HybridDev&);
 // tiles
 // on-device refit (refit.hip): per-mesh object->world rows, and what one refit pass touches
 struct RefitMesh {

@@ -2510,4 +2510,215 @@ void launch_unpack_tiles(const LaunchCfg& c, float4* acc, const float4* in, uint
    k_tiles<false><<<stream_grid(c, W * H), kBlock, 0, c.stream>>>(acc, const_cast<float4*>(in), W, H, rank, world, tile);
 }
 
+// ------------------------------------------------------------------------------------------
+// The hybrid graph's ray-traced passes (build_render_graph, renderers/mod.rs:61-186): a G-buffer of four targets (gbuffer.vert /
+// gbuffer.frag as a primary-ray cast), rt_shadows (rt_shadows.rgen) and rt_reflections (rt_reflections.{rgen,rchit,rmiss}, the
+// IBL-off branch). Arithmetic: DESIGN.md section 2 "Hybrid passes".
+// ------------------------------------------------------------------------------------------
+// the clear value of every target (pass.rs:210-214): (1, 1, 1, 0); the two RT images hold the same until their pass first runs
+__global__ __launch_bounds__(kBlock) void k_hybrid_clear(HybridDev hd, uint32_t n) {
+   for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+      const float4 one = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+      hd.pos[i] = one;
+      hd.nrm[i] = one;
+      hd.pbr[i] = one;
+      hd.alb[i] = make_uchar4(255, 255, 255, 0);
+      hd.shadow[i] = 255;
+      hd.refl[i] = make_uchar4(255, 255, 255, 0);
+   }
+}
+
+__device__ __forceinline__ V3 cross3(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+// mat3(world) * a: ((col0 * x + col1 * y) + col2 * z), world row-major
+__device__ __forceinline__ V3 mat3_mul(const float* m, V3 a) {
+   return v3((m[0] * a.x + m[1] * a.y) + m[2] * a.z, (m[3] * a.x + m[4] * a.y) + m[5] * a.z, (m[6] * a.x + m[7] * a.y) + m[8] * a.z);
+}
+// mat3(transpose(inverse(world))) * n with the row-major inverse: the same expression as world_normal_of (rchit:32)
+__device__ __forceinline__ V3 inverse_transpose_mul(const float* w2o, V3 n) {
+   return v3((n.x * w2o[0] + n.y * w2o[3]) + n.z * w2o[6], (n.x * w2o[1] + n.y * w2o[4]) + n.z * w2o[7], (n.x * w2o[2] + n.y * w2o[5]) + n.z * w2o[8]);
+}
+
+// gbuffer.vert:29-46 per vertex + the rasteriser's interpolation + gbuffer.frag:27-51, at the cast's hit. The cast left its records in the
+// targets: ray origin in the normal target, direction in the pbr target, hit record (t, u, v, packet) in the position target; a lane
+// reads the three of its pixel before it writes the four.
+__global__ __launch_bounds__(kBlock) void k_hybrid_gbuffer_resolve(SceneDev sc, HybridDev hd, uint32_t n) {
+   for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < n; j += gridDim.x * kBlock) {
+      const float4 h = hd.pos[j], ro = hd.nrm[j], rd = hd.pbr[j];
+      const uint32_t packet = __float_as_uint(h.w);
+      const float4 clear = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+      float4 pos = clear, nrm = clear, pbr = clear;
+      uchar4 alb = make_uchar4(255, 255, 255, 0);
+      if (packet != kEmptyRef) {
+         const V3 p = v3(ro.x, ro.y, ro.z) + h.x * v3(rd.x, rd.y, rd.z);  // k_gbuffer_resolve's expression: the same words
+         pos = make_float4(p.x, p.y, p.z, 1.0f);
+         const uint32_t key = __float_as_uint(sc.tris[kTriStride16 * (size_t)packet + 2].y);
+         const uint32_t mesh = key >> kPrimBits, prim = key & kPrimMask;
+         const HybridMesh m = hd.meshes[mesh];
+         const uint32_t* tri = hd.indices + m.index_base + 3 * (size_t)prim;
+         const UhVertex* vb = hd.vertices + m.vertex_base;
+         const UhVertex& v0 = vb[tri[0]];
+         const UhVertex& v1 = vb[tri[1]];
+         const UhVertex& v2 = vb[tri[2]];
+         const float b0 = 1.0f - h.y - h.z, b1 = h.y, b2 = h.z;
+         auto lerp3 = [&](V3 a, V3 b, V3 c) { return (a * b0 + b * b1) + c * b2; };
+         auto vec = [](const float* f) { return v3(f[0], f[1], f[2]); };
+         const float uu = (v0.uv[0] * b0 + v1.uv[0] * b1) + v2.uv[0] * b2;
+         const float vv = (v0.uv[1] * b0 + v1.uv[1] * b1) + v2.uv[1] * b2;
+         const V3 n0 = vec(v0.normal), n1 = vec(v1.normal), n2 = vec(v2.normal);
+         const V3 t0 = vec(v0.tangent), t1 = vec(v1.tangent), t2 = vec(v2.tangent);
+         const V3 tangent = lerp3(t0, t1, t2);                                            // in_tangent.xyz
+         V3 nn;
+         if (tangent.x != 0.0f || tangent.y != 0.0f || tangent.z != 0.0f) {             // frag:41
+            auto tbn = [&](V3 nk, V3 tk, V3& T, V3& B, V3& N) {                            // vert:31-35
+               T = normalize3(mat3_mul(m.o2w, tk));
+               B = normalize3(mat3_mul(m.o2w, cross3(nk, tk)));
+               N = normalize3(mat3_mul(m.o2w, nk));
+            };
+            V3 T0, B0, N0, T1, B1, N1, T2, B2, N2;
+            tbn(n0, t0, T0, B0, N0);
+            tbn(n1, t1, T1, B1, N1);
+            tbn(n2, t2, T2, B2, N2);
+            const V3 T = lerp3(T0, T1, T2), B = lerp3(B0, B1, B2), N = lerp3(N0, N1, N2);
+            const V3 nm = sample_texture(sc, sc.unorm_lut, m.normal_map, uu, vv);
+            const V3 x = normalize3(v3(nm.x * 2.0f - 1.0f, nm.y * 2.0f - 1.0f, nm.z * 2.0f - 1.0f));  // frag:43
+            nn = normalize3((T * x.x + B * x.y) + N * x.z);                                  // frag:44
+         } else {
+            nn = normalize3(lerp3(inverse_transpose_mul(m.w2o, n0), inverse_transpose_mul(m.w2o, n1), inverse_transpose_mul(m.w2o, n2)));  // vert:41, frag:39
+         }
+         nrm = make_float4(nn.x, nn.y, nn.z, 1.0f);
+         const V3 d = sample_texture(sc, sc.unorm_lut, m.diffuse_map, uu, vv);
+         alb = make_uchar4((unsigned char)unorm8(d.x), (unsigned char)unorm8(d.y), (unsigned char)unorm8(d.z), 255);
+         const V3 mr = sample_texture(sc, sc.unorm_lut, m.metallic_roughness_map, uu, vv);
+         const V3 oc = sample_texture(sc, sc.unorm_lut, m.occlusion_map, uu, vv);
+         pbr = make_float4(mr.z, mr.y, oc.x, (float)mesh);  // one material per mesh: material index = mesh index
+      }
+      hd.pos[j] = pos;
+      hd.nrm[j] = nrm;
+      hd.alb[j] = alb;
+      hd.pbr[j] = pbr;
+   }
+}
+
+// rt_shadows.rgen:17-38: one any-hit ray per pixel toward the sun from the G-buffer's texel corner. Persistent waves with the LDS refill
+// of k_trace_shadow; the pool carries no ray records (the lane that takes pixel p makes its ray from the G-buffer there).
+__global__ __launch_bounds__(kBlock, 5) void k_hybrid_shadow(SceneDev sc, HybridDev hd) {
+   __shared__ uint32_t s_stack[kWavesPerBlock][kLdsStack][64];
+   __shared__ RayPool<0> s_pool[kWavesPerBlock];
+   const uint32_t lane = lane_id();
+   const uint32_t wave = threadIdx.x >> 6;
+   uint32_t* lds_col = &s_stack[wave][0][lane];
+   RayPool<0>& pool = s_pool[wave];
+   RaySource src;
+   src.queue = nullptr;
+   src.count = hd.W * hd.H;
+   src.cursor = nullptr;
+   src.wave_index = blockIdx.x * kWavesPerBlock + wave;
+   src.num_waves = gridDim.x * kWavesPerBlock;
+   auto source_of = [](int, uint32_t) { return (const float4*)nullptr; };
+   Feeder<0> f;
+   Trav t;
+   t.cur = kEmptyRef;
+   t.sp = 0;
+   uint32_t pix = 0, n_nodes = 0, n_tris = 0;
+   uint32_t spill[kSpillStack];
+   const V3 sun = v3(hd.sun_dir[0], hd.sun_dir[1], hd.sun_dir[2]);  // rgen:28
+   auto take = [&](uint32_t slot) {
+      pix = f.pool_base + slot;
+      const uint32_t px = pix % hd.W, py = pix / hd.W;
+      const V3 p = gbuffer_fetch(hd.pos, hd.W, px, py), nn = gbuffer_fetch(hd.nrm, hd.W, px, py);  // rgen:22-24 (not renormalised)
+      const V3 o = offset_ray(p, nn);                                                                // rgen:25
+      trav_init(t, make_float4(o.x, o.y, o.z, 0.001f), make_float4(sun.x, sun.y, sun.z, 10000.0f), 0.001f, 10000.0f, INFINITY);
+   };
+   while (refill_lanes<0>(f, src, pool, t.cur == kEmptyRef, source_of, take)) {
+      if (t.cur != kEmptyRef) {
+         bool occluded = false;
+         if (trav_step<true, false>(sc.nodes, sc.tris, t, lds_col, spill, occluded, n_nodes, n_tris)) hd.shadow[pix] = occluded ? 0 : 255;  // rgen:34-37
+      }
+   }
+}
+
+// the texel-corner fetch of gbuffer_fetch, alpha only
+__device__ __forceinline__ float gbuffer_fetch_w(const float4* __restrict__ g, uint32_t W, uint32_t px, uint32_t py) {
+   uint32_t x0 = px == 0 ? 0 : px - 1, y0 = py == 0 ? 0 : py - 1;
+   return ((g[(size_t)y0 * W + x0].w + g[(size_t)y0 * W + px].w) + (g[(size_t)py * W + x0].w + g[(size_t)py * W + px].w)) * 0.25f;
+}
+
+// rt_reflections.rgen:34-47, the test: the material of uint(filtered pbr.a) is metal. Metal pixels are appended to a dense queue (one
+// atomic per wave), every other pixel gets (0, 0, 0, 0) here.
+__global__ __launch_bounds__(kBlock) void k_hybrid_reflect_classify(SceneDev sc, HybridDev hd) {
+   const uint32_t n = hd.W * hd.H, groups = (n + 63) / 64, lane = lane_id();
+   for (uint32_t g = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); g < groups; g += gridDim.x * kWavesPerBlock) {
+      const uint32_t pix = g * 64u + lane;
+      const bool own = pix < n;
+      bool metal = false;
+      if (own) {
+         const uint32_t material = (uint32_t)gbuffer_fetch_w(hd.pbr, hd.W, pix % hd.W, pix / hd.W);  // rgen:34: the filtered index, truncated
+         metal = material < sc.num_meshes && sc.meshes[material].type == 1.0f;                       // rgen:38
+         if (!metal) hd.refl[pix] = make_uchar4(0, 0, 0, 0);                                         // rgen:46
+      }
+      const uint32_t slot = wave_append(hd.counter, metal);
+      if (metal) hd.queue[slot] = pix;
+   }
+}
+
+// rt_reflections.rgen:22-44 + .rchit:22-64 (IBL off) + .rmiss:9-24 for the queued metal pixels: closest hit, then a lane shades its own ray
+__global__ __launch_bounds__(kBlock) void k_hybrid_reflect(SceneDev sc, HybridDev hd) {
+   __shared__ uint32_t s_stack[kWavesPerBlock][kLdsStack][64];
+   uint32_t* lds_col = &s_stack[threadIdx.x >> 6][0][lane_id()];
+   const uint32_t count = *hd.counter;
+   const V3 eye = v3(hd.eye[0], hd.eye[1], hd.eye[2]), sun = v3(hd.sun_dir[0], hd.sun_dir[1], hd.sun_dir[2]);
+   uint32_t n_nodes = 0, n_tris = 0;
+   for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < count; i += gridDim.x * kBlock) {
+      const uint32_t pix = hd.queue[i], px = pix % hd.W, py = pix / hd.W;
+      const V3 p = gbuffer_fetch(hd.pos, hd.W, px, py), nn = gbuffer_fetch(hd.nrm, hd.W, px, py);  // rgen:28-30
+      const V3 o = offset_ray(p, nn);                                                                // rgen:31
+      const V3 to_eye = normalize3(eye - o);                                                         // rgen:33
+      const V3 dir = reflect3(vneg(to_eye), nn);                                                     // rgen:34: I - (2 dot(N, I)) N, N not normalised
+      Hit h;
+      V3 c;
+      if (traverse<false, false>(sc, o, dir, 0.001f, 10000.0f, INFINITY, h, lds_col, n_nodes, n_tris)) {
+         const float4* s = sc.shade + 4 * (size_t)h.idx;
+         const float4 s0 = s[0], s1 = s[1], s2 = s[2], s3 = s[3];
+         V3 normal;
+         float uu, vv;
+         surface_normal_uv(s0, s1, s2, s3, h.u, h.v, normal, uu, vv);                                // rchit:30,39
+         const MeshShade ms = sc.meshes[__float_as_uint(s3.w)];
+         V3 color = sample_texture(sc, sc.unorm_lut, ms.diffuse_map, uu, vv);                        // rchit:41
+         color = color * v3(ms.base_color[0], ms.base_color[1], ms.base_color[2]);                   // rchit:42
+         c = 0.1f * color;                                                                           // rchit:62
+      } else if (hd.furnace) {
+         c = v3(1.0f, 1.0f, 1.0f);                                                                   // rmiss:12 (FURNACE_TEST)
+      } else {
+         const V3 sk = sky::integrate_scattering(o, dir, 999999999.0f, sun);                         // rmiss:16-19
+         c = v3(fminf(sk.x, 1.0f), fminf(sk.y, 1.0f), fminf(sk.z, 1.0f));                            // rmiss:22
+      }
+      hd.refl[pix] = make_uchar4((unsigned char)unorm8(c.x), (unsigned char)unorm8(c.y), (unsigned char)unorm8(c.z), 0);  // rgen:42
+   }
+}
+
+void launch_hybrid_clear(const LaunchCfg& c, const HybridDev& hd) {
+   k_hybrid_clear<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(hd, hd.W * hd.H);
+}
+void launch_hybrid_gbuffer(const LaunchCfg& c, const FrameParams& fp, const SceneDev& sc, const HybridDev& hd, const SunGridDev* camera_grid) {
+   const uint32_t n = hd.W * hd.H;
+   const RawRays rr{hd.nrm, hd.pbr, hd.pos};
+   const RowSpans spans = whole_frame(hd.W, hd.H);
+   k_gbuffer_generate<<<stream_grid(c, n), kBlock, 0, c.stream>>>(fp, rr, spans);
+   if (camera_grid)
+      k_gbuffer_camera_grid<<<stream_grid(c, n), kBlock, 0, c.stream>>>(sc, rr, spans, hd.W, *camera_grid);
+   else {
+      const uint32_t full = c.num_cus * c.closest_blocks_per_cu, need = (n + kBlock - 1) / kBlock;
+      launch_closest(c, dim3(need < full ? need : full), sc, false, rr.ray_o, rr.ray_d, rr.hit, 0, nullptr, nullptr, 0, 0, 0, n);
+   }
+   k_hybrid_gbuffer_resolve<<<stream_grid(c, n), kBlock, 0, c.stream>>>(sc, hd, n);
+}
+void launch_hybrid_shadows(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd) {
+   const uint32_t full = c.num_cus * c.shadow_blocks_per_cu, need = (hd.W * hd.H + kBlock - 1) / kBlock;
+   k_hybrid_shadow<<<dim3(need < full ? need : full), kBlock, 0, c.stream>>>(sc, hd);
+}
+void launch_hybrid_reflections(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd) {
+   k_hybrid_reflect_classify<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(sc, hd);
+   k_hybrid_reflect<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(sc, hd);
+}
+
 }  // namespace uh

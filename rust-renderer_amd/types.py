@@ -166,3 +166,17 @@ PASS_ALL = 0x3F
 
 UH_OK = 0
 ERR_NAMES = {1: "INVALID_ARGUMENT", 2: "NO_DEVICE", 3: "HIP", 4: "CAPACITY", 5: "NOT_BUILT", 6: "OUT_OF_MEMORY"}
+
+# the hybrid graph's ray-traced passes (uh_render_hybrid; utopian/src/renderers/mod.rs:61-186)
+HYBRID_RT_SHADOWS, HYBRID_GBUFFER, HYBRID_RT_REFLECTIONS = 1 << 0, 1 << 1, 1 << 2
+HYBRID_ALL = 7
+HYBRID_POSITION, HYBRID_NORMAL, HYBRID_ALBEDO, HYBRID_PBR, HYBRID_SHADOWS, HYBRID_REFLECTIONS = range(6)
+
+
+class HybridStats(C.Structure):
+    """UhHybridStats: the last uh_render_hybrid call - rays and hipEvent ms of (G-buffer, rt_shadows, rt_reflections)"""
+
+    _fields_ = [("rays", C.c_uint64 * 3), ("pass_ms", C.c_float * 3), ("reflection_pixels", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+assert C.sizeof(HybridStats) == 48 and HybridStats.pass_ms.offset == 24 and HybridStats.reflection_pixels.offset == 36

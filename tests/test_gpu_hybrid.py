@@ -1,0 +1,331 @@
+"""GPU: the hybrid graph's ray-traced passes (uh_render_hybrid) against the CPU reference of tests/hybrid_reference.py - the G-buffer's
+four targets and rt_shadows byte for byte, rt_reflections byte for byte where the ray hits and within 1 LSB where it meets the sky -,
+the reference's pass order and gates, and the isolation of a hybrid call from the path-tracing graph."""
+import numpy as np
+import pytest
+
+import hybrid_reference as hr
+import oracle_api as oa
+import rust_renderer_amd as rr
+from rust_renderer_amd.api import UtopianError
+from rust_renderer_amd.scenes import Mesh, Model, Scene, icosphere, procedural_texture, quad
+from test_reference_assets import reference_cornell_scene, reference_spheres_scene
+
+pytestmark = pytest.mark.gpu
+
+W, H = 160, 120
+
+
+@pytest.fixture(scope="module")
+def assets():
+    import os
+
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_assets.npz"))
+
+
+def _normal_map(size=32):
+    """a bumpy tangent-space normal map (z dominant), RGBA8"""
+    y, x = np.meshgrid(np.arange(size), np.arange(size), indexing="ij")
+    nx, ny = 0.45 * np.sin(x * 0.7), 0.45 * np.cos(y * 0.5)
+    nz = np.sqrt(np.maximum(1.0 - nx * nx - ny * ny, 0.0))
+    rgba = np.stack([(nx * 0.5 + 0.5) * 255, (ny * 0.5 + 0.5) * 255, (nz * 0.5 + 0.5) * 255, np.full_like(nx, 255)], axis=-1)
+    return np.ascontiguousarray(np.rint(rgba).astype(np.uint8))
+
+
+class SyntheticScene(Scene):
+    """mesh 0: a metal, normal-mapped floor (tangent (1, 0, 0)) - material 0 is metal, so the sky pixels trace too; mesh 1: a
+    Lambertian sphere under a rotated, non-uniformly scaled instance, tangent zero; mesh 2: a normal-mapped box-side quad under another
+    rotation and scale, textured maps everywhere; mesh 3: a metal sphere. The upper rows see the sky."""
+
+    def upload(self, renderer):
+        renderer.default_diffuse_map()
+        tex = [renderer.add_texture(procedural_texture(11, k, 32)) for k in range(4)]
+        nmap = renderer.add_texture(_normal_map())
+
+        def mat(kind, diffuse, normal, base=(1.0, 1.0, 1.0, 1.0)):
+            m = rr.make_material(kind, 0.0, base, diffuse_map=diffuse)
+            m.normal_map, m.metallic_roughness_map, m.occlusion_map = normal, tex[2], tex[3]
+            return m
+
+        fv, fi = quad((-6.0, 0.0, 6.0), (12.0, 0.0, 0.0), (0.0, 0.0, -12.0), nu=6, nv=6, uv_scale=(3.0, 3.0))
+        fv["tangent"][:, :3] = (1.0, 0.0, 0.0)
+        renderer.add_mesh(fv, fi, mat(rr.METAL, tex[0], nmap, (0.9, 0.8, 0.7, 1.0)))
+        sv, si = icosphere(2)
+        rot = np.array([[0.8, -0.6, 0.0], [0.6, 0.8, 0.0], [0.0, 0.0, 1.0]], np.float32)
+        renderer.add_mesh(sv, si, mat(rr.LAMBERTIAN, tex[1], nmap, (0.5, 0.9, 0.4, 1.0)), rr.transform3x4((1.4, 0.6, 0.9), (-1.5, 0.8, 0.0), rot))
+        qv, qi = quad((-1.0, -1.0, 0.0), (2.0, 0.0, 0.0), (0.0, 2.0, 0.0), nu=3, nv=3, uv_scale=(2.0, 2.0))
+        qv["tangent"][:, :3] = (1.0, 0.0, 0.0)
+        rot2 = np.array([[0.0, 0.0, 1.0], [0.0, 1.0, 0.0], [-1.0, 0.0, 0.0]], np.float32) @ np.array([[0.96, 0.0, -0.28], [0.0, 1.0, 0.0], [0.28, 0.0, 0.96]], np.float32)
+        renderer.add_mesh(qv, qi, mat(rr.LAMBERTIAN, tex[2], nmap), rr.transform3x4((1.0, 0.7, 1.6), (2.2, 1.0, -1.0), rot2))
+        renderer.add_mesh(sv, si, mat(rr.METAL, tex[3], nmap), rr.transform3x4((0.7, 0.7, 0.7), (0.6, 0.7, 1.4)))
+        renderer.initialize_raytracing()
+        return renderer
+
+
+def synthetic_scene():
+    cam = rr.camera.Camera((0.0, 2.2, 6.5), (0.0, 0.9, 0.0), 60.0, W / H, 0.01, 1000.0)
+    return SyntheticScene("hybrid_synthetic", [], [], cam, dict(sky_enabled=1))
+
+
+def scene_named(name, assets):
+    return {"cornell": lambda: reference_cornell_scene(assets), "spheres": lambda: reference_spheres_scene(assets), "synthetic": synthetic_scene}[name]()
+
+
+def pair(scene, width=W, height=H):
+    gpu = rr.Renderer(width, height)
+    cpu = oa.OracleRenderer(width, height)
+    meshes = hr.upload_recorded(scene, gpu, defaults=not isinstance(scene, SyntheticScene))
+    hr.upload_recorded(scene, cpu, defaults=not isinstance(scene, SyntheticScene))
+    return gpu, cpu, meshes
+
+
+def hybrid_view(scene, width=W, height=H, **kw):
+    v = scene.make_view(width, height, **kw)
+    v.ibl_enabled = 0  # the reflection pass's non-IBL branch: the IBL maps are not part of the library
+    return v
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def read_gbuffer(r):
+    return {k: r.read_hybrid(i) for k, i in (("position", rr.HYBRID_POSITION), ("normal", rr.HYBRID_NORMAL), ("albedo", rr.HYBRID_ALBEDO), ("pbr", rr.HYBRID_PBR))}
+
+
+def assert_reflections(got, ref, kind):
+    assert np.array_equal(got[kind == 0], ref[kind == 0]) and not got[kind == 0].any(), "non-metal pixels are exactly 0"
+    assert np.array_equal(got[kind == 1], ref[kind == 1]), "pixels whose ray hits are byte-identical"
+    d = np.abs(got[kind == 2].astype(np.int16) - ref[kind == 2].astype(np.int16))
+    assert d.size == 0 or d.max() <= 1, "sky pixels within 1 LSB"
+    assert (got[..., 3] == 0).all()
+
+
+# ---- 1. the G-buffer ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["cornell", "spheres", "synthetic"])
+@pytest.mark.parametrize("camera_grid", [1, 0])
+def test_gbuffer_position_is_the_path_tracers_and_the_targets_are_the_references(assets, name, camera_grid):
+    scene = scene_named(name, assets)
+    gpu, cpu, meshes = pair(scene)
+    gpu.set_option("camera_grid", camera_grid)
+    view = hybrid_view(scene)
+    for _ in range(2):  # the same camera twice: the camera grid is built (option on) and the G-buffer cast goes through it
+        gpu.render_frame(view, rr.PASS_GBUFFER)
+    grid = gpu.get_stats().camera_grid_cells > 0
+    # (the library refuses the grid for the spheres view - long per-pixel lists - and the cast walks the tree there)
+    assert grid == (bool(camera_grid) and name != "spheres")
+    gpu.render_hybrid(view, rr.HYBRID_GBUFFER)
+    got = read_gbuffer(gpu)
+    assert np.array_equal(bits(got["position"]), bits(gpu.read_gbuffer_position()))
+    ref = hr.gbuffer(cpu, meshes, view, W, H)
+    for k in ("position", "normal", "pbr"):
+        assert np.array_equal(bits(got[k]), bits(ref[k])), k
+    assert np.array_equal(got["albedo"], ref["albedo"])
+    hit = got["position"][..., 3] == 1.0
+    assert hit.any() and (name == "cornell" or (~hit).any()), "the view holds surfaces (and, but for the closed box, sky)"
+    if name == "synthetic":
+        assert (np.abs(got["normal"][hit][:, :3] - [0.0, 1.0, 0.0]).max(axis=1) > 1e-3).any(), "the normal map bends the floor's normals"
+
+
+# ---- 2. rt_shadows --------------------------------------------------------------------------------------------------------
+SUNS = [(sx * 0.4, sy * 1.0, sz * 0.7) for sx in (1, -1) for sy in (1, -1) for sz in (1, -1)] + [(1.0, 0.02, 0.1)]
+
+
+@pytest.mark.parametrize("name", ["cornell", "spheres", "synthetic"])
+def test_shadows_equal_the_reference_in_every_octant(assets, name):
+    scene = scene_named(name, assets)
+    gpu, cpu, meshes = pair(scene)
+    view = hybrid_view(scene)
+    gpu.render_hybrid(view, rr.HYBRID_GBUFFER)
+    g = read_gbuffer(gpu)
+    for sun in SUNS:
+        view.sun_dir[:] = sun
+        gpu.render_hybrid(view, rr.HYBRID_RT_SHADOWS)
+        got = gpu.read_hybrid(rr.HYBRID_SHADOWS)
+        ref = hr.shadows(cpu, g["position"], g["normal"], view)
+        assert np.array_equal(got, ref), f"sun {sun}: {np.count_nonzero(got != ref)} pixels differ"
+        s = gpu.hybrid_stats()
+        assert list(s.rays) == [0, W * H, 0] and s.pass_ms[1] > 0.0
+
+
+def test_shadows_at_1080p_on_the_config1_scene():
+    scene = rr.scenes.scene_for_config(1, with_spheres=True)  # Sponza-class with the reference's two spheres, one of them metal
+    Wf, Hf = 1920, 1080
+    gpu, cpu = scene.upload(rr.Renderer(Wf, Hf)), scene.upload(oa.OracleRenderer(Wf, Hf))
+    view = hybrid_view(scene, Wf, Hf)
+    gpu.render_hybrid(view, rr.HYBRID_GBUFFER)
+    gpu.render_hybrid(view, rr.HYBRID_RT_SHADOWS)
+    got = gpu.read_hybrid(rr.HYBRID_SHADOWS)
+    ref = hr.shadows(cpu, gpu.read_hybrid(rr.HYBRID_POSITION), gpu.read_hybrid(rr.HYBRID_NORMAL), view)  # trace_any batched (one call)
+    assert np.array_equal(got, ref), f"{np.count_nonzero(got != ref)} pixels differ"
+    assert 0 < np.count_nonzero(got == 0) < Wf * Hf
+
+
+# ---- 3. rt_reflections ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["spheres", "synthetic"])
+@pytest.mark.parametrize("furnace", [0, 1])
+def test_reflections_equal_the_reference(assets, name, furnace):
+    scene = scene_named(name, assets)
+    gpu, cpu, meshes = pair(scene)
+    gpu.set_option("furnace", furnace)
+    view = hybrid_view(scene)
+    gpu.render_hybrid(view, rr.HYBRID_GBUFFER | rr.HYBRID_RT_REFLECTIONS)
+    g = read_gbuffer(gpu)
+    got = gpu.read_hybrid(rr.HYBRID_REFLECTIONS)
+    ref, kind = hr.reflections(cpu, meshes, g["position"], g["normal"], g["pbr"], view, furnace=bool(furnace))
+    assert_reflections(got, ref, kind)
+    assert (kind == 1).any() and (kind == 2).any()
+    if furnace:
+        assert (got[kind == 2][:, :3] == 255).all(), "under furnace every miss is white"
+    s = gpu.hybrid_stats()
+    assert s.reflection_pixels == s.rays[2] == np.count_nonzero(kind) and s.rays[0] == W * H and s.rays[1] == 0
+    if name == "synthetic":
+        sky = (g["position"][..., 3] == 0) & (hr.corner(g["position"])[..., 3] == 0)
+        assert sky.any() and (kind[sky] != 0).all(), "material 0 is metal: the sky pixels trace"
+
+
+def _flat(origin, eu, ev, n=1):
+    v, i = quad(origin, eu, ev, nu=n, nv=n)
+    return v, i
+
+
+def test_metal_floor_under_a_flat_ceiling_reflects_a_tenth_of_its_colour():
+    c = (0.8, 0.4, 0.2)
+    floor = Mesh(*_flat((-50.0, 0.0, 50.0), (100.0, 0.0, 0.0), (0.0, 0.0, -100.0)), rr.METAL, name="floor")
+    ceiling = Mesh(*_flat((-500.0, 1.0, -500.0), (1000.0, 0.0, 0.0), (0.0, 0.0, 1000.0)), rr.LAMBERTIAN, base_color=c + (1.0,), name="ceiling")
+    cam = rr.camera.Camera((0.0, 0.5, 0.0), (0.0, 0.0, -1.0), 60.0, W / H, 0.01, 1000.0)
+    scene = Scene("mirror_floor", [(Model([floor, ceiling], []), None)], [], cam)
+    gpu, cpu, meshes = pair(scene)
+    view = hybrid_view(scene)
+    gpu.render_hybrid(view, rr.HYBRID_GBUFFER | rr.HYBRID_RT_REFLECTIONS)
+    pbr, got = gpu.read_hybrid(rr.HYBRID_PBR), gpu.read_hybrid(rr.HYBRID_REFLECTIONS)
+    floor_px = (hr.corner(pbr)[..., 3] == 0) & (hr.corner(gpu.read_hybrid(rr.HYBRID_POSITION))[..., 3] == 1)
+    assert floor_px.sum() > W * H // 4
+    want = hr.unorm8(np.float32(0.1) * np.array(c, np.float32))  # the white default diffuse texel is exactly 1
+    assert (got[floor_px][:, :3] == want).all() and (got[floor_px][:, 3] == 0).all()
+    assert not got[hr.corner(pbr)[..., 3] == 1].any(), "the ceiling is not metal"
+
+
+def test_material_index_is_the_truncated_filtered_alpha():
+    """a pixel on the border between materials 2 and 5 reads uint(3.5) = material 3, which is metal here; 2 and 5 are not"""
+    tiny = lambda x: Mesh(*_flat((x, -50.0, -40.0), (0.1, 0.0, 0.0), (0.0, 0.1, 0.0)), rr.LAMBERTIAN)
+    left = Mesh(*_flat((-100.0, -100.0, 0.0), (100.0, 0.0, 0.0), (0.0, 200.0, 0.0)), rr.LAMBERTIAN, name="material 2")
+    right = Mesh(*_flat((0.0, -100.0, 0.0), (100.0, 0.0, 0.0), (0.0, 200.0, 0.0)), rr.LAMBERTIAN, name="material 5")
+    metal3 = Mesh(*_flat((5.0, -50.0, -40.0), (0.1, 0.0, 0.0), (0.0, 0.1, 0.0)), rr.METAL, name="material 3")
+    cam = rr.camera.Camera((0.37, 0.0, 5.0), (0.37, 0.0, 0.0), 60.0, W / H, 0.01, 1000.0)
+    scene = Scene("border", [(Model([tiny(-5.0), tiny(-3.0), left, metal3, tiny(3.0), right], []), None)], [], cam)
+    gpu, cpu, meshes = pair(scene)
+    view = hybrid_view(scene)
+    gpu.render_hybrid(view, rr.HYBRID_GBUFFER | rr.HYBRID_RT_REFLECTIONS)
+    g = read_gbuffer(gpu)
+    filtered = hr.corner(g["pbr"])[..., 3]
+    border = filtered == 3.5
+    assert border.any() and set(np.unique(filtered)) <= {2.0, 3.5, 5.0}
+    ref, kind = hr.reflections(cpu, meshes, g["position"], g["normal"], g["pbr"], view)
+    assert np.array_equal(kind != 0, border), "exactly the border pixels trace"
+    assert gpu.hybrid_stats().reflection_pixels == border.sum()
+    assert_reflections(gpu.read_hybrid(rr.HYBRID_REFLECTIONS), ref, kind)
+
+
+# ---- 4. semantics ---------------------------------------------------------------------------------------------------------
+def test_pass_order_shadows_read_the_previous_gbuffer(assets):
+    scene = synthetic_scene()
+    gpu, cpu, meshes = pair(scene)
+    a = hybrid_view(scene)
+    a.sun_dir[:] = (0.3, 1.0, 0.2)
+    gpu.render_hybrid(a, rr.HYBRID_ALL)
+    clear = np.tile(np.array([1, 1, 1, 0], np.float32), (H, W, 1))
+    assert np.array_equal(gpu.read_hybrid(rr.HYBRID_SHADOWS), hr.shadows(cpu, clear, clear, a)), "the first call reads the clear G-buffer"
+    ga = read_gbuffer(gpu)
+    scene.camera = rr.camera.Camera((2.0, 3.0, 5.0), (0.0, 0.5, 0.0), 60.0, W / H, 0.01, 1000.0)
+    b = hybrid_view(scene)
+    b.sun_dir[:] = a.sun_dir[:]
+    gpu.render_hybrid(b, rr.HYBRID_ALL)
+    assert np.array_equal(gpu.read_hybrid(rr.HYBRID_SHADOWS), hr.shadows(cpu, ga["position"], ga["normal"], b)), "B's shadows come from A's G-buffer"
+    gb = read_gbuffer(gpu)
+    assert not np.array_equal(bits(gb["position"]), bits(ga["position"]))
+    ref, kind = hr.reflections(cpu, meshes, gb["position"], gb["normal"], gb["pbr"], b)
+    assert_reflections(gpu.read_hybrid(rr.HYBRID_REFLECTIONS), ref, kind)  # reflections: this call's G-buffer
+    s = gpu.hybrid_stats()
+    assert s.rays[0] == s.rays[1] == W * H and s.rays[2] == np.count_nonzero(kind) and all(ms > 0 for ms in s.pass_ms)
+    # bits outside UH_HYBRID_ALL are ignored, as uh_render_frame ignores unknown pass bits
+    gpu.render_hybrid(b, rr.HYBRID_ALL | (1 << 9))
+    assert np.array_equal(gpu.read_hybrid(rr.HYBRID_SHADOWS), hr.shadows(cpu, gb["position"], gb["normal"], b))
+
+
+def test_ibl_refusal_and_the_raytracing_gate():
+    scene = synthetic_scene()
+    gpu, cpu, meshes = pair(scene)
+    with pytest.raises(UtopianError):
+        gpu.read_hybrid(rr.HYBRID_SHADOWS)  # nothing rendered yet
+    v = hybrid_view(scene)
+    gpu.render_hybrid(v, rr.HYBRID_ALL)
+    before = {i: gpu.read_hybrid(i) for i in range(6)}
+    v.ibl_enabled = 1
+    with pytest.raises(UtopianError, match="IBL") as e:
+        gpu.render_hybrid(v, rr.HYBRID_ALL)
+    assert "INVALID_ARGUMENT" in str(e.value) and "not part of this library" in str(e.value)
+    for i in range(6):
+        assert np.array_equal(before[i], gpu.read_hybrid(i)), "a refused call runs nothing"
+    gpu.render_hybrid(v, rr.HYBRID_GBUFFER | rr.HYBRID_RT_SHADOWS)  # without reflections IBL does not matter
+    shadows, refl = gpu.read_hybrid(rr.HYBRID_SHADOWS), gpu.read_hybrid(rr.HYBRID_REFLECTIONS)
+    scene.camera = rr.camera.Camera((1.0, 1.0, 4.0), (0.0, 0.5, 0.0), 60.0, W / H, 0.01, 1000.0)
+    v2 = hybrid_view(scene, raytracing_supported=0)
+    gpu.render_hybrid(v2, rr.HYBRID_ALL)
+    assert np.array_equal(gpu.read_hybrid(rr.HYBRID_SHADOWS), shadows) and np.array_equal(gpu.read_hybrid(rr.HYBRID_REFLECTIONS), refl)
+    assert not np.array_equal(bits(gpu.read_hybrid(rr.HYBRID_POSITION)), bits(before[rr.HYBRID_POSITION])), "the G-buffer pass still runs"
+    assert list(gpu.hybrid_stats().rays) == [W * H, 0, 0]
+
+
+def test_moved_instances_with_rebuild_tlas_equal_a_fresh_build():
+    scene = synthetic_scene()
+    gpu, _, _ = pair(scene)
+    moved = rr.transform3x4((1.1, 0.5, 0.9), (1.0, 1.2, 0.5))
+    gpu.set_instance_transform(1, moved)
+    v = hybrid_view(scene)
+    with pytest.raises(UtopianError, match="NOT_BUILT"):
+        gpu.render_hybrid(v, rr.HYBRID_ALL)
+    v.rebuild_tlas = 1
+    gpu.render_hybrid(v, rr.HYBRID_GBUFFER)
+    gpu.render_hybrid(v, rr.HYBRID_RT_SHADOWS | rr.HYBRID_RT_REFLECTIONS)
+    fresh = rr.Renderer(W, H)
+    scene.upload(fresh)
+    fresh.set_instance_transform(1, moved)
+    fresh.initialize_raytracing()
+    v.rebuild_tlas = 0
+    fresh.render_hybrid(v, rr.HYBRID_GBUFFER)
+    fresh.render_hybrid(v, rr.HYBRID_RT_SHADOWS | rr.HYBRID_RT_REFLECTIONS)
+    for i in range(6):
+        assert np.array_equal(gpu.read_hybrid(i), fresh.read_hybrid(i)), i
+
+
+# ---- 5. isolation ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("in_flight", [4, 1])
+def test_hybrid_calls_change_nothing_the_path_tracer_reads_or_reports(assets, in_flight):
+    scene = reference_spheres_scene(assets)
+    scene.view_flags = dict(scene.view_flags, use_ris_light_sampling=1)
+
+    def run(with_hybrid):
+        r = scene.upload(rr.Renderer(W, H))
+        r.set_option("frames_in_flight", in_flight)
+        loop = rr.FrameLoop(r, scene.make_view(W, H))
+        hv = hybrid_view(scene)
+        hv.sun_dir[:] = (0.2, 1.0, -0.4)
+        for i in range(5):
+            loop.frame(rr.PASS_ALL)
+            if with_hybrid:
+                r.render_hybrid(hv, rr.HYBRID_ALL if i % 2 else rr.HYBRID_GBUFFER)
+        loop.frames(3, rr.PASS_ALL)
+        if with_hybrid:
+            r.render_hybrid(hv, rr.HYBRID_ALL)
+        s = r.get_stats()
+        out = dict(acc=bits(r.read_accumulation()), out=r.read_output_bgra8(), pos=bits(r.read_gbuffer_position()),
+                   stats=(list(s.rays), s.frames, s.camera_grid_cells, s.sun_grid_cells, s.closest_hits, s.misses))
+        for k in range(3):
+            out[f"res{k}"] = r.read_reservoirs(k).view(np.uint8)
+        return out
+
+    a, b = run(False), run(True)
+    assert a.pop("stats") == b.pop("stats")
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
