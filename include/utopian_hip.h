@@ -524,7 +524,7 @@ int uh_mgpu_set_option(uh_mgpu* group, const char* name, int value);
  * GATES: view->raytracing_supported == 0 skips both ray-traced passes and leaves their images as they are (mod.rs:107,134);
  * UH_HYBRID_RT_REFLECTIONS with view->ibl_enabled == 1 is UH_ERR_INVALID_ARGUMENT - the IBL maps (irradiance, specular, BRDF LUT of
  * ibl.rs) are not part of this library - and nothing runs; mask bits, UH_ERR_NOT_BUILT and moved instances with view->rebuild_tlas
- * as for uh_render_frame (bits outside UH_HYBRID_ALL are ignored).
+ * as for uh_render_frame (bits outside UH_HYBRID_FRAME, below, are ignored).
  * STREAM ORDER: uh_render_hybrid enqueues like a frame (behind the frames in flight, ahead of those that follow); uh_read_hybrid and
  * uh_get_hybrid_stats wait for all work of the context and are complete on return.
  * Arithmetic: DESIGN.md section 2, "Hybrid passes". */
@@ -551,6 +551,51 @@ UH_LAYOUT_ASSERT(sizeof(UhHybridStats) == 48 && offsetof(UhHybridStats, pass_ms)
 int uh_render_hybrid(uh_ctx* ctx, const UhViewUniformData* view, uint32_t hybrid_mask);
 int uh_read_hybrid(uh_ctx* ctx, int which, void* out); /* UH_ERR_INVALID_ARGUMENT before the first uh_render_hybrid */
 int uh_get_hybrid_stats(uh_ctx* ctx, UhHybridStats* out);
+
+/* ---- the hybrid graph's final frame: ssao_pass, deferred_pass, atmosphere_pass, present_pass (mod.rs:136-186) -------------
+ * Four more bits of uh_render_hybrid, run after the three above in the reference's order:
+ *   UH_HYBRID_SSAO      ssao.frag (radius 0.1, the 32 fixed kernel samples, randomVec (1, 1, 0), strength 1.6, no blur: ssao.rs) into
+ *                       the R16 UNORM ssao_output; it does not run with view->ssao_enabled != 1 (ssao.rs:27)
+ *   UH_HYBRID_DEFERRED  deferred.frag + pbr_lighting.glsl / brdf.glsl into the RGBA32F deferred_output: the sun as a directional light
+ *                       of colour 1, then view->num_lights lights of the uh_add_light table (all 96 bytes of each: point, spot and
+ *                       directional), ambient 0.03 * diffuse * occlusion, rt_reflections on metal pixels and rt_shadows (max(s, 0.3))
+ *                       when view->raytracing_supported == 1, ssao_output when view->ssao_enabled == 1
+ *   UH_HYBRID_SKY       atmosphere.frag, cubemap_enabled = 0 branch: IntegrateScattering along the un-jittered primary ray of every pixel
+ *                       the G-buffer cast missed (a deviation: the reference draws the first mesh scaled by 1000 with a depth test)
+ *   UH_HYBRID_PRESENT   present.frag + fxaa.glsl (threshold 0.45: present.rs; FXAA when view->fxaa_enabled == 1) + linearToSrgb into an
+ *                       8-bit image of the layout and channel order of uh_read_output_bgra8 (B, G, R, A = 255), row 0 at the top
+ * UH_HYBRID_FRAME runs all seven: rt_shadows (previous G-buffer), G-buffer, rt_reflections, SSAO, deferred, sky, present.
+ * THE REFERENCE'S DEFAULTS (prototype/src/main.rs) SET shadows_enabled, ibl_enabled AND cubemap_enabled TO 1: a caller of these passes
+ * must clear them. UH_ERR_INVALID_ARGUMENT with a message, and nothing runs, for UH_HYBRID_DEFERRED with view->shadows_enabled == 1
+ * (the cascaded shadow maps are raster passes outside this library) or view->ibl_enabled == 1 (the IBL maps of ibl.rs), for
+ * UH_HYBRID_SKY with view->cubemap_enabled == 1 (the environment cube of ibl.rs), and for UH_HYBRID_DEFERRED with view->num_lights
+ * above the lights added with uh_add_light. view->marching_cubes_enabled is not read: meshes of uh_add_isosurface_mesh are scene
+ * geometry and go through the G-buffer like any other.
+ * ORIENTATION (the reference draws under a Y-flipped viewport, pass.rs:260-267): deferred pixel (x, y) and present pixel (x, y) read the
+ * G-buffer and deferred texel (x, y); ssao_output texel (x, y) is the occlusion of G-buffer texel (x, H-1-y) (ssao.frag samples at the
+ * unflipped in_uv), and deferred pixel (x, y) reads ssao_output texel (x, H-1-y), so it is lit by its own texel's occlusion.
+ * RESOURCES: the three images (22 bytes per pixel) are allocated by the first call whose mask holds one of these four bits, cleared to
+ * (1, 1, 1, 0) (ssao 65535, present (255, 255, 255, 0)), and freed by uh_destroy; the light table goes with them. The passes change
+ * nothing the path tracer or the three passes above read or report. Arithmetic: DESIGN.md section 2, "Hybrid frame passes". */
+enum { UH_HYBRID_SSAO = 1u << 3, UH_HYBRID_DEFERRED = 1u << 4, UH_HYBRID_SKY = 1u << 5, UH_HYBRID_PRESENT = 1u << 6, UH_HYBRID_FRAME = 0x7f };
+/* more images of uh_read_hybrid (W*H texels each) */
+enum {
+   UH_HYBRID_SSAO_IMAGE = 6,        /* uint16 (R16 UNORM) */
+   UH_HYBRID_DEFERRED_OUTPUT = 7,   /* RGBA32F */
+   UH_HYBRID_PRESENT_OUTPUT = 8     /* 8 bits x 4 channels, B G R A */
+};
+/* the last uh_render_hybrid call: pass_ms[k] the hipEvent time of the pass of bit k (rt_shadows, G-buffer, rt_reflections, SSAO, deferred,
+ * sky, present; 0 for a pass that did not run); sky_pixels the pixels the sky pass wrote; lights the lights the deferred pass evaluated
+ * per pixel (the sun included; 0 when it did not run) */
+typedef struct UhHybridFrameStats {
+   float pass_ms[7];
+   uint32_t sky_pixels;
+   uint32_t lights;
+   uint32_t reserved[3];
+} UhHybridFrameStats;
+UH_LAYOUT_ASSERT(sizeof(UhHybridFrameStats) == 48 && offsetof(UhHybridFrameStats, sky_pixels) == 28 && offsetof(UhHybridFrameStats, lights) == 32,
+                 "UhHybridFrameStats (48 B)");
+int uh_get_hybrid_frame_stats(uh_ctx* ctx, UhHybridFrameStats* out); /* waits; all zero before the first uh_render_hybrid */
 
 #ifdef __cplusplus
 }

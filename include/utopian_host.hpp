@@ -299,11 +299,16 @@ class Renderer {
       return s;
    }
    // the hybrid graph's ray-traced passes (build_render_graph, renderers/mod.rs:61-186): rt_shadows on the previous G-buffer, the
-   // G-buffer pass, rt_reflections on the new one - for the bits of `mask` (utopian_hip.h "uh_render_hybrid")
+   // G-buffer pass, rt_reflections on the new one, then SSAO, deferred, sky and present - for the bits of `mask` (utopian_hip.h
+   // "uh_render_hybrid")
    void render_hybrid(const UhViewUniformData& view, uint32_t mask = UH_HYBRID_ALL) { check(uh_render_hybrid(ctx_, &view, mask), "render_hybrid"); }
-   // one image as bytes: W*H texels of 16 (position, normal, pbr), 4 (albedo, reflections) or 1 (shadows) bytes
+   // one image as bytes: W*H texels of 16 (position, normal, pbr, deferred output), 4 (albedo, reflections, present output), 2 (SSAO)
+   // or 1 (shadows) bytes
    std::vector<uint8_t> read_hybrid(int which) {
-      const size_t texel = (which == UH_HYBRID_SHADOWS) ? 1 : (which == UH_HYBRID_ALBEDO || which == UH_HYBRID_REFLECTIONS) ? 4 : 16;
+      const size_t texel = (which == UH_HYBRID_SHADOWS)      ? 1
+                           : (which == UH_HYBRID_SSAO_IMAGE) ? 2
+                           : (which == UH_HYBRID_ALBEDO || which == UH_HYBRID_REFLECTIONS || which == UH_HYBRID_PRESENT_OUTPUT) ? 4
+                                                                                                                               : 16;
       std::vector<uint8_t> out((size_t)width_ * height_ * texel);
       check(uh_read_hybrid(ctx_, which, out.data()), "read_hybrid");
       return out;
@@ -311,6 +316,12 @@ class Renderer {
    UhHybridStats hybrid_stats() {
       UhHybridStats s;
       check(uh_get_hybrid_stats(ctx_, &s), "hybrid_stats");
+      return s;
+   }
+   // pass_ms of all seven passes of the last render_hybrid (bit order), with UH_HYBRID_FRAME = 0x7f the whole final frame
+   UhHybridFrameStats hybrid_frame_stats() {
+      UhHybridFrameStats s;
+      check(uh_get_hybrid_frame_stats(ctx_, &s), "hybrid_frame_stats");
       return s;
    }
    // uh_set_option: "device_build", "frames_in_flight", ... (DESIGN.md "Options")

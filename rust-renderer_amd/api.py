@@ -23,13 +23,17 @@ from .types import (
     VERTEX_DTYPE,
     HYBRID_ALBEDO,
     HYBRID_ALL,
+    HYBRID_DEFERRED_OUTPUT,
     HYBRID_NORMAL,
     HYBRID_POSITION,
     HYBRID_PBR,
+    HYBRID_PRESENT_OUTPUT,
     HYBRID_REFLECTIONS,
     HYBRID_SHADOWS,
+    HYBRID_SSAO_IMAGE,
     GpuLight,
     GpuMaterial,
+    HybridFrameStats,
     HybridStats,
     Reservoir,
     RestirRows,
@@ -79,8 +83,9 @@ class CApi:
             "render_hybrid": [vp, p(ViewUniformData), u32],
             "read_hybrid": [vp, C.c_int, vp],
             "get_hybrid_stats": [vp, p(HybridStats)],
+            "get_hybrid_frame_stats": [vp, p(HybridFrameStats)],
         }
-        hybrid = ("render_hybrid", "read_hybrid", "get_hybrid_stats")
+        hybrid = ("render_hybrid", "read_hybrid", "get_hybrid_stats", "get_hybrid_frame_stats")
         for name, argtypes in sig.items():
             if not hasattr(lib, prefix + name) and (name == "render_frames" or name in hybrid or prefix == "uh_mgpu_"):
                 continue  # the oracle renders frame by frame and has no hybrid passes; the GPU group has no per-context queries
@@ -416,11 +421,12 @@ class Renderer:
     # -- the hybrid graph's ray-traced passes (uh_render_hybrid; include/utopian_hip.h) ----
     def _hybrid_api(self):
         if self.backend != "hip" or not hasattr(self._api, "render_hybrid"):
-            raise NotImplementedError(f"the hybrid passes (rt_shadows / rt_reflections) are per-context verbs of the HIP library; backend {self.backend!r} has none")
+            raise NotImplementedError(f"the hybrid passes (rt_shadows / rt_reflections / the final frame) are per-context verbs of the HIP library; backend {self.backend!r} has none")
         return self._api
 
     def render_hybrid(self, view, mask=HYBRID_ALL):
-        """rt_shadows (previous G-buffer), gbuffer, rt_reflections (this one) - the reference's pass order - for the bits of `mask`"""
+        """rt_shadows (previous G-buffer), gbuffer, rt_reflections (this one), ssao, deferred, sky, present - the reference's pass order -
+        for the bits of `mask` (HYBRID_FRAME: all seven)"""
         api = self._hybrid_api()
         self._check(api.render_hybrid(self._ctx, C.byref(view), int(mask)))
 
@@ -431,13 +437,17 @@ class Renderer:
         HYBRID_PBR: (np.float32, 4),
         HYBRID_SHADOWS: (np.uint8, 1),
         HYBRID_REFLECTIONS: (np.uint8, 4),
+        HYBRID_SSAO_IMAGE: (np.uint16, 1),
+        HYBRID_DEFERRED_OUTPUT: (np.float32, 4),
+        HYBRID_PRESENT_OUTPUT: (np.uint8, 4),
     }
 
     def read_hybrid(self, which):
-        """one image of the hybrid graph: (H, W, 4) float32 position / normal / pbr, (H, W, 4) uint8 albedo / reflections, (H, W) uint8 shadows"""
+        """one image of the hybrid graph: (H, W, 4) float32 position / normal / pbr / deferred output, (H, W, 4) uint8 albedo / reflections /
+        present output (B, G, R, A), (H, W) uint8 shadows, (H, W) uint16 SSAO"""
         api = self._hybrid_api()
         if which not in self._HYBRID_IMAGES:
-            raise ValueError(f"hybrid image index {which} (0..5)")
+            raise ValueError(f"hybrid image index {which} (0..8)")
         dtype, ch = self._HYBRID_IMAGES[which]
         out = np.empty((self.height, self.width, ch) if ch > 1 else (self.height, self.width), dtype=dtype)
         self._check(api.read_hybrid(self._ctx, int(which), out.ctypes.data))
@@ -447,6 +457,13 @@ class Renderer:
         api = self._hybrid_api()
         s = HybridStats()
         self._check(api.get_hybrid_stats(self._ctx, C.byref(s)))
+        return s
+
+    def hybrid_frame_stats(self):
+        """UhHybridFrameStats of the last render_hybrid call: pass_ms of all seven passes in bit order"""
+        api = self._hybrid_api()
+        s = HybridFrameStats()
+        self._check(api.get_hybrid_frame_stats(self._ctx, C.byref(s)))
         return s
 
     # -- stand-alone ray queries ----------------------------------------------------------

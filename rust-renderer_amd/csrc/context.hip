@@ -324,8 +324,18 @@ struct uh_ctx {
       DevBuf<uint32_t> indices;
       uint64_t geom = 0;                       // geom_version the mesh tables were made for
       hipEvent_t waits[2 * kMaxSlots + 1] = {};  // behind the frames in flight
-      hipEvent_t ev[4] = {};                   // pass boundaries of the last call (timing)
+      hipEvent_t ev[8] = {};                   // pass boundaries of the last call, in pass order (timing)
       bool ran[3] = {false, false, false};     // G-buffer, rt_shadows, rt_reflections in the last call
+      // the final frame's passes (SSAO, deferred, sky, present), allocated by the first call that asks for one of them
+      DevBuf<uint16_t> ssao;
+      DevBuf<float4> deferred;
+      DevBuf<uchar4> present;
+      DevBuf<uint32_t> sky_counter;
+      DevBuf<UhGpuLight> raw_lights;           // the uh_add_light table as added
+      DevBuf<HybridLight> lights;              // its records as the deferred pass reads them, the sun first
+      size_t lights_uploaded = SIZE_MAX;       // c->lights.size() when raw_lights was uploaded
+      bool frame_ran[4] = {false, false, false, false};  // SSAO, deferred, sky, present in the last call
+      uint32_t frame_lights = 0;               // lights the deferred pass of the last call evaluated (the sun included)
    } hy;
 };
 
@@ -589,6 +599,12 @@ void uh_destroy(uh_ctx* c) {
       h.meshes.release();
       h.vertices.release();
       h.indices.release();
+      h.ssao.release();
+      h.deferred.release();
+      h.present.release();
+      h.sky_counter.release();
+      h.raw_lights.release();
+      h.lights.release();
       for (hipEvent_t ev : h.waits)
          if (ev) (void)hipEventDestroy(ev);
       for (hipEvent_t ev : h.ev)
@@ -2599,6 +2615,32 @@ static int hybrid_tables(uh_ctx* c) {
    return UH_OK;
 }
 
+// the final frame's images and light table (first call with one of its bits); the metal-pixel queue of rt_reflections is reused
+// for the sky pixels, which are queued after rt_reflections has run
+static int hybrid_frame_alloc(uh_ctx* c) {
+   uh_ctx::Hybrid& h = c->hy;
+   if (h.sky_counter.p) return UH_OK;
+   const size_t n = (size_t)c->W * c->H;
+   HIP_TRY(c, h.ssao.alloc(n));
+   HIP_TRY(c, h.deferred.alloc(n));
+   HIP_TRY(c, h.present.alloc(n));
+   HIP_TRY(c, h.lights.alloc(UH_MAX_GPU_LIGHTS + 1));
+   HIP_TRY(c, h.sky_counter.alloc(1));  // last: its pointer says "allocated"
+   return UH_OK;
+}
+
+// the uh_add_light table as the deferred pass reads it (lights are only ever appended: the count says whether it changed)
+static int hybrid_light_table(uh_ctx* c) {
+   uh_ctx::Hybrid& h = c->hy;
+   if (h.lights_uploaded == c->lights.size()) return UH_OK;
+   HIP_TRY(c, h.raw_lights.alloc(c->lights.size()));
+   if (!c->lights.empty())
+      HIP_TRY(c, hipMemcpyAsync(h.raw_lights.p, c->lights.data(), c->lights.size() * sizeof(UhGpuLight), hipMemcpyHostToDevice, c->stream));
+   HIP_TRY(c, hipStreamSynchronize(c->stream));
+   h.lights_uploaded = c->lights.size();
+   return UH_OK;
+}
+
 int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    if (!view) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_render_hybrid: null view");
@@ -2606,6 +2648,22 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
       return fail(c, UH_ERR_INVALID_ARGUMENT,
                   "uh_render_hybrid: rt_reflections with view.ibl_enabled = 1 needs the IBL maps (irradiance, specular, BRDF LUT of ibl.rs), "
                   "which are not part of this library; set ibl_enabled = 0 for the reflection pass's non-IBL branch");
+   if (mask & UH_HYBRID_DEFERRED) {
+      if (view->shadows_enabled == 1)
+         return fail(c, UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: the deferred pass with view.shadows_enabled = 1 needs the cascaded shadow maps (shadow.rs), raster passes "
+                     "that are not part of this library; set shadows_enabled = 0 for the rt_shadows branch");
+      if (view->ibl_enabled == 1)
+         return fail(c, UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: the deferred pass with view.ibl_enabled = 1 needs the IBL maps (irradiance, specular, BRDF LUT of ibl.rs), "
+                     "which are not part of this library; set ibl_enabled = 0 for the ambient term 0.03 * diffuse * occlusion");
+      if (view->num_lights > c->lights.size())
+         return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_render_hybrid: view.num_lights exceeds the lights added with uh_add_light");
+   }
+   if ((mask & UH_HYBRID_SKY) && view->cubemap_enabled == 1)
+      return fail(c, UH_ERR_INVALID_ARGUMENT,
+                  "uh_render_hybrid: the sky pass with view.cubemap_enabled = 1 needs the environment cube (ibl.rs), which is not part of "
+                  "this library; set cubemap_enabled = 0 for the IntegrateScattering branch");
    if (!c->built && c->topology_valid && view->rebuild_tlas == 1)
       if (int st = uh_refit_acceleration(c)) return st;
    if (!c->built) return fail(c, UH_ERR_NOT_BUILT, "uh_render_hybrid before uh_build_acceleration");
@@ -2614,6 +2672,13 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    const bool first = !h.counter.p;
    if (int st = hybrid_alloc(c)) return st;
    if (int st = hybrid_tables(c)) return st;
+   const uint32_t frame_bits = UH_HYBRID_SSAO | UH_HYBRID_DEFERRED | UH_HYBRID_SKY | UH_HYBRID_PRESENT;
+   const bool frame_first = (mask & frame_bits) && !h.sky_counter.p;
+   if (mask & frame_bits) {
+      if (int st = hybrid_frame_alloc(c)) return st;
+      if (mask & UH_HYBRID_DEFERRED)
+         if (int st = hybrid_light_table(c)) return st;
+   }
    const FrameParams fp = make_params(c, *view);
    HybridDev hd{};
    hd.pos = h.pos.p;
@@ -2655,6 +2720,22 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    LaunchCfg lc = cfg(c);
    lc.count_visits = false;  // nothing of this call goes to UhStats
    if (first) launch_hybrid_clear(lc, hd);
+   HybridFrameDev fd{};
+   fd.ssao = h.ssao.p;
+   fd.deferred = h.deferred.p;
+   fd.present = h.present.p;
+   fd.sky_counter = h.sky_counter.p;
+   fd.lights = h.lights.p;
+   fd.raw_lights = h.raw_lights.p;
+   std::memcpy(fd.view, view->view, sizeof(fd.view));
+   std::memcpy(fd.proj, view->projection, sizeof(fd.proj));
+   std::memcpy(fd.inv_view, view->inverse_view, sizeof(fd.inv_view));
+   fd.num_lights = view->num_lights;
+   fd.ssao_on = view->ssao_enabled == 1;
+   fd.rt_on = view->raytracing_supported == 1;
+   fd.fxaa_on = view->fxaa_enabled == 1;
+   for (int a = 0; a < 3; a++) fd.sun_raw[a] = view->sun_dir[a];
+   if (frame_first) launch_hybrid_frame_clear(lc, hd, fd);
    // the camera grid when the path tracer's is built for this camera and geometry (read only: the grid's state is the path tracer's)
    float mats[32];
    std::memcpy(mats, fp.inv_view, sizeof(float) * 16);
@@ -2675,6 +2756,23 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
       launch_hybrid_reflections(lc, c->scene, hd);
    }
    HIP_TRY(c, hipEventRecord(h.ev[3], c->stream));
+   // the final frame (mod.rs:136-186): ssao_pass (not with ssao_enabled != 1, ssao.rs:27), deferred_pass, atmosphere_pass, present_pass
+   h.frame_ran[0] = (mask & UH_HYBRID_SSAO) && view->ssao_enabled == 1;
+   h.frame_ran[1] = (mask & UH_HYBRID_DEFERRED) != 0;
+   h.frame_ran[2] = (mask & UH_HYBRID_SKY) != 0;
+   h.frame_ran[3] = (mask & UH_HYBRID_PRESENT) != 0;
+   h.frame_lights = h.frame_ran[1] ? view->num_lights + 1 : 0;
+   if (h.frame_ran[0]) launch_hybrid_ssao(lc, hd, fd);
+   HIP_TRY(c, hipEventRecord(h.ev[4], c->stream));
+   if (h.frame_ran[1]) launch_hybrid_deferred(lc, c->scene, hd, fd);
+   HIP_TRY(c, hipEventRecord(h.ev[5], c->stream));
+   if (h.frame_ran[2]) {
+      HIP_TRY(c, hipMemsetAsync(h.sky_counter.p, 0, sizeof(uint32_t), c->stream));
+      launch_hybrid_sky(lc, fp, hd, fd);
+   }
+   HIP_TRY(c, hipEventRecord(h.ev[6], c->stream));
+   if (h.frame_ran[3]) launch_hybrid_present(lc, hd, fd);
+   HIP_TRY(c, hipEventRecord(h.ev[7], c->stream));
    HIP_TRY(c, hipGetLastError());
    return UH_OK;
 }
@@ -2691,8 +2789,34 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
    case UH_HYBRID_PBR: return read_back(c, out, h.pbr.p, n * sizeof(float4));
    case UH_HYBRID_SHADOWS: return read_back(c, out, h.shadow.p, n);
    case UH_HYBRID_REFLECTIONS: return read_back(c, out, h.refl.p, n * sizeof(uchar4));
-   default: return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..5");
+   case UH_HYBRID_SSAO_IMAGE:
+   case UH_HYBRID_DEFERRED_OUTPUT:
+   case UH_HYBRID_PRESENT_OUTPUT:
+      if (!h.sky_counter.p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 6..8 before the first call with an SSAO, deferred, sky or present bit");
+      if (which == UH_HYBRID_SSAO_IMAGE) return read_back(c, out, h.ssao.p, n * sizeof(uint16_t));
+      if (which == UH_HYBRID_DEFERRED_OUTPUT) return read_back(c, out, h.deferred.p, n * sizeof(float4));
+      return read_back(c, out, h.present.p, n * sizeof(uchar4));
+   default: return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..8");
    }
+}
+
+int uh_get_hybrid_frame_stats(uh_ctx* c, UhHybridFrameStats* out) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_hybrid_frame_stats: null destination");
+   std::memset(out, 0, sizeof(*out));
+   const uh_ctx::Hybrid& h = c->hy;
+   if (!h.counter.p) return UH_OK;
+   HIP_TRY(c, hipSetDevice(c->device));
+   if (int st = sync_all(c)) return st;
+   const bool ran[7] = {h.ran[1], h.ran[0], h.ran[2], h.frame_ran[0], h.frame_ran[1], h.frame_ran[2], h.frame_ran[3]};
+   for (int k = 0; k < 7; k++) {
+      float ms = 0.0f;
+      if (ran[k]) HIP_TRY(c, hipEventElapsedTime(&ms, h.ev[k], h.ev[k + 1]));  // pass k between events k and k + 1
+      out->pass_ms[k] = ms;
+   }
+   if (h.frame_ran[2]) HIP_TRY(c, hipMemcpy(&out->sky_pixels, h.sky_counter.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+   out->lights = h.frame_lights;
+   return UH_OK;
 }
 
 int uh_get_hybrid_stats(uh_ctx* c, UhHybridStats* out) {

@@ -218,6 +218,29 @@ struct HybridDev {
    float eye[3];      // view.eye_pos
    uint32_t W, H, furnace;
 };
+// the final frame's passes (ssao_pass, deferred_pass, atmosphere_pass, present_pass): their images and what they read of the view
+struct HybridLight {  // one light as the deferred pass's loop reads it (k_hybrid_light_prep): 64 B, the light-only terms made once
+   float pos[3];      // light.pos
+   float mode;        // 0 directional, 1 point, 2 spot, 3 any other type (L = 0, attenuation 1)
+   float color[3];    // light.color.rgb
+   float spot;        // light.spot
+   float att[3];      // light.att
+   float pad0;
+   float dir[3];      // directional: normalize(light.dir * (-1, 1, -1)) = L; spot: normalize(light.dir)
+   float pad1;
+};
+struct HybridFrameDev {
+   uint16_t* ssao;            // ssao_output R16 UNORM
+   float4* deferred;          // deferred_output RGBA32F
+   uchar4* present;           // present output B8G8R8A8
+   uint32_t* sky_counter;     // [0]: sky pixels queued in HybridDev::queue
+   HybridLight* lights;       // [0] the sun, [1 .. num_lights] the uh_add_light table in order
+   const UhGpuLight* raw_lights;
+   float view[16], proj[16], inv_view[16];  // column-major, as UhViewUniformData
+   uint32_t num_lights;       // view.num_lights (the sun not counted)
+   uint32_t ssao_on, rt_on, fxaa_on;  // view.ssao_enabled == 1, view.raytracing_supported == 1, view.fxaa_enabled == 1
+   float sun_raw[3];          // view.sun_dir as given (the sun light's dir = sun_raw * (-1, 1, -1))
+};
 
 // launch wrappers implemented in kernels.hip --------------------------------------------------
 struct LaunchCfg {
@@ -264,6 +287,11 @@ void launch_hybrid_clear(const LaunchCfg&, const HybridDev&);
 void launch_hybrid_gbuffer(const LaunchCfg&, const FrameParams&, const SceneDev&, const HybridDev&, const SunGridDev* camera_grid);
 void launch_hybrid_shadows(const LaunchCfg&, const SceneDev&, const HybridDev&);
 void launch_hybrid_reflections(const LaunchCfg&, const SceneDev&, const HybridDev&);
+void launch_hybrid_frame_clear(const LaunchCfg&, const HybridDev&, const HybridFrameDev&);
+void launch_hybrid_ssao(const LaunchCfg&, const HybridDev&, const HybridFrameDev&);
+void launch_hybrid_deferred(const LaunchCfg&, const SceneDev&, const HybridDev&, const HybridFrameDev&);
+void launch_hybrid_sky(const LaunchCfg&, const FrameParams&, const HybridDev&, const HybridFrameDev&);
+void launch_hybrid_present(const LaunchCfg&, const HybridDev&, const HybridFrameDev&);
 // tiles
 // on-device refit (refit.hip): per-mesh object->world rows, and what one refit pass touches
 struct RefitMesh {

@@ -2721,4 +2721,346 @@ void launch_hybrid_reflections(const LaunchCfg& c, const SceneDev& sc, const Hyb
    k_hybrid_reflect<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(sc, hd);
 }
 
+// ------------------------------------------------------------------------------------------
+// The hybrid graph's final frame (build_render_graph, renderers/mod.rs:136-186): ssao_pass (ssao.frag), deferred_pass
+// (deferred.frag + pbr_lighting.glsl / brdf.glsl), atmosphere_pass (atmosphere.frag, cubemap off) and present_pass (present.frag +
+// fxaa.glsl). Arithmetic and orientation: DESIGN.md section 2 "Hybrid frame passes".
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_hybrid_frame_clear(HybridFrameDev fd, uint32_t n) {
+   for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+      fd.ssao[i] = 65535;
+      fd.deferred[i] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+      fd.present[i] = make_uchar4(255, 255, 255, 0);
+   }
+}
+
+// texture(image, uv) of an RGBA32F image through LINEAR + MIRRORED_REPEAT at texel coordinates (x, y) = uv * size - 0.5 (texture.rs's
+// sampler, level 0): sample_texture's filter - weights x - floor(x), (t00 (1 - ax) + t10 ax) (1 - ay) + (t01 (1 - ax) + t11 ax) ay.
+// Coordinates beyond 1e9 texels read 0, as there.
+__device__ __forceinline__ V3 bilinear_rgb(const float4* __restrict__ img, uint32_t W, uint32_t H, float x, float y) {
+   if (!(fabsf(x) < 1e9f) || !(fabsf(y) < 1e9f)) return v3(0.0f, 0.0f, 0.0f);
+   const float fx = floorf(x), fy = floorf(y);
+   const float ax = x - fx, ay = y - fy;
+   const int x0 = mirror_index((int)fx, (int)W), x1 = mirror_index((int)fx + 1, (int)W);
+   const int y0 = mirror_index((int)fy, (int)H), y1 = mirror_index((int)fy + 1, (int)H);
+   const V3 t00 = xyz(img[(size_t)y0 * W + x0]), t10 = xyz(img[(size_t)y0 * W + x1]);
+   const V3 t01 = xyz(img[(size_t)y1 * W + x0]), t11 = xyz(img[(size_t)y1 * W + x1]);
+   const V3 a = t00 * (1.0f - ax) + t10 * ax;
+   const V3 b = t01 * (1.0f - ax) + t11 * ax;
+   return a * (1.0f - ay) + b * ay;
+}
+__device__ __forceinline__ uint32_t unorm16(float x) {
+   if (!(x > 0.0f)) x = 0.0f;
+   if (x > 1.0f) x = 1.0f;
+   return (uint32_t)rintf(x * 65535.0f);
+}
+
+// ssao.frag:31-64, the fixed kernel (kernelSamples[i].xyz)
+__device__ __forceinline__ V3 ssao_sample(int i) {
+   constexpr float k[32][3] = {
+      {-0.68217f, 0.23565f, 0.48243f}, {-0.14448f, 0.01628f, 0.22807f}, {0.00604f, 0.01909f, 0.0127f},   {0.09733f, 0.39072f, 0.7324f},
+      {0.06055f, 0.87847f, 0.33303f},  {0.00734f, 0.19034f, 0.13091f},  {-0.01377f, 0.01745f, 0.00399f}, {0.01468f, 0.16627f, 0.09108f},
+      {-0.10093f, -0.08015f, 0.06625f}, {-0.27125f, -0.39937f, 0.0601f}, {-0.06181f, -0.03065f, 0.01213f}, {-0.40189f, -0.48095f, 0.21808f},
+      {0.04027f, -0.05818f, 0.26542f}, {-0.33535f, -0.07516f, 0.24997f}, {0.32748f, -0.18112f, 0.27292f}, {0.53962f, -0.03361f, 0.58926f},
+      {-0.09598f, -0.25424f, 0.35754f}, {-0.17368f, 0.01261f, 0.23964f}, {0.1283f, 0.12573f, 0.16467f},  {-0.34418f, 0.19403f, 0.70285f},
+      {-0.09686f, -0.0928f, 0.11447f}, {0.32727f, -0.49713f, 0.17518f}, {0.12345f, 0.13862f, 0.23822f},  {-0.39258f, -0.31128f, 0.67374f},
+      {0.03308f, 0.07616f, 0.03422f},  {-0.31777f, 0.1885f, 0.40808f},  {-0.17464f, 0.28096f, 0.11686f}, {-0.50199f, -0.49002f, 0.2709f},
+      {0.38629f, 0.15627f, 0.56716f},  {0.06649f, -0.05762f, 0.0857f},  {-0.1065f, -0.11726f, 0.10818f}, {0.53236f, -0.5286f, 0.45444f}};
+   return v3(k[i][0], k[i][1], k[i][2]);
+}
+
+// ssao.frag:66-118 (radius 0.1, randomVec (1, 1, 0), strength 1.6: ssao.rs:11). Texel (x, y) of ssao_output samples the G-buffer at the
+// UNFLIPPED in_uv, i.e. at texel (x, H-1-y), exactly; the projected samples go through FLIP_UV_Y and read bilinearly.
+__global__ __launch_bounds__(kBlock) void k_hybrid_ssao(HybridDev hd, HybridFrameDev fd) {
+   const uint32_t n = hd.W * hd.H, i = blockIdx.x * kBlock + threadIdx.x;
+   if (i >= n) return;
+   const uint32_t x = i % hd.W, y = i / hd.W;
+   const size_t src = (size_t)(hd.H - 1 - y) * hd.W + x;
+   const float4 p4 = hd.pos[src];
+   float occ = 1.0f;                                                                             // frag:76-79: the sky
+   if (!(p4.x == 1.0f && p4.y == 1.0f && p4.z == 1.0f)) {
+      const float4 f4 = mat4_mul(fd.view, p4.x, p4.y, p4.z, 1.0f);                               // frag:73
+      const V3 frag = v3(f4.x, f4.y, f4.z);
+      const float4 n4 = hd.nrm[src];
+      const float* m = fd.inv_view;  // transpose(inverse(view)) * vec4(n, 0): row i of the transpose = column i of inverse_view
+      const V3 nv = normalize3(v3(((m[0] * n4.x + m[1] * n4.y) + m[2] * n4.z) + m[3] * 0.0f, ((m[4] * n4.x + m[5] * n4.y) + m[6] * n4.z) + m[7] * 0.0f,
+                                  ((m[8] * n4.x + m[9] * n4.y) + m[10] * n4.z) + m[11] * 0.0f));  // frag:81-83
+      const V3 rnd = v3(1.0f, 1.0f, 0.0f);
+      const V3 tangent = normalize3(rnd - nv * dot3(rnd, nv));                                  // frag:90
+      const V3 bitangent = cross3(tangent, nv);                                                 // frag:91
+      float o = 0.0f;
+#pragma unroll 4
+      for (int k = 0; k < 32; k++) {
+         const V3 kk = ssao_sample(k);
+         const V3 sp = frag + ((tangent * kk.x + bitangent * kk.y) + nv * kk.z) * 0.1f;         // frag:98-99
+         const float4 c = mat4_mul(fd.proj, sp.x, sp.y, sp.z, 1.0f);                            // frag:102-103
+         const float u = (c.x / c.w) * 0.5f + 0.5f, v = 1.0f - ((c.y / c.w) * 0.5f + 0.5f);   // frag:104-106
+         const V3 q = bilinear_rgb(hd.pos, hd.W, hd.H, u * (float)hd.W - 0.5f, v * (float)hd.H - 0.5f);
+         const float depth = mat4_mul(fd.view, q.x, q.y, q.z, 1.0f).z;                          // frag:108
+         float t = 0.1f / fabsf(frag.z - depth);                                                // frag:110: smoothstep(0, 1, .)
+         t = fminf(fmaxf(t, 0.0f), 1.0f);
+         const float range = (t * t) * (3.0f - 2.0f * t);
+         o = o + (depth >= sp.z ? 1.0f : 0.0f) * range;                                         // frag:111
+      }
+      occ = 1.0f - (o / 32.0f) * 1.6f;                                                          // frag:114-115
+   }
+   fd.ssao[i] = (uint16_t)unorm16(occ);
+}
+
+// the light-only terms of surfaceShading (pbr_lighting.glsl:36-53), once per light: record 0 is deferred.frag:74's sun, record k the
+// light k - 1 of the uh_add_light table
+__global__ void k_hybrid_light_prep(HybridFrameDev fd) {
+   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= fd.num_lights; i += gridDim.x * blockDim.x) {
+      float type, spot;
+      V3 pos, dir, att;
+      float4 color;
+      if (i == 0) {
+         type = 0.0f;
+         spot = 0.0f;
+         pos = v3(0.0f, 0.0f, 0.0f);
+         dir = v3(fd.sun_raw[0] * -1.0f, fd.sun_raw[1] * 1.0f, fd.sun_raw[2] * -1.0f);
+         att = v3(1.0f, 1.0f, 1.0f);
+         color = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+      } else {
+         const UhGpuLight& l = fd.raw_lights[i - 1];
+         type = l.light_type;
+         spot = l.spot;
+         pos = v3(l.position[0], l.position[1], l.position[2]);
+         dir = v3(l.direction[0], l.direction[1], l.direction[2]);
+         att = v3(l.attenuation[0], l.attenuation[1], l.attenuation[2]);
+         color = make_float4(l.color[0], l.color[1], l.color[2], l.color[3]);
+      }
+      HybridLight h;
+      h.mode = type == 0.0f ? 0.0f : type == 1.0f ? 1.0f : type == 2.0f ? 2.0f : 3.0f;
+      V3 d = v3(0.0f, 0.0f, 0.0f);
+      if (type == 0.0f) d = normalize3(dir * v3(-1.0f, 1.0f, -1.0f));  // :38
+      if (type == 2.0f) d = normalize3(dir);                           // :51
+      h.pos[0] = pos.x, h.pos[1] = pos.y, h.pos[2] = pos.z;
+      h.color[0] = color.x, h.color[1] = color.y, h.color[2] = color.z;
+      h.spot = spot;
+      h.att[0] = att.x, h.att[1] = att.y, h.att[2] = att.z;
+      h.dir[0] = d.x, h.dir[1] = d.y, h.dir[2] = d.z;
+      h.pad0 = h.pad1 = 0.0f;
+      fd.lights[i] = h;
+   }
+}
+
+// deferred.frag:43-118 with surfaceShading (pbr_lighting.glsl:20-79) and brdf.glsl. One lane per pixel, no grid-stride loop (so the
+// light records, read at wave-uniform addresses from a table nothing in the kernel writes, become scalar loads), the light loop
+// wave-uniform with a scalar branch on the light's mode. The light-independent terms (V, F0, NdotV, GeometrySchlickGGX(NdotV), a2,
+// k, 1 - metallic, 4 NdotV) are hoisted: the same operations on the same operands, so the same bits.
+constexpr float kPiBrdf = 3.14159265359f;  // brdf.glsl:1
+__global__ __launch_bounds__(kBlock) void k_hybrid_deferred(SceneDev sc, HybridDev hd, HybridFrameDev fd, const HybridLight* __restrict__ lights, uint32_t count) {
+   __shared__ float s_gamma[256];  // pow(c / 255, 2.2) of every UNORM8 value: pow in double, rounded to float
+   s_gamma[threadIdx.x] = (float)pow((double)((float)threadIdx.x / 255.0f), (double)2.2f);
+   __syncthreads();
+   const uint32_t n = hd.W * hd.H, i = blockIdx.x * kBlock + threadIdx.x;
+   if (i >= n) return;
+   const float4 P4 = hd.pos[i], N4 = hd.nrm[i], R4 = hd.pbr[i];
+   const uchar4 A = hd.alb[i];
+   const uint32_t material = (uint32_t)R4.w;                                                    // frag:46
+   float mf = 1.0f, rf = 1.0f, type = 0.0f;
+   V3 bc = v3(1.0f, 1.0f, 1.0f);
+   if (material < sc.num_meshes) {
+      const MeshShade& ms = sc.meshes[material];
+      mf = ms.metallic;
+      rf = ms.roughness;
+      type = ms.type;
+      bc = v3(ms.base_color[0], ms.base_color[1], ms.base_color[2]);
+   }
+   const V3 P = v3(P4.x, P4.y, P4.z), N = v3(N4.x, N4.y, N4.z);
+   const float roughness = R4.y * rf, metallic = R4.x * mf, occlusion = R4.z;                   // frag:52-58
+   const V3 diffuse = v3(s_gamma[A.x], s_gamma[A.y], s_gamma[A.z]);                            // frag:61
+   const V3 base = diffuse * bc;                                                                // frag:65
+   const V3 V = normalize3(v3(hd.eye[0], hd.eye[1], hd.eye[2]) - P);                            // lighting:26
+   const float om = 1.0f - metallic;
+   const V3 F0 = v3(0.04f, 0.04f, 0.04f) * om + base * metallic;                                // lighting:29-30
+   const float NdotV = fmaxf(dot3(N, V), 0.0f);
+   const float a = roughness * roughness, a2 = a * a, a2m1 = a2 - 1.0f;                          // brdf:5-6
+   const float r1 = roughness + 1.0f, k = (r1 * r1) / 8.0f, omk = 1.0f - k;                     // brdf:19-20
+   const float ggxV = NdotV / (NdotV * omk + k);                                                // brdf:31
+   const float nv4 = 4.0f * NdotV;                                                              // lighting:71
+   V3 Lo = v3(0.0f, 0.0f, 0.0f);
+   for (uint32_t l = 0; l < count; l++) {
+      const HybridLight& hl = lights[l];
+      const float mode = hl.mode;
+      V3 L;
+      float att;
+      if (mode == 0.0f) {                                                                       // lighting:36-40
+         L = v3(hl.dir[0], hl.dir[1], hl.dir[2]);
+         att = 1.0f;
+      } else if (mode == 3.0f) {
+         L = v3(0.0f, 0.0f, 0.0f);
+         att = 1.0f;
+      } else {                                                                                  // lighting:41-53
+         const V3 ptl = v3(hl.pos[0], hl.pos[1], hl.pos[2]) - P;
+         const float d = sqrtf(dot3(ptl, ptl));
+         L = ptl * (1.0f / d);
+         const float den = (hl.att[0] * 1.0f + hl.att[1] * d) + hl.att[2] * (d * d);
+         if (mode == 2.0f)
+            att = powf(fmaxf(dot3(L, v3(hl.dir[0], hl.dir[1], hl.dir[2])), 0.0f), hl.spot) / den;
+         else
+            att = 1.0f / den;
+      }
+      const V3 Hv = normalize3(V + L);                                                          // lighting:58
+      const V3 rad = v3(hl.color[0] * att, hl.color[1] * att, hl.color[2] * att);               // lighting:59
+      const float NdotH = fmaxf(dot3(N, Hv), 0.0f);                                             // brdf:7-14
+      float dn = (NdotH * NdotH) * a2m1 + 1.0f;
+      dn = (kPiBrdf * dn) * dn;
+      const float NDF = a2 / dn;
+      const float NdotL = fmaxf(dot3(N, L), 0.0f);                                              // brdf:28-36
+      const float G = (NdotL / (NdotL * omk + k)) * ggxV;
+      const float x = fminf(fmaxf(1.0f - fmaxf(dot3(Hv, V), 0.0f), 0.0f), 1.0f);              // brdf:82-85
+      const float p5 = ((x * x) * (x * x)) * x;
+      const V3 F = F0 + (v3(1.0f, 1.0f, 1.0f) - F0) * p5;
+      const V3 kD = (v3(1.0f, 1.0f, 1.0f) - F) * om;                                            // lighting:66-68
+      const float NG = NDF * G, den2 = nv4 * NdotL + 0.0001f;                                   // lighting:70-72
+      const V3 spec = v3((NG * F.x) / den2, (NG * F.y) / den2, (NG * F.z) / den2);
+      const V3 kb = kD * base;                                                                  // lighting:76
+      const V3 c = v3(kb.x / kPiBrdf + spec.x, kb.y / kPiBrdf + spec.y, kb.z / kPiBrdf + spec.z);
+      Lo = Lo + (c * rad) * NdotL;
+   }
+   V3 color = (0.03f * diffuse) * occlusion + Lo;                                               // frag:83,90
+   if (fd.rt_on && type == 1.0f) {                                                              // frag:92-95: mix(c, r, 1.0)
+      const uchar4 r = hd.refl[i];
+      const V3 refl = v3(sc.unorm_lut[r.x], sc.unorm_lut[r.y], sc.unorm_lut[r.z]);
+      color = color * (1.0f - 1.0f) + refl * 1.0f;
+   }
+   if (fd.rt_on) color = color * fmaxf(sc.unorm_lut[hd.shadow[i]], 0.3f);                      // frag:108-111
+   if (fd.ssao_on) color = color * ((float)fd.ssao[(size_t)(hd.H - 1 - i / hd.W) * hd.W + i % hd.W] / 65535.0f);  // frag:55,113-115
+   fd.deferred[i] = make_float4(color.x, color.y, color.z, 1.0f);
+}
+
+// atmosphere.frag (cubemap_enabled = 0) on the pixels the G-buffer cast missed: compacted first (one atomic per wave), so that
+// geometry pixels cost nothing
+__global__ __launch_bounds__(kBlock) void k_hybrid_sky_classify(HybridDev hd, HybridFrameDev fd) {
+   const uint32_t n = hd.W * hd.H, groups = (n + 63) / 64, lane = lane_id();
+   for (uint32_t g = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); g < groups; g += gridDim.x * kWavesPerBlock) {
+      const uint32_t pix = g * 64u + lane;
+      const bool sky = pix < n && hd.pos[pix].w == 0.0f;
+      const uint32_t slot = wave_append(fd.sky_counter, sky);
+      if (sky) hd.queue[slot] = pix;
+   }
+}
+__global__ __launch_bounds__(kBlock) void k_hybrid_sky(FrameParams fp, HybridDev hd, HybridFrameDev fd) {
+   const uint32_t count = *fd.sky_counter;
+   const V3 sun = v3(hd.sun_dir[0], hd.sun_dir[1], hd.sun_dir[2]);
+   for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < count; i += gridDim.x * kBlock) {
+      const uint32_t pix = hd.queue[i];
+      V3 o, d;
+      primary_ray(fp, pix % hd.W, pix / hd.W, 0.5f, 0.5f, o, d);  // origin: inverse_view's translation (extract_camera_position)
+      const V3 c = sky::integrate_scattering(o, d, 999999999.0f, sun);                          // frag:19-32
+      fd.deferred[pix] = make_float4(c.x, c.y, c.z, 1.0f);                                      // frag:35
+   }
+}
+
+// present.frag + fxaa.glsl (enabled 1, debug 0, threshold 0.45: present.rs:10-23; SCREEN_WIDTH / HEIGHT 2000 x 1260 at every size)
+__device__ __forceinline__ float rgb2luma(V3 c) { return sqrtf(dot3(c, v3(0.299f, 0.587f, 0.114f))); }  // fxaa:12-15
+__device__ __forceinline__ float srgb_pow(float c) {                                            // view.glsl:53-61, pow in double
+   if (c < 0.0031308f) return c * 12.92f;
+   return 1.055f * (float)pow((double)c, (double)(1.0f / 2.4f)) - 0.055f;
+}
+__global__ __launch_bounds__(kBlock) void k_hybrid_present(HybridDev hd, HybridFrameDev fd) {
+   const uint32_t W = hd.W, H = hd.H, n = W * H, i = blockIdx.x * kBlock + threadIdx.x;
+   if (i >= n) return;
+   const float fW = (float)W, fH = (float)H;
+   const float u = ((float)(i % W) + 0.5f) / fW, v = ((float)(i / W) + 0.5f) / fH;             // present.frag:24 FLIP_UV_Y(in_uv)
+   const float4* img = fd.deferred;
+   auto tex = [&](float uu, float vv) { return bilinear_rgb(img, W, H, uu * fW - 0.5f, vv * fH - 0.5f); };
+   auto off = [&](int ox, int oy) { return rgb2luma(bilinear_rgb(img, W, H, (u * fW + (float)ox) - 0.5f, (v * fH + (float)oy) - 0.5f)); };
+   const V3 center = tex(u, v);
+   V3 color = center;
+   if (fd.fxaa_on) {
+      const float lC = rgb2luma(center);
+      const float lD = off(0, -1), lU = off(0, 1), lL = off(-1, 0), lR = off(1, 0);
+      const float lMin = fminf(lC, fminf(fminf(lD, lU), fminf(lL, lR)));
+      const float lMax = fmaxf(lC, fmaxf(fmaxf(lD, lU), fmaxf(lL, lR)));
+      const float range = lMax - lMin;
+      if (!(range < fmaxf(0.0312f, lMax * 0.45f))) {                                            // fxaa:49
+         const float lDL = off(-1, -1), lUR = off(1, 1), lUL = off(-1, 1), lDR = off(1, -1);
+         const float lDU = lD + lU, lLR = lL + lR;
+         const float lLC = lDL + lUL, lDC = lDL + lDR, lRC = lDR + lUR, lUC = lUR + lUL;
+         const float eH = (fabsf(-2.0f * lL + lLC) + fabsf(-2.0f * lC + lDU) * 2.0f) + fabsf(-2.0f * lR + lRC);
+         const float eV = (fabsf(-2.0f * lU + lUC) + fabsf(-2.0f * lC + lLR) * 2.0f) + fabsf(-2.0f * lD + lDC);
+         const bool horiz = eH >= eV;
+         const float l1 = horiz ? lD : lL, l2 = horiz ? lU : lR;
+         const float g1 = l1 - lC, g2 = l2 - lC;
+         const bool steep1 = fabsf(g1) >= fabsf(g2);
+         const float gs = 0.25f * fmaxf(fabsf(g1), fabsf(g2));
+         const float isx = 1.0f / 2000.0f, isy = 1.0f / 1260.0f;
+         float step = horiz ? isy : isx;
+         float avg;
+         if (steep1) {
+            step = -step;
+            avg = 0.5f * (l1 + lC);
+         } else {
+            avg = 0.5f * (l2 + lC);
+         }
+         float cu = u, cv = v;
+         if (horiz)
+            cv = cv + step * 0.5f;
+         else
+            cu = cu + step * 0.5f;
+         const float ox = horiz ? isx : 0.0f, oy = horiz ? 0.0f : isy;
+         float u1 = cu - ox, v1 = cv - oy, u2 = cu + ox, v2 = cv + oy;
+         float e1 = rgb2luma(tex(u1, v1)), e2 = rgb2luma(tex(u2, v2));
+         e1 = e1 - avg;
+         e2 = e2 - avg;
+         bool r1 = fabsf(e1) >= gs, r2 = fabsf(e2) >= gs;
+         if (!r1) u1 = u1 - ox, v1 = v1 - oy;
+         if (!r2) u2 = u2 + ox, v2 = v2 + oy;
+         if (!(r1 && r2)) {
+            const float quality[7] = {1.5f, 2.0f, 2.0f, 2.0f, 2.0f, 4.0f, 8.0f};
+            for (int it = 2; it < 7; it++) {
+               if (!r1) e1 = rgb2luma(tex(u1, v1)) - avg;
+               if (!r2) e2 = rgb2luma(tex(u2, v2)) - avg;
+               r1 = fabsf(e1) >= gs;
+               r2 = fabsf(e2) >= gs;
+               if (!r1) u1 = u1 - ox * quality[it], v1 = v1 - oy * quality[it];
+               if (!r2) u2 = u2 + ox * quality[it], v2 = v2 + oy * quality[it];
+               if (r1 && r2) break;
+            }
+         }
+         const float d1 = horiz ? (u - u1) : (v - v1), d2 = horiz ? (u2 - u) : (v2 - v);
+         const bool dir1 = d1 < d2;
+         const float dmin = fminf(d1, d2), thick = d1 + d2;
+         const float pix_off = -dmin / thick + 0.5f;
+         const bool smaller = lC < avg;
+         const bool correct = ((dir1 ? e1 : e2) < 0.0f) != smaller;
+         float fo = correct ? pix_off : 0.0f;
+         const float lAvg = (1.0f / 12.0f) * (((2.0f * (lDU + lLR)) + lLC) + lRC);
+         const float s1 = fminf(fmaxf(fabsf(lAvg - lC) / range, 0.0f), 1.0f);
+         const float s2 = ((-2.0f * s1 + 3.0f) * s1) * s1;
+         fo = fmaxf(fo, (s2 * s2) * 0.75f);
+         float fu = u, fv = v;
+         if (horiz)
+            fv = fv + fo * step;
+         else
+            fu = fu + fo * step;
+         color = tex(fu, fv);
+      }
+   }
+   const V3 s = v3(srgb_pow(color.x), srgb_pow(color.y), srgb_pow(color.z));                  // present.frag:37
+   fd.present[i] = make_uchar4((unsigned char)unorm8(s.z), (unsigned char)unorm8(s.y), (unsigned char)unorm8(s.x), 255);  // B8G8R8A8, alpha 1.0
+}
+
+void launch_hybrid_frame_clear(const LaunchCfg& c, const HybridDev& hd, const HybridFrameDev& fd) {
+   k_hybrid_frame_clear<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(fd, hd.W * hd.H);
+}
+static inline dim3 one_lane_per_pixel(const HybridDev& hd) { return dim3((hd.W * hd.H + kBlock - 1) / kBlock); }
+void launch_hybrid_ssao(const LaunchCfg& c, const HybridDev& hd, const HybridFrameDev& fd) {
+   k_hybrid_ssao<<<one_lane_per_pixel(hd), kBlock, 0, c.stream>>>(hd, fd);
+}
+void launch_hybrid_deferred(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd, const HybridFrameDev& fd) {
+   k_hybrid_light_prep<<<(fd.num_lights + 1 + 255) / 256, 256, 0, c.stream>>>(fd);
+   k_hybrid_deferred<<<one_lane_per_pixel(hd), kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, fd.num_lights + 1);
+}
+void launch_hybrid_sky(const LaunchCfg& c, const FrameParams& fp, const HybridDev& hd, const HybridFrameDev& fd) {
+   k_hybrid_sky_classify<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(hd, fd);
+   k_hybrid_sky<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(fp, hd, fd);
+}
+void launch_hybrid_present(const LaunchCfg& c, const HybridDev& hd, const HybridFrameDev& fd) {
+   k_hybrid_present<<<one_lane_per_pixel(hd), kBlock, 0, c.stream>>>(hd, fd);
+}
+
 }  // namespace uh

@@ -180,3 +180,19 @@ class HybridStats(C.Structure):
 
 
 assert C.sizeof(HybridStats) == 48 and HybridStats.pass_ms.offset == 24 and HybridStats.reflection_pixels.offset == 36
+
+
+# the hybrid graph's final frame (ssao_pass, deferred_pass, atmosphere_pass, present_pass; mod.rs:136-186)
+HYBRID_SSAO, HYBRID_DEFERRED, HYBRID_SKY, HYBRID_PRESENT = 1 << 3, 1 << 4, 1 << 5, 1 << 6
+HYBRID_FRAME = 0x7F
+HYBRID_SSAO_IMAGE, HYBRID_DEFERRED_OUTPUT, HYBRID_PRESENT_OUTPUT = 6, 7, 8
+
+
+class HybridFrameStats(C.Structure):
+    """UhHybridFrameStats: the last uh_render_hybrid call - hipEvent ms of the pass of each bit (rt_shadows, G-buffer, rt_reflections,
+    SSAO, deferred, sky, present), the sky pixels written and the lights evaluated per pixel (the sun included)"""
+
+    _fields_ = [("pass_ms", C.c_float * 7), ("sky_pixels", C.c_uint32), ("lights", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+assert C.sizeof(HybridFrameStats) == 48 and HybridFrameStats.sky_pixels.offset == 28 and HybridFrameStats.lights.offset == 32
