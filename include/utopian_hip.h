@@ -522,9 +522,9 @@ int uh_mgpu_set_option(uh_mgpu* group, const char* name, int value);
  * the camera / sun grids' state); its rays and times go to UhHybridStats only. The passes are always full-frame:
  * uh_set_tile_partition and uh_set_restir_partition do not apply to them.
  * GATES: view->raytracing_supported == 0 skips both ray-traced passes and leaves their images as they are (mod.rs:107,134);
- * UH_HYBRID_RT_REFLECTIONS with view->ibl_enabled == 1 is UH_ERR_INVALID_ARGUMENT - the IBL maps (irradiance, specular, BRDF LUT of
- * ibl.rs) are not part of this library - and nothing runs; mask bits, UH_ERR_NOT_BUILT and moved instances with view->rebuild_tlas
- * as for uh_render_frame (bits outside UH_HYBRID_FRAME, below, are ignored).
+ * UH_HYBRID_RT_REFLECTIONS with view->ibl_enabled == 1 is UH_ERR_INVALID_ARGUMENT - and nothing runs - until the IBL maps (irradiance,
+ * specular, BRDF LUT of ibl.rs) have been built with UH_HYBRID_ENVIRONMENT, below; mask bits, UH_ERR_NOT_BUILT and moved instances with
+ * view->rebuild_tlas as for uh_render_frame (bits above UH_HYBRID_ENVIRONMENT, below, are ignored).
  * STREAM ORDER: uh_render_hybrid enqueues like a frame (behind the frames in flight, ahead of those that follow); uh_read_hybrid and
  * uh_get_hybrid_stats wait for all work of the context and are complete on return.
  * Arithmetic: DESIGN.md section 2, "Hybrid passes". */
@@ -566,9 +566,10 @@ int uh_get_hybrid_stats(uh_ctx* ctx, UhHybridStats* out);
  *                       8-bit image of the layout and channel order of uh_read_output_bgra8 (B, G, R, A = 255), row 0 at the top
  * UH_HYBRID_FRAME runs all seven: rt_shadows (previous G-buffer), G-buffer, rt_reflections, SSAO, deferred, sky, present.
  * THE REFERENCE'S DEFAULTS (prototype/src/main.rs) SET shadows_enabled, ibl_enabled AND cubemap_enabled TO 1: a caller of these passes
- * must clear them. UH_ERR_INVALID_ARGUMENT with a message, and nothing runs, for UH_HYBRID_DEFERRED with view->shadows_enabled == 1
- * (the cascaded shadow maps are raster passes outside this library) or view->ibl_enabled == 1 (the IBL maps of ibl.rs), for
- * UH_HYBRID_SKY with view->cubemap_enabled == 1 (the environment cube of ibl.rs), and for UH_HYBRID_DEFERRED with view->num_lights
+ * must clear them, or (ibl_enabled, cubemap_enabled) build the maps with UH_HYBRID_ENVIRONMENT, below. UH_ERR_INVALID_ARGUMENT with a
+ * message, and nothing runs, for UH_HYBRID_DEFERRED with view->shadows_enabled == 1 (the cascaded shadow maps are raster passes outside
+ * this library) or, before the first build, view->ibl_enabled == 1 (the IBL maps of ibl.rs), for UH_HYBRID_SKY with
+ * view->cubemap_enabled == 1 before the first build (the environment cube of ibl.rs), and for UH_HYBRID_DEFERRED with view->num_lights
  * above the lights added with uh_add_light. view->marching_cubes_enabled is not read: meshes of uh_add_isosurface_mesh are scene
  * geometry and go through the G-buffer like any other.
  * ORIENTATION (the reference draws under a Y-flipped viewport, pass.rs:260-267): deferred pixel (x, y) and present pixel (x, y) read the
@@ -596,6 +597,58 @@ typedef struct UhHybridFrameStats {
 UH_LAYOUT_ASSERT(sizeof(UhHybridFrameStats) == 48 && offsetof(UhHybridFrameStats, sky_pixels) == 28 && offsetof(UhHybridFrameStats, lights) == 32,
                  "UhHybridFrameStats (48 B)");
 int uh_get_hybrid_frame_stats(uh_ctx* ctx, UhHybridFrameStats* out); /* waits; all zero before the first uh_render_hybrid */
+
+/* ---- image-based lighting: setup_cubemap_pass (ibl.rs) and its consumers ---------------------------------------------------
+ * One more bit of uh_render_hybrid, run where the reference adds the pass (mod.rs:121): after the G-buffer pass, before rt_reflections.
+ *   UH_HYBRID_ENVIRONMENT  builds the four maps of ibl.rs at the reference's sizes, in its order:
+ *     environment cube  cubemap.frag: RGBA32F, 512^2, 8 mips, every mip integrated from the atmosphere at its own size (not
+ *                       downsampled); rayStart = the translation of view->inverse_view (extract_camera_position), view->sun_dir as
+ *                       given (not normalised)
+ *     irradiance cube   irradiance_filter.frag: RGBA32F, 512^2, 1 mip; the shader's 252 x 63 float-stepped taps in its order, on
+ *                       environment mip 0
+ *     specular cube     specular_filter.frag: RGBA32F, 512^2, 8 mips; 32 GGX taps at roughness mip / 7, trilinear environment lookups
+ *     BRDF LUT          brdf_lut.frag: 512^2 R16G16_SFLOAT (fp16 pairs, rounded to nearest even), 1024 taps per texel
+ * The reference rebuilds them when renderer.need_environment_map_update is set (the first frame, or on request); here the caller asks
+ * by setting the bit. The maps persist in the context until the next call with the bit: moving the sun without it leaves them
+ * stale, as there. UH_HYBRID_FRAME stays 0x7f: it does not build them.
+ * CONSUMERS, once the maps exist (built by an earlier call or earlier in the same call):
+ *   UH_HYBRID_DEFERRED with view->ibl_enabled == 1      ambient = imageBasedLighting (pbr_lighting.glsl:81-108) instead of 0.03 * diffuse * occlusion
+ *   UH_HYBRID_SKY with view->cubemap_enabled == 1       textureLod(environment, dir * (1, -1, 1), 2) (atmosphere.frag:27-29), dir the
+ *                                                       pixel's un-jittered primary-ray direction
+ *   UH_HYBRID_RT_REFLECTIONS with view->ibl_enabled == 1  the hit shader's IBL branch (rt_reflections.rchit:50-61): imageBasedLighting of
+ *                                                       the hit, stored like the non-IBL payload; the miss branch is unchanged
+ * On a context whose maps were never built, these three are refused as before (UH_ERR_INVALID_ARGUMENT, nothing runs); the message
+ * names UH_HYBRID_ENVIRONMENT. view->shadows_enabled == 1 stays refused for the deferred pass.
+ * RESOURCES: the four maps (about 93 MB) are allocated by the first call whose mask holds UH_HYBRID_ENVIRONMENT (UH_ERR_OUT_OF_MEMORY
+ * when that fails) and freed by uh_destroy; a context that never sets the bit allocates nothing for them. A build changes no other
+ * image of the hybrid graph and nothing in UhStats or UhHybridStats.
+ * READ-BACK: uh_read_environment copies face `face` (0..5: +X, -X, +Y, -Y, +Z, -Z layers of the reference's cube) of mip `mip` of map
+ * `which`: (512 >> mip)^2 texels, row 0 first. RGBA32F for the cubes; the LUT (face 0, mip 0) is 512^2 pairs of IEEE half floats
+ * (R, G), row 0 first. UH_ERR_INVALID_ARGUMENT before the first build, and for an unknown map, face or mip. Waits like uh_read_hybrid.
+ * Arithmetic (texel directions, cube addressing and seamless filtering, the deviations): DESIGN.md section 2, "Environment and IBL maps". */
+enum { UH_HYBRID_ENVIRONMENT = 1u << 7 };
+enum { UH_ENV_SIZE = 512, UH_ENV_MIPS = 8, UH_BRDF_LUT_SIZE = 512 };
+enum {
+   UH_ENV_ENVIRONMENT = 0, /* RGBA32F, 6 faces, 8 mips */
+   UH_ENV_IRRADIANCE = 1,  /* RGBA32F, 6 faces, mip 0 */
+   UH_ENV_SPECULAR = 2,    /* RGBA32F, 6 faces, 8 mips */
+   UH_ENV_BRDF_LUT = 3     /* 2 x fp16, face 0, mip 0 */
+};
+int uh_read_environment(uh_ctx* ctx, int which, int face, int mip, void* out);
+/* the last build: pass_ms the hipEvent time of its four sub-passes (environment, irradiance, specular, BRDF LUT); builds the number
+ * of builds so far; sun_dir (as given) and eye (the translation of view->inverse_view) the maps were built with. All zero before the
+ * first build. Waits for all work of the context. */
+typedef struct UhEnvironmentStats {
+   float pass_ms[4];
+   uint32_t builds;
+   float sun_dir[3];
+   float eye[3];
+   uint32_t reserved[5];
+} UhEnvironmentStats;
+UH_LAYOUT_ASSERT(sizeof(UhEnvironmentStats) == 64 && offsetof(UhEnvironmentStats, builds) == 16 && offsetof(UhEnvironmentStats, sun_dir) == 20 &&
+                    offsetof(UhEnvironmentStats, eye) == 32,
+                 "UhEnvironmentStats (64 B)");
+int uh_get_environment_stats(uh_ctx* ctx, UhEnvironmentStats* out);
 
 #ifdef __cplusplus
 }

@@ -324,6 +324,20 @@ class Renderer {
       check(uh_get_hybrid_frame_stats(ctx_, &s), "hybrid_frame_stats");
       return s;
    }
+   // one face and mip of an IBL map built with UH_HYBRID_ENVIRONMENT (utopian_hip.h "uh_read_environment"): (512 >> mip)^2 texels of
+   // 4 floats for the cubes, 512^2 pairs of IEEE half floats (as uint16_t bits) for the BRDF LUT
+   std::vector<float> read_environment(int which, int face = 0, int mip = 0) {
+      const size_t s = (size_t)UH_ENV_SIZE >> mip;
+      std::vector<float> out(which == UH_ENV_BRDF_LUT ? (size_t)UH_BRDF_LUT_SIZE * UH_BRDF_LUT_SIZE : s * s * 4);
+      check(uh_read_environment(ctx_, which, face, mip, out.data()), "read_environment");
+      return out;
+   }
+   // pass_ms of the last build's four sub-passes (environment, irradiance, specular, BRDF LUT), the builds so far, its sun and eye
+   UhEnvironmentStats environment_stats() {
+      UhEnvironmentStats s;
+      check(uh_get_environment_stats(ctx_, &s), "environment_stats");
+      return s;
+   }
    // uh_set_option: "device_build", "frames_in_flight", ... (DESIGN.md "Options")
    void set_option(const char* name, int value) { check(uh_set_option(ctx_, name, value), name); }
    // marching_cubes.rs:17-83 / marching_cubes.comp: the density field's iso-surface, extracted on the GPU and added

@@ -21,6 +21,13 @@ from .types import (
     RESERVOIR_DTYPE,
     RESTIR_EXCHANGE_FN,
     VERTEX_DTYPE,
+    BRDF_LUT_SIZE,
+    ENV_BRDF_LUT,
+    ENV_ENVIRONMENT,
+    ENV_IRRADIANCE,
+    ENV_MIPS,
+    ENV_SIZE,
+    ENV_SPECULAR,
     HYBRID_ALBEDO,
     HYBRID_ALL,
     HYBRID_DEFERRED_OUTPUT,
@@ -33,6 +40,7 @@ from .types import (
     HYBRID_SSAO_IMAGE,
     GpuLight,
     GpuMaterial,
+    EnvironmentStats,
     HybridFrameStats,
     HybridStats,
     Reservoir,
@@ -84,8 +92,10 @@ class CApi:
             "read_hybrid": [vp, C.c_int, vp],
             "get_hybrid_stats": [vp, p(HybridStats)],
             "get_hybrid_frame_stats": [vp, p(HybridFrameStats)],
+            "read_environment": [vp, C.c_int, C.c_int, C.c_int, vp],
+            "get_environment_stats": [vp, p(EnvironmentStats)],
         }
-        hybrid = ("render_hybrid", "read_hybrid", "get_hybrid_stats", "get_hybrid_frame_stats")
+        hybrid = ("render_hybrid", "read_hybrid", "get_hybrid_stats", "get_hybrid_frame_stats", "read_environment", "get_environment_stats")
         for name, argtypes in sig.items():
             if not hasattr(lib, prefix + name) and (name == "render_frames" or name in hybrid or prefix == "uh_mgpu_"):
                 continue  # the oracle renders frame by frame and has no hybrid passes; the GPU group has no per-context queries
@@ -457,6 +467,27 @@ class Renderer:
         api = self._hybrid_api()
         s = HybridStats()
         self._check(api.get_hybrid_stats(self._ctx, C.byref(s)))
+        return s
+
+    def read_environment(self, which, face=0, mip=0):
+        """one face and mip of an IBL map (ENV_ENVIRONMENT / ENV_IRRADIANCE / ENV_SPECULAR: (S, S, 4) float32, S = 512 >> mip, row 0
+        first) or the BRDF LUT (ENV_BRDF_LUT, face 0, mip 0: (512, 512, 2) float16, R and G)"""
+        api = self._hybrid_api()
+        if which == ENV_BRDF_LUT:
+            out = np.empty((BRDF_LUT_SIZE, BRDF_LUT_SIZE, 2), dtype=np.float16)
+        elif which in (ENV_ENVIRONMENT, ENV_IRRADIANCE, ENV_SPECULAR) and 0 <= mip < ENV_MIPS:
+            s = ENV_SIZE >> mip
+            out = np.empty((s, s, 4), dtype=np.float32)
+        else:
+            raise ValueError(f"environment map {which} (0..3), mip {mip} (0..7)")
+        self._check(api.read_environment(self._ctx, int(which), int(face), int(mip), out.ctypes.data))
+        return out
+
+    def environment_stats(self):
+        """UhEnvironmentStats of the last HYBRID_ENVIRONMENT build: pass_ms of its four sub-passes, builds, sun_dir and eye"""
+        api = self._hybrid_api()
+        s = EnvironmentStats()
+        self._check(api.get_environment_stats(self._ctx, C.byref(s)))
         return s
 
     def hybrid_frame_stats(self):

@@ -324,7 +324,7 @@ struct uh_ctx {
       DevBuf<uint32_t> indices;
       uint64_t geom = 0;                       // geom_version the mesh tables were made for
       hipEvent_t waits[2 * kMaxSlots + 1] = {};  // behind the frames in flight
-      hipEvent_t ev[8] = {};                   // pass boundaries of the last call, in pass order (timing)
+      hipEvent_t ev[9] = {};                   // pass boundaries of the last call, in pass order (timing); [8]: rt_reflections' start
       bool ran[3] = {false, false, false};     // G-buffer, rt_shadows, rt_reflections in the last call
       // the final frame's passes (SSAO, deferred, sky, present), allocated by the first call that asks for one of them
       DevBuf<uint16_t> ssao;
@@ -336,6 +336,13 @@ struct uh_ctx {
       size_t lights_uploaded = SIZE_MAX;       // c->lights.size() when raw_lights was uploaded
       bool frame_ran[4] = {false, false, false, false};  // SSAO, deferred, sky, present in the last call
       uint32_t frame_lights = 0;               // lights the deferred pass of the last call evaluated (the sun included)
+      // the IBL maps of setup_cubemap_pass (UH_HYBRID_ENVIRONMENT), allocated by the first call that builds them
+      DevBuf<float4> env, irr, spec;
+      DevBuf<uint32_t> lut;
+      DevBuf<float4> taps;                     // the irradiance filter's tap table
+      hipEvent_t env_ev[5] = {};               // sub-pass boundaries of the last build (environment, irradiance, specular, LUT)
+      uint32_t env_builds = 0;
+      float env_sun[3] = {0, 0, 0}, env_eye[3] = {0, 0, 0};  // what the last build was made with
    } hy;
 };
 
@@ -605,9 +612,16 @@ void uh_destroy(uh_ctx* c) {
       h.sky_counter.release();
       h.raw_lights.release();
       h.lights.release();
+      h.env.release();
+      h.irr.release();
+      h.spec.release();
+      h.lut.release();
+      h.taps.release();
       for (hipEvent_t ev : h.waits)
          if (ev) (void)hipEventDestroy(ev);
       for (hipEvent_t ev : h.ev)
+         if (ev) (void)hipEventDestroy(ev);
+      for (hipEvent_t ev : h.env_ev)
          if (ev) (void)hipEventDestroy(ev);
    }
    for (auto& s : c->slots) s.destroy();
@@ -2641,29 +2655,62 @@ static int hybrid_light_table(uh_ctx* c) {
    return UH_OK;
 }
 
+// the IBL maps (first call with UH_HYBRID_ENVIRONMENT) and the irradiance filter's tap table: irradiance_filter.frag:38-46's phi and
+// theta are float accumulators stepped by 0.025 while below 2 PI and PI / 2 (float); sin and cos in double, rounded to float, and the
+// products tangentSample.x = sin(theta) cos(phi), .y = sin(theta) sin(phi) in float
+static int env_alloc(uh_ctx* c) {
+   uh_ctx::Hybrid& h = c->hy;
+   if (h.lut.p) return UH_OK;
+   std::vector<float4> taps;
+   taps.reserve(kIrrPhi * kIrrTheta);
+   const float pi = 3.14159265358979323846f, delta = 0.025f;
+   for (float phi = 0.0f; phi < 2.0f * pi; phi += delta) {
+      for (float theta = 0.0f; theta < 0.5f * pi; theta += delta) {
+         const float st = (float)std::sin((double)theta), ct = (float)std::cos((double)theta);
+         const float cp = (float)std::cos((double)phi), sp = (float)std::sin((double)phi);
+         taps.push_back(make_float4(st * cp, st * sp, ct, st));
+      }
+   }
+   if (taps.size() != (size_t)kIrrPhi * kIrrTheta) return fail(c, UH_ERR_HIP, "irradiance tap count");
+   const size_t cube = env_mip_offset(kEnvMips);
+   HIP_TRY(c, h.env.alloc(cube));
+   HIP_TRY(c, h.irr.alloc(6 * (size_t)kEnvSize * kEnvSize));
+   HIP_TRY(c, h.spec.alloc(cube));
+   HIP_TRY(c, h.taps.alloc(taps.size()));
+   HIP_TRY(c, hipMemcpyAsync(h.taps.p, taps.data(), taps.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+   HIP_TRY(c, hipStreamSynchronize(c->stream));
+   for (hipEvent_t& ev : h.env_ev)
+      if (!ev) HIP_TRY(c, hipEventCreate(&ev));
+   HIP_TRY(c, h.lut.alloc((size_t)kLutSize * kLutSize));  // last: its pointer says "allocated"
+   return UH_OK;
+}
+
 int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    if (!view) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_render_hybrid: null view");
-   if ((mask & UH_HYBRID_RT_REFLECTIONS) && view->ibl_enabled == 1)
+   // the IBL maps exist for this call's consumers when an earlier call built them or this one does, before rt_reflections
+   const bool maps = c->hy.env_builds > 0 || (mask & UH_HYBRID_ENVIRONMENT);
+   if ((mask & UH_HYBRID_RT_REFLECTIONS) && view->ibl_enabled == 1 && !maps)
       return fail(c, UH_ERR_INVALID_ARGUMENT,
                   "uh_render_hybrid: rt_reflections with view.ibl_enabled = 1 needs the IBL maps (irradiance, specular, BRDF LUT of ibl.rs), "
-                  "which are not part of this library; set ibl_enabled = 0 for the reflection pass's non-IBL branch");
+                  "which are not part of this library until a call with UH_HYBRID_ENVIRONMENT builds them; set that bit, or ibl_enabled = 0 "
+                  "for the reflection pass's non-IBL branch");
    if (mask & UH_HYBRID_DEFERRED) {
       if (view->shadows_enabled == 1)
          return fail(c, UH_ERR_INVALID_ARGUMENT,
                      "uh_render_hybrid: the deferred pass with view.shadows_enabled = 1 needs the cascaded shadow maps (shadow.rs), raster passes "
                      "that are not part of this library; set shadows_enabled = 0 for the rt_shadows branch");
-      if (view->ibl_enabled == 1)
+      if (view->ibl_enabled == 1 && !maps)
          return fail(c, UH_ERR_INVALID_ARGUMENT,
                      "uh_render_hybrid: the deferred pass with view.ibl_enabled = 1 needs the IBL maps (irradiance, specular, BRDF LUT of ibl.rs), "
-                     "which are not part of this library; set ibl_enabled = 0 for the ambient term 0.03 * diffuse * occlusion");
+                     "which a call with UH_HYBRID_ENVIRONMENT builds; set that bit, or ibl_enabled = 0 for the ambient term 0.03 * diffuse * occlusion");
       if (view->num_lights > c->lights.size())
          return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_render_hybrid: view.num_lights exceeds the lights added with uh_add_light");
    }
-   if ((mask & UH_HYBRID_SKY) && view->cubemap_enabled == 1)
+   if ((mask & UH_HYBRID_SKY) && view->cubemap_enabled == 1 && !maps)
       return fail(c, UH_ERR_INVALID_ARGUMENT,
-                  "uh_render_hybrid: the sky pass with view.cubemap_enabled = 1 needs the environment cube (ibl.rs), which is not part of "
-                  "this library; set cubemap_enabled = 0 for the IntegrateScattering branch");
+                  "uh_render_hybrid: the sky pass with view.cubemap_enabled = 1 needs the environment cube (ibl.rs), which a call with "
+                  "UH_HYBRID_ENVIRONMENT builds; set that bit, or cubemap_enabled = 0 for the IntegrateScattering branch");
    if (!c->built && c->topology_valid && view->rebuild_tlas == 1)
       if (int st = uh_refit_acceleration(c)) return st;
    if (!c->built) return fail(c, UH_ERR_NOT_BUILT, "uh_render_hybrid before uh_build_acceleration");
@@ -2679,6 +2726,8 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
       if (mask & UH_HYBRID_DEFERRED)
          if (int st = hybrid_light_table(c)) return st;
    }
+   if (mask & UH_HYBRID_ENVIRONMENT)
+      if (int st = env_alloc(c)) return st;
    const FrameParams fp = make_params(c, *view);
    HybridDev hd{};
    hd.pos = h.pos.p;
@@ -2751,9 +2800,39 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    HIP_TRY(c, hipEventRecord(h.ev[1], c->stream));
    if (h.ran[0]) launch_hybrid_gbuffer(lc, fp, c->scene, hd, grid ? &c->cam_dev : nullptr);
    HIP_TRY(c, hipEventRecord(h.ev[2], c->stream));
+   // setup_cubemap_pass (mod.rs:121): after the G-buffer, before rt_reflections; the maps persist until the next build
+   IblMaps ibl{h.env.p, h.irr.p, h.spec.p, h.lut.p};
+   if (mask & UH_HYBRID_ENVIRONMENT) {
+      EnvDev e{};
+      e.env = h.env.p;
+      e.irr = h.irr.p;
+      e.spec = h.spec.p;
+      e.lut = h.lut.p;
+      e.taps = h.taps.p;
+      for (int a = 0; a < 3; a++) {
+         e.eye[a] = view->inverse_view[12 + a];  // extract_camera_position(view.view): inverse(view)[3]
+         e.sun[a] = view->sun_dir[a];
+         h.env_eye[a] = e.eye[a];
+         h.env_sun[a] = e.sun[a];
+      }
+      HIP_TRY(c, hipEventRecord(h.env_ev[0], c->stream));
+      launch_env_cube(lc, e);
+      HIP_TRY(c, hipEventRecord(h.env_ev[1], c->stream));
+      launch_env_irradiance(lc, e);
+      HIP_TRY(c, hipEventRecord(h.env_ev[2], c->stream));
+      launch_env_specular(lc, e);
+      HIP_TRY(c, hipEventRecord(h.env_ev[3], c->stream));
+      launch_env_brdf_lut(lc, e);
+      HIP_TRY(c, hipEventRecord(h.env_ev[4], c->stream));
+      h.env_builds++;
+   }
+   HIP_TRY(c, hipEventRecord(h.ev[8], c->stream));
    if (h.ran[2]) {
       HIP_TRY(c, hipMemsetAsync(h.counter.p, 0, sizeof(uint32_t), c->stream));
-      launch_hybrid_reflections(lc, c->scene, hd);
+      if (view->ibl_enabled == 1)
+         launch_hybrid_reflections_ibl(lc, c->scene, hd, ibl);
+      else
+         launch_hybrid_reflections(lc, c->scene, hd);
    }
    HIP_TRY(c, hipEventRecord(h.ev[3], c->stream));
    // the final frame (mod.rs:136-186): ssao_pass (not with ssao_enabled != 1, ssao.rs:27), deferred_pass, atmosphere_pass, present_pass
@@ -2764,11 +2843,19 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    h.frame_lights = h.frame_ran[1] ? view->num_lights + 1 : 0;
    if (h.frame_ran[0]) launch_hybrid_ssao(lc, hd, fd);
    HIP_TRY(c, hipEventRecord(h.ev[4], c->stream));
-   if (h.frame_ran[1]) launch_hybrid_deferred(lc, c->scene, hd, fd);
+   if (h.frame_ran[1]) {
+      if (view->ibl_enabled == 1)
+         launch_hybrid_deferred_ibl(lc, c->scene, hd, fd, ibl);
+      else
+         launch_hybrid_deferred(lc, c->scene, hd, fd);
+   }
    HIP_TRY(c, hipEventRecord(h.ev[5], c->stream));
    if (h.frame_ran[2]) {
       HIP_TRY(c, hipMemsetAsync(h.sky_counter.p, 0, sizeof(uint32_t), c->stream));
-      launch_hybrid_sky(lc, fp, hd, fd);
+      if (view->cubemap_enabled == 1)
+         launch_hybrid_sky_cube(lc, fp, hd, fd, ibl);
+      else
+         launch_hybrid_sky(lc, fp, hd, fd);
    }
    HIP_TRY(c, hipEventRecord(h.ev[6], c->stream));
    if (h.frame_ran[3]) launch_hybrid_present(lc, hd, fd);
@@ -2811,11 +2898,42 @@ int uh_get_hybrid_frame_stats(uh_ctx* c, UhHybridFrameStats* out) {
    const bool ran[7] = {h.ran[1], h.ran[0], h.ran[2], h.frame_ran[0], h.frame_ran[1], h.frame_ran[2], h.frame_ran[3]};
    for (int k = 0; k < 7; k++) {
       float ms = 0.0f;
-      if (ran[k]) HIP_TRY(c, hipEventElapsedTime(&ms, h.ev[k], h.ev[k + 1]));  // pass k between events k and k + 1
+      if (ran[k]) HIP_TRY(c, hipEventElapsedTime(&ms, h.ev[k == 2 ? 8 : k], h.ev[k + 1]));  // pass k between events k (rt_reflections: 8) and k + 1
       out->pass_ms[k] = ms;
    }
    if (h.frame_ran[2]) HIP_TRY(c, hipMemcpy(&out->sky_pixels, h.sky_counter.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
    out->lights = h.frame_lights;
+   return UH_OK;
+}
+
+int uh_read_environment(uh_ctx* c, int which, int face, int mip, void* out) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   const uh_ctx::Hybrid& h = c->hy;
+   if (h.env_builds == 0) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_environment before the first call with UH_HYBRID_ENVIRONMENT");
+   if (which == UH_ENV_BRDF_LUT) {
+      if (face != 0 || mip != 0) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_environment: the BRDF LUT has face 0 and mip 0 only");
+      return read_back(c, out, h.lut.p, (size_t)kLutSize * kLutSize * sizeof(uint32_t));
+   }
+   if (which < UH_ENV_ENVIRONMENT || which > UH_ENV_SPECULAR) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_environment: map must be 0..3");
+   const int mips = which == UH_ENV_IRRADIANCE ? 1 : (int)kEnvMips;
+   if (face < 0 || face > 5 || mip < 0 || mip >= mips) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_environment: face 0..5, mip 0..7 (irradiance: 0)");
+   const size_t S = kEnvSize >> mip;
+   const float4* base = which == UH_ENV_ENVIRONMENT ? h.env.p : which == UH_ENV_IRRADIANCE ? h.irr.p : h.spec.p;
+   return read_back(c, out, base + env_mip_offset((uint32_t)mip) + (size_t)face * S * S, S * S * sizeof(float4));
+}
+
+int uh_get_environment_stats(uh_ctx* c, UhEnvironmentStats* out) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_environment_stats: null destination");
+   std::memset(out, 0, sizeof(*out));
+   const uh_ctx::Hybrid& h = c->hy;
+   if (h.env_builds == 0) return UH_OK;
+   HIP_TRY(c, hipSetDevice(c->device));
+   if (int st = sync_all(c)) return st;
+   for (int k = 0; k < 4; k++) HIP_TRY(c, hipEventElapsedTime(&out->pass_ms[k], h.env_ev[k], h.env_ev[k + 1]));
+   out->builds = h.env_builds;
+   std::memcpy(out->sun_dir, h.env_sun, sizeof(out->sun_dir));
+   std::memcpy(out->eye, h.env_eye, sizeof(out->eye));
    return UH_OK;
 }
 
@@ -2834,10 +2952,10 @@ int uh_get_hybrid_stats(uh_ctx* c, UhHybridStats* out) {
    out->rays[1] = h.ran[1] ? n : 0;
    out->rays[2] = metal;
    out->reflection_pixels = metal;
-   const int from[3] = {1, 0, 2};  // G-buffer between events 1 and 2, rt_shadows 0 and 1, rt_reflections 2 and 3
+   const int from[3] = {1, 0, 8}, to[3] = {2, 1, 3};  // G-buffer between events 1 and 2, rt_shadows 0 and 1, rt_reflections 8 and 3
    for (int k = 0; k < 3; k++) {
       float ms = 0.0f;
-      if (h.ran[k]) HIP_TRY(c, hipEventElapsedTime(&ms, h.ev[from[k]], h.ev[from[k] + 1]));
+      if (h.ran[k]) HIP_TRY(c, hipEventElapsedTime(&ms, h.ev[from[k]], h.ev[to[k]]));
       out->pass_ms[k] = ms;
    }
    return UH_OK;

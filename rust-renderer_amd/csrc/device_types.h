@@ -292,6 +292,38 @@ void launch_hybrid_ssao(const LaunchCfg&, const HybridDev&, const HybridFrameDev
 void launch_hybrid_deferred(const LaunchCfg&, const SceneDev&, const HybridDev&, const HybridFrameDev&);
 void launch_hybrid_sky(const LaunchCfg&, const FrameParams&, const HybridDev&, const HybridFrameDev&);
 void launch_hybrid_present(const LaunchCfg&, const HybridDev&, const HybridFrameDev&);
+// image-based lighting (setup_cubemap_pass, ibl.rs; ibl.hip): the four maps and their consumers
+constexpr uint32_t kEnvSize = 512, kEnvMips = 8, kLutSize = 512;
+// the irradiance filter's float-stepped loops (irradiance_filter.frag:38-41): phi 0, 0.025, ... < 2 PI; theta 0, 0.025, ... < PI / 2
+constexpr uint32_t kIrrPhi = 252, kIrrTheta = 63;
+// a cube of kEnvSize: mip m (size kEnvSize >> m) starts at texel env_mip_offset(m); face f of it at + f * size^2; row-major inside
+__host__ __device__ inline uint32_t env_mip_offset(uint32_t m) {
+   uint32_t o = 0;
+   for (uint32_t k = 0; k < m; k++) o += 6u * (kEnvSize >> k) * (kEnvSize >> k);
+   return o;
+}
+struct IblMaps {                // what the consumers read
+   const float4* env;           // environment cube, kEnvMips mips
+   const float4* irr;           // irradiance cube, mip 0
+   const float4* spec;          // prefiltered specular cube, kEnvMips mips
+   const uint32_t* lut;         // BRDF LUT, kLutSize^2 half pairs (R in the low 16 bits)
+};
+struct EnvDev {                 // what the build writes
+   float4* env;
+   float4* irr;
+   float4* spec;
+   uint32_t* lut;
+   const float4* taps;          // kIrrPhi * kIrrTheta: (sin t cos p, sin t sin p, cos t, sin t), phi-major, rounded from double
+   float eye[3];                // rayStart: the translation of view.inverse_view
+   float sun[3];                // view.sun_dir as given
+};
+void launch_env_cube(const LaunchCfg&, const EnvDev&);
+void launch_env_irradiance(const LaunchCfg&, const EnvDev&);
+void launch_env_specular(const LaunchCfg&, const EnvDev&);
+void launch_env_brdf_lut(const LaunchCfg&, const EnvDev&);
+void launch_hybrid_deferred_ibl(const LaunchCfg&, const SceneDev&, const HybridDev&, const HybridFrameDev&, const IblMaps&);
+void launch_hybrid_sky_cube(const LaunchCfg&, const FrameParams&, const HybridDev&, const HybridFrameDev&, const IblMaps&);
+void launch_hybrid_reflections_ibl(const LaunchCfg&, const SceneDev&, const HybridDev&, const IblMaps&);
 // tiles
 // on-device refit (refit.hip): per-mesh object->world rows, and what one refit pass touches
 struct RefitMesh {

@@ -15,6 +15,7 @@
 
 #include "device_math.h"
 #include "device_types.h"
+#include "ibl_device.h"
 
 namespace uh {
 
@@ -2661,8 +2662,10 @@ __global__ __launch_bounds__(kBlock) void k_hybrid_reflect_classify(SceneDev sc,
    }
 }
 
-// rt_reflections.rgen:22-44 + .rchit:22-64 (IBL off) + .rmiss:9-24 for the queued metal pixels: closest hit, then a lane shades its own ray
-__global__ __launch_bounds__(kBlock) void k_hybrid_reflect(SceneDev sc, HybridDev hd) {
+// rt_reflections.rgen:22-44 + .rchit:22-64 + .rmiss:9-24 for the queued metal pixels: closest hit, then a lane shades its own ray. kIbl: the
+// hit shader's ibl_enabled branch (rchit:50-61) on the IBL maps
+template <bool kIbl>
+__global__ __launch_bounds__(kBlock) void k_hybrid_reflect(SceneDev sc, HybridDev hd, IblMaps ibl) {
    __shared__ uint32_t s_stack[kWavesPerBlock][kLdsStack][64];
    uint32_t* lds_col = &s_stack[threadIdx.x >> 6][0][lane_id()];
    const uint32_t count = *hd.counter;
@@ -2685,7 +2688,16 @@ __global__ __launch_bounds__(kBlock) void k_hybrid_reflect(SceneDev sc, HybridDe
          const MeshShade ms = sc.meshes[__float_as_uint(s3.w)];
          V3 color = sample_texture(sc, sc.unorm_lut, ms.diffuse_map, uu, vv);                        // rchit:41
          color = color * v3(ms.base_color[0], ms.base_color[1], ms.base_color[2]);                   // rchit:42
-         c = 0.1f * color;                                                                           // rchit:62
+         if (kIbl) {
+            const HybridMesh& hm = hd.meshes[__float_as_uint(s3.w)];
+            const V3 mr = sample_texture(sc, sc.unorm_lut, hm.metallic_roughness_map, uu, vv);        // rchit:56-57
+            const V3 oc = sample_texture(sc, sc.unorm_lut, hm.occlusion_map, uu, vv);                 // rchit:58
+            const V3 wn = world_normal_of(ms, normal, dir);                                          // rchit:32-37
+            const V3 pos = o + h.t * dir;                                                            // the hit point of the ray
+            c = ibl::image_based_lighting(ibl, pos, color, wn, mr.z, mr.y, oc.x, eye);               // rchit:60
+         } else {
+            c = 0.1f * color;                                                                        // rchit:62
+         }
       } else if (hd.furnace) {
          c = v3(1.0f, 1.0f, 1.0f);                                                                   // rmiss:12 (FURNACE_TEST)
       } else {
@@ -2718,7 +2730,11 @@ void launch_hybrid_shadows(const LaunchCfg& c, const SceneDev& sc, const HybridD
 }
 void launch_hybrid_reflections(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd) {
    k_hybrid_reflect_classify<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(sc, hd);
-   k_hybrid_reflect<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(sc, hd);
+   k_hybrid_reflect<false><<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(sc, hd, IblMaps{});
+}
+void launch_hybrid_reflections_ibl(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd, const IblMaps& ibl) {
+   k_hybrid_reflect_classify<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(sc, hd);
+   k_hybrid_reflect<true><<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(sc, hd, ibl);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2849,8 +2865,11 @@ __global__ void k_hybrid_light_prep(HybridFrameDev fd) {
 // light records, read at wave-uniform addresses from a table nothing in the kernel writes, become scalar loads), the light loop
 // wave-uniform with a scalar branch on the light's mode. The light-independent terms (V, F0, NdotV, GeometrySchlickGGX(NdotV), a2,
 // k, 1 - metallic, 4 NdotV) are hoisted: the same operations on the same operands, so the same bits.
+// kIbl: the ambient term is imageBasedLighting on the IBL maps (frag:85-88) instead of 0.03 * diffuse * occlusion.
 constexpr float kPiBrdf = 3.14159265359f;  // brdf.glsl:1
-__global__ __launch_bounds__(kBlock) void k_hybrid_deferred(SceneDev sc, HybridDev hd, HybridFrameDev fd, const HybridLight* __restrict__ lights, uint32_t count) {
+template <bool kIbl>
+__global__ __launch_bounds__(kBlock) void k_hybrid_deferred(SceneDev sc, HybridDev hd, HybridFrameDev fd, const HybridLight* __restrict__ lights, uint32_t count,
+                                                            IblMaps ibl) {
    __shared__ float s_gamma[256];  // pow(c / 255, 2.2) of every UNORM8 value: pow in double, rounded to float
    s_gamma[threadIdx.x] = (float)pow((double)((float)threadIdx.x / 255.0f), (double)2.2f);
    __syncthreads();
@@ -2920,7 +2939,9 @@ __global__ __launch_bounds__(kBlock) void k_hybrid_deferred(SceneDev sc, HybridD
       const V3 c = v3(kb.x / kPiBrdf + spec.x, kb.y / kPiBrdf + spec.y, kb.z / kPiBrdf + spec.z);
       Lo = Lo + (c * rad) * NdotL;
    }
-   V3 color = (0.03f * diffuse) * occlusion + Lo;                                               // frag:83,90
+   V3 ambient = (0.03f * diffuse) * occlusion;                                                  // frag:83
+   if (kIbl) ambient = ibl::image_based_lighting(ibl, P, base, N, metallic, roughness, occlusion, v3(hd.eye[0], hd.eye[1], hd.eye[2]));  // frag:85-88
+   V3 color = ambient + Lo;                                                                     // frag:90
    if (fd.rt_on && type == 1.0f) {                                                              // frag:92-95: mix(c, r, 1.0)
       const uchar4 r = hd.refl[i];
       const V3 refl = v3(sc.unorm_lut[r.x], sc.unorm_lut[r.y], sc.unorm_lut[r.z]);
@@ -2942,14 +2963,17 @@ __global__ __launch_bounds__(kBlock) void k_hybrid_sky_classify(HybridDev hd, Hy
       if (sky) hd.queue[slot] = pix;
    }
 }
-__global__ __launch_bounds__(kBlock) void k_hybrid_sky(FrameParams fp, HybridDev hd, HybridFrameDev fd) {
+// kCube (cubemap_enabled = 1): textureLod(environment, dir * (1, -1, 1), 2) (frag:27-29) instead of IntegrateScattering
+template <bool kCube>
+__global__ __launch_bounds__(kBlock) void k_hybrid_sky(FrameParams fp, HybridDev hd, HybridFrameDev fd, IblMaps ibl) {
    const uint32_t count = *fd.sky_counter;
    const V3 sun = v3(hd.sun_dir[0], hd.sun_dir[1], hd.sun_dir[2]);
    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < count; i += gridDim.x * kBlock) {
       const uint32_t pix = hd.queue[i];
       V3 o, d;
       primary_ray(fp, pix % hd.W, pix / hd.W, 0.5f, 0.5f, o, d);  // origin: inverse_view's translation (extract_camera_position)
-      const V3 c = sky::integrate_scattering(o, d, 999999999.0f, sun);                          // frag:19-32
+      const V3 c = kCube ? ibl::cube_lod(ibl.env, v3(d.x, -d.y, d.z), 2.0f)                     // frag:27-29
+                         : sky::integrate_scattering(o, d, 999999999.0f, sun);                  // frag:19-32
       fd.deferred[pix] = make_float4(c.x, c.y, c.z, 1.0f);                                      // frag:35
    }
 }
@@ -3053,11 +3077,19 @@ void launch_hybrid_ssao(const LaunchCfg& c, const HybridDev& hd, const HybridFra
 }
 void launch_hybrid_deferred(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd, const HybridFrameDev& fd) {
    k_hybrid_light_prep<<<(fd.num_lights + 1 + 255) / 256, 256, 0, c.stream>>>(fd);
-   k_hybrid_deferred<<<one_lane_per_pixel(hd), kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, fd.num_lights + 1);
+   k_hybrid_deferred<false><<<one_lane_per_pixel(hd), kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, fd.num_lights + 1, IblMaps{});
+}
+void launch_hybrid_deferred_ibl(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd, const HybridFrameDev& fd, const IblMaps& ibl) {
+   k_hybrid_light_prep<<<(fd.num_lights + 1 + 255) / 256, 256, 0, c.stream>>>(fd);
+   k_hybrid_deferred<true><<<one_lane_per_pixel(hd), kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, fd.num_lights + 1, ibl);
 }
 void launch_hybrid_sky(const LaunchCfg& c, const FrameParams& fp, const HybridDev& hd, const HybridFrameDev& fd) {
    k_hybrid_sky_classify<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(hd, fd);
-   k_hybrid_sky<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(fp, hd, fd);
+   k_hybrid_sky<false><<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(fp, hd, fd, IblMaps{});
+}
+void launch_hybrid_sky_cube(const LaunchCfg& c, const FrameParams& fp, const HybridDev& hd, const HybridFrameDev& fd, const IblMaps& ibl) {
+   k_hybrid_sky_classify<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(hd, fd);
+   k_hybrid_sky<true><<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(fp, hd, fd, ibl);
 }
 void launch_hybrid_present(const LaunchCfg& c, const HybridDev& hd, const HybridFrameDev& fd) {
    k_hybrid_present<<<one_lane_per_pixel(hd), kBlock, 0, c.stream>>>(hd, fd);

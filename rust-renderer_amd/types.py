@@ -196,3 +196,19 @@ class HybridFrameStats(C.Structure):
 
 
 assert C.sizeof(HybridFrameStats) == 48 and HybridFrameStats.sky_pixels.offset == 28 and HybridFrameStats.lights.offset == 32
+
+
+# image-based lighting: setup_cubemap_pass (ibl.rs) - the environment, irradiance and specular cubes and the BRDF LUT
+HYBRID_ENVIRONMENT = 1 << 7
+ENV_SIZE, ENV_MIPS, BRDF_LUT_SIZE = 512, 8, 512
+ENV_ENVIRONMENT, ENV_IRRADIANCE, ENV_SPECULAR, ENV_BRDF_LUT = range(4)
+
+
+class EnvironmentStats(C.Structure):
+    """UhEnvironmentStats: the last UH_HYBRID_ENVIRONMENT build - hipEvent ms of its sub-passes (environment, irradiance, specular,
+    BRDF LUT), the builds so far, and the sun direction (as given) and eye the maps were built with"""
+
+    _fields_ = [("pass_ms", C.c_float * 4), ("builds", C.c_uint32), ("sun_dir", C.c_float * 3), ("eye", C.c_float * 3), ("reserved", C.c_uint32 * 5)]
+
+
+assert C.sizeof(EnvironmentStats) == 64 and EnvironmentStats.builds.offset == 16 and EnvironmentStats.sun_dir.offset == 20 and EnvironmentStats.eye.offset == 32
