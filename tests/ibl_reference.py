@@ -173,11 +173,15 @@ def lut_bilinear(lut, u, v):
 
 
 # ---- brdf.glsl --------------------------------------------------------------------------------------------------------------------
-def random2(cx, cy):
-    """random(co): mod(x, y) = x - y * floor(x / y); numpy's float32 sin where the device uses sinf"""
+def random2(cx, cy, sin_ulps=0):
+    """random(co): mod(x, y) = x - y * floor(x / y); numpy's float32 sin where the device uses sinf. sin_ulps moves the sine by that many
+    float32 ulps (the device's sinf may round the other way)"""
     dt = np.asarray(cx, np.float32) * F(12.9898) + np.asarray(cy, np.float32) * F(78.233)
     sn = dt - F(3.14) * np.floor(dt / F(3.14))
-    r = np.sin(sn).astype(np.float32) * F(43758.5453)
+    s = np.sin(sn).astype(np.float32)
+    for _ in range(abs(sin_ulps)):
+        s = np.nextafter(s, F(np.inf) if sin_ulps > 0 else F(-np.inf)).astype(np.float32)
+    r = s * F(43758.5453)
     return r - np.floor(r)
 
 
@@ -243,12 +247,12 @@ def irradiance(env0, f, i, j, taps=None):
     return (PI * acc) * (F(1.0) / F(len(taps)))
 
 
-def specular(env_levels, m, f, i, j):
-    """specular_filter.frag (prefilterEnvMap(N, m / 7), envMapDim 512) at texels (i, j) of face f of mip m: (N, 3)"""
+def specular(env_levels, m, f, i, j, sin_ulps=0):
+    """specular_filter.frag (prefilterEnvMap(N, m / 7), envMapDim 512) at texels (i, j) of face f of mip m: (N, 3); sin_ulps: random2's"""
     rough = F(m) / F(MIPS - 1)
     N = texel_dir(f, i, j, SIZE >> m)
     V = N
-    rnd = random2(N[:, 0], N[:, 2])
+    rnd = random2(N[:, 0], N[:, 2], sin_ulps)
     alpha = rough * rough
     alpha2 = alpha * alpha
     dim = F(SIZE)
