@@ -66,6 +66,12 @@ struct DevBuf {
 
 }  // namespace
 
+// the hybrid graph's stages (uh_ctx::Hybrid::stage): its seven passes in the order of their UH_HYBRID_* bits, then the environment's
+enum HybridStage : int {
+   kStShadows, kStGbuffer, kStReflections, kStSsao, kStDeferred, kStSky, kStPresent, kHybridPasses,
+   kStEnvCube = kHybridPasses, kStEnvIrradiance, kStEnvSpecular, kStEnvLut, kHybridStages
+};
+
 // One frame in flight: its own stream pair, hazard events, path state and queue control block.
 // Frames of the path-tracing pass are independent except for the order of the accumulation
 // read-modify-write (reference.rgen:131-143), so up to `frames_in_flight` of them overlap on the
@@ -324,8 +330,12 @@ struct uh_ctx {
       DevBuf<uint32_t> indices;
       uint64_t geom = 0;                       // geom_version the mesh tables were made for
       hipEvent_t waits[2 * kMaxSlots + 1] = {};  // behind the frames in flight
-      hipEvent_t ev[9] = {};                   // pass boundaries of the last call, in pass order (timing); [8]: rt_reflections' start
-      bool ran[3] = {false, false, false};     // G-buffer, rt_shadows, rt_reflections in the last call
+      // one record per stage: stage k < kHybridPasses is bit k of UH_HYBRID_* (rt_shadows, G-buffer, rt_reflections, SSAO, deferred,
+      // sky, present: the last call's), the environment's sub-passes follow (cube, irradiance, specular, BRDF LUT: the last build's)
+      struct Stage {
+         hipEvent_t begin = nullptr, end = nullptr;
+         bool ran = false;
+      } stage[kHybridStages];
       // the final frame's passes (SSAO, deferred, sky, present), allocated by the first call that asks for one of them
       DevBuf<uint16_t> ssao;
       DevBuf<float4> deferred;
@@ -334,15 +344,26 @@ struct uh_ctx {
       DevBuf<UhGpuLight> raw_lights;           // the uh_add_light table as added
       DevBuf<HybridLight> lights;              // its records as the deferred pass reads them, the sun first
       size_t lights_uploaded = SIZE_MAX;       // c->lights.size() when raw_lights was uploaded
-      bool frame_ran[4] = {false, false, false, false};  // SSAO, deferred, sky, present in the last call
       uint32_t frame_lights = 0;               // lights the deferred pass of the last call evaluated (the sun included)
       // the IBL maps of setup_cubemap_pass (UH_HYBRID_ENVIRONMENT), allocated by the first call that builds them
       DevBuf<float4> env, irr, spec;
       DevBuf<uint32_t> lut;
       DevBuf<float4> taps;                     // the irradiance filter's tap table
-      hipEvent_t env_ev[5] = {};               // sub-pass boundaries of the last build (environment, irradiance, specular, LUT)
       uint32_t env_builds = 0;
       float env_sun[3] = {0, 0, 0}, env_eye[3] = {0, 0, 0};  // what the last build was made with
+
+      // the three groups allocated on first use, each named once for allocation and uh_destroy: f(buffer, length), n pixels; a
+      // group's last buffer is allocated last, its pointer says "allocated"
+      template <class F> void rt_images(size_t n, F&& f) {
+         f(pos, n), f(nrm, n), f(pbr, n), f(alb, n), f(refl, n), f(shadow, n), f(queue, n), f(counter, 1);
+      }
+      template <class F> void frame_images(size_t n, F&& f) {
+         f(ssao, n), f(deferred, n), f(present, n), f(lights, UH_MAX_GPU_LIGHTS + 1), f(sky_counter, 1);
+      }
+      template <class F> void env_maps(F&& f) {
+         const size_t cube = env_mip_offset(kEnvMips);
+         f(env, cube), f(irr, 6 * (size_t)kEnvSize * kEnvSize), f(spec, cube), f(lut, (size_t)kLutSize * kLutSize);
+      }
    } hy;
 };
 
@@ -597,32 +618,20 @@ void uh_destroy(uh_ctx* c) {
    c->dstats.release();
    {  // (its events were recorded on the slots' streams: they go first)
       uh_ctx::Hybrid& h = c->hy;
-      for (auto* b : {&h.pos, &h.nrm, &h.pbr}) b->release();
-      h.alb.release();
-      h.refl.release();
-      h.shadow.release();
-      h.queue.release();
-      h.counter.release();
+      const auto release = [](auto& b, size_t) { b.release(); };
+      h.rt_images(0, release);
+      h.frame_images(0, release);
+      h.env_maps(release);
       h.meshes.release();
       h.vertices.release();
       h.indices.release();
-      h.ssao.release();
-      h.deferred.release();
-      h.present.release();
-      h.sky_counter.release();
       h.raw_lights.release();
-      h.lights.release();
-      h.env.release();
-      h.irr.release();
-      h.spec.release();
-      h.lut.release();
       h.taps.release();
       for (hipEvent_t ev : h.waits)
          if (ev) (void)hipEventDestroy(ev);
-      for (hipEvent_t ev : h.ev)
-         if (ev) (void)hipEventDestroy(ev);
-      for (hipEvent_t ev : h.env_ev)
-         if (ev) (void)hipEventDestroy(ev);
+      for (const auto& st : h.stage)
+         for (hipEvent_t ev : {st.begin, st.end})
+            if (ev) (void)hipEventDestroy(ev);
    }
    for (auto& s : c->slots) s.destroy();
    for (hipEvent_t ev : c->ev_band)
@@ -2569,23 +2578,27 @@ int uh_read_mesh(uh_ctx* c, uint32_t mesh_index, UhVertex* vertices, uint32_t* i
 }
 
 // ---- the hybrid graph's ray-traced passes (utopian_hip.h "uh_render_hybrid") ----
+// allocates one of uh_ctx::Hybrid's groups, visit(f) naming its buffers; stops at the first error, before the group's last buffer
+extern "C++" template <class Visit> static int alloc_group(uh_ctx* c, Visit visit) {
+   hipError_t e = hipSuccess;
+   visit([&e](auto& b, size_t n) {
+      if (e == hipSuccess) e = b.alloc(n);
+   });
+   if (e != hipSuccess)
+      return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string("uh_render_hybrid: allocation: ") + hipGetErrorString(e));
+   return UH_OK;
+}
+
+// the ray-traced images and the events (first call)
 static int hybrid_alloc(uh_ctx* c) {
    uh_ctx::Hybrid& h = c->hy;
    if (h.counter.p) return UH_OK;
-   const size_t n = (size_t)c->W * c->H;
-   HIP_TRY(c, h.pos.alloc(n));
-   HIP_TRY(c, h.nrm.alloc(n));
-   HIP_TRY(c, h.pbr.alloc(n));
-   HIP_TRY(c, h.alb.alloc(n));
-   HIP_TRY(c, h.refl.alloc(n));
-   HIP_TRY(c, h.shadow.alloc(n));
-   HIP_TRY(c, h.queue.alloc(n));
    for (hipEvent_t& ev : h.waits)
       if (!ev) HIP_TRY(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-   for (hipEvent_t& ev : h.ev)
-      if (!ev) HIP_TRY(c, hipEventCreate(&ev));
-   HIP_TRY(c, h.counter.alloc(1));  // last: its pointer says "allocated"
-   return UH_OK;
+   for (auto& st : h.stage)
+      for (hipEvent_t* ev : {&st.begin, &st.end})
+         if (!*ev) HIP_TRY(c, hipEventCreate(ev));
+   return alloc_group(c, [&](auto f) { h.rt_images((size_t)c->W * c->H, f); });
 }
 
 // the meshes as the vertex and fragment shaders read them: vertices, indices, the instance's world matrix and the material's maps
@@ -2634,13 +2647,7 @@ static int hybrid_tables(uh_ctx* c) {
 static int hybrid_frame_alloc(uh_ctx* c) {
    uh_ctx::Hybrid& h = c->hy;
    if (h.sky_counter.p) return UH_OK;
-   const size_t n = (size_t)c->W * c->H;
-   HIP_TRY(c, h.ssao.alloc(n));
-   HIP_TRY(c, h.deferred.alloc(n));
-   HIP_TRY(c, h.present.alloc(n));
-   HIP_TRY(c, h.lights.alloc(UH_MAX_GPU_LIGHTS + 1));
-   HIP_TRY(c, h.sky_counter.alloc(1));  // last: its pointer says "allocated"
-   return UH_OK;
+   return alloc_group(c, [&](auto f) { h.frame_images((size_t)c->W * c->H, f); });
 }
 
 // the uh_add_light table as the deferred pass reads it (lights are only ever appended: the count says whether it changed)
@@ -2672,17 +2679,10 @@ static int env_alloc(uh_ctx* c) {
       }
    }
    if (taps.size() != (size_t)kIrrPhi * kIrrTheta) return fail(c, UH_ERR_HIP, "irradiance tap count");
-   const size_t cube = env_mip_offset(kEnvMips);
-   HIP_TRY(c, h.env.alloc(cube));
-   HIP_TRY(c, h.irr.alloc(6 * (size_t)kEnvSize * kEnvSize));
-   HIP_TRY(c, h.spec.alloc(cube));
    HIP_TRY(c, h.taps.alloc(taps.size()));
    HIP_TRY(c, hipMemcpyAsync(h.taps.p, taps.data(), taps.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
    HIP_TRY(c, hipStreamSynchronize(c->stream));
-   for (hipEvent_t& ev : h.env_ev)
-      if (!ev) HIP_TRY(c, hipEventCreate(&ev));
-   HIP_TRY(c, h.lut.alloc((size_t)kLutSize * kLutSize));  // last: its pointer says "allocated"
-   return UH_OK;
+   return alloc_group(c, [&](auto f) { h.env_maps(f); });
 }
 
 int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
@@ -2791,75 +2791,71 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    std::memcpy(mats + 16, fp.inv_proj, sizeof(float) * 16);
    const bool grid = c->cam_grid_enabled && c->cam_valid && c->cam_geom == c->geom_version && std::memcmp(mats, c->cam_mats, sizeof(mats)) == 0;
    const bool rt = view->raytracing_supported != 0;
-   h.ran[0] = (mask & UH_HYBRID_GBUFFER) != 0;
-   h.ran[1] = rt && (mask & UH_HYBRID_RT_SHADOWS);
-   h.ran[2] = rt && (mask & UH_HYBRID_RT_REFLECTIONS);
+   // every stage this call runs between its two events; the passes that do not run report 0, the environment's last build stays
+   for (int k = 0; k < kHybridPasses; k++) h.stage[k].ran = false;
+   const auto begin = [&](int k) {
+      h.stage[k].ran = true;
+      return hipEventRecord(h.stage[k].begin, c->stream);
+   };
+   const auto end = [&](int k) { return hipEventRecord(h.stage[k].end, c->stream); };
    // pass order of build_render_graph (mod.rs:100-134, graph.rs:743): rt_shadows, gbuffer, rt_reflections
-   HIP_TRY(c, hipEventRecord(h.ev[0], c->stream));
-   if (h.ran[1]) launch_hybrid_shadows(lc, c->scene, hd);
-   HIP_TRY(c, hipEventRecord(h.ev[1], c->stream));
-   if (h.ran[0]) launch_hybrid_gbuffer(lc, fp, c->scene, hd, grid ? &c->cam_dev : nullptr);
-   HIP_TRY(c, hipEventRecord(h.ev[2], c->stream));
+   if (rt && (mask & UH_HYBRID_RT_SHADOWS)) {
+      HIP_TRY(c, begin(kStShadows));
+      launch_hybrid_shadows(lc, c->scene, hd);
+      HIP_TRY(c, end(kStShadows));
+   }
+   if (mask & UH_HYBRID_GBUFFER) {
+      HIP_TRY(c, begin(kStGbuffer));
+      launch_hybrid_gbuffer(lc, fp, c->scene, hd, grid ? &c->cam_dev : nullptr);
+      HIP_TRY(c, end(kStGbuffer));
+   }
    // setup_cubemap_pass (mod.rs:121): after the G-buffer, before rt_reflections; the maps persist until the next build
-   IblMaps ibl{h.env.p, h.irr.p, h.spec.p, h.lut.p};
+   const IblMaps ibl{h.env.p, h.irr.p, h.spec.p, h.lut.p};
    if (mask & UH_HYBRID_ENVIRONMENT) {
-      EnvDev e{};
-      e.env = h.env.p;
-      e.irr = h.irr.p;
-      e.spec = h.spec.p;
-      e.lut = h.lut.p;
-      e.taps = h.taps.p;
+      EnvDev e{h.env.p, h.irr.p, h.spec.p, h.lut.p, h.taps.p, {}, {}};
       for (int a = 0; a < 3; a++) {
          e.eye[a] = view->inverse_view[12 + a];  // extract_camera_position(view.view): inverse(view)[3]
          e.sun[a] = view->sun_dir[a];
          h.env_eye[a] = e.eye[a];
          h.env_sun[a] = e.sun[a];
       }
-      HIP_TRY(c, hipEventRecord(h.env_ev[0], c->stream));
-      launch_env_cube(lc, e);
-      HIP_TRY(c, hipEventRecord(h.env_ev[1], c->stream));
-      launch_env_irradiance(lc, e);
-      HIP_TRY(c, hipEventRecord(h.env_ev[2], c->stream));
-      launch_env_specular(lc, e);
-      HIP_TRY(c, hipEventRecord(h.env_ev[3], c->stream));
-      launch_env_brdf_lut(lc, e);
-      HIP_TRY(c, hipEventRecord(h.env_ev[4], c->stream));
+      void (*const build[4])(const LaunchCfg&, const EnvDev&) = {launch_env_cube, launch_env_irradiance, launch_env_specular, launch_env_brdf_lut};
+      for (int k = 0; k < 4; k++) {
+         HIP_TRY(c, begin(kStEnvCube + k));
+         build[k](lc, e);
+         HIP_TRY(c, end(kStEnvCube + k));
+      }
       h.env_builds++;
    }
-   HIP_TRY(c, hipEventRecord(h.ev[8], c->stream));
-   if (h.ran[2]) {
+   if (rt && (mask & UH_HYBRID_RT_REFLECTIONS)) {
+      HIP_TRY(c, begin(kStReflections));
       HIP_TRY(c, hipMemsetAsync(h.counter.p, 0, sizeof(uint32_t), c->stream));
-      if (view->ibl_enabled == 1)
-         launch_hybrid_reflections_ibl(lc, c->scene, hd, ibl);
-      else
-         launch_hybrid_reflections(lc, c->scene, hd);
+      launch_hybrid_reflections(lc, c->scene, hd, view->ibl_enabled == 1 ? &ibl : nullptr);
+      HIP_TRY(c, end(kStReflections));
    }
-   HIP_TRY(c, hipEventRecord(h.ev[3], c->stream));
    // the final frame (mod.rs:136-186): ssao_pass (not with ssao_enabled != 1, ssao.rs:27), deferred_pass, atmosphere_pass, present_pass
-   h.frame_ran[0] = (mask & UH_HYBRID_SSAO) && view->ssao_enabled == 1;
-   h.frame_ran[1] = (mask & UH_HYBRID_DEFERRED) != 0;
-   h.frame_ran[2] = (mask & UH_HYBRID_SKY) != 0;
-   h.frame_ran[3] = (mask & UH_HYBRID_PRESENT) != 0;
-   h.frame_lights = h.frame_ran[1] ? view->num_lights + 1 : 0;
-   if (h.frame_ran[0]) launch_hybrid_ssao(lc, hd, fd);
-   HIP_TRY(c, hipEventRecord(h.ev[4], c->stream));
-   if (h.frame_ran[1]) {
-      if (view->ibl_enabled == 1)
-         launch_hybrid_deferred_ibl(lc, c->scene, hd, fd, ibl);
-      else
-         launch_hybrid_deferred(lc, c->scene, hd, fd);
+   if ((mask & UH_HYBRID_SSAO) && view->ssao_enabled == 1) {
+      HIP_TRY(c, begin(kStSsao));
+      launch_hybrid_ssao(lc, hd, fd);
+      HIP_TRY(c, end(kStSsao));
    }
-   HIP_TRY(c, hipEventRecord(h.ev[5], c->stream));
-   if (h.frame_ran[2]) {
+   if (mask & UH_HYBRID_DEFERRED) {
+      HIP_TRY(c, begin(kStDeferred));
+      launch_hybrid_deferred(lc, c->scene, hd, fd, view->ibl_enabled == 1 ? &ibl : nullptr);
+      HIP_TRY(c, end(kStDeferred));
+   }
+   h.frame_lights = h.stage[kStDeferred].ran ? view->num_lights + 1 : 0;
+   if (mask & UH_HYBRID_SKY) {
+      HIP_TRY(c, begin(kStSky));
       HIP_TRY(c, hipMemsetAsync(h.sky_counter.p, 0, sizeof(uint32_t), c->stream));
-      if (view->cubemap_enabled == 1)
-         launch_hybrid_sky_cube(lc, fp, hd, fd, ibl);
-      else
-         launch_hybrid_sky(lc, fp, hd, fd);
+      launch_hybrid_sky(lc, fp, hd, fd, view->cubemap_enabled == 1 ? &ibl : nullptr);
+      HIP_TRY(c, end(kStSky));
    }
-   HIP_TRY(c, hipEventRecord(h.ev[6], c->stream));
-   if (h.frame_ran[3]) launch_hybrid_present(lc, hd, fd);
-   HIP_TRY(c, hipEventRecord(h.ev[7], c->stream));
+   if (mask & UH_HYBRID_PRESENT) {
+      HIP_TRY(c, begin(kStPresent));
+      launch_hybrid_present(lc, hd, fd);
+      HIP_TRY(c, end(kStPresent));
+   }
    HIP_TRY(c, hipGetLastError());
    return UH_OK;
 }
@@ -2868,23 +2864,22 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    const uh_ctx::Hybrid& h = c->hy;
    if (!h.counter.p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid before the first uh_render_hybrid");
-   const size_t n = (size_t)c->W * c->H;
-   switch (which) {
-   case UH_HYBRID_POSITION: return read_back(c, out, h.pos.p, n * sizeof(float4));
-   case UH_HYBRID_NORMAL: return read_back(c, out, h.nrm.p, n * sizeof(float4));
-   case UH_HYBRID_ALBEDO: return read_back(c, out, h.alb.p, n * sizeof(uchar4));
-   case UH_HYBRID_PBR: return read_back(c, out, h.pbr.p, n * sizeof(float4));
-   case UH_HYBRID_SHADOWS: return read_back(c, out, h.shadow.p, n);
-   case UH_HYBRID_REFLECTIONS: return read_back(c, out, h.refl.p, n * sizeof(uchar4));
-   case UH_HYBRID_SSAO_IMAGE:
-   case UH_HYBRID_DEFERRED_OUTPUT:
-   case UH_HYBRID_PRESENT_OUTPUT:
-      if (!h.sky_counter.p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 6..8 before the first call with an SSAO, deferred, sky or present bit");
-      if (which == UH_HYBRID_SSAO_IMAGE) return read_back(c, out, h.ssao.p, n * sizeof(uint16_t));
-      if (which == UH_HYBRID_DEFERRED_OUTPUT) return read_back(c, out, h.deferred.p, n * sizeof(float4));
-      return read_back(c, out, h.present.p, n * sizeof(uchar4));
-   default: return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..8");
-   }
+   if (which < 0 || which > UH_HYBRID_PRESENT_OUTPUT) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..8");
+   if (which >= UH_HYBRID_SSAO_IMAGE && !h.sky_counter.p)
+      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 6..8 before the first call with an SSAO, deferred, sky or present bit");
+   // image k's pixels and its bytes per pixel, in UH_HYBRID_* image order
+   const std::pair<const void*, size_t> img[] = {
+      {h.pos.p, sizeof(float4)}, {h.nrm.p, sizeof(float4)}, {h.alb.p, sizeof(uchar4)}, {h.pbr.p, sizeof(float4)}, {h.shadow.p, 1},
+      {h.refl.p, sizeof(uchar4)}, {h.ssao.p, sizeof(uint16_t)}, {h.deferred.p, sizeof(float4)}, {h.present.p, sizeof(uchar4)}};
+   return read_back(c, out, img[which].first, (size_t)c->W * c->H * img[which].second);
+}
+
+// stage k's time in the last call (an environment stage: build) that ran it, 0 when that did not
+static int stage_ms(uh_ctx* c, int k, float* out) {
+   const uh_ctx::Hybrid::Stage& st = c->hy.stage[k];
+   *out = 0.0f;
+   if (st.ran) HIP_TRY(c, hipEventElapsedTime(out, st.begin, st.end));
+   return UH_OK;
 }
 
 int uh_get_hybrid_frame_stats(uh_ctx* c, UhHybridFrameStats* out) {
@@ -2895,13 +2890,9 @@ int uh_get_hybrid_frame_stats(uh_ctx* c, UhHybridFrameStats* out) {
    if (!h.counter.p) return UH_OK;
    HIP_TRY(c, hipSetDevice(c->device));
    if (int st = sync_all(c)) return st;
-   const bool ran[7] = {h.ran[1], h.ran[0], h.ran[2], h.frame_ran[0], h.frame_ran[1], h.frame_ran[2], h.frame_ran[3]};
-   for (int k = 0; k < 7; k++) {
-      float ms = 0.0f;
-      if (ran[k]) HIP_TRY(c, hipEventElapsedTime(&ms, h.ev[k == 2 ? 8 : k], h.ev[k + 1]));  // pass k between events k (rt_reflections: 8) and k + 1
-      out->pass_ms[k] = ms;
-   }
-   if (h.frame_ran[2]) HIP_TRY(c, hipMemcpy(&out->sky_pixels, h.sky_counter.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+   for (int k = 0; k < kHybridPasses; k++)
+      if (int st = stage_ms(c, k, &out->pass_ms[k])) return st;
+   if (h.stage[kStSky].ran) HIP_TRY(c, hipMemcpy(&out->sky_pixels, h.sky_counter.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
    out->lights = h.frame_lights;
    return UH_OK;
 }
@@ -2930,7 +2921,8 @@ int uh_get_environment_stats(uh_ctx* c, UhEnvironmentStats* out) {
    if (h.env_builds == 0) return UH_OK;
    HIP_TRY(c, hipSetDevice(c->device));
    if (int st = sync_all(c)) return st;
-   for (int k = 0; k < 4; k++) HIP_TRY(c, hipEventElapsedTime(&out->pass_ms[k], h.env_ev[k], h.env_ev[k + 1]));
+   for (int k = 0; k < 4; k++)
+      if (int st = stage_ms(c, kStEnvCube + k, &out->pass_ms[k])) return st;
    out->builds = h.env_builds;
    std::memcpy(out->sun_dir, h.env_sun, sizeof(out->sun_dir));
    std::memcpy(out->eye, h.env_eye, sizeof(out->eye));
@@ -2946,18 +2938,15 @@ int uh_get_hybrid_stats(uh_ctx* c, UhHybridStats* out) {
    HIP_TRY(c, hipSetDevice(c->device));
    if (int st = sync_all(c)) return st;
    uint32_t metal = 0;
-   if (h.ran[2]) HIP_TRY(c, hipMemcpy(&metal, h.counter.p, sizeof(metal), hipMemcpyDeviceToHost));
+   if (h.stage[kStReflections].ran) HIP_TRY(c, hipMemcpy(&metal, h.counter.p, sizeof(metal), hipMemcpyDeviceToHost));
    const uint64_t n = (uint64_t)c->W * c->H;
-   out->rays[0] = h.ran[0] ? n : 0;
-   out->rays[1] = h.ran[1] ? n : 0;
+   out->rays[0] = h.stage[kStGbuffer].ran ? n : 0;
+   out->rays[1] = h.stage[kStShadows].ran ? n : 0;
    out->rays[2] = metal;
    out->reflection_pixels = metal;
-   const int from[3] = {1, 0, 8}, to[3] = {2, 1, 3};  // G-buffer between events 1 and 2, rt_shadows 0 and 1, rt_reflections 8 and 3
-   for (int k = 0; k < 3; k++) {
-      float ms = 0.0f;
-      if (h.ran[k]) HIP_TRY(c, hipEventElapsedTime(&ms, h.ev[from[k]], h.ev[to[k]]));
-      out->pass_ms[k] = ms;
-   }
+   const int stages[3] = {kStGbuffer, kStShadows, kStReflections};  // the header's order
+   for (int k = 0; k < 3; k++)
+      if (int st = stage_ms(c, stages[k], &out->pass_ms[k])) return st;
    return UH_OK;
 }
 

@@ -286,11 +286,8 @@ void launch_hybrid_clear(const LaunchCfg&, const HybridDev&);
 // records live in the targets themselves until the resolve (ray_o = normal, ray_d = pbr, hit = position target)
 void launch_hybrid_gbuffer(const LaunchCfg&, const FrameParams&, const SceneDev&, const HybridDev&, const SunGridDev* camera_grid);
 void launch_hybrid_shadows(const LaunchCfg&, const SceneDev&, const HybridDev&);
-void launch_hybrid_reflections(const LaunchCfg&, const SceneDev&, const HybridDev&);
 void launch_hybrid_frame_clear(const LaunchCfg&, const HybridDev&, const HybridFrameDev&);
 void launch_hybrid_ssao(const LaunchCfg&, const HybridDev&, const HybridFrameDev&);
-void launch_hybrid_deferred(const LaunchCfg&, const SceneDev&, const HybridDev&, const HybridFrameDev&);
-void launch_hybrid_sky(const LaunchCfg&, const FrameParams&, const HybridDev&, const HybridFrameDev&);
 void launch_hybrid_present(const LaunchCfg&, const HybridDev&, const HybridFrameDev&);
 // image-based lighting (setup_cubemap_pass, ibl.rs; ibl.hip): the four maps and their consumers
 constexpr uint32_t kEnvSize = 512, kEnvMips = 8, kLutSize = 512;
@@ -321,9 +318,10 @@ void launch_env_cube(const LaunchCfg&, const EnvDev&);
 void launch_env_irradiance(const LaunchCfg&, const EnvDev&);
 void launch_env_specular(const LaunchCfg&, const EnvDev&);
 void launch_env_brdf_lut(const LaunchCfg&, const EnvDev&);
-void launch_hybrid_deferred_ibl(const LaunchCfg&, const SceneDev&, const HybridDev&, const HybridFrameDev&, const IblMaps&);
-void launch_hybrid_sky_cube(const LaunchCfg&, const FrameParams&, const HybridDev&, const HybridFrameDev&, const IblMaps&);
-void launch_hybrid_reflections_ibl(const LaunchCfg&, const SceneDev&, const HybridDev&, const IblMaps&);
+// the passes with an IBL branch: nullptr for the non-IBL one (the sky's: the environment cube, or IntegrateScattering)
+void launch_hybrid_reflections(const LaunchCfg&, const SceneDev&, const HybridDev&, const IblMaps* ibl);
+void launch_hybrid_deferred(const LaunchCfg&, const SceneDev&, const HybridDev&, const HybridFrameDev&, const IblMaps* ibl);
+void launch_hybrid_sky(const LaunchCfg&, const FrameParams&, const HybridDev&, const HybridFrameDev&, const IblMaps* cube);
 // tiles
 // on-device refit (refit.hip): per-mesh object->world rows, and what one refit pass touches
 struct RefitMesh {

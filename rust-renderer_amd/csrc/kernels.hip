@@ -2728,13 +2728,12 @@ void launch_hybrid_shadows(const LaunchCfg& c, const SceneDev& sc, const HybridD
    const uint32_t full = c.num_cus * c.shadow_blocks_per_cu, need = (hd.W * hd.H + kBlock - 1) / kBlock;
    k_hybrid_shadow<<<dim3(need < full ? need : full), kBlock, 0, c.stream>>>(sc, hd);
 }
-void launch_hybrid_reflections(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd) {
+void launch_hybrid_reflections(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd, const IblMaps* ibl) {
    k_hybrid_reflect_classify<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(sc, hd);
-   k_hybrid_reflect<false><<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(sc, hd, IblMaps{});
-}
-void launch_hybrid_reflections_ibl(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd, const IblMaps& ibl) {
-   k_hybrid_reflect_classify<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(sc, hd);
-   k_hybrid_reflect<true><<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(sc, hd, ibl);
+   if (!ibl)
+      k_hybrid_reflect<false><<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(sc, hd, IblMaps{});
+   else
+      k_hybrid_reflect<true><<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(sc, hd, *ibl);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3075,21 +3074,19 @@ static inline dim3 one_lane_per_pixel(const HybridDev& hd) { return dim3((hd.W *
 void launch_hybrid_ssao(const LaunchCfg& c, const HybridDev& hd, const HybridFrameDev& fd) {
    k_hybrid_ssao<<<one_lane_per_pixel(hd), kBlock, 0, c.stream>>>(hd, fd);
 }
-void launch_hybrid_deferred(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd, const HybridFrameDev& fd) {
+void launch_hybrid_deferred(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd, const HybridFrameDev& fd, const IblMaps* ibl) {
    k_hybrid_light_prep<<<(fd.num_lights + 1 + 255) / 256, 256, 0, c.stream>>>(fd);
-   k_hybrid_deferred<false><<<one_lane_per_pixel(hd), kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, fd.num_lights + 1, IblMaps{});
+   if (!ibl)
+      k_hybrid_deferred<false><<<one_lane_per_pixel(hd), kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, fd.num_lights + 1, IblMaps{});
+   else
+      k_hybrid_deferred<true><<<one_lane_per_pixel(hd), kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, fd.num_lights + 1, *ibl);
 }
-void launch_hybrid_deferred_ibl(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd, const HybridFrameDev& fd, const IblMaps& ibl) {
-   k_hybrid_light_prep<<<(fd.num_lights + 1 + 255) / 256, 256, 0, c.stream>>>(fd);
-   k_hybrid_deferred<true><<<one_lane_per_pixel(hd), kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, fd.num_lights + 1, ibl);
-}
-void launch_hybrid_sky(const LaunchCfg& c, const FrameParams& fp, const HybridDev& hd, const HybridFrameDev& fd) {
+void launch_hybrid_sky(const LaunchCfg& c, const FrameParams& fp, const HybridDev& hd, const HybridFrameDev& fd, const IblMaps* cube) {
    k_hybrid_sky_classify<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(hd, fd);
-   k_hybrid_sky<false><<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(fp, hd, fd, IblMaps{});
-}
-void launch_hybrid_sky_cube(const LaunchCfg& c, const FrameParams& fp, const HybridDev& hd, const HybridFrameDev& fd, const IblMaps& ibl) {
-   k_hybrid_sky_classify<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(hd, fd);
-   k_hybrid_sky<true><<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(fp, hd, fd, ibl);
+   if (!cube)
+      k_hybrid_sky<false><<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(fp, hd, fd, IblMaps{});
+   else
+      k_hybrid_sky<true><<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(fp, hd, fd, *cube);
 }
 void launch_hybrid_present(const LaunchCfg& c, const HybridDev& hd, const HybridFrameDev& fd) {
    k_hybrid_present<<<one_lane_per_pixel(hd), kBlock, 0, c.stream>>>(hd, fd);

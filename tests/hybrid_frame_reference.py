@@ -22,26 +22,6 @@ SSAO_KERNEL = np.array([
     (0.38629, 0.15627, 0.56716), (0.06649, -0.05762, 0.0857), (-0.1065, -0.11726, 0.10818), (0.53236, -0.5286, 0.45444)], dtype=np.float32)
 
 
-def upload_recorded(scene, renderer, defaults=True):
-    """hybrid_reference.upload_recorded plus each mesh's metallic / roughness factors, which the deferred pass reads"""
-    factors = []
-    add = renderer.add_mesh
-
-    def add_mesh(vertices, indices, material, world3x4=None):
-        factors.append((F(material.metallic_factor), F(material.roughness_factor)))
-        return add(vertices, indices, material, world3x4)
-
-    renderer.add_mesh = add_mesh
-    try:
-        meshes = hr.upload_recorded(scene, renderer, defaults)
-    finally:
-        if "add_mesh" in vars(renderer):
-            del renderer.add_mesh
-    for m, (mf, rf) in zip(meshes, factors):
-        m["metallic"], m["roughness"] = mf, rf
-    return meshes
-
-
 # ---- the shared pieces ---------------------------------------------------------------------------------------------------------
 def mat4_mul(m, p, w):
     """column-major mat4 (m[c*4 + r]) times vec4(p, w): ((c0 x + c1 y) + c2 z) + c3 w, for (N, 3) p"""

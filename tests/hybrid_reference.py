@@ -13,7 +13,8 @@ MISS = 0xFFFFFFFF
 
 def upload_recorded(scene, renderer, defaults=True):
     """scene.upload(renderer) with Renderer.initialize's four default maps first (so every material carries a normal, occlusion and
-    metallic-roughness map), recording what each add_mesh call received: the reference needs the meshes as the shaders read them"""
+    metallic-roughness map), recording what each add_mesh call received: the references need the meshes as the shaders read them (the
+    metallic / roughness factors: the deferred pass)"""
     meshes = []
     add = renderer.add_mesh
 
@@ -22,7 +23,8 @@ def upload_recorded(scene, renderer, defaults=True):
         meshes.append(dict(vertices=np.ascontiguousarray(vertices, dtype=VERTEX_DTYPE), indices=np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1),
                            world=w.copy(), diffuse_map=material.diffuse_map, normal_map=material.normal_map,
                            metallic_roughness_map=material.metallic_roughness_map, occlusion_map=material.occlusion_map,
-                           base_color=np.array(material.base_color_factor[:3], dtype=np.float32), type=float(material.raytrace_properties[0])))
+                           base_color=np.array(material.base_color_factor[:3], dtype=np.float32), type=float(material.raytrace_properties[0]),
+                           metallic=F(material.metallic_factor), roughness=F(material.roughness_factor)))
         return add(vertices, indices, material, world3x4)
 
     renderer.add_mesh = add_mesh

@@ -4,13 +4,13 @@ GPU: frames rendered through Renderer::add_model / build_path_tracing_render_gra
 equal the ctypes path bit for bit."""
 import ctypes as C
 import os
-import struct
 import subprocess
 
 import numpy as np
 import pytest
 
 import rust_renderer_amd as rr
+from util import write_blob
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -24,39 +24,6 @@ def build_cpp(tmp_path):
         check=True,
     )
     return exe
-
-
-def write_blob(path, scene, W, H, frames, pass_mask):
-    view = scene.make_view(W, H)
-    view.num_lights = len(scene.lights)
-    cam = scene.camera
-    with open(path, "wb") as f:
-        f.write(struct.pack("<5I", 0x43534855, W, H, frames, pass_mask))
-        f.write(bytes(view))
-        f.write(struct.pack("<9f", *cam.position, *cam.target, cam.fov_degrees, cam.z_near, cam.z_far))
-        textures, meshes = [], []
-        for model, transform in scene.models:
-            base = len(textures)
-            textures += model.textures
-            for m in model.meshes:
-                w = m.transform if transform is None else rr.api.compose3x4(transform, m.transform)
-                meshes.append((m, base, w))
-        f.write(struct.pack("<I", len(textures)))
-        for t in textures:
-            f.write(struct.pack("<2I", t.shape[1], t.shape[0]))
-            f.write(np.ascontiguousarray(t, dtype=np.uint8).tobytes())
-        f.write(struct.pack("<I", len(meshes)))
-        for m, base, w in meshes:
-            f.write(struct.pack("<2I", len(m.vertices), len(m.indices)))
-            f.write(np.ascontiguousarray(m.vertices).tobytes())
-            f.write(np.ascontiguousarray(m.indices, dtype=np.uint32).tobytes())
-            f.write(struct.pack("<i4fIf", -1 if m.texture is None else base + m.texture, *m.base_color, int(m.material_type), float(m.material_property)))
-            mat4 = np.vstack([np.asarray(w, dtype=np.float32).reshape(3, 4), [0, 0, 0, 1]]).astype(np.float32)
-            f.write(np.ascontiguousarray(mat4.T).tobytes())  # column-major
-        f.write(struct.pack("<I", len(scene.lights)))
-        for p in scene.lights:
-            f.write(struct.pack("<3f", *p))
-    return view
 
 
 @pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="a GPU is present")

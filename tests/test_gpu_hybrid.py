@@ -7,98 +7,12 @@ import pytest
 import hybrid_reference as hr
 import oracle_api as oa
 import rust_renderer_amd as rr
+from hybrid_util import W, H, assert_reflections, assets, bits, gbuf, hybrid_view, pair, scene_named, synthetic_scene  # noqa: F401 (assets is a fixture)
 from rust_renderer_amd.api import UtopianError
-from rust_renderer_amd.scenes import Mesh, Model, Scene, icosphere, procedural_texture, quad
-from test_reference_assets import reference_cornell_scene, reference_spheres_scene
+from rust_renderer_amd.scenes import Mesh, Model, Scene, quad
+from util import reference_spheres_scene
 
 pytestmark = pytest.mark.gpu
-
-W, H = 160, 120
-
-
-@pytest.fixture(scope="module")
-def assets():
-    import os
-
-    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_assets.npz"))
-
-
-def _normal_map(size=32):
-    """a bumpy tangent-space normal map (z dominant), RGBA8"""
-    y, x = np.meshgrid(np.arange(size), np.arange(size), indexing="ij")
-    nx, ny = 0.45 * np.sin(x * 0.7), 0.45 * np.cos(y * 0.5)
-    nz = np.sqrt(np.maximum(1.0 - nx * nx - ny * ny, 0.0))
-    rgba = np.stack([(nx * 0.5 + 0.5) * 255, (ny * 0.5 + 0.5) * 255, (nz * 0.5 + 0.5) * 255, np.full_like(nx, 255)], axis=-1)
-    return np.ascontiguousarray(np.rint(rgba).astype(np.uint8))
-
-
-class SyntheticScene(Scene):
-    """mesh 0: a metal, normal-mapped floor (tangent (1, 0, 0)) - material 0 is metal, so the sky pixels trace too; mesh 1: a
-    Lambertian sphere under a rotated, non-uniformly scaled instance, tangent zero; mesh 2: a normal-mapped box-side quad under another
-    rotation and scale, textured maps everywhere; mesh 3: a metal sphere. The upper rows see the sky."""
-
-    def upload(self, renderer):
-        renderer.default_diffuse_map()
-        tex = [renderer.add_texture(procedural_texture(11, k, 32)) for k in range(4)]
-        nmap = renderer.add_texture(_normal_map())
-
-        def mat(kind, diffuse, normal, base=(1.0, 1.0, 1.0, 1.0)):
-            m = rr.make_material(kind, 0.0, base, diffuse_map=diffuse)
-            m.normal_map, m.metallic_roughness_map, m.occlusion_map = normal, tex[2], tex[3]
-            return m
-
-        fv, fi = quad((-6.0, 0.0, 6.0), (12.0, 0.0, 0.0), (0.0, 0.0, -12.0), nu=6, nv=6, uv_scale=(3.0, 3.0))
-        fv["tangent"][:, :3] = (1.0, 0.0, 0.0)
-        renderer.add_mesh(fv, fi, mat(rr.METAL, tex[0], nmap, (0.9, 0.8, 0.7, 1.0)))
-        sv, si = icosphere(2)
-        rot = np.array([[0.8, -0.6, 0.0], [0.6, 0.8, 0.0], [0.0, 0.0, 1.0]], np.float32)
-        renderer.add_mesh(sv, si, mat(rr.LAMBERTIAN, tex[1], nmap, (0.5, 0.9, 0.4, 1.0)), rr.transform3x4((1.4, 0.6, 0.9), (-1.5, 0.8, 0.0), rot))
-        qv, qi = quad((-1.0, -1.0, 0.0), (2.0, 0.0, 0.0), (0.0, 2.0, 0.0), nu=3, nv=3, uv_scale=(2.0, 2.0))
-        qv["tangent"][:, :3] = (1.0, 0.0, 0.0)
-        rot2 = np.array([[0.0, 0.0, 1.0], [0.0, 1.0, 0.0], [-1.0, 0.0, 0.0]], np.float32) @ np.array([[0.96, 0.0, -0.28], [0.0, 1.0, 0.0], [0.28, 0.0, 0.96]], np.float32)
-        renderer.add_mesh(qv, qi, mat(rr.LAMBERTIAN, tex[2], nmap), rr.transform3x4((1.0, 0.7, 1.6), (2.2, 1.0, -1.0), rot2))
-        renderer.add_mesh(sv, si, mat(rr.METAL, tex[3], nmap), rr.transform3x4((0.7, 0.7, 0.7), (0.6, 0.7, 1.4)))
-        renderer.initialize_raytracing()
-        return renderer
-
-
-def synthetic_scene():
-    cam = rr.camera.Camera((0.0, 2.2, 6.5), (0.0, 0.9, 0.0), 60.0, W / H, 0.01, 1000.0)
-    return SyntheticScene("hybrid_synthetic", [], [], cam, dict(sky_enabled=1))
-
-
-def scene_named(name, assets):
-    return {"cornell": lambda: reference_cornell_scene(assets), "spheres": lambda: reference_spheres_scene(assets), "synthetic": synthetic_scene}[name]()
-
-
-def pair(scene, width=W, height=H):
-    gpu = rr.Renderer(width, height)
-    cpu = oa.OracleRenderer(width, height)
-    meshes = hr.upload_recorded(scene, gpu, defaults=not isinstance(scene, SyntheticScene))
-    hr.upload_recorded(scene, cpu, defaults=not isinstance(scene, SyntheticScene))
-    return gpu, cpu, meshes
-
-
-def hybrid_view(scene, width=W, height=H, **kw):
-    v = scene.make_view(width, height, **kw)
-    v.ibl_enabled = 0  # the reflection pass's non-IBL branch: the IBL maps are not part of the library
-    return v
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def read_gbuffer(r):
-    return {k: r.read_hybrid(i) for k, i in (("position", rr.HYBRID_POSITION), ("normal", rr.HYBRID_NORMAL), ("albedo", rr.HYBRID_ALBEDO), ("pbr", rr.HYBRID_PBR))}
-
-
-def assert_reflections(got, ref, kind):
-    assert np.array_equal(got[kind == 0], ref[kind == 0]) and not got[kind == 0].any(), "non-metal pixels are exactly 0"
-    assert np.array_equal(got[kind == 1], ref[kind == 1]), "pixels whose ray hits are byte-identical"
-    d = np.abs(got[kind == 2].astype(np.int16) - ref[kind == 2].astype(np.int16))
-    assert d.size == 0 or d.max() <= 1, "sky pixels within 1 LSB"
-    assert (got[..., 3] == 0).all()
 
 
 # ---- 1. the G-buffer ------------------------------------------------------------------------------------------------------
@@ -115,7 +29,7 @@ def test_gbuffer_position_is_the_path_tracers_and_the_targets_are_the_references
     # (the library refuses the grid for the spheres view - long per-pixel lists - and the cast walks the tree there)
     assert grid == (bool(camera_grid) and name != "spheres")
     gpu.render_hybrid(view, rr.HYBRID_GBUFFER)
-    got = read_gbuffer(gpu)
+    got = gbuf(gpu)
     assert np.array_equal(bits(got["position"]), bits(gpu.read_gbuffer_position()))
     ref = hr.gbuffer(cpu, meshes, view, W, H)
     for k in ("position", "normal", "pbr"):
@@ -137,7 +51,7 @@ def test_shadows_equal_the_reference_in_every_octant(assets, name):
     gpu, cpu, meshes = pair(scene)
     view = hybrid_view(scene)
     gpu.render_hybrid(view, rr.HYBRID_GBUFFER)
-    g = read_gbuffer(gpu)
+    g = gbuf(gpu)
     for sun in SUNS:
         view.sun_dir[:] = sun
         gpu.render_hybrid(view, rr.HYBRID_RT_SHADOWS)
@@ -170,7 +84,7 @@ def test_reflections_equal_the_reference(assets, name, furnace):
     gpu.set_option("furnace", furnace)
     view = hybrid_view(scene)
     gpu.render_hybrid(view, rr.HYBRID_GBUFFER | rr.HYBRID_RT_REFLECTIONS)
-    g = read_gbuffer(gpu)
+    g = gbuf(gpu)
     got = gpu.read_hybrid(rr.HYBRID_REFLECTIONS)
     ref, kind = hr.reflections(cpu, meshes, g["position"], g["normal"], g["pbr"], view, furnace=bool(furnace))
     assert_reflections(got, ref, kind)
@@ -217,7 +131,7 @@ def test_material_index_is_the_truncated_filtered_alpha():
     gpu, cpu, meshes = pair(scene)
     view = hybrid_view(scene)
     gpu.render_hybrid(view, rr.HYBRID_GBUFFER | rr.HYBRID_RT_REFLECTIONS)
-    g = read_gbuffer(gpu)
+    g = gbuf(gpu)
     filtered = hr.corner(g["pbr"])[..., 3]
     border = filtered == 3.5
     assert border.any() and set(np.unique(filtered)) <= {2.0, 3.5, 5.0}
@@ -236,13 +150,13 @@ def test_pass_order_shadows_read_the_previous_gbuffer(assets):
     gpu.render_hybrid(a, rr.HYBRID_ALL)
     clear = np.tile(np.array([1, 1, 1, 0], np.float32), (H, W, 1))
     assert np.array_equal(gpu.read_hybrid(rr.HYBRID_SHADOWS), hr.shadows(cpu, clear, clear, a)), "the first call reads the clear G-buffer"
-    ga = read_gbuffer(gpu)
+    ga = gbuf(gpu)
     scene.camera = rr.camera.Camera((2.0, 3.0, 5.0), (0.0, 0.5, 0.0), 60.0, W / H, 0.01, 1000.0)
     b = hybrid_view(scene)
     b.sun_dir[:] = a.sun_dir[:]
     gpu.render_hybrid(b, rr.HYBRID_ALL)
     assert np.array_equal(gpu.read_hybrid(rr.HYBRID_SHADOWS), hr.shadows(cpu, ga["position"], ga["normal"], b)), "B's shadows come from A's G-buffer"
-    gb = read_gbuffer(gpu)
+    gb = gbuf(gpu)
     assert not np.array_equal(bits(gb["position"]), bits(ga["position"]))
     ref, kind = hr.reflections(cpu, meshes, gb["position"], gb["normal"], gb["pbr"], b)
     assert_reflections(gpu.read_hybrid(rr.HYBRID_REFLECTIONS), ref, kind)  # reflections: this call's G-buffer

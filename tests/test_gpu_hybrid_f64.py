@@ -7,16 +7,14 @@ import pytest
 
 import hybrid_f64 as hf
 import hybrid_frame_reference as fr
+import hybrid_reference as hr
 import ibl_reference as ir
 import rust_renderer_amd as rr
+from hybrid_util import (CONSUMER_ULP, DEFERRED_ULP, W, H, SyntheticScene, add_lights, assets, frame_view, gbuf, ibl_view, pair,  # noqa: F401
+                         record, scene_named, ulps)
 from rust_renderer_amd.scenes import quad
-from test_gpu_hybrid import SyntheticScene, assets, scene_named  # noqa: F401 (assets is a fixture)
-from test_gpu_hybrid_frame import DEFERRED_ULP, add_lights, frame_view, gbuf, pair, record, ulps
-from test_gpu_ibl import CONSUMER_ULP, ibl_view
 
 pytestmark = pytest.mark.gpu
-
-W, H = 160, 120
 
 
 def check_f64(gpu, view, meshes, lights, maps, name, rows=None):
@@ -45,7 +43,7 @@ def check_f64(gpu, view, meshes, lights, maps, name, rows=None):
     # present (the caller ran with FXAA off)
     _, p64 = hf.present(d)
     lsb = int(np.abs(gpu.read_hybrid(rr.HYBRID_PRESENT_OUTPUT)[sel].astype(int) - p64[sel].astype(int)).max())
-    record(f"f64-{name}", deferred_worst_of_bound=round(ratio, 4), well_max_ulp_of_scale=round(rel(well), 2), peak_pixels=int(peak.sum()),
+    record("hybrid_frame", f"f64-{name}", deferred_worst_of_bound=round(ratio, 4), well_max_ulp_of_scale=round(rel(well), 2), peak_pixels=int(peak.sum()),
            peak_max_ulp_of_scale=round(rel(peak), 2), ssao_outside=outside, ssao_median_width=float(np.median(hi - lo)), present_max_lsb=lsb)
     assert geo.any() and ratio <= 1.0, f"{name}: deferred error {ratio:.3g} x the bound"
     assert outside == 0, f"{name}: {outside} SSAO texels outside the interval"
@@ -74,7 +72,7 @@ def test_1024_lights_at_1080p_against_the_float64_reading_on_sampled_rows(ibl):
     scene = rr.scenes.scene_for_config(1, with_spheres=True)
     Wf, Hf = 1920, 1080
     gpu = rr.Renderer(Wf, Hf)
-    meshes = fr.upload_recorded(scene, gpu, defaults=False)
+    meshes = hr.upload_recorded(scene, gpu, defaults=False)
     lights = add_lights(gpu, 1024, 11, (1, 2))
     v = ibl_view(scene, Wf, Hf, fxaa_enabled=0) if ibl else frame_view(scene, Wf, Hf, fxaa_enabled=0)
     v.num_lights = 1024
@@ -182,6 +180,6 @@ def test_value_edges_against_the_restatement_and_the_float64_reading(ibl):
     fin = np.isfinite(ref[geo])
     assert np.array_equal(np.isfinite(d[geo]), fin), "non-finite patterns"
     u = ulps(d[geo][fin], ref[geo][fin])
-    record(f"edges-ibl{ibl}", restatement_max_ulp=int(u.max()), nonfinite=int((~fin).sum()))
+    record("hybrid_frame", f"edges-ibl{ibl}", restatement_max_ulp=int(u.max()), nonfinite=int((~fin).sum()))
     assert u.max() <= (CONSUMER_ULP if ibl else DEFERRED_ULP), u.max()
     check_f64(gpu, v, meshes, lights, maps, f"edges-ibl{ibl}")

@@ -2,115 +2,19 @@
 tests/hybrid_frame_reference.py, one pass at a time on the device's own input images; the image orientation, the refusals and gates,
 UH_HYBRID_FRAME against the passes one by one, isolation from the path tracer and the ray-traced passes, 1080p and 1,024 lights, and
 the C++ mirror."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import hybrid_frame_reference as fr
 import hybrid_reference as hr
-import oracle_api as oa
 import rust_renderer_amd as rr
+from hybrid_util import (DEFERRED_ULP, W, H, add_lights, assets, check_frame, cpp_scene, cpp_view, frame_view, gbuf, pair, read_all,  # noqa: F401
+                         record, run_cpp, scene_named, synthetic_scene, ulps)
 from rust_renderer_amd.api import UtopianError
 from rust_renderer_amd.scenes import Mesh, Model, Scene, quad
-from test_gpu_hybrid import SyntheticScene, assets, scene_named, synthetic_scene  # noqa: F401 (assets is a fixture)
+from util import reference_spheres_scene
 
 pytestmark = pytest.mark.gpu
-
-W, H = 160, 120
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.environ.get("HYBRID_FRAME_RECORD")  # a directory: the measured ulp bounds and pass times are appended there
-# deferred output against the reference: device powf (spot lights) is not correctly rounded; measured 0 ulp at up to 12 lights,
-# 3 ulp at 1,024 lights (512 spot lights)
-DEFERRED_ULP = 4
-
-
-def frame_view(scene, width=W, height=H, **kw):
-    v = scene.make_view(width, height, **kw)
-    v.shadows_enabled = v.ibl_enabled = v.cubemap_enabled = 0  # the reference's defaults are refused: see utopian_hip.h
-    return v
-
-
-def pair(scene, width=W, height=H):
-    gpu = rr.Renderer(width, height)
-    defaults = not isinstance(scene, SyntheticScene)
-    meshes = fr.upload_recorded(scene, gpu, defaults)
-    cpu = oa.OracleRenderer(width, height)
-    hr.upload_recorded(scene, cpu, defaults)
-    return gpu, cpu, meshes
-
-
-def read_all(r):
-    return {i: r.read_hybrid(i) for i in range(9)}
-
-
-def gbuf(r):
-    return dict(position=r.read_hybrid(rr.HYBRID_POSITION), normal=r.read_hybrid(rr.HYBRID_NORMAL), albedo=r.read_hybrid(rr.HYBRID_ALBEDO),
-                pbr=r.read_hybrid(rr.HYBRID_PBR))
-
-
-def ulps(a, b):
-    """distance in float32 units in the last place (same-sign values; either sign of zero is 0)"""
-    ia, ib = a.view(np.int32).astype(np.int64), b.view(np.int32).astype(np.int64)
-    ia = np.where(ia < 0, -(ia & 0x7FFFFFFF), ia)
-    ib = np.where(ib < 0, -(ib & 0x7FFFFFFF), ib)
-    return np.abs(ia - ib)
-
-
-def record(name, **values):
-    if not OUT:
-        return
-    os.makedirs(OUT, exist_ok=True)
-    with open(os.path.join(OUT, "hybrid_frame_measured.txt"), "a") as f:
-        f.write(f"{name} " + " ".join(f"{k}={v}" for k, v in values.items()) + "\n")
-
-
-def add_lights(gpu, n, seed, kinds=(1, 2)):
-    """n GpuLight records (point, spot, directional or an unknown type, by `kinds`) above the synthetic scene; the renderer's tree is rebuilt"""
-    rng = np.random.default_rng(seed)
-    lights = []
-    for k in range(n):
-        l = rr.make_light(rng.uniform((-4.0, 0.5, -4.0), (4.0, 4.0, 3.0)), color=tuple(rng.uniform(0.2, 1.0, 3)))
-        l.light_type = float(kinds[k % len(kinds)])
-        l.attenuation[:] = (float(rng.uniform(0.5, 1.0)), float(rng.uniform(0.0, 0.3)), float(rng.uniform(0.05, 0.4)))
-        l.direction[:] = tuple(rng.uniform(-1.0, 1.0, 3) + np.array([0.0, -1.5, 0.0]))
-        l.spot = float(rng.uniform(1.0, 16.0))
-        gpu.add_gpu_light(l)
-        lights.append(l)
-    gpu.initialize_raytracing()
-    return lights
-
-
-def check_frame(gpu, cpu, meshes, view, lights, name):
-    """one UH_HYBRID_FRAME call, then each pass against the reference on the device's own inputs"""
-    gpu.render_hybrid(view, rr.HYBRID_FRAME)
-    g = gbuf(gpu)
-    sh, refl = gpu.read_hybrid(rr.HYBRID_SHADOWS), gpu.read_hybrid(rr.HYBRID_REFLECTIONS)
-    ss, d, p = gpu.read_hybrid(rr.HYBRID_SSAO_IMAGE), gpu.read_hybrid(rr.HYBRID_DEFERRED_OUTPUT), gpu.read_hybrid(rr.HYBRID_PRESENT_OUTPUT)
-    # SSAO: exact
-    assert np.array_equal(ss, fr.ssao(g["position"], g["normal"], view)), "ssao"
-    # deferred: the geometry pixels (the sky pass overwrites the others)
-    ref = fr.deferred(g, sh, refl, ss, view, meshes, lights)
-    geo = g["position"][..., 3] == 1.0
-    u = ulps(d[geo], ref[geo])
-    assert geo.any() and np.isfinite(d[geo]).all()
-    record(name, deferred_max_ulp=int(u.max()), deferred_exact=float((u == 0).mean()))
-    assert u.max() <= DEFERRED_ULP, f"deferred: {u.max()} ulp"
-    # sky: within 1 LSB after present's conversion
-    sky = fr.sky(g["position"], view)
-    if sky:
-        ys, xs = np.array(list(sky)).T
-        want = np.array(list(sky.values()), np.float32)
-        got = d[ys, xs, :3]
-        assert (d[ys, xs, 3] == 1.0).all()
-        assert np.abs(hr.unorm8(fr.linear_to_srgb(got)).astype(int) - hr.unorm8(fr.linear_to_srgb(want)).astype(int)).max() <= 1
-        assert np.allclose(got, want, rtol=1e-4, atol=1e-6)
-    # present: exact given the device's deferred output
-    assert np.array_equal(p, fr.present(d, view.fxaa_enabled == 1)), "present"
-    s = gpu.hybrid_frame_stats()
-    assert all(ms > 0 for ms in s.pass_ms) and s.sky_pixels == len(sky) and s.lights == view.num_lights + 1
-    return g, d, p
 
 
 # ---- 1. every pass against the reference -------------------------------------------------------------------------------------
@@ -236,8 +140,6 @@ def test_frame_equals_the_passes_one_by_one():
 # ---- 4. isolation ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("in_flight", [4, 1])
 def test_frame_calls_change_nothing_the_path_tracer_or_the_ray_traced_passes_read(assets, in_flight):
-    from test_reference_assets import reference_spheres_scene
-
     scene = reference_spheres_scene(assets)
 
     def run(with_frame):
@@ -277,7 +179,7 @@ def test_1080p_frame_on_the_config1_scene():
     scene = rr.scenes.scene_for_config(1, with_spheres=True)
     Wf, Hf = 1920, 1080
     gpu = rr.Renderer(Wf, Hf)
-    meshes = fr.upload_recorded(scene, gpu, defaults=False)
+    meshes = hr.upload_recorded(scene, gpu, defaults=False)
     view = frame_view(scene, Wf, Hf)
     view.num_lights = 0
     gpu.render_hybrid(view, rr.HYBRID_GBUFFER)
@@ -293,7 +195,7 @@ def test_1080p_frame_on_the_config1_scene():
     assert ulps(d[rows][geo], ref[geo]).max() <= DEFERRED_ULP
     assert np.array_equal(p, fr.present(d))
     s = gpu.hybrid_frame_stats()
-    record("config1-1080p", **{f"ms{k}": round(s.pass_ms[k], 4) for k in range(7)}, sky=s.sky_pixels)
+    record("hybrid_frame", "config1-1080p", **{f"ms{k}": round(s.pass_ms[k], 4) for k in range(7)}, sky=s.sky_pixels)
     assert all(ms > 0 for ms in s.pass_ms)
 
 
@@ -301,7 +203,7 @@ def test_1024_lights_at_1080p_on_sampled_rows():
     scene = rr.scenes.scene_for_config(1, with_spheres=True)
     Wf, Hf = 1920, 1080
     gpu = rr.Renderer(Wf, Hf)
-    meshes = fr.upload_recorded(scene, gpu, defaults=False)
+    meshes = hr.upload_recorded(scene, gpu, defaults=False)
     lights = add_lights(gpu, 1024, 11, (1, 2))
     view = frame_view(scene, Wf, Hf)
     view.num_lights = 1024
@@ -314,32 +216,17 @@ def test_1024_lights_at_1080p_on_sampled_rows():
     ref = _sampled_deferred(g, sh, refl, ss, view, meshes, lights, rows)
     geo = g["position"][rows][..., 3] == 1.0
     u = ulps(d[rows][geo], ref[geo])
-    record("1024-lights", deferred_max_ulp=int(u.max()), deferred_exact=float((u == 0).mean()), ms=round(gpu.hybrid_frame_stats().pass_ms[4], 4))
+    record("hybrid_frame", "1024-lights", deferred_max_ulp=int(u.max()), deferred_exact=float((u == 0).mean()), ms=round(gpu.hybrid_frame_stats().pass_ms[4], 4))
     assert u.max() <= DEFERRED_ULP
     assert gpu.hybrid_frame_stats().lights == 1025
 
 
 # ---- 6. the C++ mirror ----------------------------------------------------------------------------------------------------
 def test_cpp_frame_images_equal_the_ctypes_images(tmp_path):
-    import test_hybrid_cpp as tc
-
-    exe = str(tmp_path / "hybrid_frame_host")
-    libdir = os.path.dirname(rr.api.LIB_PATH)
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cpp", "hybrid_frame_host.cpp"), "-o", exe, "-L", libdir, "-lutopian_hip", f"-Wl,-rpath,{libdir}"], check=True)
-    meshes, v = tc.scene(), tc.view()
+    meshes, v = cpp_scene(), cpp_view()
     v.shadows_enabled = v.cubemap_enabled = 0
-    blob, out = tmp_path / "scene.blob", tmp_path / "out.bin"
-    tc.write_blob(blob, meshes, v)
-    res = subprocess.run([exe, str(blob), str(out)], capture_output=True, text=True, timeout=120)
-    assert res.returncode == 0, res.stderr
-    r = rr.Renderer(tc.W, tc.H)
-    white = r.default_diffuse_map()
-    for vert, idx, kind, base in meshes:
-        r.add_mesh(vert, idx, rr.make_material(kind, 0.0, base, diffuse_map=white))
-    r.initialize_raytracing()
+    res, blob_out, r = run_cpp(tmp_path, "frame", meshes, v)
     r.render_hybrid(v, rr.HYBRID_FRAME)
-    blob_out = np.fromfile(out, dtype=np.uint8)
     at = 0
     for which in (rr.HYBRID_SSAO_IMAGE, rr.HYBRID_DEFERRED_OUTPUT, rr.HYBRID_PRESENT_OUTPUT):
         mine = r.read_hybrid(which).view(np.uint8).reshape(-1)

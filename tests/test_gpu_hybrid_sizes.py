@@ -8,9 +8,7 @@ import pytest
 import hybrid_reference as hr
 import ibl_reference as ir
 import rust_renderer_amd as rr
-from test_gpu_hybrid import assert_reflections, bits, read_gbuffer, synthetic_scene
-from test_gpu_hybrid_frame import add_lights, check_frame, frame_view, pair, read_all
-from test_gpu_ibl import _ibl_frame, ibl_view
+from hybrid_util import add_lights, assert_reflections, bits, check_frame, check_ibl_frame, frame_view, gbuf, ibl_view, pair, read_all, synthetic_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -19,7 +17,7 @@ SIZES = [(1, 1), (1, 45), (67, 1), (65, 3), (257, 3), (97, 61), (255, 17), (320,
 
 
 def sized_scene(w, h):
-    """the synthetic scene of test_gpu_hybrid.py with a camera of this aspect, so that the frame holds sky, metal and non-metal pixels.
+    """the synthetic scene of hybrid_util.py with a camera of this aspect, so that the frame holds sky, metal and non-metal pixels.
     A one-pixel column looks down through the Lambertian sphere: sky above, the metal floor below, the sphere between. A one-pixel
     row looks at that sphere from close by, so that it covers more than one pixel (the texel-corner fetch averages the material index
     of neighbours); a frame of two or three rows from further away. Their wide views end in the floor and the sky. Other frames keep
@@ -52,7 +50,7 @@ def test_every_pass_at_an_awkward_size(w, h):
         for _ in range(2):
             gpu.render_frame(view, rr.PASS_GBUFFER)
         gpu.render_hybrid(view, rr.HYBRID_GBUFFER)
-        g = read_gbuffer(gpu)
+        g = gbuf(gpu)
         assert np.array_equal(bits(g["position"]), bits(gpu.read_gbuffer_position())), grid
         ref = ref or hr.gbuffer(cpu, meshes, view, w, h)
         for k in ("position", "normal", "pbr"):
@@ -98,5 +96,5 @@ def test_ibl_consumers_at_an_awkward_size(w, h):
     v.num_lights = 0
     gpu.render_hybrid(v, rr.HYBRID_GBUFFER | rr.HYBRID_ENVIRONMENT)
     maps = ir.read_maps(gpu)
-    g, d = _ibl_frame(gpu, cpu, meshes, v, maps, f"ibl-size{w}x{h}")
+    g, d = check_ibl_frame(gpu, cpu, meshes, v, maps, f"ibl-size{w}x{h}")
     assert (g["position"][..., 3] == 0).any() and (g["position"][..., 3] == 1).any()

@@ -2,53 +2,25 @@
 each stage on the device's own inputs: the environment cube against the oracle's sky, the irradiance and specular cubes and the BRDF LUT
 against the restatement fed the device's environment map, a known answer at roughness 0, the deferred pass, the sky and rt_reflections
 with IBL, the reference's default view, the gates and isolation, the 1080p frame with IBL and the C++ mirror."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-import hybrid_frame_reference as fr
+import hybrid_reference as hr
 import ibl_reference as ir
 import rust_renderer_amd as rr
+from hybrid_util import (assets, check_ibl_frame, cpp_scene, cpp_view, ibl_view, pair, read_all, record, run_cpp, scene_named,  # noqa: F401
+                         synthetic_scene, ulps)
 from rust_renderer_amd.api import UtopianError
-from test_gpu_hybrid import assets, scene_named, synthetic_scene  # noqa: F401 (assets is a fixture)
-from test_gpu_hybrid_frame import DEFERRED_ULP, gbuf, pair, read_all, ulps
 
 pytestmark = pytest.mark.gpu
 
-W, H = 160, 120
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.environ.get("HYBRID_FRAME_RECORD")  # a directory: the measured errors and pass times are appended there
 ENV = rr.HYBRID_ENVIRONMENT
 # tolerances (DESIGN.md section 2 "Environment and IBL maps"): the environment is the sky pass's integrator (the sky pass's tolerance);
 # the irradiance filter has no transcendental on the device (the tap table is made on the host) and matches to IRR_ULP; the specular
 # filter's random() goes through device sinf and its lod through log2f (SPEC_RTOL); the LUT through sinf / cosf / powf, within one
-# fp16 ulp after rounding; the consumers read the device's maps with the same arithmetic as the restatement (CONSUMER_ULP)
+# fp16 ulp after rounding; the consumers read the device's maps with the same arithmetic as the restatement (CONSUMER_ULP, hybrid_util)
 IRR_ULP = 2
 SPEC_RTOL = 2e-3
-CONSUMER_ULP = DEFERRED_ULP
-
-
-def record(name, **values):
-    if not OUT:
-        return
-    os.makedirs(OUT, exist_ok=True)
-    with open(os.path.join(OUT, "ibl_measured.txt"), "a") as f:
-        f.write(f"{name} " + " ".join(f"{k}={v}" for k, v in values.items()) + "\n")
-
-
-def unit_sun(view):
-    s = np.array(view.sun_dir[:], np.float64)
-    view.sun_dir[:] = tuple(np.float32(s / np.linalg.norm(s)))
-    return view
-
-
-def ibl_view(scene, width=W, height=H, **kw):
-    v = scene.make_view(width, height, **kw)
-    v.shadows_enabled = 0
-    v.ibl_enabled = v.cubemap_enabled = 1
-    return unit_sun(v)
 
 
 def eye_of(view):
@@ -108,7 +80,7 @@ def test_environment_texels_equal_the_sky_on_every_face_mip_edge_and_corner(buil
             got = env[m][f, j, i, :3]
             worst = max(worst, float(np.max(np.abs(got - want) / (np.abs(want) + 1e-6))))
             assert np.allclose(got, want, rtol=1e-4, atol=1e-6), (m, f)
-    record("environment", max_rel=worst)
+    record("ibl", "environment", max_rel=worst)
     s = built["gpu"].environment_stats()
     assert s.builds == 1 and all(ms > 0 for ms in s.pass_ms)
     assert np.array_equal(np.array(s.sun_dir[:], np.float32), np.array(v.sun_dir[:], np.float32)) and np.array_equal(np.array(s.eye[:], np.float32), eye_of(v))
@@ -128,7 +100,7 @@ def test_irradiance_equals_the_restatement_on_the_device_environment(built):
         worst = max(worst, int(u.max()))
         assert u.max() <= IRR_ULP, (f, u.max())
     assert (maps["irr"][..., 3] == 1.0).all() and np.isfinite(maps["irr"]).all()
-    record("irradiance", max_ulp=worst)
+    record("ibl", "irradiance", max_ulp=worst)
 
 
 def test_every_specular_mip_equals_the_restatement_on_the_device_environment(built):
@@ -157,7 +129,7 @@ def test_every_specular_mip_equals_the_restatement_on_the_device_environment(bui
             rel = np.abs(got - want) / (np.abs(want) + 1e-7)
             worst = max(worst, float(rel.max()))
             assert np.allclose(got, want, rtol=SPEC_RTOL, atol=1e-7), (m, f, rel.max())
-    record("specular", max_rel=worst, texels_at_a_random_wrap=wrapped)
+    record("ibl", "specular", max_rel=worst, texels_at_a_random_wrap=wrapped)
 
 
 def test_the_whole_brdf_lut_after_fp16_rounding(built):
@@ -165,7 +137,7 @@ def test_the_whole_brdf_lut_after_fp16_rounding(built):
     assert lut.shape == (512, 512, 2) and lut.dtype == np.float16
     want = ir.brdf_lut().astype(np.float16)
     d = np.abs(lut.view(np.int16).astype(np.int32) - want.view(np.int16).astype(np.int32))
-    record("brdf_lut", max_fp16_ulp=int(d.max()), exact=float((d == 0).mean()))
+    record("ibl", "brdf_lut", max_fp16_ulp=int(d.max()), exact=float((d == 0).mean()))
     assert d.max() <= 1, d.max()
 
 
@@ -181,31 +153,6 @@ def test_specular_mip0_is_the_environment_mip0_mirrored_in_y(built):
 
 
 # ---- 5. the consumers ---------------------------------------------------------------------------------------------------------------
-def _ibl_frame(gpu, cpu, meshes, view, maps, name):
-    gpu.render_hybrid(view, rr.HYBRID_FRAME)
-    g = gbuf(gpu)
-    sh, refl = gpu.read_hybrid(rr.HYBRID_SHADOWS), gpu.read_hybrid(rr.HYBRID_REFLECTIONS)
-    ss, d = gpu.read_hybrid(rr.HYBRID_SSAO_IMAGE), gpu.read_hybrid(rr.HYBRID_DEFERRED_OUTPUT)
-    # rt_reflections with IBL: hits shaded by imageBasedLighting, misses the sky as before
-    want_refl, kind = ir.reflections_ibl(cpu, meshes, g["position"], g["normal"], g["pbr"], view, maps)
-    diff = np.abs(refl.astype(int) - want_refl.astype(int))
-    assert diff.max() <= 1, (name, diff.max())
-    # deferred with IBL on the geometry pixels
-    ref = ir.deferred_ibl(g, sh, refl, ss, view, meshes, [], maps)
-    geo = g["position"][..., 3] == 1.0
-    u = ulps(d[geo], ref[geo])
-    assert geo.any() and np.isfinite(d[geo]).all()
-    assert u.max() <= CONSUMER_ULP, (name, u.max())
-    # the sky from the cube
-    sky = ir.sky_cube(g["position"], view, maps["env"])
-    if sky:
-        ys, xs = np.array(list(sky)).T
-        want = np.array(list(sky.values()), np.float32)
-        assert np.allclose(d[ys, xs, :3], want, rtol=1e-5, atol=1e-7), name
-    record(name, deferred_max_ulp=int(u.max()), reflection_hits=int((kind == 1).sum()), sky=len(sky), refl_max_lsb=int(diff.max()))
-    return g, d
-
-
 @pytest.mark.parametrize("name", ["synthetic", "spheres"])
 def test_deferred_sky_and_reflections_with_ibl_equal_the_restatement(assets, name):
     scene = scene_named(name, assets)
@@ -214,11 +161,11 @@ def test_deferred_sky_and_reflections_with_ibl_equal_the_restatement(assets, nam
     v.num_lights = 0
     gpu.render_hybrid(v, rr.HYBRID_GBUFFER | ENV)
     maps = ir.read_maps(gpu)
-    _ibl_frame(gpu, cpu, meshes, v, maps, name)
+    check_ibl_frame(gpu, cpu, meshes, v, maps, name)
     # and without SSAO and the ray-traced inputs
     v2 = ibl_view(scene, ssao_enabled=0, raytracing_supported=0)
     v2.num_lights = 0
-    _ibl_frame(gpu, cpu, meshes, v2, maps, name + "-plain")
+    check_ibl_frame(gpu, cpu, meshes, v2, maps, name + "-plain")
 
 
 def test_the_reference_default_view_renders_a_present_image():
@@ -282,9 +229,11 @@ def test_maps_persist_go_stale_with_the_sun_and_stay_per_context():
     v = ibl_view(scene)
     gpu.render_hybrid(v, ENV)
     first = ir.read_maps(gpu)
+    built_ms = list(gpu.environment_stats().pass_ms)
     moved = ibl_view(scene)
     moved.sun_dir[:] = tuple(np.float32(np.array([0.3, 0.5, -0.81]) / np.linalg.norm([0.3, 0.5, -0.81])))
     gpu.render_hybrid(moved, rr.HYBRID_FRAME)  # no bit: the maps stay as they were, as in the reference
+    assert list(gpu.environment_stats().pass_ms) == built_ms, "the stats stay the last build's"
     stale = ir.read_maps(gpu)
     for k in ("irr", "lut"):
         assert np.array_equal(first[k].view(np.uint8), stale[k].view(np.uint8)), k
@@ -307,7 +256,7 @@ def test_1080p_config1_frame_with_ibl():
     scene = rr.scenes.scene_for_config(1, with_spheres=True)
     Wf, Hf = 1920, 1080
     gpu = rr.Renderer(Wf, Hf)
-    meshes = fr.upload_recorded(scene, gpu, defaults=False)
+    meshes = hr.upload_recorded(scene, gpu, defaults=False)
     v = ibl_view(scene, Wf, Hf)
     v.num_lights = 0
     gpu.render_hybrid(v, rr.HYBRID_GBUFFER | ENV)
@@ -317,33 +266,18 @@ def test_1080p_config1_frame_with_ibl():
     s = gpu.hybrid_frame_stats()
     d = gpu.read_hybrid(rr.HYBRID_DEFERRED_OUTPUT)
     assert np.isfinite(d).all()
-    record("config1-1080p-ibl", frame_ms=round(sum(s.pass_ms), 4), **{f"ms{k}": round(s.pass_ms[k], 4) for k in range(7)},
+    record("ibl", "config1-1080p-ibl", frame_ms=round(sum(s.pass_ms), 4), **{f"ms{k}": round(s.pass_ms[k], 4) for k in range(7)},
            **{f"env{k}": round(env.pass_ms[k], 3) for k in range(4)})
     assert all(ms > 0 for ms in s.pass_ms)
 
 
 # ---- the C++ mirror -----------------------------------------------------------------------------------------------------------------
 def test_cpp_reads_a_map_and_renders_an_ibl_frame(tmp_path):
-    import test_hybrid_cpp as tc
-
-    exe = str(tmp_path / "ibl_host")
-    libdir = os.path.dirname(rr.api.LIB_PATH)
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "ibl_host.cpp"),
-                    "-o", exe, "-L", libdir, "-lutopian_hip", f"-Wl,-rpath,{libdir}"], check=True)
-    meshes, v = tc.scene(), tc.view()
+    meshes, v = cpp_scene(), cpp_view()
     v.shadows_enabled = 0
     v.ibl_enabled = v.cubemap_enabled = 1
-    blob, out = tmp_path / "scene.blob", tmp_path / "out.bin"
-    tc.write_blob(blob, meshes, v)
-    res = subprocess.run([exe, str(blob), str(out)], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stderr
-    r = rr.Renderer(tc.W, tc.H)
-    white = r.default_diffuse_map()
-    for vert, idx, kind, base in meshes:
-        r.add_mesh(vert, idx, rr.make_material(kind, 0.0, base, diffuse_map=white))
-    r.initialize_raytracing()
+    res, blob_out, r = run_cpp(tmp_path, "ibl", meshes, v, timeout=300)
     r.render_hybrid(v, rr.HYBRID_FRAME | ENV)
-    blob_out = np.fromfile(out, dtype=np.uint8)
     mine = np.concatenate([r.read_environment(rr.ENV_IRRADIANCE, 2, 0).view(np.uint8).reshape(-1), r.read_hybrid(rr.HYBRID_PRESENT_OUTPUT).reshape(-1)])
     assert np.array_equal(blob_out, mine)
     assert f"builds {r.environment_stats().builds}" in res.stdout

@@ -9,7 +9,7 @@ import hybrid_f64 as hf
 import hybrid_frame_reference as fr
 import ibl_reference as ir
 import rust_renderer_amd as rr
-from test_hybrid_frame_cpu import _cast, _view
+from hybrid_util import cast_planes, plane_view
 
 F = np.float32
 W, H = 48, 36
@@ -62,7 +62,7 @@ def lights_of_every_kind(seed, n=8):
 
 
 def view_for(eye, rt, ssao, n_lights):
-    v = _view(eye, (0.0, 0.0, 0.0))
+    v = plane_view(eye, (0.0, 0.0, 0.0), W, H)
     v.eye_pos[:] = eye
     v.sun_dir[:] = (0.3, 0.8, -0.5)
     v.raytracing_supported, v.ssao_enabled, v.num_lights = rt, ssao, n_lights
@@ -172,8 +172,8 @@ def test_cube_reading_equals_the_restatement_at_edges_and_corners(maps, S):
 
 def test_ssao_interval_holds_the_restatement():
     """the corner of two planes and a flat wall: the restatement's texels lie in the float64 interval, and the interval is narrow"""
-    view = _view((0.0, 0.2, 0.0), (0.0, -0.6, -2.0))
-    pos, nrm = _cast(view, [((0.0, -0.5, 0.0), np.array([0.0, 1.0, 0.0])), ((0.0, 0.0, -2.0), np.array([0.0, 0.0, 1.0]))])
+    view = plane_view((0.0, 0.2, 0.0), (0.0, -0.6, -2.0), W, H)
+    pos, nrm = cast_planes(view, [((0.0, -0.5, 0.0), np.array([0.0, 1.0, 0.0])), ((0.0, 0.0, -2.0), np.array([0.0, 0.0, 1.0]))], W, H)
     got = fr.ssao(pos, nrm, view).astype(np.int64)
     lo, hi = hf.ssao(pos, nrm, view)
     assert ((lo <= got) & (got <= hi)).all(), np.count_nonzero((got < lo) | (got > hi))

@@ -11,6 +11,7 @@ import hybrid_frame_reference as fr
 import hybrid_reference as hr
 import oracle_api as oa
 import rust_renderer_amd as rr
+from hybrid_util import cast_planes, plane_view
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "utopian_hip.h")
@@ -67,44 +68,16 @@ def test_python_layer_and_the_oracle_renderer():
 W, H = 48, 36
 
 
-def _view(eye, target):
-    cam = rr.camera.Camera(eye, target, 60.0, W / H, 0.01, 1000.0)
-    v = rr.default_view(cam, W, H)
-    v.shadows_enabled = v.ibl_enabled = v.cubemap_enabled = 0
-    return v
-
-
-def _cast(view, planes):
-    """position and normal targets of a scene of infinite planes (point, normal): the nearest along each primary ray"""
-    pos = np.tile(np.array([1, 1, 1, 0], np.float32), (H, W, 1))
-    nrm = pos.copy()
-    for y in range(H):
-        for x in range(W):
-            r = oa.primary_ray(view, W, H, x, y, 0.5, 0.5).astype(np.float64)
-            best = None
-            for p0, n in planes:
-                den = np.dot(r[3:], n)
-                if abs(den) < 1e-9:
-                    continue
-                t = np.dot(np.asarray(p0) - r[:3], n) / den
-                if t > 0 and (best is None or t < best[0]):
-                    best = (t, n)
-            if best:
-                pos[y, x, :3], pos[y, x, 3] = r[:3] + best[0] * r[3:], 1.0
-                nrm[y, x, :3], nrm[y, x, 3] = best[1], 1.0
-    return pos, nrm
-
-
 def test_ssao_of_a_flat_plane_facing_the_camera_is_exactly_one():
-    view = _view((0.0, 0.0, 0.0), (0.0, 0.0, -1.0))
-    pos, nrm = _cast(view, [((0.0, 0.0, -3.0), np.array([0.0, 0.0, 1.0]))])
+    view = plane_view((0.0, 0.0, 0.0), (0.0, 0.0, -1.0), W, H)
+    pos, nrm = cast_planes(view, [((0.0, 0.0, -3.0), np.array([0.0, 0.0, 1.0]))], W, H)
     assert (pos[..., 3] == 1).all()
     assert (fr.ssao(pos, nrm, view) == 65535).all(), "every kernel sample has z > 0: in front of the plane"
 
 
 def test_ssao_darkens_an_inside_corner_and_only_near_it():
-    view = _view((0.0, 0.2, 0.0), (0.0, -0.6, -2.0))
-    pos, nrm = _cast(view, [((0.0, -0.5, 0.0), np.array([0.0, 1.0, 0.0])), ((0.0, 0.0, -2.0), np.array([0.0, 0.0, 1.0]))])
+    view = plane_view((0.0, 0.2, 0.0), (0.0, -0.6, -2.0), W, H)
+    pos, nrm = cast_planes(view, [((0.0, -0.5, 0.0), np.array([0.0, 1.0, 0.0])), ((0.0, 0.0, -2.0), np.array([0.0, 0.0, 1.0]))], W, H)
     occ = fr.ssao(pos, nrm, view)
     crease = np.abs(pos[..., 1] + 0.5) + np.abs(pos[..., 2] + 2.0) < 0.05  # G-buffer texels at the corner
     far = (np.abs(pos[..., 1] + 0.5) + np.abs(pos[..., 2] + 2.0) > 0.6) & (pos[..., 3] == 1)
@@ -115,7 +88,7 @@ def test_ssao_darkens_an_inside_corner_and_only_near_it():
 
 
 def test_one_sunlit_lambertian_pixel_is_the_closed_form_surface_shading():
-    view = _view((0.0, 5.0, 0.0), (0.0, 0.0, -1.0))
+    view = plane_view((0.0, 5.0, 0.0), (0.0, 0.0, -1.0), W, H)
     view.eye_pos[:] = (0.0, 5.0, 0.0)
     view.sun_dir[:] = (0.0, 1.0, 0.0)
     view.raytracing_supported = view.ssao_enabled = 0
@@ -132,7 +105,7 @@ def test_one_sunlit_lambertian_pixel_is_the_closed_form_surface_shading():
 
 
 def test_a_point_light_below_the_horizon_adds_nothing_and_one_above_adds_its_share():
-    view = _view((0.0, 5.0, 0.0), (0.0, 0.0, -1.0))
+    view = plane_view((0.0, 5.0, 0.0), (0.0, 0.0, -1.0), W, H)
     view.eye_pos[:] = (0.0, 5.0, 0.0)
     view.sun_dir[:] = (0.6, -0.8, 0.0)  # the sun below the horizon: NdotL = 0 (not opposite V, where H = normalize(0) is NaN)
     view.raytracing_supported = view.ssao_enabled = 0

@@ -20,9 +20,7 @@ import pytest
 import oracle_api as oa
 import rust_renderer_amd as rr
 from rust_renderer_amd import gltf
-from rust_renderer_amd.scenes import Mesh, Model, Scene
-from rust_renderer_amd.types import VERTEX_DTYPE
-from util import L2_TOL, per_pixel_l2, reference_file
+from util import L2_TOL, model_from, per_pixel_l2, reference_cornell_scene, reference_file, reference_spheres_scene
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -30,36 +28,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 @pytest.fixture(scope="module")
 def assets():
     return np.load(os.path.join(HERE, "golden", "reference_assets.npz"))
-
-
-def model_from(assets, key):
-    meshes = []
-    for i in range(int(assets[f"{key}_count"])):
-        v = np.ascontiguousarray(assets[f"{key}_{i}_vertices"]).view(VERTEX_DTYPE).reshape(-1)
-        meshes.append(Mesh(v, assets[f"{key}_{i}_indices"], rr.LAMBERTIAN, 0.0, tuple(float(x) for x in assets[f"{key}_{i}_base_color"]), None,
-                           assets[f"{key}_{i}_transform"].copy(), name=str(assets[f"{key}_{i}_name"])))
-    return Model(meshes, [])
-
-
-REFERENCE_LIGHTS = [(float((i // 30) * 20), 3.5, float((i % 30) * 20)) for i in range(10)]  # scenes.rs:16-24
-
-
-def reference_cornell_scene(assets):
-    light = gltf.load_cube()
-    light.meshes[0].material_type = rr.DIFFUSE_LIGHT  # scenes.rs:79-80
-    cam = rr.camera.Camera((0.0, 0.9, 2.0), (0.0, 0.5, 0.0), 60.0, 1.0, 0.01, 1000.0)  # scenes.rs:63-66, fov / near / far of main.rs:44-52
-    return Scene("reference_cornell", [(model_from(assets, "cornell"), None), (light, rr.transform3x4((0.50, 0.05, 0.35), (0.0, 1.95, 0.0)))],
-                 REFERENCE_LIGHTS, cam, dict(sky_enabled=1, sun_shadow_enabled=1, lights_enabled=1, use_ris_light_sampling=1))
-
-
-def reference_spheres_scene(assets):
-    metal, glass = model_from(assets, "sphere"), model_from(assets, "sphere")
-    metal.meshes[0].material_type = rr.METAL                                       # scenes.rs:116-117
-    glass.meshes[0].material_type, glass.meshes[0].material_property = rr.DIELECTRIC, 1.5  # scenes.rs:118-122
-    cam = rr.camera.Camera((-10.28, 2.10, -0.18), (0.0, 0.5, 0.0), 60.0, 1.0, 0.01, 1000.0)  # scenes.rs:107-110
-    place = lambda y: rr.transform3x4((0.6, 0.6, 0.6), (-3.0, y, 0.7))             # scenes.rs:130-149
-    return Scene("reference_spheres", [(metal, place(2.65)), (glass, place(0.65))], REFERENCE_LIGHTS, cam,
-                 dict(sky_enabled=1, sun_shadow_enabled=1, lights_enabled=1, use_ris_light_sampling=0))
 
 
 def test_fixture_matches_the_asset_inventory(assets):

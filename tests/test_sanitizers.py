@@ -74,7 +74,7 @@ def test_oracle_under_asan_ubsan_matches_the_plain_build(tmp_path):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import oracle_api as oa
     import rust_renderer_amd as rr
-    from test_cpp_host import write_blob
+    from util import write_blob
 
     exe = str(tmp_path / "oracle_frames")
     subprocess.run(

@@ -1,11 +1,15 @@
 """Shared helpers for the parity tests: drive the HIP path (through the C ABI) and the CPU oracle
 through the same host calls on the same seeded scene."""
 import os
+import struct
 
 import numpy as np
 
 import oracle_api as oa
 import rust_renderer_amd as rr
+from rust_renderer_amd import gltf
+from rust_renderer_amd.scenes import Mesh, Model, Scene
+from rust_renderer_amd.types import VERTEX_DTYPE
 
 L2_TOL = 1e-3  # BASELINE.json north_star: per-pixel L2 <= 1e-3 on linear radiance
 REFERENCE_FILES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_files.npz")
@@ -21,6 +25,71 @@ def reference_file(name, directory=None):
     with open(path, "wb") as f:
         f.write(data)
     return path
+
+
+# ---- the reference's own assets (tests/golden/reference_assets.npz) placed by its scene scripts: test_reference_assets.py
+def model_from(assets, key):
+    meshes = []
+    for i in range(int(assets[f"{key}_count"])):
+        v = np.ascontiguousarray(assets[f"{key}_{i}_vertices"]).view(VERTEX_DTYPE).reshape(-1)
+        meshes.append(Mesh(v, assets[f"{key}_{i}_indices"], rr.LAMBERTIAN, 0.0, tuple(float(x) for x in assets[f"{key}_{i}_base_color"]), None,
+                           assets[f"{key}_{i}_transform"].copy(), name=str(assets[f"{key}_{i}_name"])))
+    return Model(meshes, [])
+
+
+REFERENCE_LIGHTS = [(float((i // 30) * 20), 3.5, float((i % 30) * 20)) for i in range(10)]  # scenes.rs:16-24
+
+
+def reference_cornell_scene(assets):
+    light = gltf.load_cube()
+    light.meshes[0].material_type = rr.DIFFUSE_LIGHT  # scenes.rs:79-80
+    cam = rr.camera.Camera((0.0, 0.9, 2.0), (0.0, 0.5, 0.0), 60.0, 1.0, 0.01, 1000.0)  # scenes.rs:63-66, fov / near / far of main.rs:44-52
+    return Scene("reference_cornell", [(model_from(assets, "cornell"), None), (light, rr.transform3x4((0.50, 0.05, 0.35), (0.0, 1.95, 0.0)))],
+                 REFERENCE_LIGHTS, cam, dict(sky_enabled=1, sun_shadow_enabled=1, lights_enabled=1, use_ris_light_sampling=1))
+
+
+def reference_spheres_scene(assets):
+    metal, glass = model_from(assets, "sphere"), model_from(assets, "sphere")
+    metal.meshes[0].material_type = rr.METAL                                       # scenes.rs:116-117
+    glass.meshes[0].material_type, glass.meshes[0].material_property = rr.DIELECTRIC, 1.5  # scenes.rs:118-122
+    cam = rr.camera.Camera((-10.28, 2.10, -0.18), (0.0, 0.5, 0.0), 60.0, 1.0, 0.01, 1000.0)  # scenes.rs:107-110
+    place = lambda y: rr.transform3x4((0.6, 0.6, 0.6), (-3.0, y, 0.7))             # scenes.rs:130-149
+    return Scene("reference_spheres", [(metal, place(2.65)), (glass, place(0.65))], REFERENCE_LIGHTS, cam,
+                 dict(sky_enabled=1, sun_shadow_enabled=1, lights_enabled=1, use_ris_light_sampling=0))
+
+
+# ---- the scene blob of tests/cpp/host_frames.cpp and oracle_frames.cpp: test_cpp_host.py, test_sanitizers.py
+def write_blob(path, scene, W, H, frames, pass_mask):
+    view = scene.make_view(W, H)
+    view.num_lights = len(scene.lights)
+    cam = scene.camera
+    with open(path, "wb") as f:
+        f.write(struct.pack("<5I", 0x43534855, W, H, frames, pass_mask))
+        f.write(bytes(view))
+        f.write(struct.pack("<9f", *cam.position, *cam.target, cam.fov_degrees, cam.z_near, cam.z_far))
+        textures, meshes = [], []
+        for model, transform in scene.models:
+            base = len(textures)
+            textures += model.textures
+            for m in model.meshes:
+                w = m.transform if transform is None else rr.api.compose3x4(transform, m.transform)
+                meshes.append((m, base, w))
+        f.write(struct.pack("<I", len(textures)))
+        for t in textures:
+            f.write(struct.pack("<2I", t.shape[1], t.shape[0]))
+            f.write(np.ascontiguousarray(t, dtype=np.uint8).tobytes())
+        f.write(struct.pack("<I", len(meshes)))
+        for m, base, w in meshes:
+            f.write(struct.pack("<2I", len(m.vertices), len(m.indices)))
+            f.write(np.ascontiguousarray(m.vertices).tobytes())
+            f.write(np.ascontiguousarray(m.indices, dtype=np.uint32).tobytes())
+            f.write(struct.pack("<i4fIf", -1 if m.texture is None else base + m.texture, *m.base_color, int(m.material_type), float(m.material_property)))
+            mat4 = np.vstack([np.asarray(w, dtype=np.float32).reshape(3, 4), [0, 0, 0, 1]]).astype(np.float32)
+            f.write(np.ascontiguousarray(mat4.T).tobytes())  # column-major
+        f.write(struct.pack("<I", len(scene.lights)))
+        for p in scene.lights:
+            f.write(struct.pack("<3f", *p))
+    return view
 
 
 def make_pair(scene, W, H, **oracle_kw):

@@ -1,52 +1,124 @@
-"""Timing of the hybrid graph's ray-traced passes (uh_render_hybrid) on the config-1 scene (Sponza-class with the reference's two
-spheres, one metal) at 1920 x 1080, camera at rest, UH_HYBRID_ALL, warm: hipEvent ms of each pass, rays per pass and metal pixels.
-Prints one JSON line. Run it under `rocprofv3 --kernel-trace --stats -- python tools/hybrid_timing.py` for the kernel table.
+"""Timing of the hybrid graph (uh_render_hybrid) at 1920 x 1080 on the config-1 scene (Sponza-class with the reference's two spheres, one
+metal), camera at rest, warm: the hipEvent ms of each pass, median of --iters calls. Prints one JSON line per measurement. --mode picks
+what is timed:
 
-  python tools/hybrid_timing.py [--width 1920 --height 1080 --warmup 3 --iters 20 --out FILE]"""
+  passes  the ray-traced passes (UH_HYBRID_ALL, IBL off): ms, rays per pass and metal pixels
+  frame   the whole frame (UH_HYBRID_FRAME: rt_shadows, G-buffer, rt_reflections, SSAO, deferred, sky, present; IBL off) with each light
+          count of --lights (1,024: the light count of BASELINE config 2; point and spot lights alternate)
+  ibl     the IBL maps (UH_HYBRID_ENVIRONMENT: environment cube, irradiance cube, specular cube, BRDF LUT), median of --builds builds,
+          then the whole frame with IBL off and with the reference's flags (ibl_enabled = cubemap_enabled = 1, shadows_enabled = 0)
+
+Run it under `rocprofv3 --kernel-trace --stats -- python tools/hybrid_timing.py --mode ...` for the kernel table.
+
+  python tools/hybrid_timing.py [--mode passes|frame|ibl --width 1920 --height 1080 --warmup 3 --iters 20 --lights 0,16,1024
+                                 --builds 5 --out FILE]"""
 import argparse
 import json
 import os
 import statistics
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import rust_renderer_amd as rr  # noqa: E402
 
+PASSES = ("rt_shadows", "gbuffer", "rt_reflections", "ssao", "deferred", "sky", "present")
+SUBPASSES = ("environment", "irradiance", "specular", "brdf_lut")
+
+
+def add_lights(r, n, seed=11):
+    rng = np.random.default_rng(seed)
+    for k in range(n):
+        l = rr.make_light(rng.uniform((-12.0, 0.5, -5.0), (12.0, 10.0, 5.0)), color=tuple(rng.uniform(0.2, 1.0, 3)))
+        l.light_type = 1.0 if k % 2 == 0 else 2.0
+        l.direction[:] = (0.0, -1.0, 0.0)
+        l.spot = 8.0
+        r.add_gpu_light(l)
+
+
+def setup(a, lights=0, **flags):
+    """the scene on a new renderer with `lights` lights, its view with `flags` set, and the path tracer's camera grid for this camera
+    (two frames at rest): the G-buffer cast goes through it, as it does in a frame"""
+    scene = rr.scenes.scene_for_config(1, with_spheres=True)
+    r = scene.upload(rr.Renderer(a.width, a.height))
+    if lights:
+        add_lights(r, lights)
+        r.initialize_raytracing()
+    view = scene.make_view(a.width, a.height)
+    for k, v in flags.items():
+        setattr(view, k, v)
+    for _ in range(2):
+        r.render_frame(view, rr.PASS_GBUFFER)
+    return scene, r, view
+
+
+def timed(a, r, view, mask, stats):
+    """--warmup calls, then --iters calls each followed by stats(r), which waits (one call at a time on an idle GPU): the median of
+    each pass_ms entry and the last call's stats"""
+    for _ in range(a.warmup):
+        r.render_hybrid(view, mask)
+    per = []
+    for _ in range(a.iters):
+        r.render_hybrid(view, mask)
+        per.append(stats(r))
+    ms = [list(s.pass_ms) for s in per]
+    return [statistics.median(m[k] for m in ms) for k in range(len(ms[0]))], per[-1]
+
+
+def passes(a):
+    scene, r, view = setup(a, ibl_enabled=0)
+    med, s = timed(a, r, view, rr.HYBRID_ALL, rr.Renderer.hybrid_stats)
+    yield dict(metric="hybrid_frame", config=1, width=a.width, height=a.height, iters=a.iters,
+               gbuffer_ms=med[0], rt_shadows_ms=med[1], rt_reflections_ms=med[2], total_ms=sum(med),
+               rays=dict(zip(("gbuffer", "shadow", "reflection"), list(s.rays))), metal_pixels=s.reflection_pixels,
+               camera_grid=r.get_stats().camera_grid_cells > 0, triangles=scene.num_triangles)
+
+
+def frame(a):
+    for n in (int(x) for x in a.lights.split(",")):
+        scene, r, view = setup(a, n, shadows_enabled=0, ibl_enabled=0, cubemap_enabled=0, num_lights=n)
+        med, s = timed(a, r, view, rr.HYBRID_FRAME, rr.Renderer.hybrid_frame_stats)
+        yield dict(metric="hybrid_frame_full", config=1, lights=n, width=a.width, height=a.height, iters=a.iters,
+                   **{f"{p}_ms": m for p, m in zip(PASSES, med)}, total_ms=sum(med), sky_pixels=s.sky_pixels, triangles=scene.num_triangles)
+
+
+def ibl(a):
+    _, r, view = setup(a, shadows_enabled=0, num_lights=0)
+    builds = []
+    for _ in range(a.builds):
+        r.render_hybrid(view, rr.HYBRID_ENVIRONMENT)
+        builds.append(list(r.environment_stats().pass_ms))  # waits: one build at a time on an idle GPU
+    med = [statistics.median(b[k] for b in builds) for k in range(4)]
+    yield dict(metric="ibl_environment_update", builds=a.builds, **{f"{p}_ms": m for p, m in zip(SUBPASSES, med)}, total_ms=sum(med),
+               first_build_ms=sum(builds[0]))
+    for on in (0, 1):
+        view.ibl_enabled = view.cubemap_enabled = on
+        med, _ = timed(a, r, view, rr.HYBRID_FRAME, rr.Renderer.hybrid_frame_stats)
+        yield dict(metric="hybrid_frame_full", config=1, lights=0, ibl=on, width=a.width, height=a.height, iters=a.iters,
+                   **{f"{p}_ms": m for p, m in zip(PASSES, med)}, total_ms=sum(med))
+
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=("passes", "frame", "ibl"), default="passes")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--lights", default="0,16,1024", help="frame: the light counts")
+    ap.add_argument("--builds", type=int, default=5, help="ibl: the map builds")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    scene = rr.scenes.scene_for_config(1, with_spheres=True)
-    r = scene.upload(rr.Renderer(a.width, a.height))
-    view = scene.make_view(a.width, a.height)
-    view.ibl_enabled = 0
-    # the path tracer's camera grid for this camera (two frames at rest): the G-buffer cast goes through it, as it does in a frame
-    for _ in range(2):
-        r.render_frame(view, rr.PASS_GBUFFER)
-    for _ in range(a.warmup):
-        r.render_hybrid(view, rr.HYBRID_ALL)
-    per = []
-    for _ in range(a.iters):
-        r.render_hybrid(view, rr.HYBRID_ALL)
-        s = r.hybrid_stats()  # waits: one call at a time on an idle GPU
-        per.append((list(s.pass_ms), list(s.rays), s.reflection_pixels))
-    med = [statistics.median(p[0][k] for p in per) for k in range(3)]
-    out = dict(metric="hybrid_frame", config=1, width=a.width, height=a.height, iters=a.iters,
-               gbuffer_ms=med[0], rt_shadows_ms=med[1], rt_reflections_ms=med[2], total_ms=sum(med),
-               rays=dict(zip(("gbuffer", "shadow", "reflection"), per[-1][1])), metal_pixels=per[-1][2],
-               camera_grid=r.get_stats().camera_grid_cells > 0, triangles=scene.num_triangles)
-    line = json.dumps(out)
-    print(line)
+    lines = []
+    for out in {"passes": passes, "frame": frame, "ibl": ibl}[a.mode](a):
+        lines.append(json.dumps(out))
+        print(lines[-1], flush=True)
     if a.out:
         with open(a.out, "w") as f:
-            f.write(line + "\n")
+            f.write("\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":
