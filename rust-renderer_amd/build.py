@@ -25,17 +25,15 @@ def _stale(out, srcs):
     return any(os.path.getmtime(s) > t for s in srcs)
 
 
-def build_library(force=False, verbose=False, extra_flags=(), lib=LIB):
-    """extra_flags: experiments (-D switches); such a build goes to another `lib` path and its own object directory"""
+def build_library(force=False, verbose=False):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.cpp")))
     headers = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(_HERE, "..", "include", "*.h")) + [os.path.abspath(__file__)]
-    if not force and not _stale(lib, srcs + headers):
-        return lib  # (also what a GPU box sees: the built .so travels with the snapshot, the objects do not)
-    obj_dir = OBJ_DIR if lib == LIB else lib + ".obj"
-    os.makedirs(obj_dir, exist_ok=True)
-    flags = HIPCC_FLAGS + list(extra_flags) + ["-I", os.path.join(_HERE, "..", "include"), "-I", CSRC]
-    objs = [os.path.join(obj_dir, os.path.basename(s) + ".o") for s in srcs]
+    if not force and not _stale(LIB, srcs + headers):
+        return LIB  # (also what a GPU box sees: the built .so travels with the snapshot, the objects do not)
+    os.makedirs(OBJ_DIR, exist_ok=True)
+    flags = HIPCC_FLAGS + ["-I", os.path.join(_HERE, "..", "include"), "-I", CSRC]
+    objs = [os.path.join(OBJ_DIR, os.path.basename(s) + ".o") for s in srcs]
     todo = [(s, o) for s, o in zip(srcs, objs) if force or _stale(o, [s] + headers)]
 
     def compile_one(so):
@@ -47,9 +45,9 @@ def build_library(force=False, verbose=False, extra_flags=(), lib=LIB):
     if todo:
         with ThreadPoolExecutor(max_workers=min(len(todo), max(1, (os.cpu_count() or 2) - 1))) as ex:
             list(ex.map(compile_one, todo))
-    if todo or not os.path.exists(lib):
-        cmd = [hipcc, "-shared", "-fPIC", "--offload-arch=gfx950", "-pthread", "-o", lib] + objs
+    if todo or not os.path.exists(LIB):
+        cmd = [hipcc, "-shared", "-fPIC", "--offload-arch=gfx950", "-pthread", "-o", LIB] + objs
         if verbose:
             print(" ".join(cmd))
         subprocess.run(cmd, check=True)
-    return lib
+    return LIB

@@ -37,10 +37,8 @@ struct NodeW {
 // outwards, so the slab test stays conservative and hits do not change.
 // Slots [0, n_tri) are triangles: packet tri_base + slot. Slots [n_tri, n_child) are nodes: node child_base + (slot - n_tri).
 // The remaining slots are empty: an inverted box (qlo = 255, qhi = 0) that no ray hits.
-// The first 16 bytes are the node's frame; everything else a visit needs lies in the other 32 (n_tri rides in the top bits of
-// child_base), so that a build with UH_INHERIT_FRAME = 1 - the frame a function of the parent's frame and of this node's quantised box
-// there, node_quant.h qn_inherit - can derive the frame in registers and load 32 bytes only. Measured slower (the derivation's ~45 VALU
-// instructions cost more than the load they save): the default build gives every node its own frame.
+// The first 16 bytes are the node's frame (node_quant.h); the child planes and references are the other 32, with n_tri in the top
+// bits of child_base, so a visit reads n_tri without meta.
 struct alignas(16) Node4C {
    float origin[3];    // the frame's origin: at or below the lower corner of the node's own (padded) box
    uint32_t meta;      // bits 0-7 / 8-15 / 16-23: biased exponent of the x / y / z quantisation step (a power of two, byte >= 1);
@@ -50,27 +48,15 @@ struct alignas(16) Node4C {
    uint32_t child_base;  // bits 0-28: first node child; bits 29-31: n_tri
    uint32_t tri_base;
 };
-static_assert(sizeof(Node4C) == 48, "device node = three 16-byte loads (two when the frame is inherited)");
+static_assert(sizeof(Node4C) == 48, "device node = three 16-byte loads");
 constexpr uint32_t kMetaTriShift = 24, kMetaChildShift = 28;
-// Build-time experiment (round 5, measured SLOWER and therefore off: profiles/README.md "inherited frames"): 1 = a node's frame is inherited
-// from its parent (node_quant.h) and a traversal that descends into a child derives it in registers instead of loading the child's
-// first quad. 0 = every node's frame is its own and every visit loads the three quads.
-#ifndef UH_INHERIT_FRAME
-#define UH_INHERIT_FRAME 0
-#endif
 constexpr uint32_t kChildBaseBits = 29, kChildBaseMask = (1u << kChildBaseBits) - 1;  // (node counts stay below 2^29: kMaxTriangles nodes at most, far fewer in practice)
 // Stride of the device arrays in 16-byte units. A 48-byte record at a 48-byte stride straddles two 64-byte cache
 // sectors half of the time; at a 64-byte stride (the last 16 bytes unused) every record is one sector - more bytes of
 // working set against fewer sector fetches per record. Measured (profiles/README.md "record stride"): neutral for both
 // arrays in round 2; with the sun grid, whose rays fetch packets and nothing else of the tree, triangle packets at 64 bytes
 // are worth +3 % (config 1 7,620 -> 7,841 Mrays/s, 4K Bistro-class 6,230 -> 6,429, config 2 +1.9 %), nodes at 64 bytes -3 %.
-#ifndef UH_NODE_STRIDE16
-#define UH_NODE_STRIDE16 3
-#endif
-#ifndef UH_TRI_STRIDE16
-#define UH_TRI_STRIDE16 4
-#endif
-constexpr uint32_t kNodeStride16 = UH_NODE_STRIDE16, kTriStride16 = UH_TRI_STRIDE16;
+constexpr uint32_t kNodeStride16 = 3, kTriStride16 = 4;
 
 struct alignas(16) TriPacket {
    float v0[3];
@@ -125,9 +111,8 @@ void build_sah_top(const float* boxes6, uint32_t count, std::vector<TopNode>& ou
 constexpr uint32_t kTraversalStackEntries = 16 + 96;
 constexpr uint32_t kMaxTreeLevels = kTraversalStackEntries / 3;
 
-// the full-precision tree (BFS order, node 0 the root) -> the device nodes: every node's frame is its own (UH_INHERIT_FRAME = 1: only the
-// root's, the others' inherited from their parents - node_quant.h, shared with the refit kernels); children's planes rounded outwards in
-// the node's frame
+// the full-precision tree (BFS order, node 0 the root) -> the device nodes: every node's frame is its own (node_quant.h, shared with the
+// refit kernels); children's planes rounded outwards in the node's frame
 void quantise_tree(const std::vector<NodeW>& nodes, std::vector<Node4C>& out);
 
 }  // namespace uh

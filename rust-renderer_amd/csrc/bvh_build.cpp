@@ -1,8 +1,8 @@
 // bvh_build.cpp — host builder of the flattened BVH4 (see bvh.h). Replaces
 // Raytracing::create_bottom_level_acceleration_structure / create_top_level_acceleration_structure
 // (reference: utopian/src/raytracing.rs:113-217, :279-398), whose build runs inside the Vulkan
-// driver. Binned SAH (16 bins, 3 axes) -> BVH2 down to single triangles -> greedy collapse to 4-wide nodes by surface
-// area, emitted breadth-first with every node's triangle children and node children in contiguous slots (bvh.h).
+// driver. Binned SAH (16 bins, 3 axes) -> BVH2 down to single triangles -> SAH-optimal collapse to 4-wide nodes,
+// emitted breadth-first with every node's triangle children and node children in contiguous slots (bvh.h).
 #include "bvh.h"
 #include "node_quant.h"
 
@@ -43,18 +43,9 @@ struct Box {
    }
 };
 
-// build knobs (what the studies of rounds 3-4 varied, tools/bvh_visits.py; the values below are what they settled on - the library
-// reads no environment variable)
-struct Knobs {
-   int collapse = 1;        // 0 = greedy by area (rounds 1-3), 1 = SAH-optimal collapse by dynamic programming (Ylitie et al. 2017)
-   int sweep_below = 0;     // ranges of at most this many triangles are split by an exact sweep over the sorted centroids instead of 16 bins
-   int bins = 16;
-#ifndef UH_BVH_CTRI
-#define UH_BVH_CTRI 1.0f
-#endif
-   float c_tri = UH_BVH_CTRI;  // cost of a triangle slot relative to a node visit, per unit of area (collapse = 1); build-time switch for tools/bvh_visits.py
-};
-static Knobs knobs_from_env() { return Knobs(); }
+// what the builder studies of rounds 3-4 settled on (tools/bvh_visits.py)
+constexpr int kBins = 16;         // SAH split candidates per axis
+constexpr float kTriCost = 1.0f;  // cost of a triangle slot relative to a node visit, per unit of area (the collapse)
 
 struct Node2 {
    Box box;
@@ -69,7 +60,6 @@ struct Builder {
    std::vector<Node2> nodes;
    uint32_t max_depth = 0;
    bool balanced = false;  // median splits only: depth ceil(log2 n), for geometry whose SAH tree would be too deep for the traversal stack
-   Knobs kn;
 
    Builder(const std::vector<Box>& tb_, const std::vector<float>& cen_, std::vector<uint32_t>& idx_) : tb(tb_), cen(cen_), idx(idx_) {}
 
@@ -101,56 +91,14 @@ struct Builder {
          nodes[me].count = count;
          return me;
       }
-      if ((int)count <= kn.sweep_below && !balanced && depth <= 48) {
-         // exact sweep: every split position of the range sorted by centroid, on each axis
-         float best = INFINITY;
-         int axis = -1;
-         uint32_t at = 0;
-         std::vector<uint32_t> order(idx.begin() + first, idx.begin() + first + count), best_order;
-         std::vector<float> right(count);
-         for (int a = 0; a < 3; a++) {
-            std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-               const float cx = cen[3 * (size_t)x + a], cy = cen[3 * (size_t)y + a];
-               return cx < cy || (cx == cy && x < y);
-            });
-            Box acc;
-            acc.reset();
-            for (uint32_t k = count - 1; k > 0; k--) {
-               acc.grow(tb[order[k]]);
-               right[k] = acc.half_area();
-            }
-            acc.reset();
-            for (uint32_t k = 0; k + 1 < count; k++) {
-               acc.grow(tb[order[k]]);
-               const float cost = acc.half_area() * (float)(k + 1) + right[k + 1] * (float)(count - k - 1);
-               if (cost < best) {
-                  best = cost;
-                  axis = a;
-                  at = k + 1;
-               }
-            }
-            if (axis == a) best_order = order;
-         }
-         if (axis >= 0) {
-            std::copy(best_order.begin(), best_order.end(), idx.begin() + first);
-            int32_t l = build(first, at, depth + 1);
-            int32_t r = build(first + at, count - at, depth + 1);
-            nodes[me].left = l;
-            nodes[me].right = r;
-            nodes[me].first = first;
-            nodes[me].count = count;
-            return me;
-         }
-      }
-      constexpr int NBMAX = 64;
-      const int NB = kn.bins;
+      constexpr int NB = kBins;
       float best_cost = INFINITY;
       int best_axis = -1, best_split = -1;
       for (int a = 0; a < 3; a++) {
          float lo = cb.lo[a], ext = cb.hi[a] - cb.lo[a];
          if (!(ext > 0) || !std::isfinite(ext)) continue;
-         Box bb[NBMAX];
-         uint32_t bc[NBMAX];
+         Box bb[NB];
+         uint32_t bc[NB];
          for (int b = 0; b < NB; b++) {
             bb[b].reset();
             bc[b] = 0;
@@ -163,8 +111,8 @@ struct Builder {
             bb[b].grow(tb[t]);
             bc[b]++;
          }
-         float right_area[NBMAX];
-         uint32_t right_cnt[NBMAX];
+         float right_area[NB];
+         uint32_t right_cnt[NB];
          Box acc;
          acc.reset();
          uint32_t c = 0;
@@ -233,9 +181,6 @@ inline void padded(const Box& b, float* lo, float* hi) {
 
 void quantise_tree(const std::vector<NodeW>& nodes, std::vector<Node4C>& out) {
    out.assign(nodes.size(), Node4C{});
-   if (nodes.empty()) return;
-   // BFS order: a node's children lie behind it, so one pass in index order meets every node after its parent has set its frame
-   std::vector<uint8_t> framed(nodes.size(), 0);
    for (size_t i = 0; i < nodes.size(); i++) {
       const NodeW& nd = nodes[i];
       Node4C& q = out[i];
@@ -250,28 +195,16 @@ void quantise_tree(const std::vector<NodeW>& nodes, std::vector<Node4C>& out) {
          n_child++;
          if (nd.child[k] & kLeafBit) n_tri++;
       }
-      if (!framed[i] || !UH_INHERIT_FRAME) {  // the root takes its own frame (and so does every node of a build without inherited frames)
-         uint32_t exps = 0;
-         qn_own_frame(lo, hi, n_child, q.origin, exps);
-         q.meta = exps;
-      }
-      float child_origin[4][3];
-      uint32_t child_exps[4] = {0, 0, 0, 0};
-      qn_quantise(q.origin, q.meta & 0xffffffu, lo, hi, n_tri, n_child, q.qlo, q.qhi, child_origin, child_exps, UH_INHERIT_FRAME != 0);
-      q.meta = (q.meta & 0xffffffu) | (n_tri << kMetaTriShift) | (n_child << kMetaChildShift);
+      uint32_t exps = 0;
+      qn_own_frame(lo, hi, n_child, q.origin, exps);
+      qn_quantise(q.origin, exps, lo, hi, n_child, q.qlo, q.qhi);
+      q.meta = exps | (n_tri << kMetaTriShift) | (n_child << kMetaChildShift);
       uint32_t child_base = 0;
       q.tri_base = 0;
       for (int k = 0; k < 4; k++) {
          if (nd.child[k] == kEmptyRef) continue;
          if ((nd.child[k] & kLeafBit) && k == 0) q.tri_base = nd.child[k] & ~kLeafBit;
-         if (!(nd.child[k] & kLeafBit)) {
-            if ((uint32_t)k == n_tri) child_base = nd.child[k];
-            if (!UH_INHERIT_FRAME) continue;
-            Node4C& c = out[nd.child[k]];
-            for (int a = 0; a < 3; a++) c.origin[a] = child_origin[k][a];
-            c.meta = child_exps[k];
-            framed[nd.child[k]] = 1;
-         }
+         if (!(nd.child[k] & kLeafBit) && (uint32_t)k == n_tri) child_base = nd.child[k];
       }
       q.child_base = (child_base & kChildBaseMask) | (n_tri << kChildBaseBits);
    }
@@ -353,7 +286,6 @@ void build_bvh4(const BuildInput& in, BuildOutput& out, int num_threads, bool ba
    {
       Builder top(tb, cen, out.tri_order);
       top.balanced = balanced;
-      top.kn = knobs_from_env();
       if (num_threads <= 1 || n < 65536) {
          top.build(0, n, 0);
          n2.swap(top.nodes);
@@ -480,7 +412,6 @@ void build_bvh4(const BuildInput& in, BuildOutput& out, int num_threads, bool ba
                if (j >= jobs.size()) break;
                Builder b(tb, cen, out.tri_order);
                b.balanced = balanced;
-               b.kn = top.kn;
                b.build(jobs[j].first, jobs[j].count, jobs[j].depth);
                sub[j].swap(b.nodes);
                sub_depth[j] = b.max_depth;
@@ -510,18 +441,14 @@ void build_bvh4(const BuildInput& in, BuildOutput& out, int num_threads, bool ba
    // packets are consecutive: the packet order is DEFINED here, node by node), then its node children (consecutive
    // node indices), then empty slots.
    // SAH-optimal collapse (Ylitie, Karras, Laine 2017, section 3.1, for single-triangle leaves): T[n][i] = the least cost of
-   // representing BVH2 subtree n by at most i + 1 slots of a wide node - a slot being one triangle (cost c_tri x its area) or one
-   // wide node (its area, plus the best distribution of its two children over W slots). Replaces the greedy "open the child
+   // representing BVH2 subtree n by at most i + 1 slots of a wide node - a slot being one triangle (cost kTriCost x its area) or one
+   // wide node (its area, plus the best distribution of its two children over W slots). Replaced the greedy "open the child
    // with the largest area" of rounds 1-3, which fills nodes to 3.0 of 4 children on the config-1 scene.
-   const Knobs kn = knobs_from_env();
    const int W = (int)width;
-   std::vector<float> T;      // [n * W + i]
-   std::vector<uint8_t> split;  // [n * W + i]: how many of the slots the left child gets (0 = n itself is one slot) ...
-   std::vector<uint8_t> used;   // ... and how many slots the two children take together (<= i + 1: a smaller budget's plan may be the best)
-   if (kn.collapse == 1) {
-      T.assign(n2.size() * (size_t)W, 0.0f);
-      split.assign(n2.size() * (size_t)W, 0);
-      used.assign(n2.size() * (size_t)W, 0);
+   std::vector<float> T(n2.size() * (size_t)W, 0.0f);      // [n * W + i]
+   std::vector<uint8_t> split(n2.size() * (size_t)W, 0);  // [n * W + i]: how many of the slots the left child gets (0 = n itself is one slot) ...
+   std::vector<uint8_t> used(n2.size() * (size_t)W, 0);   // ... and how many slots the two children take together (<= i + 1: a smaller budget's plan may be the best)
+   {
       // every child before its parent: the reverse of a pre-order walk from the root (the index order of the builders has that
       // property too, but not once the optimiser has moved nodes around)
       std::vector<int32_t> pre;
@@ -546,7 +473,7 @@ void build_bvh4(const BuildInput& in, BuildOutput& out, int num_threads, bool ba
          uint8_t* sp = &split[k * (size_t)W];
          uint8_t* us = &used[k * (size_t)W];
          if (nd.left < 0) {
-            for (int i = 0; i < W; i++) t[i] = kn.c_tri * area;
+            for (int i = 0; i < W; i++) t[i] = kTriCost * area;
             continue;
          }
          const float* tl = &T[(size_t)nd.left * W];
@@ -639,28 +566,8 @@ void build_bvh4(const BuildInput& in, BuildOutput& out, int num_threads, bool ba
       int nc = 0;
       if (src.left < 0) {
          ch[nc++] = queue[qi];  // a single triangle at the root: wrap it
-      } else if (kn.collapse == 1) {
-         nc = dp_children(queue[qi], ch);
       } else {
-         ch[nc++] = src.left;
-         ch[nc++] = src.right;
-         for (;;) {
-            if (nc == W) break;
-            int pick = -1;
-            float pa = -1.0f;
-            for (int k = 0; k < nc; k++)
-               if (n2[ch[k]].left >= 0) {
-                  float a = n2[ch[k]].box.half_area();
-                  if (a > pa) {
-                     pa = a;
-                     pick = k;
-                  }
-               }
-            if (pick < 0) break;
-            int32_t c = ch[pick];
-            ch[pick] = n2[c].left;
-            ch[nc++] = n2[c].right;
-         }
+         nc = dp_children(queue[qi], ch);
       }
       std::stable_partition(ch, ch + nc, [&](int32_t c) { return n2[c].left < 0; });  // triangles first
       {

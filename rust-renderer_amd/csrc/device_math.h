@@ -356,52 +356,29 @@ __device__ __forceinline__ bool owns_pixel(const FrameParams& fp, uint32_t x, ui
 // ---- streaming (non-temporal) access to per-path state -----------------------------------------
 // Path state is touched once per kernel and is hundreds of MB per wavefront of frames; the BVH (nodes + triangle packets,
 // tens of MB) is what the traversal kernels re-read. `nt` loads / stores ask the caches not to keep the stream, so that it
-// does not push the tree out of the 4 MiB L2 of each XCD (+1-1.5 % frame rate, profiles/README.md). A BUILD-time switch:
-// as a run-time flag every access was a branch with its own wait behind it, and the independent loads of a kernel's
-// prologue ran one after the other (k_shade_hit: eight dependent round trips instead of four).
-#ifndef UH_STREAM_NT
-#define UH_STREAM_NT 1
-#endif
-constexpr bool kStreamNt = UH_STREAM_NT != 0;
+// does not push the tree out of the 4 MiB L2 of each XCD (+1-1.5 % frame rate, profiles/README.md). Not a run-time flag:
+// as one every access was a branch with its own wait behind it, and the independent loads of a kernel's prologue ran one
+// after the other (k_shade_hit: eight dependent round trips instead of four).
 typedef float v4f_t __attribute__((ext_vector_type(4)));
 typedef uint32_t v2u_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float4 ld_stream(const float4* p) {
-   if (kStreamNt) {
-      const v4f_t v = __builtin_nontemporal_load((const v4f_t*)p);
-      return make_float4(v.x, v.y, v.z, v.w);
-   }
-   return *p;
+   const v4f_t v = __builtin_nontemporal_load((const v4f_t*)p);
+   return make_float4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ void st_stream(float4* p, float4 x) {
-   if (kStreamNt) {
-      const v4f_t v = {x.x, x.y, x.z, x.w};
-      __builtin_nontemporal_store(v, (v4f_t*)p);
-   } else {
-      *p = x;
-   }
+   const v4f_t v = {x.x, x.y, x.z, x.w};
+   __builtin_nontemporal_store(v, (v4f_t*)p);
 }
 __device__ __forceinline__ uint2 ld_stream(const uint2* p) {
-   if (kStreamNt) {
-      const v2u_t v = __builtin_nontemporal_load((const v2u_t*)p);
-      return make_uint2(v.x, v.y);
-   }
-   return *p;
+   const v2u_t v = __builtin_nontemporal_load((const v2u_t*)p);
+   return make_uint2(v.x, v.y);
 }
 __device__ __forceinline__ void st_stream(uint2* p, uint2 x) {
-   if (kStreamNt) {
-      const v2u_t v = {x.x, x.y};
-      __builtin_nontemporal_store(v, (v2u_t*)p);
-   } else {
-      *p = x;
-   }
+   const v2u_t v = {x.x, x.y};
+   __builtin_nontemporal_store(v, (v2u_t*)p);
 }
-__device__ __forceinline__ uint32_t ld_stream(const uint32_t* p) { return kStreamNt ? __builtin_nontemporal_load(p) : *p; }
-__device__ __forceinline__ void st_stream(uint32_t* p, uint32_t x) {
-   if (kStreamNt)
-      __builtin_nontemporal_store(x, p);
-   else
-      *p = x;
-}
+__device__ __forceinline__ uint32_t ld_stream(const uint32_t* p) { return __builtin_nontemporal_load(p); }
+__device__ __forceinline__ void st_stream(uint32_t* p, uint32_t x) { __builtin_nontemporal_store(x, p); }
 
 // ---- path state planes (device_types.h PathState): streamed like the other per-path arrays -------------------------------
 __device__ __forceinline__ float4 ld_rec(const float4* p) { return ld_stream(p); }

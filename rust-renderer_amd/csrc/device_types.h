@@ -248,7 +248,7 @@ struct LaunchCfg {
    uint32_t num_cus;
    uint32_t closest_blocks_per_cu, shadow_blocks_per_cu;
    bool count_visits;
-   uint32_t fused_blocks_per_cu = 4;  // k_path_fused (kernels.hip UH_FUSED_BLOCKS)
+   uint32_t fused_blocks_per_cu = 4;  // k_path_fused's grid (option "fused_bounces" 2..8); its registers and LDS are sized for kernels.hip kFusedBlocks
 };
 
 void launch_generate(const LaunchCfg&, const FrameParams&, const PathState&, Control*, uint32_t sample);

@@ -21,26 +21,9 @@ namespace uh {
 
 constexpr int kBlock = 256;                 // 4 waves
 constexpr int kWavesPerBlock = kBlock / 64;
-#ifndef UH_SUN_RAYS_PER_LANE
-#define UH_SUN_RAYS_PER_LANE 2  // k_trace_sun_grid (inline records): chains of dependent loads a lane keeps in flight
-#endif
-#ifndef UH_SHADE_HIT_BLOCKS
-#define UH_SHADE_HIT_BLOCKS 4  // blocks per CU the register budget of k_shade_hit is sized for
-#endif
-#ifndef UH_LDS_STACK
-#define UH_LDS_STACK 16
-#endif
-// Build-time experiments of round 5 on the traversal step (profiles/README.md "k_trace_closest, round 5"; tools/ab.sh compares builds):
-#ifndef UH_PK_SLAB
-#define UH_PK_SLAB 0  // 1: the slab test's 24 fused multiply-adds as 12 v_pk_fma_f32 (near and far plane of an axis in one instruction)
-#endif
-#ifndef UH_GATE_LEAVES
-#define UH_GATE_LEAVES 0  // k > 0: lanes at a leaf wait (no load, no test) until k lanes of the wave stand at one, a lane has waited UH_GATE_WAIT iterations, or no lane is at a node
-#endif
-#ifndef UH_GATE_WAIT
-#define UH_GATE_WAIT 3
-#endif
-constexpr int kLdsStack = UH_LDS_STACK;      // per-lane traversal stack entries kept in LDS (16 KiB per 256-thread block)
+constexpr int kSunRaysPerLane = 2;   // k_trace_sun_grid (inline records): chains of dependent loads a lane keeps in flight
+constexpr int kShadeHitBlocks = 4;   // blocks per CU the register budget of k_shade_hit is sized for
+constexpr int kLdsStack = 16;        // per-lane traversal stack entries kept in LDS (16 KiB per 256-thread block)
 constexpr int kSpillStack = (int)kTraversalStackEntries - kLdsStack;             // overflow entries in private memory (rarely touched); the host refuses trees deeper than the two together hold
 
 // ------------------------------------------------------------------------------------------
@@ -109,15 +92,6 @@ struct Trav {
    Hit best;
    int sp;
    uint32_t cur;
-   // the quantisation frame of `cur` when the lane DESCENDED into it from its parent (node_quant.h qn_inherit): origin, and the three
-   // step exponent bytes - 0 = none (cur was popped, is a leaf, or is the root: the visit loads the record's first quad)
-#if UH_INHERIT_FRAME
-   float fx, fy, fz;
-   uint32_t fexp;
-#endif
-#if UH_GATE_LEAVES
-   uint32_t wait;  // iterations this lane has stood at a leaf without testing it
-#endif
 };
 
 __device__ __forceinline__ void trav_init(Trav& t, float4 ro, float4 rd, float tmin, float tmax, float tlimit) {
@@ -132,13 +106,6 @@ __device__ __forceinline__ void trav_init(Trav& t, float4 ro, float4 rd, float t
    t.best.key = 0xffffffffu;
    t.sp = 0;
    t.cur = 0;
-#if UH_GATE_LEAVES
-   t.wait = 0;
-#endif
-#if UH_INHERIT_FRAME
-   t.fx = t.fy = t.fz = 0.0f;
-   t.fexp = 0u;
-#endif
 }
 
 __device__ __forceinline__ void trav_push(Trav& t, uint32_t* lds_col, uint32_t* spill, uint32_t ref) {
@@ -169,29 +136,10 @@ __device__ __forceinline__ uint32_t trav_pop(Trav& t, const uint32_t* lds_col, c
 // the other hits. plane = origin + scale * q  =>  t = q * (scale * idir) + (origin - o) * idir.
 //   w0 = origin.xyz, step exponents (the node's FRAME) ; w1 = qlo.xyz, qhi.x ; w2 = qhi.y, qhi.z, child_base | n_tri << 29, tri_base
 // Child references are implicit (bvh.h): slot k is triangle packet tri_base + k below n_tri, node child_base + k - n_tri above.
-// The frame of the child the lane continues with is derived here (node_quant.h qn_inherit, restated: v_cvt_f32_ubyte, v_fma_f32,
-// v_ffbh_u32) and left in t.fx .. t.fexp: the next visit does not load that node's first quad.
 // Instruction diet: the near / far plane words are picked once per axis by the sign of idir instead of min/max per
 // plane; an empty slot is an inverted box (no child != empty test); only the nearest child is fully ordered
 // (3 comparators); pushes are branch-free (write always, advance the stack pointer by the hit bit).
 // Returns false when no child was hit: the caller pops (trav_step pops once for its node lanes and its leaf lanes together).
-// the frame of node child `next` (= node0 + slot) of the node (w0, w1, w2), or none when `next` is no node child that was hit
-__device__ __forceinline__ void inherit_frame(const uint4 w0, const uint4 w1, const uint4 w2, float sx, float sy, float sz, uint32_t node0, uint32_t next, bool to_node, Trav& t) {
-#if UH_INHERIT_FRAME
-   const uint32_t sh = ((next - node0) & 3u) << 3;
-   const uint32_t lx = (w1.x >> sh) & 0xffu, ly = (w1.y >> sh) & 0xffu, lz = (w1.z >> sh) & 0xffu;
-   const uint32_t hx = (w1.w >> sh) & 0xffu, hy = (w2.x >> sh) & 0xffu, hz = (w2.y >> sh) & 0xffu;
-   t.fx = fmaf((float)lx, sx, __uint_as_float(w0.x));
-   t.fy = fmaf((float)ly, sy, __uint_as_float(w0.y));
-   t.fz = fmaf((float)lz, sz, __uint_as_float(w0.z));
-   // exponent byte + bit length of the box's width in steps - 8, at least 1 (bit length of 0 is 0: __clz(0) = 32)
-   const int ex = (int)(w0.w & 0xffu) + (24 - __clz((int)((hx - lx) & 0xffu))), ey = (int)((w0.w >> 8) & 0xffu) + (24 - __clz((int)((hy - ly) & 0xffu))),
-             ez = (int)((w0.w >> 16) & 0xffu) + (24 - __clz((int)((hz - lz) & 0xffu)));
-   const uint32_t packed = (uint32_t)(ex < 1 ? 1 : ex) | ((uint32_t)(ey < 1 ? 1 : ey) << 8) | ((uint32_t)(ez < 1 ? 1 : ez) << 16);
-   t.fexp = to_node ? packed : 0u;
-#endif
-}
-
 // CAP (closest-hit order, k_path_fused): children beyond t.tlimit are culled as in a visibility walk - the kernel's shadow rays go
 // through the closest-hit walk (occluded <=> the closest hit lies within the limit) beside the other lanes' bounce rays
 template <bool ANY, bool CAP = false>
@@ -214,22 +162,11 @@ __device__ __forceinline__ bool node_compute(const uint4 w0, const uint4 w1, con
 #pragma unroll
    for (int k = 0; k < 4; k++) cr[k] = ((uint32_t)k < n_tri ? tri0 : node0) + (uint32_t)k;
    bool hit[4];
-#if UH_PK_SLAB
-   typedef float f2_t __attribute__((ext_vector_type(2)));
-   const f2_t ax2 = {ax, ax}, ay2 = {ay, ay}, az2 = {az, az}, bx2 = {bx, bx}, by2 = {by, by}, bz2 = {bz, bz};
-#endif
 #pragma unroll
    for (int k = 0; k < 4; k++) {
-#if UH_PK_SLAB
-      const f2_t qx = {(float)((qnx >> (8 * k)) & 0xffu), (float)((qfx >> (8 * k)) & 0xffu)}, qy = {(float)((qny >> (8 * k)) & 0xffu), (float)((qfy >> (8 * k)) & 0xffu)},
-                 qz = {(float)((qnz >> (8 * k)) & 0xffu), (float)((qfz >> (8 * k)) & 0xffu)};
-      const f2_t tx = __builtin_elementwise_fma(qx, ax2, bx2), ty = __builtin_elementwise_fma(qy, ay2, by2), tz = __builtin_elementwise_fma(qz, az2, bz2);
-      const float t0x = tx.x, t1x = tx.y, t0y = ty.x, t1y = ty.y, t0z = tz.x, t1z = tz.y;
-#else
       const float t0x = fmaf((float)((qnx >> (8 * k)) & 0xffu), ax, bx), t1x = fmaf((float)((qfx >> (8 * k)) & 0xffu), ax, bx);
       const float t0y = fmaf((float)((qny >> (8 * k)) & 0xffu), ay, by), t1y = fmaf((float)((qfy >> (8 * k)) & 0xffu), ay, by);
       const float t0z = fmaf((float)((qnz >> (8 * k)) & 0xffu), az, bz), t1z = fmaf((float)((qfz >> (8 * k)) & 0xffu), az, bz);
-#endif
       const float tnear = fmaxf(fmaxf(t0x, t0y), fmaxf(t0z, t.tmin));
       const float tfar = fminf(fminf(t1x, t1y), fminf(t1z, tcap));
       hit[k] = tnear <= tfar;
@@ -258,7 +195,6 @@ __device__ __forceinline__ bool node_compute(const uint4 w0, const uint4 w1, con
          if (p2) trav_push(t, lds_col, spill, cr[2]);
       }
       t.cur = next;
-      inherit_frame(w0, w1, w2, sx, sy, sz, node0, next, any && !(next & kLeafBit), t);
       return any;
    }
    {
@@ -292,14 +228,13 @@ __device__ __forceinline__ bool node_compute(const uint4 w0, const uint4 w1, con
       if (tn[1] < INFINITY) trav_push(t, lds_col, spill, cr[1]);
    }
    t.cur = cr[0];
-   inherit_frame(w0, w1, w2, sx, sy, sz, node0, cr[0], tn[0] < INFINITY && !(cr[0] & kLeafBit), t);
    return tn[0] < INFINITY;
 }
 
 template <bool ANY>
 __device__ __forceinline__ void node_step(const uint4* __restrict__ nodes, Trav& t, uint32_t* lds_col, uint32_t* spill) {
    const uint4* n = nodes + kNodeStride16 * (size_t)t.cur;
-   const uint4 w0 = n[0], w1 = n[1], w2 = n[2];  // (this walk loads every node whole: the stored frame is the inherited one, bit for bit)
+   const uint4 w0 = n[0], w1 = n[1], w2 = n[2];
    if (!node_compute<ANY>(w0, w1, w2, t, lds_col, spill)) t.cur = trav_pop(t, lds_col, spill);
 }
 
@@ -380,10 +315,7 @@ struct alignas(16) RayPool {
 
 __device__ __forceinline__ void dma16(const float4* gsrc, float4* lds_dst) {
    // lds_dst is wave-uniform; lane l's 16 bytes land at lds_dst + l. aux = 2: the nt cache policy
-   if (kStreamNt)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 2);
-   else
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
+   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 2);
 }
 __device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
@@ -498,31 +430,11 @@ __device__ __forceinline__ bool trav_step(const uint4* __restrict__ nodes, const
                                           uint32_t& n_nodes, uint32_t& n_tris) {
    const bool at_node = !(t.cur & kLeafBit);
    const uint32_t packet = t.cur & ~kLeafBit;
-#if UH_GATE_LEAVES
-   {  // the triangle branch (~70 instructions for the handful of lanes that stand at a leaf) only when enough lanes want it
-      const unsigned long long leaves = __ballot(!at_node), at_nodes = __ballot(at_node);
-      const bool run = (uint32_t)__popcll(leaves) >= (uint32_t)UH_GATE_LEAVES || at_nodes == 0ull || __ballot(!at_node && t.wait >= (uint32_t)UH_GATE_WAIT) != 0ull;
-      if (!at_node) {
-         if (!run) {
-            t.wait++;
-            return false;
-         }
-         t.wait = 0;
-      }
-   }
-#endif
    // nodes and triangle packets are both three-quad records: ONE address and ONE set of loads for the whole wave.
    // (Written as two branches, each with its own loads, the compiler gave the second branch's address the first
    // branch's destination registers and made it wait for them: the two groups' loads ran one after the other.)
    const uint4* rec = at_node ? nodes + kNodeStride16 * (size_t)packet : (const uint4*)tris + kTriStride16 * (size_t)packet;
-   // a lane that descended into this node brought the node's frame along (node_compute): it loads two quads, not three
-#if UH_INHERIT_FRAME
-   uint4 w0 = make_uint4(__float_as_uint(t.fx), __float_as_uint(t.fy), __float_as_uint(t.fz), t.fexp);
-   if (!(at_node && t.fexp != 0u)) w0 = rec[0];
-   uint4 w1 = rec[1], w2 = rec[2];
-#else
    uint4 w0 = rec[0], w1 = rec[1], w2 = rec[2];
-#endif
    // the packet's last two dwords are padding: without this the compiler loads them in the node branch only (a fourth load)
    asm volatile("" : "+v"(w2.z), "+v"(w2.w));
    bool pop;  // one pop for both groups: an LDS read and its wait once per iteration, not once per branch
@@ -541,12 +453,7 @@ __device__ __forceinline__ bool trav_step(const uint4* __restrict__ nodes, const
          pop = false;
       }
    }
-   if (pop) {
-      t.cur = trav_pop(t, lds_col, spill);
-#if UH_INHERIT_FRAME
-      t.fexp = 0u;  // a popped node's frame is in its record
-#endif
-   }
+   if (pop) t.cur = trav_pop(t, lds_col, spill);
    return t.cur == kEmptyRef;
 }
 
@@ -763,7 +670,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_sun_grid(SceneDev sc, FramePar
    // K rays per lane, each step of the chain (origin -> coarse cover -> cell record -> first list entry [-> its packet] -> throughput /
    // radiance) requested for all K before the first is used: the kernel is a chain of dependent round trips with a few instructions
    // between them, and a wave that keeps K chains in flight hides K times the latency (registers are no constraint: 40 at K = 1)
-   constexpr int K = UH_SUN_RAYS_PER_LANE;
+   constexpr int K = kSunRaysPerLane;
    typedef float f4_t __attribute__((ext_vector_type(4)));  // (arrays of HIP's float4 struct assigned under a condition end up in scratch)
    const f4_t* __restrict__ recs = reinterpret_cast<const f4_t*>(g.recs);       // INLINE
    const f4_t* __restrict__ tris = reinterpret_cast<const f4_t*>(sc.tris);      // plain lists: the packets
@@ -1302,7 +1209,7 @@ __device__ __forceinline__ bool select_light(const FrameParams& fp, const SceneD
    return false;
 }
 
-__global__ __launch_bounds__(kBlock, UH_SHADE_HIT_BLOCKS) void k_shade_hit(FrameParams fp, SceneDev sc, PathState ps, Control* ctl, DeviceStats* stats, uint32_t bounce) {
+__global__ __launch_bounds__(kBlock, kShadeHitBlocks) void k_shade_hit(FrameParams fp, SceneDev sc, PathState ps, Control* ctl, DeviceStats* stats, uint32_t bounce) {
    // c / 255.0f table in LDS: the 12 per-fetch table gathers were texture-addresser traffic (the
    // kernel ran 86 % TA-busy at 2 % VALU, profiles/r01c_*); LDS serves them at no TA cost
    __shared__ float s_lut[256];
@@ -1632,12 +1539,7 @@ __device__ __forceinline__ int sun_grid_query(const SunGridDev& g, const float4*
    }
 }
 
-#ifndef UH_FUSED_STAGGER
-#define UH_FUSED_STAGGER 0     // 1: the blocks of a CU offset against each other by quarters of a phase (k_path_fused STAGGER; measured 2.545 against 2.505 ms per frame: off)
-#endif
-#ifndef UH_FUSED_BLOCKS
-#define UH_FUSED_BLOCKS 4      // blocks per CU the kernel's registers and LDS are sized for
-#endif
+constexpr int kFusedBlocks = 4;  // blocks per CU the kernel's registers and LDS are sized for
 struct FusedTraceLds {
    uint32_t stack[kWavesPerBlock][kLdsStack][64];
    RayPool<2> pool[kWavesPerBlock];
@@ -1647,19 +1549,13 @@ struct FusedShadeLds {
    uint32_t miss[kWavesPerBlock][2][128];  // per wave: (position, id) of the paths that missed
 };
 template <bool COUNT, bool INLINE>
-__global__ __launch_bounds__(kBlock, UH_FUSED_BLOCKS) void k_path_fused(SceneDev sc, FrameParams fp, PathState ps, Control* ctl, DeviceStats* stats, SunGridDev g, bool use_grid,
-                                                                         bool sun_of_bounce0, uint32_t stagger_unit) {
+__global__ __launch_bounds__(kBlock, kFusedBlocks) void k_path_fused(SceneDev sc, FrameParams fp, PathState ps, Control* ctl, DeviceStats* stats, SunGridDev g, bool use_grid,
+                                                                      bool sun_of_bounce0) {
    constexpr uint32_t kFirst = 1;  // the paths are those of bounce 1's ray queue, their state lies in set 1 at their positions there
    // (positions fit 23 bits: the host fuses only when shard_cap < 2^23; bits 23..28: how many bounces follow the entry's ray)
    constexpr uint32_t kHasRay = 1u << 31, kSun = 1u << 30, kLight = 1u << 29, kLeftShift = 23, kLeftMask = 63u << kLeftShift, kPosMask = (1u << kLeftShift) - 1u;
    __shared__ float s_lut[256];
-#if UH_FUSED_BLOCKS >= 6
-   constexpr uint32_t kLdsMeshes = 4, kLdsTextures = 2;    // (26.6 KiB of LDS per block: the mesh and texture records from global memory)
-#elif UH_FUSED_BLOCKS >= 5
-   constexpr uint32_t kLdsMeshes = 48, kLdsTextures = 32;  // (32 KiB of LDS per block)
-#else
    constexpr uint32_t kLdsMeshes = 128, kLdsTextures = 64;
-#endif
    __shared__ MeshShade s_mesh[kLdsMeshes];
    __shared__ TexInfo s_tex[kLdsTextures];
    __shared__ union {
@@ -1692,13 +1588,7 @@ __global__ __launch_bounds__(kBlock, UH_FUSED_BLOCKS) void k_path_fused(SceneDev
    // k_shade_hit(0) scattered) are asked here instead of by a k_trace_sun_grid / k_trace_shadow pair in front of this kernel - the grid
    // on the spot, what it does not answer as the entry's sun ray in the first trace phase. (Not when lights are on: bounce 0's light
    // rays are the wavefront's, and they come after the sun rays.)
-   // STAGGER: the blocks of a CU would run their phases in step - all trace, all drain their last rays, all shade. The block of
-   // dispatch round r (blockIdx / stagger_unit: a CU's resident blocks come from different rounds) therefore puts only the first
-   // 1 - (r mod 4) / 4 of its range into the first list and the rest straight into the second: its phases are [part], [all], ..,
-   // [rest] - one more than the others', offset against theirs by a quarter, a half, three quarters of a phase - and one block's
-   // drain runs under the others' full lists
-   const uint32_t n_range = hi - lo, round = (blockIdx.x / (stagger_unit ? stagger_unit : 1u)) & 3u;
-   const uint32_t n_first = stagger_unit ? ((n_range * (4u - round) / 4u + 63u) & ~63u) < n_range ? ((n_range * (4u - round) / 4u + 63u) & ~63u) : n_range : n_range;
+   const uint32_t n_range = hi - lo;
    const uint32_t left1 = (fp.num_bounces - 2u) << kLeftShift;  // bounce 1's rays
    for (uint32_t i0 = 0; i0 < n_range; i0 += kBlock) {
       const uint32_t i = i0 + threadIdx.x;
@@ -1719,18 +1609,15 @@ __global__ __launch_bounds__(kBlock, UH_FUSED_BLOCKS) void k_path_fused(SceneDev
          if (r == 2) e |= kSun;
          to_tree = r == 2 && use_grid;
       }
-      if (valid) {
-         if (i < n_first) lists[0][i] = e;
-         else lists[1][i - n_first] = e;
-      }
+      if (valid) lists[0][i] = e;
       if (sun_of_bounce0) {
          w_sun += (uint32_t)__popcll(__ballot(valid));
          w_sun_tree += (uint32_t)__popcll(__ballot(to_tree));
       }
    }
    if (threadIdx.x == 0) {
-      s_count[0] = n_first;
-      s_count[1] = n_range - n_first;
+      s_count[0] = n_range;
+      s_count[1] = 0;
       s_cursor = 0;
    }
    __syncthreads();
@@ -2392,7 +2279,7 @@ void launch_flush_survivors(const LaunchCfg& c, const FrameParams& fp, const Pat
 void launch_path_fused(const LaunchCfg& c, const FrameParams& fp, const SceneDev& sc, const PathState& ps, Control* ctl, DeviceStats* stats, const SunGridDev& g,
                        bool use_grid, bool sun_of_bounce0) {
    const dim3 grid = sharded_grid(c.num_cus * c.fused_blocks_per_cu);
-#define UH_FUSED(COUNT, INLINE) k_path_fused<COUNT, INLINE><<<grid, kBlock, 0, c.stream>>>(sc, fp, ps, ctl, stats, g, use_grid, sun_of_bounce0, UH_FUSED_STAGGER ? c.num_cus : 0u)
+#define UH_FUSED(COUNT, INLINE) k_path_fused<COUNT, INLINE><<<grid, kBlock, 0, c.stream>>>(sc, fp, ps, ctl, stats, g, use_grid, sun_of_bounce0)
    if (use_grid && g.recs) {
       if (c.count_visits) UH_FUSED(true, true);
       else UH_FUSED(false, true);

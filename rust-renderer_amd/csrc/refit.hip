@@ -108,35 +108,28 @@ __global__ __launch_bounds__(kBlock) void k_refit_boxes(const uint4* __restrict_
    }
 }
 
-// pass 2, one thread per node of one BFS level, root level first: the node takes its own frame (UH_INHERIT_FRAME = 1: the frame is in
-// its record already - written by its parent's thread one level up; only the root takes its own), its children's padded boxes are quantised in it exactly as bvh_build.cpp
-// quantise_tree does (node_quant.h: the same functions), and the frame every node child inherits goes into that child's record
+// pass 2, one thread per node of one BFS level: the node takes its own frame and its children's padded boxes are quantised in it
+// exactly as bvh_build.cpp quantise_tree does (node_quant.h: the same functions)
 __global__ __launch_bounds__(kBlock) void k_refit_quantise(uint4* __restrict__ nodes, const float* __restrict__ node_box, const float* __restrict__ world_corners, uint32_t first,
                                                            uint32_t count) {
    uint32_t j = blockIdx.x * kBlock + threadIdx.x;
    if (j >= count) return;
    const uint32_t ni = first + j;
    uint4* nd = nodes + kNodeStride16 * (size_t)ni;
-   const uint4 w0 = nd[0], w2 = nd[2];
-   const uint32_t meta = w0.w;
+   const uint32_t meta = nd[0].w;
+   const uint4 w2 = nd[2];
    const uint32_t n_tri = (meta >> kMetaTriShift) & 7u, n_child = (meta >> kMetaChildShift) & 7u;
    const uint32_t child_base = w2.z & kChildBaseMask, tri_base = w2.w;
    float lo[4][3], hi[4][3], tlo[3], thi[3];
    child_boxes(node_box, world_corners, n_tri, n_child, child_base, tri_base, lo, hi, tlo, thi);
-   float origin[3] = {__uint_as_float(w0.x), __uint_as_float(w0.y), __uint_as_float(w0.z)};
-   uint32_t exps = meta & 0xffffffu;
-   if (ni == 0 || !UH_INHERIT_FRAME) qn_own_frame(lo, hi, n_child, origin, exps);
-   uint32_t qlo[3], qhi[3], child_exps[4] = {0, 0, 0, 0};
-   float child_origin[4][3];
-   qn_quantise(origin, exps, lo, hi, n_tri, n_child, qlo, qhi, child_origin, child_exps, UH_INHERIT_FRAME != 0);
+   float origin[3];
+   uint32_t exps;
+   qn_own_frame(lo, hi, n_child, origin, exps);
+   uint32_t qlo[3], qhi[3];
+   qn_quantise(origin, exps, lo, hi, n_child, qlo, qhi);
    nd[0] = make_uint4(__float_as_uint(origin[0]), __float_as_uint(origin[1]), __float_as_uint(origin[2]), (meta & 0xff000000u) | exps);
    nd[1] = make_uint4(qlo[0], qlo[1], qlo[2], qhi[0]);
    nd[2] = make_uint4(qhi[1], qhi[2], child_base | (n_tri << kChildBaseBits), tri_base);
-   for (uint32_t k = n_tri; UH_INHERIT_FRAME && k < n_child && k < 4; k++) {
-      uint4* cd = nodes + kNodeStride16 * (size_t)(child_base + k - n_tri);
-      const uint32_t cmeta = cd[0].w;  // the child's own counts stay
-      cd[0] = make_uint4(__float_as_uint(child_origin[k][0]), __float_as_uint(child_origin[k][1]), __float_as_uint(child_origin[k][2]), (cmeta & 0xff000000u) | child_exps[k]);
-   }
 }
 
 }  // namespace
@@ -148,7 +141,7 @@ void launch_refit(const LaunchCfg& c, const RefitArgs& a) {
       const uint32_t first = a.level_start[l], count = a.level_start[l + 1] - first;
       if (count) k_refit_boxes<<<dim3((count + kBlock - 1) / kBlock), kBlock, 0, c.stream>>>(a.nodes, a.node_box, a.world_corners, first, count);
    }
-   for (uint32_t l = 0; l < a.num_levels; l++) {  // frames and planes: root to leaves (a node's frame is inherited from its parent's)
+   for (uint32_t l = 0; l < a.num_levels; l++) {  // frames and planes: a level per launch, as the boxes
       const uint32_t first = a.level_start[l], count = a.level_start[l + 1] - first;
       if (count) k_refit_quantise<<<dim3((count + kBlock - 1) / kBlock), kBlock, 0, c.stream>>>(a.nodes, a.node_box, a.world_corners, first, count);
    }

@@ -8,12 +8,10 @@
 //   the full-precision box; empty slots are inverted boxes; level_start describes the breadth-first levels.
 #include <cmath>
 #include <cstdio>
-#include <cstring>
 #include <cstdlib>
 #include <vector>
 
 #include "bvh.h"
-#include "node_quant.h"
 
 using namespace uh;
 
@@ -101,22 +99,6 @@ static int check(const std::vector<float>& corners, int threads, const char* nam
                continue;
             }
             node_refs[c]++;
-            {  // the child's stored frame IS the one a traversal derives from this node's frame and the child's quantised box here
-               // (node_quant.h qn_inherit - kernels.hip inherit_frame restates it), and 255 of its steps cover the child's padded box
-               uint32_t ql[3], qh[3], ce = 0;
-               float co[3];
-               for (int a = 0; a < 3; a++) {
-                  ql[a] = (q.qlo[a] >> (8 * k)) & 0xff;
-                  qh[a] = (q.qhi[a] >> (8 * k)) & 0xff;
-               }
-               qn_inherit(q.origin, q.meta & 0xffffffu, ql, qh, co, ce);
-               const Node4C& cq = out.cnodes[c];
-               if (UH_INHERIT_FRAME && (std::memcmp(co, cq.origin, sizeof(co)) != 0 || ce != (cq.meta & 0xffffffu))) fail("a child's stored frame is not the inherited one", ni, c);
-               for (int a = 0; a < 3; a++) {
-                  const double top = (double)co[a] + 255.0 * std::ldexp(1.0, (int)((ce >> (8 * a)) & 0xff) - 127);
-                  if (UH_INHERIT_FRAME && geometry && (!((double)co[a] <= (double)lo[a]) || !(top >= (double)hi[a]))) fail("the inherited frame does not cover the child's padded box", ni, c);
-               }
-            }
             // child's own children must lie inside this slot's box (boxes are padded outwards at every level)
             const NodeW& ch = out.nodes[c];
             for (int j = 0; j < 4; j++)

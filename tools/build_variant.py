@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""An experiment's library: csrc/kernels.hip compiled with extra -D switches, linked with the default build's other objects.
-  python tools/build_variant.py <name> -DUH_X=1 ...   ->  rust-renderer_amd/libuh_<name>.so   (UTOPIAN_HIP_LIB / tools/ab.sh take it)"""
+"""A measurement library: csrc/kernels.hip compiled with extra -D switches, linked with the default build's other objects. Its use is
+the instrumented build of tools/fused_phase_profile.py (kernels.hip UH_FUSED_PROFILE, the only switch the kernels read):
+  python tools/build_variant.py prof -DUH_FUSED_PROFILE   ->  rust-renderer_amd/libuh_prof.so   (UTOPIAN_HIP_LIB takes it)"""
 import os
 import subprocess
 import sys
