@@ -524,9 +524,11 @@ int uh_mgpu_set_option(uh_mgpu* group, const char* name, int value);
  * GATES: view->raytracing_supported == 0 skips both ray-traced passes and leaves their images as they are (mod.rs:107,134);
  * UH_HYBRID_RT_REFLECTIONS with view->ibl_enabled == 1 is UH_ERR_INVALID_ARGUMENT - and nothing runs - until the IBL maps (irradiance,
  * specular, BRDF LUT of ibl.rs) have been built with UH_HYBRID_ENVIRONMENT, below; mask bits, UH_ERR_NOT_BUILT and moved instances with
- * view->rebuild_tlas as for uh_render_frame (bits above UH_HYBRID_ENVIRONMENT, below, are ignored).
+ * view->rebuild_tlas as for uh_render_frame (bits above UH_HYBRID_SHADOW_MAPS, below, are ignored).
  * STREAM ORDER: uh_render_hybrid enqueues like a frame (behind the frames in flight, ahead of those that follow); uh_read_hybrid and
- * uh_get_hybrid_stats wait for all work of the context and are complete on return.
+ * uh_get_hybrid_stats wait for all work of the context and are complete on return. The exception is UH_HYBRID_SHADOW_MAPS, below: a
+ * call that renders shadow maps BLOCKS the host until the frames in flight and the pass's binning have finished (it reads the
+ * binning's totals back to size its buffers); the passes after it are enqueued as usual.
  * Arithmetic: DESIGN.md section 2, "Hybrid passes". */
 enum { UH_HYBRID_RT_SHADOWS = 1u << 0, UH_HYBRID_GBUFFER = 1u << 1, UH_HYBRID_RT_REFLECTIONS = 1u << 2, UH_HYBRID_ALL = 7 };
 /* which image uh_read_hybrid copies out (W*H texels each) */
@@ -566,9 +568,10 @@ int uh_get_hybrid_stats(uh_ctx* ctx, UhHybridStats* out);
  *                       8-bit image of the layout and channel order of uh_read_output_bgra8 (B, G, R, A = 255), row 0 at the top
  * UH_HYBRID_FRAME runs all seven: rt_shadows (previous G-buffer), G-buffer, rt_reflections, SSAO, deferred, sky, present.
  * THE REFERENCE'S DEFAULTS (prototype/src/main.rs) SET shadows_enabled, ibl_enabled AND cubemap_enabled TO 1: a caller of these passes
- * must clear them, or (ibl_enabled, cubemap_enabled) build the maps with UH_HYBRID_ENVIRONMENT, below. UH_ERR_INVALID_ARGUMENT with a
- * message, and nothing runs, for UH_HYBRID_DEFERRED with view->shadows_enabled == 1 (the cascaded shadow maps are raster passes outside
- * this library) or, before the first build, view->ibl_enabled == 1 (the IBL maps of ibl.rs), for UH_HYBRID_SKY with
+ * must clear them, or build the maps they read: shadows_enabled with UH_HYBRID_SHADOW_MAPS, ibl_enabled and cubemap_enabled with
+ * UH_HYBRID_ENVIRONMENT, below. UH_ERR_INVALID_ARGUMENT with a
+ * message, and nothing runs, for UH_HYBRID_DEFERRED with view->shadows_enabled == 1 before the first shadow-map render (the cascaded
+ * shadow maps of shadow.rs) or, before the first build, view->ibl_enabled == 1 (the IBL maps of ibl.rs), for UH_HYBRID_SKY with
  * view->cubemap_enabled == 1 before the first build (the environment cube of ibl.rs), and for UH_HYBRID_DEFERRED with view->num_lights
  * above the lights added with uh_add_light. view->marching_cubes_enabled is not read: meshes of uh_add_isosurface_mesh are scene
  * geometry and go through the G-buffer like any other.
@@ -618,7 +621,7 @@ int uh_get_hybrid_frame_stats(uh_ctx* ctx, UhHybridFrameStats* out); /* waits; a
  *   UH_HYBRID_RT_REFLECTIONS with view->ibl_enabled == 1  the hit shader's IBL branch (rt_reflections.rchit:50-61): imageBasedLighting of
  *                                                       the hit, stored like the non-IBL payload; the miss branch is unchanged
  * On a context whose maps were never built, these three are refused as before (UH_ERR_INVALID_ARGUMENT, nothing runs); the message
- * names UH_HYBRID_ENVIRONMENT. view->shadows_enabled == 1 stays refused for the deferred pass.
+ * names UH_HYBRID_ENVIRONMENT. view->shadows_enabled == 1 needs the shadow maps of UH_HYBRID_SHADOW_MAPS, below.
  * RESOURCES: the four maps (about 93 MB) are allocated by the first call whose mask holds UH_HYBRID_ENVIRONMENT (UH_ERR_OUT_OF_MEMORY
  * when that fails) and freed by uh_destroy; a context that never sets the bit allocates nothing for them. A build changes no other
  * image of the hybrid graph and nothing in UhStats or UhHybridStats.
@@ -649,6 +652,56 @@ UH_LAYOUT_ASSERT(sizeof(UhEnvironmentStats) == 64 && offsetof(UhEnvironmentStats
                     offsetof(UhEnvironmentStats, eye) == 32,
                  "UhEnvironmentStats (64 B)");
 int uh_get_environment_stats(uh_ctx* ctx, UhEnvironmentStats* out);
+
+/* ---- cascaded shadow maps: setup_shadow_pass (shadow.rs) and the deferred pass's calculateShadow ---------------------------
+ * uh_shadow_cascades is setup_shadow_pass's host arithmetic: four cascades, split lambda 0.927 between z_near and z_far, each an
+ * orthographic light view of the sphere around its slice of the view frustum (corners from inverse(projection * view)). It takes no
+ * context, needs no device, and fills the UBO_shadowmapParams of deferred.frag:28-32 byte for byte (column-major matrices,
+ * split_depth = z_near + split * (z_far - z_near)). UH_ERR_INVALID_ARGUMENT, and *out untouched, for z_near <= 0, z_far <= z_near,
+ * a non-finite input, a singular projection * view, a zero sun_dir or one parallel to +Y (look_at_rh degenerates), or any
+ * non-finite result. The order of its float32 operations: DESIGN.md section 2, "Shadow maps".
+ * uh_set_shadowmap_params copies params into the context (host state only: it waits for nothing). Every value must be finite and
+ * every matrix's last row (0, 0, 0, 1), as the orthographic matrices of setup_shadow_pass are; UH_ERR_INVALID_ARGUMENT otherwise.
+ * A caller that runs its own setup_shadow_pass passes its output here.
+ * UH_HYBRID_SHADOW_MAPS (bit 8) of uh_render_hybrid renders all four cascades of the params last set into four D32 layers of
+ * shadow_map_size^2 (option, default 4096): every triangle of every mesh, no culling, depth test LESS_OR_EQUAL cleared to 1.0, under
+ * the Y-flipped viewport (pass.rs:260-267). It waits on the host: see STREAM ORDER above. It runs first in the call, before
+ * rt_shadows (mod.rs:91-98), and only with
+ * view->shadows_enabled == 1: otherwise the bit is a no-op and its pass_ms is 0 (setup_shadow_pass's early return). Without params
+ * set, the call is UH_ERR_INVALID_ARGUMENT and nothing runs. UH_HYBRID_FRAME stays 0x7f: the reference's default view is
+ * UH_HYBRID_FRAME | UH_HYBRID_SHADOW_MAPS (| UH_HYBRID_ENVIRONMENT).
+ * CONSUMER: UH_HYBRID_DEFERRED with view->shadows_enabled == 1 multiplies by calculateShadow (shadow_mapping.glsl: cascade choice,
+ * 3 x 3 PCF of bilinear depth reads, 0.3 / 1.0 per tap) instead of the rt_shadows factor, once maps exist (rendered earlier in the
+ * same call or by an earlier one), with the params snapshot the maps were rendered with. Before that it is refused as before.
+ * READ-BACK: uh_read_shadow_map copies layer `cascade` (0..3): size^2 floats, row 0 the texel row at NDC y = +1 (the first row of the
+ * flipped viewport). UH_ERR_INVALID_ARGUMENT before the first render. Waits like uh_read_hybrid.
+ * RESOURCES: the maps (16 bytes per texel of one layer) and the binning buffers are allocated by the first call that renders them
+ * (UH_ERR_OUT_OF_MEMORY when that fails) and freed by uh_destroy; changing shadow_map_size frees them. A render that fails part way
+ * (UH_ERR_OUT_OF_MEMORY, UH_ERR_CAPACITY) leaves no maps: the deferred pass with shadows is refused until a render completes. The pass changes no other
+ * image, nothing in UhStats, UhHybridStats or UhHybridFrameStats. Arithmetic: DESIGN.md section 2, "Shadow maps". */
+typedef struct UhShadowmapParams {
+   float view_projection_matrices[4][16]; /* column-major, cascade c at [c] */
+   float cascade_splits[4];               /* split depths (view-space distances) */
+} UhShadowmapParams;
+UH_LAYOUT_ASSERT(sizeof(UhShadowmapParams) == 272 && offsetof(UhShadowmapParams, cascade_splits) == 256, "UhShadowmapParams (272 B)");
+enum { UH_HYBRID_SHADOW_MAPS = 1u << 8, UH_SHADOW_CASCADES = 4 };
+int uh_shadow_cascades(const float view[16], const float projection[16], float z_near, float z_far, const float sun_dir[3], UhShadowmapParams* out);
+int uh_set_shadowmap_params(uh_ctx* ctx, const UhShadowmapParams* params);
+int uh_read_shadow_map(uh_ctx* ctx, int cascade, float* out);
+/* the last shadow-map render: pass_ms its hipEvent time, renders the number so far, size the maps' size, triangles[c] the triangles
+ * of cascade c that reached the rasteriser (after the setup's rejects; a triangle clipped to the guard band counts once per piece),
+ * params the snapshot the deferred pass reads. All zero before the first render. Waits for all work of the context. */
+typedef struct UhShadowMapStats {
+   float pass_ms;
+   uint32_t renders;
+   uint32_t size;
+   uint32_t triangles[4];
+   uint32_t reserved;
+   UhShadowmapParams params;
+} UhShadowMapStats;
+UH_LAYOUT_ASSERT(sizeof(UhShadowMapStats) == 304 && offsetof(UhShadowMapStats, triangles) == 12 && offsetof(UhShadowMapStats, params) == 32,
+                 "UhShadowMapStats (304 B)");
+int uh_get_shadow_map_stats(uh_ctx* ctx, UhShadowMapStats* out);
 
 #ifdef __cplusplus
 }

@@ -160,6 +160,8 @@ class Camera {
    Mat4 get_view() const { return Mat4::look_at_rh(pos_, target_, {0, 1, 0}); }
    Mat4 get_projection() const { return Mat4::perspective_rh(fov_ * 3.14159265358979323846f / 180.0f, aspect_, near_, far_); }
    Vec3 get_position() const { return pos_; }
+   float get_near_plane() const { return near_; }
+   float get_far_plane() const { return far_; }
 
   private:
    Vec3 pos_, target_;
@@ -338,6 +340,20 @@ class Renderer {
       check(uh_get_environment_stats(ctx_, &s), "environment_stats");
       return s;
    }
+   // the cascaded shadow maps (utopian_hip.h "UH_HYBRID_SHADOW_MAPS"): the params the next render uses, one layer (size^2 depths,
+   // row 0 at NDC y = +1) and the last render's stats
+   void set_shadowmap_params(const UhShadowmapParams& params) { check(uh_set_shadowmap_params(ctx_, &params), "set_shadowmap_params"); }
+   std::vector<float> read_shadow_map(int cascade) {
+      const UhShadowMapStats s = shadow_map_stats();
+      std::vector<float> out((size_t)s.size * s.size);
+      check(uh_read_shadow_map(ctx_, cascade, out.data()), "read_shadow_map");
+      return out;
+   }
+   UhShadowMapStats shadow_map_stats() {
+      UhShadowMapStats s;
+      check(uh_get_shadow_map_stats(ctx_, &s), "shadow_map_stats");
+      return s;
+   }
    // uh_set_option: "device_build", "frames_in_flight", ... (DESIGN.md "Options")
    void set_option(const char* name, int value) { check(uh_set_option(ctx_, name, value), name); }
    // marching_cubes.rs:17-83 / marching_cubes.comp: the density field's iso-surface, extracted on the GPU and added
@@ -418,6 +434,15 @@ inline void build_path_tracing_render_graph(Graph& graph) {
 }
 
 // ---- prototype/src/main.rs: view defaults (:55-86) and the frame protocol (:460-471, :545-546) ----
+// setup_shadow_pass (shadow.rs) for the camera's own near / far planes: uh_shadow_cascades, host arithmetic only
+inline UhShadowmapParams shadow_cascades(const Camera& camera, Vec3 sun_dir) {
+   UhShadowmapParams p;
+   const float sun[3] = {sun_dir.x, sun_dir.y, sun_dir.z};
+   const int st = uh_shadow_cascades(camera.get_view().m, camera.get_projection().m, camera.get_near_plane(), camera.get_far_plane(), sun, &p);
+   if (st != UH_OK) throw Error(st, "shadow_cascades: degenerate camera or sun direction");
+   return p;
+}
+
 inline ViewUniformData default_view_data(const Camera& camera, uint32_t width, uint32_t height) {
    ViewUniformData v;
    std::memset(&v, 0, sizeof(v));

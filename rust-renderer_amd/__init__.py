@@ -13,6 +13,7 @@ from .api import (  # noqa: F401
     load_library,
     make_light,
     make_material,
+    shadow_cascades,
     transform3x4,
 )
 from .build import build_library  # noqa: F401

@@ -43,6 +43,8 @@ from .types import (
     EnvironmentStats,
     HybridFrameStats,
     HybridStats,
+    ShadowmapParams,
+    ShadowMapStats,
     Reservoir,
     RestirRows,
     Stats,
@@ -497,6 +499,32 @@ class Renderer:
         self._check(api.get_hybrid_frame_stats(self._ctx, C.byref(s)))
         return s
 
+    # -- cascaded shadow maps (UH_HYBRID_SHADOW_MAPS; include/utopian_hip.h) ---------------
+    def _shadow_fn(self, name, argtypes):
+        self._hybrid_api()
+        fn = getattr(self._lib, "uh_" + name)
+        fn.argtypes, fn.restype = [C.c_void_p] + argtypes, C.c_int
+        return fn
+
+    def set_shadowmap_params(self, params):
+        """the cascades the next HYBRID_SHADOW_MAPS render uses: a ShadowmapParams (shadow_cascades, or the caller's own)"""
+        self._check(self._shadow_fn("set_shadowmap_params", [C.POINTER(ShadowmapParams)])(self._ctx, C.byref(params)))
+
+    def read_shadow_map(self, cascade):
+        """layer `cascade` of the shadow maps: (S, S) float32, row 0 at NDC y = +1"""
+        s = self.shadow_map_stats().size
+        if not s:
+            s = 16  # the library refuses the read before the first render
+        out = np.empty((s, s), dtype=np.float32)
+        self._check(self._shadow_fn("read_shadow_map", [C.c_int, C.c_void_p])(self._ctx, int(cascade), out.ctypes.data))
+        return out
+
+    def shadow_map_stats(self):
+        """UhShadowMapStats of the last shadow-map render"""
+        s = ShadowMapStats()
+        self._check(self._shadow_fn("get_shadow_map_stats", [C.POINTER(ShadowMapStats)])(self._ctx, C.byref(s)))
+        return s
+
     # -- stand-alone ray queries ----------------------------------------------------------
     def trace_closest(self, rays):
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
@@ -748,3 +776,20 @@ class FrameLoop:
         """camera / setting change: total_samples = 0 (main.rs:400-413)."""
         self.view.total_samples = 0
         self.renderer.reset_accumulation()
+
+
+def shadow_cascades(camera, sun_dir):
+    """setup_shadow_pass (shadow.rs) for `camera` (its own z_near / z_far) and `sun_dir`: a ShadowmapParams, by uh_shadow_cascades
+    (host arithmetic: no device needed)"""
+    lib = load_library()
+    fn = lib.uh_shadow_cascades
+    fp = C.POINTER(C.c_float)
+    fn.argtypes, fn.restype = [fp, fp, C.c_float, C.c_float, fp, C.POINTER(ShadowmapParams)], C.c_int
+    view = (C.c_float * 16)(*cam.to_glam(camera.get_view()).tolist())
+    proj = (C.c_float * 16)(*cam.to_glam(camera.get_projection()).tolist())
+    sun = (C.c_float * 3)(*[float(x) for x in sun_dir])
+    out = ShadowmapParams()
+    st = fn(view, proj, float(camera.z_near), float(camera.z_far), sun, C.byref(out))
+    if st != 0:
+        raise UtopianError(f"uh_shadow_cascades: {ERR_NAMES.get(st, st)}")
+    return out

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "bvh.h"
+#include "device_scan.h"
 #include "device_types.h"
 #include "utopian_hip.h"
 
@@ -66,10 +67,11 @@ struct DevBuf {
 
 }  // namespace
 
-// the hybrid graph's stages (uh_ctx::Hybrid::stage): its seven passes in the order of their UH_HYBRID_* bits, then the environment's
+// the hybrid graph's stages (uh_ctx::Hybrid::stage): its seven passes in the order of their UH_HYBRID_* bits, then the environment's,
+// then the shadow maps
 enum HybridStage : int {
    kStShadows, kStGbuffer, kStReflections, kStSsao, kStDeferred, kStSky, kStPresent, kHybridPasses,
-   kStEnvCube = kHybridPasses, kStEnvIrradiance, kStEnvSpecular, kStEnvLut, kHybridStages
+   kStEnvCube = kHybridPasses, kStEnvIrradiance, kStEnvSpecular, kStEnvLut, kStShadowMaps, kHybridStages
 };
 
 // One frame in flight: its own stream pair, hazard events, path state and queue control block.
@@ -253,6 +255,7 @@ struct uh_ctx {
    // options / stats
    bool count_visits = false, time_kernels = false, full_frame_restir = false;
    bool iso_reference = true;  // option "iso_reference_triangulation": uh_add_isosurface_mesh emits the reference's triangles (isosurface.hip)
+   uint32_t shadow_map_size = 4096;  // option "shadow_map_size": the cascaded shadow maps' size (shadow.rs: 4096)
    bool furnace = false;  // option "furnace": reference.rmiss compiled with FURNACE_TEST (a miss returns white whatever view.sky_enabled says)
    uint64_t frames = 0;
    float build_ms = 0.0f, last_frame_ms = 0.0f;
@@ -332,9 +335,12 @@ struct uh_ctx {
       hipEvent_t waits[2 * kMaxSlots + 1] = {};  // behind the frames in flight
       // one record per stage: stage k < kHybridPasses is bit k of UH_HYBRID_* (rt_shadows, G-buffer, rt_reflections, SSAO, deferred,
       // sky, present: the last call's), the environment's sub-passes follow (cube, irradiance, specular, BRDF LUT: the last build's)
+      // ms: the elapsed time, resolved from the two events by the first stats read after the stage ran and kept (a later read
+      // returns the same bits)
       struct Stage {
          hipEvent_t begin = nullptr, end = nullptr;
-         bool ran = false;
+         bool ran = false, timed = false;
+         float ms = 0.0f;
       } stage[kHybridStages];
       // the final frame's passes (SSAO, deferred, sky, present), allocated by the first call that asks for one of them
       DevBuf<uint16_t> ssao;
@@ -351,6 +357,19 @@ struct uh_ctx {
       DevBuf<float4> taps;                     // the irradiance filter's tap table
       uint32_t env_builds = 0;
       float env_sun[3] = {0, 0, 0}, env_eye[3] = {0, 0, 0};  // what the last build was made with
+      // the cascaded shadow maps (UH_HYBRID_SHADOW_MAPS), allocated by the first call that renders them; freed by a size change
+      DevBuf<float> smaps;                     // 4 layers of smap_size^2
+      DevBuf<uint32_t> s_tile_count, s_tile_cursor, s_rec_count, s_tri_mesh, s_chunks, s_entries;
+      DevBuf<unsigned long long> s_totals;     // the grand totals of the two scans: records, tile entries
+      DevBuf<uint4> s_records;
+      DevBuf<float> s_mats;                    // [cascade][mesh][16]
+      DevBuf<UhShadowmapParams> s_params;      // the snapshot the deferred pass reads
+      std::vector<float> s_mats_host;
+      uint64_t s_geom = 0;                     // geom_version of s_tri_mesh / s_rec_count
+      bool params_set = false;
+      UhShadowmapParams params{}, snapshot{}, pending{};  // the last uh_set_shadowmap_params; what the maps were rendered with;
+                                                          // what the render in progress uses
+      uint32_t s_renders = 0, smap_size = 0, s_tris[4] = {0, 0, 0, 0};
 
       // the three groups allocated on first use, each named once for allocation and uh_destroy: f(buffer, length), n pixels; a
       // group's last buffer is allocated last, its pointer says "allocated"
@@ -359,6 +378,10 @@ struct uh_ctx {
       }
       template <class F> void frame_images(size_t n, F&& f) {
          f(ssao, n), f(deferred, n), f(present, n), f(lights, UH_MAX_GPU_LIGHTS + 1), f(sky_counter, 1);
+      }
+      template <class F> void shadow_maps(F&& f) {
+         f(smaps, 0), f(s_tile_count, 0), f(s_tile_cursor, 0), f(s_rec_count, 0), f(s_tri_mesh, 0), f(s_chunks, 0), f(s_entries, 0),
+            f(s_totals, 0), f(s_records, 0), f(s_mats, 0), f(s_params, 0);
       }
       template <class F> void env_maps(F&& f) {
          const size_t cube = env_mip_offset(kEnvMips);
@@ -622,6 +645,7 @@ void uh_destroy(uh_ctx* c) {
       h.rt_images(0, release);
       h.frame_images(0, release);
       h.env_maps(release);
+      h.shadow_maps(release);
       h.meshes.release();
       h.vertices.release();
       h.indices.release();
@@ -2123,6 +2147,16 @@ int uh_set_option(uh_ctx* c, const char* name, int value) {
       c->iso_reference = value != 0;
    else if (n == "furnace")
       c->furnace = value != 0;  // applies to the frames enqueued from now on
+   else if (n == "shadow_map_size") {
+      if (!range(16, 8192)) return bad("must be 16..8192");
+      if ((uint32_t)value != c->shadow_map_size) {  // the maps go: the deferred pass with shadows is refused until they are rendered again
+         if (int st = sync_all(c)) return st;
+         c->hy.shadow_maps([](auto& b, size_t) { b.release(); });
+         c->hy.s_geom = 0;
+         c->hy.smap_size = 0;
+      }
+      c->shadow_map_size = (uint32_t)value;
+   }
    // ---- how the frames are scheduled
    else if (n == "overlap")
       c->overlap_miss = c->overlap_shadow = value != 0;  // k_shade_miss and the shadow traversals on the slot's side stream
@@ -2685,6 +2719,105 @@ static int env_alloc(uh_ctx* c) {
    return alloc_group(c, [&](auto f) { h.env_maps(f); });
 }
 
+// ---- the cascaded shadow maps (utopian_hip.h "UH_HYBRID_SHADOW_MAPS"; shadow_map.hip) ----
+// vp * W for every cascade and mesh: W the instance's 3x4 from the last build or refit with row (0, 0, 0, 1); element (r, c) summed
+// ((a(r,0) b(0,c) + a(r,1) b(1,c)) + a(r,2) b(2,c)) + a(r,3) b(3,c)
+static void cascade_mesh_matrices(const uh_ctx* c, const UhShadowmapParams& p, std::vector<float>& out) {
+   const size_t nm = c->meshes.size();
+   out.assign(4 * nm * 16, 0.0f);
+   for (int k = 0; k < 4; k++) {
+      const float* a = p.view_projection_matrices[k];
+      for (size_t m = 0; m < nm; m++) {
+         const float* o = c->meshes[m].o2w;
+         float w[16];  // column-major
+         for (int col = 0; col < 4; col++) {
+            for (int r = 0; r < 3; r++) w[4 * col + r] = o[4 * r + col];
+            w[4 * col + 3] = col == 3 ? 1.0f : 0.0f;
+         }
+         float* d = &out[((size_t)k * nm + m) * 16];
+         for (int col = 0; col < 4; col++)
+            for (int r = 0; r < 4; r++)
+               d[4 * col + r] = ((a[r] * w[4 * col] + a[4 + r] * w[4 * col + 1]) + a[8 + r] * w[4 * col + 2]) + a[12 + r] * w[4 * col + 3];
+      }
+   }
+}
+
+// count, scan, emit, resolve: the records' and tile entries' totals come back to the host in between (the buffers grow to them)
+static int render_shadow_maps(uh_ctx* c, const LaunchCfg& lc) {
+   uh_ctx::Hybrid& h = c->hy;
+   const uint32_t S = c->shadow_map_size, tiles_x = (S + kShadowTile - 1) / kShadowTile, tiles = 4 * tiles_x * tiles_x;
+   size_t ntri = 0;
+   for (const HostMesh& m : c->meshes) ntri += m.indices.size() / 3;
+   if (4 * ntri >= (1ull << 32)) return fail(c, UH_ERR_CAPACITY, "uh_render_hybrid: shadow maps of more than 2^30 triangles");
+   const auto grow = [&](auto& b, size_t n) -> int {
+      if (b.p && b.n >= n) return UH_OK;
+      const hipError_t e = b.alloc(n);
+      if (e != hipSuccess)
+         return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string("uh_render_hybrid: allocation: ") + hipGetErrorString(e));
+      return UH_OK;
+   };
+   for (int st : {grow(h.smaps, 4 * (size_t)S * S), grow(h.s_tile_count, tiles), grow(h.s_tile_cursor, tiles), grow(h.s_totals, 2),
+                  grow(h.s_params, 1), grow(h.s_mats, std::max<size_t>(1, 64 * c->meshes.size())),
+                  grow(h.s_chunks, std::max<size_t>(1, scan_chunk_count((uint32_t)std::max<size_t>(4 * ntri, tiles))))})
+      if (st) return st;
+   if (h.s_geom != c->geom_version || !h.s_rec_count.p) {
+      std::vector<uint32_t> tm;
+      tm.reserve(ntri);
+      for (size_t m = 0; m < c->meshes.size(); m++) tm.insert(tm.end(), c->meshes[m].indices.size() / 3, (uint32_t)m);
+      HIP_TRY(c, h.s_tri_mesh.alloc(std::max<size_t>(1, ntri)));
+      HIP_TRY(c, h.s_rec_count.alloc(std::max<size_t>(1, 4 * ntri)));
+      if (ntri) HIP_TRY(c, hipMemcpy(h.s_tri_mesh.p, tm.data(), ntri * sizeof(uint32_t), hipMemcpyHostToDevice));
+      h.s_geom = c->geom_version;
+   }
+   // until this render completes the maps and their params are invalid: a failure below leaves the deferred pass refused
+   h.smap_size = 0;
+   h.pending = h.params;
+   cascade_mesh_matrices(c, h.pending, h.s_mats_host);
+   if (!h.s_mats_host.empty())
+      HIP_TRY(c, hipMemcpyAsync(h.s_mats.p, h.s_mats_host.data(), h.s_mats_host.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+   HIP_TRY(c, hipMemcpyAsync(h.s_params.p, &h.pending, sizeof(UhShadowmapParams), hipMemcpyHostToDevice, c->stream));
+   HIP_TRY(c, hipMemsetAsync(h.s_tile_count.p, 0, tiles * sizeof(uint32_t), c->stream));
+   ShadowDev sd{};
+   sd.vertices = h.vertices.p;
+   sd.indices = h.indices.p;
+   sd.meshes = h.meshes.p;
+   sd.tri_mesh = h.s_tri_mesh.p;
+   sd.mats = h.s_mats.p;
+   sd.num_tris = (uint32_t)ntri;
+   sd.num_meshes = (uint32_t)c->meshes.size();
+   sd.size = S;
+   sd.tiles_x = tiles_x;
+   sd.rec_count = h.s_rec_count.p;
+   sd.tile_count = h.s_tile_count.p;
+   sd.tile_cursor = h.s_tile_cursor.p;
+   sd.maps = h.smaps.p;
+   launch_shadow_count(lc, sd);
+   unsigned long long totals[2] = {0, 0};
+   uint32_t first[4] = {0, 0, 0, 0};  // the first record of each cascade
+   if (ntri) device_exclusive_scan_u32(h.s_rec_count.p, (uint32_t)(4 * ntri), h.s_chunks.p, h.s_totals.p, c->stream);
+   device_exclusive_scan_u32(h.s_tile_count.p, tiles, h.s_chunks.p, h.s_totals.p + 1, c->stream);
+   HIP_TRY(c, hipMemcpyAsync(h.s_tile_cursor.p, h.s_tile_count.p, tiles * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+   HIP_TRY(c, hipStreamSynchronize(c->stream));
+   HIP_TRY(c, hipMemcpy(totals + 1, h.s_totals.p + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+   if (ntri) {
+      HIP_TRY(c, hipMemcpy(totals, h.s_totals.p, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+      for (int k = 1; k < 4; k++) HIP_TRY(c, hipMemcpy(first + k, h.s_rec_count.p + k * ntri, sizeof(uint32_t), hipMemcpyDeviceToHost));
+   }
+   if (totals[0] >= (1ull << 32) || totals[1] >= (1ull << 32))
+      return fail(c, UH_ERR_CAPACITY, "uh_render_hybrid: shadow maps with 2^32 or more triangle pieces or tile entries");
+   for (int st : {grow(h.s_records, std::max<size_t>(1, 3 * (size_t)totals[0])), grow(h.s_entries, std::max<size_t>(1, (size_t)totals[1]))})
+      if (st) return st;
+   sd.records = h.s_records.p;
+   sd.entries = h.s_entries.p;
+   launch_shadow_emit(lc, sd);
+   launch_shadow_resolve(lc, sd);
+   for (int k = 0; k < 4; k++) h.s_tris[k] = (k < 3 ? first[k + 1] : (uint32_t)totals[0]) - first[k];
+   h.snapshot = h.pending;
+   h.smap_size = S;
+   h.s_renders++;
+   return UH_OK;
+}
+
 int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    if (!view) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_render_hybrid: null view");
@@ -2695,11 +2828,15 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
                   "uh_render_hybrid: rt_reflections with view.ibl_enabled = 1 needs the IBL maps (irradiance, specular, BRDF LUT of ibl.rs), "
                   "which are not part of this library until a call with UH_HYBRID_ENVIRONMENT builds them; set that bit, or ibl_enabled = 0 "
                   "for the reflection pass's non-IBL branch");
+   const bool render_maps = (mask & UH_HYBRID_SHADOW_MAPS) && view->shadows_enabled == 1;
+   if (render_maps && !c->hy.params_set)
+      return fail(c, UH_ERR_INVALID_ARGUMENT,
+                  "uh_render_hybrid: UH_HYBRID_SHADOW_MAPS before uh_set_shadowmap_params (the cascades of uh_shadow_cascades or the caller's own)");
    if (mask & UH_HYBRID_DEFERRED) {
-      if (view->shadows_enabled == 1)
+      if (view->shadows_enabled == 1 && !c->hy.smap_size && !render_maps)
          return fail(c, UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: the deferred pass with view.shadows_enabled = 1 needs the cascaded shadow maps (shadow.rs), raster passes "
-                     "that are not part of this library; set shadows_enabled = 0 for the rt_shadows branch");
+                     "uh_render_hybrid: the deferred pass with view.shadows_enabled = 1 needs the cascaded shadow maps (shadow.rs), which a call "
+                     "with UH_HYBRID_SHADOW_MAPS renders; set that bit, or shadows_enabled = 0 for the rt_shadows branch");
       if (view->ibl_enabled == 1 && !maps)
          return fail(c, UH_ERR_INVALID_ARGUMENT,
                      "uh_render_hybrid: the deferred pass with view.ibl_enabled = 1 needs the IBL maps (irradiance, specular, BRDF LUT of ibl.rs), "
@@ -2792,12 +2929,25 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    const bool grid = c->cam_grid_enabled && c->cam_valid && c->cam_geom == c->geom_version && std::memcmp(mats, c->cam_mats, sizeof(mats)) == 0;
    const bool rt = view->raytracing_supported != 0;
    // every stage this call runs between its two events; the passes that do not run report 0, the environment's last build stays
-   for (int k = 0; k < kHybridPasses; k++) h.stage[k].ran = false;
+   // (a call that only renders shadow maps leaves the passes' records as they are)
+   if ((mask & (UH_HYBRID_FRAME | UH_HYBRID_ENVIRONMENT | UH_HYBRID_SHADOW_MAPS)) != UH_HYBRID_SHADOW_MAPS)
+      for (int k = 0; k < kHybridPasses; k++) h.stage[k].ran = false;
+   if (mask & UH_HYBRID_SHADOW_MAPS) h.stage[kStShadowMaps].ran = false;
    const auto begin = [&](int k) {
       h.stage[k].ran = true;
+      h.stage[k].timed = false;
       return hipEventRecord(h.stage[k].begin, c->stream);
    };
    const auto end = [&](int k) { return hipEventRecord(h.stage[k].end, c->stream); };
+   // setup_shadow_pass's four passes are added first (mod.rs:91-98)
+   if (render_maps) {
+      HIP_TRY(c, begin(kStShadowMaps));
+      int st = render_shadow_maps(c, lc);
+      const hipError_t e = st ? hipSuccess : end(kStShadowMaps);
+      if (st || e != hipSuccess) h.stage[kStShadowMaps].ran = false;  // no time for a render that did not complete
+      if (st) return st;
+      HIP_TRY(c, e);
+   }
    // pass order of build_render_graph (mod.rs:100-134, graph.rs:743): rt_shadows, gbuffer, rt_reflections
    if (rt && (mask & UH_HYBRID_RT_SHADOWS)) {
       HIP_TRY(c, begin(kStShadows));
@@ -2841,7 +2991,8 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    }
    if (mask & UH_HYBRID_DEFERRED) {
       HIP_TRY(c, begin(kStDeferred));
-      launch_hybrid_deferred(lc, c->scene, hd, fd, view->ibl_enabled == 1 ? &ibl : nullptr);
+      const ShadowLookup sl{h.smaps.p, h.s_params.p, h.smap_size};
+      launch_hybrid_deferred(lc, c->scene, hd, fd, view->ibl_enabled == 1 ? &ibl : nullptr, view->shadows_enabled == 1 ? &sl : nullptr);
       HIP_TRY(c, end(kStDeferred));
    }
    h.frame_lights = h.stage[kStDeferred].ran ? view->num_lights + 1 : 0;
@@ -2876,9 +3027,14 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
 
 // stage k's time in the last call (an environment stage: build) that ran it, 0 when that did not
 static int stage_ms(uh_ctx* c, int k, float* out) {
-   const uh_ctx::Hybrid::Stage& st = c->hy.stage[k];
+   uh_ctx::Hybrid::Stage& st = c->hy.stage[k];
    *out = 0.0f;
-   if (st.ran) HIP_TRY(c, hipEventElapsedTime(out, st.begin, st.end));
+   if (!st.ran) return UH_OK;
+   if (!st.timed) {
+      HIP_TRY(c, hipEventElapsedTime(&st.ms, st.begin, st.end));
+      st.timed = true;
+   }
+   *out = st.ms;
    return UH_OK;
 }
 
@@ -2947,6 +3103,47 @@ int uh_get_hybrid_stats(uh_ctx* c, UhHybridStats* out) {
    const int stages[3] = {kStGbuffer, kStShadows, kStReflections};  // the header's order
    for (int k = 0; k < 3; k++)
       if (int st = stage_ms(c, stages[k], &out->pass_ms[k])) return st;
+   return UH_OK;
+}
+
+int uh_set_shadowmap_params(uh_ctx* c, const UhShadowmapParams* p) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_set_shadowmap_params: null params");
+   for (int k = 0; k < 4; k++) {
+      const float* m = p->view_projection_matrices[k];
+      for (int i = 0; i < 16; i++)
+         if (!std::isfinite(m[i])) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_set_shadowmap_params: a non-finite matrix element");
+      if (!std::isfinite(p->cascade_splits[k])) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_set_shadowmap_params: a non-finite split");
+      if (m[3] != 0.0f || m[7] != 0.0f || m[11] != 0.0f || m[15] != 1.0f)
+         return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_set_shadowmap_params: a matrix whose last row is not (0, 0, 0, 1) (not orthographic)");
+   }
+   c->hy.params = *p;
+   c->hy.params_set = true;
+   return UH_OK;
+}
+
+int uh_read_shadow_map(uh_ctx* c, int cascade, float* out) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   const uh_ctx::Hybrid& h = c->hy;
+   if (!h.smaps.p || !h.smap_size) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_shadow_map before the maps were rendered (UH_HYBRID_SHADOW_MAPS)");
+   if (cascade < 0 || cascade > 3) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_shadow_map: cascade must be 0..3");
+   const size_t n = (size_t)h.smap_size * h.smap_size;
+   return read_back(c, out, h.smaps.p + (size_t)cascade * n, n * sizeof(float));
+}
+
+int uh_get_shadow_map_stats(uh_ctx* c, UhShadowMapStats* out) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_shadow_map_stats: null destination");
+   std::memset(out, 0, sizeof(*out));
+   const uh_ctx::Hybrid& h = c->hy;
+   if (h.s_renders == 0) return UH_OK;
+   HIP_TRY(c, hipSetDevice(c->device));
+   if (int st = sync_all(c)) return st;
+   if (int st = stage_ms(c, kStShadowMaps, &out->pass_ms)) return st;
+   out->renders = h.s_renders;
+   out->size = h.smap_size;
+   std::memcpy(out->triangles, h.s_tris, sizeof(out->triangles));
+   out->params = h.snapshot;
    return UH_OK;
 }
 

@@ -320,7 +320,33 @@ void launch_env_specular(const LaunchCfg&, const EnvDev&);
 void launch_env_brdf_lut(const LaunchCfg&, const EnvDev&);
 // the passes with an IBL branch: nullptr for the non-IBL one (the sky's: the environment cube, or IntegrateScattering)
 void launch_hybrid_reflections(const LaunchCfg&, const SceneDev&, const HybridDev&, const IblMaps* ibl);
-void launch_hybrid_deferred(const LaunchCfg&, const SceneDev&, const HybridDev&, const HybridFrameDev&, const IblMaps* ibl);
+// the deferred pass's calculateShadow (shadow_mapping.glsl) reads the cascaded shadow maps with the params they were rendered with
+struct ShadowLookup {
+   const float* maps;           // 4 layers of size^2 D32, row 0 at NDC y = +1
+   const UhShadowmapParams* params;  // the snapshot the maps were rendered with (device copy)
+   uint32_t size;
+};
+void launch_hybrid_deferred(const LaunchCfg&, const SceneDev&, const HybridDev&, const HybridFrameDev&, const IblMaps* ibl,
+                            const ShadowLookup* shadow);
+// the shadow-map rasteriser (shadow_map.hip): setup per (triangle, cascade), binning into kShadowTile^2 tiles, resolve per tile in LDS
+constexpr uint32_t kShadowTile = 128;
+struct ShadowDev {
+   const UhVertex* vertices;    // HybridDev's tables: vertex vertex_base + indices[3 t + k] of triangle t (mesh tri_mesh[t])
+   const uint32_t* indices;
+   const HybridMesh* meshes;
+   const uint32_t* tri_mesh;
+   const float* mats;           // [cascade][mesh][16]: vp[cascade] * world, column-major, last row (0, 0, 0, 1)
+   uint32_t num_tris, num_meshes, size, tiles_x;
+   uint32_t* rec_count;         // [cascade * num_tris + t]: the records of (t, cascade); scanned in place into record offsets
+   uint32_t* tile_count;        // [cascade * tiles_x^2 + tile]: entries per tile; scanned in place into the tiles' first entries
+   uint32_t* tile_cursor;       // a copy of the tiles' first entries, advanced by the scatter to their ends
+   uint4* records;              // 3 per record
+   uint32_t* entries;           // record ids, grouped by tile
+   float* maps;
+};
+void launch_shadow_count(const LaunchCfg&, const ShadowDev&);
+void launch_shadow_emit(const LaunchCfg&, const ShadowDev&);
+void launch_shadow_resolve(const LaunchCfg&, const ShadowDev&);
 void launch_hybrid_sky(const LaunchCfg&, const FrameParams&, const HybridDev&, const HybridFrameDev&, const IblMaps* cube);
 // tiles
 // on-device refit (refit.hip): per-mesh object->world rows, and what one refit pass touches

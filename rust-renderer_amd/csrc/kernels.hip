@@ -2752,10 +2752,58 @@ __global__ void k_hybrid_light_prep(HybridFrameDev fd) {
 // wave-uniform with a scalar branch on the light's mode. The light-independent terms (V, F0, NdotV, GeometrySchlickGGX(NdotV), a2,
 // k, 1 - metallic, 4 NdotV) are hoisted: the same operations on the same operands, so the same bits.
 // kIbl: the ambient term is imageBasedLighting on the IBL maps (frag:85-88) instead of 0.03 * diffuse * occlusion.
+// kShadow (shadows_enabled = 1): calculateShadow on the cascaded shadow maps (frag:98-106) instead of the rt_shadows factor.
 constexpr float kPiBrdf = 3.14159265359f;  // brdf.glsl:1
-template <bool kIbl>
+
+// shadow_mapping.glsl calculateShadow: the cascade from the view-space depth, the light-space position divided by w, xy * 0.5 + 0.5,
+// FLIP_UV_Y, then 3 x 3 PCF (x outer, y inner) of texture() reads of layer c - LINEAR + MIRRORED_REPEAT (texture.rs:85-94): the bilinear
+// blend of bilinear_rgb at uv * size - 0.5 - each tap 0.3 when z - 0.0005 > depth, else 1.0 (1.0 when z is outside (-1, 1]); sum / 9
+__device__ __forceinline__ float shadow_depth(const float* __restrict__ map, int S, float x, float y) {
+   if (!(fabsf(x) < 1e9f) || !(fabsf(y) < 1e9f)) return 0.0f;
+   const float fx = floorf(x), fy = floorf(y);
+   const float ax = x - fx, ay = y - fy;
+   const int x0 = mirror_index((int)fx, S), x1 = mirror_index((int)fx + 1, S);
+   const int y0 = mirror_index((int)fy, S), y1 = mirror_index((int)fy + 1, S);
+   const float t00 = map[(size_t)y0 * S + x0], t10 = map[(size_t)y0 * S + x1];
+   const float t01 = map[(size_t)y1 * S + x0], t11 = map[(size_t)y1 * S + x1];
+   const float a = t00 * (1.0f - ax) + t10 * ax;
+   const float b = t01 * (1.0f - ax) + t11 * ax;
+   return a * (1.0f - ay) + b * ay;
+}
+__device__ __forceinline__ float calculate_shadow(const ShadowLookup& sl, const float* view, V3 P) {
+   const float vz = ((view[2] * P.x + view[6] * P.y) + view[10] * P.z) + view[14] * 1.0f;
+   uint32_t c = 0;
+   for (uint32_t i = 0; i < 3; i++)
+      if (vz < -sl.params->cascade_splits[i]) c = i + 1;
+   const float* m = sl.params->view_projection_matrices[c];
+   const float lx = ((m[0] * P.x + m[4] * P.y) + m[8] * P.z) + m[12] * 1.0f;
+   const float ly = ((m[1] * P.x + m[5] * P.y) + m[9] * P.z) + m[13] * 1.0f;
+   const float lz = ((m[2] * P.x + m[6] * P.y) + m[10] * P.z) + m[14] * 1.0f;
+   const float lw = ((m[3] * P.x + m[7] * P.y) + m[11] * P.z) + m[15] * 1.0f;
+   const float px = lx / lw, py = ly / lw, pz = lz / lw;
+   const float u = px * 0.5f + 0.5f, v = 1.0f - (py * 0.5f + 0.5f);
+   const int S = (int)sl.size;
+   const float fS = (float)S, ts = 1.0f / fS;
+   const float* map = sl.maps + (size_t)c * sl.size * sl.size;
+   const bool inside = pz <= 1.0f && pz > -1.0f;
+   float shadow = 0.0f;
+   for (int x = -1; x <= 1; x++) {
+      for (int y = -1; y <= 1; y++) {
+         if (inside) {
+            const float uu = u + (float)x * ts, vv = v + (float)y * ts;
+            const float d = shadow_depth(map, S, uu * fS - 0.5f, vv * fS - 0.5f);
+            shadow += (pz - 0.0005f) > d ? 0.3f : 1.0f;
+         } else {
+            shadow += 1.0f;
+         }
+      }
+   }
+   return shadow / 9.0f;
+}
+
+template <bool kIbl, bool kShadow>
 __global__ __launch_bounds__(kBlock) void k_hybrid_deferred(SceneDev sc, HybridDev hd, HybridFrameDev fd, const HybridLight* __restrict__ lights, uint32_t count,
-                                                            IblMaps ibl) {
+                                                            IblMaps ibl, ShadowLookup sl) {
    __shared__ float s_gamma[256];  // pow(c / 255, 2.2) of every UNORM8 value: pow in double, rounded to float
    s_gamma[threadIdx.x] = (float)pow((double)((float)threadIdx.x / 255.0f), (double)2.2f);
    __syncthreads();
@@ -2833,7 +2881,10 @@ __global__ __launch_bounds__(kBlock) void k_hybrid_deferred(SceneDev sc, HybridD
       const V3 refl = v3(sc.unorm_lut[r.x], sc.unorm_lut[r.y], sc.unorm_lut[r.z]);
       color = color * (1.0f - 1.0f) + refl * 1.0f;
    }
-   if (fd.rt_on) color = color * fmaxf(sc.unorm_lut[hd.shadow[i]], 0.3f);                      // frag:108-111
+   if (kShadow)
+      color = color * calculate_shadow(sl, fd.view, P);                                         // frag:98-106
+   else if (fd.rt_on)
+      color = color * fmaxf(sc.unorm_lut[hd.shadow[i]], 0.3f);                                  // frag:108-111
    if (fd.ssao_on) color = color * ((float)fd.ssao[(size_t)(hd.H - 1 - i / hd.W) * hd.W + i % hd.W] / 65535.0f);  // frag:55,113-115
    fd.deferred[i] = make_float4(color.x, color.y, color.z, 1.0f);
 }
@@ -2961,12 +3012,21 @@ static inline dim3 one_lane_per_pixel(const HybridDev& hd) { return dim3((hd.W *
 void launch_hybrid_ssao(const LaunchCfg& c, const HybridDev& hd, const HybridFrameDev& fd) {
    k_hybrid_ssao<<<one_lane_per_pixel(hd), kBlock, 0, c.stream>>>(hd, fd);
 }
-void launch_hybrid_deferred(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd, const HybridFrameDev& fd, const IblMaps* ibl) {
+void launch_hybrid_deferred(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd, const HybridFrameDev& fd, const IblMaps* ibl,
+                            const ShadowLookup* shadow) {
    k_hybrid_light_prep<<<(fd.num_lights + 1 + 255) / 256, 256, 0, c.stream>>>(fd);
-   if (!ibl)
-      k_hybrid_deferred<false><<<one_lane_per_pixel(hd), kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, fd.num_lights + 1, IblMaps{});
+   const IblMaps im = ibl ? *ibl : IblMaps{};
+   const ShadowLookup sl = shadow ? *shadow : ShadowLookup{};
+   const dim3 grid = one_lane_per_pixel(hd);
+   const uint32_t n = fd.num_lights + 1;
+   if (!ibl && !shadow)
+      k_hybrid_deferred<false, false><<<grid, kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, n, im, sl);
+   else if (!shadow)
+      k_hybrid_deferred<true, false><<<grid, kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, n, im, sl);
+   else if (!ibl)
+      k_hybrid_deferred<false, true><<<grid, kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, n, im, sl);
    else
-      k_hybrid_deferred<true><<<one_lane_per_pixel(hd), kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, fd.num_lights + 1, *ibl);
+      k_hybrid_deferred<true, true><<<grid, kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, n, im, sl);
 }
 void launch_hybrid_sky(const LaunchCfg& c, const FrameParams& fp, const HybridDev& hd, const HybridFrameDev& fd, const IblMaps* cube) {
    k_hybrid_sky_classify<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(hd, fd);

@@ -212,3 +212,28 @@ class EnvironmentStats(C.Structure):
 
 
 assert C.sizeof(EnvironmentStats) == 64 and EnvironmentStats.builds.offset == 16 and EnvironmentStats.sun_dir.offset == 20 and EnvironmentStats.eye.offset == 32
+
+
+# cascaded shadow maps: setup_shadow_pass (shadow.rs) and the deferred pass's calculateShadow
+HYBRID_SHADOW_MAPS = 1 << 8
+SHADOW_CASCADES = 4
+
+
+class ShadowmapParams(C.Structure):
+    """UhShadowmapParams: deferred.frag's UBO_shadowmapParams - four column-major view-projection matrices and the split depths"""
+
+    _fields_ = [("view_projection_matrices", (C.c_float * 16) * 4), ("cascade_splits", C.c_float * 4)]
+
+
+assert C.sizeof(ShadowmapParams) == 272 and ShadowmapParams.cascade_splits.offset == 256
+
+
+class ShadowMapStats(C.Structure):
+    """UhShadowMapStats: the last shadow-map render - hipEvent ms, renders so far, map size, triangles per cascade that reached the
+    rasteriser, and the params snapshot the deferred pass reads"""
+
+    _fields_ = [("pass_ms", C.c_float), ("renders", C.c_uint32), ("size", C.c_uint32), ("triangles", C.c_uint32 * 4), ("reserved", C.c_uint32),
+                ("params", ShadowmapParams)]
+
+
+assert C.sizeof(ShadowMapStats) == 304 and ShadowMapStats.triangles.offset == 12 and ShadowMapStats.params.offset == 32

@@ -7,10 +7,14 @@ what is timed:
           count of --lights (1,024: the light count of BASELINE config 2; point and spot lights alternate)
   ibl     the IBL maps (UH_HYBRID_ENVIRONMENT: environment cube, irradiance cube, specular cube, BRDF LUT), median of --builds builds,
           then the whole frame with IBL off and with the reference's flags (ibl_enabled = cubemap_enabled = 1, shadows_enabled = 0)
+  shadows the cascaded shadow maps (UH_HYBRID_SHADOW_MAPS at the default 4096^2, uh_shadow_cascades of the scene's camera and sun),
+          median of --builds renders, with the triangles per cascade; the whole frame with shadows_enabled = 0 and 1 (maps rendered
+          once); the whole frame with the reference's default flags (shadows_enabled = ibl_enabled = cubemap_enabled = 1, the IBL
+          and shadow maps built once), and the same frame with the shadow maps re-rendered in every call, as the reference does
 
 Run it under `rocprofv3 --kernel-trace --stats -- python tools/hybrid_timing.py --mode ...` for the kernel table.
 
-  python tools/hybrid_timing.py [--mode passes|frame|ibl --width 1920 --height 1080 --warmup 3 --iters 20 --lights 0,16,1024
+  python tools/hybrid_timing.py [--mode passes|frame|ibl|shadows --width 1920 --height 1080 --warmup 3 --iters 20 --lights 0,16,1024
                                  --builds 5 --out FILE]"""
 import argparse
 import json
@@ -101,9 +105,40 @@ def ibl(a):
                    **{f"{p}_ms": m for p, m in zip(PASSES, med)}, total_ms=sum(med))
 
 
+def shadows(a):
+    scene, r, view = setup(a, shadows_enabled=1, ibl_enabled=0, cubemap_enabled=0, num_lights=0)
+    r.set_shadowmap_params(rr.shadow_cascades(scene.camera, view.sun_dir[:]))
+    renders = []
+    for _ in range(a.builds):
+        r.render_hybrid(view, rr.HYBRID_SHADOW_MAPS)
+        renders.append(r.shadow_map_stats())  # waits: one render at a time on an idle GPU
+    s = renders[-1]
+    yield dict(metric="shadow_maps", config=1, size=s.size, renders=a.builds, pass_ms=statistics.median(x.pass_ms for x in renders),
+               first_render_ms=renders[0].pass_ms, triangles_per_cascade=list(s.triangles), triangles=scene.num_triangles)
+    for on in (0, 1):
+        view.shadows_enabled = on
+        med, _ = timed(a, r, view, rr.HYBRID_FRAME, rr.Renderer.hybrid_frame_stats)
+        yield dict(metric="hybrid_frame_full", config=1, lights=0, shadows=on, width=a.width, height=a.height, iters=a.iters,
+                   **{f"{p}_ms": m for p, m in zip(PASSES, med)}, total_ms=sum(med))
+    view.shadows_enabled = view.ibl_enabled = view.cubemap_enabled = 1
+    r.render_hybrid(view, rr.HYBRID_ENVIRONMENT)
+    med, _ = timed(a, r, view, rr.HYBRID_FRAME, rr.Renderer.hybrid_frame_stats)
+    yield dict(metric="hybrid_frame_full", config=1, lights=0, reference_defaults=True, width=a.width, height=a.height, iters=a.iters,
+               **{f"{p}_ms": m for p, m in zip(PASSES, med)}, total_ms=sum(med))
+
+    class Both:  # the seven passes and the shadow-map pass of one call
+        def __init__(self, r):
+            self.pass_ms = list(r.hybrid_frame_stats().pass_ms) + [r.shadow_map_stats().pass_ms]
+
+    # the reference re-renders the cascades every frame (setup_shadow_pass runs in every graph build): the per-frame cost
+    med, _ = timed(a, r, view, rr.HYBRID_FRAME | rr.HYBRID_SHADOW_MAPS, Both)
+    yield dict(metric="hybrid_frame_full", config=1, lights=0, reference_defaults=True, shadow_maps_every_frame=True, width=a.width,
+               height=a.height, iters=a.iters, **{f"{p}_ms": m for p, m in zip(PASSES + ("shadow_maps",), med)}, total_ms=sum(med))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("passes", "frame", "ibl"), default="passes")
+    ap.add_argument("--mode", choices=("passes", "frame", "ibl", "shadows"), default="passes")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--warmup", type=int, default=3)
@@ -113,7 +148,7 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     lines = []
-    for out in {"passes": passes, "frame": frame, "ibl": ibl}[a.mode](a):
+    for out in {"passes": passes, "frame": frame, "ibl": ibl, "shadows": shadows}[a.mode](a):
         lines.append(json.dumps(out))
         print(lines[-1], flush=True)
     if a.out:
