@@ -703,6 +703,65 @@ UH_LAYOUT_ASSERT(sizeof(UhShadowMapStats) == 304 && offsetof(UhShadowMapStats, t
                  "UhShadowMapStats (304 B)");
 int uh_get_shadow_map_stats(uh_ctx* ctx, UhShadowMapStats* out);
 
+/* ---- the forward graph: build_minimal_forward_render_graph (utopian/src/renderers/mod.rs; the reference's render mode 3) ----------
+ * uh_render_forward runs the three passes of the reference's Minimal mode, in its order, for the bits of `mask`:
+ *   UH_FORWARD_SHADOW_MAPS  setup_shadow_pass: the same pass and the same four maps as UH_HYBRID_SHADOW_MAPS (above), rendered from the
+ *                           params last set, only with view->shadows_enabled == 1 (otherwise a no-op), first in the call
+ *   UH_FORWARD_PASS         setup_forward_pass (forward.vert / forward.frag): every triangle of every mesh in order (the draw index of a
+ *                           triangle is its mesh's first triangle plus its primitive, meshes in the order added) through a perspective
+ *                           rasteriser - clip to 0 <= z <= w, the viewport (0, H, W, -H), the shadow maps' guard band, 8-bit snap and
+ *                           top-left rule, no culling, one sample per pixel at its centre, depth LESS_OR_EQUAL with writes, cleared to
+ *                           1.0 - then forward.frag once per pixel on the surviving fragment (the last in draw order among those of
+ *                           minimum depth), with perspective-correct attributes: the unquantised diffuse texel ^ 2.2 times the
+ *                           material's base_color_factor, metallic and roughness from the texture without the factors, the sun plus
+ *                           view->num_lights lights through surfaceShading, ambient 0.03 * diffuse * occlusion, calculateShadow when
+ *                           view->shadows_enabled == 1; no IBL, SSAO, reflections or rt_shadows. Colour cleared to (1, 1, 1, 0).
+ *   UH_FORWARD_PRESENT      setup_present_pass: present.frag + FXAA (view->fxaa_enabled == 1) as UH_HYBRID_PRESENT, reading forward_output
+ *                           and writing the forward graph's own 8-bit image (the hybrid graph's present image is untouched)
+ * UH_FORWARD_GRAPH runs all three. view->raytracing_supported is not read: the graph needs no ray tracing.
+ * UH_ERR_INVALID_ARGUMENT with a message, and nothing runs, for a null view, UH_FORWARD_SHADOW_MAPS (with shadows_enabled == 1) before
+ * uh_set_shadowmap_params, and UH_FORWARD_PASS with view->shadows_enabled == 1 before any shadow-map render (by either graph) or with
+ * view->num_lights above the lights added; UH_ERR_NOT_BUILT before the first build (moved instances with view->rebuild_tlas as for
+ * uh_render_frame); UH_ERR_CAPACITY for a frame wider or taller than 65535 pixels or 2^32 - 1 or more triangle pieces.
+ * ORIENTATION: every forward image is W*H texels, row-major, row 0 the pixel row at NDC y = +1 (the first row of the flipped viewport,
+ * as uh_read_shadow_map) - the layout of the hybrid graph's images: forward pixel (x, y) and G-buffer texel (x, y) see the same point.
+ * STREAM ORDER: a call enqueues like uh_render_hybrid (behind the frames in flight, on the context's first stream), but UH_FORWARD_PASS
+ * BLOCKS the host until the frames in flight and the pass's binning have finished: it reads the number of triangle pieces and tile
+ * entries back to size its buffers, as UH_FORWARD_SHADOW_MAPS does. uh_read_forward and uh_get_forward_stats wait and are complete on
+ * return.
+ * RESOURCES: the images (37 bytes per pixel with the visibility buffer's record ids) are allocated by the first call, cleared, and
+ * freed by uh_destroy; the binning buffers grow with the scene. A context that never calls uh_render_forward allocates nothing for it.
+ * The graph shares the hybrid graph's mesh tables, light table and shadow maps.
+ * ISOLATION: a call changes no path-traced or hybrid image and nothing in UhStats, UhHybridStats or UhHybridFrameStats; the one
+ * exception is the shadow maps (and UhShadowMapStats) when its mask renders them.
+ * Arithmetic: DESIGN.md section 2, "Forward pass". */
+enum { UH_FORWARD_PASS = 1u << 0, UH_FORWARD_PRESENT = 1u << 1, UH_FORWARD_SHADOW_MAPS = UH_HYBRID_SHADOW_MAPS, UH_FORWARD_GRAPH = UH_HYBRID_SHADOW_MAPS | 3u };
+/* which image uh_read_forward copies out (W*H texels each) */
+enum {
+   UH_FORWARD_OUTPUT = 0,         /* RGBA32F forward_output */
+   UH_FORWARD_DEPTH = 1,          /* float32 depth, 1.0 where nothing was drawn */
+   UH_FORWARD_VISIBILITY = 2,     /* uint32 draw index of the surviving fragment, 0xFFFFFFFF for none */
+   UH_FORWARD_PRESENT_OUTPUT = 3  /* 8 bits x 4 channels, B G R A (as uh_read_output_bgra8) */
+};
+/* the last uh_render_forward call: pass_ms the hipEvent time of (shadow maps, forward, present), 0 for a pass that did not run;
+ * renders the calls that ran the forward pass so far; pieces the triangle pieces that reached the rasteriser (after clipping and the
+ * setup's rejects), covered_pixels the pixels with a surviving fragment and lights the lights forward.frag evaluated (the sun
+ * included), all three of the last forward pass. All zero before the first call. Waits for all work of the context. */
+typedef struct UhForwardStats {
+   float pass_ms[3];
+   uint32_t renders;
+   uint32_t pieces;
+   uint32_t covered_pixels;
+   uint32_t lights;
+   uint32_t reserved;
+} UhForwardStats;
+UH_LAYOUT_ASSERT(sizeof(UhForwardStats) == 32 && offsetof(UhForwardStats, renders) == 12 && offsetof(UhForwardStats, pieces) == 16 &&
+                    offsetof(UhForwardStats, covered_pixels) == 20 && offsetof(UhForwardStats, lights) == 24,
+                 "UhForwardStats (32 B)");
+int uh_render_forward(uh_ctx* ctx, const UhViewUniformData* view, uint32_t mask);
+int uh_read_forward(uh_ctx* ctx, int which, void* out); /* UH_ERR_INVALID_ARGUMENT before the first uh_render_forward */
+int uh_get_forward_stats(uh_ctx* ctx, UhForwardStats* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -354,6 +354,20 @@ class Renderer {
       check(uh_get_shadow_map_stats(ctx_, &s), "shadow_map_stats");
       return s;
    }
+   // the forward graph (build_minimal_forward_render_graph, the reference's render mode 3; utopian_hip.h "uh_render_forward"): shadow
+   // maps, forward pass and present for the bits of `mask`; one image as bytes, W*H texels of 16 (output), 4 (depth float, draw index
+   // uint32, present B G R A) bytes, row 0 at NDC y = +1; the last call's stats
+   void render_forward(const UhViewUniformData& view, uint32_t mask = UH_FORWARD_GRAPH) { check(uh_render_forward(ctx_, &view, mask), "render_forward"); }
+   std::vector<uint8_t> read_forward(int which) {
+      std::vector<uint8_t> out((size_t)width_ * height_ * (which == UH_FORWARD_OUTPUT ? 16 : 4));
+      check(uh_read_forward(ctx_, which, out.data()), "read_forward");
+      return out;
+   }
+   UhForwardStats forward_stats() {
+      UhForwardStats s;
+      check(uh_get_forward_stats(ctx_, &s), "forward_stats");
+      return s;
+   }
    // uh_set_option: "device_build", "frames_in_flight", ... (DESIGN.md "Options")
    void set_option(const char* name, int value) { check(uh_set_option(ctx_, name, value), name); }
    // marching_cubes.rs:17-83 / marching_cubes.comp: the density field's iso-surface, extracted on the GPU and added

@@ -45,6 +45,12 @@ from .types import (
     HybridStats,
     ShadowmapParams,
     ShadowMapStats,
+    FORWARD_DEPTH,
+    FORWARD_GRAPH,
+    FORWARD_OUTPUT,
+    FORWARD_PRESENT_OUTPUT,
+    FORWARD_VISIBILITY,
+    ForwardStats,
     Reservoir,
     RestirRows,
     Stats,
@@ -523,6 +529,43 @@ class Renderer:
         """UhShadowMapStats of the last shadow-map render"""
         s = ShadowMapStats()
         self._check(self._shadow_fn("get_shadow_map_stats", [C.POINTER(ShadowMapStats)])(self._ctx, C.byref(s)))
+        return s
+
+    # -- the forward graph (uh_render_forward; include/utopian_hip.h) ------------------------
+    def _forward_fn(self, name, argtypes):
+        if self.backend != "hip" or not hasattr(self._lib, "uh_" + name):
+            raise NotImplementedError(f"the forward graph (shadow maps, forward pass, present) is a per-context verb of the HIP library; backend {self.backend!r} has none")
+        fn = getattr(self._lib, "uh_" + name)
+        fn.argtypes, fn.restype = [C.c_void_p] + argtypes, C.c_int
+        return fn
+
+    def render_forward(self, view, mask=FORWARD_GRAPH):
+        """shadow maps, forward pass, present - the reference's Minimal mode in its pass order - for the bits of `mask`"""
+        fn = self._forward_fn("render_forward", [C.POINTER(ViewUniformData), C.c_uint32])
+        self._check(fn(self._ctx, C.byref(view), int(mask)))
+
+    _FORWARD_IMAGES = {
+        FORWARD_OUTPUT: (np.float32, 4),
+        FORWARD_DEPTH: (np.float32, 1),
+        FORWARD_VISIBILITY: (np.uint32, 1),
+        FORWARD_PRESENT_OUTPUT: (np.uint8, 4),
+    }
+
+    def read_forward(self, which):
+        """one image of the forward graph, row 0 at NDC y = +1: (H, W, 4) float32 output, (H, W) float32 depth, (H, W) uint32 draw index
+        (FORWARD_NONE where nothing was drawn), (H, W, 4) uint8 present output (B, G, R, A)"""
+        fn = self._forward_fn("read_forward", [C.c_int, C.c_void_p])
+        if which not in self._FORWARD_IMAGES:
+            raise ValueError(f"forward image index {which} (0..3)")
+        dtype, ch = self._FORWARD_IMAGES[which]
+        out = np.empty((self.height, self.width, ch) if ch > 1 else (self.height, self.width), dtype=dtype)
+        self._check(fn(self._ctx, int(which), out.ctypes.data))
+        return out
+
+    def forward_stats(self):
+        """UhForwardStats of the last render_forward call"""
+        s = ForwardStats()
+        self._check(self._forward_fn("get_forward_stats", [C.POINTER(ForwardStats)])(self._ctx, C.byref(s)))
         return s
 
     # -- stand-alone ray queries ----------------------------------------------------------

@@ -388,6 +388,31 @@ struct uh_ctx {
          f(env, cube), f(irr, 6 * (size_t)kEnvSize * kEnvSize), f(spec, cube), f(lut, (size_t)kLutSize * kLutSize);
       }
    } hy;
+
+   // the forward graph (uh_render_forward): its images, light records and binning buffers, allocated by the first call; it shares the
+   // hybrid graph's mesh tables, uploaded light table and shadow maps
+   struct Forward {
+      DevBuf<float4> color;                    // forward_output RGBA32F
+      DevBuf<float> depth;
+      DevBuf<uint32_t> vis, rec_of, covered;   // draw index, surviving record per pixel; [0] the covered pixels of the last pass
+      DevBuf<uchar4> present;                  // the forward graph's present image, B8G8R8A8
+      DevBuf<HybridLight> lights;              // forward.frag's light records, the sun first
+      DevBuf<uint32_t> tile_count, tile_cursor, rec_count, tri_mesh, chunks, entries;
+      DevBuf<unsigned long long> totals;       // the grand totals of the two scans: records, tile entries
+      DevBuf<uint4> records;
+      DevBuf<float> mats;                      // [mesh][28]
+      std::vector<float> mats_host;
+      uint64_t geom = 0;                       // geom_version of tri_mesh / rec_count
+      // pass k: 0 shadow maps, 1 forward, 2 present (the last call's; ms resolved by the first stats read and kept)
+      uh_ctx::Hybrid::Stage stage[3];
+      uint32_t renders = 0, pieces = 0, lights_used = 0;
+      template <class F> void images(size_t n, F&& f) {
+         f(depth, n), f(vis, n), f(rec_of, n), f(present, n), f(lights, UH_MAX_GPU_LIGHTS + 1), f(covered, 1), f(color, n);
+      }
+      template <class F> void bins(F&& f) {
+         f(tile_count, 0), f(tile_cursor, 0), f(rec_count, 0), f(tri_mesh, 0), f(chunks, 0), f(entries, 0), f(totals, 0), f(records, 0), f(mats, 0);
+      }
+   } fw;
 };
 
 namespace {
@@ -654,6 +679,12 @@ void uh_destroy(uh_ctx* c) {
       for (hipEvent_t ev : h.waits)
          if (ev) (void)hipEventDestroy(ev);
       for (const auto& st : h.stage)
+         for (hipEvent_t ev : {st.begin, st.end})
+            if (ev) (void)hipEventDestroy(ev);
+      uh_ctx::Forward& f = c->fw;
+      f.images(0, release);
+      f.bins(release);
+      for (const auto& st : f.stage)
          for (hipEvent_t ev : {st.begin, st.end})
             if (ev) (void)hipEventDestroy(ev);
    }
@@ -2624,14 +2655,20 @@ extern "C++" template <class Visit> static int alloc_group(uh_ctx* c, Visit visi
 }
 
 // the ray-traced images and the events (first call)
-static int hybrid_alloc(uh_ctx* c) {
+// the events of the hybrid stages and of the waits behind the frames in flight (first hybrid or forward call)
+static int hybrid_events(uh_ctx* c) {
    uh_ctx::Hybrid& h = c->hy;
-   if (h.counter.p) return UH_OK;
    for (hipEvent_t& ev : h.waits)
       if (!ev) HIP_TRY(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
    for (auto& st : h.stage)
       for (hipEvent_t* ev : {&st.begin, &st.end})
          if (!*ev) HIP_TRY(c, hipEventCreate(ev));
+   return UH_OK;
+}
+static int hybrid_alloc(uh_ctx* c) {
+   uh_ctx::Hybrid& h = c->hy;
+   if (h.counter.p) return UH_OK;
+   if (int st = hybrid_events(c)) return st;
    return alloc_group(c, [&](auto f) { h.rt_images((size_t)c->W * c->H, f); });
 }
 
@@ -2743,17 +2780,17 @@ static void cascade_mesh_matrices(const uh_ctx* c, const UhShadowmapParams& p, s
 }
 
 // count, scan, emit, resolve: the records' and tile entries' totals come back to the host in between (the buffers grow to them)
-static int render_shadow_maps(uh_ctx* c, const LaunchCfg& lc) {
+static int render_shadow_maps(uh_ctx* c, const LaunchCfg& lc, const char* verb) {
    uh_ctx::Hybrid& h = c->hy;
    const uint32_t S = c->shadow_map_size, tiles_x = (S + kShadowTile - 1) / kShadowTile, tiles = 4 * tiles_x * tiles_x;
    size_t ntri = 0;
    for (const HostMesh& m : c->meshes) ntri += m.indices.size() / 3;
-   if (4 * ntri >= (1ull << 32)) return fail(c, UH_ERR_CAPACITY, "uh_render_hybrid: shadow maps of more than 2^30 triangles");
+   if (4 * ntri >= (1ull << 32)) return fail(c, UH_ERR_CAPACITY, std::string(verb) + ": shadow maps of more than 2^30 triangles");
    const auto grow = [&](auto& b, size_t n) -> int {
       if (b.p && b.n >= n) return UH_OK;
       const hipError_t e = b.alloc(n);
       if (e != hipSuccess)
-         return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string("uh_render_hybrid: allocation: ") + hipGetErrorString(e));
+         return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string(verb) + ": allocation: " + hipGetErrorString(e));
       return UH_OK;
    };
    for (int st : {grow(h.smaps, 4 * (size_t)S * S), grow(h.s_tile_count, tiles), grow(h.s_tile_cursor, tiles), grow(h.s_totals, 2),
@@ -2804,7 +2841,7 @@ static int render_shadow_maps(uh_ctx* c, const LaunchCfg& lc) {
       for (int k = 1; k < 4; k++) HIP_TRY(c, hipMemcpy(first + k, h.s_rec_count.p + k * ntri, sizeof(uint32_t), hipMemcpyDeviceToHost));
    }
    if (totals[0] >= (1ull << 32) || totals[1] >= (1ull << 32))
-      return fail(c, UH_ERR_CAPACITY, "uh_render_hybrid: shadow maps with 2^32 or more triangle pieces or tile entries");
+      return fail(c, UH_ERR_CAPACITY, std::string(verb) + ": shadow maps with 2^32 or more triangle pieces or tile entries");
    for (int st : {grow(h.s_records, std::max<size_t>(1, 3 * (size_t)totals[0])), grow(h.s_entries, std::max<size_t>(1, (size_t)totals[1]))})
       if (st) return st;
    sd.records = h.s_records.p;
@@ -2815,6 +2852,29 @@ static int render_shadow_maps(uh_ctx* c, const LaunchCfg& lc) {
    h.snapshot = h.pending;
    h.smap_size = S;
    h.s_renders++;
+   return UH_OK;
+}
+
+// behind every frame in flight: the context's first stream (slot 0's, where hybrid and forward calls run) waits for the others
+static int wait_frames_in_flight(uh_ctx* c) {
+   uh_ctx::Hybrid& h = c->hy;
+   int w = 0;
+   for (uint32_t i = 1; i < kMaxSlots; i++) {
+      const Slot& s = c->slots[i];
+      if (!s.ready) continue;
+      for (hipStream_t st : {s.stream, s.side}) {
+         HIP_TRY(c, hipEventRecord(h.waits[w], st));
+         HIP_TRY(c, hipStreamWaitEvent(c->stream, h.waits[w++], 0));
+      }
+   }
+   if (c->restir_stream) {
+      HIP_TRY(c, hipEventRecord(h.waits[w], c->restir_stream));
+      HIP_TRY(c, hipStreamWaitEvent(c->stream, h.waits[w++], 0));
+   }
+   if (c->slots[0].ready) {
+      HIP_TRY(c, hipEventRecord(h.waits[w], c->slots[0].side));
+      HIP_TRY(c, hipStreamWaitEvent(c->stream, h.waits[w++], 0));
+   }
    return UH_OK;
 }
 
@@ -2885,24 +2945,7 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    hd.W = c->W;
    hd.H = c->H;
    hd.furnace = c->furnace ? 1u : 0u;
-   // behind every frame in flight: the context's first stream (slot 0's, where this call runs) waits for the others
-   int w = 0;
-   for (uint32_t i = 1; i < kMaxSlots; i++) {
-      const Slot& s = c->slots[i];
-      if (!s.ready) continue;
-      for (hipStream_t st : {s.stream, s.side}) {
-         HIP_TRY(c, hipEventRecord(h.waits[w], st));
-         HIP_TRY(c, hipStreamWaitEvent(c->stream, h.waits[w++], 0));
-      }
-   }
-   if (c->restir_stream) {
-      HIP_TRY(c, hipEventRecord(h.waits[w], c->restir_stream));
-      HIP_TRY(c, hipStreamWaitEvent(c->stream, h.waits[w++], 0));
-   }
-   if (c->slots[0].ready) {
-      HIP_TRY(c, hipEventRecord(h.waits[w], c->slots[0].side));
-      HIP_TRY(c, hipStreamWaitEvent(c->stream, h.waits[w++], 0));
-   }
+   if (int st = wait_frames_in_flight(c)) return st;
    LaunchCfg lc = cfg(c);
    lc.count_visits = false;  // nothing of this call goes to UhStats
    if (first) launch_hybrid_clear(lc, hd);
@@ -2942,7 +2985,7 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    // setup_shadow_pass's four passes are added first (mod.rs:91-98)
    if (render_maps) {
       HIP_TRY(c, begin(kStShadowMaps));
-      int st = render_shadow_maps(c, lc);
+      int st = render_shadow_maps(c, lc, "uh_render_hybrid");
       const hipError_t e = st ? hipSuccess : end(kStShadowMaps);
       if (st || e != hipSuccess) h.stage[kStShadowMaps].ran = false;  // no time for a render that did not complete
       if (st) return st;
@@ -3144,6 +3187,248 @@ int uh_get_shadow_map_stats(uh_ctx* c, UhShadowMapStats* out) {
    out->size = h.smap_size;
    std::memcpy(out->triangles, h.s_tris, sizeof(out->triangles));
    out->params = h.snapshot;
+   return UH_OK;
+}
+
+// ---- the forward graph (utopian_hip.h "uh_render_forward"; forward.hip) ----
+// per mesh: (P V) W column-major - P V first, then times the instance's 3x4 with row (0, 0, 0, 1), each element summed
+// ((a(r,0) b(0,c) + a(r,1) b(1,c)) + a(r,2) b(2,c)) + a(r,3) b(3,c) - followed by the instance's 3x4 row-major
+static void forward_mesh_matrices(const uh_ctx* c, const UhViewUniformData& v, std::vector<float>& out) {
+   auto mul = [](const float* a, const float* b, float* o) {
+      for (int col = 0; col < 4; col++)
+         for (int r = 0; r < 4; r++)
+            o[4 * col + r] = ((a[r] * b[4 * col] + a[4 + r] * b[4 * col + 1]) + a[8 + r] * b[4 * col + 2]) + a[12 + r] * b[4 * col + 3];
+   };
+   float pv[16];
+   mul(v.projection, v.view, pv);
+   const size_t nm = c->meshes.size();
+   out.assign(nm * 28, 0.0f);
+   for (size_t m = 0; m < nm; m++) {
+      const float* o = c->meshes[m].o2w;
+      float w[16];  // column-major
+      for (int col = 0; col < 4; col++) {
+         for (int r = 0; r < 3; r++) w[4 * col + r] = o[4 * r + col];
+         w[4 * col + 3] = col == 3 ? 1.0f : 0.0f;
+      }
+      mul(pv, w, &out[m * 28]);
+      std::memcpy(&out[m * 28 + 16], o, 12 * sizeof(float));
+   }
+}
+
+// count, scan, emit, resolve, then forward.frag: the records' and tile entries' totals come back to the host in between (the buffers
+// grow to them)
+static int render_forward_pass(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformData& view) {
+   uh_ctx::Hybrid& h = c->hy;
+   uh_ctx::Forward& f = c->fw;
+   const uint32_t W = c->W, H = c->H, tiles_x = (W + kForwardTile - 1) / kForwardTile, tiles_y = (H + kForwardTile - 1) / kForwardTile;
+   const uint32_t tiles = tiles_x * tiles_y;
+   size_t ntri = 0;
+   for (const HostMesh& m : c->meshes) ntri += m.indices.size() / 3;
+   if (ntri >= (1ull << 32) - 1) return fail(c, UH_ERR_CAPACITY, "uh_render_forward: 2^32 - 1 or more triangles");
+   const auto grow = [&](auto& b, size_t n) -> int {
+      if (b.p && b.n >= n) return UH_OK;
+      const hipError_t e = b.alloc(n);
+      if (e != hipSuccess)
+         return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string("uh_render_forward: allocation: ") + hipGetErrorString(e));
+      return UH_OK;
+   };
+   for (int st : {grow(f.tile_count, tiles), grow(f.tile_cursor, tiles), grow(f.totals, 2), grow(f.mats, std::max<size_t>(1, 28 * c->meshes.size())),
+                  grow(f.chunks, std::max<size_t>(1, scan_chunk_count((uint32_t)std::max<size_t>(ntri, tiles))))})
+      if (st) return st;
+   if (f.geom != c->geom_version || !f.rec_count.p) {
+      std::vector<uint32_t> tm;
+      tm.reserve(ntri);
+      for (size_t m = 0; m < c->meshes.size(); m++) tm.insert(tm.end(), c->meshes[m].indices.size() / 3, (uint32_t)m);
+      for (int st : {grow(f.tri_mesh, std::max<size_t>(1, ntri)), grow(f.rec_count, std::max<size_t>(1, ntri))})
+         if (st) return st;
+      if (ntri) HIP_TRY(c, hipMemcpy(f.tri_mesh.p, tm.data(), ntri * sizeof(uint32_t), hipMemcpyHostToDevice));
+      f.geom = c->geom_version;
+   }
+   forward_mesh_matrices(c, view, f.mats_host);
+   if (!f.mats_host.empty())
+      HIP_TRY(c, hipMemcpyAsync(f.mats.p, f.mats_host.data(), f.mats_host.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+   HIP_TRY(c, hipMemsetAsync(f.tile_count.p, 0, tiles * sizeof(uint32_t), c->stream));
+   HIP_TRY(c, hipMemsetAsync(f.covered.p, 0, sizeof(uint32_t), c->stream));
+   ForwardDev fd{};
+   fd.vertices = h.vertices.p;
+   fd.indices = h.indices.p;
+   fd.meshes = h.meshes.p;
+   fd.tri_mesh = f.tri_mesh.p;
+   fd.mats = f.mats.p;
+   fd.num_tris = (uint32_t)ntri;
+   fd.W = W;
+   fd.H = H;
+   fd.tiles_x = tiles_x;
+   fd.tiles_y = tiles_y;
+   fd.rec_count = f.rec_count.p;
+   fd.tile_count = f.tile_count.p;
+   fd.tile_cursor = f.tile_cursor.p;
+   fd.depth = f.depth.p;
+   fd.vis = f.vis.p;
+   fd.rec_of = f.rec_of.p;
+   fd.color = f.color.p;
+   fd.covered = f.covered.p;
+   launch_forward_count(lc, fd);
+   unsigned long long totals[2] = {0, 0};
+   if (ntri) device_exclusive_scan_u32(f.rec_count.p, (uint32_t)ntri, f.chunks.p, f.totals.p, c->stream);
+   device_exclusive_scan_u32(f.tile_count.p, tiles, f.chunks.p, f.totals.p + 1, c->stream);
+   HIP_TRY(c, hipMemcpyAsync(f.tile_cursor.p, f.tile_count.p, tiles * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+   HIP_TRY(c, hipStreamSynchronize(c->stream));
+   HIP_TRY(c, hipMemcpy(totals + 1, f.totals.p + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+   if (ntri) HIP_TRY(c, hipMemcpy(totals, f.totals.p, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+   // record ids below 2^32 - 1: the resolve's key holds ~record, and 0xFFFFFFFF stands for none
+   if (totals[0] >= (1ull << 32) - 1 || totals[1] >= (1ull << 32))
+      return fail(c, UH_ERR_CAPACITY, "uh_render_forward: 2^32 - 1 or more triangle pieces, or 2^32 or more tile entries");
+   for (int st : {grow(f.records, std::max<size_t>(1, 6 * (size_t)totals[0])), grow(f.entries, std::max<size_t>(1, (size_t)totals[1]))})
+      if (st) return st;
+   fd.records = f.records.p;
+   fd.entries = f.entries.p;
+   launch_forward_emit(lc, fd);
+   launch_forward_resolve(lc, fd);
+   HybridFrameDev lp{};  // k_hybrid_light_prep's inputs, into the forward graph's own records
+   lp.lights = f.lights.p;
+   lp.raw_lights = h.raw_lights.p;
+   lp.num_lights = view.num_lights;
+   for (int a = 0; a < 3; a++) lp.sun_raw[a] = view.sun_dir[a];
+   launch_hybrid_light_prep(lc, lp);
+   ForwardShade fs{};
+   fs.lights = f.lights.p;
+   fs.count = view.num_lights + 1;
+   for (int a = 0; a < 3; a++) fs.eye[a] = view.eye_pos[a];
+   std::memcpy(fs.view, view.view, sizeof(fs.view));
+   const ShadowLookup sl{h.smaps.p, h.s_params.p, h.smap_size};
+   launch_forward_shade(lc, c->scene, fd, fs, view.shadows_enabled == 1 ? &sl : nullptr);
+   f.pieces = (uint32_t)totals[0];
+   f.lights_used = view.num_lights + 1;
+   f.renders++;
+   return UH_OK;
+}
+
+int uh_render_forward(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!view) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_render_forward: null view");
+   const bool render_maps = (mask & UH_FORWARD_SHADOW_MAPS) && view->shadows_enabled == 1;
+   if (render_maps && !c->hy.params_set)
+      return fail(c, UH_ERR_INVALID_ARGUMENT,
+                  "uh_render_forward: UH_FORWARD_SHADOW_MAPS before uh_set_shadowmap_params (the cascades of uh_shadow_cascades or the caller's own)");
+   if (mask & UH_FORWARD_PASS) {
+      if (view->shadows_enabled == 1 && !c->hy.smap_size && !render_maps)
+         return fail(c, UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_forward: the forward pass with view.shadows_enabled = 1 needs the cascaded shadow maps (shadow.rs), which a call "
+                     "with UH_FORWARD_SHADOW_MAPS renders; set that bit, or shadows_enabled = 0");
+      if (view->num_lights > c->lights.size())
+         return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_render_forward: view.num_lights exceeds the lights added with uh_add_light");
+   }
+   if (!c->built && c->topology_valid && view->rebuild_tlas == 1)
+      if (int st = uh_refit_acceleration(c)) return st;
+   if (!c->built) return fail(c, UH_ERR_NOT_BUILT, "uh_render_forward before uh_build_acceleration");
+   if (c->W > 65535 || c->H > 65535) return fail(c, UH_ERR_CAPACITY, "uh_render_forward: a frame wider or taller than 65535 pixels");
+   HIP_TRY(c, hipSetDevice(c->device));
+   uh_ctx::Hybrid& h = c->hy;
+   uh_ctx::Forward& f = c->fw;
+   if (int st = hybrid_events(c)) return st;
+   if (int st = hybrid_tables(c)) return st;
+   const bool first = !f.color.p;
+   if (first) {
+      for (auto& st : f.stage)
+         for (hipEvent_t* ev : {&st.begin, &st.end})
+            if (!*ev) HIP_TRY(c, hipEventCreate(ev));
+      if (int st = alloc_group(c, [&](auto fn) { f.images((size_t)c->W * c->H, fn); })) return st;
+   }
+   if (mask & UH_FORWARD_PASS)
+      if (int st = hybrid_light_table(c)) return st;
+   if (int st = wait_frames_in_flight(c)) return st;
+   LaunchCfg lc = cfg(c);
+   lc.count_visits = false;  // nothing of this call goes to UhStats
+   ForwardDev cd{};
+   cd.W = c->W;
+   cd.H = c->H;
+   cd.depth = f.depth.p;
+   cd.vis = f.vis.p;
+   cd.rec_of = f.rec_of.p;
+   cd.color = f.color.p;
+   if (first) launch_forward_clear(lc, cd, f.present.p);
+   for (auto& st : f.stage) st.ran = false;
+   const auto begin = [&](int k) {
+      f.stage[k].ran = true;
+      f.stage[k].timed = false;
+      return hipEventRecord(f.stage[k].begin, c->stream);
+   };
+   const auto end = [&](int k) { return hipEventRecord(f.stage[k].end, c->stream); };
+   // setup_shadow_pass, setup_forward_pass, setup_present_pass (build_minimal_forward_render_graph): the maps are the hybrid graph's,
+   // and their own record (uh_get_shadow_map_stats) is kept as a hybrid call with UH_HYBRID_SHADOW_MAPS keeps it
+   if (render_maps) {
+      h.stage[kStShadowMaps].ran = false;
+      uh_ctx::Hybrid::Stage& hs = h.stage[kStShadowMaps];
+      HIP_TRY(c, begin(0));
+      HIP_TRY(c, hipEventRecord(hs.begin, c->stream));
+      hs.ran = true;
+      hs.timed = false;
+      int st = render_shadow_maps(c, lc, "uh_render_forward");
+      hipError_t e = st ? hipSuccess : end(0);
+      if (e == hipSuccess && !st) e = hipEventRecord(hs.end, c->stream);
+      if (st || e != hipSuccess) f.stage[0].ran = hs.ran = false;  // no time for a render that did not complete
+      if (st) return st;
+      HIP_TRY(c, e);
+   }
+   if (mask & UH_FORWARD_PASS) {
+      HIP_TRY(c, begin(1));
+      int st = render_forward_pass(c, lc, *view);
+      if (st) {
+         f.stage[1].ran = false;
+         return st;
+      }
+      HIP_TRY(c, end(1));
+   }
+   if (mask & UH_FORWARD_PRESENT) {  // present.frag + FXAA on forward_output, into the forward graph's own image
+      HIP_TRY(c, begin(2));
+      HybridDev hd{};
+      hd.W = c->W;
+      hd.H = c->H;
+      HybridFrameDev pd{};
+      pd.deferred = f.color.p;
+      pd.present = f.present.p;
+      pd.fxaa_on = view->fxaa_enabled == 1;
+      launch_hybrid_present(lc, hd, pd);
+      HIP_TRY(c, end(2));
+   }
+   HIP_TRY(c, hipGetLastError());
+   return UH_OK;
+}
+
+int uh_read_forward(uh_ctx* c, int which, void* out) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   const uh_ctx::Forward& f = c->fw;
+   if (!f.color.p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_forward before the first uh_render_forward");
+   if (which < UH_FORWARD_OUTPUT || which > UH_FORWARD_PRESENT_OUTPUT) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_forward: image index must be 0..3");
+   // image k's pixels and its bytes per pixel, in UH_FORWARD_* image order
+   const std::pair<const void*, size_t> img[] = {{f.color.p, sizeof(float4)}, {f.depth.p, sizeof(float)}, {f.vis.p, sizeof(uint32_t)}, {f.present.p, sizeof(uchar4)}};
+   return read_back(c, out, img[which].first, (size_t)c->W * c->H * img[which].second);
+}
+
+int uh_get_forward_stats(uh_ctx* c, UhForwardStats* out) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_forward_stats: null destination");
+   std::memset(out, 0, sizeof(*out));
+   uh_ctx::Forward& f = c->fw;
+   if (!f.color.p) return UH_OK;
+   HIP_TRY(c, hipSetDevice(c->device));
+   if (int st = sync_all(c)) return st;
+   for (int k = 0; k < 3; k++) {
+      uh_ctx::Hybrid::Stage& st = f.stage[k];
+      if (!st.ran) continue;
+      if (!st.timed) {
+         HIP_TRY(c, hipEventElapsedTime(&st.ms, st.begin, st.end));
+         st.timed = true;
+      }
+      out->pass_ms[k] = st.ms;
+   }
+   out->renders = f.renders;
+   if (f.stage[1].ran) {
+      out->pieces = f.pieces;
+      out->lights = f.lights_used;
+      HIP_TRY(c, hipMemcpy(&out->covered_pixels, f.covered.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+   }
    return UH_OK;
 }
 

@@ -348,6 +348,39 @@ void launch_shadow_count(const LaunchCfg&, const ShadowDev&);
 void launch_shadow_emit(const LaunchCfg&, const ShadowDev&);
 void launch_shadow_resolve(const LaunchCfg&, const ShadowDev&);
 void launch_hybrid_sky(const LaunchCfg&, const FrameParams&, const HybridDev&, const HybridFrameDev&, const IblMaps* cube);
+// the forward pass's rasteriser (forward.hip): setup per triangle, binning into kForwardTile^2 tiles, a visibility buffer resolved per
+// tile in LDS (the 64-bit min of depth bits << 32 | ~record), then one shading lane per pixel
+constexpr uint32_t kForwardTile = 64;
+struct ForwardDev {
+   const UhVertex* vertices;    // HybridDev's tables: vertex vertex_base + indices[3 t + k] of triangle t (mesh tri_mesh[t]); t is the draw index
+   const uint32_t* indices;
+   const HybridMesh* meshes;
+   const uint32_t* tri_mesh;
+   const float* mats;           // [mesh][28]: (P V) W column-major (16), then the instance's 3x4 row-major (12)
+   uint32_t num_tris, W, H, tiles_x, tiles_y;
+   uint32_t* rec_count;         // [t]: the records of triangle t; scanned in place into record offsets (so records follow draw order)
+   uint32_t* tile_count;        // [tile]: entries per tile; scanned in place into the tiles' first entries
+   uint32_t* tile_cursor;       // a copy of the tiles' first entries, advanced by the scatter to their ends
+   uint4* records;              // 6 per record
+   uint32_t* entries;           // record ids, grouped by tile
+   float* depth;                // W * H, row 0 at NDC y = +1
+   uint32_t* vis;               // W * H draw indices, 0xFFFFFFFF none
+   uint32_t* rec_of;            // W * H: the surviving record, 0xFFFFFFFF none
+   float4* color;               // forward_output, W * H
+   uint32_t* covered;           // [0]: pixels the resolve left covered
+};
+struct ForwardShade {           // what forward.frag reads besides the scene and the fragment
+   const HybridLight* lights;   // k_hybrid_light_prep's records, the sun first
+   uint32_t count;              // view.num_lights + 1
+   float eye[3];                // view.eye_pos
+   float view[16];              // view.view (calculateShadow's cascade choice)
+};
+void launch_forward_clear(const LaunchCfg&, const ForwardDev&, uchar4* present);
+void launch_forward_count(const LaunchCfg&, const ForwardDev&);
+void launch_forward_emit(const LaunchCfg&, const ForwardDev&);
+void launch_forward_resolve(const LaunchCfg&, const ForwardDev&);
+void launch_forward_shade(const LaunchCfg&, const SceneDev&, const ForwardDev&, const ForwardShade&, const ShadowLookup* shadow);
+void launch_hybrid_light_prep(const LaunchCfg&, const HybridFrameDev&);
 // tiles
 // on-device refit (refit.hip): per-mesh object->world rows, and what one refit pass touches
 struct RefitMesh {

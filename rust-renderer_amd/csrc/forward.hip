@@ -1,0 +1,326 @@
+// forward.hip — the forward pass of build_minimal_forward_render_graph (utopian/src/renderers/forward.rs, shaders/forward/forward.vert /
+// forward.frag) on gfx950: a perspective triangle rasteriser with a depth test and perspective-correct interpolation, then forward.frag
+// once per pixel (a visibility buffer: under LESS_OR_EQUAL only the surviving fragment's colour remains). Four kernels:
+//   k_forward_count    one lane per triangle (= draw index): forward.vert's gl_Position, clip to 0 <= z <= w, divide, viewport, then
+//                      raster_device.h's guard-band clip, snap and rejects; counts its records and, per tile its box touches, one entry
+//   (device_scan.h)    record offsets (in draw order) and the tiles' first entries
+//   k_forward_emit     the same setup again: writes the records and scatters their ids into the tiles' lists
+//   k_forward_resolve  one block per tile: the 64-bit min of depth_bits << 32 | ~record per pixel in LDS (ds_min_u64) - the last record
+//                      in draw order among those of minimum depth - then depth, draw index and record written out once
+//   k_forward_shade    one lane per pixel: the surviving record's perspective-correct barycentrics, forward.vert's attributes and
+//                      forward.frag (surfaceShading over the sun and the lights, ambient, calculateShadow)
+// Every step is exact and pinned: DESIGN.md section 2, "Forward pass".
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "device_math.h"
+#include "device_types.h"
+#include "hybrid_shading.h"
+#include "raster_device.h"
+#include "utopian_hip.h"
+
+namespace uh {
+
+namespace {
+using raster::SubTri;
+constexpr int kSetupBlock = 256, kResolveBlock = 256, kShadeBlock = 256;
+constexpr int kSmallPixels = 16;                   // a piece whose box in the tile has at most this many pixels is drawn by one lane
+constexpr unsigned long long kEmptyKey = ~0ull;    // no fragment: depth 1.0, no visibility
+constexpr uint32_t kNone = 0xFFFFFFFFu;
+
+// a clip-space vertex and its barycentrics with respect to the original triangle
+struct HVert {
+   float x, y, z, w, b[3];
+};
+// a screen-space vertex: x, y in pixels, z the depth, w the clip w, b the original triangle's barycentrics. A guard-band crossing
+// interpolates 1/w and b/w (affine in screen space) and divides back, so the new vertex stays on the triangle.
+struct FVert {
+   float x, y, z, w, b[3];
+   __device__ static void lerp(FVert& r, const FVert& a, const FVert& b, float t) {
+      r.z = a.z + t * (b.z - a.z);
+      const float ia = 1.0f / a.w, ib = 1.0f / b.w, iw = ia + t * (ib - ia);
+      r.w = 1.0f / iw;
+      for (int j = 0; j < 3; j++) {
+         const float pa = a.b[j] * ia, pb = b.b[j] * ib;
+         r.b[j] = (pa + t * (pb - pa)) / iw;
+      }
+   }
+};
+
+// Sutherland-Hodgman in homogeneous space against z >= 0, then z <= w (d = z, then d = w - z): a crossing is computed from its
+// inside end a towards its outside end b, t = d_a / (d_a - d_b), every component a + t (b - a). Returns the count (0 or 3..5).
+__device__ __forceinline__ int clip_depth(HVert* v, int n) {
+   HVert tmp[5];
+   for (int p = 0; p < 2; p++) {
+      auto dist = [&](const HVert& q) { return p ? q.w - q.z : q.z; };
+      int m = 0;
+      for (int i = 0; i < n; i++) {
+         const HVert cur = v[i], nxt = v[(i + 1) % n];
+         const float dc = dist(cur), dn = dist(nxt);
+         const bool ci = dc >= 0.0f, ni = dn >= 0.0f;
+         if (ci) tmp[m++] = cur;
+         if (ci != ni) {
+            const HVert a = ci ? cur : nxt, b = ci ? nxt : cur;
+            const float da = ci ? dc : dn, db = ci ? dn : dc;
+            const float t = da / (da - db);
+            HVert r;
+            r.x = a.x + t * (b.x - a.x);
+            r.y = a.y + t * (b.y - a.y);
+            r.z = a.z + t * (b.z - a.z);
+            r.w = a.w + t * (b.w - a.w);
+            for (int j = 0; j < 3; j++) r.b[j] = a.b[j] + t * (b.b[j] - a.b[j]);
+            tmp[m++] = r;
+         }
+      }
+      n = m;
+      for (int i = 0; i < n; i++) v[i] = tmp[i];
+      if (n < 3) return 0;
+   }
+   return n;
+}
+
+// triangle t through forward.vert's gl_Position and the fixed-function stages: emit(k, SubTri, piece) for each piece that reaches the
+// rasteriser, piece[0..2] its three screen-space vertices in SubTri order before the winding swap
+template <class Emit>
+__device__ __forceinline__ void setup(const ForwardDev& fd, uint32_t t, Emit&& emit) {
+   const uint32_t mesh = fd.tri_mesh[t];
+   const float* M = fd.mats + (size_t)mesh * 28;
+   const uint32_t vb = fd.meshes[mesh].vertex_base;
+   HVert v[5];
+   bool finite = true;
+   for (int k = 0; k < 3; k++) {
+      const UhVertex& vx = fd.vertices[vb + fd.indices[3 * (size_t)t + k]];
+      const float px = vx.pos[0], py = vx.pos[1], pz = vx.pos[2];
+      // gl_Position = ((P V) W) (p, 1), mat4_mul's column order
+      v[k].x = ((M[0] * px + M[4] * py) + M[8] * pz) + M[12] * 1.0f;
+      v[k].y = ((M[1] * px + M[5] * py) + M[9] * pz) + M[13] * 1.0f;
+      v[k].z = ((M[2] * px + M[6] * py) + M[10] * pz) + M[14] * 1.0f;
+      v[k].w = ((M[3] * px + M[7] * py) + M[11] * pz) + M[15] * 1.0f;
+      for (int j = 0; j < 3; j++) v[k].b[j] = j == k ? 1.0f : 0.0f;
+      finite = finite && isfinite(v[k].x) && isfinite(v[k].y) && isfinite(v[k].z) && isfinite(v[k].w);
+   }
+   if (!finite) return;
+   const int n = clip_depth(v, 3);
+   const float fW = (float)fd.W, fH = (float)fd.H, hw = fW * 0.5f, hh = fH * 0.5f, nhh = -hh;
+   FVert s[5];
+   for (int i = 0; i < n; i++) {  // divide by w, then the viewport (0, H, W, -H): x = W/2 + xn W/2, y = H/2 - yn H/2
+      const float xn = v[i].x / v[i].w, yn = v[i].y / v[i].w, zn = v[i].z / v[i].w;
+      s[i].x = xn * hw + hw;
+      s[i].y = yn * nhh + hh;
+      s[i].z = zn;
+      s[i].w = v[i].w;
+      for (int j = 0; j < 3; j++) s[i].b[j] = v[i].b[j];
+   }
+   int k = 0;
+   for (int j = 1; j + 1 < n; j++)  // the fan (s0, sj, sj+1)
+      raster::screen_triangle(s[0], s[j], s[j + 1], (int)fd.W, (int)fd.H, [&](int, const SubTri& st, const FVert* const* piece) { emit(k++, st, piece); });
+}
+
+template <class F>
+__device__ __forceinline__ void for_tiles(const SubTri& st, uint32_t tiles_x, F&& f) {
+   for (int ty = st.y0 / (int)kForwardTile; ty <= st.y1 / (int)kForwardTile; ty++)
+      for (int tx = st.x0 / (int)kForwardTile; tx <= st.x1 / (int)kForwardTile; tx++) f((uint32_t)ty * tiles_x + (uint32_t)tx);
+}
+
+__global__ __launch_bounds__(kSetupBlock) void k_forward_count(ForwardDev fd) {
+   for (uint32_t t = blockIdx.x * kSetupBlock + threadIdx.x; t < fd.num_tris; t += gridDim.x * kSetupBlock) {
+      uint32_t count = 0;
+      setup(fd, t, [&](int, const SubTri& st, const FVert* const*) {
+         count++;
+         for_tiles(st, fd.tiles_x, [&](uint32_t tile) { atomicAdd(&fd.tile_count[tile], 1u); });
+      });
+      fd.rec_count[t] = count;
+   }
+}
+
+// record r, 6 uint4: (X0, Y0, X1, Y1) (X2, Y2, z0, z1) (z2, x0 | x1 << 16, y0 | y1 << 16, draw) (w0, w1, w2, b00) (b01, b02, b10, b11)
+// (b12, b20, b21, b22), vertex order after the winding swap; the first three are the shadow maps' record with the draw index added
+__global__ __launch_bounds__(kSetupBlock) void k_forward_emit(ForwardDev fd) {
+   for (uint32_t t = blockIdx.x * kSetupBlock + threadIdx.x; t < fd.num_tris; t += gridDim.x * kSetupBlock) {
+      const uint32_t first = fd.rec_count[t];
+      setup(fd, t, [&](int k, const SubTri& st, const FVert* const* piece) {
+         const uint32_t r = first + (uint32_t)k;
+         const FVert* p[3] = {piece[0], st.swapped ? piece[2] : piece[1], st.swapped ? piece[1] : piece[2]};
+         uint4* q = fd.records + 6 * (size_t)r;
+         auto u = [](float f) { return __float_as_uint(f); };
+         q[0] = make_uint4((uint32_t)st.X[0], (uint32_t)st.Y[0], (uint32_t)st.X[1], (uint32_t)st.Y[1]);
+         q[1] = make_uint4((uint32_t)st.X[2], (uint32_t)st.Y[2], u(st.z[0]), u(st.z[1]));
+         q[2] = make_uint4(u(st.z[2]), (uint32_t)st.x0 | ((uint32_t)st.x1 << 16), (uint32_t)st.y0 | ((uint32_t)st.y1 << 16), t);
+         q[3] = make_uint4(u(p[0]->w), u(p[1]->w), u(p[2]->w), u(p[0]->b[0]));
+         q[4] = make_uint4(u(p[0]->b[1]), u(p[0]->b[2]), u(p[1]->b[0]), u(p[1]->b[1]));
+         q[5] = make_uint4(u(p[1]->b[2]), u(p[2]->b[0]), u(p[2]->b[1]), u(p[2]->b[2]));
+         for_tiles(st, fd.tiles_x, [&](uint32_t tile) { fd.entries[atomicAdd(&fd.tile_cursor[tile], 1u)] = r; });
+      });
+   }
+}
+
+struct Rec {
+   raster::Edges e;
+   float z0, z1, z2;
+   int x0, x1, y0, y1;
+};
+__device__ __forceinline__ Rec load_rec(const uint4* __restrict__ records, uint32_t r) {
+   const uint4 a = records[6 * (size_t)r], b = records[6 * (size_t)r + 1], c = records[6 * (size_t)r + 2];
+   Rec q;
+   q.e = raster::make_edges((int)a.x, (int)a.y, (int)a.z, (int)a.w, (int)b.x, (int)b.y);
+   q.z0 = __uint_as_float(b.z), q.z1 = __uint_as_float(b.w), q.z2 = __uint_as_float(c.x);
+   q.x0 = (int)(c.y & 0xffffu), q.x1 = (int)(c.y >> 16), q.y0 = (int)(c.z & 0xffffu), q.y1 = (int)(c.z >> 16);
+   return q;
+}
+// pixel (px, py) of record r: covered, then z kept when 0 <= z <= 1 (-0 as +0), then the unsigned min of the key
+__device__ __forceinline__ void raster_pixel(const Rec& q, uint32_t r, int px, int py, unsigned long long* keys, int ox, int oy) {
+   long long e0, e1, e2;
+   if (!raster::cover(q.e, px, py, e0, e1, e2)) return;
+   const float z = raster::depth_at(q.e, q.z0, q.z1, q.z2, e1, e2);
+   if (!(z >= 0.0f && z <= 1.0f)) return;
+   const uint32_t bits = z == 0.0f ? 0u : __float_as_uint(z);
+   atomicMin(&keys[(py - oy) * (int)kForwardTile + (px - ox)], ((unsigned long long)bits << 32) | (unsigned long long)(~r));
+}
+
+__global__ __launch_bounds__(kResolveBlock) void k_forward_resolve(ForwardDev fd) {
+   __shared__ unsigned long long s_key[kForwardTile * kForwardTile];  // 32 KiB
+   __shared__ uint32_t s_big[kResolveBlock];
+   __shared__ uint32_t s_nbig, s_covered;
+   const uint32_t tile = blockIdx.x;
+   const int ox = (int)((tile % fd.tiles_x) * kForwardTile), oy = (int)((tile / fd.tiles_x) * kForwardTile);
+   const int W = (int)fd.W, tw = min((int)kForwardTile, W - ox), th = min((int)kForwardTile, (int)fd.H - oy);
+   for (uint32_t i = threadIdx.x; i < kForwardTile * kForwardTile; i += kResolveBlock) s_key[i] = kEmptyKey;
+   if (threadIdx.x == 0) s_nbig = 0, s_covered = 0;
+   __syncthreads();
+   const uint32_t begin = fd.tile_count[tile], end = fd.tile_cursor[tile];
+   for (uint32_t base = begin; base < end; base += kResolveBlock) {
+      const uint32_t i = base + threadIdx.x;
+      if (i < end) {
+         const uint32_t r = fd.entries[i];
+         const Rec q = load_rec(fd.records, r);
+         const int x0 = max(q.x0, ox), x1 = min(q.x1, ox + tw - 1), y0 = max(q.y0, oy), y1 = min(q.y1, oy + th - 1);
+         if ((x1 - x0 + 1) * (y1 - y0 + 1) <= kSmallPixels) {
+            for (int py = y0; py <= y1; py++)
+               for (int px = x0; px <= x1; px++) raster_pixel(q, r, px, py, s_key, ox, oy);
+         } else {
+            s_big[atomicAdd(&s_nbig, 1u)] = r;
+         }
+      }
+      __syncthreads();
+      const uint32_t nbig = s_nbig;
+      for (uint32_t k = 0; k < nbig; k++) {  // the large boxes: the whole block strides over the box's pixels in the tile
+         const uint32_t r = s_big[k];
+         const Rec q = load_rec(fd.records, r);
+         const int x0 = max(q.x0, ox), x1 = min(q.x1, ox + tw - 1), y0 = max(q.y0, oy), y1 = min(q.y1, oy + th - 1);
+         const int w = x1 - x0 + 1, npx = w * (y1 - y0 + 1);
+         for (int p = (int)threadIdx.x; p < npx; p += kResolveBlock) raster_pixel(q, r, x0 + p % w, y0 + p / w, s_key, ox, oy);
+      }
+      __syncthreads();
+      if (threadIdx.x == 0) s_nbig = 0;
+      __syncthreads();
+   }
+   for (int i = (int)threadIdx.x; i < tw * th; i += kResolveBlock) {
+      const int ly = i / tw, lx = i - ly * tw;
+      const unsigned long long key = s_key[ly * (int)kForwardTile + lx];
+      const size_t pix = (size_t)(oy + ly) * W + ox + lx;
+      const uint32_t r = key == kEmptyKey ? kNone : ~(uint32_t)key;
+      fd.depth[pix] = key == kEmptyKey ? 1.0f : __uint_as_float((uint32_t)(key >> 32));
+      fd.rec_of[pix] = r;
+      fd.vis[pix] = r == kNone ? kNone : fd.records[6 * (size_t)r + 2].w;
+      if (r != kNone) atomicAdd(&s_covered, 1u);
+   }
+   __syncthreads();
+   if (threadIdx.x == 0 && s_covered) atomicAdd(fd.covered, s_covered);
+}
+
+// forward.frag at pixel i: the surviving record's integer edge functions give the screen weights l_k = e_k / area; q_k = l_k / w_k and
+// b = (q0 B0 + q1 B1 + q2 B2) / (q0 + q1 + q2) are the original triangle's barycentrics; every attribute is (a0 b0 + a1 b1) + a2 b2.
+// One lane per pixel, no grid-stride loop (the light records become scalar loads, as in k_hybrid_deferred).
+template <bool kShadow>
+__global__ __launch_bounds__(kShadeBlock) void k_forward_shade(SceneDev sc, ForwardDev fd, ForwardShade fs, ShadowLookup sl) {
+   const uint32_t n = fd.W * fd.H, i = blockIdx.x * kShadeBlock + threadIdx.x;
+   if (i >= n) return;
+   const uint32_t r = fd.rec_of[i];
+   if (r == kNone) {  // the clear colour (pass.rs: (1, 1, 1, 0))
+      fd.color[i] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+      return;
+   }
+   const uint4* q = fd.records + 6 * (size_t)r;
+   const uint4 a = q[0], b = q[1], c = q[2], d = q[3], e = q[4], f = q[5];
+   const raster::Edges ed = raster::make_edges((int)a.x, (int)a.y, (int)a.z, (int)a.w, (int)b.x, (int)b.y);
+   long long e0, e1, e2;
+   raster::cover(ed, (int)(i % fd.W), (int)(i / fd.W), e0, e1, e2);
+   const float l0 = (float)e0 / ed.fa, l1 = (float)e1 / ed.fa, l2 = (float)e2 / ed.fa;
+   const float q0 = l0 / __uint_as_float(d.x), q1 = l1 / __uint_as_float(d.y), q2 = l2 / __uint_as_float(d.z);
+   const float B[3][3] = {{__uint_as_float(d.w), __uint_as_float(e.x), __uint_as_float(e.y)},
+                          {__uint_as_float(e.z), __uint_as_float(e.w), __uint_as_float(f.x)},
+                          {__uint_as_float(f.y), __uint_as_float(f.z), __uint_as_float(f.w)}};
+   const float s = (q0 + q1) + q2;
+   const float b0 = ((q0 * B[0][0] + q1 * B[1][0]) + q2 * B[2][0]) / s;
+   const float b1 = ((q0 * B[0][1] + q1 * B[1][1]) + q2 * B[2][1]) / s;
+   const float b2 = ((q0 * B[0][2] + q1 * B[1][2]) + q2 * B[2][2]) / s;
+   const uint32_t t = c.w, mesh = fd.tri_mesh[t];
+   const HybridMesh m = fd.meshes[mesh];
+   const UhVertex& v0 = fd.vertices[m.vertex_base + fd.indices[3 * (size_t)t]];
+   const UhVertex& v1 = fd.vertices[m.vertex_base + fd.indices[3 * (size_t)t + 1]];
+   const UhVertex& v2 = fd.vertices[m.vertex_base + fd.indices[3 * (size_t)t + 2]];
+   const float* o = fd.mats + (size_t)mesh * 28 + 16;  // out_pos = (world (p, 1)).xyz, world row-major 3x4
+   auto world = [&](const UhVertex& v) {
+      return v3(((o[0] * v.pos[0] + o[1] * v.pos[1]) + o[2] * v.pos[2]) + o[3] * 1.0f, ((o[4] * v.pos[0] + o[5] * v.pos[1]) + o[6] * v.pos[2]) + o[7] * 1.0f,
+                ((o[8] * v.pos[0] + o[9] * v.pos[1]) + o[10] * v.pos[2]) + o[11] * 1.0f);
+   };
+   const V3 P = (world(v0) * b0 + world(v1) * b1) + world(v2) * b2;
+   V3 N;
+   float uu, vv;
+   surface_attributes(sc, m, v0, v1, v2, b0, b1, b2, N, uu, vv);                                // vert, frag:44-53
+   const V3 dt = sample_texture(sc, sc.unorm_lut, m.diffuse_map, uu, vv);                      // frag:39
+   const V3 mr = sample_texture(sc, sc.unorm_lut, m.metallic_roughness_map, uu, vv);           // frag:41-42
+   const V3 oc = sample_texture(sc, sc.unorm_lut, m.occlusion_map, uu, vv);                    // frag:43
+   auto gamma = [](float x) { return (float)pow((double)x, (double)2.2f); };                   // frag:46, pow in double
+   const V3 diffuse = v3(gamma(dt.x), gamma(dt.y), gamma(dt.z));
+   V3 bc = v3(1.0f, 1.0f, 1.0f);
+   if (mesh < sc.num_meshes) bc = v3(sc.meshes[mesh].base_color[0], sc.meshes[mesh].base_color[1], sc.meshes[mesh].base_color[2]);
+   const V3 base = diffuse * bc;                                                                // frag:57
+   const float metallic = mr.z, roughness = mr.y, occlusion = oc.x;                             // frag:41-43, no factors
+   const V3 V = normalize3(v3(fs.eye[0], fs.eye[1], fs.eye[2]) - P);                            // lighting:26
+   const V3 Lo = direct_lighting(fs.lights, fs.count, P, N, V, base, metallic, roughness);      // frag:66-74
+   V3 color = (0.03f * diffuse) * occlusion + Lo;                                               // frag:77-78
+   if (kShadow) color = color * calculate_shadow(sl, fs.view, P);                               // frag:81-85
+   fd.color[i] = make_float4(color.x, color.y, color.z, 1.0f);                                  // frag:93
+}
+
+// the images as the first call finds them: forward_output (1, 1, 1, 0), depth 1.0, no visibility, present (255, 255, 255, 0)
+__global__ __launch_bounds__(kShadeBlock) void k_forward_clear(ForwardDev fd, uchar4* present) {
+   const uint32_t n = fd.W * fd.H;
+   for (uint32_t i = blockIdx.x * kShadeBlock + threadIdx.x; i < n; i += gridDim.x * kShadeBlock) {
+      fd.color[i] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+      fd.depth[i] = 1.0f;
+      fd.vis[i] = kNone;
+      fd.rec_of[i] = kNone;
+      present[i] = make_uchar4(255, 255, 255, 0);
+   }
+}
+
+inline dim3 setup_grid(const LaunchCfg& c, uint32_t n) {
+   const uint32_t blocks = (n + kSetupBlock - 1) / kSetupBlock, cap = c.num_cus * 8;
+   return dim3(blocks < cap ? (blocks ? blocks : 1) : cap);
+}
+}  // namespace
+
+void launch_forward_clear(const LaunchCfg& c, const ForwardDev& fd, uchar4* present) {
+   k_forward_clear<<<setup_grid(c, fd.W * fd.H), kShadeBlock, 0, c.stream>>>(fd, present);
+}
+void launch_forward_count(const LaunchCfg& c, const ForwardDev& fd) {
+   if (fd.num_tris) k_forward_count<<<setup_grid(c, fd.num_tris), kSetupBlock, 0, c.stream>>>(fd);
+}
+void launch_forward_emit(const LaunchCfg& c, const ForwardDev& fd) {
+   if (fd.num_tris) k_forward_emit<<<setup_grid(c, fd.num_tris), kSetupBlock, 0, c.stream>>>(fd);
+}
+void launch_forward_resolve(const LaunchCfg& c, const ForwardDev& fd) {
+   k_forward_resolve<<<dim3(fd.tiles_x * fd.tiles_y), kResolveBlock, 0, c.stream>>>(fd);
+}
+void launch_forward_shade(const LaunchCfg& c, const SceneDev& sc, const ForwardDev& fd, const ForwardShade& fs, const ShadowLookup* shadow) {
+   const dim3 grid((fd.W * fd.H + kShadeBlock - 1) / kShadeBlock);
+   if (shadow)
+      k_forward_shade<true><<<grid, kShadeBlock, 0, c.stream>>>(sc, fd, fs, *shadow);
+   else
+      k_forward_shade<false><<<grid, kShadeBlock, 0, c.stream>>>(sc, fd, fs, ShadowLookup{});
+}
+
+}  // namespace uh

@@ -15,101 +15,31 @@
 
 #include "device_scan.h"
 #include "device_types.h"
+#include "raster_device.h"
 #include "utopian_hip.h"
 
 namespace uh {
 
 namespace {
+using raster::SubTri;
 constexpr int kSetupBlock = 256, kResolveBlock = 256;
-constexpr float kGuard = 524288.0f;     // 2^19 texels: the guard band every vertex is clipped to; snapped coordinates stay below 2^27
 constexpr int kSmallPixels = 16;        // a triangle whose box in the tile has at most this many texels is drawn by one lane
 constexpr uint32_t kOne = 0x3f800000u;  // 1.0f, the cleared depth
 
 struct ClipVert {
    float x, y, z;
-};
-struct SubTri {
-   int X[3], Y[3];
-   float z[3];
-   int x0, x1, y0, y1;  // the texels whose centres the snapped box holds, inclusive, inside [0, S)
+   __device__ static void lerp(ClipVert& r, const ClipVert& a, const ClipVert& b, float t) { r.z = a.z + t * (b.z - a.z); }
 };
 
-__device__ __forceinline__ int ceil_shift8(int a) { return -((-a) >> 8); }
-
-// snap, orient, box and reject one triangle of screen-space vertices (all inside the guard band); false when it emits nothing
-__device__ __forceinline__ bool finish(const ClipVert& a, const ClipVert& b, const ClipVert& c, int S, SubTri& t) {
-   if (a.z < 0.0f && b.z < 0.0f && c.z < 0.0f) return false;
-   if (a.z > 1.0f && b.z > 1.0f && c.z > 1.0f) return false;
-   int X[3] = {(int)rintf(a.x * 256.0f), (int)rintf(b.x * 256.0f), (int)rintf(c.x * 256.0f)};
-   int Y[3] = {(int)rintf(a.y * 256.0f), (int)rintf(b.y * 256.0f), (int)rintf(c.y * 256.0f)};
-   float z[3] = {a.z, b.z, c.z};
-   const long long area = (long long)(X[1] - X[0]) * (Y[2] - Y[0]) - (long long)(Y[1] - Y[0]) * (X[2] - X[0]);
-   if (area == 0) return false;
-   if (area < 0) {  // no culling: the other winding is swapped into this one
-      int tx = X[1], ty = Y[1];
-      float tz = z[1];
-      X[1] = X[2], Y[1] = Y[2], z[1] = z[2];
-      X[2] = tx, Y[2] = ty, z[2] = tz;
-   }
-   const int xmin = min(X[0], min(X[1], X[2])), xmax = max(X[0], max(X[1], X[2]));
-   const int ymin = min(Y[0], min(Y[1], Y[2])), ymax = max(Y[0], max(Y[1], Y[2]));
-   t.x0 = max(ceil_shift8(xmin - 128), 0);
-   t.x1 = min((xmax - 128) >> 8, S - 1);
-   t.y0 = max(ceil_shift8(ymin - 128), 0);
-   t.y1 = min((ymax - 128) >> 8, S - 1);
-   if (t.x0 > t.x1 || t.y0 > t.y1) return false;
-   for (int k = 0; k < 3; k++) t.X[k] = X[k], t.Y[k] = Y[k], t.z[k] = z[k];
-   return true;
-}
-
-// Sutherland-Hodgman against x >= -G, x <= G, y >= -G, y <= G, in that order; a crossing edge's point is computed from its inside
-// end a towards its outside end b (so the two triangles of a shared edge compute the same point): t = (B - a.c) / (b.c - a.c),
-// the clipped coordinate B, the other a.o + t (b.o - a.o), z likewise. Returns the vertex count (0 or 3..7) in v.
-__device__ __noinline__ int clip_guard(ClipVert* v, int n) {
-   ClipVert tmp[8];
-   for (int p = 0; p < 4; p++) {
-      const int axis = p >> 1;
-      const float B = (p & 1) ? kGuard : -kGuard;
-      auto coord = [&](const ClipVert& q) { return axis ? q.y : q.x; };
-      auto inside = [&](const ClipVert& q) { return (p & 1) ? coord(q) <= B : coord(q) >= B; };
-      int m = 0;
-      for (int i = 0; i < n; i++) {
-         const ClipVert cur = v[i], nxt = v[(i + 1) % n];
-         const bool ci = inside(cur), ni = inside(nxt);
-         if (ci) tmp[m++] = cur;
-         if (ci != ni) {
-            const ClipVert a = ci ? cur : nxt, b = ci ? nxt : cur;
-            const float t = (B - coord(a)) / (coord(b) - coord(a));
-            ClipVert r;
-            if (axis) {
-               r.y = B;
-               r.x = a.x + t * (b.x - a.x);
-            } else {
-               r.x = B;
-               r.y = a.y + t * (b.y - a.y);
-            }
-            r.z = a.z + t * (b.z - a.z);
-            tmp[m++] = r;
-         }
-      }
-      n = m;
-      for (int i = 0; i < n; i++) v[i] = tmp[i];
-      if (n < 3) return 0;
-   }
-   for (int i = 0; i < n; i++)
-      if (!(fabsf(v[i].x) <= kGuard) || !(fabsf(v[i].y) <= kGuard) || !(v[i].z == v[i].z)) return 0;
-   return n;
-}
-
-// triangle t of cascade c through shadow.vert and the fixed-function stages: emit(k, SubTri) for each piece that reaches the rasteriser
+// triangle t of cascade c through shadow.vert and the fixed-function stages (raster_device.h): emit(k, SubTri) for each piece that
+// reaches the rasteriser
 template <class Emit>
 __device__ __forceinline__ void setup(const ShadowDev& sd, uint32_t t, uint32_t c, Emit&& emit) {
    const uint32_t mesh = sd.tri_mesh[t];
    const float* M = sd.mats + ((size_t)c * sd.num_meshes + mesh) * 16;
    const uint32_t vb = sd.meshes[mesh].vertex_base;
    const float S = (float)sd.size, half = S * 0.5f, nhalf = -half;
-   ClipVert v[8];
-   bool guard = false, finite = true;
+   ClipVert v[3];
    for (int k = 0; k < 3; k++) {
       const UhVertex& vx = sd.vertices[vb + sd.indices[3 * (size_t)t + k]];
       const float px = vx.pos[0], py = vx.pos[1], pz = vx.pos[2];
@@ -120,24 +50,8 @@ __device__ __forceinline__ void setup(const ShadowDev& sd, uint32_t t, uint32_t 
       v[k].x = xd * half + half;   // viewport (0, S, S, -S): x = S/2 + xd S/2, y = S/2 - yd S/2, depth 0..1
       v[k].y = yd * nhalf + half;
       v[k].z = zd;
-      finite = finite && isfinite(v[k].x) && isfinite(v[k].y) && isfinite(v[k].z);
-      guard = guard || !(fabsf(v[k].x) <= kGuard) || !(fabsf(v[k].y) <= kGuard);
    }
-   if (!finite) return;
-   if (v[0].z < 0.0f && v[1].z < 0.0f && v[2].z < 0.0f) return;
-   if (v[0].z > 1.0f && v[1].z > 1.0f && v[2].z > 1.0f) return;
-   // every vertex on the far side of one viewport edge: no texel centre can be covered (snapping moves a vertex by 1/512 texel)
-   if ((v[0].x < 0.0f && v[1].x < 0.0f && v[2].x < 0.0f) || (v[0].y < 0.0f && v[1].y < 0.0f && v[2].y < 0.0f)) return;
-   if ((v[0].x > S && v[1].x > S && v[2].x > S) || (v[0].y > S && v[1].y > S && v[2].y > S)) return;
-   SubTri st;
-   if (!guard) {
-      if (finish(v[0], v[1], v[2], (int)sd.size, st)) emit(0, st);
-      return;
-   }
-   const int n = clip_guard(v, 3);
-   int k = 0;
-   for (int j = 1; j + 1 < n; j++)  // the fan (v0, vj, vj+1)
-      if (finish(v[0], v[j], v[j + 1], (int)sd.size, st)) emit(k++, st);
+   raster::screen_triangle(v[0], v[1], v[2], (int)sd.size, (int)sd.size, [&](int k, const SubTri& st, const ClipVert* const*) { emit(k, st); });
 }
 
 template <class F>
@@ -175,36 +89,23 @@ __global__ __launch_bounds__(kSetupBlock) void k_shadow_emit(ShadowDev sd) {
 }
 
 struct Rec {
-   int X0, Y0, X1, Y1, X2, Y2;
-   float z0, z1, z2, fa;
-   bool tl0, tl1, tl2;  // top-left edges v1 -> v2, v2 -> v0, v0 -> v1
+   raster::Edges e;
+   float z0, z1, z2;
    int x0, x1, y0, y1;
 };
-__device__ __forceinline__ bool top_left(int dx, int dy) { return dy < 0 || (dy == 0 && dx > 0); }
 __device__ __forceinline__ Rec load_rec(const uint4* __restrict__ records, uint32_t r) {
    const uint4 a = records[3 * (size_t)r], b = records[3 * (size_t)r + 1], c = records[3 * (size_t)r + 2];
    Rec q;
-   q.X0 = (int)a.x, q.Y0 = (int)a.y, q.X1 = (int)a.z, q.Y1 = (int)a.w, q.X2 = (int)b.x, q.Y2 = (int)b.y;
+   q.e = raster::make_edges((int)a.x, (int)a.y, (int)a.z, (int)a.w, (int)b.x, (int)b.y);
    q.z0 = __uint_as_float(b.z), q.z1 = __uint_as_float(b.w), q.z2 = __uint_as_float(c.x);
    q.x0 = (int)(c.y & 0xffffu), q.x1 = (int)(c.y >> 16), q.y0 = (int)(c.z & 0xffffu), q.y1 = (int)(c.z >> 16);
-   const long long area = (long long)(q.X1 - q.X0) * (q.Y2 - q.Y0) - (long long)(q.Y1 - q.Y0) * (q.X2 - q.X0);
-   q.fa = (float)area;
-   q.tl0 = top_left(q.X2 - q.X1, q.Y2 - q.Y1);
-   q.tl1 = top_left(q.X0 - q.X2, q.Y0 - q.Y2);
-   q.tl2 = top_left(q.X1 - q.X0, q.Y1 - q.Y0);
    return q;
 }
-// texel (px, py): covered when every edge function at the centre is > 0, or = 0 on a top-left edge; then z from the integer
-// barycentrics, kept when 0 <= z <= 1, -0 stored as +0
-__device__ __forceinline__ void raster(const Rec& q, int px, int py, uint32_t* tile_depth, int ox, int oy) {
-   const long long Px = (long long)px * 256 + 128, Py = (long long)py * 256 + 128;
-   const long long e0 = (long long)(q.X2 - q.X1) * (Py - q.Y1) - (long long)(q.Y2 - q.Y1) * (Px - q.X1);
-   const long long e1 = (long long)(q.X0 - q.X2) * (Py - q.Y2) - (long long)(q.Y0 - q.Y2) * (Px - q.X2);
-   const long long e2 = (long long)(q.X1 - q.X0) * (Py - q.Y0) - (long long)(q.Y1 - q.Y0) * (Px - q.X0);
-   const bool in = (e0 > 0 || (e0 == 0 && q.tl0)) && (e1 > 0 || (e1 == 0 && q.tl1)) && (e2 > 0 || (e2 == 0 && q.tl2));
-   if (!in) return;
-   const float l1 = (float)e1 / q.fa, l2 = (float)e2 / q.fa;
-   const float z = (q.z0 + l1 * (q.z1 - q.z0)) + l2 * (q.z2 - q.z0);
+// texel (px, py): covered (raster::cover), then z from the integer barycentrics, kept when 0 <= z <= 1, -0 stored as +0
+__device__ __forceinline__ void raster_texel(const Rec& q, int px, int py, uint32_t* tile_depth, int ox, int oy) {
+   long long e0, e1, e2;
+   if (!raster::cover(q.e, px, py, e0, e1, e2)) return;
+   const float z = raster::depth_at(q.e, q.z0, q.z1, q.z2, e1, e2);
    if (!(z >= 0.0f && z <= 1.0f)) return;
    const uint32_t bits = z == 0.0f ? 0u : __float_as_uint(z);
    atomicMin(&tile_depth[(py - oy) * (int)kShadowTile + (px - ox)], bits);
@@ -229,7 +130,7 @@ __global__ __launch_bounds__(kResolveBlock) void k_shadow_resolve(ShadowDev sd) 
          const int x0 = max(q.x0, ox), x1 = min(q.x1, ox + tw - 1), y0 = max(q.y0, oy), y1 = min(q.y1, oy + th - 1);
          if ((x1 - x0 + 1) * (y1 - y0 + 1) <= kSmallPixels) {
             for (int py = y0; py <= y1; py++)
-               for (int px = x0; px <= x1; px++) raster(q, px, py, s_depth, ox, oy);
+               for (int px = x0; px <= x1; px++) raster_texel(q, px, py, s_depth, ox, oy);
          } else {
             s_big[atomicAdd(&s_nbig, 1u)] = r;
          }
@@ -240,7 +141,7 @@ __global__ __launch_bounds__(kResolveBlock) void k_shadow_resolve(ShadowDev sd) 
          const Rec q = load_rec(sd.records, s_big[k]);
          const int x0 = max(q.x0, ox), x1 = min(q.x1, ox + tw - 1), y0 = max(q.y0, oy), y1 = min(q.y1, oy + th - 1);
          const int w = x1 - x0 + 1, npx = w * (y1 - y0 + 1);
-         for (int p = (int)threadIdx.x; p < npx; p += kResolveBlock) raster(q, x0 + p % w, y0 + p / w, s_depth, ox, oy);
+         for (int p = (int)threadIdx.x; p < npx; p += kResolveBlock) raster_texel(q, x0 + p % w, y0 + p / w, s_depth, ox, oy);
       }
       __syncthreads();
       if (threadIdx.x == 0) s_nbig = 0;

@@ -237,3 +237,24 @@ class ShadowMapStats(C.Structure):
 
 
 assert C.sizeof(ShadowMapStats) == 304 and ShadowMapStats.triangles.offset == 12 and ShadowMapStats.params.offset == 32
+
+
+# the forward graph: build_minimal_forward_render_graph (utopian/src/renderers/mod.rs; the reference's render mode 3)
+FORWARD_PASS, FORWARD_PRESENT = 1 << 0, 1 << 1
+FORWARD_SHADOW_MAPS = HYBRID_SHADOW_MAPS
+FORWARD_GRAPH = FORWARD_SHADOW_MAPS | FORWARD_PASS | FORWARD_PRESENT
+FORWARD_OUTPUT, FORWARD_DEPTH, FORWARD_VISIBILITY, FORWARD_PRESENT_OUTPUT = range(4)
+FORWARD_NONE = 0xFFFFFFFF  # FORWARD_VISIBILITY of a pixel nothing was drawn on
+
+
+class ForwardStats(C.Structure):
+    """UhForwardStats: the last uh_render_forward call - hipEvent ms of (shadow maps, forward, present), the forward renders so far, and
+    of the last forward pass the triangle pieces that reached the rasteriser, the covered pixels and the lights evaluated (the sun
+    included)"""
+
+    _fields_ = [("pass_ms", C.c_float * 3), ("renders", C.c_uint32), ("pieces", C.c_uint32), ("covered_pixels", C.c_uint32), ("lights", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(ForwardStats) == 32 and ForwardStats.renders.offset == 12 and ForwardStats.pieces.offset == 16 and \
+    ForwardStats.covered_pixels.offset == 20 and ForwardStats.lights.offset == 24

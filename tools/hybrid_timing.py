@@ -11,10 +11,13 @@ what is timed:
           median of --builds renders, with the triangles per cascade; the whole frame with shadows_enabled = 0 and 1 (maps rendered
           once); the whole frame with the reference's default flags (shadows_enabled = ibl_enabled = cubemap_enabled = 1, the IBL
           and shadow maps built once), and the same frame with the shadow maps re-rendered in every call, as the reference does
+  forward the forward graph (uh_render_forward: shadow maps, forward pass, present) with each light count of --lights and
+          shadows_enabled = 0, then shadows_enabled = 1 with the maps re-rendered in every call (the reference's key 3), beside the
+          hybrid G-buffer cast + deferred pass of the same view
 
 Run it under `rocprofv3 --kernel-trace --stats -- python tools/hybrid_timing.py --mode ...` for the kernel table.
 
-  python tools/hybrid_timing.py [--mode passes|frame|ibl|shadows --width 1920 --height 1080 --warmup 3 --iters 20 --lights 0,16,1024
+  python tools/hybrid_timing.py [--mode passes|frame|ibl|shadows|forward --width 1920 --height 1080 --warmup 3 --iters 20 --lights 0,16,1024
                                  --builds 5 --out FILE]"""
 import argparse
 import json
@@ -136,9 +139,33 @@ def shadows(a):
                height=a.height, iters=a.iters, **{f"{p}_ms": m for p, m in zip(PASSES + ("shadow_maps",), med)}, total_ms=sum(med))
 
 
+def forward(a):
+    for n in (int(x) for x in a.lights.split(",")):
+        scene, r, view = setup(a, n, shadows_enabled=0, ibl_enabled=0, cubemap_enabled=0, num_lights=n)
+        for shadows in (0, 1):
+            view.shadows_enabled = shadows
+            if shadows:
+                r.set_shadowmap_params(rr.shadow_cascades(scene.camera, view.sun_dir[:]))
+            for _ in range(a.warmup):
+                r.render_forward(view)
+            per = []
+            for _ in range(a.iters):
+                r.render_forward(view)
+                per.append(r.forward_stats())  # waits: one call at a time on an idle GPU
+            med = [statistics.median(s.pass_ms[k] for s in per) for k in range(3)]
+            s = per[-1]
+            yield dict(metric="forward_graph", config=1, lights=n, shadows=shadows, width=a.width, height=a.height, iters=a.iters,
+                       shadow_maps_ms=med[0], forward_ms=med[1], present_ms=med[2], total_ms=sum(med), pieces=s.pieces,
+                       covered_pixels=s.covered_pixels, triangles=scene.num_triangles)
+        view.shadows_enabled = 0
+        med, _ = timed(a, r, view, rr.HYBRID_GBUFFER | rr.HYBRID_DEFERRED, rr.Renderer.hybrid_frame_stats)
+        yield dict(metric="hybrid_gbuffer_deferred", config=1, lights=n, width=a.width, height=a.height, iters=a.iters,
+                   gbuffer_ms=med[1], deferred_ms=med[4], total_ms=med[1] + med[4])
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("passes", "frame", "ibl", "shadows"), default="passes")
+    ap.add_argument("--mode", choices=("passes", "frame", "ibl", "shadows", "forward"), default="passes")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--warmup", type=int, default=3)
@@ -148,7 +175,7 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     lines = []
-    for out in {"passes": passes, "frame": frame, "ibl": ibl, "shadows": shadows}[a.mode](a):
+    for out in {"passes": passes, "frame": frame, "ibl": ibl, "shadows": shadows, "forward": forward}[a.mode](a):
         lines.append(json.dumps(out))
         print(lines[-1], flush=True)
     if a.out:
