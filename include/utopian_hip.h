@@ -524,7 +524,7 @@ int uh_mgpu_set_option(uh_mgpu* group, const char* name, int value);
  * GATES: view->raytracing_supported == 0 skips both ray-traced passes and leaves their images as they are (mod.rs:107,134);
  * UH_HYBRID_RT_REFLECTIONS with view->ibl_enabled == 1 is UH_ERR_INVALID_ARGUMENT - and nothing runs - until the IBL maps (irradiance,
  * specular, BRDF LUT of ibl.rs) have been built with UH_HYBRID_ENVIRONMENT, below; mask bits, UH_ERR_NOT_BUILT and moved instances with
- * view->rebuild_tlas as for uh_render_frame (bits above UH_HYBRID_SHADOW_MAPS, below, are ignored).
+ * view->rebuild_tlas as for uh_render_frame (bits above UH_HYBRID_SHADOW_MAPS, below, are ignored, except UH_HYBRID_MARCHING_CUBES).
  * STREAM ORDER: uh_render_hybrid enqueues like a frame (behind the frames in flight, ahead of those that follow); uh_read_hybrid and
  * uh_get_hybrid_stats wait for all work of the context and are complete on return. The exception is UH_HYBRID_SHADOW_MAPS, below: a
  * call that renders shadow maps BLOCKS the host until the frames in flight and the pass's binning have finished (it reads the
@@ -573,8 +573,8 @@ int uh_get_hybrid_stats(uh_ctx* ctx, UhHybridStats* out);
  * message, and nothing runs, for UH_HYBRID_DEFERRED with view->shadows_enabled == 1 before the first shadow-map render (the cascaded
  * shadow maps of shadow.rs) or, before the first build, view->ibl_enabled == 1 (the IBL maps of ibl.rs), for UH_HYBRID_SKY with
  * view->cubemap_enabled == 1 before the first build (the environment cube of ibl.rs), and for UH_HYBRID_DEFERRED with view->num_lights
- * above the lights added with uh_add_light. view->marching_cubes_enabled is not read: meshes of uh_add_isosurface_mesh are scene
- * geometry and go through the G-buffer like any other.
+ * above the lights added with uh_add_light. view->marching_cubes_enabled is read by UH_HYBRID_MARCHING_CUBES, below; meshes of
+ * uh_add_isosurface_mesh are scene geometry and go through the G-buffer like any other.
  * ORIENTATION (the reference draws under a Y-flipped viewport, pass.rs:260-267): deferred pixel (x, y) and present pixel (x, y) read the
  * G-buffer and deferred texel (x, y); ssao_output texel (x, y) is the occlusion of G-buffer texel (x, H-1-y) (ssao.frag samples at the
  * unflipped in_uv), and deferred pixel (x, y) reads ssao_output texel (x, H-1-y), so it is lit by its own texel's occlusion.
@@ -761,6 +761,66 @@ UH_LAYOUT_ASSERT(sizeof(UhForwardStats) == 32 && offsetof(UhForwardStats, render
 int uh_render_forward(uh_ctx* ctx, const UhViewUniformData* view, uint32_t mask);
 int uh_read_forward(uh_ctx* ctx, int which, void* out); /* UH_ERR_INVALID_ARGUMENT before the first uh_render_forward */
 int uh_get_forward_stats(uh_ctx* ctx, UhForwardStats* out);
+
+/* ---- the hybrid graph's marching-cubes pass: setup_marching_cubes_pass (mod.rs:164-174, renderers/marching_cubes.rs) ------------
+ * UH_HYBRID_MARCHING_CUBES (bit 10; bit 9 stays unused and ignored) of uh_render_hybrid runs after UH_HYBRID_DEFERRED and before
+ * UH_HYBRID_SKY, the reference's order, and only with view->marching_cubes_enabled == 1: otherwise the bit is a no-op and its pass_ms
+ * is 0. UH_HYBRID_FRAME stays 0x7f: the reference's default hybrid view with the checkbox on is
+ * UH_HYBRID_FRAME | UH_HYBRID_SHADOW_MAPS | UH_HYBRID_MARCHING_CUBES. Every call that runs it:
+ *   extraction      marching_cubes.comp on the device at view->time: the reference's 32^3 grid of voxel size 1 from the origin, the
+ *                   reference's triangulation (whatever the option iso_reference_triangulation says). pos and normal equal, bit for
+ *                   bit, those of uh_add_isosurface_mesh(ctx, 32, 0.0f, 32.0f, view->time, ...) with that triangulation; uv, colour
+ *                   and tangent are zero. The draw index of a triangle is its place in extraction order (cells x fastest, then the
+ *                   case list). The triangles are a transient buffer, not scene geometry: no mesh is added, and they are in no tree,
+ *                   shadow map, rt_shadows or rt_reflections ray.
+ *   depth buffer    the reference rasterises it in the G-buffer pass; here it comes from the G-buffer last rendered: per pixel
+ *                   d = c.z / c.w with c = (P V) (position, 1), kept when c.w > 0 and 0 <= d <= 1, else 1.0; 1.0 where the cast missed
+ *   draw            forward.vert / forward.frag (world = identity, mesh_index = 0) through the forward pass's rasteriser, depth test
+ *                   LESS_OR_EQUAL with writes against that buffer (a fragment at exactly the G-buffer's depth is drawn), shaded
+ *                   with the material of the FIRST MESH ADDED (its maps and base_color_factor: the reference's quirk) at uv (0, 0),
+ *                   the sun plus view->num_lights lights, ambient 0.03 * diffuse * occlusion, calculateShadow when
+ *                   view->shadows_enabled == 1; (colour, 1) into deferred_output at covered pixels, every other pixel untouched
+ *   sky             UH_HYBRID_SKY in the same call skips the pixels a marching-cubes fragment covers (the atmosphere pass's
+ *                   depth test): sky_pixels drops by as many
+ * UH_ERR_INVALID_ARGUMENT with a message, and nothing runs, when the bit is set with view->marching_cubes_enabled == 1 and no
+ * G-buffer was rendered (by this call or an earlier one), the scene has no mesh, view->shadows_enabled == 1 and no shadow-map render
+ * has completed (by this call or an earlier one), or view->num_lights is above the lights added. UH_ERR_NOT_BUILT and moved
+ * instances as for the other bits.
+ * STREAM ORDER: the pass BLOCKS the host until the frames in flight, the passes before it in the call and its extraction and binning
+ * have finished: it reads the triangle count and the binning totals back to size its buffers, as UH_FORWARD_PASS does.
+ * READ-BACK (uh_read_hybrid, UH_ERR_INVALID_ARGUMENT before the first pass): UH_HYBRID_DEPTH, the float32 depth buffer after the last
+ * pass, and UH_HYBRID_MARCHING_CUBES_VISIBILITY, the uint32 draw index of the surviving marching-cubes fragment or 0xFFFFFFFF;
+ * W*H texels, row 0 at NDC y = +1 as the other hybrid images.
+ * RESOURCES: the depth, visibility and triangle buffers (and the binning buffers, which grow with the mesh) are allocated by the first
+ * pass (and the final frame's images, if no earlier call allocated them) and freed by uh_destroy.
+ * ISOLATION: with the bit absent or the flag 0 nothing changes. The pass writes deferred_output and its own buffers only: no
+ * path-traced image, G-buffer, rt_shadows, rt_reflections, forward or shadow-map image, and nothing in UhStats, UhHybridStats,
+ * UhShadowMapStats or UhHybridFrameStats beyond the sky pass's sky_pixels.
+ * Arithmetic: DESIGN.md section 2, "Marching-cubes pass". */
+enum { UH_HYBRID_MARCHING_CUBES = 1u << 10 };
+enum {
+   UH_HYBRID_DEPTH = 9,                     /* float32 */
+   UH_HYBRID_MARCHING_CUBES_VISIBILITY = 10 /* uint32 draw index, 0xFFFFFFFF for none */
+};
+/* the last pass: pass_ms its hipEvent time (0 when the last call with the bit did not run it); renders the passes so far; triangles
+ * extracted (zero-area ones included), pieces that reached the rasteriser, covered_pixels with a surviving fragment, lights evaluated
+ * (the sun included) and the view->time used, all of the last pass that ran. All zero before the first pass. Waits for all work of
+ * the context. */
+typedef struct UhMarchingCubesStats {
+   float pass_ms;
+   uint32_t renders;
+   uint32_t triangles;
+   uint32_t pieces;
+   uint32_t covered_pixels;
+   uint32_t lights;
+   float time;
+   uint32_t reserved;
+} UhMarchingCubesStats;
+UH_LAYOUT_ASSERT(sizeof(UhMarchingCubesStats) == 32 && offsetof(UhMarchingCubesStats, triangles) == 8 && offsetof(UhMarchingCubesStats, pieces) == 12 &&
+                    offsetof(UhMarchingCubesStats, covered_pixels) == 16 && offsetof(UhMarchingCubesStats, lights) == 20 &&
+                    offsetof(UhMarchingCubesStats, time) == 24,
+                 "UhMarchingCubesStats (32 B)");
+int uh_get_marching_cubes_stats(uh_ctx* ctx, UhMarchingCubesStats* out);
 
 #ifdef __cplusplus
 }

@@ -31,6 +31,8 @@ from .types import (
     HYBRID_ALBEDO,
     HYBRID_ALL,
     HYBRID_DEFERRED_OUTPUT,
+    HYBRID_DEPTH,
+    HYBRID_MARCHING_CUBES_VISIBILITY,
     HYBRID_NORMAL,
     HYBRID_POSITION,
     HYBRID_PBR,
@@ -43,6 +45,7 @@ from .types import (
     EnvironmentStats,
     HybridFrameStats,
     HybridStats,
+    MarchingCubesStats,
     ShadowmapParams,
     ShadowMapStats,
     FORWARD_DEPTH,
@@ -458,14 +461,17 @@ class Renderer:
         HYBRID_SSAO_IMAGE: (np.uint16, 1),
         HYBRID_DEFERRED_OUTPUT: (np.float32, 4),
         HYBRID_PRESENT_OUTPUT: (np.uint8, 4),
+        HYBRID_DEPTH: (np.float32, 1),
+        HYBRID_MARCHING_CUBES_VISIBILITY: (np.uint32, 1),
     }
 
     def read_hybrid(self, which):
         """one image of the hybrid graph: (H, W, 4) float32 position / normal / pbr / deferred output, (H, W, 4) uint8 albedo / reflections /
-        present output (B, G, R, A), (H, W) uint8 shadows, (H, W) uint16 SSAO"""
+        present output (B, G, R, A), (H, W) uint8 shadows, (H, W) uint16 SSAO, (H, W) float32 marching-cubes depth buffer, (H, W) uint32
+        marching-cubes draw index (MARCHING_CUBES_NONE where none survived)"""
         api = self._hybrid_api()
         if which not in self._HYBRID_IMAGES:
-            raise ValueError(f"hybrid image index {which} (0..8)")
+            raise ValueError(f"hybrid image index {which} (0..10)")
         dtype, ch = self._HYBRID_IMAGES[which]
         out = np.empty((self.height, self.width, ch) if ch > 1 else (self.height, self.width), dtype=dtype)
         self._check(api.read_hybrid(self._ctx, int(which), out.ctypes.data))
@@ -503,6 +509,15 @@ class Renderer:
         api = self._hybrid_api()
         s = HybridFrameStats()
         self._check(api.get_hybrid_frame_stats(self._ctx, C.byref(s)))
+        return s
+
+    def marching_cubes_stats(self):
+        """UhMarchingCubesStats of the last HYBRID_MARCHING_CUBES pass"""
+        self._hybrid_api()
+        fn = getattr(self._lib, "uh_get_marching_cubes_stats")
+        fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(MarchingCubesStats)], C.c_int
+        s = MarchingCubesStats()
+        self._check(fn(self._ctx, C.byref(s)))
         return s
 
     # -- cascaded shadow maps (UH_HYBRID_SHADOW_MAPS; include/utopian_hip.h) ---------------

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "bvh.h"
+#include "context_internal.h"
 #include "device_scan.h"
 #include "device_types.h"
 #include "utopian_hip.h"
@@ -68,10 +69,10 @@ struct DevBuf {
 }  // namespace
 
 // the hybrid graph's stages (uh_ctx::Hybrid::stage): its seven passes in the order of their UH_HYBRID_* bits, then the environment's,
-// then the shadow maps
+// then the shadow maps, then the marching-cubes pass
 enum HybridStage : int {
    kStShadows, kStGbuffer, kStReflections, kStSsao, kStDeferred, kStSky, kStPresent, kHybridPasses,
-   kStEnvCube = kHybridPasses, kStEnvIrradiance, kStEnvSpecular, kStEnvLut, kStShadowMaps, kHybridStages
+   kStEnvCube = kHybridPasses, kStEnvIrradiance, kStEnvSpecular, kStEnvLut, kStShadowMaps, kStMarchingCubes, kHybridStages
 };
 
 // One frame in flight: its own stream pair, hazard events, path state and queue control block.
@@ -370,6 +371,20 @@ struct uh_ctx {
       UhShadowmapParams params{}, snapshot{}, pending{};  // the last uh_set_shadowmap_params; what the maps were rendered with;
                                                           // what the render in progress uses
       uint32_t s_renders = 0, smap_size = 0, s_tris[4] = {0, 0, 0, 0};
+      bool gbuffer_done = false;               // a G-buffer pass has been enqueued (the marching-cubes pass's depth seed reads it)
+      // the marching-cubes pass (UH_HYBRID_MARCHING_CUBES), allocated by the first pass: its depth buffer, visibility, surviving
+      // records, light records, extracted triangles and the forward rasteriser's binning buffers
+      DevBuf<float> mc_depth;
+      DevBuf<uint32_t> mc_vis, mc_rec_of, mc_covered;
+      DevBuf<HybridLight> mc_lights;
+      DevBuf<UhVertex> mc_verts;               // 3 per triangle, extraction order
+      DevBuf<uint32_t> mc_block_counts, mc_tile_count, mc_tile_cursor, mc_rec_count, mc_chunks, mc_entries;
+      DevBuf<unsigned long long> mc_totals;    // the grand totals of the three scans: triangles, records, tile entries
+      DevBuf<uint4> mc_records;
+      DevBuf<float> mc_mats;                   // (P V) I column-major, the identity 3x4, then P V (44 floats)
+      DevBuf<HybridMesh> mc_mesh;              // mesh_index 0's maps with world = identity
+      uint32_t mc_renders = 0, mc_tris = 0, mc_pieces = 0, mc_lights_used = 0;
+      float mc_time = 0.0f;
 
       // the three groups allocated on first use, each named once for allocation and uh_destroy: f(buffer, length), n pixels; a
       // group's last buffer is allocated last, its pointer says "allocated"
@@ -382,6 +397,13 @@ struct uh_ctx {
       template <class F> void shadow_maps(F&& f) {
          f(smaps, 0), f(s_tile_count, 0), f(s_tile_cursor, 0), f(s_rec_count, 0), f(s_tri_mesh, 0), f(s_chunks, 0), f(s_entries, 0),
             f(s_totals, 0), f(s_records, 0), f(s_mats, 0), f(s_params, 0);
+      }
+      template <class F> void mc_images(size_t n, F&& f) {
+         f(mc_depth, n), f(mc_vis, n), f(mc_rec_of, n), f(mc_lights, UH_MAX_GPU_LIGHTS + 1), f(mc_block_counts, kMcBlocks), f(mc_mats, 44),
+            f(mc_mesh, 1), f(mc_totals, 3), f(mc_covered, 1);
+      }
+      template <class F> void mc_bins(F&& f) {
+         f(mc_verts, 0), f(mc_tile_count, 0), f(mc_tile_cursor, 0), f(mc_rec_count, 0), f(mc_chunks, 0), f(mc_entries, 0), f(mc_records, 0);
       }
       template <class F> void env_maps(F&& f) {
          const size_t cube = env_mip_offset(kEnvMips);
@@ -671,6 +693,8 @@ void uh_destroy(uh_ctx* c) {
       h.frame_images(0, release);
       h.env_maps(release);
       h.shadow_maps(release);
+      h.mc_images(0, release);
+      h.mc_bins(release);
       h.meshes.release();
       h.vertices.release();
       h.indices.release();
@@ -2878,6 +2902,113 @@ static int wait_frames_in_flight(uh_ctx* c) {
    return UH_OK;
 }
 
+// ---- the marching-cubes pass (utopian_hip.h "UH_HYBRID_MARCHING_CUBES"; isosurface.hip, forward.hip) ----
+// the column-major product a b, element (r, c) summed ((a(r,0) b(0,c) + a(r,1) b(1,c)) + a(r,2) b(2,c)) + a(r,3) b(3,c): mat4_mul
+static void mat4_mul(const float* a, const float* b, float* o) {
+   for (int col = 0; col < 4; col++)
+      for (int r = 0; r < 4; r++) o[4 * col + r] = ((a[r] * b[4 * col] + a[4 + r] * b[4 * col + 1]) + a[8 + r] * b[4 * col + 2]) + a[12 + r] * b[4 * col + 3];
+}
+
+// extraction (count, scan, emit), depth seed, count, scan, emit, seeded resolve, then forward.frag into deferred_output: the triangle
+// count and the binning totals come back to the host in between (the buffers grow to them)
+static int render_mc_pass(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformData& view) {
+   uh_ctx::Hybrid& h = c->hy;
+   const uint32_t W = c->W, H = c->H, tiles_x = (W + kForwardTile - 1) / kForwardTile, tiles_y = (H + kForwardTile - 1) / kForwardTile;
+   const uint32_t tiles = tiles_x * tiles_y;
+   const auto grow = [&](auto& b, size_t n) -> int {
+      if (b.p && b.n >= n) return UH_OK;
+      const hipError_t e = b.alloc(n);
+      if (e != hipSuccess)
+         return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string("uh_render_hybrid: marching cubes: allocation: ") + hipGetErrorString(e));
+      return UH_OK;
+   };
+   for (int st : {grow(h.mc_tile_count, tiles), grow(h.mc_tile_cursor, tiles), grow(h.mc_chunks, scan_chunk_count(std::max<uint32_t>(kMcBlocks, tiles)))})
+      if (st) return st;
+   // the material of mesh_index 0 under world = identity, and the matrices: (P V) I as forward_mesh_matrices makes it, then P V
+   HybridMesh mm{};
+   for (int k = 0; k < 9; k++) mm.o2w[k] = mm.w2o[k] = k % 4 == 0 ? 1.0f : 0.0f;
+   const UhGpuMaterial& m0 = c->meshes[0].material;
+   mm.diffuse_map = m0.diffuse_map;
+   mm.normal_map = m0.normal_map;
+   mm.metallic_roughness_map = m0.metallic_roughness_map;
+   mm.occlusion_map = m0.occlusion_map;
+   float mats[44], pv[16], ident[16];
+   for (int k = 0; k < 16; k++) ident[k] = k % 5 == 0 ? 1.0f : 0.0f;
+   mat4_mul(view.projection, view.view, pv);
+   mat4_mul(pv, ident, mats);
+   for (int r = 0; r < 3; r++)
+      for (int k = 0; k < 4; k++) mats[16 + 4 * r + k] = r == k ? 1.0f : 0.0f;
+   std::memcpy(mats + 28, pv, sizeof(pv));
+   HIP_TRY(c, hipMemcpyAsync(h.mc_mesh.p, &mm, sizeof(mm), hipMemcpyHostToDevice, c->stream));
+   HIP_TRY(c, hipMemcpyAsync(h.mc_mats.p, mats, sizeof(mats), hipMemcpyHostToDevice, c->stream));
+   HIP_TRY(c, hipMemsetAsync(h.mc_tile_count.p, 0, tiles * sizeof(uint32_t), c->stream));
+   HIP_TRY(c, hipMemsetAsync(h.mc_covered.p, 0, sizeof(uint32_t), c->stream));
+   // marching_cubes.comp at view.time: per-block counts, their scan, then (with the total known) the triangles
+   if (!uhi_mc_extract_count(c->stream, view.time, h.mc_block_counts.p)) return fail(c, UH_ERR_HIP, "uh_render_hybrid: marching-cubes tables");
+   device_exclusive_scan_u32(h.mc_block_counts.p, kMcBlocks, h.mc_chunks.p, h.mc_totals.p, c->stream);
+   ForwardDev fd{};
+   fd.meshes = h.mc_mesh.p;
+   fd.mats = h.mc_mats.p;
+   fd.W = W;
+   fd.H = H;
+   fd.tiles_x = tiles_x;
+   fd.tiles_y = tiles_y;
+   fd.tile_count = h.mc_tile_count.p;
+   fd.tile_cursor = h.mc_tile_cursor.p;
+   fd.depth = h.mc_depth.p;
+   fd.vis = h.mc_vis.p;
+   fd.rec_of = h.mc_rec_of.p;
+   fd.color = h.deferred.p;
+   fd.covered = h.mc_covered.p;
+   launch_mc_depth_seed(lc, h.pos.p, fd);
+   unsigned long long ntri = 0;
+   HIP_TRY(c, hipStreamSynchronize(c->stream));
+   HIP_TRY(c, hipMemcpy(&ntri, h.mc_totals.p, sizeof(ntri), hipMemcpyDeviceToHost));
+   if (ntri > 5ull * kMcRes * kMcRes * kMcRes) return fail(c, UH_ERR_HIP, "uh_render_hybrid: marching-cubes triangle count out of range");
+   for (int st : {grow(h.mc_verts, std::max<size_t>(3, 3 * (size_t)ntri)), grow(h.mc_rec_count, std::max<size_t>(1, (size_t)ntri)),
+                  grow(h.mc_chunks, scan_chunk_count(std::max<uint32_t>((uint32_t)ntri, tiles)))})
+      if (st) return st;
+   if (ntri && !uhi_mc_extract_emit(c->stream, view.time, h.mc_block_counts.p, h.mc_verts.p)) return fail(c, UH_ERR_HIP, "uh_render_hybrid: marching-cubes tables");
+   fd.vertices = h.mc_verts.p;
+   fd.num_tris = (uint32_t)ntri;
+   fd.rec_count = h.mc_rec_count.p;
+   launch_forward_count(lc, fd, true);
+   unsigned long long totals[2] = {0, 0};
+   if (ntri) device_exclusive_scan_u32(h.mc_rec_count.p, (uint32_t)ntri, h.mc_chunks.p, h.mc_totals.p + 1, c->stream);
+   device_exclusive_scan_u32(h.mc_tile_count.p, tiles, h.mc_chunks.p, h.mc_totals.p + 2, c->stream);
+   HIP_TRY(c, hipMemcpyAsync(h.mc_tile_cursor.p, h.mc_tile_count.p, tiles * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+   HIP_TRY(c, hipStreamSynchronize(c->stream));
+   HIP_TRY(c, hipMemcpy(totals + 1, h.mc_totals.p + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+   if (ntri) HIP_TRY(c, hipMemcpy(totals, h.mc_totals.p + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+   if (totals[0] >= (1ull << 32) - 1 || totals[1] >= (1ull << 32))
+      return fail(c, UH_ERR_CAPACITY, "uh_render_hybrid: marching cubes: 2^32 - 1 or more triangle pieces, or 2^32 or more tile entries");
+   for (int st : {grow(h.mc_records, std::max<size_t>(1, 6 * (size_t)totals[0])), grow(h.mc_entries, std::max<size_t>(1, (size_t)totals[1]))})
+      if (st) return st;
+   fd.records = h.mc_records.p;
+   fd.entries = h.mc_entries.p;
+   launch_forward_emit(lc, fd, true);
+   launch_forward_resolve(lc, fd, true);
+   HybridFrameDev lp{};  // k_hybrid_light_prep's inputs, into the pass's own records
+   lp.lights = h.mc_lights.p;
+   lp.raw_lights = h.raw_lights.p;
+   lp.num_lights = view.num_lights;
+   for (int a = 0; a < 3; a++) lp.sun_raw[a] = view.sun_dir[a];
+   launch_hybrid_light_prep(lc, lp);
+   ForwardShade fs{};
+   fs.lights = h.mc_lights.p;
+   fs.count = view.num_lights + 1;
+   for (int a = 0; a < 3; a++) fs.eye[a] = view.eye_pos[a];
+   std::memcpy(fs.view, view.view, sizeof(fs.view));
+   const ShadowLookup sl{h.smaps.p, h.s_params.p, h.smap_size};
+   launch_forward_shade(lc, c->scene, fd, fs, view.shadows_enabled == 1 ? &sl : nullptr, true);
+   h.mc_tris = (uint32_t)ntri;
+   h.mc_pieces = (uint32_t)totals[0];
+   h.mc_lights_used = view.num_lights + 1;
+   h.mc_time = view.time;
+   h.mc_renders++;
+   return UH_OK;
+}
+
 int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    if (!view) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_render_hybrid: null view");
@@ -2908,6 +3039,22 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
       return fail(c, UH_ERR_INVALID_ARGUMENT,
                   "uh_render_hybrid: the sky pass with view.cubemap_enabled = 1 needs the environment cube (ibl.rs), which a call with "
                   "UH_HYBRID_ENVIRONMENT builds; set that bit, or cubemap_enabled = 0 for the IntegrateScattering branch");
+   // setup_marching_cubes_pass (mod.rs:164): only with the checkbox on
+   const bool mc = (mask & UH_HYBRID_MARCHING_CUBES) && view->marching_cubes_enabled == 1;
+   if (mc) {
+      if (!(mask & UH_HYBRID_GBUFFER) && !c->hy.gbuffer_done)
+         return fail(c, UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: the marching-cubes pass depth-tests against the G-buffer's depth, and no G-buffer has been rendered; "
+                     "set UH_HYBRID_GBUFFER, or marching_cubes_enabled = 0");
+      if (c->meshes.empty())
+         return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_render_hybrid: the marching-cubes pass shades with the first mesh's material (mesh_index 0), and the scene has no mesh");
+      if (view->shadows_enabled == 1 && !c->hy.smap_size && !render_maps)
+         return fail(c, UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: the marching-cubes pass with view.shadows_enabled = 1 needs the cascaded shadow maps (shadow.rs), which a "
+                     "call with UH_HYBRID_SHADOW_MAPS renders; set that bit, or shadows_enabled = 0");
+      if (view->num_lights > c->lights.size())
+         return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_render_hybrid: the marching-cubes pass: view.num_lights exceeds the lights added with uh_add_light");
+   }
    if (!c->built && c->topology_valid && view->rebuild_tlas == 1)
       if (int st = uh_refit_acceleration(c)) return st;
    if (!c->built) return fail(c, UH_ERR_NOT_BUILT, "uh_render_hybrid before uh_build_acceleration");
@@ -2917,12 +3064,14 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    if (int st = hybrid_alloc(c)) return st;
    if (int st = hybrid_tables(c)) return st;
    const uint32_t frame_bits = UH_HYBRID_SSAO | UH_HYBRID_DEFERRED | UH_HYBRID_SKY | UH_HYBRID_PRESENT;
-   const bool frame_first = (mask & frame_bits) && !h.sky_counter.p;
-   if (mask & frame_bits) {
+   const bool frame_first = ((mask & frame_bits) || mc) && !h.sky_counter.p;
+   if ((mask & frame_bits) || mc) {
       if (int st = hybrid_frame_alloc(c)) return st;
-      if (mask & UH_HYBRID_DEFERRED)
+      if ((mask & UH_HYBRID_DEFERRED) || mc)
          if (int st = hybrid_light_table(c)) return st;
    }
+   if (mc && !h.mc_covered.p)
+      if (int st = alloc_group(c, [&](auto f) { h.mc_images((size_t)c->W * c->H, f); })) return st;
    if (mask & UH_HYBRID_ENVIRONMENT)
       if (int st = env_alloc(c)) return st;
    const FrameParams fp = make_params(c, *view);
@@ -2976,6 +3125,7 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    if ((mask & (UH_HYBRID_FRAME | UH_HYBRID_ENVIRONMENT | UH_HYBRID_SHADOW_MAPS)) != UH_HYBRID_SHADOW_MAPS)
       for (int k = 0; k < kHybridPasses; k++) h.stage[k].ran = false;
    if (mask & UH_HYBRID_SHADOW_MAPS) h.stage[kStShadowMaps].ran = false;
+   if (mask & UH_HYBRID_MARCHING_CUBES) h.stage[kStMarchingCubes].ran = false;
    const auto begin = [&](int k) {
       h.stage[k].ran = true;
       h.stage[k].timed = false;
@@ -3001,6 +3151,7 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
       HIP_TRY(c, begin(kStGbuffer));
       launch_hybrid_gbuffer(lc, fp, c->scene, hd, grid ? &c->cam_dev : nullptr);
       HIP_TRY(c, end(kStGbuffer));
+      h.gbuffer_done = true;
    }
    // setup_cubemap_pass (mod.rs:121): after the G-buffer, before rt_reflections; the maps persist until the next build
    const IblMaps ibl{h.env.p, h.irr.p, h.spec.p, h.lut.p};
@@ -3039,10 +3190,19 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
       HIP_TRY(c, end(kStDeferred));
    }
    h.frame_lights = h.stage[kStDeferred].ran ? view->num_lights + 1 : 0;
+   // setup_marching_cubes_pass (mod.rs:164-174): after the deferred pass, before the atmosphere pass
+   if (mc) {
+      HIP_TRY(c, begin(kStMarchingCubes));
+      if (int st = render_mc_pass(c, lc, *view)) {
+         h.stage[kStMarchingCubes].ran = false;  // no time for a pass that did not complete
+         return st;
+      }
+      HIP_TRY(c, end(kStMarchingCubes));
+   }
    if (mask & UH_HYBRID_SKY) {
       HIP_TRY(c, begin(kStSky));
       HIP_TRY(c, hipMemsetAsync(h.sky_counter.p, 0, sizeof(uint32_t), c->stream));
-      launch_hybrid_sky(lc, fp, hd, fd, view->cubemap_enabled == 1 ? &ibl : nullptr);
+      launch_hybrid_sky(lc, fp, hd, fd, view->cubemap_enabled == 1 ? &ibl : nullptr, mc ? h.mc_vis.p : nullptr);
       HIP_TRY(c, end(kStSky));
    }
    if (mask & UH_HYBRID_PRESENT) {
@@ -3058,13 +3218,16 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    const uh_ctx::Hybrid& h = c->hy;
    if (!h.counter.p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid before the first uh_render_hybrid");
-   if (which < 0 || which > UH_HYBRID_PRESENT_OUTPUT) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..8");
-   if (which >= UH_HYBRID_SSAO_IMAGE && !h.sky_counter.p)
+   if (which < 0 || which > UH_HYBRID_MARCHING_CUBES_VISIBILITY) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..10");
+   if (which >= UH_HYBRID_SSAO_IMAGE && which <= UH_HYBRID_PRESENT_OUTPUT && !h.sky_counter.p)
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 6..8 before the first call with an SSAO, deferred, sky or present bit");
+   if (which >= UH_HYBRID_DEPTH && h.mc_renders == 0)
+      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 9..10 before the first marching-cubes pass");
    // image k's pixels and its bytes per pixel, in UH_HYBRID_* image order
    const std::pair<const void*, size_t> img[] = {
       {h.pos.p, sizeof(float4)}, {h.nrm.p, sizeof(float4)}, {h.alb.p, sizeof(uchar4)}, {h.pbr.p, sizeof(float4)}, {h.shadow.p, 1},
-      {h.refl.p, sizeof(uchar4)}, {h.ssao.p, sizeof(uint16_t)}, {h.deferred.p, sizeof(float4)}, {h.present.p, sizeof(uchar4)}};
+      {h.refl.p, sizeof(uchar4)}, {h.ssao.p, sizeof(uint16_t)}, {h.deferred.p, sizeof(float4)}, {h.present.p, sizeof(uchar4)},
+      {h.mc_depth.p, sizeof(float)}, {h.mc_vis.p, sizeof(uint32_t)}};
    return read_back(c, out, img[which].first, (size_t)c->W * c->H * img[which].second);
 }
 
@@ -3093,6 +3256,24 @@ int uh_get_hybrid_frame_stats(uh_ctx* c, UhHybridFrameStats* out) {
       if (int st = stage_ms(c, k, &out->pass_ms[k])) return st;
    if (h.stage[kStSky].ran) HIP_TRY(c, hipMemcpy(&out->sky_pixels, h.sky_counter.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
    out->lights = h.frame_lights;
+   return UH_OK;
+}
+
+int uh_get_marching_cubes_stats(uh_ctx* c, UhMarchingCubesStats* out) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_marching_cubes_stats: null destination");
+   std::memset(out, 0, sizeof(*out));
+   const uh_ctx::Hybrid& h = c->hy;
+   if (h.mc_renders == 0) return UH_OK;
+   HIP_TRY(c, hipSetDevice(c->device));
+   if (int st = sync_all(c)) return st;
+   if (int st = stage_ms(c, kStMarchingCubes, &out->pass_ms)) return st;
+   out->renders = h.mc_renders;
+   out->triangles = h.mc_tris;
+   out->pieces = h.mc_pieces;
+   HIP_TRY(c, hipMemcpy(&out->covered_pixels, h.mc_covered.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+   out->lights = h.mc_lights_used;
+   out->time = h.mc_time;
    return UH_OK;
 }
 

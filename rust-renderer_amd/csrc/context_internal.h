@@ -26,3 +26,11 @@ int uhi_enqueue_pack_tiles(uh_ctx*, void* device_out, void** out_stream);
 int uhi_enqueue_compose_tiles(uh_ctx*, const void* device_all, uint64_t stride_pixels, uint32_t total_samples, uint32_t accumulation_limit, void* const* wait_events, int n_waits);
 void* uhi_composed_event(uh_ctx*);  // hipEvent_t behind the context's last pack / composition (null before the first)
 }
+// the hybrid graph's marching-cubes pass (isosurface.hip): the reference's grid (marching_cubes.rs:17-45, kMcRes^3 cells of size 1 from
+// the origin) at `time`, reference triangulation, enqueued on `stream` (hipStream_t). Count writes the triangles of each block of 256
+// cells, x fastest (kMcBlocks of them); emit writes vertex 3 t + k of triangle t at block_offsets[block] (their exclusive scan) plus
+// the block's prefix: pos and normal those of uh_add_isosurface_mesh(ctx, kMcRes, 0, kMcRes, time, ...), uv, colour and tangent zero.
+// false when the case tables could not be loaded.
+constexpr uint32_t kMcRes = 32, kMcBlocks = kMcRes * kMcRes * kMcRes / 256;
+bool uhi_mc_extract_count(void* stream, float time, uint32_t* block_counts);
+bool uhi_mc_extract_emit(void* stream, float time, const uint32_t* block_offsets, UhVertex* verts);

@@ -347,7 +347,9 @@ struct ShadowDev {
 void launch_shadow_count(const LaunchCfg&, const ShadowDev&);
 void launch_shadow_emit(const LaunchCfg&, const ShadowDev&);
 void launch_shadow_resolve(const LaunchCfg&, const ShadowDev&);
-void launch_hybrid_sky(const LaunchCfg&, const FrameParams&, const HybridDev&, const HybridFrameDev&, const IblMaps* cube);
+// skip: when not null, a pixel p with skip[p] != 0xFFFFFFFF is not sky (the marching-cubes pass's visibility: the atmosphere pass's
+// depth test against the fragments it drew)
+void launch_hybrid_sky(const LaunchCfg&, const FrameParams&, const HybridDev&, const HybridFrameDev&, const IblMaps* cube, const uint32_t* skip = nullptr);
 // the forward pass's rasteriser (forward.hip): setup per triangle, binning into kForwardTile^2 tiles, a visibility buffer resolved per
 // tile in LDS (the 64-bit min of depth bits << 32 | ~record), then one shading lane per pixel
 constexpr uint32_t kForwardTile = 64;
@@ -356,7 +358,8 @@ struct ForwardDev {
    const uint32_t* indices;
    const HybridMesh* meshes;
    const uint32_t* tri_mesh;
-   const float* mats;           // [mesh][28]: (P V) W column-major (16), then the instance's 3x4 row-major (12)
+   const float* mats;           // [mesh][28]: (P V) W column-major (16), then the instance's 3x4 row-major (12); the marching-cubes
+                                // pass: mesh 0 with W the identity, then P V (16) for its depth seed
    uint32_t num_tris, W, H, tiles_x, tiles_y;
    uint32_t* rec_count;         // [t]: the records of triangle t; scanned in place into record offsets (so records follow draw order)
    uint32_t* tile_count;        // [tile]: entries per tile; scanned in place into the tiles' first entries
@@ -376,10 +379,14 @@ struct ForwardShade {           // what forward.frag reads besides the scene and
    float view[16];              // view.view (calculateShadow's cascade choice)
 };
 void launch_forward_clear(const LaunchCfg&, const ForwardDev&, uchar4* present);
-void launch_forward_count(const LaunchCfg&, const ForwardDev&);
-void launch_forward_emit(const LaunchCfg&, const ForwardDev&);
-void launch_forward_resolve(const LaunchCfg&, const ForwardDev&);
-void launch_forward_shade(const LaunchCfg&, const SceneDev&, const ForwardDev&, const ForwardShade&, const ShadowLookup* shadow);
+// flat: the marching-cubes pass's triangle source (vertex 3 t + k of triangle t, mesh 0 of `meshes` and `mats`; shading leaves the
+// pixels it does not cover untouched); seeded: the resolve starts from the depths in `depth` and loses ties
+void launch_forward_count(const LaunchCfg&, const ForwardDev&, bool flat = false);
+void launch_forward_emit(const LaunchCfg&, const ForwardDev&, bool flat = false);
+void launch_forward_resolve(const LaunchCfg&, const ForwardDev&, bool seeded = false);
+void launch_forward_shade(const LaunchCfg&, const SceneDev&, const ForwardDev&, const ForwardShade&, const ShadowLookup* shadow, bool flat = false);
+// the marching-cubes pass's depth buffer from the G-buffer positions, into fd.depth; P V column-major at fd.mats + 28
+void launch_mc_depth_seed(const LaunchCfg&, const float4* gbuffer_pos, const ForwardDev&);
 void launch_hybrid_light_prep(const LaunchCfg&, const HybridFrameDev&);
 // tiles
 // on-device refit (refit.hip): per-mesh object->world rows, and what one refit pass touches

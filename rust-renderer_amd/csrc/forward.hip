@@ -5,11 +5,14 @@
 //                      raster_device.h's guard-band clip, snap and rejects; counts its records and, per tile its box touches, one entry
 //   (device_scan.h)    record offsets (in draw order) and the tiles' first entries
 //   k_forward_emit     the same setup again: writes the records and scatters their ids into the tiles' lists
-//   k_forward_resolve  one block per tile: the 64-bit min of depth_bits << 32 | ~record per pixel in LDS (ds_min_u64) - the last record
-//                      in draw order among those of minimum depth - then depth, draw index and record written out once
+//   k_forward_resolve  one block per tile: the 64-bit min of depth_bits << 32 | (0xFFFFFFFE - record) per pixel in LDS (ds_min_u64) -
+//                      the last record in draw order among those of minimum depth - then depth, draw index and record written out once
 //   k_forward_shade    one lane per pixel: the surviving record's perspective-correct barycentrics, forward.vert's attributes and
 //                      forward.frag (surfaceShading over the sun and the lights, ambient, calculateShadow)
-// Every step is exact and pinned: DESIGN.md section 2, "Forward pass".
+// The kernels are templates on the triangle source and the depth seed. The forward pass draws the scene's meshes (kFlat = false) into
+// a depth buffer cleared to 1.0; the hybrid graph's marching-cubes pass draws a flat list of world-space triangles (vertex 3 t + k of
+// triangle t, one mesh of its own) against a depth buffer seeded from the G-buffer (kSeed), shading only the pixels it covers.
+// Every step is exact and pinned: DESIGN.md section 2, "Forward pass" and "Marching-cubes pass".
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -28,6 +31,13 @@ constexpr int kSetupBlock = 256, kResolveBlock = 256, kShadeBlock = 256;
 constexpr int kSmallPixels = 16;                   // a piece whose box in the tile has at most this many pixels is drawn by one lane
 constexpr unsigned long long kEmptyKey = ~0ull;    // no fragment: depth 1.0, no visibility
 constexpr uint32_t kNone = 0xFFFFFFFFu;
+// a key's low word: 0xFFFFFFFE - record (records stay below 0xFFFFFFFF), so the last record in draw order has the smallest, and
+// 0xFFFFFFFF is left for no fragment - a seeded depth loses every tie with a fragment
+__device__ __forceinline__ uint32_t key_low(uint32_t r) { return 0xFFFFFFFEu - r; }
+__device__ __forceinline__ uint32_t key_record(unsigned long long key) {
+   const uint32_t lo = (uint32_t)key;
+   return lo == kNone ? kNone : 0xFFFFFFFEu - lo;
+}
 
 // a clip-space vertex and its barycentrics with respect to the original triangle
 struct HVert {
@@ -82,15 +92,23 @@ __device__ __forceinline__ int clip_depth(HVert* v, int n) {
 
 // triangle t through forward.vert's gl_Position and the fixed-function stages: emit(k, SubTri, piece) for each piece that reaches the
 // rasteriser, piece[0..2] its three screen-space vertices in SubTri order before the winding swap
-template <class Emit>
+// the vertex k of triangle t and its mesh: the scene's tables, or (kFlat) vertex 3 t + k of mesh 0
+template <bool kFlat>
+__device__ __forceinline__ uint32_t mesh_of(const ForwardDev& fd, uint32_t t) { return kFlat ? 0u : fd.tri_mesh[t]; }
+template <bool kFlat>
+__device__ __forceinline__ const UhVertex& vertex_of(const ForwardDev& fd, uint32_t vertex_base, uint32_t t, int k) {
+   return kFlat ? fd.vertices[3 * (size_t)t + k] : fd.vertices[vertex_base + fd.indices[3 * (size_t)t + k]];
+}
+
+template <bool kFlat, class Emit>
 __device__ __forceinline__ void setup(const ForwardDev& fd, uint32_t t, Emit&& emit) {
-   const uint32_t mesh = fd.tri_mesh[t];
+   const uint32_t mesh = mesh_of<kFlat>(fd, t);
    const float* M = fd.mats + (size_t)mesh * 28;
-   const uint32_t vb = fd.meshes[mesh].vertex_base;
+   const uint32_t vb = kFlat ? 0u : fd.meshes[mesh].vertex_base;
    HVert v[5];
    bool finite = true;
    for (int k = 0; k < 3; k++) {
-      const UhVertex& vx = fd.vertices[vb + fd.indices[3 * (size_t)t + k]];
+      const UhVertex& vx = vertex_of<kFlat>(fd, vb, t, k);
       const float px = vx.pos[0], py = vx.pos[1], pz = vx.pos[2];
       // gl_Position = ((P V) W) (p, 1), mat4_mul's column order
       v[k].x = ((M[0] * px + M[4] * py) + M[8] * pz) + M[12] * 1.0f;
@@ -123,10 +141,11 @@ __device__ __forceinline__ void for_tiles(const SubTri& st, uint32_t tiles_x, F&
       for (int tx = st.x0 / (int)kForwardTile; tx <= st.x1 / (int)kForwardTile; tx++) f((uint32_t)ty * tiles_x + (uint32_t)tx);
 }
 
+template <bool kFlat>
 __global__ __launch_bounds__(kSetupBlock) void k_forward_count(ForwardDev fd) {
    for (uint32_t t = blockIdx.x * kSetupBlock + threadIdx.x; t < fd.num_tris; t += gridDim.x * kSetupBlock) {
       uint32_t count = 0;
-      setup(fd, t, [&](int, const SubTri& st, const FVert* const*) {
+      setup<kFlat>(fd, t, [&](int, const SubTri& st, const FVert* const*) {
          count++;
          for_tiles(st, fd.tiles_x, [&](uint32_t tile) { atomicAdd(&fd.tile_count[tile], 1u); });
       });
@@ -136,10 +155,11 @@ __global__ __launch_bounds__(kSetupBlock) void k_forward_count(ForwardDev fd) {
 
 // record r, 6 uint4: (X0, Y0, X1, Y1) (X2, Y2, z0, z1) (z2, x0 | x1 << 16, y0 | y1 << 16, draw) (w0, w1, w2, b00) (b01, b02, b10, b11)
 // (b12, b20, b21, b22), vertex order after the winding swap; the first three are the shadow maps' record with the draw index added
+template <bool kFlat>
 __global__ __launch_bounds__(kSetupBlock) void k_forward_emit(ForwardDev fd) {
    for (uint32_t t = blockIdx.x * kSetupBlock + threadIdx.x; t < fd.num_tris; t += gridDim.x * kSetupBlock) {
       const uint32_t first = fd.rec_count[t];
-      setup(fd, t, [&](int k, const SubTri& st, const FVert* const* piece) {
+      setup<kFlat>(fd, t, [&](int k, const SubTri& st, const FVert* const* piece) {
          const uint32_t r = first + (uint32_t)k;
          const FVert* p[3] = {piece[0], st.swapped ? piece[2] : piece[1], st.swapped ? piece[1] : piece[2]};
          uint4* q = fd.records + 6 * (size_t)r;
@@ -175,9 +195,12 @@ __device__ __forceinline__ void raster_pixel(const Rec& q, uint32_t r, int px, i
    const float z = raster::depth_at(q.e, q.z0, q.z1, q.z2, e1, e2);
    if (!(z >= 0.0f && z <= 1.0f)) return;
    const uint32_t bits = z == 0.0f ? 0u : __float_as_uint(z);
-   atomicMin(&keys[(py - oy) * (int)kForwardTile + (px - ox)], ((unsigned long long)bits << 32) | (unsigned long long)(~r));
+   atomicMin(&keys[(py - oy) * (int)kForwardTile + (px - ox)], ((unsigned long long)bits << 32) | (unsigned long long)key_low(r));
 }
 
+// kSeed: every pixel's key starts at seed_bits << 32 | 0xFFFFFFFF (fd.depth holds the seed and receives the result), so a fragment
+// survives when its depth is at most the seed's (LESS_OR_EQUAL against the seeded depth buffer)
+template <bool kSeed>
 __global__ __launch_bounds__(kResolveBlock) void k_forward_resolve(ForwardDev fd) {
    __shared__ unsigned long long s_key[kForwardTile * kForwardTile];  // 32 KiB
    __shared__ uint32_t s_big[kResolveBlock];
@@ -185,7 +208,14 @@ __global__ __launch_bounds__(kResolveBlock) void k_forward_resolve(ForwardDev fd
    const uint32_t tile = blockIdx.x;
    const int ox = (int)((tile % fd.tiles_x) * kForwardTile), oy = (int)((tile / fd.tiles_x) * kForwardTile);
    const int W = (int)fd.W, tw = min((int)kForwardTile, W - ox), th = min((int)kForwardTile, (int)fd.H - oy);
-   for (uint32_t i = threadIdx.x; i < kForwardTile * kForwardTile; i += kResolveBlock) s_key[i] = kEmptyKey;
+   for (uint32_t i = threadIdx.x; i < kForwardTile * kForwardTile; i += kResolveBlock) {
+      unsigned long long key = kEmptyKey;
+      if (kSeed) {
+         const int ly = (int)(i / kForwardTile), lx = (int)(i % kForwardTile);
+         if (lx < tw && ly < th) key = ((unsigned long long)__float_as_uint(fd.depth[(size_t)(oy + ly) * W + ox + lx]) << 32) | kNone;
+      }
+      s_key[i] = key;
+   }
    if (threadIdx.x == 0) s_nbig = 0, s_covered = 0;
    __syncthreads();
    const uint32_t begin = fd.tile_count[tile], end = fd.tile_cursor[tile];
@@ -219,8 +249,8 @@ __global__ __launch_bounds__(kResolveBlock) void k_forward_resolve(ForwardDev fd
       const int ly = i / tw, lx = i - ly * tw;
       const unsigned long long key = s_key[ly * (int)kForwardTile + lx];
       const size_t pix = (size_t)(oy + ly) * W + ox + lx;
-      const uint32_t r = key == kEmptyKey ? kNone : ~(uint32_t)key;
-      fd.depth[pix] = key == kEmptyKey ? 1.0f : __uint_as_float((uint32_t)(key >> 32));
+      const uint32_t r = key_record(key);
+      fd.depth[pix] = !kSeed && r == kNone ? 1.0f : __uint_as_float((uint32_t)(key >> 32));
       fd.rec_of[pix] = r;
       fd.vis[pix] = r == kNone ? kNone : fd.records[6 * (size_t)r + 2].w;
       if (r != kNone) atomicAdd(&s_covered, 1u);
@@ -231,14 +261,15 @@ __global__ __launch_bounds__(kResolveBlock) void k_forward_resolve(ForwardDev fd
 
 // forward.frag at pixel i: the surviving record's integer edge functions give the screen weights l_k = e_k / area; q_k = l_k / w_k and
 // b = (q0 B0 + q1 B1 + q2 B2) / (q0 + q1 + q2) are the original triangle's barycentrics; every attribute is (a0 b0 + a1 b1) + a2 b2.
-// One lane per pixel, no grid-stride loop (the light records become scalar loads, as in k_hybrid_deferred).
-template <bool kShadow>
+// One lane per pixel, no grid-stride loop (the light records become scalar loads, as in k_hybrid_deferred). kFlat (the marching-cubes
+// pass): the material is fd.meshes[0]'s and the base colour scene mesh 0's (mesh_index = 0), and an uncovered pixel keeps its colour.
+template <bool kFlat, bool kShadow>
 __global__ __launch_bounds__(kShadeBlock) void k_forward_shade(SceneDev sc, ForwardDev fd, ForwardShade fs, ShadowLookup sl) {
    const uint32_t n = fd.W * fd.H, i = blockIdx.x * kShadeBlock + threadIdx.x;
    if (i >= n) return;
    const uint32_t r = fd.rec_of[i];
-   if (r == kNone) {  // the clear colour (pass.rs: (1, 1, 1, 0))
-      fd.color[i] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+   if (r == kNone) {  // the clear colour (pass.rs: (1, 1, 1, 0)); load_write: untouched
+      if (!kFlat) fd.color[i] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
       return;
    }
    const uint4* q = fd.records + 6 * (size_t)r;
@@ -255,11 +286,11 @@ __global__ __launch_bounds__(kShadeBlock) void k_forward_shade(SceneDev sc, Forw
    const float b0 = ((q0 * B[0][0] + q1 * B[1][0]) + q2 * B[2][0]) / s;
    const float b1 = ((q0 * B[0][1] + q1 * B[1][1]) + q2 * B[2][1]) / s;
    const float b2 = ((q0 * B[0][2] + q1 * B[1][2]) + q2 * B[2][2]) / s;
-   const uint32_t t = c.w, mesh = fd.tri_mesh[t];
+   const uint32_t t = c.w, mesh = mesh_of<kFlat>(fd, t);
    const HybridMesh m = fd.meshes[mesh];
-   const UhVertex& v0 = fd.vertices[m.vertex_base + fd.indices[3 * (size_t)t]];
-   const UhVertex& v1 = fd.vertices[m.vertex_base + fd.indices[3 * (size_t)t + 1]];
-   const UhVertex& v2 = fd.vertices[m.vertex_base + fd.indices[3 * (size_t)t + 2]];
+   const UhVertex& v0 = vertex_of<kFlat>(fd, m.vertex_base, t, 0);
+   const UhVertex& v1 = vertex_of<kFlat>(fd, m.vertex_base, t, 1);
+   const UhVertex& v2 = vertex_of<kFlat>(fd, m.vertex_base, t, 2);
    const float* o = fd.mats + (size_t)mesh * 28 + 16;  // out_pos = (world (p, 1)).xyz, world row-major 3x4
    auto world = [&](const UhVertex& v) {
       return v3(((o[0] * v.pos[0] + o[1] * v.pos[1]) + o[2] * v.pos[2]) + o[3] * 1.0f, ((o[4] * v.pos[0] + o[5] * v.pos[1]) + o[6] * v.pos[2]) + o[7] * 1.0f,
@@ -301,26 +332,64 @@ inline dim3 setup_grid(const LaunchCfg& c, uint32_t n) {
    const uint32_t blocks = (n + kSetupBlock - 1) / kSetupBlock, cap = c.num_cus * 8;
    return dim3(blocks < cap ? (blocks ? blocks : 1) : cap);
 }
+// the marching-cubes pass's depth seed ("Marching-cubes pass"): one lane per pixel, c = (P V) (p, 1) of the
+// G-buffer position, d = c.z / c.w kept when c.w > 0 and 0 <= d <= 1 (-0 as +0), 1.0 otherwise and where the cast missed
+__global__ __launch_bounds__(kShadeBlock) void k_mc_depth_seed(const float4* __restrict__ pos, ForwardDev fd) {
+   const uint32_t n = fd.W * fd.H, i = blockIdx.x * kShadeBlock + threadIdx.x;
+   if (i >= n) return;
+   const float4 p = pos[i];
+   const float* M = fd.mats + 28;  // P V, column-major
+   float d = 1.0f;
+   if (p.w != 0.0f) {
+      const float cz = ((M[2] * p.x + M[6] * p.y) + M[10] * p.z) + M[14];
+      const float cw = ((M[3] * p.x + M[7] * p.y) + M[11] * p.z) + M[15];
+      const float q = cz / cw;
+      if (cw > 0.0f && q >= 0.0f && q <= 1.0f) d = q == 0.0f ? 0.0f : q;
+   }
+   fd.depth[i] = d;
+}
 }  // namespace
 
 void launch_forward_clear(const LaunchCfg& c, const ForwardDev& fd, uchar4* present) {
    k_forward_clear<<<setup_grid(c, fd.W * fd.H), kShadeBlock, 0, c.stream>>>(fd, present);
 }
-void launch_forward_count(const LaunchCfg& c, const ForwardDev& fd) {
-   if (fd.num_tris) k_forward_count<<<setup_grid(c, fd.num_tris), kSetupBlock, 0, c.stream>>>(fd);
-}
-void launch_forward_emit(const LaunchCfg& c, const ForwardDev& fd) {
-   if (fd.num_tris) k_forward_emit<<<setup_grid(c, fd.num_tris), kSetupBlock, 0, c.stream>>>(fd);
-}
-void launch_forward_resolve(const LaunchCfg& c, const ForwardDev& fd) {
-   k_forward_resolve<<<dim3(fd.tiles_x * fd.tiles_y), kResolveBlock, 0, c.stream>>>(fd);
-}
-void launch_forward_shade(const LaunchCfg& c, const SceneDev& sc, const ForwardDev& fd, const ForwardShade& fs, const ShadowLookup* shadow) {
-   const dim3 grid((fd.W * fd.H + kShadeBlock - 1) / kShadeBlock);
-   if (shadow)
-      k_forward_shade<true><<<grid, kShadeBlock, 0, c.stream>>>(sc, fd, fs, *shadow);
+void launch_forward_count(const LaunchCfg& c, const ForwardDev& fd, bool flat) {
+   if (!fd.num_tris) return;
+   if (flat)
+      k_forward_count<true><<<setup_grid(c, fd.num_tris), kSetupBlock, 0, c.stream>>>(fd);
    else
-      k_forward_shade<false><<<grid, kShadeBlock, 0, c.stream>>>(sc, fd, fs, ShadowLookup{});
+      k_forward_count<false><<<setup_grid(c, fd.num_tris), kSetupBlock, 0, c.stream>>>(fd);
+}
+void launch_forward_emit(const LaunchCfg& c, const ForwardDev& fd, bool flat) {
+   if (!fd.num_tris) return;
+   if (flat)
+      k_forward_emit<true><<<setup_grid(c, fd.num_tris), kSetupBlock, 0, c.stream>>>(fd);
+   else
+      k_forward_emit<false><<<setup_grid(c, fd.num_tris), kSetupBlock, 0, c.stream>>>(fd);
+}
+void launch_forward_resolve(const LaunchCfg& c, const ForwardDev& fd, bool seeded) {
+   if (seeded)
+      k_forward_resolve<true><<<dim3(fd.tiles_x * fd.tiles_y), kResolveBlock, 0, c.stream>>>(fd);
+   else
+      k_forward_resolve<false><<<dim3(fd.tiles_x * fd.tiles_y), kResolveBlock, 0, c.stream>>>(fd);
+}
+void launch_forward_shade(const LaunchCfg& c, const SceneDev& sc, const ForwardDev& fd, const ForwardShade& fs, const ShadowLookup* shadow, bool flat) {
+   const dim3 grid((fd.W * fd.H + kShadeBlock - 1) / kShadeBlock);
+   const ShadowLookup sl = shadow ? *shadow : ShadowLookup{};
+   if (flat) {
+      if (shadow)
+         k_forward_shade<true, true><<<grid, kShadeBlock, 0, c.stream>>>(sc, fd, fs, sl);
+      else
+         k_forward_shade<true, false><<<grid, kShadeBlock, 0, c.stream>>>(sc, fd, fs, sl);
+   } else {
+      if (shadow)
+         k_forward_shade<false, true><<<grid, kShadeBlock, 0, c.stream>>>(sc, fd, fs, sl);
+      else
+         k_forward_shade<false, false><<<grid, kShadeBlock, 0, c.stream>>>(sc, fd, fs, sl);
+   }
+}
+void launch_mc_depth_seed(const LaunchCfg& c, const float4* gbuffer_pos, const ForwardDev& fd) {
+   k_mc_depth_seed<<<dim3((fd.W * fd.H + kShadeBlock - 1) / kShadeBlock), kShadeBlock, 0, c.stream>>>(gbuffer_pos, fd);
 }
 
 }  // namespace uh

@@ -44,6 +44,7 @@ struct IsoParams {
    float sphere_r;      // 8 |sin(0.3 t)|
    float inv_domain;    // uv = pos.xz * inv_domain
    uint32_t reference;  // 1: the reference's triangle table, corner order and zero-area triangles (the default)
+   uint32_t bare;       // 1: uv and colour zero (the hybrid graph's marching-cubes pass: the shader writes only pos and normal)
 };
 
 __device__ __forceinline__ float len2(float a, float b) { return sqrtf(a * a + b * b); }
@@ -126,9 +127,11 @@ __device__ __forceinline__ void write_vertex(const IsoParams& q, UhVertex* out, 
    v.normal[0] = -g[0] / gl;  // generateNormal (marching_cubes.comp:160-177): the density grows inwards
    v.normal[1] = -g[1] / gl;
    v.normal[2] = -g[2] / gl;
-   v.uv[0] = p[0] * q.inv_domain;
-   v.uv[1] = p[2] * q.inv_domain;
-   v.color[0] = v.color[1] = v.color[2] = v.color[3] = 1.0f;
+   if (!q.bare) {
+      v.uv[0] = p[0] * q.inv_domain;
+      v.uv[1] = p[2] * q.inv_domain;
+      v.color[0] = v.color[1] = v.color[2] = v.color[3] = 1.0f;
+   }
    *out = v;
 }
 
@@ -231,7 +234,36 @@ static bool load_tables() {
    return true;
 }
 
+// the grid of uh_add_isosurface_mesh(ctx, res, lo, hi, time, ...)
+IsoParams iso_params(uint32_t resolution, float lo, float hi, float time, bool reference) {
+   IsoParams q;
+   q.res = resolution;
+   q.lo = lo;
+   q.h = (hi - lo) / (float)resolution;
+   q.sphere_r = 8.0f * std::fabs(std::sin(time * 0.3f));
+   q.inv_domain = 1.0f / (hi - lo);
+   q.reference = reference ? 1u : 0u;
+   q.bare = 0;
+   return q;
+}
+IsoParams mc_pass_params(float time) {
+   IsoParams q = iso_params(kMcRes, 0.0f, (float)kMcRes, time, true);
+   q.bare = 1;
+   return q;
+}
+
 }  // namespace
+
+bool uhi_mc_extract_count(void* stream, float time, uint32_t* block_counts) {
+   if (!load_tables()) return false;
+   k_iso_count<<<kMcBlocks, kBlock, 0, (hipStream_t)stream>>>(mc_pass_params(time), block_counts);
+   return true;
+}
+bool uhi_mc_extract_emit(void* stream, float time, const uint32_t* block_offsets, UhVertex* verts) {
+   if (!load_tables()) return false;
+   k_iso_emit<<<kMcBlocks, kBlock, 0, (hipStream_t)stream>>>(mc_pass_params(time), block_offsets, verts);
+   return true;
+}
 
 extern "C" int uh_isosurface_cells(uh_ctx* ctx, uint32_t resolution, float lo, float hi, float time, uint8_t* out_cube_index, uint8_t* out_triangle_count) {
    if (!ctx || resolution < 1 || resolution > 1024 || !(hi > lo)) return UH_ERR_INVALID_ARGUMENT;
@@ -239,13 +271,7 @@ extern "C" int uh_isosurface_cells(uh_ctx* ctx, uint32_t resolution, float lo, f
    if (int st = uh_stream(ctx, &stream_v)) return st;
    hipStream_t stream = (hipStream_t)stream_v;
    if (!load_tables()) return UH_ERR_HIP;
-   IsoParams q;
-   q.res = resolution;
-   q.lo = lo;
-   q.h = (hi - lo) / (float)resolution;
-   q.sphere_r = 8.0f * std::fabs(std::sin(time * 0.3f));
-   q.inv_domain = 1.0f / (hi - lo);
-   q.reference = uhi_iso_reference_triangulation(ctx) ? 1u : 0u;
+   const IsoParams q = iso_params(resolution, lo, hi, time, uhi_iso_reference_triangulation(ctx) != 0);
    const uint64_t cells = (uint64_t)resolution * resolution * resolution;
    uint8_t *d_a = nullptr, *d_b = nullptr;
    if (hipMalloc(&d_a, cells) != hipSuccess || hipMalloc(&d_b, cells) != hipSuccess) {
@@ -270,13 +296,7 @@ extern "C" int uh_add_isosurface_mesh(uh_ctx* ctx, uint32_t resolution, float lo
    void* stream_v = nullptr;
    if (int st = uh_stream(ctx, &stream_v)) return st;  // also selects the context's device
    hipStream_t stream = (hipStream_t)stream_v;
-   IsoParams q;
-   q.res = resolution;
-   q.lo = lo;
-   q.h = (hi - lo) / (float)resolution;
-   q.sphere_r = 8.0f * std::fabs(std::sin(time * 0.3f));
-   q.inv_domain = 1.0f / (hi - lo);
-   q.reference = uhi_iso_reference_triangulation(ctx) ? 1u : 0u;
+   const IsoParams q = iso_params(resolution, lo, hi, time, uhi_iso_reference_triangulation(ctx) != 0);
    const uint64_t cells = (uint64_t)resolution * resolution * resolution;
    const uint32_t blocks = (uint32_t)((cells + kBlock - 1) / kBlock);
    uint32_t *d_counts = nullptr, *d_chunks = nullptr;

@@ -2766,12 +2766,13 @@ __global__ __launch_bounds__(kBlock) void k_hybrid_deferred(SceneDev sc, HybridD
 }
 
 // atmosphere.frag (cubemap_enabled = 0) on the pixels the G-buffer cast missed: compacted first (one atomic per wave), so that
-// geometry pixels cost nothing
-__global__ __launch_bounds__(kBlock) void k_hybrid_sky_classify(HybridDev hd, HybridFrameDev fd) {
+// geometry pixels cost nothing; skip (nullable): the marching-cubes pass's visibility, whose covered pixels fail the atmosphere pass's
+// depth test
+__global__ __launch_bounds__(kBlock) void k_hybrid_sky_classify(HybridDev hd, HybridFrameDev fd, const uint32_t* __restrict__ skip) {
    const uint32_t n = hd.W * hd.H, groups = (n + 63) / 64, lane = lane_id();
    for (uint32_t g = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); g < groups; g += gridDim.x * kWavesPerBlock) {
       const uint32_t pix = g * 64u + lane;
-      const bool sky = pix < n && hd.pos[pix].w == 0.0f;
+      const bool sky = pix < n && hd.pos[pix].w == 0.0f && (!skip || skip[pix] == 0xFFFFFFFFu);
       const uint32_t slot = wave_append(fd.sky_counter, sky);
       if (sky) hd.queue[slot] = pix;
    }
@@ -2907,8 +2908,8 @@ void launch_hybrid_deferred(const LaunchCfg& c, const SceneDev& sc, const Hybrid
    else
       k_hybrid_deferred<true, true><<<grid, kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, n, im, sl);
 }
-void launch_hybrid_sky(const LaunchCfg& c, const FrameParams& fp, const HybridDev& hd, const HybridFrameDev& fd, const IblMaps* cube) {
-   k_hybrid_sky_classify<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(hd, fd);
+void launch_hybrid_sky(const LaunchCfg& c, const FrameParams& fp, const HybridDev& hd, const HybridFrameDev& fd, const IblMaps* cube, const uint32_t* skip) {
+   k_hybrid_sky_classify<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(hd, fd, skip);
    if (!cube)
       k_hybrid_sky<false><<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(fp, hd, fd, IblMaps{});
    else

@@ -258,3 +258,21 @@ class ForwardStats(C.Structure):
 
 assert C.sizeof(ForwardStats) == 32 and ForwardStats.renders.offset == 12 and ForwardStats.pieces.offset == 16 and \
     ForwardStats.covered_pixels.offset == 20 and ForwardStats.lights.offset == 24
+
+
+# the hybrid graph's marching-cubes pass: setup_marching_cubes_pass (mod.rs:164-174, renderers/marching_cubes.rs); bit 9 stays unused
+HYBRID_MARCHING_CUBES = 1 << 10
+HYBRID_DEPTH, HYBRID_MARCHING_CUBES_VISIBILITY = 9, 10
+MARCHING_CUBES_NONE = 0xFFFFFFFF  # HYBRID_MARCHING_CUBES_VISIBILITY of a pixel no marching-cubes fragment survived on
+
+
+class MarchingCubesStats(C.Structure):
+    """UhMarchingCubesStats: the last marching-cubes pass - hipEvent ms, the passes so far, triangles extracted (zero-area ones included),
+    pieces that reached the rasteriser, covered pixels, lights evaluated (the sun included) and the view.time used"""
+
+    _fields_ = [("pass_ms", C.c_float), ("renders", C.c_uint32), ("triangles", C.c_uint32), ("pieces", C.c_uint32), ("covered_pixels", C.c_uint32),
+                ("lights", C.c_uint32), ("time", C.c_float), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(MarchingCubesStats) == 32 and MarchingCubesStats.triangles.offset == 8 and MarchingCubesStats.pieces.offset == 12 and \
+    MarchingCubesStats.covered_pixels.offset == 16 and MarchingCubesStats.lights.offset == 20 and MarchingCubesStats.time.offset == 24

@@ -1,0 +1,157 @@
+"""CPU reference of the hybrid graph's marching-cubes pass (uh_render_hybrid with UH_HYBRID_MARCHING_CUBES) in numpy, in the order
+DESIGN.md section 2 "Marching-cubes pass" pins, built on forward_reference.py's rasteriser: the extraction of the reference's 32^3 grid,
+the depth buffer from the G-buffer positions, the resolve seeded from it (LESS_OR_EQUAL, the seed losing ties) and forward.frag with
+mesh 0's material at uv (0, 0). Not a conftest: test modules import it."""
+import numpy as np
+
+import forward_reference as fw
+import hybrid_reference as hr
+import shadow_map_reference as sr
+from rust_renderer_amd.types import VERTEX_DTYPE
+
+F = np.float32
+NONE = fw.NONE
+RES = 32  # marching_cubes.rs:17-45: 32^3 invocations, voxel size 1, from the origin
+
+# the corner offsets (marching_cubes.rs:23-32) and the corner pairs marching_cubes.comp:204-226 hands to vertexInterp, per edge
+CORNERS = np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0], [0, 0, 1], [1, 0, 1], [1, 1, 1], [0, 1, 1]], np.int64)
+EDGE_CORNERS = np.array([[0, 1], [1, 2], [2, 3], [3, 0], [4, 5], [5, 6], [6, 7], [7, 4], [0, 4], [1, 5], [2, 6], [3, 7]], np.int64)
+
+
+# ---- extraction -----------------------------------------------------------------------------------------------------------------
+def sphere_radius(time):
+    """8 |sin(0.3 t)| in float32: the product rounded, sin correctly rounded to float32"""
+    return F(8.0) * F(abs(np.float32(np.sin(np.float64(F(time) * F(0.3))))))
+
+
+def density(x, y, z, r):
+    """marching_cubes.comp:83-103 in float32: max(-1, -sdTorus, -sdBox, -sdSphere(r)), positive inside"""
+    x, y, z = np.asarray(x, F), np.asarray(y, F), np.asarray(z, F)
+    len2 = lambda a, b: np.sqrt(a * a + b * b)
+    len3 = lambda a, b, c: np.sqrt((a * a + b * b) + c * c)
+    s = F(16.0)
+    torus = len2(len2(x - s, z - s) - F(5.0), y - F(20.0)) - F(3.0)
+    dx, dy, dz = np.abs(x - s) - F(5.0), np.abs(y - F(10.0)) - F(5.0), np.abs(z - s) - F(5.0)
+    zero = F(0.0)
+    box = np.minimum(np.maximum(dx, np.maximum(dy, dz)), zero) + len3(np.maximum(dx, zero), np.maximum(dy, zero), np.maximum(dz, zero))
+    sphere = len3(x - s, y - F(26.0), z - s) - r
+    d = np.maximum(-torus, F(-1.0))
+    d = np.maximum(-box, d)
+    return np.maximum(-sphere, d).astype(F)
+
+
+def normal_at(p, r):
+    """generateNormal (marching_cubes.comp:160-177): central differences at step 1, negated and normalised (length at least 1e-20)"""
+    x, y, z = p[..., 0], p[..., 1], p[..., 2]
+    one = F(1.0)
+    g = np.stack([density(x + one, y, z, r) - density(x - one, y, z, r), density(x, y + one, z, r) - density(x, y - one, z, r),
+                  density(x, y, z + one, r) - density(x, y, z - one, r)], -1).astype(F)
+    gl = np.maximum(np.sqrt((g[..., 0] * g[..., 0] + g[..., 1] * g[..., 1]) + g[..., 2] * g[..., 2]), F(1e-20))
+    return (-g / gl[..., None]).astype(F)
+
+
+def extract(time, triangle_table):
+    """the pass's triangles at view.time: (positions (T, 3, 3), normals (T, 3, 3)) float32 in draw order - cells x fastest, then the case
+    list up to its first -1, zero-area triangles included; triangle_table the reference's [256][16]"""
+    r = sphere_radius(time)
+    n = RES
+    iz, iy, ix = np.meshgrid(np.arange(n), np.arange(n), np.arange(n), indexing="ij")
+    cell = np.stack([ix.reshape(-1), iy.reshape(-1), iz.reshape(-1)], -1)  # x fastest
+    corner = (cell[:, None, :] + CORNERS[None, :, :]).astype(F)                 # lo + h (i + offset) with lo = 0, h = 1: exact
+    v = density(corner[..., 0], corner[..., 1], corner[..., 2], r)
+    case = ((v < 0).astype(np.int64) << np.arange(8)).sum(-1)
+    table = np.asarray(triangle_table, np.int64).reshape(256, 16)
+    cells, edges = [], []
+    for c in np.nonzero(table[case, 0] >= 0)[0]:
+        row = table[case[c]]
+        for i in range(0, 15, 3):
+            if row[i] < 0:
+                break
+            cells.append(c)
+            edges.append(row[i:i + 3])
+    if not cells:
+        z = np.zeros((0, 3, 3), F)
+        return z, z.copy()
+    cells, edges = np.array(cells), np.array(edges)  # (T,), (T, 3)
+    a, b = EDGE_CORNERS[edges, 0], EDGE_CORNERS[edges, 1]
+    ci = cells[:, None]
+    va, vb = v[ci, a], v[ci, b]
+    pa, pb = corner[ci, a], corner[ci, b]
+    t = (F(0.0) - va) / (vb - va)                                    # vertexInterp (:136)
+    pos = (pa + t[..., None] * (pb - pa)).astype(F)                  # mix(x, y, a) = x + a (y - x)
+    return pos, normal_at(pos, r)
+
+
+def pass_mesh(positions, normals, material_mesh):
+    """the extracted triangles as forward_reference reads a mesh: vertex 3 t + k, pos and normal only (uv, colour, tangent zero), world
+    the identity, the material (maps, base colour) of `material_mesh` - the first mesh added (mesh_index = 0)"""
+    T = len(positions)
+    vtx = np.zeros(3 * T, VERTEX_DTYPE)
+    vtx["pos"][:, :3] = positions.reshape(-1, 3)
+    vtx["pos"][:, 3] = 1.0
+    vtx["normal"][:, :3] = normals.reshape(-1, 3)
+    m = {k: material_mesh[k] for k in ("diffuse_map", "normal_map", "metallic_roughness_map", "occlusion_map", "base_color")}
+    m.update(vertices=vtx, indices=np.arange(3 * T, dtype=np.uint32), world=np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], F))
+    return m
+
+
+# ---- the depth buffer and the seeded resolve ------------------------------------------------------------------------------------
+def depth_seed(position, view):
+    """the G-buffer pass's depth from the cast's positions (H, W, 4): c = (P V) (p, 1), d = c.z / c.w kept when c.w > 0 and
+    0 <= d <= 1 (-0 as +0), else 1.0; 1.0 where the cast missed (w == 0)"""
+    M = sr._mat_mul(np.array(view.projection[:], F), np.array(view.view[:], F))
+    p = np.asarray(position, F)
+    x, y, z = p[..., 0], p[..., 1], p[..., 2]
+    with np.errstate(all="ignore"):
+        cz = ((M[2] * x + M[6] * y) + M[10] * z) + M[14]
+        cw = ((M[3] * x + M[7] * y) + M[11] * z) + M[15]
+        d = (cz / cw).astype(F)
+    keep = (p[..., 3] != 0) & (cw > 0) & (d >= 0) & (d <= 1)
+    return np.where(keep, np.where(d == 0, F(0.0), d), F(1.0)).astype(F)
+
+
+def resolve_seeded(recs, seed, W, H):
+    """the depth test LESS_OR_EQUAL against `seed` (H, W): the min of depth_bits << 32 | (0xFFFFFFFE - record), each pixel starting at
+    seed_bits << 32 | 0xFFFFFFFF -> (depth (H, W), visibility (H, W) draw index, record (H, W), -1 for none)"""
+    key = (np.asarray(seed, F).reshape(-1).view(np.uint32).astype(np.uint64) << np.uint64(32)) | np.uint64(0xFFFFFFFF)
+    for r, rec in enumerate(recs):
+        px, py, zz = fw._fragments(rec)
+        if not len(px):
+            continue
+        bits = np.where(zz == 0, F(0.0), zz).astype(F).view(np.uint32).astype(np.uint64)
+        np.minimum.at(key, py * W + px, (bits << np.uint64(32)) | np.uint64(0xFFFFFFFE - r))
+    low = (key & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    rec = np.where(low == 0xFFFFFFFF, -1, 0xFFFFFFFE - low)
+    depth = (key >> np.uint64(32)).astype(np.uint32).view(F)
+    draws = np.array([r["draw"] for r in recs] or [0], np.int64)
+    vis = np.where(rec < 0, NONE, draws[np.maximum(rec, 0)]).astype(np.uint32)
+    return depth.reshape(H, W), vis.reshape(H, W), rec.reshape(H, W)
+
+
+# ---- the pass -------------------------------------------------------------------------------------------------------------------
+def marching_cubes_pass(mesh, textures, view, lights, position, deferred, shadow=None):
+    """the pass on a frame: mesh from pass_mesh, position the G-buffer's (H, W, 4), deferred the deferred_output it draws into ->
+    dict(output (H, W, 4), depth, visibility, records, seed); shadow = (params, maps) when view.shadows_enabled == 1"""
+    H, W = position.shape[:2]
+    recs = fw.records_for([mesh], view, W, H)
+    seed = depth_seed(position, view)
+    depth, vis, rec = resolve_seeded(recs, seed, W, H)
+    out = np.array(deferred, F).reshape(W * H, 4)
+    pix, _, P, N, uu, vv = fw.surface([mesh], textures, recs, rec, W, H)
+    if len(pix):
+        idx = lambda key: np.full(len(pix), mesh[key], np.uint32)
+        with np.errstate(all="ignore"):
+            dt = fw.sample_texture(textures, idx("diffuse_map"), uu, vv)
+            mr = fw.sample_texture(textures, idx("metallic_roughness_map"), uu, vv)
+            oc = fw.sample_texture(textures, idx("occlusion_map"), uu, vv)
+            diffuse = np.power(dt.astype(np.float64), np.float64(F(2.2))).astype(F)
+            base = diffuse * np.asarray(mesh["base_color"], F)[None, :]
+            metallic, roughness, occlusion = mr[:, 2], mr[:, 1], oc[:, 0]
+            V = hr.normalize(np.array(view.eye_pos[:], F)[None, :] - P)
+            Lo = fw.direct_lighting(P, N, V, base, metallic, roughness, view, lights)
+            color = (F(0.03) * diffuse) * occlusion[:, None] + Lo
+            if view.shadows_enabled == 1:
+                params, smaps = shadow
+                color = color * sr.calculate_shadow(P, view, params, smaps)[0][:, None]
+        out[pix, :3], out[pix, 3] = color, 1.0
+    return dict(output=out.reshape(H, W, 4), depth=depth, visibility=vis, records=recs, seed=seed)

@@ -14,10 +14,13 @@ what is timed:
   forward the forward graph (uh_render_forward: shadow maps, forward pass, present) with each light count of --lights and
           shadows_enabled = 0, then shadows_enabled = 1 with the maps re-rendered in every call (the reference's key 3), beside the
           hybrid G-buffer cast + deferred pass of the same view
+  marching_cubes  the marching-cubes pass (UH_HYBRID_MARCHING_CUBES, marching_cubes_enabled = 1, view.time 5) in the whole frame,
+          with shadows_enabled = 0 and 1 (maps rendered once): the pass's ms, its triangles, pieces and covered pixels, and the frame's
+          passes beside it; then the same on a scene of one floor with the isosurface in full view
 
 Run it under `rocprofv3 --kernel-trace --stats -- python tools/hybrid_timing.py --mode ...` for the kernel table.
 
-  python tools/hybrid_timing.py [--mode passes|frame|ibl|shadows|forward --width 1920 --height 1080 --warmup 3 --iters 20 --lights 0,16,1024
+  python tools/hybrid_timing.py [--mode passes|frame|ibl|shadows|forward|marching_cubes --width 1920 --height 1080 --warmup 3 --iters 20 --lights 0,16,1024
                                  --builds 5 --out FILE]"""
 import argparse
 import json
@@ -163,9 +166,47 @@ def forward(a):
                    gbuffer_ms=med[1], deferred_ms=med[4], total_ms=med[1] + med[4])
 
 
+def _mc_timed(a, r, view, scene_name):
+    for _ in range(a.warmup):
+        r.render_hybrid(view, rr.HYBRID_FRAME | rr.HYBRID_MARCHING_CUBES)
+    per, frames = [], []
+    for _ in range(a.iters):
+        r.render_hybrid(view, rr.HYBRID_FRAME | rr.HYBRID_MARCHING_CUBES)
+        per.append(r.marching_cubes_stats())  # waits: one call at a time on an idle GPU
+        frames.append(r.hybrid_frame_stats())
+    med = [statistics.median(f.pass_ms[k] for f in frames) for k in range(len(PASSES))]
+    s = per[-1]
+    mc = statistics.median(p.pass_ms for p in per)
+    return dict(metric="hybrid_marching_cubes", scene=scene_name, lights=0, shadows=view.shadows_enabled, width=a.width, height=a.height,
+                iters=a.iters, marching_cubes_ms=mc, triangles=s.triangles, pieces=s.pieces, covered_pixels=s.covered_pixels,
+                **{f"{p}_ms": m for p, m in zip(PASSES, med)}, total_ms=sum(med) + mc)
+
+
+def marching_cubes(a):
+    scene, r, view = setup(a, 0, shadows_enabled=0, ibl_enabled=0, cubemap_enabled=0, num_lights=0)
+    view.marching_cubes_enabled, view.time = 1, 5.0
+    for shadows in (0, 1):
+        view.shadows_enabled = shadows
+        if shadows:
+            r.set_shadowmap_params(rr.shadow_cascades(scene.camera, view.sun_dir[:]))
+            r.render_hybrid(view, rr.HYBRID_SHADOW_MAPS)
+        yield _mc_timed(a, r, view, "config 1")
+    # the isosurface in full view: one floor under the domain [0, 32]^3, the camera aimed at (10, 15, 10)
+    r = rr.Renderer(a.width, a.height)
+    m = rr.make_material(rr.LAMBERTIAN, 0.0, (0.7, 0.7, 0.7, 1.0), diffuse_map=r.default_diffuse_map())
+    fv, fi = rr.scenes.quad((-12.0, -0.5, 44.0), (56.0, 0.0, 0.0), (0.0, 0.0, -56.0), nu=4, nv=4)
+    r.add_mesh(fv, fi, m)
+    r.initialize_raytracing()
+    cam = rr.camera.Camera((-30.0, 28.0, -22.0), (10.0, 15.0, 10.0), 60.0, a.width / a.height, 0.1, 1000.0)
+    view = rr.default_view(cam, a.width, a.height)
+    view.shadows_enabled = view.ibl_enabled = view.cubemap_enabled = 0
+    view.marching_cubes_enabled, view.time = 1, 5.0
+    yield _mc_timed(a, r, view, "floor and isosurface")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("passes", "frame", "ibl", "shadows", "forward"), default="passes")
+    ap.add_argument("--mode", choices=("passes", "frame", "ibl", "shadows", "forward", "marching_cubes"), default="passes")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--warmup", type=int, default=3)
@@ -175,7 +216,7 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     lines = []
-    for out in {"passes": passes, "frame": frame, "ibl": ibl, "shadows": shadows, "forward": forward}[a.mode](a):
+    for out in {"passes": passes, "frame": frame, "ibl": ibl, "shadows": shadows, "forward": forward, "marching_cubes": marching_cubes}[a.mode](a):
         lines.append(json.dumps(out))
         print(lines[-1], flush=True)
     if a.out:
