@@ -524,11 +524,13 @@ int uh_mgpu_set_option(uh_mgpu* group, const char* name, int value);
  * GATES: view->raytracing_supported == 0 skips both ray-traced passes and leaves their images as they are (mod.rs:107,134);
  * UH_HYBRID_RT_REFLECTIONS with view->ibl_enabled == 1 is UH_ERR_INVALID_ARGUMENT - and nothing runs - until the IBL maps (irradiance,
  * specular, BRDF LUT of ibl.rs) have been built with UH_HYBRID_ENVIRONMENT, below; mask bits, UH_ERR_NOT_BUILT and moved instances with
- * view->rebuild_tlas as for uh_render_frame (bits above UH_HYBRID_SHADOW_MAPS, below, are ignored, except UH_HYBRID_MARCHING_CUBES).
+ * view->rebuild_tlas as for uh_render_frame (bits above UH_HYBRID_SHADOW_MAPS, below, are ignored, except UH_HYBRID_MARCHING_CUBES and
+ * UH_HYBRID_GBUFFER_RASTER).
  * STREAM ORDER: uh_render_hybrid enqueues like a frame (behind the frames in flight, ahead of those that follow); uh_read_hybrid and
  * uh_get_hybrid_stats wait for all work of the context and are complete on return. The exception is UH_HYBRID_SHADOW_MAPS, below: a
  * call that renders shadow maps BLOCKS the host until the frames in flight and the pass's binning have finished (it reads the
- * binning's totals back to size its buffers); the passes after it are enqueued as usual.
+ * binning's totals back to size its buffers); the passes after it are enqueued as usual. So does a G-buffer pass rasterised with
+ * UH_HYBRID_GBUFFER_RASTER, below, for the same reason.
  * Arithmetic: DESIGN.md section 2, "Hybrid passes". */
 enum { UH_HYBRID_RT_SHADOWS = 1u << 0, UH_HYBRID_GBUFFER = 1u << 1, UH_HYBRID_RT_REFLECTIONS = 1u << 2, UH_HYBRID_ALL = 7 };
 /* which image uh_read_hybrid copies out (W*H texels each) */
@@ -540,7 +542,7 @@ enum {
    UH_HYBRID_SHADOWS = 4,    /* R8 */
    UH_HYBRID_REFLECTIONS = 5 /* RGBA8 */
 };
-/* the last uh_render_hybrid call: rays[0] G-buffer cast, rays[1] rt_shadows, rays[2] rt_reflections (= metal pixels); pass_ms the
+/* the last uh_render_hybrid call: rays[0] G-buffer cast (0 for a rasterised G-buffer), rays[1] rt_shadows, rays[2] rt_reflections (= metal pixels); pass_ms the
  * hipEvent time of each pass in the same order (0 for a pass that did not run) */
 typedef struct UhHybridStats {
    uint64_t rays[3];
@@ -589,7 +591,7 @@ enum {
    UH_HYBRID_PRESENT_OUTPUT = 8     /* 8 bits x 4 channels, B G R A */
 };
 /* the last uh_render_hybrid call: pass_ms[k] the hipEvent time of the pass of bit k (rt_shadows, G-buffer, rt_reflections, SSAO, deferred,
- * sky, present; 0 for a pass that did not run); sky_pixels the pixels the sky pass wrote; lights the lights the deferred pass evaluated
+ * sky, present; 0 for a pass that did not run; pass_ms[1] times the G-buffer pass cast or rasterised); sky_pixels the pixels the sky pass wrote; lights the lights the deferred pass evaluated
  * per pixel (the sun included; 0 when it did not run) */
 typedef struct UhHybridFrameStats {
    float pass_ms[7];
@@ -821,6 +823,56 @@ UH_LAYOUT_ASSERT(sizeof(UhMarchingCubesStats) == 32 && offsetof(UhMarchingCubesS
                     offsetof(UhMarchingCubesStats, time) == 24,
                  "UhMarchingCubesStats (32 B)");
 int uh_get_marching_cubes_stats(uh_ctx* ctx, UhMarchingCubesStats* out);
+
+/* ---- the hybrid graph's G-buffer pass rasterised: gbuffer_pass (renderers/gbuffer.rs, gbuffer.vert / gbuffer.frag) ---------------------
+ * UH_HYBRID_GBUFFER_RASTER (bit 11; bit 9 stays unused and ignored) is a modifier of UH_HYBRID_GBUFFER: with both bits set, the
+ * G-buffer pass of that call is drawn through the forward pass's rasteriser instead of cast, as the reference draws it. UH_HYBRID_FRAME
+ * stays 0x7f and the cast stays the default: the reference's default frame is
+ * UH_HYBRID_FRAME | UH_HYBRID_GBUFFER_RASTER | UH_HYBRID_SHADOW_MAPS. The pass runs at the G-buffer's slot (rt_shadows of the same call
+ * still reads the PREVIOUS G-buffer, whichever kind it was):
+ *   raster      UH_FORWARD_PASS's stages unchanged - every triangle of every mesh in draw order, clip to 0 <= z <= w, the viewport
+ *               (0, H, W, -H), guard band, snap, top-left rule, no culling, one sample at the pixel centre, LESS_OR_EQUAL with writes
+ *               against a depth buffer cleared to 1.0 - so its depth and visibility equal uh_render_forward's UH_FORWARD_DEPTH and
+ *               UH_FORWARD_VISIBILITY for the same view, bit for bit
+ *   fragment    gbuffer.frag once per covered pixel on the surviving fragment with perspective-correct attributes: position the
+ *               interpolated (world (p, 1), 1), and normal, albedo and pbr as the cast's resolve writes them (above)
+ *   uncovered   the clear values of the cast's miss: (1, 1, 1, 0), albedo (255, 255, 255, 0)
+ *   depth       the marching-cubes pass after a rasterised G-buffer depth-tests against this depth buffer, bit for bit (the reference's
+ *               shared attachment); after a cast it reconstructs the depth from the positions, as described above. The choice follows
+ *               the G-buffer pass that ran last, in this call or an earlier one.
+ * UH_ERR_INVALID_ARGUMENT with a message, and nothing runs, for the bit without UH_HYBRID_GBUFFER. UH_ERR_NOT_BUILT and moved
+ * instances with view->rebuild_tlas as for UH_HYBRID_GBUFFER; UH_ERR_CAPACITY, as in uh_render_forward, for a frame wider or taller
+ * than 65535 pixels or 2^32 - 1 or more triangle pieces.
+ * STREAM ORDER: the pass BLOCKS the host until the frames in flight, the passes before it in the call and its binning have finished: it
+ * reads the binning totals back to size its buffers, as UH_FORWARD_PASS does. The passes after it are enqueued as usual.
+ * READ-BACK (uh_read_hybrid, UH_ERR_INVALID_ARGUMENT before the first rasterised pass): UH_HYBRID_GBUFFER_DEPTH, the float32 depth
+ * buffer, and UH_HYBRID_GBUFFER_VISIBILITY, the uint32 draw index of the surviving fragment or 0xFFFFFFFF; both after the last
+ * rasterised pass, W*H texels, row 0 at NDC y = +1 as the other hybrid images. UH_HYBRID_DEPTH stays the marching-cubes pass's buffer.
+ * RESOURCES: about 12 bytes per pixel (depth, visibility, surviving record) and binning buffers that grow with the scene, allocated by
+ * the first rasterised pass and freed by uh_destroy. A context that never sets the bit allocates nothing for it.
+ * ISOLATION: the pass writes the four G-buffer targets and its own depth and visibility: no forward-graph image, path-traced image,
+ * reservoir or shadow map, and nothing in UhStats or UhForwardStats. In UhHybridFrameStats pass_ms[1] times the G-buffer pass
+ * whichever way it ran; in UhHybridStats rays[0] is 0 for a rasterised pass. The path-tracing graph's UH_PASS_GBUFFER stays a cast.
+ * Arithmetic: DESIGN.md section 2, "Rasterised G-buffer". */
+enum { UH_HYBRID_GBUFFER_RASTER = 1u << 11 };
+enum {
+   UH_HYBRID_GBUFFER_DEPTH = 11,     /* float32, 1.0 where nothing was drawn */
+   UH_HYBRID_GBUFFER_VISIBILITY = 12 /* uint32 draw index, 0xFFFFFFFF for none */
+};
+/* the last rasterised G-buffer pass: pass_ms its hipEvent time (0 when the last call that ran a G-buffer pass cast it, or when the
+ * last call ran none); renders the rasterised passes so far; pieces the triangle pieces that reached the rasteriser (after clipping
+ * and the setup's rejects) and covered_pixels the pixels with a surviving fragment, both of the last rasterised pass. All zero before
+ * the first one. Waits for all work of the context. */
+typedef struct UhGbufferRasterStats {
+   float pass_ms;
+   uint32_t renders;
+   uint32_t pieces;
+   uint32_t covered_pixels;
+} UhGbufferRasterStats;
+UH_LAYOUT_ASSERT(sizeof(UhGbufferRasterStats) == 16 && offsetof(UhGbufferRasterStats, renders) == 4 && offsetof(UhGbufferRasterStats, pieces) == 8 &&
+                    offsetof(UhGbufferRasterStats, covered_pixels) == 12,
+                 "UhGbufferRasterStats (16 B)");
+int uh_get_gbuffer_raster_stats(uh_ctx* ctx, UhGbufferRasterStats* out);
 
 #ifdef __cplusplus
 }

@@ -305,13 +305,14 @@ class Renderer {
    // "uh_render_hybrid")
    void render_hybrid(const UhViewUniformData& view, uint32_t mask = UH_HYBRID_ALL) { check(uh_render_hybrid(ctx_, &view, mask), "render_hybrid"); }
    // one image as bytes: W*H texels of 16 (position, normal, pbr, deferred output), 4 (albedo, reflections, present output, the
-   // marching-cubes depth float and draw index uint32), 2 (SSAO) or 1 (shadows) bytes
+   // marching-cubes and rasterised G-buffer depth floats and draw indices uint32), 2 (SSAO) or 1 (shadows) bytes
    std::vector<uint8_t> read_hybrid(int which) {
       const size_t texel = (which == UH_HYBRID_SHADOWS)      ? 1
                            : (which == UH_HYBRID_SSAO_IMAGE) ? 2
                            : (which == UH_HYBRID_ALBEDO || which == UH_HYBRID_REFLECTIONS || which == UH_HYBRID_PRESENT_OUTPUT ||
-                              which == UH_HYBRID_DEPTH || which == UH_HYBRID_MARCHING_CUBES_VISIBILITY) ? 4
-                                                                                                         : 16;
+                              which == UH_HYBRID_DEPTH || which == UH_HYBRID_MARCHING_CUBES_VISIBILITY || which == UH_HYBRID_GBUFFER_DEPTH ||
+                              which == UH_HYBRID_GBUFFER_VISIBILITY) ? 4
+                                                                     : 16;
       std::vector<uint8_t> out((size_t)width_ * height_ * texel);
       check(uh_read_hybrid(ctx_, which, out.data()), "read_hybrid");
       return out;
@@ -331,6 +332,12 @@ class Renderer {
    UhMarchingCubesStats marching_cubes_stats() {
       UhMarchingCubesStats s;
       check(uh_get_marching_cubes_stats(ctx_, &s), "marching_cubes_stats");
+      return s;
+   }
+   // the last rasterised G-buffer pass (UH_HYBRID_GBUFFER | UH_HYBRID_GBUFFER_RASTER; utopian_hip.h)
+   UhGbufferRasterStats gbuffer_raster_stats() {
+      UhGbufferRasterStats s;
+      check(uh_get_gbuffer_raster_stats(ctx_, &s), "gbuffer_raster_stats");
       return s;
    }
    // one face and mip of an IBL map built with UH_HYBRID_ENVIRONMENT (utopian_hip.h "uh_read_environment"): (512 >> mip)^2 texels of

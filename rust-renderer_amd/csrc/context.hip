@@ -66,6 +66,20 @@ struct DevBuf {
    }
 };
 
+// the forward rasteriser's binning buffers for the scene's meshes (raster_scene): the forward pass and the hybrid graph's rasterised
+// G-buffer have a set each; they grow with the scene
+struct SceneBins {
+   DevBuf<uint32_t> tile_count, tile_cursor, rec_count, tri_mesh, chunks, entries;
+   DevBuf<unsigned long long> totals;       // the grand totals of the two scans: records, tile entries
+   DevBuf<uint4> records;
+   DevBuf<float> mats;                      // [mesh][28]
+   std::vector<float> mats_host;
+   uint64_t geom = 0;                       // geom_version of tri_mesh / rec_count
+   template <class F> void each(F&& f) {
+      f(tile_count, 0), f(tile_cursor, 0), f(rec_count, 0), f(tri_mesh, 0), f(chunks, 0), f(entries, 0), f(totals, 0), f(records, 0), f(mats, 0);
+   }
+};
+
 }  // namespace
 
 // the hybrid graph's stages (uh_ctx::Hybrid::stage): its seven passes in the order of their UH_HYBRID_* bits, then the environment's,
@@ -372,6 +386,13 @@ struct uh_ctx {
                                                           // what the render in progress uses
       uint32_t s_renders = 0, smap_size = 0, s_tris[4] = {0, 0, 0, 0};
       bool gbuffer_done = false;               // a G-buffer pass has been enqueued (the marching-cubes pass's depth seed reads it)
+      bool gbuffer_rasterised = false;         // the last G-buffer pass enqueued was rasterised: its depth is the marching-cubes seed
+      // the rasterised G-buffer (UH_HYBRID_GBUFFER_RASTER), allocated by the first rasterised pass: its depth buffer, visibility,
+      // surviving records and binning buffers
+      DevBuf<float> gr_depth;
+      DevBuf<uint32_t> gr_vis, gr_rec_of, gr_covered;
+      SceneBins gr_bins;
+      uint32_t gr_renders = 0, gr_pieces = 0;
       // the marching-cubes pass (UH_HYBRID_MARCHING_CUBES), allocated by the first pass: its depth buffer, visibility, surviving
       // records, light records, extracted triangles and the forward rasteriser's binning buffers
       DevBuf<float> mc_depth;
@@ -405,6 +426,7 @@ struct uh_ctx {
       template <class F> void mc_bins(F&& f) {
          f(mc_verts, 0), f(mc_tile_count, 0), f(mc_tile_cursor, 0), f(mc_rec_count, 0), f(mc_chunks, 0), f(mc_entries, 0), f(mc_records, 0);
       }
+      template <class F> void gr_images(size_t n, F&& f) { f(gr_depth, n), f(gr_vis, n), f(gr_rec_of, n), f(gr_covered, 1); }
       template <class F> void env_maps(F&& f) {
          const size_t cube = env_mip_offset(kEnvMips);
          f(env, cube), f(irr, 6 * (size_t)kEnvSize * kEnvSize), f(spec, cube), f(lut, (size_t)kLutSize * kLutSize);
@@ -419,20 +441,12 @@ struct uh_ctx {
       DevBuf<uint32_t> vis, rec_of, covered;   // draw index, surviving record per pixel; [0] the covered pixels of the last pass
       DevBuf<uchar4> present;                  // the forward graph's present image, B8G8R8A8
       DevBuf<HybridLight> lights;              // forward.frag's light records, the sun first
-      DevBuf<uint32_t> tile_count, tile_cursor, rec_count, tri_mesh, chunks, entries;
-      DevBuf<unsigned long long> totals;       // the grand totals of the two scans: records, tile entries
-      DevBuf<uint4> records;
-      DevBuf<float> mats;                      // [mesh][28]
-      std::vector<float> mats_host;
-      uint64_t geom = 0;                       // geom_version of tri_mesh / rec_count
+      SceneBins bins;
       // pass k: 0 shadow maps, 1 forward, 2 present (the last call's; ms resolved by the first stats read and kept)
       uh_ctx::Hybrid::Stage stage[3];
       uint32_t renders = 0, pieces = 0, lights_used = 0;
       template <class F> void images(size_t n, F&& f) {
          f(depth, n), f(vis, n), f(rec_of, n), f(present, n), f(lights, UH_MAX_GPU_LIGHTS + 1), f(covered, 1), f(color, n);
-      }
-      template <class F> void bins(F&& f) {
-         f(tile_count, 0), f(tile_cursor, 0), f(rec_count, 0), f(tri_mesh, 0), f(chunks, 0), f(entries, 0), f(totals, 0), f(records, 0), f(mats, 0);
       }
    } fw;
 };
@@ -695,6 +709,8 @@ void uh_destroy(uh_ctx* c) {
       h.shadow_maps(release);
       h.mc_images(0, release);
       h.mc_bins(release);
+      h.gr_images(0, release);
+      h.gr_bins.each(release);
       h.meshes.release();
       h.vertices.release();
       h.indices.release();
@@ -707,7 +723,7 @@ void uh_destroy(uh_ctx* c) {
             if (ev) (void)hipEventDestroy(ev);
       uh_ctx::Forward& f = c->fw;
       f.images(0, release);
-      f.bins(release);
+      f.bins.each(release);
       for (const auto& st : f.stage)
          for (hipEvent_t ev : {st.begin, st.end})
             if (ev) (void)hipEventDestroy(ev);
@@ -2960,7 +2976,11 @@ static int render_mc_pass(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformDat
    fd.rec_of = h.mc_rec_of.p;
    fd.color = h.deferred.p;
    fd.covered = h.mc_covered.p;
-   launch_mc_depth_seed(lc, h.pos.p, fd);
+   // the G-buffer's depth attachment (marching_cubes.rs:97, LOAD): the rasterised pass's own, or the cast's reconstruction
+   if (h.gbuffer_rasterised)
+      HIP_TRY(c, hipMemcpyAsync(h.mc_depth.p, h.gr_depth.p, (size_t)W * H * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+   else
+      launch_mc_depth_seed(lc, h.pos.p, fd);
    unsigned long long ntri = 0;
    HIP_TRY(c, hipStreamSynchronize(c->stream));
    HIP_TRY(c, hipMemcpy(&ntri, h.mc_totals.p, sizeof(ntri), hipMemcpyDeviceToHost));
@@ -3009,9 +3029,33 @@ static int render_mc_pass(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformDat
    return UH_OK;
 }
 
+// ---- the rasterised G-buffer (utopian_hip.h "UH_HYBRID_GBUFFER_RASTER"; forward.hip) ----
+static int raster_scene(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformData& view, SceneBins& b, ForwardDev& fd, const char* who, uint32_t* pieces);
+
+// raster_scene into the pass's own depth, visibility and records, then gbuffer.frag into the four targets
+static int render_gbuffer_raster(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformData& view, const HybridDev& hd) {
+   uh_ctx::Hybrid& h = c->hy;
+   ForwardDev fd{};
+   fd.depth = h.gr_depth.p;
+   fd.vis = h.gr_vis.p;
+   fd.rec_of = h.gr_rec_of.p;
+   fd.covered = h.gr_covered.p;
+   uint32_t pieces = 0;
+   if (int st = raster_scene(c, lc, view, h.gr_bins, fd, "uh_render_hybrid: rasterised G-buffer", &pieces)) return st;
+   launch_gbuffer_raster_shade(lc, c->scene, fd, hd);
+   h.gr_pieces = pieces;
+   h.gr_renders++;
+   return UH_OK;
+}
+
 int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    if (!view) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_render_hybrid: null view");
+   const bool raster = (mask & UH_HYBRID_GBUFFER_RASTER) != 0;
+   if (raster && !(mask & UH_HYBRID_GBUFFER))
+      return fail(c, UH_ERR_INVALID_ARGUMENT,
+                  "uh_render_hybrid: UH_HYBRID_GBUFFER_RASTER without UH_HYBRID_GBUFFER (the bit chooses how the G-buffer pass runs); set both, "
+                  "or neither");
    // the IBL maps exist for this call's consumers when an earlier call built them or this one does, before rt_reflections
    const bool maps = c->hy.env_builds > 0 || (mask & UH_HYBRID_ENVIRONMENT);
    if ((mask & UH_HYBRID_RT_REFLECTIONS) && view->ibl_enabled == 1 && !maps)
@@ -3058,11 +3102,15 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    if (!c->built && c->topology_valid && view->rebuild_tlas == 1)
       if (int st = uh_refit_acceleration(c)) return st;
    if (!c->built) return fail(c, UH_ERR_NOT_BUILT, "uh_render_hybrid before uh_build_acceleration");
+   if (raster && (c->W > 65535 || c->H > 65535))
+      return fail(c, UH_ERR_CAPACITY, "uh_render_hybrid: rasterised G-buffer: a frame wider or taller than 65535 pixels");
    HIP_TRY(c, hipSetDevice(c->device));
    uh_ctx::Hybrid& h = c->hy;
    const bool first = !h.counter.p;
    if (int st = hybrid_alloc(c)) return st;
    if (int st = hybrid_tables(c)) return st;
+   if (raster && !h.gr_covered.p)
+      if (int st = alloc_group(c, [&](auto f) { h.gr_images((size_t)c->W * c->H, f); })) return st;
    const uint32_t frame_bits = UH_HYBRID_SSAO | UH_HYBRID_DEFERRED | UH_HYBRID_SKY | UH_HYBRID_PRESENT;
    const bool frame_first = ((mask & frame_bits) || mc) && !h.sky_counter.p;
    if ((mask & frame_bits) || mc) {
@@ -3149,9 +3197,17 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    }
    if (mask & UH_HYBRID_GBUFFER) {
       HIP_TRY(c, begin(kStGbuffer));
-      launch_hybrid_gbuffer(lc, fp, c->scene, hd, grid ? &c->cam_dev : nullptr);
+      if (raster) {
+         if (int st = render_gbuffer_raster(c, lc, *view, hd)) {
+            h.stage[kStGbuffer].ran = false;  // no time for a pass that did not complete
+            return st;
+         }
+      } else {
+         launch_hybrid_gbuffer(lc, fp, c->scene, hd, grid ? &c->cam_dev : nullptr);
+      }
       HIP_TRY(c, end(kStGbuffer));
       h.gbuffer_done = true;
+      h.gbuffer_rasterised = raster;
    }
    // setup_cubemap_pass (mod.rs:121): after the G-buffer, before rt_reflections; the maps persist until the next build
    const IblMaps ibl{h.env.p, h.irr.p, h.spec.p, h.lut.p};
@@ -3218,16 +3274,18 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    const uh_ctx::Hybrid& h = c->hy;
    if (!h.counter.p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid before the first uh_render_hybrid");
-   if (which < 0 || which > UH_HYBRID_MARCHING_CUBES_VISIBILITY) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..10");
+   if (which < 0 || which > UH_HYBRID_GBUFFER_VISIBILITY) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..12");
    if (which >= UH_HYBRID_SSAO_IMAGE && which <= UH_HYBRID_PRESENT_OUTPUT && !h.sky_counter.p)
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 6..8 before the first call with an SSAO, deferred, sky or present bit");
-   if (which >= UH_HYBRID_DEPTH && h.mc_renders == 0)
+   if ((which == UH_HYBRID_DEPTH || which == UH_HYBRID_MARCHING_CUBES_VISIBILITY) && h.mc_renders == 0)
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 9..10 before the first marching-cubes pass");
+   if (which >= UH_HYBRID_GBUFFER_DEPTH && h.gr_renders == 0)
+      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 11..12 before the first rasterised G-buffer pass");
    // image k's pixels and its bytes per pixel, in UH_HYBRID_* image order
    const std::pair<const void*, size_t> img[] = {
       {h.pos.p, sizeof(float4)}, {h.nrm.p, sizeof(float4)}, {h.alb.p, sizeof(uchar4)}, {h.pbr.p, sizeof(float4)}, {h.shadow.p, 1},
       {h.refl.p, sizeof(uchar4)}, {h.ssao.p, sizeof(uint16_t)}, {h.deferred.p, sizeof(float4)}, {h.present.p, sizeof(uchar4)},
-      {h.mc_depth.p, sizeof(float)}, {h.mc_vis.p, sizeof(uint32_t)}};
+      {h.mc_depth.p, sizeof(float)}, {h.mc_vis.p, sizeof(uint32_t)}, {h.gr_depth.p, sizeof(float)}, {h.gr_vis.p, sizeof(uint32_t)}};
    return read_back(c, out, img[which].first, (size_t)c->W * c->H * img[which].second);
 }
 
@@ -3277,6 +3335,22 @@ int uh_get_marching_cubes_stats(uh_ctx* c, UhMarchingCubesStats* out) {
    return UH_OK;
 }
 
+int uh_get_gbuffer_raster_stats(uh_ctx* c, UhGbufferRasterStats* out) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_gbuffer_raster_stats: null destination");
+   std::memset(out, 0, sizeof(*out));
+   const uh_ctx::Hybrid& h = c->hy;
+   if (h.gr_renders == 0) return UH_OK;
+   HIP_TRY(c, hipSetDevice(c->device));
+   if (int st = sync_all(c)) return st;
+   if (h.gbuffer_rasterised)  // the G-buffer stage's record is the last rasterised pass's
+      if (int st = stage_ms(c, kStGbuffer, &out->pass_ms)) return st;
+   out->renders = h.gr_renders;
+   out->pieces = h.gr_pieces;
+   HIP_TRY(c, hipMemcpy(&out->covered_pixels, h.gr_covered.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+   return UH_OK;
+}
+
 int uh_read_environment(uh_ctx* c, int which, int face, int mip, void* out) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    const uh_ctx::Hybrid& h = c->hy;
@@ -3320,7 +3394,7 @@ int uh_get_hybrid_stats(uh_ctx* c, UhHybridStats* out) {
    uint32_t metal = 0;
    if (h.stage[kStReflections].ran) HIP_TRY(c, hipMemcpy(&metal, h.counter.p, sizeof(metal), hipMemcpyDeviceToHost));
    const uint64_t n = (uint64_t)c->W * c->H;
-   out->rays[0] = h.stage[kStGbuffer].ran ? n : 0;
+   out->rays[0] = h.stage[kStGbuffer].ran && !h.gbuffer_rasterised ? n : 0;  // a rasterised pass casts no ray
    out->rays[1] = h.stage[kStShadows].ran ? n : 0;
    out->rays[2] = metal;
    out->reflection_pixels = metal;
@@ -3396,76 +3470,86 @@ static void forward_mesh_matrices(const uh_ctx* c, const UhViewUniformData& v, s
    }
 }
 
-// count, scan, emit, resolve, then forward.frag: the records' and tile entries' totals come back to the host in between (the buffers
-// grow to them)
-static int render_forward_pass(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformData& view) {
+// the scene's meshes through the forward rasteriser into fd.depth (cleared to 1.0), fd.vis and fd.rec_of, which the caller sets: count,
+// scan, emit, resolve. The records' and tile entries' totals come back to the host in between (the buffers grow to them); *pieces
+// receives the records. `who` names the entry point in messages.
+static int raster_scene(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformData& view, SceneBins& b, ForwardDev& fd, const char* who, uint32_t* pieces) {
    uh_ctx::Hybrid& h = c->hy;
-   uh_ctx::Forward& f = c->fw;
    const uint32_t W = c->W, H = c->H, tiles_x = (W + kForwardTile - 1) / kForwardTile, tiles_y = (H + kForwardTile - 1) / kForwardTile;
    const uint32_t tiles = tiles_x * tiles_y;
    size_t ntri = 0;
    for (const HostMesh& m : c->meshes) ntri += m.indices.size() / 3;
-   if (ntri >= (1ull << 32) - 1) return fail(c, UH_ERR_CAPACITY, "uh_render_forward: 2^32 - 1 or more triangles");
-   const auto grow = [&](auto& b, size_t n) -> int {
-      if (b.p && b.n >= n) return UH_OK;
-      const hipError_t e = b.alloc(n);
+   if (ntri >= (1ull << 32) - 1) return fail(c, UH_ERR_CAPACITY, std::string(who) + ": 2^32 - 1 or more triangles");
+   const auto grow = [&](auto& buf, size_t n) -> int {
+      if (buf.p && buf.n >= n) return UH_OK;
+      const hipError_t e = buf.alloc(n);
       if (e != hipSuccess)
-         return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string("uh_render_forward: allocation: ") + hipGetErrorString(e));
+         return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string(who) + ": allocation: " + hipGetErrorString(e));
       return UH_OK;
    };
-   for (int st : {grow(f.tile_count, tiles), grow(f.tile_cursor, tiles), grow(f.totals, 2), grow(f.mats, std::max<size_t>(1, 28 * c->meshes.size())),
-                  grow(f.chunks, std::max<size_t>(1, scan_chunk_count((uint32_t)std::max<size_t>(ntri, tiles))))})
+   for (int st : {grow(b.tile_count, tiles), grow(b.tile_cursor, tiles), grow(b.totals, 2), grow(b.mats, std::max<size_t>(1, 28 * c->meshes.size())),
+                  grow(b.chunks, std::max<size_t>(1, scan_chunk_count((uint32_t)std::max<size_t>(ntri, tiles))))})
       if (st) return st;
-   if (f.geom != c->geom_version || !f.rec_count.p) {
+   if (b.geom != c->geom_version || !b.rec_count.p) {
       std::vector<uint32_t> tm;
       tm.reserve(ntri);
       for (size_t m = 0; m < c->meshes.size(); m++) tm.insert(tm.end(), c->meshes[m].indices.size() / 3, (uint32_t)m);
-      for (int st : {grow(f.tri_mesh, std::max<size_t>(1, ntri)), grow(f.rec_count, std::max<size_t>(1, ntri))})
+      for (int st : {grow(b.tri_mesh, std::max<size_t>(1, ntri)), grow(b.rec_count, std::max<size_t>(1, ntri))})
          if (st) return st;
-      if (ntri) HIP_TRY(c, hipMemcpy(f.tri_mesh.p, tm.data(), ntri * sizeof(uint32_t), hipMemcpyHostToDevice));
-      f.geom = c->geom_version;
+      if (ntri) HIP_TRY(c, hipMemcpy(b.tri_mesh.p, tm.data(), ntri * sizeof(uint32_t), hipMemcpyHostToDevice));
+      b.geom = c->geom_version;
    }
-   forward_mesh_matrices(c, view, f.mats_host);
-   if (!f.mats_host.empty())
-      HIP_TRY(c, hipMemcpyAsync(f.mats.p, f.mats_host.data(), f.mats_host.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-   HIP_TRY(c, hipMemsetAsync(f.tile_count.p, 0, tiles * sizeof(uint32_t), c->stream));
-   HIP_TRY(c, hipMemsetAsync(f.covered.p, 0, sizeof(uint32_t), c->stream));
-   ForwardDev fd{};
+   forward_mesh_matrices(c, view, b.mats_host);
+   if (!b.mats_host.empty())
+      HIP_TRY(c, hipMemcpyAsync(b.mats.p, b.mats_host.data(), b.mats_host.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+   HIP_TRY(c, hipMemsetAsync(b.tile_count.p, 0, tiles * sizeof(uint32_t), c->stream));
+   HIP_TRY(c, hipMemsetAsync(fd.covered, 0, sizeof(uint32_t), c->stream));
    fd.vertices = h.vertices.p;
    fd.indices = h.indices.p;
    fd.meshes = h.meshes.p;
-   fd.tri_mesh = f.tri_mesh.p;
-   fd.mats = f.mats.p;
+   fd.tri_mesh = b.tri_mesh.p;
+   fd.mats = b.mats.p;
    fd.num_tris = (uint32_t)ntri;
    fd.W = W;
    fd.H = H;
    fd.tiles_x = tiles_x;
    fd.tiles_y = tiles_y;
-   fd.rec_count = f.rec_count.p;
-   fd.tile_count = f.tile_count.p;
-   fd.tile_cursor = f.tile_cursor.p;
+   fd.rec_count = b.rec_count.p;
+   fd.tile_count = b.tile_count.p;
+   fd.tile_cursor = b.tile_cursor.p;
+   launch_forward_count(lc, fd);
+   unsigned long long totals[2] = {0, 0};
+   if (ntri) device_exclusive_scan_u32(b.rec_count.p, (uint32_t)ntri, b.chunks.p, b.totals.p, c->stream);
+   device_exclusive_scan_u32(b.tile_count.p, tiles, b.chunks.p, b.totals.p + 1, c->stream);
+   HIP_TRY(c, hipMemcpyAsync(b.tile_cursor.p, b.tile_count.p, tiles * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+   HIP_TRY(c, hipStreamSynchronize(c->stream));
+   HIP_TRY(c, hipMemcpy(totals + 1, b.totals.p + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+   if (ntri) HIP_TRY(c, hipMemcpy(totals, b.totals.p, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+   // record ids below 2^32 - 1: the resolve's key holds 0xFFFFFFFE - record, and 0xFFFFFFFF stands for none
+   if (totals[0] >= (1ull << 32) - 1 || totals[1] >= (1ull << 32))
+      return fail(c, UH_ERR_CAPACITY, std::string(who) + ": 2^32 - 1 or more triangle pieces, or 2^32 or more tile entries");
+   for (int st : {grow(b.records, std::max<size_t>(1, 6 * (size_t)totals[0])), grow(b.entries, std::max<size_t>(1, (size_t)totals[1]))})
+      if (st) return st;
+   fd.records = b.records.p;
+   fd.entries = b.entries.p;
+   launch_forward_emit(lc, fd);
+   launch_forward_resolve(lc, fd);
+   *pieces = (uint32_t)totals[0];
+   return UH_OK;
+}
+
+// raster_scene, then forward.frag into forward_output
+static int render_forward_pass(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformData& view) {
+   uh_ctx::Hybrid& h = c->hy;
+   uh_ctx::Forward& f = c->fw;
+   ForwardDev fd{};
    fd.depth = f.depth.p;
    fd.vis = f.vis.p;
    fd.rec_of = f.rec_of.p;
    fd.color = f.color.p;
    fd.covered = f.covered.p;
-   launch_forward_count(lc, fd);
-   unsigned long long totals[2] = {0, 0};
-   if (ntri) device_exclusive_scan_u32(f.rec_count.p, (uint32_t)ntri, f.chunks.p, f.totals.p, c->stream);
-   device_exclusive_scan_u32(f.tile_count.p, tiles, f.chunks.p, f.totals.p + 1, c->stream);
-   HIP_TRY(c, hipMemcpyAsync(f.tile_cursor.p, f.tile_count.p, tiles * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-   HIP_TRY(c, hipStreamSynchronize(c->stream));
-   HIP_TRY(c, hipMemcpy(totals + 1, f.totals.p + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-   if (ntri) HIP_TRY(c, hipMemcpy(totals, f.totals.p, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-   // record ids below 2^32 - 1: the resolve's key holds ~record, and 0xFFFFFFFF stands for none
-   if (totals[0] >= (1ull << 32) - 1 || totals[1] >= (1ull << 32))
-      return fail(c, UH_ERR_CAPACITY, "uh_render_forward: 2^32 - 1 or more triangle pieces, or 2^32 or more tile entries");
-   for (int st : {grow(f.records, std::max<size_t>(1, 6 * (size_t)totals[0])), grow(f.entries, std::max<size_t>(1, (size_t)totals[1]))})
-      if (st) return st;
-   fd.records = f.records.p;
-   fd.entries = f.entries.p;
-   launch_forward_emit(lc, fd);
-   launch_forward_resolve(lc, fd);
+   uint32_t pieces = 0;
+   if (int st = raster_scene(c, lc, view, f.bins, fd, "uh_render_forward", &pieces)) return st;
    HybridFrameDev lp{};  // k_hybrid_light_prep's inputs, into the forward graph's own records
    lp.lights = f.lights.p;
    lp.raw_lights = h.raw_lights.p;
@@ -3479,7 +3563,7 @@ static int render_forward_pass(uh_ctx* c, const LaunchCfg& lc, const UhViewUnifo
    std::memcpy(fs.view, view.view, sizeof(fs.view));
    const ShadowLookup sl{h.smaps.p, h.s_params.p, h.smap_size};
    launch_forward_shade(lc, c->scene, fd, fs, view.shadows_enabled == 1 ? &sl : nullptr);
-   f.pieces = (uint32_t)totals[0];
+   f.pieces = pieces;
    f.lights_used = view.num_lights + 1;
    f.renders++;
    return UH_OK;

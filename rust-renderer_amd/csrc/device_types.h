@@ -385,6 +385,8 @@ void launch_forward_count(const LaunchCfg&, const ForwardDev&, bool flat = false
 void launch_forward_emit(const LaunchCfg&, const ForwardDev&, bool flat = false);
 void launch_forward_resolve(const LaunchCfg&, const ForwardDev&, bool seeded = false);
 void launch_forward_shade(const LaunchCfg&, const SceneDev&, const ForwardDev&, const ForwardShade&, const ShadowLookup* shadow, bool flat = false);
+// the hybrid graph's rasterised G-buffer: gbuffer.frag on the surviving records of a resolve of the scene's meshes into hd's four targets
+void launch_gbuffer_raster_shade(const LaunchCfg&, const SceneDev&, const ForwardDev&, const HybridDev&);
 // the marching-cubes pass's depth buffer from the G-buffer positions, into fd.depth; P V column-major at fd.mats + 28
 void launch_mc_depth_seed(const LaunchCfg&, const float4* gbuffer_pos, const ForwardDev&);
 void launch_hybrid_light_prep(const LaunchCfg&, const HybridFrameDev&);

@@ -1,6 +1,7 @@
 // forward.hip — the forward pass of build_minimal_forward_render_graph (utopian/src/renderers/forward.rs, shaders/forward/forward.vert /
 // forward.frag) on gfx950: a perspective triangle rasteriser with a depth test and perspective-correct interpolation, then forward.frag
-// once per pixel (a visibility buffer: under LESS_OR_EQUAL only the surviving fragment's colour remains). Four kernels:
+// once per pixel (a visibility buffer: under LESS_OR_EQUAL only the surviving fragment's colour remains). Four kernels, and a fifth
+// for the hybrid graph's rasterised G-buffer:
 //   k_forward_count    one lane per triangle (= draw index): forward.vert's gl_Position, clip to 0 <= z <= w, divide, viewport, then
 //                      raster_device.h's guard-band clip, snap and rejects; counts its records and, per tile its box touches, one entry
 //   (device_scan.h)    record offsets (in draw order) and the tiles' first entries
@@ -9,10 +10,12 @@
 //                      the last record in draw order among those of minimum depth - then depth, draw index and record written out once
 //   k_forward_shade    one lane per pixel: the surviving record's perspective-correct barycentrics, forward.vert's attributes and
 //                      forward.frag (surfaceShading over the sun and the lights, ambient, calculateShadow)
+//   k_gbuffer_raster_shade  one lane per pixel: the same prologue (fragment_at), then gbuffer.frag's four targets
 // The kernels are templates on the triangle source and the depth seed. The forward pass draws the scene's meshes (kFlat = false) into
 // a depth buffer cleared to 1.0; the hybrid graph's marching-cubes pass draws a flat list of world-space triangles (vertex 3 t + k of
 // triangle t, one mesh of its own) against a depth buffer seeded from the G-buffer (kSeed), shading only the pixels it covers.
-// Every step is exact and pinned: DESIGN.md section 2, "Forward pass" and "Marching-cubes pass".
+// The rasterised G-buffer draws the scene's meshes as the forward pass does, into a depth buffer of its own.
+// Every step is exact and pinned: DESIGN.md section 2, "Forward pass", "Marching-cubes pass" and "Rasterised G-buffer".
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -259,19 +262,18 @@ __global__ __launch_bounds__(kResolveBlock) void k_forward_resolve(ForwardDev fd
    if (threadIdx.x == 0 && s_covered) atomicAdd(fd.covered, s_covered);
 }
 
-// forward.frag at pixel i: the surviving record's integer edge functions give the screen weights l_k = e_k / area; q_k = l_k / w_k and
-// b = (q0 B0 + q1 B1 + q2 B2) / (q0 + q1 + q2) are the original triangle's barycentrics; every attribute is (a0 b0 + a1 b1) + a2 b2.
-// One lane per pixel, no grid-stride loop (the light records become scalar loads, as in k_hybrid_deferred). kFlat (the marching-cubes
-// pass): the material is fd.meshes[0]'s and the base colour scene mesh 0's (mesh_index = 0), and an uncovered pixel keeps its colour.
-template <bool kFlat, bool kShadow>
-__global__ __launch_bounds__(kShadeBlock) void k_forward_shade(SceneDev sc, ForwardDev fd, ForwardShade fs, ShadowLookup sl) {
-   const uint32_t n = fd.W * fd.H, i = blockIdx.x * kShadeBlock + threadIdx.x;
-   if (i >= n) return;
-   const uint32_t r = fd.rec_of[i];
-   if (r == kNone) {  // the clear colour (pass.rs: (1, 1, 1, 0)); load_write: untouched
-      if (!kFlat) fd.color[i] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-      return;
-   }
+// the fragment stage's prologue at pixel i of surviving record r: the record's integer edge functions give the screen weights
+// l_k = e_k / area; q_k = l_k / w_k and b = (q0 B0 + q1 B1 + q2 B2) / (q0 + q1 + q2) are the original triangle's barycentrics; every
+// attribute is (a0 b0 + a1 b1) + a2 b2: out_pos = (world (p, 1)).xyz (world row-major 3x4), then surface_attributes. forward.frag and
+// gbuffer.frag share it (k_forward_shade, k_gbuffer_raster_shade).
+struct Fragment {
+   uint32_t mesh;
+   HybridMesh m;
+   V3 P, N;
+   float uu, vv;
+};
+template <bool kFlat>
+__device__ __forceinline__ Fragment fragment_at(const SceneDev& sc, const ForwardDev& fd, uint32_t i, uint32_t r) {
    const uint4* q = fd.records + 6 * (size_t)r;
    const uint4 a = q[0], b = q[1], c = q[2], d = q[3], e = q[4], f = q[5];
    const raster::Edges ed = raster::make_edges((int)a.x, (int)a.y, (int)a.z, (int)a.w, (int)b.x, (int)b.y);
@@ -286,20 +288,40 @@ __global__ __launch_bounds__(kShadeBlock) void k_forward_shade(SceneDev sc, Forw
    const float b0 = ((q0 * B[0][0] + q1 * B[1][0]) + q2 * B[2][0]) / s;
    const float b1 = ((q0 * B[0][1] + q1 * B[1][1]) + q2 * B[2][1]) / s;
    const float b2 = ((q0 * B[0][2] + q1 * B[1][2]) + q2 * B[2][2]) / s;
-   const uint32_t t = c.w, mesh = mesh_of<kFlat>(fd, t);
-   const HybridMesh m = fd.meshes[mesh];
-   const UhVertex& v0 = vertex_of<kFlat>(fd, m.vertex_base, t, 0);
-   const UhVertex& v1 = vertex_of<kFlat>(fd, m.vertex_base, t, 1);
-   const UhVertex& v2 = vertex_of<kFlat>(fd, m.vertex_base, t, 2);
-   const float* o = fd.mats + (size_t)mesh * 28 + 16;  // out_pos = (world (p, 1)).xyz, world row-major 3x4
+   Fragment fr;
+   const uint32_t t = c.w;
+   fr.mesh = mesh_of<kFlat>(fd, t);
+   fr.m = fd.meshes[fr.mesh];
+   const UhVertex& v0 = vertex_of<kFlat>(fd, fr.m.vertex_base, t, 0);
+   const UhVertex& v1 = vertex_of<kFlat>(fd, fr.m.vertex_base, t, 1);
+   const UhVertex& v2 = vertex_of<kFlat>(fd, fr.m.vertex_base, t, 2);
+   const float* o = fd.mats + (size_t)fr.mesh * 28 + 16;
    auto world = [&](const UhVertex& v) {
       return v3(((o[0] * v.pos[0] + o[1] * v.pos[1]) + o[2] * v.pos[2]) + o[3] * 1.0f, ((o[4] * v.pos[0] + o[5] * v.pos[1]) + o[6] * v.pos[2]) + o[7] * 1.0f,
                 ((o[8] * v.pos[0] + o[9] * v.pos[1]) + o[10] * v.pos[2]) + o[11] * 1.0f);
    };
-   const V3 P = (world(v0) * b0 + world(v1) * b1) + world(v2) * b2;
-   V3 N;
-   float uu, vv;
-   surface_attributes(sc, m, v0, v1, v2, b0, b1, b2, N, uu, vv);                                // vert, frag:44-53
+   fr.P = (world(v0) * b0 + world(v1) * b1) + world(v2) * b2;
+   surface_attributes(sc, fr.m, v0, v1, v2, b0, b1, b2, fr.N, fr.uu, fr.vv);                  // vert, frag:44-53
+   return fr;
+}
+
+// forward.frag at pixel i on the surviving record's fragment_at. One lane per pixel, no grid-stride loop (the light records become
+// scalar loads, as in k_hybrid_deferred). kFlat (the marching-cubes pass): the material is fd.meshes[0]'s and the base colour scene
+// mesh 0's (mesh_index = 0), and an uncovered pixel keeps its colour.
+template <bool kFlat, bool kShadow>
+__global__ __launch_bounds__(kShadeBlock) void k_forward_shade(SceneDev sc, ForwardDev fd, ForwardShade fs, ShadowLookup sl) {
+   const uint32_t n = fd.W * fd.H, i = blockIdx.x * kShadeBlock + threadIdx.x;
+   if (i >= n) return;
+   const uint32_t r = fd.rec_of[i];
+   if (r == kNone) {  // the clear colour (pass.rs: (1, 1, 1, 0)); load_write: untouched
+      if (!kFlat) fd.color[i] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+      return;
+   }
+   const Fragment fr = fragment_at<kFlat>(sc, fd, i, r);
+   const HybridMesh& m = fr.m;
+   const uint32_t mesh = fr.mesh;
+   const V3 P = fr.P, N = fr.N;
+   const float uu = fr.uu, vv = fr.vv;
    const V3 dt = sample_texture(sc, sc.unorm_lut, m.diffuse_map, uu, vv);                      // frag:39
    const V3 mr = sample_texture(sc, sc.unorm_lut, m.metallic_roughness_map, uu, vv);           // frag:41-42
    const V3 oc = sample_texture(sc, sc.unorm_lut, m.occlusion_map, uu, vv);                    // frag:43
@@ -314,6 +336,27 @@ __global__ __launch_bounds__(kShadeBlock) void k_forward_shade(SceneDev sc, Forw
    V3 color = (0.03f * diffuse) * occlusion + Lo;                                               // frag:77-78
    if (kShadow) color = color * calculate_shadow(sl, fs.view, P);                               // frag:81-85
    fd.color[i] = make_float4(color.x, color.y, color.z, 1.0f);                                  // frag:93
+}
+
+// gbuffer.frag at pixel i on the surviving record's fragment_at (the hybrid graph's rasterised G-buffer): the four targets as
+// gbuffer_targets writes them for the cast, the clear values (1, 1, 1, 0) / albedo (255, 255, 255, 0) where no fragment survived. One
+// lane per pixel; depth and visibility are the resolve's.
+__global__ __launch_bounds__(kShadeBlock) void k_gbuffer_raster_shade(SceneDev sc, ForwardDev fd, HybridDev hd) {
+   const uint32_t n = fd.W * fd.H, i = blockIdx.x * kShadeBlock + threadIdx.x;
+   if (i >= n) return;
+   const uint32_t r = fd.rec_of[i];
+   const float4 clear = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+   float4 pos = clear, nrm = clear, pbr = clear;
+   uchar4 alb = make_uchar4(255, 255, 255, 0);
+   if (r != kNone) {
+      const Fragment fr = fragment_at<false>(sc, fd, i, r);
+      pos = make_float4(fr.P.x, fr.P.y, fr.P.z, 1.0f);                                         // frag:47, out_pos with w = 1
+      gbuffer_targets(sc, fr.m, fr.mesh, fr.N, fr.uu, fr.vv, nrm, alb, pbr);
+   }
+   hd.pos[i] = pos;
+   hd.nrm[i] = nrm;
+   hd.alb[i] = alb;
+   hd.pbr[i] = pbr;
 }
 
 // the images as the first call finds them: forward_output (1, 1, 1, 0), depth 1.0, no visibility, present (255, 255, 255, 0)
@@ -387,6 +430,9 @@ void launch_forward_shade(const LaunchCfg& c, const SceneDev& sc, const ForwardD
       else
          k_forward_shade<false, false><<<grid, kShadeBlock, 0, c.stream>>>(sc, fd, fs, sl);
    }
+}
+void launch_gbuffer_raster_shade(const LaunchCfg& c, const SceneDev& sc, const ForwardDev& fd, const HybridDev& hd) {
+   k_gbuffer_raster_shade<<<dim3((fd.W * fd.H + kShadeBlock - 1) / kShadeBlock), kShadeBlock, 0, c.stream>>>(sc, fd, hd);
 }
 void launch_mc_depth_seed(const LaunchCfg& c, const float4* gbuffer_pos, const ForwardDev& fd) {
    k_mc_depth_seed<<<dim3((fd.W * fd.H + kShadeBlock - 1) / kShadeBlock), kShadeBlock, 0, c.stream>>>(gbuffer_pos, fd);

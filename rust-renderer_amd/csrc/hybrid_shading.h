@@ -51,6 +51,20 @@ __device__ __forceinline__ void surface_attributes(const SceneDev& sc, const Hyb
    }
 }
 
+// gbuffer.frag:47-56's other three targets at a surface point of mesh `mesh` (shading normal nn, uv): normal (nn, 1), albedo the diffuse
+// texel quantised (no base_color_factor, alpha 255), pbr (metallic = the metallic-roughness map's b, roughness = its g, occlusion = the
+// occlusion map's r, the material index: mesh i has material i). The G-buffer cast (k_hybrid_gbuffer_resolve) and the rasterised
+// G-buffer (k_gbuffer_raster_shade) share it.
+__device__ __forceinline__ void gbuffer_targets(const SceneDev& sc, const HybridMesh& m, uint32_t mesh, V3 nn, float uu, float vv, float4& nrm,
+                                                uchar4& alb, float4& pbr) {
+   nrm = make_float4(nn.x, nn.y, nn.z, 1.0f);
+   const V3 d = sample_texture(sc, sc.unorm_lut, m.diffuse_map, uu, vv);
+   alb = make_uchar4((unsigned char)unorm8(d.x), (unsigned char)unorm8(d.y), (unsigned char)unorm8(d.z), 255);
+   const V3 mr = sample_texture(sc, sc.unorm_lut, m.metallic_roughness_map, uu, vv);
+   const V3 oc = sample_texture(sc, sc.unorm_lut, m.occlusion_map, uu, vv);
+   pbr = make_float4(mr.z, mr.y, oc.x, (float)mesh);
+}
+
 constexpr float kPiBrdf = 3.14159265359f;  // brdf.glsl:1
 
 // surfaceShading (pbr_lighting.glsl:20-79) with brdf.glsl, summed over the light records of k_hybrid_light_prep (the sun first). The

@@ -2442,12 +2442,7 @@ __global__ __launch_bounds__(kBlock) void k_hybrid_gbuffer_resolve(SceneDev sc, 
          V3 nn;
          float uu, vv;
          surface_attributes(sc, m, v0, v1, v2, b0, b1, b2, nn, uu, vv);
-         nrm = make_float4(nn.x, nn.y, nn.z, 1.0f);
-         const V3 d = sample_texture(sc, sc.unorm_lut, m.diffuse_map, uu, vv);
-         alb = make_uchar4((unsigned char)unorm8(d.x), (unsigned char)unorm8(d.y), (unsigned char)unorm8(d.z), 255);
-         const V3 mr = sample_texture(sc, sc.unorm_lut, m.metallic_roughness_map, uu, vv);
-         const V3 oc = sample_texture(sc, sc.unorm_lut, m.occlusion_map, uu, vv);
-         pbr = make_float4(mr.z, mr.y, oc.x, (float)mesh);  // one material per mesh: material index = mesh index
+         gbuffer_targets(sc, m, mesh, nn, uu, vv, nrm, alb, pbr);
       }
       hd.pos[j] = pos;
       hd.nrm[j] = nrm;

@@ -276,3 +276,20 @@ class MarchingCubesStats(C.Structure):
 
 assert C.sizeof(MarchingCubesStats) == 32 and MarchingCubesStats.triangles.offset == 8 and MarchingCubesStats.pieces.offset == 12 and \
     MarchingCubesStats.covered_pixels.offset == 16 and MarchingCubesStats.lights.offset == 20 and MarchingCubesStats.time.offset == 24
+
+
+# the hybrid graph's G-buffer pass rasterised (gbuffer.rs, gbuffer.vert / gbuffer.frag): a modifier of HYBRID_GBUFFER
+HYBRID_GBUFFER_RASTER = 1 << 11
+HYBRID_GBUFFER_DEPTH, HYBRID_GBUFFER_VISIBILITY = 11, 12
+GBUFFER_NONE = 0xFFFFFFFF  # HYBRID_GBUFFER_VISIBILITY of a pixel no fragment survived on
+
+
+class GbufferRasterStats(C.Structure):
+    """UhGbufferRasterStats: the last rasterised G-buffer pass - hipEvent ms, the rasterised passes so far, pieces that reached the
+    rasteriser and covered pixels"""
+
+    _fields_ = [("pass_ms", C.c_float), ("renders", C.c_uint32), ("pieces", C.c_uint32), ("covered_pixels", C.c_uint32)]
+
+
+assert C.sizeof(GbufferRasterStats) == 16 and GbufferRasterStats.renders.offset == 4 and GbufferRasterStats.pieces.offset == 8 and \
+    GbufferRasterStats.covered_pixels.offset == 12

@@ -1,0 +1,298 @@
+"""GPU: the hybrid graph's rasterised G-buffer (uh_render_hybrid with UH_HYBRID_GBUFFER | UH_HYBRID_GBUFFER_RASTER) against the numpy
+restatement of tests/gbuffer_raster_reference.py - depth, visibility and the four targets bit for bit - on the synthetic scene at awkward
+sizes, the reference's assets and config 1 at 1080p; against uh_render_forward's depth and visibility; the near plane, a moved
+instance and a floor beyond the guard band; the whole frame and the marching-cubes pass on it; refusals, isolation and the C++ mirror."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import forward_reference as fw
+import gbuffer_raster_reference as gr
+import hybrid_frame_reference as fr
+import hybrid_reference as hr
+import marching_cubes_pass_reference as mr
+import oracle_api as oa
+import rust_renderer_amd as rr
+from hybrid_util import CPP_H, CPP_W, DEFERRED_ULP, ROOT, SyntheticScene, assert_reflections, assets, bits, cpp_scene, cpp_view, frame_view, gbuf, \
+    scene_named, synthetic_scene, ulps, write_blob  # noqa: F401
+from rust_renderer_amd.api import UtopianError
+from test_gbuffer_raster_cpu import near_wall_scene
+from test_gpu_forward import _HugeFloor
+from test_gpu_marching_cubes_pass import _extracted, mc_scene
+
+pytestmark = pytest.mark.gpu
+W, H = 160, 120
+RASTER = rr.HYBRID_GBUFFER | rr.HYBRID_GBUFFER_RASTER
+
+
+def _setup(scene, width=W, height=H):
+    gpu = rr.Renderer(width, height)
+    meshes, textures = fw.upload_recorded(scene, gpu, defaults=not isinstance(scene, SyntheticScene))
+    view = frame_view(scene, width, height)
+    view.num_lights = 0
+    return gpu, meshes, textures, view
+
+
+def _check(gpu, meshes, textures, view, draws=None):
+    """the device's targets, depth and visibility against the restatement, bit for bit (with `draws`: where the subset restatement's
+    visibility is the device's); returns the restatement"""
+    Wd, Hd = gpu.width, gpu.height
+    ref = gr.gbuffer_raster(meshes, textures, view, Wd, Hd, draws)
+    depth, vis = gpu.read_hybrid(rr.HYBRID_GBUFFER_DEPTH), gpu.read_hybrid(rr.HYBRID_GBUFFER_VISIBILITY)
+    got = gbuf(gpu)
+    where = np.ones((Hd, Wd), bool) if draws is None else (ref["visibility"] == vis) & (vis != gr.NONE)
+    assert np.array_equal(vis[where], ref["visibility"][where]), f"visibility: {(vis != ref['visibility']).sum()} pixels differ"
+    assert np.array_equal(bits(depth)[where], bits(ref["depth"])[where]), "depth bits"
+    for k in ("position", "normal", "pbr"):
+        assert np.array_equal(bits(got[k])[where], bits(ref[k])[where]), f"{k}: {(bits(got[k]) != bits(ref[k]))[where].any(-1).sum()} pixels differ"
+    assert np.array_equal(got["albedo"][where], ref["albedo"][where]), "albedo bytes"
+    s = gpu.gbuffer_raster_stats()
+    if draws is None:
+        assert s.pieces == len(ref["records"]) and s.covered_pixels == int((vis != gr.NONE).sum())
+    assert s.renders >= 1 and s.pass_ms > 0
+    return ref
+
+
+@pytest.mark.parametrize("size", [(1, 1), (7, 5), (257, 129), (W, H)])
+def test_synthetic_scene_at_awkward_sizes(size):
+    gpu, meshes, textures, view = _setup(synthetic_scene(), *size)
+    gpu.render_hybrid(view, RASTER)
+    _check(gpu, meshes, textures, view)
+    assert gpu.hybrid_stats().rays[0] == 0, "a rasterised pass casts no ray"
+    assert gpu.hybrid_frame_stats().pass_ms[1] == gpu.gbuffer_raster_stats().pass_ms > 0
+
+
+@pytest.mark.parametrize("name", ["cornell", "spheres"])
+def test_reference_assets(name, assets):
+    gpu, meshes, textures, view = _setup(scene_named(name, assets))
+    gpu.render_hybrid(view, RASTER)
+    _check(gpu, meshes, textures, view)
+
+
+def test_config_1_at_1080p():
+    scene = rr.scenes.scene_for_config(1, with_spheres=True)
+    gpu, meshes, textures, view = _setup(scene, 1920, 1080)
+    gpu.render_hybrid(view, RASTER)
+    vis = gpu.read_hybrid(rr.HYBRID_GBUFFER_VISIBILITY)
+    other = rr.Renderer(1920, 1080)
+    scene.upload(other)
+    other.render_forward(view, rr.FORWARD_PASS)
+    assert np.array_equal(vis, other.read_forward(rr.FORWARD_VISIBILITY))
+    assert np.array_equal(bits(gpu.read_hybrid(rr.HYBRID_GBUFFER_DEPTH)), bits(other.read_forward(rr.FORWARD_DEPTH)))
+    assert gpu.gbuffer_raster_stats().pieces == other.forward_stats().pieces
+    # the 272k-triangle scene restated on the triangles of 4,000 sampled pixels
+    covered = np.nonzero(vis.reshape(-1) != gr.NONE)[0]
+    assert len(covered) > 0.5 * vis.size
+    pick = np.random.default_rng(1).choice(covered, 4000, replace=False)
+    ref = _check(gpu, meshes, textures, view, draws=vis.reshape(-1)[pick])
+    assert (ref["visibility"].reshape(-1)[pick] == vis.reshape(-1)[pick]).all(), "every sampled pixel restated"
+
+
+def test_same_rasteriser_as_the_forward_pass():
+    scene = synthetic_scene()
+    gpu, meshes, textures, view = _setup(scene, 257, 129)
+    gpu.render_hybrid(view, RASTER)
+    other, _, _, _ = _setup(scene, 257, 129)
+    other.render_forward(view, rr.FORWARD_PASS)
+    assert np.array_equal(gpu.read_hybrid(rr.HYBRID_GBUFFER_VISIBILITY), other.read_forward(rr.FORWARD_VISIBILITY))
+    assert np.array_equal(bits(gpu.read_hybrid(rr.HYBRID_GBUFFER_DEPTH)), bits(other.read_forward(rr.FORWARD_DEPTH)))
+    assert gpu.gbuffer_raster_stats().covered_pixels == other.forward_stats().covered_pixels
+
+
+def test_near_plane_clips_what_the_cast_hits():
+    w, h = 32, 24
+    gpu, meshes, textures, view = _setup(near_wall_scene(w, h), w, h)
+    gpu.render_hybrid(view, rr.HYBRID_GBUFFER)
+    cast = gpu.read_hybrid(rr.HYBRID_POSITION)
+    assert np.allclose(cast[..., 2], -0.05, atol=1e-6) and (cast[..., 3] == 1).all(), "the cast hits the wall inside the near plane"
+    gpu.render_hybrid(view, RASTER)
+    ref = _check(gpu, meshes, textures, view)
+    pos = gpu.read_hybrid(rr.HYBRID_POSITION)
+    assert np.allclose(pos[..., 2], -5.0, atol=1e-4), "the raster sees the back wall"
+    assert (ref["depth"] < 1.0).all()
+
+
+def test_moved_instance_after_refit():
+    gpu, meshes, textures, view = _setup(synthetic_scene())
+    gpu.render_hybrid(view, RASTER)
+    w = rr.transform3x4((1.2, 0.6, 0.9), (-0.7, 1.1, 0.4), np.array([[0.8, 0.0, -0.6], [0.0, 1.0, 0.0], [0.6, 0.0, 0.8]], np.float32))
+    gpu.set_instance_transform(1, w)
+    meshes[1]["world"] = w.copy()
+    view.rebuild_tlas = 1
+    gpu.render_hybrid(view, RASTER)
+    _check(gpu, meshes, textures, view)
+
+
+def test_floor_beyond_the_guard_band():
+    cam = rr.camera.Camera((0.0, 2.0, 3.0), (0.0, 0.5, 0.0), 60.0, W / H, 0.3, 100000.0)
+    gpu, meshes, textures, view = _setup(_HugeFloor("huge_floor", [], [], cam, dict(sky_enabled=1)))
+    gpu.render_hybrid(view, RASTER)
+    ref = _check(gpu, meshes, textures, view)
+    assert len(ref["records"]) > 2 and (ref["visibility"] == 0).mean() > 0.3
+
+
+def _check_frame(gpu, meshes, view, mask, deferred=True):
+    """one call with `mask`, then hybrid_util.check_frame's assertions on the device's own raster G-buffer (the deferred pass only
+    without shadow maps and IBL, whose own suites cover those branches)"""
+    gpu.render_hybrid(view, mask)
+    g = gbuf(gpu)
+    sh, refl = gpu.read_hybrid(rr.HYBRID_SHADOWS), gpu.read_hybrid(rr.HYBRID_REFLECTIONS)
+    ss, d, p = gpu.read_hybrid(rr.HYBRID_SSAO_IMAGE), gpu.read_hybrid(rr.HYBRID_DEFERRED_OUTPUT), gpu.read_hybrid(rr.HYBRID_PRESENT_OUTPUT)
+    assert np.array_equal(ss, fr.ssao(g["position"], g["normal"], view)), "ssao"
+    geo = g["position"][..., 3] == 1.0
+    assert geo.any() and np.isfinite(d[geo]).all()
+    if deferred:
+        ref = fr.deferred(g, sh, refl, ss, view, meshes, [])
+        assert ulps(d[geo], ref[geo]).max() <= DEFERRED_ULP, "deferred"
+    sky = fr.sky(g["position"], view)
+    if sky and not view.cubemap_enabled:
+        ys, xs = np.array(list(sky)).T
+        want = np.array(list(sky.values()), np.float32)
+        assert (d[ys, xs, 3] == 1.0).all() and np.allclose(d[ys, xs, :3], want, rtol=1e-4, atol=1e-6), "sky"
+    assert np.array_equal(p, fr.present(d, view.fxaa_enabled == 1)), "present"
+    s = gpu.hybrid_frame_stats()
+    assert all(ms > 0 for ms in s.pass_ms) and s.sky_pixels == len(sky) == int((~geo).sum())
+
+
+@pytest.mark.parametrize("shadows,ibl", [(0, 0), (1, 0), (0, 1)])
+def test_whole_frame_on_the_raster_gbuffer(shadows, ibl):
+    scene = synthetic_scene()
+    gpu, meshes, textures, view = _setup(scene)
+    cpu = oa.OracleRenderer(W, H)
+    hr.upload_recorded(scene, cpu, False)
+    view.shadows_enabled = shadows
+    mask = rr.HYBRID_FRAME | rr.HYBRID_GBUFFER_RASTER
+    if shadows:
+        gpu.set_option("shadow_map_size", 512)
+        gpu.set_shadowmap_params(rr.shadow_cascades(scene.camera, view.sun_dir[:]))
+        mask |= rr.HYBRID_SHADOW_MAPS
+    if ibl:
+        view.ibl_enabled = view.cubemap_enabled = 1
+        gpu.render_hybrid(view, rr.HYBRID_ENVIRONMENT)
+    # this frame's shadows: the G-buffer first, then the ray-traced passes on it
+    gpu.render_hybrid(view, RASTER)
+    _check(gpu, meshes, textures, view)
+    gpu.render_hybrid(view, rr.HYBRID_RT_SHADOWS)
+    g = gbuf(gpu)
+    assert np.array_equal(gpu.read_hybrid(rr.HYBRID_SHADOWS), hr.shadows(cpu, g["position"], g["normal"], view))
+    if not ibl:
+        gpu.render_hybrid(view, rr.HYBRID_RT_REFLECTIONS)
+        want, kind = hr.reflections(cpu, meshes, g["position"], g["normal"], g["pbr"], view)
+        assert_reflections(gpu.read_hybrid(rr.HYBRID_REFLECTIONS), want, kind)
+    gpu.render_hybrid(view, mask)  # the steady state: rt_shadows reads the previous (rasterised) G-buffer
+    _check_frame(gpu, meshes, view, mask, deferred=not (shadows or ibl))
+    _check(gpu, meshes, textures, view)
+
+
+def test_marching_cubes_on_the_raster_depth():
+    scene = mc_scene(W, H)
+    gpu, meshes, textures, view = _setup(scene)
+    view.marching_cubes_enabled, view.time = 1, 5.0
+    gpu.render_hybrid(view, rr.HYBRID_FRAME | rr.HYBRID_GBUFFER_RASTER | rr.HYBRID_MARCHING_CUBES)
+    gdepth = gpu.read_hybrid(rr.HYBRID_GBUFFER_DEPTH)
+    depth, vis = gpu.read_hybrid(rr.HYBRID_DEPTH), gpu.read_hybrid(rr.HYBRID_MARCHING_CUBES_VISIBILITY)
+    pos, nrm = _extracted(view.time)
+    mesh = mr.pass_mesh(pos, nrm, meshes[0])
+    recs = fw.records_for([mesh], view, W, H)
+    rd, rv, _ = mr.resolve_seeded(recs, gdepth, W, H)
+    assert np.array_equal(vis, rv) and np.array_equal(bits(depth), bits(rd))
+    none = vis == mr.NONE
+    assert none.any() and (~none).any()
+    assert np.array_equal(bits(depth)[none], bits(gdepth)[none]), "the G-buffer's depth where no marching-cubes fragment survives"
+    # a marching-cubes call with no G-buffer pass still seeds from the rasterised G-buffer, not its own earlier output
+    gpu.render_hybrid(view, rr.HYBRID_MARCHING_CUBES)
+    assert np.array_equal(gpu.read_hybrid(rr.HYBRID_MARCHING_CUBES_VISIBILITY), rv)
+    assert np.array_equal(bits(gpu.read_hybrid(rr.HYBRID_DEPTH)), bits(rd))
+    # after a cast the seed is the reconstruction again
+    gpu.render_hybrid(view, rr.HYBRID_GBUFFER | rr.HYBRID_MARCHING_CUBES)
+    seed = mr.depth_seed(gpu.read_hybrid(rr.HYBRID_POSITION), view)
+    cd, cv, _ = mr.resolve_seeded(recs, seed, W, H)
+    assert np.array_equal(gpu.read_hybrid(rr.HYBRID_MARCHING_CUBES_VISIBILITY), cv)
+    assert np.array_equal(bits(gpu.read_hybrid(rr.HYBRID_DEPTH)), bits(cd))
+
+
+def _all(gpu):
+    return [gpu.read_hybrid(i) for i in range(9)]
+
+
+def test_refusals_and_reads_before_the_first_pass():
+    gpu, meshes, textures, view = _setup(synthetic_scene())
+    with pytest.raises(UtopianError, match="INVALID_ARGUMENT: uh_render_hybrid: UH_HYBRID_GBUFFER_RASTER without UH_HYBRID_GBUFFER"):
+        gpu.render_hybrid(view, rr.HYBRID_GBUFFER_RASTER)
+    with pytest.raises(UtopianError):
+        gpu.read_hybrid(rr.HYBRID_POSITION)  # nothing ran: not even the first call's allocation
+    gpu.render_hybrid(view, rr.HYBRID_FRAME)
+    before = _all(gpu)
+    for mask in (rr.HYBRID_GBUFFER_RASTER, rr.HYBRID_FRAME & ~rr.HYBRID_GBUFFER | rr.HYBRID_GBUFFER_RASTER):
+        with pytest.raises(UtopianError, match="INVALID_ARGUMENT"):
+            gpu.render_hybrid(view, mask)
+        assert all(np.array_equal(a, b) for a, b in zip(_all(gpu), before)), "every image unchanged"
+    for k in (rr.HYBRID_GBUFFER_DEPTH, rr.HYBRID_GBUFFER_VISIBILITY):
+        with pytest.raises(UtopianError, match="INVALID_ARGUMENT"):
+            gpu.read_hybrid(k)
+    s = gpu.gbuffer_raster_stats()
+    assert (s.pass_ms, s.renders, s.pieces, s.covered_pixels) == (0.0, 0, 0, 0)
+    not_built = rr.Renderer(W, H)
+    with pytest.raises(UtopianError, match="NOT_BUILT"):
+        not_built.render_hybrid(view, RASTER)
+
+
+def test_isolation_and_a_cast_after_a_raster_pass():
+    scene = synthetic_scene()
+    gpu, meshes, textures, view = _setup(scene)
+    loop = rr.FrameLoop(gpu, view)
+    loop.frame(rr.PASS_ALL)
+    acc, stats = gpu.read_accumulation(), gpu.get_stats()
+    gpu.render_forward(view, rr.FORWARD_PASS | rr.FORWARD_PRESENT)
+    fwd, fs = [gpu.read_forward(i) for i in range(4)], gpu.forward_stats()
+    gpu.render_hybrid(view, rr.HYBRID_FRAME | rr.HYBRID_GBUFFER_RASTER)
+    assert gpu.gbuffer_raster_stats().covered_pixels > 0
+    assert np.array_equal(gpu.read_accumulation(), acc) and gpu.get_stats().path_rays == stats.path_rays
+    assert all(np.array_equal(gpu.read_forward(i), a) for i, a in enumerate(fwd))
+    f2 = gpu.forward_stats()
+    assert (f2.renders, f2.pieces, f2.covered_pixels, list(f2.pass_ms)) == (fs.renders, fs.pieces, fs.covered_pixels, list(fs.pass_ms))
+    assert gpu.shadow_map_stats().renders == 0
+    # a cast after a rasterised pass equals the cast of a fresh context
+    gpu.render_hybrid(view, rr.HYBRID_GBUFFER)
+    fresh, _, _, _ = _setup(scene)
+    fresh.render_hybrid(view, rr.HYBRID_GBUFFER)
+    a, b = gbuf(gpu), gbuf(fresh)
+    assert all(np.array_equal(bits(a[k]) if a[k].dtype == np.float32 else a[k], bits(b[k]) if b[k].dtype == np.float32 else b[k]) for k in a)
+    assert gpu.hybrid_stats().rays[0] == W * H and gpu.gbuffer_raster_stats().pass_ms == 0.0
+
+
+def test_a_context_that_never_sets_the_bit_has_no_raster_state():
+    gpu, _, _, view = _setup(synthetic_scene())
+    for _ in range(2):
+        gpu.render_hybrid(view, rr.HYBRID_FRAME | (1 << 9))
+    for k in (rr.HYBRID_GBUFFER_DEPTH, rr.HYBRID_GBUFFER_VISIBILITY):
+        with pytest.raises(UtopianError, match="before the first rasterised G-buffer pass"):
+            gpu.read_hybrid(k)
+    s = gpu.gbuffer_raster_stats()
+    assert (s.pass_ms, s.renders, s.pieces, s.covered_pixels) == (0.0, 0, 0, 0)
+    assert gpu.hybrid_stats().rays[0] == W * H
+
+
+def test_cpp_mirror_renders_what_the_python_layer_renders(tmp_path):
+    exe = str(tmp_path / "gbuffer_raster_host")
+    libdir = os.path.dirname(rr.api.LIB_PATH)
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "cpp", "gbuffer_raster_host.cpp"), "-o", exe, "-L", libdir, "-lutopian_hip",
+                    f"-Wl,-rpath,{libdir}"], check=True)
+    meshes, view = cpp_scene(), cpp_view()
+    blob, out = tmp_path / "scene.blob", tmp_path / "out.bin"
+    write_blob(blob, meshes, view)
+    res = subprocess.run([exe, str(blob), str(out)], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stderr
+    r = rr.Renderer(CPP_W, CPP_H)
+    white = r.default_diffuse_map()
+    for vert, idx, kind, base in meshes:
+        r.add_mesh(vert, idx, rr.make_material(kind, 0.0, base, diffuse_map=white))
+    r.initialize_raytracing()
+    r.render_hybrid(view, RASTER)
+    order = (rr.HYBRID_POSITION, rr.HYBRID_NORMAL, rr.HYBRID_ALBEDO, rr.HYBRID_PBR, rr.HYBRID_GBUFFER_DEPTH, rr.HYBRID_GBUFFER_VISIBILITY)
+    assert np.fromfile(out, np.uint8).tobytes() == b"".join(r.read_hybrid(k).tobytes() for k in order)
+    s = r.gbuffer_raster_stats()
+    assert s.covered_pixels > 0 and f"renders {s.renders} pieces {s.pieces} covered {s.covered_pixels}" in res.stdout

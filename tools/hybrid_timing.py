@@ -17,10 +17,13 @@ what is timed:
   marching_cubes  the marching-cubes pass (UH_HYBRID_MARCHING_CUBES, marching_cubes_enabled = 1, view.time 5) in the whole frame,
           with shadows_enabled = 0 and 1 (maps rendered once): the pass's ms, its triangles, pieces and covered pixels, and the frame's
           passes beside it; then the same on a scene of one floor with the isosurface in full view
+  gbuffer_raster  the G-buffer pass rasterised (UH_HYBRID_GBUFFER | UH_HYBRID_GBUFFER_RASTER) alone, with its pieces and covered
+          pixels, beside the cast alone; then the whole frame (UH_HYBRID_FRAME, IBL and shadows off) with the rasterised and with the
+          cast G-buffer
 
 Run it under `rocprofv3 --kernel-trace --stats -- python tools/hybrid_timing.py --mode ...` for the kernel table.
 
-  python tools/hybrid_timing.py [--mode passes|frame|ibl|shadows|forward|marching_cubes --width 1920 --height 1080 --warmup 3 --iters 20 --lights 0,16,1024
+  python tools/hybrid_timing.py [--mode passes|frame|ibl|shadows|forward|marching_cubes|gbuffer_raster --width 1920 --height 1080 --warmup 3 --iters 20 --lights 0,16,1024
                                  --builds 5 --out FILE]"""
 import argparse
 import json
@@ -204,9 +207,27 @@ def marching_cubes(a):
     yield _mc_timed(a, r, view, "floor and isosurface")
 
 
+def gbuffer_raster(a):
+    scene, r, view = setup(a, 0, shadows_enabled=0, ibl_enabled=0, cubemap_enabled=0, num_lights=0)
+    for raster in (1, 0):
+        mask = rr.HYBRID_GBUFFER | (rr.HYBRID_GBUFFER_RASTER if raster else 0)
+        med, _ = timed(a, r, view, mask, rr.Renderer.hybrid_frame_stats)
+        line = dict(metric="hybrid_gbuffer", config=1, rasterised=bool(raster), width=a.width, height=a.height, iters=a.iters, gbuffer_ms=med[1],
+                    triangles=scene.num_triangles)
+        if raster:
+            s = r.gbuffer_raster_stats()
+            line.update(pieces=s.pieces, covered_pixels=s.covered_pixels)
+        yield line
+    for raster in (1, 0):
+        mask = rr.HYBRID_FRAME | (rr.HYBRID_GBUFFER_RASTER if raster else 0)
+        med, _ = timed(a, r, view, mask, rr.Renderer.hybrid_frame_stats)
+        yield dict(metric="hybrid_frame_full", config=1, lights=0, gbuffer_rasterised=bool(raster), width=a.width, height=a.height, iters=a.iters,
+                   **{f"{p}_ms": m for p, m in zip(PASSES, med)}, total_ms=sum(med))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("passes", "frame", "ibl", "shadows", "forward", "marching_cubes"), default="passes")
+    ap.add_argument("--mode", choices=("passes", "frame", "ibl", "shadows", "forward", "marching_cubes", "gbuffer_raster"), default="passes")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--warmup", type=int, default=3)
@@ -216,7 +237,8 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     lines = []
-    for out in {"passes": passes, "frame": frame, "ibl": ibl, "shadows": shadows, "forward": forward, "marching_cubes": marching_cubes}[a.mode](a):
+    for out in {"passes": passes, "frame": frame, "ibl": ibl, "shadows": shadows, "forward": forward, "marching_cubes": marching_cubes,
+                "gbuffer_raster": gbuffer_raster}[a.mode](a):
         lines.append(json.dumps(out))
         print(lines[-1], flush=True)
     if a.out:
