@@ -322,7 +322,7 @@ int uh_trace_any(uh_ctx* ctx, const float* rays, uint32_t n, uint8_t* out_occlud
 /* ---- stats / options ------------------------------------------------------------------- */
 int uh_get_stats(uh_ctx* ctx, UhStats* out);
 int uh_reset_stats(uh_ctx* ctx);
-/* The 25 options (DESIGN.md section 7 has the defaults and what was measured); unknown names return UH_ERR_INVALID_ARGUMENT.
+/* The 26 options (DESIGN.md section 7 has the defaults and what was measured); unknown names return UH_ERR_INVALID_ARGUMENT.
  *  diagnostics   "count_visits" (0/1: UhStats' node / triangle / cover counters), "time_kernels" (0/1: hipEvent time per kernel kind)
  *  results       "full_frame_restir" (0/1; 1 = documented divergence: the reservoir for every pixel instead of the reference's
  *                x > W/2 split), "furnace" (0/1: the reference's FURNACE_TEST build of the miss shader, reference.rmiss:14-28 - a path
@@ -339,7 +339,10 @@ int uh_reset_stats(uh_ctx* ctx);
  *                "sun_grid_force" (0/1: 1 = never refused for its worth - long lists, much of the surface handed to the tree), "sun_grid_inline_max_mb" (the lists a
  *                second time as 64-byte records that carry their triangle packet - one round trip per triangle test instead of two:
  *                budget in MB, -1 = default = four times the packet array, 0 = never), "sun_grid_coarse" (0..6, default 2: a cover
- *                depth per block of 4 x 4 cells, small enough to stay in the L2, asked before the cell's own record; 0: none)
+ *                depth per block of 4 x 4 cells, small enough to stay in the L2, asked before the cell's own record; 0: none),
+ *                "sun_verdicts" (0/1, default 1: with the grid in use and lights disabled the sun-ray kernels leave one verdict bit per
+ *                ray, and the kernels that read the path's radiance next add its throughput there - no read-modify-write of the
+ *                radiance in the sun kernels; 0: they add it themselves; same images)
  *  camera grid   "camera_grid" (0/1, default 1: the primary rays of a camera that has been the same for two consecutive frame calls -
  *                or for a call of 8 or more frames - go through a per-camera grid of packet lists, one cell per pixel, instead of
  *                the tree; same hit records bit for bit), "camera_grid_max_walk", "camera_grid_walk_whole",

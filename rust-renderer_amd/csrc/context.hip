@@ -105,6 +105,7 @@ struct Slot {
    hipEvent_t frame_start = nullptr, frame_stop = nullptr;
    DevBuf<float4> rec, radf, pixcol;  // rec: two sets of four path-state planes + the hit plane (device_types.h PathState)
    DevBuf<uint32_t> queues[5];
+   DevBuf<unsigned long long> sun_lit;  // the sun rays' verdicts: one bit per queue position (PathState::sun_lit)
    DevBuf<Control> control;
    PathState ps{};
    bool ready = false;
@@ -119,6 +120,7 @@ struct Slot {
          for (uint32_t r = 0; r < runs; r++) per_shard[shard_of_run(r)]++;
          for (uint32_t s = 0; s < kShards; s++) shard_cap = per_shard[s] * 64 > shard_cap ? per_shard[s] * 64 : shard_cap;
       }
+      if (shard_cap >= (1u << 31)) return hipErrorInvalidValue;  // a queue position's top bit carries the path's sun verdict (kernels.hip kSunLitBit)
       hipError_t e;
 #define SLOT_TRY(expr)                 \
    if ((e = (expr)) != hipSuccess) return e
@@ -138,6 +140,9 @@ struct Slot {
       // sharded queues: capacity per shard = the pixels (64-pixel runs) a shard can own
       // (the miss queue holds (position, id) pairs: twice the words)
       for (int qi = 0; qi < 5; qi++) SLOT_TRY(queues[qi].alloc((size_t)shard_cap * kShards * (qi == 4 ? 2 : 1)));
+      // shard_cap is a multiple of 64: a shard's segment is whole words. The sun kernels store every word the next kernels read
+      SLOT_TRY(sun_lit.alloc((size_t)shard_cap * kShards / 64));
+      SLOT_TRY(hipMemsetAsync(sun_lit.p, 0, sun_lit.n * sizeof(unsigned long long), stream));
       SLOT_TRY(control.alloc(1));
       SLOT_TRY(hipMemsetAsync(control.p, 0, sizeof(Control), stream));
       SLOT_TRY(hipStreamSynchronize(stream));
@@ -148,6 +153,7 @@ struct Slot {
       ps.radf = radf.p;
       ps.pixcol = pixcol.p;
       for (int i = 0; i < 5; i++) ps.queue[i] = queues[i].p;
+      ps.sun_lit = sun_lit.p;
       ps.shard_cap = shard_cap;
       ready = true;
       return hipSuccess;
@@ -159,6 +165,7 @@ struct Slot {
       radf.release();
       pixcol.release();
       for (auto& q : queues) q.release();
+      sun_lit.release();
       control.release();
       for (hipEvent_t* ev : {&ev_traced, &ev_missed, &ev_shaded, &ev_shadowed, &ev_side_done, &ev_acc, &frame_start, &frame_stop}) {
          if (*ev) (void)hipEventDestroy(*ev);
@@ -285,6 +292,7 @@ struct uh_ctx {
    // geometry has changed and then stayed put for two consecutive frames - a sun or an instance that moves every frame keeps
    // the tree walk.
    bool sun_grid_enabled = true;
+   bool sun_verdicts = true;        // option "sun_verdicts" (FrameParams::sun_verdicts)
    bool sun_valid = false;          // d_sun_* hold a usable grid for (sun_geom, sun_dir_built)
    bool sun_attempted = false;      // a build for (sun_geom, sun_dir_built) was tried (it may have been refused: sun_why)
    bool sun_have_pending = false;
@@ -1502,7 +1510,8 @@ static int ensure_camera_grid(uh_ctx* c, const FrameParams& fp, uint32_t batch) 
 }
 
 // reference_pt_pass of one frame on one slot (reference.rgen:22-145 as a kernel chain)
-static int enqueue_path_trace(uh_ctx* c, Slot& s, const FrameParams& fp) {
+static int enqueue_path_trace(uh_ctx* c, Slot& s, const FrameParams& frame) {
+   FrameParams fp = frame;  // + sun_verdicts, which follows the launches chosen below
    LaunchCfg lc = cfg(c);
    lc.stream = s.stream;
    if (fp.batch_frames == 1) {  // a lone frame's launches are small: fewer persistent waves reach the end of their tails sooner
@@ -1526,6 +1535,11 @@ static int enqueue_path_trace(uh_ctx* c, Slot& s, const FrameParams& fp) {
       const bool fused = c->fused_bounces && fp.batch_frames == 1 && fp.num_bounces >= 2 && fp.num_bounces <= 64 && s.ps.shard_cap < (1u << 23) &&
                          ((gpu_idle && fp.n_owned <= uh_ctx::kFusedMaxPaths) || c->fused_always);
       const bool fused_sun0 = fused && fp.sun_shadow_enabled == 1 && fp.lights_enabled != 1;  // bounce 0's sun rays inside the fused kernel too
+      // The sun rays leave verdicts, and the kernels that read a path's radiance next add its throughput (option "sun_verdicts") - when
+      // the grid serves them (the tree walk of every sun ray keeps the read-modify-write: a plane to clear and an atomic per lit ray
+      // otherwise), when no light ray adds to the same radiance behind them (the reference adds the sun's term first, rgen:63-122, and
+      // float addition does not commute bit for bit) and when the wavefront runs every bounce (the fused kernel adds its own terms)
+      fp.sun_verdicts = (c->sun_verdicts && c->sun_this_frame && fp.sun_shadow_enabled == 1 && fp.lights_enabled != 1 && !fused) ? 1u : 0u;
       for (uint32_t b = 0; b < (fused ? 1u : fp.num_bounces); b++) {
          begin_timed(c, (b == 0 && c->cam_this_frame) ? 3 : 0, s.stream);
          if (b == 0 && c->cam_this_frame) {
@@ -2186,7 +2200,11 @@ int uh_set_option(uh_ctx* c, const char* name, int value) {
       if (!range(-1, 1 << 20)) return bad("must be -1 (auto: 4 x the packet array), 0 (off) .. 1048576");
       c->sun_inline_max_mb = value;
       c->sun_attempted = false;
-   } else if (n == "sun_grid_coarse") {
+   } else if (n == "sun_verdicts")
+      // 1: the grid's sun kernels leave one bit per ray and the next shading kernel (or the flush) adds the lit paths' throughput to
+      // their radiance; 0: the sun kernels add it themselves. Same images; frames with lights enabled always take the second form
+      c->sun_verdicts = value != 0;
+   else if (n == "sun_grid_coarse") {
       // the coarse cover (sun_grid.h): one depth per block of 2^value x 2^value cells, asked before the cell's own record; 0: none
       if (!range(0, 6)) return bad("(log2 of the block edge in cells) must be 0..6");
       c->sun_coarse_shift = (uint32_t)value;

@@ -121,6 +121,10 @@ struct FrameParams {
    // k_generate only fills the ray queue with path ids, and every kernel of bounce 0 computes a path's origin, direction,
    // throughput (1) and RNG words from its id (device_math.h primary_state): 48 bytes less written and 96 less read per path
    uint32_t primary_implicit;
+   // option "sun_verdicts" (set per sample pass where the launches are chosen, context.hip enqueue_path_trace): 1 = the sun kernels of
+   // this pass leave one verdict bit per ray in PathState::sun_lit and the kernels that read a path's radiance next add its throughput
+   // there; 0 = the sun kernels add it themselves (lights enabled, no grid for the bounce, the fused kernel's frames, the option off)
+   uint32_t sun_verdicts;
    uint32_t furnace;  // option "furnace": the reference's FURNACE_TEST build of the miss shader (reference.rmiss:14-28): a miss returns white
    uint32_t num_lights_used;  // min(view.num_lights, view.max_num_lights_used)
    uint32_t temporal_enabled, spatial_enabled;
@@ -145,7 +149,7 @@ struct FrameParams {
 //   plane 0  ray origin.xyz            | raygen rngState (bits)            reference.rgen:24,31
 //   plane 1  ray direction.xyz         | rayPayload.randomSeed (bits)      un-normalised direction (rgen:61); seed: rgen:30, rchit:91
 //   plane 2  throughput.rgb            | light weight f                    radiance += throughput * f when the light is visible (rgen:121)
-//   plane 3  radiance.rgb              | light index (bits)                rgen:69-78, :118-122 add to it; not materialised for bounce 0 (it is zero)
+//   plane 3  radiance.rgb              | light index (bits)                rgen:69-78, :118-122 add to it; not materialised for bounce 0 (it is zero), nor - with sun verdicts - for bounce 1
 // The hit record of a bounce's ray (t, u, v | packet index, 0xffffffff = miss) lies in a plane of its own at the same position.
 constexpr uint32_t kRecQuads = 4;
 enum { REC_ORIGIN = 0, REC_DIR = 1, REC_THR = 2, REC_RAD = 3 };
@@ -161,6 +165,10 @@ struct PathState {
    // 0,1 = ray ping-pong: path ids; 2 = light, 3 = sun rays for the tree walk: positions in the NEXT bounce's ray queue; 4 = misses:
    // (position in the CURRENT one, id) pairs; each kShards * shard_cap entries
    uint32_t* queue[5];
+   // the sun rays' verdicts (FrameParams::sun_verdicts): bit p & 63 of word p >> 6 = the sun ray that left position p of the NEXT bounce's
+   // ray queue was not occluded. Shard segments start at multiples of 64, so the 64 positions a wave reads in one piece are one word.
+   // One plane: the verdicts of bounce b are read by k_shade_hit(b + 1) (or the flush), which the sun kernels of bounce b + 1 wait for
+   unsigned long long* sun_lit;
    uint32_t shard_cap;  // entries per shard segment = pixels a shard can own (multiple of 64)
 };
 __host__ __device__ inline float4* rec_quad(const PathRecs& rec, uint32_t pos, int quad) { return rec.base + rec.plane * (size_t)quad + pos; }

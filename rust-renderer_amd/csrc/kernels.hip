@@ -537,41 +537,61 @@ __global__ __launch_bounds__(kBlock, 6) void k_trace_closest(SceneDev sc, bool s
 // An unoccluded ray adds its path's throughput (x light weight) to the path's radiance (rgen:69-78 / :118-122).
 // ------------------------------------------------------------------------------------------
 struct ShadowRay {
-   float4 ro, rd, lit;  // origin / direction (tmin, tmax in w) and the radiance record the path gets if the ray is unoccluded
+   float4 ro, rd;  // origin / direction (tmin, tmax in w)
    float tlimit;
 };
+// light_bits: the path's light index (radiance.w), read by a light ray only
 template <bool LIGHT>
-__device__ __forceinline__ ShadowRay make_shadow_ray(const SceneDev& sc, const FrameParams& fp, float4 ro, float4 thr, float4 rad) {
+__device__ __forceinline__ ShadowRay make_shadow_ray(const SceneDev& sc, const FrameParams& fp, float4 ro, uint32_t light_bits) {
    ShadowRay s;
    s.ro = make_float4(ro.x, ro.y, ro.z, 0.001f);
    s.tlimit = INFINITY;
    if (LIGHT) {
-      const int light_index = (int)__float_as_uint(rad.w);
+      const int light_index = (int)light_bits;
       V3 lpos = v3(0, 0, 0);
       if (light_index >= 0 && (uint32_t)light_index < sc.num_lights) lpos = xyz(sc.lights[2 * light_index]);
       const V3 o = v3(ro.x, ro.y, ro.z);
       const V3 dir = normalize3(lpos - o);  // rgen:113
       s.tlimit = length3(lpos - o);         // rgen:114
-      const float f = thr.w;
-      s.lit = make_float4(rad.x + thr.x * f, rad.y + thr.y * f, rad.z + thr.z * f, rad.w);
       s.rd = make_float4(dir.x, dir.y, dir.z, 10000.0f);
    } else {
-      s.lit = make_float4(rad.x + thr.x, rad.y + thr.y, rad.z + thr.z, rad.w);
       s.rd = make_float4(fp.sun_dir[0], fp.sun_dir[1], fp.sun_dir[2], 10000.0f);  // rgen:64
    }
    return s;
 }
+// the radiance record the path gets if its shadow ray is unoccluded (rgen:69-78 / :118-122)
+template <bool LIGHT>
+__device__ __forceinline__ float4 shadow_lit(float4 thr, float4 rad) {
+   if (LIGHT) {
+      const float f = thr.w;
+      return make_float4(rad.x + thr.x * f, rad.y + thr.y * f, rad.z + thr.z * f, rad.w);
+   }
+   return make_float4(rad.x + thr.x, rad.y + thr.y, rad.z + thr.z, rad.w);
+}
+// The sun rays' verdicts (PathState::sun_lit, FrameParams::sun_verdicts). A sun ray is a predicate: with verdicts its kernels leave one
+// bit per ray and touch the path state through the origin plane alone; k_shade_hit(b + 1), the miss shading and k_flush_survivors -
+// which read the path's throughput and radiance next anyway - add the throughput where they hold both, with shadow_lit's expression.
+__device__ __forceinline__ unsigned long long* sun_lit_word(const PathState& ps, uint32_t pos) { return ps.sun_lit + (pos >> 6); }
+// Is the radiance of the paths of bounce b's queue materialised? Never for bounce 0 (it is zero). With verdicts not for bounce 1
+// either: nothing adds to a path's radiance before k_shade_hit(1) (or the miss shading, or the flush) reads it - they start from
+// 0.0f and add the lit paths' throughput, the very words the stored zero would have given.
+__device__ __forceinline__ bool rad_stored(const FrameParams& fp, uint32_t b) { return b > fp.sun_verdicts; }
+constexpr uint32_t kSunLitBit = 0x80000000u;  // the verdict beside a queue position (k_shade_hit's lists, Q_MISS): positions stay below 2^31
 
 // leftovers (sun rays only): the rays k_trace_sun_grid could not serve from its grid (queue 3); they are already counted
-template <bool COUNT, bool LIGHT>
+// VERDICT (sun leftovers only): behind a grid kernel that left verdicts, an unoccluded ray sets its bit in the word the grid kernel
+// stored (same stream, so the word is there) - the pool carries the origin alone
+template <bool COUNT, bool LIGHT, bool VERDICT = false>
 __global__ __launch_bounds__(kBlock, 5) void k_trace_shadow(SceneDev sc, FrameParams fp, PathState ps, Control* ctl, DeviceStats* stats, uint32_t bounce,
                                                               uint32_t cursor_slot, bool leftovers) {
    __shared__ uint32_t s_stack[kWavesPerBlock][kLdsStack][64];
-   __shared__ RayPool<3> s_pool[kWavesPerBlock];
+   static_assert(!(VERDICT && LIGHT), "verdicts are the sun rays'");
+   constexpr int NA = VERDICT ? 1 : 3;
+   __shared__ RayPool<NA> s_pool[kWavesPerBlock];
    const uint32_t lane = lane_id();
    const uint32_t wave = threadIdx.x >> 6;
    uint32_t* lds_col = &s_stack[wave][0][lane];
-   RayPool<3>& pool = s_pool[wave];
+   RayPool<NA>& pool = s_pool[wave];
    const ShardCtx sx = shard_ctx();
    const uint32_t seg = sx.shard * ps.shard_cap;
    RaySource src;
@@ -590,7 +610,7 @@ __global__ __launch_bounds__(kBlock, 5) void k_trace_shadow(SceneDev sc, FramePa
    const PathRecs rec = ps.set[(bounce + 1) & 1];  // the state of the scattered paths, at their positions in the next bounce's queue
    float4* rad = rec_quad(rec, seg, REC_RAD);
    auto source_of = [&](int a, uint32_t pos) { return (const float4*)rec_quad(rec, seg + pos, a == 0 ? REC_ORIGIN : a == 1 ? REC_THR : REC_RAD); };
-   Feeder<3> f;
+   Feeder<NA> f;
    Trav t;
    t.cur = kEmptyRef;
    t.sp = 0;
@@ -599,14 +619,25 @@ __global__ __launch_bounds__(kBlock, 5) void k_trace_shadow(SceneDev sc, FramePa
    uint32_t spill[kSpillStack];
    auto take = [&](uint32_t slot) {
       id = pool.id[slot];
-      const ShadowRay s = make_shadow_ray<LIGHT>(sc, fp, pool.v[0][slot], pool.v[1][slot], pool.v[2][slot]);
-      lit = s.lit;
+      ShadowRay s;
+      if constexpr (VERDICT) {
+         s = make_shadow_ray<false>(sc, fp, pool.v[0][slot], 0u);
+      } else {
+         const float4 thr = pool.v[1][slot], r4 = pool.v[2][slot];
+         s = make_shadow_ray<LIGHT>(sc, fp, pool.v[0][slot], __float_as_uint(r4.w));
+         lit = shadow_lit<LIGHT>(thr, r4);
+      }
       trav_init(t, s.ro, s.rd, s.ro.w, s.rd.w, s.tlimit);
    };
-   while (refill_lanes<3>(f, src, pool, t.cur == kEmptyRef, source_of, take)) {
+   while (refill_lanes<NA>(f, src, pool, t.cur == kEmptyRef, source_of, take)) {
       if (t.cur != kEmptyRef) {
          bool occluded = false;
-         if (trav_step<true, COUNT>(nodes, tris, t, lds_col, spill, occluded, n_nodes, n_tris) && !occluded) st_stream(rad + id, lit);
+         if (trav_step<true, COUNT>(nodes, tris, t, lds_col, spill, occluded, n_nodes, n_tris) && !occluded) {
+            if constexpr (VERDICT)
+               atomicOr(sun_lit_word(ps, seg + id), 1ull << (id & 63u));  // no-return: nothing waits for it
+            else
+               st_stream(rad + id, lit);
+         }
       }
    }
    if (COUNT) {
@@ -655,7 +686,8 @@ __device__ __forceinline__ bool sun_coarse_covered(float coarse, float pw) { ret
 // Every position of the next bounce's ray queue is a ray; the coarse cover - when the grid has one - is asked first. (Round 4 also had
 // k_shade_hit ask the coarse cover and list the rays it did not answer - level on the frame - and a one-ray-per-lane loop for the plain
 // lists: both removed in round 5.)
-template <bool COUNT, bool INLINE>
+// VERDICT: the kernel leaves one bit per ray (lit or not) instead of adding the lit rays' throughput to their radiance - see sun_lit_word
+template <bool COUNT, bool INLINE, bool VERDICT>
 __global__ __launch_bounds__(kBlock) void k_trace_sun_grid(SceneDev sc, FrameParams fp, PathState ps, Control* ctl, DeviceStats* stats, uint32_t bounce,
                                                             uint32_t cursor_slot, SunGridDev g) {
    const uint32_t lane = lane_id();
@@ -819,18 +851,29 @@ __global__ __launch_bounds__(kBlock) void k_trace_sun_grid(SceneDev sc, FramePar
             lit[k] = !occluded;
          }
       });
-      float4 thr[K], rad[K];
-      static_for<K>([&](auto kc) {
-         constexpr int k = decltype(kc)::value;
-         if (lit[k]) {  // rgen:69-78: radiance += throughput
-            thr[k] = ld_rec(rec_quad(rec, seg + id[k], REC_THR));
-            rad[k] = ld_rec(rec_quad(rec, seg + id[k], REC_RAD));
-         }
-      });
-      static_for<K>([&](auto kc) {
-         constexpr int k = decltype(kc)::value;
-         if (lit[k]) st_rec(rec_quad(rec, seg + id[k], REC_RAD), make_float4(rad[k].x + thr[k].x, rad[k].y + thr[k].y, rad[k].z + thr[k].z, rad[k].w));
-      });
+      if constexpr (VERDICT) {
+         // lane l of sub-chunk k holds position base + 64 k + l (the cursor starts at 0 and moves by 64 K; segments start at multiples
+         // of 64): the ballot is that run's verdict word. Deferred rays and lanes beyond the count contribute 0 - the leftover kernel
+         // sets the bits of the deferred rays it finds lit. Every word below the count is stored, so the plane needs no clearing.
+         static_for<K>([&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            const unsigned long long word = __ballot(lit[k]);
+            if (lane == 0 && base + 64u * k < count) *sun_lit_word(ps, seg + base + 64u * k) = word;
+         });
+      } else {
+         float4 thr[K], rad[K];
+         static_for<K>([&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            if (lit[k]) {  // rgen:69-78: radiance += throughput
+               thr[k] = ld_rec(rec_quad(rec, seg + id[k], REC_THR));
+               rad[k] = ld_rec(rec_quad(rec, seg + id[k], REC_RAD));
+            }
+         });
+         static_for<K>([&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            if (lit[k]) st_rec(rec_quad(rec, seg + id[k], REC_RAD), shadow_lit<false>(thr[k], rad[k]));
+         });
+      }
       static_for<K>([&](auto kc) {
          constexpr int k = decltype(kc)::value;
          if (__ballot(defer[k]) != 0ull) {  // wave-uniform: every lane of the wave takes part in the append
@@ -1039,8 +1082,9 @@ __global__ __launch_bounds__(kBlock) void k_generate(FrameParams fp, PathState p
 // runs on 64 of them at a time with every lane live.
 // ------------------------------------------------------------------------------------------
 // pos: the path's position in the bounce's ray queue (shard segment included), id: its path id. The path ends here: its radiance
-// goes to the per-id array, with the raygen's RNG word (the frame's next sample starts from it, rgen:28-31)
-__device__ __forceinline__ void shade_miss_path(const FrameParams& fp, const PathState& ps, uint32_t pos, uint32_t id, uint32_t bounce) {
+// goes to the per-id array, with the raygen's RNG word (the frame's next sample starts from it, rgen:28-31).
+// sun_lit: the verdict of the sun ray the path cast when it scattered, not yet added to its radiance (FrameParams::sun_verdicts)
+__device__ __forceinline__ void shade_miss_path(const FrameParams& fp, const PathState& ps, uint32_t pos, uint32_t id, uint32_t bounce, bool sun_lit) {
    const PathRecs rec = ps.set[bounce & 1];
    const bool implicit = bounce == 0 && fp.primary_implicit;  // origin and throughput of a primary ray: not stored (FrameParams)
    float4 ro, rd_implicit = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -1059,14 +1103,15 @@ __device__ __forceinline__ void shade_miss_path(const FrameParams& fp, const Pat
    float4 thr = make_float4(1.0f, 1.0f, 1.0f, 0.0f);  // rgen:39
    if (!implicit) thr = ld_rec(rec_quad(rec, pos, REC_THR));
    float4 rad = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-   if (bounce != 0) rad = ld_rec(rec_quad(rec, pos, REC_RAD));
+   if (rad_stored(fp, bounce)) rad = ld_rec(rec_quad(rec, pos, REC_RAD));
+   if (sun_lit) rad = shadow_lit<false>(thr, rad);                           // rgen:69-78, of the bounce before
    V3 t = v3(thr.x, thr.y, thr.z) * sky_color;                               // rgen:48
    st_stream(ps.radf + id, make_float4(rad.x + t.x, rad.y + t.y, rad.z + t.z, ro.w));   // rgen:55
 }
 
 // The bounce's misses arrive as a queue of their own (Q_MISS), written by k_shade_hit while it classifies the bounce's RAY
 // queue: every lane has a path, no hit record is read here, and nothing but the sky integral (~600 VALU instructions per
-// path) and four 16-byte records per path is left in the kernel.
+// path) and four 16-byte records per path is left in the kernel. The position's top bit is the path's sun verdict (kSunLitBit).
 __global__ __launch_bounds__(kBlock) void k_shade_miss(FrameParams fp, PathState ps, Control* ctl, DeviceStats* stats, uint32_t bounce) {
    const ShardCtx sx = shard_ctx();
    const uint32_t seg = sx.shard * ps.shard_cap;
@@ -1074,7 +1119,7 @@ __global__ __launch_bounds__(kBlock) void k_shade_miss(FrameParams fp, PathState
    const uint32_t count = ctl->q_count[qc_index(bounce, Q_MISS, sx.shard)];
    for (uint32_t i = sx.lb * kBlock + threadIdx.x; i < count; i += sx.nb * kBlock) {
       const uint2 e = ld_stream(queue + i);
-      shade_miss_path(fp, ps, seg + e.x, e.y, bounce);
+      shade_miss_path(fp, ps, seg + (e.x & ~kSunLitBit), e.y, bounce, (e.x & kSunLitBit) != 0u);
    }
    if (sx.lb == 0 && threadIdx.x == 0 && count) atomicAdd(&stats->misses, (unsigned long long)count);
 }
@@ -1245,8 +1290,10 @@ __global__ __launch_bounds__(kBlock, kShadeHitBlocks) void k_shade_hit(FramePara
    const uint32_t rounds = (count + stride - 1) / stride;
    uint32_t n_hits = 0;
    // one path per lane: `valid` lanes shade their hit; every lane of the wave takes part in the queue appends.
-   // pos: the path's position in this bounce's queue (without the shard segment)
-   auto shade = [&](uint32_t id, uint32_t pos, float4 hr, bool valid) {
+   // pos: the path's position in this bounce's queue (without the shard segment); its top bit: the path's sun verdict (kSunLitBit)
+   auto shade = [&](uint32_t id, uint32_t pos_lit, float4 hr, bool valid) {
+      const uint32_t pos = pos_lit & ~kSunLitBit;
+      const bool sun_lit = (pos_lit & kSunLitBit) != 0u;
       const uint32_t pk = __float_as_uint(hr.w);
       bool scattered = false, want_light = false;
       uint32_t slot = 0;        // the scattered path's position in the next bounce's queue
@@ -1267,7 +1314,7 @@ __global__ __launch_bounds__(kBlock, kShadeHitBlocks) void k_shade_hit(FramePara
          }
          uint2 rng = make_uint2(__float_as_uint(ro.w), __float_as_uint(rd.w));
          float4 rad4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // radiance so far: zero before the first bounce (not materialised)
-         if (bounce != 0) rad4 = ld_rec(rec_quad(cur, seg + pos, REC_RAD));  // (the compiler waits for it on the spot: measured level with an unconditional read, which costs 16 bytes per hit at bounce 0)
+         if (rad_stored(fp, bounce)) rad4 = ld_rec(rec_quad(cur, seg + pos, REC_RAD));  // (the compiler waits for it on the spot: measured level with an unconditional read, which costs 16 bytes per hit at bounce 0)
          const V3 ray_dir = v3(rd.x, rd.y, rd.z);
          const float t = hr.x, bu = hr.y, bv = hr.z;
          const float4* sp = sc.shade + 4 * (size_t)pk;  // pk = hr.w, known since the classification: no wait for hr before these
@@ -1282,6 +1329,7 @@ __global__ __launch_bounds__(kBlock, kShadeHitBlocks) void k_shade_hit(FramePara
          surface_normal_uv(s0, s1, s2, s3, bu, bv, normal, uu, vv);                    // rchit:30-31, :39
          // keeps the compiler from sinking the early loads to their first use
          asm volatile("" : "+v"(rng.x), "+v"(rng.y), "+v"(thr4.x), "+v"(thr4.y), "+v"(thr4.z), "+v"(rad4.x), "+v"(rad4.y), "+v"(rad4.z));
+         if (sun_lit) rad4 = shadow_lit<false>(thr4, rad4);  // rgen:69-78 of the bounce before: its sun ray left a verdict, the records are here
          const V3 world_normal = world_normal_of(ms, normal, ray_dir);                 // rchit:32-37
          // where the path goes on from (and its sun ray starts): needs nothing the texels bring
          V3 origin = v3(ro.x, ro.y, ro.z) + t * ray_dir;                               // rgen:59
@@ -1334,7 +1382,7 @@ __global__ __launch_bounds__(kBlock, kShadeHitBlocks) void k_shade_hit(FramePara
          st_rec(rec_quad(nxt, seg + slot, REC_ORIGIN), n_o);
          if (bounce + 1 < fp.num_bounces) st_rec(rec_quad(nxt, seg + slot, REC_DIR), n_d);  // (after the last bounce no ray is traced: k_flush_survivors reads radiance and the raygen RNG word)
          st_rec(rec_quad(nxt, seg + slot, REC_THR), n_t);
-         st_rec(rec_quad(nxt, seg + slot, REC_RAD), n_r);
+         if (rad_stored(fp, bounce + 1)) st_rec(rec_quad(nxt, seg + slot, REC_RAD), n_r);
       }
       if (want_light) st_stream(q_light + lslot, slot);  // the light ray leaves from the path's new position
    };
@@ -1345,6 +1393,8 @@ __global__ __launch_bounds__(kBlock, kShadeHitBlocks) void k_shade_hit(FramePara
    uint32_t(*missed)[128] = s_miss[threadIdx.x >> 6];  // [0] positions, [1] ids
    const uint32_t lane = lane_id();
    uint32_t n_list = 0, n_missed = 0;  // wave-uniform
+   // the sun rays of the bounce before left verdicts, one bit per position of this queue: a wave's 64 entries are one aligned word
+   const bool verdicts = bounce != 0 && fp.sun_verdicts != 0;
    // `n` entries from the front of the wave's miss list go to the bounce's miss queue (one atomic per call)
    auto flush_misses = [&](uint32_t n) {
       uint32_t base = 0;
@@ -1363,13 +1413,18 @@ __global__ __launch_bounds__(kBlock, kShadeHitBlocks) void k_shade_hit(FramePara
          // traversal kernel left it at the ray's queue position: the wave reads 1 KiB in one piece
          hr = ld_rec(ps.hit + seg + i);
       }
+      uint32_t i_lit = i;  // the position with the path's verdict beside it
+      if (verdicts) {
+         const uint32_t i0 = __builtin_amdgcn_readfirstlane(i - lane);  // wave-uniform: one load for the wave
+         if (i0 < count && ((*sun_lit_word(ps, seg + i0) >> lane) & 1ull)) i_lit |= kSunLitBit;
+      }
       const bool is_hit = __float_as_uint(hr.w) != kEmptyRef;
       const unsigned long long mask = __ballot(is_hit);
       const unsigned long long mmask = __ballot(i < count && !is_hit);
       if (mmask) {
          const uint32_t mp = __builtin_amdgcn_mbcnt_hi((uint32_t)(mmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mmask, 0u));
          if (i < count && !is_hit) {
-            missed[0][n_missed + mp] = i;
+            missed[0][n_missed + mp] = i_lit;
             missed[1][n_missed + mp] = id;
          }
          n_missed += (uint32_t)__popcll(mmask);
@@ -1395,7 +1450,7 @@ __global__ __launch_bounds__(kBlock, kShadeHitBlocks) void k_shade_hit(FramePara
       const uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
       if (is_hit) {
          list[0][n_list + prefix] = id;
-         list[1][n_list + prefix] = i;
+         list[1][n_list + prefix] = i_lit;
          list[2][n_list + prefix] = __float_as_uint(hr.x);
          list[3][n_list + prefix] = __float_as_uint(hr.y);
          list[4][n_list + prefix] = __float_as_uint(hr.z);
@@ -1430,7 +1485,8 @@ __global__ __launch_bounds__(kBlock, kShadeHitBlocks) void k_shade_hit(FramePara
 
 // The paths still alive after the last bounce (the ray queue shade_hit(num_bounces - 1) built): their radiance - with what the
 // last bounce's shadow rays added - and their raygen RNG word go to the per-id array k_finish_sample and the next sample's
-// k_generate read (rgen:127, :28-31). Dense reads by queue position, one 16-byte store per surviving path.
+// k_generate read (rgen:127, :28-31). Dense reads by queue position, one 16-byte store per surviving path. With sun verdicts the
+// last bounce's sun term is added here: one word per wave, and the throughput of the lit survivors.
 __global__ __launch_bounds__(kBlock) void k_flush_survivors(FrameParams fp, PathState ps, Control* ctl) {
    const ShardCtx sx = shard_ctx();
    const uint32_t seg = sx.shard * ps.shard_cap, b = fp.num_bounces;
@@ -1439,7 +1495,13 @@ __global__ __launch_bounds__(kBlock) void k_flush_survivors(FrameParams fp, Path
    const PathRecs rec = ps.set[b & 1];
    for (uint32_t i = sx.lb * kBlock + threadIdx.x; i < count; i += sx.nb * kBlock) {
       const uint32_t id = ld_stream(queue + i);
-      const float4 rad = ld_rec(rec_quad(rec, seg + i, REC_RAD)), ro = ld_rec(rec_quad(rec, seg + i, REC_ORIGIN));
+      float4 rad = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (rad_stored(fp, b)) rad = ld_rec(rec_quad(rec, seg + i, REC_RAD));
+      const float4 ro = ld_rec(rec_quad(rec, seg + i, REC_ORIGIN));
+      if (fp.sun_verdicts) {
+         const uint32_t i0 = __builtin_amdgcn_readfirstlane(i - lane_id());  // (the first active lane's: lanes hold consecutive positions)
+         if ((*sun_lit_word(ps, seg + i0) >> lane_id()) & 1ull) rad = shadow_lit<false>(ld_rec(rec_quad(rec, seg + i, REC_THR)), rad);
+      }
       st_stream(ps.radf + id, make_float4(rad.x, rad.y, rad.z, ro.w));
    }
 }
@@ -1650,12 +1712,12 @@ __global__ __launch_bounds__(kBlock, kFusedBlocks) void k_path_fused(SceneDev sc
          const float4 o4 = make_float4(t.o.x, t.o.y, t.o.z, 0.0f);
          if (entry & kSun) {
             entry &= ~kSun;
-            const ShadowRay s = make_shadow_ray<false>(sc, fp, o4, make_float4(thr.x, thr.y, thr.z, lf), make_float4(rad.x, rad.y, rad.z, 0.0f));
+            const ShadowRay s = make_shadow_ray<false>(sc, fp, o4, 0u);
             trav_init(t, s.ro, s.rd, s.ro.w, s.rd.w, s.tlimit);
             kind = SUN_RAY;
          } else if (entry & kLight) {
             entry &= ~kLight;
-            const ShadowRay s = make_shadow_ray<true>(sc, fp, o4, make_float4(thr.x, thr.y, thr.z, lf), make_float4(rad.x, rad.y, rad.z, __uint_as_float(light_bits)));
+            const ShadowRay s = make_shadow_ray<true>(sc, fp, o4, light_bits);
             trav_init(t, s.ro, s.rd, s.ro.w, s.rd.w, s.tlimit);
             kind = LIGHT_RAY;
          } else {
@@ -1812,7 +1874,7 @@ __global__ __launch_bounds__(kBlock, kFusedBlocks) void k_path_fused(SceneDev sc
       // reference.rmiss for `n` paths from the front of the wave's miss list: their state is where shade_miss_path reads it (their
       // records of set 1, untouched since their ray was made)
       auto flush_misses = [&](uint32_t n) {
-         if (lane < n) shade_miss_path(fp, ps, seg + missed[0][lane], missed[1][lane], kFirst);
+         if (lane < n) shade_miss_path(fp, ps, seg + missed[0][lane], missed[1][lane], kFirst, false);  // (the kernel adds its sun terms itself)
          w_miss += n;
       };
       auto entry_of = [&](uint32_t k) { return make_float4(__uint_as_float(list[2][k]), __uint_as_float(list[3][k]), __uint_as_float(list[4][k]), __uint_as_float(list[5][k])); };
@@ -1932,7 +1994,7 @@ __global__ __launch_bounds__(kBlock, kFusedBlocks) void k_path_fused(SceneDev sc
       __syncthreads();
    }
    if (carry_n) {  // the last misses: reference.rmiss on a partial wave, once
-      if (lane < carry_n) shade_miss_path(fp, ps, seg + carry_pos, carry_id, kFirst);
+      if (lane < carry_n) shade_miss_path(fp, ps, seg + carry_pos, carry_id, kFirst, false);
       w_miss += carry_n;
    }
    if (lane == 0) {
@@ -2293,14 +2355,18 @@ void launch_path_fused(const LaunchCfg& c, const FrameParams& fp, const SceneDev
 
 void launch_trace_shadow(const LaunchCfg& c, const FrameParams& fp, const SceneDev& sc, const PathState& ps, Control* ctl, DeviceStats* stats,
                          uint32_t bounce, uint32_t cursor_slot, bool light, bool sun_leftovers) {
-   // sun_leftovers: what the sun grid handed to the tree (queue 3)
-#define UH_SHADOW(COUNT, LIGHT) k_trace_shadow<COUNT, LIGHT><<<shadow_grid(c), kBlock, 0, c.stream>>>(sc, fp, ps, ctl, stats, bounce, cursor_slot, sun_leftovers)
-   if (light) {
-      if (c.count_visits) UH_SHADOW(true, true);
-      else UH_SHADOW(false, true);
+   // sun_leftovers: what the sun grid handed to the tree (queue 3); behind a grid kernel that left verdicts they set their bits
+#define UH_SHADOW(COUNT, LIGHT, VERDICT) \
+   k_trace_shadow<COUNT, LIGHT, VERDICT><<<shadow_grid(c), kBlock, 0, c.stream>>>(sc, fp, ps, ctl, stats, bounce, cursor_slot, sun_leftovers)
+   if (!light && sun_leftovers && fp.sun_verdicts) {
+      if (c.count_visits) UH_SHADOW(true, false, true);
+      else UH_SHADOW(false, false, true);
+   } else if (light) {
+      if (c.count_visits) UH_SHADOW(true, true, false);
+      else UH_SHADOW(false, true, false);
    } else {
-      if (c.count_visits) UH_SHADOW(true, false);
-      else UH_SHADOW(false, false);
+      if (c.count_visits) UH_SHADOW(true, false, false);
+      else UH_SHADOW(false, false, false);
    }
 #undef UH_SHADOW
 }
@@ -2308,13 +2374,15 @@ void launch_trace_shadow(const LaunchCfg& c, const FrameParams& fp, const SceneD
 void launch_trace_sun_grid(const LaunchCfg& c, const FrameParams& fp, const SceneDev& sc, const PathState& ps, Control* ctl, DeviceStats* stats, uint32_t bounce,
                            uint32_t cursor_slot, const SunGridDev& g) {
    const dim3 grid = sharded_grid(c.num_cus * 8);
-#define UH_SUN_GRID(COUNT, INLINE) k_trace_sun_grid<COUNT, INLINE><<<grid, kBlock, 0, c.stream>>>(sc, fp, ps, ctl, stats, bounce, cursor_slot, g)
+#define UH_SUN_GRID(COUNT, INLINE)                                                                                                      \
+   if (fp.sun_verdicts) k_trace_sun_grid<COUNT, INLINE, true><<<grid, kBlock, 0, c.stream>>>(sc, fp, ps, ctl, stats, bounce, cursor_slot, g); \
+   else k_trace_sun_grid<COUNT, INLINE, false><<<grid, kBlock, 0, c.stream>>>(sc, fp, ps, ctl, stats, bounce, cursor_slot, g)
    if (g.recs) {
-      if (c.count_visits) UH_SUN_GRID(true, true);
-      else UH_SUN_GRID(false, true);
+      if (c.count_visits) { UH_SUN_GRID(true, true); }
+      else { UH_SUN_GRID(false, true); }
    } else {
-      if (c.count_visits) UH_SUN_GRID(true, false);
-      else UH_SUN_GRID(false, false);
+      if (c.count_visits) { UH_SUN_GRID(true, false); }
+      else { UH_SUN_GRID(false, false); }
    }
 #undef UH_SUN_GRID
 }
