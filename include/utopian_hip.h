@@ -240,14 +240,16 @@ typedef struct uh_ctx uh_ctx;
  *   waits + complete on return:  uh_reset_stats, uh_get_stats, uh_reset_accumulation, uh_synchronize, every uh_read_*,
  *        uh_write_reservoirs, uh_write_gbuffer_position, uh_build_acceleration, uh_refit_acceleration (also when uh_render_frame calls it for
  *        view->rebuild_tlas), uh_set_tile_partition, uh_set_restir_partition, uh_rccl_attach / uh_rccl_detach, uh_pack_tiles,
- *        uh_unpack_tiles, uh_compose_tiles, uh_resolve_output, uh_add_isosurface_mesh, uh_destroy;
+ *        uh_unpack_tiles, uh_compose_tiles, uh_resolve_output, uh_add_isosurface_mesh, uh_update_isosurface_mesh (it reads the
+ *        triangle total, 8 bytes, back to size its buffers), uh_get_isosurface_update_stats, uh_destroy;
  *   enqueues like a frame, ordered behind the frames in flight and before those that follow:  uh_rccl_gather_tiles, uh_mgpu_compose;
  *        uh_set_option for "frames_in_flight" and for "time_kernels" 1 -> 0 (the others only change what the NEXT enqueued
  *        frame does: "furnace", "sun_grid*", "camera_grid*", "overlap", "batch_frames", "trace_blocks_per_cu", "count_visits",
  *        "full_frame_restir", "primary_implicit"; "device_build", "ploc_sah_top" invalidate the tree: the next frame
  *        needs uh_build_acceleration, which waits);
  *   host state only (no device access, nothing to wait for):  uh_add_mesh, uh_add_light, uh_set_instance_transform,
- *        uh_get_num_lights, uh_mesh_info, uh_read_mesh, uh_get_restir_rows, uh_tile_pack_count, uh_last_error;
+ *        uh_get_num_lights, uh_mesh_info, uh_read_mesh, uh_get_restir_rows, uh_tile_pack_count, uh_last_error
+ *        (uh_read_mesh of a mesh that uh_update_isosurface_mesh has made device-resident copies it from the device: a blocking copy);
  *   uh_add_texture_rgba8 uploads into a fresh allocation no frame in flight can reference (textures enter a frame's tables at the
  *        next uh_build_acceleration) and is complete on return;
  *   uh_trace_closest / uh_trace_any run on the context's first stream, in order with the frames of that stream, read the scene
@@ -459,6 +461,50 @@ int uh_isosurface_cells(uh_ctx* ctx, uint32_t resolution, float lo, float hi, fl
 /* the context's host copy of a mesh (Model keeps CPU copies, primitive.rs:19-24): sizes, then the data */
 int uh_mesh_info(uh_ctx* ctx, uint32_t mesh_index, uint32_t* num_vertices, uint32_t* num_indices);
 int uh_read_mesh(uh_ctx* ctx, uint32_t mesh_index, UhVertex* vertices, uint32_t* indices);
+
+/* ---- the density field at another time, without leaving the GPU -------------------------------------------------------
+ * Re-extracts the field at `time` with the resolution, lo, hi and triangulation mesh `mesh_index` was created with by
+ * uh_add_isosurface_mesh in this context, and makes the result that mesh's geometry. Material, transform and the mesh's index stay;
+ * the triangle count may grow, shrink or become zero (the mesh keeps its index with no vertices and comes back with a later update).
+ * *out_triangles (may be NULL) receives the new count.
+ * Equivalence: after the update and a uh_build_acceleration every observable of the context - traces, the hybrid and forward
+ * graphs' images, the shadow maps, uh_read_mesh, and frames rendered from cleared temporal state - equals, bit for bit, that of a
+ * fresh context whose same scene was made with uh_add_isosurface_mesh(..., time, ...) in the first place. Temporal state is the
+ * accumulation (uh_reset_accumulation) and the reservoirs' history, which an update does not touch and uh_reset_accumulation does not
+ * clear (uh_write_reservoirs does): a frame's temporal pass reads what the frames before the update left, as it does after any
+ * other change of the scene.
+ * State: that of uh_add_mesh - the context is not built. Every render and trace verb and uh_refit_acceleration return
+ * UH_ERR_NOT_BUILT until uh_build_acceleration has run (the topology changed: view->rebuild_tlas does not rebuild by itself).
+ * Errors: UH_ERR_INVALID_ARGUMENT for a null context, an index out of range, a mesh that uh_add_isosurface_mesh did not create, or a
+ * non-finite time; UH_ERR_CAPACITY above 4 Mi triangles; UH_ERR_OUT_OF_MEMORY when the vertex buffer cannot grow: all of these leave
+ * everything as it was (a built context stays built and renders as before). UH_ERR_HIP from the emit pass itself, behind that
+ * point, leaves the mesh with its new size and undefined vertices and the context not built: update again.
+ * Stream order: waits for the frames in flight and is complete on return.
+ * Memory: the mesh's vertices then live on the device, 240 bytes per triangle (the buffer grows when needed and is reused
+ * otherwise), and the host copy is dropped. Every consumer is fed from there: with option "device_build" 1 or 2 the build's
+ * per-triangle sources (104 bytes per triangle of the scene, as before; while a changed count is being applied a second set exists)
+ * are written by a kernel and the other meshes' ranges are moved on the device; the hybrid / forward graphs' mesh tables are
+ * refreshed by device copies. With "device_build" 0 the host builder needs the host copy: the mesh is read back once per update
+ * (80 bytes per vertex) and its packets uploaded as before (112 bytes per triangle) - the slow route, same results.
+ * uh_mesh_info answers from the recorded counts; uh_read_mesh of such a mesh copies from the device (a blocking copy the call does
+ * not make for other meshes). */
+int uh_update_isosurface_mesh(uh_ctx* ctx, uint32_t mesh_index, float time, uint32_t* out_triangles);
+typedef struct UhIsosurfaceUpdateStats {
+   float extract_ms;             /* hipEvent: count + scan + emit of the last update */
+   float scatter_ms;             /* hipEvent: the refreshes from device vertices since the last update: the build sources of the last
+                                    uh_build_acceleration plus the raster tables of the hybrid / forward call after it */
+   uint32_t updates;             /* so far */
+   uint32_t triangles;           /* of the last update */
+   uint64_t host_geometry_bytes; /* cumulative: vertex, index, corner and shade-packet bytes of updated isosurface meshes that this
+                                    context moved between host and device, either way, in any verb (uh_read_mesh's index list, which
+                                    is written on the host, counts as handed over: 4 bytes per index) */
+   uint64_t device_bytes;        /* device memory held for device-resident meshes: their vertex buffers and the extraction's scratch */
+} UhIsosurfaceUpdateStats;
+UH_LAYOUT_ASSERT(sizeof(UhIsosurfaceUpdateStats) == 32 && offsetof(UhIsosurfaceUpdateStats, updates) == 8 && offsetof(UhIsosurfaceUpdateStats, triangles) == 12 &&
+                    offsetof(UhIsosurfaceUpdateStats, host_geometry_bytes) == 16 && offsetof(UhIsosurfaceUpdateStats, device_bytes) == 24,
+                 "UhIsosurfaceUpdateStats (32 B)");
+/* all zero before the first update; waits for the frames in flight like the other stats calls */
+int uh_get_isosurface_update_stats(uh_ctx* ctx, UhIsosurfaceUpdateStats* out);
 
 /* ---- several GPUs behind ONE application process (SURVEY.md section 8b "multi-GPU", 8e) ------------
  * The reference application is a single process with one render thread (prototype/src/main.rs:86-570);

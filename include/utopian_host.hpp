@@ -400,6 +400,18 @@ class Renderer {
       check(uh_add_isosurface_mesh(ctx_, resolution, lo, hi, time, &m, w.data(), &mesh, &tris), "add_isosurface_mesh");
       return tris;
    }
+   // uh_update_isosurface_mesh: the field at another time as mesh `mesh`'s geometry, on the device; returns the triangle count.
+   // build_acceleration() has to follow
+   uint32_t update_isosurface_mesh(uint32_t mesh, float time) {
+      uint32_t tris = 0;
+      check(uh_update_isosurface_mesh(ctx_, mesh, time, &tris), "update_isosurface_mesh");
+      return tris;
+   }
+   UhIsosurfaceUpdateStats isosurface_update_stats() {
+      UhIsosurfaceUpdateStats s;
+      check(uh_get_isosurface_update_stats(ctx_, &s), "isosurface_update_stats");
+      return s;
+   }
    // ---- one process per GPU (the reference is single-device: utopian/src/device.rs:45) ----
    // path tracing: tiles t % world == rank; reservoir passes: this rank's band of rows, exchanged over RCCL inside the library
    // (rank 0 makes the id, the launcher hands the 128 bytes to every rank); composition on the root: compose_tiles

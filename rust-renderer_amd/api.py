@@ -48,6 +48,7 @@ from .types import (
     HybridFrameStats,
     HybridStats,
     GbufferRasterStats,
+    IsosurfaceUpdateStats,
     MarchingCubesStats,
     ShadowmapParams,
     ShadowMapStats,
@@ -332,6 +333,24 @@ class Renderer:
         mesh, tris = C.c_uint32(), C.c_uint32()
         self._check(fn(self._ctx, int(resolution), float(lo), float(hi), float(time), C.byref(material), w.ctypes.data_as(C.POINTER(C.c_float)), C.byref(mesh), C.byref(tris)))
         return (None if mesh.value == 0xFFFFFFFF else mesh.value), tris.value
+
+    def update_isosurface_mesh(self, mesh, time):
+        """uh_update_isosurface_mesh: re-extracts the field at `time` with the parameters mesh `mesh` was created with by
+        add_isosurface_mesh and makes the result its geometry, on the device. Returns the triangle count; the context needs
+        build_acceleration afterwards."""
+        fn = self._lib.uh_update_isosurface_mesh
+        fn.argtypes, fn.restype = [C.c_void_p, C.c_uint32, C.c_float, C.POINTER(C.c_uint32)], C.c_int
+        tris = C.c_uint32()
+        self._check(fn(self._ctx, int(mesh), float(time), C.byref(tris)))
+        return tris.value
+
+    def isosurface_update_stats(self):
+        """UhIsosurfaceUpdateStats (all zero before the first update_isosurface_mesh)"""
+        fn = self._lib.uh_get_isosurface_update_stats
+        fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(IsosurfaceUpdateStats)], C.c_int
+        s = IsosurfaceUpdateStats()
+        self._check(fn(self._ctx, C.byref(s)))
+        return s
 
     def isosurface_cells(self, resolution, lo, hi, time=0.0):
         """uh_isosurface_cells: per cell of the extraction grid (x fastest) its marching-cubes case index and the triangles it keeps"""

@@ -35,6 +35,22 @@ struct HostMesh {
    UhGpuMaterial material;
    float o2w[12];
    float w2o[9];
+   // a mesh of uh_add_isosurface_mesh: what uh_update_isosurface_mesh re-extracts with
+   bool iso = false, iso_reference = true;
+   uint32_t iso_res = 0;
+   float iso_lo = 0.0f, iso_hi = 0.0f;
+   // device-resident (after uh_update_isosurface_mesh): d_verts holds 3 * dev_tris vertices, the index list is their iota.
+   // vertices / indices above are then a mirror that exists only while host_valid (the host builder asks for it)
+   bool dev = false, host_valid = true;
+   UhVertex* d_verts = nullptr;
+   size_t d_capacity = 0;        // vertices d_verts can hold
+   uint32_t dev_tris = 0;
+   uint64_t serial = 0;          // bumped by every update: what the build sources and the raster tables key this mesh's range on
+   float olo[3] = {0, 0, 0}, ohi[3] = {0, 0, 0};  // object-space box of the device vertices (k_iso_scatter), for `box_serial`
+   uint64_t box_serial = ~0ull;
+   size_t tris() const { return dev ? dev_tris : indices.size() / 3; }
+   size_t num_vertices() const { return dev ? 3 * (size_t)dev_tris : vertices.size(); }
+   size_t num_indices() const { return dev ? 3 * (size_t)dev_tris : indices.size(); }
 };
 
 struct EventPair {
@@ -261,6 +277,18 @@ struct uh_ctx {
    DevBuf<float> d_src_corners;
    DevBuf<uint32_t> d_src_keys;
    DevBuf<float4> d_src_shade;
+   // the layout of d_src_*: triangles and HostMesh::serial of each mesh's range (a mesh whose serial moved is rewritten from its
+   // device vertices, the ranges behind it are moved on the device)
+   std::vector<uint32_t> src_tris;
+   std::vector<uint64_t> src_serial;
+   // uh_update_isosurface_mesh: extraction scratch, the box words of k_iso_scatter, two events and the figures of
+   // uh_get_isosurface_update_stats; nothing of it exists before the first update
+   struct IsoUpdate {
+      DevBuf<uint32_t> counts, chunks, box;
+      DevBuf<unsigned long long> total;
+      hipEvent_t begin = nullptr, end = nullptr;
+      UhIsosurfaceUpdateStats st{};
+   } iso;
    float refit_ms = 0.0f;
    DevBuf<TexInfo> d_tex;
    DevBuf<float> d_lut;
@@ -355,6 +383,10 @@ struct uh_ctx {
       DevBuf<UhVertex> vertices;
       DevBuf<uint32_t> indices;
       uint64_t geom = 0;                       // geom_version the mesh tables were made for
+      // with device-resident meshes: each mesh's range in vertices / indices and the HostMesh::serial it holds (unchanged ranges
+      // are moved on the device instead of uploaded again)
+      struct Range { uint32_t vb, ib, nv, ni; uint64_t serial; };
+      std::vector<Range> layout;
       hipEvent_t waits[2 * kMaxSlots + 1] = {};  // behind the frames in flight
       // one record per stage: stage k < kHybridPasses is bit k of UH_HYBRID_* (rt_shadows, G-buffer, rt_reflections, SSAO, deferred,
       // sky, present: the last call's), the environment's sub-passes follow (cube, irradiance, specular, BRDF LUT: the last build's)
@@ -722,6 +754,14 @@ void uh_destroy(uh_ctx* c) {
       h.meshes.release();
       h.vertices.release();
       h.indices.release();
+      for (HostMesh& m : c->meshes)
+         if (m.d_verts) (void)hipFree(m.d_verts);
+      for (hipEvent_t ev : {c->iso.begin, c->iso.end})
+         if (ev) (void)hipEventDestroy(ev);
+      c->iso.counts.release();
+      c->iso.chunks.release();
+      c->iso.box.release();
+      c->iso.total.release();
       h.raw_lights.release();
       h.taps.release();
       for (hipEvent_t ev : h.waits)
@@ -880,14 +920,36 @@ static int upload_scene_tables(uh_ctx* c) {
 
 static int build_on_device(uh_ctx* c);
 
+// the host builder and the host refit read HostMesh::vertices / indices: a device-resident mesh is copied back (once per update)
+static int ensure_host_mirrors(uh_ctx* c) {
+   for (HostMesh& m : c->meshes) {
+      if (!m.dev || m.host_valid) continue;
+      m.vertices.resize(3 * (size_t)m.dev_tris);
+      m.indices.resize(m.vertices.size());
+      if (m.dev_tris) {
+         HIP_TRY(c, hipMemcpy(m.vertices.data(), m.d_verts, m.vertices.size() * sizeof(UhVertex), hipMemcpyDeviceToHost));  // blocking
+         c->iso.st.host_geometry_bytes += m.vertices.size() * sizeof(UhVertex);
+      }
+      for (size_t i = 0; i < m.indices.size(); i++) m.indices[i] = (uint32_t)i;
+      m.host_valid = true;
+   }
+   return UH_OK;
+}
+// bytes per triangle of the device-resident meshes that a host-side assembly uploads
+static void count_host_upload(uh_ctx* c, size_t bytes_per_triangle) {
+   for (const HostMesh& m : c->meshes)
+      if (m.dev) c->iso.st.host_geometry_bytes += bytes_per_triangle * m.dev_tris;
+}
+
 int uh_build_acceleration(uh_ctx* c) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    HIP_TRY(c, hipSetDevice(c->device));
    if (c->device_build) return build_on_device(c);
    auto t0 = std::chrono::steady_clock::now();
+   if (int st = ensure_host_mirrors(c)) return st;
    // bake instance transforms: world = ((m0*x + m1*y) + m2*z) + m3 per row (identity: verbatim)
    size_t total = 0;
-   for (const HostMesh& m : c->meshes) total += m.indices.size() / 3;
+   for (const HostMesh& m : c->meshes) total += m.tris();
    if (total > kMaxTriangles) return fail(c, UH_ERR_CAPACITY, "scene has more than 2^31 - 2 triangles");
    std::vector<float> corners(9 * total);
    std::vector<uint32_t> keys(total);
@@ -896,7 +958,7 @@ int uh_build_acceleration(uh_ctx* c) {
       const HostMesh& m = c->meshes[mi];
       const bool ident = is_identity3x4(m.o2w);
       const float* w = m.o2w;
-      const uint32_t nt = (uint32_t)m.indices.size() / 3;
+      const uint32_t nt = (uint32_t)m.tris();
       for (uint32_t p = 0; p < nt; p++, t++) {
          for (int k = 0; k < 3; k++) {
             const UhVertex& vx = m.vertices[m.indices[3 * (size_t)p + k]];
@@ -973,6 +1035,7 @@ int uh_build_acceleration(uh_ctx* c) {
    if (total) {
       HIP_TRY(c, hipMemcpy2D(c->d_tris.p, 16 * kTriStride16, tp.data(), sizeof(TriPacket), sizeof(TriPacket), total, hipMemcpyHostToDevice));
       HIP_TRY(c, hipMemcpy(c->d_shade.p, sp.data(), total * sizeof(ShadePacket), hipMemcpyHostToDevice));
+      count_host_upload(c, sizeof(TriPacket) + sizeof(ShadePacket));
    }
    c->scene.nodes = reinterpret_cast<const uint4*>(c->d_nodes.p);
    c->scene.tris = c->d_tris.p;
@@ -1002,6 +1065,7 @@ int uh_refit_acceleration(uh_ctx* c) {
    if (int st = sync_all(c)) return st;  // frames in flight still traverse the old boxes
    const size_t total = c->packet_keys.size();
    if (total && !c->d_obj_corners.p) {
+      count_host_upload(c, 9 * sizeof(float));  // (only the host builder leaves no d_obj_corners, and it has made the mirrors)
       std::vector<float> oc(9 * total);
       for (size_t i = 0; i < total; i++) {
          const HostMesh& m = c->meshes[c->packet_keys[i] >> kPrimBits];
@@ -1049,22 +1113,47 @@ int uh_refit_acceleration(uh_ctx* c) {
    return UH_OK;
 }
 
-// uh_build_acceleration with option "device_build": Morton-order tree built by lbvh.hip, boxes by refit.hip
-static int build_on_device(uh_ctx* c) {
-   auto t0 = std::chrono::steady_clock::now();
-   size_t total = 0;
-   for (const HostMesh& m : c->meshes) total += m.indices.size() / 3;
-   if (total > kMaxTriangles) return fail(c, UH_ERR_CAPACITY, "scene has more than 2^31 - 2 triangles");
-   if (int st = sync_all(c)) return st;
-   if (int st = upload_scene_tables(c)) return st;
+// brackets of UhIsosurfaceUpdateStats::scatter_ms on the context's stream (the events exist once an update has run)
+static void iso_scatter_begin(uh_ctx* c) {
+   if (c->iso.begin) (void)hipEventRecord(c->iso.begin, c->stream);
+}
+static int iso_scatter_end(uh_ctx* c, bool add) {
+   if (!c->iso.begin) return UH_OK;
+   HIP_TRY(c, hipEventRecord(c->iso.end, c->stream));
+   HIP_TRY(c, hipEventSynchronize(c->iso.end));
+   float ms = 0.0f;
+   HIP_TRY(c, hipEventElapsedTime(&ms, c->iso.begin, c->iso.end));
+   c->iso.st.scatter_ms = add ? c->iso.st.scatter_ms + ms : ms;
+   return UH_OK;
+}
+
+// d_src_corners / d_src_keys / d_src_shade: the on-device build's per-triangle sources in mesh order (object-space corners,
+// key = mesh << 22 | primitive, normals and uvs of the three vertices, the mesh index). Host-resident meshes are assembled on the
+// host and uploaded when the mesh list has changed (src_valid); a device-resident mesh's range is written by k_iso_scatter from its
+// device vertices whenever its serial has moved, and the ranges of the meshes that did not change are then copied on the device.
+static int refresh_build_sources(uh_ctx* c, size_t total) {
+   const size_t nm = c->meshes.size();
+   std::vector<uint32_t> tris(nm);
+   std::vector<size_t> at(nm + 1, 0);
+   bool any_dev = false;
+   for (size_t i = 0; i < nm; i++) {
+      tris[i] = (uint32_t)c->meshes[i].tris();
+      at[i + 1] = at[i] + tris[i];
+      any_dev = any_dev || c->meshes[i].dev;
+   }
+   std::vector<uint32_t> todo;  // meshes whose range k_iso_scatter writes
    if (!c->src_valid) {
       std::vector<float> corners(9 * total);
       std::vector<uint32_t> keys(total);
       std::vector<ShadePacket> sp(total);
       size_t t = 0;
-      for (uint32_t mi = 0; mi < c->meshes.size(); mi++) {
+      for (uint32_t mi = 0; mi < nm; mi++) {
          const HostMesh& m = c->meshes[mi];
-         const uint32_t nt = (uint32_t)m.indices.size() / 3;
+         if (m.dev) {
+            t += m.dev_tris;
+            continue;
+         }
+         const uint32_t nt = (uint32_t)m.tris();
          for (uint32_t p = 0; p < nt; p++, t++) {
             const UhVertex* v[3] = {&m.vertices[m.indices[3 * (size_t)p]], &m.vertices[m.indices[3 * (size_t)p + 1]], &m.vertices[m.indices[3 * (size_t)p + 2]]};
             ShadePacket& s = sp[t];
@@ -1087,13 +1176,113 @@ static int build_on_device(uh_ctx* c) {
       HIP_TRY(c, c->d_src_corners.alloc(9 * total));
       HIP_TRY(c, c->d_src_keys.alloc(total));
       HIP_TRY(c, c->d_src_shade.alloc(4 * total));
-      if (total) {
-         HIP_TRY(c, hipMemcpy(c->d_src_corners.p, corners.data(), corners.size() * sizeof(float), hipMemcpyHostToDevice));
-         HIP_TRY(c, hipMemcpy(c->d_src_keys.p, keys.data(), keys.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-         HIP_TRY(c, hipMemcpy(c->d_src_shade.p, sp.data(), sp.size() * sizeof(ShadePacket), hipMemcpyHostToDevice));
+      // one upload per run of host-resident meshes (the whole array when no mesh is device-resident)
+      for (size_t i = 0; i < nm;) {
+         if (c->meshes[i].dev) {
+            todo.push_back((uint32_t)i++);
+            continue;
+         }
+         size_t j = i;
+         while (j < nm && !c->meshes[j].dev) j++;
+         const size_t first = at[i], n = at[j] - at[i];
+         if (n) {
+            HIP_TRY(c, hipMemcpy(c->d_src_corners.p + 9 * first, corners.data() + 9 * first, 9 * n * sizeof(float), hipMemcpyHostToDevice));
+            HIP_TRY(c, hipMemcpy(c->d_src_keys.p + first, keys.data() + first, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+            HIP_TRY(c, hipMemcpy(c->d_src_shade.p + 4 * first, sp.data() + first, n * sizeof(ShadePacket), hipMemcpyHostToDevice));
+         }
+         i = j;
       }
-      c->src_valid = true;
+      iso_scatter_begin(c);
+   } else {
+      if (!any_dev) return UH_OK;  // (uh_add_mesh invalidates: the layout is that of the mesh list)
+      bool same_counts = true;
+      for (size_t i = 0; i < nm; i++) {
+         if (c->src_serial[i] != c->meshes[i].serial) todo.push_back((uint32_t)i);
+         same_counts = same_counts && c->src_tris[i] == tris[i];
+      }
+      if (todo.empty()) return UH_OK;
+      iso_scatter_begin(c);
+      if (!same_counts) {
+         // the ranges move: a second set of arrays, the unchanged runs copied across on the device
+         DevBuf<float> nc;
+         DevBuf<uint32_t> nk;
+         DevBuf<float4> ns;
+         const auto give_up = [&](hipError_t e, const char* what) {
+            nc.release(), nk.release(), ns.release();
+            return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string("build sources: ") + what + ": " + hipGetErrorString(e));
+         };
+         hipError_t e;
+         if ((e = nc.alloc(9 * total)) != hipSuccess || (e = nk.alloc(total)) != hipSuccess || (e = ns.alloc(4 * total)) != hipSuccess) return give_up(e, "allocation");
+         std::vector<size_t> old_at(nm + 1, 0);
+         for (size_t i = 0; i < nm; i++) old_at[i + 1] = old_at[i] + c->src_tris[i];
+         for (size_t i = 0; i < nm;) {
+            if (c->src_serial[i] != c->meshes[i].serial) {
+               i++;
+               continue;
+            }
+            size_t j = i;
+            while (j < nm && c->src_serial[j] == c->meshes[j].serial) j++;
+            const size_t from = old_at[i], to = at[i], n = at[j] - at[i];
+            if (n) {
+               if ((e = hipMemcpyAsync(nc.p + 9 * to, c->d_src_corners.p + 9 * from, 9 * n * sizeof(float), hipMemcpyDeviceToDevice, c->stream)) != hipSuccess ||
+                   (e = hipMemcpyAsync(nk.p + to, c->d_src_keys.p + from, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream)) != hipSuccess ||
+                   (e = hipMemcpyAsync(ns.p + 4 * to, c->d_src_shade.p + 4 * from, n * sizeof(ShadePacket), hipMemcpyDeviceToDevice, c->stream)) != hipSuccess) {
+                  (void)hipStreamSynchronize(c->stream);
+                  return give_up(e, "device copy");
+               }
+            }
+            i = j;
+         }
+         if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return give_up(e, "device copy");
+         std::swap(c->d_src_corners, nc);
+         std::swap(c->d_src_keys, nk);
+         std::swap(c->d_src_shade, ns);
+         nc.release(), nk.release(), ns.release();
+         c->src_valid = false;  // src_tris / src_serial describe the old layout until the end of this call: a failure below starts over
+      }
    }
+   if (!todo.empty()) {
+      // every device-resident mesh in `todo` through k_iso_scatter; its box words come back with the build's own wait
+      std::vector<uint32_t> box(6 * todo.size());
+      for (size_t k = 0; k < todo.size(); k++)
+         for (int a = 0; a < 6; a++) box[6 * k + a] = a < 3 ? 0xffffffffu : 0u;
+      if (c->iso.box.n < box.size()) HIP_TRY(c, c->iso.box.alloc(box.size()));
+      HIP_TRY(c, hipMemcpy(c->iso.box.p, box.data(), box.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+      for (size_t k = 0; k < todo.size(); k++) {
+         const HostMesh& m = c->meshes[todo[k]];
+         const size_t first = at[todo[k]];
+         uhi_iso_scatter(c->stream, m.d_verts, m.dev_tris, todo[k], c->d_src_corners.p + 9 * first, c->d_src_keys.p + first,
+                         c->d_src_shade.p + 4 * first, c->iso.box.p + 6 * k);
+      }
+      HIP_TRY(c, hipGetLastError());
+      if (int st = iso_scatter_end(c, false)) return st;
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      HIP_TRY(c, hipMemcpy(box.data(), c->iso.box.p, box.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      for (size_t k = 0; k < todo.size(); k++) {
+         HostMesh& m = c->meshes[todo[k]];
+         for (int a = 0; a < 3; a++) {
+            m.olo[a] = uhi_box_decode(box[6 * k + a]);
+            m.ohi[a] = uhi_box_decode(box[6 * k + 3 + a]);
+         }
+         m.box_serial = m.serial;
+      }
+   }
+   c->src_tris = tris;
+   c->src_serial.resize(nm);
+   for (size_t i = 0; i < nm; i++) c->src_serial[i] = c->meshes[i].serial;
+   c->src_valid = true;
+   return UH_OK;
+}
+
+// uh_build_acceleration with option "device_build": Morton-order tree built by lbvh.hip, boxes by refit.hip
+static int build_on_device(uh_ctx* c) {
+   auto t0 = std::chrono::steady_clock::now();
+   size_t total = 0;
+   for (const HostMesh& m : c->meshes) total += m.tris();
+   if (total > kMaxTriangles) return fail(c, UH_ERR_CAPACITY, "scene has more than 2^31 - 2 triangles");
+   if (int st = sync_all(c)) return st;
+   if (int st = upload_scene_tables(c)) return st;
+   if (int st = refresh_build_sources(c, total)) return st;
    // per-mesh rows + a box that holds every centroid: the 8 corners of each mesh's object-space box, transformed
    std::vector<RefitMesh> rm(c->meshes.size());
    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -1103,12 +1292,19 @@ static int build_on_device(uh_ctx* c) {
       std::memcpy(rm[i].o2w, m.o2w, sizeof(rm[i].o2w));
       rm[i].identity = is_identity3x4(m.o2w) ? 1u : 0u;
       float olo[3] = {INFINITY, INFINITY, INFINITY}, ohi[3] = {-INFINITY, -INFINITY, -INFINITY};
-      for (const UhVertex& v : m.vertices)
-         for (int a = 0; a < 3; a++) {
-            olo[a] = std::fmin(olo[a], v.pos[a]);
-            ohi[a] = std::fmax(ohi[a], v.pos[a]);
-         }
-      if (m.vertices.empty()) continue;
+      if (m.dev) {
+         // the same minima and maxima, reduced on the device by k_iso_scatter (refresh_build_sources)
+         if (!m.dev_tris) continue;
+         if (m.box_serial != m.serial) return fail(c, UH_ERR_HIP, "internal: a device-resident mesh has no box");
+         for (int a = 0; a < 3; a++) olo[a] = m.olo[a], ohi[a] = m.ohi[a];
+      } else {
+         for (const UhVertex& v : m.vertices)
+            for (int a = 0; a < 3; a++) {
+               olo[a] = std::fmin(olo[a], v.pos[a]);
+               ohi[a] = std::fmax(ohi[a], v.pos[a]);
+            }
+         if (m.vertices.empty()) continue;
+      }
       for (int k = 0; k < 8; k++) {
          const float x = (k & 1) ? ohi[0] : olo[0], y = (k & 2) ? ohi[1] : olo[1], z = (k & 4) ? ohi[2] : olo[2];
          for (int a = 0; a < 3; a++) {
@@ -2686,8 +2882,8 @@ int uh_device_pointer(uh_ctx* c, int which, void** out) {
 int uh_mesh_info(uh_ctx* c, uint32_t mesh_index, uint32_t* num_vertices, uint32_t* num_indices) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    if (mesh_index >= c->meshes.size()) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_mesh_info: bad mesh index");
-   if (num_vertices) *num_vertices = (uint32_t)c->meshes[mesh_index].vertices.size();
-   if (num_indices) *num_indices = (uint32_t)c->meshes[mesh_index].indices.size();
+   if (num_vertices) *num_vertices = (uint32_t)c->meshes[mesh_index].num_vertices();
+   if (num_indices) *num_indices = (uint32_t)c->meshes[mesh_index].num_indices();
    return UH_OK;
 }
 
@@ -2695,8 +2891,99 @@ int uh_read_mesh(uh_ctx* c, uint32_t mesh_index, UhVertex* vertices, uint32_t* i
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    if (mesh_index >= c->meshes.size()) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_mesh: bad mesh index");
    const HostMesh& m = c->meshes[mesh_index];
+   if (m.dev && !m.host_valid) {
+      // a device-resident mesh without a host mirror: the vertices come from the device (a blocking copy; they are idle since the
+      // update returned)
+      if (!m.dev_tris) return UH_OK;
+      HIP_TRY(c, hipSetDevice(c->device));
+      const size_t n = 3 * (size_t)m.dev_tris;
+      if (vertices) {
+         HIP_TRY(c, hipMemcpy(vertices, m.d_verts, n * sizeof(UhVertex), hipMemcpyDeviceToHost));
+         c->iso.st.host_geometry_bytes += n * sizeof(UhVertex);
+      }
+      if (indices) {
+         for (size_t i = 0; i < n; i++) indices[i] = (uint32_t)i;  // the index list of a device-resident mesh is never stored
+         c->iso.st.host_geometry_bytes += n * sizeof(uint32_t);    // counted as handed to the host, like the vertices
+      }
+      return UH_OK;
+   }
    if (vertices && !m.vertices.empty()) std::memcpy(vertices, m.vertices.data(), m.vertices.size() * sizeof(UhVertex));
    if (indices && !m.indices.empty()) std::memcpy(indices, m.indices.data(), m.indices.size() * sizeof(uint32_t));
+   return UH_OK;
+}
+
+int uhi_mark_isosurface(uh_ctx* c, uint32_t mesh_index, uint32_t resolution, float lo, float hi, int reference) {
+   if (!c || mesh_index >= c->meshes.size()) return UH_ERR_INVALID_ARGUMENT;
+   HostMesh& m = c->meshes[mesh_index];
+   m.iso = true;
+   m.iso_reference = reference != 0;
+   m.iso_res = resolution;
+   m.iso_lo = lo;
+   m.iso_hi = hi;
+   return UH_OK;
+}
+
+int uh_update_isosurface_mesh(uh_ctx* c, uint32_t mesh_index, float time, uint32_t* out_triangles) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (mesh_index >= c->meshes.size()) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_update_isosurface_mesh: bad mesh index");
+   if (!c->meshes[mesh_index].iso) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_update_isosurface_mesh: the mesh was not created by uh_add_isosurface_mesh");
+   if (!std::isfinite(time)) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_update_isosurface_mesh: time is not finite");
+   HIP_TRY(c, hipSetDevice(c->device));
+   if (int st = sync_all(c)) return st;
+   HostMesh& m = c->meshes[mesh_index];
+   uh_ctx::IsoUpdate& u = c->iso;
+   for (hipEvent_t* ev : {&u.begin, &u.end})
+      if (!*ev) HIP_TRY(c, hipEventCreate(ev));
+   const uint32_t blocks = uhi_iso_blocks(m.iso_res), n_chunks = scan_chunk_count(blocks);
+   if (u.counts.n < blocks) HIP_TRY(c, u.counts.alloc(blocks));
+   if (u.chunks.n < n_chunks) HIP_TRY(c, u.chunks.alloc(n_chunks));
+   if (!u.total.p) HIP_TRY(c, u.total.alloc(1));
+   HIP_TRY(c, hipEventRecord(u.begin, c->stream));
+   unsigned long long total = 0;  // the 8 bytes that size the buffers
+   if (!uhi_iso_count_triangles(c->stream, m.iso_res, m.iso_lo, m.iso_hi, time, m.iso_reference, u.counts.p, u.chunks.p, u.total.p, &total))
+      return fail(c, UH_ERR_HIP, std::string("uh_update_isosurface_mesh: count pass: ") + hipGetErrorString(hipGetLastError()));
+   if (total > (1ull << kPrimBits)) return fail(c, UH_ERR_CAPACITY, "uh_update_isosurface_mesh: more than 4 Mi triangles");
+   if (3 * total > m.d_capacity) {
+      // the new buffer first: a refusal leaves the mesh as it was
+      UhVertex* grown = nullptr;
+      HIP_TRY(c, hipMalloc((void**)&grown, 3 * total * sizeof(UhVertex)));
+      if (m.d_verts) (void)hipFree(m.d_verts);
+      m.d_verts = grown;
+      m.d_capacity = 3 * total;
+   }
+   // from here on the mesh's geometry is the new one (the vertex buffer is being overwritten): whatever happens, the context is not built
+   m.dev = true;
+   m.host_valid = false;
+   m.dev_tris = (uint32_t)total;
+   m.serial++;
+   std::vector<UhVertex>().swap(m.vertices);
+   std::vector<uint32_t>().swap(m.indices);
+   c->built = false;
+   c->topology_valid = false;
+   if (total && !uhi_iso_extract_emit(c->stream, m.iso_res, m.iso_lo, m.iso_hi, time, m.iso_reference, u.counts.p, m.d_verts))
+      return fail(c, UH_ERR_HIP, "uh_update_isosurface_mesh: the case tables could not be loaded");
+   HIP_TRY(c, hipGetLastError());
+   HIP_TRY(c, hipEventRecord(u.end, c->stream));
+   HIP_TRY(c, hipStreamSynchronize(c->stream));
+   HIP_TRY(c, hipEventElapsedTime(&u.st.extract_ms, u.begin, u.end));
+   u.st.scatter_ms = 0.0f;
+   u.st.updates++;
+   u.st.triangles = (uint32_t)total;
+   if (out_triangles) *out_triangles = (uint32_t)total;
+   return UH_OK;
+}
+
+int uh_get_isosurface_update_stats(uh_ctx* c, UhIsosurfaceUpdateStats* out) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_isosurface_update_stats: null destination");
+   std::memset(out, 0, sizeof(*out));
+   HIP_TRY(c, hipSetDevice(c->device));
+   if (int st = sync_all(c)) return st;
+   if (!c->iso.st.updates) return UH_OK;
+   *out = c->iso.st;
+   const uh_ctx::IsoUpdate& u = c->iso;
+   out->device_bytes = u.counts.n * sizeof(uint32_t) + u.chunks.n * sizeof(uint32_t) + u.box.n * sizeof(uint32_t) + u.total.n * sizeof(unsigned long long);
+   for (const HostMesh& m : c->meshes) out->device_bytes += m.d_capacity * sizeof(UhVertex);
    return UH_OK;
 }
 
@@ -2748,10 +3035,78 @@ static int hybrid_tables(uh_ctx* c) {
       d.normal_map = m.material.normal_map;
       d.metallic_roughness_map = m.material.metallic_roughness_map;
       d.occlusion_map = m.material.occlusion_map;
-      nv += m.vertices.size();
-      ni += m.indices.size();
+      nv += m.num_vertices();
+      ni += m.num_indices();
    }
    if (nv >= (1ull << 32) || ni >= (1ull << 32)) return fail(c, UH_ERR_CAPACITY, "uh_render_hybrid: more than 2^32 vertices or indices");
+   bool any_dev = false;
+   for (const HostMesh& m : c->meshes) any_dev = any_dev || m.dev;
+   if (any_dev) {
+      // a second pair of arrays; per mesh: a range the old pair holds for the same serial is copied across on the device, a
+      // device-resident mesh is copied from its vertex buffer with an iota index list, a host-resident one is uploaded
+      DevBuf<UhVertex> vb;
+      DevBuf<uint32_t> ib;
+      const auto give_up = [&](hipError_t e) {
+         (void)hipStreamSynchronize(c->stream);
+         vb.release(), ib.release();
+         return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string("mesh tables: ") + hipGetErrorString(e));
+      };
+      hipError_t e;
+      bool in_place = h.meshes.p && h.layout.size() == c->meshes.size();
+      for (size_t i = 0; in_place && i < c->meshes.size(); i++)
+         in_place = h.layout[i].nv == c->meshes[i].num_vertices() && h.layout[i].ni == c->meshes[i].num_indices();
+      if (in_place) {
+         // no count changed: the updated meshes' vertices over their old ones (their iota stays), the bases as they are
+         iso_scatter_begin(c);
+         for (size_t i = 0; i < c->meshes.size(); i++) {
+            const HostMesh& m = c->meshes[i];
+            if (h.layout[i].serial == m.serial) continue;
+            if (h.layout[i].nv) HIP_TRY(c, hipMemcpyAsync(h.vertices.p + h.layout[i].vb, m.d_verts, h.layout[i].nv * sizeof(UhVertex), hipMemcpyDeviceToDevice, c->stream));
+            h.layout[i].serial = ~0ull;  // (until the copy is known to have completed)
+         }
+         HIP_TRY(c, hipMemcpyAsync(h.meshes.p, ms.data(), ms.size() * sizeof(HybridMesh), hipMemcpyHostToDevice, c->stream));
+         if (int st = iso_scatter_end(c, true)) return st;
+         HIP_TRY(c, hipStreamSynchronize(c->stream));
+         for (size_t i = 0; i < c->meshes.size(); i++) h.layout[i].serial = c->meshes[i].serial;
+         h.geom = c->geom_version;
+         return UH_OK;
+      }
+      if ((e = vb.alloc(nv)) != hipSuccess || (e = ib.alloc(ni)) != hipSuccess) return give_up(e);
+      std::vector<uh_ctx::Hybrid::Range> layout(c->meshes.size());
+      iso_scatter_begin(c);
+      for (size_t i = 0; i < c->meshes.size(); i++) {
+         const HostMesh& m = c->meshes[i];
+         uh_ctx::Hybrid::Range& r = layout[i];
+         r = uh_ctx::Hybrid::Range{ms[i].vertex_base, ms[i].index_base, (uint32_t)m.num_vertices(), (uint32_t)m.num_indices(), m.serial};
+         const uh_ctx::Hybrid::Range* old = h.meshes.p && i < h.layout.size() ? &h.layout[i] : nullptr;
+         e = hipSuccess;
+         if (old && old->serial == r.serial && old->nv == r.nv && old->ni == r.ni) {
+            if (r.nv) e = hipMemcpyAsync(vb.p + r.vb, h.vertices.p + old->vb, r.nv * sizeof(UhVertex), hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess && r.ni) e = hipMemcpyAsync(ib.p + r.ib, h.indices.p + old->ib, r.ni * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream);
+         } else if (m.dev) {
+            if (r.nv) e = hipMemcpyAsync(vb.p + r.vb, m.d_verts, r.nv * sizeof(UhVertex), hipMemcpyDeviceToDevice, c->stream);
+            uhi_iota(c->stream, ib.p + r.ib, r.ni);
+            if (e == hipSuccess) e = hipGetLastError();
+         } else {
+            if (r.nv) e = hipMemcpy(vb.p + r.vb, m.vertices.data(), r.nv * sizeof(UhVertex), hipMemcpyHostToDevice);
+            if (e == hipSuccess && r.ni) e = hipMemcpy(ib.p + r.ib, m.indices.data(), r.ni * sizeof(uint32_t), hipMemcpyHostToDevice);
+         }
+         if (e != hipSuccess) return give_up(e);
+      }
+      if ((e = h.meshes.n == ms.size() && h.meshes.p ? hipSuccess : h.meshes.alloc(ms.size())) != hipSuccess) return give_up(e);
+      if ((e = hipMemcpyAsync(h.meshes.p, ms.data(), ms.size() * sizeof(HybridMesh), hipMemcpyHostToDevice, c->stream)) != hipSuccess) return give_up(e);
+      if (int st = iso_scatter_end(c, true)) {
+         vb.release(), ib.release();
+         return st;
+      }
+      if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return give_up(e);
+      std::swap(h.vertices, vb);
+      std::swap(h.indices, ib);
+      vb.release(), ib.release();
+      h.layout = std::move(layout);
+      h.geom = c->geom_version;
+      return UH_OK;
+   }
    std::vector<UhVertex> verts;
    std::vector<uint32_t> idx;
    verts.reserve(nv);
@@ -2767,6 +3122,9 @@ static int hybrid_tables(uh_ctx* c) {
    if (!verts.empty()) HIP_TRY(c, hipMemcpyAsync(h.vertices.p, verts.data(), verts.size() * sizeof(UhVertex), hipMemcpyHostToDevice, c->stream));
    if (!idx.empty()) HIP_TRY(c, hipMemcpyAsync(h.indices.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
    HIP_TRY(c, hipStreamSynchronize(c->stream));  // the host vectors go out of scope
+   h.layout.resize(ms.size());
+   for (size_t i = 0; i < ms.size(); i++)
+      h.layout[i] = uh_ctx::Hybrid::Range{ms[i].vertex_base, ms[i].index_base, (uint32_t)c->meshes[i].num_vertices(), (uint32_t)c->meshes[i].num_indices(), c->meshes[i].serial};
    h.geom = c->geom_version;
    return UH_OK;
 }
@@ -2837,12 +3195,27 @@ static void cascade_mesh_matrices(const uh_ctx* c, const UhShadowmapParams& p, s
    }
 }
 
+// the rasterisers' per-triangle mesh ids (tm, made on the host): uploaded, or - once a mesh is device-resident, whose count changes with
+// every update - written on the device, one fill per mesh range, on the stream the rasterisers run on
+static int fill_tri_mesh(uh_ctx* c, uint32_t* dst, const std::vector<uint32_t>& tm) {
+   bool any_dev = false;
+   for (const HostMesh& m : c->meshes) any_dev = any_dev || m.dev;
+   if (!any_dev) {
+      if (!tm.empty()) HIP_TRY(c, hipMemcpy(dst, tm.data(), tm.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+      return UH_OK;
+   }
+   size_t at = 0;
+   for (size_t i = 0; i < c->meshes.size(); at += c->meshes[i].tris(), i++) uhi_fill_u32(c->stream, dst + at, (uint32_t)c->meshes[i].tris(), (uint32_t)i);
+   HIP_TRY(c, hipGetLastError());
+   return UH_OK;
+}
+
 // count, scan, emit, resolve: the records' and tile entries' totals come back to the host in between (the buffers grow to them)
 static int render_shadow_maps(uh_ctx* c, const LaunchCfg& lc, const char* verb) {
    uh_ctx::Hybrid& h = c->hy;
    const uint32_t S = c->shadow_map_size, tiles_x = (S + kShadowTile - 1) / kShadowTile, tiles = 4 * tiles_x * tiles_x;
    size_t ntri = 0;
-   for (const HostMesh& m : c->meshes) ntri += m.indices.size() / 3;
+   for (const HostMesh& m : c->meshes) ntri += m.tris();
    if (4 * ntri >= (1ull << 32)) return fail(c, UH_ERR_CAPACITY, std::string(verb) + ": shadow maps of more than 2^30 triangles");
    const auto grow = [&](auto& b, size_t n) -> int {
       if (b.p && b.n >= n) return UH_OK;
@@ -2858,10 +3231,10 @@ static int render_shadow_maps(uh_ctx* c, const LaunchCfg& lc, const char* verb) 
    if (h.s_geom != c->geom_version || !h.s_rec_count.p) {
       std::vector<uint32_t> tm;
       tm.reserve(ntri);
-      for (size_t m = 0; m < c->meshes.size(); m++) tm.insert(tm.end(), c->meshes[m].indices.size() / 3, (uint32_t)m);
+      for (size_t m = 0; m < c->meshes.size(); m++) tm.insert(tm.end(), c->meshes[m].tris(), (uint32_t)m);
       HIP_TRY(c, h.s_tri_mesh.alloc(std::max<size_t>(1, ntri)));
       HIP_TRY(c, h.s_rec_count.alloc(std::max<size_t>(1, 4 * ntri)));
-      if (ntri) HIP_TRY(c, hipMemcpy(h.s_tri_mesh.p, tm.data(), ntri * sizeof(uint32_t), hipMemcpyHostToDevice));
+      if (int st = fill_tri_mesh(c, h.s_tri_mesh.p, tm)) return st;
       h.s_geom = c->geom_version;
    }
    // until this render completes the maps and their params are invalid: a failure below leaves the deferred pass refused
@@ -3496,7 +3869,7 @@ static int raster_scene(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformData&
    const uint32_t W = c->W, H = c->H, tiles_x = (W + kForwardTile - 1) / kForwardTile, tiles_y = (H + kForwardTile - 1) / kForwardTile;
    const uint32_t tiles = tiles_x * tiles_y;
    size_t ntri = 0;
-   for (const HostMesh& m : c->meshes) ntri += m.indices.size() / 3;
+   for (const HostMesh& m : c->meshes) ntri += m.tris();
    if (ntri >= (1ull << 32) - 1) return fail(c, UH_ERR_CAPACITY, std::string(who) + ": 2^32 - 1 or more triangles");
    const auto grow = [&](auto& buf, size_t n) -> int {
       if (buf.p && buf.n >= n) return UH_OK;
@@ -3511,10 +3884,10 @@ static int raster_scene(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformData&
    if (b.geom != c->geom_version || !b.rec_count.p) {
       std::vector<uint32_t> tm;
       tm.reserve(ntri);
-      for (size_t m = 0; m < c->meshes.size(); m++) tm.insert(tm.end(), c->meshes[m].indices.size() / 3, (uint32_t)m);
+      for (size_t m = 0; m < c->meshes.size(); m++) tm.insert(tm.end(), c->meshes[m].tris(), (uint32_t)m);
       for (int st : {grow(b.tri_mesh, std::max<size_t>(1, ntri)), grow(b.rec_count, std::max<size_t>(1, ntri))})
          if (st) return st;
-      if (ntri) HIP_TRY(c, hipMemcpy(b.tri_mesh.p, tm.data(), ntri * sizeof(uint32_t), hipMemcpyHostToDevice));
+      if (int st = fill_tri_mesh(c, b.tri_mesh.p, tm)) return st;
       b.geom = c->geom_version;
    }
    forward_mesh_matrices(c, view, b.mats_host);

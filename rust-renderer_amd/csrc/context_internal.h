@@ -34,3 +34,22 @@ void* uhi_composed_event(uh_ctx*);  // hipEvent_t behind the context's last pack
 constexpr uint32_t kMcRes = 32, kMcBlocks = kMcRes * kMcRes * kMcRes / 256;
 bool uhi_mc_extract_count(void* stream, float time, uint32_t* block_counts);
 bool uhi_mc_extract_emit(void* stream, float time, const uint32_t* block_offsets, UhVertex* verts);
+// the extraction of uh_add_isosurface_mesh / uh_update_isosurface_mesh (isosurface.hip) in its two halves, on `stream` (hipStream_t).
+// uhi_iso_count_triangles: the triangles of each block of 256 cells, x fastest (uhi_iso_blocks(resolution) of them), scanned in place
+// into block_counts (chunks: scan_chunk_count(blocks) words of scratch, d_total: one device word), waits and reads the 64-bit total
+// back; false on a HIP error or when the case tables could not be loaded. uhi_iso_extract_emit (enqueued): vertex 3 t + k of
+// triangle t at block_offsets[block] (that scan) plus the block's prefix.
+uint32_t uhi_iso_blocks(uint32_t resolution);
+bool uhi_iso_count_triangles(void* stream, uint32_t resolution, float lo, float hi, float time, bool reference, uint32_t* block_counts, uint32_t* chunks,
+                             unsigned long long* d_total, unsigned long long* total);
+bool uhi_iso_extract_emit(void* stream, uint32_t resolution, float lo, float hi, float time, bool reference, const uint32_t* block_offsets, UhVertex* verts);
+// context.hip: mesh `mesh_index` was made by uh_add_isosurface_mesh with these parameters (uh_update_isosurface_mesh re-extracts with them)
+extern "C" int uhi_mark_isosurface(uh_ctx*, uint32_t mesh_index, uint32_t resolution, float lo, float hi, int reference);
+// iso_update.hip: what feeds a device-resident mesh's consumers from its device vertices, enqueued on `stream`.
+// uhi_iso_scatter: per triangle p of the mesh (vertices 3 p .. 3 p + 2) the on-device build's sources - 9 corner floats, key = mesh << 22 | p,
+// the 64-byte shade packet - at corners / keys / shade (already offset to the mesh's range), and the mesh's object-space box folded into
+// box[0..2] (minima) / box[3..5] (maxima) as ordered integers: initialise them to 0xffffffff / 0 and read them with uhi_box_decode.
+void uhi_iso_scatter(void* stream, const UhVertex* verts, uint32_t num_tris, uint32_t mesh, float* corners, uint32_t* keys, float4* shade, uint32_t* box);
+void uhi_iota(void* stream, uint32_t* out, uint32_t n);
+void uhi_fill_u32(void* stream, uint32_t* out, uint32_t n, uint32_t value);
+float uhi_box_decode(uint32_t ordered);

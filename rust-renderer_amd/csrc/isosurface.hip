@@ -265,6 +265,23 @@ bool uhi_mc_extract_emit(void* stream, float time, const uint32_t* block_offsets
    return true;
 }
 
+uint32_t uhi_iso_blocks(uint32_t resolution) { return (uint32_t)(((uint64_t)resolution * resolution * resolution + kBlock - 1) / kBlock); }
+bool uhi_iso_count_triangles(void* stream_v, uint32_t resolution, float lo, float hi, float time, bool reference, uint32_t* block_counts, uint32_t* chunks,
+                             unsigned long long* d_total, unsigned long long* total) {
+   hipStream_t stream = (hipStream_t)stream_v;
+   if (!load_tables()) return false;
+   const uint32_t blocks = uhi_iso_blocks(resolution);
+   k_iso_count<<<blocks, kBlock, 0, stream>>>(iso_params(resolution, lo, hi, time, reference), block_counts);
+   device_exclusive_scan_u32(block_counts, blocks, chunks, d_total, stream);  // exclusive scan of the per-block counts, on the device
+   if (hipStreamSynchronize(stream) != hipSuccess || hipGetLastError() != hipSuccess) return false;
+   return hipMemcpy(total, d_total, sizeof(*total), hipMemcpyDeviceToHost) == hipSuccess;  // blocking (a local)
+}
+bool uhi_iso_extract_emit(void* stream, uint32_t resolution, float lo, float hi, float time, bool reference, const uint32_t* block_offsets, UhVertex* verts) {
+   if (!load_tables()) return false;
+   k_iso_emit<<<uhi_iso_blocks(resolution), kBlock, 0, (hipStream_t)stream>>>(iso_params(resolution, lo, hi, time, reference), block_offsets, verts);
+   return true;
+}
+
 extern "C" int uh_isosurface_cells(uh_ctx* ctx, uint32_t resolution, float lo, float hi, float time, uint8_t* out_cube_index, uint8_t* out_triangle_count) {
    if (!ctx || resolution < 1 || resolution > 1024 || !(hi > lo)) return UH_ERR_INVALID_ARGUMENT;
    void* stream_v = nullptr;
@@ -307,17 +324,12 @@ extern "C" int uh_add_isosurface_mesh(uh_ctx* ctx, uint32_t resolution, float lo
          if (p) (void)hipFree(p);
       return st;
    };
-   if (!load_tables()) return UH_ERR_HIP;
    const uint32_t n_chunks = scan_chunk_count(blocks);
    if (hipMalloc(&d_counts, (size_t)blocks * sizeof(uint32_t)) != hipSuccess || hipMalloc(&d_chunks, (size_t)n_chunks * sizeof(uint32_t)) != hipSuccess ||
        hipMalloc(&d_total, sizeof(unsigned long long)) != hipSuccess)
       return fail(UH_ERR_OUT_OF_MEMORY);
-   k_iso_count<<<blocks, kBlock, 0, stream>>>(q, d_counts);
-   // exclusive scan of the per-block counts, on the device
-   device_exclusive_scan_u32(d_counts, blocks, d_chunks, d_total, stream);
    unsigned long long total = 0;
-   if (hipStreamSynchronize(stream) != hipSuccess || hipGetLastError() != hipSuccess) return fail(UH_ERR_HIP);
-   if (hipMemcpy(&total, d_total, sizeof(total), hipMemcpyDeviceToHost) != hipSuccess) return fail(UH_ERR_HIP);  // blocking (a local)
+   if (!uhi_iso_count_triangles(stream, resolution, lo, hi, time, q.reference != 0, d_counts, d_chunks, d_total, &total)) return fail(UH_ERR_HIP);
    // a mesh holds at most 4 Mi triangles (key = mesh << 22 | primitive); `total` is the true 64-bit sum (device_scan.h), so a
    // grid whose count would wrap the 32-bit offsets is refused here, before the emit pass sizes anything by it
    if (total > (1ull << 22)) return fail(UH_ERR_CAPACITY);
@@ -336,5 +348,8 @@ extern "C" int uh_add_isosurface_mesh(uh_ctx* ctx, uint32_t resolution, float lo
    }
    std::vector<uint32_t> indices(verts.size());
    for (size_t i = 0; i < indices.size(); i++) indices[i] = (uint32_t)i;
-   return uh_add_mesh(ctx, verts.data(), (uint32_t)verts.size(), indices.data(), (uint32_t)indices.size(), material, world3x4, out_mesh_index);
+   uint32_t mesh_index = 0;
+   if (int st = uh_add_mesh(ctx, verts.data(), (uint32_t)verts.size(), indices.data(), (uint32_t)indices.size(), material, world3x4, &mesh_index)) return st;
+   if (out_mesh_index) *out_mesh_index = mesh_index;
+   return uhi_mark_isosurface(ctx, mesh_index, resolution, lo, hi, q.reference ? 1 : 0);  // what uh_update_isosurface_mesh re-extracts with
 }

@@ -278,6 +278,19 @@ assert C.sizeof(MarchingCubesStats) == 32 and MarchingCubesStats.triangles.offse
     MarchingCubesStats.covered_pixels.offset == 16 and MarchingCubesStats.lights.offset == 20 and MarchingCubesStats.time.offset == 24
 
 
+class IsosurfaceUpdateStats(C.Structure):
+    """UhIsosurfaceUpdateStats: uh_update_isosurface_mesh so far - hipEvent ms of the last extraction and of the refreshes from device
+    vertices since, the updates, the last one's triangles, geometry bytes of updated meshes moved between host and device (cumulative)
+    and the device memory held for device-resident meshes"""
+
+    _fields_ = [("extract_ms", C.c_float), ("scatter_ms", C.c_float), ("updates", C.c_uint32), ("triangles", C.c_uint32),
+                ("host_geometry_bytes", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+
+assert C.sizeof(IsosurfaceUpdateStats) == 32 and IsosurfaceUpdateStats.updates.offset == 8 and IsosurfaceUpdateStats.triangles.offset == 12 and \
+    IsosurfaceUpdateStats.host_geometry_bytes.offset == 16 and IsosurfaceUpdateStats.device_bytes.offset == 24
+
+
 # the hybrid graph's G-buffer pass rasterised (gbuffer.rs, gbuffer.vert / gbuffer.frag): a modifier of HYBRID_GBUFFER
 HYBRID_GBUFFER_RASTER = 1 << 11
 HYBRID_GBUFFER_DEPTH, HYBRID_GBUFFER_VISIBILITY = 11, 12
