@@ -2,6 +2,7 @@
 // structure build, the per-frame pass chain and read-backs. Host-side counterpart of
 // utopian::Renderer (utopian/src/renderer.rs), utopian::Raytracing (utopian/src/raytracing.rs) and
 // build_path_tracing_render_graph (utopian/src/renderers/mod.rs:189-375) for this path only.
+// struct uh_ctx is context_state.h; the hybrid and the forward graph (uh_render_hybrid, uh_render_forward) are graphs.hip.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: the library opens librccl at run time (uh_rccl_attach)
 #include <dlfcn.h>
@@ -19,6 +20,7 @@
 
 #include "bvh.h"
 #include "context_internal.h"
+#include "context_state.h"
 #include "device_scan.h"
 #include "device_types.h"
 #include "utopian_hip.h"
@@ -26,472 +28,8 @@
 using namespace uh;
 
 namespace {
-
 std::string g_create_error;
-
-struct HostMesh {
-   std::vector<UhVertex> vertices;
-   std::vector<uint32_t> indices;
-   UhGpuMaterial material;
-   float o2w[12];
-   float w2o[9];
-   // a mesh of uh_add_isosurface_mesh: what uh_update_isosurface_mesh re-extracts with
-   bool iso = false, iso_reference = true;
-   uint32_t iso_res = 0;
-   float iso_lo = 0.0f, iso_hi = 0.0f;
-   // device-resident (after uh_update_isosurface_mesh): d_verts holds 3 * dev_tris vertices, the index list is their iota.
-   // vertices / indices above are then a mirror that exists only while host_valid (the host builder asks for it)
-   bool dev = false, host_valid = true;
-   UhVertex* d_verts = nullptr;
-   size_t d_capacity = 0;        // vertices d_verts can hold
-   uint32_t dev_tris = 0;
-   uint64_t serial = 0;          // bumped by every update: what the build sources and the raster tables key this mesh's range on
-   float olo[3] = {0, 0, 0}, ohi[3] = {0, 0, 0};  // object-space box of the device vertices (k_iso_scatter), for `box_serial`
-   uint64_t box_serial = ~0ull;
-   size_t tris() const { return dev ? dev_tris : indices.size() / 3; }
-   size_t num_vertices() const { return dev ? 3 * (size_t)dev_tris : vertices.size(); }
-   size_t num_indices() const { return dev ? 3 * (size_t)dev_tris : indices.size(); }
-};
-
-struct EventPair {
-   hipEvent_t start, stop;
-   int kind;  // 0 trace_closest, 1 trace_shadow, 2 shade
-};
-
-template <typename T>
-struct DevBuf {
-   T* p = nullptr;
-   void* base = nullptr;
-   size_t n = 0;
-   // stagger_bytes shifts the array inside its allocation: the per-pixel SoA arrays are all the same
-   // size, and kernels touch the same index of several of them at once; without a stagger those
-   // accesses are an exact multiple of the array size apart
-   hipError_t alloc(size_t count, size_t stagger_bytes = 0) {
-      release();
-      n = count;
-      if (count == 0) return hipSuccess;
-      hipError_t e = hipMalloc(&base, count * sizeof(T) + stagger_bytes);
-      if (e == hipSuccess) p = reinterpret_cast<T*>(static_cast<char*>(base) + stagger_bytes);
-      return e;
-   }
-   void release() {
-      if (base) (void)hipFree(base);
-      p = nullptr;
-      base = nullptr;
-      n = 0;
-   }
-};
-
-// the forward rasteriser's binning buffers for the scene's meshes (raster_scene): the forward pass and the hybrid graph's rasterised
-// G-buffer have a set each; they grow with the scene
-struct SceneBins {
-   DevBuf<uint32_t> tile_count, tile_cursor, rec_count, tri_mesh, chunks, entries;
-   DevBuf<unsigned long long> totals;       // the grand totals of the two scans: records, tile entries
-   DevBuf<uint4> records;
-   DevBuf<float> mats;                      // [mesh][28]
-   std::vector<float> mats_host;
-   uint64_t geom = 0;                       // geom_version of tri_mesh / rec_count
-   template <class F> void each(F&& f) {
-      f(tile_count, 0), f(tile_cursor, 0), f(rec_count, 0), f(tri_mesh, 0), f(chunks, 0), f(entries, 0), f(totals, 0), f(records, 0), f(mats, 0);
-   }
-};
-
-}  // namespace
-
-// the hybrid graph's stages (uh_ctx::Hybrid::stage): its seven passes in the order of their UH_HYBRID_* bits, then the environment's,
-// then the shadow maps, then the marching-cubes pass
-enum HybridStage : int {
-   kStShadows, kStGbuffer, kStReflections, kStSsao, kStDeferred, kStSky, kStPresent, kHybridPasses,
-   kStEnvCube = kHybridPasses, kStEnvIrradiance, kStEnvSpecular, kStEnvLut, kStShadowMaps, kStMarchingCubes, kHybridStages
-};
-
-// One frame in flight: its own stream pair, hazard events, path state and queue control block.
-// Frames of the path-tracing pass are independent except for the order of the accumulation
-// read-modify-write (reference.rgen:131-143), so up to `frames_in_flight` of them overlap on the
-// GPU: one frame's memory-bound shading and kernel tails are filled by another frame's traversal,
-// and a rank that owns only 1/N of the pixels still keeps the chip busy.
-constexpr uint32_t kMaxSlots = 8;
-struct Slot {
-   hipStream_t stream = nullptr;
-   // second stream: shade_miss (pure VALU, touches only paths that left the scene) and the shadow
-   // traversals overlap the main stream's shade_hit / next closest-hit traversal
-   hipStream_t side = nullptr;
-   hipEvent_t ev_traced = nullptr, ev_missed = nullptr, ev_shaded = nullptr, ev_shadowed = nullptr, ev_side_done = nullptr;
-   hipEvent_t ev_acc = nullptr;  // recorded after the frame's accumulate / store tail
-   hipEvent_t frame_start = nullptr, frame_stop = nullptr;
-   DevBuf<float4> rec, radf, pixcol;  // rec: two sets of four path-state planes + the hit plane (device_types.h PathState)
-   DevBuf<uint32_t> queues[5];
-   DevBuf<unsigned long long> sun_lit;  // the sun rays' verdicts: one bit per queue position (PathState::sun_lit)
-   DevBuf<Control> control;
-   PathState ps{};
-   bool ready = false;
-   size_t capacity = 0;  // path ids this slot can hold (pixels x frames per batch)
-
-   hipError_t create(size_t n) {
-      capacity = n;
-      uint32_t shard_cap = 0;
-      {  // exact: the largest number of 64-path runs one shard receives (shard_of_run)
-         const uint32_t runs = (uint32_t)((n + 63) / 64);
-         uint32_t per_shard[kShards] = {0};
-         for (uint32_t r = 0; r < runs; r++) per_shard[shard_of_run(r)]++;
-         for (uint32_t s = 0; s < kShards; s++) shard_cap = per_shard[s] * 64 > shard_cap ? per_shard[s] * 64 : shard_cap;
-      }
-      if (shard_cap >= (1u << 31)) return hipErrorInvalidValue;  // a queue position's top bit carries the path's sun verdict (kernels.hip kSunLitBit)
-      hipError_t e;
-#define SLOT_TRY(expr)                 \
-   if ((e = (expr)) != hipSuccess) return e
-      SLOT_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-      SLOT_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-      for (hipEvent_t* ev : {&ev_traced, &ev_missed, &ev_shaded, &ev_shadowed, &ev_side_done, &ev_acc}) SLOT_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-      SLOT_TRY(hipEventCreate(&frame_start));
-      SLOT_TRY(hipEventCreate(&frame_stop));
-      const size_t stagger = 4352;  // 4 KiB + 256 B per array slot
-      // planes staggered like the arrays: the same index of two planes must not alias. The hit plane is indexed by queue position
-      // (shard segment + position in the shard's queue), which runs to kShards * shard_cap >= n
-      const size_t cap_q = (size_t)shard_cap * kShards;
-      const size_t plane = (n > cap_q ? n : cap_q) + stagger / sizeof(float4);
-      SLOT_TRY(rec.alloc(plane * (2 * kRecQuads + 1), 0 * stagger));
-      SLOT_TRY(radf.alloc(n, 1 * stagger));
-      SLOT_TRY(pixcol.alloc(n, 2 * stagger));
-      // sharded queues: capacity per shard = the pixels (64-pixel runs) a shard can own
-      // (the miss queue holds (position, id) pairs: twice the words)
-      for (int qi = 0; qi < 5; qi++) SLOT_TRY(queues[qi].alloc((size_t)shard_cap * kShards * (qi == 4 ? 2 : 1)));
-      // shard_cap is a multiple of 64: a shard's segment is whole words. The sun kernels store every word the next kernels read
-      SLOT_TRY(sun_lit.alloc((size_t)shard_cap * kShards / 64));
-      SLOT_TRY(hipMemsetAsync(sun_lit.p, 0, sun_lit.n * sizeof(unsigned long long), stream));
-      SLOT_TRY(control.alloc(1));
-      SLOT_TRY(hipMemsetAsync(control.p, 0, sizeof(Control), stream));
-      SLOT_TRY(hipStreamSynchronize(stream));
-#undef SLOT_TRY
-      ps.set[0] = PathRecs{rec.p, plane};
-      ps.set[1] = PathRecs{rec.p + plane * kRecQuads, plane};
-      ps.hit = rec.p + plane * 2 * kRecQuads;
-      ps.radf = radf.p;
-      ps.pixcol = pixcol.p;
-      for (int i = 0; i < 5; i++) ps.queue[i] = queues[i].p;
-      ps.sun_lit = sun_lit.p;
-      ps.shard_cap = shard_cap;
-      ready = true;
-      return hipSuccess;
-   }
-   void destroy() {
-      if (stream) (void)hipStreamSynchronize(stream);
-      if (side) (void)hipStreamSynchronize(side);
-      rec.release();
-      radf.release();
-      pixcol.release();
-      for (auto& q : queues) q.release();
-      sun_lit.release();
-      control.release();
-      for (hipEvent_t* ev : {&ev_traced, &ev_missed, &ev_shaded, &ev_shadowed, &ev_side_done, &ev_acc, &frame_start, &frame_stop}) {
-         if (*ev) (void)hipEventDestroy(*ev);
-         *ev = nullptr;  // (a create() that fails half-way must not leave handles for the next destroy())
-      }
-      if (side) (void)hipStreamDestroy(side);
-      if (stream) (void)hipStreamDestroy(stream);
-      stream = side = nullptr;
-      ready = false;
-   }
-};
-
-// frames of the reservoir passes one uh_render_frames wavefront carries at most, and the ring of spatial buffers that
-// lets the next batch's chains run beside the current wavefront (two batches + the history slot)
-constexpr uint32_t kRestirBatch = 16;
-constexpr int kSpatialRing = 2 * (int)kRestirBatch + 1;
-
-struct uh_ctx {
-   int device = 0;
-   Slot slots[kMaxSlots];
-   uint32_t frames_in_flight = 4;     // slots used round-robin by path-tracing frames (swept: profiles/README.md)
-   uint32_t batch_frames = 0;         // frames one uh_render_frames launch chain carries (option "batch_frames"); 0 = auto
-   uint32_t next_slot = 0;
-   uint32_t shard_cap = 0;
-   hipEvent_t last_acc = nullptr;     // ev_acc of the most recent frame (accumulation order)
-   // G-buffer cast + reservoir passes run in call order on their own stream, beside path-tracing frames in flight.
-   // spatial_reuse_reservoirs is a RING of kSpatialRing buffers: the path tracer of frame f reads slot `spatial_cur` while
-   // frame f+1's passes already run - its temporal pass reads the same slot and its spatial pass writes the next one, after
-   // the last path-tracing wavefront that read THAT one has finished (spatial_reader[]). A batch of B static-camera frames
-   // runs its B reservoir chains back to back (slots cur+1 .. cur+B) and then ONE path-tracing wavefront in which the
-   // paths of frame f sample from slot cur+1+f (FrameParams::spatial_of): the ring holds two batches and the history.
-   hipStream_t restir_stream = nullptr;
-   hipEvent_t ev_restir = nullptr, rs_start = nullptr, rs_stop = nullptr;
-   bool restir_recorded = false;
-   int spatial_cur = 0;
-   hipEvent_t spatial_reader[kSpatialRing] = {};
-   // the reservoir passes by bands of rows over the ranks of a job (uh_set_restir_partition)
-   uint32_t rp_rank = 0, rp_world = 1, rp_band_rows = 0;
-   size_t res_stride = 0;  // reservoirs per spatial_reuse buffer: the frame, padded to rp_world equal bands
-   UhRestirExchangeFn rp_exchange = nullptr;
-   void* rp_user = nullptr;
-   hipEvent_t ev_band[kSpatialRing] = {};  // "this context's band of ring slot k is written" (in-process groups pull on it)
-   void* rccl = nullptr;                   // RcclLink (uh_rccl_attach)
-   hipEvent_t t_start = nullptr, t_stop = nullptr;  // bracket of the last uh_render_frame call (last_frame_ms)
-   Slot* last_slot = nullptr;
-   hipStream_t& stream = slots[0].stream;  // slot 0 also serves every non-frame operation
-   PathState& ps = slots[0].ps;
-   DevBuf<Control>& control = slots[0].control;
-   bool overlap_miss = true, overlap_shadow = true;
-   uint32_t W = 0, H = 0;
-   uint32_t num_cus = 256;
-   // persistent grids of the traversal kernels, blocks per CU (the refill kernels' LDS - stacks + ray pool - admits 6 / 5). Round 4,
-   // closest / shadow = 6/5, 5/5, 5/4, 4/4, 4/3, 3/4: a 16-frame wavefront 1.774 / 1.777 / 1.764 / 1.780 / 1.773 / 1.799 ms per frame,
-   // one frame per call with a wait after it 2.95 / 2.88 / 2.88 / 2.84 / 2.85 / 2.89 ms: fewer waves finish a small launch's tail sooner
-   uint32_t closest_blocks_per_cu = 5, shadow_blocks_per_cu = 5;  // (config 2, whose light shadow rays are a third of the frame: 6/5, 5/5, 5/4, 6/4 = 8,230 / 8,266 / 7,997 / 7,950 Mrays/s)
-   uint32_t cam_walk_whole = 512;     // option "camera_grid_walk_whole" (sun_grid.h SunGridDev::walk_whole)
-   // one frame per call: bounces 1 .. of a lone frame inside one persistent kernel (k_path_fused) instead of four launches per bounce
-   bool fused_bounces = true;  // option "fused_bounces"
-   bool fused_always = false;  // fused_bounces = -1: also with frames in flight and for frames of any size (tests)
-   static constexpr uint32_t kFusedMaxPaths = 4u << 20;
-   uint32_t fused_blocks_per_cu = 4;
-   static constexpr uint32_t kSingleFrameBlocksPerCu = 4;  // the cap on both for a wavefront of one frame (fewer persistent waves reach the end of a small launch's tail sooner: round 4's sweep)
-   std::string err;
-
-   // host scene
-   std::vector<HostMesh> meshes;
-   std::vector<UhGpuLight> lights;
-   struct HostTex {
-      uint32_t w, h;
-      uchar4* dev;
-      uint32_t tiles_x;  // 0 = row-major
-   };
-   std::vector<HostTex> textures;
-   bool built = false;
-
-   // device scene
-   DevBuf<float4> d_nodes, d_tris, d_shade, d_lights;
-   DevBuf<MeshShade> d_meshes;
-   // on-device refit (refit.hip), allocated by the first uh_refit_acceleration
-   DevBuf<float> d_obj_corners, d_world_corners, d_node_box;
-   DevBuf<RefitMesh> d_refit_meshes;
-   std::vector<uint32_t> packet_keys;  // key of triangle packet i (leaf order)
-   std::vector<uint32_t> level_start;  // BFS levels of the node array
-   bool topology_valid = false;        // the device tree matches the mesh list (transforms may differ)
-   // on-device build (lbvh.hip, option "device_build"): per-triangle sources in mesh order, kept on the device
-   // until a mesh is added, so that a rebuild after moved instances or changed parameters uploads nothing
-   bool device_build = false, src_valid = false;
-   uint32_t device_build_kind = 1;  // 1 = PLOC, 2 = radix tree (lbvh.hip)
-   // PLOC rounds stop at this many clusters; a host SAH tree over them is the top (option "ploc_sah_top", 0 = PLOC to the root).
-   // Config-1 scene: 0 / 1,024 / 8,192 / 131,072 clusters = 21.7 / 20.3 / 20.1 / 19.0 nodes per ray, rebuild 7.7 / 6.0 / 9.4 / 66 ms (host tree: 18.8)
-   uint32_t ploc_sah_top = 1024;
-   static constexpr uint32_t kPlocRadius = 8;  // swept 4..64 in round 3: tree quality flat (21.7-23.0 nodes/ray), build time grows with it (profiles/README.md)
-   DevBuf<float> d_src_corners;
-   DevBuf<uint32_t> d_src_keys;
-   DevBuf<float4> d_src_shade;
-   // the layout of d_src_*: triangles and HostMesh::serial of each mesh's range (a mesh whose serial moved is rewritten from its
-   // device vertices, the ranges behind it are moved on the device)
-   std::vector<uint32_t> src_tris;
-   std::vector<uint64_t> src_serial;
-   // uh_update_isosurface_mesh: extraction scratch, the box words of k_iso_scatter, two events and the figures of
-   // uh_get_isosurface_update_stats; nothing of it exists before the first update
-   struct IsoUpdate {
-      DevBuf<uint32_t> counts, chunks, box;
-      DevBuf<unsigned long long> total;
-      hipEvent_t begin = nullptr, end = nullptr;
-      UhIsosurfaceUpdateStats st{};
-   } iso;
-   float refit_ms = 0.0f;
-   DevBuf<TexInfo> d_tex;
-   DevBuf<float> d_lut;
-   SceneDev scene{};
-
-   // frame-persistent per-pixel images (graph resources of renderers/mod.rs:199-244)
-   DevBuf<float4> accumulation, gbuffer;
-   DevBuf<uchar4> output;
-   DevBuf<UhReservoir> reservoirs[3], spatial_ring;  // ring slot 0 = reservoirs[2], slots 1.. = spatial_ring (allocated by the first reservoir pass)
-   DevBuf<float4> gb_ray_o, gb_ray_d, gb_hit;  // scratch of the G-buffer cast (allocated by the first G-buffer pass)
-   DevBuf<DeviceStats> dstats;
-   Images im{};
-
-   // options / stats
-   bool count_visits = false, time_kernels = false, full_frame_restir = false;
-   bool iso_reference = true;  // option "iso_reference_triangulation": uh_add_isosurface_mesh emits the reference's triangles (isosurface.hip)
-   uint32_t shadow_map_size = 4096;  // option "shadow_map_size": the cascaded shadow maps' size (shadow.rs: 4096)
-   bool furnace = false;  // option "furnace": reference.rmiss compiled with FURNACE_TEST (a miss returns white whatever view.sky_enabled says)
-   uint64_t frames = 0;
-   float build_ms = 0.0f, last_frame_ms = 0.0f;
-   float ms_by_kind[5] = {0, 0, 0, 0, 0};  // trace_closest, sun shadow rays (grid + tree), shade, camera grid (bounce 0 through the grid + its leftovers), light shadow rays
-   uint32_t trace_closest_launches = 0, trace_light_launches = 0;
-   bool frame_timed = false;
-   std::vector<EventPair> pending, free_events;
-   uint32_t bvh_nodes = 0, bvh_tris = 0;
-
-   // sun shadow rays through a per-direction grid instead of the tree (sun_grid.h; option "sun_grid"). The grid belongs to one
-   // (geometry, sun direction) pair: it is built on the first frame that traces sun rays and again when the direction or the
-   // geometry has changed and then stayed put for two consecutive frames - a sun or an instance that moves every frame keeps
-   // the tree walk.
-   bool sun_grid_enabled = true;
-   bool sun_verdicts = true;        // option "sun_verdicts" (FrameParams::sun_verdicts)
-   bool sun_valid = false;          // d_sun_* hold a usable grid for (sun_geom, sun_dir_built)
-   bool sun_attempted = false;      // a build for (sun_geom, sun_dir_built) was tried (it may have been refused: sun_why)
-   bool sun_have_pending = false;
-   uint64_t geom_version = 1, sun_geom = 0, sun_geom_pending = 0;
-   float sun_dir_built[3] = {0, 0, 0}, sun_dir_pending[3] = {0, 0, 0};
-   DevBuf<uint32_t> d_sun_cells;
-   DevBuf<SunGridEntry> d_sun_entries;
-   DevBuf<float4> d_sun_recs;       // the entries with their packets inline (SunGridDev::recs; option "sun_grid_inline")
-   DevBuf<float> d_sun_coarse;      // the coarse cover (SunGridDev::coarse; option "sun_grid_coarse")
-   uint32_t sun_coarse_shift = 2;   // blocks of 4 x 4 cells; 0: no coarse cover
-   // the lists a second time as 64-byte records that carry their packet (SunGridDev::recs): by default only while they stay within
-   // four times the packet array (a grid of 96 entries per triangle repeats every packet 96 times: 1.4 GB for the 17 MB of the
-   // config-1 scene); option "sun_grid_inline_max_mb" raises the budget (0: never)
-   int64_t sun_inline_max_mb = -1;  // -1: auto = 4 x the packet array
-   SunGridDev sun_dev{};
-   SunGridLimits sun_limits;
-   std::string sun_why;
-   float sun_build_ms = 0.0f, sun_mean_list = 0.0f;
-   float sun_fallback_area = 1.0f;  // share of the scene's surface whose cell hands its sun rays to the tree (the builders' figure)
-   uint32_t sun_cells = 0, sun_entries = 0, sun_max_list = 0;
-   bool sun_this_frame = false;     // set by render_batch for the frame being enqueued
-   bool primary_implicit = true;    // option "primary_implicit" (FrameParams::primary_implicit)
-   bool sun_device_build = true;    // option "sun_grid_build": 1 = on the device (sun_grid_build.hip: a few ms), 0 = the host builder (sun_grid.cpp)
-
-   // the primary rays through a per-camera grid instead of the tree (sun_grid.h "camera grid"; option "camera_grid"). The grid belongs
-   // to one (geometry, inverse_view, inverse_projection, frame size): it is built - on the device, a few milliseconds - when the
-   // same camera has been asked for in two consecutive frame calls, or at once by a call that carries several frames of it; a
-   // camera that moves every frame keeps the tree walk.
-   bool cam_grid_enabled = true;
-   bool cam_valid = false, cam_attempted = false, cam_have_pending = false;
-   uint64_t cam_geom = 0, cam_geom_pending = 0;
-   float cam_mats[32] = {0}, cam_mats_pending[32] = {0};  // inverse_view, inverse_projection of the grid / of the last request
-   DevBuf<uint32_t> d_cam_cells;
-   DevBuf<SunGridEntry> d_cam_entries;
-   SunGridDev cam_dev{};
-   SunGridLimits cam_limits;
-   std::string cam_why;
-   float cam_build_ms = 0.0f, cam_mean_list = 0.0f;
-   uint32_t cam_cells = 0, cam_entries = 0, cam_max_list = 0, cam_max_list_interior = 0;
-   bool cam_this_frame = false;
-
-   // tile partition
-   uint32_t tp_rank = 0, tp_world = 1, tp_tile = 64;
-   DevBuf<uint32_t> owned_pixels;  // ascending pixel ids this rank owns (empty = the whole frame)
-   uint32_t n_owned = 0;
-   // composition of a partitioned frame without a host wait (uh_rccl_gather_tiles; the in-process group's uh_mgpu_compose): this
-   // rank's packed tiles, on the root every rank's, and the event behind the last pack / composition - the next frame's accumulate
-   // tail waits for it like for a frame's (last_acc)
-   DevBuf<float4> tile_send, tile_recv;
-   hipEvent_t ev_compose = nullptr;
-
-   // the hybrid graph's passes (uh_render_hybrid): images, the metal-pixel queue and a copy of the scene's meshes as gbuffer.vert
-   // reads them, all allocated by the first call
-   struct Hybrid {
-      DevBuf<float4> pos, nrm, pbr;
-      DevBuf<uchar4> alb, refl;
-      DevBuf<uint8_t> shadow;
-      DevBuf<uint32_t> queue, counter;
-      DevBuf<HybridMesh> meshes;
-      DevBuf<UhVertex> vertices;
-      DevBuf<uint32_t> indices;
-      uint64_t geom = 0;                       // geom_version the mesh tables were made for
-      // with device-resident meshes: each mesh's range in vertices / indices and the HostMesh::serial it holds (unchanged ranges
-      // are moved on the device instead of uploaded again)
-      struct Range { uint32_t vb, ib, nv, ni; uint64_t serial; };
-      std::vector<Range> layout;
-      hipEvent_t waits[2 * kMaxSlots + 1] = {};  // behind the frames in flight
-      // one record per stage: stage k < kHybridPasses is bit k of UH_HYBRID_* (rt_shadows, G-buffer, rt_reflections, SSAO, deferred,
-      // sky, present: the last call's), the environment's sub-passes follow (cube, irradiance, specular, BRDF LUT: the last build's)
-      // ms: the elapsed time, resolved from the two events by the first stats read after the stage ran and kept (a later read
-      // returns the same bits)
-      struct Stage {
-         hipEvent_t begin = nullptr, end = nullptr;
-         bool ran = false, timed = false;
-         float ms = 0.0f;
-      } stage[kHybridStages];
-      // the final frame's passes (SSAO, deferred, sky, present), allocated by the first call that asks for one of them
-      DevBuf<uint16_t> ssao;
-      DevBuf<float4> deferred;
-      DevBuf<uchar4> present;
-      DevBuf<uint32_t> sky_counter;
-      DevBuf<UhGpuLight> raw_lights;           // the uh_add_light table as added
-      DevBuf<HybridLight> lights;              // its records as the deferred pass reads them, the sun first
-      size_t lights_uploaded = SIZE_MAX;       // c->lights.size() when raw_lights was uploaded
-      uint32_t frame_lights = 0;               // lights the deferred pass of the last call evaluated (the sun included)
-      // the IBL maps of setup_cubemap_pass (UH_HYBRID_ENVIRONMENT), allocated by the first call that builds them
-      DevBuf<float4> env, irr, spec;
-      DevBuf<uint32_t> lut;
-      DevBuf<float4> taps;                     // the irradiance filter's tap table
-      uint32_t env_builds = 0;
-      float env_sun[3] = {0, 0, 0}, env_eye[3] = {0, 0, 0};  // what the last build was made with
-      // the cascaded shadow maps (UH_HYBRID_SHADOW_MAPS), allocated by the first call that renders them; freed by a size change
-      DevBuf<float> smaps;                     // 4 layers of smap_size^2
-      DevBuf<uint32_t> s_tile_count, s_tile_cursor, s_rec_count, s_tri_mesh, s_chunks, s_entries;
-      DevBuf<unsigned long long> s_totals;     // the grand totals of the two scans: records, tile entries
-      DevBuf<uint4> s_records;
-      DevBuf<float> s_mats;                    // [cascade][mesh][16]
-      DevBuf<UhShadowmapParams> s_params;      // the snapshot the deferred pass reads
-      std::vector<float> s_mats_host;
-      uint64_t s_geom = 0;                     // geom_version of s_tri_mesh / s_rec_count
-      bool params_set = false;
-      UhShadowmapParams params{}, snapshot{}, pending{};  // the last uh_set_shadowmap_params; what the maps were rendered with;
-                                                          // what the render in progress uses
-      uint32_t s_renders = 0, smap_size = 0, s_tris[4] = {0, 0, 0, 0};
-      bool gbuffer_done = false;               // a G-buffer pass has been enqueued (the marching-cubes pass's depth seed reads it)
-      bool gbuffer_rasterised = false;         // the last G-buffer pass enqueued was rasterised: its depth is the marching-cubes seed
-      // the rasterised G-buffer (UH_HYBRID_GBUFFER_RASTER), allocated by the first rasterised pass: its depth buffer, visibility,
-      // surviving records and binning buffers
-      DevBuf<float> gr_depth;
-      DevBuf<uint32_t> gr_vis, gr_rec_of, gr_covered;
-      SceneBins gr_bins;
-      uint32_t gr_renders = 0, gr_pieces = 0;
-      // the marching-cubes pass (UH_HYBRID_MARCHING_CUBES), allocated by the first pass: its depth buffer, visibility, surviving
-      // records, light records, extracted triangles and the forward rasteriser's binning buffers
-      DevBuf<float> mc_depth;
-      DevBuf<uint32_t> mc_vis, mc_rec_of, mc_covered;
-      DevBuf<HybridLight> mc_lights;
-      DevBuf<UhVertex> mc_verts;               // 3 per triangle, extraction order
-      DevBuf<uint32_t> mc_block_counts, mc_tile_count, mc_tile_cursor, mc_rec_count, mc_chunks, mc_entries;
-      DevBuf<unsigned long long> mc_totals;    // the grand totals of the three scans: triangles, records, tile entries
-      DevBuf<uint4> mc_records;
-      DevBuf<float> mc_mats;                   // (P V) I column-major, the identity 3x4, then P V (44 floats)
-      DevBuf<HybridMesh> mc_mesh;              // mesh_index 0's maps with world = identity
-      uint32_t mc_renders = 0, mc_tris = 0, mc_pieces = 0, mc_lights_used = 0;
-      float mc_time = 0.0f;
-
-      // the three groups allocated on first use, each named once for allocation and uh_destroy: f(buffer, length), n pixels; a
-      // group's last buffer is allocated last, its pointer says "allocated"
-      template <class F> void rt_images(size_t n, F&& f) {
-         f(pos, n), f(nrm, n), f(pbr, n), f(alb, n), f(refl, n), f(shadow, n), f(queue, n), f(counter, 1);
-      }
-      template <class F> void frame_images(size_t n, F&& f) {
-         f(ssao, n), f(deferred, n), f(present, n), f(lights, UH_MAX_GPU_LIGHTS + 1), f(sky_counter, 1);
-      }
-      template <class F> void shadow_maps(F&& f) {
-         f(smaps, 0), f(s_tile_count, 0), f(s_tile_cursor, 0), f(s_rec_count, 0), f(s_tri_mesh, 0), f(s_chunks, 0), f(s_entries, 0),
-            f(s_totals, 0), f(s_records, 0), f(s_mats, 0), f(s_params, 0);
-      }
-      template <class F> void mc_images(size_t n, F&& f) {
-         f(mc_depth, n), f(mc_vis, n), f(mc_rec_of, n), f(mc_lights, UH_MAX_GPU_LIGHTS + 1), f(mc_block_counts, kMcBlocks), f(mc_mats, 44),
-            f(mc_mesh, 1), f(mc_totals, 3), f(mc_covered, 1);
-      }
-      template <class F> void mc_bins(F&& f) {
-         f(mc_verts, 0), f(mc_tile_count, 0), f(mc_tile_cursor, 0), f(mc_rec_count, 0), f(mc_chunks, 0), f(mc_entries, 0), f(mc_records, 0);
-      }
-      template <class F> void gr_images(size_t n, F&& f) { f(gr_depth, n), f(gr_vis, n), f(gr_rec_of, n), f(gr_covered, 1); }
-      template <class F> void env_maps(F&& f) {
-         const size_t cube = env_mip_offset(kEnvMips);
-         f(env, cube), f(irr, 6 * (size_t)kEnvSize * kEnvSize), f(spec, cube), f(lut, (size_t)kLutSize * kLutSize);
-      }
-   } hy;
-
-   // the forward graph (uh_render_forward): its images, light records and binning buffers, allocated by the first call; it shares the
-   // hybrid graph's mesh tables, uploaded light table and shadow maps
-   struct Forward {
-      DevBuf<float4> color;                    // forward_output RGBA32F
-      DevBuf<float> depth;
-      DevBuf<uint32_t> vis, rec_of, covered;   // draw index, surviving record per pixel; [0] the covered pixels of the last pass
-      DevBuf<uchar4> present;                  // the forward graph's present image, B8G8R8A8
-      DevBuf<HybridLight> lights;              // forward.frag's light records, the sun first
-      SceneBins bins;
-      // pass k: 0 shadow maps, 1 forward, 2 present (the last call's; ms resolved by the first stats read and kept)
-      uh_ctx::Hybrid::Stage stage[3];
-      uint32_t renders = 0, pieces = 0, lights_used = 0;
-      template <class F> void images(size_t n, F&& f) {
-         f(depth, n), f(vis, n), f(rec_of, n), f(present, n), f(lights, UH_MAX_GPU_LIGHTS + 1), f(covered, 1), f(color, n);
-      }
-   } fw;
-};
-
-namespace {
+}
 
 int fail(uh_ctx* c, int code, const std::string& msg) {
    if (c)
@@ -501,12 +39,7 @@ int fail(uh_ctx* c, int code, const std::string& msg) {
    return code;
 }
 
-#define HIP_TRY(ctx, expr)                                                                                   \
-   do {                                                                                                      \
-      hipError_t e_ = (expr);                                                                                \
-      if (e_ != hipSuccess) return fail(ctx, e_ == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, \
-                                        std::string(#expr) + ": " + hipGetErrorString(e_));                 \
-   } while (0)
+namespace {
 
 bool is_identity3x4(const float* m) {
    static const float I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
@@ -538,10 +71,6 @@ void set_transform(HostMesh& m, const float* w) {
    } else {
       invert3x3(w, m.w2o);
    }
-}
-
-LaunchCfg cfg(uh_ctx* c) {
-   return LaunchCfg{c->stream, c->num_cus, c->closest_blocks_per_cu, c->shadow_blocks_per_cu, c->count_visits, c->fused_blocks_per_cu};
 }
 
 void begin_timed(uh_ctx* c, int kind, hipStream_t stream = nullptr) {
@@ -577,6 +106,10 @@ void drain_timed(uh_ctx* c) {
 }
 
 }  // namespace
+
+LaunchCfg cfg(uh_ctx* c) {
+   return LaunchCfg{c->stream, c->num_cus, c->closest_blocks_per_cu, c->shadow_blocks_per_cu, c->count_visits, c->fused_blocks_per_cu};
+}
 
 namespace {
 std::string hip_version_string(int v) { return std::to_string(v / 10000000) + "." + std::to_string(v / 100000 % 100) + "." + std::to_string(v % 100000); }
@@ -740,42 +273,15 @@ void uh_destroy(uh_ctx* c) {
    c->output.release();
    for (auto& r : c->reservoirs) r.release();
    c->dstats.release();
-   {  // (its events were recorded on the slots' streams: they go first)
-      uh_ctx::Hybrid& h = c->hy;
-      const auto release = [](auto& b, size_t) { b.release(); };
-      h.rt_images(0, release);
-      h.frame_images(0, release);
-      h.env_maps(release);
-      h.shadow_maps(release);
-      h.mc_images(0, release);
-      h.mc_bins(release);
-      h.gr_images(0, release);
-      h.gr_bins.each(release);
-      h.meshes.release();
-      h.vertices.release();
-      h.indices.release();
-      for (HostMesh& m : c->meshes)
-         if (m.d_verts) (void)hipFree(m.d_verts);
-      for (hipEvent_t ev : {c->iso.begin, c->iso.end})
-         if (ev) (void)hipEventDestroy(ev);
-      c->iso.counts.release();
-      c->iso.chunks.release();
-      c->iso.box.release();
-      c->iso.total.release();
-      h.raw_lights.release();
-      h.taps.release();
-      for (hipEvent_t ev : h.waits)
-         if (ev) (void)hipEventDestroy(ev);
-      for (const auto& st : h.stage)
-         for (hipEvent_t ev : {st.begin, st.end})
-            if (ev) (void)hipEventDestroy(ev);
-      uh_ctx::Forward& f = c->fw;
-      f.images(0, release);
-      f.bins.each(release);
-      for (const auto& st : f.stage)
-         for (hipEvent_t ev : {st.begin, st.end})
-            if (ev) (void)hipEventDestroy(ev);
-   }
+   for (HostMesh& m : c->meshes)
+      if (m.d_verts) (void)hipFree(m.d_verts);
+   for (hipEvent_t ev : {c->iso.begin, c->iso.end})
+      if (ev) (void)hipEventDestroy(ev);
+   c->iso.counts.release();
+   c->iso.chunks.release();
+   c->iso.box.release();
+   c->iso.total.release();
+   destroy_graphs(c);  // (their events were recorded on the slots' streams: they go first)
    for (auto& s : c->slots) s.destroy();
    for (hipEvent_t ev : c->ev_band)
       if (ev) (void)hipEventDestroy(ev);
@@ -876,7 +382,6 @@ int uh_set_instance_transform(uh_ctx* c, uint32_t mesh_index, const float world3
    return UH_OK;
 }
 
-static int sync_all(uh_ctx* c);
 
 // per-mesh shading records, light table, texture descriptors: everything of the scene except the geometry
 static int upload_scene_tables(uh_ctx* c) {
@@ -1114,10 +619,10 @@ int uh_refit_acceleration(uh_ctx* c) {
 }
 
 // brackets of UhIsosurfaceUpdateStats::scatter_ms on the context's stream (the events exist once an update has run)
-static void iso_scatter_begin(uh_ctx* c) {
+extern "C++" void iso_scatter_begin(uh_ctx* c) {
    if (c->iso.begin) (void)hipEventRecord(c->iso.begin, c->stream);
 }
-static int iso_scatter_end(uh_ctx* c, bool add) {
+extern "C++" int iso_scatter_end(uh_ctx* c, bool add) {
    if (!c->iso.begin) return UH_OK;
    HIP_TRY(c, hipEventRecord(c->iso.end, c->stream));
    HIP_TRY(c, hipEventSynchronize(c->iso.end));
@@ -1393,7 +898,7 @@ static int build_on_device(uh_ctx* c) {
    return UH_OK;
 }
 
-static FrameParams make_params(uh_ctx* c, const UhViewUniformData& v) {
+extern "C++" FrameParams make_params(uh_ctx* c, const UhViewUniformData& v) {
    FrameParams fp;
    std::memset(&fp, 0, sizeof(fp));
    std::memcpy(fp.inv_view, v.inverse_view, sizeof(fp.inv_view));
@@ -1433,7 +938,7 @@ static FrameParams make_params(uh_ctx* c, const UhViewUniformData& v) {
 }
 
 // every stream of every slot idle (read-backs, scene rebuilds, stats)
-static int sync_all(uh_ctx* c) {
+extern "C++" int sync_all(uh_ctx* c) {
    if (c->restir_stream) HIP_TRY(c, hipStreamSynchronize(c->restir_stream));
    for (auto& s : c->slots) {
       if (!s.ready) continue;
@@ -2152,7 +1657,7 @@ static int staged_read(uh_ctx* c, void* dst, const void* src, size_t bytes) {
    return UH_OK;
 }
 
-static int read_back(uh_ctx* c, void* dst, const void* src, size_t bytes) {
+extern "C++" int read_back(uh_ctx* c, void* dst, const void* src, size_t bytes) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    if (!dst) return fail(c, UH_ERR_INVALID_ARGUMENT, "null destination");
    HIP_TRY(c, hipSetDevice(c->device));
@@ -2437,7 +1942,7 @@ int uh_set_option(uh_ctx* c, const char* name, int value) {
       if ((uint32_t)value != c->shadow_map_size) {  // the maps go: the deferred pass with shadows is refused until they are rendered again
          if (int st = sync_all(c)) return st;
          c->hy.shadow_maps([](auto& b, size_t) { b.release(); });
-         c->hy.s_geom = 0;
+         c->hy.s_bins.geom = 0;
          c->hy.smap_size = 0;
       }
       c->shadow_map_size = (uint32_t)value;
@@ -2984,1107 +2489,6 @@ int uh_get_isosurface_update_stats(uh_ctx* c, UhIsosurfaceUpdateStats* out) {
    const uh_ctx::IsoUpdate& u = c->iso;
    out->device_bytes = u.counts.n * sizeof(uint32_t) + u.chunks.n * sizeof(uint32_t) + u.box.n * sizeof(uint32_t) + u.total.n * sizeof(unsigned long long);
    for (const HostMesh& m : c->meshes) out->device_bytes += m.d_capacity * sizeof(UhVertex);
-   return UH_OK;
-}
-
-// ---- the hybrid graph's ray-traced passes (utopian_hip.h "uh_render_hybrid") ----
-// allocates one of uh_ctx::Hybrid's groups, visit(f) naming its buffers; stops at the first error, before the group's last buffer
-extern "C++" template <class Visit> static int alloc_group(uh_ctx* c, Visit visit) {
-   hipError_t e = hipSuccess;
-   visit([&e](auto& b, size_t n) {
-      if (e == hipSuccess) e = b.alloc(n);
-   });
-   if (e != hipSuccess)
-      return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string("uh_render_hybrid: allocation: ") + hipGetErrorString(e));
-   return UH_OK;
-}
-
-// the ray-traced images and the events (first call)
-// the events of the hybrid stages and of the waits behind the frames in flight (first hybrid or forward call)
-static int hybrid_events(uh_ctx* c) {
-   uh_ctx::Hybrid& h = c->hy;
-   for (hipEvent_t& ev : h.waits)
-      if (!ev) HIP_TRY(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-   for (auto& st : h.stage)
-      for (hipEvent_t* ev : {&st.begin, &st.end})
-         if (!*ev) HIP_TRY(c, hipEventCreate(ev));
-   return UH_OK;
-}
-static int hybrid_alloc(uh_ctx* c) {
-   uh_ctx::Hybrid& h = c->hy;
-   if (h.counter.p) return UH_OK;
-   if (int st = hybrid_events(c)) return st;
-   return alloc_group(c, [&](auto f) { h.rt_images((size_t)c->W * c->H, f); });
-}
-
-// the meshes as the vertex and fragment shaders read them: vertices, indices, the instance's world matrix and the material's maps
-static int hybrid_tables(uh_ctx* c) {
-   uh_ctx::Hybrid& h = c->hy;
-   if (h.geom == c->geom_version && h.meshes.p) return UH_OK;
-   std::vector<HybridMesh> ms(c->meshes.size());
-   size_t nv = 0, ni = 0;
-   for (size_t i = 0; i < c->meshes.size(); i++) {
-      const HostMesh& m = c->meshes[i];
-      HybridMesh& d = ms[i];
-      for (int r = 0; r < 3; r++)
-         for (int k = 0; k < 3; k++) d.o2w[3 * r + k] = m.o2w[4 * r + k];
-      std::memcpy(d.w2o, m.w2o, sizeof(d.w2o));
-      d.vertex_base = (uint32_t)nv;
-      d.index_base = (uint32_t)ni;
-      d.diffuse_map = m.material.diffuse_map;
-      d.normal_map = m.material.normal_map;
-      d.metallic_roughness_map = m.material.metallic_roughness_map;
-      d.occlusion_map = m.material.occlusion_map;
-      nv += m.num_vertices();
-      ni += m.num_indices();
-   }
-   if (nv >= (1ull << 32) || ni >= (1ull << 32)) return fail(c, UH_ERR_CAPACITY, "uh_render_hybrid: more than 2^32 vertices or indices");
-   bool any_dev = false;
-   for (const HostMesh& m : c->meshes) any_dev = any_dev || m.dev;
-   if (any_dev) {
-      // a second pair of arrays; per mesh: a range the old pair holds for the same serial is copied across on the device, a
-      // device-resident mesh is copied from its vertex buffer with an iota index list, a host-resident one is uploaded
-      DevBuf<UhVertex> vb;
-      DevBuf<uint32_t> ib;
-      const auto give_up = [&](hipError_t e) {
-         (void)hipStreamSynchronize(c->stream);
-         vb.release(), ib.release();
-         return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string("mesh tables: ") + hipGetErrorString(e));
-      };
-      hipError_t e;
-      bool in_place = h.meshes.p && h.layout.size() == c->meshes.size();
-      for (size_t i = 0; in_place && i < c->meshes.size(); i++)
-         in_place = h.layout[i].nv == c->meshes[i].num_vertices() && h.layout[i].ni == c->meshes[i].num_indices();
-      if (in_place) {
-         // no count changed: the updated meshes' vertices over their old ones (their iota stays), the bases as they are
-         iso_scatter_begin(c);
-         for (size_t i = 0; i < c->meshes.size(); i++) {
-            const HostMesh& m = c->meshes[i];
-            if (h.layout[i].serial == m.serial) continue;
-            if (h.layout[i].nv) HIP_TRY(c, hipMemcpyAsync(h.vertices.p + h.layout[i].vb, m.d_verts, h.layout[i].nv * sizeof(UhVertex), hipMemcpyDeviceToDevice, c->stream));
-            h.layout[i].serial = ~0ull;  // (until the copy is known to have completed)
-         }
-         HIP_TRY(c, hipMemcpyAsync(h.meshes.p, ms.data(), ms.size() * sizeof(HybridMesh), hipMemcpyHostToDevice, c->stream));
-         if (int st = iso_scatter_end(c, true)) return st;
-         HIP_TRY(c, hipStreamSynchronize(c->stream));
-         for (size_t i = 0; i < c->meshes.size(); i++) h.layout[i].serial = c->meshes[i].serial;
-         h.geom = c->geom_version;
-         return UH_OK;
-      }
-      if ((e = vb.alloc(nv)) != hipSuccess || (e = ib.alloc(ni)) != hipSuccess) return give_up(e);
-      std::vector<uh_ctx::Hybrid::Range> layout(c->meshes.size());
-      iso_scatter_begin(c);
-      for (size_t i = 0; i < c->meshes.size(); i++) {
-         const HostMesh& m = c->meshes[i];
-         uh_ctx::Hybrid::Range& r = layout[i];
-         r = uh_ctx::Hybrid::Range{ms[i].vertex_base, ms[i].index_base, (uint32_t)m.num_vertices(), (uint32_t)m.num_indices(), m.serial};
-         const uh_ctx::Hybrid::Range* old = h.meshes.p && i < h.layout.size() ? &h.layout[i] : nullptr;
-         e = hipSuccess;
-         if (old && old->serial == r.serial && old->nv == r.nv && old->ni == r.ni) {
-            if (r.nv) e = hipMemcpyAsync(vb.p + r.vb, h.vertices.p + old->vb, r.nv * sizeof(UhVertex), hipMemcpyDeviceToDevice, c->stream);
-            if (e == hipSuccess && r.ni) e = hipMemcpyAsync(ib.p + r.ib, h.indices.p + old->ib, r.ni * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream);
-         } else if (m.dev) {
-            if (r.nv) e = hipMemcpyAsync(vb.p + r.vb, m.d_verts, r.nv * sizeof(UhVertex), hipMemcpyDeviceToDevice, c->stream);
-            uhi_iota(c->stream, ib.p + r.ib, r.ni);
-            if (e == hipSuccess) e = hipGetLastError();
-         } else {
-            if (r.nv) e = hipMemcpy(vb.p + r.vb, m.vertices.data(), r.nv * sizeof(UhVertex), hipMemcpyHostToDevice);
-            if (e == hipSuccess && r.ni) e = hipMemcpy(ib.p + r.ib, m.indices.data(), r.ni * sizeof(uint32_t), hipMemcpyHostToDevice);
-         }
-         if (e != hipSuccess) return give_up(e);
-      }
-      if ((e = h.meshes.n == ms.size() && h.meshes.p ? hipSuccess : h.meshes.alloc(ms.size())) != hipSuccess) return give_up(e);
-      if ((e = hipMemcpyAsync(h.meshes.p, ms.data(), ms.size() * sizeof(HybridMesh), hipMemcpyHostToDevice, c->stream)) != hipSuccess) return give_up(e);
-      if (int st = iso_scatter_end(c, true)) {
-         vb.release(), ib.release();
-         return st;
-      }
-      if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return give_up(e);
-      std::swap(h.vertices, vb);
-      std::swap(h.indices, ib);
-      vb.release(), ib.release();
-      h.layout = std::move(layout);
-      h.geom = c->geom_version;
-      return UH_OK;
-   }
-   std::vector<UhVertex> verts;
-   std::vector<uint32_t> idx;
-   verts.reserve(nv);
-   idx.reserve(ni);
-   for (const HostMesh& m : c->meshes) {
-      verts.insert(verts.end(), m.vertices.begin(), m.vertices.end());
-      idx.insert(idx.end(), m.indices.begin(), m.indices.end());
-   }
-   HIP_TRY(c, h.meshes.alloc(ms.size()));
-   HIP_TRY(c, h.vertices.alloc(verts.size()));
-   HIP_TRY(c, h.indices.alloc(idx.size()));
-   if (!ms.empty()) HIP_TRY(c, hipMemcpyAsync(h.meshes.p, ms.data(), ms.size() * sizeof(HybridMesh), hipMemcpyHostToDevice, c->stream));
-   if (!verts.empty()) HIP_TRY(c, hipMemcpyAsync(h.vertices.p, verts.data(), verts.size() * sizeof(UhVertex), hipMemcpyHostToDevice, c->stream));
-   if (!idx.empty()) HIP_TRY(c, hipMemcpyAsync(h.indices.p, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-   HIP_TRY(c, hipStreamSynchronize(c->stream));  // the host vectors go out of scope
-   h.layout.resize(ms.size());
-   for (size_t i = 0; i < ms.size(); i++)
-      h.layout[i] = uh_ctx::Hybrid::Range{ms[i].vertex_base, ms[i].index_base, (uint32_t)c->meshes[i].num_vertices(), (uint32_t)c->meshes[i].num_indices(), c->meshes[i].serial};
-   h.geom = c->geom_version;
-   return UH_OK;
-}
-
-// the final frame's images and light table (first call with one of its bits); the metal-pixel queue of rt_reflections is reused
-// for the sky pixels, which are queued after rt_reflections has run
-static int hybrid_frame_alloc(uh_ctx* c) {
-   uh_ctx::Hybrid& h = c->hy;
-   if (h.sky_counter.p) return UH_OK;
-   return alloc_group(c, [&](auto f) { h.frame_images((size_t)c->W * c->H, f); });
-}
-
-// the uh_add_light table as the deferred pass reads it (lights are only ever appended: the count says whether it changed)
-static int hybrid_light_table(uh_ctx* c) {
-   uh_ctx::Hybrid& h = c->hy;
-   if (h.lights_uploaded == c->lights.size()) return UH_OK;
-   HIP_TRY(c, h.raw_lights.alloc(c->lights.size()));
-   if (!c->lights.empty())
-      HIP_TRY(c, hipMemcpyAsync(h.raw_lights.p, c->lights.data(), c->lights.size() * sizeof(UhGpuLight), hipMemcpyHostToDevice, c->stream));
-   HIP_TRY(c, hipStreamSynchronize(c->stream));
-   h.lights_uploaded = c->lights.size();
-   return UH_OK;
-}
-
-// the IBL maps (first call with UH_HYBRID_ENVIRONMENT) and the irradiance filter's tap table: irradiance_filter.frag:38-46's phi and
-// theta are float accumulators stepped by 0.025 while below 2 PI and PI / 2 (float); sin and cos in double, rounded to float, and the
-// products tangentSample.x = sin(theta) cos(phi), .y = sin(theta) sin(phi) in float
-static int env_alloc(uh_ctx* c) {
-   uh_ctx::Hybrid& h = c->hy;
-   if (h.lut.p) return UH_OK;
-   std::vector<float4> taps;
-   taps.reserve(kIrrPhi * kIrrTheta);
-   const float pi = 3.14159265358979323846f, delta = 0.025f;
-   for (float phi = 0.0f; phi < 2.0f * pi; phi += delta) {
-      for (float theta = 0.0f; theta < 0.5f * pi; theta += delta) {
-         const float st = (float)std::sin((double)theta), ct = (float)std::cos((double)theta);
-         const float cp = (float)std::cos((double)phi), sp = (float)std::sin((double)phi);
-         taps.push_back(make_float4(st * cp, st * sp, ct, st));
-      }
-   }
-   if (taps.size() != (size_t)kIrrPhi * kIrrTheta) return fail(c, UH_ERR_HIP, "irradiance tap count");
-   HIP_TRY(c, h.taps.alloc(taps.size()));
-   HIP_TRY(c, hipMemcpyAsync(h.taps.p, taps.data(), taps.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-   HIP_TRY(c, hipStreamSynchronize(c->stream));
-   return alloc_group(c, [&](auto f) { h.env_maps(f); });
-}
-
-// ---- the cascaded shadow maps (utopian_hip.h "UH_HYBRID_SHADOW_MAPS"; shadow_map.hip) ----
-// vp * W for every cascade and mesh: W the instance's 3x4 from the last build or refit with row (0, 0, 0, 1); element (r, c) summed
-// ((a(r,0) b(0,c) + a(r,1) b(1,c)) + a(r,2) b(2,c)) + a(r,3) b(3,c)
-static void cascade_mesh_matrices(const uh_ctx* c, const UhShadowmapParams& p, std::vector<float>& out) {
-   const size_t nm = c->meshes.size();
-   out.assign(4 * nm * 16, 0.0f);
-   for (int k = 0; k < 4; k++) {
-      const float* a = p.view_projection_matrices[k];
-      for (size_t m = 0; m < nm; m++) {
-         const float* o = c->meshes[m].o2w;
-         float w[16];  // column-major
-         for (int col = 0; col < 4; col++) {
-            for (int r = 0; r < 3; r++) w[4 * col + r] = o[4 * r + col];
-            w[4 * col + 3] = col == 3 ? 1.0f : 0.0f;
-         }
-         float* d = &out[((size_t)k * nm + m) * 16];
-         for (int col = 0; col < 4; col++)
-            for (int r = 0; r < 4; r++)
-               d[4 * col + r] = ((a[r] * w[4 * col] + a[4 + r] * w[4 * col + 1]) + a[8 + r] * w[4 * col + 2]) + a[12 + r] * w[4 * col + 3];
-      }
-   }
-}
-
-// the rasterisers' per-triangle mesh ids (tm, made on the host): uploaded, or - once a mesh is device-resident, whose count changes with
-// every update - written on the device, one fill per mesh range, on the stream the rasterisers run on
-static int fill_tri_mesh(uh_ctx* c, uint32_t* dst, const std::vector<uint32_t>& tm) {
-   bool any_dev = false;
-   for (const HostMesh& m : c->meshes) any_dev = any_dev || m.dev;
-   if (!any_dev) {
-      if (!tm.empty()) HIP_TRY(c, hipMemcpy(dst, tm.data(), tm.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-      return UH_OK;
-   }
-   size_t at = 0;
-   for (size_t i = 0; i < c->meshes.size(); at += c->meshes[i].tris(), i++) uhi_fill_u32(c->stream, dst + at, (uint32_t)c->meshes[i].tris(), (uint32_t)i);
-   HIP_TRY(c, hipGetLastError());
-   return UH_OK;
-}
-
-// count, scan, emit, resolve: the records' and tile entries' totals come back to the host in between (the buffers grow to them)
-static int render_shadow_maps(uh_ctx* c, const LaunchCfg& lc, const char* verb) {
-   uh_ctx::Hybrid& h = c->hy;
-   const uint32_t S = c->shadow_map_size, tiles_x = (S + kShadowTile - 1) / kShadowTile, tiles = 4 * tiles_x * tiles_x;
-   size_t ntri = 0;
-   for (const HostMesh& m : c->meshes) ntri += m.tris();
-   if (4 * ntri >= (1ull << 32)) return fail(c, UH_ERR_CAPACITY, std::string(verb) + ": shadow maps of more than 2^30 triangles");
-   const auto grow = [&](auto& b, size_t n) -> int {
-      if (b.p && b.n >= n) return UH_OK;
-      const hipError_t e = b.alloc(n);
-      if (e != hipSuccess)
-         return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string(verb) + ": allocation: " + hipGetErrorString(e));
-      return UH_OK;
-   };
-   for (int st : {grow(h.smaps, 4 * (size_t)S * S), grow(h.s_tile_count, tiles), grow(h.s_tile_cursor, tiles), grow(h.s_totals, 2),
-                  grow(h.s_params, 1), grow(h.s_mats, std::max<size_t>(1, 64 * c->meshes.size())),
-                  grow(h.s_chunks, std::max<size_t>(1, scan_chunk_count((uint32_t)std::max<size_t>(4 * ntri, tiles))))})
-      if (st) return st;
-   if (h.s_geom != c->geom_version || !h.s_rec_count.p) {
-      std::vector<uint32_t> tm;
-      tm.reserve(ntri);
-      for (size_t m = 0; m < c->meshes.size(); m++) tm.insert(tm.end(), c->meshes[m].tris(), (uint32_t)m);
-      HIP_TRY(c, h.s_tri_mesh.alloc(std::max<size_t>(1, ntri)));
-      HIP_TRY(c, h.s_rec_count.alloc(std::max<size_t>(1, 4 * ntri)));
-      if (int st = fill_tri_mesh(c, h.s_tri_mesh.p, tm)) return st;
-      h.s_geom = c->geom_version;
-   }
-   // until this render completes the maps and their params are invalid: a failure below leaves the deferred pass refused
-   h.smap_size = 0;
-   h.pending = h.params;
-   cascade_mesh_matrices(c, h.pending, h.s_mats_host);
-   if (!h.s_mats_host.empty())
-      HIP_TRY(c, hipMemcpyAsync(h.s_mats.p, h.s_mats_host.data(), h.s_mats_host.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-   HIP_TRY(c, hipMemcpyAsync(h.s_params.p, &h.pending, sizeof(UhShadowmapParams), hipMemcpyHostToDevice, c->stream));
-   HIP_TRY(c, hipMemsetAsync(h.s_tile_count.p, 0, tiles * sizeof(uint32_t), c->stream));
-   ShadowDev sd{};
-   sd.vertices = h.vertices.p;
-   sd.indices = h.indices.p;
-   sd.meshes = h.meshes.p;
-   sd.tri_mesh = h.s_tri_mesh.p;
-   sd.mats = h.s_mats.p;
-   sd.num_tris = (uint32_t)ntri;
-   sd.num_meshes = (uint32_t)c->meshes.size();
-   sd.size = S;
-   sd.tiles_x = tiles_x;
-   sd.rec_count = h.s_rec_count.p;
-   sd.tile_count = h.s_tile_count.p;
-   sd.tile_cursor = h.s_tile_cursor.p;
-   sd.maps = h.smaps.p;
-   launch_shadow_count(lc, sd);
-   unsigned long long totals[2] = {0, 0};
-   uint32_t first[4] = {0, 0, 0, 0};  // the first record of each cascade
-   if (ntri) device_exclusive_scan_u32(h.s_rec_count.p, (uint32_t)(4 * ntri), h.s_chunks.p, h.s_totals.p, c->stream);
-   device_exclusive_scan_u32(h.s_tile_count.p, tiles, h.s_chunks.p, h.s_totals.p + 1, c->stream);
-   HIP_TRY(c, hipMemcpyAsync(h.s_tile_cursor.p, h.s_tile_count.p, tiles * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-   HIP_TRY(c, hipStreamSynchronize(c->stream));
-   HIP_TRY(c, hipMemcpy(totals + 1, h.s_totals.p + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-   if (ntri) {
-      HIP_TRY(c, hipMemcpy(totals, h.s_totals.p, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-      for (int k = 1; k < 4; k++) HIP_TRY(c, hipMemcpy(first + k, h.s_rec_count.p + k * ntri, sizeof(uint32_t), hipMemcpyDeviceToHost));
-   }
-   if (totals[0] >= (1ull << 32) || totals[1] >= (1ull << 32))
-      return fail(c, UH_ERR_CAPACITY, std::string(verb) + ": shadow maps with 2^32 or more triangle pieces or tile entries");
-   for (int st : {grow(h.s_records, std::max<size_t>(1, 3 * (size_t)totals[0])), grow(h.s_entries, std::max<size_t>(1, (size_t)totals[1]))})
-      if (st) return st;
-   sd.records = h.s_records.p;
-   sd.entries = h.s_entries.p;
-   launch_shadow_emit(lc, sd);
-   launch_shadow_resolve(lc, sd);
-   for (int k = 0; k < 4; k++) h.s_tris[k] = (k < 3 ? first[k + 1] : (uint32_t)totals[0]) - first[k];
-   h.snapshot = h.pending;
-   h.smap_size = S;
-   h.s_renders++;
-   return UH_OK;
-}
-
-// behind every frame in flight: the context's first stream (slot 0's, where hybrid and forward calls run) waits for the others
-static int wait_frames_in_flight(uh_ctx* c) {
-   uh_ctx::Hybrid& h = c->hy;
-   int w = 0;
-   for (uint32_t i = 1; i < kMaxSlots; i++) {
-      const Slot& s = c->slots[i];
-      if (!s.ready) continue;
-      for (hipStream_t st : {s.stream, s.side}) {
-         HIP_TRY(c, hipEventRecord(h.waits[w], st));
-         HIP_TRY(c, hipStreamWaitEvent(c->stream, h.waits[w++], 0));
-      }
-   }
-   if (c->restir_stream) {
-      HIP_TRY(c, hipEventRecord(h.waits[w], c->restir_stream));
-      HIP_TRY(c, hipStreamWaitEvent(c->stream, h.waits[w++], 0));
-   }
-   if (c->slots[0].ready) {
-      HIP_TRY(c, hipEventRecord(h.waits[w], c->slots[0].side));
-      HIP_TRY(c, hipStreamWaitEvent(c->stream, h.waits[w++], 0));
-   }
-   return UH_OK;
-}
-
-// ---- the marching-cubes pass (utopian_hip.h "UH_HYBRID_MARCHING_CUBES"; isosurface.hip, forward.hip) ----
-// the column-major product a b, element (r, c) summed ((a(r,0) b(0,c) + a(r,1) b(1,c)) + a(r,2) b(2,c)) + a(r,3) b(3,c): mat4_mul
-static void mat4_mul(const float* a, const float* b, float* o) {
-   for (int col = 0; col < 4; col++)
-      for (int r = 0; r < 4; r++) o[4 * col + r] = ((a[r] * b[4 * col] + a[4 + r] * b[4 * col + 1]) + a[8 + r] * b[4 * col + 2]) + a[12 + r] * b[4 * col + 3];
-}
-
-// extraction (count, scan, emit), depth seed, count, scan, emit, seeded resolve, then forward.frag into deferred_output: the triangle
-// count and the binning totals come back to the host in between (the buffers grow to them)
-static int render_mc_pass(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformData& view) {
-   uh_ctx::Hybrid& h = c->hy;
-   const uint32_t W = c->W, H = c->H, tiles_x = (W + kForwardTile - 1) / kForwardTile, tiles_y = (H + kForwardTile - 1) / kForwardTile;
-   const uint32_t tiles = tiles_x * tiles_y;
-   const auto grow = [&](auto& b, size_t n) -> int {
-      if (b.p && b.n >= n) return UH_OK;
-      const hipError_t e = b.alloc(n);
-      if (e != hipSuccess)
-         return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string("uh_render_hybrid: marching cubes: allocation: ") + hipGetErrorString(e));
-      return UH_OK;
-   };
-   for (int st : {grow(h.mc_tile_count, tiles), grow(h.mc_tile_cursor, tiles), grow(h.mc_chunks, scan_chunk_count(std::max<uint32_t>(kMcBlocks, tiles)))})
-      if (st) return st;
-   // the material of mesh_index 0 under world = identity, and the matrices: (P V) I as forward_mesh_matrices makes it, then P V
-   HybridMesh mm{};
-   for (int k = 0; k < 9; k++) mm.o2w[k] = mm.w2o[k] = k % 4 == 0 ? 1.0f : 0.0f;
-   const UhGpuMaterial& m0 = c->meshes[0].material;
-   mm.diffuse_map = m0.diffuse_map;
-   mm.normal_map = m0.normal_map;
-   mm.metallic_roughness_map = m0.metallic_roughness_map;
-   mm.occlusion_map = m0.occlusion_map;
-   float mats[44], pv[16], ident[16];
-   for (int k = 0; k < 16; k++) ident[k] = k % 5 == 0 ? 1.0f : 0.0f;
-   mat4_mul(view.projection, view.view, pv);
-   mat4_mul(pv, ident, mats);
-   for (int r = 0; r < 3; r++)
-      for (int k = 0; k < 4; k++) mats[16 + 4 * r + k] = r == k ? 1.0f : 0.0f;
-   std::memcpy(mats + 28, pv, sizeof(pv));
-   HIP_TRY(c, hipMemcpyAsync(h.mc_mesh.p, &mm, sizeof(mm), hipMemcpyHostToDevice, c->stream));
-   HIP_TRY(c, hipMemcpyAsync(h.mc_mats.p, mats, sizeof(mats), hipMemcpyHostToDevice, c->stream));
-   HIP_TRY(c, hipMemsetAsync(h.mc_tile_count.p, 0, tiles * sizeof(uint32_t), c->stream));
-   HIP_TRY(c, hipMemsetAsync(h.mc_covered.p, 0, sizeof(uint32_t), c->stream));
-   // marching_cubes.comp at view.time: per-block counts, their scan, then (with the total known) the triangles
-   if (!uhi_mc_extract_count(c->stream, view.time, h.mc_block_counts.p)) return fail(c, UH_ERR_HIP, "uh_render_hybrid: marching-cubes tables");
-   device_exclusive_scan_u32(h.mc_block_counts.p, kMcBlocks, h.mc_chunks.p, h.mc_totals.p, c->stream);
-   ForwardDev fd{};
-   fd.meshes = h.mc_mesh.p;
-   fd.mats = h.mc_mats.p;
-   fd.W = W;
-   fd.H = H;
-   fd.tiles_x = tiles_x;
-   fd.tiles_y = tiles_y;
-   fd.tile_count = h.mc_tile_count.p;
-   fd.tile_cursor = h.mc_tile_cursor.p;
-   fd.depth = h.mc_depth.p;
-   fd.vis = h.mc_vis.p;
-   fd.rec_of = h.mc_rec_of.p;
-   fd.color = h.deferred.p;
-   fd.covered = h.mc_covered.p;
-   // the G-buffer's depth attachment (marching_cubes.rs:97, LOAD): the rasterised pass's own, or the cast's reconstruction
-   if (h.gbuffer_rasterised)
-      HIP_TRY(c, hipMemcpyAsync(h.mc_depth.p, h.gr_depth.p, (size_t)W * H * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-   else
-      launch_mc_depth_seed(lc, h.pos.p, fd);
-   unsigned long long ntri = 0;
-   HIP_TRY(c, hipStreamSynchronize(c->stream));
-   HIP_TRY(c, hipMemcpy(&ntri, h.mc_totals.p, sizeof(ntri), hipMemcpyDeviceToHost));
-   if (ntri > 5ull * kMcRes * kMcRes * kMcRes) return fail(c, UH_ERR_HIP, "uh_render_hybrid: marching-cubes triangle count out of range");
-   for (int st : {grow(h.mc_verts, std::max<size_t>(3, 3 * (size_t)ntri)), grow(h.mc_rec_count, std::max<size_t>(1, (size_t)ntri)),
-                  grow(h.mc_chunks, scan_chunk_count(std::max<uint32_t>((uint32_t)ntri, tiles)))})
-      if (st) return st;
-   if (ntri && !uhi_mc_extract_emit(c->stream, view.time, h.mc_block_counts.p, h.mc_verts.p)) return fail(c, UH_ERR_HIP, "uh_render_hybrid: marching-cubes tables");
-   fd.vertices = h.mc_verts.p;
-   fd.num_tris = (uint32_t)ntri;
-   fd.rec_count = h.mc_rec_count.p;
-   launch_forward_count(lc, fd, true);
-   unsigned long long totals[2] = {0, 0};
-   if (ntri) device_exclusive_scan_u32(h.mc_rec_count.p, (uint32_t)ntri, h.mc_chunks.p, h.mc_totals.p + 1, c->stream);
-   device_exclusive_scan_u32(h.mc_tile_count.p, tiles, h.mc_chunks.p, h.mc_totals.p + 2, c->stream);
-   HIP_TRY(c, hipMemcpyAsync(h.mc_tile_cursor.p, h.mc_tile_count.p, tiles * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-   HIP_TRY(c, hipStreamSynchronize(c->stream));
-   HIP_TRY(c, hipMemcpy(totals + 1, h.mc_totals.p + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-   if (ntri) HIP_TRY(c, hipMemcpy(totals, h.mc_totals.p + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-   if (totals[0] >= (1ull << 32) - 1 || totals[1] >= (1ull << 32))
-      return fail(c, UH_ERR_CAPACITY, "uh_render_hybrid: marching cubes: 2^32 - 1 or more triangle pieces, or 2^32 or more tile entries");
-   for (int st : {grow(h.mc_records, std::max<size_t>(1, 6 * (size_t)totals[0])), grow(h.mc_entries, std::max<size_t>(1, (size_t)totals[1]))})
-      if (st) return st;
-   fd.records = h.mc_records.p;
-   fd.entries = h.mc_entries.p;
-   launch_forward_emit(lc, fd, true);
-   launch_forward_resolve(lc, fd, true);
-   HybridFrameDev lp{};  // k_hybrid_light_prep's inputs, into the pass's own records
-   lp.lights = h.mc_lights.p;
-   lp.raw_lights = h.raw_lights.p;
-   lp.num_lights = view.num_lights;
-   for (int a = 0; a < 3; a++) lp.sun_raw[a] = view.sun_dir[a];
-   launch_hybrid_light_prep(lc, lp);
-   ForwardShade fs{};
-   fs.lights = h.mc_lights.p;
-   fs.count = view.num_lights + 1;
-   for (int a = 0; a < 3; a++) fs.eye[a] = view.eye_pos[a];
-   std::memcpy(fs.view, view.view, sizeof(fs.view));
-   const ShadowLookup sl{h.smaps.p, h.s_params.p, h.smap_size};
-   launch_forward_shade(lc, c->scene, fd, fs, view.shadows_enabled == 1 ? &sl : nullptr, true);
-   h.mc_tris = (uint32_t)ntri;
-   h.mc_pieces = (uint32_t)totals[0];
-   h.mc_lights_used = view.num_lights + 1;
-   h.mc_time = view.time;
-   h.mc_renders++;
-   return UH_OK;
-}
-
-// ---- the rasterised G-buffer (utopian_hip.h "UH_HYBRID_GBUFFER_RASTER"; forward.hip) ----
-static int raster_scene(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformData& view, SceneBins& b, ForwardDev& fd, const char* who, uint32_t* pieces);
-
-// raster_scene into the pass's own depth, visibility and records, then gbuffer.frag into the four targets
-static int render_gbuffer_raster(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformData& view, const HybridDev& hd) {
-   uh_ctx::Hybrid& h = c->hy;
-   ForwardDev fd{};
-   fd.depth = h.gr_depth.p;
-   fd.vis = h.gr_vis.p;
-   fd.rec_of = h.gr_rec_of.p;
-   fd.covered = h.gr_covered.p;
-   uint32_t pieces = 0;
-   if (int st = raster_scene(c, lc, view, h.gr_bins, fd, "uh_render_hybrid: rasterised G-buffer", &pieces)) return st;
-   launch_gbuffer_raster_shade(lc, c->scene, fd, hd);
-   h.gr_pieces = pieces;
-   h.gr_renders++;
-   return UH_OK;
-}
-
-int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!view) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_render_hybrid: null view");
-   const bool raster = (mask & UH_HYBRID_GBUFFER_RASTER) != 0;
-   if (raster && !(mask & UH_HYBRID_GBUFFER))
-      return fail(c, UH_ERR_INVALID_ARGUMENT,
-                  "uh_render_hybrid: UH_HYBRID_GBUFFER_RASTER without UH_HYBRID_GBUFFER (the bit chooses how the G-buffer pass runs); set both, "
-                  "or neither");
-   // the IBL maps exist for this call's consumers when an earlier call built them or this one does, before rt_reflections
-   const bool maps = c->hy.env_builds > 0 || (mask & UH_HYBRID_ENVIRONMENT);
-   if ((mask & UH_HYBRID_RT_REFLECTIONS) && view->ibl_enabled == 1 && !maps)
-      return fail(c, UH_ERR_INVALID_ARGUMENT,
-                  "uh_render_hybrid: rt_reflections with view.ibl_enabled = 1 needs the IBL maps (irradiance, specular, BRDF LUT of ibl.rs), "
-                  "which are not part of this library until a call with UH_HYBRID_ENVIRONMENT builds them; set that bit, or ibl_enabled = 0 "
-                  "for the reflection pass's non-IBL branch");
-   const bool render_maps = (mask & UH_HYBRID_SHADOW_MAPS) && view->shadows_enabled == 1;
-   if (render_maps && !c->hy.params_set)
-      return fail(c, UH_ERR_INVALID_ARGUMENT,
-                  "uh_render_hybrid: UH_HYBRID_SHADOW_MAPS before uh_set_shadowmap_params (the cascades of uh_shadow_cascades or the caller's own)");
-   if (mask & UH_HYBRID_DEFERRED) {
-      if (view->shadows_enabled == 1 && !c->hy.smap_size && !render_maps)
-         return fail(c, UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: the deferred pass with view.shadows_enabled = 1 needs the cascaded shadow maps (shadow.rs), which a call "
-                     "with UH_HYBRID_SHADOW_MAPS renders; set that bit, or shadows_enabled = 0 for the rt_shadows branch");
-      if (view->ibl_enabled == 1 && !maps)
-         return fail(c, UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: the deferred pass with view.ibl_enabled = 1 needs the IBL maps (irradiance, specular, BRDF LUT of ibl.rs), "
-                     "which a call with UH_HYBRID_ENVIRONMENT builds; set that bit, or ibl_enabled = 0 for the ambient term 0.03 * diffuse * occlusion");
-      if (view->num_lights > c->lights.size())
-         return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_render_hybrid: view.num_lights exceeds the lights added with uh_add_light");
-   }
-   if ((mask & UH_HYBRID_SKY) && view->cubemap_enabled == 1 && !maps)
-      return fail(c, UH_ERR_INVALID_ARGUMENT,
-                  "uh_render_hybrid: the sky pass with view.cubemap_enabled = 1 needs the environment cube (ibl.rs), which a call with "
-                  "UH_HYBRID_ENVIRONMENT builds; set that bit, or cubemap_enabled = 0 for the IntegrateScattering branch");
-   // setup_marching_cubes_pass (mod.rs:164): only with the checkbox on
-   const bool mc = (mask & UH_HYBRID_MARCHING_CUBES) && view->marching_cubes_enabled == 1;
-   if (mc) {
-      if (!(mask & UH_HYBRID_GBUFFER) && !c->hy.gbuffer_done)
-         return fail(c, UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: the marching-cubes pass depth-tests against the G-buffer's depth, and no G-buffer has been rendered; "
-                     "set UH_HYBRID_GBUFFER, or marching_cubes_enabled = 0");
-      if (c->meshes.empty())
-         return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_render_hybrid: the marching-cubes pass shades with the first mesh's material (mesh_index 0), and the scene has no mesh");
-      if (view->shadows_enabled == 1 && !c->hy.smap_size && !render_maps)
-         return fail(c, UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: the marching-cubes pass with view.shadows_enabled = 1 needs the cascaded shadow maps (shadow.rs), which a "
-                     "call with UH_HYBRID_SHADOW_MAPS renders; set that bit, or shadows_enabled = 0");
-      if (view->num_lights > c->lights.size())
-         return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_render_hybrid: the marching-cubes pass: view.num_lights exceeds the lights added with uh_add_light");
-   }
-   if (!c->built && c->topology_valid && view->rebuild_tlas == 1)
-      if (int st = uh_refit_acceleration(c)) return st;
-   if (!c->built) return fail(c, UH_ERR_NOT_BUILT, "uh_render_hybrid before uh_build_acceleration");
-   if (raster && (c->W > 65535 || c->H > 65535))
-      return fail(c, UH_ERR_CAPACITY, "uh_render_hybrid: rasterised G-buffer: a frame wider or taller than 65535 pixels");
-   HIP_TRY(c, hipSetDevice(c->device));
-   uh_ctx::Hybrid& h = c->hy;
-   const bool first = !h.counter.p;
-   if (int st = hybrid_alloc(c)) return st;
-   if (int st = hybrid_tables(c)) return st;
-   if (raster && !h.gr_covered.p)
-      if (int st = alloc_group(c, [&](auto f) { h.gr_images((size_t)c->W * c->H, f); })) return st;
-   const uint32_t frame_bits = UH_HYBRID_SSAO | UH_HYBRID_DEFERRED | UH_HYBRID_SKY | UH_HYBRID_PRESENT;
-   const bool frame_first = ((mask & frame_bits) || mc) && !h.sky_counter.p;
-   if ((mask & frame_bits) || mc) {
-      if (int st = hybrid_frame_alloc(c)) return st;
-      if ((mask & UH_HYBRID_DEFERRED) || mc)
-         if (int st = hybrid_light_table(c)) return st;
-   }
-   if (mc && !h.mc_covered.p)
-      if (int st = alloc_group(c, [&](auto f) { h.mc_images((size_t)c->W * c->H, f); })) return st;
-   if (mask & UH_HYBRID_ENVIRONMENT)
-      if (int st = env_alloc(c)) return st;
-   const FrameParams fp = make_params(c, *view);
-   HybridDev hd{};
-   hd.pos = h.pos.p;
-   hd.nrm = h.nrm.p;
-   hd.alb = h.alb.p;
-   hd.pbr = h.pbr.p;
-   hd.shadow = h.shadow.p;
-   hd.refl = h.refl.p;
-   hd.queue = h.queue.p;
-   hd.counter = h.counter.p;
-   hd.meshes = h.meshes.p;
-   hd.vertices = h.vertices.p;
-   hd.indices = h.indices.p;
-   for (int a = 0; a < 3; a++) {
-      hd.sun_dir[a] = fp.sun_dir[a];
-      hd.eye[a] = view->eye_pos[a];
-   }
-   hd.W = c->W;
-   hd.H = c->H;
-   hd.furnace = c->furnace ? 1u : 0u;
-   if (int st = wait_frames_in_flight(c)) return st;
-   LaunchCfg lc = cfg(c);
-   lc.count_visits = false;  // nothing of this call goes to UhStats
-   if (first) launch_hybrid_clear(lc, hd);
-   HybridFrameDev fd{};
-   fd.ssao = h.ssao.p;
-   fd.deferred = h.deferred.p;
-   fd.present = h.present.p;
-   fd.sky_counter = h.sky_counter.p;
-   fd.lights = h.lights.p;
-   fd.raw_lights = h.raw_lights.p;
-   std::memcpy(fd.view, view->view, sizeof(fd.view));
-   std::memcpy(fd.proj, view->projection, sizeof(fd.proj));
-   std::memcpy(fd.inv_view, view->inverse_view, sizeof(fd.inv_view));
-   fd.num_lights = view->num_lights;
-   fd.ssao_on = view->ssao_enabled == 1;
-   fd.rt_on = view->raytracing_supported == 1;
-   fd.fxaa_on = view->fxaa_enabled == 1;
-   for (int a = 0; a < 3; a++) fd.sun_raw[a] = view->sun_dir[a];
-   if (frame_first) launch_hybrid_frame_clear(lc, hd, fd);
-   // the camera grid when the path tracer's is built for this camera and geometry (read only: the grid's state is the path tracer's)
-   float mats[32];
-   std::memcpy(mats, fp.inv_view, sizeof(float) * 16);
-   std::memcpy(mats + 16, fp.inv_proj, sizeof(float) * 16);
-   const bool grid = c->cam_grid_enabled && c->cam_valid && c->cam_geom == c->geom_version && std::memcmp(mats, c->cam_mats, sizeof(mats)) == 0;
-   const bool rt = view->raytracing_supported != 0;
-   // every stage this call runs between its two events; the passes that do not run report 0, the environment's last build stays
-   // (a call that only renders shadow maps leaves the passes' records as they are)
-   if ((mask & (UH_HYBRID_FRAME | UH_HYBRID_ENVIRONMENT | UH_HYBRID_SHADOW_MAPS)) != UH_HYBRID_SHADOW_MAPS)
-      for (int k = 0; k < kHybridPasses; k++) h.stage[k].ran = false;
-   if (mask & UH_HYBRID_SHADOW_MAPS) h.stage[kStShadowMaps].ran = false;
-   if (mask & UH_HYBRID_MARCHING_CUBES) h.stage[kStMarchingCubes].ran = false;
-   const auto begin = [&](int k) {
-      h.stage[k].ran = true;
-      h.stage[k].timed = false;
-      return hipEventRecord(h.stage[k].begin, c->stream);
-   };
-   const auto end = [&](int k) { return hipEventRecord(h.stage[k].end, c->stream); };
-   // setup_shadow_pass's four passes are added first (mod.rs:91-98)
-   if (render_maps) {
-      HIP_TRY(c, begin(kStShadowMaps));
-      int st = render_shadow_maps(c, lc, "uh_render_hybrid");
-      const hipError_t e = st ? hipSuccess : end(kStShadowMaps);
-      if (st || e != hipSuccess) h.stage[kStShadowMaps].ran = false;  // no time for a render that did not complete
-      if (st) return st;
-      HIP_TRY(c, e);
-   }
-   // pass order of build_render_graph (mod.rs:100-134, graph.rs:743): rt_shadows, gbuffer, rt_reflections
-   if (rt && (mask & UH_HYBRID_RT_SHADOWS)) {
-      HIP_TRY(c, begin(kStShadows));
-      launch_hybrid_shadows(lc, c->scene, hd);
-      HIP_TRY(c, end(kStShadows));
-   }
-   if (mask & UH_HYBRID_GBUFFER) {
-      HIP_TRY(c, begin(kStGbuffer));
-      if (raster) {
-         if (int st = render_gbuffer_raster(c, lc, *view, hd)) {
-            h.stage[kStGbuffer].ran = false;  // no time for a pass that did not complete
-            return st;
-         }
-      } else {
-         launch_hybrid_gbuffer(lc, fp, c->scene, hd, grid ? &c->cam_dev : nullptr);
-      }
-      HIP_TRY(c, end(kStGbuffer));
-      h.gbuffer_done = true;
-      h.gbuffer_rasterised = raster;
-   }
-   // setup_cubemap_pass (mod.rs:121): after the G-buffer, before rt_reflections; the maps persist until the next build
-   const IblMaps ibl{h.env.p, h.irr.p, h.spec.p, h.lut.p};
-   if (mask & UH_HYBRID_ENVIRONMENT) {
-      EnvDev e{h.env.p, h.irr.p, h.spec.p, h.lut.p, h.taps.p, {}, {}};
-      for (int a = 0; a < 3; a++) {
-         e.eye[a] = view->inverse_view[12 + a];  // extract_camera_position(view.view): inverse(view)[3]
-         e.sun[a] = view->sun_dir[a];
-         h.env_eye[a] = e.eye[a];
-         h.env_sun[a] = e.sun[a];
-      }
-      void (*const build[4])(const LaunchCfg&, const EnvDev&) = {launch_env_cube, launch_env_irradiance, launch_env_specular, launch_env_brdf_lut};
-      for (int k = 0; k < 4; k++) {
-         HIP_TRY(c, begin(kStEnvCube + k));
-         build[k](lc, e);
-         HIP_TRY(c, end(kStEnvCube + k));
-      }
-      h.env_builds++;
-   }
-   if (rt && (mask & UH_HYBRID_RT_REFLECTIONS)) {
-      HIP_TRY(c, begin(kStReflections));
-      HIP_TRY(c, hipMemsetAsync(h.counter.p, 0, sizeof(uint32_t), c->stream));
-      launch_hybrid_reflections(lc, c->scene, hd, view->ibl_enabled == 1 ? &ibl : nullptr);
-      HIP_TRY(c, end(kStReflections));
-   }
-   // the final frame (mod.rs:136-186): ssao_pass (not with ssao_enabled != 1, ssao.rs:27), deferred_pass, atmosphere_pass, present_pass
-   if ((mask & UH_HYBRID_SSAO) && view->ssao_enabled == 1) {
-      HIP_TRY(c, begin(kStSsao));
-      launch_hybrid_ssao(lc, hd, fd);
-      HIP_TRY(c, end(kStSsao));
-   }
-   if (mask & UH_HYBRID_DEFERRED) {
-      HIP_TRY(c, begin(kStDeferred));
-      const ShadowLookup sl{h.smaps.p, h.s_params.p, h.smap_size};
-      launch_hybrid_deferred(lc, c->scene, hd, fd, view->ibl_enabled == 1 ? &ibl : nullptr, view->shadows_enabled == 1 ? &sl : nullptr);
-      HIP_TRY(c, end(kStDeferred));
-   }
-   h.frame_lights = h.stage[kStDeferred].ran ? view->num_lights + 1 : 0;
-   // setup_marching_cubes_pass (mod.rs:164-174): after the deferred pass, before the atmosphere pass
-   if (mc) {
-      HIP_TRY(c, begin(kStMarchingCubes));
-      if (int st = render_mc_pass(c, lc, *view)) {
-         h.stage[kStMarchingCubes].ran = false;  // no time for a pass that did not complete
-         return st;
-      }
-      HIP_TRY(c, end(kStMarchingCubes));
-   }
-   if (mask & UH_HYBRID_SKY) {
-      HIP_TRY(c, begin(kStSky));
-      HIP_TRY(c, hipMemsetAsync(h.sky_counter.p, 0, sizeof(uint32_t), c->stream));
-      launch_hybrid_sky(lc, fp, hd, fd, view->cubemap_enabled == 1 ? &ibl : nullptr, mc ? h.mc_vis.p : nullptr);
-      HIP_TRY(c, end(kStSky));
-   }
-   if (mask & UH_HYBRID_PRESENT) {
-      HIP_TRY(c, begin(kStPresent));
-      launch_hybrid_present(lc, hd, fd);
-      HIP_TRY(c, end(kStPresent));
-   }
-   HIP_TRY(c, hipGetLastError());
-   return UH_OK;
-}
-
-int uh_read_hybrid(uh_ctx* c, int which, void* out) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   const uh_ctx::Hybrid& h = c->hy;
-   if (!h.counter.p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid before the first uh_render_hybrid");
-   if (which < 0 || which > UH_HYBRID_GBUFFER_VISIBILITY) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..12");
-   if (which >= UH_HYBRID_SSAO_IMAGE && which <= UH_HYBRID_PRESENT_OUTPUT && !h.sky_counter.p)
-      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 6..8 before the first call with an SSAO, deferred, sky or present bit");
-   if ((which == UH_HYBRID_DEPTH || which == UH_HYBRID_MARCHING_CUBES_VISIBILITY) && h.mc_renders == 0)
-      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 9..10 before the first marching-cubes pass");
-   if (which >= UH_HYBRID_GBUFFER_DEPTH && h.gr_renders == 0)
-      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 11..12 before the first rasterised G-buffer pass");
-   // image k's pixels and its bytes per pixel, in UH_HYBRID_* image order
-   const std::pair<const void*, size_t> img[] = {
-      {h.pos.p, sizeof(float4)}, {h.nrm.p, sizeof(float4)}, {h.alb.p, sizeof(uchar4)}, {h.pbr.p, sizeof(float4)}, {h.shadow.p, 1},
-      {h.refl.p, sizeof(uchar4)}, {h.ssao.p, sizeof(uint16_t)}, {h.deferred.p, sizeof(float4)}, {h.present.p, sizeof(uchar4)},
-      {h.mc_depth.p, sizeof(float)}, {h.mc_vis.p, sizeof(uint32_t)}, {h.gr_depth.p, sizeof(float)}, {h.gr_vis.p, sizeof(uint32_t)}};
-   return read_back(c, out, img[which].first, (size_t)c->W * c->H * img[which].second);
-}
-
-// stage k's time in the last call (an environment stage: build) that ran it, 0 when that did not
-static int stage_ms(uh_ctx* c, int k, float* out) {
-   uh_ctx::Hybrid::Stage& st = c->hy.stage[k];
-   *out = 0.0f;
-   if (!st.ran) return UH_OK;
-   if (!st.timed) {
-      HIP_TRY(c, hipEventElapsedTime(&st.ms, st.begin, st.end));
-      st.timed = true;
-   }
-   *out = st.ms;
-   return UH_OK;
-}
-
-int uh_get_hybrid_frame_stats(uh_ctx* c, UhHybridFrameStats* out) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_hybrid_frame_stats: null destination");
-   std::memset(out, 0, sizeof(*out));
-   const uh_ctx::Hybrid& h = c->hy;
-   if (!h.counter.p) return UH_OK;
-   HIP_TRY(c, hipSetDevice(c->device));
-   if (int st = sync_all(c)) return st;
-   for (int k = 0; k < kHybridPasses; k++)
-      if (int st = stage_ms(c, k, &out->pass_ms[k])) return st;
-   if (h.stage[kStSky].ran) HIP_TRY(c, hipMemcpy(&out->sky_pixels, h.sky_counter.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-   out->lights = h.frame_lights;
-   return UH_OK;
-}
-
-int uh_get_marching_cubes_stats(uh_ctx* c, UhMarchingCubesStats* out) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_marching_cubes_stats: null destination");
-   std::memset(out, 0, sizeof(*out));
-   const uh_ctx::Hybrid& h = c->hy;
-   if (h.mc_renders == 0) return UH_OK;
-   HIP_TRY(c, hipSetDevice(c->device));
-   if (int st = sync_all(c)) return st;
-   if (int st = stage_ms(c, kStMarchingCubes, &out->pass_ms)) return st;
-   out->renders = h.mc_renders;
-   out->triangles = h.mc_tris;
-   out->pieces = h.mc_pieces;
-   HIP_TRY(c, hipMemcpy(&out->covered_pixels, h.mc_covered.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-   out->lights = h.mc_lights_used;
-   out->time = h.mc_time;
-   return UH_OK;
-}
-
-int uh_get_gbuffer_raster_stats(uh_ctx* c, UhGbufferRasterStats* out) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_gbuffer_raster_stats: null destination");
-   std::memset(out, 0, sizeof(*out));
-   const uh_ctx::Hybrid& h = c->hy;
-   if (h.gr_renders == 0) return UH_OK;
-   HIP_TRY(c, hipSetDevice(c->device));
-   if (int st = sync_all(c)) return st;
-   if (h.gbuffer_rasterised)  // the G-buffer stage's record is the last rasterised pass's
-      if (int st = stage_ms(c, kStGbuffer, &out->pass_ms)) return st;
-   out->renders = h.gr_renders;
-   out->pieces = h.gr_pieces;
-   HIP_TRY(c, hipMemcpy(&out->covered_pixels, h.gr_covered.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-   return UH_OK;
-}
-
-int uh_read_environment(uh_ctx* c, int which, int face, int mip, void* out) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   const uh_ctx::Hybrid& h = c->hy;
-   if (h.env_builds == 0) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_environment before the first call with UH_HYBRID_ENVIRONMENT");
-   if (which == UH_ENV_BRDF_LUT) {
-      if (face != 0 || mip != 0) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_environment: the BRDF LUT has face 0 and mip 0 only");
-      return read_back(c, out, h.lut.p, (size_t)kLutSize * kLutSize * sizeof(uint32_t));
-   }
-   if (which < UH_ENV_ENVIRONMENT || which > UH_ENV_SPECULAR) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_environment: map must be 0..3");
-   const int mips = which == UH_ENV_IRRADIANCE ? 1 : (int)kEnvMips;
-   if (face < 0 || face > 5 || mip < 0 || mip >= mips) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_environment: face 0..5, mip 0..7 (irradiance: 0)");
-   const size_t S = kEnvSize >> mip;
-   const float4* base = which == UH_ENV_ENVIRONMENT ? h.env.p : which == UH_ENV_IRRADIANCE ? h.irr.p : h.spec.p;
-   return read_back(c, out, base + env_mip_offset((uint32_t)mip) + (size_t)face * S * S, S * S * sizeof(float4));
-}
-
-int uh_get_environment_stats(uh_ctx* c, UhEnvironmentStats* out) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_environment_stats: null destination");
-   std::memset(out, 0, sizeof(*out));
-   const uh_ctx::Hybrid& h = c->hy;
-   if (h.env_builds == 0) return UH_OK;
-   HIP_TRY(c, hipSetDevice(c->device));
-   if (int st = sync_all(c)) return st;
-   for (int k = 0; k < 4; k++)
-      if (int st = stage_ms(c, kStEnvCube + k, &out->pass_ms[k])) return st;
-   out->builds = h.env_builds;
-   std::memcpy(out->sun_dir, h.env_sun, sizeof(out->sun_dir));
-   std::memcpy(out->eye, h.env_eye, sizeof(out->eye));
-   return UH_OK;
-}
-
-int uh_get_hybrid_stats(uh_ctx* c, UhHybridStats* out) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_hybrid_stats: null destination");
-   std::memset(out, 0, sizeof(*out));
-   const uh_ctx::Hybrid& h = c->hy;
-   if (!h.counter.p) return UH_OK;
-   HIP_TRY(c, hipSetDevice(c->device));
-   if (int st = sync_all(c)) return st;
-   uint32_t metal = 0;
-   if (h.stage[kStReflections].ran) HIP_TRY(c, hipMemcpy(&metal, h.counter.p, sizeof(metal), hipMemcpyDeviceToHost));
-   const uint64_t n = (uint64_t)c->W * c->H;
-   out->rays[0] = h.stage[kStGbuffer].ran && !h.gbuffer_rasterised ? n : 0;  // a rasterised pass casts no ray
-   out->rays[1] = h.stage[kStShadows].ran ? n : 0;
-   out->rays[2] = metal;
-   out->reflection_pixels = metal;
-   const int stages[3] = {kStGbuffer, kStShadows, kStReflections};  // the header's order
-   for (int k = 0; k < 3; k++)
-      if (int st = stage_ms(c, stages[k], &out->pass_ms[k])) return st;
-   return UH_OK;
-}
-
-int uh_set_shadowmap_params(uh_ctx* c, const UhShadowmapParams* p) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_set_shadowmap_params: null params");
-   for (int k = 0; k < 4; k++) {
-      const float* m = p->view_projection_matrices[k];
-      for (int i = 0; i < 16; i++)
-         if (!std::isfinite(m[i])) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_set_shadowmap_params: a non-finite matrix element");
-      if (!std::isfinite(p->cascade_splits[k])) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_set_shadowmap_params: a non-finite split");
-      if (m[3] != 0.0f || m[7] != 0.0f || m[11] != 0.0f || m[15] != 1.0f)
-         return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_set_shadowmap_params: a matrix whose last row is not (0, 0, 0, 1) (not orthographic)");
-   }
-   c->hy.params = *p;
-   c->hy.params_set = true;
-   return UH_OK;
-}
-
-int uh_read_shadow_map(uh_ctx* c, int cascade, float* out) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   const uh_ctx::Hybrid& h = c->hy;
-   if (!h.smaps.p || !h.smap_size) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_shadow_map before the maps were rendered (UH_HYBRID_SHADOW_MAPS)");
-   if (cascade < 0 || cascade > 3) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_shadow_map: cascade must be 0..3");
-   const size_t n = (size_t)h.smap_size * h.smap_size;
-   return read_back(c, out, h.smaps.p + (size_t)cascade * n, n * sizeof(float));
-}
-
-int uh_get_shadow_map_stats(uh_ctx* c, UhShadowMapStats* out) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_shadow_map_stats: null destination");
-   std::memset(out, 0, sizeof(*out));
-   const uh_ctx::Hybrid& h = c->hy;
-   if (h.s_renders == 0) return UH_OK;
-   HIP_TRY(c, hipSetDevice(c->device));
-   if (int st = sync_all(c)) return st;
-   if (int st = stage_ms(c, kStShadowMaps, &out->pass_ms)) return st;
-   out->renders = h.s_renders;
-   out->size = h.smap_size;
-   std::memcpy(out->triangles, h.s_tris, sizeof(out->triangles));
-   out->params = h.snapshot;
-   return UH_OK;
-}
-
-// ---- the forward graph (utopian_hip.h "uh_render_forward"; forward.hip) ----
-// per mesh: (P V) W column-major - P V first, then times the instance's 3x4 with row (0, 0, 0, 1), each element summed
-// ((a(r,0) b(0,c) + a(r,1) b(1,c)) + a(r,2) b(2,c)) + a(r,3) b(3,c) - followed by the instance's 3x4 row-major
-static void forward_mesh_matrices(const uh_ctx* c, const UhViewUniformData& v, std::vector<float>& out) {
-   auto mul = [](const float* a, const float* b, float* o) {
-      for (int col = 0; col < 4; col++)
-         for (int r = 0; r < 4; r++)
-            o[4 * col + r] = ((a[r] * b[4 * col] + a[4 + r] * b[4 * col + 1]) + a[8 + r] * b[4 * col + 2]) + a[12 + r] * b[4 * col + 3];
-   };
-   float pv[16];
-   mul(v.projection, v.view, pv);
-   const size_t nm = c->meshes.size();
-   out.assign(nm * 28, 0.0f);
-   for (size_t m = 0; m < nm; m++) {
-      const float* o = c->meshes[m].o2w;
-      float w[16];  // column-major
-      for (int col = 0; col < 4; col++) {
-         for (int r = 0; r < 3; r++) w[4 * col + r] = o[4 * r + col];
-         w[4 * col + 3] = col == 3 ? 1.0f : 0.0f;
-      }
-      mul(pv, w, &out[m * 28]);
-      std::memcpy(&out[m * 28 + 16], o, 12 * sizeof(float));
-   }
-}
-
-// the scene's meshes through the forward rasteriser into fd.depth (cleared to 1.0), fd.vis and fd.rec_of, which the caller sets: count,
-// scan, emit, resolve. The records' and tile entries' totals come back to the host in between (the buffers grow to them); *pieces
-// receives the records. `who` names the entry point in messages.
-static int raster_scene(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformData& view, SceneBins& b, ForwardDev& fd, const char* who, uint32_t* pieces) {
-   uh_ctx::Hybrid& h = c->hy;
-   const uint32_t W = c->W, H = c->H, tiles_x = (W + kForwardTile - 1) / kForwardTile, tiles_y = (H + kForwardTile - 1) / kForwardTile;
-   const uint32_t tiles = tiles_x * tiles_y;
-   size_t ntri = 0;
-   for (const HostMesh& m : c->meshes) ntri += m.tris();
-   if (ntri >= (1ull << 32) - 1) return fail(c, UH_ERR_CAPACITY, std::string(who) + ": 2^32 - 1 or more triangles");
-   const auto grow = [&](auto& buf, size_t n) -> int {
-      if (buf.p && buf.n >= n) return UH_OK;
-      const hipError_t e = buf.alloc(n);
-      if (e != hipSuccess)
-         return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string(who) + ": allocation: " + hipGetErrorString(e));
-      return UH_OK;
-   };
-   for (int st : {grow(b.tile_count, tiles), grow(b.tile_cursor, tiles), grow(b.totals, 2), grow(b.mats, std::max<size_t>(1, 28 * c->meshes.size())),
-                  grow(b.chunks, std::max<size_t>(1, scan_chunk_count((uint32_t)std::max<size_t>(ntri, tiles))))})
-      if (st) return st;
-   if (b.geom != c->geom_version || !b.rec_count.p) {
-      std::vector<uint32_t> tm;
-      tm.reserve(ntri);
-      for (size_t m = 0; m < c->meshes.size(); m++) tm.insert(tm.end(), c->meshes[m].tris(), (uint32_t)m);
-      for (int st : {grow(b.tri_mesh, std::max<size_t>(1, ntri)), grow(b.rec_count, std::max<size_t>(1, ntri))})
-         if (st) return st;
-      if (int st = fill_tri_mesh(c, b.tri_mesh.p, tm)) return st;
-      b.geom = c->geom_version;
-   }
-   forward_mesh_matrices(c, view, b.mats_host);
-   if (!b.mats_host.empty())
-      HIP_TRY(c, hipMemcpyAsync(b.mats.p, b.mats_host.data(), b.mats_host.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-   HIP_TRY(c, hipMemsetAsync(b.tile_count.p, 0, tiles * sizeof(uint32_t), c->stream));
-   HIP_TRY(c, hipMemsetAsync(fd.covered, 0, sizeof(uint32_t), c->stream));
-   fd.vertices = h.vertices.p;
-   fd.indices = h.indices.p;
-   fd.meshes = h.meshes.p;
-   fd.tri_mesh = b.tri_mesh.p;
-   fd.mats = b.mats.p;
-   fd.num_tris = (uint32_t)ntri;
-   fd.W = W;
-   fd.H = H;
-   fd.tiles_x = tiles_x;
-   fd.tiles_y = tiles_y;
-   fd.rec_count = b.rec_count.p;
-   fd.tile_count = b.tile_count.p;
-   fd.tile_cursor = b.tile_cursor.p;
-   launch_forward_count(lc, fd);
-   unsigned long long totals[2] = {0, 0};
-   if (ntri) device_exclusive_scan_u32(b.rec_count.p, (uint32_t)ntri, b.chunks.p, b.totals.p, c->stream);
-   device_exclusive_scan_u32(b.tile_count.p, tiles, b.chunks.p, b.totals.p + 1, c->stream);
-   HIP_TRY(c, hipMemcpyAsync(b.tile_cursor.p, b.tile_count.p, tiles * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-   HIP_TRY(c, hipStreamSynchronize(c->stream));
-   HIP_TRY(c, hipMemcpy(totals + 1, b.totals.p + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-   if (ntri) HIP_TRY(c, hipMemcpy(totals, b.totals.p, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-   // record ids below 2^32 - 1: the resolve's key holds 0xFFFFFFFE - record, and 0xFFFFFFFF stands for none
-   if (totals[0] >= (1ull << 32) - 1 || totals[1] >= (1ull << 32))
-      return fail(c, UH_ERR_CAPACITY, std::string(who) + ": 2^32 - 1 or more triangle pieces, or 2^32 or more tile entries");
-   for (int st : {grow(b.records, std::max<size_t>(1, 6 * (size_t)totals[0])), grow(b.entries, std::max<size_t>(1, (size_t)totals[1]))})
-      if (st) return st;
-   fd.records = b.records.p;
-   fd.entries = b.entries.p;
-   launch_forward_emit(lc, fd);
-   launch_forward_resolve(lc, fd);
-   *pieces = (uint32_t)totals[0];
-   return UH_OK;
-}
-
-// raster_scene, then forward.frag into forward_output
-static int render_forward_pass(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformData& view) {
-   uh_ctx::Hybrid& h = c->hy;
-   uh_ctx::Forward& f = c->fw;
-   ForwardDev fd{};
-   fd.depth = f.depth.p;
-   fd.vis = f.vis.p;
-   fd.rec_of = f.rec_of.p;
-   fd.color = f.color.p;
-   fd.covered = f.covered.p;
-   uint32_t pieces = 0;
-   if (int st = raster_scene(c, lc, view, f.bins, fd, "uh_render_forward", &pieces)) return st;
-   HybridFrameDev lp{};  // k_hybrid_light_prep's inputs, into the forward graph's own records
-   lp.lights = f.lights.p;
-   lp.raw_lights = h.raw_lights.p;
-   lp.num_lights = view.num_lights;
-   for (int a = 0; a < 3; a++) lp.sun_raw[a] = view.sun_dir[a];
-   launch_hybrid_light_prep(lc, lp);
-   ForwardShade fs{};
-   fs.lights = f.lights.p;
-   fs.count = view.num_lights + 1;
-   for (int a = 0; a < 3; a++) fs.eye[a] = view.eye_pos[a];
-   std::memcpy(fs.view, view.view, sizeof(fs.view));
-   const ShadowLookup sl{h.smaps.p, h.s_params.p, h.smap_size};
-   launch_forward_shade(lc, c->scene, fd, fs, view.shadows_enabled == 1 ? &sl : nullptr);
-   f.pieces = pieces;
-   f.lights_used = view.num_lights + 1;
-   f.renders++;
-   return UH_OK;
-}
-
-int uh_render_forward(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!view) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_render_forward: null view");
-   const bool render_maps = (mask & UH_FORWARD_SHADOW_MAPS) && view->shadows_enabled == 1;
-   if (render_maps && !c->hy.params_set)
-      return fail(c, UH_ERR_INVALID_ARGUMENT,
-                  "uh_render_forward: UH_FORWARD_SHADOW_MAPS before uh_set_shadowmap_params (the cascades of uh_shadow_cascades or the caller's own)");
-   if (mask & UH_FORWARD_PASS) {
-      if (view->shadows_enabled == 1 && !c->hy.smap_size && !render_maps)
-         return fail(c, UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_forward: the forward pass with view.shadows_enabled = 1 needs the cascaded shadow maps (shadow.rs), which a call "
-                     "with UH_FORWARD_SHADOW_MAPS renders; set that bit, or shadows_enabled = 0");
-      if (view->num_lights > c->lights.size())
-         return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_render_forward: view.num_lights exceeds the lights added with uh_add_light");
-   }
-   if (!c->built && c->topology_valid && view->rebuild_tlas == 1)
-      if (int st = uh_refit_acceleration(c)) return st;
-   if (!c->built) return fail(c, UH_ERR_NOT_BUILT, "uh_render_forward before uh_build_acceleration");
-   if (c->W > 65535 || c->H > 65535) return fail(c, UH_ERR_CAPACITY, "uh_render_forward: a frame wider or taller than 65535 pixels");
-   HIP_TRY(c, hipSetDevice(c->device));
-   uh_ctx::Hybrid& h = c->hy;
-   uh_ctx::Forward& f = c->fw;
-   if (int st = hybrid_events(c)) return st;
-   if (int st = hybrid_tables(c)) return st;
-   const bool first = !f.color.p;
-   if (first) {
-      for (auto& st : f.stage)
-         for (hipEvent_t* ev : {&st.begin, &st.end})
-            if (!*ev) HIP_TRY(c, hipEventCreate(ev));
-      if (int st = alloc_group(c, [&](auto fn) { f.images((size_t)c->W * c->H, fn); })) return st;
-   }
-   if (mask & UH_FORWARD_PASS)
-      if (int st = hybrid_light_table(c)) return st;
-   if (int st = wait_frames_in_flight(c)) return st;
-   LaunchCfg lc = cfg(c);
-   lc.count_visits = false;  // nothing of this call goes to UhStats
-   ForwardDev cd{};
-   cd.W = c->W;
-   cd.H = c->H;
-   cd.depth = f.depth.p;
-   cd.vis = f.vis.p;
-   cd.rec_of = f.rec_of.p;
-   cd.color = f.color.p;
-   if (first) launch_forward_clear(lc, cd, f.present.p);
-   for (auto& st : f.stage) st.ran = false;
-   const auto begin = [&](int k) {
-      f.stage[k].ran = true;
-      f.stage[k].timed = false;
-      return hipEventRecord(f.stage[k].begin, c->stream);
-   };
-   const auto end = [&](int k) { return hipEventRecord(f.stage[k].end, c->stream); };
-   // setup_shadow_pass, setup_forward_pass, setup_present_pass (build_minimal_forward_render_graph): the maps are the hybrid graph's,
-   // and their own record (uh_get_shadow_map_stats) is kept as a hybrid call with UH_HYBRID_SHADOW_MAPS keeps it
-   if (render_maps) {
-      h.stage[kStShadowMaps].ran = false;
-      uh_ctx::Hybrid::Stage& hs = h.stage[kStShadowMaps];
-      HIP_TRY(c, begin(0));
-      HIP_TRY(c, hipEventRecord(hs.begin, c->stream));
-      hs.ran = true;
-      hs.timed = false;
-      int st = render_shadow_maps(c, lc, "uh_render_forward");
-      hipError_t e = st ? hipSuccess : end(0);
-      if (e == hipSuccess && !st) e = hipEventRecord(hs.end, c->stream);
-      if (st || e != hipSuccess) f.stage[0].ran = hs.ran = false;  // no time for a render that did not complete
-      if (st) return st;
-      HIP_TRY(c, e);
-   }
-   if (mask & UH_FORWARD_PASS) {
-      HIP_TRY(c, begin(1));
-      int st = render_forward_pass(c, lc, *view);
-      if (st) {
-         f.stage[1].ran = false;
-         return st;
-      }
-      HIP_TRY(c, end(1));
-   }
-   if (mask & UH_FORWARD_PRESENT) {  // present.frag + FXAA on forward_output, into the forward graph's own image
-      HIP_TRY(c, begin(2));
-      HybridDev hd{};
-      hd.W = c->W;
-      hd.H = c->H;
-      HybridFrameDev pd{};
-      pd.deferred = f.color.p;
-      pd.present = f.present.p;
-      pd.fxaa_on = view->fxaa_enabled == 1;
-      launch_hybrid_present(lc, hd, pd);
-      HIP_TRY(c, end(2));
-   }
-   HIP_TRY(c, hipGetLastError());
-   return UH_OK;
-}
-
-int uh_read_forward(uh_ctx* c, int which, void* out) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   const uh_ctx::Forward& f = c->fw;
-   if (!f.color.p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_forward before the first uh_render_forward");
-   if (which < UH_FORWARD_OUTPUT || which > UH_FORWARD_PRESENT_OUTPUT) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_forward: image index must be 0..3");
-   // image k's pixels and its bytes per pixel, in UH_FORWARD_* image order
-   const std::pair<const void*, size_t> img[] = {{f.color.p, sizeof(float4)}, {f.depth.p, sizeof(float)}, {f.vis.p, sizeof(uint32_t)}, {f.present.p, sizeof(uchar4)}};
-   return read_back(c, out, img[which].first, (size_t)c->W * c->H * img[which].second);
-}
-
-int uh_get_forward_stats(uh_ctx* c, UhForwardStats* out) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_forward_stats: null destination");
-   std::memset(out, 0, sizeof(*out));
-   uh_ctx::Forward& f = c->fw;
-   if (!f.color.p) return UH_OK;
-   HIP_TRY(c, hipSetDevice(c->device));
-   if (int st = sync_all(c)) return st;
-   for (int k = 0; k < 3; k++) {
-      uh_ctx::Hybrid::Stage& st = f.stage[k];
-      if (!st.ran) continue;
-      if (!st.timed) {
-         HIP_TRY(c, hipEventElapsedTime(&st.ms, st.begin, st.end));
-         st.timed = true;
-      }
-      out->pass_ms[k] = st.ms;
-   }
-   out->renders = f.renders;
-   if (f.stage[1].ran) {
-      out->pieces = f.pieces;
-      out->lights = f.lights_used;
-      HIP_TRY(c, hipMemcpy(&out->covered_pixels, f.covered.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-   }
    return UH_OK;
 }
 

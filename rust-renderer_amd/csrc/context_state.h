@@ -1,0 +1,487 @@
+// context_state.h - struct uh_ctx and the types it is made of, for the two files that implement the context: context.hip (lifetime,
+// scene, builders, the path tracer, the multi-GPU composition) and graphs.hip (the hybrid and the forward graph). Private: not
+// installed, not part of the C ABI (include/utopian_hip.h), where uh_ctx stays opaque.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "bvh.h"
+#include "context_internal.h"
+#include "device_types.h"
+#include "utopian_hip.h"
+
+using namespace uh;  // (both including files are written inside it)
+
+struct HostMesh {
+   std::vector<UhVertex> vertices;
+   std::vector<uint32_t> indices;
+   UhGpuMaterial material;
+   float o2w[12];
+   float w2o[9];
+   // a mesh of uh_add_isosurface_mesh: what uh_update_isosurface_mesh re-extracts with
+   bool iso = false, iso_reference = true;
+   uint32_t iso_res = 0;
+   float iso_lo = 0.0f, iso_hi = 0.0f;
+   // device-resident (after uh_update_isosurface_mesh): d_verts holds 3 * dev_tris vertices, the index list is their iota.
+   // vertices / indices above are then a mirror that exists only while host_valid (the host builder asks for it)
+   bool dev = false, host_valid = true;
+   UhVertex* d_verts = nullptr;
+   size_t d_capacity = 0;        // vertices d_verts can hold
+   uint32_t dev_tris = 0;
+   uint64_t serial = 0;          // bumped by every update: what the build sources and the raster tables key this mesh's range on
+   float olo[3] = {0, 0, 0}, ohi[3] = {0, 0, 0};  // object-space box of the device vertices (k_iso_scatter), for `box_serial`
+   uint64_t box_serial = ~0ull;
+   size_t tris() const { return dev ? dev_tris : indices.size() / 3; }
+   size_t num_vertices() const { return dev ? 3 * (size_t)dev_tris : vertices.size(); }
+   size_t num_indices() const { return dev ? 3 * (size_t)dev_tris : indices.size(); }
+};
+
+struct EventPair {
+   hipEvent_t start, stop;
+   int kind;  // 0 trace_closest, 1 trace_shadow, 2 shade
+};
+
+template <typename T>
+struct DevBuf {
+   T* p = nullptr;
+   void* base = nullptr;
+   size_t n = 0;
+   // stagger_bytes shifts the array inside its allocation: the per-pixel SoA arrays are all the same
+   // size, and kernels touch the same index of several of them at once; without a stagger those
+   // accesses are an exact multiple of the array size apart
+   hipError_t alloc(size_t count, size_t stagger_bytes = 0) {
+      release();
+      n = count;
+      if (count == 0) return hipSuccess;
+      hipError_t e = hipMalloc(&base, count * sizeof(T) + stagger_bytes);
+      if (e == hipSuccess) p = reinterpret_cast<T*>(static_cast<char*>(base) + stagger_bytes);
+      return e;
+   }
+   void release() {
+      if (base) (void)hipFree(base);
+      p = nullptr;
+      base = nullptr;
+      n = 0;
+   }
+};
+
+// a rasteriser's binning buffers (graphs.hip bin_and_resolve): the shadow maps, the marching-cubes pass, the rasterised
+// G-buffer and the forward pass have a set each; they grow with what is drawn
+struct RasterBins {
+   DevBuf<uint32_t> tile_count, tile_cursor, rec_count, tri_mesh, chunks, entries;
+   DevBuf<unsigned long long> totals;       // the grand totals of the two scans: records, tile entries
+   DevBuf<uint4> records;
+   DevBuf<float> mats;                      // per mesh (shadow maps: per cascade and mesh) what the pass's vertex stage multiplies by
+   std::vector<float> mats_host;
+   uint64_t geom = 0;                       // geom_version of tri_mesh / rec_count
+   template <class F> void each(F&& f) {
+      f(tile_count, 0), f(tile_cursor, 0), f(rec_count, 0), f(tri_mesh, 0), f(chunks, 0), f(entries, 0), f(totals, 0), f(records, 0), f(mats, 0);
+   }
+};
+
+// what a perspective rasteriser resolves into, n pixels: depth, draw index and surviving record per pixel; covered[0] the covered
+// pixels of the last pass. covered is allocated last: its pointer says "allocated"
+struct RasterTarget {
+   DevBuf<float> depth;
+   DevBuf<uint32_t> vis, rec_of, covered;
+   template <class F> void each(size_t n, F&& f) { f(depth, n), f(vis, n), f(rec_of, n), f(covered, 1); }
+};
+
+// one timed stage of a graph, between its two events (stage_begin / stage_end). ms: the elapsed time, resolved from the events by the
+// first stats read after the stage ran and kept (a later read returns the same bits)
+struct Stage {
+   hipEvent_t begin = nullptr, end = nullptr;
+   bool ran = false, timed = false;
+   float ms = 0.0f;
+};
+
+// the hybrid graph's stages (uh_ctx::Hybrid::stage): its seven passes in the order of their UH_HYBRID_* bits, then the environment's,
+// then the shadow maps, then the marching-cubes pass
+enum HybridStage : int {
+   kStShadows, kStGbuffer, kStReflections, kStSsao, kStDeferred, kStSky, kStPresent, kHybridPasses,
+   kStEnvCube = kHybridPasses, kStEnvIrradiance, kStEnvSpecular, kStEnvLut, kStShadowMaps, kStMarchingCubes, kHybridStages
+};
+
+// One frame in flight: its own stream pair, hazard events, path state and queue control block.
+// Frames of the path-tracing pass are independent except for the order of the accumulation
+// read-modify-write (reference.rgen:131-143), so up to `frames_in_flight` of them overlap on the
+// GPU: one frame's memory-bound shading and kernel tails are filled by another frame's traversal,
+// and a rank that owns only 1/N of the pixels still keeps the chip busy.
+constexpr uint32_t kMaxSlots = 8;
+struct Slot {
+   hipStream_t stream = nullptr;
+   // second stream: shade_miss (pure VALU, touches only paths that left the scene) and the shadow
+   // traversals overlap the main stream's shade_hit / next closest-hit traversal
+   hipStream_t side = nullptr;
+   hipEvent_t ev_traced = nullptr, ev_missed = nullptr, ev_shaded = nullptr, ev_shadowed = nullptr, ev_side_done = nullptr;
+   hipEvent_t ev_acc = nullptr;  // recorded after the frame's accumulate / store tail
+   hipEvent_t frame_start = nullptr, frame_stop = nullptr;
+   DevBuf<float4> rec, radf, pixcol;  // rec: two sets of four path-state planes + the hit plane (device_types.h PathState)
+   DevBuf<uint32_t> queues[5];
+   DevBuf<unsigned long long> sun_lit;  // the sun rays' verdicts: one bit per queue position (PathState::sun_lit)
+   DevBuf<Control> control;
+   PathState ps{};
+   bool ready = false;
+   size_t capacity = 0;  // path ids this slot can hold (pixels x frames per batch)
+
+   hipError_t create(size_t n) {
+      capacity = n;
+      uint32_t shard_cap = 0;
+      {  // exact: the largest number of 64-path runs one shard receives (shard_of_run)
+         const uint32_t runs = (uint32_t)((n + 63) / 64);
+         uint32_t per_shard[kShards] = {0};
+         for (uint32_t r = 0; r < runs; r++) per_shard[shard_of_run(r)]++;
+         for (uint32_t s = 0; s < kShards; s++) shard_cap = per_shard[s] * 64 > shard_cap ? per_shard[s] * 64 : shard_cap;
+      }
+      if (shard_cap >= (1u << 31)) return hipErrorInvalidValue;  // a queue position's top bit carries the path's sun verdict (kernels.hip kSunLitBit)
+      hipError_t e;
+#define SLOT_TRY(expr)                 \
+   if ((e = (expr)) != hipSuccess) return e
+      SLOT_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+      SLOT_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+      for (hipEvent_t* ev : {&ev_traced, &ev_missed, &ev_shaded, &ev_shadowed, &ev_side_done, &ev_acc}) SLOT_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+      SLOT_TRY(hipEventCreate(&frame_start));
+      SLOT_TRY(hipEventCreate(&frame_stop));
+      const size_t stagger = 4352;  // 4 KiB + 256 B per array slot
+      // planes staggered like the arrays: the same index of two planes must not alias. The hit plane is indexed by queue position
+      // (shard segment + position in the shard's queue), which runs to kShards * shard_cap >= n
+      const size_t cap_q = (size_t)shard_cap * kShards;
+      const size_t plane = (n > cap_q ? n : cap_q) + stagger / sizeof(float4);
+      SLOT_TRY(rec.alloc(plane * (2 * kRecQuads + 1), 0 * stagger));
+      SLOT_TRY(radf.alloc(n, 1 * stagger));
+      SLOT_TRY(pixcol.alloc(n, 2 * stagger));
+      // sharded queues: capacity per shard = the pixels (64-pixel runs) a shard can own
+      // (the miss queue holds (position, id) pairs: twice the words)
+      for (int qi = 0; qi < 5; qi++) SLOT_TRY(queues[qi].alloc((size_t)shard_cap * kShards * (qi == 4 ? 2 : 1)));
+      // shard_cap is a multiple of 64: a shard's segment is whole words. The sun kernels store every word the next kernels read
+      SLOT_TRY(sun_lit.alloc((size_t)shard_cap * kShards / 64));
+      SLOT_TRY(hipMemsetAsync(sun_lit.p, 0, sun_lit.n * sizeof(unsigned long long), stream));
+      SLOT_TRY(control.alloc(1));
+      SLOT_TRY(hipMemsetAsync(control.p, 0, sizeof(Control), stream));
+      SLOT_TRY(hipStreamSynchronize(stream));
+#undef SLOT_TRY
+      ps.set[0] = PathRecs{rec.p, plane};
+      ps.set[1] = PathRecs{rec.p + plane * kRecQuads, plane};
+      ps.hit = rec.p + plane * 2 * kRecQuads;
+      ps.radf = radf.p;
+      ps.pixcol = pixcol.p;
+      for (int i = 0; i < 5; i++) ps.queue[i] = queues[i].p;
+      ps.sun_lit = sun_lit.p;
+      ps.shard_cap = shard_cap;
+      ready = true;
+      return hipSuccess;
+   }
+   void destroy() {
+      if (stream) (void)hipStreamSynchronize(stream);
+      if (side) (void)hipStreamSynchronize(side);
+      rec.release();
+      radf.release();
+      pixcol.release();
+      for (auto& q : queues) q.release();
+      sun_lit.release();
+      control.release();
+      for (hipEvent_t* ev : {&ev_traced, &ev_missed, &ev_shaded, &ev_shadowed, &ev_side_done, &ev_acc, &frame_start, &frame_stop}) {
+         if (*ev) (void)hipEventDestroy(*ev);
+         *ev = nullptr;  // (a create() that fails half-way must not leave handles for the next destroy())
+      }
+      if (side) (void)hipStreamDestroy(side);
+      if (stream) (void)hipStreamDestroy(stream);
+      stream = side = nullptr;
+      ready = false;
+   }
+};
+
+// frames of the reservoir passes one uh_render_frames wavefront carries at most, and the ring of spatial buffers that
+// lets the next batch's chains run beside the current wavefront (two batches + the history slot)
+constexpr uint32_t kRestirBatch = 16;
+constexpr int kSpatialRing = 2 * (int)kRestirBatch + 1;
+
+struct uh_ctx {
+   int device = 0;
+   Slot slots[kMaxSlots];
+   uint32_t frames_in_flight = 4;     // slots used round-robin by path-tracing frames (swept: profiles/README.md)
+   uint32_t batch_frames = 0;         // frames one uh_render_frames launch chain carries (option "batch_frames"); 0 = auto
+   uint32_t next_slot = 0;
+   uint32_t shard_cap = 0;
+   hipEvent_t last_acc = nullptr;     // ev_acc of the most recent frame (accumulation order)
+   // G-buffer cast + reservoir passes run in call order on their own stream, beside path-tracing frames in flight.
+   // spatial_reuse_reservoirs is a RING of kSpatialRing buffers: the path tracer of frame f reads slot `spatial_cur` while
+   // frame f+1's passes already run - its temporal pass reads the same slot and its spatial pass writes the next one, after
+   // the last path-tracing wavefront that read THAT one has finished (spatial_reader[]). A batch of B static-camera frames
+   // runs its B reservoir chains back to back (slots cur+1 .. cur+B) and then ONE path-tracing wavefront in which the
+   // paths of frame f sample from slot cur+1+f (FrameParams::spatial_of): the ring holds two batches and the history.
+   hipStream_t restir_stream = nullptr;
+   hipEvent_t ev_restir = nullptr, rs_start = nullptr, rs_stop = nullptr;
+   bool restir_recorded = false;
+   int spatial_cur = 0;
+   hipEvent_t spatial_reader[kSpatialRing] = {};
+   // the reservoir passes by bands of rows over the ranks of a job (uh_set_restir_partition)
+   uint32_t rp_rank = 0, rp_world = 1, rp_band_rows = 0;
+   size_t res_stride = 0;  // reservoirs per spatial_reuse buffer: the frame, padded to rp_world equal bands
+   UhRestirExchangeFn rp_exchange = nullptr;
+   void* rp_user = nullptr;
+   hipEvent_t ev_band[kSpatialRing] = {};  // "this context's band of ring slot k is written" (in-process groups pull on it)
+   void* rccl = nullptr;                   // RcclLink (uh_rccl_attach)
+   hipEvent_t t_start = nullptr, t_stop = nullptr;  // bracket of the last uh_render_frame call (last_frame_ms)
+   Slot* last_slot = nullptr;
+   hipStream_t& stream = slots[0].stream;  // slot 0 also serves every non-frame operation
+   PathState& ps = slots[0].ps;
+   DevBuf<Control>& control = slots[0].control;
+   bool overlap_miss = true, overlap_shadow = true;
+   uint32_t W = 0, H = 0;
+   uint32_t num_cus = 256;
+   // persistent grids of the traversal kernels, blocks per CU (the refill kernels' LDS - stacks + ray pool - admits 6 / 5). Round 4,
+   // closest / shadow = 6/5, 5/5, 5/4, 4/4, 4/3, 3/4: a 16-frame wavefront 1.774 / 1.777 / 1.764 / 1.780 / 1.773 / 1.799 ms per frame,
+   // one frame per call with a wait after it 2.95 / 2.88 / 2.88 / 2.84 / 2.85 / 2.89 ms: fewer waves finish a small launch's tail sooner
+   uint32_t closest_blocks_per_cu = 5, shadow_blocks_per_cu = 5;  // (config 2, whose light shadow rays are a third of the frame: 6/5, 5/5, 5/4, 6/4 = 8,230 / 8,266 / 7,997 / 7,950 Mrays/s)
+   uint32_t cam_walk_whole = 512;     // option "camera_grid_walk_whole" (sun_grid.h SunGridDev::walk_whole)
+   // one frame per call: bounces 1 .. of a lone frame inside one persistent kernel (k_path_fused) instead of four launches per bounce
+   bool fused_bounces = true;  // option "fused_bounces"
+   bool fused_always = false;  // fused_bounces = -1: also with frames in flight and for frames of any size (tests)
+   static constexpr uint32_t kFusedMaxPaths = 4u << 20;
+   uint32_t fused_blocks_per_cu = 4;
+   static constexpr uint32_t kSingleFrameBlocksPerCu = 4;  // the cap on both for a wavefront of one frame (fewer persistent waves reach the end of a small launch's tail sooner: round 4's sweep)
+   std::string err;
+
+   // host scene
+   std::vector<HostMesh> meshes;
+   std::vector<UhGpuLight> lights;
+   struct HostTex {
+      uint32_t w, h;
+      uchar4* dev;
+      uint32_t tiles_x;  // 0 = row-major
+   };
+   std::vector<HostTex> textures;
+   bool built = false;
+
+   // device scene
+   DevBuf<float4> d_nodes, d_tris, d_shade, d_lights;
+   DevBuf<MeshShade> d_meshes;
+   // on-device refit (refit.hip), allocated by the first uh_refit_acceleration
+   DevBuf<float> d_obj_corners, d_world_corners, d_node_box;
+   DevBuf<RefitMesh> d_refit_meshes;
+   std::vector<uint32_t> packet_keys;  // key of triangle packet i (leaf order)
+   std::vector<uint32_t> level_start;  // BFS levels of the node array
+   bool topology_valid = false;        // the device tree matches the mesh list (transforms may differ)
+   // on-device build (lbvh.hip, option "device_build"): per-triangle sources in mesh order, kept on the device
+   // until a mesh is added, so that a rebuild after moved instances or changed parameters uploads nothing
+   bool device_build = false, src_valid = false;
+   uint32_t device_build_kind = 1;  // 1 = PLOC, 2 = radix tree (lbvh.hip)
+   // PLOC rounds stop at this many clusters; a host SAH tree over them is the top (option "ploc_sah_top", 0 = PLOC to the root).
+   // Config-1 scene: 0 / 1,024 / 8,192 / 131,072 clusters = 21.7 / 20.3 / 20.1 / 19.0 nodes per ray, rebuild 7.7 / 6.0 / 9.4 / 66 ms (host tree: 18.8)
+   uint32_t ploc_sah_top = 1024;
+   static constexpr uint32_t kPlocRadius = 8;  // swept 4..64 in round 3: tree quality flat (21.7-23.0 nodes/ray), build time grows with it (profiles/README.md)
+   DevBuf<float> d_src_corners;
+   DevBuf<uint32_t> d_src_keys;
+   DevBuf<float4> d_src_shade;
+   // the layout of d_src_*: triangles and HostMesh::serial of each mesh's range (a mesh whose serial moved is rewritten from its
+   // device vertices, the ranges behind it are moved on the device)
+   std::vector<uint32_t> src_tris;
+   std::vector<uint64_t> src_serial;
+   // uh_update_isosurface_mesh: extraction scratch, the box words of k_iso_scatter, two events and the figures of
+   // uh_get_isosurface_update_stats; nothing of it exists before the first update
+   struct IsoUpdate {
+      DevBuf<uint32_t> counts, chunks, box;
+      DevBuf<unsigned long long> total;
+      hipEvent_t begin = nullptr, end = nullptr;
+      UhIsosurfaceUpdateStats st{};
+   } iso;
+   float refit_ms = 0.0f;
+   DevBuf<TexInfo> d_tex;
+   DevBuf<float> d_lut;
+   SceneDev scene{};
+
+   // frame-persistent per-pixel images (graph resources of renderers/mod.rs:199-244)
+   DevBuf<float4> accumulation, gbuffer;
+   DevBuf<uchar4> output;
+   DevBuf<UhReservoir> reservoirs[3], spatial_ring;  // ring slot 0 = reservoirs[2], slots 1.. = spatial_ring (allocated by the first reservoir pass)
+   DevBuf<float4> gb_ray_o, gb_ray_d, gb_hit;  // scratch of the G-buffer cast (allocated by the first G-buffer pass)
+   DevBuf<DeviceStats> dstats;
+   Images im{};
+
+   // options / stats
+   bool count_visits = false, time_kernels = false, full_frame_restir = false;
+   bool iso_reference = true;  // option "iso_reference_triangulation": uh_add_isosurface_mesh emits the reference's triangles (isosurface.hip)
+   uint32_t shadow_map_size = 4096;  // option "shadow_map_size": the cascaded shadow maps' size (shadow.rs: 4096)
+   bool furnace = false;  // option "furnace": reference.rmiss compiled with FURNACE_TEST (a miss returns white whatever view.sky_enabled says)
+   uint64_t frames = 0;
+   float build_ms = 0.0f, last_frame_ms = 0.0f;
+   float ms_by_kind[5] = {0, 0, 0, 0, 0};  // trace_closest, sun shadow rays (grid + tree), shade, camera grid (bounce 0 through the grid + its leftovers), light shadow rays
+   uint32_t trace_closest_launches = 0, trace_light_launches = 0;
+   bool frame_timed = false;
+   std::vector<EventPair> pending, free_events;
+   uint32_t bvh_nodes = 0, bvh_tris = 0;
+
+   // sun shadow rays through a per-direction grid instead of the tree (sun_grid.h; option "sun_grid"). The grid belongs to one
+   // (geometry, sun direction) pair: it is built on the first frame that traces sun rays and again when the direction or the
+   // geometry has changed and then stayed put for two consecutive frames - a sun or an instance that moves every frame keeps
+   // the tree walk.
+   bool sun_grid_enabled = true;
+   bool sun_verdicts = true;        // option "sun_verdicts" (FrameParams::sun_verdicts)
+   bool sun_valid = false;          // d_sun_* hold a usable grid for (sun_geom, sun_dir_built)
+   bool sun_attempted = false;      // a build for (sun_geom, sun_dir_built) was tried (it may have been refused: sun_why)
+   bool sun_have_pending = false;
+   uint64_t geom_version = 1, sun_geom = 0, sun_geom_pending = 0;
+   float sun_dir_built[3] = {0, 0, 0}, sun_dir_pending[3] = {0, 0, 0};
+   DevBuf<uint32_t> d_sun_cells;
+   DevBuf<SunGridEntry> d_sun_entries;
+   DevBuf<float4> d_sun_recs;       // the entries with their packets inline (SunGridDev::recs; option "sun_grid_inline")
+   DevBuf<float> d_sun_coarse;      // the coarse cover (SunGridDev::coarse; option "sun_grid_coarse")
+   uint32_t sun_coarse_shift = 2;   // blocks of 4 x 4 cells; 0: no coarse cover
+   // the lists a second time as 64-byte records that carry their packet (SunGridDev::recs): by default only while they stay within
+   // four times the packet array (a grid of 96 entries per triangle repeats every packet 96 times: 1.4 GB for the 17 MB of the
+   // config-1 scene); option "sun_grid_inline_max_mb" raises the budget (0: never)
+   int64_t sun_inline_max_mb = -1;  // -1: auto = 4 x the packet array
+   SunGridDev sun_dev{};
+   SunGridLimits sun_limits;
+   std::string sun_why;
+   float sun_build_ms = 0.0f, sun_mean_list = 0.0f;
+   float sun_fallback_area = 1.0f;  // share of the scene's surface whose cell hands its sun rays to the tree (the builders' figure)
+   uint32_t sun_cells = 0, sun_entries = 0, sun_max_list = 0;
+   bool sun_this_frame = false;     // set by render_batch for the frame being enqueued
+   bool primary_implicit = true;    // option "primary_implicit" (FrameParams::primary_implicit)
+   bool sun_device_build = true;    // option "sun_grid_build": 1 = on the device (sun_grid_build.hip: a few ms), 0 = the host builder (sun_grid.cpp)
+
+   // the primary rays through a per-camera grid instead of the tree (sun_grid.h "camera grid"; option "camera_grid"). The grid belongs
+   // to one (geometry, inverse_view, inverse_projection, frame size): it is built - on the device, a few milliseconds - when the
+   // same camera has been asked for in two consecutive frame calls, or at once by a call that carries several frames of it; a
+   // camera that moves every frame keeps the tree walk.
+   bool cam_grid_enabled = true;
+   bool cam_valid = false, cam_attempted = false, cam_have_pending = false;
+   uint64_t cam_geom = 0, cam_geom_pending = 0;
+   float cam_mats[32] = {0}, cam_mats_pending[32] = {0};  // inverse_view, inverse_projection of the grid / of the last request
+   DevBuf<uint32_t> d_cam_cells;
+   DevBuf<SunGridEntry> d_cam_entries;
+   SunGridDev cam_dev{};
+   SunGridLimits cam_limits;
+   std::string cam_why;
+   float cam_build_ms = 0.0f, cam_mean_list = 0.0f;
+   uint32_t cam_cells = 0, cam_entries = 0, cam_max_list = 0, cam_max_list_interior = 0;
+   bool cam_this_frame = false;
+
+   // tile partition
+   uint32_t tp_rank = 0, tp_world = 1, tp_tile = 64;
+   DevBuf<uint32_t> owned_pixels;  // ascending pixel ids this rank owns (empty = the whole frame)
+   uint32_t n_owned = 0;
+   // composition of a partitioned frame without a host wait (uh_rccl_gather_tiles; the in-process group's uh_mgpu_compose): this
+   // rank's packed tiles, on the root every rank's, and the event behind the last pack / composition - the next frame's accumulate
+   // tail waits for it like for a frame's (last_acc)
+   DevBuf<float4> tile_send, tile_recv;
+   hipEvent_t ev_compose = nullptr;
+
+   // the hybrid graph's passes (uh_render_hybrid): images, the metal-pixel queue and a copy of the scene's meshes as gbuffer.vert
+   // reads them, all allocated by the first call
+   struct Hybrid {
+      DevBuf<float4> pos, nrm, pbr;
+      DevBuf<uchar4> alb, refl;
+      DevBuf<uint8_t> shadow;
+      DevBuf<uint32_t> queue, counter;
+      DevBuf<HybridMesh> meshes;
+      DevBuf<UhVertex> vertices;
+      DevBuf<uint32_t> indices;
+      uint64_t geom = 0;                       // geom_version the mesh tables were made for
+      // with device-resident meshes: each mesh's range in vertices / indices and the HostMesh::serial it holds (unchanged ranges
+      // are moved on the device instead of uploaded again)
+      struct Range { uint32_t vb, ib, nv, ni; uint64_t serial; };
+      std::vector<Range> layout;
+      hipEvent_t waits[2 * kMaxSlots + 1] = {};  // behind the frames in flight
+      // one record per stage: stage k < kHybridPasses is bit k of UH_HYBRID_* (rt_shadows, G-buffer, rt_reflections, SSAO, deferred,
+      // sky, present: the last call's), the environment's sub-passes follow (cube, irradiance, specular, BRDF LUT: the last build's)
+      Stage stage[kHybridStages];
+      // the final frame's passes (SSAO, deferred, sky, present), allocated by the first call that asks for one of them
+      DevBuf<uint16_t> ssao;
+      DevBuf<float4> deferred;
+      DevBuf<uchar4> present;
+      DevBuf<uint32_t> sky_counter;
+      DevBuf<UhGpuLight> raw_lights;           // the uh_add_light table as added
+      DevBuf<HybridLight> lights;              // its records as the deferred pass reads them, the sun first
+      size_t lights_uploaded = SIZE_MAX;       // c->lights.size() when raw_lights was uploaded
+      uint32_t frame_lights = 0;               // lights the deferred pass of the last call evaluated (the sun included)
+      // the IBL maps of setup_cubemap_pass (UH_HYBRID_ENVIRONMENT), allocated by the first call that builds them
+      DevBuf<float4> env, irr, spec;
+      DevBuf<uint32_t> lut;
+      DevBuf<float4> taps;                     // the irradiance filter's tap table
+      uint32_t env_builds = 0;
+      float env_sun[3] = {0, 0, 0}, env_eye[3] = {0, 0, 0};  // what the last build was made with
+      // the cascaded shadow maps (UH_HYBRID_SHADOW_MAPS), allocated by the first call that renders them; freed by a size change
+      DevBuf<float> smaps;                     // 4 layers of smap_size^2
+      DevBuf<UhShadowmapParams> s_params;      // the snapshot the deferred pass reads
+      RasterBins s_bins;                       // rec_count: [cascade][triangle]; mats: [cascade][mesh][16]
+      bool params_set = false;
+      UhShadowmapParams params{}, snapshot{}, pending{};  // the last uh_set_shadowmap_params; what the maps were rendered with;
+                                                          // what the render in progress uses
+      uint32_t s_renders = 0, smap_size = 0, s_tris[4] = {0, 0, 0, 0};
+      bool gbuffer_done = false;               // a G-buffer pass has been enqueued (the marching-cubes pass's depth seed reads it)
+      bool gbuffer_rasterised = false;         // the last G-buffer pass enqueued was rasterised: its depth is the marching-cubes seed
+      // the rasterised G-buffer (UH_HYBRID_GBUFFER_RASTER), allocated by the first rasterised pass: its depth buffer, visibility,
+      // surviving records and binning buffers ([mesh][28] matrices)
+      RasterTarget gr;
+      RasterBins gr_bins;
+      uint32_t gr_renders = 0, gr_pieces = 0;
+      // the marching-cubes pass (UH_HYBRID_MARCHING_CUBES), allocated by the first pass: its depth buffer, visibility, surviving
+      // records, light records, extracted triangles and binning buffers, whose chunks also serve the extraction's scan and whose
+      // matrices are (P V) I column-major, the identity 3x4, then P V (44 floats)
+      RasterTarget mc;
+      RasterBins mc_bins;
+      DevBuf<HybridLight> mc_lights;
+      DevBuf<UhVertex> mc_verts;               // 3 per triangle, extraction order
+      DevBuf<uint32_t> mc_block_counts;
+      DevBuf<unsigned long long> mc_total;     // the extraction scan's grand total: triangles
+      DevBuf<HybridMesh> mc_mesh;              // mesh_index 0's maps with world = identity
+      uint32_t mc_renders = 0, mc_tris = 0, mc_pieces = 0, mc_lights_used = 0;
+      float mc_time = 0.0f;
+
+      // the three groups allocated on first use, each named once for allocation and uh_destroy: f(buffer, length), n pixels; a
+      // group's last buffer is allocated last, its pointer says "allocated"
+      template <class F> void rt_images(size_t n, F&& f) {
+         f(pos, n), f(nrm, n), f(pbr, n), f(alb, n), f(refl, n), f(shadow, n), f(queue, n), f(counter, 1);
+      }
+      template <class F> void frame_images(size_t n, F&& f) {
+         f(ssao, n), f(deferred, n), f(present, n), f(lights, UH_MAX_GPU_LIGHTS + 1), f(sky_counter, 1);
+      }
+      template <class F> void shadow_maps(F&& f) { f(smaps, 0), f(s_params, 0), s_bins.each(f); }  // (all grown by the pass)
+      template <class F> void mc_images(size_t n, F&& f) {
+         f(mc_lights, UH_MAX_GPU_LIGHTS + 1), f(mc_block_counts, kMcBlocks), f(mc_bins.mats, 44), f(mc_mesh, 1), f(mc_total, 1), f(mc_bins.totals, 2),
+            f(mc_verts, 0), mc.each(n, f);  // (mc_verts and the rest of mc_bins are grown by the pass)
+      }
+      template <class F> void env_maps(F&& f) {
+         const size_t cube = env_mip_offset(kEnvMips);
+         f(env, cube), f(irr, 6 * (size_t)kEnvSize * kEnvSize), f(spec, cube), f(lut, (size_t)kLutSize * kLutSize);
+      }
+   } hy;
+
+   // the forward graph (uh_render_forward): its images, light records and binning buffers, allocated by the first call; it shares the
+   // hybrid graph's mesh tables, uploaded light table and shadow maps
+   struct Forward {
+      DevBuf<float4> color;                    // forward_output RGBA32F
+      RasterTarget target;
+      DevBuf<uchar4> present;                  // the forward graph's present image, B8G8R8A8
+      DevBuf<HybridLight> lights;              // forward.frag's light records, the sun first
+      RasterBins bins;                         // [mesh][28] matrices
+      Stage stage[3];                          // pass k: 0 shadow maps, 1 forward, 2 present (the last call's)
+      uint32_t renders = 0, pieces = 0, lights_used = 0;
+      template <class F> void images(size_t n, F&& f) { target.each(n, f), f(present, n), f(lights, UH_MAX_GPU_LIGHTS + 1), f(color, n); }
+   } fw;
+};
+
+// ---- context.hip, for graphs.hip (not exported: the library's dynamic symbols stay the C ABI's) ----
+#pragma GCC visibility push(hidden)
+int fail(uh_ctx* c, int code, const std::string& msg);  // sets uh_last_error (c null: uh_create's); returns code
+#define HIP_TRY(ctx, expr)                                                                                   \
+   do {                                                                                                      \
+      hipError_t e_ = (expr);                                                                                \
+      if (e_ != hipSuccess) return fail(ctx, e_ == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, \
+                                        std::string(#expr) + ": " + hipGetErrorString(e_));                 \
+   } while (0)
+LaunchCfg cfg(uh_ctx* c);
+FrameParams make_params(uh_ctx* c, const UhViewUniformData& v);
+int sync_all(uh_ctx* c);
+int read_back(uh_ctx* c, void* dst, const void* src, size_t bytes);
+// brackets of UhIsosurfaceUpdateStats::scatter_ms on the context's stream (the mesh tables of device-resident meshes count into it)
+void iso_scatter_begin(uh_ctx* c);
+int iso_scatter_end(uh_ctx* c, bool add);
+// ---- graphs.hip, for uh_destroy ----
+void destroy_graphs(uh_ctx* c);  // everything uh_ctx::Hybrid and uh_ctx::Forward own; before the slots' streams go
+#pragma GCC visibility pop
