@@ -1,8 +1,9 @@
-// context.hip — the C ABI of include/utopian_hip.h: context lifetime, scene upload, acceleration
-// structure build, the per-frame pass chain and read-backs. Host-side counterpart of
+// context.hip — the C ABI of include/utopian_hip.h: context lifetime, textures and lights, the sun and camera grids,
+// the per-frame pass chain and read-backs. Host-side counterpart of
 // utopian::Renderer (utopian/src/renderer.rs), utopian::Raytracing (utopian/src/raytracing.rs) and
 // build_path_tracing_render_graph (utopian/src/renderers/mod.rs:189-375) for this path only.
-// struct uh_ctx is context_state.h; the hybrid and the forward graph (uh_render_hybrid, uh_render_forward) are graphs.hip.
+// struct uh_ctx is context_state.h; meshes, the tree builders and the refit are scene_build.hip; the hybrid and the forward graph
+// (uh_render_hybrid, uh_render_forward) are graphs.hip.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: the library opens librccl at run time (uh_rccl_attach)
 #include <dlfcn.h>
@@ -40,38 +41,6 @@ int fail(uh_ctx* c, int code, const std::string& msg) {
 }
 
 namespace {
-
-bool is_identity3x4(const float* m) {
-   static const float I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-   return std::memcmp(m, I, sizeof(I)) == 0;
-}
-
-// inverse of the upper 3x3 of a row-major 3x4 by cofactors (arithmetic contract: cofactor * (1/det))
-void invert3x3(const float* m, float* inv) {
-   float a = m[0], b = m[1], c = m[2], d = m[4], e = m[5], f = m[6], g = m[8], h = m[9], i = m[10];
-   float A = e * i - f * h, B = -(d * i - f * g), C = d * h - e * g;
-   float det = (a * A + b * B) + c * C;
-   float id = 1.0f / det;
-   inv[0] = A * id;
-   inv[1] = -(b * i - c * h) * id;
-   inv[2] = (b * f - c * e) * id;
-   inv[3] = B * id;
-   inv[4] = (a * i - c * g) * id;
-   inv[5] = -(a * f - c * d) * id;
-   inv[6] = C * id;
-   inv[7] = -(a * h - b * g) * id;
-   inv[8] = (a * e - b * d) * id;
-}
-
-void set_transform(HostMesh& m, const float* w) {
-   std::memcpy(m.o2w, w, sizeof(m.o2w));
-   if (is_identity3x4(w)) {
-      static const float I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-      std::memcpy(m.w2o, I, sizeof(I));
-   } else {
-      invert3x3(w, m.w2o);
-   }
-}
 
 void begin_timed(uh_ctx* c, int kind, hipStream_t stream = nullptr) {
    if (!stream) stream = c->stream;
@@ -257,9 +226,7 @@ void uh_destroy(uh_ctx* c) {
    c->d_world_corners.release();
    c->d_node_box.release();
    c->d_refit_meshes.release();
-   c->d_src_corners.release();
-   c->d_src_keys.release();
-   c->d_src_shade.release();
+   c->d_src.release();
    c->d_tex.release();
    c->d_lut.release();
    c->d_sun_cells.release();
@@ -328,33 +295,6 @@ int uh_add_texture_rgba8(uh_ctx* c, const uint8_t* pixels, uint32_t w, uint32_t 
    return UH_OK;
 }
 
-int uh_add_mesh(uh_ctx* c, const UhVertex* vertices, uint32_t num_vertices, const uint32_t* indices, uint32_t num_indices,
-                const UhGpuMaterial* material, const float world3x4[12], uint32_t* out_mesh_index) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!vertices || !indices || !material || !world3x4 || num_indices % 3 != 0)
-      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_add_mesh: null argument or index count not a multiple of 3");
-   if (c->meshes.size() >= UH_MAX_GPU_MESHES) return fail(c, UH_ERR_CAPACITY, "uh_add_mesh: more than 1024 meshes (MAX_NUM_GPU_MESHES)");
-   if (num_indices / 3 > (1u << kPrimBits)) return fail(c, UH_ERR_CAPACITY, "uh_add_mesh: more than 4 Mi triangles in one mesh");
-   for (uint32_t i = 0; i < num_indices; i++)
-      if (indices[i] >= num_vertices) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_add_mesh: index out of range");
-   for (uint32_t i = 0; i < num_vertices; i++)
-      if (!std::isfinite(vertices[i].pos[0]) || !std::isfinite(vertices[i].pos[1]) || !std::isfinite(vertices[i].pos[2]))
-         return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_add_mesh: vertex position is not finite");
-   for (int i = 0; i < 12; i++)
-      if (!std::isfinite(world3x4[i])) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_add_mesh: transform is not finite");
-   HostMesh m;
-   m.vertices.assign(vertices, vertices + num_vertices);
-   m.indices.assign(indices, indices + num_indices);
-   m.material = *material;
-   set_transform(m, world3x4);
-   c->meshes.push_back(std::move(m));
-   c->built = false;
-   c->topology_valid = false;
-   c->src_valid = false;
-   if (out_mesh_index) *out_mesh_index = (uint32_t)c->meshes.size() - 1;
-   return UH_OK;
-}
-
 int uh_add_light(uh_ctx* c, const UhGpuLight* light, uint32_t* out_index) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    if (!light) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_add_light: null light");
@@ -369,532 +309,6 @@ int uh_add_light(uh_ctx* c, const UhGpuLight* light, uint32_t* out_index) {
 int uh_get_num_lights(uh_ctx* c, uint32_t* out) {
    if (!c || !out) return UH_ERR_INVALID_ARGUMENT;
    *out = (uint32_t)c->lights.size();
-   return UH_OK;
-}
-
-int uh_set_instance_transform(uh_ctx* c, uint32_t mesh_index, const float world3x4[12]) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (mesh_index >= c->meshes.size() || !world3x4) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_set_instance_transform: bad mesh index");
-   for (int i = 0; i < 12; i++)
-      if (!std::isfinite(world3x4[i])) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_set_instance_transform: transform is not finite");
-   set_transform(c->meshes[mesh_index], world3x4);
-   c->built = false;
-   return UH_OK;
-}
-
-
-// per-mesh shading records, light table, texture descriptors: everything of the scene except the geometry
-static int upload_scene_tables(uh_ctx* c) {
-   std::vector<MeshShade> ms(c->meshes.size());
-   for (size_t i = 0; i < c->meshes.size(); i++) {
-      const HostMesh& m = c->meshes[i];
-      std::memcpy(ms[i].w2o, m.w2o, sizeof(m.w2o));
-      ms[i].diffuse_map = m.material.diffuse_map;
-      for (int a = 0; a < 3; a++) ms[i].base_color[a] = m.material.base_color_factor[a];
-      ms[i].type = m.material.raytrace_properties[0];
-      ms[i].property = m.material.raytrace_properties[1];
-      ms[i].pad = 0;
-      ms[i].metallic = m.material.metallic_factor;
-      ms[i].roughness = m.material.roughness_factor;
-      ms[i].pad2[0] = ms[i].pad2[1] = 0.0f;
-   }
-   std::vector<float4> lights(2 * c->lights.size());
-   for (size_t i = 0; i < c->lights.size(); i++) {
-      const UhGpuLight& l = c->lights[i];
-      lights[2 * i] = make_float4(l.position[0], l.position[1], l.position[2], 0.0f);
-      lights[2 * i + 1] = make_float4(l.intensity[0], l.intensity[1], l.intensity[2], 0.0f);
-   }
-   std::vector<TexInfo> tex(c->textures.size());
-   for (size_t i = 0; i < tex.size(); i++) tex[i] = TexInfo{c->textures[i].dev, c->textures[i].w, c->textures[i].h, c->textures[i].tiles_x, 0};
-
-   HIP_TRY(c, c->d_meshes.alloc(ms.size()));
-   HIP_TRY(c, c->d_lights.alloc(lights.size()));
-   HIP_TRY(c, c->d_tex.alloc(tex.size()));
-   if (!ms.empty()) HIP_TRY(c, hipMemcpy(c->d_meshes.p, ms.data(), ms.size() * sizeof(MeshShade), hipMemcpyHostToDevice));
-   if (!lights.empty()) HIP_TRY(c, hipMemcpy(c->d_lights.p, lights.data(), lights.size() * sizeof(float4), hipMemcpyHostToDevice));
-   if (!tex.empty()) HIP_TRY(c, hipMemcpy(c->d_tex.p, tex.data(), tex.size() * sizeof(TexInfo), hipMemcpyHostToDevice));
-   c->scene.meshes = c->d_meshes.p;
-   c->scene.textures = c->d_tex.p;
-   c->scene.lights = c->d_lights.p;
-   c->scene.unorm_lut = c->d_lut.p;
-   c->scene.num_meshes = (uint32_t)ms.size();
-   c->scene.num_textures = (uint32_t)tex.size();
-   c->scene.num_lights = (uint32_t)c->lights.size();
-   return UH_OK;
-}
-
-static int build_on_device(uh_ctx* c);
-
-// the host builder and the host refit read HostMesh::vertices / indices: a device-resident mesh is copied back (once per update)
-static int ensure_host_mirrors(uh_ctx* c) {
-   for (HostMesh& m : c->meshes) {
-      if (!m.dev || m.host_valid) continue;
-      m.vertices.resize(3 * (size_t)m.dev_tris);
-      m.indices.resize(m.vertices.size());
-      if (m.dev_tris) {
-         HIP_TRY(c, hipMemcpy(m.vertices.data(), m.d_verts, m.vertices.size() * sizeof(UhVertex), hipMemcpyDeviceToHost));  // blocking
-         c->iso.st.host_geometry_bytes += m.vertices.size() * sizeof(UhVertex);
-      }
-      for (size_t i = 0; i < m.indices.size(); i++) m.indices[i] = (uint32_t)i;
-      m.host_valid = true;
-   }
-   return UH_OK;
-}
-// bytes per triangle of the device-resident meshes that a host-side assembly uploads
-static void count_host_upload(uh_ctx* c, size_t bytes_per_triangle) {
-   for (const HostMesh& m : c->meshes)
-      if (m.dev) c->iso.st.host_geometry_bytes += bytes_per_triangle * m.dev_tris;
-}
-
-int uh_build_acceleration(uh_ctx* c) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   HIP_TRY(c, hipSetDevice(c->device));
-   if (c->device_build) return build_on_device(c);
-   auto t0 = std::chrono::steady_clock::now();
-   if (int st = ensure_host_mirrors(c)) return st;
-   // bake instance transforms: world = ((m0*x + m1*y) + m2*z) + m3 per row (identity: verbatim)
-   size_t total = 0;
-   for (const HostMesh& m : c->meshes) total += m.tris();
-   if (total > kMaxTriangles) return fail(c, UH_ERR_CAPACITY, "scene has more than 2^31 - 2 triangles");
-   std::vector<float> corners(9 * total);
-   std::vector<uint32_t> keys(total);
-   size_t t = 0;
-   for (uint32_t mi = 0; mi < c->meshes.size(); mi++) {
-      const HostMesh& m = c->meshes[mi];
-      const bool ident = is_identity3x4(m.o2w);
-      const float* w = m.o2w;
-      const uint32_t nt = (uint32_t)m.tris();
-      for (uint32_t p = 0; p < nt; p++, t++) {
-         for (int k = 0; k < 3; k++) {
-            const UhVertex& vx = m.vertices[m.indices[3 * (size_t)p + k]];
-            float x = vx.pos[0], y = vx.pos[1], z = vx.pos[2];
-            float* o = &corners[9 * t + 3 * k];
-            if (ident) {
-               o[0] = x;
-               o[1] = y;
-               o[2] = z;
-            } else {
-               o[0] = ((w[0] * x + w[1] * y) + w[2] * z) + w[3];
-               o[1] = ((w[4] * x + w[5] * y) + w[6] * z) + w[7];
-               o[2] = ((w[8] * x + w[9] * y) + w[10] * z) + w[11];
-            }
-         }
-         keys[t] = (mi << kPrimBits) | p;
-      }
-   }
-   BuildInput in{corners.data(), keys.data(), (uint32_t)total};
-   BuildOutput bo;
-   int threads = (int)std::thread::hardware_concurrency();
-   if (threads < 1) threads = 1;
-   if (threads > 32) threads = 32;
-   build_bvh4(in, bo, threads);
-   if (bo.level_start.size() - 1 > kMaxTreeLevels) {
-      // a tree deeper than the traversal stack holds (clustered / exponentially scaled geometry) would drop subtrees
-      // silently: rebuild it balanced (median splits, depth ceil(log2 n) / 1..2 per 4-wide level)
-      build_bvh4(in, bo, threads, true);
-      if (bo.level_start.size() - 1 > kMaxTreeLevels) return fail(c, UH_ERR_CAPACITY, "internal: balanced BVH deeper than the traversal stack");
-   }
-
-   // packets in leaf order
-   std::vector<TriPacket> tp(total);
-   std::vector<ShadePacket> sp(total);
-   for (size_t i = 0; i < total; i++) {
-      uint32_t src = bo.tri_order[i];
-      const float* cr = &corners[9 * (size_t)src];
-      TriPacket& q = tp[i];
-      q.v0[0] = cr[0];
-      q.v0[1] = cr[1];
-      q.v0[2] = cr[2];
-      q.e1x = cr[3] - cr[0];
-      q.e1yz[0] = cr[4] - cr[1];
-      q.e1yz[1] = cr[5] - cr[2];
-      q.e2[0] = cr[6] - cr[0];
-      q.e2[1] = cr[7] - cr[1];
-      q.e2z = cr[8] - cr[2];
-      q.key = keys[src];
-      q.pad[0] = q.pad[1] = 0;
-      uint32_t mi = keys[src] >> kPrimBits, p = keys[src] & kPrimMask;
-      const HostMesh& m = c->meshes[mi];
-      const UhVertex* v[3] = {&m.vertices[m.indices[3 * (size_t)p]], &m.vertices[m.indices[3 * (size_t)p + 1]], &m.vertices[m.indices[3 * (size_t)p + 2]]};
-      ShadePacket& s = sp[i];
-      for (int a = 0; a < 3; a++) {
-         s.n0[a] = v[0]->normal[a];
-         s.n1[a] = v[1]->normal[a];
-         s.n2[a] = v[2]->normal[a];
-      }
-      for (int a = 0; a < 2; a++) {
-         s.uv0[a] = v[0]->uv[a];
-         s.uv1[a] = v[1]->uv[a];
-         s.uv2[a] = v[2]->uv[a];
-      }
-      s.mesh = mi;
-   }
-   if (bo.cnodes.empty()) return fail(c, UH_ERR_INVALID_ARGUMENT, "internal: BVH builder produced no root node");
-   if (int st = sync_all(c)) return st;
-   if (int st = upload_scene_tables(c)) return st;
-   HIP_TRY(c, c->d_nodes.alloc(bo.cnodes.size() * kNodeStride16));
-   HIP_TRY(c, c->d_tris.alloc(total * kTriStride16));
-   HIP_TRY(c, c->d_shade.alloc(total * 4));
-   // 48-byte records into arrays of stride kNodeStride16 / kTriStride16 x 16 bytes
-   HIP_TRY(c, hipMemcpy2D(c->d_nodes.p, 16 * kNodeStride16, bo.cnodes.data(), sizeof(Node4C), sizeof(Node4C), bo.cnodes.size(), hipMemcpyHostToDevice));
-   if (total) {
-      HIP_TRY(c, hipMemcpy2D(c->d_tris.p, 16 * kTriStride16, tp.data(), sizeof(TriPacket), sizeof(TriPacket), total, hipMemcpyHostToDevice));
-      HIP_TRY(c, hipMemcpy(c->d_shade.p, sp.data(), total * sizeof(ShadePacket), hipMemcpyHostToDevice));
-      count_host_upload(c, sizeof(TriPacket) + sizeof(ShadePacket));
-   }
-   c->scene.nodes = reinterpret_cast<const uint4*>(c->d_nodes.p);
-   c->scene.tris = c->d_tris.p;
-   c->scene.shade = c->d_shade.p;
-   c->scene.num_nodes = (uint32_t)bo.nodes.size();
-   c->scene.num_tris = (uint32_t)total;
-   c->bvh_nodes = c->scene.num_nodes;
-   c->bvh_tris = c->scene.num_tris;
-   c->packet_keys.resize(total);
-   for (size_t i = 0; i < total; i++) c->packet_keys[i] = tp[i].key;
-   c->level_start = bo.level_start;
-   c->d_obj_corners.release();  // leaf order changed: the next refit re-creates its inputs
-   c->geom_version++;
-   c->topology_valid = true;
-   c->built = true;
-   c->build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-   return UH_OK;
-}
-
-// Raytracing::rebuild_tlas (raytracing.rs:400-459) for a flattened tree: see refit.hip
-int uh_refit_acceleration(uh_ctx* c) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!c->topology_valid)
-      return fail(c, UH_ERR_NOT_BUILT, "uh_refit_acceleration: meshes or lights were added since the last uh_build_acceleration (or it never ran)");
-   HIP_TRY(c, hipSetDevice(c->device));
-   auto t0 = std::chrono::steady_clock::now();
-   if (int st = sync_all(c)) return st;  // frames in flight still traverse the old boxes
-   const size_t total = c->packet_keys.size();
-   if (total && !c->d_obj_corners.p) {
-      count_host_upload(c, 9 * sizeof(float));  // (only the host builder leaves no d_obj_corners, and it has made the mirrors)
-      std::vector<float> oc(9 * total);
-      for (size_t i = 0; i < total; i++) {
-         const HostMesh& m = c->meshes[c->packet_keys[i] >> kPrimBits];
-         const uint32_t p = c->packet_keys[i] & kPrimMask;
-         for (int k = 0; k < 3; k++) {
-            const UhVertex& vx = m.vertices[m.indices[3 * (size_t)p + k]];
-            for (int a = 0; a < 3; a++) oc[9 * i + 3 * k + a] = vx.pos[a];
-         }
-      }
-      HIP_TRY(c, c->d_obj_corners.alloc(9 * total));
-      HIP_TRY(c, c->d_world_corners.alloc(9 * total));
-      HIP_TRY(c, c->d_node_box.alloc(6 * (size_t)c->scene.num_nodes));
-      HIP_TRY(c, c->d_refit_meshes.alloc(c->meshes.size()));
-      HIP_TRY(c, hipMemcpy(c->d_obj_corners.p, oc.data(), oc.size() * sizeof(float), hipMemcpyHostToDevice));
-   }
-   std::vector<RefitMesh> rm(c->meshes.size());
-   std::vector<MeshShade> ms(c->meshes.size());
-   HIP_TRY(c, hipMemcpy(ms.data(), c->d_meshes.p, ms.size() * sizeof(MeshShade), hipMemcpyDeviceToHost));
-   for (size_t i = 0; i < c->meshes.size(); i++) {
-      std::memset(&rm[i], 0, sizeof(RefitMesh));
-      std::memcpy(rm[i].o2w, c->meshes[i].o2w, sizeof(rm[i].o2w));
-      rm[i].identity = is_identity3x4(c->meshes[i].o2w) ? 1u : 0u;
-      std::memcpy(ms[i].w2o, c->meshes[i].w2o, sizeof(ms[i].w2o));
-   }
-   if (!ms.empty()) HIP_TRY(c, hipMemcpy(c->d_meshes.p, ms.data(), ms.size() * sizeof(MeshShade), hipMemcpyHostToDevice));
-   if (total) {
-      HIP_TRY(c, hipMemcpy(c->d_refit_meshes.p, rm.data(), rm.size() * sizeof(RefitMesh), hipMemcpyHostToDevice));
-      RefitArgs a;
-      a.obj_corners = c->d_obj_corners.p;
-      a.meshes = c->d_refit_meshes.p;
-      a.tris = c->d_tris.p;
-      a.world_corners = c->d_world_corners.p;
-      a.nodes = reinterpret_cast<uint4*>(c->d_nodes.p);
-      a.node_box = c->d_node_box.p;
-      a.level_start = c->level_start.data();
-      a.num_levels = (uint32_t)c->level_start.size() - 1;
-      a.num_tris = (uint32_t)total;
-      launch_refit(cfg(c), a);
-      HIP_TRY(c, hipGetLastError());
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-   }
-   c->built = true;
-   c->geom_version++;
-   c->build_ms = c->refit_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-   return UH_OK;
-}
-
-// brackets of UhIsosurfaceUpdateStats::scatter_ms on the context's stream (the events exist once an update has run)
-extern "C++" void iso_scatter_begin(uh_ctx* c) {
-   if (c->iso.begin) (void)hipEventRecord(c->iso.begin, c->stream);
-}
-extern "C++" int iso_scatter_end(uh_ctx* c, bool add) {
-   if (!c->iso.begin) return UH_OK;
-   HIP_TRY(c, hipEventRecord(c->iso.end, c->stream));
-   HIP_TRY(c, hipEventSynchronize(c->iso.end));
-   float ms = 0.0f;
-   HIP_TRY(c, hipEventElapsedTime(&ms, c->iso.begin, c->iso.end));
-   c->iso.st.scatter_ms = add ? c->iso.st.scatter_ms + ms : ms;
-   return UH_OK;
-}
-
-// d_src_corners / d_src_keys / d_src_shade: the on-device build's per-triangle sources in mesh order (object-space corners,
-// key = mesh << 22 | primitive, normals and uvs of the three vertices, the mesh index). Host-resident meshes are assembled on the
-// host and uploaded when the mesh list has changed (src_valid); a device-resident mesh's range is written by k_iso_scatter from its
-// device vertices whenever its serial has moved, and the ranges of the meshes that did not change are then copied on the device.
-static int refresh_build_sources(uh_ctx* c, size_t total) {
-   const size_t nm = c->meshes.size();
-   std::vector<uint32_t> tris(nm);
-   std::vector<size_t> at(nm + 1, 0);
-   bool any_dev = false;
-   for (size_t i = 0; i < nm; i++) {
-      tris[i] = (uint32_t)c->meshes[i].tris();
-      at[i + 1] = at[i] + tris[i];
-      any_dev = any_dev || c->meshes[i].dev;
-   }
-   std::vector<uint32_t> todo;  // meshes whose range k_iso_scatter writes
-   if (!c->src_valid) {
-      std::vector<float> corners(9 * total);
-      std::vector<uint32_t> keys(total);
-      std::vector<ShadePacket> sp(total);
-      size_t t = 0;
-      for (uint32_t mi = 0; mi < nm; mi++) {
-         const HostMesh& m = c->meshes[mi];
-         if (m.dev) {
-            t += m.dev_tris;
-            continue;
-         }
-         const uint32_t nt = (uint32_t)m.tris();
-         for (uint32_t p = 0; p < nt; p++, t++) {
-            const UhVertex* v[3] = {&m.vertices[m.indices[3 * (size_t)p]], &m.vertices[m.indices[3 * (size_t)p + 1]], &m.vertices[m.indices[3 * (size_t)p + 2]]};
-            ShadePacket& s = sp[t];
-            for (int k = 0; k < 3; k++)
-               for (int a = 0; a < 3; a++) corners[9 * t + 3 * k + a] = v[k]->pos[a];
-            for (int a = 0; a < 3; a++) {
-               s.n0[a] = v[0]->normal[a];
-               s.n1[a] = v[1]->normal[a];
-               s.n2[a] = v[2]->normal[a];
-            }
-            for (int a = 0; a < 2; a++) {
-               s.uv0[a] = v[0]->uv[a];
-               s.uv1[a] = v[1]->uv[a];
-               s.uv2[a] = v[2]->uv[a];
-            }
-            s.mesh = mi;
-            keys[t] = (mi << kPrimBits) | p;
-         }
-      }
-      HIP_TRY(c, c->d_src_corners.alloc(9 * total));
-      HIP_TRY(c, c->d_src_keys.alloc(total));
-      HIP_TRY(c, c->d_src_shade.alloc(4 * total));
-      // one upload per run of host-resident meshes (the whole array when no mesh is device-resident)
-      for (size_t i = 0; i < nm;) {
-         if (c->meshes[i].dev) {
-            todo.push_back((uint32_t)i++);
-            continue;
-         }
-         size_t j = i;
-         while (j < nm && !c->meshes[j].dev) j++;
-         const size_t first = at[i], n = at[j] - at[i];
-         if (n) {
-            HIP_TRY(c, hipMemcpy(c->d_src_corners.p + 9 * first, corners.data() + 9 * first, 9 * n * sizeof(float), hipMemcpyHostToDevice));
-            HIP_TRY(c, hipMemcpy(c->d_src_keys.p + first, keys.data() + first, n * sizeof(uint32_t), hipMemcpyHostToDevice));
-            HIP_TRY(c, hipMemcpy(c->d_src_shade.p + 4 * first, sp.data() + first, n * sizeof(ShadePacket), hipMemcpyHostToDevice));
-         }
-         i = j;
-      }
-      iso_scatter_begin(c);
-   } else {
-      if (!any_dev) return UH_OK;  // (uh_add_mesh invalidates: the layout is that of the mesh list)
-      bool same_counts = true;
-      for (size_t i = 0; i < nm; i++) {
-         if (c->src_serial[i] != c->meshes[i].serial) todo.push_back((uint32_t)i);
-         same_counts = same_counts && c->src_tris[i] == tris[i];
-      }
-      if (todo.empty()) return UH_OK;
-      iso_scatter_begin(c);
-      if (!same_counts) {
-         // the ranges move: a second set of arrays, the unchanged runs copied across on the device
-         DevBuf<float> nc;
-         DevBuf<uint32_t> nk;
-         DevBuf<float4> ns;
-         const auto give_up = [&](hipError_t e, const char* what) {
-            nc.release(), nk.release(), ns.release();
-            return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string("build sources: ") + what + ": " + hipGetErrorString(e));
-         };
-         hipError_t e;
-         if ((e = nc.alloc(9 * total)) != hipSuccess || (e = nk.alloc(total)) != hipSuccess || (e = ns.alloc(4 * total)) != hipSuccess) return give_up(e, "allocation");
-         std::vector<size_t> old_at(nm + 1, 0);
-         for (size_t i = 0; i < nm; i++) old_at[i + 1] = old_at[i] + c->src_tris[i];
-         for (size_t i = 0; i < nm;) {
-            if (c->src_serial[i] != c->meshes[i].serial) {
-               i++;
-               continue;
-            }
-            size_t j = i;
-            while (j < nm && c->src_serial[j] == c->meshes[j].serial) j++;
-            const size_t from = old_at[i], to = at[i], n = at[j] - at[i];
-            if (n) {
-               if ((e = hipMemcpyAsync(nc.p + 9 * to, c->d_src_corners.p + 9 * from, 9 * n * sizeof(float), hipMemcpyDeviceToDevice, c->stream)) != hipSuccess ||
-                   (e = hipMemcpyAsync(nk.p + to, c->d_src_keys.p + from, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream)) != hipSuccess ||
-                   (e = hipMemcpyAsync(ns.p + 4 * to, c->d_src_shade.p + 4 * from, n * sizeof(ShadePacket), hipMemcpyDeviceToDevice, c->stream)) != hipSuccess) {
-                  (void)hipStreamSynchronize(c->stream);
-                  return give_up(e, "device copy");
-               }
-            }
-            i = j;
-         }
-         if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return give_up(e, "device copy");
-         std::swap(c->d_src_corners, nc);
-         std::swap(c->d_src_keys, nk);
-         std::swap(c->d_src_shade, ns);
-         nc.release(), nk.release(), ns.release();
-         c->src_valid = false;  // src_tris / src_serial describe the old layout until the end of this call: a failure below starts over
-      }
-   }
-   if (!todo.empty()) {
-      // every device-resident mesh in `todo` through k_iso_scatter; its box words come back with the build's own wait
-      std::vector<uint32_t> box(6 * todo.size());
-      for (size_t k = 0; k < todo.size(); k++)
-         for (int a = 0; a < 6; a++) box[6 * k + a] = a < 3 ? 0xffffffffu : 0u;
-      if (c->iso.box.n < box.size()) HIP_TRY(c, c->iso.box.alloc(box.size()));
-      HIP_TRY(c, hipMemcpy(c->iso.box.p, box.data(), box.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-      for (size_t k = 0; k < todo.size(); k++) {
-         const HostMesh& m = c->meshes[todo[k]];
-         const size_t first = at[todo[k]];
-         uhi_iso_scatter(c->stream, m.d_verts, m.dev_tris, todo[k], c->d_src_corners.p + 9 * first, c->d_src_keys.p + first,
-                         c->d_src_shade.p + 4 * first, c->iso.box.p + 6 * k);
-      }
-      HIP_TRY(c, hipGetLastError());
-      if (int st = iso_scatter_end(c, false)) return st;
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      HIP_TRY(c, hipMemcpy(box.data(), c->iso.box.p, box.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-      for (size_t k = 0; k < todo.size(); k++) {
-         HostMesh& m = c->meshes[todo[k]];
-         for (int a = 0; a < 3; a++) {
-            m.olo[a] = uhi_box_decode(box[6 * k + a]);
-            m.ohi[a] = uhi_box_decode(box[6 * k + 3 + a]);
-         }
-         m.box_serial = m.serial;
-      }
-   }
-   c->src_tris = tris;
-   c->src_serial.resize(nm);
-   for (size_t i = 0; i < nm; i++) c->src_serial[i] = c->meshes[i].serial;
-   c->src_valid = true;
-   return UH_OK;
-}
-
-// uh_build_acceleration with option "device_build": Morton-order tree built by lbvh.hip, boxes by refit.hip
-static int build_on_device(uh_ctx* c) {
-   auto t0 = std::chrono::steady_clock::now();
-   size_t total = 0;
-   for (const HostMesh& m : c->meshes) total += m.tris();
-   if (total > kMaxTriangles) return fail(c, UH_ERR_CAPACITY, "scene has more than 2^31 - 2 triangles");
-   if (int st = sync_all(c)) return st;
-   if (int st = upload_scene_tables(c)) return st;
-   if (int st = refresh_build_sources(c, total)) return st;
-   // per-mesh rows + a box that holds every centroid: the 8 corners of each mesh's object-space box, transformed
-   std::vector<RefitMesh> rm(c->meshes.size());
-   float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-   for (size_t i = 0; i < c->meshes.size(); i++) {
-      const HostMesh& m = c->meshes[i];
-      std::memset(&rm[i], 0, sizeof(RefitMesh));
-      std::memcpy(rm[i].o2w, m.o2w, sizeof(rm[i].o2w));
-      rm[i].identity = is_identity3x4(m.o2w) ? 1u : 0u;
-      float olo[3] = {INFINITY, INFINITY, INFINITY}, ohi[3] = {-INFINITY, -INFINITY, -INFINITY};
-      if (m.dev) {
-         // the same minima and maxima, reduced on the device by k_iso_scatter (refresh_build_sources)
-         if (!m.dev_tris) continue;
-         if (m.box_serial != m.serial) return fail(c, UH_ERR_HIP, "internal: a device-resident mesh has no box");
-         for (int a = 0; a < 3; a++) olo[a] = m.olo[a], ohi[a] = m.ohi[a];
-      } else {
-         for (const UhVertex& v : m.vertices)
-            for (int a = 0; a < 3; a++) {
-               olo[a] = std::fmin(olo[a], v.pos[a]);
-               ohi[a] = std::fmax(ohi[a], v.pos[a]);
-            }
-         if (m.vertices.empty()) continue;
-      }
-      for (int k = 0; k < 8; k++) {
-         const float x = (k & 1) ? ohi[0] : olo[0], y = (k & 2) ? ohi[1] : olo[1], z = (k & 4) ? ohi[2] : olo[2];
-         for (int a = 0; a < 3; a++) {
-            const float w = m.o2w[4 * a] * x + m.o2w[4 * a + 1] * y + m.o2w[4 * a + 2] * z + m.o2w[4 * a + 3];
-            lo[a] = std::fmin(lo[a], w);
-            hi[a] = std::fmax(hi[a], w);
-         }
-      }
-   }
-   for (int a = 0; a < 3; a++)
-      if (!(lo[a] <= hi[a]) || !std::isfinite(lo[a]) || !std::isfinite(hi[a])) lo[a] = hi[a] = 0.0f;
-   const size_t node_cap = total > 1 ? total : 1;
-   HIP_TRY(c, c->d_nodes.alloc(node_cap * kNodeStride16));
-   HIP_TRY(c, c->d_tris.alloc(total * kTriStride16));
-   HIP_TRY(c, c->d_shade.alloc(total * 4));
-   HIP_TRY(c, c->d_obj_corners.alloc(9 * total));
-   HIP_TRY(c, c->d_world_corners.alloc(9 * total));
-   HIP_TRY(c, c->d_node_box.alloc(6 * node_cap));
-   HIP_TRY(c, c->d_refit_meshes.alloc(rm.size()));
-   if (!rm.empty()) HIP_TRY(c, hipMemcpy(c->d_refit_meshes.p, rm.data(), rm.size() * sizeof(RefitMesh), hipMemcpyHostToDevice));
-   LbvhArgs la;
-   la.src_corners = c->d_src_corners.p;
-   la.src_keys = c->d_src_keys.p;
-   la.src_shade = c->d_src_shade.p;
-   la.meshes = c->d_refit_meshes.p;
-   for (int a = 0; a < 3; a++) {
-      la.bounds_lo[a] = lo[a];
-      la.bounds_hi[a] = hi[a];
-   }
-   la.num_tris = (uint32_t)total;
-   la.kind = c->device_build_kind;
-   la.ploc_radius = uh_ctx::kPlocRadius;
-   la.sah_top = c->ploc_sah_top;
-   la.nodes = reinterpret_cast<uint4*>(c->d_nodes.p);
-   la.node_capacity = (uint32_t)node_cap;
-   la.tris = c->d_tris.p;
-   la.shade = c->d_shade.p;
-   la.obj_corners = c->d_obj_corners.p;
-   uint32_t num_nodes = 1;
-   hipError_t e = lbvh_build(la, c->stream, c->level_start, &num_nodes);
-   if (e == hipErrorUnknown) {
-      // the builder gave up on this geometry (a PLOC round that merges nothing: every union area inf / NaN, e.g. coordinates
-      // around 1e19 whose area products overflow): like a tree that came out too deep, such a scene gets the host builder
-      (void)hipGetLastError();
-      c->device_build = false;
-      const int st = uh_build_acceleration(c);
-      c->device_build = true;
-      return st;
-   }
-   if (e != hipSuccess) return fail(c, UH_ERR_HIP, std::string("device BVH build: ") + hipGetErrorString(e));
-   if (c->level_start.size() - 1 > kMaxTreeLevels) {
-      // a Morton tree over clustered geometry can be a long chain; deeper than the traversal stack it would drop
-      // subtrees silently: this scene gets the host builder (which has a balanced fallback of its own)
-      c->device_build = false;
-      const int st = uh_build_acceleration(c);
-      c->device_build = true;
-      return st;
-   }
-   if (total) {
-      RefitArgs a;
-      a.obj_corners = c->d_obj_corners.p;
-      a.meshes = c->d_refit_meshes.p;
-      a.tris = c->d_tris.p;
-      a.world_corners = c->d_world_corners.p;
-      a.nodes = reinterpret_cast<uint4*>(c->d_nodes.p);
-      a.node_box = c->d_node_box.p;
-      a.level_start = c->level_start.data();
-      a.num_levels = (uint32_t)c->level_start.size() - 1;
-      a.num_tris = (uint32_t)total;
-      launch_refit(cfg(c), a);
-      HIP_TRY(c, hipGetLastError());
-   }
-   HIP_TRY(c, hipStreamSynchronize(c->stream));
-   c->scene.nodes = reinterpret_cast<const uint4*>(c->d_nodes.p);
-   c->scene.tris = c->d_tris.p;
-   c->scene.shade = c->d_shade.p;
-   c->scene.num_nodes = num_nodes;
-   c->scene.num_tris = (uint32_t)total;
-   c->bvh_nodes = num_nodes;
-   c->bvh_tris = (uint32_t)total;
-   c->packet_keys.assign(total, 0u);  // only its size is used once d_obj_corners exists (uh_refit_acceleration)
-   c->geom_version++;
-   c->topology_valid = true;
-   c->built = true;
-   c->build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
    return UH_OK;
 }
 
@@ -2381,114 +1795,6 @@ int uh_device_pointer(uh_ctx* c, int which, void** out) {
       *out = c->output.p;
    else
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_device_pointer: which must be 0 or 1");
-   return UH_OK;
-}
-
-int uh_mesh_info(uh_ctx* c, uint32_t mesh_index, uint32_t* num_vertices, uint32_t* num_indices) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (mesh_index >= c->meshes.size()) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_mesh_info: bad mesh index");
-   if (num_vertices) *num_vertices = (uint32_t)c->meshes[mesh_index].num_vertices();
-   if (num_indices) *num_indices = (uint32_t)c->meshes[mesh_index].num_indices();
-   return UH_OK;
-}
-
-int uh_read_mesh(uh_ctx* c, uint32_t mesh_index, UhVertex* vertices, uint32_t* indices) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (mesh_index >= c->meshes.size()) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_mesh: bad mesh index");
-   const HostMesh& m = c->meshes[mesh_index];
-   if (m.dev && !m.host_valid) {
-      // a device-resident mesh without a host mirror: the vertices come from the device (a blocking copy; they are idle since the
-      // update returned)
-      if (!m.dev_tris) return UH_OK;
-      HIP_TRY(c, hipSetDevice(c->device));
-      const size_t n = 3 * (size_t)m.dev_tris;
-      if (vertices) {
-         HIP_TRY(c, hipMemcpy(vertices, m.d_verts, n * sizeof(UhVertex), hipMemcpyDeviceToHost));
-         c->iso.st.host_geometry_bytes += n * sizeof(UhVertex);
-      }
-      if (indices) {
-         for (size_t i = 0; i < n; i++) indices[i] = (uint32_t)i;  // the index list of a device-resident mesh is never stored
-         c->iso.st.host_geometry_bytes += n * sizeof(uint32_t);    // counted as handed to the host, like the vertices
-      }
-      return UH_OK;
-   }
-   if (vertices && !m.vertices.empty()) std::memcpy(vertices, m.vertices.data(), m.vertices.size() * sizeof(UhVertex));
-   if (indices && !m.indices.empty()) std::memcpy(indices, m.indices.data(), m.indices.size() * sizeof(uint32_t));
-   return UH_OK;
-}
-
-int uhi_mark_isosurface(uh_ctx* c, uint32_t mesh_index, uint32_t resolution, float lo, float hi, int reference) {
-   if (!c || mesh_index >= c->meshes.size()) return UH_ERR_INVALID_ARGUMENT;
-   HostMesh& m = c->meshes[mesh_index];
-   m.iso = true;
-   m.iso_reference = reference != 0;
-   m.iso_res = resolution;
-   m.iso_lo = lo;
-   m.iso_hi = hi;
-   return UH_OK;
-}
-
-int uh_update_isosurface_mesh(uh_ctx* c, uint32_t mesh_index, float time, uint32_t* out_triangles) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (mesh_index >= c->meshes.size()) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_update_isosurface_mesh: bad mesh index");
-   if (!c->meshes[mesh_index].iso) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_update_isosurface_mesh: the mesh was not created by uh_add_isosurface_mesh");
-   if (!std::isfinite(time)) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_update_isosurface_mesh: time is not finite");
-   HIP_TRY(c, hipSetDevice(c->device));
-   if (int st = sync_all(c)) return st;
-   HostMesh& m = c->meshes[mesh_index];
-   uh_ctx::IsoUpdate& u = c->iso;
-   for (hipEvent_t* ev : {&u.begin, &u.end})
-      if (!*ev) HIP_TRY(c, hipEventCreate(ev));
-   const uint32_t blocks = uhi_iso_blocks(m.iso_res), n_chunks = scan_chunk_count(blocks);
-   if (u.counts.n < blocks) HIP_TRY(c, u.counts.alloc(blocks));
-   if (u.chunks.n < n_chunks) HIP_TRY(c, u.chunks.alloc(n_chunks));
-   if (!u.total.p) HIP_TRY(c, u.total.alloc(1));
-   HIP_TRY(c, hipEventRecord(u.begin, c->stream));
-   unsigned long long total = 0;  // the 8 bytes that size the buffers
-   if (!uhi_iso_count_triangles(c->stream, m.iso_res, m.iso_lo, m.iso_hi, time, m.iso_reference, u.counts.p, u.chunks.p, u.total.p, &total))
-      return fail(c, UH_ERR_HIP, std::string("uh_update_isosurface_mesh: count pass: ") + hipGetErrorString(hipGetLastError()));
-   if (total > (1ull << kPrimBits)) return fail(c, UH_ERR_CAPACITY, "uh_update_isosurface_mesh: more than 4 Mi triangles");
-   if (3 * total > m.d_capacity) {
-      // the new buffer first: a refusal leaves the mesh as it was
-      UhVertex* grown = nullptr;
-      HIP_TRY(c, hipMalloc((void**)&grown, 3 * total * sizeof(UhVertex)));
-      if (m.d_verts) (void)hipFree(m.d_verts);
-      m.d_verts = grown;
-      m.d_capacity = 3 * total;
-   }
-   // from here on the mesh's geometry is the new one (the vertex buffer is being overwritten): whatever happens, the context is not built
-   m.dev = true;
-   m.host_valid = false;
-   m.dev_tris = (uint32_t)total;
-   m.serial++;
-   std::vector<UhVertex>().swap(m.vertices);
-   std::vector<uint32_t>().swap(m.indices);
-   c->built = false;
-   c->topology_valid = false;
-   if (total && !uhi_iso_extract_emit(c->stream, m.iso_res, m.iso_lo, m.iso_hi, time, m.iso_reference, u.counts.p, m.d_verts))
-      return fail(c, UH_ERR_HIP, "uh_update_isosurface_mesh: the case tables could not be loaded");
-   HIP_TRY(c, hipGetLastError());
-   HIP_TRY(c, hipEventRecord(u.end, c->stream));
-   HIP_TRY(c, hipStreamSynchronize(c->stream));
-   HIP_TRY(c, hipEventElapsedTime(&u.st.extract_ms, u.begin, u.end));
-   u.st.scatter_ms = 0.0f;
-   u.st.updates++;
-   u.st.triangles = (uint32_t)total;
-   if (out_triangles) *out_triangles = (uint32_t)total;
-   return UH_OK;
-}
-
-int uh_get_isosurface_update_stats(uh_ctx* c, UhIsosurfaceUpdateStats* out) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_isosurface_update_stats: null destination");
-   std::memset(out, 0, sizeof(*out));
-   HIP_TRY(c, hipSetDevice(c->device));
-   if (int st = sync_all(c)) return st;
-   if (!c->iso.st.updates) return UH_OK;
-   *out = c->iso.st;
-   const uh_ctx::IsoUpdate& u = c->iso;
-   out->device_bytes = u.counts.n * sizeof(uint32_t) + u.chunks.n * sizeof(uint32_t) + u.box.n * sizeof(uint32_t) + u.total.n * sizeof(unsigned long long);
-   for (const HostMesh& m : c->meshes) out->device_bytes += m.d_capacity * sizeof(UhVertex);
    return UH_OK;
 }
 

@@ -43,7 +43,7 @@ uint32_t uhi_iso_blocks(uint32_t resolution);
 bool uhi_iso_count_triangles(void* stream, uint32_t resolution, float lo, float hi, float time, bool reference, uint32_t* block_counts, uint32_t* chunks,
                              unsigned long long* d_total, unsigned long long* total);
 bool uhi_iso_extract_emit(void* stream, uint32_t resolution, float lo, float hi, float time, bool reference, const uint32_t* block_offsets, UhVertex* verts);
-// context.hip: mesh `mesh_index` was made by uh_add_isosurface_mesh with these parameters (uh_update_isosurface_mesh re-extracts with them)
+// scene_build.hip: mesh `mesh_index` was made by uh_add_isosurface_mesh with these parameters (uh_update_isosurface_mesh re-extracts with them)
 extern "C" int uhi_mark_isosurface(uh_ctx*, uint32_t mesh_index, uint32_t resolution, float lo, float hi, int reference);
 // iso_update.hip: what feeds a device-resident mesh's consumers from its device vertices, enqueued on `stream`.
 // uhi_iso_scatter: per triangle p of the mesh (vertices 3 p .. 3 p + 2) the on-device build's sources - 9 corner floats, key = mesh << 22 | p,

@@ -1,10 +1,11 @@
-// context_state.h - struct uh_ctx and the types it is made of, for the two files that implement the context: context.hip (lifetime,
-// scene, builders, the path tracer, the multi-GPU composition) and graphs.hip (the hybrid and the forward graph). Private: not
-// installed, not part of the C ABI (include/utopian_hip.h), where uh_ctx stays opaque.
+// context_state.h - struct uh_ctx and the types it is made of, for the three files that implement the context: context.hip (lifetime,
+// the path tracer, the multi-GPU composition), scene_build.hip (meshes, builders, refit) and graphs.hip (the hybrid and the forward
+// graph). Private: not installed, not part of the C ABI (include/utopian_hip.h), where uh_ctx stays opaque.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "bvh.h"
@@ -12,7 +13,7 @@
 #include "device_types.h"
 #include "utopian_hip.h"
 
-using namespace uh;  // (both including files are written inside it)
+using namespace uh;  // (the including files are written inside it)
 
 struct HostMesh {
    std::vector<UhVertex> vertices;
@@ -64,6 +65,34 @@ struct DevBuf {
       p = nullptr;
       base = nullptr;
       n = 0;
+   }
+};
+
+// the on-device build's per-triangle sources in mesh order: 9 floats of object-space corners, the key mesh << 22 | primitive and a
+// ShadePacket (4 float4: normals and uvs of the three vertices, the mesh index) per triangle
+struct __attribute__((visibility("hidden"))) BuildSources {
+   DevBuf<float> corners;
+   DevBuf<uint32_t> keys;
+   DevBuf<float4> shade;
+   struct View { const float* corners; const uint32_t* keys; const float4* shade; };
+   View view() const { return View{corners.p, keys.p, shade.p}; }
+   hipError_t alloc(size_t total) {
+      hipError_t e;
+      if ((e = corners.alloc(9 * total)) != hipSuccess || (e = keys.alloc(total)) != hipSuccess) return e;
+      return shade.alloc(4 * total);
+   }
+   void release() { corners.release(), keys.release(), shade.release(); }
+   void swap(BuildSources& o) { std::swap(corners, o.corners), std::swap(keys, o.keys), std::swap(shade, o.shade); }
+   // triangles [src_first, src_first + n) of src to [dst_first, dst_first + n) of these arrays, if any: enqueued on `stream`, or,
+   // without one, three blocking copies
+   hipError_t copy_range(size_t dst_first, const View& src, size_t src_first, size_t n, hipMemcpyKind kind, hipStream_t stream) {
+      const auto copy = [&](void* dst, const void* from, size_t bytes) { return stream ? hipMemcpyAsync(dst, from, bytes, kind, stream) : hipMemcpy(dst, from, bytes, kind); };
+      if (!n) return hipSuccess;
+      hipError_t e;
+      if ((e = copy(corners.p + 9 * dst_first, src.corners + 9 * src_first, 9 * n * sizeof(float))) != hipSuccess ||
+          (e = copy(keys.p + dst_first, src.keys + src_first, n * sizeof(uint32_t))) != hipSuccess)
+         return e;
+      return copy(shade.p + 4 * dst_first, src.shade + 4 * src_first, 4 * n * sizeof(float4));
    }
 };
 
@@ -273,10 +302,8 @@ struct uh_ctx {
    // Config-1 scene: 0 / 1,024 / 8,192 / 131,072 clusters = 21.7 / 20.3 / 20.1 / 19.0 nodes per ray, rebuild 7.7 / 6.0 / 9.4 / 66 ms (host tree: 18.8)
    uint32_t ploc_sah_top = 1024;
    static constexpr uint32_t kPlocRadius = 8;  // swept 4..64 in round 3: tree quality flat (21.7-23.0 nodes/ray), build time grows with it (profiles/README.md)
-   DevBuf<float> d_src_corners;
-   DevBuf<uint32_t> d_src_keys;
-   DevBuf<float4> d_src_shade;
-   // the layout of d_src_*: triangles and HostMesh::serial of each mesh's range (a mesh whose serial moved is rewritten from its
+   BuildSources d_src;
+   // the layout of d_src: triangles and HostMesh::serial of each mesh's range (a mesh whose serial moved is rewritten from its
    // device vertices, the ranges behind it are moved on the device)
    std::vector<uint32_t> src_tris;
    std::vector<uint64_t> src_serial;
@@ -466,7 +493,7 @@ struct uh_ctx {
    } fw;
 };
 
-// ---- context.hip, for graphs.hip (not exported: the library's dynamic symbols stay the C ABI's) ----
+// ---- context.hip, for scene_build.hip and graphs.hip (not exported: the library's dynamic symbols stay the C ABI's) ----
 #pragma GCC visibility push(hidden)
 int fail(uh_ctx* c, int code, const std::string& msg);  // sets uh_last_error (c null: uh_create's); returns code
 #define HIP_TRY(ctx, expr)                                                                                   \
@@ -479,6 +506,7 @@ LaunchCfg cfg(uh_ctx* c);
 FrameParams make_params(uh_ctx* c, const UhViewUniformData& v);
 int sync_all(uh_ctx* c);
 int read_back(uh_ctx* c, void* dst, const void* src, size_t bytes);
+// ---- scene_build.hip, for graphs.hip ----
 // brackets of UhIsosurfaceUpdateStats::scatter_ms on the context's stream (the mesh tables of device-resident meshes count into it)
 void iso_scatter_begin(uh_ctx* c);
 int iso_scatter_end(uh_ctx* c, bool add);

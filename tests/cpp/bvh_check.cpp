@@ -171,7 +171,7 @@ int main() {
    {
       // clusters on a geometric series (each a factor 0.5 closer to the origin than the one before): SAH peels them off one
       // by one and the tree becomes a chain. The traversal stack holds kTraversalStackEntries entries = kMaxTreeLevels
-      // levels; the context rebuilds such a scene balanced (csrc/context.hip), which must fit for any triangle count.
+      // levels; the context rebuilds such a scene balanced (csrc/scene_build.hip), which must fit for any triangle count.
       std::vector<float> chain;
       g_state = 99;
       for (int k = 0; k < 120; k++) {

@@ -62,7 +62,7 @@ def inverse_transpose_mul(w2o, n):
 
 
 def invert3x3(w):
-    """the library's inverse of the upper 3x3 of a row-major 3x4 (context.hip invert3x3: cofactor * (1 / det)); identity verbatim"""
+    """the library's inverse of the upper 3x3 of a row-major 3x4 (scene_build.hip invert3x3: cofactor * (1 / det)); identity verbatim"""
     w = np.asarray(w, dtype=np.float32)
     if np.array_equal(w, rr.identity3x4()):
         return np.eye(3, dtype=np.float32).reshape(9)

@@ -237,6 +237,71 @@ def test_there_and_back(device_build):
     assert va[0].tobytes() == vb[0].tobytes() and np.array_equal(va[1], vb[1])
 
 
+# ---- 4b. two device-resident meshes with host-resident ones between and behind them ------------------------------------------------
+TWO_GROUND, TWO_A, TWO_SPHERE, TWO_B, TWO_BOX = range(5)
+TWO_B_WORLD = rr.transform3x4((0.4, 0.4, 0.4), (-2.0, 3.0, 14.0))  # B beside A (x 1.2 .. 7.6; A starts at x = 8), left of it on screen
+
+
+def make_two(res, t_a, t_b, device_build):
+    """ground, isosurface A at t_a, sphere, isosurface B at t_b, box: built"""
+    r = rr.Renderer(W, H)
+    r.set_option("sun_grid_force", 1)
+    r.set_option("device_build", device_build)
+
+    def mat(*rgb):
+        return rr.make_material(base_color=rgb + (1.0,), diffuse_map=r.default_diffuse_map())
+
+    assert r.add_mesh(*quad((-64, 4.99, -64), (0, 0, 160), (160, 0, 0), 8, 8), mat(0.6, 0.6, 0.6)) == TWO_GROUND
+    assert r.add_isosurface_mesh(res, LO, HI, t_a, material=mat(0.8, 0.8, 0.8)) == (TWO_A, oracle(res, t_a, positions=False)["triangles"])
+    assert r.add_mesh(*icosphere(2), mat(0.8, 0.3, 0.2), rr.transform3x4((3, 3, 3), (4.0, 9.0, 26.0))) == TWO_SPHERE
+    assert r.add_isosurface_mesh(res, LO, HI, t_b, material=mat(0.3, 0.8, 0.4), world3x4=TWO_B_WORLD) == (TWO_B, oracle(res, t_b, positions=False)["triangles"])
+    assert r.add_mesh(*box((27.0, 7.5, 8.0), (2.0, 2.5, 2.0)), mat(0.2, 0.4, 0.8)) == TWO_BOX
+    for p in LIGHTS:
+        r.add_light(p, (1.0, 0.9, 0.8), 40.0)
+    r.build_acceleration()
+    return r
+
+
+def assert_two_equal_fresh(a, res, t_a, t_b, device_build, what):
+    """traces, both meshes and the raster consumers of `a` against a context created at (t_a, t_b); returns that context"""
+    b = make_two(res, t_a, t_b, device_build)
+    ta = traced(a)
+    assert_same(ta, traced(b), f"{what}: traces")
+    for mesh in (TWO_A, TWO_B):
+        assert np.count_nonzero(ta["mesh"] == mesh) > 50, f"{what}: rays miss mesh {mesh}"
+        (va, ia), (vb, ib) = a.read_mesh(mesh), b.read_mesh(mesh)
+        assert va.tobytes() == vb.tobytes() and np.array_equal(ia, ib), f"{what}: mesh {mesh}"
+    ra = rastered(a)
+    assert_same(ra, rastered(b), f"{what}: raster")
+    first = np.cumsum([0] + [len(a.read_mesh(m)[1]) // 3 for m in range(5)])
+    for mesh in (TWO_A, TWO_B):
+        for k in ("gbuffer_visibility", "forward_visibility"):
+            assert np.count_nonzero((ra[k] >= first[mesh]) & (ra[k] < first[mesh + 1])) > 50, f"{what}: {k} misses mesh {mesh}"
+    return b
+
+
+@pytest.mark.parametrize("device_build", [0, 1])
+def test_two_device_meshes_between_host_meshes(device_build):
+    """one mesh updated while the other device-resident one and the host-resident ones behind it move by device copy; then the
+    other with the layout kept; then both before a single build"""
+    res = 32
+    count = {t: oracle(res, t, positions=False)["triangles"] for t in (0.0, 1.0, 3.0, T_PI)}
+    assert count[3.0] != count[0.0] == count[T_PI] and count[1.0] != count[3.0]
+    a = make_two(res, 0.0, 0.0, device_build)
+    rastered(a)  # both graphs have been used before the first update: stale tables would show
+    assert update(a, 3.0, res, mesh=TWO_A) == count[3.0]
+    assert_two_equal_fresh(a, res, 3.0, 0.0, device_build, "A alone")
+    assert update(a, T_PI, res, mesh=TWO_B) == count[T_PI]
+    assert_two_equal_fresh(a, res, 3.0, T_PI, device_build, "B alone")
+    assert a.update_isosurface_mesh(TWO_A, 1.0) == count[1.0]
+    assert update(a, 3.0, res, mesh=TWO_B) == count[3.0]  # (builds)
+    b = assert_two_equal_fresh(a, res, 1.0, 3.0, device_build, "both")
+    (pa, sa), (pb, sb) = path_traced(a), path_traced(b)
+    assert_same(pa, pb, "frames")
+    assert_grids(sa), assert_grids(sb)
+    assert pa["bvh_triangles"] == 128 + count[1.0] + 320 + count[3.0] + 12
+
+
 # ---- 5. a mesh that becomes empty --------------------------------------------------------------------------------------------------
 def _aimed_rays(tri, n=2000, seed=3):
     """rays from around the scene towards points inside one triangle"""
