@@ -498,14 +498,22 @@ static void build_bvh(Oracle& o) {
    }
 }
 
+// Slab test, conservative against its own rounding and against tri_test()'s. Both grow with the distance to the ray's origin: a
+// plane parameter (plane - o) * id carries a few 2^-24 of its own size, and tri_test() works on o - v0, which it knows to 2^-24
+// of its length only, so it accepts rays that pass a triangle - and its box, whose padding near a coordinate plane is an
+// absolute 1e-4 - at a distance of that order, in any direction. The box is therefore grown on every side by kSlabMargin times
+// its largest distance from the origin along any axis, the same bound as the device's node test (DESIGN.md "Arithmetic
+// contract", where the constant is derived and measured). The growth enters per axis as a parameter margin of at most 1e30
+// times it, so an axis-parallel ray (id = +-inf) keeps its infinite parameters and still misses the boxes beside it.
+constexpr float kSlabMargin = 0x1p-16f;  // the device's constant (csrc/node_slab.h); test_oracle_far_rays.py alone needs 2^-21
 static inline bool slab(const BNode& n, V3 o, V3 id, float tmin, float tmax) {
-   float t0x = (n.bmin[0] - o.x) * id.x, t1x = (n.bmax[0] - o.x) * id.x;
-   float t0y = (n.bmin[1] - o.y) * id.y, t1y = (n.bmax[1] - o.y) * id.y;
-   float t0z = (n.bmin[2] - o.z) * id.z, t1z = (n.bmax[2] - o.z) * id.z;
-   float tn = std::fmax(std::fmax(std::fmin(t0x, t1x), std::fmin(t0y, t1y)), std::fmax(std::fmin(t0z, t1z), tmin));
-   float tf = std::fmin(std::fmin(std::fmax(t0x, t1x), std::fmax(t0y, t1y)), std::fmin(std::fmax(t0z, t1z), tmax));
-   // robust: widen the far bound by 4 ulp-ish (Ize, "Robust BVH Ray Traversal")
-   return tn <= tf * 1.0000005f + 1e-30f;
+   float d0x = n.bmin[0] - o.x, d1x = n.bmax[0] - o.x, d0y = n.bmin[1] - o.y, d1y = n.bmax[1] - o.y, d0z = n.bmin[2] - o.z, d1z = n.bmax[2] - o.z;
+   float grow = kSlabMargin * std::fmax(std::fmax(std::fmax(std::fabs(d0x), std::fabs(d1x)), std::fmax(std::fabs(d0y), std::fabs(d1y))), std::fmax(std::fabs(d0z), std::fabs(d1z)));
+   float mx = grow * std::fmin(std::fabs(id.x), 1e30f), my = grow * std::fmin(std::fabs(id.y), 1e30f), mz = grow * std::fmin(std::fabs(id.z), 1e30f);
+   float t0x = d0x * id.x, t1x = d1x * id.x, t0y = d0y * id.y, t1y = d1y * id.y, t0z = d0z * id.z, t1z = d1z * id.z;
+   float tn = std::fmax(std::fmax(std::fmin(t0x, t1x) - mx, std::fmin(t0y, t1y) - my), std::fmax(std::fmin(t0z, t1z) - mz, tmin));
+   float tf = std::fmin(std::fmin(std::fmax(t0x, t1x) + mx, std::fmax(t0y, t1y) + my), std::fmin(std::fmax(t0z, t1z) + mz, tmax));
+   return tn <= tf;
 }
 
 // closest hit over (tmin, tmax). Returns mesh == 0xffffffff on miss.

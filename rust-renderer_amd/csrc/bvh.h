@@ -42,7 +42,8 @@ struct NodeW {
 struct alignas(16) Node4C {
    float origin[3];    // the frame's origin: at or below the lower corner of the node's own (padded) box
    uint32_t meta;      // bits 0-7 / 8-15 / 16-23: biased exponent of the x / y / z quantisation step (a power of two, byte >= 1);
-                       // bits 24-26: n_tri; bits 28-30: n_child (both for the builders and the refit: the traversal reads neither here)
+                       // bits 24-26: n_tri (for the builders and the refit); bits 28-30: n_child (the traversal reads it: a slot at or
+                       // beyond n_child is never entered, however far the ray's margin opens its inverted box)
    uint32_t qlo[3];    // per axis: child slot k's quantised lower plane in byte k
    uint32_t qhi[3];    // per axis: upper plane
    uint32_t child_base;  // bits 0-28: first node child; bits 29-31: n_tri

@@ -17,6 +17,7 @@
 #include "device_types.h"
 #include "hybrid_shading.h"
 #include "ibl_device.h"
+#include "node_slab.h"
 
 namespace uh {
 
@@ -30,8 +31,8 @@ constexpr int kSpillStack = (int)kTraversalStackEntries - kLdsStack;            
 // ------------------------------------------------------------------------------------------
 // BVH4 traversal (thread per ray). Closest hit: min t over all triangles with tmin < t < tmax,
 // ties broken by the smaller key (mesh << 22 | prim) — independent of traversal order, because
-// node boxes are padded conservatively by the builder. Any hit: first triangle with
-// tmin < t < tmax and t <= tlimit.
+// the node test culls no triangle the triangle test accepts (node_slab.h: the builders' padded boxes, grown by the
+// rounding of both tests at the ray's distance). Any hit: first triangle with tmin < t < tmax and t <= tlimit.
 // ------------------------------------------------------------------------------------------
 struct Hit {
    float t, u, v;
@@ -82,8 +83,9 @@ __device__ __forceinline__ bool tri_test(const float4* __restrict__ tris, uint32
 }
 
 __device__ __forceinline__ float safe_rcp_dir(float x) {
-   // the slab test only has to be conservative (boxes are padded by >= 1e-5 relative, the 1-ulp hardware
-   // reciprocal is 1e-7): no IEEE division here; a zero component becomes +-1e-30 so no inf/NaN appears
+   // the slab test only has to be conservative, and its margin (node_slab.h: 2^-16 of the node's reach, measured with idir an ulp
+   // off either way) is 256 times the 1-ulp error of the hardware reciprocal: no IEEE division here; a zero component becomes
+   // +-1e-30 so no inf/NaN appears
    return __builtin_amdgcn_rcpf(fabsf(x) < 1e-30f ? copysignf(1e-30f, x) : x);
 }
 
@@ -134,11 +136,12 @@ __device__ __forceinline__ uint32_t trav_pop(Trav& t, const uint32_t* lds_col, c
 }
 
 // one interior node (Node4C, 48 B = three loads): slab-test the 4 children, continue with the nearest, push
-// the other hits. plane = origin + scale * q  =>  t = q * (scale * idir) + (origin - o) * idir.
+// the other hits. plane = origin + scale * q  =>  t = q * (scale * idir) + (origin - o) * idir -+ the margin of this ray at this node (node_slab.h).
 //   w0 = origin.xyz, step exponents (the node's FRAME) ; w1 = qlo.xyz, qhi.x ; w2 = qhi.y, qhi.z, child_base | n_tri << 29, tri_base
 // Child references are implicit (bvh.h): slot k is triangle packet tri_base + k below n_tri, node child_base + k - n_tri above.
 // Instruction diet: the near / far plane words are picked once per axis by the sign of idir instead of min/max per
-// plane; an empty slot is an inverted box (no child != empty test); only the nearest child is fully ordered
+// plane; an empty slot is an inverted box, and since the margin can open it, slots are counted against n_child (a bit
+// field of the frame word that is loaded anyway); only the nearest child is fully ordered
 // (3 comparators); pushes are branch-free (write always, advance the stack pointer by the hit bit).
 // Returns false when no child was hit: the caller pops (trav_step pops once for its node lanes and its leaf lanes together).
 // CAP (closest-hit order, k_path_fused): children beyond t.tlimit are culled as in a visibility walk - the kernel's shadow rays go
@@ -148,8 +151,12 @@ __device__ __forceinline__ bool node_compute(const uint4 w0, const uint4 w1, con
    const uint32_t meta = w0.w;
    // a power-of-two step is its biased exponent moved to bits 23..30
    const float sx = __uint_as_float((meta & 0xffu) << 23), sy = __uint_as_float((meta << 15) & 0x7f800000u), sz = __uint_as_float((meta << 7) & 0x7f800000u);
-   const float ax = sx * t.idir.x, ay = sy * t.idir.y, az = sz * t.idir.z;
-   const float bx = (__uint_as_float(w0.x) - t.o.x) * t.idir.x, by = (__uint_as_float(w0.y) - t.o.y) * t.idir.y, bz = (__uint_as_float(w0.z) - t.o.z) * t.idir.z;
+   float ax, ay, az, bnx, bny, bnz, bfx, bfy, bfz;
+   const float dx = __uint_as_float(w0.x) - t.o.x, dy = __uint_as_float(w0.y) - t.o.y, dz = __uint_as_float(w0.z) - t.o.z;
+   const float growth = slab_node_growth(dx, sx, dy, sy, dz, sz);
+   slab_axis(dx, sx, t.idir.x, growth, ax, bnx, bfx);
+   slab_axis(dy, sy, t.idir.y, growth, ay, bny, bfy);
+   slab_axis(dz, sz, t.idir.z, growth, az, bnz, bfz);
    const bool nx = t.idir.x < 0.0f, ny = t.idir.y < 0.0f, nz = t.idir.z < 0.0f;
    // qlo = (w1.x, w1.y, w1.z), qhi = (w1.w, w2.x, w2.y)
    const uint32_t qnx = nx ? w1.w : w1.x, qfx = nx ? w1.x : w1.w;
@@ -157,7 +164,7 @@ __device__ __forceinline__ bool node_compute(const uint4 w0, const uint4 w1, con
    const uint32_t qnz = nz ? w2.y : w1.z, qfz = nz ? w1.z : w2.y;
    const float tcap = (ANY || CAP) ? fminf(t.best.t, t.tlimit) : t.best.t;  // closest: tlimit is +inf
    float tn[4];
-   const uint32_t n_tri = w2.z >> kChildBaseBits;
+   const uint32_t n_tri = w2.z >> kChildBaseBits, n_child = (meta >> kMetaChildShift) & 7u;
    const uint32_t tri0 = kLeafBit | w2.w, node0 = (w2.z & kChildBaseMask) - n_tri;
    uint32_t cr[4];
 #pragma unroll
@@ -165,12 +172,12 @@ __device__ __forceinline__ bool node_compute(const uint4 w0, const uint4 w1, con
    bool hit[4];
 #pragma unroll
    for (int k = 0; k < 4; k++) {
-      const float t0x = fmaf((float)((qnx >> (8 * k)) & 0xffu), ax, bx), t1x = fmaf((float)((qfx >> (8 * k)) & 0xffu), ax, bx);
-      const float t0y = fmaf((float)((qny >> (8 * k)) & 0xffu), ay, by), t1y = fmaf((float)((qfy >> (8 * k)) & 0xffu), ay, by);
-      const float t0z = fmaf((float)((qnz >> (8 * k)) & 0xffu), az, bz), t1z = fmaf((float)((qfz >> (8 * k)) & 0xffu), az, bz);
+      const float t0x = slab_t((qnx >> (8 * k)) & 0xffu, ax, bnx), t1x = slab_t((qfx >> (8 * k)) & 0xffu, ax, bfx);
+      const float t0y = slab_t((qny >> (8 * k)) & 0xffu, ay, bny), t1y = slab_t((qfy >> (8 * k)) & 0xffu, ay, bfy);
+      const float t0z = slab_t((qnz >> (8 * k)) & 0xffu, az, bnz), t1z = slab_t((qfz >> (8 * k)) & 0xffu, az, bfz);
       const float tnear = fmaxf(fmaxf(t0x, t0y), fmaxf(t0z, t.tmin));
       const float tfar = fminf(fminf(t1x, t1y), fminf(t1z, tcap));
-      hit[k] = tnear <= tfar;
+      hit[k] = tnear <= tfar && (uint32_t)k < n_child;  // the margin can open an empty slot's inverted box: count the slots
       tn[k] = hit[k] ? tnear : INFINITY;
    }
    if (ANY) {

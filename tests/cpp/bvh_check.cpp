@@ -6,12 +6,22 @@
 //   then empty slots; the device node's implicit addressing (tri_base + slot, child_base + slot - n_tri) reproduces
 //   the explicit refs; every full-precision child box contains its subtree's triangles; every quantised box contains
 //   the full-precision box; empty slots are inverted boxes; level_start describes the breadth-first levels.
+// The node test's arithmetic (csrc/node_slab.h, the very text node_compute of kernels.hip compiles) against the triangle test's
+// (tri_compute of kernels.hip, restated here with fmaf in the same order), for rays that start up to 1e6 away from the geometry:
+//   for every (ray, triangle) pair the triangle test accepts, every slot on the way from the root to the triangle's leaf passes
+//   the node test - with idir as the host computes it (correctly rounded) and with every component one ulp up and one ulp down
+//   (the hardware reciprocal is good to one ulp).
+// `bvh_check count` prints the number of culled pairs instead of failing on them: with -DUH_SLAB_MARGIN=... that measures the
+// smallest margin that culls nothing (DESIGN.md "Arithmetic contract").
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "bvh.h"
+#include "node_slab.h"
 
 using namespace uh;
 
@@ -23,7 +33,164 @@ static float rnd() {
    return (float)w / 4294967296.0f;
 }
 
-static int check(const std::vector<float>& corners, int threads, const char* name, bool geometry = true) {
+static double rnd64() { return ((double)(uint32_t)(rnd() * 4294967296.0f) + 0.5) / 4294967296.0; }  // (0, 1)
+
+static bool g_count_only = false;
+static unsigned long long g_culled = 0, g_accepted = 0;
+
+struct F3 {
+   float x, y, z;
+};
+static F3 operator-(F3 a, F3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+static float dot_fma(F3 a, F3 b) { return std::fmaf(a.z, b.z, std::fmaf(a.y, b.y, a.x * b.x)); }
+static F3 cross_fma(F3 a, F3 b) { return {std::fmaf(a.y, b.z, -(a.z * b.y)), std::fmaf(a.z, b.x, -(a.x * b.z)), std::fmaf(a.x, b.y, -(a.y * b.x))}; }
+
+// tri_compute of kernels.hip on a packet baked as scene_build.hip bakes it (v0, e1 = v1 - v0, e2 = v2 - v0 in float): true when a
+// ray that has found nothing yet (best.t = tmax) accepts the triangle; *t_out = its parameter
+static bool tri_accepts(const float* c, F3 o, F3 d, float tmin, float tmax, float* t_out) {
+   const F3 v0 = {c[0], c[1], c[2]}, e1 = {c[3] - c[0], c[4] - c[1], c[5] - c[2]}, e2 = {c[6] - c[0], c[7] - c[1], c[8] - c[2]};
+   const F3 p = cross_fma(d, e2);
+   const float det = dot_fma(e1, p);
+   if (det == 0.0f) return false;
+   const float inv = 1.0f / det;
+   const F3 tv = o - v0;
+   const float u = dot_fma(tv, p) * inv;
+   if (!(u >= 0.0f && u <= 1.0f)) return false;
+   const F3 q = cross_fma(tv, e1);
+   const float v = dot_fma(d, q) * inv;
+   if (!(v >= 0.0f && u + v <= 1.0f)) return false;
+   const float t = dot_fma(e2, q) * inv;
+   if (!(t > tmin) || !(t < tmax)) return false;
+   *t_out = t;
+   return true;
+}
+
+static float safe_rcp_dir(float x) { return 1.0f / (std::fabs(x) < 1e-30f ? std::copysign(1e-30f, x) : x); }  // kernels.hip, with the host's division
+
+// node_compute of kernels.hip for one slot: the planes by the text the kernel compiles (node_slab.h); tcap = the t of the hit
+// that must not be lost (whatever the walk has found by then is no nearer, or the triangle does not matter)
+static bool slot_passes(const Node4C& q, int k, F3 o, F3 idir, float tmin, float tcap) {
+   const float ov[3] = {o.x, o.y, o.z}, iv[3] = {idir.x, idir.y, idir.z};
+   float tnear = tmin, tfar = tcap, step[3], d[3];
+   for (int a = 0; a < 3; a++) {
+      const uint32_t bits = ((q.meta >> (8 * a)) & 0xffu) << 23;
+      std::memcpy(&step[a], &bits, 4);
+      d[a] = q.origin[a] - ov[a];
+   }
+   const float growth = slab_node_growth(d[0], step[0], d[1], step[1], d[2], step[2]);
+   for (int a = 0; a < 3; a++) {
+      float sa, bn, bf;
+      slab_axis(d[a], step[a], iv[a], growth, sa, bn, bf);
+      const bool neg = iv[a] < 0.0f;
+      const uint32_t qn = ((neg ? q.qhi[a] : q.qlo[a]) >> (8 * k)) & 0xffu, qf = ((neg ? q.qlo[a] : q.qhi[a]) >> (8 * k)) & 0xffu;
+      tnear = std::fmax(tnear, slab_t(qn, sa, bn));
+      tfar = std::fmin(tfar, slab_t(qf, sa, bf));
+   }
+   return tnear <= tfar;
+}
+
+// rays from `distance` away towards points of the triangles (a third anywhere on one, a third within 2e-7 * distance of one of
+// its edges on the inside, a third exactly at a vertex), from directions within acos(0.3) of the triangle's normal; direction =
+// target - origin, unnormalised (t about 1) or of unit length (t about distance). Every ray is held against `near` triangles: the
+// one it aims at and those after it in packet order (its neighbours in the tree), or all of them.
+static int far_ray_check(const std::vector<float>& corners, const BuildOutput& out, const char* name, int rays, uint32_t near) {
+   const uint32_t n = (uint32_t)(corners.size() / 9);
+   if (n == 0 || out.cnodes.empty()) return 0;
+   std::vector<uint32_t> up_node(out.cnodes.size(), kEmptyRef), up_slot(out.cnodes.size(), 0), leaf_node(n, kEmptyRef), leaf_slot(n, 0);
+   for (uint32_t ni = 0; ni < out.nodes.size(); ni++)
+      for (uint32_t k = 0; k < 4; k++) {
+         const uint32_t c = out.nodes[ni].child[k];
+         if (c == kEmptyRef) continue;
+         if (c & kLeafBit) {
+            if ((c & ~kLeafBit) < n) leaf_node[c & ~kLeafBit] = ni, leaf_slot[c & ~kLeafBit] = k;
+         } else if (c < out.cnodes.size()) {
+            up_node[c] = ni, up_slot[c] = k;
+         }
+      }
+   unsigned long long accepted = 0, culled = 0;
+   int errors = 0;
+   const double distances[5] = {1e2, 3e3, 1e4, 1e5, 1e6};
+   for (int di = 0; di < 5; di++)
+      for (int unit = 0; unit < (distances[di] <= 3e3 ? 2 : 1); unit++)
+         for (int r = 0; r < rays; r++) {
+            const double D = distances[di];
+            const uint32_t p = std::min(n - 1, (uint32_t)(rnd64() * n));
+            const float* c = &corners[9 * (size_t)out.tri_order[p]];
+            double w[3] = {rnd64(), rnd64(), rnd64()};
+            if (r % 3 == 2) {
+               const int v = (int)(rnd64() * 3) % 3;
+               w[0] = v == 0, w[1] = v == 1, w[2] = v == 2;
+            } else {
+               if (w[0] + w[1] > 1.0) w[0] = 1.0 - w[0], w[1] = 1.0 - w[1];
+               w[2] = 1.0 - w[0] - w[1];
+               if (r % 3 == 1) {
+                  // towards an edge: the weight of the opposite vertex = distance from the edge / height over it <= 2e-7 D / height
+                  const int v = (int)(rnd64() * 3) % 3, i1 = (v + 1) % 3, i2 = (v + 2) % 3;
+                  double e[3], f[3];
+                  for (int a = 0; a < 3; a++) e[a] = (double)c[3 * i2 + a] - c[3 * i1 + a], f[a] = (double)c[3 * v + a] - c[3 * i1 + a];
+                  const double ee = e[0] * e[0] + e[1] * e[1] + e[2] * e[2], fe = f[0] * e[0] + f[1] * e[1] + f[2] * e[2];
+                  const double h2 = f[0] * f[0] + f[1] * f[1] + f[2] * f[2] - (ee > 0 ? fe * fe / ee : 0.0);
+                  const double wv = h2 > 0 ? std::fmin(1.0, rnd64() * 2e-7 * D / std::sqrt(h2)) : 0.0, s = rnd64();
+                  w[v] = wv, w[i1] = (1.0 - wv) * s, w[i2] = (1.0 - wv) * (1.0 - s);
+               }
+            }
+            double tg[3], nrm[3];
+            for (int a = 0; a < 3; a++) tg[a] = (double)(float)(w[0] * c[a] + w[1] * c[3 + a] + w[2] * c[6 + a]);
+            {
+               const double e1[3] = {(double)c[3] - c[0], (double)c[4] - c[1], (double)c[5] - c[2]}, e2[3] = {(double)c[6] - c[0], (double)c[7] - c[1], (double)c[8] - c[2]};
+               nrm[0] = e1[1] * e2[2] - e1[2] * e2[1], nrm[1] = e1[2] * e2[0] - e1[0] * e2[2], nrm[2] = e1[0] * e2[1] - e1[1] * e2[0];
+               const double l = std::sqrt(nrm[0] * nrm[0] + nrm[1] * nrm[1] + nrm[2] * nrm[2]);
+               if (l > 0) nrm[0] /= l, nrm[1] /= l, nrm[2] /= l; else nrm[0] = 0, nrm[1] = 0, nrm[2] = 1;
+            }
+            // a unit vector with cos to the normal uniform in [0.3, 1]
+            double tx[3] = {std::fabs(nrm[0]) < 0.9 ? 1.0 : 0.0, std::fabs(nrm[0]) < 0.9 ? 0.0 : 1.0, 0.0}, bx[3];
+            const double tn = tx[0] * nrm[0] + tx[1] * nrm[1] + tx[2] * nrm[2];
+            for (int a = 0; a < 3; a++) tx[a] -= tn * nrm[a];
+            const double tl = std::sqrt(tx[0] * tx[0] + tx[1] * tx[1] + tx[2] * tx[2]);
+            for (int a = 0; a < 3; a++) tx[a] /= tl;
+            bx[0] = nrm[1] * tx[2] - nrm[2] * tx[1], bx[1] = nrm[2] * tx[0] - nrm[0] * tx[2], bx[2] = nrm[0] * tx[1] - nrm[1] * tx[0];
+            const double cz = 0.3 + 0.7 * rnd64(), sz = std::sqrt(1.0 - cz * cz), phi = 6.283185307179586 * rnd64();
+            float of[3], df[3];
+            double len = 0;
+            for (int a = 0; a < 3; a++) {
+               of[a] = (float)(tg[a] + D * (cz * nrm[a] + sz * (std::cos(phi) * tx[a] + std::sin(phi) * bx[a])));
+               len += (tg[a] - (double)of[a]) * (tg[a] - (double)of[a]);
+            }
+            for (int a = 0; a < 3; a++) df[a] = (float)((tg[a] - (double)of[a]) / (unit ? std::sqrt(len) : 1.0));
+            const F3 o = {of[0], of[1], of[2]}, d = {df[0], df[1], df[2]};
+            const float tmin = 0.001f, tmax = 10000.0f;
+            const uint32_t first = near >= n ? 0 : p, last = near >= n ? n : std::min(n, p + near);
+            for (uint32_t j = first; j < last; j++) {
+               float t;
+               if (!tri_accepts(&corners[9 * (size_t)out.tri_order[j]], o, d, tmin, tmax, &t)) continue;
+               accepted++;
+               for (int ulp = -1; ulp <= 1; ulp++) {
+                  F3 idir = {safe_rcp_dir(d.x), safe_rcp_dir(d.y), safe_rcp_dir(d.z)};
+                  if (ulp) {
+                     const float to = ulp > 0 ? INFINITY : -INFINITY;
+                     idir = {std::nextafterf(idir.x, to), std::nextafterf(idir.y, to), std::nextafterf(idir.z, to)};
+                  }
+                  bool lost = false;
+                  for (uint32_t node = leaf_node[j], slot = leaf_slot[j]; node != kEmptyRef && !lost; slot = up_slot[node], node = up_node[node])
+                     lost = !slot_passes(out.cnodes[node], (int)slot, o, idir, tmin, t);
+                  if (lost) {
+                     culled++;
+                     if (!g_count_only && errors++ < 5)
+                        std::printf("FAIL[%s]: the node test culls a triangle the triangle test accepts (packet %u, distance %g, idir %+d ulp, t %g)\n", name, j, D, ulp, (double)t);
+                  }
+               }
+            }
+         }
+   g_accepted += accepted, g_culled += culled;
+   std::printf("%s: far rays: %llu accepted (ray, triangle) pairs, %llu culled on the way to the leaf (3 reciprocals each)\n", name, accepted, culled);
+   if (accepted < (unsigned long long)rays) {
+      std::printf("FAIL[%s]: the far rays hit too little for the check to mean anything\n", name);
+      errors++;
+   }
+   return g_count_only ? 0 : errors;
+}
+
+static int check(const std::vector<float>& corners, int threads, const char* name, bool geometry = true, int far_rays = 0, uint32_t near = 16) {
    const uint32_t n = (uint32_t)(corners.size() / 9);
    std::vector<uint32_t> keys(n);
    for (uint32_t i = 0; i < n; i++) keys[i] = i;
@@ -117,11 +284,13 @@ static int check(const std::vector<float>& corners, int threads, const char* nam
       if (packet_use[p] != 1) fail("packet not referenced by exactly one leaf", p, packet_use[p]);
    for (size_t i = 1; i < node_refs.size(); i++)
       if (node_refs[i] != 1) fail("interior node not referenced exactly once", (uint32_t)i, node_refs[i]);
+   if (far_rays && !errors) errors += far_ray_check(corners, out, name, far_rays, near);
    std::printf("%s: %u tris -> %zu nodes, depth %u, %s\n", name, n, out.nodes.size(), out.max_depth, errors ? "FAILED" : "ok");
    return errors;
 }
 
-int main() {
+int main(int argc, char** argv) {
+   g_count_only = argc > 1 && !std::strcmp(argv[1], "count");
    int errors = 0;
    for (uint32_t seed : {1u, 4u}) {
       for (int threads : {1, 4}) {
@@ -132,14 +301,26 @@ int main() {
             for (int v = 0; v < 3; v++)
                for (int a = 0; a < 3; a++) soup.push_back(c[a] + (rnd() - 0.5f) * 0.4f);
          }
-         errors += check(soup, threads, "random soup");
+         errors += check(soup, threads, "random soup", true, 6000);
       }
    }
    {
       std::vector<float> empty;
       errors += check(empty, 1, "empty");
       std::vector<float> one = {0, 0, 0, 1, 0, 0, 0, 1, 0};
-      errors += check(one, 1, "single triangle");
+      errors += check(one, 1, "single triangle", true, 40000);
+      {
+         // 32 x 32 quads on the unit square in the plane z = 0: small triangles in a coordinate plane, where the builders' box
+         // padding is an absolute 1e-4
+         std::vector<float> grid;
+         for (int i = 0; i < 32; i++)
+            for (int j = 0; j < 32; j++) {
+               const float x0 = (float)i / 32, x1 = (float)(i + 1) / 32, y0 = (float)j / 32, y1 = (float)(j + 1) / 32;
+               const float t[18] = {x0, y0, 0, x1, y0, 0, x1, y1, 0, x0, y0, 0, x1, y1, 0, x0, y1, 0};
+               grid.insert(grid.end(), t, t + 18);
+            }
+         errors += check(grid, 2, "32 x 32 grid in z = 0", true, 2000, 0xffffffffu);
+      }
       std::vector<float> dup;
       for (int i = 0; i < 1000; i++) dup.insert(dup.end(), one.begin(), one.end());
       errors += check(dup, 4, "1000 identical triangles");
@@ -161,7 +342,7 @@ int main() {
          float t[9] = {x, 0, z, x + 0.1f, 0, z, x, 0, z + 0.1f};
          planar.insert(planar.end(), t, t + 9);
       }
-      errors += check(planar, 4, "coplanar sheet");
+      errors += check(planar, 4, "coplanar sheet", true, 12000);
       // non-finite vertices must not break the structure (every packet in exactly one leaf, no crash): such
       // triangles are never hit (NaN fails every comparison in the slab and triangle tests)
       std::vector<float> poisoned = planar;
@@ -261,6 +442,7 @@ int main() {
          errors += bad;
       }
    }
+   std::printf("far rays in all: %llu accepted (ray, triangle) pairs, %llu culled by the node test, margin %g\n", g_accepted, g_culled, (double)kSlabMargin);
    std::printf(errors ? "BVH CHECK FAILED (%d)\n" : "BVH CHECK OK\n", errors);
    return errors ? 1 : 0;
 }

@@ -14,8 +14,8 @@ def test_bvh_builder_invariants_under_asan_ubsan(tmp_path):
     exe = str(tmp_path / "bvh_check")
     csrc = os.path.join(ROOT, "rust-renderer_amd", "csrc")
     subprocess.run(
-        ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-Wall", "-Wextra",
-         "-I", csrc, os.path.join(ROOT, "tests", "cpp", "bvh_check.cpp"), os.path.join(csrc, "bvh_build.cpp"), "-o", exe, "-pthread"],
+        ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-ffp-contract=off", "-mfma", "-Wall",
+         "-Wextra", "-I", csrc, os.path.join(ROOT, "tests", "cpp", "bvh_check.cpp"), os.path.join(csrc, "bvh_build.cpp"), "-o", exe, "-pthread"],
         check=True,
     )
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))

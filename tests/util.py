@@ -269,3 +269,83 @@ def extract_isosurface(density, lo, hi, resolution, slab=16):
                 tris.append(np.stack([a, b, c2], 1))
                 tris.append(np.stack([a, c2, d2], 1))
     return np.concatenate(tris) if tris else np.zeros((0, 3, 3))
+
+
+# ---- rays that start far from small geometry lying in a coordinate plane: test_oracle_far_rays.py, test_gpu_far_rays.py.
+# The slab tests' rounding error grows with the distance to the ray origin, the builders' absolute box padding does not
+# (DESIGN.md "Arithmetic contract").
+FAR_SCENES = ("triangle", "quad", "grid", "grid_at_1000")
+FAR_DISTANCES = (1e2, 3e3, 1e4, 1e5, 1e6)
+FAR_WALL_START = (0.3, -0.2, -0.5)  # where the wall stands before set_instance_transform puts it in place (the refitted tree)
+
+
+def far_scene(kind, wall_moved=False):
+    """mesh 0, in the plane z = 0: "triangle" = one right triangle with its legs on the axes, "quad" = the unit square as two
+    triangles, "grid" = 32 x 32 quads on the unit square (2,048 triangles), "grid_at_1000" = that grid moved to (1000, 1000, 0),
+    where the relative term of the box padding acts. Mesh 1: a wall one unit behind, so that a hole in mesh 0 shows as a different
+    hit, not as a miss; with wall_moved it starts displaced by FAR_WALL_START (the caller moves it back and refits)."""
+    from rust_renderer_amd.camera import Camera
+
+    def mesh(pos, idx, transform=None):
+        pos = np.asarray(pos, dtype=np.float32)
+        m = Mesh(rr.scenes._pack_vertices(pos, np.tile(np.float32([0, 0, 1]), (len(pos), 1)), pos[:, :2].copy()), np.asarray(idx, dtype=np.uint32).reshape(-1))
+        if transform is not None:
+            m.transform = np.asarray(transform, dtype=np.float32).reshape(12)
+        return m
+
+    shift = np.float64([1000.0, 1000.0, 0.0]) if kind == "grid_at_1000" else np.zeros(3)
+    if kind == "triangle":
+        front = mesh([[0, 0, 0], [1, 0, 0], [0, 1, 0]], [0, 1, 2])
+    else:
+        n = 1 if kind == "quad" else 32
+        g = np.arange(n + 1, dtype=np.float64) / n
+        X, Y = np.meshgrid(g, g, indexing="ij")
+        pos = np.stack([X, Y, np.zeros_like(X)], -1).reshape(-1, 3) + shift
+        i = (np.arange(n)[:, None] * (n + 1) + np.arange(n)[None, :]).reshape(-1)
+        front = mesh(pos, np.stack([i, i + n + 1, i + n + 2, i, i + n + 2, i + 1], -1))
+    wall = mesh(np.float64([[-1, -1, -1], [2, -1, -1], [2, 2, -1], [-1, 2, -1]]) + shift, [0, 1, 2, 0, 2, 3],
+                rr.transform3x4((1.0, 1.0, 1.0), FAR_WALL_START) if wall_moved else None)
+    centre = (0.5 + shift[0], 0.5 + shift[1], 0.0)
+    return Scene("far_" + kind, [(Model([front, wall], []), None)], [], Camera((centre[0], centre[1], 5000.0), centre, 60.0, 1.0, 0.01, 1000.0))
+
+
+def far_rays(kind, distance, n, seed, normalised=False):
+    """n rays towards mesh 0 of far_scene(kind) from `distance` away: origin = target + distance * dir with dir uniform on the part
+    of the upper hemisphere with dir.z >= 0.3; direction = target - origin, unnormalised (t is about 1, so tmax = 10000 never cuts
+    a ray) or, with `normalised`, of unit length (t is about `distance`). Targets: a third uniform on the surface, a third within
+    2e-7 * distance of an axis-aligned edge on its inside (interior grid lines: either side), a third exactly at vertices."""
+    rng = np.random.default_rng(seed)
+    cells = {"triangle": 1, "quad": 1}.get(kind, 32)
+    shift = np.float64([1000.0, 1000.0, 0.0]) if kind == "grid_at_1000" else np.zeros(3)
+    tgt = np.zeros((n, 3))
+    tgt[:, :2] = rng.uniform(0.0, 1.0, (n, 2))
+    edge, vertex = np.arange(n) % 3 == 1, np.arange(n) % 3 == 2
+    # edges: a line x = i / cells or y = j / cells, a point along it, a step off it that stays on the surface
+    m = int(edge.sum())
+    line = rng.integers(0, cells + 1, m) / cells
+    off = rng.uniform(0.0, 1.0, m) * min(2e-7 * distance, 0.5)
+    side = np.where(line == 0.0, 1.0, np.where(line == 1.0, -1.0, rng.choice([-1.0, 1.0], m)))
+    across = np.clip(line + side * off, 0.0, 1.0)
+    along = rng.uniform(0.0, 1.0, m)
+    axis = rng.integers(0, 2, m)
+    tgt[edge, 0] = np.where(axis == 0, across, along)
+    tgt[edge, 1] = np.where(axis == 0, along, across)
+    tgt[vertex, :2] = rng.integers(0, cells + 1, (int(vertex.sum()), 2)) / cells
+    if kind == "triangle":
+        # fold the unit square onto the triangle x + y <= 1; its axis-aligned edges are the legs only
+        tgt[edge, 0] = np.where(axis == 0, off, along * (1.0 - off))
+        tgt[edge, 1] = np.where(axis == 0, along * (1.0 - off), off)
+        over = tgt[:, 0] + tgt[:, 1] > 1.0
+        tgt[over & ~vertex, :2] = 1.0 - tgt[over & ~vertex, :2]
+        tgt[over & vertex, :2] = 0.0
+    tgt = (tgt + shift).astype(np.float32).astype(np.float64)
+    z = rng.uniform(0.3, 1.0, n)
+    phi = rng.uniform(0.0, 2.0 * np.pi, n)
+    s = np.sqrt(1.0 - z * z)
+    o = (tgt + distance * np.stack([s * np.cos(phi), s * np.sin(phi), z], -1)).astype(np.float32)
+    d = tgt - o.astype(np.float64)
+    if normalised:
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+    rays = np.empty((n, 8), dtype=np.float32)
+    rays[:, 0:3], rays[:, 3], rays[:, 4:7], rays[:, 7] = o, 0.001, d, 10000.0
+    return rays
