@@ -373,6 +373,19 @@ int uh_set_option(uh_ctx* ctx, const char* name, int value);
  * compared, out[7] the host builder's time in microseconds. UH_ERR_INVALID_ARGUMENT when no grid is in use. */
 int uh_sun_grid_compare_builders(uh_ctx* ctx, uint64_t out[8]);
 
+/* diagnostics: the tree in use - whichever builder or refit wrote it - read back (nodes, packets, world corners, shade packets) and
+ * held on the host, in double, to the invariants the traversal relies on (csrc/bvh_invariants.h; the host builder's trees are their
+ * reference, tests/cpp/bvh_check.cpp). Waits for the frames in flight. out[0] nodes, out[1] triangles, out[2] levels, then one
+ * violation count per class: out[3] levels (level_start well formed, at most as many as the traversal stack holds, every child in a
+ * later level than its parent), out[4] counts (n_tri <= n_child <= 4, child_base's copy of n_tri, step exponents), out[5] refs (every
+ * node but the root and every packet referenced exactly once), out[6] keys (the packets' keys are the scene's, each once; the shade
+ * packet's mesh), out[7] packets (the packet is the bake of its world corners bit for bit), out[8] empty slots (inverted boxes),
+ * out[9] containment (a slot's planes contain the padded box of its subtree; not checked when out[11] = 0: non-finite corners);
+ * out[10] the bits of a double: the sum of the slots' box areas over the root's (reported, not judged). Violations are the result,
+ * not an error: UH_OK, and uh_last_error names the first offender of each class (empty when there is none).
+ * UH_ERR_INVALID_ARGUMENT when no tree has been built for the scene as it is. There is no raw read-back of the tree. */
+int uh_check_acceleration(uh_ctx* ctx, uint64_t out[16]);
+
 /* ---- multi-GPU framebuffer tile partition (one process per GPU) ------------------------ */
 /* After this call uh_render_frame path-traces only pixels of tiles t with t % world == rank
  * (tile_size x tile_size tiles, row-major tile ids). ReSTIR passes stay full-frame unless uh_set_restir_partition says otherwise. */

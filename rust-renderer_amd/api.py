@@ -693,6 +693,21 @@ class Renderer:
         keys = ("cells", "entries_device", "entries_host", "cells_length_differs", "cells_list_differs", "cells_cover_differs", "walkable_cells", "host_build_us")
         return dict(zip(keys, (int(x) for x in out)))
 
+    def check_acceleration(self):
+        """uh_check_acceleration: the tree in use read back and held to the builders' invariants (csrc/bvh_invariants.h). One
+        violation count per class under "violations" (all zero for a sound tree), the first offenders as text under "first"."""
+        out = (C.c_uint64 * 16)()
+        self._lib.uh_check_acceleration.argtypes, self._lib.uh_check_acceleration.restype = [C.c_void_p, C.POINTER(C.c_uint64)], C.c_int
+        self._check(self._lib.uh_check_acceleration(self._ctx, out))
+        classes = ("levels", "counts", "refs", "keys", "packets", "empty_slots", "containment")
+        return {
+            "nodes": int(out[0]), "triangles": int(out[1]), "levels": int(out[2]),
+            "violations": {k: int(out[3 + i]) for i, k in enumerate(classes)},
+            "sah": float(np.array([out[10]], dtype=np.uint64).view(np.float64)[0]),
+            "geometry_checked": bool(out[11]),
+            "first": (self._lib.uh_last_error(self._ctx) or b"").decode(),
+        }
+
     def rccl_comm_count(self):
         """ranks of the attached RCCL communicator as ncclCommCount reports them (0: none attached)"""
         n = C.c_uint32(0)

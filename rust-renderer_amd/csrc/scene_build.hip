@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "bvh.h"
+#include "bvh_invariants.h"
 #include "context_internal.h"
 #include "context_state.h"
 #include "device_scan.h"
@@ -590,6 +591,69 @@ static int build_on_device(uh_ctx* c) {
    HIP_TRY(c, hipStreamSynchronize(c->stream));
    c->packet_keys.assign(total, 0u);  // only its size is used once d_obj_corners exists (uh_refit_acceleration)
    publish_tree(c, num_nodes, total, t0);
+   return UH_OK;
+}
+
+// diagnostics: the tree in use, read back and held to bvh_invariants.h - see utopian_hip.h
+int uh_check_acceleration(uh_ctx* c, uint64_t out[16]) {
+   if (!c || !out) return UH_ERR_INVALID_ARGUMENT;
+   for (int k = 0; k < 16; k++) out[k] = 0;
+   HIP_TRY(c, hipSetDevice(c->device));
+   if (int st = sync_all(c)) return st;
+   if (!c->built || !c->topology_valid || !c->d_nodes.p || c->level_start.size() < 2)
+      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_check_acceleration: no tree has been built for the scene as it is (uh_build_acceleration or uh_refit_acceleration first)");
+   const uint32_t nn = c->scene.num_nodes, nt = c->scene.num_tris;
+   std::vector<Node4C> nodes(nn);
+   std::vector<TriPacket> packets(nt);
+   std::vector<ShadePacket> shade(nt);
+   std::vector<float> corners(9 * (size_t)nt);
+   HIP_TRY(c, hipMemcpy2D(nodes.data(), sizeof(Node4C), c->d_nodes.p, 16 * kNodeStride16, sizeof(Node4C), nn, hipMemcpyDeviceToHost));
+   if (nt) {
+      HIP_TRY(c, hipMemcpy2D(packets.data(), sizeof(TriPacket), c->d_tris.p, 16 * kTriStride16, sizeof(TriPacket), nt, hipMemcpyDeviceToHost));
+      HIP_TRY(c, hipMemcpy(shade.data(), c->d_shade.p, (size_t)nt * sizeof(ShadePacket), hipMemcpyDeviceToHost));
+   }
+   if (nt && c->d_obj_corners.p) {
+      // a device build or a refit has baked them (k_refit_triangles): the corners the boxes on the device were made from
+      HIP_TRY(c, hipMemcpy(corners.data(), c->d_world_corners.p, corners.size() * sizeof(float), hipMemcpyDeviceToHost));
+   } else {
+      // the host builder's tree, never refitted: no corners on the device. Its bake (uh_build_acceleration) again, by the packets' keys
+      for (uint32_t i = 0; i < nt; i++) {
+         const uint32_t mi = packets[i].key >> kPrimBits, p = packets[i].key & kPrimMask;
+         float* o = &corners[9 * (size_t)i];
+         if (mi >= c->meshes.size() || c->meshes[mi].vertices.empty() || p >= c->meshes[mi].indices.size() / 3) {
+            for (int k = 0; k < 9; k++) o[k] = 0.0f;  // (a key the scene does not have: the report's `keys`)
+            continue;
+         }
+         const HostMesh& m = c->meshes[mi];
+         write_obj_corners(tri_verts(m, p), o);
+         if (is_identity3x4(m.o2w)) continue;
+         const float* w = m.o2w;
+         for (int k = 0; k < 3; k++, o += 3) {
+            const float x = o[0], y = o[1], z = o[2];
+            o[0] = ((w[0] * x + w[1] * y) + w[2] * z) + w[3];
+            o[1] = ((w[4] * x + w[5] * y) + w[6] * z) + w[7];
+            o[2] = ((w[8] * x + w[9] * y) + w[10] * z) + w[11];
+         }
+      }
+   }
+   std::vector<uint32_t> keys;  // mesh order, primitive order: ascending
+   for (uint32_t mi = 0; mi < c->meshes.size(); mi++)
+      for (uint32_t p = 0, np = (uint32_t)c->meshes[mi].tris(); p < np; p++) keys.push_back((mi << kPrimBits) | p);
+   TreeView v;
+   v.nodes = nodes.data(), v.num_nodes = nn;
+   v.packets = packets.data(), v.num_tris = nt;
+   v.corners = corners.data();
+   v.shade_mesh = nt ? &shade[0].mesh : nullptr;
+   v.level_start = c->level_start.data(), v.level_entries = (uint32_t)c->level_start.size();
+   v.keys = keys.data(), v.num_keys = (uint32_t)keys.size();
+   const TreeReport rep = check_tree(v);
+   out[0] = nn;
+   out[1] = nt;
+   out[2] = rep.levels;
+   for (int k = 0; k < kTreeClasses; k++) out[3 + k] = rep.violations[k];
+   std::memcpy(&out[10], &rep.sah, sizeof(double));
+   out[11] = rep.geometry ? 1 : 0;
+   c->err = rep.total() ? "uh_check_acceleration: " + rep.text() : std::string();  // violations are the result, not an error
    return UH_OK;
 }
 

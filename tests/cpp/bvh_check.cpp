@@ -6,6 +6,10 @@
 //   then empty slots; the device node's implicit addressing (tri_base + slot, child_base + slot - n_tri) reproduces
 //   the explicit refs; every full-precision child box contains its subtree's triangles; every quantised box contains
 //   the full-precision box; empty slots are inverted boxes; level_start describes the breadth-first levels.
+// Every tree is also held to check_tree (csrc/bvh_invariants.h: the statement of the same invariants on the device's arrays alone,
+// which uh_check_acceleration runs on trees written by the GPU), with packets and corners baked from tri_order as the context bakes
+// them: the host builder is its reference and must pass with no violation. A mutation section then breaks a tree in ten ways, one
+// per kind of fault check_tree exists to find, and expects each to be reported in its class ("MUTATIONS k/k caught").
 // The node test's arithmetic (csrc/node_slab.h, the very text node_compute of kernels.hip compiles) against the triangle test's
 // (tri_compute of kernels.hip, restated here with fmaf in the same order), for rays that start up to 1e6 away from the geometry:
 //   for every (ray, triangle) pair the triangle test accepts, every slot on the way from the root to the triangle's leaf passes
@@ -18,9 +22,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <vector>
 
 #include "bvh.h"
+#include "bvh_invariants.h"
 #include "node_slab.h"
 
 using namespace uh;
@@ -36,6 +42,7 @@ static float rnd() {
 static double rnd64() { return ((double)(uint32_t)(rnd() * 4294967296.0f) + 0.5) / 4294967296.0; }  // (0, 1)
 
 static bool g_count_only = false;
+static int g_mutations_caught = 0, g_mutations_tried = 0;
 static unsigned long long g_culled = 0, g_accepted = 0;
 
 struct F3 {
@@ -190,7 +197,152 @@ static int far_ray_check(const std::vector<float>& corners, const BuildOutput& o
    return g_count_only ? 0 : errors;
 }
 
-static int check(const std::vector<float>& corners, int threads, const char* name, bool geometry = true, int far_rays = 0, uint32_t near = 16) {
+// a host-built tree as the context uploads it (scene_build.hip uh_build_acceleration): packets and world corners in leaf order
+struct DeviceForm {
+   std::vector<Node4C> nodes;
+   std::vector<TriPacket> packets;
+   std::vector<float> corners;
+   std::vector<uint32_t> mesh, level_start, keys;  // keys: the scene's, ascending
+   DeviceForm(const std::vector<float>& soup, const std::vector<uint32_t>& soup_keys, const BuildOutput& out) : nodes(out.cnodes), level_start(out.level_start), keys(soup_keys) {
+      const size_t n = out.tri_order.size();
+      packets.resize(n);
+      corners.resize(9 * n);
+      mesh.resize(n);
+      for (size_t i = 0; i < n; i++) {
+         const uint32_t src = out.tri_order[i];
+         if (src >= soup_keys.size()) continue;  // (reported by check())
+         const float* c = &soup[9 * (size_t)src];
+         std::memcpy(&corners[9 * i], c, 9 * sizeof(float));
+         TriPacket& q = packets[i];
+         q.v0[0] = c[0], q.v0[1] = c[1], q.v0[2] = c[2];
+         q.e1x = c[3] - c[0], q.e1yz[0] = c[4] - c[1], q.e1yz[1] = c[5] - c[2];
+         q.e2[0] = c[6] - c[0], q.e2[1] = c[7] - c[1], q.e2z = c[8] - c[2];
+         q.key = soup_keys[src];
+         q.pad[0] = q.pad[1] = 0;
+         mesh[i] = q.key >> kPrimBits;
+      }
+      std::sort(keys.begin(), keys.end());
+   }
+   TreeView view() const {
+      TreeView v;
+      v.nodes = nodes.data(), v.num_nodes = (uint32_t)nodes.size();
+      v.packets = packets.data(), v.num_tris = (uint32_t)packets.size();
+      v.corners = corners.data();
+      v.shade_mesh = mesh.data(), v.shade_stride = sizeof(uint32_t);
+      v.level_start = level_start.data(), v.level_entries = (uint32_t)level_start.size();
+      v.keys = keys.data(), v.num_keys = (uint32_t)keys.size();
+      return v;
+   }
+};
+
+// check_tree must find each of these in its class, and nothing in the tree they were made from
+static int mutation_check(const std::vector<float>& soup, const char* name, int* caught, int* tried) {
+   std::vector<uint32_t> keys(soup.size() / 9);
+   for (uint32_t i = 0; i < keys.size(); i++) keys[i] = i;
+   BuildInput in{soup.data(), keys.data(), (uint32_t)keys.size()};
+   BuildOutput out;
+   build_bvh4(in, out, 2);
+   const DeviceForm good(soup, keys, out);
+   int errors = 0;
+   if (check_tree(good.view()).total()) {
+      std::printf("FAIL[%s]: the tree the mutations start from has violations: %s\n", name, check_tree(good.view()).text().c_str());
+      return 1;
+   }
+   std::vector<uint32_t> level_of(good.nodes.size(), 0);
+   for (uint32_t l = 0; l + 1 < good.level_start.size(); l++)
+      for (uint32_t i = good.level_start[l]; i < good.level_start[l + 1]; i++) level_of[i] = l;
+   auto n_tri = [](const Node4C& q) { return (q.meta >> kMetaTriShift) & 7u; };
+   auto n_child = [](const Node4C& q) { return (q.meta >> kMetaChildShift) & 7u; };
+   // the last node (deep in the tree) that `want` accepts
+   auto find = [&](auto want) {
+      for (uint32_t i = (uint32_t)good.nodes.size(); i-- > 0;)
+         if (want(good.nodes[i])) return (int64_t)i;
+      return (int64_t)-1;
+   };
+   auto set_byte = [](uint32_t& w, uint32_t k, uint32_t b) { w = (w & ~(0xffu << (8 * k))) | (b << (8 * k)); };
+   struct Mutation {
+      const char* what;
+      int cls;
+      std::function<bool(DeviceForm&)> apply;  // false: the tree has no place for it
+   };
+   const int64_t with_tri = find([&](const Node4C& q) { return n_tri(q) >= 1; }), with_node = find([&](const Node4C& q) { return n_child(q) > n_tri(q); }),
+                 with_empty = find([&](const Node4C& q) { return n_child(q) < 4; });
+   const std::vector<Mutation> mutations = {
+      {"a plane of a triangle slot moved inwards past the padded box", kTcContainment, [&](DeviceForm& t) {
+          if (with_tri < 0) return false;
+          set_byte(t.nodes[with_tri].qlo[0], 0, t.nodes[with_tri].qhi[0] & 0xffu);  // the lower x plane onto the upper one
+          return true;
+       }},
+      {"a plane of a node slot moved inwards past the padded box", kTcContainment, [&](DeviceForm& t) {
+          if (with_node < 0) return false;
+          Node4C& q = t.nodes[with_node];
+          const uint32_t k = n_tri(q);
+          set_byte(q.qhi[1], k, (q.qlo[1] >> (8 * k)) & 0xffu);  // the upper y plane onto the lower one
+          return true;
+       }},
+      {"meta's n_child lowered by one", kTcRefs, [&](DeviceForm& t) {
+          if (with_node < 0) return false;
+          t.nodes[with_node].meta -= 1u << kMetaChildShift;  // its last node child is no longer referenced
+          return true;
+       }},
+      {"child_base's n_tri bits differ from meta's", kTcCounts, [&](DeviceForm& t) {
+          t.nodes[0].child_base ^= 1u << kChildBaseBits;
+          return true;
+       }},
+      {"tri_base shifted by one", kTcRefs, [&](DeviceForm& t) {
+          if (with_tri < 0) return false;
+          t.nodes[with_tri].tri_base += 1;
+          return true;
+       }},
+      {"a child_base points into its own level", kTcLevels, [&](DeviceForm& t) {
+          if (with_node < 0) return false;
+          Node4C& q = t.nodes[with_node];
+          q.child_base = (q.child_base & ~kChildBaseMask) | t.level_start[level_of[with_node]];
+          return true;
+       }},
+      {"an empty slot given a real box", kTcEmpty, [&](DeviceForm& t) {
+          if (with_empty < 0) return false;
+          Node4C& q = t.nodes[with_empty];
+          set_byte(q.qlo[2], n_child(q), 0u);
+          set_byte(q.qhi[2], n_child(q), 255u);
+          return true;
+       }},
+      {"an exponent byte set to 0", kTcCounts, [&](DeviceForm& t) {
+          t.nodes[t.nodes.size() / 2].meta &= ~0xff00u;
+          return true;
+       }},
+      {"a packet's e1 changed by an ulp", kTcPackets, [&](DeviceForm& t) {
+          float& e = t.packets[t.packets.size() / 3].e1x;
+          e = std::nextafterf(e, INFINITY);
+          return true;
+       }},
+      {"one key duplicated over another", kTcKeys, [&](DeviceForm& t) {
+          if (t.packets.size() < 2) return false;
+          t.packets[1].key = t.packets[0].key;
+          return true;
+       }},
+   };
+   for (const Mutation& m : mutations) {
+      DeviceForm t = good;
+      ++*tried;
+      const bool applied = m.apply(t);
+      const TreeReport rep = applied ? check_tree(t.view()) : TreeReport();
+      if (applied && rep.violations[m.cls]) {
+         ++*caught;
+      } else {
+         std::printf("FAIL[%s]: %s: %s\n", name, m.what, applied ? ("not reported as " + std::string(tree_class_name(m.cls)) + "; check_tree says: " + rep.text()).c_str() : "the tree has no place for it");
+         errors++;
+      }
+   }
+   // (every mutation worked on a copy: the tree they share is as it was)
+   if (check_tree(good.view()).total()) {
+      std::printf("FAIL[%s]: the restored tree has violations\n", name);
+      errors++;
+   }
+   return errors;
+}
+
+static int check(const std::vector<float>& corners, int threads, const char* name, bool geometry = true, int far_rays = 0, uint32_t near = 16, bool too_deep = false) {
    const uint32_t n = (uint32_t)(corners.size() / 9);
    std::vector<uint32_t> keys(n);
    for (uint32_t i = 0; i < n; i++) keys[i] = i;
@@ -198,6 +350,17 @@ static int check(const std::vector<float>& corners, int threads, const char* nam
    BuildOutput out;
    build_bvh4(in, out, threads);
    int errors = 0;
+   {
+      // the same tree through the statement that device-built trees are held to: no violation, and it skips the geometry exactly
+      // where this check is told to. too_deep: the one tree here that the context would not install - its depth is the one finding
+      const DeviceForm dev(corners, keys, out);
+      const TreeReport rep = check_tree(dev.view());
+      std::printf("%s: check_tree: %u levels, SAH figure %.3f, %s%s\n", name, rep.levels, rep.sah, rep.text().c_str(), rep.geometry ? "" : " (non-finite corners: containment skipped)");
+      if (rep.total() != (too_deep ? 1u : 0u) || rep.violations[kTcLevels] != (too_deep ? 1u : 0u) || rep.geometry != geometry) {
+         std::printf("FAIL[%s]: check_tree on the host builder's tree\n", name);
+         errors++;
+      }
+   }
    auto fail = [&](const char* what, uint32_t a, uint32_t b) {
       if (errors++ < 5) std::printf("FAIL[%s]: %s (%u, %u)\n", name, what, a, b);
    };
@@ -320,6 +483,17 @@ int main(int argc, char** argv) {
                grid.insert(grid.end(), t, t + 18);
             }
          errors += check(grid, 2, "32 x 32 grid in z = 0", true, 2000, 0xffffffffu);
+         errors += mutation_check(grid, "32 x 32 grid in z = 0", &g_mutations_caught, &g_mutations_tried);
+      }
+      {
+         std::vector<float> soup;
+         g_state = 20250;
+         for (int i = 0; i < 5000; i++) {
+            float c[3] = {rnd() * 40 - 20, rnd() * 15, rnd() * 16 - 8};
+            for (int v = 0; v < 3; v++)
+               for (int a = 0; a < 3; a++) soup.push_back(c[a] + (rnd() - 0.5f) * 0.4f);
+         }
+         errors += mutation_check(soup, "5000-triangle soup", &g_mutations_caught, &g_mutations_tried);
       }
       std::vector<float> dup;
       for (int i = 0; i < 1000; i++) dup.insert(dup.end(), one.begin(), one.end());
@@ -363,7 +537,7 @@ int main(int argc, char** argv) {
                for (int a = 0; a < 3; a++) chain.push_back(c[a] + s * 0.01f * rnd());
          }
       }
-      errors += check(chain, 2, "geometric-series clusters (SAH)");
+      errors += check(chain, 2, "geometric-series clusters (SAH)", true, 0, 16, true);
       std::vector<uint32_t> keys(chain.size() / 9);
       BuildInput in{chain.data(), keys.data(), (uint32_t)keys.size()};
       BuildOutput sah, bal;
@@ -373,6 +547,12 @@ int main(int argc, char** argv) {
       if (bal.level_start.size() - 1 > kMaxTreeLevels) {
          std::printf("FAIL: balanced tree deeper than the traversal stack\n");
          errors++;
+      }
+      {
+         for (uint32_t i = 0; i < keys.size(); i++) keys[i] = i;
+         const TreeReport rep = check_tree(DeviceForm(chain, keys, bal).view());
+         std::printf("geometric-series clusters (balanced): check_tree: %u levels, SAH figure %.3f, %s\n", rep.levels, rep.sah, rep.text().c_str());
+         errors += rep.total() ? 1 : 0;
       }
       if (sah.level_start.size() - 1 <= 12) {
          std::printf("FAIL: the chain scene no longer produces a deep SAH tree (test lost its point)\n");
@@ -443,6 +623,7 @@ int main(int argc, char** argv) {
       }
    }
    std::printf("far rays in all: %llu accepted (ray, triangle) pairs, %llu culled by the node test, margin %g\n", g_accepted, g_culled, (double)kSlabMargin);
+   std::printf("MUTATIONS %d/%d caught\n", g_mutations_caught, g_mutations_tried);
    std::printf(errors ? "BVH CHECK FAILED (%d)\n" : "BVH CHECK OK\n", errors);
    return errors ? 1 : 0;
 }

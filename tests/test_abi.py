@@ -25,7 +25,8 @@ def test_header_declares_the_boundary():
     names = declared_functions()
     for must in ("uh_create", "uh_destroy", "uh_add_texture_rgba8", "uh_add_mesh", "uh_add_light", "uh_set_instance_transform",
                  "uh_build_acceleration", "uh_render_frame", "uh_reset_accumulation", "uh_read_accumulation", "uh_read_output_bgra8",
-                 "uh_read_reservoirs", "uh_get_stats", "uh_last_error", "uh_set_tile_partition", "uh_pack_tiles", "uh_unpack_tiles"):
+                 "uh_read_reservoirs", "uh_get_stats", "uh_last_error", "uh_set_tile_partition", "uh_pack_tiles", "uh_unpack_tiles",
+                 "uh_refit_acceleration", "uh_check_acceleration"):
         assert must in names
 
 

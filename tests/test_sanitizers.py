@@ -21,6 +21,10 @@ def test_bvh_builder_invariants_under_asan_ubsan(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert "BVH CHECK OK" in r.stdout
+    # check_tree (csrc/bvh_invariants.h, what uh_check_acceleration holds device-built trees to) finds nothing in the host builder's
+    # trees and every one of the ten faults planted in two of them
+    assert "MUTATIONS 20/20 caught" in r.stdout, r.stdout[-3000:]
+    assert r.stdout.count("check_tree: ") >= 12
 
 
 def test_sun_grid_builder_under_asan_ubsan_never_hides_an_occluder(tmp_path):
