@@ -241,7 +241,8 @@ typedef struct uh_ctx uh_ctx;
  *        uh_write_reservoirs, uh_write_gbuffer_position, uh_build_acceleration, uh_refit_acceleration (also when uh_render_frame calls it for
  *        view->rebuild_tlas), uh_set_tile_partition, uh_set_restir_partition, uh_rccl_attach / uh_rccl_detach, uh_pack_tiles,
  *        uh_unpack_tiles, uh_compose_tiles, uh_resolve_output, uh_add_isosurface_mesh, uh_update_isosurface_mesh (it reads the
- *        triangle total, 8 bytes, back to size its buffers), uh_get_isosurface_update_stats, uh_destroy;
+ *        triangle total, 8 bytes, back to size its buffers), uh_get_isosurface_update_stats, uh_update_mesh_vertices (device input:
+ *        it reads a 4-byte verdict on the caller's buffer back before it takes it), uh_get_mesh_update_stats, uh_destroy;
  *   enqueues like a frame, ordered behind the frames in flight and before those that follow:  uh_rccl_gather_tiles, uh_mgpu_compose;
  *        uh_set_option for "frames_in_flight" and for "time_kernels" 1 -> 0 (the others only change what the NEXT enqueued
  *        frame does: "furnace", "sun_grid*", "camera_grid*", "overlap", "batch_frames", "trace_blocks_per_cu", "count_visits",
@@ -249,7 +250,8 @@ typedef struct uh_ctx uh_ctx;
  *        needs uh_build_acceleration, which waits);
  *   host state only (no device access, nothing to wait for):  uh_add_mesh, uh_add_light, uh_set_instance_transform,
  *        uh_get_num_lights, uh_mesh_info, uh_read_mesh, uh_get_restir_rows, uh_tile_pack_count, uh_last_error
- *        (uh_read_mesh of a mesh that uh_update_isosurface_mesh has made device-resident copies it from the device: a blocking copy);
+ *        (uh_read_mesh of a mesh that uh_update_isosurface_mesh has made device-resident, or that uh_update_mesh_vertices last updated
+ *        from a device pointer, copies it from the device: a blocking copy);
  *   uh_add_texture_rgba8 uploads into a fresh allocation no frame in flight can reference (textures enter a frame's tables at the
  *        next uh_build_acceleration) and is complete on return;
  *   uh_trace_closest / uh_trace_any run on the context's first stream, in order with the frames of that stream, read the scene
@@ -518,6 +520,52 @@ UH_LAYOUT_ASSERT(sizeof(UhIsosurfaceUpdateStats) == 32 && offsetof(UhIsosurfaceU
                  "UhIsosurfaceUpdateStats (32 B)");
 /* all zero before the first update; waits for the frames in flight like the other stats calls */
 int uh_get_isosurface_update_stats(uh_ctx* ctx, UhIsosurfaceUpdateStats* out);
+
+/* ---- deforming meshes: new vertices for a mesh of uh_add_mesh, refitted on the device ----------------------------------
+ * Replaces ALL vertices of mesh `mesh_index` - positions, normals, uvs and the rest of the 80-byte record - with the `num_vertices`
+ * records at `vertices`; num_vertices must equal the mesh's count. The index list, material, transform and mesh index stay. `where`
+ * says what `vertices` is: UH_VERTICES_HOST a host pointer, UH_VERTICES_DEVICE a device pointer on the context's device, whose buffer
+ * the caller has finished writing; the library copies it into the mesh's own buffer and the caller may reuse it after return.
+ * State: that of uh_set_instance_transform, not that of uh_add_mesh - the context is not built, the topology is as valid as it was.
+ * uh_refit_acceleration is accepted, and uh_render_frame / uh_render_hybrid / uh_render_forward refit by themselves when
+ * view->rebuild_tlas == 1 (UH_ERR_NOT_BUILT without it); the per-frame protocol is update, rebuild_tlas = 1, render. The refit writes
+ * the moved meshes' triangle packets again in the tree's leaf order (k_deform_gather) and then recomputes every box; instances moved
+ * in the same interval are served by the same refit. uh_build_acceleration is the other way out, for a surface that has drifted far
+ * from where the tree was built (the refitted tree answers the same, at more node visits). If meshes were added since the last
+ * build only a build will do, as ever.
+ * Equivalence: after the update and either a refit or a build every observable of the context - uh_read_mesh, uh_trace_closest /
+ * uh_trace_any, frames path traced from cleared temporal state (see uh_update_isosurface_mesh) with both grids, the cast and the
+ * rasterised G-buffer, the shadow maps, the forward graph - equals, bit for bit, that of a fresh context whose same scene was made
+ * with uh_add_mesh from the new vertices and then built. Node-visit counters are not observables.
+ * Errors: UH_ERR_INVALID_ARGUMENT for a null context, a null pointer with num_vertices > 0, an index out of range, a count that
+ * differs from the mesh's, a `where` other than the two values, a mesh created by uh_add_isosurface_mesh (it has its own verb) or a
+ * non-finite position - host input is checked on the host as uh_add_mesh checks it, device input by a pass over the caller's buffer
+ * before anything of the mesh is overwritten; UH_ERR_OUT_OF_MEMORY when the mesh's device buffers cannot be made. All of these leave
+ * everything as it was (a built context stays built and renders as before). A mesh with zero vertices accepts num_vertices == 0,
+ * which changes nothing but the stats.
+ * Stream order: waits for the frames in flight and is complete on return.
+ * Memory: an updated mesh keeps its vertices in a device buffer of its own (80 bytes per vertex) behind its index list, which goes to
+ * the device once, with the first update. Host input also overwrites the host copy; after device input the host copy is stale, and
+ * the host builder ("device_build" 0) and uh_read_mesh fetch it with a blocking copy (the index list never: the host still has it).
+ * With "device_build" 1 or 2 a UH_VERTICES_DEVICE update followed by a refit or a build moves no geometry between host and device. */
+#define UH_VERTICES_HOST   0
+#define UH_VERTICES_DEVICE 1
+int uh_update_mesh_vertices(uh_ctx* ctx, uint32_t mesh_index, const UhVertex* vertices, uint32_t num_vertices, int where);
+typedef struct UhMeshUpdateStats {
+   float gather_ms;              /* hipEvent: k_deform_gather of the last refit that had moved vertices to gather */
+   float refit_ms;               /* hipEvent: the passes of that refit behind it (the bake and the boxes) */
+   uint32_t updates;             /* so far */
+   uint32_t triangles;           /* rewritten by that refit: the triangles of the meshes whose vertices had moved */
+   uint64_t host_geometry_bytes; /* cumulative: vertex, corner and packet bytes of updated meshes that this context moved between host
+                                    and device, either way, in any verb. The index list's one upload, 4 bytes per index with a mesh's
+                                    first update, is not in it: it is the same list the host keeps */
+   uint64_t device_bytes;        /* the vertex and index buffers held for updated meshes */
+} UhMeshUpdateStats;
+UH_LAYOUT_ASSERT(sizeof(UhMeshUpdateStats) == 32 && offsetof(UhMeshUpdateStats, updates) == 8 && offsetof(UhMeshUpdateStats, triangles) == 12 &&
+                    offsetof(UhMeshUpdateStats, host_geometry_bytes) == 16 && offsetof(UhMeshUpdateStats, device_bytes) == 24,
+                 "UhMeshUpdateStats (32 B)");
+/* all zero before the first update; waits for the frames in flight like the other stats calls */
+int uh_get_mesh_update_stats(uh_ctx* ctx, UhMeshUpdateStats* out);
 
 /* ---- several GPUs behind ONE application process (SURVEY.md section 8b "multi-GPU", 8e) ------------
  * The reference application is a single process with one render thread (prototype/src/main.rs:86-570);

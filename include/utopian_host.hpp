@@ -412,6 +412,17 @@ class Renderer {
       check(uh_get_isosurface_update_stats(ctx_, &s), "isosurface_update_stats");
       return s;
    }
+   // uh_update_mesh_vertices: new vertices for a mesh of add_mesh (its count of them; the index list stays), from the host or from
+   // device memory the caller has finished writing (where = UH_VERTICES_DEVICE). rebuild_tlas(), a frame with
+   // view.rebuild_tlas = 1 or initialize_raytracing() has to follow
+   void update_mesh_vertices(uint32_t mesh, const UhVertex* vertices, uint32_t num_vertices, int where = UH_VERTICES_HOST) {
+      check(uh_update_mesh_vertices(ctx_, mesh, vertices, num_vertices, where), "update_mesh_vertices");
+   }
+   UhMeshUpdateStats mesh_update_stats() {
+      UhMeshUpdateStats s;
+      check(uh_get_mesh_update_stats(ctx_, &s), "mesh_update_stats");
+      return s;
+   }
    // ---- one process per GPU (the reference is single-device: utopian/src/device.rs:45) ----
    // path tracing: tiles t % world == rank; reservoir passes: this rank's band of rows, exchanged over RCCL inside the library
    // (rank 0 makes the id, the launcher hands the 128 bytes to every rank); composition on the root: compose_tiles

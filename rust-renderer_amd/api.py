@@ -49,6 +49,7 @@ from .types import (
     HybridStats,
     GbufferRasterStats,
     IsosurfaceUpdateStats,
+    MeshUpdateStats,
     MarchingCubesStats,
     ShadowmapParams,
     ShadowMapStats,
@@ -349,6 +350,27 @@ class Renderer:
         fn = self._lib.uh_get_isosurface_update_stats
         fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(IsosurfaceUpdateStats)], C.c_int
         s = IsosurfaceUpdateStats()
+        self._check(fn(self._ctx, C.byref(s)))
+        return s
+
+    def update_mesh_vertices(self, mesh, vertices=None, *, device_ptr=None, count=None):
+        """uh_update_mesh_vertices: new vertices for a mesh of add_mesh, its index list kept. Host input: `vertices`, a VERTEX_DTYPE
+        array of the mesh's length. Device input: `device_ptr`, the address of `count` vertex records on the renderer's device, which
+        the caller has finished writing. refit_acceleration (or a frame with view.rebuild_tlas = 1) or build_acceleration follows."""
+        fn = self._lib.uh_update_mesh_vertices
+        fn.argtypes, fn.restype = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int], C.c_int
+        if device_ptr is not None:
+            assert vertices is None and count is not None, "device input: device_ptr= with count="
+            self._check(fn(self._ctx, int(mesh), C.c_void_p(int(device_ptr)), int(count), 1))
+            return
+        vertices = np.ascontiguousarray(vertices, dtype=VERTEX_DTYPE)
+        self._check(fn(self._ctx, int(mesh), C.c_void_p(vertices.ctypes.data if len(vertices) else None), len(vertices), 0))
+
+    def mesh_update_stats(self):
+        """UhMeshUpdateStats (all zero before the first update_mesh_vertices)"""
+        fn = self._lib.uh_get_mesh_update_stats
+        fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(MeshUpdateStats)], C.c_int
+        s = MeshUpdateStats()
         self._check(fn(self._ctx, C.byref(s)))
         return s
 

@@ -240,8 +240,14 @@ void uh_destroy(uh_ctx* c) {
    c->output.release();
    for (auto& r : c->reservoirs) r.release();
    c->dstats.release();
-   for (HostMesh& m : c->meshes)
+   for (HostMesh& m : c->meshes) {
       if (m.d_verts) (void)hipFree(m.d_verts);
+      if (m.d_indices) (void)hipFree(m.d_indices);
+   }
+   for (hipEvent_t ev : c->mupd.ev)
+      if (ev) (void)hipEventDestroy(ev);
+   c->mupd.table.release();
+   c->mupd.flag.release();
    for (hipEvent_t ev : {c->iso.begin, c->iso.end})
       if (ev) (void)hipEventDestroy(ev);
    c->iso.counts.release();

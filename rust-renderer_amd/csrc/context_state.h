@@ -34,6 +34,11 @@ struct HostMesh {
    uint64_t serial = 0;          // bumped by every update: what the build sources and the raster tables key this mesh's range on
    float olo[3] = {0, 0, 0}, ohi[3] = {0, 0, 0};  // object-space box of the device vertices (k_iso_scatter), for `box_serial`
    uint64_t box_serial = ~0ull;
+   // indexed and device-resident (after uh_update_mesh_vertices): d_verts holds vertices.size() records and d_indices the index list,
+   // uploaded by the first update. `indices` stays; `vertices` is stale while !host_valid (the last update took a device pointer)
+   bool upd = false;
+   uint32_t* d_indices = nullptr;
+   bool resident() const { return dev || upd; }
    size_t tris() const { return dev ? dev_tris : indices.size() / 3; }
    size_t num_vertices() const { return dev ? 3 * (size_t)dev_tris : vertices.size(); }
    size_t num_indices() const { return dev ? 3 * (size_t)dev_tris : indices.size(); }
@@ -315,6 +320,16 @@ struct uh_ctx {
       hipEvent_t begin = nullptr, end = nullptr;
       UhIsosurfaceUpdateStats st{};
    } iso;
+   // uh_update_mesh_vertices: HostMesh::serial of every mesh when the tree's packets (d_obj_corners, d_shade) were last written - by
+   // a build or by k_deform_gather -, that kernel's per-mesh table, the device pass's flag word, the events around the gather and
+   // around the refit behind it, and the figures of uh_get_mesh_update_stats; nothing but packet_serial exists before the first update
+   std::vector<uint64_t> packet_serial;
+   struct MeshUpdate {
+      DevBuf<DeformMesh> table;
+      DevBuf<uint32_t> flag;
+      hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // before the gather, between it and the refit, behind the refit
+      UhMeshUpdateStats st{};
+   } mupd;
    float refit_ms = 0.0f;
    DevBuf<TexInfo> d_tex;
    DevBuf<float> d_lut;

@@ -418,6 +418,24 @@ struct RefitArgs {
 };
 void launch_refit(const LaunchCfg&, const RefitArgs&);
 
+// uh_update_mesh_vertices (deform.hip): a mesh that keeps its vertices on the device behind its index list, as k_deform_gather reads
+// it - one row per mesh of the scene; a row with moved == 0 is never dereferenced
+struct DeformMesh {
+   const UhVertex* verts;
+   const uint32_t* indices;
+   uint32_t moved;
+   uint32_t pad;
+};
+// every triangle packet i (leaf order) of a moved mesh: obj_corners[9 i ..] and shade[4 i ..] again from the mesh's vertices
+void launch_deform_gather(hipStream_t, const DeformMesh* table, uint32_t num_meshes, const float4* tris, float* obj_corners, float4* shade, uint32_t num_tris);
+// the on-device build's sources of one such mesh (k_iso_scatter's outputs, through the index list), already offset to its range
+void launch_deform_scatter(hipStream_t, const UhVertex* verts, const uint32_t* indices, uint32_t num_tris, uint32_t mesh, float* corners, uint32_t* keys, float4* shade);
+// the box of ALL its vertices, as build_on_device's host loop takes it: box[0..2] minima, box[3..5] maxima as ordered integers
+// (initialise to 0xffffffff / 0, read with uhi_box_decode)
+void launch_deform_box(hipStream_t, const UhVertex* verts, uint32_t num_vertices, uint32_t* box);
+// *flag |= 1 when a position among `verts` (any alignment a UhVertex may have) is not finite
+void launch_deform_check(hipStream_t, const UhVertex* verts, uint32_t num_vertices, uint32_t* flag);
+
 // on-device LBVH build (lbvh.hip): topology + packets in Morton order; boxes come from launch_refit afterwards
 struct LbvhArgs {
    const float* src_corners;     // 9 floats per triangle, object space, mesh order

@@ -121,10 +121,11 @@ static int hybrid_tables(uh_ctx* c) {
    }
    if (nv >= (1ull << 32) || ni >= (1ull << 32)) return fail(c, UH_ERR_CAPACITY, "uh_render_hybrid: more than 2^32 vertices or indices");
    bool any_dev = false;
-   for (const HostMesh& m : c->meshes) any_dev = any_dev || m.dev;
+   for (const HostMesh& m : c->meshes) any_dev = any_dev || m.resident();
    if (any_dev) {
       // a second pair of arrays; per mesh: a range the old pair holds for the same serial is copied across on the device, a
-      // device-resident mesh is copied from its vertex buffer with an iota index list, a host-resident one is uploaded
+      // device-resident mesh is copied from its vertex buffer with an iota index list (uh_update_mesh_vertices: with its own index
+      // list, which is on the device too), a host-resident one is uploaded
       DevBuf<UhVertex> vb;
       DevBuf<uint32_t> ib;
       const auto give_up = [&](hipError_t e) {
@@ -137,7 +138,7 @@ static int hybrid_tables(uh_ctx* c) {
       for (size_t i = 0; in_place && i < c->meshes.size(); i++)
          in_place = h.layout[i].nv == c->meshes[i].num_vertices() && h.layout[i].ni == c->meshes[i].num_indices();
       if (in_place) {
-         // no count changed: the updated meshes' vertices over their old ones (their iota stays), the bases as they are
+         // no count changed: the updated meshes' vertices over their old ones (their index range stays), the bases as they are
          iso_scatter_begin(c);
          for (size_t i = 0; i < c->meshes.size(); i++) {
             const HostMesh& m = c->meshes[i];
@@ -168,6 +169,9 @@ static int hybrid_tables(uh_ctx* c) {
             if (r.nv) e = hipMemcpyAsync(vb.p + r.vb, m.d_verts, r.nv * sizeof(UhVertex), hipMemcpyDeviceToDevice, c->stream);
             uhi_iota(c->stream, ib.p + r.ib, r.ni);
             if (e == hipSuccess) e = hipGetLastError();
+         } else if (m.upd) {
+            if (r.nv) e = hipMemcpyAsync(vb.p + r.vb, m.d_verts, r.nv * sizeof(UhVertex), hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess && r.ni) e = hipMemcpyAsync(ib.p + r.ib, m.d_indices, r.ni * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream);
          } else {
             if (r.nv) e = hipMemcpy(vb.p + r.vb, m.vertices.data(), r.nv * sizeof(UhVertex), hipMemcpyHostToDevice);
             if (e == hipSuccess && r.ni) e = hipMemcpy(ib.p + r.ib, m.indices.data(), r.ni * sizeof(uint32_t), hipMemcpyHostToDevice);

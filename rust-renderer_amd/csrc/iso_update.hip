@@ -8,6 +8,7 @@
 // 36- and 240-byte record sizes are. A mesh has one index list (iota), so triangle p's vertices are 3 p .. 3 p + 2.
 #include <hip/hip_runtime.h>
 
+#include "box_reduce.h"
 #include "bvh.h"
 #include "context_internal.h"
 
@@ -17,21 +18,6 @@ constexpr uint32_t kTile = 128;                   // triangles per tile = thread
 constexpr uint32_t kVertexFloats = sizeof(UhVertex) / 4;  // 20
 constexpr uint32_t kTileQuads = kTile * 3 * sizeof(UhVertex) / 16;  // 1,920 16-byte loads per tile
 static_assert(sizeof(UhVertex) == 80 && sizeof(uh::ShadePacket) == 64, "k_iso_scatter's record arithmetic");
-
-// floats as unsigned integers of the same order (for atomicMin / atomicMax)
-__device__ __forceinline__ uint32_t ordered(float f) {
-   const uint32_t u = __float_as_uint(f);
-   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-   for (int s = 32; s > 0; s >>= 1) v = fminf(v, __shfl_xor(v, s));
-   return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-   for (int s = 32; s > 0; s >>= 1) v = fmaxf(v, __shfl_xor(v, s));
-   return v;
-}
 
 __global__ __launch_bounds__(kTile) void k_iso_scatter(const float4* __restrict__ verts, uint32_t num_tris, uint32_t mesh, float* __restrict__ corners,
                                                        uint32_t* __restrict__ keys, float4* __restrict__ shade, uint32_t* __restrict__ box) {

@@ -1,6 +1,7 @@
 // scene_build.hip — the scene's geometry and the trees over it: uh_add_mesh and the instance transforms, the host builder
 // (uh_build_acceleration; bvh_build.cpp), the on-device builders (option "device_build"; lbvh.hip) with their per-triangle sources,
-// the refit (uh_refit_acceleration; refit.hip), and the device-resident meshes of uh_update_isosurface_mesh with the mesh read-backs.
+// the refit (uh_refit_acceleration; refit.hip), and the device-resident meshes of uh_update_isosurface_mesh and uh_update_mesh_vertices
+// (deform.hip) with the mesh read-backs.
 // Host-side counterpart of Renderer::add_model (utopian/src/renderer.rs) and utopian::Raytracing (utopian/src/raytracing.rs).
 // Host code only; struct uh_ctx is context_state.h, the rest of the C ABI is context.hip and graphs.hip.
 #include <hip/hip_runtime.h>
@@ -153,12 +154,20 @@ static int ensure_host_mirrors(uh_ctx* c) {
       for (size_t i = 0; i < m.indices.size(); i++) m.indices[i] = (uint32_t)i;
       m.host_valid = true;
    }
+   for (HostMesh& m : c->meshes) {
+      if (!m.upd || m.host_valid) continue;  // (its last update took a device pointer: the index list is still the host's)
+      HIP_TRY(c, hipMemcpy(m.vertices.data(), m.d_verts, m.vertices.size() * sizeof(UhVertex), hipMemcpyDeviceToHost));  // blocking
+      c->mupd.st.host_geometry_bytes += m.vertices.size() * sizeof(UhVertex);
+      m.host_valid = true;
+   }
    return UH_OK;
 }
-// bytes per triangle of the device-resident meshes that a host-side assembly uploads
+// bytes per triangle of the device-resident meshes that a host-side assembly uploads (from their mirrors: a mesh without one is not in it)
 static void count_host_upload(uh_ctx* c, size_t bytes_per_triangle) {
-   for (const HostMesh& m : c->meshes)
+   for (const HostMesh& m : c->meshes) {
       if (m.dev) c->iso.st.host_geometry_bytes += bytes_per_triangle * m.dev_tris;
+      if (m.upd && m.host_valid) c->mupd.st.host_geometry_bytes += bytes_per_triangle * m.tris();
+   }
 }
 
 // triangle p of a host-resident mesh: its three vertices through the index list, its nine object-space corners, its shading packet
@@ -229,6 +238,8 @@ static void publish_tree(uh_ctx* c, uint32_t num_nodes, size_t total, std::chron
    c->geom_version++;
    c->topology_valid = true;
    c->built = true;
+   c->packet_serial.resize(c->meshes.size());
+   for (size_t i = 0; i < c->meshes.size(); i++) c->packet_serial[i] = c->meshes[i].serial;
    c->build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
@@ -326,11 +337,28 @@ int uh_refit_acceleration(uh_ctx* c) {
    auto t0 = std::chrono::steady_clock::now();
    if (int st = sync_all(c)) return st;  // frames in flight still traverse the old boxes
    const size_t total = c->packet_keys.size();
-   if (total && !c->d_obj_corners.p) {
-      count_host_upload(c, 9 * sizeof(float));  // (only the host builder leaves no d_obj_corners, and it has made the mirrors)
+   // meshes whose vertices moved since the tree's packets were written (uh_update_mesh_vertices): k_deform_gather writes their
+   // object-space corners and shade packets again, in leaf order, and the refit below bakes them like any other
+   const bool fresh_corners = total && !c->d_obj_corners.p;
+   std::vector<DeformMesh> dm(c->meshes.size());
+   uint32_t moved_tris = 0;
+   bool any_moved = false;
+   for (size_t i = 0; i < dm.size(); i++) {
+      const HostMesh& m = c->meshes[i];
+      const bool moved = m.upd && m.tris() && (i >= c->packet_serial.size() || c->packet_serial[i] != m.serial || (fresh_corners && !m.host_valid));
+      dm[i] = DeformMesh{moved ? m.d_verts : nullptr, moved ? m.d_indices : nullptr, moved ? 1u : 0u, 0u};
+      if (moved) moved_tris += (uint32_t)m.tris();
+      any_moved = any_moved || moved;
+   }
+   if (fresh_corners) {
+      // (only the host builder leaves no d_obj_corners, and it has made the mirrors; a mesh updated from a device pointer since then
+      // has none: its slots are the gather's)
+      count_host_upload(c, 9 * sizeof(float));
       std::vector<float> oc(9 * total);
-      for (size_t i = 0; i < total; i++)
-         write_obj_corners(tri_verts(c->meshes[c->packet_keys[i] >> kPrimBits], c->packet_keys[i] & kPrimMask), &oc[9 * i]);
+      for (size_t i = 0; i < total; i++) {
+         const HostMesh& m = c->meshes[c->packet_keys[i] >> kPrimBits];
+         if (!m.upd || m.host_valid) write_obj_corners(tri_verts(m, c->packet_keys[i] & kPrimMask), &oc[9 * i]);
+      }
       HIP_TRY(c, c->d_obj_corners.alloc(9 * total));
       HIP_TRY(c, c->d_world_corners.alloc(9 * total));
       HIP_TRY(c, c->d_node_box.alloc(6 * (size_t)c->scene.num_nodes));
@@ -342,12 +370,28 @@ int uh_refit_acceleration(uh_ctx* c) {
    HIP_TRY(c, hipMemcpy(ms.data(), c->d_meshes.p, ms.size() * sizeof(MeshShade), hipMemcpyDeviceToHost));
    for (size_t i = 0; i < c->meshes.size(); i++) std::memcpy(ms[i].w2o, c->meshes[i].w2o, sizeof(ms[i].w2o));
    if (!ms.empty()) HIP_TRY(c, hipMemcpy(c->d_meshes.p, ms.data(), ms.size() * sizeof(MeshShade), hipMemcpyHostToDevice));
+   uh_ctx::MeshUpdate& u = c->mupd;
    if (total) {
       HIP_TRY(c, hipMemcpy(c->d_refit_meshes.p, rm.data(), rm.size() * sizeof(RefitMesh), hipMemcpyHostToDevice));
+      if (any_moved) {
+         if (u.table.n < dm.size()) HIP_TRY(c, u.table.alloc(dm.size()));
+         HIP_TRY(c, hipMemcpy(u.table.p, dm.data(), dm.size() * sizeof(DeformMesh), hipMemcpyHostToDevice));
+         HIP_TRY(c, hipEventRecord(u.ev[0], c->stream));
+         launch_deform_gather(c->stream, u.table.p, (uint32_t)dm.size(), c->d_tris.p, c->d_obj_corners.p, c->d_shade.p, (uint32_t)total);
+         HIP_TRY(c, hipEventRecord(u.ev[1], c->stream));
+      }
       launch_refit(cfg(c), refit_args(c, total));
+      if (any_moved) HIP_TRY(c, hipEventRecord(u.ev[2], c->stream));
       HIP_TRY(c, hipGetLastError());
       HIP_TRY(c, hipStreamSynchronize(c->stream));
+      if (any_moved) {
+         HIP_TRY(c, hipEventElapsedTime(&u.st.gather_ms, u.ev[0], u.ev[1]));
+         HIP_TRY(c, hipEventElapsedTime(&u.st.refit_ms, u.ev[1], u.ev[2]));
+         u.st.triangles = moved_tris;
+      }
    }
+   c->packet_serial.resize(c->meshes.size());
+   for (size_t i = 0; i < c->meshes.size(); i++) c->packet_serial[i] = c->meshes[i].serial;
    c->built = true;
    c->geom_version++;
    c->build_ms = c->refit_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -396,7 +440,7 @@ static int upload_host_sources(uh_ctx* c, const std::vector<size_t>& at) {
    std::vector<ShadePacket> sp(total);
    for (uint32_t mi = 0; mi < nm; mi++) {
       const HostMesh& m = c->meshes[mi];
-      if (m.dev) continue;
+      if (m.resident()) continue;
       size_t t = at[mi];
       const uint32_t nt = (uint32_t)m.tris();
       for (uint32_t p = 0; p < nt; p++, t++) {
@@ -409,7 +453,7 @@ static int upload_host_sources(uh_ctx* c, const std::vector<size_t>& at) {
    hipError_t e = c->d_src.alloc(total);
    if (e != hipSuccess) return sources_fail(c, e, "allocation");
    const BuildSources::View host{corners.data(), keys.data(), reinterpret_cast<const float4*>(sp.data())};
-   e = for_each_run(nm, [&](size_t i) { return !c->meshes[i].dev; }, [&](size_t i, size_t j) {
+   e = for_each_run(nm, [&](size_t i) { return !c->meshes[i].resident(); }, [&](size_t i, size_t j) {
       return c->d_src.copy_range(at[i], host, at[i], at[j] - at[i], hipMemcpyHostToDevice, nullptr);
    });
    return e == hipSuccess ? UH_OK : sources_fail(c, e, "upload");
@@ -438,7 +482,8 @@ static int move_unchanged_sources(uh_ctx* c, const std::vector<size_t>& at) {
    return UH_OK;
 }
 
-// every device-resident mesh in `todo` through k_iso_scatter; its box words come back with the build's own wait
+// every device-resident mesh in `todo` through k_iso_scatter, or through k_deform_scatter and k_deform_box when it is indexed
+// (uh_update_mesh_vertices); its box words come back with the build's own wait
 static int scatter_device_sources(uh_ctx* c, const std::vector<size_t>& at, const std::vector<uint32_t>& todo) {
    std::vector<uint32_t> box(6 * todo.size());
    for (size_t k = 0; k < todo.size(); k++)
@@ -448,6 +493,12 @@ static int scatter_device_sources(uh_ctx* c, const std::vector<size_t>& at, cons
    for (size_t k = 0; k < todo.size(); k++) {
       const HostMesh& m = c->meshes[todo[k]];
       const size_t first = at[todo[k]];
+      if (m.upd) {
+         launch_deform_scatter(c->stream, m.d_verts, m.d_indices, (uint32_t)m.tris(), todo[k], c->d_src.corners.p + 9 * first, c->d_src.keys.p + first,
+                               c->d_src.shade.p + 4 * first);
+         launch_deform_box(c->stream, m.d_verts, (uint32_t)m.num_vertices(), c->iso.box.p + 6 * k);
+         continue;
+      }
       uhi_iso_scatter(c->stream, m.d_verts, m.dev_tris, todo[k], c->d_src.corners.p + 9 * first, c->d_src.keys.p + first,
                       c->d_src.shade.p + 4 * first, c->iso.box.p + 6 * k);
    }
@@ -474,12 +525,12 @@ static int refresh_build_sources(uh_ctx* c) {
    for (size_t i = 0; i < nm; i++) {
       tris[i] = (uint32_t)c->meshes[i].tris();
       at[i + 1] = at[i] + tris[i];
-      any_dev = any_dev || c->meshes[i].dev;
+      any_dev = any_dev || c->meshes[i].resident();
    }
-   std::vector<uint32_t> todo;  // meshes whose range k_iso_scatter writes
+   std::vector<uint32_t> todo;  // meshes whose range is written from their device vertices
    if (!c->src_valid) {
       for (size_t i = 0; i < nm; i++)
-         if (c->meshes[i].dev) todo.push_back((uint32_t)i);
+         if (c->meshes[i].resident()) todo.push_back((uint32_t)i);
       if (int st = upload_host_sources(c, at)) return st;
       iso_scatter_begin(c);
    } else {
@@ -516,9 +567,9 @@ static int build_on_device(uh_ctx* c) {
    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
    for (const HostMesh& m : c->meshes) {
       float olo[3] = {INFINITY, INFINITY, INFINITY}, ohi[3] = {-INFINITY, -INFINITY, -INFINITY};
-      if (m.dev) {
-         // the same minima and maxima, reduced on the device by k_iso_scatter (refresh_build_sources)
-         if (!m.dev_tris) continue;
+      if (m.resident()) {
+         // the same minima and maxima, reduced on the device by k_iso_scatter / k_deform_box (refresh_build_sources)
+         if (m.dev ? !m.dev_tris : m.vertices.empty()) continue;
          if (m.box_serial != m.serial) return fail(c, UH_ERR_HIP, "internal: a device-resident mesh has no box");
          for (int a = 0; a < 3; a++) olo[a] = m.olo[a], ohi[a] = m.ohi[a];
       } else {
@@ -685,6 +736,16 @@ int uh_read_mesh(uh_ctx* c, uint32_t mesh_index, UhVertex* vertices, uint32_t* i
       }
       return UH_OK;
    }
+   if (m.upd && !m.host_valid) {
+      // updated from a device pointer: the vertices come from the device the same way, the index list is the host's
+      if (vertices) {
+         HIP_TRY(c, hipSetDevice(c->device));
+         HIP_TRY(c, hipMemcpy(vertices, m.d_verts, m.vertices.size() * sizeof(UhVertex), hipMemcpyDeviceToHost));
+         c->mupd.st.host_geometry_bytes += m.vertices.size() * sizeof(UhVertex);
+      }
+      if (indices) std::memcpy(indices, m.indices.data(), m.indices.size() * sizeof(uint32_t));
+      return UH_OK;
+   }
    if (vertices && !m.vertices.empty()) std::memcpy(vertices, m.vertices.data(), m.vertices.size() * sizeof(UhVertex));
    if (indices && !m.indices.empty()) std::memcpy(indices, m.indices.data(), m.indices.size() * sizeof(uint32_t));
    return UH_OK;
@@ -761,7 +822,89 @@ int uh_get_isosurface_update_stats(uh_ctx* c, UhIsosurfaceUpdateStats* out) {
    *out = c->iso.st;
    const uh_ctx::IsoUpdate& u = c->iso;
    out->device_bytes = u.counts.n * sizeof(uint32_t) + u.chunks.n * sizeof(uint32_t) + u.box.n * sizeof(uint32_t) + u.total.n * sizeof(unsigned long long);
-   for (const HostMesh& m : c->meshes) out->device_bytes += m.d_capacity * sizeof(UhVertex);
+   for (const HostMesh& m : c->meshes)
+      if (!m.upd) out->device_bytes += m.d_capacity * sizeof(UhVertex);
+   return UH_OK;
+}
+
+int uh_update_mesh_vertices(uh_ctx* c, uint32_t mesh_index, const UhVertex* vertices, uint32_t num_vertices, int where) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (mesh_index >= c->meshes.size()) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_update_mesh_vertices: bad mesh index");
+   if (where != UH_VERTICES_HOST && where != UH_VERTICES_DEVICE) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_update_mesh_vertices: `where` is neither UH_VERTICES_HOST nor UH_VERTICES_DEVICE");
+   HostMesh& m = c->meshes[mesh_index];
+   if (m.iso) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_update_mesh_vertices: the mesh was created by uh_add_isosurface_mesh (uh_update_isosurface_mesh updates it)");
+   if (num_vertices != m.vertices.size()) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_update_mesh_vertices: the vertex count differs from the mesh's");
+   if (num_vertices && !vertices) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_update_mesh_vertices: null vertices");
+   if (where == UH_VERTICES_HOST)
+      for (uint32_t i = 0; i < num_vertices; i++)
+         if (!std::isfinite(vertices[i].pos[0]) || !std::isfinite(vertices[i].pos[1]) || !std::isfinite(vertices[i].pos[2]))
+            return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_update_mesh_vertices: vertex position is not finite");
+   HIP_TRY(c, hipSetDevice(c->device));
+   if (int st = sync_all(c)) return st;
+   uh_ctx::MeshUpdate& u = c->mupd;
+   for (hipEvent_t& ev : u.ev)
+      if (!ev) HIP_TRY(c, hipEventCreate(&ev));
+   if (!num_vertices) {  // nothing to move: the mesh stays where it is
+      u.st.updates++;
+      return UH_OK;
+   }
+   if (where == UH_VERTICES_DEVICE) {
+      // the caller's buffer is looked at before anything of the mesh is overwritten
+      if (!u.flag.p) HIP_TRY(c, u.flag.alloc(1));
+      uint32_t flag = 0;
+      HIP_TRY(c, hipMemsetAsync(u.flag.p, 0, sizeof(uint32_t), c->stream));
+      launch_deform_check(c->stream, vertices, num_vertices, u.flag.p);
+      HIP_TRY(c, hipGetLastError());
+      HIP_TRY(c, hipMemcpyAsync(&flag, u.flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      if (flag) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_update_mesh_vertices: vertex position is not finite");
+   }
+   if (!m.upd) {
+      // the mesh's own buffers, and its index list to the device this once; a refusal leaves the mesh as it was
+      UhVertex* dv = nullptr;
+      uint32_t* di = nullptr;
+      const size_t index_bytes = m.indices.size() * sizeof(uint32_t);
+      hipError_t e = hipMalloc((void**)&dv, num_vertices * sizeof(UhVertex));
+      if (e == hipSuccess && index_bytes) e = hipMalloc((void**)&di, index_bytes);
+      if (e == hipSuccess && index_bytes) e = hipMemcpy(di, m.indices.data(), index_bytes, hipMemcpyHostToDevice);
+      if (e != hipSuccess) {
+         if (dv) (void)hipFree(dv);
+         if (di) (void)hipFree(di);
+         return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string("uh_update_mesh_vertices: the mesh's device buffers: ") + hipGetErrorString(e));
+      }
+      m.d_verts = dv;
+      m.d_indices = di;
+      m.d_capacity = num_vertices;
+      m.upd = true;
+   }
+   // from here on the mesh's geometry is the new one: whatever happens, the context is not built
+   m.serial++;
+   c->built = false;
+   const size_t bytes = num_vertices * sizeof(UhVertex);
+   if (where == UH_VERTICES_HOST) {
+      std::memcpy(m.vertices.data(), vertices, bytes);
+      m.host_valid = true;
+      HIP_TRY(c, hipMemcpy(m.d_verts, vertices, bytes, hipMemcpyHostToDevice));
+      u.st.host_geometry_bytes += bytes;
+   } else {
+      m.host_valid = false;
+      HIP_TRY(c, hipMemcpyAsync(m.d_verts, vertices, bytes, hipMemcpyDeviceToDevice, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+   }
+   u.st.updates++;
+   return UH_OK;
+}
+
+int uh_get_mesh_update_stats(uh_ctx* c, UhMeshUpdateStats* out) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_mesh_update_stats: null destination");
+   std::memset(out, 0, sizeof(*out));
+   HIP_TRY(c, hipSetDevice(c->device));
+   if (int st = sync_all(c)) return st;
+   if (!c->mupd.st.updates) return UH_OK;
+   *out = c->mupd.st;
+   for (const HostMesh& m : c->meshes)
+      if (m.upd) out->device_bytes += m.d_capacity * sizeof(UhVertex) + m.indices.size() * sizeof(uint32_t);
    return UH_OK;
 }
 

@@ -291,6 +291,22 @@ assert C.sizeof(IsosurfaceUpdateStats) == 32 and IsosurfaceUpdateStats.updates.o
     IsosurfaceUpdateStats.host_geometry_bytes.offset == 16 and IsosurfaceUpdateStats.device_bytes.offset == 24
 
 
+VERTICES_HOST, VERTICES_DEVICE = 0, 1  # uh_update_mesh_vertices' `where`
+
+
+class MeshUpdateStats(C.Structure):
+    """UhMeshUpdateStats: uh_update_mesh_vertices so far - hipEvent ms of k_deform_gather and of the refit behind it in the last refit
+    that gathered, the updates, the triangles that refit rewrote, vertex and packet bytes of updated meshes moved between host and
+    device (cumulative) and the vertex and index buffers held for updated meshes"""
+
+    _fields_ = [("gather_ms", C.c_float), ("refit_ms", C.c_float), ("updates", C.c_uint32), ("triangles", C.c_uint32),
+                ("host_geometry_bytes", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+
+assert C.sizeof(MeshUpdateStats) == 32 and MeshUpdateStats.updates.offset == 8 and MeshUpdateStats.triangles.offset == 12 and \
+    MeshUpdateStats.host_geometry_bytes.offset == 16 and MeshUpdateStats.device_bytes.offset == 24
+
+
 # the hybrid graph's G-buffer pass rasterised (gbuffer.rs, gbuffer.vert / gbuffer.frag): a modifier of HYBRID_GBUFFER
 HYBRID_GBUFFER_RASTER = 1 << 11
 HYBRID_GBUFFER_DEPTH, HYBRID_GBUFFER_VISIBILITY = 11, 12
