@@ -1,5 +1,5 @@
 // bvh.h — memory layout of the acceleration structure shared by the host builder (bvh_build.cpp), the device builder
-// and refit (lbvh.hip, refit.hip) and the gfx950 traversal kernels (kernels.hip). Replaces the driver-private BLAS/TLAS of
+// and refit (lbvh.hip, refit.hip) and the gfx950 traversal (traversal.h). Replaces the driver-private BLAS/TLAS of
 // VK_KHR_acceleration_structure (reference: utopian/src/raytracing.rs:113-398).
 //
 // One flattened BVH4 over world-space triangles (instance transforms baked at build time). Every leaf is ONE triangle.

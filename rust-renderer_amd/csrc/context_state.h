@@ -169,7 +169,7 @@ struct Slot {
          for (uint32_t r = 0; r < runs; r++) per_shard[shard_of_run(r)]++;
          for (uint32_t s = 0; s < kShards; s++) shard_cap = per_shard[s] * 64 > shard_cap ? per_shard[s] * 64 : shard_cap;
       }
-      if (shard_cap >= (1u << 31)) return hipErrorInvalidValue;  // a queue position's top bit carries the path's sun verdict (kernels.hip kSunLitBit)
+      if (shard_cap >= (1u << 31)) return hipErrorInvalidValue;  // a queue position's top bit carries the path's sun verdict (path_shading.h kSunLitBit)
       hipError_t e;
 #define SLOT_TRY(expr)                 \
    if ((e = (expr)) != hipSuccess) return e

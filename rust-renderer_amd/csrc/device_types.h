@@ -1,5 +1,5 @@
 // device_types.h — structs passed between the host context (context.hip) and the kernels
-// (kernels.hip). Device pointers only; everything here is plain data.
+// (kernels.hip and the other kernel files). Device pointers only; everything here is plain data.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -250,13 +250,13 @@ struct HybridFrameDev {
    float sun_raw[3];          // view.sun_dir as given (the sun light's dir = sun_raw * (-1, 1, -1))
 };
 
-// launch wrappers implemented in kernels.hip --------------------------------------------------
+// launch wrappers implemented in kernels.hip, path_fused.hip, restir.hip, tiles.hip and hybrid_kernels.hip --------------------------------------------------
 struct LaunchCfg {
    hipStream_t stream;
    uint32_t num_cus;
    uint32_t closest_blocks_per_cu, shadow_blocks_per_cu;
    bool count_visits;
-   uint32_t fused_blocks_per_cu = 4;  // k_path_fused's grid (option "fused_bounces" 2..8); its registers and LDS are sized for kernels.hip kFusedBlocks
+   uint32_t fused_blocks_per_cu = 4;  // k_path_fused's grid (option "fused_bounces" 2..8); its registers and LDS are sized for path_fused.hip kFusedBlocks
 };
 
 void launch_generate(const LaunchCfg&, const FrameParams&, const PathState&, Control*, uint32_t sample);

@@ -1,4 +1,4 @@
-// hybrid_shading.h — the shading the hybrid graph's G-buffer and deferred passes (kernels.hip) share with the forward pass
+// hybrid_shading.h — the shading the hybrid graph's G-buffer and deferred passes (hybrid_kernels.hip) share with the forward pass
 // (forward.hip): gbuffer.vert / forward.vert's per-vertex TBN and normal plus the fragment shaders' normal-map block, surfaceShading's
 // light loop (pbr_lighting.glsl / brdf.glsl) and shadow_mapping.glsl's calculateShadow. Arithmetic: DESIGN.md section 2, "Hybrid
 // passes", "Hybrid frame passes" and "Shadow maps".

@@ -1,5 +1,5 @@
 // ibl_device.h — device arithmetic of the IBL maps (ibl.rs and its shaders) shared by their build (ibl.hip) and their consumers
-// (kernels.hip): cube addressing with seamless edges, the LINEAR / trilinear filters, the brdf.glsl helpers and imageBasedLighting.
+// (hybrid_kernels.hip): cube addressing with seamless edges, the LINEAR / trilinear filters, the brdf.glsl helpers and imageBasedLighting.
 // Every line is pinned in DESIGN.md section 2 "Environment and IBL maps"; tests/ibl_reference.py restates it in numpy.
 #pragma once
 #include <hip/hip_fp16.h>

@@ -247,7 +247,7 @@ __global__ __launch_bounds__(kBlock) void k_lbvh_collapse(const uint4* __restric
       ch[nc++] = e.y;
    }
    // node children in ascending weight (area, or triangle count for the radix tree): a visibility walk takes them from the
-   // highest slot down, biggest subtree first (kernels.hip node_compute, bvh_build.cpp)
+   // highest slot down, biggest subtree first (traversal.h node_compute, bvh_build.cpp)
    uint32_t nd[4];
    uint32_t n_node = 0, n_tri = 0;
    for (int k = 0; k < nc; k++) {

@@ -1,4 +1,4 @@
-// node_slab.h - the float arithmetic of the BVH4 node test (kernels.hip node_compute), as host + device functions, so that the
+// node_slab.h - the float arithmetic of the BVH4 node test (traversal.h node_compute), as host + device functions, so that the
 // traversal kernels and the host check of that arithmetic (tests/cpp/bvh_check.cpp) compile the same text.
 //
 // A child plane is origin + step * q (bvh.h Node4C, node_quant.h), so along one axis

@@ -10,7 +10,7 @@ The reservoir passes (config 2) are partitioned differently - by bands of rows, 
 spatial_reuse_reservoirs per frame (partition_reservoir_passes below; include/utopian_hip.h uh_set_restir_partition).
 
 The same index math runs in three places and is tested against each other: k_tiles (HIP,
-csrc/kernels.hip), pack_tiles_host / unpack_tiles_host here (numpy; CPU gloo tests and the oracle),
+csrc/tiles.hip), pack_tiles_host / unpack_tiles_host here (numpy; CPU gloo tests and the oracle),
 and owns_pixel in both tracers.
 """
 import numpy as np

@@ -10,8 +10,8 @@
 // which uh_check_acceleration runs on trees written by the GPU), with packets and corners baked from tri_order as the context bakes
 // them: the host builder is its reference and must pass with no violation. A mutation section then breaks a tree in ten ways, one
 // per kind of fault check_tree exists to find, and expects each to be reported in its class ("MUTATIONS k/k caught").
-// The node test's arithmetic (csrc/node_slab.h, the very text node_compute of kernels.hip compiles) against the triangle test's
-// (tri_compute of kernels.hip, restated here with fmaf in the same order), for rays that start up to 1e6 away from the geometry:
+// The node test's arithmetic (csrc/node_slab.h, the very text node_compute of traversal.h compiles) against the triangle test's
+// (tri_compute of traversal.h, restated here with fmaf in the same order), for rays that start up to 1e6 away from the geometry:
 //   for every (ray, triangle) pair the triangle test accepts, every slot on the way from the root to the triangle's leaf passes
 //   the node test - with idir as the host computes it (correctly rounded) and with every component one ulp up and one ulp down
 //   (the hardware reciprocal is good to one ulp).
@@ -52,7 +52,7 @@ static F3 operator-(F3 a, F3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 static float dot_fma(F3 a, F3 b) { return std::fmaf(a.z, b.z, std::fmaf(a.y, b.y, a.x * b.x)); }
 static F3 cross_fma(F3 a, F3 b) { return {std::fmaf(a.y, b.z, -(a.z * b.y)), std::fmaf(a.z, b.x, -(a.x * b.z)), std::fmaf(a.x, b.y, -(a.y * b.x))}; }
 
-// tri_compute of kernels.hip on a packet baked as scene_build.hip bakes it (v0, e1 = v1 - v0, e2 = v2 - v0 in float): true when a
+// tri_compute of traversal.h on a packet baked as scene_build.hip bakes it (v0, e1 = v1 - v0, e2 = v2 - v0 in float): true when a
 // ray that has found nothing yet (best.t = tmax) accepts the triangle; *t_out = its parameter
 static bool tri_accepts(const float* c, F3 o, F3 d, float tmin, float tmax, float* t_out) {
    const F3 v0 = {c[0], c[1], c[2]}, e1 = {c[3] - c[0], c[4] - c[1], c[5] - c[2]}, e2 = {c[6] - c[0], c[7] - c[1], c[8] - c[2]};
@@ -72,9 +72,9 @@ static bool tri_accepts(const float* c, F3 o, F3 d, float tmin, float tmax, floa
    return true;
 }
 
-static float safe_rcp_dir(float x) { return 1.0f / (std::fabs(x) < 1e-30f ? std::copysign(1e-30f, x) : x); }  // kernels.hip, with the host's division
+static float safe_rcp_dir(float x) { return 1.0f / (std::fabs(x) < 1e-30f ? std::copysign(1e-30f, x) : x); }  // traversal.h, with the host's division
 
-// node_compute of kernels.hip for one slot: the planes by the text the kernel compiles (node_slab.h); tcap = the t of the hit
+// node_compute of traversal.h for one slot: the planes by the text the kernel compiles (node_slab.h); tcap = the t of the hit
 // that must not be lost (whatever the walk has found by then is no nearer, or the triangle does not matter)
 static bool slot_passes(const Node4C& q, int k, F3 o, F3 idir, float tmin, float tcap) {
    const float ov[3] = {o.x, o.y, o.z}, iv[3] = {idir.x, idir.y, idir.z};

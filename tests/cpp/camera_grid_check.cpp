@@ -5,7 +5,7 @@
 // The builder's arithmetic lives in csrc/camera_grid.h as host + device functions (pg_make_cam, pg_project_packet, sg_packet_edges,
 // sg_cell_touches, sg_cell_of): the kernels of csrc/sun_grid_build.hip call them per packet / per cell, and this file calls THE
 // SAME FUNCTIONS on the host, bins the packets the way k_sg_bin / k_sg_sort do, and then replays k_trace_camera_grid for rays in
-// the kernels' float arithmetic (primary_ray of device_math.h, tri_compute<false> of kernels.hip, restated with std::fmaf) against
+// the kernels' float arithmetic (primary_ray of device_math.h, tri_compute<false> of traversal.h, restated with std::fmaf) against
 // brute force over ALL packets. Three properties, each for every ray:
 //   (1) listing     every packet whose float test accepts the ray (and whose padded box the ray meets: what a padded-box tree asks)
 //                   is listed in the ray's pixel;
@@ -49,7 +49,7 @@ struct Hit {
 };
 static Hit no_hit() { return Hit{10000.0f, 0.0f, 0.0f, 0xffffffffu, 0xffffffffu}; }  // rgen:45: tmax
 
-// tri_compute<ANY = false> of kernels.hip (tmin 0.001): true when the packet ACCEPTS the ray (barycentrics and t > tmin); the best
+// tri_compute<ANY = false> of traversal.h (tmin 0.001): true when the packet ACCEPTS the ray (barycentrics and t > tmin); the best
 // hit is updated as the kernel does (nearer t, ties by the smaller key)
 static bool tri_compute(const float* q, uint32_t i, uint32_t key, F3 o, F3 d, Hit& best, float* t_out) {
    F3 v0{q[0], q[1], q[2]}, e1{q[3], q[4], q[5]}, e2{q[6], q[7], q[8]};

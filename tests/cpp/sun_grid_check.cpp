@@ -2,7 +2,7 @@
 // For random and adversarial triangle soups and sun directions it replays, on the host and in the kernel's float arithmetic,
 // what k_trace_sun_grid does for a ray (project, clamp to a cell, walk the cell's list until the far-depth break) and compares
 // the verdict with a brute-force any-hit over ALL triangles through the same Moeller-Trumbore arithmetic (tri_compute<ANY> of
-// kernels.hip, restated with std::fmaf). Rays are the hard ones: origins on surfaces, rays through shared edges and vertices
+// traversal.h, restated with std::fmaf). Rays are the hard ones: origins on surfaces, rays through shared edges and vertices
 // (exactly and a few ulps off), edge-on triangles, slivers, huge / tiny / non-finite triangles, axis-aligned directions.
 // Build: g++ -std=c++17 -O1 -ffp-contract=off -mfma -fsanitize=address,undefined ... sun_grid_check.cpp ../../rust-renderer_amd/csrc/sun_grid.cpp
 #include <cmath>
@@ -30,7 +30,7 @@ struct F3 {
 static float dot_fma(F3 a, F3 b) { return std::fmaf(a.z, b.z, std::fmaf(a.y, b.y, a.x * b.x)); }
 static F3 cross_fma(F3 a, F3 b) { return F3{std::fmaf(a.y, b.z, -(a.z * b.y)), std::fmaf(a.z, b.x, -(a.x * b.z)), std::fmaf(a.x, b.y, -(a.y * b.x))}; }
 
-// tri_compute<ANY = true> of kernels.hip with tmin 0.001, tmax 10000, tlimit inf
+// tri_compute<ANY = true> of traversal.h with tmin 0.001, tmax 10000, tlimit inf
 // solid = true additionally ignores packets whose plane contains the direction to within 1e-5 rad: for a ray that lies in such a
 // plane the test divides rounding noise by rounding noise, and which of those packets gets asked (hence the verdict) differs
 // between any two conservative culling schemes - tree or grid. Shadow rays leave surfaces displaced along the normal

@@ -1,5 +1,5 @@
 """One frame per call (renderers/mod.rs:357, main.rs:460-471): bounces 1 .. of a lone frame inside one persistent kernel
-(csrc/kernels.hip k_path_fused: a wavefront per block, the paths' state in place) must give the words the wavefront of launches
+(csrc/path_fused.hip k_path_fused: a wavefront per block, the paths' state in place) must give the words the wavefront of launches
 gives - radiance, output, ray counts - on every kind of frame the library renders, and the oracle's image."""
 import numpy as np
 import pytest
@@ -109,6 +109,28 @@ def test_fused_against_the_oracle(atrium):
         run_frames(r, atrium, W, H, 2, rr.PASS_REFERENCE_PT)
     assert per_pixel_l2(gpu.read_accumulation(), cpu.read_accumulation()) <= L2_TOL
     assert list(gpu.get_stats().rays) == list(cpu.get_stats().rays)
+
+
+@pytest.mark.parametrize("W,H", [(8, 5), (16, 4), (24, 11)])
+def test_fused_equals_wavefront_at_the_wave_list_edges(cornell, atrium, W, H):
+    """the edges of the per-wave LDS lists both shading loops (k_shade_hit, k_path_fused's shading phase) collect hits and misses in,
+    which the larger frames above cross only incidentally: 40 paths - one partial wave, so only the final partial shade and the register carry of the misses
+    run; exactly 64 - the list is emptied with no tail to move; 264 - one block and a partial wave, with tails that move. The library
+    renders all three sizes as asked."""
+    for scene in (cornell, atrium):
+        for bounces in (2, 5):
+            fused, wave = pair(scene, W, H)
+            for r in (fused, wave):
+                run_frames(r, scene, W, H, 3, rr.PASS_REFERENCE_PT, num_bounces=bounces)
+            same_frames(fused, wave)
+    if (W, H) == (24, 11):
+        for bounces in (2, 5):
+            gpu, cpu = make_pair(atrium, W, H)
+            gpu.set_option("fused_bounces", -1)
+            for r in (gpu, cpu):
+                run_frames(r, atrium, W, H, 3, rr.PASS_REFERENCE_PT, num_bounces=bounces)
+            assert per_pixel_l2(gpu.read_accumulation(), cpu.read_accumulation()) <= L2_TOL
+            assert list(gpu.get_stats().rays) == list(cpu.get_stats().rays)
 
 
 def test_fused_only_while_no_frame_is_in_flight(atrium):

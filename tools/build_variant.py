@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""A measurement library: csrc/kernels.hip compiled with extra -D switches, linked with the default build's other objects. Its use is
-the instrumented build of tools/fused_phase_profile.py (kernels.hip UH_FUSED_PROFILE, the only switch the kernels read):
+"""A measurement library: the csrc file that holds k_path_fused compiled with extra -D switches, linked with the default build's other
+objects. Its use is the instrumented build of tools/fused_phase_profile.py (UH_FUSED_PROFILE, the only switch the kernels read):
   python tools/build_variant.py prof -DUH_FUSED_PROFILE   ->  rust-renderer_amd/libuh_prof.so   (UTOPIAN_HIP_LIB takes it)"""
 import os
 import subprocess
@@ -16,9 +16,10 @@ import build as b  # noqa: E402
 
 name, flags = sys.argv[1], sys.argv[2:]
 b.build_library()
-obj = os.path.join(b.OBJ_DIR, "kernels_%s.o" % name)
-subprocess.run(["hipcc"] + b.HIPCC_FLAGS + flags + ["-I", os.path.join(ROOT, "include"), "-I", b.CSRC, "-c", os.path.join(b.CSRC, "kernels.hip"), "-o", obj], check=True)
-others = [os.path.join(b.OBJ_DIR, f) for f in os.listdir(b.OBJ_DIR) if f.endswith(".o") and not f.startswith("kernels")]
+src = next(f for f in sorted(os.listdir(b.CSRC)) if f.endswith(".hip") and "void k_path_fused(" in open(os.path.join(b.CSRC, f)).read())
+obj = os.path.join(b.OBJ_DIR, "variant_%s.o" % name)
+subprocess.run(["hipcc"] + b.HIPCC_FLAGS + flags + ["-I", os.path.join(ROOT, "include"), "-I", b.CSRC, "-c", os.path.join(b.CSRC, src), "-o", obj], check=True)
+others = [os.path.join(b.OBJ_DIR, f) for f in os.listdir(b.OBJ_DIR) if f.endswith(".o") and f != src + ".o" and not f.startswith("variant_")]
 lib = os.path.join(pkg, "libuh_%s.so" % name)
 subprocess.run(["hipcc", "-shared", "-fPIC", "--offload-arch=gfx950", "-pthread", "-o", lib, obj] + others, check=True)
 print(lib)

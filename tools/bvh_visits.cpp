@@ -2,7 +2,7 @@
 // child-ordering policies, on the product's host builder (csrc/bvh_build.cpp) and full-precision boxes.
 //   input: a binary file written by tools/bvh_visits.py: u32 n_tris, u32 n_rays, 9*n_tris floats (corners), 8*n_rays floats (o, tmin, d, tmax)
 // Policies: 0 = full sort by entry distance (push far to near); 1 = nearest child first, the other hits pushed in slot order
-// (what kernels.hip does); 2 = as 1 but any-hit (first hit ends the ray).
+// (what traversal.h does); 2 = as 1 but any-hit (first hit ends the ray).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
