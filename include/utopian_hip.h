@@ -634,8 +634,8 @@ int uh_mgpu_set_option(uh_mgpu* group, const char* name, int value);
  * GATES: view->raytracing_supported == 0 skips both ray-traced passes and leaves their images as they are (mod.rs:107,134);
  * UH_HYBRID_RT_REFLECTIONS with view->ibl_enabled == 1 is UH_ERR_INVALID_ARGUMENT - and nothing runs - until the IBL maps (irradiance,
  * specular, BRDF LUT of ibl.rs) have been built with UH_HYBRID_ENVIRONMENT, below; mask bits, UH_ERR_NOT_BUILT and moved instances with
- * view->rebuild_tlas as for uh_render_frame (bits above UH_HYBRID_SHADOW_MAPS, below, are ignored, except UH_HYBRID_MARCHING_CUBES and
- * UH_HYBRID_GBUFFER_RASTER).
+ * view->rebuild_tlas as for uh_render_frame (bits above UH_HYBRID_SHADOW_MAPS, below, are ignored, except UH_HYBRID_MARCHING_CUBES,
+ * UH_HYBRID_GBUFFER_RASTER and UH_HYBRID_RESTIR_LIGHTS).
  * STREAM ORDER: uh_render_hybrid enqueues like a frame (behind the frames in flight, ahead of those that follow); uh_read_hybrid and
  * uh_get_hybrid_stats wait for all work of the context and are complete on return. The exception is UH_HYBRID_SHADOW_MAPS, below: a
  * call that renders shadow maps BLOCKS the host until the frames in flight and the pass's binning have finished (it reads the
@@ -983,6 +983,49 @@ UH_LAYOUT_ASSERT(sizeof(UhGbufferRasterStats) == 16 && offsetof(UhGbufferRasterS
                     offsetof(UhGbufferRasterStats, covered_pixels) == 12,
                  "UhGbufferRasterStats (16 B)");
 int uh_get_gbuffer_raster_stats(uh_ctx* ctx, UhGbufferRasterStats* out);
+
+/* ---- the hybrid frame's local lights from the ReSTIR reservoirs: one light and one shadow ray per pixel ---------------------------------
+ * An EXTENSION: the reference's hybrid graph with reservoirs (build_hybrid_render_graph, renderers/mod.rs:377-391) is an empty "Todo".
+ * UH_HYBRID_RESTIR_LIGHTS (bit 12; bit 9 stays unused and ignored) does two things in one uh_render_hybrid call:
+ *   restir_lights   a pass of its own after rt_reflections and before SSAO. A pixel casts a ray exactly when its position texel is geometry
+ *                   (w != 0), its spatial reservoir r has 0 <= r.Y < view->num_lights, light r.Y is a point or spot light (light_type 1
+ *                   or 2), r.W_X is finite and > 0, and the light is above the pixel's horizon (the deferred pass's own NdotL of that light
+ *                   is not 0; NaN counts as 0). The ray is the path tracer's light shadow ray (reference.rgen:113-119) from offsetRay of the
+ *                   pixel's own position and normal texels toward the light's position: tmin 0.001, tmax 10000, occluded when a triangle
+ *                   has tmin < t < tmax and t <= the distance. The pass writes the light-visibility image: 255 where a ray was cast and
+ *                   found the light, 0 where it was occluded or none was cast.
+ *   deferred        UH_HYBRID_DEFERRED of the same call evaluates the sun with its light loop and then, where the visibility texel is 255,
+ *                   adds the one light of the pixel's reservoir - one iteration of the same loop on that light's record - times r.W_X,
+ *                   instead of looping over all view->num_lights lights unshadowed. Everything after the loop is unchanged.
+ *                   UhHybridFrameStats.lights reports 2.
+ * RESERVOIRS: the ones uh_read_reservoirs(ctx, 2) reads - whatever the last uh_render_frame with UH_PASS_RESTIR or more left. Rendering
+ * them with the SAME CAMERA (and lights) as this call's view is the caller's job: nothing checks it. The pass only reads them. A light
+ * the reservoir passes never sample lights nothing in this mode: lights beyond view->max_num_lights_used, lights of another type, and
+ * lights whose `intensity` has zero luminance.
+ * UH_ERR_INVALID_ARGUMENT with a message, and nothing runs: the bit with view->raytracing_supported != 1; no G-buffer rendered in this
+ * call or an earlier one; no reservoir pass has ever run on the context; a reservoir row partition with world > 1 is set
+ * (uh_set_restir_partition); and, as without the bit, UH_HYBRID_DEFERRED with view->num_lights above the lights added.
+ * READ-BACK (uh_read_hybrid, UH_ERR_INVALID_ARGUMENT before the first call with the bit): UH_HYBRID_LIGHT_VISIBILITY, R8, W*H texels.
+ * RESOURCES: 5 bytes per pixel (the image and a queue of the pixels that cast), allocated by the first call with the bit, the image
+ * cleared to 0; freed by uh_destroy. A context that never sets the bit allocates nothing for it.
+ * STREAM ORDER: as uh_render_hybrid; a reservoir pass enqueued later starts behind this call's reads.
+ * ISOLATION: the bit changes no reservoir, accumulation, gbuffer_position, grid or UhStats, and no hybrid image but the two named; its
+ * rays are counted in UhHybridRestirStats only. Without the bit every pass is what it was. No uh_mgpu_ twin.
+ * Arithmetic: DESIGN.md section 2, "Reservoir lights". */
+enum { UH_HYBRID_RESTIR_LIGHTS = 1u << 12 };
+enum { UH_HYBRID_LIGHT_VISIBILITY = 13 /* R8: 255 lit, 0 occluded or no ray */ };
+/* the last call with the bit: rays cast, how many of them were occluded, and the pass's hipEvent time. All zero before the first call
+ * with the bit. Waits for all work of the context. */
+typedef struct UhHybridRestirStats {
+   uint64_t rays;
+   uint64_t occluded;
+   float pass_ms;
+   uint32_t reserved[3];
+} UhHybridRestirStats;
+UH_LAYOUT_ASSERT(sizeof(UhHybridRestirStats) == 32 && offsetof(UhHybridRestirStats, occluded) == 8 && offsetof(UhHybridRestirStats, pass_ms) == 16 &&
+                    offsetof(UhHybridRestirStats, reserved) == 20,
+                 "UhHybridRestirStats (32 B)");
+int uh_get_hybrid_restir_stats(uh_ctx* ctx, UhHybridRestirStats* out);
 
 #ifdef __cplusplus
 }

@@ -305,9 +305,9 @@ class Renderer {
    // "uh_render_hybrid")
    void render_hybrid(const UhViewUniformData& view, uint32_t mask = UH_HYBRID_ALL) { check(uh_render_hybrid(ctx_, &view, mask), "render_hybrid"); }
    // one image as bytes: W*H texels of 16 (position, normal, pbr, deferred output), 4 (albedo, reflections, present output, the
-   // marching-cubes and rasterised G-buffer depth floats and draw indices uint32), 2 (SSAO) or 1 (shadows) bytes
+   // marching-cubes and rasterised G-buffer depth floats and draw indices uint32), 2 (SSAO) or 1 (shadows, light visibility) bytes
    std::vector<uint8_t> read_hybrid(int which) {
-      const size_t texel = (which == UH_HYBRID_SHADOWS)      ? 1
+      const size_t texel = (which == UH_HYBRID_SHADOWS || which == UH_HYBRID_LIGHT_VISIBILITY) ? 1
                            : (which == UH_HYBRID_SSAO_IMAGE) ? 2
                            : (which == UH_HYBRID_ALBEDO || which == UH_HYBRID_REFLECTIONS || which == UH_HYBRID_PRESENT_OUTPUT ||
                               which == UH_HYBRID_DEPTH || which == UH_HYBRID_MARCHING_CUBES_VISIBILITY || which == UH_HYBRID_GBUFFER_DEPTH ||
@@ -338,6 +338,12 @@ class Renderer {
    UhGbufferRasterStats gbuffer_raster_stats() {
       UhGbufferRasterStats s;
       check(uh_get_gbuffer_raster_stats(ctx_, &s), "gbuffer_raster_stats");
+      return s;
+   }
+   // the last call with UH_HYBRID_RESTIR_LIGHTS: rays cast toward the reservoirs' lights, the occluded ones, the pass's time (utopian_hip.h)
+   UhHybridRestirStats hybrid_restir_stats() {
+      UhHybridRestirStats s;
+      check(uh_get_hybrid_restir_stats(ctx_, &s), "hybrid_restir_stats");
       return s;
    }
    // one face and mip of an IBL map built with UH_HYBRID_ENVIRONMENT (utopian_hip.h "uh_read_environment"): (512 >> mip)^2 texels of

@@ -34,6 +34,7 @@ from .types import (
     HYBRID_DEPTH,
     HYBRID_GBUFFER_DEPTH,
     HYBRID_GBUFFER_VISIBILITY,
+    HYBRID_LIGHT_VISIBILITY,
     HYBRID_MARCHING_CUBES_VISIBILITY,
     HYBRID_NORMAL,
     HYBRID_POSITION,
@@ -46,6 +47,7 @@ from .types import (
     GpuMaterial,
     EnvironmentStats,
     HybridFrameStats,
+    HybridRestirStats,
     HybridStats,
     GbufferRasterStats,
     IsosurfaceUpdateStats,
@@ -509,16 +511,17 @@ class Renderer:
         HYBRID_MARCHING_CUBES_VISIBILITY: (np.uint32, 1),
         HYBRID_GBUFFER_DEPTH: (np.float32, 1),
         HYBRID_GBUFFER_VISIBILITY: (np.uint32, 1),
+        HYBRID_LIGHT_VISIBILITY: (np.uint8, 1),
     }
 
     def read_hybrid(self, which):
         """one image of the hybrid graph: (H, W, 4) float32 position / normal / pbr / deferred output, (H, W, 4) uint8 albedo / reflections /
         present output (B, G, R, A), (H, W) uint8 shadows, (H, W) uint16 SSAO, (H, W) float32 marching-cubes depth buffer, (H, W) uint32
         marching-cubes draw index (MARCHING_CUBES_NONE where none survived), (H, W) float32 rasterised G-buffer depth, (H, W) uint32
-        rasterised G-buffer draw index (GBUFFER_NONE where none survived)"""
+        rasterised G-buffer draw index (GBUFFER_NONE where none survived), (H, W) uint8 light visibility of HYBRID_RESTIR_LIGHTS"""
         api = self._hybrid_api()
         if which not in self._HYBRID_IMAGES:
-            raise ValueError(f"hybrid image index {which} (0..12)")
+            raise ValueError(f"hybrid image index {which} (0..13)")
         dtype, ch = self._HYBRID_IMAGES[which]
         out = np.empty((self.height, self.width, ch) if ch > 1 else (self.height, self.width), dtype=dtype)
         self._check(api.read_hybrid(self._ctx, int(which), out.ctypes.data))
@@ -573,6 +576,15 @@ class Renderer:
         fn = getattr(self._lib, "uh_get_gbuffer_raster_stats")
         fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(GbufferRasterStats)], C.c_int
         s = GbufferRasterStats()
+        self._check(fn(self._ctx, C.byref(s)))
+        return s
+
+    def hybrid_restir_stats(self):
+        """UhHybridRestirStats of the last render_hybrid call with HYBRID_RESTIR_LIGHTS: rays, occluded, pass_ms"""
+        self._hybrid_api()
+        fn = getattr(self._lib, "uh_get_hybrid_restir_stats")
+        fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(HybridRestirStats)], C.c_int
+        s = HybridRestirStats()
         self._check(fn(self._ctx, C.byref(s)))
         return s
 

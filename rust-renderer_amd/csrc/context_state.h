@@ -132,10 +132,10 @@ struct Stage {
 };
 
 // the hybrid graph's stages (uh_ctx::Hybrid::stage): its seven passes in the order of their UH_HYBRID_* bits, then the environment's,
-// then the shadow maps, then the marching-cubes pass
+// then the shadow maps, then the marching-cubes pass, then the reservoir lights
 enum HybridStage : int {
    kStShadows, kStGbuffer, kStReflections, kStSsao, kStDeferred, kStSky, kStPresent, kHybridPasses,
-   kStEnvCube = kHybridPasses, kStEnvIrradiance, kStEnvSpecular, kStEnvLut, kStShadowMaps, kStMarchingCubes, kHybridStages
+   kStEnvCube = kHybridPasses, kStEnvIrradiance, kStEnvSpecular, kStEnvLut, kStShadowMaps, kStMarchingCubes, kStRestirLights, kHybridStages
 };
 
 // One frame in flight: its own stream pair, hazard events, path state and queue control block.
@@ -474,6 +474,12 @@ struct uh_ctx {
       DevBuf<HybridMesh> mc_mesh;              // mesh_index 0's maps with world = identity
       uint32_t mc_renders = 0, mc_tris = 0, mc_pieces = 0, mc_lights_used = 0;
       float mc_time = 0.0f;
+      // the reservoir lights (UH_HYBRID_RESTIR_LIGHTS), allocated by the first call with the bit: the light-visibility image, the queue
+      // of the pixels that cast a ray and the pass's counters (rays, occluded); rl_read: behind the call's last read of the reservoirs
+      DevBuf<uint8_t> rl_vis;
+      DevBuf<uint32_t> rl_queue, rl_counters;
+      hipEvent_t rl_read = nullptr;
+      uint32_t rl_renders = 0;
 
       // the three groups allocated on first use, each named once for allocation and uh_destroy: f(buffer, length), n pixels; a
       // group's last buffer is allocated last, its pointer says "allocated"
@@ -488,6 +494,7 @@ struct uh_ctx {
          f(mc_lights, UH_MAX_GPU_LIGHTS + 1), f(mc_block_counts, kMcBlocks), f(mc_bins.mats, 44), f(mc_mesh, 1), f(mc_total, 1), f(mc_bins.totals, 2),
             f(mc_verts, 0), mc.each(n, f);  // (mc_verts and the rest of mc_bins are grown by the pass)
       }
+      template <class F> void restir_images(size_t n, F&& f) { f(rl_vis, n), f(rl_queue, n), f(rl_counters, 2); }
       template <class F> void env_maps(F&& f) {
          const size_t cube = env_mip_offset(kEnvMips);
          f(env, cube), f(irr, 6 * (size_t)kEnvSize * kEnvSize), f(spec, cube), f(lut, (size_t)kLutSize * kLutSize);

@@ -250,6 +250,16 @@ struct HybridFrameDev {
    float sun_raw[3];          // view.sun_dir as given (the sun light's dir = sun_raw * (-1, 1, -1))
 };
 
+// the reservoir lights of the hybrid frame (UH_HYBRID_RESTIR_LIGHTS): what the restir_lights pass writes and the deferred pass reads
+struct HybridRestirDev {
+   uint8_t* vis;                   // light visibility R8: 255 where a ray was cast and found the light, else 0
+   uint32_t* queue;                // the pixels that cast a ray, compacted
+   uint32_t* counters;             // [0]: entries of `queue` = rays cast, [1]: occluded rays
+   const UhReservoir* reservoirs;  // spatial_reuse_reservoirs as the last reservoir pass left them (read only)
+   const UhGpuLight* raw_lights;   // the uh_add_light table as added
+   uint32_t num_lights;            // view.num_lights, at most the table's length
+};
+
 // launch wrappers implemented in kernels.hip, path_fused.hip, restir.hip, tiles.hip and hybrid_kernels.hip --------------------------------------------------
 struct LaunchCfg {
    hipStream_t stream;
@@ -334,8 +344,11 @@ struct ShadowLookup {
    const UhShadowmapParams* params;  // the snapshot the maps were rendered with (device copy)
    uint32_t size;
 };
+// restir: when not null, the light loop evaluates the sun alone and the pixels whose visibility texel is 255 add their reservoir's light
 void launch_hybrid_deferred(const LaunchCfg&, const SceneDev&, const HybridDev&, const HybridFrameDev&, const IblMaps* ibl,
-                            const ShadowLookup* shadow);
+                            const ShadowLookup* shadow, const HybridRestirDev* restir = nullptr);
+// the restir_lights pass: classify (which pixels cast a ray toward their reservoir's light), then the rays; rl.counters zeroed by the caller
+void launch_hybrid_restir_lights(const LaunchCfg&, const FrameParams&, const SceneDev&, const HybridDev&, const HybridRestirDev&);
 // the shadow-map rasteriser (shadow_map.hip): setup per (triangle, cascade), binning into kShadowTile^2 tiles, resolve per tile in LDS
 constexpr uint32_t kShadowTile = 128;
 struct ShadowDev {

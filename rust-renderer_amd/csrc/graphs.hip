@@ -81,6 +81,8 @@ void destroy_graphs(uh_ctx* c) {
    h.env_maps(release);
    h.shadow_maps(release);
    h.mc_images(0, release);
+   h.restir_images(0, release);
+   if (h.rl_read) (void)hipEventDestroy(h.rl_read);
    h.mc_bins.each(release);
    h.gr.each(0, release);
    h.gr_bins.each(release);
@@ -584,6 +586,25 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
       return fail(c, UH_ERR_INVALID_ARGUMENT,
                   "uh_render_hybrid: the sky pass with view.cubemap_enabled = 1 needs the environment cube (ibl.rs), which a call with "
                   "UH_HYBRID_ENVIRONMENT builds; set that bit, or cubemap_enabled = 0 for the IntegrateScattering branch");
+   // the reservoir lights: one shadow ray per pixel toward the light of its spatial reservoir, which the deferred pass then adds
+   const bool restir = (mask & UH_HYBRID_RESTIR_LIGHTS) != 0;
+   if (restir) {
+      if (view->raytracing_supported != 1)
+         return fail(c, UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_RESTIR_LIGHTS casts shadow rays and view.raytracing_supported is not 1; set it, or clear the bit");
+      if (!(mask & UH_HYBRID_GBUFFER) && !c->hy.gbuffer_done)
+         return fail(c, UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_RESTIR_LIGHTS casts its rays from the G-buffer, and no G-buffer has been rendered; set "
+                     "UH_HYBRID_GBUFFER");
+      if (!c->restir_recorded)
+         return fail(c, UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_RESTIR_LIGHTS reads the spatial reservoirs, and no reservoir pass has run on this context; "
+                     "render a frame with UH_PASS_RESTIR (same camera) first");
+      if (c->rp_world > 1)
+         return fail(c, UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_RESTIR_LIGHTS needs the whole frame's reservoirs, and a row partition with world > 1 is set "
+                     "(uh_set_restir_partition)");
+   }
    // setup_marching_cubes_pass (mod.rs:164): only with the checkbox on
    const bool mc = (mask & UH_HYBRID_MARCHING_CUBES) && view->marching_cubes_enabled == 1;
    if (mc) {
@@ -621,6 +642,15 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    }
    if (mc && !h.mc.covered.p)
       if (int st = alloc_group(c, [&](auto f) { h.mc_images((size_t)c->W * c->H, f); })) return st;
+   if (restir) {
+      if (int st = hybrid_light_table(c)) return st;
+      if (!h.rl_read) HIP_TRY(c, hipEventCreateWithFlags(&h.rl_read, hipEventDisableTiming));
+      if (!h.rl_counters.p) {
+         if (int st = alloc_group(c, [&](auto f) { h.restir_images((size_t)c->W * c->H, f); })) return st;
+         HIP_TRY(c, hipMemsetAsync(h.rl_vis.p, 0, (size_t)c->W * c->H, c->stream));
+         HIP_TRY(c, hipMemsetAsync(h.rl_counters.p, 0, 2 * sizeof(uint32_t), c->stream));
+      }
+   }
    if (mask & UH_HYBRID_ENVIRONMENT)
       if (int st = env_alloc(c)) return st;
    const FrameParams fp = make_params(c, *view);
@@ -675,6 +705,7 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
       for (int k = 0; k < kHybridPasses; k++) h.stage[k].ran = false;
    if (mask & UH_HYBRID_SHADOW_MAPS) h.stage[kStShadowMaps].ran = false;
    if (mask & UH_HYBRID_MARCHING_CUBES) h.stage[kStMarchingCubes].ran = false;
+   if (restir) h.stage[kStRestirLights].ran = false;
    // setup_shadow_pass's four passes are added first (mod.rs:91-98)
    if (render_maps) {
       HIP_TRY(c, stage_begin(h.stage[kStShadowMaps], c->stream));
@@ -728,6 +759,16 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
       launch_hybrid_reflections(lc, c->scene, hd, view->ibl_enabled == 1 ? &ibl : nullptr);
       HIP_TRY(c, stage_end(h.stage[kStReflections], c->stream));
    }
+   // restir_lights: the pixels' reservoirs (whatever the last reservoir pass left: read only) and this call's light count
+   const HybridRestirDev rl{h.rl_vis.p, h.rl_queue.p, h.rl_counters.p, c->im.reservoirs[2], h.raw_lights.p,
+                            (uint32_t)std::min<size_t>(view->num_lights, c->lights.size())};
+   if (restir) {
+      HIP_TRY(c, stage_begin(h.stage[kStRestirLights], c->stream));
+      HIP_TRY(c, hipMemsetAsync(h.rl_counters.p, 0, 2 * sizeof(uint32_t), c->stream));
+      launch_hybrid_restir_lights(lc, fp, c->scene, hd, rl);
+      HIP_TRY(c, stage_end(h.stage[kStRestirLights], c->stream));
+      h.rl_renders++;
+   }
    // the final frame (mod.rs:136-186): ssao_pass (not with ssao_enabled != 1, ssao.rs:27), deferred_pass, atmosphere_pass, present_pass
    if ((mask & UH_HYBRID_SSAO) && view->ssao_enabled == 1) {
       HIP_TRY(c, stage_begin(h.stage[kStSsao], c->stream));
@@ -737,10 +778,15 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    if (mask & UH_HYBRID_DEFERRED) {
       HIP_TRY(c, stage_begin(h.stage[kStDeferred], c->stream));
       const ShadowLookup sl{h.smaps.p, h.s_params.p, h.smap_size};
-      launch_hybrid_deferred(lc, c->scene, hd, fd, view->ibl_enabled == 1 ? &ibl : nullptr, view->shadows_enabled == 1 ? &sl : nullptr);
+      launch_hybrid_deferred(lc, c->scene, hd, fd, view->ibl_enabled == 1 ? &ibl : nullptr, view->shadows_enabled == 1 ? &sl : nullptr, restir ? &rl : nullptr);
       HIP_TRY(c, stage_end(h.stage[kStDeferred], c->stream));
    }
-   h.frame_lights = h.stage[kStDeferred].ran ? view->num_lights + 1 : 0;
+   h.frame_lights = h.stage[kStDeferred].ran ? (restir ? 2 : view->num_lights + 1) : 0;  // with the reservoir lights: the sun and the reservoir's
+   if (restir) {
+      // a reservoir pass enqueued after this call starts behind the call's reads (the spatial ring comes round to the slot read here)
+      HIP_TRY(c, hipEventRecord(h.rl_read, c->stream));
+      HIP_TRY(c, hipStreamWaitEvent(c->restir_stream, h.rl_read, 0));
+   }
    // setup_marching_cubes_pass (mod.rs:164-174): after the deferred pass, before the atmosphere pass
    if (mc) {
       HIP_TRY(c, stage_begin(h.stage[kStMarchingCubes], c->stream));
@@ -769,18 +815,21 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    const uh_ctx::Hybrid& h = c->hy;
    if (!h.counter.p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid before the first uh_render_hybrid");
-   if (which < 0 || which > UH_HYBRID_GBUFFER_VISIBILITY) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..12");
+   if (which < 0 || which > UH_HYBRID_LIGHT_VISIBILITY) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..13");
    if (which >= UH_HYBRID_SSAO_IMAGE && which <= UH_HYBRID_PRESENT_OUTPUT && !h.sky_counter.p)
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 6..8 before the first call with an SSAO, deferred, sky or present bit");
    if ((which == UH_HYBRID_DEPTH || which == UH_HYBRID_MARCHING_CUBES_VISIBILITY) && h.mc_renders == 0)
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 9..10 before the first marching-cubes pass");
-   if (which >= UH_HYBRID_GBUFFER_DEPTH && h.gr_renders == 0)
+   if ((which == UH_HYBRID_GBUFFER_DEPTH || which == UH_HYBRID_GBUFFER_VISIBILITY) && h.gr_renders == 0)
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 11..12 before the first rasterised G-buffer pass");
+   if (which == UH_HYBRID_LIGHT_VISIBILITY && !h.rl_counters.p)
+      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image 13 before the first call with UH_HYBRID_RESTIR_LIGHTS");
    // image k's pixels and its bytes per pixel, in UH_HYBRID_* image order
    const std::pair<const void*, size_t> img[] = {
       {h.pos.p, sizeof(float4)}, {h.nrm.p, sizeof(float4)}, {h.alb.p, sizeof(uchar4)}, {h.pbr.p, sizeof(float4)}, {h.shadow.p, 1},
       {h.refl.p, sizeof(uchar4)}, {h.ssao.p, sizeof(uint16_t)}, {h.deferred.p, sizeof(float4)}, {h.present.p, sizeof(uchar4)},
-      {h.mc.depth.p, sizeof(float)}, {h.mc.vis.p, sizeof(uint32_t)}, {h.gr.depth.p, sizeof(float)}, {h.gr.vis.p, sizeof(uint32_t)}};
+      {h.mc.depth.p, sizeof(float)}, {h.mc.vis.p, sizeof(uint32_t)}, {h.gr.depth.p, sizeof(float)}, {h.gr.vis.p, sizeof(uint32_t)},
+      {h.rl_vis.p, 1}};
    return read_back(c, out, img[which].first, (size_t)c->W * c->H * img[which].second);
 }
 
@@ -796,6 +845,22 @@ int uh_get_hybrid_frame_stats(uh_ctx* c, UhHybridFrameStats* out) {
       if (int st = stage_ms(c, c->hy.stage[k], &out->pass_ms[k])) return st;
    if (h.stage[kStSky].ran) HIP_TRY(c, hipMemcpy(&out->sky_pixels, h.sky_counter.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
    out->lights = h.frame_lights;
+   return UH_OK;
+}
+
+int uh_get_hybrid_restir_stats(uh_ctx* c, UhHybridRestirStats* out) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_hybrid_restir_stats: null destination");
+   std::memset(out, 0, sizeof(*out));
+   const uh_ctx::Hybrid& h = c->hy;
+   if (h.rl_renders == 0) return UH_OK;
+   HIP_TRY(c, hipSetDevice(c->device));
+   if (int st = sync_all(c)) return st;
+   if (int st = stage_ms(c, c->hy.stage[kStRestirLights], &out->pass_ms)) return st;
+   uint32_t counters[2] = {0, 0};
+   HIP_TRY(c, hipMemcpy(counters, h.rl_counters.p, sizeof(counters), hipMemcpyDeviceToHost));
+   out->rays = counters[0];
+   out->occluded = counters[1];
    return UH_OK;
 }
 

@@ -172,6 +172,80 @@ __global__ __launch_bounds__(kBlock) void k_hybrid_reflect(SceneDev sc, HybridDe
    }
 }
 
+// The reservoir lights (UH_HYBRID_RESTIR_LIGHTS; DESIGN.md section 2, "Reservoir lights"): which pixels cast a ray toward the light of
+// their spatial reservoir. One lane per pixel; every texel of the visibility image is written 0 here, the pixels that cast are appended to
+// a dense queue (one atomic per wave). The cull is direct_lighting's own NdotL (light_term): a culled pixel's term would be exactly zero.
+__global__ __launch_bounds__(kBlock) void k_hybrid_restir_classify(HybridDev hd, HybridRestirDev rl) {
+   const uint32_t n = hd.W * hd.H, groups = (n + 63) / 64, lane = lane_id();
+   for (uint32_t g = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); g < groups; g += gridDim.x * kWavesPerBlock) {
+      const uint32_t pix = g * 64u + lane;
+      bool cast = false;
+      if (pix < n) {
+         rl.vis[pix] = 0;
+         const float4 P4 = hd.pos[pix];
+         const UhReservoir r = rl.reservoirs[pix];
+         if (P4.w != 0.0f && r.Y >= 0 && (uint32_t)r.Y < rl.num_lights && r.W_X > 0.0f && r.W_X < INFINITY) {
+            const UhGpuLight& l = rl.raw_lights[r.Y];
+            if (l.light_type == 1.0f || l.light_type == 2.0f) {                                   // HybridLight::mode 1 or 2
+               const float4 N4 = hd.nrm[pix];
+               const V3 ptl = v3(l.position[0], l.position[1], l.position[2]) - v3(P4.x, P4.y, P4.z);
+               const float d = sqrtf(dot3(ptl, ptl));
+               const V3 L = ptl * (1.0f / d);
+               cast = fmaxf(dot3(v3(N4.x, N4.y, N4.z), L), 0.0f) != 0.0f;                         // NaN: culled
+            }
+         }
+      }
+      const uint32_t slot = wave_append(rl.counters, cast);
+      if (cast) rl.queue[slot] = pix;
+   }
+}
+
+// One any-hit ray per queued pixel toward its reservoir's light: reference.rgen:113-119 as the path tracer pins it (make_shadow_ray<true>),
+// from offset_ray of the pixel's own G-buffer texels. Persistent waves with the LDS refill of k_hybrid_shadow; the pool carries the pixel
+// ids alone (the lane that takes one makes its ray from the G-buffer, the reservoir and the light table there). No shading here: the
+// deferred pass, which holds the surface terms anyway, adds the light where this kernel stores 255.
+__global__ __launch_bounds__(kBlock, 5) void k_hybrid_restir_trace(SceneDev sc, FrameParams fp, HybridDev hd, HybridRestirDev rl) {
+   __shared__ uint32_t s_stack[kWavesPerBlock][kLdsStack][64];
+   __shared__ RayPool<0> s_pool[kWavesPerBlock];
+   const uint32_t lane = lane_id();
+   const uint32_t wave = threadIdx.x >> 6;
+   uint32_t* lds_col = &s_stack[wave][0][lane];
+   RayPool<0>& pool = s_pool[wave];
+   RaySource src;
+   src.queue = rl.queue;
+   src.count = rl.counters[0];
+   src.cursor = nullptr;
+   src.wave_index = blockIdx.x * kWavesPerBlock + wave;
+   src.num_waves = gridDim.x * kWavesPerBlock;
+   auto source_of = [](int, uint32_t) { return (const float4*)nullptr; };
+   Feeder<0> f;
+   Trav t;
+   t.cur = kEmptyRef;
+   t.sp = 0;
+   uint32_t pix = 0, n_nodes = 0, n_tris = 0, n_occluded = 0;
+   uint32_t spill[kSpillStack];
+   auto take = [&](uint32_t slot) {
+      pix = pool.id[slot];
+      const float4 P4 = hd.pos[pix], N4 = hd.nrm[pix];
+      const V3 o = offset_ray(v3(P4.x, P4.y, P4.z), v3(N4.x, N4.y, N4.z));
+      const ShadowRay s = make_shadow_ray<true>(sc, fp, make_float4(o.x, o.y, o.z, 0.0f), (uint32_t)rl.reservoirs[pix].Y);
+      trav_init(t, s.ro, s.rd, s.ro.w, s.rd.w, s.tlimit);
+   };
+   while (refill_lanes<0>(f, src, pool, t.cur == kEmptyRef, source_of, take)) {
+      if (t.cur != kEmptyRef) {
+         bool occluded = false;
+         if (trav_step<true, false>(sc.nodes, sc.tris, t, lds_col, spill, occluded, n_nodes, n_tris)) {
+            if (occluded)
+               n_occluded++;
+            else
+               rl.vis[pix] = 255;
+         }
+      }
+   }
+   for (int off = 32; off > 0; off >>= 1) n_occluded += __shfl_down(n_occluded, off);  // one atomic per wave
+   if (lane == 0 && n_occluded) atomicAdd(&rl.counters[1], n_occluded);
+}
+
 void launch_hybrid_clear(const LaunchCfg& c, const HybridDev& hd) {
    k_hybrid_clear<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(hd, hd.W * hd.H);
 }
@@ -184,6 +258,11 @@ void launch_hybrid_gbuffer(const LaunchCfg& c, const FrameParams& fp, const Scen
 void launch_hybrid_shadows(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd) {
    const uint32_t full = c.num_cus * c.shadow_blocks_per_cu, need = (hd.W * hd.H + kBlock - 1) / kBlock;
    k_hybrid_shadow<<<dim3(need < full ? need : full), kBlock, 0, c.stream>>>(sc, hd);
+}
+void launch_hybrid_restir_lights(const LaunchCfg& c, const FrameParams& fp, const SceneDev& sc, const HybridDev& hd, const HybridRestirDev& rl) {
+   k_hybrid_restir_classify<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(hd, rl);
+   const uint32_t full = c.num_cus * c.shadow_blocks_per_cu, need = (hd.W * hd.H + kBlock - 1) / kBlock;
+   k_hybrid_restir_trace<<<dim3(need < full ? need : full), kBlock, 0, c.stream>>>(sc, fp, hd, rl);
 }
 void launch_hybrid_reflections(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd, const IblMaps* ibl) {
    k_hybrid_reflect_classify<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(sc, hd);
@@ -323,10 +402,12 @@ __global__ void k_hybrid_light_prep(HybridFrameDev fd) {
 // k, 1 - metallic, 4 NdotV) are hoisted: the same operations on the same operands, so the same bits.
 // kIbl: the ambient term is imageBasedLighting on the IBL maps (frag:85-88) instead of 0.03 * diffuse * occlusion.
 // kShadow (shadows_enabled = 1): calculateShadow on the cascaded shadow maps (frag:98-106) instead of the rt_shadows factor.
+// kRestir (UH_HYBRID_RESTIR_LIGHTS): count is 1 (the sun); a pixel whose light-visibility texel is 255 adds the term of its reservoir's
+// light, record Y + 1, times the reservoir's W_X ("Reservoir lights"): a per-lane record, so vector loads.
 
-template <bool kIbl, bool kShadow>
+template <bool kIbl, bool kShadow, bool kRestir>
 __global__ __launch_bounds__(kBlock) void k_hybrid_deferred(SceneDev sc, HybridDev hd, HybridFrameDev fd, const HybridLight* __restrict__ lights, uint32_t count,
-                                                            IblMaps ibl, ShadowLookup sl) {
+                                                            IblMaps ibl, ShadowLookup sl, HybridRestirDev rl) {
    __shared__ float s_gamma[256];  // pow(c / 255, 2.2) of every UNORM8 value: pow in double, rounded to float
    s_gamma[threadIdx.x] = (float)pow((double)((float)threadIdx.x / 255.0f), (double)2.2f);
    __syncthreads();
@@ -349,7 +430,12 @@ __global__ __launch_bounds__(kBlock) void k_hybrid_deferred(SceneDev sc, HybridD
    const V3 diffuse = v3(s_gamma[A.x], s_gamma[A.y], s_gamma[A.z]);                            // frag:61
    const V3 base = diffuse * bc;                                                                // frag:65
    const V3 V = normalize3(v3(hd.eye[0], hd.eye[1], hd.eye[2]) - P);                            // lighting:26
-   const V3 Lo = direct_lighting(lights, count, P, N, V, base, metallic, roughness);
+   V3 Lo = direct_lighting(lights, count, P, N, V, base, metallic, roughness);
+   if (kRestir && rl.vis[i] == 255) {
+      const UhReservoir r = rl.reservoirs[i];
+      const LightTerm t = light_term(lights[r.Y + 1], surface_terms(N, V, base, metallic, roughness), P, N, V, base);
+      Lo = Lo + (((t.c * t.rad) * t.NdotL) * r.W_X);
+   }
    V3 ambient = (0.03f * diffuse) * occlusion;                                                  // frag:83
    if (kIbl) ambient = ibl::image_based_lighting(ibl, P, base, N, metallic, roughness, occlusion, v3(hd.eye[0], hd.eye[1], hd.eye[2]));  // frag:85-88
    V3 color = ambient + Lo;                                                                     // frag:90
@@ -494,20 +580,20 @@ void launch_hybrid_light_prep(const LaunchCfg& c, const HybridFrameDev& fd) {
    k_hybrid_light_prep<<<(fd.num_lights + 1 + 255) / 256, 256, 0, c.stream>>>(fd);
 }
 void launch_hybrid_deferred(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd, const HybridFrameDev& fd, const IblMaps* ibl,
-                            const ShadowLookup* shadow) {
+                            const ShadowLookup* shadow, const HybridRestirDev* restir) {
    launch_hybrid_light_prep(c, fd);
    const IblMaps im = ibl ? *ibl : IblMaps{};
    const ShadowLookup sl = shadow ? *shadow : ShadowLookup{};
+   const HybridRestirDev rl = restir ? *restir : HybridRestirDev{};
    const dim3 grid = one_lane_per_pixel(hd);
-   const uint32_t n = fd.num_lights + 1;
-   if (!ibl && !shadow)
-      k_hybrid_deferred<false, false><<<grid, kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, n, im, sl);
-   else if (!shadow)
-      k_hybrid_deferred<true, false><<<grid, kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, n, im, sl);
-   else if (!ibl)
-      k_hybrid_deferred<false, true><<<grid, kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, n, im, sl);
-   else
-      k_hybrid_deferred<true, true><<<grid, kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, n, im, sl);
+   const uint32_t n = restir ? 1 : fd.num_lights + 1;
+   as_constant(ibl != nullptr, [&](auto kIbl) {
+      as_constant(shadow != nullptr, [&](auto kShadow) {
+         as_constant(restir != nullptr, [&](auto kRestir) {
+            k_hybrid_deferred<decltype(kIbl)::value, decltype(kShadow)::value, decltype(kRestir)::value><<<grid, kBlock, 0, c.stream>>>(sc, hd, fd, fd.lights, n, im, sl, rl);
+         });
+      });
+   });
 }
 void launch_hybrid_sky(const LaunchCfg& c, const FrameParams& fp, const HybridDev& hd, const HybridFrameDev& fd, const IblMaps* cube, const uint32_t* skip) {
    k_hybrid_sky_classify<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(hd, fd, skip);

@@ -67,57 +67,81 @@ __device__ __forceinline__ void gbuffer_targets(const SceneDev& sc, const Hybrid
 
 constexpr float kPiBrdf = 3.14159265359f;  // brdf.glsl:1
 
-// surfaceShading (pbr_lighting.glsl:20-79) with brdf.glsl, summed over the light records of k_hybrid_light_prep (the sun first). The
-// light-independent terms (F0, NdotV, GeometrySchlickGGX(NdotV), a2, k, 1 - metallic, 4 NdotV) are hoisted: the same operations on
-// the same operands, so the same bits. The loop is wave-uniform with a scalar branch on the light's mode.
+// surfaceShading (pbr_lighting.glsl:20-79) with brdf.glsl, in two pieces: the light-independent terms (F0, NdotV,
+// GeometrySchlickGGX(NdotV), a2, k, 1 - metallic, 4 NdotV), hoisted out of the light loop - the same operations on the same operands, so
+// the same bits -, and one light's term from a record of k_hybrid_light_prep. direct_lighting sums the term over the records (the sun
+// first); the deferred pass's reservoir term ("Reservoir lights") is the same function on one record.
+struct SurfaceTerms {
+   V3 F0;
+   float om, a2, a2m1, k, omk, ggxV, nv4;
+};
+__device__ __forceinline__ SurfaceTerms surface_terms(V3 N, V3 V, V3 base, float metallic, float roughness) {
+   SurfaceTerms s;
+   s.om = 1.0f - metallic;
+   s.F0 = v3(0.04f, 0.04f, 0.04f) * s.om + base * metallic;                                     // lighting:29-30
+   const float NdotV = fmaxf(dot3(N, V), 0.0f);
+   const float a = roughness * roughness;                                                       // brdf:5-6
+   s.a2 = a * a;
+   s.a2m1 = s.a2 - 1.0f;
+   const float r1 = roughness + 1.0f;                                                           // brdf:19-20
+   s.k = (r1 * r1) / 8.0f;
+   s.omk = 1.0f - s.k;
+   s.ggxV = NdotV / (NdotV * s.omk + s.k);                                                      // brdf:31
+   s.nv4 = 4.0f * NdotV;                                                                        // lighting:71
+   return s;
+}
+// one light: Lo += (c * rad) * NdotL. The branch on the light's mode is scalar where the record's address is wave-uniform.
+struct LightTerm {
+   V3 c, rad;
+   float NdotL;
+};
+__device__ __forceinline__ LightTerm light_term(const HybridLight& hl, const SurfaceTerms& s, V3 P, V3 N, V3 V, V3 base) {
+   const float mode = hl.mode;
+   V3 L;
+   float att;
+   if (mode == 0.0f) {                                                                          // lighting:36-40
+      L = v3(hl.dir[0], hl.dir[1], hl.dir[2]);
+      att = 1.0f;
+   } else if (mode == 3.0f) {
+      L = v3(0.0f, 0.0f, 0.0f);
+      att = 1.0f;
+   } else {                                                                                     // lighting:41-53
+      const V3 ptl = v3(hl.pos[0], hl.pos[1], hl.pos[2]) - P;
+      const float d = sqrtf(dot3(ptl, ptl));
+      L = ptl * (1.0f / d);
+      const float den = (hl.att[0] * 1.0f + hl.att[1] * d) + hl.att[2] * (d * d);
+      if (mode == 2.0f)
+         att = powf(fmaxf(dot3(L, v3(hl.dir[0], hl.dir[1], hl.dir[2])), 0.0f), hl.spot) / den;
+      else
+         att = 1.0f / den;
+   }
+   LightTerm t;
+   const V3 Hv = normalize3(V + L);                                                             // lighting:58
+   t.rad = v3(hl.color[0] * att, hl.color[1] * att, hl.color[2] * att);                         // lighting:59
+   const float NdotH = fmaxf(dot3(N, Hv), 0.0f);                                                // brdf:7-14
+   float dn = (NdotH * NdotH) * s.a2m1 + 1.0f;
+   dn = (kPiBrdf * dn) * dn;
+   const float NDF = s.a2 / dn;
+   t.NdotL = fmaxf(dot3(N, L), 0.0f);                                                           // brdf:28-36
+   const float G = (t.NdotL / (t.NdotL * s.omk + s.k)) * s.ggxV;
+   const float x = fminf(fmaxf(1.0f - fmaxf(dot3(Hv, V), 0.0f), 0.0f), 1.0f);                 // brdf:82-85
+   const float p5 = ((x * x) * (x * x)) * x;
+   const V3 F = s.F0 + (v3(1.0f, 1.0f, 1.0f) - s.F0) * p5;
+   const V3 kD = (v3(1.0f, 1.0f, 1.0f) - F) * s.om;                                             // lighting:66-68
+   const float NG = NDF * G, den2 = s.nv4 * t.NdotL + 0.0001f;                                  // lighting:70-72
+   const V3 spec = v3((NG * F.x) / den2, (NG * F.y) / den2, (NG * F.z) / den2);
+   const V3 kb = kD * base;                                                                     // lighting:76
+   t.c = v3(kb.x / kPiBrdf + spec.x, kb.y / kPiBrdf + spec.y, kb.z / kPiBrdf + spec.z);
+   return t;
+}
+// summed over the light records of k_hybrid_light_prep (the sun first); the loop is wave-uniform
 __device__ __forceinline__ V3 direct_lighting(const HybridLight* __restrict__ lights, uint32_t count, V3 P, V3 N, V3 V, V3 base, float metallic,
                                               float roughness) {
-   const float om = 1.0f - metallic;
-   const V3 F0 = v3(0.04f, 0.04f, 0.04f) * om + base * metallic;                                // lighting:29-30
-   const float NdotV = fmaxf(dot3(N, V), 0.0f);
-   const float a = roughness * roughness, a2 = a * a, a2m1 = a2 - 1.0f;                          // brdf:5-6
-   const float r1 = roughness + 1.0f, k = (r1 * r1) / 8.0f, omk = 1.0f - k;                     // brdf:19-20
-   const float ggxV = NdotV / (NdotV * omk + k);                                                // brdf:31
-   const float nv4 = 4.0f * NdotV;                                                              // lighting:71
+   const SurfaceTerms s = surface_terms(N, V, base, metallic, roughness);
    V3 Lo = v3(0.0f, 0.0f, 0.0f);
    for (uint32_t l = 0; l < count; l++) {
-      const HybridLight& hl = lights[l];
-      const float mode = hl.mode;
-      V3 L;
-      float att;
-      if (mode == 0.0f) {                                                                       // lighting:36-40
-         L = v3(hl.dir[0], hl.dir[1], hl.dir[2]);
-         att = 1.0f;
-      } else if (mode == 3.0f) {
-         L = v3(0.0f, 0.0f, 0.0f);
-         att = 1.0f;
-      } else {                                                                                  // lighting:41-53
-         const V3 ptl = v3(hl.pos[0], hl.pos[1], hl.pos[2]) - P;
-         const float d = sqrtf(dot3(ptl, ptl));
-         L = ptl * (1.0f / d);
-         const float den = (hl.att[0] * 1.0f + hl.att[1] * d) + hl.att[2] * (d * d);
-         if (mode == 2.0f)
-            att = powf(fmaxf(dot3(L, v3(hl.dir[0], hl.dir[1], hl.dir[2])), 0.0f), hl.spot) / den;
-         else
-            att = 1.0f / den;
-      }
-      const V3 Hv = normalize3(V + L);                                                          // lighting:58
-      const V3 rad = v3(hl.color[0] * att, hl.color[1] * att, hl.color[2] * att);               // lighting:59
-      const float NdotH = fmaxf(dot3(N, Hv), 0.0f);                                             // brdf:7-14
-      float dn = (NdotH * NdotH) * a2m1 + 1.0f;
-      dn = (kPiBrdf * dn) * dn;
-      const float NDF = a2 / dn;
-      const float NdotL = fmaxf(dot3(N, L), 0.0f);                                              // brdf:28-36
-      const float G = (NdotL / (NdotL * omk + k)) * ggxV;
-      const float x = fminf(fmaxf(1.0f - fmaxf(dot3(Hv, V), 0.0f), 0.0f), 1.0f);              // brdf:82-85
-      const float p5 = ((x * x) * (x * x)) * x;
-      const V3 F = F0 + (v3(1.0f, 1.0f, 1.0f) - F0) * p5;
-      const V3 kD = (v3(1.0f, 1.0f, 1.0f) - F) * om;                                            // lighting:66-68
-      const float NG = NDF * G, den2 = nv4 * NdotL + 0.0001f;                                   // lighting:70-72
-      const V3 spec = v3((NG * F.x) / den2, (NG * F.y) / den2, (NG * F.z) / den2);
-      const V3 kb = kD * base;                                                                  // lighting:76
-      const V3 c = v3(kb.x / kPiBrdf + spec.x, kb.y / kPiBrdf + spec.y, kb.z / kPiBrdf + spec.z);
-      Lo = Lo + (c * rad) * NdotL;
+      const LightTerm t = light_term(lights[l], s, P, N, V, base);
+      Lo = Lo + (t.c * t.rad) * t.NdotL;
    }
    return Lo;
 }

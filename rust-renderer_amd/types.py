@@ -322,3 +322,18 @@ class GbufferRasterStats(C.Structure):
 
 assert C.sizeof(GbufferRasterStats) == 16 and GbufferRasterStats.renders.offset == 4 and GbufferRasterStats.pieces.offset == 8 and \
     GbufferRasterStats.covered_pixels.offset == 12
+
+
+# the hybrid frame's local lights from the ReSTIR reservoirs (an extension; utopian_hip.h "UH_HYBRID_RESTIR_LIGHTS"); bit 9 stays unused
+HYBRID_RESTIR_LIGHTS = 1 << 12
+HYBRID_LIGHT_VISIBILITY = 13
+
+
+class HybridRestirStats(C.Structure):
+    """UhHybridRestirStats: the last render_hybrid call with HYBRID_RESTIR_LIGHTS - rays cast, the occluded ones, hipEvent ms of the pass"""
+
+    _fields_ = [("rays", C.c_uint64), ("occluded", C.c_uint64), ("pass_ms", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
+assert C.sizeof(HybridRestirStats) == 32 and HybridRestirStats.occluded.offset == 8 and HybridRestirStats.pass_ms.offset == 16 and \
+    HybridRestirStats.reserved.offset == 20

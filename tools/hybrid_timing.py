@@ -20,10 +20,16 @@ what is timed:
   gbuffer_raster  the G-buffer pass rasterised (UH_HYBRID_GBUFFER | UH_HYBRID_GBUFFER_RASTER) alone, with its pieces and covered
           pixels, beside the cast alone; then the whole frame (UH_HYBRID_FRAME, IBL and shadows off) with the rasterised and with the
           cast G-buffer
+  restir_lights  on config 2's scene class (the same scene with 1,024 point lights), for each light count of --lights as view.num_lights:
+          the reservoir passes (uh_render_frame with UH_PASS_RESTIR: G-buffer cast, initial RIS, temporal and spatial reuse) as
+          UhStats.last_frame_ms; the whole frame with UH_HYBRID_RESTIR_LIGHTS - the restir_lights pass (UhHybridRestirStats, with its rays
+          and occluded rays) and the deferred pass that adds one light per pixel - beside the whole frame without the bit, whose deferred
+          pass loops over all the lights unshadowed. With UTOPIAN_HIP_LIB naming a library from before the bit existed (the parent
+          commit's), the reservoir passes and the plain frame alone
 
 Run it under `rocprofv3 --kernel-trace --stats -- python tools/hybrid_timing.py --mode ...` for the kernel table.
 
-  python tools/hybrid_timing.py [--mode passes|frame|ibl|shadows|forward|marching_cubes|gbuffer_raster --width 1920 --height 1080 --warmup 3 --iters 20 --lights 0,16,1024
+  python tools/hybrid_timing.py [--mode passes|frame|ibl|shadows|forward|marching_cubes|gbuffer_raster|restir_lights --width 1920 --height 1080 --warmup 3 --iters 20 --lights 0,16,1024
                                  --builds 5 --out FILE]"""
 import argparse
 import json
@@ -225,20 +231,54 @@ def gbuffer_raster(a):
                    **{f"{p}_ms": m for p, m in zip(PASSES, med)}, total_ms=sum(med))
 
 
+def restir_lights(a):
+    scene = rr.scenes.scene_for_config(2, with_spheres=True)
+    r = scene.upload(rr.Renderer(a.width, a.height))
+    for n in (int(x) for x in a.lights.split(",")):
+        if not 0 < n <= r.get_num_lights():
+            continue
+        view = scene.make_view(a.width, a.height, shadows_enabled=0, ibl_enabled=0, cubemap_enabled=0)
+        view.num_lights = n
+        frame_ms = []
+        for k in range(a.warmup + a.iters):  # a camera at rest: the temporal pass reprojects onto the same pixel
+            view.total_samples += 1
+            r.render_frame(view, rr.PASS_RESTIR)
+            frame_ms.append(r.get_stats().last_frame_ms)  # waits
+        line = dict(metric="hybrid_restir_lights", config=2, lights=n, width=a.width, height=a.height, iters=a.iters, triangles=scene.num_triangles,
+                    reservoir_passes_ms=statistics.median(frame_ms[a.warmup:]))
+
+        class Both:  # the seven passes and the restir_lights pass of one call
+            def __init__(self, r):
+                self.restir = r.hybrid_restir_stats()
+                self.pass_ms = list(r.hybrid_frame_stats().pass_ms) + [self.restir.pass_ms]
+
+        med, _ = timed(a, r, view, rr.HYBRID_FRAME, rr.Renderer.hybrid_frame_stats)
+        line.update(deferred_all_lights_ms=med[4], frame_all_lights_ms=sum(med))
+        if not hasattr(r._lib, "uh_get_hybrid_restir_stats"):  # UTOPIAN_HIP_LIB names a library from before the bit: the plain frame alone
+            yield line
+            continue
+        med, s = timed(a, r, view, rr.HYBRID_FRAME | rr.HYBRID_RESTIR_LIGHTS, Both)
+        line.update(restir_lights_ms=med[7], deferred_with_bit_ms=med[4], frame_with_bit_ms=sum(med), rays=s.restir.rays, occluded=s.restir.occluded)
+        line["reservoir_path_ms"] = line["reservoir_passes_ms"] + line["restir_lights_ms"] + line["deferred_with_bit_ms"]
+        line["reservoir_path_faster"] = line["reservoir_path_ms"] < line["deferred_all_lights_ms"]
+        yield line
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("passes", "frame", "ibl", "shadows", "forward", "marching_cubes", "gbuffer_raster"), default="passes")
+    ap.add_argument("--mode", choices=("passes", "frame", "ibl", "shadows", "forward", "marching_cubes", "gbuffer_raster", "restir_lights"),
+                    default="passes")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--lights", default="0,16,1024", help="frame: the light counts")
+    ap.add_argument("--lights", default="0,16,1024", help="frame, forward, restir_lights: the light counts")
     ap.add_argument("--builds", type=int, default=5, help="ibl: the map builds")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     lines = []
     for out in {"passes": passes, "frame": frame, "ibl": ibl, "shadows": shadows, "forward": forward, "marching_cubes": marching_cubes,
-                "gbuffer_raster": gbuffer_raster}[a.mode](a):
+                "gbuffer_raster": gbuffer_raster, "restir_lights": restir_lights}[a.mode](a):
         lines.append(json.dumps(out))
         print(lines[-1], flush=True)
     if a.out:
