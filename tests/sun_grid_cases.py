@@ -1,0 +1,186 @@
+"""Scenes, suns and the case matrix of test_gpu_sun_grid_builders.py: the geometry the host builder of the sun grid is proven on
+(tests/cpp/sun_grid_check.cpp: shared edges and vertices, edge-on triangles and slivers, huge and tiny triangles, axis-aligned
+directions) as scenes the DEVICE builder and the grid walk can be run on. No GPU is touched here."""
+import functools
+
+import numpy as np
+
+from rust_renderer_amd.camera import Camera
+from rust_renderer_amd.scenes import Mesh, Model, Scene, _pack_vertices, quad
+from util import far_scene, torture_scene
+
+# ---- suns -----------------------------------------------------------------------------------------------------------------------
+# the nine of test_gpu_sun_grid.SUNS under names, the negative axes, a grazing direction and one with a component of 1e-30
+SUN = {
+    "up_tilt": (0.0, 0.9, 0.15), "oct_ppp": (0.3, 0.8, 0.2), "oct_nnp": (-0.3, -0.8, 0.2), "pos_y": (0.0, 1.0, 0.0), "pos_x": (1.0, 0.0, 0.0),
+    "neg_z": (0.0, 0.0, -1.0), "diag_xy": (0.7, 0.7, 0.0), "near_y": (1e-4, 1.0, 0.0), "oct_npp": (-0.5, 0.1, 0.85),
+    "neg_y": (0.0, -1.0, 0.0), "neg_x": (-1.0, 0.0, 0.0), "grazing": (1.0, 0.02, 0.1), "tiny": (1e-30, 0.6, 0.8),
+}
+ALL_SUNS = tuple(SUN)
+
+
+def unit(sun):
+    """the direction as the frame normalises it (context.hip make_params: float32, v * (1 / sqrt(dot)))"""
+    v = np.float32(sun)
+    d = np.float32(np.float32(v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
+    return v * np.float32(np.float32(1.0) / np.sqrt(d, dtype=np.float32))
+
+
+# ---- scenes ---------------------------------------------------------------------------------------------------------------------
+def soup_mesh(pos, color=(1.0, 1.0, 1.0, 1.0)):
+    """triangles without shared vertices: pos is (n, 3, 3)"""
+    pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
+    return Mesh(_pack_vertices(pos, np.tile(np.float32([0, 0, 1]), (len(pos), 1)), np.zeros((len(pos), 2), np.float32)), np.arange(len(pos), dtype=np.uint32), base_color=color)
+
+
+def scene_of(name, meshes, eye=(0, 0, 6), target=(0, 0, 0), fov=60.0, **flags):
+    return Scene(name, [(Model(list(meshes), []), None)], [], Camera(eye, target, fov, 1.0, 0.01, 1000.0), dict(flags))
+
+
+def tilted_patch(centre=(0.0, 0.0, 0.0), scale=1.0, n=12):
+    """an n x n patch of quads with shared vertices, slightly bumped (no two neighbours coplanar), at a general angle to every axis"""
+    eu, ev = scale * np.float64([1.9, 0.7, -0.5]), scale * np.float64([-0.4, 1.3, 1.1])
+    origin = np.float64(centre) - 0.5 * (eu + ev)
+    return Mesh(*quad(origin, eu, ev, n, n, bump=lambda S, T: scale * 0.08 * np.sin(5.0 * S + 1.0) * np.cos(4.0 * T)), base_color=(0.9, 0.9, 0.9, 1.0), name="tilted patch")
+
+
+def edge_on_triangles(sun, centre=(0.0, 0.0, 0.0), scale=1.0):
+    """(n, 3, 3): triangles whose plane contains the direction `sun` - spanned by the very float32 direction the frame uses (the
+    determinant of the triangle test is then zero or a few ulps), tilted out of it by 1e-7 and by +-1e-6 rad, and in the three
+    coordinate planes (exactly edge-on to an axis-aligned sun) -, with an ordinary triangle beside each group"""
+    d = unit(sun).astype(np.float64)
+    p = np.cross(d, [0.3, -0.5, 0.8])
+    p /= np.linalg.norm(p)
+    n0 = np.cross(d, p)
+    tris = []
+    for k, tilt in enumerate((0.0, 1e-7, 1e-6, -1e-6)):
+        v0 = 0.35 * (k - 1.5) * n0 - 0.3 * d
+        tris.append([v0, v0 + 0.9 * (d + tilt * n0), v0 + 0.4 * d + 0.5 * p])
+        tris.append([v0 + 0.1 * n0, v0 + 0.1 * n0 + 0.6 * p, v0 + 0.1 * n0 + 0.5 * n0 + 0.2 * d])  # ordinary
+    for axis in range(3):
+        a, b = np.eye(3)[(axis + 1) % 3], np.eye(3)[(axis + 2) % 3]
+        v0 = 0.25 * np.eye(3)[axis] - 0.2 * (a + b)
+        tris.append([v0, v0 + 0.7 * a, v0 + 0.6 * b])
+    return np.float64(centre) + scale * np.float64(tris)
+
+
+def edge_on_scene(sun):
+    ground = Mesh(*quad((-1.5, -1.2, -1.4), (3.0, 0.4, 0.0), (0.0, 0.3, 3.0), 6, 6), base_color=(0.8, 0.8, 0.8, 1.0))
+    return scene_of("edge_on", [ground, soup_mesh(edge_on_triangles(sun))])
+
+
+def small_triangles(n, seed, lo=0.0, hi=4.0, size=0.08):
+    rng = np.random.default_rng(seed)
+    return rng.uniform(lo, hi, (n, 1, 3)) + rng.normal(scale=size, size=(n, 3, 3))
+
+
+def huge_among_small():
+    """one triangle a thousand times the raster (which follows the small ones: the 0.5 % .. 99.5 % range of the centres)"""
+    t = small_triangles(300, 21, 0.0, 1.0, 0.03)
+    t[150] = [[-2000.0, -1500.0, 0.5], [2500.0, -1000.0, 0.4], [100.0, 3000.0, 0.6]]
+    return scene_of("huge_among_small", [soup_mesh(t)])
+
+
+FEW = np.float64([[[-1.0, -0.8, 0.1], [1.2, -0.5, 0.3], [0.1, 1.1, -0.2]], [[0.2, 0.1, 1.0], [0.9, 0.3, 1.4], [0.4, 0.8, 0.7]],
+                  [[-0.7, 0.2, -0.9], [-0.1, 0.9, -1.3], [-0.9, 0.8, -0.4]], [[0.5, -0.9, 0.6], [1.4, -1.0, -0.3], [0.8, -0.2, 0.2]],
+                  [[-1.2, -1.1, -0.6], [-0.4, -1.3, 0.5], [-0.8, -0.3, 0.0]]])
+
+
+@functools.lru_cache(maxsize=None)
+def builder_scene(which, sun_name=None):
+    """the scenes of part 1 by id (edge_on is made for its sun)"""
+    from test_gpu_parity import _soup_scene
+    from test_gpu_sun_grid import deep_scene
+    from test_gpu_tree_invariants import _scene as tree_scene
+
+    if which in ("identical", "points", "sheet", "one", "far_grid_at_1000"):
+        return tree_scene(which)
+    if which.startswith("soup"):
+        return _soup_scene(int(which[4:]))
+    if which.startswith("few"):
+        return scene_of(which, [soup_mesh(FEW[: int(which[3:])])])
+    if which.startswith("stride"):
+        return scene_of(which, [soup_mesh(small_triangles(int(which[6:]), 22))])
+    return {"torture": torture_scene, "far_grid": lambda: far_scene("grid"), "deep": deep_scene, "huge": huge_among_small,
+            "tilted": lambda: scene_of("tilted", [tilted_patch()]), "edge_on": lambda: edge_on_scene(SUN[sun_name])}[which]()
+
+
+# k_sg_sample (sun_grid_build.hip build_grid_impl): "stride = n > 8192 ? (n + 8191) / 8192 : 1" - 8192 packets are all sampled,
+# with 8193 every second one is skipped
+SAMPLE_ALL_UP_TO = 8192
+
+DEFAULTS = ()
+OPTION_SETS = {"density1": (("sun_grid_density", 1),), "density4096": (("sun_grid_density", 4096),), "walk1": (("sun_grid_max_walk", 1),),
+               "walk2": (("sun_grid_max_walk", 2),), "walk4096": (("sun_grid_max_walk", 4096),), "mb1": (("sun_grid_max_mb", 1),)}
+
+
+def builder_cases():
+    """[(id, scene, sun name, options)]: every scene against a choice of suns at default options, the option sets on the torture
+    scene, a soup and the tilted patch"""
+    per_scene = {
+        "torture": ALL_SUNS, "soup1": ALL_SUNS, "tilted": ALL_SUNS,
+        "soup2": ("oct_ppp", "neg_y", "grazing", "tiny"), "soup3": ("oct_nnp", "neg_x", "near_y", "diag_xy"),
+        "identical": ("up_tilt", "neg_z", "pos_x"), "points": ("up_tilt", "neg_y"), "sheet": ("up_tilt", "oct_nnp", "pos_y", "pos_x"),
+        "one": ("oct_ppp", "neg_z", "tiny", "pos_y"), "far_grid": ("oct_ppp", "neg_z", "grazing", "diag_xy"),
+        "far_grid_at_1000": ("up_tilt", "oct_npp", "neg_z", "neg_x"), "deep": ("pos_y", "up_tilt", "neg_y", "oct_ppp"),
+        "edge_on": ("pos_y", "oct_ppp", "neg_x", "grazing", "tiny", "oct_npp"), "huge": ("up_tilt", "neg_z", "grazing", "oct_nnp"),
+        "few1": ("oct_ppp", "neg_y", "oct_npp", "pos_x"), "few2": ("oct_ppp", "neg_y", "oct_npp", "diag_xy"), "few3": ("oct_ppp", "neg_y", "oct_npp", "near_y"),
+        "few4": ("oct_ppp", "neg_y", "oct_npp", "grazing"), "few5": ("oct_ppp", "neg_y", "oct_npp", "tiny"),
+        f"stride{SAMPLE_ALL_UP_TO}": ("up_tilt", "neg_x", "oct_npp"), f"stride{SAMPLE_ALL_UP_TO + 1}": ("up_tilt", "neg_x", "oct_npp"),
+    }
+    cases = [(f"{scene}-{sun}-defaults", scene, sun, DEFAULTS) for scene, suns in per_scene.items() for sun in suns]
+    for scene in ("torture", "soup1", "tilted"):
+        for sun in ("oct_ppp", "oct_npp"):  # (neither lies in the torture scene's planes z = const)
+            cases += [(f"{scene}-{sun}-{name}", scene, sun, opts) for name, opts in OPTION_SETS.items()]
+    # 1000 identical triangles: every occupied cell lists all of them at one far depth - with max_walk = 4096 a ray may walk such a
+    # list, so each is sorted, by the packet index alone
+    cases += [("identical-oct_npp-walk4096", "identical", "oct_npp", OPTION_SETS["walk4096"]), ("huge-up_tilt-walk4096", "huge", "up_tilt", OPTION_SETS["walk4096"]), ("huge-up_tilt-mb1", "huge", "up_tilt", OPTION_SETS["mb1"]),
+              (f"stride{SAMPLE_ALL_UP_TO + 1}-up_tilt-density1", f"stride{SAMPLE_ALL_UP_TO + 1}", "up_tilt", OPTION_SETS["density1"])]
+    return cases
+
+
+# ---- part 2: probe arrangements -------------------------------------------------------------------------------------------------
+PROBE_W = PROBE_H = 96
+FLOOR_Z, FLOOR_HALF, EYE_Z = -3.0, 3.0, -1.2
+
+
+def probe_scene(which):
+    """a receiver floor of 40 x 40 quads in the plane z = FLOOR_Z, the occluders above z = -1, the camera BELOW them on the z axis
+    looking straight down at the floor, which fills the frame: one bounce, sky off, lights off - every pixel is a point of the floor,
+    lit or not, and its sun ray climbs through the occluders"""
+    floor = Mesh(*quad((-FLOOR_HALF, -FLOOR_HALF, FLOOR_Z), (2 * FLOOR_HALF, 0, 0), (0, 2 * FLOOR_HALF, 0), 40, 40), base_color=(0.7, 0.7, 0.7, 1.0), name="floor")
+    if which == "torture":
+        # the torture scene's meshes; its 1e5-unit triangle (mesh 4) is replaced by one of 15 units over a corner of the floor: with
+        # coordinates of 1e5 every margin is two units wide (2e-5 of the largest coordinate), every cell of the floor lists more
+        # packets than a ray walks and the case would test the fallback alone
+        occluders = [m for k, m in enumerate(torture_scene().models[0][0].meshes) if k != 4]
+        occluders.append(soup_mesh([[[3.0, -5.0, 2.5], [-5.0, 3.0, 2.6], [-12.0, -12.0, 2.4]]]))
+    elif which == "tilted":
+        occluders = [tilted_patch((0.3, -0.4, 0.4), 1.5, 20), soup_mesh(edge_on_triangles((0.3, 0.2, 0.8), (-1.3, 1.5, 0.6), 1.4))]
+    else:  # "soup": small triangles at every height, and 60 slivers (three nearly collinear corners)
+        rng = np.random.default_rng(5)
+        t = small_triangles(400, 6, -2.2, 2.2, 0.3)
+        t[..., 2] = 0.6 * t[..., 2] + 0.7
+        c = rng.uniform(-1.5, 1.5, (60, 1, 3)) * [1.0, 1.0, 0.5] + [0.0, 0.0, 0.75]
+        a = rng.normal(size=(60, 1, 3)) * [1.0, 1.0, 0.2]
+        sliver = c + a * np.float64([0.0, 1.0, 0.5]).reshape(1, 3, 1) + rng.normal(scale=1e-4, size=(60, 3, 3))
+        occluders = [soup_mesh(np.concatenate([t, sliver]))]
+    return scene_of("probe_" + which, [floor] + occluders, eye=(0.0, 0.0, EYE_Z), target=(0.0, 0.0, FLOOR_Z), fov=2.0 * np.degrees(np.arctan(FLOOR_HALF * 0.98 / (EYE_Z - FLOOR_Z))),
+                    sky_enabled=0, lights_enabled=0, sun_shadow_enabled=1, num_bounces=1)
+
+
+# suns above the floor (z > 0): overhead, oblique in three octants, nearly overhead, low, one with a component of 1e-30
+PROBE_SUNS = {"overhead": (0.0, 0.0, 1.0), "oblique": (0.3, 0.2, 0.8), "oblique_n": (-0.5, 0.1, 0.85), "diag_xz": (0.7, 0.0, 0.7), "near_z": (1e-4, 0.0, 1.0),
+              "low": (0.6, 0.02, 0.5), "tiny": (1e-30, 0.6, 0.8)}
+
+
+def soak_direction(seed):
+    """tools/soak_sun_grid.py's draw: a normal direction, a quarter of them with one component zeroed (walls edge-on), 15 % snapped
+    to an axis"""
+    rng = np.random.default_rng(seed)
+    d = rng.normal(size=3)
+    if rng.random() < 0.25:
+        d[int(rng.integers(0, 3))] = 0.0
+    if rng.random() < 0.15:
+        d = np.sign(d) * (np.abs(d) > np.abs(d).max() - 1e-9)
+    return tuple(float(x) for x in d / np.linalg.norm(d))

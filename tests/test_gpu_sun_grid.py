@@ -198,10 +198,8 @@ def test_tile_partition_and_batches_with_the_grid(atrium):
     assert list(ref.get_stats().rays) == list(group.get_stats().rays)
 
 
-def test_scene_deeper_than_tmax_along_the_sun():
-    """ADVICE r3: the cell's cover depth must respect the rays' tmax = 10000 (rgen:45,66-67). A floor at y = 0 under a roof at
-    y = 20000 with the sun straight up: the roof covers every cell, but a ray from the floor would meet it at t = 19999 > tmax -
-    the tree walk and the oracle leave the floor lit, and so must the grid. A slab at y = 8000 does shade its part of the floor."""
+def deep_scene():
+    """a floor at y = 0 under a roof at y = 20000 and a slab at y = 8000 (also a case of test_gpu_sun_grid_builders.py)"""
     from rust_renderer_amd.scenes import Mesh, Model, Scene, quad
     from rust_renderer_amd.camera import Camera
 
@@ -209,7 +207,14 @@ def test_scene_deeper_than_tmax_along_the_sun():
               Mesh(*quad((-40, 20000, -40), (80, 0, 0), (0, 0, 80), 1, 1), base_color=(0.5, 0.5, 0.5, 1.0), name="roof"),
               Mesh(*quad((-1, 8000, -1), (2, 0, 0), (0, 0, 2), 1, 1), base_color=(0.5, 0.5, 0.5, 1.0), name="slab")]
     cam = Camera((0.0, 6.0, 7.0), (0.0, 0.0, 0.0), 60.0, 1.0, 0.01, 1000.0)
-    scene = Scene("deep", [(Model(meshes, []), None)], [], cam, dict(sky_enabled=0, sun_shadow_enabled=1, lights_enabled=0, num_bounces=2))
+    return Scene("deep", [(Model(meshes, []), None)], [], cam, dict(sky_enabled=0, sun_shadow_enabled=1, lights_enabled=0, num_bounces=2))
+
+
+def test_scene_deeper_than_tmax_along_the_sun():
+    """ADVICE r3: the cell's cover depth must respect the rays' tmax = 10000 (rgen:45,66-67). A floor at y = 0 under a roof at
+    y = 20000 with the sun straight up: the roof covers every cell, but a ray from the floor would meet it at t = 19999 > tmax -
+    the tree walk and the oracle leave the floor lit, and so must the grid. A slab at y = 8000 does shade its part of the floor."""
+    scene = deep_scene()
     W, H = 96, 96
     grid = scene.upload(rr.Renderer(W, H))
     grid.set_option("sun_grid_force", 1)  # margins at |y| = 20000 are half a unit wide: long lists, and this test wants the grid

@@ -1,5 +1,7 @@
 """Soak for the sun grid (cover depth, margins, fall-back): random sun directions over several scenes, the grid against the tree
-walk it replaces - accumulation bit for bit and ray counts - on the GPU. Not part of the test suite.
+walk it replaces - accumulation bit for bit and ray counts - on the GPU. Not part of the test suite: its bounded form is
+tests/test_gpu_sun_grid_builders.py::test_soak_directions_grid_equals_tree (twelve of these directions on the small cornell scene;
+the same module holds the device builder to the host builder and the walk to brute force on adversarial geometry).
 usage (GPU box): [UH_SOAK_OPTS=name=value,...] python tools/soak_sun_grid.py [first_seed] [count]   (the options go to the grid's renderer)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
