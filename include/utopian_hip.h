@@ -242,7 +242,8 @@ typedef struct uh_ctx uh_ctx;
  *        view->rebuild_tlas), uh_set_tile_partition, uh_set_restir_partition, uh_rccl_attach / uh_rccl_detach, uh_pack_tiles,
  *        uh_unpack_tiles, uh_compose_tiles, uh_resolve_output, uh_add_isosurface_mesh, uh_update_isosurface_mesh (it reads the
  *        triangle total, 8 bytes, back to size its buffers), uh_get_isosurface_update_stats, uh_update_mesh_vertices (device input:
- *        it reads a 4-byte verdict on the caller's buffer back before it takes it), uh_get_mesh_update_stats, uh_destroy;
+ *        it reads a 4-byte verdict on the caller's buffer back before it takes it), uh_get_mesh_update_stats, uh_read_denoised,
+ *        uh_get_denoise_stats, uh_reset_denoise_history, uh_destroy;
  *   enqueues like a frame, ordered behind the frames in flight and before those that follow:  uh_rccl_gather_tiles, uh_mgpu_compose;
  *        uh_set_option for "frames_in_flight" and for "time_kernels" 1 -> 0 (the others only change what the NEXT enqueued
  *        frame does: "furnace", "sun_grid*", "camera_grid*", "overlap", "batch_frames", "trace_blocks_per_cu", "count_visits",
@@ -258,6 +259,7 @@ typedef struct uh_ctx uh_ctx;
  *        only, and are complete on return;
  *   uh_render_hybrid enqueues like a frame, ordered behind the frames in flight and before those that follow (on the context's first
  *        stream, after a wait for the others); uh_read_hybrid and uh_get_hybrid_stats wait and are complete on return.
+ *   uh_denoise enqueues like uh_render_hybrid; a frame enqueued after it accumulates behind its read of the accumulation image.
  * The sun-direction grid and the camera grid are (re)built inside the first frame call that wants them, after a wait for the frames in flight. */
 
 /* ---- lifetime -------------------------------------------------------------------------- */
@@ -1026,6 +1028,79 @@ UH_LAYOUT_ASSERT(sizeof(UhHybridRestirStats) == 32 && offsetof(UhHybridRestirSta
                     offsetof(UhHybridRestirStats, reserved) == 20,
                  "UhHybridRestirStats (32 B)");
 int uh_get_hybrid_restir_stats(uh_ctx* ctx, UhHybridRestirStats* out);
+
+/* ---- the denoiser: reprojected history and a variance-guided a-trous filter over a path-traced frame ------------------------------------
+ * An EXTENSION: the reference has no denoiser. uh_denoise is SVGF (Schied et al. 2017) cut short: temporal accumulation of colour and
+ * luminance moments through view->prev_frame_projection_view, a spatial variance estimate where the history is shorter than 4 frames,
+ * and `iterations` levels of an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) guided by normals, plane distance and
+ * luminance over that variance. Per-context verbs: no uh_mgpu_ twin.
+ * INPUTS, all already on the device: the accumulation image as the last uh_render_frame left it, divided by
+ * n = min(view->total_samples, view->accumulation_limit) (reference.rgen:140), and the hybrid G-buffer (position, normal, albedo, and the
+ * mesh index in pbr.a) of the last uh_render_hybrid(..., UH_HYBRID_GBUFFER ...). Rendering both with the SAME CAMERA as `view` is the
+ * caller's job: nothing checks it. A caller that wants one frame's samples renders each frame with total_samples = samples_per_frame
+ * (the reference's own protocol after a camera move); the filter takes the accumulation for what it is. A pixel is geometry when its
+ * position texel has w != 0; every other pixel passes through unchanged, is never a tap, and has history 0 and variance 0.
+ * view->prev_frame_projection_view is projection * view of the previous uh_denoise call; view->view gives the depth the plane
+ * tolerances scale with.
+ * HISTORY: the call keeps its own copies of this frame's position, normal with the mesh index beside it, temporal colour, history
+ * length and moments for the next call (the hybrid targets are overwritten by then). The scene is assumed static between calls: after
+ * uh_update_isosurface_mesh / uh_update_mesh_vertices / uh_set_instance_transform with a refit, call uh_reset_denoise_history, or accept
+ * ghosting on the moved mesh. Without UH_DENOISE_TEMPORAL every call starts from no history (and still leaves one).
+ * UH_ERR_INVALID_ARGUMENT with a message - nothing runs, the history is untouched: a null view or params; no hybrid G-buffer rendered
+ * yet; n == 0; iterations > 5; a non-zero reserved word; unknown flag bits; a parameter outside its range (below) or not finite; a
+ * tile partition with world > 1 is set (uh_set_tile_partition: the accumulation is then partial). UH_ERR_NOT_BUILT before
+ * uh_build_acceleration, as for a frame.
+ * ISOLATION: the call changes no accumulation, reservoir, gbuffer_position, hybrid image, grid or UhStats.
+ * RESOURCES: 204 bytes per pixel (two history sets of 56, two filter images of 16, the input, temporal and colour images of 16, the
+ * 8-bit image, history length and variance of 4 each), allocated by the first uh_denoise (UH_ERR_OUT_OF_MEMORY when that fails) and
+ * freed by uh_destroy. A context that never calls uh_denoise allocates nothing for it.
+ * STREAM ORDER: uh_denoise enqueues like uh_render_hybrid (behind the frames in flight, on the context's first stream; a frame enqueued
+ * later accumulates behind the call's read of the accumulation). uh_read_denoised, uh_get_denoise_stats and uh_reset_denoise_history
+ * wait and are complete on return.
+ * Arithmetic: DESIGN.md section 2, "Denoiser: the arithmetic contract of uh_denoise". */
+enum { UH_DENOISE_TEMPORAL = 1u << 0, UH_DENOISE_DEMODULATE = 1u << 1 };
+typedef struct UhDenoiseParams {
+   uint32_t flags;             /* UH_DENOISE_* */
+   uint32_t iterations;        /* a-trous levels, 0..5; level i has step 2^i */
+   uint32_t max_history;       /* >= 1; default 32 */
+   float alpha_min;            /* [0, 1]; default 0.2 (SVGF) */
+   float sigma_luminance;      /* > 0; default 4 (SVGF) */
+   float sigma_plane;          /* > 0; plane distance tolerated, as a fraction of view depth; default 0.005 */
+   float reproject_normal_cos; /* [-1, 1]; default 0.9 */
+   float reproject_plane;      /* > 0; the same fraction, for history taps; default 0.005 */
+   uint32_t reserved[4];       /* must be 0 */
+} UhDenoiseParams;
+UH_LAYOUT_ASSERT(sizeof(UhDenoiseParams) == 48 && offsetof(UhDenoiseParams, iterations) == 4 && offsetof(UhDenoiseParams, max_history) == 8 &&
+                    offsetof(UhDenoiseParams, alpha_min) == 12 && offsetof(UhDenoiseParams, sigma_luminance) == 16 &&
+                    offsetof(UhDenoiseParams, sigma_plane) == 20 && offsetof(UhDenoiseParams, reproject_normal_cos) == 24 &&
+                    offsetof(UhDenoiseParams, reproject_plane) == 28 && offsetof(UhDenoiseParams, reserved) == 32,
+                 "UhDenoiseParams (48 B)");
+/* which image uh_read_denoised copies out (W*H texels each), all of the last uh_denoise call */
+enum {
+   UH_DENOISE_COLOR = 0,          /* RGBA32F: the filtered colour, linear, alpha 0 like the accumulation */
+   UH_DENOISE_OUTPUT = 1,         /* 8 bits x 4 channels, B G R A: the filtered colour through the path tracer's linearToSrgb and packing */
+   UH_DENOISE_INPUT = 2,          /* RGBA32F: what the filter read (accumulation / n, demodulated on geometry with UH_DENOISE_DEMODULATE) */
+   UH_DENOISE_TEMPORAL_COLOR = 3, /* RGBA32F: the colour after the temporal stage, remodulated */
+   UH_DENOISE_HISTORY = 4,        /* float32: history length N (0 where not geometry) */
+   UH_DENOISE_VARIANCE = 5        /* float32: the variance level 0 of the filter read */
+};
+/* the last uh_denoise call: pass_ms the hipEvent time of its stages (input + temporal, variance estimate, all a-trous levels, output),
+ * geometry_pixels the pixels whose position texel has w != 0, history_pixels those of them that kept a history (a valid reprojection).
+ * All zero before the first call. Waits for all work of the context. */
+typedef struct UhDenoiseStats {
+   float pass_ms[4];
+   uint32_t geometry_pixels;
+   uint32_t history_pixels;
+   uint32_t reserved[2];
+} UhDenoiseStats;
+UH_LAYOUT_ASSERT(sizeof(UhDenoiseStats) == 32 && offsetof(UhDenoiseStats, geometry_pixels) == 16 && offsetof(UhDenoiseStats, history_pixels) == 20 &&
+                    offsetof(UhDenoiseStats, reserved) == 24,
+                 "UhDenoiseStats (32 B)");
+int uh_denoise_default_params(UhDenoiseParams* out); /* needs no GPU; UH_ERR_INVALID_ARGUMENT for NULL */
+int uh_denoise(uh_ctx* ctx, const UhViewUniformData* view, const UhDenoiseParams* params);
+int uh_reset_denoise_history(uh_ctx* ctx);           /* the next uh_denoise starts from no history */
+int uh_read_denoised(uh_ctx* ctx, int which, void* out); /* UH_ERR_INVALID_ARGUMENT before the first uh_denoise */
+int uh_get_denoise_stats(uh_ctx* ctx, UhDenoiseStats* out);
 
 #ifdef __cplusplus
 }

@@ -346,6 +346,28 @@ class Renderer {
       check(uh_get_hybrid_restir_stats(ctx_, &s), "hybrid_restir_stats");
       return s;
    }
+   // the denoiser (utopian_hip.h "the denoiser"): the accumulation of the last render_frame over the G-buffer of the last render_hybrid,
+   // both rendered with view's camera by the caller; view.prev_frame_projection_view is projection * view of the previous call
+   static UhDenoiseParams default_denoise_params() {
+      UhDenoiseParams p;
+      if (uh_denoise_default_params(&p) != UH_OK) throw Error(UH_ERR_INVALID_ARGUMENT, "uh_denoise_default_params");
+      return p;
+   }
+   void denoise(const UhViewUniformData& view, const UhDenoiseParams& params) { check(uh_denoise(ctx_, &view, &params), "denoise"); }
+   void denoise(const UhViewUniformData& view) { denoise(view, default_denoise_params()); }
+   // one image of the last denoise as bytes: W*H texels of 16 (colour, input, temporal colour) or 4 (the 8-bit output, history, variance) bytes
+   std::vector<uint8_t> read_denoised(int which) {
+      const size_t texel = (which == UH_DENOISE_OUTPUT || which == UH_DENOISE_HISTORY || which == UH_DENOISE_VARIANCE) ? 4 : 16;
+      std::vector<uint8_t> out((size_t)width_ * height_ * texel);
+      check(uh_read_denoised(ctx_, which, out.data()), "read_denoised");
+      return out;
+   }
+   void reset_denoise_history() { check(uh_reset_denoise_history(ctx_), "reset_denoise_history"); }
+   UhDenoiseStats denoise_stats() {
+      UhDenoiseStats s;
+      check(uh_get_denoise_stats(ctx_, &s), "denoise_stats");
+      return s;
+   }
    // one face and mip of an IBL map built with UH_HYBRID_ENVIRONMENT (utopian_hip.h "uh_read_environment"): (512 >> mip)^2 texels of
    // 4 floats for the cubes, 512^2 pairs of IEEE half floats (as uint16_t bits) for the BRDF LUT
    std::vector<float> read_environment(int which, int face = 0, int mip = 0) {

@@ -7,6 +7,7 @@ from .api import (  # noqa: F401
     MultiGpuRenderer,
     Renderer,
     UtopianError,
+    default_denoise_params,
     default_view,
     hip_versions,
     identity3x4,

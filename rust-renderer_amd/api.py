@@ -22,6 +22,14 @@ from .types import (
     RESTIR_EXCHANGE_FN,
     VERTEX_DTYPE,
     BRDF_LUT_SIZE,
+    DENOISE_COLOR,
+    DENOISE_HISTORY,
+    DENOISE_INPUT,
+    DENOISE_OUTPUT,
+    DENOISE_TEMPORAL_COLOR,
+    DENOISE_VARIANCE,
+    DenoiseParams,
+    DenoiseStats,
     ENV_BRDF_LUT,
     ENV_ENVIRONMENT,
     ENV_IRRADIANCE,
@@ -588,6 +596,49 @@ class Renderer:
         self._check(fn(self._ctx, C.byref(s)))
         return s
 
+    # -- the denoiser (uh_denoise; include/utopian_hip.h "the denoiser") --------------------
+    def _denoise_fn(self, name, argtypes):
+        if self.backend != "hip":
+            raise NotImplementedError(f"the denoiser is a per-context verb of the HIP library; backend {self.backend!r} has none")
+        fn = getattr(self._lib, "uh_" + name)
+        fn.argtypes, fn.restype = [C.c_void_p] + argtypes, C.c_int
+        return fn
+
+    def denoise(self, view, params=None):
+        """uh_denoise on the accumulation of the last render_frame and the G-buffer of the last render_hybrid (same camera as `view`:
+        the caller's job); view.prev_frame_projection_view is projection * view of the previous call. params None: the defaults"""
+        params = default_denoise_params() if params is None else params
+        self._check(self._denoise_fn("denoise", [C.POINTER(ViewUniformData), C.POINTER(DenoiseParams)])(self._ctx, C.byref(view), C.byref(params)))
+
+    _DENOISE_IMAGES = {
+        DENOISE_COLOR: (np.float32, 4),
+        DENOISE_OUTPUT: (np.uint8, 4),
+        DENOISE_INPUT: (np.float32, 4),
+        DENOISE_TEMPORAL_COLOR: (np.float32, 4),
+        DENOISE_HISTORY: (np.float32, 1),
+        DENOISE_VARIANCE: (np.float32, 1),
+    }
+
+    def read_denoised(self, which):
+        """one image of the last denoise call: (H, W, 4) float32 colour / input / temporal colour, (H, W, 4) uint8 output (B, G, R, A),
+        (H, W) float32 history length / variance"""
+        fn = self._denoise_fn("read_denoised", [C.c_int, C.c_void_p])
+        if which not in self._DENOISE_IMAGES:
+            raise ValueError(f"denoiser image index {which} (0..5)")
+        dtype, ch = self._DENOISE_IMAGES[which]
+        out = np.empty((self.height, self.width, ch) if ch > 1 else (self.height, self.width), dtype=dtype)
+        self._check(fn(self._ctx, int(which), out.ctypes.data))
+        return out
+
+    def reset_denoise_history(self):
+        self._check(self._denoise_fn("reset_denoise_history", [])(self._ctx))
+
+    def denoise_stats(self):
+        """UhDenoiseStats of the last denoise call: pass_ms of its four stages, geometry pixels, pixels that kept a history"""
+        s = DenoiseStats()
+        self._check(self._denoise_fn("get_denoise_stats", [C.POINTER(DenoiseStats)])(self._ctx, C.byref(s)))
+        return s
+
     # -- cascaded shadow maps (UH_HYBRID_SHADOW_MAPS; include/utopian_hip.h) ---------------
     def _shadow_fn(self, name, argtypes):
         self._hybrid_api()
@@ -828,6 +879,16 @@ class MultiGpuRenderer(Renderer):
 
     def compose(self):
         self._check(self._lib.uh_mgpu_compose(self._ctx))
+
+
+def default_denoise_params():
+    """UhDenoiseParams as uh_denoise_default_params fills it (needs no GPU)"""
+    fn = load_library().uh_denoise_default_params
+    fn.argtypes, fn.restype = [C.POINTER(DenoiseParams)], C.c_int
+    p = DenoiseParams()
+    if fn(C.byref(p)) != 0:
+        raise UtopianError("uh_denoise_default_params failed")
+    return p
 
 
 def compose3x4(a, b):

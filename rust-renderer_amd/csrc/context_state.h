@@ -513,6 +513,25 @@ struct uh_ctx {
       uint32_t renders = 0, pieces = 0, lights_used = 0;
       template <class F> void images(size_t n, F&& f) { target.each(n, f), f(present, n), f(lights, UH_MAX_GPU_LIGHTS + 1), f(color, n); }
    } fw;
+
+   // the denoiser (uh_denoise): two history sets (the previous call's, read, and this call's, written), the filter's two images and the
+   // images uh_read_denoised copies out, all allocated by the first call; counters: geometry pixels, pixels that kept a history
+   struct Denoise {
+      DevBuf<float4> h_pos[2], h_nrm[2], h_col[2], cv[2], input, temporal, color;
+      DevBuf<float2> h_mom[2];
+      DevBuf<float> history, variance;
+      DevBuf<uchar4> output;
+      DevBuf<uint32_t> counters;
+      Stage stage[4];                          // input + temporal, variance estimate, the a-trous levels, output (the last call's)
+      hipEvent_t acc_read = nullptr;           // behind the call's read of the accumulation image (the next frame's tail waits for it)
+      int cur = 0;                             // the set the next call writes
+      bool have_history = false;
+      uint32_t calls = 0;
+      template <class F> void images(size_t n, F&& f) {
+         for (int k = 0; k < 2; k++) f(h_pos[k], n), f(h_nrm[k], n), f(h_col[k], n), f(h_mom[k], n), f(cv[k], n);
+         f(input, n), f(temporal, n), f(color, n), f(history, n), f(variance, n), f(output, n), f(counters, 2);
+      }
+   } dn;
 };
 
 // ---- context.hip, for scene_build.hip and graphs.hip (not exported: the library's dynamic symbols stay the C ABI's) ----
@@ -533,5 +552,5 @@ int read_back(uh_ctx* c, void* dst, const void* src, size_t bytes);
 void iso_scatter_begin(uh_ctx* c);
 int iso_scatter_end(uh_ctx* c, bool add);
 // ---- graphs.hip, for uh_destroy ----
-void destroy_graphs(uh_ctx* c);  // everything uh_ctx::Hybrid and uh_ctx::Forward own; before the slots' streams go
+void destroy_graphs(uh_ctx* c);  // everything uh_ctx::Hybrid, uh_ctx::Forward and uh_ctx::Denoise own; before the slots' streams go
 #pragma GCC visibility pop

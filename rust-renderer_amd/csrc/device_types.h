@@ -260,6 +260,35 @@ struct HybridRestirDev {
    uint32_t num_lights;            // view.num_lights, at most the table's length
 };
 
+// the denoiser (uh_denoise; denoise.hip): one frame's guides and moments as the next call's history reads them
+struct DenoiseHistory {
+   float4* pos;                    // the position texel (w != 0: geometry)
+   float4* nrm;                    // the normal texel's xyz, w = the mesh index (pbr.a)
+   float4* col;                    // temporal colour (demodulated), w = history length N
+   float2* mom;                    // temporal first and second luminance moments
+};
+struct DenoiseDev {
+   const float4* acc;              // the path tracer's accumulation image (read only)
+   const float4 *g_pos, *g_nrm, *g_pbr;  // the hybrid G-buffer (read only)
+   const uchar4* g_alb;
+   const float* unorm_lut;         // c / 255
+   DenoiseHistory prev, cur;       // the previous call's set (read) and this call's (written by the temporal stage)
+   float4* input;                  // UH_DENOISE_INPUT
+   float4* cv[2];                  // the filter's images: colour and variance, ping-pong; the temporal stage writes cv[0]
+   float4* temporal;               // UH_DENOISE_TEMPORAL_COLOR
+   float4* color;                  // UH_DENOISE_COLOR
+   uchar4* output;                 // UH_DENOISE_OUTPUT
+   float* history;                 // UH_DENOISE_HISTORY
+   float* variance;                // UH_DENOISE_VARIANCE
+   uint32_t* counters;             // [0] geometry pixels, [1] pixels that kept a history
+   uint32_t W, H;
+   float n;                        // min(total_samples, accumulation_limit)
+   float view[16], prev_pv[16];    // column-major
+   uint32_t temporal_on;           // UH_DENOISE_TEMPORAL and a history exists
+   uint32_t demodulate;
+   float max_history, alpha_min, sigma_luminance, sigma_plane, reproject_normal_cos, reproject_plane;
+};
+
 // launch wrappers implemented in kernels.hip, path_fused.hip, restir.hip, tiles.hip and hybrid_kernels.hip --------------------------------------------------
 struct LaunchCfg {
    hipStream_t stream;
@@ -411,6 +440,12 @@ void launch_gbuffer_raster_shade(const LaunchCfg&, const SceneDev&, const Forwar
 // the marching-cubes pass's depth buffer from the G-buffer positions, into fd.depth; P V column-major at fd.mats + 28
 void launch_mc_depth_seed(const LaunchCfg&, const float4* gbuffer_pos, const ForwardDev&);
 void launch_hybrid_light_prep(const LaunchCfg&, const HybridFrameDev&);
+// the denoiser's stages (denoise.hip): input + temporal (counters zeroed by the caller), the short-history variance estimate, one
+// a-trous level of step 1 << level from cv[level & 1] into cv[~level & 1], and the output from cv[from]
+void launch_denoise_temporal(const LaunchCfg&, const DenoiseDev&);
+void launch_denoise_variance(const LaunchCfg&, const DenoiseDev&);
+void launch_denoise_atrous(const LaunchCfg&, const DenoiseDev&, uint32_t level);
+void launch_denoise_output(const LaunchCfg&, const DenoiseDev&, uint32_t from);
 // tiles
 // on-device refit (refit.hip): per-mesh object->world rows, and what one refit pass touches
 struct RefitMesh {

@@ -337,3 +337,32 @@ class HybridRestirStats(C.Structure):
 
 assert C.sizeof(HybridRestirStats) == 32 and HybridRestirStats.occluded.offset == 8 and HybridRestirStats.pass_ms.offset == 16 and \
     HybridRestirStats.reserved.offset == 20
+
+
+# the denoiser (an extension; utopian_hip.h "the denoiser"): uh_denoise's flags, the images of uh_read_denoised, params and stats
+DENOISE_TEMPORAL, DENOISE_DEMODULATE = 1 << 0, 1 << 1
+DENOISE_COLOR, DENOISE_OUTPUT, DENOISE_INPUT, DENOISE_TEMPORAL_COLOR, DENOISE_HISTORY, DENOISE_VARIANCE = range(6)
+
+
+class DenoiseParams(C.Structure):
+    """UhDenoiseParams: flags (DENOISE_*), a-trous levels (0..5), the history cap, the smallest blend factor, the luminance and plane
+    tolerances of the filter, and the normal and plane tolerances of a history tap; uh_denoise_default_params fills the defaults"""
+
+    _fields_ = [("flags", C.c_uint32), ("iterations", C.c_uint32), ("max_history", C.c_uint32), ("alpha_min", C.c_float),
+                ("sigma_luminance", C.c_float), ("sigma_plane", C.c_float), ("reproject_normal_cos", C.c_float), ("reproject_plane", C.c_float),
+                ("reserved", C.c_uint32 * 4)]
+
+
+assert C.sizeof(DenoiseParams) == 48 and DenoiseParams.alpha_min.offset == 12 and DenoiseParams.reproject_plane.offset == 28 and \
+    DenoiseParams.reserved.offset == 32
+
+
+class DenoiseStats(C.Structure):
+    """UhDenoiseStats: the last uh_denoise call - hipEvent ms of (input + temporal, variance estimate, a-trous levels, output), the
+    geometry pixels and those of them that kept a history"""
+
+    _fields_ = [("pass_ms", C.c_float * 4), ("geometry_pixels", C.c_uint32), ("history_pixels", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+assert C.sizeof(DenoiseStats) == 32 and DenoiseStats.geometry_pixels.offset == 16 and DenoiseStats.history_pixels.offset == 20 and \
+    DenoiseStats.reserved.offset == 24
