@@ -328,12 +328,16 @@ int uh_trace_any(uh_ctx* ctx, const float* rays, uint32_t n, uint8_t* out_occlud
 /* ---- stats / options ------------------------------------------------------------------- */
 int uh_get_stats(uh_ctx* ctx, UhStats* out);
 int uh_reset_stats(uh_ctx* ctx);
-/* The 26 options (DESIGN.md section 7 has the defaults and what was measured); unknown names return UH_ERR_INVALID_ARGUMENT.
+/* The 27 options (DESIGN.md section 7 has the defaults and what was measured); unknown names return UH_ERR_INVALID_ARGUMENT.
  *  diagnostics   "count_visits" (0/1: UhStats' node / triangle / cover counters), "time_kernels" (0/1: hipEvent time per kernel kind)
  *  results       "full_frame_restir" (0/1; 1 = documented divergence: the reservoir for every pixel instead of the reference's
  *                x > W/2 split), "furnace" (0/1: the reference's FURNACE_TEST build of the miss shader, reference.rmiss:14-28 - a path
  *                ray that leaves the scene returns white whatever view->sky_enabled says), "iso_reference_triangulation" (0/1,
  *                default 1: see uh_add_isosurface_mesh)
+ *  textures      "texture_blocks" (0/1, default 1: uh_add_texture_rgba8 stores the textures added from now on as overlapped blocks of
+ *                texels, one block per cache line, so that a bilinear footprint lies in one line - about 1.5 times the texels'
+ *                memory; 0: as 8x8-texel tiles, or as rows when a side is no multiple of 8. Same images bit for bit. With 1 a texture
+ *                whose blocks would hold more than 2^32 texels is refused with UH_ERR_CAPACITY)
  *  the tree      "device_build" (0/1/2; 1 or 2 = uh_build_acceleration builds the tree ON THE DEVICE in a few ms instead of the host
  *                SAH tree in tens to hundreds: same hits bit for bit, about 10 % (1: clusters under a SAH top) or 30 % (2: radix tree)
  *                more traversal work per ray - for geometry that changes every few frames), "ploc_sah_top" (clusters the PLOC rounds

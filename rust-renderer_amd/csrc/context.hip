@@ -24,6 +24,7 @@
 #include "context_state.h"
 #include "device_scan.h"
 #include "device_types.h"
+#include "texture_layout.h"
 #include "utopian_hip.h"
 
 using namespace uh;
@@ -274,28 +275,38 @@ void uh_destroy(uh_ctx* c) {
 int uh_add_texture_rgba8(uh_ctx* c, const uint8_t* pixels, uint32_t w, uint32_t h, uint32_t* out_index) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    if (!pixels || !w || !h) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_add_texture_rgba8: null or empty texture");
-   HIP_TRY(c, hipSetDevice(c->device));
-   uchar4* dev = nullptr;
-   HIP_TRY(c, hipMalloc((void**)&dev, (size_t)w * h * 4));
-   // 8x8-texel tiles when the size allows (device_types.h TexInfo)
-   const uint32_t tiles_x = (w % 8 == 0 && h % 8 == 0) ? w / 8 : 0;
-   std::vector<uint8_t> tiled;
+   // Overlapped blocks, one per cache line (texture_layout.h), whatever the size; with option "texture_blocks" 0: 8x8-texel tiles
+   // when both sides are multiples of 8, rows otherwise (device_types.h TexInfo)
+   size_t texels = (size_t)w * h;
+   uint32_t tiles_x = 0, blocks_x = 0;
+   std::vector<uint8_t> packed;
    const uint8_t* src = pixels;
-   if (tiles_x) {
-      tiled.resize((size_t)w * h * 4);
+   if (c->texture_blocks) {
+      if (TexLayout::texel_count(w, h, &texels) != UH_OK)
+         return fail(c, UH_ERR_CAPACITY, "uh_add_texture_rgba8: the blocked texture would hold more than 2^32 texels (option texture_blocks = 0 stores it as it is)");
+      blocks_x = (uint32_t)TexLayout::blocks_x(w);
+      packed.resize(texels * 4);
+      TexLayout::repack(pixels, w, h, packed.data());
+      src = packed.data();
+   } else if (w % 8 == 0 && h % 8 == 0) {
+      tiles_x = w / 8;
+      packed.resize(texels * 4);
       for (uint32_t y = 0; y < h; y++)
          for (uint32_t x = 0; x < w; x++) {
             size_t at = ((size_t)((y >> 3) * tiles_x + (x >> 3)) << 6) + ((y & 7) << 3) + (x & 7);
-            std::memcpy(&tiled[at * 4], &pixels[((size_t)y * w + x) * 4], 4);
+            std::memcpy(&packed[at * 4], &pixels[((size_t)y * w + x) * 4], 4);
          }
-      src = tiled.data();
+      src = packed.data();
    }
-   hipError_t e = hipMemcpy(dev, src, (size_t)w * h * 4, hipMemcpyHostToDevice);
+   HIP_TRY(c, hipSetDevice(c->device));
+   uchar4* dev = nullptr;
+   HIP_TRY(c, hipMalloc((void**)&dev, texels * 4));
+   hipError_t e = hipMemcpy(dev, src, texels * 4, hipMemcpyHostToDevice);
    if (e != hipSuccess) {
       (void)hipFree(dev);
       return fail(c, UH_ERR_HIP, std::string("texture upload: ") + hipGetErrorString(e));
    }
-   c->textures.push_back(uh_ctx::HostTex{w, h, dev, tiles_x});
+   c->textures.push_back(uh_ctx::HostTex{w, h, dev, tiles_x, blocks_x});
    c->built = false;
    if (out_index) *out_index = (uint32_t)c->textures.size() - 1;
    return UH_OK;
@@ -1357,6 +1368,10 @@ int uh_set_option(uh_ctx* c, const char* name, int value) {
       c->iso_reference = value != 0;
    else if (n == "furnace")
       c->furnace = value != 0;  // applies to the frames enqueued from now on
+   else if (n == "texture_blocks")
+      // 1: the textures added from now on are stored as overlapped blocks, a bilinear footprint in one cache line (texture_layout.h);
+      // 0: as 8x8 tiles, or rows. Same images bit for bit: the same four texel words enter the filter
+      c->texture_blocks = value != 0;
    else if (n == "shadow_map_size") {
       if (!range(16, 8192)) return bad("must be 16..8192");
       if ((uint32_t)value != c->shadow_map_size) {  // the maps go: the deferred pass with shadows is refused until they are rendered again

@@ -277,6 +277,7 @@ struct uh_ctx {
    static constexpr uint32_t kFusedMaxPaths = 4u << 20;
    uint32_t fused_blocks_per_cu = 4;
    static constexpr uint32_t kSingleFrameBlocksPerCu = 4;  // the cap on both for a wavefront of one frame (fewer persistent waves reach the end of a small launch's tail sooner: round 4's sweep)
+   bool texture_blocks = true;  // option "texture_blocks": how uh_add_texture_rgba8 lays the next textures out
    std::string err;
 
    // host scene
@@ -285,7 +286,8 @@ struct uh_ctx {
    struct HostTex {
       uint32_t w, h;
       uchar4* dev;
-      uint32_t tiles_x;  // 0 = row-major
+      uint32_t tiles_x;   // 8x8 tiles per row; 0 = not tiled
+      uint32_t blocks_x;  // overlapped blocks per row (texture_layout.h); 0 = not blocked: tiles, or rows when tiles_x is 0 too
    };
    std::vector<HostTex> textures;
    bool built = false;

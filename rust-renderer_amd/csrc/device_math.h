@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_types.h"
+#include "texture_layout.h"
 
 namespace uh {
 
@@ -224,12 +225,7 @@ __device__ __forceinline__ TexInfo lds_fetch(const TexInfo* lds) {
 }
 
 // ---- texture sampling (utopian/src/texture.rs:85-98: RGBA8 UNORM, LINEAR, MIRRORED_REPEAT) ---
-__device__ __forceinline__ int mirror_index(int i, int n) {
-   int period = 2 * n;
-   int m = i % period;
-   if (m < 0) m += period;
-   return m < n ? m : period - 1 - m;
-}
+// mirror_index: texture_layout.h (shared with the host check of the blocked layout)
 // lds_tex (may be null): the first n_lds_tex texture descriptors staged in LDS by the caller
 // `pre` is called exactly once, right before the four texels are requested (or before an early return): what it requests
 // is in flight TOGETHER with the texels. k_shade_hit asks for its scattered paths' queue positions there (a returning atomic) and,
@@ -259,28 +255,46 @@ __device__ __forceinline__ V3 sample_texture_pre(const SceneDev& sc, const float
    float ax = x - fx, ay = y - fy;
    int x0 = mirror_index((int)fx, (int)t.w), x1 = mirror_index((int)fx + 1, (int)t.w);
    int y0 = mirror_index((int)fy, (int)t.h), y1 = mirror_index((int)fy + 1, (int)t.h);
-   // the four texel addresses first (branch-free: a branch per texel put a wait behind every fetch and the four
-   // fetches ran one after the other), then the four fetches together, then the table look-ups
+   // Blocked textures (texture_layout.h, TexInfo::blocks_x != 0): the footprint's four texels lie in ONE block - one cache line -, as
+   // the 2 x 2 at the block position of (min(x0, x1), min(y0, y1)): two 8-byte loads, one per row, and the four words picked by where
+   // x0, x1, y0, y1 stand against the minima (x1 - x0 and y1 - y0 are -1, 0 or +1 under mirrored repeat).
+   // Otherwise the four texel addresses first (branch-free: a branch per texel put a wait behind every fetch and the four
+   // fetches ran one after the other), then the four fetches together. Then the table look-ups.
+   const bool blocked = t.blocks_x != 0;
+   const int mx = x0 < x1 ? x0 : x1, my = y0 < y1 ? y0 : y1;
    const bool tiled = t.tiles_x != 0;
    auto address = [&](int xx, int yy) {
       const uint32_t in_tiles = ((uint32_t)((yy >> 3) * (int)t.tiles_x + (xx >> 3)) << 6) + (uint32_t)(((yy & 7) << 3) + (xx & 7));
       const uint32_t in_rows = (uint32_t)yy * t.w + (uint32_t)xx;
       return tiled ? in_tiles : in_rows;
    };
-   const uchar4* q00 = t.texels + address(x0, y0);
-   const uchar4* q10 = t.texels + address(x1, y0);
-   const uchar4* q01 = t.texels + address(x0, y1);
-   const uchar4* q11 = t.texels + address(x1, y1);
+   const uchar4* q00 = t.texels + (blocked ? TexLayout::footprint_offset(t.blocks_x, (uint32_t)mx, (uint32_t)my) : address(x0, y0));
    // one block: as four C++ loads the compiler still made the third wait for the first (register reuse), and as loads
    // through the descriptor's generic pointer they were flat loads
    uint32_t w00, w10, w01, w11;
    pre();
-   asm volatile(
-      "global_load_dword %0, %4, off\n\tglobal_load_dword %1, %5, off\n\tglobal_load_dword %2, %6, off\n\tglobal_load_dword %3, %7, off\n\t"
-      "s_waitcnt vmcnt(0)"
-      : "=&v"(w00), "=&v"(w10), "=&v"(w01), "=&v"(w11)
-      : "v"(q00), "v"(q10), "v"(q01), "v"(q11)
-      : "memory");
+   if (blocked) {
+      u2_t r0, r1;  // the footprint's upper and lower row: (mx, my) (mx + 1, my) / (mx, my + 1) (mx + 1, my + 1)
+      asm volatile("global_load_dwordx2 %0, %2, off\n\tglobal_load_dwordx2 %1, %2, off offset:%3\n\ts_waitcnt vmcnt(0)"
+                   : "=&v"(r0), "=&v"(r1)
+                   : "v"(q00), "n"(TexLayout::kW * 4)
+                   : "memory");
+      const u2_t ra = y0 != my ? r1 : r0, rb = y1 != my ? r1 : r0;  // the rows of y0 and of y1
+      w00 = x0 != mx ? ra.y : ra.x;
+      w10 = x1 != mx ? ra.y : ra.x;
+      w01 = x0 != mx ? rb.y : rb.x;
+      w11 = x1 != mx ? rb.y : rb.x;
+   } else {
+      const uchar4* q10 = t.texels + address(x1, y0);
+      const uchar4* q01 = t.texels + address(x0, y1);
+      const uchar4* q11 = t.texels + address(x1, y1);
+      asm volatile(
+         "global_load_dword %0, %4, off\n\tglobal_load_dword %1, %5, off\n\tglobal_load_dword %2, %6, off\n\tglobal_load_dword %3, %7, off\n\t"
+         "s_waitcnt vmcnt(0)"
+         : "=&v"(w00), "=&v"(w10), "=&v"(w01), "=&v"(w11)
+         : "v"(q00), "v"(q10), "v"(q01), "v"(q11)
+         : "memory");
+   }
    auto texel = [](uint32_t w) { return make_uchar4((unsigned char)(w & 0xffu), (unsigned char)((w >> 8) & 0xffu), (unsigned char)((w >> 16) & 0xffu), (unsigned char)(w >> 24)); };
    const uchar4 p00 = texel(w00), p10 = texel(w10), p01 = texel(w01), p11 = texel(w11);
    const V3 t00 = v3(lut[p00.x], lut[p00.y], lut[p00.z]), t10 = v3(lut[p10.x], lut[p10.y], lut[p10.z]);

@@ -82,11 +82,12 @@ static_assert(sizeof(MeshShade) == 80, "mesh shading record");
 struct TexInfo {
    const uchar4* texels;
    uint32_t w, h;
-   // tiles_x > 0: texels are stored in 8x8-texel tiles (256 B, row-major inside the tile, tiles
-   // row-major), so the 2x2 bilinear footprint usually sits in one 128-B line instead of two rows.
-   // 0: plain row-major (sizes that are not multiples of 8).
+   // blocks_x > 0 (every texture unless option "texture_blocks" was 0 when it was added): overlapped blocks of kTexBlockW x
+   // kTexBlockH texels, one block per cache line, blocks_x of them per row of blocks (texture_layout.h): a bilinear footprint
+   // lies in one line. Otherwise tiles_x > 0: 8x8-texel tiles (256 B, row-major inside the tile, tiles row-major), a footprint
+   // in 1.4 lines; both 0: plain row-major (with blocks off, sizes that are not multiples of 8).
    uint32_t tiles_x;
-   uint32_t pad;
+   uint32_t blocks_x;
 };
 
 struct SceneDev {

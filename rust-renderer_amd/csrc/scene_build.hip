@@ -121,7 +121,7 @@ static int upload_scene_tables(uh_ctx* c) {
       lights[2 * i + 1] = make_float4(l.intensity[0], l.intensity[1], l.intensity[2], 0.0f);
    }
    std::vector<TexInfo> tex(c->textures.size());
-   for (size_t i = 0; i < tex.size(); i++) tex[i] = TexInfo{c->textures[i].dev, c->textures[i].w, c->textures[i].h, c->textures[i].tiles_x, 0};
+   for (size_t i = 0; i < tex.size(); i++) tex[i] = TexInfo{c->textures[i].dev, c->textures[i].w, c->textures[i].h, c->textures[i].tiles_x, c->textures[i].blocks_x};
 
    HIP_TRY(c, c->d_meshes.alloc(ms.size()));
    HIP_TRY(c, c->d_lights.alloc(lights.size()));
