@@ -243,14 +243,14 @@ typedef struct uh_ctx uh_ctx;
  *        uh_unpack_tiles, uh_compose_tiles, uh_resolve_output, uh_add_isosurface_mesh, uh_update_isosurface_mesh (it reads the
  *        triangle total, 8 bytes, back to size its buffers), uh_get_isosurface_update_stats, uh_update_mesh_vertices (device input:
  *        it reads a 4-byte verdict on the caller's buffer back before it takes it), uh_get_mesh_update_stats, uh_read_denoised,
- *        uh_get_denoise_stats, uh_reset_denoise_history, uh_destroy;
+ *        uh_get_denoise_stats, uh_reset_denoise_history, uh_get_rtao_stats, uh_get_rtao_visits, uh_destroy;
  *   enqueues like a frame, ordered behind the frames in flight and before those that follow:  uh_rccl_gather_tiles, uh_mgpu_compose;
  *        uh_set_option for "frames_in_flight" and for "time_kernels" 1 -> 0 (the others only change what the NEXT enqueued
  *        frame does: "furnace", "sun_grid*", "camera_grid*", "overlap", "batch_frames", "trace_blocks_per_cu", "count_visits",
- *        "full_frame_restir", "primary_implicit"; "device_build", "ploc_sah_top" invalidate the tree: the next frame
+ *        "full_frame_restir", "primary_implicit", "rtao_order"; "device_build", "ploc_sah_top" invalidate the tree: the next frame
  *        needs uh_build_acceleration, which waits);
  *   host state only (no device access, nothing to wait for):  uh_add_mesh, uh_add_light, uh_set_instance_transform,
- *        uh_get_num_lights, uh_mesh_info, uh_read_mesh, uh_get_restir_rows, uh_tile_pack_count, uh_last_error
+ *        uh_get_num_lights, uh_mesh_info, uh_read_mesh, uh_get_restir_rows, uh_tile_pack_count, uh_set_rtao_params, uh_last_error
  *        (uh_read_mesh of a mesh that uh_update_isosurface_mesh has made device-resident, or that uh_update_mesh_vertices last updated
  *        from a device pointer, copies it from the device: a blocking copy);
  *   uh_add_texture_rgba8 uploads into a fresh allocation no frame in flight can reference (textures enter a frame's tables at the
@@ -641,7 +641,7 @@ int uh_mgpu_set_option(uh_mgpu* group, const char* name, int value);
  * UH_HYBRID_RT_REFLECTIONS with view->ibl_enabled == 1 is UH_ERR_INVALID_ARGUMENT - and nothing runs - until the IBL maps (irradiance,
  * specular, BRDF LUT of ibl.rs) have been built with UH_HYBRID_ENVIRONMENT, below; mask bits, UH_ERR_NOT_BUILT and moved instances with
  * view->rebuild_tlas as for uh_render_frame (bits above UH_HYBRID_SHADOW_MAPS, below, are ignored, except UH_HYBRID_MARCHING_CUBES,
- * UH_HYBRID_GBUFFER_RASTER and UH_HYBRID_RESTIR_LIGHTS).
+ * UH_HYBRID_GBUFFER_RASTER, UH_HYBRID_RESTIR_LIGHTS and UH_HYBRID_RTAO).
  * STREAM ORDER: uh_render_hybrid enqueues like a frame (behind the frames in flight, ahead of those that follow); uh_read_hybrid and
  * uh_get_hybrid_stats wait for all work of the context and are complete on return. The exception is UH_HYBRID_SHADOW_MAPS, below: a
  * call that renders shadow maps BLOCKS the host until the frames in flight and the pass's binning have finished (it reads the
@@ -1105,6 +1105,63 @@ int uh_denoise(uh_ctx* ctx, const UhViewUniformData* view, const UhDenoiseParams
 int uh_reset_denoise_history(uh_ctx* ctx);           /* the next uh_denoise starts from no history */
 int uh_read_denoised(uh_ctx* ctx, int which, void* out); /* UH_ERR_INVALID_ARGUMENT before the first uh_denoise */
 int uh_get_denoise_stats(uh_ctx* ctx, UhDenoiseStats* out);
+
+/* ---- ray-traced ambient occlusion for the hybrid frame: short hemisphere rays instead of ssao.frag ---------------------------------------
+ * An EXTENSION: the reference's ambient occlusion is ssao.frag alone (32 fixed kernel samples, a constant "random" vector, what is on
+ * screen, no blur). UH_HYBRID_RTAO (bit 13; bit 9 stays unused and ignored) takes the SSAO slot of uh_render_hybrid: with the bit set and
+ * view->ssao_enabled == 1 the rtao pass writes ssao_output (UH_HYBRID_SSAO_IMAGE, R16 UNORM) and ssao.frag's kernel is not launched,
+ * whether or not UH_HYBRID_SSAO is set - UH_HYBRID_FRAME | UH_HYBRID_RTAO is the natural call. With ssao_enabled != 1 the pass does not
+ * run and the image keeps what it held, as for SSAO. The deferred pass is untouched: it reads ssao_output as it always has.
+ *   rays      a G-buffer pixel (px, py) whose position texel has w != 0 and whose normal texel N normalises to a finite Nn casts
+ *             `samples` rays from offsetRay(P, Nn) of its OWN texels. Ray s has direction normalize(Nn + normalize(u)), u =
+ *             randomPointInUnitSphere of the state initRNG(px, py, W, frameNumber(view) * 64 + s) (random.glsl) - the closest-hit
+ *             shader's Lambertian scatter, cosine-weighted; Nn itself where |Nn + normalize(u)|^2 < 1e-12. It is occluded when a triangle
+ *             has 0.001 < t < 10000 and t <= radius. count = the pixel's occluded rays; every other pixel casts nothing, count 0.
+ *   image     ao = 1 - strength * ((float)count / (float)samples), 1 where no ray was cast. blur_radius 0: ssao_output = unorm16(ao).
+ *             blur_radius r: a geometry pixel gets the mean of ao over the taps (dx, dy) in [-r, r)^2 (blur.frag's window) that lie in
+ *             the frame, cast rays themselves, and pass dot(Nn_tap, Nn) >= blur_normal_cos and |dot(P_tap - P, Nn)| <= blur_plane; the
+ *             centre always counts. Texel (x, y) of ssao_output belongs to G-buffer pixel (x, H - 1 - y), as ssao.frag writes it.
+ * PARAMS: uh_set_rtao_params validates and keeps them for the calls that follow (a refused call leaves the old ones); before the
+ * first call the defaults of uh_rtao_default_params hold: 4 samples, radius 1.0, strength 1.0, blur_radius 2, 0.9, 0.05.
+ * UH_ERR_INVALID_ARGUMENT with a message, and nothing runs: the bit (with ssao_enabled == 1) and view->raytracing_supported != 1; no
+ * G-buffer rendered in this call or an earlier one. UH_ERR_NOT_BUILT before uh_build_acceleration, as without the bit.
+ * READ-BACK (uh_read_hybrid, UH_ERR_INVALID_ARGUMENT before the first rtao pass): UH_HYBRID_AO_COUNTS, one byte per pixel in G-buffer
+ * orientation: the pixel's occluded rays, 0 where none were cast.
+ * RESOURCES: 5 bytes per pixel (the counts and a queue of the pixels that cast), allocated by the first pass; freed by uh_destroy. A
+ * context that never sets the bit allocates nothing for it.
+ * STREAM ORDER: as uh_render_hybrid. uh_set_rtao_params is host state, read by the next uh_render_hybrid; uh_get_rtao_stats waits.
+ * ISOLATION: the bit changes no reservoir, accumulation, gbuffer_position, grid or UhStats, and no hybrid image but ssao_output and the
+ * counts; its rays are counted in UhRtaoStats only. Without the bit every pass is what it was. No uh_mgpu_ twin.
+ * Arithmetic: DESIGN.md section 2, "Ray-traced ambient occlusion". */
+enum { UH_HYBRID_RTAO = 1u << 13 };
+enum { UH_HYBRID_AO_COUNTS = 14 /* uint8 per pixel, G-buffer orientation: occluded rays of the pixel, 0 where none were cast */ };
+typedef struct UhRtaoParams {
+   uint32_t samples;      /* rays per geometry pixel, 1..64 */
+   float radius;          /* world units; finite, > 0, <= 10000 */
+   float strength;        /* ao = 1 - strength * occluded / samples; finite, >= 0 */
+   uint32_t blur_radius;  /* 0 = no filter; else 1..4: taps dx, dy in [-r, r) as blur.frag */
+   float blur_normal_cos; /* a tap counts when dot(Nn_tap, Nn) >= this; not NaN */
+   float blur_plane;      /* and |dot(P_tap - P, Nn)| <= this (world units); not NaN */
+} UhRtaoParams;
+UH_LAYOUT_ASSERT(sizeof(UhRtaoParams) == 24 && offsetof(UhRtaoParams, radius) == 4 && offsetof(UhRtaoParams, strength) == 8 &&
+                    offsetof(UhRtaoParams, blur_radius) == 12 && offsetof(UhRtaoParams, blur_normal_cos) == 16 &&
+                    offsetof(UhRtaoParams, blur_plane) == 20,
+                 "UhRtaoParams (24 B)");
+/* the last rtao pass: the pixels that cast, their rays (pixels * samples), the occluded ones, and the hipEvent times of classify + trace
+ * and of the resolve / filter. All zero before the first pass. Waits for all work of the context. */
+typedef struct UhRtaoStats {
+   uint64_t pixels, rays, occluded;
+   float trace_ms, filter_ms;
+} UhRtaoStats;
+UH_LAYOUT_ASSERT(sizeof(UhRtaoStats) == 32 && offsetof(UhRtaoStats, rays) == 8 && offsetof(UhRtaoStats, occluded) == 16 &&
+                    offsetof(UhRtaoStats, trace_ms) == 24 && offsetof(UhRtaoStats, filter_ms) == 28,
+                 "UhRtaoStats (32 B)");
+int uh_rtao_default_params(UhRtaoParams* out); /* needs no GPU: 4, 1.0, 1.0, 2, 0.9, 0.05; UH_ERR_INVALID_ARGUMENT for NULL */
+int uh_set_rtao_params(uh_ctx* ctx, const UhRtaoParams* params); /* validated here; a refused call leaves the old ones */
+int uh_get_rtao_stats(uh_ctx* ctx, UhRtaoStats* out);            /* waits; all zero before the first pass */
+/* measurement: the node visits and triangle tests of the last pass's walks, counted while option "count_visits" is 1 (the kernel is
+ * then another instantiation, a little slower); 0 otherwise. Waits. */
+int uh_get_rtao_visits(uh_ctx* ctx, uint64_t* nodes, uint64_t* triangles);
 
 #ifdef __cplusplus
 }

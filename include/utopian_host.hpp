@@ -305,9 +305,11 @@ class Renderer {
    // "uh_render_hybrid")
    void render_hybrid(const UhViewUniformData& view, uint32_t mask = UH_HYBRID_ALL) { check(uh_render_hybrid(ctx_, &view, mask), "render_hybrid"); }
    // one image as bytes: W*H texels of 16 (position, normal, pbr, deferred output), 4 (albedo, reflections, present output, the
-   // marching-cubes and rasterised G-buffer depth floats and draw indices uint32), 2 (SSAO) or 1 (shadows, light visibility) bytes
+   // marching-cubes and rasterised G-buffer depth floats and draw indices uint32), 2 (SSAO) or 1 (shadows, light visibility, the
+   // occluded-ray counts of UH_HYBRID_RTAO) bytes
    std::vector<uint8_t> read_hybrid(int which) {
-      const size_t texel = (which == UH_HYBRID_SHADOWS || which == UH_HYBRID_LIGHT_VISIBILITY) ? 1
+      const size_t texel = (which == UH_HYBRID_AO_COUNTS) ? 1
+                           : (which == UH_HYBRID_SHADOWS || which == UH_HYBRID_LIGHT_VISIBILITY) ? 1
                            : (which == UH_HYBRID_SSAO_IMAGE) ? 2
                            : (which == UH_HYBRID_ALBEDO || which == UH_HYBRID_REFLECTIONS || which == UH_HYBRID_PRESENT_OUTPUT ||
                               which == UH_HYBRID_DEPTH || which == UH_HYBRID_MARCHING_CUBES_VISIBILITY || which == UH_HYBRID_GBUFFER_DEPTH ||
@@ -344,6 +346,19 @@ class Renderer {
    UhHybridRestirStats hybrid_restir_stats() {
       UhHybridRestirStats s;
       check(uh_get_hybrid_restir_stats(ctx_, &s), "hybrid_restir_stats");
+      return s;
+   }
+   // ray-traced ambient occlusion in the SSAO slot of render_hybrid (UH_HYBRID_RTAO; utopian_hip.h): the params of the calls that
+   // follow, and the last pass's pixels, rays, occluded rays and times
+   static UhRtaoParams default_rtao_params() {
+      UhRtaoParams p;
+      if (uh_rtao_default_params(&p) != UH_OK) throw Error(UH_ERR_INVALID_ARGUMENT, "uh_rtao_default_params");
+      return p;
+   }
+   void set_rtao_params(const UhRtaoParams& params) { check(uh_set_rtao_params(ctx_, &params), "set_rtao_params"); }
+   UhRtaoStats rtao_stats() {
+      UhRtaoStats s;
+      check(uh_get_rtao_stats(ctx_, &s), "rtao_stats");
       return s;
    }
    // the denoiser (utopian_hip.h "the denoiser"): the accumulation of the last render_frame over the G-buffer of the last render_hybrid,

@@ -14,6 +14,7 @@ from .api import (  # noqa: F401
     load_library,
     make_light,
     make_material,
+    rtao_default_params,
     shadow_cascades,
     transform3x4,
 )

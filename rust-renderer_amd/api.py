@@ -38,6 +38,7 @@ from .types import (
     ENV_SPECULAR,
     HYBRID_ALBEDO,
     HYBRID_ALL,
+    HYBRID_AO_COUNTS,
     HYBRID_DEFERRED_OUTPUT,
     HYBRID_DEPTH,
     HYBRID_GBUFFER_DEPTH,
@@ -71,6 +72,8 @@ from .types import (
     ForwardStats,
     Reservoir,
     RestirRows,
+    RtaoParams,
+    RtaoStats,
     Stats,
     ViewUniformData,
 )
@@ -520,16 +523,18 @@ class Renderer:
         HYBRID_GBUFFER_DEPTH: (np.float32, 1),
         HYBRID_GBUFFER_VISIBILITY: (np.uint32, 1),
         HYBRID_LIGHT_VISIBILITY: (np.uint8, 1),
+        HYBRID_AO_COUNTS: (np.uint8, 1),
     }
 
     def read_hybrid(self, which):
         """one image of the hybrid graph: (H, W, 4) float32 position / normal / pbr / deferred output, (H, W, 4) uint8 albedo / reflections /
         present output (B, G, R, A), (H, W) uint8 shadows, (H, W) uint16 SSAO, (H, W) float32 marching-cubes depth buffer, (H, W) uint32
         marching-cubes draw index (MARCHING_CUBES_NONE where none survived), (H, W) float32 rasterised G-buffer depth, (H, W) uint32
-        rasterised G-buffer draw index (GBUFFER_NONE where none survived), (H, W) uint8 light visibility of HYBRID_RESTIR_LIGHTS"""
+        rasterised G-buffer draw index (GBUFFER_NONE where none survived), (H, W) uint8 light visibility of HYBRID_RESTIR_LIGHTS,
+        (H, W) uint8 occluded-ray counts of HYBRID_RTAO"""
         api = self._hybrid_api()
         if which not in self._HYBRID_IMAGES:
-            raise ValueError(f"hybrid image index {which} (0..13)")
+            raise ValueError(f"hybrid image index {which} (0..14)")
         dtype, ch = self._HYBRID_IMAGES[which]
         out = np.empty((self.height, self.width, ch) if ch > 1 else (self.height, self.width), dtype=dtype)
         self._check(api.read_hybrid(self._ctx, int(which), out.ctypes.data))
@@ -595,6 +600,41 @@ class Renderer:
         s = HybridRestirStats()
         self._check(fn(self._ctx, C.byref(s)))
         return s
+
+    # -- ray-traced ambient occlusion (HYBRID_RTAO; include/utopian_hip.h "UH_HYBRID_RTAO") ---
+    def _rtao_fn(self, name, arg):
+        if self.backend != "hip":
+            raise NotImplementedError(f"ray-traced ambient occlusion is a per-context verb of the HIP library; backend {self.backend!r} has none")
+        fn = getattr(self._lib, "uh_" + name)
+        fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(arg)], C.c_int
+        return fn
+
+    def set_rtao_params(self, params=None, **fields):
+        """uh_set_rtao_params: `params` (an RtaoParams; the defaults when None) with `fields` set on a copy - the params of the
+        render_hybrid calls with HYBRID_RTAO that follow. A refused call raises and leaves the old ones."""
+        p = RtaoParams.from_buffer_copy(rtao_default_params() if params is None else params)
+        for k, v in fields.items():
+            if not hasattr(p, k):
+                raise TypeError(f"RtaoParams has no field {k!r}")
+            setattr(p, k, v)
+        self._check(self._rtao_fn("set_rtao_params", RtaoParams)(self._ctx, C.byref(p)))
+        return p
+
+    def rtao_stats(self):
+        """UhRtaoStats of the last rtao pass: pixels, rays, occluded, trace_ms, filter_ms"""
+        s = RtaoStats()
+        self._check(self._rtao_fn("get_rtao_stats", RtaoStats)(self._ctx, C.byref(s)))
+        return s
+
+    def rtao_visits(self):
+        """(node visits, triangle tests) of the last rtao pass's walks, counted while option "count_visits" is 1; else (0, 0)"""
+        if self.backend != "hip":
+            raise NotImplementedError(f"ray-traced ambient occlusion is a per-context verb of the HIP library; backend {self.backend!r} has none")
+        fn = self._lib.uh_get_rtao_visits
+        fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int
+        nodes, tris = C.c_uint64(), C.c_uint64()
+        self._check(fn(self._ctx, C.byref(nodes), C.byref(tris)))
+        return nodes.value, tris.value
 
     # -- the denoiser (uh_denoise; include/utopian_hip.h "the denoiser") --------------------
     def _denoise_fn(self, name, argtypes):
@@ -879,6 +919,16 @@ class MultiGpuRenderer(Renderer):
 
     def compose(self):
         self._check(self._lib.uh_mgpu_compose(self._ctx))
+
+
+def rtao_default_params():
+    """UhRtaoParams as uh_rtao_default_params fills it (needs no GPU)"""
+    fn = load_library().uh_rtao_default_params
+    fn.argtypes, fn.restype = [C.POINTER(RtaoParams)], C.c_int
+    p = RtaoParams()
+    if fn(C.byref(p)) != 0:
+        raise UtopianError("uh_rtao_default_params failed")
+    return p
 
 
 def default_denoise_params():

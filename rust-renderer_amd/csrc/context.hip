@@ -1368,6 +1368,12 @@ int uh_set_option(uh_ctx* c, const char* name, int value) {
       c->iso_reference = value != 0;
    else if (n == "furnace")
       c->furnace = value != 0;  // applies to the frames enqueued from now on
+   else if (n == "rtao_order") {
+      // how the rtao trace kernel lays out its work (rtao.hip; same counts whichever): 0 (default) one ray per item, a pixel's samples
+      // together; 1 one ray per item, one sample of consecutive pixels together; 2 one pixel per item, its lane walks the samples
+      if (!range(0, 2)) return bad("must be 0..2");
+      c->hy.ao_order = (uint32_t)value;
+   }
    else if (n == "texture_blocks")
       // 1: the textures added from now on are stored as overlapped blocks, a bilinear footprint in one cache line (texture_layout.h);
       // 0: as 8x8 tiles, or rows. Same images bit for bit: the same four texel words enter the filter

@@ -132,10 +132,11 @@ struct Stage {
 };
 
 // the hybrid graph's stages (uh_ctx::Hybrid::stage): its seven passes in the order of their UH_HYBRID_* bits, then the environment's,
-// then the shadow maps, then the marching-cubes pass, then the reservoir lights
+// then the shadow maps, then the marching-cubes pass, then the reservoir lights, then ray-traced ambient occlusion (classify + trace, resolve)
 enum HybridStage : int {
    kStShadows, kStGbuffer, kStReflections, kStSsao, kStDeferred, kStSky, kStPresent, kHybridPasses,
-   kStEnvCube = kHybridPasses, kStEnvIrradiance, kStEnvSpecular, kStEnvLut, kStShadowMaps, kStMarchingCubes, kStRestirLights, kHybridStages
+   kStEnvCube = kHybridPasses, kStEnvIrradiance, kStEnvSpecular, kStEnvLut, kStShadowMaps, kStMarchingCubes, kStRestirLights,
+   kStRtaoTrace, kStRtaoFilter, kHybridStages
 };
 
 // One frame in flight: its own stream pair, hazard events, path state and queue control block.
@@ -482,6 +483,14 @@ struct uh_ctx {
       DevBuf<uint32_t> rl_queue, rl_counters;
       hipEvent_t rl_read = nullptr;
       uint32_t rl_renders = 0;
+      // ray-traced ambient occlusion (UH_HYBRID_RTAO), allocated by the first pass: the occluded-ray counts (a byte per pixel, rounded
+      // up to whole words: the trace kernel adds into them by words), the queue of the pixels that cast and the pass's counters
+      // (pixels, occluded, and with option "count_visits" the walks' node visits and triangle tests); ao_params: the last uh_set_rtao_params (the defaults before); ao_samples: the last pass's
+      DevBuf<uint8_t> ao_counts;
+      DevBuf<uint32_t> ao_queue, ao_counters;
+      UhRtaoParams ao_params{4, 1.0f, 1.0f, 2, 0.9f, 0.05f};
+      uint32_t ao_renders = 0, ao_samples = 0;
+      uint32_t ao_order = 0;                   // option "rtao_order" (rtao.hip: how the trace kernel's work items are laid out; 0 measured fastest)
 
       // the three groups allocated on first use, each named once for allocation and uh_destroy: f(buffer, length), n pixels; a
       // group's last buffer is allocated last, its pointer says "allocated"
@@ -497,6 +506,7 @@ struct uh_ctx {
             f(mc_verts, 0), mc.each(n, f);  // (mc_verts and the rest of mc_bins are grown by the pass)
       }
       template <class F> void restir_images(size_t n, F&& f) { f(rl_vis, n), f(rl_queue, n), f(rl_counters, 2); }
+      template <class F> void rtao_images(size_t n, F&& f) { f(ao_counts, (n + 3) & ~(size_t)3), f(ao_queue, n), f(ao_counters, 6); }
       template <class F> void env_maps(F&& f) {
          const size_t cube = env_mip_offset(kEnvMips);
          f(env, cube), f(irr, 6 * (size_t)kEnvSize * kEnvSize), f(spec, cube), f(lut, (size_t)kLutSize * kLutSize);

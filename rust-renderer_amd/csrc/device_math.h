@@ -87,6 +87,11 @@ __device__ __forceinline__ uint32_t unorm8(float x) {
    if (x > 1.0f) x = 1.0f;
    return (uint32_t)rintf(x * 255.0f);
 }
+__device__ __forceinline__ uint32_t unorm16(float x) {
+   if (!(x > 0.0f)) x = 0.0f;
+   if (x > 1.0f) x = 1.0f;
+   return (uint32_t)rintf(x * 65535.0f);
+}
 
 // ---- include/atmosphere.glsl ---------------------------------------------------------------
 // exp/pow use the hardware exp2/log2 path (v_exp_f32 / v_log_f32): the sky is a smooth integrand,

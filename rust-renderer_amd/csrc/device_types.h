@@ -261,6 +261,17 @@ struct HybridRestirDev {
    uint32_t num_lights;            // view.num_lights, at most the table's length
 };
 
+// ray-traced ambient occlusion of the hybrid frame (UH_HYBRID_RTAO; rtao.hip): what its three kernels read and write
+struct RtaoDev {
+   uint8_t* counts;                // UH_HYBRID_AO_COUNTS: a pixel's occluded rays, G-buffer orientation; whole words (the trace adds by words)
+   uint32_t* queue;                // the pixels that cast, compacted
+   uint32_t* counters;             // [0]: entries of `queue`, [1]: occluded rays; with count_visits [2..3]: node visits, [4..5]: triangle tests (64 bits each)
+   uint32_t samples;               // UhRtaoParams::samples
+   uint32_t frame_base;            // frameNumber(view) * 64: ray s seeds its state with frame_base + s
+   uint32_t blur_radius;
+   float radius, strength, blur_normal_cos, blur_plane;
+};
+
 // the denoiser (uh_denoise; denoise.hip): one frame's guides and moments as the next call's history reads them
 struct DenoiseHistory {
    float4* pos;                    // the position texel (w != 0: geometry)
@@ -379,6 +390,13 @@ void launch_hybrid_deferred(const LaunchCfg&, const SceneDev&, const HybridDev&,
                             const ShadowLookup* shadow, const HybridRestirDev* restir = nullptr);
 // the restir_lights pass: classify (which pixels cast a ray toward their reservoir's light), then the rays; rl.counters zeroed by the caller
 void launch_hybrid_restir_lights(const LaunchCfg&, const FrameParams&, const SceneDev&, const HybridDev&, const HybridRestirDev&);
+// the rtao pass (rtao.hip): classify (which pixels cast; their counts zeroed) and the rays; ao.counters zeroed by the caller;
+// LaunchCfg::count_visits: the walks' visits are counted there too. order: 0 an
+// item is one ray, a pixel's samples consecutive; 1 an item is one ray, one sample of consecutive queued pixels; 2 an item is a pixel,
+// whose lane walks its samples one after the other and stores the count once
+void launch_rtao_trace(const LaunchCfg&, const SceneDev&, const HybridDev&, const RtaoDev&, uint32_t order);
+// ao (and its filter, blur_radius > 0) from the counts into ssao_output, texel (x, y) = G-buffer pixel (x, H - 1 - y)
+void launch_rtao_resolve(const LaunchCfg&, const HybridDev&, const RtaoDev&, uint16_t* ssao);
 // the shadow-map rasteriser (shadow_map.hip): setup per (triangle, cascade), binning into kShadowTile^2 tiles, resolve per tile in LDS
 constexpr uint32_t kShadowTile = 128;
 struct ShadowDev {

@@ -82,6 +82,7 @@ void destroy_graphs(uh_ctx* c) {
    h.shadow_maps(release);
    h.mc_images(0, release);
    h.restir_images(0, release);
+   h.rtao_images(0, release);
    if (h.rl_read) (void)hipEventDestroy(h.rl_read);
    h.mc_bins.each(release);
    h.gr.each(0, release);
@@ -612,6 +613,18 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
                      "uh_render_hybrid: UH_HYBRID_RESTIR_LIGHTS needs the whole frame's reservoirs, and a row partition with world > 1 is set "
                      "(uh_set_restir_partition)");
    }
+   // ray-traced ambient occlusion takes the SSAO slot: short hemisphere rays from the G-buffer instead of ssao.frag
+   const bool rtao = (mask & UH_HYBRID_RTAO) && view->ssao_enabled == 1;
+   if (rtao) {
+      if (view->raytracing_supported != 1)
+         return fail(c, UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_RTAO casts occlusion rays and view.raytracing_supported is not 1; set it, or clear the bit");
+      if (!(mask & UH_HYBRID_GBUFFER) && !c->hy.gbuffer_done)
+         return fail(c, UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_RTAO casts its rays from the G-buffer, and no G-buffer has been rendered; set UH_HYBRID_GBUFFER");
+      if ((uint64_t)c->W * c->H * 64u >= (1ull << 32))
+         return fail(c, UH_ERR_CAPACITY, "uh_render_hybrid: UH_HYBRID_RTAO: a frame of 2^26 pixels or more (its rays are numbered in 32 bits)");
+   }
    // setup_marching_cubes_pass (mod.rs:164): only with the checkbox on
    const bool mc = (mask & UH_HYBRID_MARCHING_CUBES) && view->marching_cubes_enabled == 1;
    if (mc) {
@@ -641,8 +654,8 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    if (raster && !h.gr.covered.p)
       if (int st = alloc_group(c, [&](auto f) { h.gr.each((size_t)c->W * c->H, f); })) return st;
    const uint32_t frame_bits = UH_HYBRID_SSAO | UH_HYBRID_DEFERRED | UH_HYBRID_SKY | UH_HYBRID_PRESENT;
-   const bool frame_first = ((mask & frame_bits) || mc) && !h.sky_counter.p;
-   if ((mask & frame_bits) || mc) {
+   const bool frame_first = ((mask & frame_bits) || mc || rtao) && !h.sky_counter.p;
+   if ((mask & frame_bits) || mc || rtao) {
       if (int st = hybrid_frame_alloc(c)) return st;
       if ((mask & UH_HYBRID_DEFERRED) || mc)
          if (int st = hybrid_light_table(c)) return st;
@@ -657,6 +670,10 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
          HIP_TRY(c, hipMemsetAsync(h.rl_vis.p, 0, (size_t)c->W * c->H, c->stream));
          HIP_TRY(c, hipMemsetAsync(h.rl_counters.p, 0, 2 * sizeof(uint32_t), c->stream));
       }
+   }
+   if (rtao && !h.ao_counters.p) {
+      if (int st = alloc_group(c, [&](auto f) { h.rtao_images((size_t)c->W * c->H, f); })) return st;
+      HIP_TRY(c, hipMemsetAsync(h.ao_counts.p, 0, h.ao_counts.n, c->stream));
    }
    if (mask & UH_HYBRID_ENVIRONMENT)
       if (int st = env_alloc(c)) return st;
@@ -713,6 +730,7 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    if (mask & UH_HYBRID_SHADOW_MAPS) h.stage[kStShadowMaps].ran = false;
    if (mask & UH_HYBRID_MARCHING_CUBES) h.stage[kStMarchingCubes].ran = false;
    if (restir) h.stage[kStRestirLights].ran = false;
+   if (rtao) h.stage[kStRtaoTrace].ran = h.stage[kStRtaoFilter].ran = false;
    // setup_shadow_pass's four passes are added first (mod.rs:91-98)
    if (render_maps) {
       HIP_TRY(c, stage_begin(h.stage[kStShadowMaps], c->stream));
@@ -777,7 +795,22 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
       h.rl_renders++;
    }
    // the final frame (mod.rs:136-186): ssao_pass (not with ssao_enabled != 1, ssao.rs:27), deferred_pass, atmosphere_pass, present_pass
-   if ((mask & UH_HYBRID_SSAO) && view->ssao_enabled == 1) {
+   if (rtao) {
+      // the rtao pass in ssao_pass's place: classify + trace into the counts, then the resolve / filter into ssao_output
+      const UhRtaoParams& p = h.ao_params;
+      const RtaoDev ao{h.ao_counts.p, h.ao_queue.p, h.ao_counters.p, p.samples, fp.frame_number * 64u, p.blur_radius, p.radius, p.strength, p.blur_normal_cos, p.blur_plane};
+      HIP_TRY(c, stage_begin(h.stage[kStRtaoTrace], c->stream));
+      HIP_TRY(c, hipMemsetAsync(h.ao_counters.p, 0, 6 * sizeof(uint32_t), c->stream));
+      LaunchCfg ac = lc;
+      ac.count_visits = c->count_visits;  // into the pass's own counters (uh_get_rtao_visits), never UhStats
+      launch_rtao_trace(ac, c->scene, hd, ao, h.ao_order);
+      HIP_TRY(c, stage_end(h.stage[kStRtaoTrace], c->stream));
+      HIP_TRY(c, stage_begin(h.stage[kStRtaoFilter], c->stream));
+      launch_rtao_resolve(lc, hd, ao, h.ssao.p);
+      HIP_TRY(c, stage_end(h.stage[kStRtaoFilter], c->stream));
+      h.ao_samples = p.samples;
+      h.ao_renders++;
+   } else if ((mask & UH_HYBRID_SSAO) && view->ssao_enabled == 1) {
       HIP_TRY(c, stage_begin(h.stage[kStSsao], c->stream));
       launch_hybrid_ssao(lc, hd, fd);
       HIP_TRY(c, stage_end(h.stage[kStSsao], c->stream));
@@ -822,7 +855,7 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    const uh_ctx::Hybrid& h = c->hy;
    if (!h.counter.p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid before the first uh_render_hybrid");
-   if (which < 0 || which > UH_HYBRID_LIGHT_VISIBILITY) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..13");
+   if (which < 0 || which > UH_HYBRID_AO_COUNTS) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..14");
    if (which >= UH_HYBRID_SSAO_IMAGE && which <= UH_HYBRID_PRESENT_OUTPUT && !h.sky_counter.p)
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 6..8 before the first call with an SSAO, deferred, sky or present bit");
    if ((which == UH_HYBRID_DEPTH || which == UH_HYBRID_MARCHING_CUBES_VISIBILITY) && h.mc_renders == 0)
@@ -831,12 +864,14 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 11..12 before the first rasterised G-buffer pass");
    if (which == UH_HYBRID_LIGHT_VISIBILITY && !h.rl_counters.p)
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image 13 before the first call with UH_HYBRID_RESTIR_LIGHTS");
+   if (which == UH_HYBRID_AO_COUNTS && h.ao_renders == 0)
+      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image 14 before the first rtao pass (UH_HYBRID_RTAO with view.ssao_enabled = 1)");
    // image k's pixels and its bytes per pixel, in UH_HYBRID_* image order
    const std::pair<const void*, size_t> img[] = {
       {h.pos.p, sizeof(float4)}, {h.nrm.p, sizeof(float4)}, {h.alb.p, sizeof(uchar4)}, {h.pbr.p, sizeof(float4)}, {h.shadow.p, 1},
       {h.refl.p, sizeof(uchar4)}, {h.ssao.p, sizeof(uint16_t)}, {h.deferred.p, sizeof(float4)}, {h.present.p, sizeof(uchar4)},
       {h.mc.depth.p, sizeof(float)}, {h.mc.vis.p, sizeof(uint32_t)}, {h.gr.depth.p, sizeof(float)}, {h.gr.vis.p, sizeof(uint32_t)},
-      {h.rl_vis.p, 1}};
+      {h.rl_vis.p, 1}, {h.ao_counts.p, 1}};
    return read_back(c, out, img[which].first, (size_t)c->W * c->H * img[which].second);
 }
 
@@ -868,6 +903,63 @@ int uh_get_hybrid_restir_stats(uh_ctx* c, UhHybridRestirStats* out) {
    HIP_TRY(c, hipMemcpy(counters, h.rl_counters.p, sizeof(counters), hipMemcpyDeviceToHost));
    out->rays = counters[0];
    out->occluded = counters[1];
+   return UH_OK;
+}
+
+// ---- ray-traced ambient occlusion (utopian_hip.h "UH_HYBRID_RTAO"; rtao.hip) ----
+int uh_rtao_default_params(UhRtaoParams* out) {
+   if (!out) return UH_ERR_INVALID_ARGUMENT;
+   *out = UhRtaoParams{4, 1.0f, 1.0f, 2, 0.9f, 0.05f};
+   return UH_OK;
+}
+
+static const char* rtao_params_refusal(const UhRtaoParams& p) {
+   if (p.samples < 1 || p.samples > 64) return "samples must be 1..64";
+   if (!(p.radius > 0.0f && p.radius <= 10000.0f)) return "radius must be finite, > 0 and <= 10000";
+   if (!(p.strength >= 0.0f && p.strength < INFINITY)) return "strength must be finite and >= 0";
+   if (p.blur_radius > 4) return "blur_radius must be 0..4";
+   if (std::isnan(p.blur_normal_cos) || std::isnan(p.blur_plane)) return "blur_normal_cos and blur_plane must not be NaN";
+   return nullptr;
+}
+
+int uh_set_rtao_params(uh_ctx* c, const UhRtaoParams* params) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!params) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_set_rtao_params: null params");
+   if (const char* why = rtao_params_refusal(*params)) return fail(c, UH_ERR_INVALID_ARGUMENT, std::string("uh_set_rtao_params: ") + why);
+   c->hy.ao_params = *params;
+   return UH_OK;
+}
+
+int uh_get_rtao_stats(uh_ctx* c, UhRtaoStats* out) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_rtao_stats: null destination");
+   std::memset(out, 0, sizeof(*out));
+   const uh_ctx::Hybrid& h = c->hy;
+   if (h.ao_renders == 0) return UH_OK;
+   HIP_TRY(c, hipSetDevice(c->device));
+   if (int st = sync_all(c)) return st;
+   if (int st = stage_ms(c, c->hy.stage[kStRtaoTrace], &out->trace_ms)) return st;
+   if (int st = stage_ms(c, c->hy.stage[kStRtaoFilter], &out->filter_ms)) return st;
+   uint32_t counters[2] = {0, 0};
+   HIP_TRY(c, hipMemcpy(counters, h.ao_counters.p, sizeof(counters), hipMemcpyDeviceToHost));
+   out->pixels = counters[0];
+   out->rays = (uint64_t)counters[0] * h.ao_samples;
+   out->occluded = counters[1];
+   return UH_OK;
+}
+
+int uh_get_rtao_visits(uh_ctx* c, uint64_t* nodes, uint64_t* triangles) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!nodes || !triangles) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_rtao_visits: null destination");
+   *nodes = *triangles = 0;
+   const uh_ctx::Hybrid& h = c->hy;
+   if (h.ao_renders == 0) return UH_OK;
+   HIP_TRY(c, hipSetDevice(c->device));
+   if (int st = sync_all(c)) return st;
+   uint64_t visits[2] = {0, 0};
+   HIP_TRY(c, hipMemcpy(visits, h.ao_counters.p + 2, sizeof(visits), hipMemcpyDeviceToHost));
+   *nodes = visits[0];
+   *triangles = visits[1];
    return UH_OK;
 }
 

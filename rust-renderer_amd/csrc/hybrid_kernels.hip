@@ -300,11 +300,6 @@ __device__ __forceinline__ V3 bilinear_rgb(const float4* __restrict__ img, uint3
    const V3 b = t01 * (1.0f - ax) + t11 * ax;
    return a * (1.0f - ay) + b * ay;
 }
-__device__ __forceinline__ uint32_t unorm16(float x) {
-   if (!(x > 0.0f)) x = 0.0f;
-   if (x > 1.0f) x = 1.0f;
-   return (uint32_t)rintf(x * 65535.0f);
-}
 
 // ssao.frag:31-64, the fixed kernel (kernelSamples[i].xyz)
 __device__ __forceinline__ V3 ssao_sample(int i) {

@@ -366,3 +366,32 @@ class DenoiseStats(C.Structure):
 
 assert C.sizeof(DenoiseStats) == 32 and DenoiseStats.geometry_pixels.offset == 16 and DenoiseStats.history_pixels.offset == 20 and \
     DenoiseStats.reserved.offset == 24
+
+
+# ray-traced ambient occlusion in the hybrid frame's SSAO slot (an extension; utopian_hip.h "UH_HYBRID_RTAO"); bit 9 stays unused
+HYBRID_RTAO = 1 << 13
+HYBRID_AO_COUNTS = 14
+
+
+class RtaoParams(C.Structure):
+    """UhRtaoParams: rays per geometry pixel (1..64), their reach in world units, the strength of ao = 1 - strength * occluded / samples,
+    the filter's radius (0 none, else 1..4: taps in [-r, r)^2) and a tap's normal and plane thresholds; uh_rtao_default_params fills
+    the defaults"""
+
+    _fields_ = [("samples", C.c_uint32), ("radius", C.c_float), ("strength", C.c_float), ("blur_radius", C.c_uint32),
+                ("blur_normal_cos", C.c_float), ("blur_plane", C.c_float)]
+
+
+assert C.sizeof(RtaoParams) == 24 and RtaoParams.radius.offset == 4 and RtaoParams.strength.offset == 8 and RtaoParams.blur_radius.offset == 12 and \
+    RtaoParams.blur_normal_cos.offset == 16 and RtaoParams.blur_plane.offset == 20
+
+
+class RtaoStats(C.Structure):
+    """UhRtaoStats: the last rtao pass - the pixels that cast, their rays, the occluded ones, hipEvent ms of classify + trace and of the
+    resolve / filter"""
+
+    _fields_ = [("pixels", C.c_uint64), ("rays", C.c_uint64), ("occluded", C.c_uint64), ("trace_ms", C.c_float), ("filter_ms", C.c_float)]
+
+
+assert C.sizeof(RtaoStats) == 32 and RtaoStats.rays.offset == 8 and RtaoStats.occluded.offset == 16 and RtaoStats.trace_ms.offset == 24 and \
+    RtaoStats.filter_ms.offset == 28
