@@ -243,7 +243,7 @@ typedef struct uh_ctx uh_ctx;
  *        uh_unpack_tiles, uh_compose_tiles, uh_resolve_output, uh_add_isosurface_mesh, uh_update_isosurface_mesh (it reads the
  *        triangle total, 8 bytes, back to size its buffers), uh_get_isosurface_update_stats, uh_update_mesh_vertices (device input:
  *        it reads a 4-byte verdict on the caller's buffer back before it takes it), uh_get_mesh_update_stats, uh_read_denoised,
- *        uh_get_denoise_stats, uh_reset_denoise_history, uh_get_rtao_stats, uh_get_rtao_visits, uh_destroy;
+ *        uh_get_denoise_stats, uh_reset_denoise_history, uh_get_rtao_stats, uh_get_rtao_visits, uh_get_motion_stats, uh_destroy;
  *   enqueues like a frame, ordered behind the frames in flight and before those that follow:  uh_rccl_gather_tiles, uh_mgpu_compose;
  *        uh_set_option for "frames_in_flight" and for "time_kernels" 1 -> 0 (the others only change what the NEXT enqueued
  *        frame does: "furnace", "sun_grid*", "camera_grid*", "overlap", "batch_frames", "trace_blocks_per_cu", "count_visits",
@@ -641,7 +641,7 @@ int uh_mgpu_set_option(uh_mgpu* group, const char* name, int value);
  * UH_HYBRID_RT_REFLECTIONS with view->ibl_enabled == 1 is UH_ERR_INVALID_ARGUMENT - and nothing runs - until the IBL maps (irradiance,
  * specular, BRDF LUT of ibl.rs) have been built with UH_HYBRID_ENVIRONMENT, below; mask bits, UH_ERR_NOT_BUILT and moved instances with
  * view->rebuild_tlas as for uh_render_frame (bits above UH_HYBRID_SHADOW_MAPS, below, are ignored, except UH_HYBRID_MARCHING_CUBES,
- * UH_HYBRID_GBUFFER_RASTER, UH_HYBRID_RESTIR_LIGHTS and UH_HYBRID_RTAO).
+ * UH_HYBRID_GBUFFER_RASTER, UH_HYBRID_RESTIR_LIGHTS, UH_HYBRID_RTAO and UH_HYBRID_MOTION).
  * STREAM ORDER: uh_render_hybrid enqueues like a frame (behind the frames in flight, ahead of those that follow); uh_read_hybrid and
  * uh_get_hybrid_stats wait for all work of the context and are complete on return. The exception is UH_HYBRID_SHADOW_MAPS, below: a
  * call that renders shadow maps BLOCKS the host until the frames in flight and the pass's binning have finished (it reads the
@@ -1047,12 +1047,22 @@ int uh_get_hybrid_restir_stats(uh_ctx* ctx, UhHybridRestirStats* out);
  * view->prev_frame_projection_view is projection * view of the previous uh_denoise call; view->view gives the depth the plane
  * tolerances scale with.
  * HISTORY: the call keeps its own copies of this frame's position, normal with the mesh index beside it, temporal colour, history
- * length and moments for the next call (the hybrid targets are overwritten by then). The scene is assumed static between calls: after
- * uh_update_isosurface_mesh / uh_update_mesh_vertices / uh_set_instance_transform with a refit, call uh_reset_denoise_history, or accept
- * ghosting on the moved mesh. Without UH_DENOISE_TEMPORAL every call starts from no history (and still leaves one).
+ * length and moments for the next call (the hybrid targets are overwritten by then). Without UH_DENOISE_MOTION the scene is assumed
+ * static between calls: after uh_update_isosurface_mesh / uh_update_mesh_vertices / uh_set_instance_transform with a refit, render the
+ * G-buffer with UH_HYBRID_MOTION and set UH_DENOISE_MOTION (below, "motion vectors") and the history follows the moved mesh; without
+ * the flag, call uh_reset_denoise_history, or accept ghosting on the moved mesh. Without UH_DENOISE_TEMPORAL every call starts from no
+ * history (and still leaves one).
+ * UH_DENOISE_MOTION (bit 3; bit 2 stays an unknown flag): with UH_DENOISE_TEMPORAL, a geometry pixel whose motion texel
+ * (UH_HYBRID_MOTION_IMAGE) has w == 1 reprojects that texel's xyz - where its surface point was at the previous motion pass - instead of
+ * its position: through prev_frame_projection_view, and in the plane test |dot(q - p_prev, n)| <= tol. The normal n, the mesh-index test,
+ * tol (from the CURRENT view depth) and the bilinear weights are as without the flag. A pixel whose motion texel has w == 0 keeps no
+ * history: N = 1, this frame's colour and moments, not counted in history_pixels. The history normal is still compared with the current
+ * normal: a mesh that turns by more than acos(reproject_normal_cos) in one frame loses its history (noise, not ghosting). Without
+ * UH_DENOISE_TEMPORAL the flag is accepted and has no effect. On a static scene the flag changes no bit of any image.
  * UH_ERR_INVALID_ARGUMENT with a message - nothing runs, the history is untouched: a null view or params; no hybrid G-buffer rendered
  * yet; n == 0; iterations > 5; a non-zero reserved word; unknown flag bits; a parameter outside its range (below) or not finite; a
- * tile partition with world > 1 is set (uh_set_tile_partition: the accumulation is then partial). UH_ERR_NOT_BUILT before
+ * tile partition with world > 1 is set (uh_set_tile_partition: the accumulation is then partial); UH_DENOISE_MOTION when the last
+ * G-buffer pass had no UH_HYBRID_MOTION. UH_ERR_NOT_BUILT before
  * uh_build_acceleration, as for a frame.
  * ISOLATION: the call changes no accumulation, reservoir, gbuffer_position, hybrid image, grid or UhStats.
  * RESOURCES: 204 bytes per pixel (two history sets of 56, two filter images of 16, the input, temporal and colour images of 16, the
@@ -1063,6 +1073,7 @@ int uh_get_hybrid_restir_stats(uh_ctx* ctx, UhHybridRestirStats* out);
  * wait and are complete on return.
  * Arithmetic: DESIGN.md section 2, "Denoiser: the arithmetic contract of uh_denoise". */
 enum { UH_DENOISE_TEMPORAL = 1u << 0, UH_DENOISE_DEMODULATE = 1u << 1 };
+enum { UH_DENOISE_MOTION = 1u << 3 /* bit 2 stays an unknown flag */ };
 typedef struct UhDenoiseParams {
    uint32_t flags;             /* UH_DENOISE_* */
    uint32_t iterations;        /* a-trous levels, 0..5; level i has step 2^i */
@@ -1162,6 +1173,47 @@ int uh_get_rtao_stats(uh_ctx* ctx, UhRtaoStats* out);            /* waits; all z
 /* measurement: the node visits and triangle tests of the last pass's walks, counted while option "count_visits" is 1 (the kernel is
  * then another instantiation, a little slower); 0 otherwise. Waits. */
 int uh_get_rtao_visits(uh_ctx* ctx, uint64_t* nodes, uint64_t* triangles);
+
+/* ---- motion vectors: where each G-buffer pixel's surface point was one motion pass ago ----------------------------------------------------
+ * An EXTENSION: the reference's G-buffer has no velocity target. UH_HYBRID_MOTION (bit 14; bit 9 stays unused and ignored) is a modifier
+ * of UH_HYBRID_GBUFFER, as UH_HYBRID_GBUFFER_RASTER is: without the G-buffer bit in the same call it is ignored. With it the G-buffer pass,
+ * cast or rasterised, also writes UH_HYBRID_MOTION_IMAGE (RGBA32F, G-buffer orientation): xyz the PREVIOUS world position of the pixel's
+ * surface point, w 1 where there is a correspondence and 0 where there is none. "Previous" is the previous uh_render_hybrid call that had
+ * the bit: the context keeps, per mesh, the object-to-world 3x4 the tree was baked with then and (16 bytes per vertex) the object-space
+ * positions then, both snapshotted on the stream behind each motion pass; only meshes whose vertices changed are copied again.
+ *   state of a mesh at a pass   static    its transform is bit-identical to the snapshot's, its vertices not updated since
+ *                               rigid     the transform differs, the vertices were not updated
+ *                               deformed  uh_update_mesh_vertices since the snapshot (the transform may differ too)
+ *                               none      not in the snapshot (added since), or uh_update_isosurface_mesh since
+ *                               At the first pass ever every mesh is static.
+ *   texel     not geometry (position w == 0): (0, 0, 0, 0). static: the position texel's xyz, the same bits, w 1. none: the position
+ *             texel's xyz, w 0. rigid / deformed: o = (q0 b0 + q1 b1) + q2 b2 with b0 = 1 - u - v, b1 = u, b2 = v of the pixel's triangle
+ *             as the G-buffer pass forms them, q the triangle's object-space corners - the previous ones when deformed, the current ones
+ *             when rigid -, xyz = prev_o2w (o, 1), w 1.
+ * READ-BACK (uh_read_hybrid, UH_ERR_INVALID_ARGUMENT before the first motion pass): UH_HYBRID_MOTION_IMAGE.
+ * The denoiser follows the image with UH_DENOISE_MOTION (above). Per frame of a moving scene: the updates, view.rebuild_tlas = 1,
+ * uh_render_frame, uh_render_hybrid(UH_HYBRID_GBUFFER | UH_HYBRID_MOTION), uh_denoise(UH_DENOISE_TEMPORAL | UH_DENOISE_MOTION); no reset.
+ * RESOURCES: 16 bytes per pixel, 16 bytes per vertex of the meshes uh_update_mesh_vertices can deform (isosurface meshes hold no row: they
+ * are never `deformed`), 64 bytes per mesh and 64 KiB of per-block counts, allocated by the first call with the bit; freed by
+ * uh_destroy. A context that never sets the bit allocates nothing and runs no new code.
+ * STREAM ORDER: as uh_render_hybrid. uh_get_motion_stats waits.
+ * ISOLATION: the bit changes no other hybrid image, reservoir, accumulation, grid or UhStats; UhHybridStats is untouched. Without the bit
+ * every pass is what it was. No uh_mgpu_ twin.
+ * Arithmetic: DESIGN.md section 2, "Motion vectors". */
+enum { UH_HYBRID_MOTION = 1u << 14 };
+enum { UH_HYBRID_MOTION_IMAGE = 15 /* RGBA32F, G-buffer orientation: previous world position, w = 1 with a correspondence, else 0 */ };
+/* the last motion pass: the geometry pixels with (w == 1) and without (w == 0) a correspondence, the meshes per state, and the hipEvent
+ * times of the motion kernel and of the snapshot behind it. All zero before the first pass. Waits for all work of the context. */
+typedef struct UhMotionStats {
+   uint32_t pixels_with, pixels_without;
+   uint32_t meshes_static, meshes_rigid, meshes_deformed, meshes_none;
+   float motion_ms, snapshot_ms;
+} UhMotionStats;
+UH_LAYOUT_ASSERT(sizeof(UhMotionStats) == 32 && offsetof(UhMotionStats, pixels_without) == 4 && offsetof(UhMotionStats, meshes_static) == 8 &&
+                    offsetof(UhMotionStats, meshes_rigid) == 12 && offsetof(UhMotionStats, meshes_deformed) == 16 &&
+                    offsetof(UhMotionStats, meshes_none) == 20 && offsetof(UhMotionStats, motion_ms) == 24 && offsetof(UhMotionStats, snapshot_ms) == 28,
+                 "UhMotionStats (32 B)");
+int uh_get_motion_stats(uh_ctx* ctx, UhMotionStats* out); /* waits; all zero before the first pass */
 
 #ifdef __cplusplus
 }

@@ -304,7 +304,7 @@ class Renderer {
    // G-buffer pass, rt_reflections on the new one, then SSAO, deferred, sky and present - for the bits of `mask` (utopian_hip.h
    // "uh_render_hybrid")
    void render_hybrid(const UhViewUniformData& view, uint32_t mask = UH_HYBRID_ALL) { check(uh_render_hybrid(ctx_, &view, mask), "render_hybrid"); }
-   // one image as bytes: W*H texels of 16 (position, normal, pbr, deferred output), 4 (albedo, reflections, present output, the
+   // one image as bytes: W*H texels of 16 (position, normal, pbr, deferred output, the motion image of UH_HYBRID_MOTION), 4 (albedo, reflections, present output, the
    // marching-cubes and rasterised G-buffer depth floats and draw indices uint32), 2 (SSAO) or 1 (shadows, light visibility, the
    // occluded-ray counts of UH_HYBRID_RTAO) bytes
    std::vector<uint8_t> read_hybrid(int which) {
@@ -314,7 +314,8 @@ class Renderer {
                            : (which == UH_HYBRID_ALBEDO || which == UH_HYBRID_REFLECTIONS || which == UH_HYBRID_PRESENT_OUTPUT ||
                               which == UH_HYBRID_DEPTH || which == UH_HYBRID_MARCHING_CUBES_VISIBILITY || which == UH_HYBRID_GBUFFER_DEPTH ||
                               which == UH_HYBRID_GBUFFER_VISIBILITY) ? 4
-                                                                     : 16;
+                                                                     : 16;  // (UH_HYBRID_MOTION_IMAGE among them)
+      static_assert(UH_HYBRID_MOTION_IMAGE == 15, "read_hybrid sizes image 15 as 16-byte texels");
       std::vector<uint8_t> out((size_t)width_ * height_ * texel);
       check(uh_read_hybrid(ctx_, which, out.data()), "read_hybrid");
       return out;
@@ -359,6 +360,13 @@ class Renderer {
    UhRtaoStats rtao_stats() {
       UhRtaoStats s;
       check(uh_get_rtao_stats(ctx_, &s), "rtao_stats");
+      return s;
+   }
+   // motion vectors (UH_HYBRID_GBUFFER | UH_HYBRID_MOTION; utopian_hip.h "motion vectors"): the last motion pass's pixels with and
+   // without a correspondence, its meshes per state, and the times of the motion kernel and of the snapshot behind it
+   UhMotionStats motion_stats() {
+      UhMotionStats s;
+      check(uh_get_motion_stats(ctx_, &s), "motion_stats");
       return s;
    }
    // the denoiser (utopian_hip.h "the denoiser"): the accumulation of the last render_frame over the G-buffer of the last render_hybrid,

@@ -45,6 +45,7 @@ from .types import (
     HYBRID_GBUFFER_VISIBILITY,
     HYBRID_LIGHT_VISIBILITY,
     HYBRID_MARCHING_CUBES_VISIBILITY,
+    HYBRID_MOTION_IMAGE,
     HYBRID_NORMAL,
     HYBRID_POSITION,
     HYBRID_PBR,
@@ -61,6 +62,7 @@ from .types import (
     GbufferRasterStats,
     IsosurfaceUpdateStats,
     MeshUpdateStats,
+    MotionStats,
     MarchingCubesStats,
     ShadowmapParams,
     ShadowMapStats,
@@ -524,6 +526,7 @@ class Renderer:
         HYBRID_GBUFFER_VISIBILITY: (np.uint32, 1),
         HYBRID_LIGHT_VISIBILITY: (np.uint8, 1),
         HYBRID_AO_COUNTS: (np.uint8, 1),
+        HYBRID_MOTION_IMAGE: (np.float32, 4),
     }
 
     def read_hybrid(self, which):
@@ -531,10 +534,11 @@ class Renderer:
         present output (B, G, R, A), (H, W) uint8 shadows, (H, W) uint16 SSAO, (H, W) float32 marching-cubes depth buffer, (H, W) uint32
         marching-cubes draw index (MARCHING_CUBES_NONE where none survived), (H, W) float32 rasterised G-buffer depth, (H, W) uint32
         rasterised G-buffer draw index (GBUFFER_NONE where none survived), (H, W) uint8 light visibility of HYBRID_RESTIR_LIGHTS,
-        (H, W) uint8 occluded-ray counts of HYBRID_RTAO"""
+        (H, W) uint8 occluded-ray counts of HYBRID_RTAO, (H, W, 4) float32 motion image of HYBRID_MOTION (previous world position, w = 1
+        with a correspondence)"""
         api = self._hybrid_api()
         if which not in self._HYBRID_IMAGES:
-            raise ValueError(f"hybrid image index {which} (0..14)")
+            raise ValueError(f"hybrid image index {which} (0..15)")
         dtype, ch = self._HYBRID_IMAGES[which]
         out = np.empty((self.height, self.width, ch) if ch > 1 else (self.height, self.width), dtype=dtype)
         self._check(api.read_hybrid(self._ctx, int(which), out.ctypes.data))
@@ -635,6 +639,18 @@ class Renderer:
         nodes, tris = C.c_uint64(), C.c_uint64()
         self._check(fn(self._ctx, C.byref(nodes), C.byref(tris)))
         return nodes.value, tris.value
+
+    # -- motion vectors (HYBRID_GBUFFER | HYBRID_MOTION; include/utopian_hip.h "motion vectors") ---
+    def motion_stats(self):
+        """UhMotionStats of the last motion pass: pixels_with / pixels_without a correspondence, meshes_static / _rigid / _deformed /
+        _none, motion_ms, snapshot_ms; all zero before the first pass"""
+        if self.backend != "hip":
+            raise NotImplementedError(f"motion vectors are a per-context verb of the HIP library; backend {self.backend!r} has none")
+        fn = self._lib.uh_get_motion_stats
+        fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(MotionStats)], C.c_int
+        s = MotionStats()
+        self._check(fn(self._ctx, C.byref(s)))
+        return s
 
     # -- the denoiser (uh_denoise; include/utopian_hip.h "the denoiser") --------------------
     def _denoise_fn(self, name, argtypes):

@@ -491,6 +491,21 @@ struct uh_ctx {
       UhRtaoParams ao_params{4, 1.0f, 1.0f, 2, 0.9f, 0.05f};
       uint32_t ao_renders = 0, ao_samples = 0;
       uint32_t ao_order = 0;                   // option "rtao_order" (rtao.hip: how the trace kernel's work items are laid out; 0 measured fastest)
+      // motion vectors (UH_HYBRID_MOTION), allocated by the first call with the bit: the motion image, the pass's counts (pixels with /
+      // without a correspondence, a pair per block of the kernel's grid, added up by uh_get_motion_stats), the per-mesh table the kernels read, and the previous-position table (16-byte rows with bases of
+      // their own: isosurface meshes, which are never `deformed`, hold none). mv_snap: the meshes as the last motion pass left them -
+      // the transform and HostMesh::serial then, and the mesh's rows
+      struct MotionSnap { float o2w[12]; uint64_t serial; uint32_t base, count; };
+      DevBuf<float4> mv_image, mv_prev;
+      DevBuf<MotionMesh> mv_table;
+      DevBuf<uint32_t> mv_counters;
+      std::vector<MotionSnap> mv_snap;
+      std::vector<MotionMesh> mv_rows;         // mv_table's host copy
+      Stage mv_stage[2];                       // the motion kernel, the snapshot behind it (the last pass's)
+      uint32_t mv_renders = 0, mv_states[4] = {0, 0, 0, 0};  // meshes per MotionState at the last pass
+      static constexpr uint32_t kMotionMaxBlocks = 8 * 1024;  // the grid's cap (8 blocks per CU) for any device this runs on
+      uint32_t mv_blocks = 0;                  // blocks of the last pass's grid
+      bool mv_last = false;                    // the last G-buffer pass enqueued had the bit (uh_denoise with UH_DENOISE_MOTION asks)
 
       // the three groups allocated on first use, each named once for allocation and uh_destroy: f(buffer, length), n pixels; a
       // group's last buffer is allocated last, its pointer says "allocated"
@@ -507,6 +522,7 @@ struct uh_ctx {
       }
       template <class F> void restir_images(size_t n, F&& f) { f(rl_vis, n), f(rl_queue, n), f(rl_counters, 2); }
       template <class F> void rtao_images(size_t n, F&& f) { f(ao_counts, (n + 3) & ~(size_t)3), f(ao_queue, n), f(ao_counters, 6); }
+      template <class F> void motion_images(size_t n, F&& f) { f(mv_prev, 0), f(mv_table, 0), f(mv_image, n), f(mv_counters, 2 * (size_t)kMotionMaxBlocks); }  // (the first two are grown by the pass)
       template <class F> void env_maps(F&& f) {
          const size_t cube = env_mip_offset(kEnvMips);
          f(env, cube), f(irr, 6 * (size_t)kEnvSize * kEnvSize), f(spec, cube), f(lut, (size_t)kLutSize * kLutSize);

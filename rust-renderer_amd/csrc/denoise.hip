@@ -24,6 +24,10 @@ __device__ __forceinline__ V3 dn_demodulator(const DenoiseDev& d, size_t i) {
 }
 
 // ---- stages 0 and 1: the input, the reprojected history, the temporal colour and moments ----
+// kMotion (UH_DENOISE_MOTION): the point that is reprojected and held against the history's plane is the motion texel's xyz - where the
+// pixel's surface point was at the previous motion pass - instead of p; a texel with w == 0 has no correspondence and keeps no history.
+// Without it the instantiation is the stage as it always was.
+template <bool kMotion>
 __global__ __launch_bounds__(256) void k_denoise_temporal(DenoiseDev d) {
    const uint32_t x = blockIdx.x * kDnRow + threadIdx.x, y = blockIdx.y * kDnRows + threadIdx.y;
    bool geo = false, kept = false;
@@ -48,8 +52,15 @@ __global__ __launch_bounds__(256) void k_denoise_temporal(DenoiseDev d) {
          const V3 p = xyz(P4), n = xyz(d.g_nrm[i]);
          const float mesh = d.g_pbr[i].w;
          float cr = r, cg = g, cb = b, m1 = l, m2 = l2, N = 1.0f;
-         if (d.temporal_on) {
-            const float4 h = mat4_mul(d.prev_pv, p.x, p.y, p.z, 1.0f);
+         V3 pp = p;
+         bool corresponds = true;
+         if (kMotion) {
+            const float4 mv = d.motion[i];
+            pp = xyz(mv);
+            corresponds = mv.w != 0.0f;
+         }
+         if (d.temporal_on && corresponds) {
+            const float4 h = mat4_mul(d.prev_pv, pp.x, pp.y, pp.z, 1.0f);
             const float u = (h.x / h.w) * 0.5f + 0.5f, v = 1.0f - ((h.y / h.w) * 0.5f + 0.5f);
             const float fx = u * (float)d.W - 0.5f, fy = v * (float)d.H - 0.5f;
             if (h.w > 0.0f && isfinite(fx) && isfinite(fy)) {
@@ -69,7 +80,7 @@ __global__ __launch_bounds__(256) void k_denoise_temporal(DenoiseDev d) {
                   const float4 qn = d.prev.nrm[j];
                   if (!(qn.w == mesh)) continue;
                   if (!(dot3(n, xyz(qn)) >= d.reproject_normal_cos)) continue;
-                  if (!(fabsf(dot3(xyz(q) - p, n)) <= tol)) continue;
+                  if (!(fabsf(dot3(xyz(q) - pp, n)) <= tol)) continue;
                   const float4 qc = d.prev.col[j];
                   const float2 qm = d.prev.mom[j];
                   sw = sw + w;
@@ -205,7 +216,12 @@ __global__ __launch_bounds__(256) void k_denoise_output(DenoiseDev d, const floa
    d.output[i] = resolve_color(c, 1u, 1u);
 }
 
-void launch_denoise_temporal(const LaunchCfg& c, const DenoiseDev& d) { k_denoise_temporal<<<dn_grid(d), dn_block(), 0, c.stream>>>(d); }
+void launch_denoise_temporal(const LaunchCfg& c, const DenoiseDev& d) {
+   if (d.motion)
+      k_denoise_temporal<true><<<dn_grid(d), dn_block(), 0, c.stream>>>(d);
+   else
+      k_denoise_temporal<false><<<dn_grid(d), dn_block(), 0, c.stream>>>(d);
+}
 void launch_denoise_variance(const LaunchCfg& c, const DenoiseDev& d) { k_denoise_variance<<<dn_grid(d), dn_block(), 0, c.stream>>>(d); }
 void launch_denoise_atrous(const LaunchCfg& c, const DenoiseDev& d, uint32_t level) {
    k_denoise_atrous<<<dn_grid(d), dn_block(), 0, c.stream>>>(d, d.cv[level & 1], d.cv[(level & 1) ^ 1], 1 << level);

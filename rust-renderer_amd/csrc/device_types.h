@@ -299,6 +299,22 @@ struct DenoiseDev {
    uint32_t temporal_on;           // UH_DENOISE_TEMPORAL and a history exists
    uint32_t demodulate;
    float max_history, alpha_min, sigma_luminance, sigma_plane, reproject_normal_cos, reproject_plane;
+   const float4* motion;           // UH_HYBRID_MOTION_IMAGE with UH_DENOISE_MOTION, else null (the launcher picks the instantiation)
+};
+
+// motion vectors (UH_HYBRID_MOTION; motion.hip, motion_device.h): one row per mesh of the scene, written by the host before a motion pass
+enum MotionState : uint32_t { kMotionStatic = 0, kMotionRigid = 1, kMotionDeformed = 2, kMotionNone = 3 };
+struct MotionMesh {                // 64 B
+   float prev_o2w[12];             // the object-to-world 3x4 (row-major) the tree was baked with at the previous motion pass
+   uint32_t prev_base, prev_count; // the mesh's rows in MotionDev::prev_pos at the previous pass (read when state is deformed)
+   uint32_t state;                 // MotionState
+   uint32_t pad;
+};
+struct MotionDev {
+   float4* image;                  // UH_HYBRID_MOTION_IMAGE
+   const MotionMesh* meshes;
+   const float4* prev_pos;         // object-space positions at the previous pass, w unused
+   uint32_t* counters;             // per block of the motion kernel's grid: [2 b] its geometry pixels with a correspondence, [2 b + 1] without
 };
 
 // launch wrappers implemented in kernels.hip, path_fused.hip, restir.hip, tiles.hip and hybrid_kernels.hip --------------------------------------------------
@@ -344,6 +360,13 @@ void launch_hybrid_clear(const LaunchCfg&, const HybridDev&);
 // the G-buffer cast of launch_gbuffer (same rays, same traversal choice) and the resolve of all four targets; the cast's ray and hit
 // records live in the targets themselves until the resolve (ray_o = normal, ray_d = pbr, hit = position target)
 void launch_hybrid_gbuffer(const LaunchCfg&, const FrameParams&, const SceneDev&, const HybridDev&, const SunGridDev* camera_grid);
+// its two halves, for a pass that runs k_hybrid_motion between them
+void launch_hybrid_gbuffer_cast(const LaunchCfg&, const FrameParams&, const SceneDev&, const HybridDev&, const SunGridDev* camera_grid);
+void launch_hybrid_gbuffer_resolve(const LaunchCfg&, const SceneDev&, const HybridDev&);
+// the motion pass (motion.hip): the cast form's kernel over the pixels' hit records, between the cast and the resolve; the snapshot of
+// n vertices' positions, vertex i of `src` to row i of `dst`
+void launch_hybrid_motion(const LaunchCfg&, const SceneDev&, const HybridDev&, const MotionDev&);
+void launch_motion_snapshot(const LaunchCfg&, const UhVertex* src, float4* dst, uint32_t n);
 void launch_hybrid_shadows(const LaunchCfg&, const SceneDev&, const HybridDev&);
 void launch_hybrid_frame_clear(const LaunchCfg&, const HybridDev&, const HybridFrameDev&);
 void launch_hybrid_ssao(const LaunchCfg&, const HybridDev&, const HybridFrameDev&);
@@ -456,6 +479,8 @@ void launch_forward_resolve(const LaunchCfg&, const ForwardDev&, bool seeded = f
 void launch_forward_shade(const LaunchCfg&, const SceneDev&, const ForwardDev&, const ForwardShade&, const ShadowLookup* shadow, bool flat = false);
 // the hybrid graph's rasterised G-buffer: gbuffer.frag on the surviving records of a resolve of the scene's meshes into hd's four targets
 void launch_gbuffer_raster_shade(const LaunchCfg&, const SceneDev&, const ForwardDev&, const HybridDev&);
+// the rasterised form's motion pass, on the same surviving records, behind launch_gbuffer_raster_shade (it reads the position target)
+void launch_gbuffer_raster_motion(const LaunchCfg&, const SceneDev&, const ForwardDev&, const HybridDev&, const MotionDev&);
 // the marching-cubes pass's depth buffer from the G-buffer positions, into fd.depth; P V column-major at fd.mats + 28
 void launch_mc_depth_seed(const LaunchCfg&, const float4* gbuffer_pos, const ForwardDev&);
 void launch_hybrid_light_prep(const LaunchCfg&, const HybridFrameDev&);

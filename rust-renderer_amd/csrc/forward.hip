@@ -23,6 +23,7 @@
 #include "device_math.h"
 #include "device_types.h"
 #include "hybrid_shading.h"
+#include "motion_device.h"
 #include "raster_device.h"
 #include "utopian_hip.h"
 
@@ -271,6 +272,8 @@ struct Fragment {
    HybridMesh m;
    V3 P, N;
    float uu, vv;
+   uint32_t tri;       // the draw index
+   float b0, b1, b2;   // the original triangle's barycentrics
 };
 template <bool kFlat>
 __device__ __forceinline__ Fragment fragment_at(const SceneDev& sc, const ForwardDev& fd, uint32_t i, uint32_t r) {
@@ -302,6 +305,8 @@ __device__ __forceinline__ Fragment fragment_at(const SceneDev& sc, const Forwar
    };
    fr.P = (world(v0) * b0 + world(v1) * b1) + world(v2) * b2;
    surface_attributes(sc, fr.m, v0, v1, v2, b0, b1, b2, fr.N, fr.uu, fr.vv);                  // vert, frag:44-53
+   fr.tri = t;
+   fr.b0 = b0, fr.b1 = b1, fr.b2 = b2;
    return fr;
 }
 
@@ -357,6 +362,31 @@ __global__ __launch_bounds__(kShadeBlock) void k_gbuffer_raster_shade(SceneDev s
    hd.nrm[i] = nrm;
    hd.alb[i] = alb;
    hd.pbr[i] = pbr;
+}
+
+// the motion texel (UH_HYBRID_MOTION) of pixel i on the same surviving record, behind k_gbuffer_raster_shade: the position texel it
+// wrote, the record's triangle and fragment_at's barycentrics into motion_device.h's motion_texel. One lane per pixel and round, one coalesced
+// 16-byte store; the normal and the texture coordinates of the prologue are not used and fall away.
+__global__ __launch_bounds__(kMotionBlock) void k_gbuffer_raster_motion(SceneDev sc, ForwardDev fd, HybridDev hd, MotionDev md) {
+   const uint32_t n = fd.W * fd.H;
+   MotionCount count;
+   for (uint32_t base = blockIdx.x * kMotionBlock; base < n; base += gridDim.x * kMotionBlock) {
+      const uint32_t i = base + threadIdx.x;
+      float4 out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      bool geo = false;
+      if (i < n) {
+         const uint32_t r = fd.rec_of[i];
+         if (r != kNone) {
+            geo = true;
+            const Fragment fr = fragment_at<false>(sc, fd, i, r);
+            const uint32_t* tri = fd.indices + 3 * (size_t)fr.tri;
+            out = motion_texel(hd, md, fr.mesh, fr.m.vertex_base, tri[0], tri[1], tri[2], fr.b0, fr.b1, fr.b2, hd.pos[i]);
+         }
+         md.image[i] = out;
+      }
+      count.add(geo, out.w);
+   }
+   count.store(md);
 }
 
 // the images as the first call finds them: forward_output (1, 1, 1, 0), depth 1.0, no visibility, present (255, 255, 255, 0)
@@ -433,6 +463,9 @@ void launch_forward_shade(const LaunchCfg& c, const SceneDev& sc, const ForwardD
 }
 void launch_gbuffer_raster_shade(const LaunchCfg& c, const SceneDev& sc, const ForwardDev& fd, const HybridDev& hd) {
    k_gbuffer_raster_shade<<<dim3((fd.W * fd.H + kShadeBlock - 1) / kShadeBlock), kShadeBlock, 0, c.stream>>>(sc, fd, hd);
+}
+void launch_gbuffer_raster_motion(const LaunchCfg& c, const SceneDev& sc, const ForwardDev& fd, const HybridDev& hd, const MotionDev& md) {
+   k_gbuffer_raster_motion<<<dim3(motion_blocks(fd.W * fd.H, c.num_cus)), kMotionBlock, 0, c.stream>>>(sc, fd, hd, md);
 }
 void launch_mc_depth_seed(const LaunchCfg& c, const float4* gbuffer_pos, const ForwardDev& fd) {
    k_mc_depth_seed<<<dim3((fd.W * fd.H + kShadeBlock - 1) / kShadeBlock), kShadeBlock, 0, c.stream>>>(gbuffer_pos, fd);

@@ -13,6 +13,7 @@
 
 #include "context_state.h"
 #include "device_scan.h"
+#include "motion_device.h"
 
 // ---- the timed stages of both graphs (context_state.h Stage) ----
 // a stage runs between its two events on the graph's stream; stage_ms: its time in the last call that ran it, 0 when that did not
@@ -83,6 +84,8 @@ void destroy_graphs(uh_ctx* c) {
    h.mc_images(0, release);
    h.restir_images(0, release);
    h.rtao_images(0, release);
+   h.motion_images(0, release);
+   stage_destroy(h.mv_stage, 2);
    if (h.rl_read) (void)hipEventDestroy(h.rl_read);
    h.mc_bins.each(release);
    h.gr.each(0, release);
@@ -547,13 +550,99 @@ static int render_mc_pass(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformDat
 // ---- the rasterised G-buffer (utopian_hip.h "UH_HYBRID_GBUFFER_RASTER"; forward.hip) ----
 static int raster_scene(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformData& view, RasterBins& b, const RasterTarget& t, ForwardDev& fd, const char* who, uint32_t* pieces);
 
-// raster_scene into the pass's own depth, visibility and records, then gbuffer.frag into the four targets
-static int render_gbuffer_raster(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformData& view, const HybridDev& hd) {
+// ---- motion vectors (utopian_hip.h "motion vectors"; motion.hip) ----
+// before a motion pass: the pass's buffers (first call with the bit) and the per-mesh table - every mesh's state against the snapshot the
+// previous motion pass left, with that snapshot's transform and rows
+static int motion_prepare(uh_ctx* c, MotionDev& md) {
+   uh_ctx::Hybrid& h = c->hy;
+   const char* const who = "uh_render_hybrid: motion vectors";
+   if (!h.mv_counters.p) {
+      if (int st = stage_create(c, h.mv_stage, 2)) return st;
+      if (int st = alloc_group(c, [&](auto f) { h.motion_images((size_t)c->W * c->H, f); })) return st;
+   }
+   const size_t nm = c->meshes.size();
+   if (int st = grow(c, h.mv_table, std::max<size_t>(1, nm), who)) return st;
+   h.mv_rows.assign(nm, MotionMesh{});
+   uint32_t states[4] = {0, 0, 0, 0};
+   for (size_t i = 0; i < nm; i++) {
+      const HostMesh& m = c->meshes[i];
+      MotionMesh& row = h.mv_rows[i];
+      std::memcpy(row.prev_o2w, m.o2w, sizeof(row.prev_o2w));
+      if (h.mv_renders == 0) {
+         row.state = kMotionStatic;  // the first pass ever: what uh_denoise assumes without the flag
+      } else if (i >= h.mv_snap.size()) {
+         row.state = kMotionNone;    // added since
+      } else {
+         const uh_ctx::Hybrid::MotionSnap& s = h.mv_snap[i];
+         std::memcpy(row.prev_o2w, s.o2w, sizeof(row.prev_o2w));
+         row.prev_base = s.base;
+         row.prev_count = s.count;
+         if (s.serial != m.serial)   // uh_update_isosurface_mesh re-extracts: no correspondence; uh_update_mesh_vertices keeps the topology
+            row.state = m.iso ? kMotionNone : kMotionDeformed;
+         else
+            row.state = std::memcmp(s.o2w, m.o2w, sizeof(s.o2w)) == 0 ? kMotionStatic : kMotionRigid;
+      }
+      states[row.state]++;
+   }
+   if (nm) HIP_TRY(c, hipMemcpyAsync(h.mv_table.p, h.mv_rows.data(), nm * sizeof(MotionMesh), hipMemcpyHostToDevice, c->stream));
+   std::memcpy(h.mv_states, states, sizeof(states));
+   h.mv_blocks = motion_blocks(c->W * c->H, c->num_cus);
+   if (h.mv_blocks > uh_ctx::Hybrid::kMotionMaxBlocks) return fail(c, UH_ERR_CAPACITY, std::string(who) + ": a device of more than 1024 compute units");
+   md = MotionDev{h.mv_image.p, h.mv_table.p, h.mv_prev.p, h.mv_counters.p};
+   return UH_OK;
+}
+
+// behind a motion pass, on its stream: the positions of the meshes whose vertices changed since the last snapshot (all of them the
+// first time and when a mesh was added: the rows are laid out again), and every mesh's transform and serial
+static int motion_snapshot(uh_ctx* c, const LaunchCfg& lc) {
+   uh_ctx::Hybrid& h = c->hy;
+   const size_t nm = c->meshes.size();
+   std::vector<uh_ctx::Hybrid::MotionSnap> snap(nm);
+   size_t rows = 0;
+   for (size_t i = 0; i < nm; i++) {
+      const HostMesh& m = c->meshes[i];
+      std::memcpy(snap[i].o2w, m.o2w, sizeof(snap[i].o2w));
+      snap[i].serial = m.serial;
+      snap[i].base = (uint32_t)rows;
+      snap[i].count = m.iso ? 0u : (uint32_t)m.num_vertices();  // an isosurface mesh is never `deformed`: no rows
+      rows += snap[i].count;
+   }
+   const bool relayout = h.mv_snap.size() != nm || !h.mv_prev.p;
+   if (relayout && h.mv_prev.n < std::max<size_t>(1, rows)) {
+      HIP_TRY(c, hipStreamSynchronize(c->stream));  // the pass read the old rows
+      if (int st = grow(c, h.mv_prev, std::max<size_t>(1, rows), "uh_render_hybrid: motion vectors")) return st;
+   }
+   // one launch per run of meshes to copy whose vertices and rows both follow one another (a whole-scene update: one launch)
+   size_t from = 0, to = 0, count = 0;
+   const auto flush = [&] {
+      if (count) launch_motion_snapshot(lc, h.vertices.p + from, h.mv_prev.p + to, (uint32_t)count);
+      count = 0;
+   };
+   for (size_t i = 0; i < nm; i++) {
+      if (!snap[i].count || (!relayout && h.mv_snap[i].serial == snap[i].serial)) continue;
+      if (count && (h.layout[i].vb != from + count || snap[i].base != to + count)) flush();
+      if (!count) from = h.layout[i].vb, to = snap[i].base;
+      count += snap[i].count;
+   }
+   flush();
+   HIP_TRY(c, hipGetLastError());
+   h.mv_snap = std::move(snap);
+   return UH_OK;
+}
+
+// raster_scene into the pass's own depth, visibility and records, then gbuffer.frag into the four targets; with `motion` the motion
+// pass on the same records behind it
+static int render_gbuffer_raster(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformData& view, const HybridDev& hd, const MotionDev* motion) {
    uh_ctx::Hybrid& h = c->hy;
    ForwardDev fd{};
    uint32_t pieces = 0;
    if (int st = raster_scene(c, lc, view, h.gr_bins, h.gr, fd, "uh_render_hybrid: rasterised G-buffer", &pieces)) return st;
    launch_gbuffer_raster_shade(lc, c->scene, fd, hd);
+   if (motion) {
+      HIP_TRY(c, stage_begin(h.mv_stage[0], c->stream));
+      launch_gbuffer_raster_motion(lc, c->scene, fd, hd, *motion);
+      HIP_TRY(c, stage_end(h.mv_stage[0], c->stream));
+   }
    h.gr_pieces = pieces;
    h.gr_renders++;
    return UH_OK;
@@ -677,6 +766,8 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    }
    if (mask & UH_HYBRID_ENVIRONMENT)
       if (int st = env_alloc(c)) return st;
+   // motion vectors: a modifier of the G-buffer pass, ignored without it
+   const bool motion = (mask & UH_HYBRID_MOTION) && (mask & UH_HYBRID_GBUFFER);
    const FrameParams fp = make_params(c, *view);
    HybridDev hd{};
    hd.pos = h.pos.p;
@@ -747,18 +838,43 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
       HIP_TRY(c, stage_end(h.stage[kStShadows], c->stream));
    }
    if (mask & UH_HYBRID_GBUFFER) {
+      MotionDev md{};
+      if (motion) {
+         h.mv_last = false;  // until this pass and its snapshot are enqueued
+         h.mv_stage[0].ran = h.mv_stage[1].ran = false;
+         if (int st = motion_prepare(c, md)) return st;
+      }
       HIP_TRY(c, stage_begin(h.stage[kStGbuffer], c->stream));
       if (raster) {
-         if (int st = render_gbuffer_raster(c, lc, *view, hd)) {
+         if (int st = render_gbuffer_raster(c, lc, *view, hd, motion ? &md : nullptr)) {
             h.stage[kStGbuffer].ran = false;  // no time for a pass that did not complete
             return st;
          }
+      } else if (motion) {
+         // k_hybrid_motion between the cast and the resolve: it reads the hit records the cast left in the targets
+         launch_hybrid_gbuffer_cast(lc, fp, c->scene, hd, grid ? &c->cam_dev : nullptr);
+         HIP_TRY(c, stage_begin(h.mv_stage[0], c->stream));
+         launch_hybrid_motion(lc, c->scene, hd, md);
+         HIP_TRY(c, stage_end(h.mv_stage[0], c->stream));
+         launch_hybrid_gbuffer_resolve(lc, c->scene, hd);
       } else {
          launch_hybrid_gbuffer(lc, fp, c->scene, hd, grid ? &c->cam_dev : nullptr);
       }
       HIP_TRY(c, stage_end(h.stage[kStGbuffer], c->stream));
       h.gbuffer_done = true;
       h.gbuffer_rasterised = raster;
+      h.mv_last = false;
+      if (motion) {
+         HIP_TRY(c, stage_begin(h.mv_stage[1], c->stream));
+         const int st = motion_snapshot(c, lc);
+         if (st) {
+            h.mv_stage[1].ran = false;
+            return st;
+         }
+         HIP_TRY(c, stage_end(h.mv_stage[1], c->stream));
+         h.mv_renders++;
+         h.mv_last = true;
+      }
    }
    // setup_cubemap_pass (mod.rs:121): after the G-buffer, before rt_reflections; the maps persist until the next build
    const IblMaps ibl{h.env.p, h.irr.p, h.spec.p, h.lut.p};
@@ -855,7 +971,7 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    const uh_ctx::Hybrid& h = c->hy;
    if (!h.counter.p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid before the first uh_render_hybrid");
-   if (which < 0 || which > UH_HYBRID_AO_COUNTS) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..14");
+   if (which < 0 || which > UH_HYBRID_MOTION_IMAGE) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..15");
    if (which >= UH_HYBRID_SSAO_IMAGE && which <= UH_HYBRID_PRESENT_OUTPUT && !h.sky_counter.p)
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 6..8 before the first call with an SSAO, deferred, sky or present bit");
    if ((which == UH_HYBRID_DEPTH || which == UH_HYBRID_MARCHING_CUBES_VISIBILITY) && h.mc_renders == 0)
@@ -866,12 +982,14 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image 13 before the first call with UH_HYBRID_RESTIR_LIGHTS");
    if (which == UH_HYBRID_AO_COUNTS && h.ao_renders == 0)
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image 14 before the first rtao pass (UH_HYBRID_RTAO with view.ssao_enabled = 1)");
+   if (which == UH_HYBRID_MOTION_IMAGE && h.mv_renders == 0)
+      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image 15 before the first motion pass (UH_HYBRID_GBUFFER | UH_HYBRID_MOTION)");
    // image k's pixels and its bytes per pixel, in UH_HYBRID_* image order
    const std::pair<const void*, size_t> img[] = {
       {h.pos.p, sizeof(float4)}, {h.nrm.p, sizeof(float4)}, {h.alb.p, sizeof(uchar4)}, {h.pbr.p, sizeof(float4)}, {h.shadow.p, 1},
       {h.refl.p, sizeof(uchar4)}, {h.ssao.p, sizeof(uint16_t)}, {h.deferred.p, sizeof(float4)}, {h.present.p, sizeof(uchar4)},
       {h.mc.depth.p, sizeof(float)}, {h.mc.vis.p, sizeof(uint32_t)}, {h.gr.depth.p, sizeof(float)}, {h.gr.vis.p, sizeof(uint32_t)},
-      {h.rl_vis.p, 1}, {h.ao_counts.p, 1}};
+      {h.rl_vis.p, 1}, {h.ao_counts.p, 1}, {h.mv_image.p, sizeof(float4)}};
    return read_back(c, out, img[which].first, (size_t)c->W * c->H * img[which].second);
 }
 
@@ -960,6 +1078,26 @@ int uh_get_rtao_visits(uh_ctx* c, uint64_t* nodes, uint64_t* triangles) {
    HIP_TRY(c, hipMemcpy(visits, h.ao_counters.p + 2, sizeof(visits), hipMemcpyDeviceToHost));
    *nodes = visits[0];
    *triangles = visits[1];
+   return UH_OK;
+}
+
+int uh_get_motion_stats(uh_ctx* c, UhMotionStats* out) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_get_motion_stats: null destination");
+   std::memset(out, 0, sizeof(*out));
+   uh_ctx::Hybrid& h = c->hy;
+   if (h.mv_renders == 0) return UH_OK;
+   HIP_TRY(c, hipSetDevice(c->device));
+   if (int st = sync_all(c)) return st;
+   if (int st = stage_ms(c, h.mv_stage[0], &out->motion_ms)) return st;
+   if (int st = stage_ms(c, h.mv_stage[1], &out->snapshot_ms)) return st;
+   std::vector<uint32_t> counts(2 * (size_t)h.mv_blocks);  // a pair per block of the kernel's grid
+   HIP_TRY(c, hipMemcpy(counts.data(), h.mv_counters.p, counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+   for (uint32_t b = 0; b < h.mv_blocks; b++) out->pixels_with += counts[2 * b], out->pixels_without += counts[2 * b + 1];
+   out->meshes_static = h.mv_states[kMotionStatic];
+   out->meshes_rigid = h.mv_states[kMotionRigid];
+   out->meshes_deformed = h.mv_states[kMotionDeformed];
+   out->meshes_none = h.mv_states[kMotionNone];
    return UH_OK;
 }
 
@@ -1298,7 +1436,7 @@ int uh_denoise_default_params(UhDenoiseParams* out) {
 
 // the first refusal of `p` by its own values, or nullptr
 static const char* denoise_params_refusal(const UhDenoiseParams& p) {
-   if (p.flags & ~(uint32_t)(UH_DENOISE_TEMPORAL | UH_DENOISE_DEMODULATE)) return "unknown flag bits";
+   if (p.flags & ~(uint32_t)(UH_DENOISE_TEMPORAL | UH_DENOISE_DEMODULATE | UH_DENOISE_MOTION)) return "unknown flag bits";
    if (p.iterations > 5) return "iterations above 5";
    if (p.max_history < 1) return "max_history below 1";
    for (uint32_t r : p.reserved)
@@ -1325,6 +1463,10 @@ int uh_denoise(uh_ctx* c, const UhViewUniformData* view, const UhDenoiseParams* 
       return fail(c, UH_ERR_INVALID_ARGUMENT,
                   "uh_denoise reads the hybrid G-buffer (position, normal, albedo, mesh index), and none has been rendered; call "
                   "uh_render_hybrid with UH_HYBRID_GBUFFER (same camera) first");
+   if ((params->flags & UH_DENOISE_MOTION) && !c->hy.mv_last)
+      return fail(c, UH_ERR_INVALID_ARGUMENT,
+                  "uh_denoise: UH_DENOISE_MOTION reads the motion image of the last G-buffer pass, and that pass had no UH_HYBRID_MOTION; render "
+                  "it with UH_HYBRID_GBUFFER | UH_HYBRID_MOTION, or clear the flag");
    if (!c->built) return fail(c, UH_ERR_NOT_BUILT, "uh_denoise before uh_build_acceleration");
    HIP_TRY(c, hipSetDevice(c->device));
    uh_ctx::Denoise& dn = c->dn;
@@ -1358,6 +1500,7 @@ int uh_denoise(uh_ctx* c, const UhViewUniformData* view, const UhDenoiseParams* 
    std::memcpy(d.prev_pv, view->prev_frame_projection_view, sizeof(d.prev_pv));
    d.temporal_on = ((params->flags & UH_DENOISE_TEMPORAL) && dn.have_history) ? 1u : 0u;
    d.demodulate = (params->flags & UH_DENOISE_DEMODULATE) ? 1u : 0u;
+   d.motion = ((params->flags & UH_DENOISE_MOTION) && d.temporal_on) ? h.mv_image.p : nullptr;  // (without a temporal stage: no effect)
    d.max_history = (float)params->max_history;
    d.alpha_min = params->alpha_min, d.sigma_luminance = params->sigma_luminance, d.sigma_plane = params->sigma_plane;
    d.reproject_normal_cos = params->reproject_normal_cos, d.reproject_plane = params->reproject_plane;

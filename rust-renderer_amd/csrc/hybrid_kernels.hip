@@ -249,11 +249,17 @@ __global__ __launch_bounds__(kBlock, 5) void k_hybrid_restir_trace(SceneDev sc, 
 void launch_hybrid_clear(const LaunchCfg& c, const HybridDev& hd) {
    k_hybrid_clear<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(hd, hd.W * hd.H);
 }
-void launch_hybrid_gbuffer(const LaunchCfg& c, const FrameParams& fp, const SceneDev& sc, const HybridDev& hd, const SunGridDev* camera_grid) {
-   const uint32_t n = hd.W * hd.H;
+void launch_hybrid_gbuffer_cast(const LaunchCfg& c, const FrameParams& fp, const SceneDev& sc, const HybridDev& hd, const SunGridDev* camera_grid) {
    const RawRays rr{hd.nrm, hd.pbr, hd.pos};
    launch_gbuffer_cast(c, fp, sc, rr, whole_frame(hd.W, hd.H), nullptr, camera_grid);
+}
+void launch_hybrid_gbuffer_resolve(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd) {
+   const uint32_t n = hd.W * hd.H;
    k_hybrid_gbuffer_resolve<<<stream_grid(c, n), kBlock, 0, c.stream>>>(sc, hd, n);
+}
+void launch_hybrid_gbuffer(const LaunchCfg& c, const FrameParams& fp, const SceneDev& sc, const HybridDev& hd, const SunGridDev* camera_grid) {
+   launch_hybrid_gbuffer_cast(c, fp, sc, hd, camera_grid);
+   launch_hybrid_gbuffer_resolve(c, sc, hd);
 }
 void launch_hybrid_shadows(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd) {
    const uint32_t full = c.num_cus * c.shadow_blocks_per_cu, need = (hd.W * hd.H + kBlock - 1) / kBlock;

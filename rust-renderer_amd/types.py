@@ -341,6 +341,7 @@ assert C.sizeof(HybridRestirStats) == 32 and HybridRestirStats.occluded.offset =
 
 # the denoiser (an extension; utopian_hip.h "the denoiser"): uh_denoise's flags, the images of uh_read_denoised, params and stats
 DENOISE_TEMPORAL, DENOISE_DEMODULATE = 1 << 0, 1 << 1
+DENOISE_MOTION = 1 << 3  # reproject through the motion image of HYBRID_MOTION; bit 2 stays an unknown flag
 DENOISE_COLOR, DENOISE_OUTPUT, DENOISE_INPUT, DENOISE_TEMPORAL_COLOR, DENOISE_HISTORY, DENOISE_VARIANCE = range(6)
 
 
@@ -395,3 +396,20 @@ class RtaoStats(C.Structure):
 
 assert C.sizeof(RtaoStats) == 32 and RtaoStats.rays.offset == 8 and RtaoStats.occluded.offset == 16 and RtaoStats.trace_ms.offset == 24 and \
     RtaoStats.filter_ms.offset == 28
+
+
+# motion vectors for moving geometry (an extension; utopian_hip.h "motion vectors"): a modifier of HYBRID_GBUFFER; bit 9 stays unused
+HYBRID_MOTION = 1 << 14
+HYBRID_MOTION_IMAGE = 15
+
+
+class MotionStats(C.Structure):
+    """UhMotionStats: the last motion pass - geometry pixels with and without a correspondence, the meshes per state, hipEvent ms of the
+    motion kernel and of the snapshot behind it"""
+
+    _fields_ = [("pixels_with", C.c_uint32), ("pixels_without", C.c_uint32), ("meshes_static", C.c_uint32), ("meshes_rigid", C.c_uint32),
+                ("meshes_deformed", C.c_uint32), ("meshes_none", C.c_uint32), ("motion_ms", C.c_float), ("snapshot_ms", C.c_float)]
+
+
+assert C.sizeof(MotionStats) == 32 and MotionStats.meshes_static.offset == 8 and MotionStats.meshes_none.offset == 20 and \
+    MotionStats.motion_ms.offset == 24 and MotionStats.snapshot_ms.offset == 28
