@@ -3,7 +3,7 @@
 // utopian::Renderer (utopian/src/renderer.rs), utopian::Raytracing (utopian/src/raytracing.rs) and
 // build_path_tracing_render_graph (utopian/src/renderers/mod.rs:189-375) for this path only.
 // struct uh_ctx is context_state.h; meshes, the tree builders and the refit are scene_build.hip; the hybrid and the forward graph
-// (uh_render_hybrid, uh_render_forward) are graphs.hip.
+// (uh_render_hybrid, uh_render_forward) are hybrid_graph.hip and forward_graph.hip over raster_driver.hip, the denoiser denoise_graph.hip.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: the library opens librccl at run time (uh_rccl_attach)
 #include <dlfcn.h>
@@ -1372,7 +1372,7 @@ int uh_set_option(uh_ctx* c, const char* name, int value) {
       // how the rtao trace kernel lays out its work (rtao.hip; same counts whichever): 0 (default) one ray per item, a pixel's samples
       // together; 1 one ray per item, one sample of consecutive pixels together; 2 one pixel per item, its lane walks the samples
       if (!range(0, 2)) return bad("must be 0..2");
-      c->hy.ao_order = (uint32_t)value;
+      c->hy.ao.order = (uint32_t)value;
    }
    else if (n == "texture_blocks")
       // 1: the textures added from now on are stored as overlapped blocks, a bilinear footprint in one cache line (texture_layout.h);
@@ -1382,9 +1382,9 @@ int uh_set_option(uh_ctx* c, const char* name, int value) {
       if (!range(16, 8192)) return bad("must be 16..8192");
       if ((uint32_t)value != c->shadow_map_size) {  // the maps go: the deferred pass with shadows is refused until they are rendered again
          if (int st = sync_all(c)) return st;
-         c->hy.shadow_maps([](auto& b, size_t) { b.release(); });
-         c->hy.s_bins.geom = 0;
-         c->hy.smap_size = 0;
+         c->hy.sm.destroy();
+         c->hy.sm.bins.geom = 0;
+         c->hy.sm.size = 0;
       }
       c->shadow_map_size = (uint32_t)value;
    }

@@ -1,6 +1,7 @@
-// context_state.h - struct uh_ctx and the types it is made of, for the three files that implement the context: context.hip (lifetime,
-// the path tracer, the multi-GPU composition), scene_build.hip (meshes, builders, refit) and graphs.hip (the hybrid and the forward
-// graph). Private: not installed, not part of the C ABI (include/utopian_hip.h), where uh_ctx stays opaque.
+// context_state.h - struct uh_ctx and the types it is made of, for the files that implement the context: context.hip (lifetime,
+// the path tracer, the multi-GPU composition), scene_build.hip (meshes, builders, refit) and the graphs (raster_driver.hip,
+// hybrid_graph.hip, forward_graph.hip, denoise_graph.hip; what they share: graphs_internal.h). Private: not installed, not part of
+// the C ABI (include/utopian_hip.h), where uh_ctx stays opaque.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -72,6 +73,11 @@ struct DevBuf {
       n = 0;
    }
 };
+// for a group's visitor (f(buffer, length)): frees every buffer it names (hidden, like every destroy() below: the library's dynamic
+// symbols stay the C ABI's)
+struct __attribute__((visibility("hidden"))) ReleaseBuf {
+   template <class Buf> void operator()(Buf& b, size_t) const { b.release(); }
+};
 
 // the on-device build's per-triangle sources in mesh order: 9 floats of object-space corners, the key mesh << 22 | primitive and a
 // ShadePacket (4 float4: normals and uvs of the three vertices, the mesh index) per triangle
@@ -101,7 +107,7 @@ struct __attribute__((visibility("hidden"))) BuildSources {
    }
 };
 
-// a rasteriser's binning buffers (graphs.hip bin_and_resolve): the shadow maps, the marching-cubes pass, the rasterised
+// a rasteriser's binning buffers (raster_driver.hip bin_and_resolve): the shadow maps, the marching-cubes pass, the rasterised
 // G-buffer and the forward pass have a set each; they grow with what is drawn
 struct RasterBins {
    DevBuf<uint32_t> tile_count, tile_cursor, rec_count, tri_mesh, chunks, entries;
@@ -123,12 +129,16 @@ struct RasterTarget {
    template <class F> void each(size_t n, F&& f) { f(depth, n), f(vis, n), f(rec_of, n), f(covered, 1); }
 };
 
-// one timed stage of a graph, between its two events (stage_begin / stage_end). ms: the elapsed time, resolved from the events by the
+// one timed stage of a graph, between its two events (graphs_internal.h timed). ms: the elapsed time, resolved from the events by the
 // first stats read after the stage ran and kept (a later read returns the same bits)
 struct Stage {
    hipEvent_t begin = nullptr, end = nullptr;
    bool ran = false, timed = false;
    float ms = 0.0f;
+   void destroy() {
+      for (hipEvent_t ev : {begin, end})
+         if (ev) (void)hipEventDestroy(ev);
+   }
 };
 
 // the hybrid graph's stages (uh_ctx::Hybrid::stage): its seven passes in the order of their UH_HYBRID_* bits, then the environment's,
@@ -417,7 +427,9 @@ struct uh_ctx {
    hipEvent_t ev_compose = nullptr;
 
    // the hybrid graph's passes (uh_render_hybrid): images, the metal-pixel queue and a copy of the scene's meshes as gbuffer.vert
-   // reads them, all allocated by the first call
+   // reads them, all allocated by the first call. Every feature below names its buffers once, in a visitor f(buffer, length) over
+   // n pixels that serves its first-use allocation and its destroy(): a group's last buffer is allocated last, its pointer says
+   // "allocated"; length 0: grown by the pass
    struct Hybrid {
       DevBuf<float4> pos, nrm, pbr;
       DevBuf<uchar4> alb, refl;
@@ -444,88 +456,131 @@ struct uh_ctx {
       DevBuf<HybridLight> lights;              // its records as the deferred pass reads them, the sun first
       size_t lights_uploaded = SIZE_MAX;       // c->lights.size() when raw_lights was uploaded
       uint32_t frame_lights = 0;               // lights the deferred pass of the last call evaluated (the sun included)
-      // the IBL maps of setup_cubemap_pass (UH_HYBRID_ENVIRONMENT), allocated by the first call that builds them
-      DevBuf<float4> env, irr, spec;
-      DevBuf<uint32_t> lut;
-      DevBuf<float4> taps;                     // the irradiance filter's tap table
-      uint32_t env_builds = 0;
-      float env_sun[3] = {0, 0, 0}, env_eye[3] = {0, 0, 0};  // what the last build was made with
-      // the cascaded shadow maps (UH_HYBRID_SHADOW_MAPS), allocated by the first call that renders them; freed by a size change
-      DevBuf<float> smaps;                     // 4 layers of smap_size^2
-      DevBuf<UhShadowmapParams> s_params;      // the snapshot the deferred pass reads
-      RasterBins s_bins;                       // rec_count: [cascade][triangle]; mats: [cascade][mesh][16]
-      bool params_set = false;
-      UhShadowmapParams params{}, snapshot{}, pending{};  // the last uh_set_shadowmap_params; what the maps were rendered with;
-                                                          // what the render in progress uses
-      uint32_t s_renders = 0, smap_size = 0, s_tris[4] = {0, 0, 0, 0};
       bool gbuffer_done = false;               // a G-buffer pass has been enqueued (the marching-cubes pass's depth seed reads it)
       bool gbuffer_rasterised = false;         // the last G-buffer pass enqueued was rasterised: its depth is the marching-cubes seed
-      // the rasterised G-buffer (UH_HYBRID_GBUFFER_RASTER), allocated by the first rasterised pass: its depth buffer, visibility,
-      // surviving records and binning buffers ([mesh][28] matrices)
-      RasterTarget gr;
-      RasterBins gr_bins;
-      uint32_t gr_renders = 0, gr_pieces = 0;
-      // the marching-cubes pass (UH_HYBRID_MARCHING_CUBES), allocated by the first pass: its depth buffer, visibility, surviving
-      // records, light records, extracted triangles and binning buffers, whose chunks also serve the extraction's scan and whose
-      // matrices are (P V) I column-major, the identity 3x4, then P V (44 floats)
-      RasterTarget mc;
-      RasterBins mc_bins;
-      DevBuf<HybridLight> mc_lights;
-      DevBuf<UhVertex> mc_verts;               // 3 per triangle, extraction order
-      DevBuf<uint32_t> mc_block_counts;
-      DevBuf<unsigned long long> mc_total;     // the extraction scan's grand total: triangles
-      DevBuf<HybridMesh> mc_mesh;              // mesh_index 0's maps with world = identity
-      uint32_t mc_renders = 0, mc_tris = 0, mc_pieces = 0, mc_lights_used = 0;
-      float mc_time = 0.0f;
-      // the reservoir lights (UH_HYBRID_RESTIR_LIGHTS), allocated by the first call with the bit: the light-visibility image, the queue
-      // of the pixels that cast a ray and the pass's counters (rays, occluded); rl_read: behind the call's last read of the reservoirs
-      DevBuf<uint8_t> rl_vis;
-      DevBuf<uint32_t> rl_queue, rl_counters;
-      hipEvent_t rl_read = nullptr;
-      uint32_t rl_renders = 0;
-      // ray-traced ambient occlusion (UH_HYBRID_RTAO), allocated by the first pass: the occluded-ray counts (a byte per pixel, rounded
-      // up to whole words: the trace kernel adds into them by words), the queue of the pixels that cast and the pass's counters
-      // (pixels, occluded, and with option "count_visits" the walks' node visits and triangle tests); ao_params: the last uh_set_rtao_params (the defaults before); ao_samples: the last pass's
-      DevBuf<uint8_t> ao_counts;
-      DevBuf<uint32_t> ao_queue, ao_counters;
-      UhRtaoParams ao_params{4, 1.0f, 1.0f, 2, 0.9f, 0.05f};
-      uint32_t ao_renders = 0, ao_samples = 0;
-      uint32_t ao_order = 0;                   // option "rtao_order" (rtao.hip: how the trace kernel's work items are laid out; 0 measured fastest)
-      // motion vectors (UH_HYBRID_MOTION), allocated by the first call with the bit: the motion image, the pass's counts (pixels with /
-      // without a correspondence, a pair per block of the kernel's grid, added up by uh_get_motion_stats), the per-mesh table the kernels read, and the previous-position table (16-byte rows with bases of
-      // their own: isosurface meshes, which are never `deformed`, hold none). mv_snap: the meshes as the last motion pass left them -
-      // the transform and HostMesh::serial then, and the mesh's rows
-      struct MotionSnap { float o2w[12]; uint64_t serial; uint32_t base, count; };
-      DevBuf<float4> mv_image, mv_prev;
-      DevBuf<MotionMesh> mv_table;
-      DevBuf<uint32_t> mv_counters;
-      std::vector<MotionSnap> mv_snap;
-      std::vector<MotionMesh> mv_rows;         // mv_table's host copy
-      Stage mv_stage[2];                       // the motion kernel, the snapshot behind it (the last pass's)
-      uint32_t mv_renders = 0, mv_states[4] = {0, 0, 0, 0};  // meshes per MotionState at the last pass
-      static constexpr uint32_t kMotionMaxBlocks = 8 * 1024;  // the grid's cap (8 blocks per CU) for any device this runs on
-      uint32_t mv_blocks = 0;                  // blocks of the last pass's grid
-      bool mv_last = false;                    // the last G-buffer pass enqueued had the bit (uh_denoise with UH_DENOISE_MOTION asks)
-
-      // the three groups allocated on first use, each named once for allocation and uh_destroy: f(buffer, length), n pixels; a
-      // group's last buffer is allocated last, its pointer says "allocated"
       template <class F> void rt_images(size_t n, F&& f) {
          f(pos, n), f(nrm, n), f(pbr, n), f(alb, n), f(refl, n), f(shadow, n), f(queue, n), f(counter, 1);
       }
       template <class F> void frame_images(size_t n, F&& f) {
          f(ssao, n), f(deferred, n), f(present, n), f(lights, UH_MAX_GPU_LIGHTS + 1), f(sky_counter, 1);
       }
-      template <class F> void shadow_maps(F&& f) { f(smaps, 0), f(s_params, 0), s_bins.each(f); }  // (all grown by the pass)
-      template <class F> void mc_images(size_t n, F&& f) {
-         f(mc_lights, UH_MAX_GPU_LIGHTS + 1), f(mc_block_counts, kMcBlocks), f(mc_bins.mats, 44), f(mc_mesh, 1), f(mc_total, 1), f(mc_bins.totals, 2),
-            f(mc_verts, 0), mc.each(n, f);  // (mc_verts and the rest of mc_bins are grown by the pass)
-      }
-      template <class F> void restir_images(size_t n, F&& f) { f(rl_vis, n), f(rl_queue, n), f(rl_counters, 2); }
-      template <class F> void rtao_images(size_t n, F&& f) { f(ao_counts, (n + 3) & ~(size_t)3), f(ao_queue, n), f(ao_counters, 6); }
-      template <class F> void motion_images(size_t n, F&& f) { f(mv_prev, 0), f(mv_table, 0), f(mv_image, n), f(mv_counters, 2 * (size_t)kMotionMaxBlocks); }  // (the first two are grown by the pass)
-      template <class F> void env_maps(F&& f) {
-         const size_t cube = env_mip_offset(kEnvMips);
-         f(env, cube), f(irr, 6 * (size_t)kEnvSize * kEnvSize), f(spec, cube), f(lut, (size_t)kLutSize * kLutSize);
+
+      // the IBL maps of setup_cubemap_pass (UH_HYBRID_ENVIRONMENT), allocated by the first call that builds them
+      struct __attribute__((visibility("hidden"))) Environment {
+         DevBuf<float4> cube, irr, spec;
+         DevBuf<uint32_t> lut;
+         DevBuf<float4> taps;                  // the irradiance filter's tap table (uploaded before the maps are allocated)
+         uint32_t builds = 0;
+         float sun[3] = {0, 0, 0}, eye[3] = {0, 0, 0};  // what the last build was made with
+         template <class F> void images(F&& f) {
+            const size_t mips = env_mip_offset(kEnvMips);
+            f(cube, mips), f(irr, 6 * (size_t)kEnvSize * kEnvSize), f(spec, mips), f(lut, (size_t)kLutSize * kLutSize);
+         }
+         void destroy() { images(ReleaseBuf{}), taps.release(); }
+      } env;
+
+      // the cascaded shadow maps (UH_HYBRID_SHADOW_MAPS), all grown by the first call that renders them; freed by a size change
+      struct __attribute__((visibility("hidden"))) ShadowMaps {
+         DevBuf<float> maps;                   // 4 layers of size^2
+         DevBuf<UhShadowmapParams> dev_params; // the snapshot the deferred pass reads
+         RasterBins bins;                      // rec_count: [cascade][triangle]; mats: [cascade][mesh][16]
+         bool params_set = false;
+         UhShadowmapParams params{}, snapshot{}, pending{};  // the last uh_set_shadowmap_params; what the maps were rendered with;
+                                                             // what the render in progress uses
+         uint32_t renders = 0, size = 0, tris[4] = {0, 0, 0, 0};
+         template <class F> void images(F&& f) { f(maps, 0), f(dev_params, 0), bins.each(f); }
+         void destroy() { images(ReleaseBuf{}); }
+      } sm;
+
+      // the rasterised G-buffer (UH_HYBRID_GBUFFER_RASTER), allocated by the first rasterised pass: its depth buffer, visibility,
+      // surviving records and binning buffers ([mesh][28] matrices)
+      struct __attribute__((visibility("hidden"))) GbufferRaster {
+         RasterTarget target;
+         RasterBins bins;
+         uint32_t renders = 0, pieces = 0;
+         template <class F> void images(size_t n, F&& f) { target.each(n, f); }  // (bins: grown by the pass)
+         void destroy() { images(0, ReleaseBuf{}), bins.each(ReleaseBuf{}); }
+      } gr;
+
+      // the marching-cubes pass (UH_HYBRID_MARCHING_CUBES), allocated by the first pass: its depth buffer, visibility, surviving
+      // records, light records, extracted triangles and binning buffers, whose chunks also serve the extraction's scan and whose
+      // matrices are (P V) I column-major, the identity 3x4, then P V (44 floats)
+      struct __attribute__((visibility("hidden"))) MarchingCubes {
+         RasterTarget target;
+         RasterBins bins;
+         DevBuf<HybridLight> lights;
+         DevBuf<UhVertex> verts;               // 3 per triangle, extraction order
+         DevBuf<uint32_t> block_counts;
+         DevBuf<unsigned long long> total;     // the extraction scan's grand total: triangles
+         DevBuf<HybridMesh> mesh;              // mesh_index 0's maps with world = identity
+         uint32_t renders = 0, tris = 0, pieces = 0, lights_used = 0;
+         float time = 0.0f;
+         template <class F> void images(size_t n, F&& f) {
+            f(lights, UH_MAX_GPU_LIGHTS + 1), f(block_counts, kMcBlocks), f(bins.mats, 44), f(mesh, 1), f(total, 1), f(bins.totals, 2), f(verts, 0);
+            target.each(n, f);  // (verts and the rest of bins are grown by the pass)
+         }
+         void destroy() { images(0, ReleaseBuf{}), bins.each(ReleaseBuf{}); }
+      } mc;
+
+      // the reservoir lights (UH_HYBRID_RESTIR_LIGHTS), allocated by the first call with the bit: the light-visibility image, the queue
+      // of the pixels that cast a ray and the pass's counters (rays, occluded); read: behind the call's last read of the reservoirs
+      struct __attribute__((visibility("hidden"))) RestirLights {
+         DevBuf<uint8_t> vis;
+         DevBuf<uint32_t> queue, counters;
+         hipEvent_t read = nullptr;
+         uint32_t renders = 0;
+         template <class F> void images(size_t n, F&& f) { f(vis, n), f(queue, n), f(counters, 2); }
+         void destroy() {
+            images(0, ReleaseBuf{});
+            if (read) (void)hipEventDestroy(read);
+         }
+      } rl;
+
+      // ray-traced ambient occlusion (UH_HYBRID_RTAO), allocated by the first pass: the occluded-ray counts (a byte per pixel, rounded
+      // up to whole words: the trace kernel adds into them by words), the queue of the pixels that cast and the pass's counters
+      // (pixels, occluded, and with option "count_visits" the walks' node visits and triangle tests); params: the last
+      // uh_set_rtao_params (the defaults before); samples: the last pass's
+      struct __attribute__((visibility("hidden"))) Rtao {
+         DevBuf<uint8_t> counts;
+         DevBuf<uint32_t> queue, counters;
+         UhRtaoParams params{4, 1.0f, 1.0f, 2, 0.9f, 0.05f};
+         uint32_t renders = 0, samples = 0;
+         uint32_t order = 0;                   // option "rtao_order" (rtao.hip: how the trace kernel's work items are laid out; 0 measured fastest)
+         template <class F> void images(size_t n, F&& f) { f(counts, (n + 3) & ~(size_t)3), f(queue, n), f(counters, 6); }
+         void destroy() { images(0, ReleaseBuf{}); }
+      } ao;
+
+      // motion vectors (UH_HYBRID_MOTION), allocated by the first call with the bit: the motion image, the pass's counts (pixels with /
+      // without a correspondence, a pair per block of the kernel's grid, added up by uh_get_motion_stats), the per-mesh table the
+      // kernels read, and the previous-position table (16-byte rows with bases of their own: isosurface meshes, which are never
+      // `deformed`, hold none). snap: the meshes as the last motion pass left them - the transform and HostMesh::serial then, and the
+      // mesh's rows
+      struct __attribute__((visibility("hidden"))) Motion {
+         struct Snap { float o2w[12]; uint64_t serial; uint32_t base, count; };
+         DevBuf<float4> image, prev;
+         DevBuf<MotionMesh> table;
+         DevBuf<uint32_t> counters;
+         std::vector<Snap> snap;
+         std::vector<MotionMesh> rows;         // table's host copy
+         Stage stage[2];                       // the motion kernel, the snapshot behind it (the last pass's)
+         uint32_t renders = 0, states[4] = {0, 0, 0, 0};  // meshes per MotionState at the last pass
+         static constexpr uint32_t kMaxBlocks = 8 * 1024;  // the grid's cap (8 blocks per CU) for any device this runs on
+         uint32_t blocks = 0;                  // blocks of the last pass's grid
+         bool last = false;                    // the last G-buffer pass enqueued had the bit (uh_denoise with UH_DENOISE_MOTION asks)
+         template <class F> void images(size_t n, F&& f) { f(prev, 0), f(table, 0), f(image, n), f(counters, 2 * (size_t)kMaxBlocks); }
+         void destroy() {
+            images(0, ReleaseBuf{});
+            for (Stage& s : stage) s.destroy();
+         }
+      } mv;
+
+      __attribute__((visibility("hidden"))) void destroy() {
+         rt_images(0, ReleaseBuf{}), frame_images(0, ReleaseBuf{});
+         env.destroy(), sm.destroy(), gr.destroy(), mc.destroy(), rl.destroy(), ao.destroy(), mv.destroy();
+         meshes.release(), vertices.release(), indices.release(), raw_lights.release();
+         for (hipEvent_t ev : waits)
+            if (ev) (void)hipEventDestroy(ev);
+         for (Stage& s : stage) s.destroy();
       }
    } hy;
 
@@ -540,6 +595,10 @@ struct uh_ctx {
       Stage stage[3];                          // pass k: 0 shadow maps, 1 forward, 2 present (the last call's)
       uint32_t renders = 0, pieces = 0, lights_used = 0;
       template <class F> void images(size_t n, F&& f) { target.each(n, f), f(present, n), f(lights, UH_MAX_GPU_LIGHTS + 1), f(color, n); }
+      __attribute__((visibility("hidden"))) void destroy() {
+         images(0, ReleaseBuf{}), bins.each(ReleaseBuf{});
+         for (Stage& s : stage) s.destroy();
+      }
    } fw;
 
    // the denoiser (uh_denoise): two history sets (the previous call's, read, and this call's, written), the filter's two images and the
@@ -559,10 +618,15 @@ struct uh_ctx {
          for (int k = 0; k < 2; k++) f(h_pos[k], n), f(h_nrm[k], n), f(h_col[k], n), f(h_mom[k], n), f(cv[k], n);
          f(input, n), f(temporal, n), f(color, n), f(history, n), f(variance, n), f(output, n), f(counters, 2);
       }
+      __attribute__((visibility("hidden"))) void destroy() {  // (uh_ctx::last_acc may still name acc_read: destroy_graphs clears it first)
+         images(0, ReleaseBuf{});
+         for (Stage& s : stage) s.destroy();
+         if (acc_read) (void)hipEventDestroy(acc_read);
+      }
    } dn;
 };
 
-// ---- context.hip, for scene_build.hip and graphs.hip (not exported: the library's dynamic symbols stay the C ABI's) ----
+// ---- context.hip, for scene_build.hip and the graphs (not exported: the library's dynamic symbols stay the C ABI's) ----
 #pragma GCC visibility push(hidden)
 int fail(uh_ctx* c, int code, const std::string& msg);  // sets uh_last_error (c null: uh_create's); returns code
 #define HIP_TRY(ctx, expr)                                                                                   \
@@ -575,10 +639,10 @@ LaunchCfg cfg(uh_ctx* c);
 FrameParams make_params(uh_ctx* c, const UhViewUniformData& v);
 int sync_all(uh_ctx* c);
 int read_back(uh_ctx* c, void* dst, const void* src, size_t bytes);
-// ---- scene_build.hip, for graphs.hip ----
+// ---- scene_build.hip, for hybrid_graph.hip ----
 // brackets of UhIsosurfaceUpdateStats::scatter_ms on the context's stream (the mesh tables of device-resident meshes count into it)
 void iso_scatter_begin(uh_ctx* c);
 int iso_scatter_end(uh_ctx* c, bool add);
-// ---- graphs.hip, for uh_destroy ----
+// ---- hybrid_graph.hip, for uh_destroy ----
 void destroy_graphs(uh_ctx* c);  // everything uh_ctx::Hybrid, uh_ctx::Forward and uh_ctx::Denoise own; before the slots' streams go
 #pragma GCC visibility pop

@@ -1,0 +1,121 @@
+// graphs_internal.h - what the host files of the graphs share (raster_driver.hip, hybrid_graph.hip, forward_graph.hip,
+// denoise_graph.hip): the timed stages, first-use allocation, the preamble of the stats verbs and the entry points of one file that
+// another calls. Private, like context_state.h; nothing here is exported.
+#pragma once
+#include <cstring>
+#include <initializer_list>
+#include <string>
+#include <type_traits>
+
+#include "context_state.h"
+
+#pragma GCC visibility push(hidden)
+// ---- the timed stages of the graphs (context_state.h Stage) ----
+// a stage runs between its two events on the graph's stream; stage_ms: its time in the last call that ran it, 0 when that did not
+static int stage_create(uh_ctx* c, Stage* s, int n) {
+   for (int k = 0; k < n; k++)
+      for (hipEvent_t* ev : {&s[k].begin, &s[k].end})
+         if (!*ev) HIP_TRY(c, hipEventCreate(ev));
+   return UH_OK;
+}
+static hipError_t stage_begin(Stage& s, hipStream_t stream) {
+   const hipError_t e = hipEventRecord(s.begin, stream);
+   s.ran = e == hipSuccess;  // no time for a stage that did not begin
+   s.timed = false;
+   return e;
+}
+static hipError_t stage_end(Stage& s, hipStream_t stream) { return hipEventRecord(s.end, stream); }
+static int stage_ms(uh_ctx* c, Stage& s, float* out) {
+   *out = 0.0f;
+   if (!s.ran) return UH_OK;
+   if (!s.timed) {
+      HIP_TRY(c, hipEventElapsedTime(&s.ms, s.begin, s.end));
+      s.timed = true;
+   }
+   *out = s.ms;
+   return UH_OK;
+}
+// One timed pass: body() between the two events of every stage of `stages` on c->stream, begun in order and ended in order. body
+// returns nothing or an int status; a status other than UH_OK, or an end that fails, leaves every stage with ran = false (no time
+// for a pass that did not complete) and is what comes back.
+template <class Body> static int timed(uh_ctx* c, std::initializer_list<Stage*> stages, Body body) {
+   for (Stage* s : stages) HIP_TRY(c, stage_begin(*s, c->stream));
+   int st = UH_OK;
+   if constexpr (std::is_void_v<decltype(body())>)
+      body();
+   else
+      st = body();
+   hipError_t e = hipSuccess;
+   for (Stage* s : stages)
+      if (!st && e == hipSuccess) e = stage_end(*s, c->stream);
+   if (st || e != hipSuccess)
+      for (Stage* s : stages) s->ran = false;
+   if (st) return st;
+   HIP_TRY(c, e);
+   return UH_OK;
+}
+template <class Body> static int timed(uh_ctx* c, Stage& s, Body body) { return timed(c, {&s}, body); }
+
+// ---- first-use allocation ----
+// allocates one of the graphs' groups, visit(f) naming its buffers; stops at the first error, before the group's last buffer
+template <class Visit> static int alloc_group(uh_ctx* c, Visit visit) {
+   hipError_t e = hipSuccess;
+   visit([&e](auto& b, size_t n) {
+      if (e == hipSuccess) e = b.alloc(n);
+   });
+   if (e != hipSuccess)
+      return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string("uh_render_hybrid: allocation: ") + hipGetErrorString(e));
+   return UH_OK;
+}
+// b holds n elements or more: kept when it does, allocated again (its contents lost) when not
+template <class Buf> static int grow(uh_ctx* c, Buf& b, size_t n, const char* prefix) {
+   if (b.p && b.n >= n) return UH_OK;
+   const hipError_t e = b.alloc(n);
+   if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string(prefix) + ": allocation: " + hipGetErrorString(e));
+   return UH_OK;
+}
+
+// ---- the stats verbs ----
+// What every uh_get_*_stats begins with: a null context is UH_ERR_INVALID_ARGUMENT, a null destination that with `null_message`; the
+// destination's `bytes` are zeroed, and they are the answer (UH_OK) while nothing has `rendered`; else every stream is waited for.
+// false: *st is what the verb returns; true: the verb fills in its own.
+static bool stats_begin(uh_ctx* c, void* out, size_t bytes, const char* null_message, bool rendered, int* st) {
+   const auto run = [&]() -> int {
+      if (!c) return UH_ERR_INVALID_ARGUMENT;
+      if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, null_message);
+      std::memset(out, 0, bytes);
+      if (!rendered) return UH_OK;
+      HIP_TRY(c, hipSetDevice(c->device));
+      return sync_all(c);
+   };
+   *st = run();
+   return *st == UH_OK && c && out && rendered;
+}
+
+// ---- hybrid_graph.hip ----
+int hybrid_events(uh_ctx* c);          // the events of the hybrid stages and of wait_frames_in_flight (first hybrid or forward call)
+int wait_frames_in_flight(uh_ctx* c);  // c->stream (where the graphs run) waits for every other stream of the context
+int hybrid_tables(uh_ctx* c);          // the meshes as the vertex and fragment shaders read them (uh_ctx::Hybrid meshes, vertices, indices)
+int hybrid_light_table(uh_ctx* c);     // the uh_add_light table as the lit passes read it (uh_ctx::Hybrid::raw_lights)
+// the kernels' arguments from the context and the view: the targets, tables and frame of every hybrid kernel (sun: make_params'
+// normalised direction, or null for a pass that reads none), and those of the final frame's passes
+HybridDev hybrid_dev(const uh_ctx* c, const UhViewUniformData& view, const float* sun);
+HybridFrameDev hybrid_frame_dev(const uh_ctx* c, const UhViewUniformData& view);
+
+// ---- raster_driver.hip ----
+// the column-major product a b, and an instance's row-major 3x4 with row (0, 0, 0, 1), column-major
+void mat4_mul(const float* a, const float* b, float* o);
+void mat4_from_3x4(const float* o, float* w);
+// the frame and its tile grid into fd, with t as what it resolves into; returns the tiles
+uint32_t forward_frame(const uh_ctx* c, const RasterTarget& t, ForwardDev& fd);
+// k_hybrid_light_prep into the pass's own records (the sun first), then forward.frag over fd's surviving records
+void light_and_shade(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformData& view, const ForwardDev& fd, HybridLight* lights, bool flat);
+// fd.num_tris triangles (flat: bare vertex triples without indices or meshes) from forward.hip's count kernel to its resolve kernel
+// over `tiles` tiles: the caller has filled fd but its records and entries, and sized and zeroed b as bin_and_resolve asks
+int bin_forward(uh_ctx* c, const LaunchCfg& lc, RasterBins& b, ForwardDev& fd, uint32_t tiles, const char* who, bool flat, uint32_t* pieces);
+// the scene's meshes through the forward rasteriser into the target t: depth (cleared to 1.0), vis and rec_of; fd receives everything
+// but its colour target. *pieces receives the records. `who` names the entry point in messages.
+int raster_scene(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformData& view, RasterBins& b, const RasterTarget& t, ForwardDev& fd, const char* who, uint32_t* pieces);
+// the four cascades of uh_ctx::Hybrid::sm; `verb` names the entry point in messages
+int render_shadow_maps(uh_ctx* c, const LaunchCfg& lc, const char* verb);
+#pragma GCC visibility pop

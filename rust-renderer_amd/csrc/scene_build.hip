@@ -3,7 +3,7 @@
 // the refit (uh_refit_acceleration; refit.hip), and the device-resident meshes of uh_update_isosurface_mesh and uh_update_mesh_vertices
 // (deform.hip) with the mesh read-backs.
 // Host-side counterpart of Renderer::add_model (utopian/src/renderer.rs) and utopian::Raytracing (utopian/src/raytracing.rs).
-// Host code only; struct uh_ctx is context_state.h, the rest of the C ABI is context.hip and graphs.hip.
+// Host code only; struct uh_ctx is context_state.h, the rest of the C ABI is context.hip and the graphs (*_graph.hip).
 #include <hip/hip_runtime.h>
 
 #include <chrono>

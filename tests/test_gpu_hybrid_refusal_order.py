@@ -1,0 +1,86 @@
+"""GPU: uh_render_hybrid requests that break two of its rules at once are refused with the message of the rule checked first, and the
+second rule's own request with that rule's message - the order of the checks, on the synthetic scene at 24 x 16. The context has no
+G-buffer, no reservoirs, no light, no IBL maps and no cascades set, so every rule can be broken by the mask and the view alone."""
+import pytest
+
+import rust_renderer_amd as rr
+from hybrid_util import frame_view, synthetic_scene
+from rust_renderer_amd.api import UtopianError
+
+pytestmark = pytest.mark.gpu
+
+W, H = 24, 16
+SHADOWS, GBUFFER, REFL, DEFERRED, SKY = rr.HYBRID_RT_SHADOWS, rr.HYBRID_GBUFFER, rr.HYBRID_RT_REFLECTIONS, rr.HYBRID_DEFERRED, rr.HYBRID_SKY
+RASTER, MAPS, MC, RESTIR, RTAO = rr.HYBRID_GBUFFER_RASTER, rr.HYBRID_SHADOW_MAPS, rr.HYBRID_MARCHING_CUBES, rr.HYBRID_RESTIR_LIGHTS, rr.HYBRID_RTAO
+
+# the rules in the order uh_render_hybrid checks them: how each message begins
+RASTER_ALONE = "uh_render_hybrid: UH_HYBRID_GBUFFER_RASTER without UH_HYBRID_GBUFFER"
+REFL_IBL = "uh_render_hybrid: rt_reflections with view.ibl_enabled = 1 needs the IBL maps"
+MAPS_PARAMS = "uh_render_hybrid: UH_HYBRID_SHADOW_MAPS before uh_set_shadowmap_params"
+DEFERRED_MAPS = "uh_render_hybrid: the deferred pass with view.shadows_enabled = 1 needs the cascaded shadow maps"
+DEFERRED_IBL = "uh_render_hybrid: the deferred pass with view.ibl_enabled = 1 needs the IBL maps"
+DEFERRED_LIGHTS = "uh_render_hybrid: view.num_lights exceeds the lights added with uh_add_light"
+SKY_CUBE = "uh_render_hybrid: the sky pass with view.cubemap_enabled = 1 needs the environment cube"
+RESTIR_RT = "uh_render_hybrid: UH_HYBRID_RESTIR_LIGHTS casts shadow rays and view.raytracing_supported is not 1"
+RESTIR_GBUFFER = "uh_render_hybrid: UH_HYBRID_RESTIR_LIGHTS casts its rays from the G-buffer, and no G-buffer has been rendered"
+RESTIR_NONE = "uh_render_hybrid: UH_HYBRID_RESTIR_LIGHTS reads the spatial reservoirs, and no reservoir pass has run on this context"
+RTAO_RT = "uh_render_hybrid: UH_HYBRID_RTAO casts occlusion rays and view.raytracing_supported is not 1"
+RTAO_GBUFFER = "uh_render_hybrid: UH_HYBRID_RTAO casts its rays from the G-buffer, and no G-buffer has been rendered"
+MC_GBUFFER = "uh_render_hybrid: the marching-cubes pass depth-tests against the G-buffer's depth, and no G-buffer has been rendered"
+MC_MAPS = "uh_render_hybrid: the marching-cubes pass with view.shadows_enabled = 1 needs the cascaded shadow maps"
+MC_LIGHTS = "uh_render_hybrid: the marching-cubes pass: view.num_lights exceeds the lights added with uh_add_light"
+NOT_BUILT = "uh_render_hybrid before uh_build_acceleration"
+
+# (mask, view fields) breaking two rules: the first rule's message; then (mask, view fields) breaking the second alone: its message
+PAIRS = {
+    "raster_without_gbuffer/reflections_ibl": ((RASTER | REFL, dict(ibl_enabled=1)), RASTER_ALONE, (REFL, dict(ibl_enabled=1)), REFL_IBL),
+    "maps_before_params/deferred_lights": ((MAPS | DEFERRED, dict(shadows_enabled=1, num_lights=1)), MAPS_PARAMS, (DEFERRED, dict(num_lights=1)), DEFERRED_LIGHTS),
+    "restir_raytracing/restir_gbuffer": ((RESTIR, dict(raytracing_supported=0)), RESTIR_RT, (RESTIR, {}), RESTIR_GBUFFER),
+    "rtao_raytracing/mc_gbuffer": ((RTAO | MC, dict(raytracing_supported=0, marching_cubes_enabled=1)), RTAO_RT, (MC, dict(marching_cubes_enabled=1)), MC_GBUFFER),
+    "reflections_ibl/maps_before_params": ((REFL | MAPS, dict(ibl_enabled=1, shadows_enabled=1)), REFL_IBL, (MAPS, dict(shadows_enabled=1)), MAPS_PARAMS),
+    "deferred_maps/deferred_ibl": ((DEFERRED, dict(shadows_enabled=1, ibl_enabled=1, num_lights=1)), DEFERRED_MAPS, (DEFERRED, dict(ibl_enabled=1, num_lights=1)), DEFERRED_IBL),
+    "deferred_ibl/deferred_lights": ((DEFERRED, dict(ibl_enabled=1, num_lights=1)), DEFERRED_IBL, (DEFERRED, dict(num_lights=1)), DEFERRED_LIGHTS),
+    "deferred_lights/sky_cube": ((DEFERRED | SKY, dict(num_lights=1, cubemap_enabled=1)), DEFERRED_LIGHTS, (SKY, dict(cubemap_enabled=1)), SKY_CUBE),
+    "sky_cube/restir_raytracing": ((SKY | RESTIR | GBUFFER, dict(cubemap_enabled=1, raytracing_supported=0)), SKY_CUBE, (RESTIR | GBUFFER, dict(raytracing_supported=0)), RESTIR_RT),
+    "restir_gbuffer/rtao_gbuffer": ((RESTIR | RTAO, {}), RESTIR_GBUFFER, (RTAO, {}), RTAO_GBUFFER),
+    "restir_no_reservoirs/mc_lights": ((RESTIR | GBUFFER | MC, dict(marching_cubes_enabled=1, num_lights=1)), RESTIR_NONE, (GBUFFER | MC, dict(marching_cubes_enabled=1, num_lights=1)), MC_LIGHTS),
+    "rtao_gbuffer/mc_gbuffer": ((RTAO | MC, dict(marching_cubes_enabled=1)), RTAO_GBUFFER, (MC, dict(marching_cubes_enabled=1)), MC_GBUFFER),
+    "mc_maps/mc_lights": ((GBUFFER | MC, dict(marching_cubes_enabled=1, shadows_enabled=1, num_lights=1)), MC_MAPS, (GBUFFER | MC, dict(marching_cubes_enabled=1, num_lights=1)), MC_LIGHTS),
+}
+
+
+@pytest.fixture(scope="module")
+def bare():
+    scene = synthetic_scene()
+    return scene, scene.upload(rr.Renderer(W, H))
+
+
+def refused(gpu, scene, request, code, message):
+    mask, fields = request
+    v = frame_view(scene, W, H)
+    for k, val in fields.items():
+        setattr(v, k, val)
+    with pytest.raises(UtopianError) as e:
+        gpu.render_hybrid(v, mask)
+    assert str(e.value).startswith(f"{code}: {message}"), str(e.value)
+
+
+@pytest.mark.parametrize("name", list(PAIRS))
+def test_the_first_rule_in_order_answers(bare, name):
+    scene, gpu = bare
+    both, first, second_alone, second = PAIRS[name]
+    refused(gpu, scene, both, "INVALID_ARGUMENT", first)
+    refused(gpu, scene, second_alone, "INVALID_ARGUMENT", second)
+    with pytest.raises(UtopianError, match="before the first uh_render_hybrid"):
+        gpu.read_hybrid(rr.HYBRID_POSITION)  # a refused call allocates nothing
+
+
+def test_every_refusal_comes_before_not_built():
+    scene = synthetic_scene()
+    gpu = scene.upload(rr.Renderer(W, H))
+    gpu.set_instance_transform(1, rr.transform3x4((1.1, 0.5, 0.9), (1.0, 1.2, 0.5)))  # the tree is stale from here on
+    refused(gpu, scene, (SKY, {}), "NOT_BUILT", NOT_BUILT)
+    for name, (both, first, second_alone, second) in PAIRS.items():
+        refused(gpu, scene, both, "INVALID_ARGUMENT", first)
+        refused(gpu, scene, second_alone, "INVALID_ARGUMENT", second)
+    refused(gpu, scene, (rr.HYBRID_FRAME, {}), "NOT_BUILT", NOT_BUILT)
