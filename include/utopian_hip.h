@@ -243,14 +243,16 @@ typedef struct uh_ctx uh_ctx;
  *        uh_unpack_tiles, uh_compose_tiles, uh_resolve_output, uh_add_isosurface_mesh, uh_update_isosurface_mesh (it reads the
  *        triangle total, 8 bytes, back to size its buffers), uh_get_isosurface_update_stats, uh_update_mesh_vertices (device input:
  *        it reads a 4-byte verdict on the caller's buffer back before it takes it), uh_get_mesh_update_stats, uh_read_denoised,
- *        uh_get_denoise_stats, uh_reset_denoise_history, uh_get_rtao_stats, uh_get_rtao_visits, uh_get_motion_stats, uh_destroy;
+ *        uh_get_denoise_stats, uh_reset_denoise_history, uh_get_rtao_stats, uh_get_rtao_visits, uh_get_motion_stats, uh_reset_taa_history,
+ *        uh_get_taa_stats, uh_destroy;
  *   enqueues like a frame, ordered behind the frames in flight and before those that follow:  uh_rccl_gather_tiles, uh_mgpu_compose;
  *        uh_set_option for "frames_in_flight" and for "time_kernels" 1 -> 0 (the others only change what the NEXT enqueued
  *        frame does: "furnace", "sun_grid*", "camera_grid*", "overlap", "batch_frames", "trace_blocks_per_cu", "count_visits",
  *        "full_frame_restir", "primary_implicit", "rtao_order"; "device_build", "ploc_sah_top" invalidate the tree: the next frame
  *        needs uh_build_acceleration, which waits);
  *   host state only (no device access, nothing to wait for):  uh_add_mesh, uh_add_light, uh_set_instance_transform,
- *        uh_get_num_lights, uh_mesh_info, uh_read_mesh, uh_get_restir_rows, uh_tile_pack_count, uh_set_rtao_params, uh_last_error
+ *        uh_get_num_lights, uh_mesh_info, uh_read_mesh, uh_get_restir_rows, uh_tile_pack_count, uh_set_rtao_params, uh_set_taa_params
+ *        (read by the next uh_render_hybrid), uh_taa_default_params, uh_taa_jitter, uh_last_error
  *        (uh_read_mesh of a mesh that uh_update_isosurface_mesh has made device-resident, or that uh_update_mesh_vertices last updated
  *        from a device pointer, copies it from the device: a blocking copy);
  *   uh_add_texture_rgba8 uploads into a fresh allocation no frame in flight can reference (textures enter a frame's tables at the
@@ -641,7 +643,7 @@ int uh_mgpu_set_option(uh_mgpu* group, const char* name, int value);
  * UH_HYBRID_RT_REFLECTIONS with view->ibl_enabled == 1 is UH_ERR_INVALID_ARGUMENT - and nothing runs - until the IBL maps (irradiance,
  * specular, BRDF LUT of ibl.rs) have been built with UH_HYBRID_ENVIRONMENT, below; mask bits, UH_ERR_NOT_BUILT and moved instances with
  * view->rebuild_tlas as for uh_render_frame (bits above UH_HYBRID_SHADOW_MAPS, below, are ignored, except UH_HYBRID_MARCHING_CUBES,
- * UH_HYBRID_GBUFFER_RASTER, UH_HYBRID_RESTIR_LIGHTS, UH_HYBRID_RTAO and UH_HYBRID_MOTION).
+ * UH_HYBRID_GBUFFER_RASTER, UH_HYBRID_RESTIR_LIGHTS, UH_HYBRID_RTAO, UH_HYBRID_MOTION and UH_HYBRID_TAA).
  * STREAM ORDER: uh_render_hybrid enqueues like a frame (behind the frames in flight, ahead of those that follow); uh_read_hybrid and
  * uh_get_hybrid_stats wait for all work of the context and are complete on return. The exception is UH_HYBRID_SHADOW_MAPS, below: a
  * call that renders shadow maps BLOCKS the host until the frames in flight and the pass's binning have finished (it reads the
@@ -1214,6 +1216,68 @@ UH_LAYOUT_ASSERT(sizeof(UhMotionStats) == 32 && offsetof(UhMotionStats, pixels_w
                     offsetof(UhMotionStats, meshes_none) == 20 && offsetof(UhMotionStats, motion_ms) == 24 && offsetof(UhMotionStats, snapshot_ms) == 28,
                  "UhMotionStats (32 B)");
 int uh_get_motion_stats(uh_ctx* ctx, UhMotionStats* out); /* waits; all zero before the first pass */
+
+/* ---- temporal anti-aliasing for the hybrid frame: a jittered camera resolved over time between the sky pass and present ------------------
+ * An EXTENSION: the reference's only anti-aliasing is present's FXAA. UH_HYBRID_TAA (bit 15; bit 9 stays unused and ignored) adds a
+ * temporal resolve to uh_render_hybrid AFTER the sky pass and BEFORE present: it reads deferred_output as that call's passes left it (or
+ * as it stands when none of them ran in the call), the G-buffer's position image, view->prev_frame_projection_view and, with
+ * UH_TAA_MOTION, the motion image, and writes taa_output (UH_HYBRID_TAA_OUTPUT, RGBA32F, G-buffer orientation as deferred_output) and the
+ * history length N (UH_HYBRID_TAA_HISTORY, float32). Per pixel, with c its deferred_output texel:
+ *   box       with UH_TAA_CLAMP: mean m1 and deviation sg per channel of deferred_output over the 3 x 3 pixels around it that lie in the
+ *             frame; lo = m1 - clamp_gamma * sg, hi = m1 + clamp_gamma * sg.
+ *   history   a geometry pixel (position w != 0) reprojects its position - with UH_TAA_MOTION the motion texel's xyz where that has
+ *             w == 1, and nothing (no history) where it has w == 0 - as a point; every other pixel (the sky, the marching-cubes pass's
+ *             pixels) reprojects the direction of its primary ray as a point at infinity. Through prev_frame_projection_view to a
+ *             bilinear fetch of the previous taa_output and N, exactly as the denoiser's temporal stage forms it (8-bit fractions, the
+ *             taps inside the image). There is NO mesh, normal or plane test.
+ *   blend     with a history: hc = the fetched colour (clamped to [lo, hi] with UH_TAA_CLAMP), N' = min(N + 1, max_history), a =
+ *             max(1 / N', alpha_min), out = hc + (c - hc) * a. Without: out = c, N' = 1. taa_output = (out.rgb, c.a).
+ * When the pass ran in a call that also has UH_HYBRID_PRESENT, present reads taa_output instead of deferred_output (FXAA and the
+ * conversion as ever); in every other call present is what it was. The first pass ever and the first after uh_reset_taa_history have no
+ * history anywhere.
+ * JITTER IS THE CALLER'S: the library never jitters anything. Per frame k the caller offsets view->projection / inverse_projection by
+ * uh_taa_jitter(k) pixels (for this perspective matrix elements 8 and 9 get -2 jx / W and +2 jy / H) and passes in
+ * prev_frame_projection_view the previous frame's UN-jittered projection * view moved by the SAME offset in clip space (rows 0 and 1
+ * less the offset times row 3): the pixel's sample lies j off its centre, and so does its reprojection, so a camera at rest reprojects
+ * every pixel onto its own texel and the history stays registered to the un-jittered pixel grid. utopian::jitter_view of
+ * utopian_host.hpp does all three to a view that holds the un-jittered matrices; the caller keeps the un-jittered product for the next
+ * frame. (With the un-jittered product passed as it is the fetch lands j off the texel and every frame resamples the history: measured
+ * on the slanted edge of tests/test_taa_cpu.py, 0.112 mean error against 0.035.) The bit counts as a final-frame pass: the final
+ * frame's images are allocated by the first call with it.
+ * LIMITS: nothing but the clamp rejects history - a disoccluded pixel keeps what the clamp lets through; the marching-cubes pass's
+ * pixels are reprojected as if at infinity and ghost within the clamp box under camera translation; a camera cut is the caller's
+ * uh_reset_taa_history.
+ * PARAMS: uh_set_taa_params validates and keeps them for the calls that follow (a refused call leaves the old ones): unknown flag bits,
+ * max_history < 1, alpha_min outside [0, 1] or clamp_gamma not finite and >= 0 are refused. Before the first call the defaults of
+ * uh_taa_default_params hold: UH_TAA_CLAMP, 16, 0.1, 1.0.
+ * UH_ERR_INVALID_ARGUMENT with a message, nothing runs and the history is untouched: no G-buffer rendered in this call or an earlier
+ * one; UH_TAA_MOTION in the params while the last G-buffer pass had no UH_HYBRID_MOTION.
+ * READ-BACK (uh_read_hybrid, UH_ERR_INVALID_ARGUMENT before the first pass): UH_HYBRID_TAA_OUTPUT, UH_HYBRID_TAA_HISTORY - the set the
+ * last pass wrote.
+ * RESOURCES: 40 bytes per pixel (two sets of RGBA32F colour and float N, ping-ponged) and 16 KiB of counters, allocated by the first call
+ * with the bit; freed by uh_destroy. A context that never sets the bit allocates nothing and runs no new code.
+ * STREAM ORDER: as uh_render_hybrid. uh_set_taa_params is host state, read by the next uh_render_hybrid; uh_reset_taa_history and
+ * uh_get_taa_stats wait.
+ * ISOLATION: the bit changes no other hybrid image, reservoir, accumulation, grid or UhStats, and not UhHybridFrameStats: its time goes
+ * to UhTaaStats only. Without the bit every pass, image and stat is what it was. No uh_mgpu_ twin.
+ * Arithmetic: DESIGN.md section 2, "Temporal anti-aliasing". */
+enum { UH_HYBRID_TAA = 1u << 15 };
+enum { UH_HYBRID_TAA_OUTPUT = 16 /* RGBA32F */, UH_HYBRID_TAA_HISTORY = 17 /* float32: N */ };
+enum { UH_TAA_CLAMP = 1u << 0, UH_TAA_MOTION = 1u << 1 };
+typedef struct UhTaaParams { uint32_t flags; uint32_t max_history; float alpha_min; float clamp_gamma; } UhTaaParams;   /* 16 B */
+UH_LAYOUT_ASSERT(sizeof(UhTaaParams) == 16 && offsetof(UhTaaParams, max_history) == 4 && offsetof(UhTaaParams, alpha_min) == 8 &&
+                    offsetof(UhTaaParams, clamp_gamma) == 12,
+                 "UhTaaParams (16 B)");
+/* the last pass: the pixels that blended a history and those that started one (their sum is the frame), and its hipEvent time */
+typedef struct UhTaaStats  { uint32_t history_pixels, reset_pixels; float taa_ms; uint32_t reserved; } UhTaaStats;       /* 16 B */
+UH_LAYOUT_ASSERT(sizeof(UhTaaStats) == 16 && offsetof(UhTaaStats, reset_pixels) == 4 && offsetof(UhTaaStats, taa_ms) == 8 &&
+                    offsetof(UhTaaStats, reserved) == 12,
+                 "UhTaaStats (16 B)");
+int uh_taa_default_params(UhTaaParams* out);        /* needs no GPU: UH_TAA_CLAMP, 16, 0.1, 1.0 */
+int uh_set_taa_params(uh_ctx*, const UhTaaParams*); /* validated here; a refused call leaves the old ones */
+int uh_reset_taa_history(uh_ctx*);                  /* the next pass starts from no history (camera cut) */
+int uh_get_taa_stats(uh_ctx*, UhTaaStats*);         /* waits; all zero before the first pass */
+int uh_taa_jitter(uint32_t index, float out[2]);    /* needs no GPU: (halton(index+1, 2) - 0.5, halton(index+1, 3) - 0.5), in pixels */
 
 #ifdef __cplusplus
 }

@@ -206,6 +206,28 @@ struct ModelInstance {
 };
 
 // ---- renderer.rs + raytracing.rs ------------------------------------------------------------
+// UH_HYBRID_TAA's sub-pixel jitter: `view` moved by (jx, jy) pixels of a width x height frame in G-buffer pixel coordinates (x right, y
+// down). Its perspective projection gets -2 jx / width on element 8 and +2 jy / height on element 9 (ndc = clip.xy / -z), and
+// inverse_projection the inverse of that; prev_frame_projection_view - which the caller has set to the previous frame's UN-jittered
+// projection * view - gets the same offset in clip space (rows 0 and 1 less the offset times row 3), so that a camera at rest reprojects
+// every pixel onto its own texel. The caller keeps the un-jittered projection * view of `view` for the next frame.
+inline UhViewUniformData jitter_view(const UhViewUniformData& view, float jx, float jy, uint32_t width, uint32_t height) {
+   UhViewUniformData v = view;
+   const float dx = -2.0f * jx / (float)width, dy = 2.0f * jy / (float)height;
+   v.projection[8] = v.projection[8] + dx;
+   v.projection[9] = v.projection[9] + dy;
+   Mat4 p;
+   std::memcpy(p.m, v.projection, sizeof(p.m));
+   const Mat4 inv = p.inverse();
+   std::memcpy(v.inverse_projection, inv.m, sizeof(inv.m));
+   for (int c = 0; c < 4; c++) {
+      float* col = v.prev_frame_projection_view + 4 * c;
+      col[0] = col[0] - dx * col[3];
+      col[1] = col[1] - dy * col[3];
+   }
+   return v;
+}
+
 class Renderer {
   public:
    Renderer(int device_ordinal, uint32_t width, uint32_t height) : width_(width), height_(height) {
@@ -306,15 +328,15 @@ class Renderer {
    void render_hybrid(const UhViewUniformData& view, uint32_t mask = UH_HYBRID_ALL) { check(uh_render_hybrid(ctx_, &view, mask), "render_hybrid"); }
    // one image as bytes: W*H texels of 16 (position, normal, pbr, deferred output, the motion image of UH_HYBRID_MOTION), 4 (albedo, reflections, present output, the
    // marching-cubes and rasterised G-buffer depth floats and draw indices uint32), 2 (SSAO) or 1 (shadows, light visibility, the
-   // occluded-ray counts of UH_HYBRID_RTAO) bytes
+   // occluded-ray counts of UH_HYBRID_RTAO) bytes; taa_output of UH_HYBRID_TAA 16, its history length 4
    std::vector<uint8_t> read_hybrid(int which) {
       const size_t texel = (which == UH_HYBRID_AO_COUNTS) ? 1
                            : (which == UH_HYBRID_SHADOWS || which == UH_HYBRID_LIGHT_VISIBILITY) ? 1
                            : (which == UH_HYBRID_SSAO_IMAGE) ? 2
                            : (which == UH_HYBRID_ALBEDO || which == UH_HYBRID_REFLECTIONS || which == UH_HYBRID_PRESENT_OUTPUT ||
                               which == UH_HYBRID_DEPTH || which == UH_HYBRID_MARCHING_CUBES_VISIBILITY || which == UH_HYBRID_GBUFFER_DEPTH ||
-                              which == UH_HYBRID_GBUFFER_VISIBILITY) ? 4
-                                                                     : 16;  // (UH_HYBRID_MOTION_IMAGE among them)
+                              which == UH_HYBRID_GBUFFER_VISIBILITY || which == UH_HYBRID_TAA_HISTORY) ? 4
+                                                                     : 16;  // (UH_HYBRID_MOTION_IMAGE and UH_HYBRID_TAA_OUTPUT among them)
       static_assert(UH_HYBRID_MOTION_IMAGE == 15, "read_hybrid sizes image 15 as 16-byte texels");
       std::vector<uint8_t> out((size_t)width_ * height_ * texel);
       check(uh_read_hybrid(ctx_, which, out.data()), "read_hybrid");
@@ -368,6 +390,27 @@ class Renderer {
       UhMotionStats s;
       check(uh_get_motion_stats(ctx_, &s), "motion_stats");
       return s;
+   }
+   // temporal anti-aliasing between the sky pass and present of render_hybrid (UH_HYBRID_TAA; utopian_hip.h "temporal anti-aliasing"):
+   // the params of the calls that follow, a camera cut, the last pass's pixels and time, and the jitter of frame `index` in pixels
+   static UhTaaParams default_taa_params() {
+      UhTaaParams p;
+      if (uh_taa_default_params(&p) != UH_OK) throw Error(UH_ERR_INVALID_ARGUMENT, "uh_taa_default_params");
+      return p;
+   }
+   void set_taa_params(const UhTaaParams& params) { check(uh_set_taa_params(ctx_, &params), "set_taa_params"); }
+   void reset_taa_history() { check(uh_reset_taa_history(ctx_), "reset_taa_history"); }
+   UhTaaStats taa_stats() {
+      UhTaaStats s;
+      check(uh_get_taa_stats(ctx_, &s), "taa_stats");
+      return s;
+   }
+   // `view` jittered by uh_taa_jitter(index) pixels of this renderer's frame (jitter_view, above): set its prev_frame_projection_view to
+   // the previous frame's UN-jittered projection * view first, and keep this frame's un-jittered product for the next
+   UhViewUniformData jittered(const UhViewUniformData& view, uint32_t index) const {
+      float j[2];
+      if (uh_taa_jitter(index, j) != UH_OK) throw Error(UH_ERR_INVALID_ARGUMENT, "uh_taa_jitter");
+      return jitter_view(view, j[0], j[1], width_, height_);
    }
    // the denoiser (utopian_hip.h "the denoiser"): the accumulation of the last render_frame over the G-buffer of the last render_hybrid,
    // both rendered with view's camera by the caller; view.prev_frame_projection_view is projection * view of the previous call

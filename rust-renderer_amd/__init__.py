@@ -16,6 +16,8 @@ from .api import (  # noqa: F401
     make_material,
     rtao_default_params,
     shadow_cascades,
+    taa_default_params,
+    taa_jitter,
     transform3x4,
 )
 from .build import build_library  # noqa: F401

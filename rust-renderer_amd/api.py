@@ -53,6 +53,9 @@ from .types import (
     HYBRID_REFLECTIONS,
     HYBRID_SHADOWS,
     HYBRID_SSAO_IMAGE,
+    HYBRID_TAA,
+    HYBRID_TAA_HISTORY,
+    HYBRID_TAA_OUTPUT,
     GpuLight,
     GpuMaterial,
     EnvironmentStats,
@@ -77,6 +80,8 @@ from .types import (
     RtaoParams,
     RtaoStats,
     Stats,
+    TaaParams,
+    TaaStats,
     ViewUniformData,
 )
 
@@ -509,6 +514,8 @@ class Renderer:
         for the bits of `mask` (HYBRID_FRAME: all seven)"""
         api = self._hybrid_api()
         self._check(api.render_hybrid(self._ctx, C.byref(view), int(mask)))
+        if int(mask) & HYBRID_TAA:
+            self._taa_rendered = True
 
     _HYBRID_IMAGES = {
         HYBRID_POSITION: (np.float32, 4),
@@ -528,6 +535,9 @@ class Renderer:
         HYBRID_AO_COUNTS: (np.uint8, 1),
         HYBRID_MOTION_IMAGE: (np.float32, 4),
     }
+    # the two images of HYBRID_TAA, which exist once a render_hybrid call with the bit has succeeded on this renderer (_taa_rendered)
+    _TAA_IMAGES = {HYBRID_TAA_OUTPUT: (np.float32, 4), HYBRID_TAA_HISTORY: (np.float32, 1)}
+    _taa_rendered = False
 
     def read_hybrid(self, which):
         """one image of the hybrid graph: (H, W, 4) float32 position / normal / pbr / deferred output, (H, W, 4) uint8 albedo / reflections /
@@ -535,11 +545,12 @@ class Renderer:
         marching-cubes draw index (MARCHING_CUBES_NONE where none survived), (H, W) float32 rasterised G-buffer depth, (H, W) uint32
         rasterised G-buffer draw index (GBUFFER_NONE where none survived), (H, W) uint8 light visibility of HYBRID_RESTIR_LIGHTS,
         (H, W) uint8 occluded-ray counts of HYBRID_RTAO, (H, W, 4) float32 motion image of HYBRID_MOTION (previous world position, w = 1
-        with a correspondence)"""
+        with a correspondence), and once a call with HYBRID_TAA has run (H, W, 4) float32 taa_output and (H, W) float32 history length"""
         api = self._hybrid_api()
-        if which not in self._HYBRID_IMAGES:
-            raise ValueError(f"hybrid image index {which} (0..15)")
-        dtype, ch = self._HYBRID_IMAGES[which]
+        images = {**self._HYBRID_IMAGES, **(self._TAA_IMAGES if self._taa_rendered else {})}
+        if which not in images:
+            raise ValueError(f"hybrid image index {which} (0..15, and 16..17 once a render_hybrid call with HYBRID_TAA has run)")
+        dtype, ch = images[which]
         out = np.empty((self.height, self.width, ch) if ch > 1 else (self.height, self.width), dtype=dtype)
         self._check(api.read_hybrid(self._ctx, int(which), out.ctypes.data))
         return out
@@ -651,6 +662,57 @@ class Renderer:
         s = MotionStats()
         self._check(fn(self._ctx, C.byref(s)))
         return s
+
+    # -- temporal anti-aliasing (HYBRID_TAA; include/utopian_hip.h "temporal anti-aliasing") ---
+    def _taa_fn(self, name, *argtypes):
+        if self.backend != "hip":
+            raise NotImplementedError(f"temporal anti-aliasing is a per-context verb of the HIP library; backend {self.backend!r} has none")
+        fn = getattr(self._lib, "uh_" + name)
+        fn.argtypes, fn.restype = [C.c_void_p] + [C.POINTER(a) for a in argtypes], C.c_int
+        return fn
+
+    @staticmethod
+    def taa_default_params():
+        """UhTaaParams as uh_taa_default_params fills it: TAA_CLAMP, 16, 0.1, 1.0"""
+        return taa_default_params()
+
+    def set_taa_params(self, params=None, **fields):
+        """uh_set_taa_params: `params` (a TaaParams; the defaults when None) with `fields` set on a copy - the params of the
+        render_hybrid calls with HYBRID_TAA that follow. A refused call raises and leaves the old ones."""
+        p = TaaParams.from_buffer_copy(taa_default_params() if params is None else params)
+        for k, v in fields.items():
+            if not hasattr(p, k):
+                raise TypeError(f"TaaParams has no field {k!r}")
+            setattr(p, k, v)
+        self._check(self._taa_fn("set_taa_params", TaaParams)(self._ctx, C.byref(p)))
+        return p
+
+    def reset_taa_history(self):
+        """uh_reset_taa_history: the next taa pass starts from no history (a camera cut)"""
+        self._check(self._taa_fn("reset_taa_history")(self._ctx))
+
+    def taa_stats(self):
+        """UhTaaStats of the last taa pass: history_pixels, reset_pixels, taa_ms; all zero before the first pass"""
+        s = TaaStats()
+        self._check(self._taa_fn("get_taa_stats", TaaStats)(self._ctx, C.byref(s)))
+        return s
+
+    @staticmethod
+    def jitter_view(view, index, width=None, height=None):
+        """a copy of `view` jittered by taa_jitter(index) pixels: projection and inverse_projection through camera.jitter_projection, and
+        prev_frame_projection_view - which the caller has set to the previous frame's UN-jittered projection * view - through
+        camera.jitter_clip with the same offset, so that a camera at rest reprojects every pixel onto its own texel. The caller keeps the
+        un-jittered projection * view of `view` for the next frame. width, height: the frame's, view.viewport_width / viewport_height
+        when None."""
+        v = ViewUniformData.from_buffer_copy(view)
+        w = int(view.viewport_width) if width is None else width
+        h = int(view.viewport_height) if height is None else height
+        jx, jy = taa_jitter(index)
+        proj, inv = cam.jitter_projection(np.array(view.projection[:], np.float32), jx, jy, w, h)
+        v.projection[:] = proj.tolist()
+        v.inverse_projection[:] = inv.tolist()
+        v.prev_frame_projection_view[:] = cam.jitter_clip(np.array(view.prev_frame_projection_view[:], np.float32), jx, jy, w, h).tolist()
+        return v
 
     # -- the denoiser (uh_denoise; include/utopian_hip.h "the denoiser") --------------------
     def _denoise_fn(self, name, argtypes):
@@ -962,6 +1024,26 @@ def compose3x4(a, b):
     A = np.vstack([np.asarray(a, dtype=np.float32).reshape(3, 4), [0, 0, 0, 1]]).astype(np.float32)
     B = np.vstack([np.asarray(b, dtype=np.float32).reshape(3, 4), [0, 0, 0, 1]]).astype(np.float32)
     return (A @ B)[:3].astype(np.float32).reshape(12)
+
+
+def taa_default_params():
+    """UhTaaParams as uh_taa_default_params fills it (needs no GPU)"""
+    fn = load_library().uh_taa_default_params
+    fn.argtypes, fn.restype = [C.POINTER(TaaParams)], C.c_int
+    p = TaaParams()
+    if fn(C.byref(p)) != 0:
+        raise UtopianError("uh_taa_default_params failed")
+    return p
+
+
+def taa_jitter(index):
+    """uh_taa_jitter: the sub-pixel offset (jx, jy) of frame `index`, Halton(2, 3) - 0.5 in pixels (needs no GPU)"""
+    fn = load_library().uh_taa_jitter
+    fn.argtypes, fn.restype = [C.c_uint32, C.POINTER(C.c_float * 2)], C.c_int
+    out = (C.c_float * 2)()
+    if fn(int(index), C.byref(out)) != 0:
+        raise UtopianError("uh_taa_jitter failed")
+    return float(out[0]), float(out[1])
 
 
 def default_view(camera, width, height, num_lights=0):

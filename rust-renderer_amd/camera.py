@@ -50,6 +50,31 @@ def inverse(m):
     return np.linalg.inv(m.astype(np.float64)).astype(f32)
 
 
+def jitter_projection(projection, jx, jy, width, height):
+    """(projection', inverse(projection')), both 16 floats column-major: the perspective projection (16 floats column-major) whose image
+    of every point is moved by (jx, jy) pixels in G-buffer pixel coordinates (x right, y down) of a width x height frame.
+    A point's pixel is ((ndc.x * 0.5 + 0.5) * width, (1 - (ndc.y * 0.5 + 0.5)) * height) and ndc = clip.xy / clip.w with clip.w = -z
+    (row 3 of perspective_rh is (0, 0, -1, 0)), so adding d to element 8 (row 0, column 2: the factor of z in clip.x) moves ndc.x by
+    d z / -z = -d: jx pixels are d = -2 jx / width; y points down, so jy pixels are +2 jy / height on element 9. (0, 0) returns the
+    input's bits."""
+    p = np.array(projection, dtype=f32).reshape(16).copy()
+    p[8] = p[8] + f32(-2.0) * f32(jx) / f32(width)
+    p[9] = p[9] + f32(2.0) * f32(jy) / f32(height)
+    return p, to_glam(inverse(p.reshape(4, 4).T))
+
+
+def jitter_clip(matrix, jx, jy, width, height):
+    """16 floats column-major: J * matrix, where J moves clip.xy by (-2 jx / width, +2 jy / height) * -clip.w - what jitter_projection does
+    to a perspective projection, applied to any matrix that ends in one (a projection * view product: the previous frame's, which a
+    jittered frame reprojects through with ITS OWN jitter, so that a camera at rest lands on its own texel)"""
+    m = np.array(matrix, dtype=f32).reshape(16).copy()
+    dx, dy = f32(-2.0) * f32(jx) / f32(width), f32(2.0) * f32(jy) / f32(height)
+    for c in range(4):
+        m[4 * c] = m[4 * c] - dx * m[4 * c + 3]
+        m[4 * c + 1] = m[4 * c + 1] - dy * m[4 * c + 3]
+    return m
+
+
 def to_glam(m):
     """row/col matrix -> 16 floats column-major."""
     return np.ascontiguousarray(m.T, dtype=f32).reshape(16)

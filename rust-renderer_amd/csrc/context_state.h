@@ -574,9 +574,30 @@ struct uh_ctx {
          }
       } mv;
 
+      // temporal anti-aliasing (UH_HYBRID_TAA), allocated by the first call with the bit: two sets of taa_output and the history length N,
+      // ping-ponged - set `cur` is the one the last pass wrote (what uh_read_hybrid and present read), the other the one the next pass
+      // writes - and the pass's counters (pixels that blended a history, pixels that started one: TaaDev's pairs); params: the last uh_set_taa_params
+      // (the defaults before); valid: set `cur` is a history the next pass may read (false before the first pass and after
+      // uh_reset_taa_history)
+      struct __attribute__((visibility("hidden"))) Taa {
+         DevBuf<float4> col[2];
+         DevBuf<float> n[2];
+         DevBuf<uint32_t> counters;
+         UhTaaParams params{UH_TAA_CLAMP, 16, 0.1f, 1.0f};
+         Stage stage;                          // the last pass's
+         int cur = 0;
+         bool valid = false;
+         uint32_t renders = 0;
+         template <class F> void images(size_t n_, F&& f) { f(col[0], n_), f(col[1], n_), f(n[0], n_), f(n[1], n_), f(counters, (size_t)kTaaCounterSlots * kTaaCounterStride); }
+         void destroy() {
+            images(0, ReleaseBuf{});
+            stage.destroy();
+         }
+      } taa;
+
       __attribute__((visibility("hidden"))) void destroy() {
          rt_images(0, ReleaseBuf{}), frame_images(0, ReleaseBuf{});
-         env.destroy(), sm.destroy(), gr.destroy(), mc.destroy(), rl.destroy(), ao.destroy(), mv.destroy();
+         env.destroy(), sm.destroy(), gr.destroy(), mc.destroy(), rl.destroy(), ao.destroy(), mv.destroy(), taa.destroy();
          meshes.release(), vertices.release(), indices.release(), raw_lights.release();
          for (hipEvent_t ev : waits)
             if (ev) (void)hipEventDestroy(ev);

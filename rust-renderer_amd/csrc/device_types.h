@@ -317,6 +317,22 @@ struct MotionDev {
    uint32_t* counters;             // per block of the motion kernel's grid: [2 b] its geometry pixels with a correspondence, [2 b + 1] without
 };
 
+// temporal anti-aliasing of the hybrid frame (UH_HYBRID_TAA; taa.hip): what its kernel reads and writes
+constexpr uint32_t kTaaCounterSlots = 256, kTaaCounterStride = 16;  // a 64-byte line per pair: 16 KiB
+struct TaaDev {
+   const float4* deferred;         // deferred_output as the call's passes left it
+   const float4* pos;              // the G-buffer's position image (w != 0: geometry)
+   const float4* motion;           // UH_HYBRID_MOTION_IMAGE with UH_TAA_MOTION, else null (the launcher picks the instantiation)
+   const float4* prev_col;         // the previous pass's taa_output and N; null: no history (the first pass, or after a reset)
+   const float* prev_n;
+   float4* col;                    // UH_HYBRID_TAA_OUTPUT
+   float* n;                       // UH_HYBRID_TAA_HISTORY
+   uint32_t* counters;             // kTaaCounterSlots pairs, kTaaCounterStride words apart: [0] pixels that blended a history, [1] pixels
+                                   // that started one; a wave adds into the pair of its number modulo the slots, the host adds the pairs up
+   uint32_t clamp;                 // UH_TAA_CLAMP
+   float max_history, alpha_min, clamp_gamma;
+};
+
 // launch wrappers implemented in kernels.hip, path_fused.hip, restir.hip, tiles.hip and hybrid_kernels.hip --------------------------------------------------
 struct LaunchCfg {
    hipStream_t stream;
@@ -420,6 +436,8 @@ void launch_hybrid_restir_lights(const LaunchCfg&, const FrameParams&, const Sce
 void launch_rtao_trace(const LaunchCfg&, const SceneDev&, const HybridDev&, const RtaoDev&, uint32_t order);
 // ao (and its filter, blur_radius > 0) from the counts into ssao_output, texel (x, y) = G-buffer pixel (x, H - 1 - y)
 void launch_rtao_resolve(const LaunchCfg&, const HybridDev&, const RtaoDev&, uint16_t* ssao);
+// the taa pass (taa.hip): one lane per pixel; fp gives the frame, the matrices of primary_ray and prev_pv; t.counters zeroed by the caller
+void launch_hybrid_taa(const LaunchCfg&, const FrameParams&, const TaaDev&);
 // the shadow-map rasteriser (shadow_map.hip): setup per (triangle, cascade), binning into kShadowTile^2 tiles, resolve per tile in LDS
 constexpr uint32_t kShadowTile = 128;
 struct ShadowDev {

@@ -1,5 +1,6 @@
 // hybrid_graph.hip - the hybrid graph of include/utopian_hip.h (uh_render_hybrid: the ray-traced passes, the final frame, the IBL
-// maps, the marching-cubes pass, the rasterised G-buffer, the reservoir lights, ray-traced ambient occlusion, motion vectors) with its
+// maps, the marching-cubes pass, the rasterised G-buffer, the reservoir lights, ray-traced ambient occlusion, motion vectors, temporal
+// anti-aliasing) with its
 // read and stats verbs, and what the forward graph and the denoiser share with it: the mesh and light tables, the wait behind the
 // frames in flight and destroy_graphs. Host code over uh_ctx::Hybrid (context_state.h); the rasterised passes go through
 // raster_driver.hip. Host-side counterpart of build_render_graph (utopian/src/renderers/mod.rs).
@@ -391,7 +392,7 @@ static int render_gbuffer_raster(uh_ctx* c, const LaunchCfg& lc, const UhViewUni
 struct HybridPlan {
    int code;
    const char* refusal;
-   bool raster, maps, render_maps, restir, rtao, mc, motion, rt;  // maps: the IBL maps exist for this call's consumers
+   bool raster, maps, render_maps, restir, rtao, mc, motion, rt, taa;  // maps: the IBL maps exist for this call's consumers
    bool deferred, frame, env;  // the deferred pass runs; the final frame's images and the IBL maps are needed
    bool first, frame_first;    // the ray-traced images, the final frame's images are allocated by this call (and cleared)
 };
@@ -483,9 +484,20 @@ static HybridPlan hybrid_plan(const uh_ctx& c, const UhViewUniformData& view, ui
    }
    // motion vectors: a modifier of the G-buffer pass, ignored without it
    p.motion = (mask & UH_HYBRID_MOTION) && (mask & UH_HYBRID_GBUFFER);
+   // temporal anti-aliasing: the resolve between the sky pass and present, over the G-buffer the call leaves
+   p.taa = (mask & UH_HYBRID_TAA) != 0;
+   if (p.taa) {
+      if (!(mask & UH_HYBRID_GBUFFER) && !h.gbuffer_done)
+         return refuse(UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_TAA reprojects the G-buffer's positions, and no G-buffer has been rendered; set UH_HYBRID_GBUFFER");
+      if ((h.taa.params.flags & UH_TAA_MOTION) && !((mask & UH_HYBRID_GBUFFER) ? p.motion : h.mv.last))
+         return refuse(UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_TAA with UH_TAA_MOTION reads the motion image, and the last G-buffer pass had no UH_HYBRID_MOTION; "
+                     "set UH_HYBRID_GBUFFER | UH_HYBRID_MOTION, or clear the flag (uh_set_taa_params)");
+   }
    p.rt = view.raytracing_supported != 0;
    p.deferred = (mask & UH_HYBRID_DEFERRED) != 0;
-   p.frame = (mask & (UH_HYBRID_SSAO | UH_HYBRID_DEFERRED | UH_HYBRID_SKY | UH_HYBRID_PRESENT)) || p.mc || p.rtao;
+   p.frame = (mask & (UH_HYBRID_SSAO | UH_HYBRID_DEFERRED | UH_HYBRID_SKY | UH_HYBRID_PRESENT)) || p.mc || p.rtao || p.taa;
    p.env = (mask & UH_HYBRID_ENVIRONMENT) != 0;
    p.first = !h.counter.p;
    p.frame_first = p.frame && !h.sky_counter.p;
@@ -522,6 +534,10 @@ static int hybrid_prepare(uh_ctx* c, const HybridPlan& p) {
    }
    if (p.env)
       if (int st = env_alloc(c)) return st;
+   if (p.taa && !h.taa.counters.p) {
+      if (int st = stage_create(c, &h.taa.stage, 1)) return st;
+      if (int st = alloc_group(c, [&](auto f) { h.taa.images(pixels, f); })) return st;
+   }
    return UH_OK;
 }
 
@@ -665,9 +681,42 @@ static int rtao_pass(uh_ctx* c, const HybridCall& k) {
    return UH_OK;
 }
 
+// the taa pass between atmosphere_pass and present_pass: deferred_output into the set that is not the history, which then becomes the
+// current one (the ping-pong is the host's: the kernel is enqueued with both pointers)
+static int taa_pass(uh_ctx* c, const HybridCall& k) {
+   uh_ctx::Hybrid& h = c->hy;
+   uh_ctx::Hybrid::Taa& t = h.taa;
+   const UhTaaParams& p = t.params;
+   const int write = t.cur ^ 1;
+   TaaDev td{};
+   td.deferred = h.deferred.p;
+   td.pos = h.pos.p;
+   td.motion = (p.flags & UH_TAA_MOTION) ? h.mv.image.p : nullptr;
+   td.prev_col = t.valid ? t.col[t.cur].p : nullptr;
+   td.prev_n = t.valid ? t.n[t.cur].p : nullptr;
+   td.col = t.col[write].p;
+   td.n = t.n[write].p;
+   td.counters = t.counters.p;
+   td.clamp = (p.flags & UH_TAA_CLAMP) ? 1u : 0u;
+   td.max_history = (float)p.max_history;
+   td.alpha_min = p.alpha_min;
+   td.clamp_gamma = p.clamp_gamma;
+   const int st = timed(c, t.stage, [&] {
+      HIP_TRY(c, hipMemsetAsync(t.counters.p, 0, t.counters.n * sizeof(uint32_t), c->stream));
+      launch_hybrid_taa(k.lc, k.fp, td);
+      return (int)UH_OK;
+   });
+   if (st) return st;
+   t.cur = write;
+   t.valid = true;
+   t.renders++;
+   return UH_OK;
+}
+
 // The passes in the order of build_render_graph (mod.rs:91-186, graph.rs:743), each between its stage's two events: setup_shadow_pass's
 // four cascades first, rt_shadows, gbuffer, setup_cubemap_pass, rt_reflections, then the final frame - ssao_pass (not with
-// ssao_enabled != 1, ssao.rs:27; the rtao pass takes its place), deferred_pass, setup_marching_cubes_pass, atmosphere_pass, present_pass
+// ssao_enabled != 1, ssao.rs:27; the rtao pass takes its place), deferred_pass, setup_marching_cubes_pass, atmosphere_pass, the taa pass
+// (an extension; present then reads its output), present_pass
 static int hybrid_passes(uh_ctx* c, const HybridCall& k, uint32_t mask) {
    uh_ctx::Hybrid& h = c->hy;
    const HybridPlan& p = k.plan;
@@ -728,7 +777,10 @@ static int hybrid_passes(uh_ctx* c, const HybridCall& k, uint32_t mask) {
       });
       if (st) return st;
    }
-   if ((mask & UH_HYBRID_PRESENT) && (st = timed(c, h.stage[kStPresent], [&] { launch_hybrid_present(lc, hd, fd); }))) return st;
+   if (p.taa && (st = taa_pass(c, k))) return st;
+   HybridFrameDev pd = fd;  // present's source: taa_output when the taa pass ran in this call
+   if (p.taa) pd.deferred = h.taa.col[h.taa.cur].p;
+   if ((mask & UH_HYBRID_PRESENT) && (st = timed(c, h.stage[kStPresent], [&] { launch_hybrid_present(lc, hd, pd); }))) return st;
    HIP_TRY(c, hipGetLastError());
    return UH_OK;
 }
@@ -761,7 +813,7 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    const uh_ctx::Hybrid& h = c->hy;
    if (!h.counter.p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid before the first uh_render_hybrid");
-   if (which < 0 || which > UH_HYBRID_MOTION_IMAGE) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..15");
+   if (which < 0 || which > UH_HYBRID_TAA_HISTORY) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..17");
    if (which >= UH_HYBRID_SSAO_IMAGE && which <= UH_HYBRID_PRESENT_OUTPUT && !h.sky_counter.p)
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 6..8 before the first call with an SSAO, deferred, sky or present bit");
    if ((which == UH_HYBRID_DEPTH || which == UH_HYBRID_MARCHING_CUBES_VISIBILITY) && h.mc.renders == 0)
@@ -774,12 +826,15 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image 14 before the first rtao pass (UH_HYBRID_RTAO with view.ssao_enabled = 1)");
    if (which == UH_HYBRID_MOTION_IMAGE && h.mv.renders == 0)
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image 15 before the first motion pass (UH_HYBRID_GBUFFER | UH_HYBRID_MOTION)");
+   if ((which == UH_HYBRID_TAA_OUTPUT || which == UH_HYBRID_TAA_HISTORY) && h.taa.renders == 0)
+      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 16..17 before the first taa pass (UH_HYBRID_TAA)");
    // image k's pixels and its bytes per pixel, in UH_HYBRID_* image order
    const std::pair<const void*, size_t> img[] = {
       {h.pos.p, sizeof(float4)}, {h.nrm.p, sizeof(float4)}, {h.alb.p, sizeof(uchar4)}, {h.pbr.p, sizeof(float4)}, {h.shadow.p, 1},
       {h.refl.p, sizeof(uchar4)}, {h.ssao.p, sizeof(uint16_t)}, {h.deferred.p, sizeof(float4)}, {h.present.p, sizeof(uchar4)},
       {h.mc.target.depth.p, sizeof(float)}, {h.mc.target.vis.p, sizeof(uint32_t)}, {h.gr.target.depth.p, sizeof(float)}, {h.gr.target.vis.p, sizeof(uint32_t)},
-      {h.rl.vis.p, 1}, {h.ao.counts.p, 1}, {h.mv.image.p, sizeof(float4)}};
+      {h.rl.vis.p, 1}, {h.ao.counts.p, 1}, {h.mv.image.p, sizeof(float4)},
+      {h.taa.col[h.taa.cur].p, sizeof(float4)}, {h.taa.n[h.taa.cur].p, sizeof(float)}};
    return read_back(c, out, img[which].first, (size_t)c->W * c->H * img[which].second);
 }
 
@@ -869,6 +924,68 @@ int uh_get_motion_stats(uh_ctx* c, UhMotionStats* out) {
    out->meshes_rigid = h.mv.states[kMotionRigid];
    out->meshes_deformed = h.mv.states[kMotionDeformed];
    out->meshes_none = h.mv.states[kMotionNone];
+   return UH_OK;
+}
+
+// ---- temporal anti-aliasing (utopian_hip.h "temporal anti-aliasing"; taa.hip) ----
+int uh_taa_default_params(UhTaaParams* out) {
+   if (!out) return UH_ERR_INVALID_ARGUMENT;
+   *out = UhTaaParams{UH_TAA_CLAMP, 16, 0.1f, 1.0f};
+   return UH_OK;
+}
+
+static const char* taa_params_refusal(const UhTaaParams& p) {
+   if (p.flags & ~(uint32_t)(UH_TAA_CLAMP | UH_TAA_MOTION)) return "unknown flag bits (UH_TAA_CLAMP, UH_TAA_MOTION)";
+   if (p.max_history < 1) return "max_history must be >= 1";
+   if (!(p.alpha_min >= 0.0f && p.alpha_min <= 1.0f)) return "alpha_min must be in [0, 1]";
+   if (!(p.clamp_gamma >= 0.0f && p.clamp_gamma < INFINITY)) return "clamp_gamma must be finite and >= 0";
+   return nullptr;
+}
+
+int uh_set_taa_params(uh_ctx* c, const UhTaaParams* params) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!params) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_set_taa_params: null params");
+   if (const char* why = taa_params_refusal(*params)) return fail(c, UH_ERR_INVALID_ARGUMENT, std::string("uh_set_taa_params: ") + why);
+   c->hy.taa.params = *params;
+   return UH_OK;
+}
+
+int uh_reset_taa_history(uh_ctx* c) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (c->hy.taa.counters.p) {
+      HIP_TRY(c, hipSetDevice(c->device));
+      if (int st = sync_all(c)) return st;
+   }
+   c->hy.taa.valid = false;
+   return UH_OK;
+}
+
+int uh_get_taa_stats(uh_ctx* c, UhTaaStats* out) {
+   int st;
+   if (!stats_begin(c, out, sizeof(*out), "uh_get_taa_stats: null destination", c && c->hy.taa.renders != 0, &st)) return st;
+   uh_ctx::Hybrid& h = c->hy;
+   if ((st = stage_ms(c, h.taa.stage, &out->taa_ms))) return st;
+   std::vector<uint32_t> counters(h.taa.counters.n);  // a pair per slot, a line apart
+   HIP_TRY(c, hipMemcpy(counters.data(), h.taa.counters.p, counters.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+   for (uint32_t s = 0; s < kTaaCounterSlots; s++)
+      out->history_pixels += counters[(size_t)s * kTaaCounterStride], out->reset_pixels += counters[(size_t)s * kTaaCounterStride + 1];
+   return UH_OK;
+}
+
+// element i (from 1) of the Halton sequence in base b, less 0.5: the radical inverse in double, rounded to float once and kept below 0.5
+static float halton_centred(uint64_t i, uint32_t b) {
+   double f = 1.0, r = 0.0;
+   for (; i; i /= b) {
+      f /= (double)b;
+      r += f * (double)(i % b);
+   }
+   return std::fmin((float)(r - 0.5), 0.49999997f);
+}
+
+int uh_taa_jitter(uint32_t index, float out[2]) {
+   if (!out) return UH_ERR_INVALID_ARGUMENT;
+   out[0] = halton_centred((uint64_t)index + 1, 2);
+   out[1] = halton_centred((uint64_t)index + 1, 3);
    return UH_OK;
 }
 

@@ -413,3 +413,29 @@ class MotionStats(C.Structure):
 
 assert C.sizeof(MotionStats) == 32 and MotionStats.meshes_static.offset == 8 and MotionStats.meshes_none.offset == 20 and \
     MotionStats.motion_ms.offset == 24 and MotionStats.snapshot_ms.offset == 28
+
+
+# temporal anti-aliasing of the hybrid frame (an extension; utopian_hip.h "temporal anti-aliasing"): the resolve between the sky pass and
+# present, its two images, and the flags of TaaParams; bit 9 stays unused
+HYBRID_TAA = 1 << 15
+HYBRID_TAA_OUTPUT, HYBRID_TAA_HISTORY = 16, 17
+TAA_CLAMP, TAA_MOTION = 1 << 0, 1 << 1
+
+
+class TaaParams(C.Structure):
+    """UhTaaParams: flags (TAA_*), the history cap, the smallest blend factor and the width of the neighbourhood clamp in standard
+    deviations; uh_taa_default_params fills the defaults"""
+
+    _fields_ = [("flags", C.c_uint32), ("max_history", C.c_uint32), ("alpha_min", C.c_float), ("clamp_gamma", C.c_float)]
+
+
+assert C.sizeof(TaaParams) == 16 and TaaParams.max_history.offset == 4 and TaaParams.alpha_min.offset == 8 and TaaParams.clamp_gamma.offset == 12
+
+
+class TaaStats(C.Structure):
+    """UhTaaStats: the last taa pass - the pixels that blended a history, those that started one, hipEvent ms of the pass"""
+
+    _fields_ = [("history_pixels", C.c_uint32), ("reset_pixels", C.c_uint32), ("taa_ms", C.c_float), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(TaaStats) == 16 and TaaStats.reset_pixels.offset == 4 and TaaStats.taa_ms.offset == 8 and TaaStats.reserved.offset == 12
