@@ -1048,6 +1048,13 @@ int uh_get_hybrid_restir_stats(uh_ctx* ctx, UhHybridRestirStats* out);
  * position texel has w != 0; every other pixel passes through unchanged, is never a tap, and has history 0 and variance 0.
  * view->prev_frame_projection_view is projection * view of the previous uh_denoise call; view->view gives the depth the plane
  * tolerances scale with.
+ * NON-FINITE INPUT: a geometry pixel is BAD when a channel of its accumulation / n is NaN, infinite or above 2^48 (281474976710656) in
+ * magnitude - the bound keeps every later product and difference finite ("Non-finite input"). A bad pixel is
+ * treated exactly as a pixel that is not geometry, in this call and in the history it leaves: its colour, not demodulated, passes
+ * through to every colour image unchanged, it is never a tap, its history is 0 and its variance 0, and the next call fetches no
+ * history from it. Every other pixel of every image is finite, whatever the bad ones hold, and stays so in the calls that follow.
+ * So UH_DENOISE_HISTORY == 0 means "took no part": not geometry, or bad. geometry_pixels still counts position w != 0, the bad
+ * pixels included; history_pixels never counts one.
  * HISTORY: the call keeps its own copies of this frame's position, normal with the mesh index beside it, temporal colour, history
  * length and moments for the next call (the hybrid targets are overwritten by then). Without UH_DENOISE_MOTION the scene is assumed
  * static between calls: after uh_update_isosurface_mesh / uh_update_mesh_vertices / uh_set_instance_transform with a refit, render the
@@ -1098,7 +1105,7 @@ enum {
    UH_DENOISE_OUTPUT = 1,         /* 8 bits x 4 channels, B G R A: the filtered colour through the path tracer's linearToSrgb and packing */
    UH_DENOISE_INPUT = 2,          /* RGBA32F: what the filter read (accumulation / n, demodulated on geometry with UH_DENOISE_DEMODULATE) */
    UH_DENOISE_TEMPORAL_COLOR = 3, /* RGBA32F: the colour after the temporal stage, remodulated */
-   UH_DENOISE_HISTORY = 4,        /* float32: history length N (0 where not geometry) */
+   UH_DENOISE_HISTORY = 4,        /* float32: history length N (0 where not geometry, and at a bad pixel: "NON-FINITE INPUT" above) */
    UH_DENOISE_VARIANCE = 5        /* float32: the variance level 0 of the filter read */
 };
 /* the last uh_denoise call: pass_ms the hipEvent time of its stages (input + temporal, variance estimate, all a-trous levels, output),
@@ -1235,6 +1242,12 @@ int uh_get_motion_stats(uh_ctx* ctx, UhMotionStats* out); /* waits; all zero bef
  * When the pass ran in a call that also has UH_HYBRID_PRESENT, present reads taa_output instead of deferred_output (FXAA and the
  * conversion as ever); in every other call present is what it was. The first pass ever and the first after uh_reset_taa_history have no
  * history anywhere.
+ * NON-FINITE INPUT: a pixel is BAD when a colour channel of its deferred_output texel is NaN, infinite or above 2^48 in magnitude (the
+ * denoiser's bound and rule: DESIGN.md section 2, "Non-finite input"). A bad pixel passes through and takes part in nothing: its
+ * taa_output is its input, bits unchanged; its N is 0, which no other pixel has (N' >= 1), so UH_HYBRID_TAA_HISTORY == 0 means "no
+ * history here" and a later call's history tap on such a texel is skipped like a tap outside the frame; the boxes of its neighbours
+ * leave it out of their mean and deviation; it counts in reset_pixels. Every other pixel of taa_output is finite, whatever the bad
+ * ones hold, and stays so in the calls that follow.
  * JITTER IS THE CALLER'S: the library never jitters anything. Per frame k the caller offsets view->projection / inverse_projection by
  * uh_taa_jitter(k) pixels (for this perspective matrix elements 8 and 9 get -2 jx / W and +2 jy / H) and passes in
  * prev_frame_projection_view the previous frame's UN-jittered projection * view moved by the SAME offset in clip space (rows 0 and 1

@@ -27,6 +27,8 @@ __device__ __forceinline__ V3 dn_demodulator(const DenoiseDev& d, size_t i) {
 // kMotion (UH_DENOISE_MOTION): the point that is reprojected and held against the history's plane is the motion texel's xyz - where the
 // pixel's surface point was at the previous motion pass - instead of p; a texel with w == 0 has no correspondence and keeps no history.
 // Without it the instantiation is the stage as it always was.
+// A geometry pixel whose stage-0 colour fails temporal_sample_ok is written as if it were not geometry, cur.pos with w = 0 included: the
+// later stages, the output's remodulation and the next call's history taps all skip it through that w. It still counts as geometry.
 template <bool kMotion>
 __global__ __launch_bounds__(256) void k_denoise_temporal(DenoiseDev d) {
    const uint32_t x = blockIdx.x * kDnRow + threadIdx.x, y = blockIdx.y * kDnRows + threadIdx.y;
@@ -37,8 +39,9 @@ __global__ __launch_bounds__(256) void k_denoise_temporal(DenoiseDev d) {
       float r = a.x / d.n, g = a.y / d.n, b = a.z / d.n;
       const float4 P4 = d.g_pos[i];
       geo = P4.w != 0.0f;
-      d.cur.pos[i] = P4;
-      if (!geo) {
+      const bool live = geo && temporal_sample_ok(r, g, b);
+      d.cur.pos[i] = live ? P4 : make_float4(P4.x, P4.y, P4.z, 0.0f);
+      if (!live) {
          const float4 c = make_float4(r, g, b, 0.0f);
          d.input[i] = c;
          d.cv[0][i] = c;

@@ -11,6 +11,14 @@ namespace uh {
 // Rec. 601 luma of a colour
 __device__ __forceinline__ float dn_luminance(float r, float g, float b) { return (0.299f * r + 0.587f * g) + 0.114f * b; }
 
+// A sample the temporal filters take in: every channel finite and at most 2^48 in magnitude (a NaN fails the compare). The bound is what
+// keeps every later product finite - the squared luminance of a colour demodulated by 0.01, 49 taps of 4 x its second moment, nine
+// squares of TAA's box - and what keeps r - prev finite for values of opposite sign ("Non-finite input")
+constexpr float kTemporalMaxSample = 281474976710656.0f;
+__device__ __forceinline__ bool temporal_sample_ok(float r, float g, float b) {
+   return fabsf(r) <= kTemporalMaxSample && fabsf(g) <= kTemporalMaxSample && fabsf(b) <= kTemporalMaxSample;
+}
+
 // z of view * (P, 1): the third row of the column-major view matrix
 __device__ __forceinline__ float dn_view_z(const float* m, V3 p) { return ((m[2] * p.x + m[6] * p.y) + m[10] * p.z) + m[14] * 1.0f; }
 

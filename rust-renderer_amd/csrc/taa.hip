@@ -6,6 +6,7 @@
 // LDS tile: DESIGN.md section 4, "Temporal anti-aliasing").
 #include <hip/hip_runtime.h>
 
+#include "denoise_device.h"
 #include "device_math.h"
 #include "device_types.h"
 #include "kernel_common.h"
@@ -16,6 +17,8 @@ constexpr uint32_t kTaaRow = 64, kTaaRows = kBlock / kTaaRow;
 
 // kMotion (UH_TAA_MOTION): a geometry pixel reprojects the motion texel's xyz - where its surface point was at the previous motion pass -
 // instead of its position; a texel with w == 0 has no correspondence and starts a new history.
+// A pixel whose colour fails temporal_sample_ok passes through with N = 0: the boxes of its neighbours leave it out, and a later call's
+// history taps skip a texel whose N is 0 as they skip one outside the frame.
 template <bool kMotion>
 __global__ __launch_bounds__(kBlock) void k_hybrid_taa(FrameParams fp, TaaDev t) {
    const uint32_t x = blockIdx.x * kTaaRow + threadIdx.x, y = blockIdx.y * kTaaRows + threadIdx.y;
@@ -24,9 +27,10 @@ __global__ __launch_bounds__(kBlock) void k_hybrid_taa(FrameParams fp, TaaDev t)
    if (x < W && y < H) {
       const size_t i = (size_t)y * W + x;
       const float4 c = t.deferred[i];
+      const bool live = temporal_sample_ok(c.x, c.y, c.z);
       // the neighbourhood box: mean and deviation per channel over the 3 x 3 pixels in the frame
       V3 lo = v3(0.0f, 0.0f, 0.0f), hi = lo;
-      if (t.clamp) {
+      if (t.clamp && live) {
          V3 s1 = v3(0.0f, 0.0f, 0.0f), s2 = s1;
          float k = 0.0f;
          for (int dy = -1; dy <= 1; dy++) {
@@ -34,6 +38,7 @@ __global__ __launch_bounds__(kBlock) void k_hybrid_taa(FrameParams fp, TaaDev t)
                const int qx = (int)x + dx, qy = (int)y + dy;
                if (qx < 0 || qx >= (int)W || qy < 0 || qy >= (int)H) continue;
                const float4 q = t.deferred[(size_t)qy * W + qx];
+               if (!temporal_sample_ok(q.x, q.y, q.z)) continue;
                s1.x = s1.x + q.x, s1.y = s1.y + q.y, s1.z = s1.z + q.z;
                s2.x = s2.x + q.x * q.x, s2.y = s2.y + q.y * q.y, s2.z = s2.z + q.z * q.z;
                k = k + 1.0f;
@@ -45,7 +50,8 @@ __global__ __launch_bounds__(kBlock) void k_hybrid_taa(FrameParams fp, TaaDev t)
          hi = v3(m1.x + t.clamp_gamma * sg.x, m1.y + t.clamp_gamma * sg.y, m1.z + t.clamp_gamma * sg.z);
       }
       float r = c.x, g = c.y, b = c.z, N = 1.0f;
-      if (t.prev_col) {
+      if (!live) N = 0.0f;
+      if (t.prev_col && live) {
          // where the history is: a geometry pixel's point, every other pixel's primary-ray direction as a point at infinity
          const float4 P4 = t.pos[i];
          bool corresponds = true;
@@ -79,6 +85,7 @@ __global__ __launch_bounds__(kBlock) void k_hybrid_taa(FrameParams fp, TaaDev t)
                   const size_t j = (size_t)(uint32_t)ty * W + (uint32_t)tx;
                   const float4 qc = t.prev_col[j];
                   const float qn = t.prev_n[j];
+                  if (qn == 0.0f) continue;
                   sw = sw + w;
                   sr = sr + w * qc.x, sg = sg + w * qc.y, sb = sb + w * qc.z, sn = sn + w * qn;
                }

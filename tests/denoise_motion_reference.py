@@ -32,7 +32,7 @@ class MotionDenoiser(dr.Denoiser):
         with np.errstate(all="ignore"):
             acc = acc.reshape(-1, 4)
             P = position.reshape(-1, 4)[:, :3]
-            geo = position.reshape(-1, 4)[:, 3] != 0
+            drawn, geo = dr.live_geometry(position, acc, n)
             PP = motion.reshape(-1, 4)[:, :3]                 # where the surface point was at the previous motion pass
             corresponds = motion.reshape(-1, 4)[:, 3] != 0
             nrm = normal.reshape(-1, 4)[:, :3]
@@ -143,4 +143,4 @@ class MotionDenoiser(dr.Denoiser):
         rgba = lambda a: np.concatenate([a, np.zeros((len(a), 1), np.float32)], axis=-1).reshape(H, W, 4)
         bgra = np.stack([srgb[:, 2], srgb[:, 1], srgb[:, 0], np.zeros(len(srgb), np.uint8)], axis=-1).reshape(H, W, 4)
         return dict(color=rgba(out), output=bgra, input=rgba(inp), temporal=rgba(temporal), history=N.reshape(H, W), variance=var0.reshape(H, W),
-                    final_variance=var.reshape(H, W), kept=kept.reshape(H, W), geometry=geo.reshape(H, W))
+                    final_variance=var.reshape(H, W), kept=kept.reshape(H, W), geometry=drawn.reshape(H, W), bad=(drawn & ~geo).reshape(H, W))

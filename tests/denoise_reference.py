@@ -7,6 +7,21 @@ F = np.float32
 TEMPORAL, DEMODULATE = 1, 2
 KERNEL = {0: F(0.375), 1: F(0.25), 2: F(0.0625)}
 CENTRE = F(0.140625)  # 9/64
+MAX_SAMPLE = F(2.0 ** 48)  # the largest channel magnitude of a sample that takes part ("Non-finite input")
+
+
+def sample_ok(c):
+    """every channel of c (..., 3) finite and at most MAX_SAMPLE in magnitude; a NaN fails the compare"""
+    with np.errstate(all="ignore"):
+        return (np.abs(c) <= MAX_SAMPLE).all(axis=-1)
+
+
+def live_geometry(position, acc, n):
+    """(drawn, live): the pixels the G-buffer wrote (position w != 0), and those of them whose stage-0 colour acc / n, before
+    demodulation, is a sample the filter takes in. A drawn pixel that is not live is treated as not geometry everywhere"""
+    drawn = position.reshape(-1, 4)[:, 3] != 0
+    with np.errstate(all="ignore"):
+        return drawn, drawn & sample_ok(acc.reshape(-1, 4)[:, :3] / n)
 
 
 def default_params(**kw):
@@ -68,7 +83,8 @@ class Denoiser:
 
     def __call__(self, acc, position, normal, albedo, pbr, view, params):
         """acc, position, normal, pbr (H, W, 4) float32, albedo (H, W, 4) uint8, view a ViewUniformData (or anything with its fields),
-        params a dict as default_params(). Returns the six images of uh_read_denoised by name, and `kept` (H, W) bool."""
+        params a dict as default_params(). Returns the six images of uh_read_denoised by name, `kept`, `geometry` (position w != 0: what
+        UhDenoiseStats.geometry_pixels counts) and `bad` (geometry the filter treated as not geometry) (H, W) bool."""
         p = params
         H, W = acc.shape[:2]
         n = F(min(int(view.total_samples), int(view.accumulation_limit)))
@@ -77,7 +93,7 @@ class Denoiser:
         with np.errstate(all="ignore"):
             acc = acc.reshape(-1, 4)
             P = position.reshape(-1, 4)[:, :3]
-            geo = position.reshape(-1, 4)[:, 3] != 0
+            drawn, geo = live_geometry(position, acc, n)
             nrm = normal.reshape(-1, 4)[:, :3]
             mesh = pbr.reshape(-1, 4)[:, 3]
             # stage 0
@@ -106,12 +122,14 @@ class Denoiser:
                 tol = F(p["reproject_plane"]) * np.abs(z)
                 sw = np.zeros(len(c), np.float32)
                 sums = [np.zeros(len(c), np.float32) for _ in range(6)]  # r, g, b, N, m1, m2
+                self.taps = []  # (in the frame with a weight, index, weight) of the four taps, for tests that reason about them
                 for t in range(4):
                     dx, dy = t & 1, t >> 1
                     w = (ax if dx else F(1.0) - ax) * (ay if dy else F(1.0) - ay)
                     tx, ty = ix + F(dx), iy + F(dy)
                     valid = ok & (w != 0) & (tx >= 0) & (tx <= F(W - 1)) & (ty >= 0) & (ty <= F(H - 1))
                     j = np.where(valid, ty, F(0.0)).astype(np.int64) * W + np.where(valid, tx, F(0.0)).astype(np.int64)
+                    self.taps.append((valid.copy(), j, w))
                     valid &= hp["geo"][j]
                     valid &= hp["mesh"][j] == mesh
                     valid &= dot3(nrm, hp["nrm"][j]) >= F(p["reproject_normal_cos"])
@@ -189,4 +207,4 @@ class Denoiser:
         rgba = lambda a: np.concatenate([a, np.zeros((len(a), 1), np.float32)], axis=-1).reshape(H, W, 4)
         bgra = np.stack([srgb[:, 2], srgb[:, 1], srgb[:, 0], np.zeros(len(srgb), np.uint8)], axis=-1).reshape(H, W, 4)
         return dict(color=rgba(out), output=bgra, input=rgba(inp), temporal=rgba(temporal), history=N.reshape(H, W), variance=var0.reshape(H, W),
-                    final_variance=var.reshape(H, W), kept=kept.reshape(H, W), geometry=geo.reshape(H, W))
+                    final_variance=var.reshape(H, W), kept=kept.reshape(H, W), geometry=drawn.reshape(H, W), bad=(drawn & ~geo).reshape(H, W))

@@ -5,6 +5,13 @@ import numpy as np
 
 F = np.float32
 CLAMP, MOTION = 1, 2
+MAX_SAMPLE = F(2.0 ** 48)  # the largest channel magnitude of a colour that takes part ("Non-finite input")
+
+
+def sample_ok(c):
+    """every channel of c (..., 3) finite and at most MAX_SAMPLE in magnitude; a NaN fails the compare"""
+    with np.errstate(all="ignore"):
+        return (np.abs(c) <= MAX_SAMPLE).all(axis=-1)
 
 
 def default_params(**kw):
@@ -40,8 +47,10 @@ def primary_directions(view, W, H):
 
 
 def box(c, W, H, gamma):
-    """(lo, hi) of step 1 for every pixel: c (H * W, 3) float32"""
+    """(lo, hi) of step 1 for every pixel: c (H * W, 3) float32. Neighbours that are not sample_ok are left out like those outside the
+    frame; the box of a pixel that is itself not sample_ok is never read (k may be 0 there)"""
     img = c.reshape(H, W, 3)
+    live = sample_ok(img)
     s1, s2, k = np.zeros_like(img), np.zeros_like(img), np.zeros((H, W, 1), np.float32)
     y, x = np.mgrid[0:H, 0:W]
     for dy in (-1, 0, 1):
@@ -49,6 +58,7 @@ def box(c, W, H, gamma):
             qx, qy = x + dx, y + dy
             inside = ((qx >= 0) & (qx < W) & (qy >= 0) & (qy < H))[..., None]
             q = img[np.clip(qy, 0, H - 1), np.clip(qx, 0, W - 1)]
+            inside = inside & live[np.clip(qy, 0, H - 1), np.clip(qx, 0, W - 1)][..., None]
             s1 = np.where(inside, s1 + q, s1)
             s2 = np.where(inside, s2 + q * q, s2)
             k = np.where(inside, k + F(1.0), k)
@@ -70,7 +80,7 @@ class Taa:
     def __call__(self, deferred, position, motion, view, params, W, H):
         """deferred, position (H, W, 4) float32, motion (H, W, 4) float32 or None (required with the MOTION flag), view a ViewUniformData
         (or anything with inverse_view, inverse_projection and prev_frame_projection_view), params a dict as default_params(). Returns
-        dict(output (H, W, 4), history (H, W), blended (H, W) bool, history_pixels, reset_pixels, lo, hi (H, W, 3) or None)."""
+        dict(output (H, W, 4), history (H, W), blended, bad (H, W) bool, history_pixels, reset_pixels, lo, hi (H, W, 3) or None)."""
         p = params
         flags = int(p["flags"])
         with np.errstate(all="ignore"):
@@ -80,7 +90,8 @@ class Taa:
             lo = hi = None
             if flags & CLAMP:
                 lo, hi = box(c, W, H, p["clamp_gamma"])
-            out, N = c.copy(), np.ones(n, np.float32)
+            live = sample_ok(c)
+            out, N = c.copy(), np.where(live, F(1.0), F(0.0))
             blended = np.zeros(n, bool)
             if self.hist is not None:
                 pv = np.array(view.prev_frame_projection_view[:], np.float32)
@@ -100,19 +111,22 @@ class Taa:
                 u = (h[0] / h[3]) * F(0.5) + F(0.5)
                 v = F(1.0) - ((h[1] / h[3]) * F(0.5) + F(0.5))
                 fx, fy = u * F(W) - F(0.5), v * F(H) - F(0.5)
-                ok = corresponds & (h[3] > 0) & np.isfinite(fx) & np.isfinite(fy)
+                ok = live & corresponds & (h[3] > 0) & np.isfinite(fx) & np.isfinite(fy)
                 fx, fy = np.where(ok, fx, F(0.0)), np.where(ok, fy, F(0.0))
                 ix, iy = np.floor(fx), np.floor(fy)
                 ax, ay = np.rint((fx - ix) * F(256.0)) / F(256.0), np.rint((fy - iy) * F(256.0)) / F(256.0)
                 sw = np.zeros(n, np.float32)
                 sums = [np.zeros(n, np.float32) for _ in range(4)]  # r, g, b, N
                 pc, pn = self.hist
+                self.taps = []  # (in the frame with a weight, index, weight) of the four taps, for tests that reason about them
                 for t in range(4):
                     dx, dy = t & 1, t >> 1
                     w = (ax if dx else F(1.0) - ax) * (ay if dy else F(1.0) - ay)
                     tx, ty = ix + F(dx), iy + F(dy)
                     valid = ok & (w != 0) & (tx >= 0) & (tx <= F(W - 1)) & (ty >= 0) & (ty <= F(H - 1))
                     j = np.where(valid, ty, F(0.0)).astype(np.int64) * W + np.where(valid, tx, F(0.0)).astype(np.int64)
+                    self.taps.append((valid.copy(), j, w))
+                    valid &= pn[j] != 0  # a texel that was not sample_ok left no history
                     sw = np.where(valid, sw + w, sw)
                     taps = [pc[j, 0], pc[j, 1], pc[j, 2], pn[j]]
                     sums = [np.where(valid, s + w * q, s) for s, q in zip(sums, taps)]
@@ -122,12 +136,15 @@ class Taa:
                 a = np.maximum(F(1.0) / Nn, F(p["alpha_min"]))
                 hc = np.stack([sums[k] / swd for k in range(3)], axis=-1)
                 if flags & CLAMP:
+                    # no NaN reaches the clamp: hc is a mean of history values, which are finite, and lo, hi come from neighbours that are
+                    # sample_ok (gamma * sg may overflow to +Inf, which only opens the box); fminf / fmaxf and these agree on such values
+                    assert not (np.isnan(hc[blended]).any() or np.isnan(lo[blended]).any() or np.isnan(hi[blended]).any())
                     hc = np.minimum(np.maximum(hc, lo), hi)
                 mixed = hc + (c - hc) * a[:, None]
                 out = np.where(blended[:, None], mixed, c)
-                N = np.where(blended, Nn, F(1.0))
+                N = np.where(blended, Nn, np.where(live, F(1.0), F(0.0)))
             self.hist = (out.copy(), N.copy())
         output = np.concatenate([out, c4[:, 3:4]], axis=-1).reshape(H, W, 4)
         shaped = lambda a: None if a is None else a.reshape(H, W, 3)
-        return dict(output=output, history=N.reshape(H, W), blended=blended.reshape(H, W), history_pixels=int(blended.sum()),
+        return dict(output=output, history=N.reshape(H, W), blended=blended.reshape(H, W), bad=~live.reshape(H, W), history_pixels=int(blended.sum()),
                     reset_pixels=int(n - blended.sum()), lo=shaped(lo), hi=shaped(hi))

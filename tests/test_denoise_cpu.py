@@ -1,9 +1,15 @@
 """CPU: the numpy restatement of uh_denoise (tests/denoise_reference.py) held to known answers on synthetic arrays - the six cases of
-DESIGN.md section 2, "Denoiser". test_gpu_denoise.py runs cases 1, 4, 5 and 6 on the device and holds the device to the restatement."""
+DESIGN.md section 2, "Denoiser". test_gpu_denoise.py runs cases 1, 4, 5 and 6 on the device and holds the device to the restatement. Then the rule for non-finite
+input ("Non-finite input") on the wall sequence of tests/temporal_cases.py: containment, that a bad pixel is
+treated as one that is not geometry, convexity, and that finite input gives the bits it always gave."""
+import os
+
 import numpy as np
 import pytest
 
+import denoise_motion_reference as dmr
 import denoise_reference as dr
+import temporal_cases as tc
 import rust_renderer_amd as rr
 from hybrid_util import cast_planes, plane_view
 
@@ -164,3 +170,111 @@ def test_pixels_that_are_not_geometry_pass_through_bit_for_bit(floor_frame, flag
             assert np.array_equal(bits(r[name][..., :3])[sky], want), name
         assert not r["history"][sky].any() and not r["variance"][sky].any()
         assert not np.array_equal(bits(r["color"][~sky]), bits(r["input"][~sky]))
+
+
+# ---- non-finite input: a bad pixel passes through and takes part in nothing ("Non-finite input") ---------------
+# The wall sequence of temporal_cases.py: call 0 clean, call 1 with the set B planted in the accumulation, the calls after it clean.
+FLOATS = ("color", "input", "temporal", "history", "variance", "final_variance")
+CASES = [pytest.param(0, False, id="plain"), pytest.param(dr.TEMPORAL, False, id="temporal"), pytest.param(dr.DEMODULATE, False, id="demodulate"),
+         pytest.param(dr.TEMPORAL | dr.DEMODULATE, False, id="temporal-demodulate"),
+         pytest.param(dr.TEMPORAL | dr.DEMODULATE, True, id="temporal-demodulate-motion")]
+
+
+def wall_calls(flags, motion, calls, edit=None):
+    """yields (k, result, acc, denoiser, the history the call read) for the wall sequence; edit(k, acc, call) may change call k's inputs"""
+    d = dmr.MotionDenoiser() if motion else dr.Denoiser()
+    p = dr.default_params(flags=flags | (dmr.MOTION if motion else 0))
+    for k in range(calls):
+        c, acc = tc.wall_call(k), tc.wall_noise(k)
+        if edit is not None:
+            acc = edit(k, acc, c)
+        before = d.hist
+        guides = (acc, c["position"], c["normal"], c["albedo"], c["pbr"]) + ((c["motion"],) if motion else ())
+        yield k, d(*guides, c["view"], p), acc, d, before
+
+
+def plant_in_call_1(k, acc, c):
+    return tc.plant(acc) if k == 1 else acc
+
+
+@pytest.mark.parametrize("flags,motion", CASES)
+def test_bad_samples_pass_through_and_reach_no_other_pixel(flags, motion):
+    bm = tc.b_mask()
+    for k, r, acc, d, before in wall_calls(flags, motion, 3, plant_in_call_1):
+        bad_now = bm if k == 1 else np.zeros_like(bm)
+        assert np.array_equal(r["bad"], bad_now) and r["geometry"].all(), "B is geometry (geometry_pixels counts it) and nothing else is bad"
+        for name in FLOATS:
+            assert np.isfinite(r[name][~bad_now]).all(), (k, name, int((~np.isfinite(r[name])).sum()))
+        if k == 1:
+            assert not np.isfinite(acc[bm][:, :3]).all(axis=-1).all() and (np.isfinite(acc[bm]).all(axis=-1)).any(), "non-finite and overflowing samples"
+            for name in ("color", "input", "temporal"):
+                assert np.array_equal(bits(r[name][bm][:, :3]), bits(acc[bm][:, :3])), name  # n = 1: the accumulation's own bits
+            assert not r["history"][bm].any() and not r["kept"][bm].any() and not r["variance"][bm].any()
+        if k == 2 and flags & dr.TEMPORAL:
+            only_bad, mixed, clean = tc.tap_kinds(d.taps, bm)
+            assert only_bad.any() and mixed.any() and clean.any(), "all three kinds of pixel exist"
+            assert (r["history"][only_bad] == 1).all() and not r["kept"][only_bad].any(), "nothing to fetch: the history starts again"
+            assert (r["history"][mixed] == 3).all() and r["kept"][mixed].all() and (r["history"][clean] == 3).all()
+            c = r["input"].reshape(-1, 4)[:, :3]
+            for i in np.flatnonzero(mixed.reshape(-1)):  # renormalised over the taps that remain: the blend from an independent fetch
+                prev = tc.renormalised(d.taps, bm, i, np.concatenate([before["col"], before["N"][:, None]], axis=1))
+                assert prev[3] == 2
+                want = prev[:3] + (c[i] - prev[:3]) * max(F(1.0) / F(3.0), F(0.2))
+                assert np.array_equal(bits(d.hist["col"][i]), bits(want)), i
+        elif k == 2:
+            assert (r["history"] == 1).all()
+
+
+@pytest.mark.parametrize("flags,motion", CASES)
+def test_a_bad_pixel_is_treated_exactly_as_a_pixel_that_is_not_geometry(flags, motion):
+    """the same sequence with B's position texels at w = 0 and finite colours there: outside B every bit is the same, in the call
+    with B and in the next"""
+    bm = tc.b_mask()
+    d2 = dmr.MotionDenoiser() if motion else dr.Denoiser()
+    p = dr.default_params(flags=flags | (dmr.MOTION if motion else 0))
+    for k, r, acc, d, before in wall_calls(flags, motion, 3, plant_in_call_1):
+        c, acc2 = tc.wall_call(k), tc.wall_noise(k)
+        if k == 1:
+            c["position"][bm, 3] = 0.0
+        guides = (acc2, c["position"], c["normal"], c["albedo"], c["pbr"]) + ((c["motion"],) if motion else ())
+        r2 = d2(*guides, c["view"], p)
+        assert not r2["bad"].any() and np.isfinite(r2["color"]).all()
+        outside = ~bm if k == 1 else np.ones_like(bm)
+        for name in FLOATS:
+            assert np.array_equal(bits(r[name])[outside], bits(r2[name])[outside]), (k, name)
+        assert np.array_equal(r["kept"], r2["kept"]) and np.array_equal(r["output"][outside], r2["output"][outside])
+
+
+# The largest relative excess of a filtered channel over the hull of the inputs, measured on these sequences with the restatement
+# itself: 0 without DEMODULATE, 3.030e-08 with it alone, 2.235e-08 with TEMPORAL as well (with and without MOTION) - the rounding of
+# the division by dm and the product with it again; the normalised sums themselves never left the hull here.
+CONVEX_MEASURED = 3.030e-08
+CONVEX_HELD = 4 * CONVEX_MEASURED
+
+
+@pytest.mark.parametrize("flags,motion", CASES)
+def test_outputs_stay_in_the_hull_of_the_finite_inputs(flags, motion):
+    bm = tc.b_mask()
+    lo, hi, worst = np.full(3, np.inf), np.full(3, -np.inf), 0.0
+    for k, r, acc, d, before in wall_calls(flags, motion, tc.CALLS, plant_in_call_1):
+        good = ~r["bad"]
+        seen = r["input"][good][:, :3].astype(np.float64)  # demodulated where the flag is set
+        assert np.isfinite(seen).all()
+        lo, hi = np.minimum(lo, seen.min(axis=0)), np.maximum(hi, seen.max(axis=0))
+        dm = np.ones((tc.H, tc.W, 3))
+        if flags & dr.DEMODULATE:
+            dm = np.maximum(tc.wall_call(k)["albedo"][..., :3].astype(np.float32) / F(255.0), F(0.01)).astype(np.float64)
+        for name in ("temporal", "color"):  # both remodulated: the hull scales by the pixel's own dm
+            out = r[name][..., :3].astype(np.float64)
+            excess = np.maximum(out - hi * dm, lo * dm - out) / (hi * dm)
+            worst = max(worst, float(excess[good].max()))
+    print(f"convexity: largest relative excess over the hull {worst:.3e}")
+    assert worst <= CONVEX_HELD
+
+
+def test_finite_input_gives_the_bits_it_gave_before_the_rule():
+    want = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "temporal_finite.npz"))
+    got = tc.finite_denoise_cases(dr, dmr)
+    assert len(got) == 60 and set(got) <= set(want.files)
+    for name, a in got.items():
+        assert np.array_equal(bits(a), bits(want[name])), name

@@ -1,10 +1,14 @@
 """CPU: camera.jitter_projection against float64 pixel coordinates, and the restatement of UH_HYBRID_TAA (tests/taa_reference.py) on
-synthetic images: known answers that need no device, and that a jittered sequence through it anti-aliases an analytic edge."""
+synthetic images: known answers that need no device, that a jittered sequence through it anti-aliases an analytic edge, and the rule
+for non-finite input ("Non-finite input") on the wall sequence of tests/temporal_cases.py."""
+import os
+
 import numpy as np
 import pytest
 
 import rust_renderer_amd as rr
 import taa_reference as tr
+import temporal_cases as tc
 
 F = np.float32
 W, H = 40, 24
@@ -217,3 +221,85 @@ def test_a_jittered_sequence_anti_aliases_a_slanted_edge():
     print(f"taa on the slanted edge: {edge.sum()} edge pixels, error {errors[15]:.4f} after 16 frames, at most {max(errors[15:]):.4f} over frames 16 to 32, "
           f"un-jittered {unjittered:.4f}")
     assert errors[15] <= 0.5 * unjittered
+
+
+# ---- non-finite input: a bad pixel passes through and takes part in nothing ("Non-finite input") ---------------
+# The wall sequence of temporal_cases.py: call 0 clean, call 1 with the set B planted in the colour image, the calls after it clean.
+NONFINITE_FLAGS = [pytest.param(0, id="free"), pytest.param(tr.CLAMP, id="clamp"), pytest.param(tr.CLAMP | tr.MOTION, id="clamp-motion")]
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def wall_frames(flags, calls):
+    """yields (k, result, input image, resolver, the history the call read) for the wall sequence with B planted in call 1"""
+    taa, p = tr.Taa(), tr.default_params(flags=flags)
+    for k in range(calls):
+        c = tc.wall_call(k)
+        img = tc.plant(tc.wall_noise(k)) if k == 1 else tc.wall_noise(k)
+        before = taa.hist
+        yield k, taa(img, c["position"], c["motion"], c["view"], p, tc.W, tc.H), img, taa, before
+
+
+@pytest.mark.parametrize("flags", NONFINITE_FLAGS)
+def test_bad_colours_pass_through_and_reach_no_other_pixel(flags):
+    bm, n = tc.b_mask(), tc.W * tc.H
+    for k, r, img, taa, before in wall_frames(flags, 3):
+        bad_now = bm if k == 1 else np.zeros_like(bm)
+        assert np.array_equal(r["bad"], bad_now)
+        assert np.isfinite(r["output"][~bad_now]).all() and np.isfinite(r["history"]).all(), k
+        assert r["history_pixels"] + r["reset_pixels"] == n and r["history_pixels"] == r["blended"].sum()
+        if flags & tr.CLAMP:
+            assert np.isfinite(r["lo"][~bad_now]).all() and np.isfinite(r["hi"][~bad_now]).all(), "the boxes leave bad neighbours out"
+        if k == 1:
+            assert np.array_equal(bits(r["output"][bm]), bits(img[bm])), "the input, bits unchanged"
+            assert not r["history"][bm].any() and (r["history"][~bm] >= 1).all(), "0 marks a texel without a history, and only that"
+            assert not r["blended"][bm].any(), "B counts in reset_pixels"
+            if flags & tr.CLAMP:  # the box beside the interior block, against float64 over the neighbours that are not bad
+                x, y = 47, 30
+                near = [img[y + dy, x + dx, :3].astype(np.float64) for dy in (-1, 0, 1) for dx in (-1, 0, 1) if not bm[y + dy, x + dx]]
+                assert len(near) == 7
+                m1, sg = np.mean(near, axis=0), np.std(near, axis=0)
+                assert np.abs(r["lo"][y, x] - (m1 - sg)).max() <= 1e-4 and np.abs(r["hi"][y, x] - (m1 + sg)).max() <= 1e-4
+        if k == 2:
+            only_bad, mixed, clean = tc.tap_kinds(taa.taps, bm)
+            assert only_bad.any() and mixed.any() and clean.any(), "all three kinds of pixel exist"
+            assert (r["history"][only_bad] == 1).all() and not r["blended"][only_bad].any(), "nothing to fetch: the history starts again"
+            assert np.array_equal(bits(r["output"][only_bad]), bits(img[only_bad]))
+            assert (r["history"][mixed] == 3).all() and r["blended"][mixed].all() and (r["history"][clean] == 3).all()
+            c, out = img.reshape(-1, 4)[:, :3], r["output"].reshape(-1, 4)[:, :3]
+            for i in np.flatnonzero(mixed.reshape(-1)):  # renormalised over the taps that remain: the blend from an independent fetch
+                prev = tc.renormalised(taa.taps, bm, i, np.concatenate([before[0], before[1][:, None]], axis=1))
+                assert prev[3] == 2
+                hc = prev[:3]
+                if flags & tr.CLAMP:
+                    hc = np.minimum(np.maximum(hc, r["lo"].reshape(-1, 3)[i]), r["hi"].reshape(-1, 3)[i])
+                assert np.array_equal(bits(out[i]), bits(hc + (c[i] - hc) * (F(1.0) / F(3.0)))), i
+
+
+# The largest relative excess of an output channel over the hull of the finite inputs so far, measured with the restatement itself on
+# these sequences: 0 - hc + (c - hc) * a never left [hc, c], and a clamped hc lies between the fetched one and the box's mean.
+TAA_CONVEX_MEASURED = 0.0
+TAA_CONVEX_HELD = 4 * TAA_CONVEX_MEASURED
+
+
+@pytest.mark.parametrize("flags", NONFINITE_FLAGS)
+def test_outputs_stay_in_the_hull_of_the_finite_inputs(flags):
+    lo, hi, worst = np.full(3, np.inf), np.full(3, -np.inf), -np.inf
+    for k, r, img, taa, before in wall_frames(flags, tc.CALLS):
+        good = ~r["bad"]
+        seen = img[good][:, :3].astype(np.float64)
+        lo, hi = np.minimum(lo, seen.min(axis=0)), np.maximum(hi, seen.max(axis=0))
+        out = r["output"][good][:, :3].astype(np.float64)
+        worst = max(worst, float((np.maximum(out - hi, lo - out) / hi).max()))
+    print(f"taa convexity: largest relative excess over the hull {max(worst, 0.0):.3e}")
+    assert max(worst, 0.0) <= TAA_CONVEX_HELD
+
+
+def test_finite_input_gives_the_bits_it_gave_before_the_rule():
+    want = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "temporal_finite.npz"))
+    got = tc.finite_taa_cases(tr)
+    assert len(got) == 18 and set(got) <= set(want.files)
+    for name, a in got.items():
+        assert np.array_equal(bits(a), bits(want[name])), name
