@@ -1,22 +1,20 @@
-// context.hip — the C ABI of include/utopian_hip.h: context lifetime, textures and lights, the sun and camera grids,
-// the per-frame pass chain and read-backs. Host-side counterpart of
-// utopian::Renderer (utopian/src/renderer.rs), utopian::Raytracing (utopian/src/raytracing.rs) and
+// context.hip — the C ABI of include/utopian_hip.h: context lifetime, textures and lights, the per-frame pass chain and
+// read-backs. Host-side counterpart of utopian::Renderer (utopian/src/renderer.rs), utopian::Raytracing (utopian/src/raytracing.rs) and
 // build_path_tracing_render_graph (utopian/src/renderers/mod.rs:189-375) for this path only.
 // struct uh_ctx is context_state.h; meshes, the tree builders and the refit are scene_build.hip; the hybrid and the forward graph
-// (uh_render_hybrid, uh_render_forward) are hybrid_graph.hip and forward_graph.hip over raster_driver.hip, the denoiser denoise_graph.hip.
+// (uh_render_hybrid, uh_render_forward) are hybrid_graph.hip and forward_graph.hip over raster_driver.hip, the denoiser denoise_graph.hip;
+// the sun and camera grids' upkeep is grid_cache.hip.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: the library opens librccl at run time (uh_rccl_attach)
 #include <dlfcn.h>
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdlib>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "bvh.h"
@@ -176,9 +174,9 @@ int uh_create(int device_ordinal, uint32_t width, uint32_t height, uh_ctx** out)
    c->im.prev_spatial = c->reservoirs[2].p;
    c->res_stride = n;
    c->rp_band_rows = height;
-   c->cam_limits.max_walk = 48;          // a pixel listing more packets than this hands its ray to the tree walk
-   c->cam_limits.max_mean_list = 24.0;   // entries per occupied pixel beyond which the grid is refused (the tree walk costs about 20 records per ray)
-   c->cam_limits.max_fallback_area = 2.0;
+   c->cam.limits.max_walk = 48;          // a pixel listing more packets than this hands its ray to the tree walk
+   c->cam.limits.max_mean_list = 24.0;   // entries per occupied pixel beyond which the grid is refused (the tree walk costs about 20 records per ray)
+   c->cam.limits.max_fallback_area = 2.0;
    // a runtime of another release than the one the library was built with: uh_last_error(NULL) says so after a SUCCESSFUL create too,
    // and stderr once per process
    g_create_error = hip_skew_warning();
@@ -230,12 +228,9 @@ void uh_destroy(uh_ctx* c) {
    c->d_src.release();
    c->d_tex.release();
    c->d_lut.release();
-   c->d_sun_cells.release();
-   c->d_sun_entries.release();
-   c->d_sun_recs.release();
-   c->d_sun_coarse.release();
-   c->d_cam_cells.release();
-   c->d_cam_entries.release();
+   c->sun.release();
+   c->sun_x.release();
+   c->cam.release();
    c->accumulation.release();
    c->gbuffer.release();
    c->output.release();
@@ -400,247 +395,6 @@ static int ensure_slot(uh_ctx* c, uint32_t i, uint32_t batch = 1) {
    return UH_OK;
 }
 
-static int attach_sun_inline_records(uh_ctx* c);
-// the grid `g` (or its refusal) becomes the context's grid for (geom, dir). Frames in flight may still read the old buffers.
-static int adopt_sun_grid(uh_ctx* c, const SunGridHost& g, bool ok, const float dir[3], uint64_t geom, float build_ms) {
-   if (int st = sync_all(c)) return st;
-   c->sun_attempted = true;
-   c->sun_have_pending = false;
-   c->sun_geom = geom;
-   std::memcpy(c->sun_dir_built, dir, sizeof(float) * 3);
-   c->sun_valid = false;
-   c->sun_why = g.why_not;
-   c->sun_mean_list = (float)g.mean_list;
-   c->sun_max_list = g.max_list;
-   c->sun_fallback_area = (float)g.fallback_area;
-   c->sun_cells = c->sun_entries = 0;
-   if (ok) {
-      // per cell four words: offset into the entries | cover depth | the first entry (packet, far depth) (sun_grid.h kSunCellWords)
-      std::vector<uint32_t> cells(kSunCellWords * g.cell_start.size());
-      for (size_t k = 0; k < g.cell_start.size(); k++) {
-         const float cover = k < g.cell_cover.size() ? g.cell_cover[k] : -INFINITY;
-         cells[kSunCellWords * k] = g.cell_start[k];
-         std::memcpy(&cells[kSunCellWords * k + 1], &cover, 4);
-         SunGridEntry first{kEmptyRef, 0.0f};
-         if (k + 1 < g.cell_start.size() && g.cell_start[k + 1] > g.cell_start[k]) first = g.entries[g.cell_start[k]];
-         cells[kSunCellWords * k + 2] = first.packet;
-         std::memcpy(&cells[kSunCellWords * k + 3], &first.wmax, 4);
-      }
-      HIP_TRY(c, c->d_sun_cells.alloc(cells.size()));
-      HIP_TRY(c, c->d_sun_entries.alloc(g.entries.size() ? g.entries.size() : 1));
-      HIP_TRY(c, hipMemcpy(c->d_sun_cells.p, cells.data(), cells.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-      if (!g.entries.empty()) HIP_TRY(c, hipMemcpy(c->d_sun_entries.p, g.entries.data(), g.entries.size() * sizeof(SunGridEntry), hipMemcpyHostToDevice));
-      SunGridDev& d = c->sun_dev;
-      std::memcpy(d.U, g.U, sizeof(d.U));
-      std::memcpy(d.V, g.V, sizeof(d.V));
-      std::memcpy(d.W, g.W, sizeof(d.W));
-      d.u0 = g.u0;
-      d.v0 = g.v0;
-      d.inv_cell = g.inv_cell;
-      d.nx = g.nx;
-      d.ny = g.ny;
-      d.max_walk = c->sun_limits.max_walk;
-      d.cell_start = c->d_sun_cells.p;
-      d.entries = c->d_sun_entries.p;
-      c->sun_cells = g.nx * g.ny;
-      c->sun_entries = (uint32_t)g.entries.size();
-      c->sun_valid = true;
-   } else {
-      c->d_sun_cells.release();
-      c->d_sun_entries.release();
-   }
-   c->sun_build_ms = build_ms;
-   return attach_sun_inline_records(c);
-}
-
-// the device builder's result becomes the context's grid (its buffers change owner)
-static int adopt_sun_grid_device(uh_ctx* c, SunGridDevice& g, bool ok, const float dir[3], uint64_t geom) {
-   c->sun_attempted = true;
-   c->sun_have_pending = false;
-   c->sun_geom = geom;
-   std::memcpy(c->sun_dir_built, dir, sizeof(float) * 3);
-   c->sun_valid = false;
-   c->sun_why = g.why_not;
-   c->sun_mean_list = (float)g.mean_list;
-   c->sun_max_list = g.max_list;
-   c->sun_fallback_area = (float)g.fallback_area;
-   c->sun_cells = c->sun_entries = 0;
-   c->d_sun_cells.release();
-   c->d_sun_entries.release();
-   if (ok) {
-      const size_t ncell = (size_t)g.params.nx * g.params.ny;
-      c->d_sun_cells.p = g.cells;
-      c->d_sun_cells.base = g.cells;
-      c->d_sun_cells.n = kSunCellWords * (ncell + 1);
-      c->d_sun_entries.p = g.entries;
-      c->d_sun_entries.base = g.entries;
-      c->d_sun_entries.n = (size_t)g.num_entries;
-      g.cells = nullptr;
-      g.entries = nullptr;
-      SunGridDev& d = c->sun_dev;
-      std::memcpy(d.U, g.params.U, sizeof(d.U));
-      std::memcpy(d.V, g.params.V, sizeof(d.V));
-      std::memcpy(d.W, g.params.W, sizeof(d.W));
-      d.u0 = g.params.u0;
-      d.v0 = g.params.v0;
-      d.inv_cell = g.params.inv_cell;
-      d.nx = g.params.nx;
-      d.ny = g.params.ny;
-      d.max_walk = c->sun_limits.max_walk;
-      d.cell_start = c->d_sun_cells.p;
-      d.entries = c->d_sun_entries.p;
-      c->sun_cells = g.params.nx * g.params.ny;
-      c->sun_entries = (uint32_t)g.num_entries;
-      c->sun_valid = true;
-   }
-   g.release();
-   return attach_sun_inline_records(c);
-}
-
-// the adopted grid's lists once more with the packets inline (sun_grid.h SunGridDev::recs): 64 bytes per entry
-static int attach_sun_inline_records(uh_ctx* c) {
-   c->d_sun_recs.release();
-   c->sun_dev.recs = nullptr;
-   c->d_sun_coarse.release();
-   c->sun_dev.coarse = nullptr;
-   c->sun_dev.coarse_shift = c->sun_dev.coarse_nx = 0;
-   if (c->sun_valid && c->sun_coarse_shift) {  // the coarse cover (sun_grid.h)
-      const uint32_t sh = c->sun_coarse_shift, b = 1u << sh, cnx = (c->sun_dev.nx + b - 1) / b, cny = (c->sun_dev.ny + b - 1) / b;
-      HIP_TRY(c, c->d_sun_coarse.alloc((size_t)cnx * cny));
-      HIP_TRY(c, (hipError_t)build_sun_coarse_cover((void*)c->stream, c->d_sun_cells.p, c->sun_dev.nx, c->sun_dev.ny, sh, c->d_sun_coarse.p));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      c->sun_dev.coarse = c->d_sun_coarse.p;
-      c->sun_dev.coarse_shift = sh;
-      c->sun_dev.coarse_nx = cnx;
-   }
-   const uint64_t n = c->sun_entries;
-   const uint64_t budget = c->sun_inline_max_mb < 0 ? 4ull * 16 * kTriStride16 * c->scene.num_tris : (uint64_t)c->sun_inline_max_mb << 20;
-   if (!c->sun_valid || n == 0 || n * 64ull > budget) return UH_OK;
-   if (c->d_sun_recs.alloc((size_t)n * 4) != hipSuccess) {  // no room: the plain lists serve
-      (void)hipGetLastError();
-      return UH_OK;
-   }
-   HIP_TRY(c, (hipError_t)build_sun_inline_records((void*)c->stream, c->d_tris.p, c->d_sun_entries.p, n, c->d_sun_recs.p));
-   HIP_TRY(c, hipStreamSynchronize(c->stream));
-   c->sun_dev.recs = reinterpret_cast<const float*>(c->d_sun_recs.p);
-   return UH_OK;
-}
-
-// the sun grid for this frame's direction, if there is (or now should be) one: see uh_ctx::sun_*
-static int ensure_sun_grid(uh_ctx* c, const float dir[3]) {
-   c->sun_this_frame = false;
-   if (!c->sun_grid_enabled || c->scene.num_tris == 0) return UH_OK;
-   const bool same_geom = c->sun_geom == c->geom_version;
-   const bool same_dir = std::memcmp(dir, c->sun_dir_built, sizeof(float) * 3) == 0;
-   if (same_geom && c->sun_attempted && same_dir) {
-      c->sun_have_pending = false;
-      c->sun_this_frame = c->sun_valid;
-      return UH_OK;
-   }
-   if (c->sun_attempted) {
-      // another direction or other geometry than the grid's (a sun dragged in the UI, instances moved with rebuild_tlas every
-      // frame): rebuild once the same pair has been asked for twice in a row, walk the tree meanwhile - a build costs as much
-      // as a thousand frames' worth of what the grid saves
-      const bool settled = c->sun_have_pending && c->sun_geom_pending == c->geom_version && std::memcmp(dir, c->sun_dir_pending, sizeof(float) * 3) == 0;
-      std::memcpy(c->sun_dir_pending, dir, sizeof(float) * 3);
-      c->sun_geom_pending = c->geom_version;
-      c->sun_have_pending = true;
-      if (!settled) return UH_OK;
-   }
-   // build: the packets as the device holds them (leaf order; host build, device build and refit all end there)
-   const uint32_t n = c->scene.num_tris;
-   if (c->sun_device_build) {
-      // on the device, from the packets where they lie: a few milliseconds, inside this frame call; the frames in flight may still
-      // read the grid this one replaces
-      if (int st = sync_all(c)) return st;
-      const auto t0 = std::chrono::steady_clock::now();
-      SunGridDevice g;
-      const bool ok = build_sun_grid_device((void*)c->stream, c->d_tris.p, n, dir, c->sun_limits, nullptr, g);
-      if (!ok && g.why_not.rfind("device build:", 0) == 0) return fail(c, UH_ERR_HIP, "sun grid: " + g.why_not);
-      if (int st = adopt_sun_grid_device(c, g, ok, dir, c->geom_version)) return st;
-      c->sun_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      c->sun_this_frame = c->sun_valid;
-      return UH_OK;
-   }
-   int threads = (int)std::thread::hardware_concurrency();
-   threads = threads < 1 ? 1 : (threads > 32 ? 32 : threads);
-   if (int st = sync_all(c)) return st;
-   const auto t0 = std::chrono::steady_clock::now();
-   std::vector<float> packets(12 * (size_t)n);
-   HIP_TRY(c, hipMemcpy2D(packets.data(), sizeof(TriPacket), c->d_tris.p, 16 * kTriStride16, sizeof(TriPacket), n, hipMemcpyDeviceToHost));
-   SunGridHost g;
-   const bool ok = build_sun_grid(packets.data(), n, dir, c->sun_limits, threads, g);
-   if (int st = adopt_sun_grid(c, g, ok, dir, c->geom_version, 0.0f)) return st;
-   c->sun_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-   c->sun_this_frame = c->sun_valid;
-   return UH_OK;
-}
-
-// the camera grid for this call's camera, if there is (or now should be) one: see uh_ctx::cam_*
-static int ensure_camera_grid(uh_ctx* c, const FrameParams& fp, uint32_t batch) {
-   c->cam_this_frame = false;
-   if (!c->cam_grid_enabled || c->scene.num_tris == 0) return UH_OK;
-   float mats[32];
-   std::memcpy(mats, fp.inv_view, sizeof(float) * 16);
-   std::memcpy(mats + 16, fp.inv_proj, sizeof(float) * 16);
-   const bool same = c->cam_attempted && c->cam_geom == c->geom_version && std::memcmp(mats, c->cam_mats, sizeof(mats)) == 0;
-   if (same) {
-      c->cam_have_pending = false;
-      c->cam_this_frame = c->cam_valid;
-      return UH_OK;
-   }
-   // another camera or other geometry than the grid's: build once the same pair has been asked for twice in a row - or at once
-   // when this call alone carries enough frames of it to repay the build
-   const bool settled = c->cam_have_pending && c->cam_geom_pending == c->geom_version && std::memcmp(mats, c->cam_mats_pending, sizeof(mats)) == 0;
-   std::memcpy(c->cam_mats_pending, mats, sizeof(mats));
-   c->cam_geom_pending = c->geom_version;
-   c->cam_have_pending = true;
-   if (!settled && batch < 8) return UH_OK;
-   if (int st = sync_all(c)) return st;
-   const auto t0 = std::chrono::steady_clock::now();
-   SunGridDevice g;
-   const bool ok = build_camera_grid_device((void*)c->stream, c->d_tris.p, c->scene.num_tris, fp.inv_view, fp.inv_proj, c->W, c->H, c->cam_limits, g);
-   if (!ok && g.why_not.rfind("device build:", 0) == 0) return fail(c, UH_ERR_HIP, "camera grid: " + g.why_not);
-   c->cam_attempted = true;
-   c->cam_have_pending = false;
-   c->cam_geom = c->geom_version;
-   std::memcpy(c->cam_mats, mats, sizeof(mats));
-   c->cam_valid = false;
-   c->cam_why = g.why_not;
-   c->cam_mean_list = (float)g.mean_list;
-   c->cam_max_list = g.max_list;
-   c->cam_max_list_interior = g.max_list_interior;
-   c->cam_cells = c->cam_entries = 0;
-   c->d_cam_cells.release();
-   c->d_cam_entries.release();
-   if (ok) {
-      const size_t ncell = (size_t)g.params.nx * g.params.ny;
-      c->d_cam_cells.p = g.cells;
-      c->d_cam_cells.base = g.cells;
-      c->d_cam_cells.n = ncell + 1;
-      c->d_cam_entries.p = g.entries;
-      c->d_cam_entries.base = g.entries;
-      c->d_cam_entries.n = (size_t)g.num_entries;
-      g.cells = nullptr;
-      g.entries = nullptr;
-      SunGridDev& d = c->cam_dev;
-      d = SunGridDev{};
-      d.nx = g.params.nx;
-      d.ny = g.params.ny;
-      d.max_walk = c->cam_limits.max_walk;
-      d.walk_whole = c->cam_walk_whole;
-      d.cell_start = c->d_cam_cells.p;
-      d.entries = c->d_cam_entries.p;
-      c->cam_cells = c->W * c->H;
-      c->cam_entries = (uint32_t)g.num_entries;
-      c->cam_valid = true;
-   }
-   g.release();
-   c->cam_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-   c->cam_this_frame = c->cam_valid;
-   return UH_OK;
-}
-
 // reference_pt_pass of one frame on one slot (reference.rgen:22-145 as a kernel chain)
 static int enqueue_path_trace(uh_ctx* c, Slot& s, const FrameParams& frame) {
    FrameParams fp = frame;  // + sun_verdicts, which follows the launches chosen below
@@ -671,12 +425,12 @@ static int enqueue_path_trace(uh_ctx* c, Slot& s, const FrameParams& frame) {
       // the grid serves them (the tree walk of every sun ray keeps the read-modify-write: a plane to clear and an atomic per lit ray
       // otherwise), when no light ray adds to the same radiance behind them (the reference adds the sun's term first, rgen:63-122, and
       // float addition does not commute bit for bit) and when the wavefront runs every bounce (the fused kernel adds its own terms)
-      fp.sun_verdicts = (c->sun_verdicts && c->sun_this_frame && fp.sun_shadow_enabled == 1 && fp.lights_enabled != 1 && !fused) ? 1u : 0u;
+      fp.sun_verdicts = (c->sun_x.verdicts && c->sun.this_frame && fp.sun_shadow_enabled == 1 && fp.lights_enabled != 1 && !fused) ? 1u : 0u;
       for (uint32_t b = 0; b < (fused ? 1u : fp.num_bounces); b++) {
-         begin_timed(c, (b == 0 && c->cam_this_frame) ? 3 : 0, s.stream);
-         if (b == 0 && c->cam_this_frame) {
+         begin_timed(c, (b == 0 && c->cam.this_frame) ? 3 : 0, s.stream);
+         if (b == 0 && c->cam.this_frame) {
             // no tree walk for the primary rays of a camera at rest (and no launch for one when no pixel's list is too long for the grid kernel)
-            launch_trace_camera_grid(lc, fp, c->scene, s.ps, ctl, st, slot, slot + 1, c->cam_dev, c->cam_max_list_interior > std::max(c->cam_dev.walk_whole, c->cam_dev.max_walk));
+            launch_trace_camera_grid(lc, fp, c->scene, s.ps, ctl, st, slot, slot + 1, c->cam.dev, c->cam.max_list_interior > std::max(c->cam.dev.walk_whole, c->cam.dev.max_walk));
             slot += 2;
          } else
             launch_trace_closest(lc, c->scene, s.ps, ctl, st, b, slot++, b == 0 ? UH_RAY_PRIMARY : UH_RAY_BOUNCE);
@@ -711,8 +465,8 @@ static int enqueue_path_trace(uh_ctx* c, Slot& s, const FrameParams& frame) {
          }
          if (fp.sun_shadow_enabled == 1 && !fused_sun0) {
             begin_timed(c, 1, sh_stream);
-            if (c->sun_this_frame) {
-               launch_trace_sun_grid(lsh, fp, c->scene, s.ps, ctl, st, b, slot++, c->sun_dev);
+            if (c->sun.this_frame) {
+               launch_trace_sun_grid(lsh, fp, c->scene, s.ps, ctl, st, b, slot++, c->sun.dev);
                launch_trace_shadow(lsh, fp, c->scene, s.ps, ctl, st, b, slot++, false, true);  // the rays the grid handed over (border cells, long lists)
             } else
                launch_trace_shadow(lsh, fp, c->scene, s.ps, ctl, st, b, slot++, false);
@@ -734,7 +488,7 @@ static int enqueue_path_trace(uh_ctx* c, Slot& s, const FrameParams& frame) {
       }
       if (fused) {
          begin_timed(c, 0, s.stream);
-         launch_path_fused(lc, fp, c->scene, s.ps, ctl, st, c->sun_dev, c->sun_this_frame, fused_sun0);
+         launch_path_fused(lc, fp, c->scene, s.ps, ctl, st, c->sun.dev, c->sun.this_frame, fused_sun0);
          end_timed(c, s.stream);
       }
       if (join_side && fused_sun0) {  // (bounce 0's sky integrals ran beside the fused kernel)
@@ -826,12 +580,12 @@ static int batch_begin(uh_ctx* c, const UhViewUniformData* view, uint32_t pass_m
       fp.frame_numbers[f] = (uint32_t)(int32_t)((float)total + view->time * 10000.0f);
    }
    // the per-camera grid serves the primary rays of the path tracer and the G-buffer cast of this call
-   c->cam_this_frame = false;
+   c->cam.this_frame = false;
    const bool primary_rays = ((pass_mask & UH_PASS_REFERENCE_PT) && fp.num_bounces > 0 && fp.samples_per_frame > 0) || (pass_mask & UH_PASS_GBUFFER);
    if (primary_rays)
       if (int st = ensure_camera_grid(c, fp, batch)) return st;
    // with the camera grid nothing but bounce 0's own kernels reads a primary ray's state: it is not stored
-   fp.primary_implicit = (c->primary_implicit && c->cam_this_frame && fp.samples_per_frame == 1) ? 1u : 0u;
+   fp.primary_implicit = (c->primary_implicit && c->cam.this_frame && fp.samples_per_frame == 1) ? 1u : 0u;
    bs.pass_mask = pass_mask;
    bs.batch = batch;
    bs.restir_frame = (pass_mask & UH_PASS_RESTIR) != 0;
@@ -890,7 +644,7 @@ static int batch_restir_frame(uh_ctx* c, uh_batch& bs, uint32_t f) {
          HIP_TRY(c, c->gb_hit.alloc(npix));
       }
       const RawRays gps{c->gb_ray_o.p, c->gb_ray_d.p, c->gb_hit.p};
-      launch_gbuffer(bs.rc, ff, c->scene, gps, im, c->dstats.p, cast, band.total(), c->cam_this_frame ? &c->cam_dev : nullptr);
+      launch_gbuffer(bs.rc, ff, c->scene, gps, im, c->dstats.p, cast, band.total(), c->cam.this_frame ? &c->cam.dev : nullptr);
    }
    if (pass_mask & UH_PASS_RESET_RESERVOIRS) launch_reset_reservoirs(bs.rc, ff, im, reuse);
    if (pass_mask & UH_PASS_INITIAL_RIS) launch_initial_ris(bs.rc, ff, c->scene, im, reuse);
@@ -936,7 +690,7 @@ static int batch_end(uh_ctx* c, uh_batch& bs) {
    for (uint32_t f = 0; f < kMaxBatchFrames; f++) fp.spatial_of[f] = spatial_buf(c, bs.read_slot[f < batch ? f : 0]);
 
    if (bs.pass_mask & UH_PASS_REFERENCE_PT) {
-      c->sun_this_frame = false;
+      c->sun.this_frame = false;
       if (fp.sun_shadow_enabled == 1 && fp.num_bounces > 0 && fp.samples_per_frame > 0)
          if (int st = ensure_sun_grid(c, fp.sun_dir)) return st;
       const uint32_t in_flight = c->frames_in_flight ? c->frames_in_flight : 1;
@@ -1238,20 +992,11 @@ int uh_get_stats(uh_ctx* c, UhStats* out) {
    out->light_nodes_visited = ds.light_nodes_visited;
    out->light_tris_tested = ds.light_tris_tested;
    out->trace_closest_launches = c->trace_closest_launches;
-   out->sun_grid_cells = c->sun_valid ? c->sun_cells : 0;
-   out->sun_grid_entries = c->sun_valid ? c->sun_entries : 0;
-   out->sun_grid_build_ms = c->sun_build_ms;
-   out->sun_grid_mean_list = c->sun_mean_list;
    out->sun_tree_rays = ds.sun_tree_rays;
-   out->camera_grid_cells = c->cam_valid && c->cam_this_frame ? c->cam_cells : 0;  // in use by the last frame call
-   out->camera_grid_entries = c->cam_valid && c->cam_this_frame ? c->cam_entries : 0;
-   out->camera_grid_build_ms = c->cam_build_ms;
-   out->camera_grid_mean_list = c->cam_mean_list;
    out->camera_tree_rays = ds.cam_tree_rays;
    out->camera_grid_tris_tested = ds.cam_tris_tested;
    out->sun_covered_rays = ds.sun_covered_rays;
-   if (c->sun_valid) out->sun_grid_bytes = c->d_sun_cells.n * sizeof(uint32_t) + c->d_sun_entries.n * sizeof(SunGridEntry) + c->d_sun_recs.n * sizeof(float4) + c->d_sun_coarse.n * sizeof(float);
-   if (c->cam_valid && c->cam_this_frame) out->camera_grid_bytes = c->d_cam_cells.n * sizeof(uint32_t) + c->d_cam_entries.n * sizeof(SunGridEntry);
+   grid_stats(c, out);
    return UH_OK;
 }
 
@@ -1305,60 +1050,60 @@ int uh_set_option(uh_ctx* c, const char* name, int value) {
    else if (n == "sun_grid")
       c->sun_grid_enabled = value != 0;  // 0: the sun shadow rays always walk the tree
    else if (n == "sun_grid_build") {
-      c->sun_device_build = value != 0;  // 1: built on the device (sun_grid_build.hip); 0: by the host builder (sun_grid.cpp, the reference implementation)
-      c->sun_attempted = false;
+      c->sun_x.device_build = value != 0;  // 1: built on the device (sun_grid_build.hip); 0: by the host builder (sun_grid.cpp, the reference implementation)
+      c->sun.cache.invalidate();
    } else if (n == "sun_grid_density") {
       if (!range(1, 4096)) return bad("(entries per triangle) must be 1..4096");
-      c->sun_limits.entries_per_triangle = (double)value;
-      c->sun_attempted = false;
+      c->sun.limits.entries_per_triangle = (double)value;
+      c->sun.cache.invalidate();
    } else if (n == "sun_grid_max_walk") {
       if (!range(1, 4096)) return bad("(longest list a ray tests itself) must be 1..4096");
-      c->sun_limits.max_walk = (uint32_t)value;
-      c->sun_attempted = false;
+      c->sun.limits.max_walk = (uint32_t)value;
+      c->sun.cache.invalidate();
    } else if (n == "sun_grid_max_mb") {
       if (!range(1, 65536)) return bad("must be 1..65536");
-      c->sun_limits.max_entries = ((uint64_t)value << 20) / sizeof(SunGridEntry);
-      c->sun_attempted = false;
+      c->sun.limits.max_entries = ((uint64_t)value << 20) / sizeof(SunGridEntry);
+      c->sun.cache.invalidate();
    } else if (n == "sun_grid_force") {
       // 1: the grid is never refused for what it would be worth (more than 12 entries per occupied cell, more than a fifth of the scene's
       // surface handed to the tree): tests and studies of scenes the defaults would refuse; 0: the defaults
       const SunGridLimits defaults;
-      c->sun_limits.max_mean_list = value ? 1e30 : defaults.max_mean_list;
-      c->sun_limits.max_fallback_area = value ? 2.0 : defaults.max_fallback_area;
-      c->sun_attempted = false;
+      c->sun.limits.max_mean_list = value ? 1e30 : defaults.max_mean_list;
+      c->sun.limits.max_fallback_area = value ? 2.0 : defaults.max_fallback_area;
+      c->sun.cache.invalidate();
    } else if (n == "sun_grid_inline_max_mb") {
       // the lists a second time as 64-byte records that carry their packet (one round trip per triangle test instead of two): memory budget
       // in MB; -1 (default) = four times the packet array; 0 = never
       if (!range(-1, 1 << 20)) return bad("must be -1 (auto: 4 x the packet array), 0 (off) .. 1048576");
-      c->sun_inline_max_mb = value;
-      c->sun_attempted = false;
+      c->sun_x.inline_max_mb = value;
+      c->sun.cache.invalidate();
    } else if (n == "sun_verdicts")
       // 1: the grid's sun kernels leave one bit per ray and the next shading kernel (or the flush) adds the lit paths' throughput to
       // their radiance; 0: the sun kernels add it themselves. Same images; frames with lights enabled always take the second form
-      c->sun_verdicts = value != 0;
+      c->sun_x.verdicts = value != 0;
    else if (n == "sun_grid_coarse") {
       // the coarse cover (sun_grid.h): one depth per block of 2^value x 2^value cells, asked before the cell's own record; 0: none
       if (!range(0, 6)) return bad("(log2 of the block edge in cells) must be 0..6");
-      c->sun_coarse_shift = (uint32_t)value;
-      c->sun_attempted = false;
+      c->sun_x.coarse_shift = (uint32_t)value;
+      c->sun.cache.invalidate();
    }
    // ---- the camera grid
    else if (n == "camera_grid")
       c->cam_grid_enabled = value != 0;  // 0: the primary rays always walk the tree
    else if (n == "camera_grid_max_walk") {
       if (!range(1, 4096)) return bad("must be 1..4096");
-      c->cam_limits.max_walk = (uint32_t)value;
-      c->cam_attempted = false;
+      c->cam.limits.max_walk = (uint32_t)value;
+      c->cam.cache.invalidate();
    } else if (n == "camera_grid_walk_whole") {
       // lists of up to this many packets are walked whole by the grid kernel (those beyond camera_grid_max_walk are not sorted: no early
       // exit) instead of handing the ray to the tree; 0: every list beyond camera_grid_max_walk goes to the tree
       if (!range(0, 65536)) return bad("must be 0..65536");
       c->cam_walk_whole = (uint32_t)value;
-      c->cam_attempted = false;
+      c->cam.cache.invalidate();
    } else if (n == "camera_grid_max_mean_list_x10") {
       if (!range(1, 100000)) return bad("must be 1..100000");
-      c->cam_limits.max_mean_list = value / 10.0;
-      c->cam_attempted = false;
+      c->cam.limits.max_mean_list = value / 10.0;
+      c->cam.cache.invalidate();
    } else if (n == "primary_implicit")
       c->primary_implicit = value != 0;  // 0: bounce 0's state planes are stored by k_generate even when the camera grid is in use
    // ---- what the frames compute
@@ -1685,75 +1430,6 @@ int uh_rccl_gather_tiles(uh_ctx* c, uint32_t root, uint32_t total_samples, uint3
    if (r != ncclSuccess) return fail(c, UH_ERR_HIP, std::string("uh_rccl_gather_tiles: ") + (api->GetErrorString ? api->GetErrorString(r) : "RCCL error"));
    if (is_root) return uhi_enqueue_compose_tiles(c, c->tile_recv.p, stride, total_samples, accumulation_limit, nullptr, 0);
    return mark_composed(c);
-}
-
-// diagnostics: the grid in use (built on the device) against the host builder on the same raster - see utopian_hip.h
-int uh_sun_grid_compare_builders(uh_ctx* c, uint64_t out[8]) {
-   if (!c || !out) return UH_ERR_INVALID_ARGUMENT;
-   for (int k = 0; k < 8; k++) out[k] = 0;
-   HIP_TRY(c, hipSetDevice(c->device));
-   if (int st = sync_all(c)) return st;
-   if (!c->sun_valid) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_sun_grid_compare_builders: no sun grid in use (" + c->sun_why + ")");
-   const uint32_t n = c->scene.num_tris;
-   const size_t ncell = (size_t)c->sun_dev.nx * c->sun_dev.ny;
-   std::vector<float> packets(12 * (size_t)n);
-   HIP_TRY(c, hipMemcpy2D(packets.data(), sizeof(TriPacket), c->d_tris.p, 16 * kTriStride16, sizeof(TriPacket), n, hipMemcpyDeviceToHost));
-   std::vector<uint32_t> cells(kSunCellWords * (ncell + 1));
-   std::vector<SunGridEntry> entries(c->sun_entries);
-   HIP_TRY(c, hipMemcpy(cells.data(), c->d_sun_cells.p, cells.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-   if (!entries.empty()) HIP_TRY(c, hipMemcpy(entries.data(), c->d_sun_entries.p, entries.size() * sizeof(SunGridEntry), hipMemcpyDeviceToHost));
-   SunGridParams prm;
-   std::memcpy(prm.U, c->sun_dev.U, sizeof(prm.U));
-   std::memcpy(prm.V, c->sun_dev.V, sizeof(prm.V));
-   std::memcpy(prm.W, c->sun_dev.W, sizeof(prm.W));
-   prm.u0 = c->sun_dev.u0;
-   prm.v0 = c->sun_dev.v0;
-   prm.inv_cell = c->sun_dev.inv_cell;
-   prm.nx = c->sun_dev.nx;
-   prm.ny = c->sun_dev.ny;
-   SunGridLimits lim = c->sun_limits;
-   lim.max_mean_list = 1e30;  // the comparison wants the host grid whatever the host builder thinks of its worth
-   lim.max_fallback_area = 2.0;
-   SunGridHost h;
-   int threads = (int)std::thread::hardware_concurrency();
-   threads = threads < 1 ? 1 : (threads > 32 ? 32 : threads);
-   if (!build_sun_grid(packets.data(), n, c->sun_dir_built, lim, threads, h, &prm)) return fail(c, UH_ERR_INVALID_ARGUMENT, "host builder refused: " + h.why_not);
-   out[0] = ncell;
-   out[1] = entries.size();
-   out[2] = h.entries.size();
-   if (h.cell_start.size() != ncell + 1) return fail(c, UH_ERR_INVALID_ARGUMENT, "host grid has another raster");
-   std::vector<uint32_t> a, b;
-   for (size_t k = 0; k < ncell; k++) {
-      const uint32_t d0 = cells[kSunCellWords * k], d1 = cells[kSunCellWords * (k + 1)], h0 = h.cell_start[k], h1 = h.cell_start[k + 1];
-      uint32_t hc;
-      std::memcpy(&hc, &h.cell_cover[k], 4);
-      if (cells[kSunCellWords * k + 1] != hc) out[5]++;  // cover depth: bit for bit
-      if (d1 - d0 != h1 - h0 || d0 != h0) {
-         out[3]++;  // another list length (or offset)
-         continue;
-      }
-      const uint32_t ix = (uint32_t)(k % prm.nx), iy = (uint32_t)(k / prm.nx), len = d1 - d0;
-      const bool walkable = !(ix == 0 || iy == 0 || ix == prm.nx - 1 || iy == prm.ny - 1) && len <= lim.max_walk;
-      bool same = true;
-      if (walkable) {
-         out[6]++;
-         for (uint32_t e = 0; e < len && same; e++) same = entries[d0 + e].packet == h.entries[h0 + e].packet && std::memcmp(&entries[d0 + e].wmax, &h.entries[h0 + e].wmax, 4) == 0;
-      } else {
-         // lists no ray walks are left in arrival order on the device: the same packets, as a set
-         a.clear();
-         b.clear();
-         for (uint32_t e = 0; e < len; e++) {
-            a.push_back(entries[d0 + e].packet);
-            b.push_back(h.entries[h0 + e].packet);
-         }
-         std::sort(a.begin(), a.end());
-         std::sort(b.begin(), b.end());
-         same = a == b;
-      }
-      if (!same) out[4]++;
-   }
-   out[7] = (uint64_t)(h.build_ms * 1000.0);  // the host builder's time on this box, microseconds
-   return UH_OK;
 }
 
 int uh_tile_pack_count(uh_ctx* c, uint32_t rank, uint64_t* out_pixels) {

@@ -1,7 +1,7 @@
 // context_state.h - struct uh_ctx and the types it is made of, for the files that implement the context: context.hip (lifetime,
 // the path tracer, the multi-GPU composition), scene_build.hip (meshes, builders, refit) and the graphs (raster_driver.hip,
 // hybrid_graph.hip, forward_graph.hip, denoise_graph.hip; what they share: graphs_internal.h). Private: not installed, not part of
-// the C ABI (include/utopian_hip.h), where uh_ctx stays opaque.
+// the C ABI (include/utopian_hip.h), where uh_ctx stays opaque. The upkeep of the sun and camera grids is grid_cache.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +12,7 @@
 #include "bvh.h"
 #include "context_internal.h"
 #include "device_types.h"
+#include "grid_cache.h"
 #include "utopian_hip.h"
 
 using namespace uh;  // (the including files are written inside it)
@@ -71,6 +72,12 @@ struct DevBuf {
       p = nullptr;
       base = nullptr;
       n = 0;
+   }
+   // a hipMalloc'ed array of `count` elements changes owner: what this buffer held is freed, `ptr` is cleared
+   void take(T*& ptr, size_t count) {
+      release();
+      p = ptr, base = ptr, n = count;
+      ptr = nullptr;
    }
 };
 // for a group's visitor (f(buffer, length)): frees every buffer it names (hidden, like every destroy() below: the library's dynamic
@@ -238,6 +245,44 @@ struct Slot {
    }
 };
 
+// A visibility grid the context keeps (sun_grid.h): the sun grid of one (geometry, direction), the camera grid of one (geometry,
+// camera). `cache` says which pair that is and when another one is built (grid_cache.h); the rest is the last build's outcome.
+template <int N>
+struct __attribute__((visibility("hidden"))) CachedGrid {
+   GridCache<N> cache;
+   bool valid = false;              // d_cells / d_entries / dev hold a usable grid for (cache.geom, cache.key); false: refused, see why
+   bool this_frame = false;         // the frame call being enqueued uses it (set by ensure_*_grid, read by the stats)
+   DevBuf<uint32_t> d_cells;
+   DevBuf<SunGridEntry> d_entries;
+   SunGridDev dev{};
+   SunGridLimits limits;
+   std::string why;
+   float build_ms = 0.0f, mean_list = 0.0f;
+   uint32_t cells = 0, entries = 0, max_list_interior = 0;  // cells: as the stats report them
+
+   bool holds(uint64_t geom, const float* key) const { return valid && cache.matches(geom, key); }
+   size_t bytes() const { return d_cells.n * sizeof(uint32_t) + d_entries.n * sizeof(SunGridEntry); }
+   void release() { d_cells.release(), d_entries.release(); }
+   // a builder's result, or its refusal (!ok), becomes the grid for (geom, key): its two allocations change owner, the old ones are
+   // freed - the caller has waited for the frames that may read them. cell_words: words per cell record. (grid_cache.hip)
+   void adopt(SunGridDevice& g, bool ok, uint64_t geom, const float* key, uint32_t cell_words);
+};
+
+// what only the sun grid has: its lists a second time as 64-byte records that carry their packet (SunGridDev::recs), the coarse
+// cover (SunGridDev::coarse), both made by attach_sun_inline_records behind every adoption, and the options of its build and use
+struct SunGridExtras {
+   DevBuf<float4> d_recs;
+   DevBuf<float> d_coarse;
+   uint32_t coarse_shift = 2;       // option "sun_grid_coarse": blocks of 4 x 4 cells; 0: no coarse cover
+   // the records only while they stay within four times the packet array (a grid of 96 entries per triangle repeats every packet 96
+   // times: 1.4 GB for the 17 MB of the config-1 scene); option "sun_grid_inline_max_mb" raises the budget (0: never)
+   int64_t inline_max_mb = -1;      // -1: auto = 4 x the packet array
+   bool device_build = true;        // option "sun_grid_build": 1 = on the device (sun_grid_build.hip: a few ms), 0 = the host builder (sun_grid.cpp)
+   bool verdicts = true;            // option "sun_verdicts" (FrameParams::sun_verdicts)
+   size_t bytes() const { return d_recs.n * sizeof(float4) + d_coarse.n * sizeof(float); }
+   void release() { d_recs.release(), d_coarse.release(); }
+};
+
 // frames of the reservoir passes one uh_render_frames wavefront carries at most, and the ring of spatial buffers that
 // lets the next batch's chains run beside the current wavefront (two batches + the history slot)
 constexpr uint32_t kRestirBatch = 16;
@@ -369,52 +414,18 @@ struct uh_ctx {
    std::vector<EventPair> pending, free_events;
    uint32_t bvh_nodes = 0, bvh_tris = 0;
 
-   // sun shadow rays through a per-direction grid instead of the tree (sun_grid.h; option "sun_grid"). The grid belongs to one
-   // (geometry, sun direction) pair: it is built on the first frame that traces sun rays and again when the direction or the
-   // geometry has changed and then stayed put for two consecutive frames - a sun or an instance that moves every frame keeps
-   // the tree walk.
+   // sun shadow rays through a per-direction grid instead of the tree (sun_grid.h; option "sun_grid"), built on the first frame that
+   // traces sun rays and again once a new direction or geometry has stayed put for two frames (grid_cache.h; grid_cache.hip ensure_sun_grid)
    bool sun_grid_enabled = true;
-   bool sun_verdicts = true;        // option "sun_verdicts" (FrameParams::sun_verdicts)
-   bool sun_valid = false;          // d_sun_* hold a usable grid for (sun_geom, sun_dir_built)
-   bool sun_attempted = false;      // a build for (sun_geom, sun_dir_built) was tried (it may have been refused: sun_why)
-   bool sun_have_pending = false;
-   uint64_t geom_version = 1, sun_geom = 0, sun_geom_pending = 0;
-   float sun_dir_built[3] = {0, 0, 0}, sun_dir_pending[3] = {0, 0, 0};
-   DevBuf<uint32_t> d_sun_cells;
-   DevBuf<SunGridEntry> d_sun_entries;
-   DevBuf<float4> d_sun_recs;       // the entries with their packets inline (SunGridDev::recs; option "sun_grid_inline")
-   DevBuf<float> d_sun_coarse;      // the coarse cover (SunGridDev::coarse; option "sun_grid_coarse")
-   uint32_t sun_coarse_shift = 2;   // blocks of 4 x 4 cells; 0: no coarse cover
-   // the lists a second time as 64-byte records that carry their packet (SunGridDev::recs): by default only while they stay within
-   // four times the packet array (a grid of 96 entries per triangle repeats every packet 96 times: 1.4 GB for the 17 MB of the
-   // config-1 scene); option "sun_grid_inline_max_mb" raises the budget (0: never)
-   int64_t sun_inline_max_mb = -1;  // -1: auto = 4 x the packet array
-   SunGridDev sun_dev{};
-   SunGridLimits sun_limits;
-   std::string sun_why;
-   float sun_build_ms = 0.0f, sun_mean_list = 0.0f;
-   float sun_fallback_area = 1.0f;  // share of the scene's surface whose cell hands its sun rays to the tree (the builders' figure)
-   uint32_t sun_cells = 0, sun_entries = 0, sun_max_list = 0;
-   bool sun_this_frame = false;     // set by render_batch for the frame being enqueued
+   uint64_t geom_version = 1;
+   CachedGrid<3> sun;               // key: the frame's sun direction
+   SunGridExtras sun_x;
    bool primary_implicit = true;    // option "primary_implicit" (FrameParams::primary_implicit)
-   bool sun_device_build = true;    // option "sun_grid_build": 1 = on the device (sun_grid_build.hip: a few ms), 0 = the host builder (sun_grid.cpp)
 
-   // the primary rays through a per-camera grid instead of the tree (sun_grid.h "camera grid"; option "camera_grid"). The grid belongs
-   // to one (geometry, inverse_view, inverse_projection, frame size): it is built - on the device, a few milliseconds - when the
-   // same camera has been asked for in two consecutive frame calls, or at once by a call that carries several frames of it; a
-   // camera that moves every frame keeps the tree walk.
+   // the primary rays through a per-camera grid instead of the tree (sun_grid.h "camera grid"; option "camera_grid"), built once the same
+   // camera has been asked for in two consecutive frame calls, or at once by a call that carries 8 frames of it (grid_cache.hip ensure_camera_grid)
    bool cam_grid_enabled = true;
-   bool cam_valid = false, cam_attempted = false, cam_have_pending = false;
-   uint64_t cam_geom = 0, cam_geom_pending = 0;
-   float cam_mats[32] = {0}, cam_mats_pending[32] = {0};  // inverse_view, inverse_projection of the grid / of the last request
-   DevBuf<uint32_t> d_cam_cells;
-   DevBuf<SunGridEntry> d_cam_entries;
-   SunGridDev cam_dev{};
-   SunGridLimits cam_limits;
-   std::string cam_why;
-   float cam_build_ms = 0.0f, cam_mean_list = 0.0f;
-   uint32_t cam_cells = 0, cam_entries = 0, cam_max_list = 0, cam_max_list_interior = 0;
-   bool cam_this_frame = false;
+   CachedGrid<32> cam;              // key: inverse_view, inverse_projection
 
    // tile partition
    uint32_t tp_rank = 0, tp_world = 1, tp_tile = 64;
@@ -660,6 +671,11 @@ LaunchCfg cfg(uh_ctx* c);
 FrameParams make_params(uh_ctx* c, const UhViewUniformData& v);
 int sync_all(uh_ctx* c);
 int read_back(uh_ctx* c, void* dst, const void* src, size_t bytes);
+// ---- grid_cache.hip, for context.hip ----
+// the sun grid for this frame's direction / the camera grid for this call's camera, if there is (or now should be) one: this_frame
+int ensure_sun_grid(uh_ctx* c, const float dir[3]);
+int ensure_camera_grid(uh_ctx* c, const FrameParams& fp, uint32_t batch);
+void grid_stats(const uh_ctx* c, UhStats* out);  // the sun_grid_* and camera_grid_* figures
 // ---- scene_build.hip, for hybrid_graph.hip ----
 // brackets of UhIsosurfaceUpdateStats::scatter_ms on the context's stream (the mesh tables of device-resident meshes count into it)
 void iso_scatter_begin(uh_ctx* c);

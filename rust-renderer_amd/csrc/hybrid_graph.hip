@@ -620,8 +620,7 @@ static int gbuffer_pass(uh_ctx* c, const HybridCall& k) {
    float mats[32];
    std::memcpy(mats, k.fp.inv_view, sizeof(float) * 16);
    std::memcpy(mats + 16, k.fp.inv_proj, sizeof(float) * 16);
-   const bool use_grid = c->cam_grid_enabled && c->cam_valid && c->cam_geom == c->geom_version && std::memcmp(mats, c->cam_mats, sizeof(mats)) == 0;
-   const SunGridDev* grid = use_grid ? &c->cam_dev : nullptr;
+   const SunGridDev* grid = c->cam_grid_enabled && c->cam.holds(c->geom_version, mats) ? &c->cam.dev : nullptr;
    const int st = timed(c, h.stage[kStGbuffer], [&]() -> int {
       if (raster) return render_gbuffer_raster(c, k.lc, k.view, k.hd, motion ? &md : nullptr);
       if (!motion) {

@@ -43,6 +43,23 @@ def test_sun_grid_builder_under_asan_ubsan_never_hides_an_occluder(tmp_path):
     assert "SUN GRID CHECK OK" in r.stdout and "MISMATCH" not in r.stdout
 
 
+def test_grid_rebuild_policy_under_asan_ubsan(tmp_path):
+    """csrc/grid_cache.h (product code: when the sun and the camera grid are reused, waited for or rebuilt) under ASan + UBSan: the
+    request sequences the GPU tests see through UhStats - directions A A B C B B B A A, geometry that moves every frame, a camera that
+    moves, rests and meets new geometry - and what differs between the two grids: the first build, the batch of 8 frames, the pending
+    pair, invalidation, -0.0 against 0.0 and a refusal that is kept (tests/cpp/grid_cache_check.cpp)."""
+    exe = str(tmp_path / "grid_cache_check")
+    csrc = os.path.join(ROOT, "rust-renderer_amd", "csrc")
+    subprocess.run(
+        ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-Wall", "-Wextra", "-I", csrc,
+         os.path.join(ROOT, "tests", "cpp", "grid_cache_check.cpp"), "-o", exe],
+        check=True,
+    )
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert "GRID CACHE CHECK OK" in r.stdout and "FAIL" not in r.stdout
+
+
 def test_camera_grid_builder_under_asan_ubsan_against_brute_force(tmp_path):
     """csrc/camera_grid.h (product code: the host + device functions the camera grid's kernels run per packet and per cell) under
     ASan + UBSan: for twelve cameras - inside, above, two centimetres above a floor, IN its plane, far outside, narrow and wide fields
