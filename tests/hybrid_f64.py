@@ -1,5 +1,6 @@
 """A float64 reading of the hybrid frame's SSAO, deferred and present passes, written from the shaders and not from the float32
-restatements: deferred.frag:43-118, pbr_lighting.glsl:20-108 (surfaceShading, imageBasedLighting), brdf.glsl:1-36 and 82-90, ssao.frag:
+restatements: deferred.frag:43-118, pbr_lighting.glsl:20-108 (surfaceShading, imageBasedLighting), brdf.glsl:1-36 and 82-90,
+shadow_mapping.glsl:8-54 (calculateShadow), the reservoir light's term of DESIGN.md section 2 "Reservoir lights", ssao.frag:
 66-118, present.frag:23-39 with view.glsl:53-66 (linearToSrgb), and the samplers they read through (texture.rs: LINEAR +
 MIRRORED_REPEAT; the IBL cubes with the Vulkan face table and seamless edges of DESIGN.md section 2). Only the inputs are shared with
 tests/hybrid_frame_reference.py and tests/ibl_reference.py (the recorded meshes and the read-back maps); no arithmetic is.
@@ -193,10 +194,14 @@ def image_based_lighting(maps, P, base, N, metallic, roughness, occlusion, eye):
         return (kD * irradiance * base + spec) * occlusion[:, None]
 
 
-def deferred(g, shadows, reflections, ssao_img, view, meshes, lights, maps=None):
+def deferred(g, shadows, reflections, ssao_img, view, meshes, lights, maps=None, shadow=None, res=None, vis=None):
     """deferred.frag in float64 on the pass's own inputs (G-buffer dict of position / normal / albedo / pbr, the rt_shadows, rt_reflections
-    and SSAO images, the view, the recorded meshes, the GpuLight records; the IBL maps when view.ibl_enabled). Returns (color, scale,
-    sens, kappa): color (H, W, 3), the per-channel magnitude scales (H, W, 3) and the condition estimate (H, W)"""
+    and SSAO images, the view, the recorded meshes, the GpuLight records; the IBL maps when view.ibl_enabled). shadow = (params, maps):
+    calculateShadow's factor in place of the rt_shadows factor (shadows_enabled = 1). res, vis (the spatial reservoirs and the
+    light-visibility image, UH_HYBRID_RESTIR_LIGHTS): the loop runs over the sun alone, and a pixel whose visibility texel is 255 adds the
+    term of light res.Y times res.W_X. Returns (color, scale, sens, kappa): color (H, W, 3), the per-channel magnitude scales (H, W, 3)
+    and the condition estimate (H, W). With `shadow` the factor is an interval (shadow_interval), and color, scale and sens have a
+    leading axis of 2: the values at the factor's lower and upper end"""
     H, W = g["position"].shape[:2]
     n = H * W
     P = g["position"][..., :3].reshape(-1, 3).astype(D)
@@ -208,9 +213,10 @@ def deferred(g, shadows, reflections, ssao_img, view, meshes, lights, maps=None)
     base = diffuse * bc
     eye = np.array(view.eye_pos[:], D)
     srcs = [(0.0, np.zeros(3), np.ones(3), 0.0, np.ones(3), np.array(view.sun_dir[:], D) * (-1, 1, -1))]  # frag:74
-    for l in list(lights)[: view.num_lights]:
-        srcs.append((D(l.light_type), np.array(l.position[:], D), np.array(l.color[:3], D), D(l.spot), np.array(l.attenuation[:], D),
-                     np.array(l.direction[:], D)))
+    table = [(D(l.light_type), np.array(l.position[:], D), np.array(l.color[:3], D), D(l.spot), np.array(l.attenuation[:], D), np.array(l.direction[:], D))
+             for l in list(lights)[: view.num_lights]]
+    if res is None:
+        srcs += table
     with np.errstate(all="ignore"):
         V = normalize(eye[None, :] - P)                                   # lighting:26
         F0 = c(0.04) * (1 - metallic)[:, None] + base * metallic[:, None]
@@ -219,7 +225,9 @@ def deferred(g, shadows, reflections, ssao_img, view, meshes, lights, maps=None)
         k = (roughness + 1.0) ** 2 / 8.0                                  # brdf:19-20
         ggx = lambda x: x / (x * (1.0 - k) + k)
         Lo, scale, sens = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 3))
-        for typ_l, pos, color, spot, att, ldir in srcs:
+
+        def one_light(typ_l, pos, color, spot, att, ldir):
+            """(lo, sens) of one light at every pixel: its contribution to Lo and how far that moves with its five dot products"""
             cos_s, spot_l, den = np.ones(n), 0.0, np.ones(n)
             if typ_l == 0.0:                                              # lighting:36-40
                 L = np.broadcast_to(normalize((ldir * (-1, 1, -1))[None, :]), (n, 3))
@@ -248,11 +256,24 @@ def deferred(g, shadows, reflections, ssao_img, view, meshes, lights, maps=None)
                 return (kD * base / PI + spec) * radiance * NdotL[:, None]  # lighting:76
 
             lo = contribution(**x)
-            Lo, scale = Lo + lo, scale + np.abs(lo)
+            moves = np.zeros((n, 3))
             for key in x:
                 for sign in (-1.0, 1.0):
                     moved = dict(x, **{key: x[key] + sign * DOT_ULPS * ULP})
-                    sens = sens + np.abs(np.nan_to_num(contribution(**moved) - lo, nan=0.0)) * 0.5
+                    moves = moves + np.abs(np.nan_to_num(contribution(**moved) - lo, nan=0.0)) * 0.5
+            return lo, moves
+
+        for src in srcs:
+            lo, moves = one_light(*src)
+            Lo, scale, sens = Lo + lo, scale + np.abs(lo), sens + moves
+        if res is not None:  # DESIGN.md section 2 "Reservoir lights": Lo += term(light Y) * W_X where the ray arrived
+            Y, WX = res["Y"].reshape(-1), res["W_X"].reshape(-1).astype(D)
+            arrived = vis.reshape(-1) == 255
+            for j in np.unique(Y[arrived]):
+                lo, moves = one_light(*table[int(j)])
+                rows = (arrived & (Y == j))[:, None]
+                lo, moves = np.where(rows, lo * WX[:, None], 0.0), np.where(rows, moves * WX[:, None], 0.0)
+                Lo, scale, sens = Lo + lo, scale + np.abs(lo), sens + moves
         if view.ibl_enabled == 1:
             ambient = image_based_lighting(maps, P, base, N, metallic, roughness, occlusion, eye)
         else:
@@ -264,13 +285,18 @@ def deferred(g, shadows, reflections, ssao_img, view, meshes, lights, maps=None)
             refl = reflections.reshape(-1, 4)[:, :3].astype(D) / 255.0
             color = np.where(metal, color * 0.0 + refl, color)
             scale, sens = np.where(metal, refl, scale), np.where(metal, 0.0, sens)
+        if shadow is not None:                                            # frag:98-106: calculateShadow, not rt_shadows
+            s = np.stack(shadow_interval(P, view, *shadow)[:2])[:, :, None]  # (2, n, 1)
+            color, scale, sens = color[None] * s, scale[None] * s, sens[None] * s
+        elif view.raytracing_supported == 1:
             s = np.maximum(shadows.reshape(-1).astype(D) / 255.0, c(0.3))[:, None]
             color, scale, sens = color * s, scale * s, sens * s
         if view.ssao_enabled == 1:                                        # frag:55, 113-115: in_ssao at the unflipped in_uv
             s = (ssao_img[::-1].reshape(-1).astype(D) / 65535.0)[:, None]
             color, scale, sens = color * s, scale * s, sens * s
-        kappa = np.nan_to_num(np.max(sens / (ULP * scale), axis=1), nan=0.0, posinf=np.inf)
-    return color.reshape(H, W, 3), scale.reshape(H, W, 3), sens.reshape(H, W, 3), kappa.reshape(H, W)
+        kappa = np.nan_to_num(np.max((sens / (ULP * scale)).reshape(-1, n, 3)[-1], axis=1), nan=0.0, posinf=np.inf)  # (a factor cancels)
+    shape = color.shape[:-2] + (H, W, 3)
+    return color.reshape(shape), scale.reshape(shape), sens.reshape(shape), kappa.reshape(H, W)
 
 
 def deferred_bound(scale, sens, kappa):
@@ -284,6 +310,99 @@ def worst_ratio(err, bound):
     with np.errstate(divide="ignore", invalid="ignore"):
         r = np.where(err > 0, err / bound, 0.0)
     return float(r.max()) if r.size else 0.0
+
+
+def interval_error(got, color, scale, sens, kappa):
+    """(err, bound) of device values `got` (H, W, 3) against the reading: |got - color| and deferred_bound, or with a factor interval
+    (a leading axis of 2 on color, scale and sens) the distance below the lower end against the bound there, or above the upper end
+    against the bound there; inside the interval the error is 0"""
+    if color.ndim == 3:
+        return np.abs(got - color), deferred_bound(scale, sens, kappa)
+    b = deferred_bound(scale, sens, kappa)
+    below, above = color[0] - got, got - color[1]
+    return np.where(below > 0, below, np.where(above > 0, above, 0.0)), np.where(below > 0, b[0], b[1])
+
+
+# ---- shadow_mapping.glsl: calculateShadow ----------------------------------------------------------------------------------------
+# The factor is a step function of three comparisons, so it is read as an interval [lo, hi] (as ssao() reads its depth comparisons): a
+# comparison whose two sides lie within the float32 pass's own rounding of each other may go either way. The roundings are counted,
+# not fitted; u = 2^-24 is the relative error of one float32 operation.
+# * A row of a 4 x 4 matrix times (P, 1), ((m0 x + m1 y) + m2 z) + m3: three products and three sums (m3 * 1 is exact), each within
+#   u of an intermediate no larger than A = |m0 x| + |m1 y| + |m2 z| + |m3|: SHADOW_ROW_ROUNDINGS u A absolute. This is the whole
+#   error of viewPosition.z against the cascade splits (which are read exactly).
+# * projCoordinate = lightSpacePosition / w: one more rounding of the quotient (w is 1, but the operation is counted).
+# * The depth side: z - bias, one rounding. So testDepth errs by at most 6 u A_z + u |z| + u |z - bias|; the same without the last
+#   term for z against the (-1, 1] ends.
+# * The uv scale: xy * 0.5 + 0.5 (the product is exact, the sum rounds), and for v the flip 1 - v; then (uv + offset) * S - 0.5 with
+#   1 / S rounded: a sum, a product and a sum. In texels, with |uv| <= 2 wherever a texel is read:
+#   S (0.5 (6 u A_xy + u |p|) + u |uv| + u |uv| (flip) + u / S + u |uv + offset|) + u |t + 0.5| + u |t|
+#   <= S (3 u A_xy + SHADOW_UV_ROUNDINGS u max(|uv|, |p|, 1)) + 2 u (|t| + 1).
+# * The blend of four depths in [0, 1]: 1 - a, two products and a sum per axis, twice: SHADOW_BLEND_ROUNDINGS u of a value <= 1.
+#   The blend is continuous in the texel coordinate, so the coordinate's error moves it by what the blend itself changes over a box of
+#   that half-width: evaluated at the box's corners.
+SHADOW_ROW_ROUNDINGS = 6
+SHADOW_UV_ROUNDINGS = 5
+SHADOW_BLEND_ROUNDINGS = 8
+
+
+def _row(m, r, P):
+    """row r of the column-major float32 matrix m (16,) times (P, 1): the value and A, the sum of the terms' magnitudes"""
+    terms = np.stack([D(m[r]) * P[:, 0], D(m[4 + r]) * P[:, 1], D(m[8 + r]) * P[:, 2], np.full(len(P), D(m[12 + r]))])
+    return terms.sum(axis=0), np.abs(terms).sum(axis=0)
+
+
+def _depth_bilinear(layer, x, y):
+    return bilinear(layer[..., None], x, y)[:, 0]
+
+
+def _cascade_interval(P, vp, layer):
+    """the factor's interval for positions P (n, 3) in one cascade: vp (16,) float32, layer (S, S) float32"""
+    S = layer.shape[0]
+    (lx, ax), (ly, ay), (lz, az), (lw, _) = (_row(vp, r, P) for r in range(4))
+    px, py, pz = lx / lw, ly / lw, lz / lw                                # shadow_mapping.glsl:19-20
+    u, v = px * 0.5 + 0.5, 1.0 - (py * 0.5 + 0.5)                         # :21-22
+    e_z = SHADOW_ROW_ROUNDINGS * ULP * az + ULP * np.abs(pz)
+    e_test = e_z + ULP * np.abs(pz - c(0.0005))
+    texel = 1.0 / S                                                       # :25
+    lo, hi = np.zeros(len(P)), np.zeros(len(P))
+    surely_in = (pz + e_z <= 1.0) & (pz - e_z > -1.0)                     # :33
+    maybe_in = (pz - e_z <= 1.0) & (pz + e_z > -1.0)
+    for ox in (-1, 0, 1):
+        for oy in (-1, 0, 1):
+            uu, vv = u + ox * texel, v + oy * texel                       # :35-36
+            tx, ty = uu * S - 0.5, vv * S - 0.5
+            dx = S * (3 * ULP * ax + SHADOW_UV_ROUNDINGS * ULP * np.maximum(np.maximum(np.abs(uu), np.abs(px)), 1.0)) + 2 * ULP * (np.abs(tx) + 1.0)
+            dy = S * (3 * ULP * ay + SHADOW_UV_ROUNDINGS * ULP * np.maximum(np.maximum(np.abs(vv), np.abs(py)), 1.0)) + 2 * ULP * (np.abs(ty) + 1.0)
+            depths = [_depth_bilinear(layer, tx + sx * dx, ty + sy * dy) for sx in (-1, 1) for sy in (-1, 1)] + [_depth_bilinear(layer, tx, ty)]
+            dmin = np.min(depths, axis=0) - SHADOW_BLEND_ROUNDINGS * ULP
+            dmax = np.max(depths, axis=0) + SHADOW_BLEND_ROUNDINGS * ULP
+            test = pz - c(0.0005)                                         # :37-39
+            shadowed, lit = test - e_test > dmax, test + e_test < dmin    # :40: testDepth > closestDepth
+            t_lo = np.where(lit, 1.0, c(0.3))
+            t_hi = np.where(shadowed, c(0.3), 1.0)
+            lo = lo + np.where(maybe_in, t_lo, 1.0)                       # :44: outside the frustum's depth no shadowing
+            hi = hi + np.where(surely_in, t_hi, 1.0)
+    return lo / 9.0, hi / 9.0                                             # :51
+
+
+def shadow_interval(P, view, params, maps):
+    """calculateShadow in float64 for world positions P (n, 3): (lo, hi, cascade_lo, cascade_hi). [lo, hi] holds the float32 pass's
+    factor; a view depth within its rounding of a split takes the union over both cascades (cascade_lo .. cascade_hi)"""
+    P = np.asarray(P, D)
+    splits = np.array(params.cascade_splits[:], D)
+    vps = [np.array(list(params.view_projection_matrices[k]), F) for k in range(4)]
+    with np.errstate(all="ignore"):
+        vz, a = _row(np.array(view.view[:], F), 2, P)                     # :11
+        e = SHADOW_ROW_ROUNDINGS * ULP * a
+        c_lo = sum((vz + e < -splits[i]).astype(np.int64) for i in range(3))  # :13-17: the splits ascend, so the last i that holds is the count
+        c_hi = sum((vz - e < -splits[i]).astype(np.int64) for i in range(3))
+        lo, hi = np.full(len(P), np.inf), np.full(len(P), -np.inf)
+        for k in range(4):
+            rows = np.nonzero((c_lo <= k) & (k <= c_hi))[0]
+            if len(rows):
+                l, h = _cascade_interval(P[rows], vps[k], maps[k])
+                lo[rows], hi[rows] = np.minimum(lo[rows], l), np.maximum(hi[rows], h)
+    return lo, hi, c_lo, c_hi
 
 
 # ---- ssao.frag -----------------------------------------------------------------------------------------------------------------

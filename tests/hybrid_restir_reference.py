@@ -44,7 +44,8 @@ def surface_terms(g, view, meshes):
         r1 = roughness + F(1.0)
         k = (r1 * r1) / F(8.0)
         omk = F(1.0) - k
-    return dict(n=n, shape=(H, W), P=P, N=N, V=V, base=base, diffuse=diffuse, occlusion=occlusion, type=typ, om=om, F0=F0, a2=a2, a2m1=a2 - F(1.0),
+    return dict(n=n, shape=(H, W), P=P, N=N, V=V, base=base, diffuse=diffuse, occlusion=occlusion, metallic=metallic, roughness=roughness,
+                type=typ, om=om, F0=F0, a2=a2, a2m1=a2 - F(1.0),
                 k=k, omk=omk, ggxV=NdotV / (NdotV * omk + k), nv4=F(4.0) * NdotV, geometry=g["position"].reshape(-1, 4)[:, 3] != 0)
 
 

@@ -129,12 +129,13 @@ def resolve_seeded(recs, seed, W, H):
 
 
 # ---- the pass -------------------------------------------------------------------------------------------------------------------
-def marching_cubes_pass(mesh, textures, view, lights, position, deferred, shadow=None):
+def marching_cubes_pass(mesh, textures, view, lights, position, deferred, shadow=None, seed=None):
     """the pass on a frame: mesh from pass_mesh, position the G-buffer's (H, W, 4), deferred the deferred_output it draws into ->
-    dict(output (H, W, 4), depth, visibility, records, seed); shadow = (params, maps) when view.shadows_enabled == 1"""
+    dict(output (H, W, 4), depth, visibility, records, seed); shadow = (params, maps) when view.shadows_enabled == 1; seed: the depth
+    buffer the pass tests against when the G-buffer was rasterised (its own depth), else the one made from `position`"""
     H, W = position.shape[:2]
     recs = fw.records_for([mesh], view, W, H)
-    seed = depth_seed(position, view)
+    seed = depth_seed(position, view) if seed is None else np.asarray(seed, F)
     depth, vis, rec = resolve_seeded(recs, seed, W, H)
     out = np.array(deferred, F).reshape(W * H, 4)
     pix, _, P, N, uu, vv = fw.surface([mesh], textures, recs, rec, W, H)

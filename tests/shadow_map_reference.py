@@ -4,6 +4,8 @@ numpy, in the order DESIGN.md section 2 "Shadow maps" pins: setup_shadow_pass in
 conftest: test modules import it."""
 import numpy as np
 
+import hybrid_frame_reference as fr
+
 F = np.float32
 GUARD = F(524288.0)
 ONE_BITS = np.uint32(0x3F800000)
@@ -356,3 +358,22 @@ def calculate_shadow(P, view, params, maps):
                 tap = np.where((pz - F(0.0005)) > d, F(0.3), F(1.0))
                 shadow = shadow + np.where(inside, tap, F(1.0))
         return (shadow / F(9.0)).astype(F), c
+
+
+# ---- the deferred pass with shadows_enabled = 1 ---------------------------------------------------------------------------------------
+def deferred_with_shadow_maps(g, reflections, ssao_img, view, meshes, params, maps, lights=()):
+    """deferred.frag with shadows_enabled = 1 from hybrid_frame_reference.deferred: the rt_shadows branch neutralised (all 255
+    multiplies by exactly 1.0) and SSAO off, then calculateShadow's factor and the SSAO factor in the reference's order. Returns the
+    image (H, W, 4) and the cascade of every pixel (H, W)"""
+    H, W = g["position"].shape[:2]
+    v0 = type(view).from_buffer_copy(view)
+    v0.ssao_enabled = 0
+    ones = np.full((H, W), 255, np.uint8)
+    base = fr.deferred(g, ones, reflections, None, v0, meshes, list(lights)).reshape(-1, 4)
+    factor, cascade = calculate_shadow(g["position"][..., :3].reshape(-1, 3).astype(np.float32), view, params, maps)
+    color = base[:, :3] * factor[:, None]
+    if view.ssao_enabled == 1:
+        color = color * (ssao_img[::-1].reshape(-1).astype(np.float32) / F(65535.0))[:, None]
+    out = base.copy()
+    out[:, :3] = color
+    return out.reshape(H, W, 4), cascade.reshape(H, W)

@@ -10,12 +10,14 @@ import pytest
 
 import forward_reference as fw
 import gbuffer_raster_reference as gr
+import hybrid_compose_reference as cr
 import hybrid_frame_reference as fr
 import hybrid_reference as hr
+import ibl_reference as ir
 import marching_cubes_pass_reference as mr
 import oracle_api as oa
 import rust_renderer_amd as rr
-from hybrid_util import CPP_H, CPP_W, DEFERRED_ULP, ROOT, SyntheticScene, assert_reflections, assets, bits, cpp_scene, cpp_view, frame_view, gbuf, \
+from hybrid_util import CONSUMER_ULP, CPP_H, CPP_W, DEFERRED_ULP, ROOT, SyntheticScene, assert_reflections, assets, bits, cpp_scene, cpp_view, frame_view, gbuf, \
     scene_named, synthetic_scene, ulps, write_blob  # noqa: F401
 from rust_renderer_amd.api import UtopianError
 from test_gbuffer_raster_cpu import near_wall_scene
@@ -133,9 +135,9 @@ def test_floor_beyond_the_guard_band():
     assert len(ref["records"]) > 2 and (ref["visibility"] == 0).mean() > 0.3
 
 
-def _check_frame(gpu, meshes, view, mask, deferred=True):
-    """one call with `mask`, then hybrid_util.check_frame's assertions on the device's own raster G-buffer (the deferred pass only
-    without shadow maps and IBL, whose own suites cover those branches)"""
+def _check_frame(gpu, meshes, view, mask):
+    """one call with `mask`, then hybrid_util.check_frame's assertions on the device's own raster G-buffer; the deferred pass against
+    the composed restatement, with the device's IBL maps and shadow maps where the view switches them on"""
     gpu.render_hybrid(view, mask)
     g = gbuf(gpu)
     sh, refl = gpu.read_hybrid(rr.HYBRID_SHADOWS), gpu.read_hybrid(rr.HYBRID_REFLECTIONS)
@@ -143,9 +145,13 @@ def _check_frame(gpu, meshes, view, mask, deferred=True):
     assert np.array_equal(ss, fr.ssao(g["position"], g["normal"], view)), "ssao"
     geo = g["position"][..., 3] == 1.0
     assert geo.any() and np.isfinite(d[geo]).all()
-    if deferred:
-        ref = fr.deferred(g, sh, refl, ss, view, meshes, [])
-        assert ulps(d[geo], ref[geo]).max() <= DEFERRED_ULP, "deferred"
+    maps = ir.read_maps(gpu) if view.ibl_enabled == 1 else None
+    shadow = (gpu.shadow_map_stats().params, np.stack([gpu.read_shadow_map(c) for c in range(4)])) if view.shadows_enabled == 1 else None
+    ref = cr.deferred(g, sh, refl, ss, view, meshes, [], maps=maps, shadow=shadow)
+    assert ulps(d[geo], ref[geo]).max() <= (CONSUMER_ULP if maps else DEFERRED_ULP), "deferred"
+    if shadow:
+        factor = cr.shadow_factor(g, view, shadow)[0].reshape(geo.shape)[geo]
+        assert (factor < 1.0).any() and (factor == 1.0).any()
     sky = fr.sky(g["position"], view)
     if sky and not view.cubemap_enabled:
         ys, xs = np.array(list(sky)).T
@@ -156,7 +162,7 @@ def _check_frame(gpu, meshes, view, mask, deferred=True):
     assert all(ms > 0 for ms in s.pass_ms) and s.sky_pixels == len(sky) == int((~geo).sum())
 
 
-@pytest.mark.parametrize("shadows,ibl", [(0, 0), (1, 0), (0, 1)])
+@pytest.mark.parametrize("shadows,ibl", [(0, 0), (1, 0), (0, 1), (1, 1)])
 def test_whole_frame_on_the_raster_gbuffer(shadows, ibl):
     scene = synthetic_scene()
     gpu, meshes, textures, view = _setup(scene)
@@ -182,7 +188,7 @@ def test_whole_frame_on_the_raster_gbuffer(shadows, ibl):
         want, kind = hr.reflections(cpu, meshes, g["position"], g["normal"], g["pbr"], view)
         assert_reflections(gpu.read_hybrid(rr.HYBRID_REFLECTIONS), want, kind)
     gpu.render_hybrid(view, mask)  # the steady state: rt_shadows reads the previous (rasterised) G-buffer
-    _check_frame(gpu, meshes, view, mask, deferred=not (shadows or ibl))
+    _check_frame(gpu, meshes, view, mask)
     _check(gpu, meshes, textures, view)
 
 

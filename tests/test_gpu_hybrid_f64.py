@@ -1,5 +1,6 @@
 """GPU: the device's SSAO, deferred and present passes against the float64 reading of tests/hybrid_f64.py, on the device's own inputs
-(cornell, spheres and the synthetic scene; 1,024 lights on sampled rows at 1080p; IBL off and on), and a scene of value edges - constant
+(cornell, spheres and the synthetic scene; 1,024 lights on sampled rows at 1080p; IBL off and on; the deferred variants that combine IBL,
+shadow maps and reservoir lights at 97 x 61), and a scene of value edges - constant
 metallic / roughness / occlusion maps of 0 and 255, factors 0, 1 and 1.5, black and white albedo, normals facing away from the eye, a
 spot light of exponent 0 and a light behind the surface - against both the float32 restatements and the float64 reading."""
 import numpy as np
@@ -13,26 +14,38 @@ import rust_renderer_amd as rr
 from hybrid_util import (CONSUMER_ULP, DEFERRED_ULP, W, H, SyntheticScene, add_lights, assets, frame_view, gbuf, ibl_view, pair,  # noqa: F401
                          record, scene_named, ulps)
 from rust_renderer_amd.scenes import quad
+from test_gpu_deferred_variants import build_variants, front_lights
 
 pytestmark = pytest.mark.gpu
 
 
-def check_f64(gpu, view, meshes, lights, maps, name, rows=None):
+def check_f64(gpu, view, meshes, lights, maps, name, rows=None, shadow=None, res=None, vis=None):
     """the device's images of the last UH_HYBRID_FRAME call against the float64 reading (deferred on the geometry pixels, SSAO inside
-    its interval, present within 1 LSB with FXAA off); rows: only these rows (deferred / present) and SSAO texel rows"""
+    its interval, present within 1 LSB with FXAA off); rows: only these rows (deferred / present) and SSAO texel rows. shadow: the
+    device's (params, maps) - the factor is then an interval, at most a quarter of the geometry pixels may have more than one value in
+    it, and the others must be both lit and shadowed; res, vis: the spatial reservoirs and the light-visibility image of the call"""
     g, d = gbuf(gpu), gpu.read_hybrid(rr.HYBRID_DEFERRED_OUTPUT)
     sh, refl, ss = gpu.read_hybrid(rr.HYBRID_SHADOWS), gpu.read_hybrid(rr.HYBRID_REFLECTIONS), gpu.read_hybrid(rr.HYBRID_SSAO_IMAGE)
     Hh = g["position"].shape[0]
     sel = np.arange(Hh) if rows is None else np.asarray(rows)
     sub = {k: v[sel] for k, v in g.items()}
-    want, scale, sens, kappa = hf.deferred(sub, sh[sel], refl[sel], ss[::-1][sel][::-1], view, meshes, lights, maps)
+    want, scale, sens, kappa = hf.deferred(sub, sh[sel], refl[sel], ss[::-1][sel][::-1], view, meshes, lights, maps, shadow,
+                                           None if res is None else res[sel], None if vis is None else vis[sel])
     geo = sub["position"][..., 3] == 1.0
     got = d[sel][..., :3].astype(np.float64)
-    fin = np.isfinite(want) & geo[..., None]
+    fin = np.isfinite(want).reshape((-1,) + got.shape).all(axis=0) & geo[..., None]
     assert np.array_equal(np.isfinite(got) & geo[..., None], fin), f"{name}: non-finite pattern"
-    err = np.where(fin, np.abs(got - np.where(fin, want, 0.0)), 0.0)
-    bound = hf.deferred_bound(scale, sens, kappa)
+    err, bound = hf.interval_error(np.where(fin, got, 0.0), np.where(fin, want, 0.0), scale, sens, kappa)
+    err = np.where(fin, err, 0.0)
     ratio = hf.worst_ratio(err, bound)
+    ambiguous = 0.0
+    if shadow is not None:
+        lo, hi = hf.shadow_interval(sub["position"][..., :3].reshape(-1, 3), view, *shadow)[:2]
+        single, flat = lo == hi, geo.reshape(-1)
+        ambiguous = float(1.0 - single[flat].mean())
+        assert ambiguous <= 0.25, f"{name}: the shadow factor is an interval at {ambiguous:.3f} of the geometry pixels"
+        assert (single & flat & (hi == 1.0)).any() and (single & flat & (hi < 1.0)).any(), f"{name}: lit and shadowed single-valued pixels"
+    scale = scale.reshape((-1,) + got.shape)[-1]
     well = geo & (kappa <= hf.KAPPA_WELL)
     rel = lambda m: hf.worst_ratio(np.where(m[..., None], err, 0.0), scale) / hf.ULP
     peak = geo & (kappa > hf.KAPPA_WELL)
@@ -44,7 +57,7 @@ def check_f64(gpu, view, meshes, lights, maps, name, rows=None):
     _, p64 = hf.present(d)
     lsb = int(np.abs(gpu.read_hybrid(rr.HYBRID_PRESENT_OUTPUT)[sel].astype(int) - p64[sel].astype(int)).max())
     record("hybrid_frame", f"f64-{name}", deferred_worst_of_bound=round(ratio, 4), well_max_ulp_of_scale=round(rel(well), 2), peak_pixels=int(peak.sum()),
-           peak_max_ulp_of_scale=round(rel(peak), 2), ssao_outside=outside, ssao_median_width=float(np.median(hi - lo)), present_max_lsb=lsb)
+           peak_max_ulp_of_scale=round(rel(peak), 2), shadow_ambiguous_share=round(ambiguous, 4), ssao_outside=outside, ssao_median_width=float(np.median(hi - lo)), present_max_lsb=lsb)
     assert geo.any() and ratio <= 1.0, f"{name}: deferred error {ratio:.3g} x the bound"
     assert outside == 0, f"{name}: {outside} SSAO texels outside the interval"
     assert lsb <= 1, f"{name}: present {lsb} LSB"
@@ -65,6 +78,29 @@ def test_the_device_against_the_float64_reading(assets, name, ibl):
         maps = ir.read_maps(gpu)
     gpu.render_hybrid(v, rr.HYBRID_FRAME)
     check_f64(gpu, v, meshes, lights, maps, f"{name}-ibl{ibl}")
+
+
+@pytest.fixture(scope="module")
+def together():
+    """the second world of tests/test_gpu_deferred_variants.py: the tightened synthetic scene at 97 x 61, 8 lights on the camera's side
+    (the reservoir light's term shows on the matte meshes), three reservoir frames, shadow maps of size 256 and the IBL maps"""
+    return build_variants(front_lights())
+
+
+@pytest.mark.parametrize("ibl, shadows, restir", [(1, 1, 0), (0, 1, 1), (1, 1, 1)])
+def test_the_device_against_the_float64_reading_with_the_features_together(together, ibl, shadows, restir):
+    """k_hybrid_deferred<kIbl, kShadow, kRestir> for the triples that combine features, against the reading's calculateShadow interval
+    and reservoir term"""
+    w, gpu = together, together.gpu
+    v = w.view(ibl=ibl, shadows=shadows, fxaa_enabled=0)
+    gpu.render_hybrid(v, rr.HYBRID_GBUFFER)
+    gpu.render_hybrid(v, rr.HYBRID_FRAME | (rr.HYBRID_RESTIR_LIGHTS if restir else 0))
+    res, vis = (gpu.read_reservoirs(2), gpu.read_hybrid(rr.HYBRID_LIGHT_VISIBILITY)) if restir else (None, None)
+    if restir:
+        matte = np.array([m["type"] for m in w.meshes], np.float32)[gpu.read_hybrid(rr.HYBRID_PBR)[..., 3].astype(int) % len(w.meshes)] != 1.0
+        assert ((vis == 255) & matte).sum() >= 100, "the reservoir light's term shows"
+    check_f64(gpu, v, w.meshes, w.all_lights(), w.maps if ibl else None, f"synthetic-97x61-ibl{ibl}-shadow{shadows}-restir{restir}",
+              shadow=w.shadow if shadows else None, res=res, vis=vis)
 
 
 @pytest.mark.parametrize("ibl", [0, 1])

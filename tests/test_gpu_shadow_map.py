@@ -6,10 +6,12 @@ import copy
 import numpy as np
 import pytest
 
+import hybrid_compose_reference as cr
 import hybrid_frame_reference as fr
+import ibl_reference as ir
 import rust_renderer_amd as rr
 import shadow_map_reference as sr
-from hybrid_util import DEFERRED_ULP, W, H, assets, frame_view, gbuf, pair, read_all, scene_named, synthetic_scene, ulps
+from hybrid_util import CONSUMER_ULP, DEFERRED_ULP, W, H, assets, frame_view, gbuf, pair, read_all, scene_named, synthetic_scene, ulps
 from rust_renderer_amd.api import UtopianError
 from rust_renderer_amd.scenes import Scene, quad
 
@@ -132,19 +134,8 @@ def _deferred_restated(gpu, view, meshes, p, maps):
     """deferred.frag with shadows_enabled = 1 from the device's own inputs: the rt_shadows branch neutralised (all 255 multiplies by
     exactly 1.0) and SSAO off, then calculateShadow's factor and the SSAO factor in the reference's order"""
     g = gbuf(gpu)
-    v0 = copy.deepcopy(view)
-    v0.ssao_enabled = 0
-    ones = np.full((gpu.height, gpu.width), 255, np.uint8)
-    base = fr.deferred(g, ones, gpu.read_hybrid(rr.HYBRID_REFLECTIONS), None, v0, meshes, []).reshape(-1, 4)
-    P = g["position"][..., :3].reshape(-1, 3).astype(np.float32)
-    factor, cascade = sr.calculate_shadow(P, view, p, maps)
-    color = base[:, :3] * factor[:, None]
-    if view.ssao_enabled == 1:
-        ss = gpu.read_hybrid(rr.HYBRID_SSAO_IMAGE)
-        color = color * (ss[::-1].reshape(-1).astype(np.float32) / np.float32(65535.0))[:, None]
-    out = base.copy()
-    out[:, :3] = color
-    return out.reshape(gpu.height, gpu.width, 4), cascade.reshape(gpu.height, gpu.width), g
+    out, cascade = sr.deferred_with_shadow_maps(g, gpu.read_hybrid(rr.HYBRID_REFLECTIONS), gpu.read_hybrid(rr.HYBRID_SSAO_IMAGE), view, meshes, p, maps)
+    return out, cascade, g
 
 
 @pytest.mark.parametrize("ssao", [0, 1])
@@ -177,6 +168,16 @@ def test_reference_default_view_end_to_end():
     deferred = gpu.read_hybrid(rr.HYBRID_DEFERRED_OUTPUT)
     present = gpu.read_hybrid(rr.HYBRID_PRESENT_OUTPUT)
     assert np.isfinite(deferred).all()
+    # k_hybrid_deferred<1, 1, 0>: IBL ambient and calculateShadow together, on the device's own inputs
+    g = gbuf(gpu)
+    p, shadow_maps = gpu.shadow_map_stats().params, np.stack([gpu.read_shadow_map(c) for c in range(4)])
+    ref = cr.deferred(g, gpu.read_hybrid(rr.HYBRID_SHADOWS), gpu.read_hybrid(rr.HYBRID_REFLECTIONS), gpu.read_hybrid(rr.HYBRID_SSAO_IMAGE), v, meshes, [],
+                      maps=ir.read_maps(gpu), shadow=(p, shadow_maps))
+    geo = g["position"][..., 3] == 1.0
+    factor, cascade = cr.shadow_factor(g, v, (p, shadow_maps))
+    assert geo.any() and (factor[geo.reshape(-1)] < 1.0).any() and (factor[geo.reshape(-1)] == 1.0).any()
+    d = ulps(deferred[geo][:, :3], ref[geo][:, :3])
+    assert d.max() <= CONSUMER_ULP, d.max()
     assert np.array_equal(present, fr.present(deferred, v.fxaa_enabled == 1))
     s = gpu.hybrid_frame_stats()
     assert all(s.pass_ms[k] > 0.0 for k in range(7)) and gpu.shadow_map_stats().renders == 1

@@ -1,15 +1,20 @@
 """CPU: the float64 reading of tests/hybrid_f64.py against the float32 restatements of tests/hybrid_frame_reference.py and
 tests/ibl_reference.py, on synthetic G-buffers of random values and of the value edges (metallic and roughness 0 and 1, factors 0, 1
 and 1.5, occlusion 0, black and white albedo, normals facing away from the eye, lights behind the surface, a spot exponent of 0). The
-restatements are what the device is held to in ulp; this pins them to an evaluation written independently from the shaders."""
+restatements are what the device is held to in ulp; this pins them to an evaluation written independently from the shaders. The
+reading's calculateShadow interval and reservoir term are held to the composed restatement (tests/hybrid_compose_reference.py) on the
+oracle's G-buffer and reservoirs and the numpy shadow maps, where the interval's ambiguous share is established too."""
 import numpy as np
 import pytest
 
+import hybrid_compose_reference as cr
 import hybrid_f64 as hf
 import hybrid_frame_reference as fr
 import ibl_reference as ir
 import rust_renderer_amd as rr
-from hybrid_util import cast_planes, plane_view
+import shadow_map_reference as sr
+from hybrid_util import cast_planes, frame_view, plane_view
+from test_hybrid_compose_cpu import H as CH, W as CW, build_world
 
 F = np.float32
 W, H = 48, 36
@@ -191,3 +196,56 @@ def test_present_reading_is_within_one_lsb_of_the_restatement():
     _, want = hf.present(img)
     got = fr.present(img, fxaa_enabled=False)
     assert np.abs(got.astype(int) - want.astype(int)).max() <= 1
+
+
+# ---- calculateShadow and the reservoir term ----------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def world():
+    return build_world()
+
+
+def test_shadow_factor_interval_holds_the_restatement_and_is_mostly_single_valued(world):
+    """on the oracle's G-buffer of the tightened synthetic scene and the numpy shadow maps at 256: the float32 restatement's factor lies
+    inside the float64 interval at every pixel; at most a quarter of the geometry pixels have an interval that is not a single value,
+    and the single-valued ones are both fully lit and shadowed"""
+    g, (params, maps) = world["g"], world["shadow"]
+    v = frame_view(world["scene"], CW, CH)
+    P = g["position"][..., :3].reshape(-1, 3)
+    geo = (g["position"][..., 3] != 0).reshape(-1)
+    lo, hi, c_lo, c_hi = hf.shadow_interval(P, v, params, maps)
+    factor, cascade = sr.calculate_shadow(P.astype(F), v, params, maps)
+    slack = 16 * hf.ULP  # the float32 sum of nine taps and its division by 9
+    assert ((lo - slack <= factor) & (factor <= hi + slack))[geo].all(), np.count_nonzero(~((lo - slack <= factor) & (factor <= hi + slack))[geo])
+    assert ((c_lo <= cascade) & (cascade <= c_hi))[geo].all()
+    single = lo == hi
+    share = 1.0 - single[geo].mean()
+    print(f"ambiguous share {share:.4f} of {geo.sum()} geometry pixels; two cascades possible at {(c_lo != c_hi)[geo].sum()}")
+    assert share <= 0.25, share
+    assert (single & geo & (hi == 1.0)).any() and (single & geo & (hi < 1.0)).any()
+    assert set(np.unique(c_lo[geo])) == {0, 1, 2, 3}
+
+
+@pytest.mark.parametrize("rt", [1, 0])
+@pytest.mark.parametrize("ibl", [0, 1])
+def test_deferred_reading_with_shadow_maps_and_reservoirs_holds_the_composed_restatement(world, maps, ibl, rt):
+    """rt = 0: no reflection mix, so the reservoir light's term shows on the metal floor too, where nearly all arrived rays start (the
+    lights stand behind the occluders)"""
+    g, sh, refl, ss, meshes, lights = (world[k] for k in ("g", "sh", "refl", "ss", "meshes", "lights"))
+    geo = g["position"][..., 3] != 0
+    for kw in (dict(shadow=world["shadow"]), dict(res=world["res"], vis=world["vis"]), dict(shadow=world["shadow"], res=world["res"], vis=world["vis"])):
+        v = frame_view(world["scene"], CW, CH, raytracing_supported=rt)
+        v.num_lights, v.ibl_enabled, v.shadows_enabled = len(lights), ibl, int("shadow" in kw)
+        m = maps if ibl else None
+        want, scale, sens, kappa = hf.deferred(g, sh, refl, ss, v, meshes, lights, m, **kw)
+        got = cr.deferred(g, sh, refl, ss, v, meshes, lights, maps=m, **kw)[..., :3].astype(np.float64)
+        assert np.isfinite(got[geo]).all() and np.isfinite(want[..., geo, :]).all()
+        err, bound = hf.interval_error(got, want, scale, sens, kappa)
+        worst = hf.worst_ratio(err[geo], bound[geo])
+        assert worst <= 1.0, (ibl, rt, sorted(kw), worst)
+        if "res" in kw and rt == 0:  # the bound notices the term: on 20 pixels at least the sun-only frame lies a hundred bounds away
+            v0 = frame_view(world["scene"], CW, CH, raytracing_supported=rt)
+            v0.num_lights, v0.ibl_enabled, v0.shadows_enabled = 0, ibl, v.shadows_enabled
+            sun = cr.deferred(g, sh, refl, ss, v0, meshes, [], maps=m, **{k: x for k, x in kw.items() if k == "shadow"})[..., :3].astype(np.float64)
+            arrived = geo & (world["vis"] == 255)
+            e, b = hf.interval_error(sun, want, scale, sens, kappa)
+            assert (e[arrived].max(axis=-1) > 100.0 * b[arrived].max(axis=-1)).sum() >= 20
