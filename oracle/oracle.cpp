@@ -124,6 +124,14 @@ static inline V3 randomPointInUnitSphere(uint32_t& s) {
       if (dot(p, p) < 1.0f) return p;
    }
 }
+// random.glsl:48-58 - rejection sampling, 2 draws per trial (no pass of the reference calls it)
+static inline void randomPointInUnitDisk(uint32_t& s, float& x, float& y) {
+   for (;;) {
+      float a = randomFloat(s), b = randomFloat(s);
+      x = 2.0f * a - 1.0f, y = 2.0f * b - 1.0f;
+      if (x * x + y * y < 1.0f) return;
+   }
+}
 // reference.rgen:24 (and the three ReSTIR raygens): int(float(total_samples) + time * 10000.0)
 static inline uint32_t frameNumber(const UhViewUniformData& v) {
    float f = (float)v.total_samples + v.time * 10000.0f;
@@ -226,7 +234,7 @@ static inline V3 Absorb(V3 od) {
    return v3(std::exp(-a.x), std::exp(-a.y), std::exp(-a.z));
 }
 // atmosphere.glsl:154-214
-static inline V3 IntegrateScattering(V3 rayStart, V3 rayDir, float rayLength, V3 lightDir, V3 lightColor) {
+static inline V3 IntegrateScattering(V3 rayStart, V3 rayDir, float rayLength, V3 lightDir, V3 lightColor, V3* transmittance = nullptr) {
    float rayHeight = AtmosphereHeight(rayStart);
    float c = 1.0f - rayHeight / ATMOSPHERE_HEIGHT;
    c = std::fmin(std::fmax(c, 0.0f), 1.0f);
@@ -259,6 +267,7 @@ static inline V3 IntegrateScattering(V3 rayStart, V3 rayDir, float rayLength, V3
       mie = mie + viewTransmittance * lightTransmittance * phaseM * localDensity.y * stepSize;
       prevRayTime = rayTime;
    }
+   if (transmittance) *transmittance = Absorb(opticalDepth);  // atmosphere.glsl:209; the miss shader never reads it
    V3 color = (rayleigh * C_RAYLEIGH() + mie * C_MIE()) * lightColor * 20.0f;
    return color;
 }
@@ -1521,6 +1530,46 @@ void orc_closest_hit_shader(orc_ctx* c, uint32_t mesh, uint32_t prim, float t, f
    *seed = pl.seed;
    float r[11] = {pl.color.x, pl.color.y, pl.color.z, pl.distance, pl.scatter.x, pl.scatter.y, pl.scatter.z, pl.scattered, pl.normal.x, pl.normal.y, pl.normal.z};
    std::memcpy(out, r, sizeof(r));
+}
+
+// ---- the same, for tests/test_ref_shaders.py: every function of the reference's include files that the oracle restates, callable
+// on its own, so that each can be held to the reference's compiled text (oracle/ref_shaders)
+void orc_random_point_in_unit_disk(uint32_t* state, float out[2]) { randomPointInUnitDisk(*state, out[0], out[1]); }
+void orc_sample_light_uniform(uint32_t num_lights, uint32_t max_num_lights_used, uint32_t* state, int* index, float* weight) {
+   UhViewUniformData view;
+   std::memset(&view, 0, sizeof(view));
+   view.num_lights = num_lights;
+   view.max_num_lights_used = max_num_lights_used;
+   sample_light_uniform(view, *state, *index, *weight);
+}
+void orc_update_reservoir(uint32_t* state, UhReservoir* r, int Xi, float w_i, int M) { updateReservoir(*state, *r, Xi, w_i, M); }
+void orc_finalize_resampling(UhReservoir* r, float p_hat) { finalize_resampling(*r, p_hat); }
+void orc_resample(orc_ctx* c, uint32_t num_lights, uint32_t max_num_lights_used, uint32_t* state, const float p[3], UhReservoir* out) {
+   UhViewUniformData view;
+   std::memset(&view, 0, sizeof(view));
+   view.num_lights = num_lights;
+   view.max_num_lights_used = max_num_lights_used;
+   *out = resample(c->o, view, *state, v3(p[0], p[1], p[2]));
+}
+// material type 4's weight for explicit N, V, L: kD * baseColor + specular * pi (see pbr_weight)
+void orc_pbr_weight(const float N[3], const float V[3], const float L[3], const float base[3], float metallic, float roughness, float out[3]) {
+   V3 r = pbr_weight(v3(N[0], N[1], N[2]), v3(V[0], V[1], V[2]), v3(L[0], L[1], L[2]), v3(base[0], base[1], base[2]), metallic, roughness);
+   out[0] = r.x, out[1] = r.y, out[2] = r.z;
+}
+void orc_sphere_intersection(const float s[3], const float d[3], const float c[3], float radius, float out[2]) {
+   sky::SphereIntersection(v3(s[0], s[1], s[2]), v3(d[0], d[1], d[2]), v3(c[0], c[1], c[2]), radius, out[0], out[1]);
+}
+float orc_phase_mie(float costh, float g) { return sky::PhaseMie(costh, g); }
+void orc_integrate_optical_depth(const float s[3], const float d[3], float out[3]) {
+   V3 r = sky::IntegrateOpticalDepth(v3(s[0], s[1], s[2]), v3(d[0], d[1], d[2]));
+   out[0] = r.x, out[1] = r.y, out[2] = r.z;
+}
+// IntegrateScattering as the text has it: the light direction is used as given, and the transmittance comes back too
+void orc_integrate_scattering(const float s[3], const float d[3], float ray_length, const float l[3], const float lc[3], float color[3], float transmittance[3]) {
+   V3 t;
+   V3 r = sky::IntegrateScattering(v3(s[0], s[1], s[2]), v3(d[0], d[1], d[2]), ray_length, v3(l[0], l[1], l[2]), v3(lc[0], lc[1], lc[2]), &t);
+   color[0] = r.x, color[1] = r.y, color[2] = r.z;
+   transmittance[0] = t.x, transmittance[1] = t.y, transmittance[2] = t.z;
 }
 
 }  // extern "C"

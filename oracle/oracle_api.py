@@ -21,6 +21,10 @@ def build_oracle(force=False):
     hdr = os.path.join(_HERE, "..", "include", "utopian_hip.h")
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
         subprocess.run(["make", "-C", _HERE, "-B", "liboracle.so"], check=True, stdout=subprocess.DEVNULL)
+    # the reference's own shader text, compiled into oracle/_ref/ where its checkout is present; does nothing elsewhere
+    import ref_shaders
+
+    ref_shaders.build(force)
     return LIB_PATH
 
 
@@ -65,6 +69,17 @@ def lib():
         L.orc_marching_cubes.restype = C.c_uint64
         L.orc_mc_density.argtypes, L.orc_mc_density.restype = [C.c_float] * 4, C.c_float
         L.orc_mc_normal.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float)]
+        fp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+        L.orc_random_point_in_unit_disk.argtypes = [up, fp]
+        L.orc_sample_light_uniform.argtypes = [C.c_uint32, C.c_uint32, up, C.POINTER(C.c_int), fp]
+        L.orc_update_reservoir.argtypes = [up, C.c_void_p, C.c_int, C.c_float, C.c_int]
+        L.orc_finalize_resampling.argtypes = [C.c_void_p, C.c_float]
+        L.orc_resample.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, up, fp, C.c_void_p]
+        L.orc_pbr_weight.argtypes = [fp, fp, fp, fp, C.c_float, C.c_float, fp]
+        L.orc_sphere_intersection.argtypes = [fp, fp, fp, C.c_float, fp]
+        L.orc_phase_mie.argtypes, L.orc_phase_mie.restype = [C.c_float, C.c_float], C.c_float
+        L.orc_integrate_optical_depth.argtypes = [fp, fp, fp]
+        L.orc_integrate_scattering.argtypes = [fp, fp, C.c_float, fp, fp, fp, fp]
     return _lib
 
 
@@ -156,6 +171,12 @@ class OracleRenderer(Renderer):
     def target_function(self, light_index, p):
         return lib().orc_target_function(self._ctx, light_index, _fv(p))
 
+    def resample(self, num_lights, max_num_lights_used, state, p):
+        """restir_sampling.glsl's resample over this renderer's lights -> (RESERVOIR_DTYPE record, state after)"""
+        s, r = C.c_uint32(state), np.zeros(1, dtype=RESERVOIR_DTYPE)
+        lib().orc_resample(self._ctx, num_lights, max_num_lights_used, C.byref(s), _fv(p), r.ctypes.data)
+        return r[0], s.value
+
     def sample_texture(self, tex, u, v):
         out = (C.c_float * 3)()
         lib().orc_sample_texture(self._ctx, tex, u, v, out)
@@ -187,6 +208,65 @@ def random_point_in_unit_sphere(state):
     out = (C.c_float * 3)()
     lib().orc_random_point_in_unit_sphere(C.byref(s), out)
     return np.array(out[:], dtype=np.float32), s.value
+
+
+def random_point_in_unit_disk(state):
+    s = C.c_uint32(state)
+    out = (C.c_float * 2)()
+    lib().orc_random_point_in_unit_disk(C.byref(s), out)
+    return np.array(out[:], dtype=np.float32), s.value
+
+
+RESERVOIR_DTYPE = np.dtype([("Y", np.int32), ("W_sum", np.float32), ("W_X", np.float32), ("M", np.int32)])
+
+
+def sample_light_uniform(num_lights, max_num_lights_used, state):
+    """-> (index, weight, state after)"""
+    s, i, w = C.c_uint32(state), C.c_int(), C.c_float()
+    lib().orc_sample_light_uniform(num_lights, max_num_lights_used, C.byref(s), C.byref(i), C.byref(w))
+    return i.value, np.float32(w.value), s.value
+
+
+def update_reservoir(state, reservoir, Xi, w_i, M):
+    """reservoir: one RESERVOIR_DTYPE record -> (record after, state after)"""
+    s, r = C.c_uint32(state), np.array([reservoir], dtype=RESERVOIR_DTYPE)
+    lib().orc_update_reservoir(C.byref(s), r.ctypes.data, int(Xi), float(w_i), int(M))
+    return r[0], s.value
+
+
+def finalize_resampling(reservoir, p_hat):
+    r = np.array([reservoir], dtype=RESERVOIR_DTYPE)
+    lib().orc_finalize_resampling(r.ctypes.data, float(p_hat))
+    return r[0]
+
+
+def pbr_weight(N, V, L, base, metallic, roughness):
+    out = (C.c_float * 3)()
+    lib().orc_pbr_weight(_fv(N), _fv(V), _fv(L), _fv(base), float(metallic), float(roughness), out)
+    return np.array(out[:], dtype=np.float32)
+
+
+def sphere_intersection(start, direction, center, radius):
+    out = (C.c_float * 2)()
+    lib().orc_sphere_intersection(_fv(start), _fv(direction), _fv(center), float(radius), out)
+    return np.array(out[:], dtype=np.float32)
+
+
+def phase_mie(costh, g):
+    return np.float32(lib().orc_phase_mie(float(costh), float(g)))
+
+
+def integrate_optical_depth(start, direction):
+    out = (C.c_float * 3)()
+    lib().orc_integrate_optical_depth(_fv(start), _fv(direction), out)
+    return np.array(out[:], dtype=np.float32)
+
+
+def integrate_scattering(start, direction, ray_length, light_dir, light_color=(1, 1, 1)):
+    """IntegrateScattering with the light direction as given -> (color, transmittance)"""
+    c, t = (C.c_float * 3)(), (C.c_float * 3)()
+    lib().orc_integrate_scattering(_fv(start), _fv(direction), float(ray_length), _fv(light_dir), _fv(light_color), c, t)
+    return np.array(c[:], dtype=np.float32), np.array(t[:], dtype=np.float32)
 
 
 def frame_number(view):

@@ -97,7 +97,8 @@ def gamma_table():
 
 
 def light_records(view, lights):
-    """record 0: deferred.frag:74's sun; then the GpuLight records in order - (mode, pos, color, spot, att, dir) as the kernel's prep"""
+    """record 0: deferred.frag:74's sun; then the GpuLight records in order - (mode, pos, color, spot, att, dir) as the kernel's prep.
+    Each record also carries `light`: the 24 floats of the Light that surfaceShading is handed (bindless.glsl's layout), untouched"""
     recs = []
     sun = np.array(view.sun_dir[:], dtype=np.float32)
     srcs = [dict(type=F(0.0), pos=np.zeros(3, np.float32), color=np.ones(3, np.float32), spot=F(0.0), att=np.ones(3, np.float32),
@@ -105,7 +106,9 @@ def light_records(view, lights):
     for l in lights:
         srcs.append(dict(type=F(l.light_type), pos=np.array(l.position[:], np.float32), color=np.array(l.color[:3], np.float32), spot=F(l.spot),
                          att=np.array(l.attenuation[:], np.float32), dir=np.array(l.direction[:], np.float32)))
-    for s in srcs:
+    raw = [np.array([1, 1, 1, 1, 0, 0, 0, 0, *srcs[0]["dir"], 0, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0], np.float32)]  # deferred.frag:74
+    raw += [np.frombuffer(bytes(l), dtype=np.float32, count=24).copy() for l in lights]
+    for s, light in zip(srcs, raw):
         t = s["type"]
         mode = 0 if t == 0 else 1 if t == 1 else 2 if t == 2 else 3
         d = np.zeros(3, np.float32)
@@ -113,13 +116,16 @@ def light_records(view, lights):
             d = hr.normalize((s["dir"] * np.array([-1.0, 1.0, -1.0], np.float32))[None, :])[0]
         if t == 2:
             d = hr.normalize(s["dir"][None, :])[0]
-        recs.append(dict(mode=mode, pos=s["pos"], color=s["color"], spot=s["spot"], att=s["att"], dir=d))
+        recs.append(dict(mode=mode, pos=s["pos"], color=s["color"], spot=s["spot"], att=s["att"], dir=d, light=light))
     return recs
 
 
-def deferred(g, shadows, reflections, ssao_img, view, meshes, lights):
+def deferred(g, shadows, reflections, ssao_img, view, meshes, lights, surface_shading=None):
     """deferred.frag: (H, W, 4) float32 from the G-buffer targets `g` (dict of hybrid_reference.gbuffer's keys), the rt_shadows (H, W)
-    and rt_reflections (H, W, 4) images, the SSAO image (H, W), the view and the GpuLight records (view.num_lights of them are used)"""
+    and rt_reflections (H, W, 4) images, the SSAO image (H, W), the view and the GpuLight records (view.num_lights of them are used).
+    surface_shading(position, base_color, normal, metallic, roughness, light, eye) -> (n, 3), with `light` the 24 floats of one Light,
+    replaces the per-light term (pbr_lighting.glsl's surfaceShading at lightColorFactor 1); the default is this file's own reading of
+    it. tests/test_ref_shaders.py runs the same glue over the reference's compiled text that way"""
     H, W = g["position"].shape[:2]
     n = H * W
     P, N, R = (g[k][..., :3].reshape(-1, 3) for k in ("position", "normal", "pbr"))
@@ -150,6 +156,9 @@ def deferred(g, shadows, reflections, ssao_img, view, meshes, lights):
         nv4 = F(4.0) * NdotV
         Lo = np.zeros((n, 3), np.float32)
         for rec in light_records(view, list(lights)[: view.num_lights]):
+            if surface_shading is not None:
+                Lo = Lo + np.asarray(surface_shading(P, base, N, metallic, roughness, rec["light"], eye), np.float32)
+                continue
             if rec["mode"] == 0:
                 L, att = np.broadcast_to(rec["dir"], (n, 3)), np.ones(n, np.float32)
             elif rec["mode"] == 3:
