@@ -244,15 +244,16 @@ typedef struct uh_ctx uh_ctx;
  *        triangle total, 8 bytes, back to size its buffers), uh_get_isosurface_update_stats, uh_update_mesh_vertices (device input:
  *        it reads a 4-byte verdict on the caller's buffer back before it takes it), uh_get_mesh_update_stats, uh_read_denoised,
  *        uh_get_denoise_stats, uh_reset_denoise_history, uh_get_rtao_stats, uh_get_rtao_visits, uh_get_motion_stats, uh_reset_taa_history,
- *        uh_get_taa_stats, uh_destroy;
+ *        uh_get_taa_stats, uh_post_image, uh_read_post, uh_get_post_stats, uh_destroy;
  *   enqueues like a frame, ordered behind the frames in flight and before those that follow:  uh_rccl_gather_tiles, uh_mgpu_compose;
  *        uh_set_option for "frames_in_flight" and for "time_kernels" 1 -> 0 (the others only change what the NEXT enqueued
  *        frame does: "furnace", "sun_grid*", "camera_grid*", "overlap", "batch_frames", "trace_blocks_per_cu", "count_visits",
  *        "full_frame_restir", "primary_implicit", "rtao_order"; "device_build", "ploc_sah_top" invalidate the tree: the next frame
  *        needs uh_build_acceleration, which waits);
  *   host state only (no device access, nothing to wait for):  uh_add_mesh, uh_add_light, uh_set_instance_transform,
- *        uh_get_num_lights, uh_mesh_info, uh_read_mesh, uh_get_restir_rows, uh_tile_pack_count, uh_set_rtao_params, uh_set_taa_params
- *        (read by the next uh_render_hybrid), uh_taa_default_params, uh_taa_jitter, uh_last_error
+ *        uh_get_num_lights, uh_mesh_info, uh_read_mesh, uh_get_restir_rows, uh_tile_pack_count, uh_set_rtao_params, uh_set_taa_params,
+ *        uh_set_post_params, uh_reset_post_exposure (read by the next uh_render_hybrid; the post pair also by the next uh_post_image),
+ *        uh_taa_default_params, uh_taa_jitter, uh_post_default_params, uh_post_level_size, uh_last_error
  *        (uh_read_mesh of a mesh that uh_update_isosurface_mesh has made device-resident, or that uh_update_mesh_vertices last updated
  *        from a device pointer, copies it from the device: a blocking copy);
  *   uh_add_texture_rgba8 uploads into a fresh allocation no frame in flight can reference (textures enter a frame's tables at the
@@ -643,7 +644,7 @@ int uh_mgpu_set_option(uh_mgpu* group, const char* name, int value);
  * UH_HYBRID_RT_REFLECTIONS with view->ibl_enabled == 1 is UH_ERR_INVALID_ARGUMENT - and nothing runs - until the IBL maps (irradiance,
  * specular, BRDF LUT of ibl.rs) have been built with UH_HYBRID_ENVIRONMENT, below; mask bits, UH_ERR_NOT_BUILT and moved instances with
  * view->rebuild_tlas as for uh_render_frame (bits above UH_HYBRID_SHADOW_MAPS, below, are ignored, except UH_HYBRID_MARCHING_CUBES,
- * UH_HYBRID_GBUFFER_RASTER, UH_HYBRID_RESTIR_LIGHTS, UH_HYBRID_RTAO, UH_HYBRID_MOTION and UH_HYBRID_TAA).
+ * UH_HYBRID_GBUFFER_RASTER, UH_HYBRID_RESTIR_LIGHTS, UH_HYBRID_RTAO, UH_HYBRID_MOTION, UH_HYBRID_TAA and UH_HYBRID_POST).
  * STREAM ORDER: uh_render_hybrid enqueues like a frame (behind the frames in flight, ahead of those that follow); uh_read_hybrid and
  * uh_get_hybrid_stats wait for all work of the context and are complete on return. The exception is UH_HYBRID_SHADOW_MAPS, below: a
  * call that renders shadow maps BLOCKS the host until the frames in flight and the pass's binning have finished (it reads the
@@ -1291,6 +1292,87 @@ int uh_set_taa_params(uh_ctx*, const UhTaaParams*); /* validated here; a refused
 int uh_reset_taa_history(uh_ctx*);                  /* the next pass starts from no history (camera cut) */
 int uh_get_taa_stats(uh_ctx*, UhTaaStats*);         /* waits; all zero before the first pass */
 int uh_taa_jitter(uint32_t index, float out[2]);    /* needs no GPU: (halton(index+1, 2) - 0.5, halton(index+1, 3) - 0.5), in pixels */
+
+/* ---- HDR display chain for the hybrid frame: exposure, bloom and tone mapping between the taa pass and present ---------------------------
+ * An EXTENSION: the reference's present.frag converts the unbounded scene-linear frame straight to 8-bit sRGB (its Reinhard line,
+ * present.frag:35-36, is commented out). UH_HYBRID_POST (bit 16; bit 9 stays unused and ignored) adds one pass to uh_render_hybrid AFTER
+ * the taa pass (after the sky pass when that did not run in the call) and BEFORE present. Its source S is the taa_output this call wrote
+ * when UH_HYBRID_TAA ran in it, else deferred_output as it stands. Three stages, max(a, b) = a > b ? a : b and min likewise throughout:
+ *   meter     with UH_POST_AUTO_EXPOSURE: a histogram of L = 0.299 r + 0.587 g + 0.114 b over 256 bins, bin = clamp((bits(L) >> 20) - 888,
+ *             0, 255) - eight bins per octave from 2^-16 up; L <= 0 and bad pixels go to bin 0, which is not metered. Of the n metered
+ *             samples those ranked [(uint64)(low_percentile n), (uint64)(high_percentile n)) in bin order are kept (all when that range
+ *             is empty); Lavg = the float with bits (888 << 20) + ((sum kept_b b) << 20) / (sum kept_b) + (1 << 19), E_target =
+ *             min(max(key / Lavg, min_exposure), max_exposure), E = E_prev + (E_target - E_prev) adaptation - or E_target on the first
+ *             pass and the first after uh_reset_post_exposure. Nothing metered: E = E_prev (manual_exposure without one). Without the
+ *             flag: E = manual_exposure and no histogram. E stays on the device; every pass leaves an E_prev to the next.
+ *   bloom     with UH_POST_BLOOM: level k is (ceil(w / 2), ceil(h / 2)) of level k - 1 for k = 1..bloom_levels while level k - 1 is
+ *             larger than 1 x 1. Level 1 filters the prefiltered frame (0 for a bad pixel; c = S.rgb E, m = its largest channel: 0
+ *             unless m > bloom_threshold, else c ((m - bloom_threshold) / m)), deeper levels the level above: 4 x 4 taps (1, 3, 3, 1) / 8
+ *             per axis at source 2X - 1 .. 2X + 2, clamped. Up: U(img) takes the two nearest texels per axis at 0.75 and 0.25, clamped;
+ *             up[last] = down[last], up[k] = (down[k] + U(up[k + 1])) 0.5. Bloom images are RGBA32F with alpha 0.
+ *   composite x = S.rgb E + bloom_intensity U(up[1]) (no second term without the flag or without a level), then the operator:
+ *             UH_TONEMAP_NONE y = x; UH_TONEMAP_REINHARD xc = min(max(x, 0), 2^20), y = xc / (xc + 1); UH_TONEMAP_ACES a = xc (2.51 xc +
+ *             0.03), b = xc (2.43 xc + 0.59) + 0.14, y = min(max(a / b, 0), 1). post_output = (y, S.a), RGBA32F, oriented as S.
+ * When the pass ran in a call that also has UH_HYBRID_PRESENT, present reads post_output (FXAA and linearToSrgb as ever, now on display-range
+ * values); in every other call present is what it was. The bit counts as a final-frame pass: the final frame's images are allocated by
+ * the first call with it. It adds no refusal to uh_render_hybrid.
+ * NON-FINITE INPUT: a pixel is BAD by TAA's rule (a channel NaN, infinite or above 2^48 in magnitude). Its post_output texel is its S
+ * texel, bits unchanged; it is not metered and contributes 0 to bloom. Every other post_output texel is finite.
+ * uh_post_image runs the same three stages on a caller's W x H RGBA32F host image (the context's frame size) with the same params and
+ * exposure state, writes post_output and runs no present: for a path-traced or denoised frame. It needs no scene.
+ * PARAMS: uh_set_post_params validates and keeps them for the passes that follow (a refused call leaves the old ones): unknown flag
+ * bits; tonemap > 2; bloom_levels outside 1..8; manual_exposure, key, min_exposure or max_exposure not finite or outside (0, 65536], or
+ * min_exposure > max_exposure; adaptation outside (0, 1]; percentiles that are not 0 <= low < high <= 1; bloom_threshold or
+ * bloom_intensity not finite, < 0 or > 65536. Before the first call the defaults of uh_post_default_params hold: both flags, ACES, 6
+ * levels, manual_exposure 1, key 0.18, exposure in [1 / 64, 64], adaptation 0.1, percentiles 0.5 and 0.95, threshold 1, intensity 0.04.
+ * READ-BACK is uh_read_post (uh_read_hybrid keeps its images 0..17): UH_POST_OUTPUT (level 0), UH_POST_BLOOM_DOWN and UH_POST_BLOOM_UP
+ * (level 1..UhPostStats::levels, W x H as uh_post_level_size gives them), UH_POST_HISTOGRAM (level 0, 256 uint32). UH_ERR_INVALID_ARGUMENT
+ * before the first pass, for a level the last pass did not build, and for the histogram when the last pass did not meter.
+ * RESOURCES: 16 bytes per pixel of post_output, about 11 more of pyramid (two images per level that exists, up to 8 levels), 2 KiB of
+ * counts and a 32-byte record, allocated by the first pass; uh_post_image's upload another 16 bytes per pixel at its first call; freed by
+ * uh_destroy. A context that never sets the bit allocates nothing and runs no new code.
+ * STREAM ORDER: the pass as uh_render_hybrid. uh_post_image, uh_read_post and uh_get_post_stats wait and are complete on return.
+ * uh_set_post_params and uh_reset_post_exposure are host state, read by the next pass.
+ * ISOLATION: the bit changes no other hybrid image but present_output, no reservoir, accumulation, grid or UhStats, and not
+ * UhHybridFrameStats: its time goes to UhPostStats only. Without the bit every pass, image and stat is what it was. No uh_mgpu_ twin.
+ * LIMITS: no firefly suppression in the prefilter (one bright texel blooms); no lens effects or grading; the display output stays the
+ * 8-bit sRGB of present; uh_denoise and uh_render_forward reach the chain through uh_post_image and the host.
+ * Arithmetic: DESIGN.md section 2, "HDR display chain". */
+enum { UH_HYBRID_POST = 1u << 16 };
+enum { UH_POST_AUTO_EXPOSURE = 1u << 0, UH_POST_BLOOM = 1u << 1 };
+enum { UH_TONEMAP_NONE = 0, UH_TONEMAP_REINHARD = 1, UH_TONEMAP_ACES = 2 };
+enum { UH_POST_OUTPUT = 0 /* RGBA32F */, UH_POST_BLOOM_DOWN = 1, UH_POST_BLOOM_UP = 2 /* RGBA32F, level 1.. */, UH_POST_HISTOGRAM = 3 /* 256 x uint32 */ };
+typedef struct UhPostParams {
+   uint32_t flags, tonemap, bloom_levels;
+   float manual_exposure, key, min_exposure, max_exposure, adaptation, low_percentile, high_percentile, bloom_threshold, bloom_intensity;
+} UhPostParams;   /* 48 B */
+UH_LAYOUT_ASSERT(sizeof(UhPostParams) == 48 && offsetof(UhPostParams, tonemap) == 4 && offsetof(UhPostParams, bloom_levels) == 8 &&
+                    offsetof(UhPostParams, manual_exposure) == 12 && offsetof(UhPostParams, key) == 16 && offsetof(UhPostParams, min_exposure) == 20 &&
+                    offsetof(UhPostParams, max_exposure) == 24 && offsetof(UhPostParams, adaptation) == 28 &&
+                    offsetof(UhPostParams, low_percentile) == 32 && offsetof(UhPostParams, high_percentile) == 36 &&
+                    offsetof(UhPostParams, bloom_threshold) == 40 && offsetof(UhPostParams, bloom_intensity) == 44,
+                 "UhPostParams (48 B)");
+/* the last pass: its exposure E, E_target (E where nothing was metered) and Lavg (0 where nothing was), the pixels in bins 1..255 (0
+ * without UH_POST_AUTO_EXPOSURE), the bad pixels, the bloom levels built, the hipEvent times of the three stages, the passes so far */
+typedef struct UhPostStats {
+   float exposure, target_exposure, average_luminance;
+   uint32_t metered_pixels, bad_pixels, levels;
+   float meter_ms, bloom_ms, tonemap_ms;
+   uint32_t renders, reserved[2];
+} UhPostStats;    /* 48 B */
+UH_LAYOUT_ASSERT(sizeof(UhPostStats) == 48 && offsetof(UhPostStats, target_exposure) == 4 && offsetof(UhPostStats, average_luminance) == 8 &&
+                    offsetof(UhPostStats, metered_pixels) == 12 && offsetof(UhPostStats, bad_pixels) == 16 && offsetof(UhPostStats, levels) == 20 &&
+                    offsetof(UhPostStats, meter_ms) == 24 && offsetof(UhPostStats, bloom_ms) == 28 && offsetof(UhPostStats, tonemap_ms) == 32 &&
+                    offsetof(UhPostStats, renders) == 36 && offsetof(UhPostStats, reserved) == 40,
+                 "UhPostStats (48 B)");
+int uh_post_default_params(UhPostParams* out);          /* needs no GPU */
+int uh_set_post_params(uh_ctx*, const UhPostParams*);   /* validated here; a refused call leaves the old ones */
+int uh_reset_post_exposure(uh_ctx*);                    /* the next pass snaps to its target (camera cut) */
+int uh_get_post_stats(uh_ctx*, UhPostStats*);           /* waits; all zero before the first pass */
+int uh_post_image(uh_ctx*, const float* rgba32f);       /* W*H*4 floats on the host; the three stages into post_output; waits */
+int uh_read_post(uh_ctx*, int which, int level, void* out);   /* waits */
+/* needs no GPU: the size of bloom level `level` (0: the frame) of a W x H frame; UH_ERR_INVALID_ARGUMENT for one that does not exist */
+int uh_post_level_size(uint32_t W, uint32_t H, uint32_t level, uint32_t* w, uint32_t* h);
 
 #ifdef __cplusplus
 }

@@ -405,6 +405,37 @@ class Renderer {
       check(uh_get_taa_stats(ctx_, &s), "taa_stats");
       return s;
    }
+   // the HDR display chain between the taa pass and present of render_hybrid (UH_HYBRID_POST; utopian_hip.h "HDR display chain"): the
+   // params of the passes that follow, a camera cut, the last pass's record and times, its images (post_output and the bloom levels
+   // as float RGBA, the histogram as 256 uint32 - all as bytes), a level's size, and the chain on a caller's W*H*4 float image
+   static UhPostParams default_post_params() {
+      UhPostParams p;
+      if (uh_post_default_params(&p) != UH_OK) throw Error(UH_ERR_INVALID_ARGUMENT, "uh_post_default_params");
+      return p;
+   }
+   void set_post_params(const UhPostParams& params) { check(uh_set_post_params(ctx_, &params), "set_post_params"); }
+   void reset_post_exposure() { check(uh_reset_post_exposure(ctx_), "reset_post_exposure"); }
+   UhPostStats post_stats() {
+      UhPostStats s;
+      check(uh_get_post_stats(ctx_, &s), "post_stats");
+      return s;
+   }
+   std::pair<uint32_t, uint32_t> post_level_size(uint32_t level) const {
+      uint32_t w = 0, h = 0;
+      if (uh_post_level_size(width_, height_, level, &w, &h) != UH_OK) throw Error(UH_ERR_INVALID_ARGUMENT, "uh_post_level_size: no such level");
+      return {w, h};
+   }
+   void post_image(const float* rgba32f) { check(uh_post_image(ctx_, rgba32f), "post_image"); }
+   std::vector<uint8_t> read_post(int which, int level = 0) {
+      size_t bytes = 256 * sizeof(uint32_t);
+      if (which != UH_POST_HISTOGRAM) {
+         const auto wh = post_level_size(which == UH_POST_OUTPUT ? 0u : (uint32_t)level);
+         bytes = (size_t)wh.first * wh.second * 16;
+      }
+      std::vector<uint8_t> out(bytes);
+      check(uh_read_post(ctx_, which, level, out.data()), "read_post");
+      return out;
+   }
    // `view` jittered by uh_taa_jitter(index) pixels of this renderer's frame (jitter_view, above): set its prev_frame_projection_view to
    // the previous frame's UN-jittered projection * view first, and keep this frame's un-jittered product for the next
    UhViewUniformData jittered(const UhViewUniformData& view, uint32_t index) const {

@@ -14,6 +14,8 @@ from .api import (  # noqa: F401
     load_library,
     make_light,
     make_material,
+    post_default_params,
+    post_level_size,
     rtao_default_params,
     shadow_cascades,
     taa_default_params,

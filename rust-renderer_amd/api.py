@@ -53,6 +53,7 @@ from .types import (
     HYBRID_REFLECTIONS,
     HYBRID_SHADOWS,
     HYBRID_SSAO_IMAGE,
+    HYBRID_POST,
     HYBRID_TAA,
     HYBRID_TAA_HISTORY,
     HYBRID_TAA_OUTPUT,
@@ -76,6 +77,12 @@ from .types import (
     FORWARD_VISIBILITY,
     ForwardStats,
     Reservoir,
+    POST_BLOOM_DOWN,
+    POST_BLOOM_UP,
+    POST_HISTOGRAM,
+    POST_OUTPUT,
+    PostParams,
+    PostStats,
     RestirRows,
     RtaoParams,
     RtaoStats,
@@ -697,6 +704,66 @@ class Renderer:
         self._check(self._taa_fn("get_taa_stats", TaaStats)(self._ctx, C.byref(s)))
         return s
 
+    # -- the HDR display chain (HYBRID_POST; include/utopian_hip.h "HDR display chain") ---
+    def _post_fn(self, name, *argtypes):
+        if self.backend != "hip":
+            raise NotImplementedError(f"the HDR display chain is a per-context verb of the HIP library; backend {self.backend!r} has none")
+        fn = getattr(self._lib, "uh_" + name)
+        fn.argtypes, fn.restype = [C.c_void_p] + list(argtypes), C.c_int
+        return fn
+
+    @staticmethod
+    def post_default_params():
+        """UhPostParams as uh_post_default_params fills it: both flags, ACES, 6 levels, 1.0, 0.18, [1/64, 64], 0.1, 0.5, 0.95, 1.0, 0.04"""
+        return post_default_params()
+
+    def set_post_params(self, params=None, **fields):
+        """uh_set_post_params: `params` (a PostParams; the defaults when None) with `fields` set on a copy - the params of the post
+        passes that follow (render_hybrid with HYBRID_POST, post_image). A refused call raises and leaves the old ones."""
+        p = PostParams.from_buffer_copy(post_default_params() if params is None else params)
+        for k, v in fields.items():
+            if not hasattr(p, k):
+                raise TypeError(f"PostParams has no field {k!r}")
+            setattr(p, k, v)
+        self._check(self._post_fn("set_post_params", C.POINTER(PostParams))(self._ctx, C.byref(p)))
+        return p
+
+    def reset_post_exposure(self):
+        """uh_reset_post_exposure: the next post pass snaps to its target exposure (a camera cut)"""
+        self._check(self._post_fn("reset_post_exposure")(self._ctx))
+
+    def post_stats(self):
+        """UhPostStats of the last post pass; all zero before the first"""
+        s = PostStats()
+        self._check(self._post_fn("get_post_stats", C.POINTER(PostStats))(self._ctx, C.byref(s)))
+        return s
+
+    def post_level_size(self, level):
+        """(w, h) of bloom level `level` of this renderer's frame (0: the frame); raises ValueError for one that does not exist"""
+        return post_level_size(self.width, self.height, level)
+
+    def post_image(self, image):
+        """uh_post_image: the three stages of the chain on `image`, (H, W, 4) float32, into post_output (read_post(POST_OUTPUT))"""
+        img = np.ascontiguousarray(image, dtype=np.float32)
+        if img.shape != (self.height, self.width, 4):
+            raise ValueError(f"post_image: the image must be ({self.height}, {self.width}, 4), not {img.shape}")
+        self._check(self._post_fn("post_image", C.c_void_p)(self._ctx, img.ctypes.data))
+
+    def read_post(self, which, level=0):
+        """uh_read_post: POST_OUTPUT (H, W, 4) float32; POST_BLOOM_DOWN / POST_BLOOM_UP level 1..post_stats().levels, (h, w, 4) float32 at
+        the level's size; POST_HISTOGRAM 256 uint32 of the last metered pass"""
+        if which == POST_HISTOGRAM:
+            out = np.empty(256, np.uint32)
+        elif which in (POST_BLOOM_DOWN, POST_BLOOM_UP):
+            w, h = self.post_level_size(level)
+            out = np.empty((h, w, 4), np.float32)
+        elif which == POST_OUTPUT:
+            out = np.empty((self.height, self.width, 4), np.float32)
+        else:
+            raise ValueError(f"post image index {which} (0..3)")
+        self._check(self._post_fn("read_post", C.c_int, C.c_int, C.c_void_p)(self._ctx, int(which), int(level), out.ctypes.data))
+        return out
+
     @staticmethod
     def jitter_view(view, index, width=None, height=None):
         """a copy of `view` jittered by taa_jitter(index) pixels: projection and inverse_projection through camera.jitter_projection, and
@@ -1034,6 +1101,26 @@ def taa_default_params():
     if fn(C.byref(p)) != 0:
         raise UtopianError("uh_taa_default_params failed")
     return p
+
+
+def post_default_params():
+    """UhPostParams as uh_post_default_params fills it (needs no GPU)"""
+    fn = load_library().uh_post_default_params
+    fn.argtypes, fn.restype = [C.POINTER(PostParams)], C.c_int
+    p = PostParams()
+    if fn(C.byref(p)) != 0:
+        raise UtopianError("uh_post_default_params failed")
+    return p
+
+
+def post_level_size(width, height, level):
+    """uh_post_level_size: (w, h) of bloom level `level` of a width x height frame (needs no GPU); ValueError for one that does not exist"""
+    fn = load_library().uh_post_level_size
+    fn.argtypes, fn.restype = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], C.c_int
+    w, h = C.c_uint32(), C.c_uint32()
+    if fn(int(width), int(height), int(level), C.byref(w), C.byref(h)) != 0:
+        raise ValueError(f"a {width} x {height} frame has no bloom level {level}")
+    return int(w.value), int(h.value)
 
 
 def taa_jitter(index):

@@ -606,9 +606,36 @@ struct uh_ctx {
          }
       } taa;
 
+      // the HDR display chain (UH_HYBRID_POST, uh_post_image), allocated by the first pass: post_output, the bloom pyramid (every level
+      // of the frame that exists, up to kPostMaxLevels; the last level a pass builds has no `up` of its own - it is its `down`), the
+      // histogram with the copy uh_read_post reads, and the exposure record, which stays on the device from pass to pass. input:
+      // uh_post_image's upload (its first call). params: the last uh_set_post_params (the defaults before). have_exposure: the record
+      // holds a previous pass's exposure (false before the first pass and after uh_reset_post_exposure); levels, metered: what the last
+      // pass built. stage: meter, bloom, composite of the last pass.
+      struct __attribute__((visibility("hidden"))) Post {
+         DevBuf<float4> out, input;
+         DevBuf<float4> down[kPostMaxLevels + 1], up[kPostMaxLevels + 1];  // [0] unused
+         DevBuf<uint32_t> hist, hist_copy;
+         DevBuf<PostRecord> rec;
+         UhPostParams params{UH_POST_AUTO_EXPOSURE | UH_POST_BLOOM, UH_TONEMAP_ACES, 6, 1.0f, 0.18f, 0.015625f, 64.0f, 0.1f, 0.5f, 0.95f, 1.0f, 0.04f};
+         Stage stage[3];
+         bool have_exposure = false, metered = false;
+         uint32_t levels = 0, renders = 0;
+         template <class F> void images(uint32_t W, uint32_t H, F&& f) {
+            f(out, (size_t)W * H);
+            for (uint32_t k = 1; k <= kPostMaxLevels; k++) f(down[k], post_level_texels(W, H, k)), f(up[k], post_level_texels(W, H, k));
+            f(hist, (size_t)kPostBins), f(hist_copy, (size_t)kPostBins), f(rec, (size_t)1);
+         }
+         void destroy() {
+            images(0, 0, ReleaseBuf{});
+            input.release();
+            for (Stage& s : stage) s.destroy();
+         }
+      } post;
+
       __attribute__((visibility("hidden"))) void destroy() {
          rt_images(0, ReleaseBuf{}), frame_images(0, ReleaseBuf{});
-         env.destroy(), sm.destroy(), gr.destroy(), mc.destroy(), rl.destroy(), ao.destroy(), mv.destroy(), taa.destroy();
+         env.destroy(), sm.destroy(), gr.destroy(), mc.destroy(), rl.destroy(), ao.destroy(), mv.destroy(), taa.destroy(), post.destroy();
          meshes.release(), vertices.release(), indices.release(), raw_lights.release();
          for (hipEvent_t ev : waits)
             if (ev) (void)hipEventDestroy(ev);

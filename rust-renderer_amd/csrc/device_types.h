@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "bvh.h"
+#include "post_levels.h"
 #include "sun_grid.h"
 #include "utopian_hip.h"
 
@@ -333,6 +334,31 @@ struct TaaDev {
    float max_history, alpha_min, clamp_gamma;
 };
 
+// the HDR display chain of the hybrid frame (UH_HYBRID_POST; post.hip): what its kernels read and write
+constexpr uint32_t kPostBins = 256;
+// the exposure record, on the device from one pass to the next: the exposure E the later kernels of a pass read, its target and the
+// metered average (0 where there was none), the metered pixels (bins 1..255) and the bad pixels the composite kernel counted
+struct PostRecord {
+   float exposure, target, lavg;
+   uint32_t metered, bad, pad[3];
+};
+struct PostDev {
+   const float4* src;              // S: taa_output of this call, deferred_output, or uh_post_image's upload
+   float4* out;                    // post_output
+   uint32_t* hist;                 // kPostBins counts, zero between passes (the exposure kernel takes them and zeroes them again)
+   uint32_t* hist_copy;            // the last metered pass's counts, for uh_read_post
+   PostRecord* rec;
+   float4* down[kPostMaxLevels + 1];  // [k]: level k, 1..levels ([0] unused); up[levels] is down[levels]
+   float4* up[kPostMaxLevels + 1];
+   uint32_t lw[kPostMaxLevels + 1], lh[kPostMaxLevels + 1];  // level sizes, [0] the frame's
+   uint32_t levels;                // the levels this pass builds: 0 without UH_POST_BLOOM or for a 1 x 1 frame
+   uint32_t W, H;
+   uint32_t auto_exposure;         // UH_POST_AUTO_EXPOSURE
+   uint32_t have_prev;             // rec->exposure is a previous pass's (not the first pass, not after uh_reset_post_exposure)
+   uint32_t tonemap;               // UH_TONEMAP_*
+   float manual_exposure, key, min_exposure, max_exposure, adaptation, low_percentile, high_percentile, bloom_threshold, bloom_intensity;
+};
+
 // launch wrappers implemented in kernels.hip, path_fused.hip, restir.hip, tiles.hip and hybrid_kernels.hip --------------------------------------------------
 struct LaunchCfg {
    hipStream_t stream;
@@ -438,6 +464,11 @@ void launch_rtao_trace(const LaunchCfg&, const SceneDev&, const HybridDev&, cons
 void launch_rtao_resolve(const LaunchCfg&, const HybridDev&, const RtaoDev&, uint16_t* ssao);
 // the taa pass (taa.hip): one lane per pixel; fp gives the frame, the matrices of primary_ray and prev_pv; t.counters zeroed by the caller
 void launch_hybrid_taa(const LaunchCfg&, const FrameParams&, const TaaDev&);
+// the three stages of the post pass (post.hip). meter: the histogram (with auto_exposure) and the exposure record; bloom: down[1..levels]
+// and up[levels - 1..1] (levels >= 1); composite: post_output, and the bad pixels into the record
+void launch_post_meter(const LaunchCfg&, const PostDev&);
+void launch_post_bloom(const LaunchCfg&, const PostDev&);
+void launch_post_composite(const LaunchCfg&, const PostDev&);
 // the shadow-map rasteriser (shadow_map.hip): setup per (triangle, cascade), binning into kShadowTile^2 tiles, resolve per tile in LDS
 constexpr uint32_t kShadowTile = 128;
 struct ShadowDev {

@@ -439,3 +439,36 @@ class TaaStats(C.Structure):
 
 
 assert C.sizeof(TaaStats) == 16 and TaaStats.reset_pixels.offset == 4 and TaaStats.taa_ms.offset == 8 and TaaStats.reserved.offset == 12
+
+
+# the HDR display chain of the hybrid frame (an extension; utopian_hip.h "HDR display chain"): the pass between the taa pass and present,
+# the flags and operators of PostParams and the images of Renderer.read_post; bit 9 stays unused
+HYBRID_POST = 1 << 16
+POST_AUTO_EXPOSURE, POST_BLOOM = 1 << 0, 1 << 1
+TONEMAP_NONE, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2
+POST_OUTPUT, POST_BLOOM_DOWN, POST_BLOOM_UP, POST_HISTOGRAM = 0, 1, 2, 3
+
+
+class PostParams(C.Structure):
+    """UhPostParams: flags (POST_*), the operator (TONEMAP_*), the bloom levels asked for, the exposure without metering, the key the
+    metered average is mapped to, the exposure clamps, the adaptation rate, the percentiles kept by the meter, the bloom threshold and
+    intensity; uh_post_default_params fills the defaults"""
+
+    _fields_ = [("flags", C.c_uint32), ("tonemap", C.c_uint32), ("bloom_levels", C.c_uint32), ("manual_exposure", C.c_float),
+                ("key", C.c_float), ("min_exposure", C.c_float), ("max_exposure", C.c_float), ("adaptation", C.c_float),
+                ("low_percentile", C.c_float), ("high_percentile", C.c_float), ("bloom_threshold", C.c_float), ("bloom_intensity", C.c_float)]
+
+
+assert C.sizeof(PostParams) == 48 and [getattr(PostParams, n).offset for n, _ in PostParams._fields_] == list(range(0, 48, 4))
+
+
+class PostStats(C.Structure):
+    """UhPostStats: the last post pass - its exposure, target and metered average luminance, the metered and the bad pixels, the bloom
+    levels built, hipEvent ms of the three stages, the passes so far"""
+
+    _fields_ = [("exposure", C.c_float), ("target_exposure", C.c_float), ("average_luminance", C.c_float), ("metered_pixels", C.c_uint32),
+                ("bad_pixels", C.c_uint32), ("levels", C.c_uint32), ("meter_ms", C.c_float), ("bloom_ms", C.c_float), ("tonemap_ms", C.c_float),
+                ("renders", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+assert C.sizeof(PostStats) == 48 and PostStats.renders.offset == 36 and PostStats.reserved.offset == 40
