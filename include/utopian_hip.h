@@ -355,7 +355,11 @@ int uh_reset_stats(uh_ctx* ctx);
  *                depth per block of 4 x 4 cells, small enough to stay in the L2, asked before the cell's own record; 0: none),
  *                "sun_verdicts" (0/1, default 1: with the grid in use and lights disabled the sun-ray kernels leave one verdict bit per
  *                ray, and the kernels that read the path's radiance next add its throughput there - no read-modify-write of the
- *                radiance in the sun kernels; 0: they add it themselves; same images)
+ *                radiance in the sun kernels; 0: they add it themselves; same images),
+ *                "slim_state" (0/1, default 1: a pass with sun verdicts and one sample per frame carries 56 bytes of state per path
+ *                instead of 64 - the path id rides with the origin, so no id queue is written or read behind bounce 0 - and the sun
+ *                kernels of its last bounce store the surviving paths' radiance themselves, no flush launch; every other pass keeps
+ *                the four-quad state; same images)
  *  camera grid   "camera_grid" (0/1, default 1: the primary rays of a camera that has been the same for two consecutive frame calls -
  *                or for a call of 8 or more frames - go through a per-camera grid of packet lists, one cell per pixel, instead of
  *                the tree; same hit records bit for bit), "camera_grid_max_walk", "camera_grid_walk_whole",

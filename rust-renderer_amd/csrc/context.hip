@@ -408,9 +408,7 @@ static int enqueue_path_trace(uh_ctx* c, Slot& s, const FrameParams& frame) {
    DeviceStats* st = c->dstats.p;
    // reference.rgen:28: samples of one frame run back to back (the raygen RNG state carries over)
    for (uint32_t smp = 0; smp < fp.samples_per_frame; smp++) {
-      HIP_TRY(c, hipMemsetAsync(ctl, 0, sizeof(Control), s.stream));
       uint32_t slot = 0;
-      launch_generate(lc, fp, s.ps, ctl, smp);
       // a lone frame: bounce 0 as a wavefront (its rays are coherent, the camera grid serves them), the others inside k_path_fused
       // ... when the caller waits for its frames (the frame before this one has left the GPU): the fused kernel fills the chip by
       // itself, so with frames in flight - a caller that does not wait - the wavefront's small launches interleave better (2.2 against
@@ -426,6 +424,11 @@ static int enqueue_path_trace(uh_ctx* c, Slot& s, const FrameParams& frame) {
       // otherwise), when no light ray adds to the same radiance behind them (the reference adds the sun's term first, rgen:63-122, and
       // float addition does not commute bit for bit) and when the wavefront runs every bounce (the fused kernel adds its own terms)
       fp.sun_verdicts = (c->sun_x.verdicts && c->sun.this_frame && fp.sun_shadow_enabled == 1 && fp.lights_enabled != 1 && !fused) ? 1u : 0u;
+      // The slim path state (option "slim_state", device_types.h PathState): where the verdicts hold no light sample rides with the path,
+      // and with one sample per frame nothing reads the raygen RNG word behind bounce 0 - its place carries the path id
+      fp.slim_state = (c->slim_state && fp.sun_verdicts == 1 && fp.samples_per_frame == 1) ? 1u : 0u;
+      HIP_TRY(c, hipMemsetAsync(ctl, 0, sizeof(Control), s.stream));
+      launch_generate(lc, fp, s.ps, ctl, smp);  // (behind the choice of the state: the origin quads it stores carry the id or the RNG word)
       for (uint32_t b = 0; b < (fused ? 1u : fp.num_bounces); b++) {
          begin_timed(c, (b == 0 && c->cam.this_frame) ? 3 : 0, s.stream);
          if (b == 0 && c->cam.this_frame) {
@@ -497,7 +500,8 @@ static int enqueue_path_trace(uh_ctx* c, Slot& s, const FrameParams& frame) {
       }
       // the paths still alive after the last bounce: their radiance (with what the last bounce's shadow rays added) goes to the
       // per-id array the tail reads
-      if (fp.num_bounces > 0 && !fused) launch_flush_survivors(lc, fp, s.ps, ctl);
+      // (slim state: the last bounce's sun kernels stood at those positions with the verdict in hand and stored it themselves)
+      if (fp.num_bounces > 0 && !fused && !fp.slim_state) launch_flush_survivors(lc, fp, s.ps, ctl);
       const bool last = smp + 1 == fp.samples_per_frame;
       // the accumulate / store tail (rgen:130-144) is a read-modify-write on the accumulation image:
       // frames must apply it in order, everything before it may overlap with other frames in flight
@@ -1081,6 +1085,9 @@ int uh_set_option(uh_ctx* c, const char* name, int value) {
       // 1: the grid's sun kernels leave one bit per ray and the next shading kernel (or the flush) adds the lit paths' throughput to
       // their radiance; 0: the sun kernels add it themselves. Same images; frames with lights enabled always take the second form
       c->sun_x.verdicts = value != 0;
+   else if (n == "slim_state")
+      // 1: a pass with sun verdicts and one sample per frame carries the slim path state (device_types.h PathState); 0: never
+      c->slim_state = value != 0;
    else if (n == "sun_grid_coarse") {
       // the coarse cover (sun_grid.h): one depth per block of 2^value x 2^value cells, asked before the cell's own record; 0: none
       if (!range(0, 6)) return bad("(log2 of the block edge in cells) must be 0..6");

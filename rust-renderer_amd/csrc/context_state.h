@@ -180,13 +180,7 @@ struct Slot {
 
    hipError_t create(size_t n) {
       capacity = n;
-      uint32_t shard_cap = 0;
-      {  // exact: the largest number of 64-path runs one shard receives (shard_of_run)
-         const uint32_t runs = (uint32_t)((n + 63) / 64);
-         uint32_t per_shard[kShards] = {0};
-         for (uint32_t r = 0; r < runs; r++) per_shard[shard_of_run(r)]++;
-         for (uint32_t s = 0; s < kShards; s++) shard_cap = per_shard[s] * 64 > shard_cap ? per_shard[s] * 64 : shard_cap;
-      }
+      const uint32_t shard_cap = layout_shard_cap(n);  // exact: the largest number of 64-path runs one shard receives (shard_of_run)
       if (shard_cap >= (1u << 31)) return hipErrorInvalidValue;  // a queue position's top bit carries the path's sun verdict (path_shading.h kSunLitBit)
       hipError_t e;
 #define SLOT_TRY(expr)                 \
@@ -196,11 +190,10 @@ struct Slot {
       for (hipEvent_t* ev : {&ev_traced, &ev_missed, &ev_shaded, &ev_shadowed, &ev_side_done, &ev_acc}) SLOT_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
       SLOT_TRY(hipEventCreate(&frame_start));
       SLOT_TRY(hipEventCreate(&frame_stop));
-      const size_t stagger = 4352;  // 4 KiB + 256 B per array slot
+      const size_t stagger = kPlaneStaggerBytes;  // 4 KiB + 256 B per array slot
       // planes staggered like the arrays: the same index of two planes must not alias. The hit plane is indexed by queue position
       // (shard segment + position in the shard's queue), which runs to kShards * shard_cap >= n
-      const size_t cap_q = (size_t)shard_cap * kShards;
-      const size_t plane = (n > cap_q ? n : cap_q) + stagger / sizeof(float4);
+      const size_t plane = layout_plane_quads(n, shard_cap);
       SLOT_TRY(rec.alloc(plane * (2 * kRecQuads + 1), 0 * stagger));
       SLOT_TRY(radf.alloc(n, 1 * stagger));
       SLOT_TRY(pixcol.alloc(n, 2 * stagger));
@@ -421,6 +414,7 @@ struct uh_ctx {
    CachedGrid<3> sun;               // key: the frame's sun direction
    SunGridExtras sun_x;
    bool primary_implicit = true;    // option "primary_implicit" (FrameParams::primary_implicit)
+   bool slim_state = true;          // option "slim_state" (FrameParams::slim_state)
 
    // the primary rays through a per-camera grid instead of the tree (sun_grid.h "camera grid"; option "camera_grid"), built once the same
    // camera has been asked for in two consecutive frame calls, or at once by a call that carries 8 frames of it (grid_cache.hip ensure_camera_grid)

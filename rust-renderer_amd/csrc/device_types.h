@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "bvh.h"
+#include "path_layout.h"
 #include "post_levels.h"
 #include "sun_grid.h"
 #include "utopian_hip.h"
@@ -35,6 +36,7 @@ constexpr uint32_t kLaunchSlots = kMaxBounces * 4 + 8;  // per bounce: closest, 
 constexpr uint32_t kShards = 32;
 constexpr uint32_t kShardBits = 5;
 static_assert((1u << kShardBits) == kShards, "kShards is a power of two");
+static_assert(kLayoutShards == kShards && kLayoutShardBits == kShardBits, "path_layout.h states the same shards");
 // Fibonacci hash of the 64-path run index (top 5 bits). A plain `run % 32` aliases with the tile
 // partition: with 64-pixel-wide tiles every run a rank owns is even, which left half of the shards
 // (and half of the traversal blocks) empty on every rank of a multi-GPU job.
@@ -127,6 +129,11 @@ struct FrameParams {
    // this pass leave one verdict bit per ray in PathState::sun_lit and the kernels that read a path's radiance next add its throughput
    // there; 0 = the sun kernels add it themselves (lights enabled, no grid for the bounce, the fused kernel's frames, the option off)
    uint32_t sun_verdicts;
+   // option "slim_state" (set per sample pass beside sun_verdicts, context.hip enqueue_path_trace: sun_verdicts == 1 and one sample per
+   // frame): 1 = the pass carries the slim path state (PathState below) - the path id rides with the origin, no id queue is written
+   // or read behind bounce 0, throughput and radiance are 24 bytes in 24, and the sun kernels of the last bounce store every surviving
+   // path's final radiance (radf[id]) themselves, so k_flush_survivors is not launched; 0 = the four-quad state, the id queues, the flush
+   uint32_t slim_state;
    uint32_t furnace;  // option "furnace": the reference's FURNACE_TEST build of the miss shader (reference.rmiss:14-28): a miss returns white
    uint32_t num_lights_used;  // min(view.num_lights, view.max_num_lights_used)
    uint32_t temporal_enabled, spatial_enabled;
@@ -153,6 +160,17 @@ struct FrameParams {
 //   plane 2  throughput.rgb            | light weight f                    radiance += throughput * f when the light is visible (rgen:121)
 //   plane 3  radiance.rgb              | light index (bits)                rgen:69-78, :118-122 add to it; not materialised for bounce 0 (it is zero), nor - with sun verdicts - for bounce 1
 // The hit record of a bounce's ray (t, u, v | packet index, 0xffffffff = miss) lies in a plane of its own at the same position.
+// SLIM state (FrameParams::slim_state: no lights, one sample per frame, sun verdicts): the light weight and the light index are never
+// read, and the raygen RNG word is consumed by select_light and the next sample's k_generate alone - three dead words. The same
+// planes, same stride, then hold 56 bytes per path:
+//   plane 0  ray origin.xyz            | path id                           in every set, also what k_generate writes when primary_implicit is off
+//   plane 1  ray direction.xyz         | rayPayload.randomSeed (bits)      as above
+//   plane 2  throughput.rgb            | radiance.r
+//   plane 3  radiance.g, radiance.b                                        8-byte PAIRS by the same position (rec_pair), in the plane's first half
+// Where the radiance is not materialised (rad_stored), plane 2's w is a zero nobody reads and plane 3 is not touched. With the id
+// beside the origin no kernel behind bounce 0 needs queue[0 / 1]: k_shade_hit neither appends ids nor, at b >= 1, reads them, and a path
+// still knows its id where it ends. (Keeping queue[0] and its counts from pass to pass - they depend on the number of ids alone - was
+// measured level with rebuilding them and is not done: profiles/README.md "Slim path state".)
 constexpr uint32_t kRecQuads = 4;
 enum { REC_ORIGIN = 0, REC_DIR = 1, REC_THR = 2, REC_RAD = 3 };
 struct PathRecs {
@@ -173,7 +191,13 @@ struct PathState {
    unsigned long long* sun_lit;
    uint32_t shard_cap;  // entries per shard segment = pixels a shard can own (multiple of 64)
 };
-__host__ __device__ inline float4* rec_quad(const PathRecs& rec, uint32_t pos, int quad) { return rec.base + rec.plane * (size_t)quad + pos; }
+// the address arithmetic of both layouts is path_layout.h rec_offset (checked on the host: tests/cpp/path_layout_check.cpp)
+__host__ __device__ inline float4* rec_quad(const PathRecs& rec, uint32_t pos, int quad) {
+   return reinterpret_cast<float4*>(reinterpret_cast<char*>(rec.base) + rec_offset(rec.plane, pos, quad));
+}
+__host__ __device__ inline float2* rec_pair(const PathRecs& rec, uint32_t pos) {  // slim state: plane 3's (radiance.g, radiance.b)
+   return reinterpret_cast<float2*>(reinterpret_cast<char*>(rec.base) + rec_offset(rec.plane, pos, REC_RAD, true));
+}
 
 // rays of the stand-alone queries (uh_trace_closest, the G-buffer cast): record i = ray i, tmin / tmax in the w components
 struct RawRays {
@@ -376,6 +400,7 @@ void launch_trace_camera_grid(const LaunchCfg&, const FrameParams&, const SceneD
 void launch_shade_miss(const LaunchCfg&, const FrameParams&, const PathState&, Control*, DeviceStats*, uint32_t bounce);
 void launch_shade_hit(const LaunchCfg&, const FrameParams&, const SceneDev&, const PathState&, const Images&, Control*, DeviceStats*, uint32_t bounce);
 // the paths still alive after the last bounce hand their radiance to the per-id array k_finish_sample reads
+// (not launched for a pass with FrameParams::slim_state: its last sun kernels store the radiance themselves)
 void launch_flush_survivors(const LaunchCfg&, const FrameParams&, const PathState&, Control*);
 void launch_path_fused(const LaunchCfg&, const FrameParams&, const SceneDev&, const PathState&, Control*, DeviceStats*, const SunGridDev& g, bool use_grid, bool sun_of_bounce0);
 void launch_trace_shadow(const LaunchCfg&, const FrameParams&, const SceneDev&, const PathState&, Control*, DeviceStats*, uint32_t bounce,

@@ -103,11 +103,15 @@ __global__ __launch_bounds__(kBlock, 6) void k_trace_closest(SceneDev sc, bool s
 // leftovers (sun rays only): the rays k_trace_sun_grid could not serve from its grid (queue 3); they are already counted
 // VERDICT (sun leftovers only): behind a grid kernel that left verdicts, an unoccluded ray sets its bit in the word the grid kernel
 // stored (same stream, so the word is there) - the pool carries the origin alone
-template <bool COUNT, bool LIGHT, bool VERDICT = false>
+// FINAL (with VERDICT; the last bounce of a pass with FrameParams::slim_state): a ray whose walk ends, lit or not, stores its path's
+// final radiance - radf[id] = radiance (+ throughput if lit), what k_flush_survivors would have stored - and no verdict; the id is
+// the origin's w, throughput and radiance are read where the walk ends (the leftovers are few: no place in the pool for them)
+template <bool COUNT, bool LIGHT, bool VERDICT = false, bool FINAL = false>
 __global__ __launch_bounds__(kBlock, 5) void k_trace_shadow(SceneDev sc, FrameParams fp, PathState ps, Control* ctl, DeviceStats* stats, uint32_t bounce,
                                                               uint32_t cursor_slot, bool leftovers) {
    __shared__ uint32_t s_stack[kWavesPerBlock][kLdsStack][64];
    static_assert(!(VERDICT && LIGHT), "verdicts are the sun rays'");
+   static_assert(VERDICT || !FINAL, "the final form replaces the verdict");
    constexpr int NA = VERDICT ? 1 : 3;
    __shared__ RayPool<NA> s_pool[kWavesPerBlock];
    const uint32_t lane = lane_id();
@@ -137,6 +141,7 @@ __global__ __launch_bounds__(kBlock, 5) void k_trace_shadow(SceneDev sc, FramePa
    t.cur = kEmptyRef;
    t.sp = 0;
    uint32_t id = 0, n_nodes = 0, n_tris = 0;  // id: the path's position in the next bounce's queue
+   uint32_t path_id = 0;                      // FINAL: the path's id (the slim state's origin.w)
    float4 lit = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
    uint32_t spill[kSpillStack];
    auto take = [&](uint32_t slot) {
@@ -144,6 +149,7 @@ __global__ __launch_bounds__(kBlock, 5) void k_trace_shadow(SceneDev sc, FramePa
       ShadowRay s;
       if constexpr (VERDICT) {
          s = make_shadow_ray<false>(sc, fp, pool.v[0][slot], 0u);
+         if constexpr (FINAL) path_id = __float_as_uint(pool.v[0][slot].w);
       } else {
          const float4 thr = pool.v[1][slot], r4 = pool.v[2][slot];
          s = make_shadow_ray<LIGHT>(sc, fp, pool.v[0][slot], __float_as_uint(r4.w));
@@ -154,7 +160,16 @@ __global__ __launch_bounds__(kBlock, 5) void k_trace_shadow(SceneDev sc, FramePa
    while (refill_lanes<NA>(f, src, pool, t.cur == kEmptyRef, source_of, take)) {
       if (t.cur != kEmptyRef) {
          bool occluded = false;
-         if (trav_step<true, COUNT>(nodes, tris, t, lds_col, spill, occluded, n_nodes, n_tris) && !occluded) {
+         const bool ended = trav_step<true, COUNT>(nodes, tris, t, lds_col, spill, occluded, n_nodes, n_tris);
+         if constexpr (FINAL) {
+            if (ended) {
+               const float4 thr = ld_rec(rec_quad(rec, seg + id, REC_THR));
+               float4 r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+               if (rad_stored(fp, bounce + 1)) r = ld_rad<true>(rec, seg + id, thr);
+               if (!occluded) r = shadow_lit<false>(thr, r);  // rgen:69-78
+               st_stream(ps.radf + path_id, make_float4(r.x, r.y, r.z, 0.0f));
+            }
+         } else if (ended && !occluded) {
             if constexpr (VERDICT)
                atomicOr(sun_lit_word(ps, seg + id), 1ull << (id & 63u));  // no-return: nothing waits for it
             else
@@ -183,7 +198,10 @@ __global__ __launch_bounds__(kBlock, 5) void k_trace_shadow(SceneDev sc, FramePa
 // k_shade_hit ask the coarse cover and list the rays it did not answer - level on the frame - and a one-ray-per-lane loop for the plain
 // lists: both removed in round 5.)
 // VERDICT: the kernel leaves one bit per ray (lit or not) instead of adding the lit rays' throughput to their radiance - see sun_lit_word
-template <bool COUNT, bool INLINE, bool VERDICT>
+// FINAL (with VERDICT; the last bounce of a pass with FrameParams::slim_state): no verdict either - the kernel stands at the surviving
+// paths' positions with the verdict in hand, so every ray it does not defer stores its path's final radiance, radf[id] = radiance
+// (+ throughput if lit) with the slim state's id, throughput | radiance.r and pair: what k_flush_survivors would have read and stored
+template <bool COUNT, bool INLINE, bool VERDICT, bool FINAL = false>
 __global__ __launch_bounds__(kBlock) void k_trace_sun_grid(SceneDev sc, FrameParams fp, PathState ps, Control* ctl, DeviceStats* stats, uint32_t bounce,
                                                             uint32_t cursor_slot, SunGridDev g) {
    const uint32_t lane = lane_id();
@@ -347,7 +365,26 @@ __global__ __launch_bounds__(kBlock) void k_trace_sun_grid(SceneDev sc, FramePar
             lit[k] = !occluded;
          }
       });
-      if constexpr (VERDICT) {
+      if constexpr (FINAL) {
+         static_assert(VERDICT, "the final form replaces the verdict");
+         const bool stored = rad_stored(fp, bounce + 1);
+         float4 thr[K], rad[K];
+         static_for<K>([&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            rad[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (valid[k] && !defer[k]) {
+               thr[k] = ld_rec(rec_quad(rec, seg + id[k], REC_THR));
+               if (stored) rad[k] = ld_rad<true>(rec, seg + id[k], thr[k]);
+            }
+         });
+         static_for<K>([&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            if (valid[k] && !defer[k]) {
+               if (lit[k]) rad[k] = shadow_lit<false>(thr[k], rad[k]);  // rgen:69-78: radiance += throughput
+               st_stream(ps.radf + __float_as_uint(ro[k].w), make_float4(rad[k].x, rad[k].y, rad[k].z, 0.0f));
+            }
+         });
+      } else if constexpr (VERDICT) {
          // lane l of sub-chunk k holds position base + 64 k + l (the cursor starts at 0 and moves by 64 K; segments start at multiples
          // of 64): the ballot is that run's verdict word. Deferred rays and lanes beyond the count contribute 0 - the leftover kernel
          // sets the bits of the deferred rays it finds lit. Every word below the count is stored, so the plane needs no clearing.
@@ -543,7 +580,7 @@ __global__ __launch_bounds__(kBlock) void k_generate(FrameParams fp, PathState p
          float jx = random_float(rng), jy = random_float(rng);                                  // rgen:31
          V3 o, d;
          primary_ray(fp, px, py, jx, jy, o, d);
-         s_o = make_float4(o.x, o.y, o.z, __uint_as_float(rng));
+         s_o = make_float4(o.x, o.y, o.z, __uint_as_float(fp.slim_state ? id : rng));  // (slim state: the path id rides with the origin in every set)
          s_d = make_float4(d.x, d.y, d.z, __uint_as_float(seed));
          // radiance = 0 / pixelColor = 0 (rgen:26,40) are not materialised: the bounce-0 shading kernels and the first
          // finish_sample use the constants directly
@@ -580,6 +617,8 @@ __global__ __launch_bounds__(kBlock) void k_generate(FrameParams fp, PathState p
 // The bounce's misses arrive as a queue of their own (Q_MISS), written by k_shade_hit while it classifies the bounce's RAY
 // queue: every lane has a path, no hit record is read here, and nothing but the sky integral (~600 VALU instructions per
 // path) and four 16-byte records per path is left in the kernel. The position's top bit is the path's sun verdict (kSunLitBit).
+// SLIM (FrameParams::slim_state): behind bounce 0 the entry's id word is not one - the id is in the origin quad (shade_miss_path)
+template <bool SLIM>
 __global__ __launch_bounds__(kBlock) void k_shade_miss(FrameParams fp, PathState ps, Control* ctl, DeviceStats* stats, uint32_t bounce) {
    const ShardCtx sx = shard_ctx();
    const uint32_t seg = sx.shard * ps.shard_cap;
@@ -587,7 +626,7 @@ __global__ __launch_bounds__(kBlock) void k_shade_miss(FrameParams fp, PathState
    const uint32_t count = ctl->q_count[qc_index(bounce, Q_MISS, sx.shard)];
    for (uint32_t i = sx.lb * kBlock + threadIdx.x; i < count; i += sx.nb * kBlock) {
       const uint2 e = ld_stream(queue + i);
-      shade_miss_path(fp, ps, seg + (e.x & ~kSunLitBit), e.y, bounce, (e.x & kSunLitBit) != 0u);
+      shade_miss_path<SLIM>(fp, ps, seg + (e.x & ~kSunLitBit), e.y, bounce, (e.x & kSunLitBit) != 0u);
    }
    if (sx.lb == 0 && threadIdx.x == 0 && count) atomicAdd(&stats->misses, (unsigned long long)count);
 }
@@ -595,6 +634,10 @@ __global__ __launch_bounds__(kBlock) void k_shade_miss(FrameParams fp, PathState
 // ------------------------------------------------------------------------------------------
 // shade_hit — reference.rchit:20-92 + rgen:48-61 and the light-sample selection of rgen:81-110
 // ------------------------------------------------------------------------------------------
+// SLIM (FrameParams::slim_state; device_types.h PathState): the path id arrives with the origin quad and leaves with it - behind bounce 0
+// no id is loaded from queue[b & 1], and none is appended to the next queue at any bounce: the queue is its count, the state planes by
+// position are its content. Radiance: r beside the throughput, (g, b) as a pair. No light sample (the pass has no lights).
+template <bool SLIM>
 __global__ __launch_bounds__(kBlock, kShadeHitBlocks) void k_shade_hit(FrameParams fp, SceneDev sc, PathState ps, Control* ctl, DeviceStats* stats, uint32_t bounce) {
    // c / 255.0f table in LDS: the 12 per-fetch table gathers were texture-addresser traffic (the
    // kernel ran 86 % TA-busy at 2 % VALU, profiles/r01c_*); LDS serves them at no TA cost
@@ -653,8 +696,12 @@ __global__ __launch_bounds__(kBlock, kShadeHitBlocks) void k_shade_hit(FramePara
             thr4 = ld_rec(rec_quad(cur, seg + pos, REC_THR));
          }
          uint2 rng = make_uint2(__float_as_uint(ro.w), __float_as_uint(rd.w));
+         if constexpr (SLIM) {
+            if (bounce != 0) id = rng.x;  // the origin's w is the path id (at bounce 0 the id came from queue[0])
+            rng.x = 0u;                   // (no raygen RNG word in the slim state: nothing of such a pass reads one)
+         }
          float4 rad4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // radiance so far: zero before the first bounce (not materialised)
-         if (rad_stored(fp, bounce)) rad4 = ld_rec(rec_quad(cur, seg + pos, REC_RAD));  // (the compiler waits for it on the spot: measured level with an unconditional read, which costs 16 bytes per hit at bounce 0)
+         if (rad_stored(fp, bounce)) rad4 = ld_rad<SLIM>(cur, seg + pos, thr4);  // (the compiler waits for it on the spot: measured level with an unconditional read, which costs 16 bytes per hit at bounce 0)
          const V3 ray_dir = v3(rd.x, rd.y, rd.z);
          const float t = hr.x, bu = hr.y, bv = hr.z;
          const float4* sp = sc.shade + 4 * (size_t)pk;  // pk = hr.w, known since the classification: no wait for hr before these
@@ -705,24 +752,29 @@ __global__ __launch_bounds__(kBlock, kShadeHitBlocks) void k_shade_hit(FramePara
          } else {
             float f = 0.0f;
             int light_index = 0;
-            if (fp.lights_enabled == 1) want_light = select_light(fp, sc, id, rng.x, origin, f, light_index);  // rgen:81-121
+            if constexpr (!SLIM)
+               if (fp.lights_enabled == 1) want_light = select_light(fp, sc, id, rng.x, origin, f, light_index);  // rgen:81-121
             // the path's state for the next bounce; written below at the position the path gets in the next bounce's queue
-            n_o = make_float4(origin.x, origin.y, origin.z, __uint_as_float(rng.x));
+            n_o = make_float4(origin.x, origin.y, origin.z, __uint_as_float(SLIM ? id : rng.x));
             n_d = make_float4(scatter.x, scatter.y, scatter.z, __uint_as_float(rng.y));  // rgen:61
-            n_t = make_float4(thr.x, thr.y, thr.z, f);
+            n_t = make_float4(thr.x, thr.y, thr.z, SLIM ? rad4.x : f);
             n_r = make_float4(rad4.x, rad4.y, rad4.z, __uint_as_float((uint32_t)light_index));  // the radiance travels with the path
          }
       }
       // a wave's scattered paths get consecutive positions: their new state leaves as contiguous stores, and the next bounce's
       // traversal, sun-ray and shading kernels read it back as streams
       // the light queue: one round trip - none at all when no lane has an entry
-      const uint32_t lslot = wave_append(n_light, want_light);
+      uint32_t lslot = 0;
+      if constexpr (!SLIM) lslot = wave_append(n_light, want_light);
       if (scattered) {
-         st_stream(q_next + slot, id);
+         if constexpr (!SLIM) st_stream(q_next + slot, id);
          st_rec(rec_quad(nxt, seg + slot, REC_ORIGIN), n_o);
          if (bounce + 1 < fp.num_bounces) st_rec(rec_quad(nxt, seg + slot, REC_DIR), n_d);  // (after the last bounce no ray is traced: k_flush_survivors reads radiance and the raygen RNG word)
-         st_rec(rec_quad(nxt, seg + slot, REC_THR), n_t);
-         if (rad_stored(fp, bounce + 1)) st_rec(rec_quad(nxt, seg + slot, REC_RAD), n_r);
+         st_rec(rec_quad(nxt, seg + slot, REC_THR), n_t);  // (SLIM: w = radiance.r - a zero nobody reads where the radiance is not materialised)
+         if (rad_stored(fp, bounce + 1)) {
+            if constexpr (SLIM) st_rad_pair(nxt, seg + slot, n_r.y, n_r.z);
+            else st_rec(rec_quad(nxt, seg + slot, REC_RAD), n_r);
+         }
       }
       if (want_light) st_stream(q_light + lslot, slot);  // the light ray leaves from the path's new position
    };
@@ -748,7 +800,7 @@ __global__ __launch_bounds__(kBlock, kShadeHitBlocks) void k_shade_hit(FramePara
       uint32_t id = 0;
       float4 hr = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kEmptyRef));
       if (i < count) {
-         id = ld_stream(queue + i);
+         if (!SLIM || bounce == 0) id = ld_stream(queue + i);  // (SLIM behind bounce 0: the id comes with the origin quad; the lists' id words are unused)
          // the whole record (one 16-byte lane load, as the packet index alone would be): shade() does not read it again. The
          // traversal kernel left it at the ray's queue position: the wave reads 1 KiB in one piece
          hr = ld_rec(ps.hit + seg + i);
@@ -789,7 +841,7 @@ __global__ __launch_bounds__(kBlock, kShadeHitBlocks) void k_shade_hit(FramePara
       if (mask == 0ull) continue;
       const uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
       if (is_hit) {
-         list[0][n_list + prefix] = id;
+         if (!SLIM || bounce == 0) list[0][n_list + prefix] = id;
          list[1][n_list + prefix] = i_lit;
          list[2][n_list + prefix] = __float_as_uint(hr.x);
          list[3][n_list + prefix] = __float_as_uint(hr.y);
@@ -827,6 +879,7 @@ __global__ __launch_bounds__(kBlock, kShadeHitBlocks) void k_shade_hit(FramePara
 // last bounce's shadow rays added - and their raygen RNG word go to the per-id array k_finish_sample and the next sample's
 // k_generate read (rgen:127, :28-31). Dense reads by queue position, one 16-byte store per surviving path. With sun verdicts the
 // last bounce's sun term is added here: one word per wave, and the throughput of the lit survivors.
+// (Not launched for a pass with the slim state: the FINAL sun kernels of its last bounce store these records themselves.)
 __global__ __launch_bounds__(kBlock) void k_flush_survivors(FrameParams fp, PathState ps, Control* ctl) {
    const ShardCtx sx = shard_ctx();
    const uint32_t seg = sx.shard * ps.shard_cap, b = fp.num_bounces;
@@ -970,13 +1023,16 @@ void launch_shade_miss(const LaunchCfg& c, const FrameParams& fp, const PathStat
    // the bounce's misses are a dense queue (Q_MISS, written by k_shade_hit): every lane shades one; the count is on the
    // device, so the grid is sized for the paths the wavefront started with
    const dim3 full = shade_grid(c, fp.n_owned * fp.batch_frames), lean = sharded_grid(c.num_cus * 8);  // blocks per CU 2 / 4 / 6 / 8: 7,599 / 7,613-7,656 / 7,699 / 7,676-7,678 Mrays/s (round 4)
-   k_shade_miss<<<full.x < lean.x ? full : lean, kBlock, 0, c.stream>>>(fp, ps, ctl, stats, bounce);
+   as_constant(fp.slim_state != 0, [&](auto slim) { k_shade_miss<decltype(slim)::value><<<full.x < lean.x ? full : lean, kBlock, 0, c.stream>>>(fp, ps, ctl, stats, bounce); });
 }
 
 void launch_shade_hit(const LaunchCfg& c, const FrameParams& fp, const SceneDev& sc, const PathState& ps, const Images& im, Control* ctl,
                       DeviceStats* stats, uint32_t bounce) {
-   k_shade_hit<<<shade_grid(c, fp.W * fp.H), kBlock, 0, c.stream>>>(fp, sc, ps, ctl, stats, bounce);
+   as_constant(fp.slim_state != 0, [&](auto slim) { k_shade_hit<decltype(slim)::value><<<shade_grid(c, fp.W * fp.H), kBlock, 0, c.stream>>>(fp, sc, ps, ctl, stats, bounce); });
 }
+// the sun rays of this bounce are the last of a pass with the slim state: they store the surviving paths' radiance themselves
+static bool final_sun_rays(const FrameParams& fp, uint32_t bounce) { return fp.slim_state != 0 && bounce + 1 == fp.num_bounces; }
+
 void launch_flush_survivors(const LaunchCfg& c, const FrameParams& fp, const PathState& ps, Control* ctl) {
    k_flush_survivors<<<shade_grid(c, fp.n_owned * fp.batch_frames), kBlock, 0, c.stream>>>(fp, ps, ctl);
 }
@@ -985,13 +1041,14 @@ void launch_trace_shadow(const LaunchCfg& c, const FrameParams& fp, const SceneD
                          uint32_t bounce, uint32_t cursor_slot, bool light, bool sun_leftovers) {
    // sun_leftovers: what the sun grid handed to the tree (queue 3); behind a grid kernel that left verdicts they set their bits
    as_constant(c.count_visits, [&](auto count) {
-      auto go = [&](auto is_light, auto verdict) {
-         k_trace_shadow<decltype(count)::value, decltype(is_light)::value, decltype(verdict)::value><<<shadow_grid(c), kBlock, 0, c.stream>>>(
+      auto go = [&](auto is_light, auto verdict, auto final) {
+         k_trace_shadow<decltype(count)::value, decltype(is_light)::value, decltype(verdict)::value, decltype(final)::value><<<shadow_grid(c), kBlock, 0, c.stream>>>(
             sc, fp, ps, ctl, stats, bounce, cursor_slot, sun_leftovers);
       };
-      if (light) go(std::true_type{}, std::false_type{});
-      else if (sun_leftovers && fp.sun_verdicts) go(std::false_type{}, std::true_type{});
-      else go(std::false_type{}, std::false_type{});
+      if (light) go(std::true_type{}, std::false_type{}, std::false_type{});
+      else if (sun_leftovers && final_sun_rays(fp, bounce)) go(std::false_type{}, std::true_type{}, std::true_type{});
+      else if (sun_leftovers && fp.sun_verdicts) go(std::false_type{}, std::true_type{}, std::false_type{});
+      else go(std::false_type{}, std::false_type{}, std::false_type{});
    });
 }
 
@@ -1000,10 +1057,13 @@ void launch_trace_sun_grid(const LaunchCfg& c, const FrameParams& fp, const Scen
    const dim3 grid = sharded_grid(c.num_cus * 8);
    as_constant(c.count_visits, [&](auto count) {
       as_constant(g.recs != nullptr, [&](auto inl) {
-         as_constant(fp.sun_verdicts != 0, [&](auto verdict) {
-            k_trace_sun_grid<decltype(count)::value, decltype(inl)::value, decltype(verdict)::value><<<grid, kBlock, 0, c.stream>>>(
+         auto go = [&](auto verdict, auto final) {
+            k_trace_sun_grid<decltype(count)::value, decltype(inl)::value, decltype(verdict)::value, decltype(final)::value><<<grid, kBlock, 0, c.stream>>>(
                sc, fp, ps, ctl, stats, bounce, cursor_slot, g);
-         });
+         };
+         if (final_sun_rays(fp, bounce)) go(std::true_type{}, std::true_type{});
+         else if (fp.sun_verdicts != 0) go(std::true_type{}, std::false_type{});
+         else go(std::false_type{}, std::false_type{});
       });
    });
 }

@@ -51,10 +51,28 @@ __device__ __forceinline__ unsigned long long* sun_lit_word(const PathState& ps,
 // 0.0f and add the lit paths' throughput, the very words the stored zero would have given.
 __device__ __forceinline__ bool rad_stored(const FrameParams& fp, uint32_t b) { return b > fp.sun_verdicts; }
 constexpr uint32_t kSunLitBit = 0x80000000u;  // the verdict beside a queue position (k_shade_hit's lists, Q_MISS): positions stay below 2^31
+// A stored radiance as (r, g, b, 0 or the light index). SLIM (FrameParams::slim_state): r came with the throughput quad `thr` the caller
+// holds, (g, b) is the pair of plane 3; otherwise plane 3's quad. pos: the queue position with its shard segment.
+typedef float v2f_t __attribute__((ext_vector_type(2)));
+template <bool SLIM>
+__device__ __forceinline__ float4 ld_rad(const PathRecs& rec, uint32_t pos, float4 thr) {
+   if constexpr (SLIM) {
+      const v2f_t gb = __builtin_nontemporal_load(reinterpret_cast<const v2f_t*>(rec_pair(rec, pos)));
+      return make_float4(thr.w, gb.x, gb.y, 0.0f);
+   } else
+      return ld_rec(rec_quad(rec, pos, REC_RAD));
+}
+__device__ __forceinline__ void st_rad_pair(const PathRecs& rec, uint32_t pos, float g, float b) {
+   const v2f_t gb = {g, b};
+   __builtin_nontemporal_store(gb, reinterpret_cast<v2f_t*>(rec_pair(rec, pos)));
+}
 
 // pos: the path's position in the bounce's ray queue (shard segment included), id: its path id. The path ends here: its radiance
 // goes to the per-id array, with the raygen's RNG word (the frame's next sample starts from it, rgen:28-31).
 // sun_lit: the verdict of the sun ray the path cast when it scattered, not yet added to its radiance (FrameParams::sun_verdicts)
+// SLIM (FrameParams::slim_state): behind bounce 0 the id is the origin quad's w, not `id`; throughput | radiance.r and the (g, b) pair;
+// the per-id record's w (the raygen RNG word, which only a second sample of the frame would read) is zero
+template <bool SLIM = false>
 __device__ __forceinline__ void shade_miss_path(const FrameParams& fp, const PathState& ps, uint32_t pos, uint32_t id, uint32_t bounce, bool sun_lit) {
    const PathRecs rec = ps.set[bounce & 1];
    const bool implicit = bounce == 0 && fp.primary_implicit;  // origin and throughput of a primary ray: not stored (FrameParams)
@@ -63,6 +81,10 @@ __device__ __forceinline__ void shade_miss_path(const FrameParams& fp, const Pat
       primary_state(fp, id, ro, rd_implicit);
    else
       ro = ld_rec(rec_quad(rec, pos, REC_ORIGIN));
+   if constexpr (SLIM) {
+      if (bounce != 0) id = __float_as_uint(ro.w);
+      ro.w = 0.0f;
+   }
    V3 sky_color = v3(0.0f, 0.0f, 0.0f);
    if (fp.furnace) {
       sky_color = v3(1.0f, 1.0f, 1.0f);  // rmiss:12 with FURNACE_TEST defined: the #ifndef block (rmiss:14-28) is compiled out
@@ -74,7 +96,7 @@ __device__ __forceinline__ void shade_miss_path(const FrameParams& fp, const Pat
    float4 thr = make_float4(1.0f, 1.0f, 1.0f, 0.0f);  // rgen:39
    if (!implicit) thr = ld_rec(rec_quad(rec, pos, REC_THR));
    float4 rad = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-   if (rad_stored(fp, bounce)) rad = ld_rec(rec_quad(rec, pos, REC_RAD));
+   if (rad_stored(fp, bounce)) rad = ld_rad<SLIM>(rec, pos, thr);
    if (sun_lit) rad = shadow_lit<false>(thr, rad);                           // rgen:69-78, of the bounce before
    V3 t = v3(thr.x, thr.y, thr.z) * sky_color;                               // rgen:48
    st_stream(ps.radf + id, make_float4(rad.x + t.x, rad.y + t.y, rad.z + t.z, ro.w));   // rgen:55

@@ -20,7 +20,8 @@ def base_name(k):
     """kernel name without its template arguments: the variants of one kernel share a profile entry - except the shadow walk of the LIGHT rays
     (k_trace_shadow<COUNT, true>), which is a kernel of its own weight in config 2 (bench.py's roofline names it k_trace_shadow_light)"""
     b = k.split("<")[0].strip()
-    if b == "k_trace_shadow" and "<" in k and k.split("<")[1].split(">")[0].split(",")[-1].strip() in ("true", "1"):
+    args = k.split("<")[1].split(">")[0].split(",") if "<" in k else []
+    if b == "k_trace_shadow" and len(args) >= 2 and args[1].strip() in ("true", "1"):  # <COUNT, LIGHT, VERDICT, FINAL>
         return "k_trace_shadow_light"
     return b
 
