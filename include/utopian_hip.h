@@ -244,16 +244,17 @@ typedef struct uh_ctx uh_ctx;
  *        triangle total, 8 bytes, back to size its buffers), uh_get_isosurface_update_stats, uh_update_mesh_vertices (device input:
  *        it reads a 4-byte verdict on the caller's buffer back before it takes it), uh_get_mesh_update_stats, uh_read_denoised,
  *        uh_get_denoise_stats, uh_reset_denoise_history, uh_get_rtao_stats, uh_get_rtao_visits, uh_get_motion_stats, uh_reset_taa_history,
- *        uh_get_taa_stats, uh_post_image, uh_read_post, uh_get_post_stats, uh_destroy;
+ *        uh_get_taa_stats, uh_post_image, uh_read_post, uh_get_post_stats, uh_get_rtgi_stats, uh_destroy;
  *   enqueues like a frame, ordered behind the frames in flight and before those that follow:  uh_rccl_gather_tiles, uh_mgpu_compose;
  *        uh_set_option for "frames_in_flight" and for "time_kernels" 1 -> 0 (the others only change what the NEXT enqueued
  *        frame does: "furnace", "sun_grid*", "camera_grid*", "overlap", "batch_frames", "trace_blocks_per_cu", "count_visits",
- *        "full_frame_restir", "primary_implicit", "rtao_order"; "device_build", "ploc_sah_top" invalidate the tree: the next frame
+ *        "full_frame_restir", "primary_implicit", "rtao_order", "rtgi_order"; "device_build", "ploc_sah_top" invalidate the tree: the next frame
  *        needs uh_build_acceleration, which waits);
  *   host state only (no device access, nothing to wait for):  uh_add_mesh, uh_add_light, uh_set_instance_transform,
  *        uh_get_num_lights, uh_mesh_info, uh_read_mesh, uh_get_restir_rows, uh_tile_pack_count, uh_set_rtao_params, uh_set_taa_params,
- *        uh_set_post_params, uh_reset_post_exposure (read by the next uh_render_hybrid; the post pair also by the next uh_post_image),
- *        uh_taa_default_params, uh_taa_jitter, uh_post_default_params, uh_post_level_size, uh_last_error
+ *        uh_set_post_params, uh_reset_post_exposure, uh_set_rtgi_params (read by the next uh_render_hybrid; the post pair also by the
+ *        next uh_post_image), uh_taa_default_params, uh_taa_jitter, uh_post_default_params, uh_post_level_size, uh_rtgi_default_params,
+ *        uh_last_error
  *        (uh_read_mesh of a mesh that uh_update_isosurface_mesh has made device-resident, or that uh_update_mesh_vertices last updated
  *        from a device pointer, copies it from the device: a blocking copy);
  *   uh_add_texture_rgba8 uploads into a fresh allocation no frame in flight can reference (textures enter a frame's tables at the
@@ -648,7 +649,7 @@ int uh_mgpu_set_option(uh_mgpu* group, const char* name, int value);
  * UH_HYBRID_RT_REFLECTIONS with view->ibl_enabled == 1 is UH_ERR_INVALID_ARGUMENT - and nothing runs - until the IBL maps (irradiance,
  * specular, BRDF LUT of ibl.rs) have been built with UH_HYBRID_ENVIRONMENT, below; mask bits, UH_ERR_NOT_BUILT and moved instances with
  * view->rebuild_tlas as for uh_render_frame (bits above UH_HYBRID_SHADOW_MAPS, below, are ignored, except UH_HYBRID_MARCHING_CUBES,
- * UH_HYBRID_GBUFFER_RASTER, UH_HYBRID_RESTIR_LIGHTS, UH_HYBRID_RTAO, UH_HYBRID_MOTION, UH_HYBRID_TAA and UH_HYBRID_POST).
+ * UH_HYBRID_GBUFFER_RASTER, UH_HYBRID_RESTIR_LIGHTS, UH_HYBRID_RTAO, UH_HYBRID_MOTION, UH_HYBRID_TAA, UH_HYBRID_POST and UH_HYBRID_RTGI).
  * STREAM ORDER: uh_render_hybrid enqueues like a frame (behind the frames in flight, ahead of those that follow); uh_read_hybrid and
  * uh_get_hybrid_stats wait for all work of the context and are complete on return. The exception is UH_HYBRID_SHADOW_MAPS, below: a
  * call that renders shadow maps BLOCKS the host until the frames in flight and the pass's binning have finished (it reads the
@@ -1377,6 +1378,82 @@ int uh_post_image(uh_ctx*, const float* rgba32f);       /* W*H*4 floats on the h
 int uh_read_post(uh_ctx*, int which, int level, void* out);   /* waits */
 /* needs no GPU: the size of bloom level `level` (0: the frame) of a W x H frame; UH_ERR_INVALID_ARGUMENT for one that does not exist */
 int uh_post_level_size(uint32_t W, uint32_t H, uint32_t level, uint32_t* w, uint32_t* h);
+
+/* ---- one-bounce ray-traced diffuse GI for the hybrid frame: the light that arrives by way of another surface ---------------------------
+ * An EXTENSION: the reference has no GI at all; the hybrid frame's whole indirect term is deferred.frag's 0.03 * diffuse * occlusion (or
+ * the IBL lookup), which knows nothing of the scene's own geometry. UH_HYBRID_RTGI (bit 17; bit 9 stays unused and ignored) adds one pass
+ * to uh_render_hybrid directly AFTER the deferred pass and BEFORE the marching-cubes, sky, taa and post passes, so TAA - which integrates
+ * the per-frame ray noise over time - and the display chain see it. UH_HYBRID_FRAME | UH_HYBRID_RTGI is the natural call. The deferred
+ * pass itself is untouched and the reference's 0.03 ambient STAYS in it: this pass adds to deferred_output, it replaces nothing.
+ *   rays      RTAO's rule says which pixels cast: position texel w != 0 and a normal texel N that normalises to a finite Nn. Such a pixel
+ *             (px, py) casts `samples` rays from offsetRay(P, Nn) of its OWN texels. Ray s has direction normalize(Nn + normalize(u)), u =
+ *             randomPointInUnitSphere of the state initRNG(px, py, W, (frameNumber(view) * 64 + s) ^ 0x52544749) - the XOR keeps the rays
+ *             from being RTAO's own; Nn itself where |Nn + normalize(u)|^2 is not >= 1e-12. tmin 0.001, tmax 10000, closest hit.
+ *   radiance  L of a ray. A miss: IntegrateScattering(o, d, 999999999, sun) as rt_reflections.rmiss forms it, unclamped; (1, 1, 1) under
+ *             option "furnace". A hit on material type 3: the emission the path tracer's closest-hit shader gives it, (1, 1, 1)
+ *             (reference.rchit:85-89); no sun ray. Any other hit: albedo = texture(diffuse_map, uv) * base_color (rchit:41-42), Nh the
+ *             hit's world normal turned toward the ray (rchit:32-37), X = o + t d, NdotL = max(dot(Nh, sun), 0). NdotL == 0 (or NaN):
+ *             the hit is DARK, L = 0, no sun ray. Otherwise one any-hit ray from offsetRay(X, Nh) toward sun (0.001, 10000): occluded
+ *             DARK, L = 0; else SUNLIT, L = ((albedo / PI) * rad_sun) * NdotL with PI of brdf.glsl and rad_sun the radiance of the
+ *             deferred pass's light record 0 (the sun: colour (1, 1, 1), attenuation 1). Under "furnace" a non-emitter hit is dark and
+ *             casts no sun ray. Then per channel L = min(L > 0 ? L : 0, max_radiance): a NaN is 0, L is always finite.
+ *   pixel     E = (L_0 + L_1 + ... + L_{samples-1}) / (float)samples, summed in sample order: it does not depend on the schedule.
+ *   filter    blur_radius 0: Ef = E. r > 0: the mean of E over the taps (dx, dy) in [-r, r]^2 (dy outer) that lie in the frame, cast
+ *             themselves and pass dot(Nn_tap, Nn) >= blur_normal_cos and |dot(P_tap - P, Nn)| <= blur_plane; the centre always counts.
+ *   composite for every pixel that cast, with base = pow(albedo, 2.2) * base_color and metallic = pbr.r * material.metallic as
+ *             deferred.frag:52-65 forms them: add = ((base * (1 - metallic)) * Ef) * intensity, times the occlusion pbr.b, times (with
+ *             view->ssao_enabled == 1) the pixel's ssao_output texel / 65535; deferred_output.rgb += add, alpha untouched. A pixel whose
+ *             material is metal (type 1) with raytracing_supported == 1 is left as it is: the deferred pass replaced its colour with the
+ *             reflection. The shadow factor is NOT applied: indirect light is not sun-shadowed.
+ * PARAMS: uh_set_rtgi_params validates and keeps them for the calls that follow (a refused call leaves the old ones); before the
+ * first call the defaults of uh_rtgi_default_params hold: 2 samples, blur_radius 3, max_radiance 16.0, intensity 1.0, 0.9, 0.05.
+ * UH_ERR_INVALID_ARGUMENT with a message, and nothing runs, in this order after the rules above: the bit and
+ * view->raytracing_supported != 1; no G-buffer rendered in this call or an earlier one; the bit and view->ibl_enabled == 1 (the IBL
+ * ambient term and this pass would both count the sky); the bit without UH_HYBRID_DEFERRED in the same call (the pass has nothing to add
+ * to). UH_ERR_CAPACITY for a frame of 2^28 pixels or more (its rays are numbered in 32 bits). UH_ERR_NOT_BUILT before
+ * uh_build_acceleration, as without the bit.
+ * READ-BACK (uh_read_hybrid, UH_ERR_INVALID_ARGUMENT before the first rtgi pass; both in G-buffer orientation): UH_HYBRID_GI_RADIANCE,
+ * RGBA32F: Ef, w = 1 where the pixel cast, (0, 0, 0, 0) elsewhere. UH_HYBRID_GI_COUNTS, 4 bytes per pixel: the rays that hit a sunlit
+ * surface, a dark one, an emitter, and those that missed; they sum to `samples` where the pixel cast and are all 0 elsewhere.
+ * RESOURCES: 40 bytes per pixel (counts, radiance, the unfiltered means, the queue of the pixels that cast) and 32 bytes per ray (its
+ * radiance and its sun-ray record) at the largest `samples` a pass has run with, allocated by the first pass; freed by uh_destroy. A
+ * context that never sets the bit allocates nothing for it.
+ * STREAM ORDER: as uh_render_hybrid. uh_set_rtgi_params is host state, read by the next uh_render_hybrid; uh_get_rtgi_stats waits.
+ * ISOLATION: the bit changes no reservoir, accumulation, gbuffer_position, grid, UhStats or RTAO state, and no hybrid image but
+ * deferred_output (and what later passes of the call make of it) and its own two; its rays are counted in UhRtgiStats only, and
+ * UhHybridFrameStats keeps its layout and its times. Without the bit every pass, image, statistic and allocation is what it was.
+ * No uh_mgpu_ twin.
+ * OUT OF SCOPE: point, spot and reservoir lights at the hit; more than one bounce; specular GI; a history of its own (UH_HYBRID_TAA
+ * serves); the forward graph.
+ * Arithmetic: DESIGN.md section 2, "Ray-traced diffuse GI". */
+enum { UH_HYBRID_RTGI = 1u << 17 };
+enum { UH_HYBRID_GI_RADIANCE = 18 /* RGBA32F: Ef, w = 1 where the pixel cast */, UH_HYBRID_GI_COUNTS = 19 /* 4 x uint8: sunlit, dark, emitter, missed */ };
+typedef struct UhRtgiParams {
+   uint32_t samples;      /* rays per pixel that casts, 1..16 */
+   uint32_t blur_radius;  /* 0 = no filter; else 1..6: taps dx, dy in [-r, r] */
+   float max_radiance;    /* the cap of a ray's L per channel; finite, > 0 */
+   float intensity;       /* scales what the composite adds; finite, >= 0 */
+   float blur_normal_cos; /* a tap counts when dot(Nn_tap, Nn) >= this; not NaN */
+   float blur_plane;      /* and |dot(P_tap - P, Nn)| <= this (world units); not NaN */
+} UhRtgiParams;
+UH_LAYOUT_ASSERT(sizeof(UhRtgiParams) == 24 && offsetof(UhRtgiParams, blur_radius) == 4 && offsetof(UhRtgiParams, max_radiance) == 8 &&
+                    offsetof(UhRtgiParams, intensity) == 12 && offsetof(UhRtgiParams, blur_normal_cos) == 16 &&
+                    offsetof(UhRtgiParams, blur_plane) == 20,
+                 "UhRtgiParams (24 B)");
+/* the last rtgi pass: the pixels that cast, their rays (pixels * samples), the sun rays cast from the hits and the rays that missed, and
+ * the hipEvent times of classify + closest-hit walk, of the sun rays' any-hit walk, of the mean + filter and of the composite. All zero
+ * before the first pass. Waits for all work of the context. */
+typedef struct UhRtgiStats {
+   uint64_t pixels, rays, shadow_rays, misses;
+   float trace_ms, shadow_ms, filter_ms, composite_ms;
+} UhRtgiStats;
+UH_LAYOUT_ASSERT(sizeof(UhRtgiStats) == 48 && offsetof(UhRtgiStats, rays) == 8 && offsetof(UhRtgiStats, shadow_rays) == 16 &&
+                    offsetof(UhRtgiStats, misses) == 24 && offsetof(UhRtgiStats, trace_ms) == 32 && offsetof(UhRtgiStats, shadow_ms) == 36 &&
+                    offsetof(UhRtgiStats, filter_ms) == 40 && offsetof(UhRtgiStats, composite_ms) == 44,
+                 "UhRtgiStats (48 B)");
+int uh_rtgi_default_params(UhRtgiParams* out); /* needs no GPU: 2, 3, 16.0, 1.0, 0.9, 0.05; UH_ERR_INVALID_ARGUMENT for NULL */
+int uh_set_rtgi_params(uh_ctx* ctx, const UhRtgiParams* params); /* validated here; a refused call leaves the old ones */
+int uh_get_rtgi_stats(uh_ctx* ctx, UhRtgiStats* out);            /* waits; all zero before the first pass */
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,7 @@ from .api import (  # noqa: F401
     post_default_params,
     post_level_size,
     rtao_default_params,
+    rtgi_default_params,
     shadow_cascades,
     taa_default_params,
     taa_jitter,

@@ -39,6 +39,8 @@ from .types import (
     HYBRID_ALBEDO,
     HYBRID_ALL,
     HYBRID_AO_COUNTS,
+    HYBRID_GI_COUNTS,
+    HYBRID_GI_RADIANCE,
     HYBRID_DEFERRED_OUTPUT,
     HYBRID_DEPTH,
     HYBRID_GBUFFER_DEPTH,
@@ -86,6 +88,8 @@ from .types import (
     RestirRows,
     RtaoParams,
     RtaoStats,
+    RtgiParams,
+    RtgiStats,
     Stats,
     TaaParams,
     TaaStats,
@@ -545,6 +549,8 @@ class Renderer:
     # the two images of HYBRID_TAA, which exist once a render_hybrid call with the bit has succeeded on this renderer (_taa_rendered)
     _TAA_IMAGES = {HYBRID_TAA_OUTPUT: (np.float32, 4), HYBRID_TAA_HISTORY: (np.float32, 1)}
     _taa_rendered = False
+    # the two images of HYBRID_RTGI: the library refuses them before the first rtgi pass
+    _GI_IMAGES = {HYBRID_GI_RADIANCE: (np.float32, 4), HYBRID_GI_COUNTS: (np.uint8, 4)}
 
     def read_hybrid(self, which):
         """one image of the hybrid graph: (H, W, 4) float32 position / normal / pbr / deferred output, (H, W, 4) uint8 albedo / reflections /
@@ -552,11 +558,13 @@ class Renderer:
         marching-cubes draw index (MARCHING_CUBES_NONE where none survived), (H, W) float32 rasterised G-buffer depth, (H, W) uint32
         rasterised G-buffer draw index (GBUFFER_NONE where none survived), (H, W) uint8 light visibility of HYBRID_RESTIR_LIGHTS,
         (H, W) uint8 occluded-ray counts of HYBRID_RTAO, (H, W, 4) float32 motion image of HYBRID_MOTION (previous world position, w = 1
-        with a correspondence), and once a call with HYBRID_TAA has run (H, W, 4) float32 taa_output and (H, W) float32 history length"""
+        with a correspondence), once a call with HYBRID_TAA has run (H, W, 4) float32 taa_output and (H, W) float32 history length, and of
+        HYBRID_RTGI (H, W, 4) float32 filtered incoming radiance (w = 1 where the pixel cast) and (H, W, 4) uint8 ray counts (sunlit, dark,
+        emitter, missed)"""
         api = self._hybrid_api()
-        images = {**self._HYBRID_IMAGES, **(self._TAA_IMAGES if self._taa_rendered else {})}
+        images = {**self._HYBRID_IMAGES, **(self._TAA_IMAGES if self._taa_rendered else {}), **self._GI_IMAGES}
         if which not in images:
-            raise ValueError(f"hybrid image index {which} (0..15, and 16..17 once a render_hybrid call with HYBRID_TAA has run)")
+            raise ValueError(f"hybrid image index {which} (0..15, 18..19, and 16..17 once a render_hybrid call with HYBRID_TAA has run)")
         dtype, ch = images[which]
         out = np.empty((self.height, self.width, ch) if ch > 1 else (self.height, self.width), dtype=dtype)
         self._check(api.read_hybrid(self._ctx, int(which), out.ctypes.data))
@@ -646,6 +654,31 @@ class Renderer:
         """UhRtaoStats of the last rtao pass: pixels, rays, occluded, trace_ms, filter_ms"""
         s = RtaoStats()
         self._check(self._rtao_fn("get_rtao_stats", RtaoStats)(self._ctx, C.byref(s)))
+        return s
+
+    # -- one-bounce ray-traced diffuse GI (HYBRID_RTGI; include/utopian_hip.h "UH_HYBRID_RTGI") ---
+    def _rtgi_fn(self, name, arg):
+        if self.backend != "hip":
+            raise NotImplementedError(f"ray-traced diffuse GI is a per-context verb of the HIP library; backend {self.backend!r} has none")
+        fn = getattr(self._lib, "uh_" + name)
+        fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(arg)], C.c_int
+        return fn
+
+    def set_rtgi_params(self, params=None, **fields):
+        """uh_set_rtgi_params: `params` (an RtgiParams; the defaults when None) with `fields` set on a copy - the params of the
+        render_hybrid calls with HYBRID_RTGI that follow. A refused call raises and leaves the old ones."""
+        p = RtgiParams.from_buffer_copy(rtgi_default_params() if params is None else params)
+        for k, v in fields.items():
+            if not hasattr(p, k):
+                raise TypeError(f"RtgiParams has no field {k!r}")
+            setattr(p, k, v)
+        self._check(self._rtgi_fn("set_rtgi_params", RtgiParams)(self._ctx, C.byref(p)))
+        return p
+
+    def rtgi_stats(self):
+        """UhRtgiStats of the last rtgi pass: pixels, rays, shadow_rays, misses, trace_ms, shadow_ms, filter_ms, composite_ms"""
+        s = RtgiStats()
+        self._check(self._rtgi_fn("get_rtgi_stats", RtgiStats)(self._ctx, C.byref(s)))
         return s
 
     def rtao_visits(self):
@@ -1064,6 +1097,16 @@ class MultiGpuRenderer(Renderer):
 
     def compose(self):
         self._check(self._lib.uh_mgpu_compose(self._ctx))
+
+
+def rtgi_default_params():
+    """UhRtgiParams as uh_rtgi_default_params fills it (needs no GPU)"""
+    fn = load_library().uh_rtgi_default_params
+    fn.argtypes, fn.restype = [C.POINTER(RtgiParams)], C.c_int
+    p = RtgiParams()
+    if fn(C.byref(p)) != 0:
+        raise UtopianError("uh_rtgi_default_params failed")
+    return p
 
 
 def rtao_default_params():

@@ -1126,6 +1126,12 @@ int uh_set_option(uh_ctx* c, const char* name, int value) {
       if (!range(0, 2)) return bad("must be 0..2");
       c->hy.ao.order = (uint32_t)value;
    }
+   else if (n == "rtgi_order") {
+      // how the rtgi closest-hit kernel lays out its work (rtgi.hip; same images whichever): 0 (default) a pixel's samples together;
+      // 1 one sample of consecutive pixels together
+      if (!range(0, 1)) return bad("must be 0 or 1");
+      c->hy.gi.order = (uint32_t)value;
+   }
    else if (n == "texture_blocks")
       // 1: the textures added from now on are stored as overlapped blocks, a bilinear footprint in one cache line (texture_layout.h);
       // 0: as 8x8 tiles, or rows. Same images bit for bit: the same four texel words enter the filter

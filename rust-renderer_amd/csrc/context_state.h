@@ -555,6 +555,25 @@ struct uh_ctx {
          void destroy() { images(0, ReleaseBuf{}); }
       } ao;
 
+      // one-bounce ray-traced diffuse GI (UH_HYBRID_RTGI), allocated by the first pass: the count words, the radiance image, the
+      // unfiltered means, the queue of the pixels that cast and the pass's counters (pixels, sun rays, misses); rays and sun_rays (a
+      // record per ray each) are grown to the largest `samples` a pass has run with. params: the last uh_set_rtgi_params (the defaults
+      // before); samples: the last pass's. stage: trace, shadow, filter, composite of the last pass.
+      struct __attribute__((visibility("hidden"))) Rtgi {
+         DevBuf<uint32_t> counts, queue, counters;
+         DevBuf<float4> radiance, mean, rays, sun_rays;
+         UhRtgiParams params{2, 3, 16.0f, 1.0f, 0.9f, 0.05f};
+         Stage stage[4];
+         uint32_t renders = 0, samples = 0;
+         uint32_t order = 0;                   // option "rtgi_order" (rtgi.hip: how the trace kernel's work items are laid out)
+         template <class F> void images(size_t n, F&& f) { f(counts, n), f(radiance, n), f(mean, n), f(queue, n), f(counters, 4); }
+         void destroy() {
+            images(0, ReleaseBuf{});
+            rays.release(), sun_rays.release();
+            for (Stage& s : stage) s.destroy();
+         }
+      } gi;
+
       // motion vectors (UH_HYBRID_MOTION), allocated by the first call with the bit: the motion image, the pass's counts (pixels with /
       // without a correspondence, a pair per block of the kernel's grid, added up by uh_get_motion_stats), the per-mesh table the
       // kernels read, and the previous-position table (16-byte rows with bases of their own: isosurface meshes, which are never
@@ -629,7 +648,7 @@ struct uh_ctx {
 
       __attribute__((visibility("hidden"))) void destroy() {
          rt_images(0, ReleaseBuf{}), frame_images(0, ReleaseBuf{});
-         env.destroy(), sm.destroy(), gr.destroy(), mc.destroy(), rl.destroy(), ao.destroy(), mv.destroy(), taa.destroy(), post.destroy();
+         env.destroy(), sm.destroy(), gr.destroy(), mc.destroy(), rl.destroy(), ao.destroy(), gi.destroy(), mv.destroy(), taa.destroy(), post.destroy();
          meshes.release(), vertices.release(), indices.release(), raw_lights.release();
          for (hipEvent_t ev : waits)
             if (ev) (void)hipEventDestroy(ev);

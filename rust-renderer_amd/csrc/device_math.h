@@ -194,6 +194,67 @@ __device__ __noinline__ V3 integrate_scattering(V3 start, V3 dir, float ray_leng
    }
    return (rayleigh * C_RAYLEIGH() + mie * C_MIE()) * v3(1, 1, 1) * 20.0f;
 }
+
+// The same integral with EXACT HEIGHTS, for the rtgi pass (rtgi.hip). A height is the difference of two float32 numbers near 6.4e6, where
+// an ulp is half a metre: where the 1-ulp hardware root above lands an ulp off, the Mie density (scale height 1,200 m) of that sample
+// moves by 4e-4. Over a frame's sky pixels that stays inside the sky's tolerance; a single ray next to the sun, where the Mie term
+// carries the result, was measured 1.1e-4 off the oracle's. Here the root is sqrtf, correctly rounded; every other operation is the
+// one above. A copy, not a shared template: with the body shared the compiler scheduled the existing kernels' integral differently; as
+// it is, their device code is instruction for instruction what it was.
+__device__ __forceinline__ float atmosphere_height_exact(V3 p) {
+   V3 q = p - PLANET_CENTER();
+   return sqrtf(dot3(q, q)) - PLANET_RADIUS;
+}
+__device__ __forceinline__ V3 integrate_optical_depth_exact_heights(V3 start, V3 dir) {  // :123-143
+   float t0, t1;
+   atmosphere_intersection(start, dir, t0, t1);
+   float step = t1 / 8.0f;
+   V3 od = v3(0, 0, 0);
+#pragma unroll 2
+   for (int i = 0; i < 8; i++) {
+      V3 p = start + dir * ((float)i + 0.5f) * step;
+      od = od + atmosphere_density(atmosphere_height_exact(p)) * step;
+   }
+   return od;
+}
+__device__ __noinline__ V3 integrate_scattering_exact_heights(V3 start, V3 dir, float ray_length, V3 light_dir) {  // :154-214 (lightColor = 1)
+   float ray_height = atmosphere_height_exact(start);
+   float c = 1.0f - ray_height * (1.0f / ATMOSPHERE_HEIGHT);
+   c = fminf(fmaxf(c, 0.0f), 1.0f);
+   float exponent = 1.0f + c * 8.0f;
+   float i0, i1;
+   atmosphere_intersection(start, dir, i0, i1);
+   ray_length = fminf(ray_length, i1);
+   if (i0 > 0) {
+      start = start + dir * i0;
+      ray_length -= i0;
+   }
+   float costh = dot3(dir, light_dir);
+   float phaseR = 3.0f * (1.0f + costh * costh) / (16.0f * PI);
+   float g = fminf(0.85f, 0.9381f);
+   float k = 1.55f * g - 0.55f * g * g * g;
+   float kcosth = k * costh;
+   float phaseM = (1.0f - k * k) / ((4.0f * PI) * (1.0f - kcosth) * (1.0f - kcosth));
+   V3 od = v3(0, 0, 0), rayleigh = v3(0, 0, 0), mie = v3(0, 0, 0);
+   float prev = 0.0f;
+   // log2(i / 16), i = 1..15: pow(i / 16, exponent) = exp2(exponent * log2(i / 16)) - one transcendental instead of two (i = 0: 0)
+   const float kLog2[16] = {0.0f,          -4.0f,         -3.0f,          -2.4150374993f, -2.0f,          -1.6780719051f, -1.4150374993f, -1.1926450779f,
+                            -1.0f,         -0.8300749986f, -0.6780719051f, -0.5405683814f, -0.4150374993f, -0.2995602819f, -0.1926450779f, -0.0931094044f};
+   for (int i = 0; i < 16; i++) {
+      float ray_time = i == 0 ? 0.0f : __builtin_amdgcn_exp2f(exponent * kLog2[i]) * ray_length;
+      float step = ray_time - prev;
+      V3 p = start + dir * ray_time;
+      V3 dens = atmosphere_density(atmosphere_height_exact(p));
+      od = od + dens * step;
+      // viewTransmittance * lightTransmittance (atmosphere.glsl:203-206) = absorb(od_view) * absorb(od_light) = absorb(od_view + od_light):
+      // absorb is exp of a linear form - three exponentials per step instead of six (the sky is compared with a tolerance, see above)
+      V3 both_t = absorb(od + integrate_optical_depth_exact_heights(p, light_dir));
+      rayleigh = rayleigh + both_t * phaseR * dens.x * step;
+      mie = mie + both_t * phaseM * dens.y * step;
+      prev = ray_time;
+   }
+   return (rayleigh * C_RAYLEIGH() + mie * C_MIE()) * v3(1, 1, 1) * 20.0f;
+}
 }  // namespace sky
 
 // ---- explicit LDS reads of whole records ------------------------------------------------------

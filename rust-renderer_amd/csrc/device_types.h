@@ -297,6 +297,23 @@ struct RtaoDev {
    float radius, strength, blur_normal_cos, blur_plane;
 };
 
+// one-bounce ray-traced diffuse GI of the hybrid frame (UH_HYBRID_RTGI; rtgi.hip): what its kernels read and write. Ray s of the pixel in
+// queue slot q is ray q * samples + s in `rays` and in the words of `sun_rays`
+struct RtgiDev {
+   uint32_t* counts;               // UH_HYBRID_GI_COUNTS: a word per pixel, bytes (low first) sunlit, dark, emitter, missed; added to by words
+   float4* radiance;               // UH_HYBRID_GI_RADIANCE: Ef.rgb, w = 1 where the pixel cast, else (0, 0, 0, 0)
+   float4* mean;                   // E.rgb of the pixels that cast (the filter's input; not written when blur_radius is 0)
+   float4* rays;                   // L.rgb of every ray, by ray number
+   float4* sun_rays;               // the sun rays queued by the closest-hit kernel: origin.xyz, ray number (bits)
+   uint32_t* queue;                // the pixels that cast, compacted
+   uint32_t* counters;             // [0]: entries of `queue`, [1]: entries of `sun_rays`, [2]: rays that missed
+   uint32_t samples;               // UhRtgiParams::samples
+   uint32_t frame_base;            // frameNumber(view) * 64: ray s seeds its state with (frame_base + s) ^ kRtgiSeedXor
+   uint32_t blur_radius;
+   float max_radiance, intensity, blur_normal_cos, blur_plane;
+};
+constexpr uint32_t kRtgiSeedXor = 0x52544749u;  // keeps the rays from being the rtao pass's own
+
 // the denoiser (uh_denoise; denoise.hip): one frame's guides and moments as the next call's history reads them
 struct DenoiseHistory {
    float4* pos;                    // the position texel (w != 0: geometry)
@@ -487,6 +504,14 @@ void launch_hybrid_restir_lights(const LaunchCfg&, const FrameParams&, const Sce
 void launch_rtao_trace(const LaunchCfg&, const SceneDev&, const HybridDev&, const RtaoDev&, uint32_t order);
 // ao (and its filter, blur_radius > 0) from the counts into ssao_output, texel (x, y) = G-buffer pixel (x, H - 1 - y)
 void launch_rtao_resolve(const LaunchCfg&, const HybridDev&, const RtaoDev&, uint16_t* ssao);
+// the rtgi pass (rtgi.hip), a launcher per timed stage; gi.counters zeroed by the caller. trace: classify (which pixels cast; counts and
+// radiance zeroed) and the closest-hit walk that shades its rays and queues the sun rays (order: 0 a pixel's samples are consecutive
+// items, 1 one sample of consecutive queued pixels); shadow: the any-hit walk over the queued sun rays; filter: E from the rays in sample
+// order, then (blur_radius > 0) the tile filter; composite: deferred_output.rgb += the pixel's share of Ef
+void launch_rtgi_trace(const LaunchCfg&, const SceneDev&, const HybridDev&, const RtgiDev&, uint32_t order);
+void launch_rtgi_shadow(const LaunchCfg&, const SceneDev&, const HybridDev&, const RtgiDev&);
+void launch_rtgi_filter(const LaunchCfg&, const HybridDev&, const RtgiDev&);
+void launch_rtgi_composite(const LaunchCfg&, const SceneDev&, const HybridDev&, const HybridFrameDev&, const RtgiDev&);
 // the taa pass (taa.hip): one lane per pixel; fp gives the frame, the matrices of primary_ray and prev_pv; t.counters zeroed by the caller
 void launch_hybrid_taa(const LaunchCfg&, const FrameParams&, const TaaDev&);
 // the three stages of the post pass (post.hip). meter: the histogram (with auto_exposure) and the exposure record; bloom: down[1..levels]

@@ -1,6 +1,6 @@
 // hybrid_graph.hip - the hybrid graph of include/utopian_hip.h (uh_render_hybrid: the ray-traced passes, the final frame, the IBL
 // maps, the marching-cubes pass, the rasterised G-buffer, the reservoir lights, ray-traced ambient occlusion, motion vectors, temporal
-// anti-aliasing, the HDR display chain) with its
+// anti-aliasing, the HDR display chain, one-bounce ray-traced diffuse GI) with its
 // read and stats verbs, and what the forward graph and the denoiser share with it: the mesh and light tables, the wait behind the
 // frames in flight and destroy_graphs. Host code over uh_ctx::Hybrid (context_state.h); the rasterised passes go through
 // raster_driver.hip. Host-side counterpart of build_render_graph (utopian/src/renderers/mod.rs).
@@ -392,7 +392,7 @@ static int render_gbuffer_raster(uh_ctx* c, const LaunchCfg& lc, const UhViewUni
 struct HybridPlan {
    int code;
    const char* refusal;
-   bool raster, maps, render_maps, restir, rtao, mc, motion, rt, taa, post;  // maps: the IBL maps exist for this call's consumers
+   bool raster, maps, render_maps, restir, rtao, rtgi, mc, motion, rt, taa, post;  // maps: the IBL maps exist for this call's consumers
    bool deferred, frame, env;  // the deferred pass runs; the final frame's images and the IBL maps are needed
    bool first, frame_first;    // the ray-traced images, the final frame's images are allocated by this call (and cleared)
 };
@@ -497,6 +497,26 @@ static HybridPlan hybrid_plan(const uh_ctx& c, const UhViewUniformData& view, ui
    }
    // the HDR display chain: between the taa pass and present, over whatever the call leaves in its source; it refuses nothing
    p.post = (mask & UH_HYBRID_POST) != 0;
+   // one-bounce diffuse GI: hemisphere rays from the G-buffer, shaded at their hits, added to what the deferred pass of this call wrote
+   p.rtgi = (mask & UH_HYBRID_RTGI) != 0;
+   if (p.rtgi) {
+      if (view.raytracing_supported != 1)
+         return refuse(UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_RTGI casts rays and view.raytracing_supported is not 1; set it, or clear the bit");
+      if (!(mask & UH_HYBRID_GBUFFER) && !h.gbuffer_done)
+         return refuse(UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_RTGI casts its rays from the G-buffer, and no G-buffer has been rendered; set UH_HYBRID_GBUFFER");
+      if (view.ibl_enabled == 1)
+         return refuse(UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_RTGI with view.ibl_enabled = 1: the IBL ambient term and this pass would both count the sky; "
+                     "set ibl_enabled = 0, or clear the bit");
+      if (!(mask & UH_HYBRID_DEFERRED))
+         return refuse(UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_RTGI without UH_HYBRID_DEFERRED in the same call: the pass adds to what the deferred pass "
+                     "writes and has nothing to add to; set UH_HYBRID_DEFERRED");
+      if ((uint64_t)c.W * c.H * 16u >= (1ull << 32))
+         return refuse(UH_ERR_CAPACITY, "uh_render_hybrid: UH_HYBRID_RTGI: a frame of 2^28 pixels or more (its rays are numbered in 32 bits)");
+   }
    p.rt = view.raytracing_supported != 0;
    p.deferred = (mask & UH_HYBRID_DEFERRED) != 0;
    p.frame = (mask & (UH_HYBRID_SSAO | UH_HYBRID_DEFERRED | UH_HYBRID_SKY | UH_HYBRID_PRESENT)) || p.mc || p.rtao || p.taa || p.post;
@@ -580,6 +600,21 @@ static int hybrid_prepare(uh_ctx* c, const HybridPlan& p) {
       if (int st = alloc_group(c, [&](auto f) { h.ao.images(pixels, f); })) return st;
       HIP_TRY(c, hipMemsetAsync(h.ao.counts.p, 0, h.ao.counts.n, c->stream));
    }
+   if (p.rtgi) {
+      uh_ctx::Hybrid::Rtgi& gi = h.gi;
+      if (!gi.counters.p) {
+         if (int st = stage_create(c, gi.stage, 4)) return st;
+         if (int st = alloc_group(c, [&](auto f) { gi.images(pixels, f); })) return st;
+      }
+      // a record per ray: kept while they hold this pass's rays, else allocated again (the stream is waited for first: a pass in flight
+      // may still use the old ones)
+      const size_t rays = pixels * gi.params.samples;
+      if (gi.rays.n < rays || gi.sun_rays.n < rays) {
+         HIP_TRY(c, hipStreamSynchronize(c->stream));
+         for (int st : {grow(c, gi.rays, rays, "uh_render_hybrid: UH_HYBRID_RTGI"), grow(c, gi.sun_rays, rays, "uh_render_hybrid: UH_HYBRID_RTGI")})
+            if (st) return st;
+      }
+   }
    if (p.env)
       if (int st = env_alloc(c)) return st;
    if (p.taa && !h.taa.counters.p) {
@@ -644,6 +679,8 @@ static void reset_stage_records(uh_ctx::Hybrid& h, const HybridPlan& p, uint32_t
    if (mask & UH_HYBRID_MARCHING_CUBES) h.stage[kStMarchingCubes].ran = false;
    if (p.restir) h.stage[kStRestirLights].ran = false;
    if (p.rtao) h.stage[kStRtaoTrace].ran = h.stage[kStRtaoFilter].ran = false;
+   if (p.rtgi)
+      for (Stage& s : h.gi.stage) s.ran = false;
 }
 
 // what the passes of one call share
@@ -730,6 +767,27 @@ static int rtao_pass(uh_ctx* c, const HybridCall& k) {
    return UH_OK;
 }
 
+// the rtgi pass behind deferred_pass: classify + closest-hit walk (which shades the rays and queues the sun rays), the sun rays' any-hit
+// walk, the per-pixel mean + filter into the radiance image, then the composite into deferred_output; a stage each
+static int rtgi_pass(uh_ctx* c, const HybridCall& k) {
+   uh_ctx::Hybrid::Rtgi& g = c->hy.gi;
+   const UhRtgiParams& p = g.params;
+   const RtgiDev gi{g.counts.p, g.radiance.p, g.mean.p, g.rays.p, g.sun_rays.p, g.queue.p, g.counters.p, p.samples, k.fp.frame_number * 64u,
+                    p.blur_radius, p.max_radiance, p.intensity, p.blur_normal_cos, p.blur_plane};
+   int st = timed(c, g.stage[0], [&] {
+      HIP_TRY(c, hipMemsetAsync(g.counters.p, 0, g.counters.n * sizeof(uint32_t), c->stream));
+      launch_rtgi_trace(k.lc, c->scene, k.hd, gi, g.order);
+      return (int)UH_OK;
+   });
+   if (st) return st;
+   if ((st = timed(c, g.stage[1], [&] { launch_rtgi_shadow(k.lc, c->scene, k.hd, gi); }))) return st;
+   if ((st = timed(c, g.stage[2], [&] { launch_rtgi_filter(k.lc, k.hd, gi); }))) return st;
+   if ((st = timed(c, g.stage[3], [&] { launch_rtgi_composite(k.lc, c->scene, k.hd, k.fd, gi); }))) return st;
+   g.samples = p.samples;
+   g.renders++;
+   return UH_OK;
+}
+
 // the taa pass between atmosphere_pass and present_pass: deferred_output into the set that is not the history, which then becomes the
 // current one (the ping-pong is the host's: the kernel is enqueued with both pointers)
 static int taa_pass(uh_ctx* c, const HybridCall& k) {
@@ -764,7 +822,7 @@ static int taa_pass(uh_ctx* c, const HybridCall& k) {
 
 // The passes in the order of build_render_graph (mod.rs:91-186, graph.rs:743), each between its stage's two events: setup_shadow_pass's
 // four cascades first, rt_shadows, gbuffer, setup_cubemap_pass, rt_reflections, then the final frame - ssao_pass (not with
-// ssao_enabled != 1, ssao.rs:27; the rtao pass takes its place), deferred_pass, setup_marching_cubes_pass, atmosphere_pass, the taa pass
+// ssao_enabled != 1, ssao.rs:27; the rtao pass takes its place), deferred_pass, the rtgi pass (an extension), setup_marching_cubes_pass, atmosphere_pass, the taa pass
 // (an extension; present then reads its output), the post pass (an extension; it reads the taa pass's output or deferred_output, and
 // present then reads its own), present_pass
 static int hybrid_passes(uh_ctx* c, const HybridCall& k, uint32_t mask) {
@@ -812,6 +870,7 @@ static int hybrid_passes(uh_ctx* c, const HybridCall& k, uint32_t mask) {
       });
       if (st) return st;
    }
+   if (p.rtgi && (st = rtgi_pass(c, k))) return st;
    h.frame_lights = h.stage[kStDeferred].ran ? (p.restir ? 2 : view.num_lights + 1) : 0;  // with the reservoir lights: the sun and the reservoir's
    if (p.restir) {
       // a reservoir pass enqueued after this call starts behind the call's reads (the spatial ring comes round to the slot read here)
@@ -867,7 +926,7 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    const uh_ctx::Hybrid& h = c->hy;
    if (!h.counter.p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid before the first uh_render_hybrid");
-   if (which < 0 || which > UH_HYBRID_TAA_HISTORY) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..17");
+   if (which < 0 || which > UH_HYBRID_GI_COUNTS) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..19");
    if (which >= UH_HYBRID_SSAO_IMAGE && which <= UH_HYBRID_PRESENT_OUTPUT && !h.sky_counter.p)
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 6..8 before the first call with an SSAO, deferred, sky or present bit");
    if ((which == UH_HYBRID_DEPTH || which == UH_HYBRID_MARCHING_CUBES_VISIBILITY) && h.mc.renders == 0)
@@ -882,13 +941,17 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image 15 before the first motion pass (UH_HYBRID_GBUFFER | UH_HYBRID_MOTION)");
    if ((which == UH_HYBRID_TAA_OUTPUT || which == UH_HYBRID_TAA_HISTORY) && h.taa.renders == 0)
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 16..17 before the first taa pass (UH_HYBRID_TAA)");
+   if ((which == UH_HYBRID_GI_RADIANCE || which == UH_HYBRID_GI_COUNTS) && h.gi.renders == 0)
+      return fail(c, UH_ERR_INVALID_ARGUMENT,
+                  "uh_read_hybrid: images 18..19 before the first rtgi pass (UH_HYBRID_RTGI); until then the image index must be 0..17");
    // image k's pixels and its bytes per pixel, in UH_HYBRID_* image order
    const std::pair<const void*, size_t> img[] = {
       {h.pos.p, sizeof(float4)}, {h.nrm.p, sizeof(float4)}, {h.alb.p, sizeof(uchar4)}, {h.pbr.p, sizeof(float4)}, {h.shadow.p, 1},
       {h.refl.p, sizeof(uchar4)}, {h.ssao.p, sizeof(uint16_t)}, {h.deferred.p, sizeof(float4)}, {h.present.p, sizeof(uchar4)},
       {h.mc.target.depth.p, sizeof(float)}, {h.mc.target.vis.p, sizeof(uint32_t)}, {h.gr.target.depth.p, sizeof(float)}, {h.gr.target.vis.p, sizeof(uint32_t)},
       {h.rl.vis.p, 1}, {h.ao.counts.p, 1}, {h.mv.image.p, sizeof(float4)},
-      {h.taa.col[h.taa.cur].p, sizeof(float4)}, {h.taa.n[h.taa.cur].p, sizeof(float)}};
+      {h.taa.col[h.taa.cur].p, sizeof(float4)}, {h.taa.n[h.taa.cur].p, sizeof(float)},
+      {h.gi.radiance.p, sizeof(float4)}, {h.gi.counts.p, sizeof(uint32_t)}};
    return read_back(c, out, img[which].first, (size_t)c->W * c->H * img[which].second);
 }
 
@@ -962,6 +1025,46 @@ int uh_get_rtao_visits(uh_ctx* c, uint64_t* nodes, uint64_t* triangles) {
    HIP_TRY(c, hipMemcpy(visits, h.ao.counters.p + 2, sizeof(visits), hipMemcpyDeviceToHost));
    *nodes = visits[0];
    *triangles = visits[1];
+   return UH_OK;
+}
+
+// ---- one-bounce ray-traced diffuse GI (utopian_hip.h "UH_HYBRID_RTGI"; rtgi.hip) ----
+int uh_rtgi_default_params(UhRtgiParams* out) {
+   if (!out) return UH_ERR_INVALID_ARGUMENT;
+   *out = UhRtgiParams{2, 3, 16.0f, 1.0f, 0.9f, 0.05f};
+   return UH_OK;
+}
+
+static const char* rtgi_params_refusal(const UhRtgiParams& p) {
+   if (p.samples < 1 || p.samples > 16) return "samples must be 1..16";
+   if (p.blur_radius > 6) return "blur_radius must be 0..6";
+   if (!(p.max_radiance > 0.0f && p.max_radiance < INFINITY)) return "max_radiance must be finite and > 0";
+   if (!(p.intensity >= 0.0f && p.intensity < INFINITY)) return "intensity must be finite and >= 0";
+   if (std::isnan(p.blur_normal_cos) || std::isnan(p.blur_plane)) return "blur_normal_cos and blur_plane must not be NaN";
+   return nullptr;
+}
+
+int uh_set_rtgi_params(uh_ctx* c, const UhRtgiParams* params) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!params) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_set_rtgi_params: null params");
+   if (const char* why = rtgi_params_refusal(*params)) return fail(c, UH_ERR_INVALID_ARGUMENT, std::string("uh_set_rtgi_params: ") + why);
+   c->hy.gi.params = *params;
+   return UH_OK;
+}
+
+int uh_get_rtgi_stats(uh_ctx* c, UhRtgiStats* out) {
+   int st;
+   if (!stats_begin(c, out, sizeof(*out), "uh_get_rtgi_stats: null destination", c && c->hy.gi.renders != 0, &st)) return st;
+   uh_ctx::Hybrid::Rtgi& g = c->hy.gi;
+   float* const ms[4] = {&out->trace_ms, &out->shadow_ms, &out->filter_ms, &out->composite_ms};
+   for (int k = 0; k < 4; k++)
+      if ((st = stage_ms(c, g.stage[k], ms[k]))) return st;
+   uint32_t counters[3] = {0, 0, 0};
+   HIP_TRY(c, hipMemcpy(counters, g.counters.p, sizeof(counters), hipMemcpyDeviceToHost));
+   out->pixels = counters[0];
+   out->rays = (uint64_t)counters[0] * g.samples;
+   out->shadow_rays = counters[1];
+   out->misses = counters[2];
    return UH_OK;
 }
 

@@ -1,6 +1,7 @@
 // kernel_common.h — what the kernel files (kernels.hip, path_fused.hip, restir.hip, tiles.hip, hybrid_kernels.hip) share besides the device
-// arithmetic: the block size, the launch-grid helpers of their launchers, and two small device functions that kernels of more than one
-// file call (resolve_color: the path tracer's resolve and the tile composition; gbuffer_fetch: the ReSTIR passes and the hybrid passes).
+// arithmetic: the block size, the launch-grid helpers of their launchers, and three small device functions that kernels of more than one
+// file call (resolve_color: the path tracer's resolve and the tile composition; gbuffer_fetch: the ReSTIR passes and the hybrid passes;
+// rtao_normal: rtao.hip and rtgi.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,6 +29,13 @@ __device__ __forceinline__ V3 gbuffer_fetch(const float4* __restrict__ g, uint32
    uint32_t x0 = px == 0 ? 0 : px - 1, y0 = py == 0 ? 0 : py - 1;
    float4 a = g[(size_t)y0 * W + x0], b = g[(size_t)y0 * W + px], c = g[(size_t)py * W + x0], d = g[(size_t)py * W + px];
    return ((xyz(a) + xyz(b)) + (xyz(c) + xyz(d))) * 0.25f;
+}
+
+// Nn of a G-buffer pixel and whether it casts hemisphere rays (the rtao and rtgi passes): normalize3 of the normal texel, finite in every
+// component
+__device__ __forceinline__ bool rtao_normal(float4 N4, V3& nn) {
+   nn = normalize3(v3(N4.x, N4.y, N4.z));
+   return fabsf(nn.x) < INFINITY && fabsf(nn.y) < INFINITY && fabsf(nn.z) < INFINITY;  // NaN: false
 }
 
 // ---- launch grids

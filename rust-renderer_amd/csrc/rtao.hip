@@ -10,12 +10,6 @@
 
 namespace uh {
 
-// Nn of a pixel and whether it casts: normalize3 of the normal texel, finite in every component
-__device__ __forceinline__ bool rtao_normal(float4 N4, V3& nn) {
-   nn = normalize3(v3(N4.x, N4.y, N4.z));
-   return fabsf(nn.x) < INFINITY && fabsf(nn.y) < INFINITY && fabsf(nn.z) < INFINITY;  // NaN: false
-}
-
 // One lane per pixel: its count is zeroed, and the geometry pixels (position w != 0) with a finite Nn are appended to a dense queue (one
 // atomic per wave, as k_hybrid_restir_classify).
 __global__ __launch_bounds__(kBlock) void k_rtao_classify(HybridDev hd, RtaoDev ao) {

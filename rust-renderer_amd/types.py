@@ -398,6 +398,34 @@ assert C.sizeof(RtaoStats) == 32 and RtaoStats.rays.offset == 8 and RtaoStats.oc
     RtaoStats.filter_ms.offset == 28
 
 
+# one-bounce ray-traced diffuse GI of the hybrid frame (an extension; utopian_hip.h "UH_HYBRID_RTGI"): the pass behind the deferred pass and
+# its two images; bit 9 stays unused
+HYBRID_RTGI = 1 << 17
+HYBRID_GI_RADIANCE, HYBRID_GI_COUNTS = 18, 19
+
+
+class RtgiParams(C.Structure):
+    """UhRtgiParams: rays per pixel that casts (1..16), the filter's radius (0 none, else 1..6: taps in [-r, r]^2), the cap of a ray's
+    radiance, the scale of what the composite adds, and a tap's normal and plane thresholds; uh_rtgi_default_params fills the defaults"""
+
+    _fields_ = [("samples", C.c_uint32), ("blur_radius", C.c_uint32), ("max_radiance", C.c_float), ("intensity", C.c_float),
+                ("blur_normal_cos", C.c_float), ("blur_plane", C.c_float)]
+
+
+assert C.sizeof(RtgiParams) == 24 and [getattr(RtgiParams, n).offset for n, _ in RtgiParams._fields_] == list(range(0, 24, 4))
+
+
+class RtgiStats(C.Structure):
+    """UhRtgiStats: the last rtgi pass - the pixels that cast, their rays, the sun rays cast from the hits, the rays that missed, hipEvent
+    ms of classify + closest-hit walk, of the sun rays' walk, of the mean + filter and of the composite"""
+
+    _fields_ = [("pixels", C.c_uint64), ("rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("misses", C.c_uint64), ("trace_ms", C.c_float),
+                ("shadow_ms", C.c_float), ("filter_ms", C.c_float), ("composite_ms", C.c_float)]
+
+
+assert C.sizeof(RtgiStats) == 48 and RtgiStats.misses.offset == 24 and RtgiStats.trace_ms.offset == 32 and RtgiStats.composite_ms.offset == 44
+
+
 # motion vectors for moving geometry (an extension; utopian_hip.h "motion vectors"): a modifier of HYBRID_GBUFFER; bit 9 stays unused
 HYBRID_MOTION = 1 << 14
 HYBRID_MOTION_IMAGE = 15
