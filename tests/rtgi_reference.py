@@ -53,19 +53,26 @@ def clamp(L, max_radiance):
 
 def rays(oracle, meshes, g, view, samples, max_radiance, furnace=False):
     """every ray of the pass: dict(rows (m,), L (m, samples, 3) float32 as stored, kind (m, samples) of SUNLIT / DARK / EMITTER / MISSED,
-    shadowed (m, samples): dark because its sun ray was occluded, shadow_rays: the sun rays cast)"""
+    shadowed (m, samples): dark because its sun ray was occluded, shadow_rays: the sun rays cast, mesh (m, samples): the mesh the ray met
+    (hybrid_reference.MISS where none), and of the hits that are shaded (no emitter, no furnace) Nh (m, samples, 3), the world normal
+    after its turn toward the ray (NaN elsewhere), and flipped (m, samples): the turn took place, dot(Nh before it, d) > 0)"""
     rows, nn, d = directions(g, view, samples)
     m = len(rows)
     L = np.zeros((m * samples, 3), np.float32)
     kind = np.full(m * samples, DARK, np.uint8)
     shadowed = np.zeros(m * samples, bool)
-    out = dict(rows=rows, L=L.reshape(m, samples, 3), kind=kind.reshape(m, samples), shadowed=shadowed.reshape(m, samples), shadow_rays=0)
+    hit_mesh = np.full(m * samples, hr.MISS, np.uint32)
+    hit_Nh = np.full((m * samples, 3), np.nan, np.float32)
+    flipped = np.zeros(m * samples, bool)
+    out = dict(rows=rows, L=L.reshape(m, samples, 3), kind=kind.reshape(m, samples), shadowed=shadowed.reshape(m, samples), shadow_rays=0,
+               mesh=hit_mesh.reshape(m, samples), Nh=hit_Nh.reshape(m, samples, 3), flipped=flipped.reshape(m, samples))
     if not m:
         return out
     o = np.repeat(hr.offset_ray(g["position"][..., :3].reshape(-1, 3)[rows], nn), samples, axis=0)
     d = d.reshape(-1, 3)
     t, u, v, mesh, prim = hr.trace(oracle, o, d)
     miss = mesh == hr.MISS
+    hit_mesh[:] = mesh
     kind[miss] = MISSED
     for k in np.nonzero(miss)[0]:
         L[k] = 1.0 if furnace else oa.sky(o[k], d[k], view.sun_dir[:])  # IntegrateScattering(o, d, 999999999, sun), unclamped
@@ -90,7 +97,9 @@ def rays(oracle, meshes, g, view, samples, max_radiance, furnace=False):
                 vn = [M["vertices"]["normal"][tri[:, k], :3].astype(np.float32) for k in range(3)]
                 n = (vn[0] * b0[sel][:, None] + vn[1] * b1[sel][:, None]) + vn[2] * b2[sel][:, None]
                 Nh[sel] = hr.normalize(hr.inverse_transpose_mul(hr.invert3x3(M["world"]), n))
-            Nh = np.where((hr.dot(Nh, d[rest]) > 0)[:, None], -Nh, Nh)
+            flipped[rest] = hr.dot(Nh, d[rest]) > 0
+            Nh = np.where(flipped[rest][:, None], -Nh, Nh)
+            hit_Nh[rest] = Nh
             X = o[rest] + t[rest][:, None] * d[rest]
             sun = hr.sun_direction(view)
             ndl = hr.dot(Nh, np.broadcast_to(sun, Nh.shape))
@@ -273,11 +282,61 @@ def courtyard_scene():
     return Scene("rtgi_courtyard", [(Model(meshes, [checker()]), None)], [], cam)
 
 
+# ---- the turned scene: back faces, a mirrored instance, the odd materials, zero normals, the clamp -----------------------------------
+TURNED_SUN = (-0.35, 0.7, 0.6)  # toward the sun: from the camera's side, so the wall below is lit on the side its vertex normals face away from
+TURNED_MESHES = dict(floor=0, wall=1, mirrored=2, metal=3, dielectric=4, pbr=5, zero=6, clamp=7)
+CLAMP_COLOR = (-1.0, 3.0e38, float("nan"), 1.0)  # a sunlit ray brings (negative, beyond every finite cap, NaN): stored as (+0, max_radiance, +0)
+
+
+def turned_scene():
+    """what no other scene of the pass has, one mesh each. A floor; a free-standing wall of one sheet whose vertex normals point away from
+    the camera and the floor before it (-z), so every floor ray meets its back, and the sun (TURNED_SUN) stands on the camera's side: the
+    hit is sunlit only if its normal is turned toward the ray. Its checker map is addressed with uv in [-1.2, 1.8]. A box under a
+    mirrored, rotated and non-uniformly scaled instance (negative determinant). A metal sphere, a dielectric box and a box of material
+    type 4 on the floor: hits on them are shaded as any other hit. A sheet over the camera's head, outside its view, whose vertex
+    normals are all zero: Nh is NaN, the hit is dark and casts no sun ray. And a panel beside the floor, outside the view, that faces the
+    sun with the base colour CLAMP_COLOR: its sunlit hits run into every branch of the clamp."""
+    import rust_renderer_amd as rr
+    from rust_renderer_amd.scenes import Mesh, Model, Scene, box, icosphere, quad
+
+    floor = quad((-5.0, 0.0, 5.0), (10.0, 0.0, 0.0), (0.0, 0.0, -10.0), nu=2, nv=2)
+    wv, wi = quad((2.0, 0.0, -1.5), (-4.0, 0.0, 0.0), (0.0, 2.0, 0.0), nu=2, nv=2)
+    assert (wv["normal"][:, 2] == -1.0).all()
+    wv["uv"][:] = wv["uv"] * np.float32(3.0) - np.float32(1.2)
+    rot = np.array([[0.8, 0.0, 0.6], [0.0, 1.0, 0.0], [-0.6, 0.0, 0.8]], np.float32)
+    mirrored = rr.transform3x4((-1.3, 0.8, 0.6), (-2.4, 0.4, 0.6), rot)
+    sv, si = icosphere(1)
+    zv, zi = quad((-2.0, 3.5, 5.0), (4.0, 0.0, 0.0), (0.0, 0.0, -3.0), nu=2, nv=2)
+    zv["normal"][:] = 0.0
+    cv, ci = quad((4.5, 0.0, 2.5), (0.0, 0.0, 1.9), (0.0, 2.5, 0.0))
+    assert (cv["normal"][:, 0] == -1.0).all()
+    meshes = [Mesh(*floor, rr.LAMBERTIAN, base_color=(0.8, 0.8, 0.8, 1.0)),
+              Mesh(wv, wi, rr.LAMBERTIAN, base_color=(1.0, 0.9, 0.8, 1.0), texture=0),
+              Mesh(*box((0.0, 0.0, 0.0), (0.5, 0.5, 0.5)), rr.LAMBERTIAN, base_color=(0.3, 0.7, 0.4, 1.0), transform=mirrored),
+              Mesh(sv, si, rr.METAL, 0.1, base_color=(0.9, 0.6, 0.3, 1.0), transform=rr.transform3x4((0.5, 0.5, 0.5), (2.3, 0.5, 0.8))),
+              Mesh(*box((1.1, 0.35, 1.9), (0.35, 0.35, 0.35)), rr.DIELECTRIC, 1.5, base_color=(0.9, 0.9, 1.0, 1.0)),
+              Mesh(*box((-1.2, 0.3, 1.9), (0.3, 0.3, 0.3)), rr.PBR, base_color=(0.6, 0.5, 0.9, 1.0), metallic=0.5, roughness=0.4),
+              Mesh(zv, zi, rr.LAMBERTIAN, base_color=(0.5, 0.5, 0.5, 1.0)),
+              Mesh(cv, ci, rr.LAMBERTIAN, base_color=CLAMP_COLOR)]
+    cam = rr.camera.Camera((0.0, 2.2, 4.5), (0.0, 0.3, 0.0), 60.0, W / H, 0.01, 1000.0)
+    return Scene("rtgi_turned", [(Model(meshes, [checker()]), None)], [], cam)
+
+
+SUNS = {"rtgi_courtyard": COURTYARD_SUN, "rtgi_turned": TURNED_SUN}
+
+# ---- frames at which the persistent walks refill (tests/test_gpu_walk_chunks.py; their adequacy: tests/test_rtgi_cpu.py) ------------------
+WALK_LANES = 65536               # the lanes of a persistent grid at option "trace_blocks_per_cu" = 1 on 256 CUs
+WALK_BOX_SIZE = (131, 97)        # the closed box at 16 samples: 203,312 rays, 3.1 grids
+WALK_EMISSIVE_SIZE = (263, 167)  # the emissive box at 3 samples: 131,763 rays, 2.01 grids, a last chunk of 51
+WALK_YARD_SIZE = (183, 113)      # the courtyard at 16 samples: the smallest odd width at 67 : 41 with two grids of sun rays
+WALK_AO_SIZE = (71, 45)          # the closed box at RTAO's 64 samples: 204,480 rays, 3.1 grids
+
+
 def scene_view(scene, width=W, height=H, **kw):
-    """hybrid_util.frame_view, with the courtyard's sun for the courtyard"""
+    """hybrid_util.frame_view, with the scene's own sun where it has one (SUNS)"""
     v = scene.make_view(width, height, **kw)
     v.shadows_enabled = v.ibl_enabled = v.cubemap_enabled = 0
-    if scene.name == "rtgi_courtyard":
-        s = np.array(COURTYARD_SUN, np.float64)
+    if scene.name in SUNS:
+        s = np.array(SUNS[scene.name], np.float64)
         v.sun_dir[:] = [float(x) for x in np.float32(s / np.linalg.norm(s))]
     return v

@@ -88,12 +88,14 @@ def scene_at(k):
     return EverythingScene("everything", [], [], camera(k), dict(sky_enabled=1))
 
 
-def frame_views():
-    """the three views: every flag on, the TAA jitter of the frame's index, the previous frame's un-jittered projection * view"""
+def frame_views(ibl=1):
+    """the three views: every flag on, the TAA jitter of the frame's index, the previous frame's un-jittered projection * view; ibl = 0:
+    without the IBL maps (ibl_enabled = cubemap_enabled = 0: test_gpu_rtgi_everything.py, whose rtgi pass refuses them)"""
     views, prev = [], None
     for k in range(FRAMES):
         v = frame_view(scene_at(k), W, H, ssao_enabled=1, raytracing_supported=1, fxaa_enabled=1, marching_cubes_enabled=1)
-        v.shadows_enabled = v.ibl_enabled = v.cubemap_enabled = 1
+        v.shadows_enabled = 1
+        v.ibl_enabled = v.cubemap_enabled = ibl
         v.num_lights, v.time, v.rebuild_tlas = 8, 5.0 + 0.75 * k, 1
         v.samples_per_frame, v.total_samples = 1, k + 1
         pv = projection_view(v)

@@ -36,28 +36,38 @@ def oracle(res, time, lo=LO, hi=HI, positions=True):
     return oa.marching_cubes(res, lo, hi, time=time, order=0, positions=positions)
 
 
-def make_ctx(res, time, device_build, lo=LO, hi=HI, placeholder=False, world=None, width=W, height=H, statics=True):
-    """the scene with the isosurface at `time` (or, placeholder, a mesh without vertices in its place), built"""
-    r = rr.Renderer(width, height)
-    r.set_option("sun_grid_force", 1)  # the sun grid refuses scenes with a ground plane by default
-    r.set_option("device_build", device_build)
-
+def fill_scene(r, add_iso, statics=True):
+    """ground and sphere, the isosurface's mesh - add_iso(material) adds it and returns its index -, box, three lights; without `statics`
+    that mesh alone. Not built"""
     def mat(*rgb):
         return rr.make_material(base_color=rgb + (1.0,), diffuse_map=r.default_diffuse_map())
 
     if statics:
         assert r.add_mesh(*quad((-64, 4.99, -64), (0, 0, 160), (160, 0, 0), 8, 8), mat(0.6, 0.6, 0.6)) == GROUND
         assert r.add_mesh(*icosphere(2), mat(0.8, 0.3, 0.2), rr.transform3x4((3, 3, 3), (4.0, 9.0, 26.0))) == SPHERE
-    if placeholder:
-        mesh = r.add_mesh(np.zeros(0, VERTEX_DTYPE), np.zeros(0, np.uint32), mat(0.8, 0.8, 0.8), world)
-    else:
-        mesh, tris = r.add_isosurface_mesh(res, lo, hi, time, material=mat(0.8, 0.8, 0.8), world3x4=world)
-        assert tris == oracle(res, time, lo, hi, positions=False)["triangles"]
+    mesh = add_iso(mat(0.8, 0.8, 0.8))
     if statics:
         assert mesh == ISO
         assert r.add_mesh(*box((27.0, 7.5, 8.0), (2.0, 2.5, 2.0)), mat(0.2, 0.4, 0.8)) == BOX
         for p in LIGHTS:
             r.add_light(p, (1.0, 0.9, 0.8), 40.0)
+    return r
+
+
+def make_ctx(res, time, device_build, lo=LO, hi=HI, placeholder=False, world=None, width=W, height=H, statics=True):
+    """the scene with the isosurface at `time` (or, placeholder, a mesh without vertices in its place), built"""
+    r = rr.Renderer(width, height)
+    r.set_option("sun_grid_force", 1)  # the sun grid refuses scenes with a ground plane by default
+    r.set_option("device_build", device_build)
+
+    def add_iso(material):
+        if placeholder:
+            return r.add_mesh(np.zeros(0, VERTEX_DTYPE), np.zeros(0, np.uint32), material, world)
+        mesh, tris = r.add_isosurface_mesh(res, lo, hi, time, material=material, world3x4=world)
+        assert tris == oracle(res, time, lo, hi, positions=False)["triangles"]
+        return mesh
+
+    fill_scene(r, add_iso, statics)
     r.build_acceleration()
     return r
 

@@ -30,18 +30,31 @@ class World:
     """a scene on a GPU renderer and on the oracle; the restatement's rays of a view are computed once per (samples, furnace, frame number)
     on the device's G-buffer and shared by the checks that follow (the G-buffer is compared before they are reused)"""
 
-    def __init__(self, scene, width=W, height=H):
+    def __init__(self, scene, width=W, height=H, on=None):
+        """on: (GPU renderer, oracle, mesh records) that hold the scene already, instead of an upload of `scene`"""
         self.scene, self.size = scene, (width, height)
-        self.gpu, self.cpu, self.meshes = pair(scene, width, height)
+        self.gpu, self.cpu, self.meshes = on if on is not None else pair(scene, width, height)
         self._gathered = {}
+
+    def set_oracle(self, cpu, meshes):
+        """another oracle and its mesh records (the geometry changed): the shared rays are forgotten"""
+        self.cpu, self.meshes = cpu, meshes
+        self.forget()
+
+    def forget(self):
+        """the shared rays were made for geometry that has changed since (their key does not know it)"""
+        self._gathered = {}
+
+    def set_params(self, **params):
+        self.params = gi.default_params(**params)
+        self.gpu.set_rtgi_params(**self.params)
 
     def view(self, **kw):
         return gi.scene_view(self.scene, *self.size, **kw)
 
     def render(self, v, mask=FRAME, **params):
         """a G-buffer pass first (rt_shadows reads the previous call's G-buffer: this camera's, whatever ran before), then the call"""
-        self.params = gi.default_params(**params)
-        self.gpu.set_rtgi_params(**self.params)
+        self.set_params(**params)
         self.gpu.render_hybrid(v, rr.HYBRID_GBUFFER)
         self.gpu.render_hybrid(v, mask)
 

@@ -1,7 +1,8 @@
 """CPU: the numpy restatement of one-bounce ray-traced diffuse GI (tests/rtgi_reference.py) held to known answers and properties on the
 oracle's own G-buffer - a bare floor under the furnace, the inside of a closed box, an emissive wall, the courtyard (where it also proves
-that the inputs of test_gpu_rtgi.py are adequate), the filter, the composite and the order of the per-pixel sum. test_gpu_rtgi.py holds
-the device to the restatement and runs the known answers there."""
+that the inputs of test_gpu_rtgi.py are adequate), the filter, the composite and the order of the per-pixel sum; and the proofs that the inputs of
+test_gpu_walk_chunks.py (frames at which the persistent walks refill) and test_gpu_rtgi_scenes.py (the synthetic and the turned scene) are
+adequate. test_gpu_rtgi.py holds the device to the restatement and runs the known answers there."""
 import numpy as np
 import pytest
 
@@ -16,12 +17,12 @@ W, H = gi.W, gi.H
 F = np.float32
 
 
-def world(scene):
+def world(scene, width=W, height=H, defaults=True):
     """the scene on the oracle, its meshes as uploaded, its view and the oracle's G-buffer of it"""
-    cpu = oa.OracleRenderer(W, H)
-    meshes = hr.upload_recorded(scene, cpu, True)
-    view = gi.scene_view(scene)
-    return cpu, meshes, view, hr.gbuffer(cpu, meshes, view, W, H)
+    cpu = oa.OracleRenderer(width, height)
+    meshes = hr.upload_recorded(scene, cpu, defaults)
+    view = gi.scene_view(scene, width, height)
+    return cpu, meshes, view, hr.gbuffer(cpu, meshes, view, width, height)
 
 
 @pytest.fixture(scope="module")
@@ -235,3 +236,132 @@ def test_the_clamp_maps_nan_negatives_and_minus_zero_to_plus_zero():
     x = np.array([np.nan, -1.0, -0.0, 0.0, 0.25, 16.0, 17.0, np.inf], np.float32)
     got = gi.clamp(x, 16.0)
     assert np.array_equal(got, np.float32([0, 0, 0, 0, 0.25, 16, 16, 16])) and not np.signbit(got).any()
+
+
+# ---- the inputs of test_gpu_walk_chunks.py ----------------------------------------------------------------------------------------
+LANES = gi.WALK_LANES
+
+
+def test_the_boxes_of_the_refill_tests_are_adequate():
+    """conditions test_gpu_walk_chunks.py relies on: at their frames every pixel of the two boxes casts and no ray misses (every pixel is
+    bit for bit), the closed box has 3 grids of rays, the emissive box 2 at three samples with a partial last chunk, and RTAO's box 3"""
+    import rtao_reference as ao
+
+    w, h = gi.WALK_BOX_SIZE
+    cpu, meshes, view, g = world(gi.inward_box_scene(), w, h)
+    counts, E, cast, totals, r = gi.gather(cpu, meshes, g, view, gi.default_params(samples=16))
+    assert cast.all() and (counts == (0, 16, 0, 0)).all() and totals[:2] == (w * h, 16 * w * h) and totals[3] == 0 and totals[1] >= 3 * LANES
+    assert 0 < totals[2] < LANES, "the sun rays of this box stay within one grid: the courtyard refills k_rtgi_shadow"
+    w, h = gi.WALK_EMISSIVE_SIZE
+    cpu, meshes, view, g = world(gi.emissive_box_scene(), w, h)
+    counts, E, cast, totals, r = gi.gather(cpu, meshes, g, view, gi.default_params(samples=3, max_radiance=0.5))
+    assert cast.all() and totals[3] == 0 and not counts[..., gi.SUNLIT].any() and 2 * LANES <= totals[1] < 3 * 2 * LANES and totals[1] % 64 != 0
+    lit = counts[..., gi.EMITTER] > 0
+    assert 0.25 < lit.mean() < 1 and np.array_equal(E, np.repeat((counts[..., gi.EMITTER] * F(0.5) / F(3.0))[..., None], 3, axis=-1))
+    w, h = gi.WALK_AO_SIZE
+    cpu, meshes, view, g = world(ao.inward_box_scene(), w, h)
+    count, totals = ao.counts(cpu, g, view, ao.MAX_SAMPLES, ao.BOX_RADIUS)
+    assert totals == (w * h, 64 * w * h, 64 * w * h) and totals[1] >= 3 * LANES and (count == 64).all()
+
+
+def yard_totals(width, height):
+    cpu, meshes, view, g = world(gi.courtyard_scene(), width, height)
+    counts, E, cast, totals, r = gi.gather(cpu, meshes, g, view, gi.default_params(samples=16))
+    return totals, r
+
+
+def test_the_courtyard_of_the_refill_tests_is_adequate_and_the_smallest_of_its_family():
+    """at WALK_YARD_SIZE and 16 samples the courtyard casts two grids of sun rays (k_rtgi_shadow refills twice), some of them occluded,
+    and some rays miss; the next smaller frame of its family (odd widths, heights the nearest odd number to 41 / 67 of the width) does
+    not reach two grids. Measured: 20,001 pixels, 320,016 rays, 134,390 sun rays, 25,479 misses; 181 x 111 gives 130,870 sun rays"""
+    w, h = gi.WALK_YARD_SIZE
+    totals, r = yard_totals(w, h)
+    print(totals)
+    assert totals[1] >= 3 * LANES and totals[2] >= 2 * LANES and totals[3] > 0
+    assert (r["kind"] == gi.SUNLIT).sum() > 0 and r["shadowed"].sum() > 0 and totals[3] < 0.1 * totals[1]
+    smaller = (w - 2, int(round((w - 2) * 41 / 67)) | 1)
+    assert yard_totals(*smaller)[0][2] < 2 * LANES, smaller
+
+
+# ---- the inputs of test_gpu_rtgi_scenes.py ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("samples", [3, 16])
+def test_the_synthetic_scene_is_an_adequate_input(samples):
+    """hybrid_util.synthetic_scene at 67 x 41: metal pixels that cast, pixels that are no metal with metallic and occlusion texels that
+    enter the composite, rays on all four meshes; and the side of the composite the device never shows: without raytracing_supported
+    the metal pixels receive too (the pass refuses such a view, so only the restatement has it)"""
+    from hybrid_util import synthetic_scene
+
+    cpu, meshes, view, g = world(synthetic_scene(), defaults=False)
+    assert view.raytracing_supported == 1 and [m["type"] for m in meshes] == [1.0, 0.0, 0.0, 1.0]
+    counts, E, cast, totals, r = gi.gather(cpu, meshes, g, view, gi.default_params(samples=samples))
+    material = g["pbr"][..., 3].astype(np.uint32)
+    geo = g["position"][..., 3] != 0
+    typ = np.array([m["type"] for m in meshes], np.float32)[np.minimum(material, 3)]
+    mf = np.array([m["metallic"] for m in meshes], np.float32)[np.minimum(material, 3)]
+    metal, matte = geo & (typ == 1.0), geo & (typ != 1.0) & cast
+    assert metal.sum() >= 100 and cast[metal].all()
+    assert (matte & (g["pbr"][..., 0] * mf != 0)).sum() >= 20 and (matte & (g["pbr"][..., 2] != 1)).sum() >= 20
+    assert all((r["mesh"] == i).sum() >= 10 for i in range(4)) and r["flipped"].any()
+    assert not np.array_equal(g["normal"][metal][:, :3], np.tile(np.float32([0, 1, 0]), (metal.sum(), 1))), "the floor's normals come from its normal map"
+    Ef = gi.filter(g, E, gi.default_params(blur_radius=0))
+    deferred = np.random.default_rng(5).random((H, W, 4), np.float32)
+    ssao = np.full((H, W), 65535, np.uint16)
+    out, touched = gi.composite(g, ssao, deferred, Ef, view, meshes, 1.0)
+    assert not touched[metal].any() and np.array_equal(out[metal], deferred[metal]) and touched[matte].all()
+    no_rt = gi.scene_view(synthetic_scene(), raytracing_supported=0)
+    out0, touched0 = gi.composite(g, ssao, deferred, Ef, no_rt, meshes, 1.0)
+    assert touched0[metal].all() and (out0[metal][:, :3] >= deferred[metal][:, :3]).all() and np.array_equal(out0[matte], out[matte])
+    # metallic below 1 lets some of it through: the floor's metallic texel times the factor is not 1 everywhere
+    assert (out0[metal][:, :3] > deferred[metal][:, :3]).any()
+
+
+@pytest.mark.parametrize("samples", [3, 16])
+def test_the_turned_scene_is_an_adequate_input(samples):
+    """the counts test_gpu_rtgi_scenes.py asserts on the device's G-buffer, here on the oracle's: at least 50 rays meet a surface from
+    behind (all of them the wall), 20 of them sunlit - which they are only because the normal was turned: before the turn it faces away
+    from the sun - 20 rays on each of the metal, dielectric and type-4 meshes and on the mirrored box, 10 on the sheet of zero normals,
+    all dark without a sun ray, and 10 sunlit rays on the panel whose colour the clamp maps to (+0, max_radiance, +0)"""
+    cpu, meshes, view, g = world(gi.turned_scene())
+    M = gi.TURNED_MESHES
+    assert [m["type"] for m in meshes] == [0.0, 0.0, 0.0, 1.0, 2.0, 4.0, 0.0, 0.0]
+    w = meshes[M["mirrored"]]["world"]
+    assert np.linalg.det(np.asarray(w, np.float64).reshape(3, 4)[:, :3]) < 0, "the mirrored instance"
+    uv = meshes[M["wall"]]["vertices"]["uv"]
+    assert uv.min() < 0 and uv.max() > 1
+    p = gi.default_params(samples=samples)
+    counts, E, cast, totals, r = gi.gather(cpu, meshes, g, view, p)
+    k, flipped = r["kind"], r["flipped"]
+    print({name: int((r["mesh"] == i).sum()) for name, i in M.items()}, "flipped", int(flipped.sum()), "of them sunlit", int((flipped & (k == gi.SUNLIT)).sum()))
+    assert flipped.sum() >= 50 and (flipped & (k == gi.SUNLIT)).sum() >= 20 and (flipped & (r["mesh"] == M["wall"])).sum() >= 50
+    sun = hr.sun_direction(view)
+    turned = flipped & (k == gi.SUNLIT)
+    assert (hr.dot(r["Nh"][turned], np.broadcast_to(sun, r["Nh"][turned].shape)) > 0).all(), "lit after the turn"
+    assert (hr.dot(-r["Nh"][turned], np.broadcast_to(sun, r["Nh"][turned].shape)) < 0).all(), "and not before it"
+    for name in ("metal", "dielectric", "pbr", "mirrored"):
+        assert (r["mesh"] == M[name]).sum() >= 20, name
+    assert ((r["mesh"] == M["mirrored"]) & (k == gi.SUNLIT)).sum() >= 10
+    zero = r["mesh"] == M["zero"]
+    assert zero.sum() >= 10 and (k[zero] == gi.DARK).all() and not r["shadowed"][zero].any() and np.isnan(r["Nh"][zero]).all()
+    assert totals[2] == (k == gi.SUNLIT).sum() + r["shadowed"].sum()
+    clamp = (r["mesh"] == M["clamp"]) & (k == gi.SUNLIT)
+    assert clamp.sum() >= 10 and (r["L"][clamp] == (0.0, 16.0, 0.0)).all() and not np.signbit(r["L"][clamp]).any()
+    visible = np.unique(g["pbr"][..., 3][g["position"][..., 3] != 0])
+    assert M["zero"] not in visible and M["clamp"] not in visible and {M["wall"], M["metal"], M["dielectric"], M["pbr"], M["mirrored"]} <= set(visible.tolist())
+    # the texture repeats: the sunlit hits on the wall bring both colours of its checker
+    wall = r["L"][(r["mesh"] == M["wall"]) & (k == gi.SUNLIT)]
+    assert len(np.unique((wall[:, 0] / wall[:, 2]).round(1))) >= 2
+    assert np.isfinite(E).all() and (E >= 0).all()
+
+
+def test_frame_numbers_that_wrap_give_other_rays():
+    """(frame * 64 + s) ^ SEED_XOR in 32 bits: the views of test_gpu_rtgi_scenes.py's wrap test have the frame numbers it says, and their
+    rays are neither frame 0's nor each other's"""
+    scene = gi.turned_scene()
+    cpu, meshes, view, g = world(scene)
+    views = [view, gi.scene_view(scene, total_samples=2 ** 26 + 8), gi.scene_view(scene, time=-0.0001)]
+    assert [oa.frame_number(v) for v in views] == [0, 2 ** 26 + 8, 2 ** 32 - 1]
+    d = [gi.directions(g, v, 3)[2] for v in views]
+    assert np.isfinite(d[1]).all() and np.isfinite(d[2]).all()
+    assert not np.array_equal(d[0], d[1]) and not np.array_equal(d[0], d[2]) and not np.array_equal(d[1], d[2])
+    # 2^26 + 8 wraps onto frame 8: the same words, the same rays
+    assert np.array_equal(d[1], gi.directions(g, gi.scene_view(scene, total_samples=8), 3)[2])
