@@ -482,4 +482,11 @@ __device__ __forceinline__ uint32_t wave_append(uint32_t* counter, bool pred) {
    return base + prefix;
 }
 
+// Wave sum (in 32 bits), then lane 0 adds it to the counter unless it is zero: one atomic per wave. Reached by all lanes of the wave.
+template <typename T>
+__device__ __forceinline__ void wave_add(T* counter, uint32_t x) {
+   for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off);
+   if (lane_id() == 0 && x) atomicAdd(counter, (T)x);
+}
+
 }  // namespace uh

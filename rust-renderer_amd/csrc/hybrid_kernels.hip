@@ -6,6 +6,7 @@
 #include "device_types.h"
 #include "hybrid_shading.h"
 #include "ibl_device.h"
+#include "item_walk.h"
 #include "kernel_common.h"
 #include "path_shading.h"
 #include "traversal.h"
@@ -64,41 +65,25 @@ __global__ __launch_bounds__(kBlock) void k_hybrid_gbuffer_resolve(SceneDev sc, 
    }
 }
 
-// rt_shadows.rgen:17-38: one any-hit ray per pixel toward the sun from the G-buffer's texel corner. Persistent waves with the LDS refill
-// of k_trace_shadow; the pool carries no ray records (the lane that takes pixel p makes its ray from the G-buffer there).
+// rt_shadows.rgen:17-38: one any-hit ray per pixel toward the sun from the G-buffer's texel corner, an item walk (item_walk.h) over the
+// pixels: the lane that takes pixel p makes its ray from the G-buffer there.
 __global__ __launch_bounds__(kBlock, 5) void k_hybrid_shadow(SceneDev sc, HybridDev hd) {
-   __shared__ uint32_t s_stack[kWavesPerBlock][kLdsStack][64];
-   __shared__ RayPool<0> s_pool[kWavesPerBlock];
-   const uint32_t lane = lane_id();
-   const uint32_t wave = threadIdx.x >> 6;
-   uint32_t* lds_col = &s_stack[wave][0][lane];
-   RayPool<0>& pool = s_pool[wave];
-   RaySource src;
-   src.queue = nullptr;
-   src.count = hd.W * hd.H;
-   src.cursor = nullptr;
-   src.wave_index = blockIdx.x * kWavesPerBlock + wave;
-   src.num_waves = gridDim.x * kWavesPerBlock;
-   auto source_of = [](int, uint32_t) { return (const float4*)nullptr; };
-   Feeder<0> f;
+   __shared__ ItemWalkLds s_walk;
    Trav t;
-   t.cur = kEmptyRef;
-   t.sp = 0;
-   uint32_t pix = 0, n_nodes = 0, n_tris = 0;
    uint32_t spill[kSpillStack];
+   ItemWalk w(s_walk, t, spill, nullptr, hd.W * hd.H);
+   uint32_t pix = 0;
    const V3 sun = v3(hd.sun_dir[0], hd.sun_dir[1], hd.sun_dir[2]);  // rgen:28
-   auto take = [&](uint32_t slot) {
-      pix = f.pool_base + slot;
+   auto start = [&](uint32_t item) {
+      pix = item;
       const uint32_t px = pix % hd.W, py = pix / hd.W;
       const V3 p = gbuffer_fetch(hd.pos, hd.W, px, py), nn = gbuffer_fetch(hd.nrm, hd.W, px, py);  // rgen:22-24 (not renormalised)
       const V3 o = offset_ray(p, nn);                                                                // rgen:25
       trav_init(t, make_float4(o.x, o.y, o.z, 0.001f), make_float4(sun.x, sun.y, sun.z, 10000.0f), 0.001f, 10000.0f, INFINITY);
    };
-   while (refill_lanes<0>(f, src, pool, t.cur == kEmptyRef, source_of, take)) {
-      if (t.cur != kEmptyRef) {
-         bool occluded = false;
-         if (trav_step<true, false>(sc.nodes, sc.tris, t, lds_col, spill, occluded, n_nodes, n_tris)) hd.shadow[pix] = occluded ? 0 : 255;  // rgen:34-37
-      }
+   while (w.next(false, start)) {
+      bool occluded;
+      if (walk_step<true, false>(w, sc, occluded)) hd.shadow[pix] = occluded ? 0 : 255;  // rgen:34-37
    }
 }
 
@@ -108,22 +93,15 @@ __device__ __forceinline__ float gbuffer_fetch_w(const float4* __restrict__ g, u
    return ((g[(size_t)y0 * W + x0].w + g[(size_t)y0 * W + px].w) + (g[(size_t)py * W + x0].w + g[(size_t)py * W + px].w)) * 0.25f;
 }
 
-// rt_reflections.rgen:34-47, the test: the material of uint(filtered pbr.a) is metal. Metal pixels are appended to a dense queue (one
-// atomic per wave), every other pixel gets (0, 0, 0, 0) here.
+// rt_reflections.rgen:34-47, the test: the material of uint(filtered pbr.a) is metal. Metal pixels are queued (queue_pixels,
+// kernel_common.h), every other pixel gets (0, 0, 0, 0) here.
 __global__ __launch_bounds__(kBlock) void k_hybrid_reflect_classify(SceneDev sc, HybridDev hd) {
-   const uint32_t n = hd.W * hd.H, groups = (n + 63) / 64, lane = lane_id();
-   for (uint32_t g = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); g < groups; g += gridDim.x * kWavesPerBlock) {
-      const uint32_t pix = g * 64u + lane;
-      const bool own = pix < n;
-      bool metal = false;
-      if (own) {
-         const uint32_t material = (uint32_t)gbuffer_fetch_w(hd.pbr, hd.W, pix % hd.W, pix / hd.W);  // rgen:34: the filtered index, truncated
-         metal = material < sc.num_meshes && sc.meshes[material].type == 1.0f;                       // rgen:38
-         if (!metal) hd.refl[pix] = make_uchar4(0, 0, 0, 0);                                         // rgen:46
-      }
-      const uint32_t slot = wave_append(hd.counter, metal);
-      if (metal) hd.queue[slot] = pix;
-   }
+   queue_pixels(hd.W * hd.H, hd.counter, hd.queue, [&](uint32_t pix) {
+      const uint32_t material = (uint32_t)gbuffer_fetch_w(hd.pbr, hd.W, pix % hd.W, pix / hd.W);  // rgen:34: the filtered index, truncated
+      const bool metal = material < sc.num_meshes && sc.meshes[material].type == 1.0f;            // rgen:38
+      if (!metal) hd.refl[pix] = make_uchar4(0, 0, 0, 0);                                         // rgen:46
+      return metal;
+   });
 }
 
 // rt_reflections.rgen:22-44 + .rchit:22-64 + .rmiss:9-24 for the queued metal pixels: closest hit, then a lane shades its own ray. kIbl: the
@@ -173,77 +151,51 @@ __global__ __launch_bounds__(kBlock) void k_hybrid_reflect(SceneDev sc, HybridDe
 }
 
 // The reservoir lights (UH_HYBRID_RESTIR_LIGHTS; DESIGN.md section 2, "Reservoir lights"): which pixels cast a ray toward the light of
-// their spatial reservoir. One lane per pixel; every texel of the visibility image is written 0 here, the pixels that cast are appended to
-// a dense queue (one atomic per wave). The cull is direct_lighting's own NdotL (light_term): a culled pixel's term would be exactly zero.
+// their spatial reservoir. Every texel of the visibility image is written 0 here, the pixels that cast are queued (queue_pixels,
+// kernel_common.h). The cull is direct_lighting's own NdotL (light_term): a culled pixel's term would be exactly zero.
 __global__ __launch_bounds__(kBlock) void k_hybrid_restir_classify(HybridDev hd, HybridRestirDev rl) {
-   const uint32_t n = hd.W * hd.H, groups = (n + 63) / 64, lane = lane_id();
-   for (uint32_t g = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); g < groups; g += gridDim.x * kWavesPerBlock) {
-      const uint32_t pix = g * 64u + lane;
-      bool cast = false;
-      if (pix < n) {
-         rl.vis[pix] = 0;
-         const float4 P4 = hd.pos[pix];
-         const UhReservoir r = rl.reservoirs[pix];
-         if (P4.w != 0.0f && r.Y >= 0 && (uint32_t)r.Y < rl.num_lights && r.W_X > 0.0f && r.W_X < INFINITY) {
-            const UhGpuLight& l = rl.raw_lights[r.Y];
-            if (l.light_type == 1.0f || l.light_type == 2.0f) {                                   // HybridLight::mode 1 or 2
-               const float4 N4 = hd.nrm[pix];
-               const V3 ptl = v3(l.position[0], l.position[1], l.position[2]) - v3(P4.x, P4.y, P4.z);
-               const float d = sqrtf(dot3(ptl, ptl));
-               const V3 L = ptl * (1.0f / d);
-               cast = fmaxf(dot3(v3(N4.x, N4.y, N4.z), L), 0.0f) != 0.0f;                         // NaN: culled
-            }
-         }
-      }
-      const uint32_t slot = wave_append(rl.counters, cast);
-      if (cast) rl.queue[slot] = pix;
-   }
+   queue_pixels(hd.W * hd.H, rl.counters, rl.queue, [&](uint32_t pix) {
+      rl.vis[pix] = 0;
+      const float4 P4 = hd.pos[pix];
+      const UhReservoir r = rl.reservoirs[pix];
+      if (!(P4.w != 0.0f && r.Y >= 0 && (uint32_t)r.Y < rl.num_lights && r.W_X > 0.0f && r.W_X < INFINITY)) return false;
+      const UhGpuLight& l = rl.raw_lights[r.Y];
+      if (!(l.light_type == 1.0f || l.light_type == 2.0f)) return false;                      // HybridLight::mode 1 or 2
+      const float4 N4 = hd.nrm[pix];
+      const V3 ptl = v3(l.position[0], l.position[1], l.position[2]) - v3(P4.x, P4.y, P4.z);
+      const float d = sqrtf(dot3(ptl, ptl));
+      const V3 L = ptl * (1.0f / d);
+      return fmaxf(dot3(v3(N4.x, N4.y, N4.z), L), 0.0f) != 0.0f;                               // NaN: culled
+   });
 }
 
 // One any-hit ray per queued pixel toward its reservoir's light: reference.rgen:113-119 as the path tracer pins it (make_shadow_ray<true>),
-// from offset_ray of the pixel's own G-buffer texels. Persistent waves with the LDS refill of k_hybrid_shadow; the pool carries the pixel
-// ids alone (the lane that takes one makes its ray from the G-buffer, the reservoir and the light table there). No shading here: the
-// deferred pass, which holds the surface terms anyway, adds the light where this kernel stores 255.
+// from offset_ray of the pixel's own G-buffer texels, an item walk (item_walk.h) over the queued pixel ids: the lane that takes one makes
+// its ray from the G-buffer, the reservoir and the light table there. No shading here: the deferred pass, which holds the surface terms
+// anyway, adds the light where this kernel stores 255.
 __global__ __launch_bounds__(kBlock, 5) void k_hybrid_restir_trace(SceneDev sc, FrameParams fp, HybridDev hd, HybridRestirDev rl) {
-   __shared__ uint32_t s_stack[kWavesPerBlock][kLdsStack][64];
-   __shared__ RayPool<0> s_pool[kWavesPerBlock];
-   const uint32_t lane = lane_id();
-   const uint32_t wave = threadIdx.x >> 6;
-   uint32_t* lds_col = &s_stack[wave][0][lane];
-   RayPool<0>& pool = s_pool[wave];
-   RaySource src;
-   src.queue = rl.queue;
-   src.count = rl.counters[0];
-   src.cursor = nullptr;
-   src.wave_index = blockIdx.x * kWavesPerBlock + wave;
-   src.num_waves = gridDim.x * kWavesPerBlock;
-   auto source_of = [](int, uint32_t) { return (const float4*)nullptr; };
-   Feeder<0> f;
+   __shared__ ItemWalkLds s_walk;
    Trav t;
-   t.cur = kEmptyRef;
-   t.sp = 0;
-   uint32_t pix = 0, n_nodes = 0, n_tris = 0, n_occluded = 0;
    uint32_t spill[kSpillStack];
-   auto take = [&](uint32_t slot) {
-      pix = pool.id[slot];
+   ItemWalk w(s_walk, t, spill, rl.queue, rl.counters[0]);
+   uint32_t pix = 0, n_occluded = 0;
+   auto start = [&](uint32_t item) {
+      pix = item;
       const float4 P4 = hd.pos[pix], N4 = hd.nrm[pix];
       const V3 o = offset_ray(v3(P4.x, P4.y, P4.z), v3(N4.x, N4.y, N4.z));
       const ShadowRay s = make_shadow_ray<true>(sc, fp, make_float4(o.x, o.y, o.z, 0.0f), (uint32_t)rl.reservoirs[pix].Y);
       trav_init(t, s.ro, s.rd, s.ro.w, s.rd.w, s.tlimit);
    };
-   while (refill_lanes<0>(f, src, pool, t.cur == kEmptyRef, source_of, take)) {
-      if (t.cur != kEmptyRef) {
-         bool occluded = false;
-         if (trav_step<true, false>(sc.nodes, sc.tris, t, lds_col, spill, occluded, n_nodes, n_tris)) {
-            if (occluded)
-               n_occluded++;
-            else
-               rl.vis[pix] = 255;
-         }
+   while (w.next(false, start)) {
+      bool occluded;
+      if (walk_step<true, false>(w, sc, occluded)) {
+         if (occluded)
+            n_occluded++;
+         else
+            rl.vis[pix] = 255;
       }
    }
-   for (int off = 32; off > 0; off >>= 1) n_occluded += __shfl_down(n_occluded, off);  // one atomic per wave
-   if (lane == 0 && n_occluded) atomicAdd(&rl.counters[1], n_occluded);
+   wave_add(&rl.counters[1], n_occluded);
 }
 
 void launch_hybrid_clear(const LaunchCfg& c, const HybridDev& hd) {
@@ -262,13 +214,11 @@ void launch_hybrid_gbuffer(const LaunchCfg& c, const FrameParams& fp, const Scen
    launch_hybrid_gbuffer_resolve(c, sc, hd);
 }
 void launch_hybrid_shadows(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd) {
-   const uint32_t full = c.num_cus * c.shadow_blocks_per_cu, need = (hd.W * hd.H + kBlock - 1) / kBlock;
-   k_hybrid_shadow<<<dim3(need < full ? need : full), kBlock, 0, c.stream>>>(sc, hd);
+   k_hybrid_shadow<<<persistent_grid(hd.W * hd.H, c.num_cus * c.shadow_blocks_per_cu), kBlock, 0, c.stream>>>(sc, hd);
 }
 void launch_hybrid_restir_lights(const LaunchCfg& c, const FrameParams& fp, const SceneDev& sc, const HybridDev& hd, const HybridRestirDev& rl) {
    k_hybrid_restir_classify<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(hd, rl);
-   const uint32_t full = c.num_cus * c.shadow_blocks_per_cu, need = (hd.W * hd.H + kBlock - 1) / kBlock;
-   k_hybrid_restir_trace<<<dim3(need < full ? need : full), kBlock, 0, c.stream>>>(sc, fp, hd, rl);
+   k_hybrid_restir_trace<<<persistent_grid(hd.W * hd.H, c.num_cus * c.shadow_blocks_per_cu), kBlock, 0, c.stream>>>(sc, fp, hd, rl);
 }
 void launch_hybrid_reflections(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd, const IblMaps* ibl) {
    k_hybrid_reflect_classify<<<stream_grid(c, hd.W * hd.H), kBlock, 0, c.stream>>>(sc, hd);
@@ -457,13 +407,7 @@ __global__ __launch_bounds__(kBlock) void k_hybrid_deferred(SceneDev sc, HybridD
 // geometry pixels cost nothing; skip (nullable): the marching-cubes pass's visibility, whose covered pixels fail the atmosphere pass's
 // depth test
 __global__ __launch_bounds__(kBlock) void k_hybrid_sky_classify(HybridDev hd, HybridFrameDev fd, const uint32_t* __restrict__ skip) {
-   const uint32_t n = hd.W * hd.H, groups = (n + 63) / 64, lane = lane_id();
-   for (uint32_t g = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); g < groups; g += gridDim.x * kWavesPerBlock) {
-      const uint32_t pix = g * 64u + lane;
-      const bool sky = pix < n && hd.pos[pix].w == 0.0f && (!skip || skip[pix] == 0xFFFFFFFFu);
-      const uint32_t slot = wave_append(fd.sky_counter, sky);
-      if (sky) hd.queue[slot] = pix;
-   }
+   queue_pixels(hd.W * hd.H, fd.sky_counter, hd.queue, [&](uint32_t pix) { return hd.pos[pix].w == 0.0f && (!skip || skip[pix] == 0xFFFFFFFFu); });
 }
 // kCube (cubemap_enabled = 1): textureLod(environment, dir * (1, -1, 1), 2) (frag:27-29) instead of IntegrateScattering
 template <bool kCube>

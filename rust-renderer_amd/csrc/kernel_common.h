@@ -1,7 +1,8 @@
-// kernel_common.h — what the kernel files (kernels.hip, path_fused.hip, restir.hip, tiles.hip, hybrid_kernels.hip) share besides the device
-// arithmetic: the block size, the launch-grid helpers of their launchers, and three small device functions that kernels of more than one
-// file call (resolve_color: the path tracer's resolve and the tile composition; gbuffer_fetch: the ReSTIR passes and the hybrid passes;
-// rtao_normal: rtao.hip and rtgi.hip).
+// kernel_common.h — what the kernel files (kernels.hip, path_fused.hip, restir.hip, tiles.hip, hybrid_kernels.hip, rtao.hip, rtgi.hip) share
+// besides the device arithmetic: the block size, the launch-grid helpers of their launchers, and four small device functions that kernels
+// of more than one file call (resolve_color: the path tracer's resolve and the tile composition; gbuffer_fetch: the ReSTIR passes and the
+// hybrid passes; rtao_normal: rtao.hip and rtgi.hip; queue_pixels: every classify kernel of the hybrid frame). The hybrid frame's ray
+// passes share more: their persistent walk is item_walk.h, the tile filter of rtao.hip and rtgi.hip is edge_filter.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,11 +39,29 @@ __device__ __forceinline__ bool rtao_normal(float4 N4, V3& nn) {
    return fabsf(nn.x) < INFINITY && fabsf(nn.y) < INFINITY && fabsf(nn.z) < INFINITY;  // NaN: false
 }
 
+// The classify of the hybrid frame's passes: one lane per pixel of the n, the pixels that satisfy pred(pix) are appended to a dense queue
+// (one atomic per wave: wave group g holds pixels g * 64 + lane). pred is called once for every pixel: a kernel clears its texels there.
+template <typename Pred>
+__device__ __forceinline__ void queue_pixels(uint32_t n, uint32_t* counter, uint32_t* queue, Pred&& pred) {
+   const uint32_t groups = (n + 63) / 64, lane = lane_id();
+   for (uint32_t g = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); g < groups; g += gridDim.x * kWavesPerBlock) {
+      const uint32_t pix = g * 64u + lane;
+      const bool queued = pix < n && pred(pix);
+      const uint32_t slot = wave_append(counter, queued);
+      if (queued) queue[slot] = pix;
+   }
+}
+
 // ---- launch grids
 static inline dim3 stream_grid(const LaunchCfg& c, uint32_t n) {
    uint32_t blocks = (n + kBlock - 1) / kBlock;
    uint32_t cap = c.num_cus * 8;
    return dim3(blocks < cap ? (blocks ? blocks : 1) : cap);
+}
+// persistent waves that take their work in chunks: at most one lane per item, at most `full` blocks
+static inline dim3 persistent_grid(uint64_t items, uint32_t full) {
+   const uint64_t need = (items + kBlock - 1) / kBlock;
+   return dim3((uint32_t)(need < full ? (need ? need : 1) : full));
 }
 // grids of sharded kernels are whole multiples of kShards (blockIdx % kShards = shard)
 static inline dim3 sharded_grid(uint32_t blocks) {

@@ -136,8 +136,7 @@ __global__ __launch_bounds__(kBlock) void k_spatial_reuse(FrameParams fp, SceneD
 
 // the reservoir kernels stage the light table per block: no more blocks than the rows at hand can feed
 static inline dim3 reservoir_grid(const LaunchCfg& c, const RowSpans& spans) {
-   const uint32_t full = c.num_cus * 4, need = (spans.total() + kBlock - 1) / kBlock;
-   return dim3(need < full ? (need ? need : 1) : full);
+   return persistent_grid(spans.total(), c.num_cus * 4);
 }
 void launch_reset_reservoirs(const LaunchCfg& c, const FrameParams& fp, const Images& im, const RowSpans& spans) {
    if (spans.total()) k_reset_reservoirs<<<stream_grid(c, spans.total()), kBlock, 0, c.stream>>>(im, spans);
