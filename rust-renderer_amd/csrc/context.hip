@@ -3,10 +3,9 @@
 // build_path_tracing_render_graph (utopian/src/renderers/mod.rs:189-375) for this path only.
 // struct uh_ctx is context_state.h; meshes, the tree builders and the refit are scene_build.hip; the hybrid and the forward graph
 // (uh_render_hybrid, uh_render_forward) are hybrid_graph.hip and forward_graph.hip over raster_driver.hip, the denoiser denoise_graph.hip;
-// the sun and camera grids' upkeep is grid_cache.hip.
+// the sun and camera grids' upkeep is grid_cache.hip; uh_set_option is options.hip; a frame split over several GPUs - the tile and band
+// partitions, the tile composition - is partition.hip, the RCCL link rccl_link.hip.
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>  // types only: the library opens librccl at run time (uh_rccl_attach)
-#include <dlfcn.h>
 
 #include <algorithm>
 #include <atomic>
@@ -23,6 +22,7 @@
 #include "device_scan.h"
 #include "device_types.h"
 #include "texture_layout.h"
+#include "tile_partition.h"
 #include "utopian_hip.h"
 
 using namespace uh;
@@ -60,6 +60,9 @@ void end_timed(uh_ctx* c, hipStream_t stream = nullptr) {
    if (!c->time_kernels) return;
    (void)hipEventRecord(c->pending.back().stop, stream ? stream : c->stream);
 }
+
+}  // namespace
+
 void drain_timed(uh_ctx* c) {
    for (EventPair& ep : c->pending) {
       float ms = 0.0f;
@@ -72,8 +75,6 @@ void drain_timed(uh_ctx* c) {
    }
    c->pending.clear();
 }
-
-}  // namespace
 
 LaunchCfg cfg(uh_ctx* c) {
    return LaunchCfg{c->stream, c->num_cus, c->closest_blocks_per_cu, c->shadow_blocks_per_cu, c->count_visits, c->fused_blocks_per_cu};
@@ -173,7 +174,7 @@ int uh_create(int device_ordinal, uint32_t width, uint32_t height, uh_ctx** out)
    for (int i = 0; i < 3; i++) c->im.reservoirs[i] = c->reservoirs[i].p;
    c->im.prev_spatial = c->reservoirs[2].p;
    c->res_stride = n;
-   c->rp_band_rows = height;
+   c->bands.rows = height;
    c->cam.limits.max_walk = 48;          // a pixel listing more packets than this hands its ray to the tree walk
    c->cam.limits.max_mean_list = 24.0;   // entries per occupied pixel beyond which the grid is refused (the tree walk costs about 20 records per ray)
    c->cam.limits.max_fallback_area = 2.0;
@@ -194,7 +195,8 @@ void uh_destroy(uh_ctx* c) {
    (void)hipSetDevice(c->device);
    // the communicator's collectives were enqueued on the reservoir stream: it goes (and every stream is drained) while that
    // stream still exists
-   uh_rccl_detach(c);
+   if (c->bands.link) (void)sync_all(c);
+   c->bands.destroy();
    // every stream idle before anything goes; the streams themselves go LAST, after every event that was recorded on or waited for by
    // one of them (slot streams wait for the reservoir stream's event and the other way round)
    (void)hipDeviceSynchronize();
@@ -260,10 +262,7 @@ void uh_destroy(uh_ctx* c) {
       (void)hipStreamDestroy(c->restir_stream);
       c->restir_stream = nullptr;
    }
-   c->owned_pixels.release();
-   c->tile_send.release();
-   c->tile_recv.release();
-   if (c->ev_compose) (void)hipEventDestroy(c->ev_compose);
+   c->tiles.destroy();
    delete c;
 }
 
@@ -354,12 +353,12 @@ extern "C++" FrameParams make_params(uh_ctx* c, const UhViewUniformData& v) {
    fp.num_lights_used = v.num_lights < v.max_num_lights_used ? v.num_lights : v.max_num_lights_used;
    fp.temporal_enabled = v.temporal_reuse_enabled;
    fp.spatial_enabled = v.spatial_reuse_enabled;
-   fp.tp_rank = c->tp_rank;
-   fp.tp_world = c->tp_world;
-   fp.tp_tile = c->tp_tile;
-   fp.tiles_x = (c->W + c->tp_tile - 1) / c->tp_tile;
-   fp.owned_pixels = c->tp_world > 1 ? c->owned_pixels.p : nullptr;
-   fp.n_owned = c->tp_world > 1 ? c->n_owned : c->W * c->H;
+   fp.tp_rank = c->tiles.rank;
+   fp.tp_world = c->tiles.world;
+   fp.tp_tile = c->tiles.tile;
+   fp.tiles_x = tiles_across(c->W, c->tiles.tile);
+   fp.owned_pixels = c->tiles.world > 1 ? c->tiles.owned_pixels.p : nullptr;
+   fp.n_owned = traced_pixels(c);
    return fp;
 }
 
@@ -376,7 +375,7 @@ extern "C++" int sync_all(uh_ctx* c) {
 
 // slot i exists and can hold `batch` frames worth of paths
 static int ensure_slot(uh_ctx* c, uint32_t i, uint32_t batch = 1) {
-   size_t need = (size_t)(c->tp_world > 1 ? c->n_owned : c->W * c->H) * batch;  // path ids are dense over the rank's owned pixels
+   size_t need = (size_t)traced_pixels(c) * batch;  // path ids are dense over the rank's owned pixels
    if (need < 64) need = 64;  // a rank that owns no pixel (more ranks than tiles) still gets a well-formed, empty slot
    Slot& s = c->slots[i];
    if (s.ready && s.capacity >= need) return UH_OK;
@@ -531,34 +530,6 @@ struct uh_batch {
 
 static UhReservoir* spatial_buf(uh_ctx* c, int slot) { return slot ? c->spatial_ring.p + (size_t)(slot - 1) * c->res_stride : c->reservoirs[2].p; }
 
-// rows of this context's reservoir passes (uh_set_restir_partition): its band, the band's 30-row neighbourhood (plus the last
-// row for the first band: spatial_reuse.rgen:54's wrapped offset is clamped to size - 1), and for the G-buffer cast the row
-// above each of those (the 2 x 2 corner filter)
-static void restir_rows(const uh_ctx* c, UhRestirRows& r) {
-   const uint32_t H = c->H, B = c->rp_world > 1 ? c->rp_band_rows : H;
-   r = UhRestirRows{};
-   r.rows_per_band = B;
-   const uint32_t b0 = std::min<uint64_t>((uint64_t)c->rp_rank * B, H), b1 = std::min<uint64_t>((uint64_t)b0 + B, H);
-   r.band_row0 = b0;
-   r.band_rows = b1 - b0;
-   if (b1 == b0) return;  // more ranks than bands: nothing to do here
-   const uint32_t halo = 30;
-   const uint32_t t0 = b0 > halo ? b0 - halo : 0, t1 = std::min<uint64_t>((uint64_t)b1 + halo, H);
-   r.reuse_row0 = t0;
-   r.reuse_rows = t1 - t0;
-   if (b0 < halo && t1 < H) {
-      r.reuse_extra_row0 = H - 1;
-      r.reuse_extra_rows = 1;
-   }
-   const uint32_t g0 = t0 > 0 ? t0 - 1 : 0;
-   r.cast_row0 = g0;
-   r.cast_rows = t1 - g0;
-   if (r.reuse_extra_rows) {
-      const uint32_t e0 = std::max(H >= 2 ? H - 2 : 0u, t1);  // rows H - 2 and H - 1, without what the first interval already holds
-      r.cast_extra_row0 = e0;
-      r.cast_extra_rows = H - e0;
-   }
-}
 static RowSpans spans_of(const uh_ctx* c, uint32_t row0, uint32_t rows, uint32_t extra0, uint32_t extra_rows) { return RowSpans{{row0, extra0}, {rows, extra_rows}, c->W}; }
 
 static int batch_begin(uh_ctx* c, const UhViewUniformData* view, uint32_t pass_mask, uint32_t batch, uh_batch& bs) {
@@ -613,7 +584,7 @@ static int batch_begin(uh_ctx* c, const UhViewUniformData* view, uint32_t pass_m
          HIP_TRY(c, c->spatial_ring.alloc((size_t)(kSpatialRing - 1) * c->res_stride));
          // every slot is written before it is read - by this context's passes; under a row partition other ranks' bands arrive by
          // the exchange, and a caller that times one rank without one (exchange == NULL) must still read defined reservoirs
-         if (c->rp_world > 1) HIP_TRY(c, hipMemsetAsync(c->spatial_ring.p, 0, c->spatial_ring.n * sizeof(UhReservoir), c->restir_stream));
+         if (c->bands.world > 1) HIP_TRY(c, hipMemsetAsync(c->spatial_ring.p, 0, c->spatial_ring.n * sizeof(UhReservoir), c->restir_stream));
          HIP_TRY(c, hipStreamSynchronize(c->stream));  // slot 0 (zeroed at creation or uh_write_reservoirs) is the history
       }
       bs.rc = cfg(c);
@@ -661,7 +632,7 @@ static int batch_restir_frame(uh_ctx* c, uh_batch& bs, uint32_t f) {
       launch_spatial_reuse(bs.rc, ff, c->scene, im, band);
       c->spatial_cur = nxt;
       c->im.reservoirs[2] = spatial_buf(c, nxt);
-      if (c->rp_world > 1) {
+      if (c->bands.world > 1) {
          if (!c->ev_band[nxt]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_band[nxt], hipEventDisableTiming));
          HIP_TRY(c, hipEventRecord(c->ev_band[nxt], c->restir_stream));
       }
@@ -673,10 +644,10 @@ static int batch_restir_frame(uh_ctx* c, uh_batch& bs, uint32_t f) {
 // the other ranks' bands of the buffer frame f's spatial pass wrote (uh_set_restir_partition)
 static int batch_exchange(uh_ctx* c, uh_batch& bs, uint32_t f) {
    (void)f;
-   if (!bs.restir_frame || !c->rp_exchange || !(bs.pass_mask & UH_PASS_SPATIAL_REUSE)) return UH_OK;  // world 1 with an exchange: a one-rank all-gather (rehearsals)
+   if (!bs.restir_frame || !c->bands.exchange || !(bs.pass_mask & UH_PASS_SPATIAL_REUSE)) return UH_OK;  // world 1 with an exchange: a one-rank all-gather (rehearsals)
    HIP_TRY(c, hipSetDevice(c->device));
-   const uint64_t band_bytes = (uint64_t)c->rp_band_rows * c->W * sizeof(UhReservoir);
-   if (int st = c->rp_exchange(c->rp_user, (void*)c->restir_stream, (void*)c->im.reservoirs[2], band_bytes, c->rp_rank, c->rp_world))
+   const uint64_t band_bytes = (uint64_t)c->bands.rows * c->W * sizeof(UhReservoir);
+   if (int st = c->bands.exchange(c->bands.user, (void*)c->restir_stream, (void*)c->im.reservoirs[2], band_bytes, c->bands.rank, c->bands.world))
       return fail(c, UH_ERR_HIP, std::string("the reservoir exchange reported error ") + std::to_string(st));
    return UH_OK;
 }
@@ -743,7 +714,7 @@ static int plan_batch(uh_ctx* c, uint32_t pass_mask, uint32_t* out_batch) {
       // 6,398 Mrays/s, the short paths of the iso-surface scene 4,974 / 5,393 / - / 6,223 (tools/sweep_batch.sh,
       // profiles/README.md) - within 33 M path-state records per slot (3.7 GB; path ids are dense over the pixels a rank
       // owns, so its wavefronts carry more frames than a whole frame's would)
-      const uint64_t pixels = (uint64_t)c->W * c->H, owned = c->n_owned ? c->n_owned : pixels;
+      const uint64_t pixels = (uint64_t)c->W * c->H, owned = c->tiles.n_owned ? c->tiles.n_owned : pixels;
       uint64_t b = (32u << 20) / (owned ? owned : 1), cap = (33u << 20) / (owned ? owned : 1);
       if (b > cap) b = cap;
       batch = (uint32_t)(b < 1 ? 1 : b);
@@ -792,7 +763,7 @@ int uhi_exchange_endpoints(uh_ctx* c, void** spatial_base, void** band_event, vo
    if (spatial_base) *spatial_base = (void*)c->im.reservoirs[2];
    if (band_event) *band_event = (void*)c->ev_band[c->spatial_cur];
    if (stream) *stream = (void*)c->restir_stream;
-   if (band_bytes) *band_bytes = (uint64_t)c->rp_band_rows * c->W * sizeof(UhReservoir);
+   if (band_bytes) *band_bytes = (uint64_t)c->bands.rows * c->W * sizeof(UhReservoir);
    return UH_OK;
 }
 
@@ -1016,490 +987,6 @@ int uh_reset_stats(uh_ctx* c) {
    c->frames = 0;
    for (float& ms : c->ms_by_kind) ms = 0.0f;
    c->trace_closest_launches = c->trace_light_launches = 0;
-   return UH_OK;
-}
-
-// The options (24): DESIGN.md section 7 has the table with defaults and what was measured. Variants that two rounds of measurements
-// left behind (batch traversal kernels, wave-per-tile primary rays, sub-frame interleave, the fused coarse-cover look-up, spatial
-// splits, insertion-based tree optimisation, the host-thread grid build) were removed in round 5 together with their options.
-int uh_set_option(uh_ctx* c, const char* name, int value) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!name) return fail(c, UH_ERR_INVALID_ARGUMENT, "null option name");
-   const std::string n(name);
-   auto range = [&](int lo, int hi) { return value >= lo && value <= hi; };
-   auto bad = [&](const char* what) { return fail(c, UH_ERR_INVALID_ARGUMENT, n + " " + what); };
-   // ---- diagnostics
-   if (n == "count_visits")
-      c->count_visits = value != 0;
-   else if (n == "time_kernels") {
-      if (c->time_kernels && !value) {
-         (void)sync_all(c);
-         drain_timed(c);
-      }
-      c->time_kernels = value != 0;
-   }
-   // ---- the tree
-   else if (n == "device_build") {
-      // 0 = host SAH builder; 1 = device build, PLOC under a host SAH top; 2 = device build, radix tree
-      if (!range(0, 2)) return bad("must be 0, 1 (PLOC) or 2 (radix tree)");
-      if (c->device_build != (value != 0) || (value && c->device_build_kind != (uint32_t)value)) c->built = c->topology_valid = false;
-      c->device_build = value != 0;
-      if (value) c->device_build_kind = (uint32_t)value;
-   } else if (n == "ploc_sah_top") {
-      if (!range(0, 1 << 20)) return bad("must be 0..1048576");
-      if (c->ploc_sah_top != (uint32_t)value && c->device_build) c->built = c->topology_valid = false;
-      c->ploc_sah_top = (uint32_t)value;
-   }
-   // ---- the sun grid (sun_grid.h): every change takes effect with the next grid that is built
-   else if (n == "sun_grid")
-      c->sun_grid_enabled = value != 0;  // 0: the sun shadow rays always walk the tree
-   else if (n == "sun_grid_build") {
-      c->sun_x.device_build = value != 0;  // 1: built on the device (sun_grid_build.hip); 0: by the host builder (sun_grid.cpp, the reference implementation)
-      c->sun.cache.invalidate();
-   } else if (n == "sun_grid_density") {
-      if (!range(1, 4096)) return bad("(entries per triangle) must be 1..4096");
-      c->sun.limits.entries_per_triangle = (double)value;
-      c->sun.cache.invalidate();
-   } else if (n == "sun_grid_max_walk") {
-      if (!range(1, 4096)) return bad("(longest list a ray tests itself) must be 1..4096");
-      c->sun.limits.max_walk = (uint32_t)value;
-      c->sun.cache.invalidate();
-   } else if (n == "sun_grid_max_mb") {
-      if (!range(1, 65536)) return bad("must be 1..65536");
-      c->sun.limits.max_entries = ((uint64_t)value << 20) / sizeof(SunGridEntry);
-      c->sun.cache.invalidate();
-   } else if (n == "sun_grid_force") {
-      // 1: the grid is never refused for what it would be worth (more than 12 entries per occupied cell, more than a fifth of the scene's
-      // surface handed to the tree): tests and studies of scenes the defaults would refuse; 0: the defaults
-      const SunGridLimits defaults;
-      c->sun.limits.max_mean_list = value ? 1e30 : defaults.max_mean_list;
-      c->sun.limits.max_fallback_area = value ? 2.0 : defaults.max_fallback_area;
-      c->sun.cache.invalidate();
-   } else if (n == "sun_grid_inline_max_mb") {
-      // the lists a second time as 64-byte records that carry their packet (one round trip per triangle test instead of two): memory budget
-      // in MB; -1 (default) = four times the packet array; 0 = never
-      if (!range(-1, 1 << 20)) return bad("must be -1 (auto: 4 x the packet array), 0 (off) .. 1048576");
-      c->sun_x.inline_max_mb = value;
-      c->sun.cache.invalidate();
-   } else if (n == "sun_verdicts")
-      // 1: the grid's sun kernels leave one bit per ray and the next shading kernel (or the flush) adds the lit paths' throughput to
-      // their radiance; 0: the sun kernels add it themselves. Same images; frames with lights enabled always take the second form
-      c->sun_x.verdicts = value != 0;
-   else if (n == "slim_state")
-      // 1: a pass with sun verdicts and one sample per frame carries the slim path state (device_types.h PathState); 0: never
-      c->slim_state = value != 0;
-   else if (n == "sun_grid_coarse") {
-      // the coarse cover (sun_grid.h): one depth per block of 2^value x 2^value cells, asked before the cell's own record; 0: none
-      if (!range(0, 6)) return bad("(log2 of the block edge in cells) must be 0..6");
-      c->sun_x.coarse_shift = (uint32_t)value;
-      c->sun.cache.invalidate();
-   }
-   // ---- the camera grid
-   else if (n == "camera_grid")
-      c->cam_grid_enabled = value != 0;  // 0: the primary rays always walk the tree
-   else if (n == "camera_grid_max_walk") {
-      if (!range(1, 4096)) return bad("must be 1..4096");
-      c->cam.limits.max_walk = (uint32_t)value;
-      c->cam.cache.invalidate();
-   } else if (n == "camera_grid_walk_whole") {
-      // lists of up to this many packets are walked whole by the grid kernel (those beyond camera_grid_max_walk are not sorted: no early
-      // exit) instead of handing the ray to the tree; 0: every list beyond camera_grid_max_walk goes to the tree
-      if (!range(0, 65536)) return bad("must be 0..65536");
-      c->cam_walk_whole = (uint32_t)value;
-      c->cam.cache.invalidate();
-   } else if (n == "camera_grid_max_mean_list_x10") {
-      if (!range(1, 100000)) return bad("must be 1..100000");
-      c->cam.limits.max_mean_list = value / 10.0;
-      c->cam.cache.invalidate();
-   } else if (n == "primary_implicit")
-      c->primary_implicit = value != 0;  // 0: bounce 0's state planes are stored by k_generate even when the camera grid is in use
-   // ---- what the frames compute
-   else if (n == "full_frame_restir")
-      c->full_frame_restir = value != 0;
-   else if (n == "iso_reference_triangulation")
-      c->iso_reference = value != 0;
-   else if (n == "furnace")
-      c->furnace = value != 0;  // applies to the frames enqueued from now on
-   else if (n == "rtao_order") {
-      // how the rtao trace kernel lays out its work (rtao.hip; same counts whichever): 0 (default) one ray per item, a pixel's samples
-      // together; 1 one ray per item, one sample of consecutive pixels together; 2 one pixel per item, its lane walks the samples
-      if (!range(0, 2)) return bad("must be 0..2");
-      c->hy.ao.order = (uint32_t)value;
-   }
-   else if (n == "rtgi_order") {
-      // how the rtgi closest-hit kernel lays out its work (rtgi.hip; same images whichever): 0 (default) a pixel's samples together;
-      // 1 one sample of consecutive pixels together
-      if (!range(0, 1)) return bad("must be 0 or 1");
-      c->hy.gi.order = (uint32_t)value;
-   }
-   else if (n == "texture_blocks")
-      // 1: the textures added from now on are stored as overlapped blocks, a bilinear footprint in one cache line (texture_layout.h);
-      // 0: as 8x8 tiles, or rows. Same images bit for bit: the same four texel words enter the filter
-      c->texture_blocks = value != 0;
-   else if (n == "shadow_map_size") {
-      if (!range(16, 8192)) return bad("must be 16..8192");
-      if ((uint32_t)value != c->shadow_map_size) {  // the maps go: the deferred pass with shadows is refused until they are rendered again
-         if (int st = sync_all(c)) return st;
-         c->hy.sm.destroy();
-         c->hy.sm.bins.geom = 0;
-         c->hy.sm.size = 0;
-      }
-      c->shadow_map_size = (uint32_t)value;
-   }
-   // ---- how the frames are scheduled
-   else if (n == "overlap")
-      c->overlap_miss = c->overlap_shadow = value != 0;  // k_shade_miss and the shadow traversals on the slot's side stream
-   else if (n == "batch_frames") {
-      if (!range(0, (int)kMaxBatchFrames)) return bad("must be 0 (auto) .. 32");
-      c->batch_frames = (uint32_t)value;
-   } else if (n == "frames_in_flight") {
-      if (!range(1, (int)kMaxSlots)) return bad("must be 1..8");
-      (void)sync_all(c);
-      c->frames_in_flight = (uint32_t)value;
-      c->next_slot = 0;
-   } else if (n == "fused_bounces") {
-      // 0: a lone frame runs the wavefront of a batch (four launches per bounce); 1: its bounces 1 .. in one persistent kernel; 2..8: that
-      // kernel's blocks per CU
-      if (!range(-1, 8)) return bad("must be 0 (off), 1 (on when no frame is in flight), -1 (always on) or 2..8 (as 1, and blocks per CU of its grid)");
-      c->fused_bounces = value != 0;
-      c->fused_always = value == -1;
-      if (value >= 2) c->fused_blocks_per_cu = (uint32_t)value;
-   } else if (n == "trace_blocks_per_cu") {
-      if (!range(1, 8)) return bad("must be 1..8");
-      c->closest_blocks_per_cu = c->shadow_blocks_per_cu = (uint32_t)value;  // persistent grids of the traversal kernels
-   } else
-      return fail(c, UH_ERR_INVALID_ARGUMENT, "unknown option: " + n);
-   return UH_OK;
-}
-
-int uh_set_tile_partition(uh_ctx* c, uint32_t rank, uint32_t world, uint32_t tile_size) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (world == 0 || rank >= world || tile_size == 0) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_set_tile_partition: need rank < world, tile_size > 0");
-   HIP_TRY(c, hipSetDevice(c->device));
-   if (int st = sync_all(c)) return st;
-   c->tp_rank = rank;
-   c->tp_world = world;
-   c->tp_tile = tile_size;
-   c->n_owned = c->W * c->H;
-   c->owned_pixels.release();
-   if (world > 1) {
-      const uint32_t tiles_x = (c->W + tile_size - 1) / tile_size;
-      std::vector<uint32_t> own;
-      own.reserve((size_t)c->W * c->H / world + 1);
-      for (uint32_t y = 0; y < c->H; y++)
-         for (uint32_t x = 0; x < c->W; x++)
-            if (((y / tile_size) * tiles_x + x / tile_size) % world == rank) own.push_back(y * c->W + x);
-      c->n_owned = (uint32_t)own.size();
-      HIP_TRY(c, c->owned_pixels.alloc(own.size() ? own.size() : 1));
-      if (!own.empty()) HIP_TRY(c, hipMemcpy(c->owned_pixels.p, own.data(), own.size() * 4, hipMemcpyHostToDevice));
-   }
-   return UH_OK;
-}
-
-int uh_set_restir_partition(uh_ctx* c, uint32_t rank, uint32_t world, UhRestirExchangeFn exchange, void* user) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (world == 0 || rank >= world) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_set_restir_partition: need rank < world");
-   HIP_TRY(c, hipSetDevice(c->device));
-   if (int st = sync_all(c)) return st;
-   const size_t npix = (size_t)c->W * c->H;
-   const uint32_t band_rows = (c->H + world - 1) / world;
-   const size_t stride = std::max(npix, (size_t)band_rows * world * c->W);
-   if (stride != c->res_stride) {
-      // the history (the current slot of the ring) moves into a buffer of the new length, which becomes slot 0
-      DevBuf<UhReservoir> fresh;
-      HIP_TRY(c, fresh.alloc(stride));
-      HIP_TRY(c, hipMemsetAsync(fresh.p, 0, stride * sizeof(UhReservoir), c->stream));
-      HIP_TRY(c, hipMemcpyAsync(fresh.p, c->im.reservoirs[2], npix * sizeof(UhReservoir), hipMemcpyDeviceToDevice, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      c->reservoirs[2].release();
-      c->reservoirs[2] = fresh;
-      fresh.p = nullptr;
-      fresh.n = 0;
-      c->spatial_ring.release();
-      c->res_stride = stride;
-   } else if (c->spatial_cur != 0) {
-      HIP_TRY(c, hipMemcpyAsync(c->reservoirs[2].p, c->im.reservoirs[2], npix * sizeof(UhReservoir), hipMemcpyDeviceToDevice, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-   }
-   c->spatial_cur = 0;
-   for (auto& r : c->spatial_reader) r = nullptr;
-   c->im.reservoirs[2] = c->reservoirs[2].p;
-   c->im.prev_spatial = c->reservoirs[2].p;
-   c->rp_rank = rank;
-   c->rp_world = world;
-   c->rp_band_rows = world > 1 ? band_rows : c->H;
-   c->rp_exchange = exchange;
-   c->rp_user = user;
-   return UH_OK;
-}
-
-int uh_get_restir_rows(uh_ctx* c, UhRestirRows* out) {
-   if (!c || !out) return UH_ERR_INVALID_ARGUMENT;
-   restir_rows(c, *out);
-   return UH_OK;
-}
-
-// ---- the exchange over RCCL. librccl is opened at run time (types from its header, no link dependency): a process that
-// never attaches needs no RCCL at all, and one that has torch's copy loaded gets that same copy (same soname). ----
-namespace {
-struct RcclApi {
-   void* so = nullptr;
-   decltype(&ncclGetUniqueId) GetUniqueId = nullptr;
-   decltype(&ncclCommInitRank) CommInitRank = nullptr;
-   decltype(&ncclCommDestroy) CommDestroy = nullptr;
-   decltype(&ncclAllGather) AllGather = nullptr;
-   decltype(&ncclSend) Send = nullptr;
-   decltype(&ncclRecv) Recv = nullptr;
-   decltype(&ncclGroupStart) GroupStart = nullptr;
-   decltype(&ncclGroupEnd) GroupEnd = nullptr;
-   decltype(&ncclCommCount) CommCount = nullptr;
-   decltype(&ncclGetErrorString) GetErrorString = nullptr;
-   std::string why;
-};
-RcclApi* rccl_api() {
-   static RcclApi api;
-   static bool tried = false;
-   if (tried) return &api;
-   tried = true;
-   for (const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-      api.so = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-      if (api.so) break;
-   }
-   if (!api.so) {
-      api.why = std::string("librccl not found: ") + (dlerror() ? dlerror() : "");
-      return &api;
-   }
-   api.GetUniqueId = (decltype(api.GetUniqueId))dlsym(api.so, "ncclGetUniqueId");
-   api.CommInitRank = (decltype(api.CommInitRank))dlsym(api.so, "ncclCommInitRank");
-   api.CommDestroy = (decltype(api.CommDestroy))dlsym(api.so, "ncclCommDestroy");
-   api.AllGather = (decltype(api.AllGather))dlsym(api.so, "ncclAllGather");
-   api.Send = (decltype(api.Send))dlsym(api.so, "ncclSend");
-   api.Recv = (decltype(api.Recv))dlsym(api.so, "ncclRecv");
-   api.GroupStart = (decltype(api.GroupStart))dlsym(api.so, "ncclGroupStart");
-   api.GroupEnd = (decltype(api.GroupEnd))dlsym(api.so, "ncclGroupEnd");
-   api.CommCount = (decltype(api.CommCount))dlsym(api.so, "ncclCommCount");
-   api.GetErrorString = (decltype(api.GetErrorString))dlsym(api.so, "ncclGetErrorString");
-   if (!api.GetUniqueId || !api.CommInitRank || !api.CommDestroy || !api.AllGather || !api.Send || !api.Recv || !api.GroupStart || !api.GroupEnd) {
-      api.why = "librccl lacks ncclGetUniqueId / ncclCommInitRank / ncclCommDestroy / ncclAllGather / ncclSend / ncclRecv / ncclGroupStart / ncclGroupEnd";
-      api.so = nullptr;
-   }
-   return &api;
-}
-struct RcclLink {
-   ncclComm_t comm = nullptr;
-   int last = 0;
-   uint32_t rank = 0, world = 1;
-};
-// UhRestirExchangeFn: in-place all-gather of the bands, enqueued on the reservoir stream
-int rccl_exchange(void* user, void* stream, void* base, uint64_t band_bytes, uint32_t rank, uint32_t) {
-   RcclLink* l = (RcclLink*)user;
-   l->last = (int)rccl_api()->AllGather((const char*)base + (size_t)rank * band_bytes, base, (size_t)band_bytes, ncclInt8, l->comm, (hipStream_t)stream);
-   return l->last;
-}
-}  // namespace
-
-int uh_rccl_unique_id(uint8_t out_id[128]) {
-   static_assert(sizeof(ncclUniqueId) == 128, "the C ABI hands the id over as 128 bytes");
-   if (!out_id) return UH_ERR_INVALID_ARGUMENT;
-   RcclApi* api = rccl_api();
-   if (!api->so) return UH_ERR_HIP;
-   ncclUniqueId id;
-   if (api->GetUniqueId(&id) != ncclSuccess) return UH_ERR_HIP;
-   memcpy(out_id, &id, 128);
-   return UH_OK;
-}
-
-int uh_rccl_attach(uh_ctx* c, uint32_t rank, uint32_t world, const uint8_t id[128]) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!id || world == 0 || rank >= world) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_rccl_attach: need an id and rank < world");
-   RcclApi* api = rccl_api();
-   if (!api->so) return fail(c, UH_ERR_HIP, "uh_rccl_attach: " + api->why);
-   HIP_TRY(c, hipSetDevice(c->device));
-   uh_rccl_detach(c);
-   RcclLink* l = new RcclLink();
-   ncclUniqueId nid;
-   memcpy(&nid, id, 128);
-   const ncclResult_t r = api->CommInitRank(&l->comm, (int)world, nid, (int)rank);
-   if (r != ncclSuccess) {
-      delete l;
-      return fail(c, UH_ERR_HIP, std::string("ncclCommInitRank: ") + (api->GetErrorString ? api->GetErrorString(r) : "failed"));
-   }
-   l->rank = rank;
-   l->world = world;
-   c->rccl = l;
-   return uh_set_restir_partition(c, rank, world, rccl_exchange, l);
-}
-
-int uh_rccl_detach(uh_ctx* c) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!c->rccl) return UH_OK;
-   (void)hipSetDevice(c->device);
-   (void)sync_all(c);
-   RcclLink* l = (RcclLink*)c->rccl;
-   if (l->comm) (void)rccl_api()->CommDestroy(l->comm);
-   delete l;
-   c->rccl = nullptr;
-   if (c->rp_exchange == rccl_exchange) {
-      c->rp_exchange = nullptr;
-      c->rp_user = nullptr;
-   }
-   return UH_OK;
-}
-
-int uh_rccl_comm_count(uh_ctx* c, uint32_t* out_ranks) {
-   if (!c || !out_ranks) return UH_ERR_INVALID_ARGUMENT;
-   *out_ranks = 0;
-   if (!c->rccl) return UH_OK;
-   RcclLink* l = (RcclLink*)c->rccl;
-   int n = 0;
-   if (!rccl_api()->CommCount || rccl_api()->CommCount(l->comm, &n) != ncclSuccess) return fail(c, UH_ERR_HIP, "ncclCommCount failed");
-   *out_ranks = (uint32_t)n;
-   return UH_OK;
-}
-
-// ---- composition of a tile-partitioned frame, ENQUEUED: nothing below waits on the host ----
-namespace {
-uint64_t max_pack_pixels(uh_ctx* c) {
-   uint64_t need = 0;
-   for (uint32_t r = 0; r < c->tp_world; r++) {
-      uint64_t n = 0;
-      uh_tile_pack_count(c, r, &n);
-      need = n > need ? n : need;
-   }
-   return need;
-}
-// what was just enqueued on the context's stream read or wrote the accumulation image: the next frame's accumulate tail
-// (enqueue_path_trace) and the next composition wait for it
-int mark_composed(uh_ctx* c) {
-   if (!c->ev_compose) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_compose, hipEventDisableTiming));
-   HIP_TRY(c, hipEventRecord(c->ev_compose, c->stream));
-   c->last_acc = c->ev_compose;
-   return UH_OK;
-}
-}  // namespace
-
-// this context's owned tiles, packed into `device_out` (>= uh_tile_pack_count pixels), on the context's stream behind the accumulate
-// tail of every frame in flight
-int uhi_enqueue_pack_tiles(uh_ctx* c, void* device_out, void** out_stream) {
-   if (!c || !device_out) return UH_ERR_INVALID_ARGUMENT;
-   HIP_TRY(c, hipSetDevice(c->device));
-   if (c->last_acc) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->last_acc, 0));
-   launch_pack_tiles(cfg(c), c->accumulation.p, (float4*)device_out, c->W, c->H, c->tp_rank, c->tp_world, c->tp_tile);
-   HIP_TRY(c, hipGetLastError());
-   if (out_stream) *out_stream = (void*)c->stream;
-   return mark_composed(c);
-}
-// the root's composition (k_compose_tiles over `device_all`: world buffers of stride_pixels, uh_compose_tiles' layout) on the context's
-// stream, behind its own frames in flight and behind the `n_waits` events (hipEvent_t) that say the other ranks' tiles have landed
-int uhi_enqueue_compose_tiles(uh_ctx* c, const void* device_all, uint64_t stride_pixels, uint32_t total_samples, uint32_t accumulation_limit, void* const* wait_events,
-                              int n_waits) {
-   if (!c || !device_all || stride_pixels < max_pack_pixels(c)) return UH_ERR_INVALID_ARGUMENT;
-   HIP_TRY(c, hipSetDevice(c->device));
-   if (c->last_acc) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->last_acc, 0));
-   for (int k = 0; k < n_waits; k++)
-      if (wait_events[k]) HIP_TRY(c, hipStreamWaitEvent(c->stream, (hipEvent_t)wait_events[k], 0));
-   launch_compose_tiles(cfg(c), c->im, (const float4*)device_all, stride_pixels, c->W, c->H, c->tp_rank, c->tp_world, c->tp_tile, total_samples, accumulation_limit);
-   HIP_TRY(c, hipGetLastError());
-   return mark_composed(c);
-}
-// the event behind this context's last pack / composition (hipEvent_t; null before the first)
-void* uhi_composed_event(uh_ctx* c) { return c ? (void*)c->ev_compose : nullptr; }
-
-// One process per GPU: the ONE collective of the path tracer's data path. Every rank packs its tiles of
-// pt_accumulation_image and sends them to `root` over the communicator uh_rccl_attach made (grouped ncclSend / ncclRecv: the peers'
-// buffers arrive on distinct xGMI links at once; the root's own tiles take the same way, a local copy); the root scatters them and
-// recomputes pt_output_image in one launch (renderers/mod.rs:199-214,354-358: the two images a single device holds). All of it on
-// the context's stream, behind the frames in flight; the call returns at once and the next uh_read_* / uh_synchronize waits.
-int uh_rccl_gather_tiles(uh_ctx* c, uint32_t root, uint32_t total_samples, uint32_t accumulation_limit) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   RcclLink* l = (RcclLink*)c->rccl;
-   if (!l) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_rccl_gather_tiles: no communicator attached (uh_rccl_attach)");
-   if (c->tp_world != l->world || c->tp_rank != l->rank)
-      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_rccl_gather_tiles: uh_set_tile_partition(rank, world) must be the communicator's rank and size");
-   if (root >= l->world) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_rccl_gather_tiles: root >= world");
-   HIP_TRY(c, hipSetDevice(c->device));
-   const uint64_t stride = max_pack_pixels(c);
-   const bool is_root = l->rank == root;
-   if (c->tile_send.n < stride || (is_root && c->tile_recv.n < stride * l->world)) {
-      if (int st = sync_all(c)) return st;  // (first call, or another partition: the old buffers may still be read)
-      HIP_TRY(c, c->tile_send.alloc(stride ? stride : 1));
-      if (is_root) HIP_TRY(c, c->tile_recv.alloc((stride ? stride : 1) * l->world));
-   }
-   if (int st = uhi_enqueue_pack_tiles(c, c->tile_send.p, nullptr)) return st;
-   RcclApi* api = rccl_api();
-   ncclResult_t r = api->GroupStart();
-   uint64_t mine = 0;
-   uh_tile_pack_count(c, l->rank, &mine);
-   if (r == ncclSuccess && mine) r = api->Send(c->tile_send.p, (size_t)mine * 4, ncclFloat, (int)root, l->comm, c->stream);
-   if (is_root)
-      for (uint32_t k = 0; k < l->world && r == ncclSuccess; k++) {
-         uint64_t n = 0;
-         uh_tile_pack_count(c, k, &n);
-         if (n) r = api->Recv(c->tile_recv.p + (size_t)k * stride, (size_t)n * 4, ncclFloat, (int)k, l->comm, c->stream);
-      }
-   const ncclResult_t e = api->GroupEnd();
-   if (r == ncclSuccess) r = e;
-   l->last = (int)r;
-   if (r != ncclSuccess) return fail(c, UH_ERR_HIP, std::string("uh_rccl_gather_tiles: ") + (api->GetErrorString ? api->GetErrorString(r) : "RCCL error"));
-   if (is_root) return uhi_enqueue_compose_tiles(c, c->tile_recv.p, stride, total_samples, accumulation_limit, nullptr, 0);
-   return mark_composed(c);
-}
-
-int uh_tile_pack_count(uh_ctx* c, uint32_t rank, uint64_t* out_pixels) {
-   if (!c || !out_pixels) return UH_ERR_INVALID_ARGUMENT;
-   if (rank >= c->tp_world) return fail(c, UH_ERR_INVALID_ARGUMENT, "rank >= world");
-   uint32_t tiles = ((c->W + c->tp_tile - 1) / c->tp_tile) * ((c->H + c->tp_tile - 1) / c->tp_tile);
-   uint32_t owned = tiles > rank ? (tiles - rank + c->tp_world - 1) / c->tp_world : 0;
-   *out_pixels = (uint64_t)owned * c->tp_tile * c->tp_tile;
-   return UH_OK;
-}
-
-int uh_pack_tiles(uh_ctx* c, void* device_out, uint64_t capacity_pixels) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   uint64_t need = 0;
-   uh_tile_pack_count(c, c->tp_rank, &need);
-   if (!device_out || capacity_pixels < need) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_pack_tiles: buffer too small");
-   HIP_TRY(c, hipSetDevice(c->device));
-   if (int st = sync_all(c)) return st;
-   launch_pack_tiles(cfg(c), c->accumulation.p, (float4*)device_out, c->W, c->H, c->tp_rank, c->tp_world, c->tp_tile);
-   HIP_TRY(c, hipStreamSynchronize(c->stream));
-   return UH_OK;
-}
-
-int uh_compose_tiles(uh_ctx* c, const void* device_all, uint64_t stride_pixels, uint32_t total_samples, uint32_t accumulation_limit) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   uint64_t need = 0;
-   for (uint32_t r = 0; r < c->tp_world; r++) {
-      uint64_t n = 0;
-      uh_tile_pack_count(c, r, &n);
-      need = n > need ? n : need;
-   }
-   if (!device_all || stride_pixels < need) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_compose_tiles: stride smaller than a rank's packed tiles");
-   HIP_TRY(c, hipSetDevice(c->device));
-   if (int st = sync_all(c)) return st;
-   launch_compose_tiles(cfg(c), c->im, (const float4*)device_all, stride_pixels, c->W, c->H, c->tp_rank, c->tp_world, c->tp_tile, total_samples, accumulation_limit);
-   HIP_TRY(c, hipStreamSynchronize(c->stream));
-   return UH_OK;
-}
-
-int uh_unpack_tiles(uh_ctx* c, uint32_t from_rank, const void* device_in, uint64_t num_pixels) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   uint64_t need = 0;
-   if (uh_tile_pack_count(c, from_rank, &need) != UH_OK) return UH_ERR_INVALID_ARGUMENT;
-   if (!device_in || num_pixels < need) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_unpack_tiles: buffer too small");
-   HIP_TRY(c, hipSetDevice(c->device));
-   if (int st = sync_all(c)) return st;
-   launch_unpack_tiles(cfg(c), c->accumulation.p, (const float4*)device_in, c->W, c->H, from_rank, c->tp_world, c->tp_tile);
-   HIP_TRY(c, hipStreamSynchronize(c->stream));
-   return UH_OK;
-}
-
-int uh_resolve_output(uh_ctx* c, uint32_t total_samples, uint32_t accumulation_limit) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   HIP_TRY(c, hipSetDevice(c->device));
-   if (int st = sync_all(c)) return st;
-   launch_resolve(cfg(c), c->im, c->W, c->H, total_samples, accumulation_limit);
-   HIP_TRY(c, hipGetLastError());
    return UH_OK;
 }
 

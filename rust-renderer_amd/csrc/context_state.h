@@ -1,5 +1,6 @@
 // context_state.h - struct uh_ctx and the types it is made of, for the files that implement the context: context.hip (lifetime,
-// the path tracer, the multi-GPU composition), scene_build.hip (meshes, builders, refit) and the graphs (raster_driver.hip,
+// the path tracer, read-backs), options.hip (uh_set_option), partition.hip (the tile and band partitions of a multi-GPU frame, the
+// tile composition), rccl_link.hip (the RCCL link), scene_build.hip (meshes, builders, refit) and the graphs (raster_driver.hip,
 // hybrid_graph.hip, forward_graph.hip, denoise_graph.hip; what they share: graphs_internal.h). Private: not installed, not part of
 // the C ABI (include/utopian_hip.h), where uh_ctx stays opaque. The upkeep of the sun and camera grids is grid_cache.hip.
 #pragma once
@@ -281,6 +282,8 @@ struct SunGridExtras {
 constexpr uint32_t kRestirBatch = 16;
 constexpr int kSpatialRing = 2 * (int)kRestirBatch + 1;
 
+struct RcclLink;  // rccl_link.hip
+
 struct uh_ctx {
    int device = 0;
    Slot slots[kMaxSlots];
@@ -300,13 +303,18 @@ struct uh_ctx {
    bool restir_recorded = false;
    int spatial_cur = 0;
    hipEvent_t spatial_reader[kSpatialRing] = {};
-   // the reservoir passes by bands of rows over the ranks of a job (uh_set_restir_partition)
-   uint32_t rp_rank = 0, rp_world = 1, rp_band_rows = 0;
-   size_t res_stride = 0;  // reservoirs per spatial_reuse buffer: the frame, padded to rp_world equal bands
-   UhRestirExchangeFn rp_exchange = nullptr;
-   void* rp_user = nullptr;
+   // the reservoir passes by bands of rows over the ranks of a job (uh_set_restir_partition, partition.hip):
+   // this rank's band, what hands the other ranks' bands over behind each spatial pass, and the RCCL link when that is what does
+   // (uh_rccl_attach, rccl_link.hip)
+   struct __attribute__((visibility("hidden"))) Bands {
+      uint32_t rank = 0, world = 1, rows = 0;  // rows per band (the frame's height without a partition)
+      UhRestirExchangeFn exchange = nullptr;
+      void* user = nullptr;
+      RcclLink* link = nullptr;
+      void destroy();  // the link and its exchange go (rccl_link.hip); the caller has drained the streams its collectives run on
+   } bands;
+   size_t res_stride = 0;  // reservoirs per spatial_reuse buffer: the frame, padded to bands.world equal bands
    hipEvent_t ev_band[kSpatialRing] = {};  // "this context's band of ring slot k is written" (in-process groups pull on it)
-   void* rccl = nullptr;                   // RcclLink (uh_rccl_attach)
    hipEvent_t t_start = nullptr, t_stop = nullptr;  // bracket of the last uh_render_frame call (last_frame_ms)
    Slot* last_slot = nullptr;
    hipStream_t& stream = slots[0].stream;  // slot 0 also serves every non-frame operation
@@ -421,15 +429,21 @@ struct uh_ctx {
    bool cam_grid_enabled = true;
    CachedGrid<32> cam;              // key: inverse_view, inverse_projection
 
-   // tile partition
-   uint32_t tp_rank = 0, tp_world = 1, tp_tile = 64;
-   DevBuf<uint32_t> owned_pixels;  // ascending pixel ids this rank owns (empty = the whole frame)
-   uint32_t n_owned = 0;
-   // composition of a partitioned frame without a host wait (uh_rccl_gather_tiles; the in-process group's uh_mgpu_compose): this
-   // rank's packed tiles, on the root every rank's, and the event behind the last pack / composition - the next frame's accumulate
-   // tail waits for it like for a frame's (last_acc)
-   DevBuf<float4> tile_send, tile_recv;
-   hipEvent_t ev_compose = nullptr;
+   // the tile partition of the path-traced frame (uh_set_tile_partition, partition.hip; the owner rule: tile_partition.h), and its
+   // composition without a host wait (uh_rccl_gather_tiles; the in-process group's uh_mgpu_compose): this rank's packed tiles, on the
+   // root every rank's, and the event behind the last pack / composition - the next frame's accumulate tail waits for it like for a
+   // frame's (last_acc)
+   struct __attribute__((visibility("hidden"))) Tiles {
+      uint32_t rank = 0, world = 1, tile = 64;
+      DevBuf<uint32_t> owned_pixels;  // ascending pixel ids this rank owns (empty = the whole frame)
+      uint32_t n_owned = 0;
+      DevBuf<float4> send, recv;
+      hipEvent_t ev_compose = nullptr;
+      void destroy() {
+         owned_pixels.release(), send.release(), recv.release();
+         if (ev_compose) (void)hipEventDestroy(ev_compose);
+      }
+   } tiles;
 
    // the hybrid graph's passes (uh_render_hybrid): images, the metal-pixel queue and a copy of the scene's meshes as gbuffer.vert
    // reads them, all allocated by the first call. Every feature below names its buffers once, in a visitor f(buffer, length) over
@@ -698,7 +712,7 @@ struct uh_ctx {
    } dn;
 };
 
-// ---- context.hip, for scene_build.hip and the graphs (not exported: the library's dynamic symbols stay the C ABI's) ----
+// ---- context.hip, for the other files of the context (not exported: the library's dynamic symbols stay the C ABI's) ----
 #pragma GCC visibility push(hidden)
 int fail(uh_ctx* c, int code, const std::string& msg);  // sets uh_last_error (c null: uh_create's); returns code
 #define HIP_TRY(ctx, expr)                                                                                   \
@@ -710,7 +724,14 @@ int fail(uh_ctx* c, int code, const std::string& msg);  // sets uh_last_error (c
 LaunchCfg cfg(uh_ctx* c);
 FrameParams make_params(uh_ctx* c, const UhViewUniformData& v);
 int sync_all(uh_ctx* c);
+void drain_timed(uh_ctx* c);  // the pending kernel timings (option "time_kernels") into ms_by_kind; waits for their events
 int read_back(uh_ctx* c, void* dst, const void* src, size_t bytes);
+// paths this rank traces per frame: path ids are dense over the pixels it owns
+inline uint32_t traced_pixels(const uh_ctx* c) { return c->tiles.world > 1 ? c->tiles.n_owned : c->W * c->H; }
+// ---- partition.hip, for context.hip and rccl_link.hip ----
+void restir_rows(const uh_ctx* c, UhRestirRows& r);  // rows of this context's reservoir passes (uh_get_restir_rows)
+uint64_t max_pack_pixels(uh_ctx* c);                 // the largest uh_tile_pack_count over the ranks: rank 0's
+int mark_composed(uh_ctx* c);                        // records tiles.ev_compose on the context's stream; it becomes last_acc
 // ---- grid_cache.hip, for context.hip ----
 // the sun grid for this frame's direction / the camera grid for this call's camera, if there is (or now should be) one: this_frame
 int ensure_sun_grid(uh_ctx* c, const float dir[3]);

@@ -48,7 +48,7 @@ int uh_denoise(uh_ctx* c, const UhViewUniformData* view, const UhDenoiseParams* 
    const uint32_t n = std::min(view->total_samples, view->accumulation_limit);
    if (n == 0)
       return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_denoise: min(view.total_samples, view.accumulation_limit) is 0: the accumulation image holds no sample to divide by");
-   if (c->tp_world > 1)
+   if (c->tiles.world > 1)
       return fail(c, UH_ERR_INVALID_ARGUMENT,
                   "uh_denoise: a tile partition with world > 1 is set (uh_set_tile_partition): this context's accumulation image is partial");
    if (!c->hy.gbuffer_done)

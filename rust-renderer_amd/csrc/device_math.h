@@ -9,6 +9,7 @@
 
 #include "device_types.h"
 #include "texture_layout.h"
+#include "tile_partition.h"
 
 namespace uh {
 
@@ -428,9 +429,7 @@ __device__ __forceinline__ void primary_state(const FrameParams& fp, uint32_t id
 }
 
 __device__ __forceinline__ bool owns_pixel(const FrameParams& fp, uint32_t x, uint32_t y) {
-   if (fp.tp_world <= 1) return true;
-   uint32_t tile = (y / fp.tp_tile) * fp.tiles_x + (x / fp.tp_tile);
-   return tile % fp.tp_world == fp.tp_rank;
+   return fp.tp_world <= 1 || pixel_owner(x, y, fp.tp_tile, fp.tiles_x, fp.tp_world) == fp.tp_rank;
 }
 
 // ---- streaming (non-temporal) access to per-path state -----------------------------------------

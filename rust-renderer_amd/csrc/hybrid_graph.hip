@@ -449,7 +449,7 @@ static HybridPlan hybrid_plan(const uh_ctx& c, const UhViewUniformData& view, ui
          return refuse(UH_ERR_INVALID_ARGUMENT,
                      "uh_render_hybrid: UH_HYBRID_RESTIR_LIGHTS reads the spatial reservoirs, and no reservoir pass has run on this context; "
                      "render a frame with UH_PASS_RESTIR (same camera) first");
-      if (c.rp_world > 1)
+      if (c.bands.world > 1)
          return refuse(UH_ERR_INVALID_ARGUMENT,
                      "uh_render_hybrid: UH_HYBRID_RESTIR_LIGHTS needs the whole frame's reservoirs, and a row partition with world > 1 is set "
                      "(uh_set_restir_partition)");

@@ -4,27 +4,20 @@
 #include "device_math.h"
 #include "device_types.h"
 #include "kernel_common.h"
+#include "tile_partition.h"
 
 namespace uh {
 
-// ------------------------------------------------------------------------------------------
-// multi-GPU tile pack / unpack of the RGBA32F accumulation image
-// ------------------------------------------------------------------------------------------
 template <bool PACK>
 __global__ __launch_bounds__(kBlock) void k_tiles(float4* acc, float4* packed, uint32_t W, uint32_t H, uint32_t rank, uint32_t world, uint32_t tile) {
-   const uint32_t tiles_x = (W + tile - 1) / tile, tiles_y = (H + tile - 1) / tile;
-   const uint32_t num_tiles = tiles_x * tiles_y;
-   const uint32_t owned = num_tiles > rank ? (num_tiles - rank + world - 1) / world : 0;
-   const uint64_t total = (uint64_t)owned * tile * tile;
+   const uint32_t tiles_x = tiles_across(W, tile);
+   const uint64_t total = pack_pixels(W, H, tile, rank, world);
    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (uint64_t)gridDim.x * kBlock) {
-      uint32_t local = (uint32_t)(i / (tile * tile)), within = (uint32_t)(i % (tile * tile));
-      uint32_t t = rank + local * world;
-      uint32_t x = (t % tiles_x) * tile + within % tile, y = (t / tiles_x) * tile + within / tile;
-      bool inside = x < W && y < H;
+      const PackedPixel p = packed_pixel(i, W, H, tile, tiles_x, rank, world);
       if (PACK)
-         packed[i] = inside ? acc[(size_t)y * W + x] : make_float4(0, 0, 0, 0);
-      else if (inside)
-         acc[(size_t)y * W + x] = packed[i];
+         packed[i] = p.inside ? acc[(size_t)p.y * W + p.x] : make_float4(0, 0, 0, 0);
+      else if (p.inside)
+         acc[(size_t)p.y * W + p.x] = packed[i];
    }
 }
 
@@ -33,15 +26,15 @@ __global__ __launch_bounds__(kBlock) void k_tiles(float4* acc, float4* packed, u
 // root's own pixels stay, and pt_output_image is recomputed for every pixel (rgen:140-144)
 __global__ __launch_bounds__(kBlock) void k_compose_tiles(Images im, const float4* __restrict__ all, uint64_t stride, uint32_t W, uint32_t H, uint32_t rank, uint32_t world,
                                                            uint32_t tile, uint32_t total_samples, uint32_t limit) {
-   const uint32_t tiles_x = (W + tile - 1) / tile, n = W * H;
+   const uint32_t tiles_x = tiles_across(W, tile), n = W * H;
    for (uint32_t pix = blockIdx.x * kBlock + threadIdx.x; pix < n; pix += gridDim.x * kBlock) {
       const uint32_t x = pix % W, y = pix / W;
-      const uint32_t t = (y / tile) * tiles_x + x / tile, owner = t % world;
+      const uint32_t t = tile_of_pixel(x, y, tile, tiles_x), owner = tile_owner(t, world);
       float4 acc;
       if (owner == rank)
          acc = im.accumulation[pix];
       else {
-         acc = all[owner * stride + (uint64_t)(t / world) * tile * tile + (y % tile) * tile + x % tile];
+         acc = all[owner * stride + packed_position(t, x, y, tile, world)];
          im.accumulation[pix] = acc;
       }
       im.output[pix] = resolve_color(acc, total_samples, limit);
