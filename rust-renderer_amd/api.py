@@ -104,53 +104,137 @@ class UtopianError(RuntimeError):
     pass
 
 
+_p, _int, _u32, _u64, _f32, _vp = C.POINTER, C.c_int, C.c_uint32, C.c_uint64, C.c_float, C.c_void_p
+_fp, _view = _p(_f32), _p(ViewUniformData)
+# One row per C entry point this module calls: its name without "uh_", then its argtypes - the restype is c_int - or (argtypes, restype).
+# ctypes never compares a row with the C declaration: tests/test_api_signatures.py holds every row to include/utopian_hip.h.
+# What every backend exports under a prefix of its own (uh_, uh_mgpu_, the oracle's orc_): CApi binds these
+_CONTEXT_VERBS = {
+    "destroy": ([_vp], None),
+    "add_texture_rgba8": [_vp, _vp, _u32, _u32, _p(_u32)],
+    "add_mesh": [_vp, _vp, _u32, _vp, _u32, _p(GpuMaterial), _fp, _p(_u32)],
+    "add_light": [_vp, _p(GpuLight), _p(_u32)],
+    "set_instance_transform": [_vp, _u32, _fp],
+    "build_acceleration": [_vp],
+    "refit_acceleration": [_vp],
+    "render_frame": [_vp, _view, _u32],
+    "render_frames": [_vp, _view, _u32, _u32],
+    "reset_accumulation": [_vp],
+    "read_accumulation": [_vp, _vp],
+    "read_output_bgra8": [_vp, _vp],
+    "read_reservoirs": [_vp, _int, _vp],
+    "write_reservoirs": [_vp, _int, _vp],
+    "write_gbuffer_position": [_vp, _vp],
+    "read_gbuffer_position": [_vp, _vp],
+    "trace_closest": [_vp, _vp, _u32, _vp, _vp, _vp],
+    "trace_any": [_vp, _vp, _u32, _vp],
+    "get_stats": [_vp, _p(Stats)],
+    "reset_stats": [_vp],
+    "set_option": [_vp, C.c_char_p, _int],
+    "set_tile_partition": [_vp, _u32, _u32, _u32],
+    "set_restir_partition": [_vp, _u32, _u32, _vp, _vp],
+    "get_restir_rows": [_vp, _p(RestirRows)],
+    "resolve_output": [_vp, _u32, _u32],
+    "render_hybrid": [_vp, _view, _u32],
+    "read_hybrid": [_vp, _int, _vp],
+    "get_hybrid_stats": [_vp, _p(HybridStats)],
+    "get_hybrid_frame_stats": [_vp, _p(HybridFrameStats)],
+    "read_environment": [_vp, _int, _int, _int, _vp],
+    "get_environment_stats": [_vp, _p(EnvironmentStats)],
+}
+_HYBRID_VERBS = ("render_hybrid", "read_hybrid", "get_hybrid_stats", "get_hybrid_frame_stats", "read_environment", "get_environment_stats")
+# The HIP library's alone, under uh_: bound where they are called (_bind)
+_LIBRARY_VERBS = {
+    "create": [_int, _u32, _u32, _p(_vp)],
+    "last_error": ([_vp], C.c_char_p),
+    "version": ([], C.c_char_p),
+    "hip_versions": [_p(_int), _p(_int)],
+    "get_num_lights": [_vp, _p(_u32)],
+    "synchronize": [_vp],
+    "tile_pack_count": [_vp, _u32, _p(_u64)],
+    "pack_tiles": [_vp, _vp, _u64],
+    "unpack_tiles": [_vp, _u32, _vp, _u64],
+    "compose_tiles": [_vp, _vp, _u64, _u32, _u32],
+    "device_pointer": [_vp, _int, _p(_vp)],
+    "stream": [_vp, _p(_vp)],
+    "add_isosurface_mesh": [_vp, _u32, _f32, _f32, _f32, _p(GpuMaterial), _fp, _p(_u32), _p(_u32)],
+    "update_isosurface_mesh": [_vp, _u32, _f32, _p(_u32)],
+    "get_isosurface_update_stats": [_vp, _p(IsosurfaceUpdateStats)],
+    "update_mesh_vertices": [_vp, _u32, _vp, _u32, _int],
+    "get_mesh_update_stats": [_vp, _p(MeshUpdateStats)],
+    "isosurface_cells": [_vp, _u32, _f32, _f32, _f32, _vp, _vp],
+    "mesh_info": [_vp, _u32, _p(_u32), _p(_u32)],
+    "read_mesh": [_vp, _u32, _vp, _vp],
+    "get_marching_cubes_stats": [_vp, _p(MarchingCubesStats)],
+    "get_gbuffer_raster_stats": [_vp, _p(GbufferRasterStats)],
+    "get_hybrid_restir_stats": [_vp, _p(HybridRestirStats)],
+    "rtao_default_params": [_p(RtaoParams)],
+    "set_rtao_params": [_vp, _p(RtaoParams)],
+    "get_rtao_stats": [_vp, _p(RtaoStats)],
+    "get_rtao_visits": [_vp, _p(_u64), _p(_u64)],
+    "rtgi_default_params": [_p(RtgiParams)],
+    "set_rtgi_params": [_vp, _p(RtgiParams)],
+    "get_rtgi_stats": [_vp, _p(RtgiStats)],
+    "get_motion_stats": [_vp, _p(MotionStats)],
+    "taa_default_params": [_p(TaaParams)],
+    "set_taa_params": [_vp, _p(TaaParams)],
+    "reset_taa_history": [_vp],
+    "get_taa_stats": [_vp, _p(TaaStats)],
+    "taa_jitter": [_u32, _p(_f32 * 2)],
+    "post_default_params": [_p(PostParams)],
+    "set_post_params": [_vp, _p(PostParams)],
+    "reset_post_exposure": [_vp],
+    "get_post_stats": [_vp, _p(PostStats)],
+    "post_level_size": [_u32, _u32, _u32, _p(_u32), _p(_u32)],
+    "post_image": [_vp, _vp],
+    "read_post": [_vp, _int, _int, _vp],
+    "denoise_default_params": [_p(DenoiseParams)],
+    "denoise": [_vp, _view, _p(DenoiseParams)],
+    "read_denoised": [_vp, _int, _vp],
+    "reset_denoise_history": [_vp],
+    "get_denoise_stats": [_vp, _p(DenoiseStats)],
+    "shadow_cascades": [_fp, _fp, _f32, _f32, _fp, _p(ShadowmapParams)],
+    "set_shadowmap_params": [_vp, _p(ShadowmapParams)],
+    "read_shadow_map": [_vp, _int, _vp],
+    "get_shadow_map_stats": [_vp, _p(ShadowMapStats)],
+    "render_forward": [_vp, _view, _u32],
+    "read_forward": [_vp, _int, _vp],
+    "get_forward_stats": [_vp, _p(ForwardStats)],
+    "rccl_unique_id": [_vp],  # (no context: the id's 128 bytes)
+    "rccl_attach": [_vp, _u32, _u32, _vp],
+    "rccl_comm_count": [_vp, _p(_u32)],
+    "rccl_gather_tiles": [_vp, _u32, _u32, _u32],
+    "rccl_detach": [_vp],
+    "sun_grid_compare_builders": [_vp, _p(_u64)],
+    "check_acceleration": [_vp, _p(_u64)],
+    "mgpu_create": [_int, _p(_int), _u32, _u32, _u32, _p(_vp)],
+    "mgpu_last_error": ([_vp], C.c_char_p),
+    "mgpu_context": ([_vp, _int], _vp),
+    "mgpu_num_devices": [_vp],
+    "mgpu_get_num_lights": [_vp, _p(_u32)],
+    "mgpu_synchronize": [_vp],
+    "mgpu_compose": [_vp],
+}
+_SIGNATURES = {**_CONTEXT_VERBS, **_LIBRARY_VERBS}
+
+
+def _bind(lib, prefix, name):
+    """`prefix + name` of `lib` with the signature of its row: the one place argtypes and restype are set"""
+    row = _SIGNATURES[name]
+    fn = getattr(lib, prefix + name)
+    fn.argtypes, fn.restype = row if isinstance(row, tuple) else (row, _int)
+    return fn
+
+
 class CApi:
     """Typed ctypes view of a library exporting the utopian_hip.h entry points under `prefix`."""
 
     def __init__(self, lib, prefix):
         self.lib, self.prefix = lib, prefix
-        p, u32, vp = C.POINTER, C.c_uint32, C.c_void_p
-        sig = {
-            "add_texture_rgba8": [vp, vp, u32, u32, p(u32)],
-            "add_mesh": [vp, vp, u32, vp, u32, p(GpuMaterial), p(C.c_float), p(u32)],
-            "add_light": [vp, p(GpuLight), p(u32)],
-            "set_instance_transform": [vp, u32, p(C.c_float)],
-            "build_acceleration": [vp],
-            "refit_acceleration": [vp],
-            "render_frame": [vp, p(ViewUniformData), u32],
-            "render_frames": [vp, p(ViewUniformData), u32, u32],
-            "reset_accumulation": [vp],
-            "read_accumulation": [vp, vp],
-            "read_output_bgra8": [vp, vp],
-            "read_reservoirs": [vp, C.c_int, vp],
-            "write_reservoirs": [vp, C.c_int, vp],
-            "write_gbuffer_position": [vp, vp],
-            "read_gbuffer_position": [vp, vp],
-            "trace_closest": [vp, vp, u32, vp, vp, vp],
-            "trace_any": [vp, vp, u32, vp],
-            "get_stats": [vp, p(Stats)],
-            "reset_stats": [vp],
-            "set_option": [vp, C.c_char_p, C.c_int],
-            "set_tile_partition": [vp, u32, u32, u32],
-            "set_restir_partition": [vp, u32, u32, vp, vp],
-            "get_restir_rows": [vp, p(RestirRows)],
-            "resolve_output": [vp, u32, u32],
-            "render_hybrid": [vp, p(ViewUniformData), u32],
-            "read_hybrid": [vp, C.c_int, vp],
-            "get_hybrid_stats": [vp, p(HybridStats)],
-            "get_hybrid_frame_stats": [vp, p(HybridFrameStats)],
-            "read_environment": [vp, C.c_int, C.c_int, C.c_int, vp],
-            "get_environment_stats": [vp, p(EnvironmentStats)],
-        }
-        hybrid = ("render_hybrid", "read_hybrid", "get_hybrid_stats", "get_hybrid_frame_stats", "read_environment", "get_environment_stats")
-        for name, argtypes in sig.items():
-            if not hasattr(lib, prefix + name) and (name == "render_frames" or name in hybrid or prefix == "uh_mgpu_"):
+        for name in _CONTEXT_VERBS:
+            if not hasattr(lib, prefix + name) and (name == "render_frames" or name in _HYBRID_VERBS or prefix == "uh_mgpu_"):
                 continue  # the oracle renders frame by frame and has no hybrid passes; the GPU group has no per-context queries
-            fn = getattr(lib, prefix + name)
-            fn.argtypes, fn.restype = argtypes, C.c_int
-            setattr(self, name, fn)
-        self.destroy = getattr(lib, prefix + "destroy")
-        self.destroy.argtypes, self.destroy.restype = [vp], None
+            setattr(self, name, _bind(lib, prefix, name))
 
 
 _lib_cache = {}
@@ -187,23 +271,9 @@ def load_library(path=LIB_PATH):
     _preload_hip_runtime()
     lib = C.CDLL(path)
     _lib_cache[path] = lib
-    lib.uh_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
-    lib.uh_create.restype = C.c_int
-    lib.uh_last_error.argtypes, lib.uh_last_error.restype = [C.c_void_p], C.c_char_p
-    lib.uh_version.restype = C.c_char_p
-    lib.uh_hip_versions.argtypes, lib.uh_hip_versions.restype = [C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int
-    for name, extra in (
-        ("uh_get_num_lights", [C.POINTER(C.c_uint32)]),
-        ("uh_synchronize", []),
-        ("uh_tile_pack_count", [C.c_uint32, C.POINTER(C.c_uint64)]),
-        ("uh_pack_tiles", [C.c_void_p, C.c_uint64]),
-        ("uh_unpack_tiles", [C.c_uint32, C.c_void_p, C.c_uint64]),
-        ("uh_compose_tiles", [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32]),
-        ("uh_device_pointer", [C.c_int, C.POINTER(C.c_void_p)]),
-        ("uh_stream", [C.POINTER(C.c_void_p)]),
-    ):
-        fn = getattr(lib, name)
-        fn.argtypes, fn.restype = [C.c_void_p] + extra, C.c_int
+    for name in ("create", "last_error", "version", "hip_versions", "get_num_lights", "synchronize", "tile_pack_count", "pack_tiles", "unpack_tiles",
+                 "compose_tiles", "device_pointer", "stream"):
+        _bind(lib, "uh_", name)
     return lib
 
 
@@ -285,6 +355,42 @@ class Renderer:
                 msg = self._lib.uh_last_error(self._ctx) or b""
             raise UtopianError(f"{ERR_NAMES.get(st, st)}: {msg.decode()}")
 
+    def _uh(self, name):
+        """uh_<name> of the HIP library, bound from the table"""
+        return _bind(self._lib, "uh_", name)
+
+    def _hip_only(self, what, name=None, present=True):
+        """The guard of the verbs that only the HIP library has: NotImplementedError naming `what` ("<a pass> is a per-context verb") on
+        another backend, or where such a verb is not `present`; else uh_<name>, bound."""
+        if self.backend != "hip" or not present:
+            raise NotImplementedError(f"{what} of the HIP library; backend {self.backend!r} has none")
+        return name and self._uh(name)
+
+    def _stats(self, Struct, fn):
+        """a `Struct` as the stats verb `fn` fills it"""
+        s = Struct()
+        self._check(fn(self._ctx, C.byref(s)))
+        return s
+
+    def _set_params(self, Struct, fn, defaults, params, fields):
+        """the params verb `fn` on a copy of `params` (of `defaults()` when None) with `fields` set; returns the copy"""
+        p = Struct.from_buffer_copy(defaults() if params is None else params)
+        for k, v in fields.items():
+            if not hasattr(p, k):
+                raise TypeError(f"{Struct.__name__} has no field {k!r}")
+            setattr(p, k, v)
+        self._check(fn(self._ctx, C.byref(p)))
+        return p
+
+    def _read_image(self, images, fn, which, refusal):
+        """image `which` of `images` ({index: (dtype, channels)}) by the read verb `fn`; ValueError(refusal) for an index not in it"""
+        if which not in images:
+            raise ValueError(refusal)
+        dtype, ch = images[which]
+        out = np.empty((self.height, self.width, ch) if ch > 1 else (self.height, self.width), dtype=dtype)
+        self._check(fn(self._ctx, int(which), out.ctypes.data))
+        return out
+
     def close(self):
         if getattr(self, "_ctx", None):
             self._api.destroy(self._ctx)
@@ -359,37 +465,27 @@ class Renderer:
         if material is None:
             material = make_material(base_color=(0.8, 0.8, 0.8, 1.0), diffuse_map=self.default_diffuse_map())
         w = identity3x4() if world3x4 is None else np.ascontiguousarray(world3x4, dtype=np.float32).reshape(12)
-        fn = self._lib.uh_add_isosurface_mesh
-        fn.argtypes = [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.POINTER(GpuMaterial), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        fn.restype = C.c_int
         mesh, tris = C.c_uint32(), C.c_uint32()
-        self._check(fn(self._ctx, int(resolution), float(lo), float(hi), float(time), C.byref(material), w.ctypes.data_as(C.POINTER(C.c_float)), C.byref(mesh), C.byref(tris)))
+        self._check(self._uh("add_isosurface_mesh")(self._ctx, int(resolution), float(lo), float(hi), float(time), C.byref(material), w.ctypes.data_as(C.POINTER(C.c_float)), C.byref(mesh), C.byref(tris)))
         return (None if mesh.value == 0xFFFFFFFF else mesh.value), tris.value
 
     def update_isosurface_mesh(self, mesh, time):
         """uh_update_isosurface_mesh: re-extracts the field at `time` with the parameters mesh `mesh` was created with by
         add_isosurface_mesh and makes the result its geometry, on the device. Returns the triangle count; the context needs
         build_acceleration afterwards."""
-        fn = self._lib.uh_update_isosurface_mesh
-        fn.argtypes, fn.restype = [C.c_void_p, C.c_uint32, C.c_float, C.POINTER(C.c_uint32)], C.c_int
         tris = C.c_uint32()
-        self._check(fn(self._ctx, int(mesh), float(time), C.byref(tris)))
+        self._check(self._uh("update_isosurface_mesh")(self._ctx, int(mesh), float(time), C.byref(tris)))
         return tris.value
 
     def isosurface_update_stats(self):
         """UhIsosurfaceUpdateStats (all zero before the first update_isosurface_mesh)"""
-        fn = self._lib.uh_get_isosurface_update_stats
-        fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(IsosurfaceUpdateStats)], C.c_int
-        s = IsosurfaceUpdateStats()
-        self._check(fn(self._ctx, C.byref(s)))
-        return s
+        return self._stats(IsosurfaceUpdateStats, self._uh("get_isosurface_update_stats"))
 
     def update_mesh_vertices(self, mesh, vertices=None, *, device_ptr=None, count=None):
         """uh_update_mesh_vertices: new vertices for a mesh of add_mesh, its index list kept. Host input: `vertices`, a VERTEX_DTYPE
         array of the mesh's length. Device input: `device_ptr`, the address of `count` vertex records on the renderer's device, which
         the caller has finished writing. refit_acceleration (or a frame with view.rebuild_tlas = 1) or build_acceleration follows."""
-        fn = self._lib.uh_update_mesh_vertices
-        fn.argtypes, fn.restype = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int], C.c_int
+        fn = self._uh("update_mesh_vertices")
         if device_ptr is not None:
             assert vertices is None and count is not None, "device input: device_ptr= with count="
             self._check(fn(self._ctx, int(mesh), C.c_void_p(int(device_ptr)), int(count), 1))
@@ -399,32 +495,22 @@ class Renderer:
 
     def mesh_update_stats(self):
         """UhMeshUpdateStats (all zero before the first update_mesh_vertices)"""
-        fn = self._lib.uh_get_mesh_update_stats
-        fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(MeshUpdateStats)], C.c_int
-        s = MeshUpdateStats()
-        self._check(fn(self._ctx, C.byref(s)))
-        return s
+        return self._stats(MeshUpdateStats, self._uh("get_mesh_update_stats"))
 
     def isosurface_cells(self, resolution, lo, hi, time=0.0):
         """uh_isosurface_cells: per cell of the extraction grid (x fastest) its marching-cubes case index and the triangles it keeps"""
         n = int(resolution) ** 3
         cube, kept = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
-        fn = self._lib.uh_isosurface_cells
-        fn.argtypes, fn.restype = [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p], C.c_int
-        self._check(fn(self._ctx, int(resolution), float(lo), float(hi), float(time), cube.ctypes.data, kept.ctypes.data))
+        self._check(self._uh("isosurface_cells")(self._ctx, int(resolution), float(lo), float(hi), float(time), cube.ctypes.data, kept.ctypes.data))
         return cube, kept
 
     def read_mesh(self, mesh_index):
         """the context's host copy of a mesh: (vertices as VERTEX_DTYPE, indices)"""
-        lib = self._lib
-        lib.uh_mesh_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        lib.uh_read_mesh.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-        lib.uh_mesh_info.restype = lib.uh_read_mesh.restype = C.c_int
         nv, ni = C.c_uint32(), C.c_uint32()
-        self._check(lib.uh_mesh_info(self._ctx, mesh_index, C.byref(nv), C.byref(ni)))
+        self._check(self._uh("mesh_info")(self._ctx, mesh_index, C.byref(nv), C.byref(ni)))
         v = np.zeros(nv.value, dtype=VERTEX_DTYPE)
         idx = np.zeros(ni.value, dtype=np.uint32)
-        self._check(lib.uh_read_mesh(self._ctx, mesh_index, v.ctypes.data, idx.ctypes.data))
+        self._check(self._uh("read_mesh")(self._ctx, mesh_index, v.ctypes.data, idx.ctypes.data))
         return v, idx
 
     def default_diffuse_map(self):
@@ -516,9 +602,13 @@ class Renderer:
 
     # -- the hybrid graph's ray-traced passes (uh_render_hybrid; include/utopian_hip.h) ----
     def _hybrid_api(self):
-        if self.backend != "hip" or not hasattr(self._api, "render_hybrid"):
-            raise NotImplementedError(f"the hybrid passes (rt_shadows / rt_reflections / the final frame) are per-context verbs of the HIP library; backend {self.backend!r} has none")
+        self._hip_only("the hybrid passes (rt_shadows / rt_reflections / the final frame) are per-context verbs", present=hasattr(self._api, "render_hybrid"))
         return self._api
+
+    def _hybrid_verb(self, name):
+        """uh_<name>, a verb of the hybrid graph that CApi does not carry"""
+        self._hybrid_api()
+        return self._uh(name)
 
     def render_hybrid(self, view, mask=HYBRID_ALL):
         """rt_shadows (previous G-buffer), gbuffer, rt_reflections (this one), ssao, deferred, sky, present - the reference's pass order -
@@ -561,20 +651,12 @@ class Renderer:
         with a correspondence), once a call with HYBRID_TAA has run (H, W, 4) float32 taa_output and (H, W) float32 history length, and of
         HYBRID_RTGI (H, W, 4) float32 filtered incoming radiance (w = 1 where the pixel cast) and (H, W, 4) uint8 ray counts (sunlit, dark,
         emitter, missed)"""
-        api = self._hybrid_api()
         images = {**self._HYBRID_IMAGES, **(self._TAA_IMAGES if self._taa_rendered else {}), **self._GI_IMAGES}
-        if which not in images:
-            raise ValueError(f"hybrid image index {which} (0..15, 18..19, and 16..17 once a render_hybrid call with HYBRID_TAA has run)")
-        dtype, ch = images[which]
-        out = np.empty((self.height, self.width, ch) if ch > 1 else (self.height, self.width), dtype=dtype)
-        self._check(api.read_hybrid(self._ctx, int(which), out.ctypes.data))
-        return out
+        return self._read_image(images, self._hybrid_api().read_hybrid, which,
+                                f"hybrid image index {which} (0..15, 18..19, and 16..17 once a render_hybrid call with HYBRID_TAA has run)")
 
     def hybrid_stats(self):
-        api = self._hybrid_api()
-        s = HybridStats()
-        self._check(api.get_hybrid_stats(self._ctx, C.byref(s)))
-        return s
+        return self._stats(HybridStats, self._hybrid_api().get_hybrid_stats)
 
     def read_environment(self, which, face=0, mip=0):
         """one face and mip of an IBL map (ENV_ENVIRONMENT / ENV_IRRADIANCE / ENV_SPECULAR: (S, S, 4) float32, S = 512 >> mip, row 0
@@ -592,101 +674,51 @@ class Renderer:
 
     def environment_stats(self):
         """UhEnvironmentStats of the last HYBRID_ENVIRONMENT build: pass_ms of its four sub-passes, builds, sun_dir and eye"""
-        api = self._hybrid_api()
-        s = EnvironmentStats()
-        self._check(api.get_environment_stats(self._ctx, C.byref(s)))
-        return s
+        return self._stats(EnvironmentStats, self._hybrid_api().get_environment_stats)
 
     def hybrid_frame_stats(self):
         """UhHybridFrameStats of the last render_hybrid call: pass_ms of all seven passes in bit order"""
-        api = self._hybrid_api()
-        s = HybridFrameStats()
-        self._check(api.get_hybrid_frame_stats(self._ctx, C.byref(s)))
-        return s
+        return self._stats(HybridFrameStats, self._hybrid_api().get_hybrid_frame_stats)
 
     def marching_cubes_stats(self):
         """UhMarchingCubesStats of the last HYBRID_MARCHING_CUBES pass"""
-        self._hybrid_api()
-        fn = getattr(self._lib, "uh_get_marching_cubes_stats")
-        fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(MarchingCubesStats)], C.c_int
-        s = MarchingCubesStats()
-        self._check(fn(self._ctx, C.byref(s)))
-        return s
+        return self._stats(MarchingCubesStats, self._hybrid_verb("get_marching_cubes_stats"))
 
     def gbuffer_raster_stats(self):
         """UhGbufferRasterStats of the last rasterised G-buffer pass (HYBRID_GBUFFER | HYBRID_GBUFFER_RASTER)"""
-        self._hybrid_api()
-        fn = getattr(self._lib, "uh_get_gbuffer_raster_stats")
-        fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(GbufferRasterStats)], C.c_int
-        s = GbufferRasterStats()
-        self._check(fn(self._ctx, C.byref(s)))
-        return s
+        return self._stats(GbufferRasterStats, self._hybrid_verb("get_gbuffer_raster_stats"))
 
     def hybrid_restir_stats(self):
         """UhHybridRestirStats of the last render_hybrid call with HYBRID_RESTIR_LIGHTS: rays, occluded, pass_ms"""
-        self._hybrid_api()
-        fn = getattr(self._lib, "uh_get_hybrid_restir_stats")
-        fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(HybridRestirStats)], C.c_int
-        s = HybridRestirStats()
-        self._check(fn(self._ctx, C.byref(s)))
-        return s
+        return self._stats(HybridRestirStats, self._hybrid_verb("get_hybrid_restir_stats"))
 
     # -- ray-traced ambient occlusion (HYBRID_RTAO; include/utopian_hip.h "UH_HYBRID_RTAO") ---
-    def _rtao_fn(self, name, arg):
-        if self.backend != "hip":
-            raise NotImplementedError(f"ray-traced ambient occlusion is a per-context verb of the HIP library; backend {self.backend!r} has none")
-        fn = getattr(self._lib, "uh_" + name)
-        fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(arg)], C.c_int
-        return fn
+    _RTAO = "ray-traced ambient occlusion is a per-context verb"
 
     def set_rtao_params(self, params=None, **fields):
         """uh_set_rtao_params: `params` (an RtaoParams; the defaults when None) with `fields` set on a copy - the params of the
         render_hybrid calls with HYBRID_RTAO that follow. A refused call raises and leaves the old ones."""
-        p = RtaoParams.from_buffer_copy(rtao_default_params() if params is None else params)
-        for k, v in fields.items():
-            if not hasattr(p, k):
-                raise TypeError(f"RtaoParams has no field {k!r}")
-            setattr(p, k, v)
-        self._check(self._rtao_fn("set_rtao_params", RtaoParams)(self._ctx, C.byref(p)))
-        return p
+        return self._set_params(RtaoParams, self._hip_only(self._RTAO, "set_rtao_params"), rtao_default_params, params, fields)
 
     def rtao_stats(self):
         """UhRtaoStats of the last rtao pass: pixels, rays, occluded, trace_ms, filter_ms"""
-        s = RtaoStats()
-        self._check(self._rtao_fn("get_rtao_stats", RtaoStats)(self._ctx, C.byref(s)))
-        return s
+        return self._stats(RtaoStats, self._hip_only(self._RTAO, "get_rtao_stats"))
 
     # -- one-bounce ray-traced diffuse GI (HYBRID_RTGI; include/utopian_hip.h "UH_HYBRID_RTGI") ---
-    def _rtgi_fn(self, name, arg):
-        if self.backend != "hip":
-            raise NotImplementedError(f"ray-traced diffuse GI is a per-context verb of the HIP library; backend {self.backend!r} has none")
-        fn = getattr(self._lib, "uh_" + name)
-        fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(arg)], C.c_int
-        return fn
+    _RTGI = "ray-traced diffuse GI is a per-context verb"
 
     def set_rtgi_params(self, params=None, **fields):
         """uh_set_rtgi_params: `params` (an RtgiParams; the defaults when None) with `fields` set on a copy - the params of the
         render_hybrid calls with HYBRID_RTGI that follow. A refused call raises and leaves the old ones."""
-        p = RtgiParams.from_buffer_copy(rtgi_default_params() if params is None else params)
-        for k, v in fields.items():
-            if not hasattr(p, k):
-                raise TypeError(f"RtgiParams has no field {k!r}")
-            setattr(p, k, v)
-        self._check(self._rtgi_fn("set_rtgi_params", RtgiParams)(self._ctx, C.byref(p)))
-        return p
+        return self._set_params(RtgiParams, self._hip_only(self._RTGI, "set_rtgi_params"), rtgi_default_params, params, fields)
 
     def rtgi_stats(self):
         """UhRtgiStats of the last rtgi pass: pixels, rays, shadow_rays, misses, trace_ms, shadow_ms, filter_ms, composite_ms"""
-        s = RtgiStats()
-        self._check(self._rtgi_fn("get_rtgi_stats", RtgiStats)(self._ctx, C.byref(s)))
-        return s
+        return self._stats(RtgiStats, self._hip_only(self._RTGI, "get_rtgi_stats"))
 
     def rtao_visits(self):
         """(node visits, triangle tests) of the last rtao pass's walks, counted while option "count_visits" is 1; else (0, 0)"""
-        if self.backend != "hip":
-            raise NotImplementedError(f"ray-traced ambient occlusion is a per-context verb of the HIP library; backend {self.backend!r} has none")
-        fn = self._lib.uh_get_rtao_visits
-        fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int
+        fn = self._hip_only(self._RTAO, "get_rtao_visits")
         nodes, tris = C.c_uint64(), C.c_uint64()
         self._check(fn(self._ctx, C.byref(nodes), C.byref(tris)))
         return nodes.value, tris.value
@@ -695,21 +727,10 @@ class Renderer:
     def motion_stats(self):
         """UhMotionStats of the last motion pass: pixels_with / pixels_without a correspondence, meshes_static / _rigid / _deformed /
         _none, motion_ms, snapshot_ms; all zero before the first pass"""
-        if self.backend != "hip":
-            raise NotImplementedError(f"motion vectors are a per-context verb of the HIP library; backend {self.backend!r} has none")
-        fn = self._lib.uh_get_motion_stats
-        fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(MotionStats)], C.c_int
-        s = MotionStats()
-        self._check(fn(self._ctx, C.byref(s)))
-        return s
+        return self._stats(MotionStats, self._hip_only("motion vectors are a per-context verb", "get_motion_stats"))
 
     # -- temporal anti-aliasing (HYBRID_TAA; include/utopian_hip.h "temporal anti-aliasing") ---
-    def _taa_fn(self, name, *argtypes):
-        if self.backend != "hip":
-            raise NotImplementedError(f"temporal anti-aliasing is a per-context verb of the HIP library; backend {self.backend!r} has none")
-        fn = getattr(self._lib, "uh_" + name)
-        fn.argtypes, fn.restype = [C.c_void_p] + [C.POINTER(a) for a in argtypes], C.c_int
-        return fn
+    _TAA = "temporal anti-aliasing is a per-context verb"
 
     @staticmethod
     def taa_default_params():
@@ -719,31 +740,18 @@ class Renderer:
     def set_taa_params(self, params=None, **fields):
         """uh_set_taa_params: `params` (a TaaParams; the defaults when None) with `fields` set on a copy - the params of the
         render_hybrid calls with HYBRID_TAA that follow. A refused call raises and leaves the old ones."""
-        p = TaaParams.from_buffer_copy(taa_default_params() if params is None else params)
-        for k, v in fields.items():
-            if not hasattr(p, k):
-                raise TypeError(f"TaaParams has no field {k!r}")
-            setattr(p, k, v)
-        self._check(self._taa_fn("set_taa_params", TaaParams)(self._ctx, C.byref(p)))
-        return p
+        return self._set_params(TaaParams, self._hip_only(self._TAA, "set_taa_params"), taa_default_params, params, fields)
 
     def reset_taa_history(self):
         """uh_reset_taa_history: the next taa pass starts from no history (a camera cut)"""
-        self._check(self._taa_fn("reset_taa_history")(self._ctx))
+        self._check(self._hip_only(self._TAA, "reset_taa_history")(self._ctx))
 
     def taa_stats(self):
         """UhTaaStats of the last taa pass: history_pixels, reset_pixels, taa_ms; all zero before the first pass"""
-        s = TaaStats()
-        self._check(self._taa_fn("get_taa_stats", TaaStats)(self._ctx, C.byref(s)))
-        return s
+        return self._stats(TaaStats, self._hip_only(self._TAA, "get_taa_stats"))
 
     # -- the HDR display chain (HYBRID_POST; include/utopian_hip.h "HDR display chain") ---
-    def _post_fn(self, name, *argtypes):
-        if self.backend != "hip":
-            raise NotImplementedError(f"the HDR display chain is a per-context verb of the HIP library; backend {self.backend!r} has none")
-        fn = getattr(self._lib, "uh_" + name)
-        fn.argtypes, fn.restype = [C.c_void_p] + list(argtypes), C.c_int
-        return fn
+    _POST = "the HDR display chain is a per-context verb"
 
     @staticmethod
     def post_default_params():
@@ -753,23 +761,15 @@ class Renderer:
     def set_post_params(self, params=None, **fields):
         """uh_set_post_params: `params` (a PostParams; the defaults when None) with `fields` set on a copy - the params of the post
         passes that follow (render_hybrid with HYBRID_POST, post_image). A refused call raises and leaves the old ones."""
-        p = PostParams.from_buffer_copy(post_default_params() if params is None else params)
-        for k, v in fields.items():
-            if not hasattr(p, k):
-                raise TypeError(f"PostParams has no field {k!r}")
-            setattr(p, k, v)
-        self._check(self._post_fn("set_post_params", C.POINTER(PostParams))(self._ctx, C.byref(p)))
-        return p
+        return self._set_params(PostParams, self._hip_only(self._POST, "set_post_params"), post_default_params, params, fields)
 
     def reset_post_exposure(self):
         """uh_reset_post_exposure: the next post pass snaps to its target exposure (a camera cut)"""
-        self._check(self._post_fn("reset_post_exposure")(self._ctx))
+        self._check(self._hip_only(self._POST, "reset_post_exposure")(self._ctx))
 
     def post_stats(self):
         """UhPostStats of the last post pass; all zero before the first"""
-        s = PostStats()
-        self._check(self._post_fn("get_post_stats", C.POINTER(PostStats))(self._ctx, C.byref(s)))
-        return s
+        return self._stats(PostStats, self._hip_only(self._POST, "get_post_stats"))
 
     def post_level_size(self, level):
         """(w, h) of bloom level `level` of this renderer's frame (0: the frame); raises ValueError for one that does not exist"""
@@ -780,7 +780,7 @@ class Renderer:
         img = np.ascontiguousarray(image, dtype=np.float32)
         if img.shape != (self.height, self.width, 4):
             raise ValueError(f"post_image: the image must be ({self.height}, {self.width}, 4), not {img.shape}")
-        self._check(self._post_fn("post_image", C.c_void_p)(self._ctx, img.ctypes.data))
+        self._check(self._hip_only(self._POST, "post_image")(self._ctx, img.ctypes.data))
 
     def read_post(self, which, level=0):
         """uh_read_post: POST_OUTPUT (H, W, 4) float32; POST_BLOOM_DOWN / POST_BLOOM_UP level 1..post_stats().levels, (h, w, 4) float32 at
@@ -794,7 +794,7 @@ class Renderer:
             out = np.empty((self.height, self.width, 4), np.float32)
         else:
             raise ValueError(f"post image index {which} (0..3)")
-        self._check(self._post_fn("read_post", C.c_int, C.c_int, C.c_void_p)(self._ctx, int(which), int(level), out.ctypes.data))
+        self._check(self._hip_only(self._POST, "read_post")(self._ctx, int(which), int(level), out.ctypes.data))
         return out
 
     @staticmethod
@@ -815,18 +815,13 @@ class Renderer:
         return v
 
     # -- the denoiser (uh_denoise; include/utopian_hip.h "the denoiser") --------------------
-    def _denoise_fn(self, name, argtypes):
-        if self.backend != "hip":
-            raise NotImplementedError(f"the denoiser is a per-context verb of the HIP library; backend {self.backend!r} has none")
-        fn = getattr(self._lib, "uh_" + name)
-        fn.argtypes, fn.restype = [C.c_void_p] + argtypes, C.c_int
-        return fn
+    _DENOISE = "the denoiser is a per-context verb"
 
     def denoise(self, view, params=None):
         """uh_denoise on the accumulation of the last render_frame and the G-buffer of the last render_hybrid (same camera as `view`:
         the caller's job); view.prev_frame_projection_view is projection * view of the previous call. params None: the defaults"""
         params = default_denoise_params() if params is None else params
-        self._check(self._denoise_fn("denoise", [C.POINTER(ViewUniformData), C.POINTER(DenoiseParams)])(self._ctx, C.byref(view), C.byref(params)))
+        self._check(self._hip_only(self._DENOISE, "denoise")(self._ctx, C.byref(view), C.byref(params)))
 
     _DENOISE_IMAGES = {
         DENOISE_COLOR: (np.float32, 4),
@@ -840,33 +835,19 @@ class Renderer:
     def read_denoised(self, which):
         """one image of the last denoise call: (H, W, 4) float32 colour / input / temporal colour, (H, W, 4) uint8 output (B, G, R, A),
         (H, W) float32 history length / variance"""
-        fn = self._denoise_fn("read_denoised", [C.c_int, C.c_void_p])
-        if which not in self._DENOISE_IMAGES:
-            raise ValueError(f"denoiser image index {which} (0..5)")
-        dtype, ch = self._DENOISE_IMAGES[which]
-        out = np.empty((self.height, self.width, ch) if ch > 1 else (self.height, self.width), dtype=dtype)
-        self._check(fn(self._ctx, int(which), out.ctypes.data))
-        return out
+        return self._read_image(self._DENOISE_IMAGES, self._hip_only(self._DENOISE, "read_denoised"), which, f"denoiser image index {which} (0..5)")
 
     def reset_denoise_history(self):
-        self._check(self._denoise_fn("reset_denoise_history", [])(self._ctx))
+        self._check(self._hip_only(self._DENOISE, "reset_denoise_history")(self._ctx))
 
     def denoise_stats(self):
         """UhDenoiseStats of the last denoise call: pass_ms of its four stages, geometry pixels, pixels that kept a history"""
-        s = DenoiseStats()
-        self._check(self._denoise_fn("get_denoise_stats", [C.POINTER(DenoiseStats)])(self._ctx, C.byref(s)))
-        return s
+        return self._stats(DenoiseStats, self._hip_only(self._DENOISE, "get_denoise_stats"))
 
     # -- cascaded shadow maps (UH_HYBRID_SHADOW_MAPS; include/utopian_hip.h) ---------------
-    def _shadow_fn(self, name, argtypes):
-        self._hybrid_api()
-        fn = getattr(self._lib, "uh_" + name)
-        fn.argtypes, fn.restype = [C.c_void_p] + argtypes, C.c_int
-        return fn
-
     def set_shadowmap_params(self, params):
         """the cascades the next HYBRID_SHADOW_MAPS render uses: a ShadowmapParams (shadow_cascades, or the caller's own)"""
-        self._check(self._shadow_fn("set_shadowmap_params", [C.POINTER(ShadowmapParams)])(self._ctx, C.byref(params)))
+        self._check(self._hybrid_verb("set_shadowmap_params")(self._ctx, C.byref(params)))
 
     def read_shadow_map(self, cascade):
         """layer `cascade` of the shadow maps: (S, S) float32, row 0 at NDC y = +1"""
@@ -874,27 +855,20 @@ class Renderer:
         if not s:
             s = 16  # the library refuses the read before the first render
         out = np.empty((s, s), dtype=np.float32)
-        self._check(self._shadow_fn("read_shadow_map", [C.c_int, C.c_void_p])(self._ctx, int(cascade), out.ctypes.data))
+        self._check(self._hybrid_verb("read_shadow_map")(self._ctx, int(cascade), out.ctypes.data))
         return out
 
     def shadow_map_stats(self):
         """UhShadowMapStats of the last shadow-map render"""
-        s = ShadowMapStats()
-        self._check(self._shadow_fn("get_shadow_map_stats", [C.POINTER(ShadowMapStats)])(self._ctx, C.byref(s)))
-        return s
+        return self._stats(ShadowMapStats, self._hybrid_verb("get_shadow_map_stats"))
 
     # -- the forward graph (uh_render_forward; include/utopian_hip.h) ------------------------
-    def _forward_fn(self, name, argtypes):
-        if self.backend != "hip" or not hasattr(self._lib, "uh_" + name):
-            raise NotImplementedError(f"the forward graph (shadow maps, forward pass, present) is a per-context verb of the HIP library; backend {self.backend!r} has none")
-        fn = getattr(self._lib, "uh_" + name)
-        fn.argtypes, fn.restype = [C.c_void_p] + argtypes, C.c_int
-        return fn
+    def _forward_verb(self, name):
+        return self._hip_only("the forward graph (shadow maps, forward pass, present) is a per-context verb", name, hasattr(self._lib, "uh_" + name))
 
     def render_forward(self, view, mask=FORWARD_GRAPH):
         """shadow maps, forward pass, present - the reference's Minimal mode in its pass order - for the bits of `mask`"""
-        fn = self._forward_fn("render_forward", [C.POINTER(ViewUniformData), C.c_uint32])
-        self._check(fn(self._ctx, C.byref(view), int(mask)))
+        self._check(self._forward_verb("render_forward")(self._ctx, C.byref(view), int(mask)))
 
     _FORWARD_IMAGES = {
         FORWARD_OUTPUT: (np.float32, 4),
@@ -906,19 +880,11 @@ class Renderer:
     def read_forward(self, which):
         """one image of the forward graph, row 0 at NDC y = +1: (H, W, 4) float32 output, (H, W) float32 depth, (H, W) uint32 draw index
         (FORWARD_NONE where nothing was drawn), (H, W, 4) uint8 present output (B, G, R, A)"""
-        fn = self._forward_fn("read_forward", [C.c_int, C.c_void_p])
-        if which not in self._FORWARD_IMAGES:
-            raise ValueError(f"forward image index {which} (0..3)")
-        dtype, ch = self._FORWARD_IMAGES[which]
-        out = np.empty((self.height, self.width, ch) if ch > 1 else (self.height, self.width), dtype=dtype)
-        self._check(fn(self._ctx, int(which), out.ctypes.data))
-        return out
+        return self._read_image(self._FORWARD_IMAGES, self._forward_verb("read_forward"), which, f"forward image index {which} (0..3)")
 
     def forward_stats(self):
         """UhForwardStats of the last render_forward call"""
-        s = ForwardStats()
-        self._check(self._forward_fn("get_forward_stats", [C.POINTER(ForwardStats)])(self._ctx, C.byref(s)))
-        return s
+        return self._stats(ForwardStats, self._forward_verb("get_forward_stats"))
 
     # -- stand-alone ray queries ----------------------------------------------------------
     def trace_closest(self, rays):
@@ -973,10 +939,8 @@ class Renderer:
 
     @staticmethod
     def rccl_unique_id():
-        lib = load_library()
-        lib.uh_rccl_unique_id.argtypes, lib.uh_rccl_unique_id.restype = [C.c_void_p], C.c_int
         buf = (C.c_uint8 * 128)()
-        st = lib.uh_rccl_unique_id(buf)
+        st = _bind(load_library(), "uh_", "rccl_unique_id")(buf)
         if st != 0:
             raise UtopianError(f"uh_rccl_unique_id failed: {ERR_NAMES.get(st, st)} (is librccl loadable?)")
         return bytes(buf)
@@ -984,15 +948,13 @@ class Renderer:
     def rccl_attach(self, rank, world, unique_id):
         """ncclCommInitRank on this context's device + the band partition with ncclAllGather as its exchange (collective:
         every rank of the job calls it with the id rank 0 made)"""
-        self._lib.uh_rccl_attach.argtypes, self._lib.uh_rccl_attach.restype = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p], C.c_int
         buf = (C.c_uint8 * 128).from_buffer_copy(bytes(unique_id))
-        self._check(self._lib.uh_rccl_attach(self._ctx, rank, world, buf))
+        self._check(self._uh("rccl_attach")(self._ctx, rank, world, buf))
 
     def sun_grid_compare_builders(self):
         """uh_sun_grid_compare_builders: the device-built grid in use against the host builder on the same raster"""
         out = (C.c_uint64 * 8)()
-        self._lib.uh_sun_grid_compare_builders.argtypes, self._lib.uh_sun_grid_compare_builders.restype = [C.c_void_p, C.POINTER(C.c_uint64)], C.c_int
-        self._check(self._lib.uh_sun_grid_compare_builders(self._ctx, out))
+        self._check(self._uh("sun_grid_compare_builders")(self._ctx, out))
         keys = ("cells", "entries_device", "entries_host", "cells_length_differs", "cells_list_differs", "cells_cover_differs", "walkable_cells", "host_build_us")
         return dict(zip(keys, (int(x) for x in out)))
 
@@ -1000,8 +962,7 @@ class Renderer:
         """uh_check_acceleration: the tree in use read back and held to the builders' invariants (csrc/bvh_invariants.h). One
         violation count per class under "violations" (all zero for a sound tree), the first offenders as text under "first"."""
         out = (C.c_uint64 * 16)()
-        self._lib.uh_check_acceleration.argtypes, self._lib.uh_check_acceleration.restype = [C.c_void_p, C.POINTER(C.c_uint64)], C.c_int
-        self._check(self._lib.uh_check_acceleration(self._ctx, out))
+        self._check(self._uh("check_acceleration")(self._ctx, out))
         classes = ("levels", "counts", "refs", "keys", "packets", "empty_slots", "containment")
         return {
             "nodes": int(out[0]), "triangles": int(out[1]), "levels": int(out[2]),
@@ -1014,19 +975,15 @@ class Renderer:
     def rccl_comm_count(self):
         """ranks of the attached RCCL communicator as ncclCommCount reports them (0: none attached)"""
         n = C.c_uint32(0)
-        self._lib.uh_rccl_comm_count.argtypes, self._lib.uh_rccl_comm_count.restype = [C.c_void_p, C.POINTER(C.c_uint32)], C.c_int
-        self._check(self._lib.uh_rccl_comm_count(self._ctx, C.byref(n)))
+        self._check(self._uh("rccl_comm_count")(self._ctx, C.byref(n)))
         return n.value
 
     def rccl_gather_tiles(self, root, total_samples, accumulation_limit=999999):
         """uh_rccl_gather_tiles: every rank's tiles to `root` over the attached communicator, composed there; enqueued (no host wait)"""
-        fn = self._lib.uh_rccl_gather_tiles
-        fn.argtypes, fn.restype = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32], C.c_int
-        self._check(fn(self._ctx, root, total_samples, accumulation_limit))
+        self._check(self._uh("rccl_gather_tiles")(self._ctx, root, total_samples, accumulation_limit))
 
     def rccl_detach(self):
-        self._lib.uh_rccl_detach.argtypes, self._lib.uh_rccl_detach.restype = [C.c_void_p], C.c_int
-        self._check(self._lib.uh_rccl_detach(self._ctx))
+        self._check(self._uh("rccl_detach")(self._ctx))
 
     def tile_pack_count(self, rank):
         out = C.c_uint64()
@@ -1062,14 +1019,8 @@ class MultiGpuRenderer(Renderer):
 
     def __init__(self, width, height, devices, tile_size=64):
         lib = load_library()
-        lib.uh_mgpu_create.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
-        lib.uh_mgpu_create.restype = C.c_int
-        lib.uh_mgpu_last_error.argtypes, lib.uh_mgpu_last_error.restype = [C.c_void_p], C.c_char_p
-        lib.uh_mgpu_context.argtypes, lib.uh_mgpu_context.restype = [C.c_void_p, C.c_int], C.c_void_p
-        lib.uh_mgpu_num_devices.argtypes, lib.uh_mgpu_num_devices.restype = [C.c_void_p], C.c_int
-        for name, extra in (("get_num_lights", [C.POINTER(C.c_uint32)]), ("synchronize", []), ("compose", []), ("refit_acceleration", [])):
-            fn = getattr(lib, "uh_mgpu_" + name)
-            fn.argtypes, fn.restype = [C.c_void_p] + extra, C.c_int
+        for name in ("mgpu_create", "mgpu_last_error", "mgpu_context", "mgpu_num_devices", "mgpu_get_num_lights", "mgpu_synchronize", "mgpu_compose"):
+            _bind(lib, "uh_", name)  # (the group's twins of the context verbs, refit_acceleration among them: CApi below)
         devices = [int(d) for d in devices]
         arr = (C.c_int * len(devices))(*devices)
 
@@ -1099,34 +1050,27 @@ class MultiGpuRenderer(Renderer):
         self._check(self._lib.uh_mgpu_compose(self._ctx))
 
 
+def _default_params(Struct, name):
+    """a `Struct` as uh_<name> fills it"""
+    p = Struct()
+    if _bind(load_library(), "uh_", name)(C.byref(p)) != 0:
+        raise UtopianError(f"uh_{name} failed")
+    return p
+
+
 def rtgi_default_params():
     """UhRtgiParams as uh_rtgi_default_params fills it (needs no GPU)"""
-    fn = load_library().uh_rtgi_default_params
-    fn.argtypes, fn.restype = [C.POINTER(RtgiParams)], C.c_int
-    p = RtgiParams()
-    if fn(C.byref(p)) != 0:
-        raise UtopianError("uh_rtgi_default_params failed")
-    return p
+    return _default_params(RtgiParams, "rtgi_default_params")
 
 
 def rtao_default_params():
     """UhRtaoParams as uh_rtao_default_params fills it (needs no GPU)"""
-    fn = load_library().uh_rtao_default_params
-    fn.argtypes, fn.restype = [C.POINTER(RtaoParams)], C.c_int
-    p = RtaoParams()
-    if fn(C.byref(p)) != 0:
-        raise UtopianError("uh_rtao_default_params failed")
-    return p
+    return _default_params(RtaoParams, "rtao_default_params")
 
 
 def default_denoise_params():
     """UhDenoiseParams as uh_denoise_default_params fills it (needs no GPU)"""
-    fn = load_library().uh_denoise_default_params
-    fn.argtypes, fn.restype = [C.POINTER(DenoiseParams)], C.c_int
-    p = DenoiseParams()
-    if fn(C.byref(p)) != 0:
-        raise UtopianError("uh_denoise_default_params failed")
-    return p
+    return _default_params(DenoiseParams, "denoise_default_params")
 
 
 def compose3x4(a, b):
@@ -1138,40 +1082,26 @@ def compose3x4(a, b):
 
 def taa_default_params():
     """UhTaaParams as uh_taa_default_params fills it (needs no GPU)"""
-    fn = load_library().uh_taa_default_params
-    fn.argtypes, fn.restype = [C.POINTER(TaaParams)], C.c_int
-    p = TaaParams()
-    if fn(C.byref(p)) != 0:
-        raise UtopianError("uh_taa_default_params failed")
-    return p
+    return _default_params(TaaParams, "taa_default_params")
 
 
 def post_default_params():
     """UhPostParams as uh_post_default_params fills it (needs no GPU)"""
-    fn = load_library().uh_post_default_params
-    fn.argtypes, fn.restype = [C.POINTER(PostParams)], C.c_int
-    p = PostParams()
-    if fn(C.byref(p)) != 0:
-        raise UtopianError("uh_post_default_params failed")
-    return p
+    return _default_params(PostParams, "post_default_params")
 
 
 def post_level_size(width, height, level):
     """uh_post_level_size: (w, h) of bloom level `level` of a width x height frame (needs no GPU); ValueError for one that does not exist"""
-    fn = load_library().uh_post_level_size
-    fn.argtypes, fn.restype = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], C.c_int
     w, h = C.c_uint32(), C.c_uint32()
-    if fn(int(width), int(height), int(level), C.byref(w), C.byref(h)) != 0:
+    if _bind(load_library(), "uh_", "post_level_size")(int(width), int(height), int(level), C.byref(w), C.byref(h)) != 0:
         raise ValueError(f"a {width} x {height} frame has no bloom level {level}")
     return int(w.value), int(h.value)
 
 
 def taa_jitter(index):
     """uh_taa_jitter: the sub-pixel offset (jx, jy) of frame `index`, Halton(2, 3) - 0.5 in pixels (needs no GPU)"""
-    fn = load_library().uh_taa_jitter
-    fn.argtypes, fn.restype = [C.c_uint32, C.POINTER(C.c_float * 2)], C.c_int
     out = (C.c_float * 2)()
-    if fn(int(index), C.byref(out)) != 0:
+    if _bind(load_library(), "uh_", "taa_jitter")(int(index), C.byref(out)) != 0:
         raise UtopianError("uh_taa_jitter failed")
     return float(out[0]), float(out[1])
 
@@ -1261,15 +1191,11 @@ class FrameLoop:
 def shadow_cascades(camera, sun_dir):
     """setup_shadow_pass (shadow.rs) for `camera` (its own z_near / z_far) and `sun_dir`: a ShadowmapParams, by uh_shadow_cascades
     (host arithmetic: no device needed)"""
-    lib = load_library()
-    fn = lib.uh_shadow_cascades
-    fp = C.POINTER(C.c_float)
-    fn.argtypes, fn.restype = [fp, fp, C.c_float, C.c_float, fp, C.POINTER(ShadowmapParams)], C.c_int
     view = (C.c_float * 16)(*cam.to_glam(camera.get_view()).tolist())
     proj = (C.c_float * 16)(*cam.to_glam(camera.get_projection()).tolist())
     sun = (C.c_float * 3)(*[float(x) for x in sun_dir])
     out = ShadowmapParams()
-    st = fn(view, proj, float(camera.z_near), float(camera.z_far), sun, C.byref(out))
+    st = _bind(load_library(), "uh_", "shadow_cascades")(view, proj, float(camera.z_near), float(camera.z_far), sun, C.byref(out))
     if st != 0:
         raise UtopianError(f"uh_shadow_cascades: {ERR_NAMES.get(st, st)}")
     return out

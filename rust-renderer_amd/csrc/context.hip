@@ -2,7 +2,7 @@
 // read-backs. Host-side counterpart of utopian::Renderer (utopian/src/renderer.rs), utopian::Raytracing (utopian/src/raytracing.rs) and
 // build_path_tracing_render_graph (utopian/src/renderers/mod.rs:189-375) for this path only.
 // struct uh_ctx is context_state.h; meshes, the tree builders and the refit are scene_build.hip; the hybrid and the forward graph
-// (uh_render_hybrid, uh_render_forward) are hybrid_graph.hip and forward_graph.hip over raster_driver.hip, the denoiser denoise_graph.hip;
+// (uh_render_hybrid, uh_render_forward) are hybrid_graph.hip (its verbs hybrid_verbs.hip, its display chain post_graph.hip) and forward_graph.hip over raster_driver.hip, the denoiser denoise_graph.hip;
 // the sun and camera grids' upkeep is grid_cache.hip; uh_set_option is options.hip; a frame split over several GPUs - the tile and band
 // partitions, the tile composition - is partition.hip, the RCCL link rccl_link.hip.
 #include <hip/hip_runtime.h>

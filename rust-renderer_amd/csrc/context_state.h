@@ -1,7 +1,7 @@
 // context_state.h - struct uh_ctx and the types it is made of, for the files that implement the context: context.hip (lifetime,
 // the path tracer, read-backs), options.hip (uh_set_option), partition.hip (the tile and band partitions of a multi-GPU frame, the
 // tile composition), rccl_link.hip (the RCCL link), scene_build.hip (meshes, builders, refit) and the graphs (raster_driver.hip,
-// hybrid_graph.hip, forward_graph.hip, denoise_graph.hip; what they share: graphs_internal.h). Private: not installed, not part of
+// hybrid_graph.hip, hybrid_verbs.hip, post_graph.hip, forward_graph.hip, denoise_graph.hip; what they share: graphs_internal.h). Private: not installed, not part of
 // the C ABI (include/utopian_hip.h), where uh_ctx stays opaque. The upkeep of the sun and camera grids is grid_cache.hip.
 #pragma once
 #include <hip/hip_runtime.h>

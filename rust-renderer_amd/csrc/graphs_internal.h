@@ -1,6 +1,6 @@
-// graphs_internal.h - what the host files of the graphs share (raster_driver.hip, hybrid_graph.hip, forward_graph.hip,
-// denoise_graph.hip): the timed stages, first-use allocation, the preamble of the stats verbs and the entry points of one file that
-// another calls. Private, like context_state.h; nothing here is exported.
+// graphs_internal.h - what the host files of the graphs share (raster_driver.hip, hybrid_graph.hip, hybrid_verbs.hip, post_graph.hip,
+// forward_graph.hip, denoise_graph.hip): the timed stages, first-use allocation, the preamble of the stats verbs, the params setter and
+// the entry points of one file that another calls. Private, like context_state.h; nothing here is exported.
 #pragma once
 #include <cstring>
 #include <initializer_list>
@@ -92,6 +92,17 @@ static bool stats_begin(uh_ctx* c, void* out, size_t bytes, const char* null_mes
    return *st == UH_OK && c && out && rendered;
 }
 
+// ---- the params verbs of the hybrid passes ----
+// uh_set_*_params of the pass `pass` (the member of uh_ctx::Hybrid that holds its `params`): a null context is UH_ERR_INVALID_ARGUMENT; null
+// params, or params in which `refusal` names a fault, that with "<verb>: null params" or "<verb>: <the fault>", the old ones staying.
+template <class P, class Pass> static int set_params(uh_ctx* c, const P* params, const char* verb, const char* (*refusal)(const P&), Pass uh_ctx::Hybrid::*pass) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!params) return fail(c, UH_ERR_INVALID_ARGUMENT, std::string(verb) + ": null params");
+   if (const char* why = refusal(*params)) return fail(c, UH_ERR_INVALID_ARGUMENT, std::string(verb) + ": " + why);
+   (c->hy.*pass).params = *params;
+   return UH_OK;
+}
+
 // ---- hybrid_graph.hip ----
 int hybrid_events(uh_ctx* c);          // the events of the hybrid stages and of wait_frames_in_flight (first hybrid or forward call)
 int wait_frames_in_flight(uh_ctx* c);  // c->stream (where the graphs run) waits for every other stream of the context
@@ -101,6 +112,10 @@ int hybrid_light_table(uh_ctx* c);     // the uh_add_light table as the lit pass
 // normalised direction, or null for a pass that reads none), and those of the final frame's passes
 HybridDev hybrid_dev(const uh_ctx* c, const UhViewUniformData& view, const float* sun);
 HybridFrameDev hybrid_frame_dev(const uh_ctx* c, const UhViewUniformData& view);
+
+// ---- post_graph.hip ----
+int post_alloc(uh_ctx* c);                                               // the display chain's images, counts and record (first post pass)
+int post_run(uh_ctx* c, const LaunchCfg& lc, const float4* src);  // its three timed stages over `src` on c->stream, into post_output
 
 // ---- raster_driver.hip ----
 // the column-major product a b, and an instance's row-major 3x4 with row (0, 0, 0, 1), column-major

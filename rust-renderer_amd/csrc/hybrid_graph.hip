@@ -1,9 +1,8 @@
-// hybrid_graph.hip - the hybrid graph of include/utopian_hip.h (uh_render_hybrid: the ray-traced passes, the final frame, the IBL
-// maps, the marching-cubes pass, the rasterised G-buffer, the reservoir lights, ray-traced ambient occlusion, motion vectors, temporal
-// anti-aliasing, the HDR display chain, one-bounce ray-traced diffuse GI) with its
-// read and stats verbs, and what the forward graph and the denoiser share with it: the mesh and light tables, the wait behind the
-// frames in flight and destroy_graphs. Host code over uh_ctx::Hybrid (context_state.h); the rasterised passes go through
-// raster_driver.hip. Host-side counterpart of build_render_graph (utopian/src/renderers/mod.rs).
+// hybrid_graph.hip - uh_render_hybrid of include/utopian_hip.h: the plan of a call (which passes run, or why it is refused), first use
+// of what they need and the passes in their order; and what the forward graph and the denoiser share with it: the mesh and light
+// tables, the wait behind the frames in flight and destroy_graphs. The read, stats and params verbs are hybrid_verbs.hip, the HDR display
+// chain post_graph.hip. Host code over uh_ctx::Hybrid (context_state.h); the rasterised passes go through raster_driver.hip.
+// Host-side counterpart of build_render_graph (utopian/src/renderers/mod.rs).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -526,52 +525,6 @@ static HybridPlan hybrid_plan(const uh_ctx& c, const UhViewUniformData& view, ui
    return p;
 }
 
-// ---- the HDR display chain (utopian_hip.h "HDR display chain"; post.hip) ----
-// the pass's images, counts and record (first pass): the counts zero, as every pass leaves them
-static int post_alloc(uh_ctx* c) {
-   uh_ctx::Hybrid::Post& t = c->hy.post;
-   if (t.rec.p) return UH_OK;
-   if (int st = stage_create(c, t.stage, 3)) return st;
-   if (int st = alloc_group(c, [&](auto f) { t.images(c->W, c->H, f); })) return st;
-   HIP_TRY(c, hipMemsetAsync(t.hist.p, 0, kPostBins * sizeof(uint32_t), c->stream));
-   HIP_TRY(c, hipMemsetAsync(t.rec.p, 0, sizeof(PostRecord), c->stream));
-   return UH_OK;
-}
-
-// the three stages over `src` on c->stream, each between its two events: uh_render_hybrid's post pass and uh_post_image
-static int post_run(uh_ctx* c, const LaunchCfg& lc, const float4* src) {
-   uh_ctx::Hybrid::Post& t = c->hy.post;
-   const UhPostParams& p = t.params;
-   PostDev pd{};
-   pd.src = src;
-   pd.out = t.out.p;
-   pd.hist = t.hist.p, pd.hist_copy = t.hist_copy.p, pd.rec = t.rec.p;
-   pd.levels = (p.flags & UH_POST_BLOOM) ? post_level_count(c->W, c->H, p.bloom_levels) : 0;
-   for (uint32_t k = 0; k <= kPostMaxLevels; k++) {
-      if (!post_level_dims(c->W, c->H, k, &pd.lw[k], &pd.lh[k])) pd.lw[k] = pd.lh[k] = 0;
-      pd.down[k] = t.down[k].p;
-      pd.up[k] = k == pd.levels ? t.down[k].p : t.up[k].p;  // up[last] = down[last]
-   }
-   pd.W = c->W, pd.H = c->H;
-   pd.auto_exposure = (p.flags & UH_POST_AUTO_EXPOSURE) ? 1u : 0u;
-   pd.have_prev = t.have_exposure ? 1u : 0u;
-   pd.tonemap = p.tonemap;
-   pd.manual_exposure = p.manual_exposure, pd.key = p.key, pd.min_exposure = p.min_exposure, pd.max_exposure = p.max_exposure;
-   pd.adaptation = p.adaptation, pd.low_percentile = p.low_percentile, pd.high_percentile = p.high_percentile;
-   pd.bloom_threshold = p.bloom_threshold, pd.bloom_intensity = p.bloom_intensity;
-   for (Stage& s : t.stage) s.ran = false;
-   if (int st = timed(c, t.stage[0], [&] { launch_post_meter(lc, pd); })) return st;
-   t.have_exposure = true;  // from here on the record holds this pass's exposure, whatever fails below
-   if (pd.levels)
-      if (int st = timed(c, t.stage[1], [&] { launch_post_bloom(lc, pd); })) return st;
-   if (int st = timed(c, t.stage[2], [&] { launch_post_composite(lc, pd); })) return st;
-   HIP_TRY(c, hipGetLastError());
-   t.metered = pd.auto_exposure != 0;
-   t.levels = pd.levels;
-   t.renders++;
-   return UH_OK;
-}
-
 // First use: the groups the plan asks for, each allocated once (its last buffer says so), and the mesh and light tables
 static int hybrid_prepare(uh_ctx* c, const HybridPlan& p) {
    uh_ctx::Hybrid& h = c->hy;
@@ -921,390 +874,3 @@ int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    reset_stage_records(c->hy, plan, mask);
    return hybrid_passes(c, HybridCall{plan, *view, fp, lc, hd, fd}, mask);
 }
-
-int uh_read_hybrid(uh_ctx* c, int which, void* out) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   const uh_ctx::Hybrid& h = c->hy;
-   if (!h.counter.p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid before the first uh_render_hybrid");
-   if (which < 0 || which > UH_HYBRID_GI_COUNTS) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..19");
-   if (which >= UH_HYBRID_SSAO_IMAGE && which <= UH_HYBRID_PRESENT_OUTPUT && !h.sky_counter.p)
-      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 6..8 before the first call with an SSAO, deferred, sky or present bit");
-   if ((which == UH_HYBRID_DEPTH || which == UH_HYBRID_MARCHING_CUBES_VISIBILITY) && h.mc.renders == 0)
-      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 9..10 before the first marching-cubes pass");
-   if ((which == UH_HYBRID_GBUFFER_DEPTH || which == UH_HYBRID_GBUFFER_VISIBILITY) && h.gr.renders == 0)
-      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 11..12 before the first rasterised G-buffer pass");
-   if (which == UH_HYBRID_LIGHT_VISIBILITY && !h.rl.counters.p)
-      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image 13 before the first call with UH_HYBRID_RESTIR_LIGHTS");
-   if (which == UH_HYBRID_AO_COUNTS && h.ao.renders == 0)
-      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image 14 before the first rtao pass (UH_HYBRID_RTAO with view.ssao_enabled = 1)");
-   if (which == UH_HYBRID_MOTION_IMAGE && h.mv.renders == 0)
-      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image 15 before the first motion pass (UH_HYBRID_GBUFFER | UH_HYBRID_MOTION)");
-   if ((which == UH_HYBRID_TAA_OUTPUT || which == UH_HYBRID_TAA_HISTORY) && h.taa.renders == 0)
-      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: images 16..17 before the first taa pass (UH_HYBRID_TAA)");
-   if ((which == UH_HYBRID_GI_RADIANCE || which == UH_HYBRID_GI_COUNTS) && h.gi.renders == 0)
-      return fail(c, UH_ERR_INVALID_ARGUMENT,
-                  "uh_read_hybrid: images 18..19 before the first rtgi pass (UH_HYBRID_RTGI); until then the image index must be 0..17");
-   // image k's pixels and its bytes per pixel, in UH_HYBRID_* image order
-   const std::pair<const void*, size_t> img[] = {
-      {h.pos.p, sizeof(float4)}, {h.nrm.p, sizeof(float4)}, {h.alb.p, sizeof(uchar4)}, {h.pbr.p, sizeof(float4)}, {h.shadow.p, 1},
-      {h.refl.p, sizeof(uchar4)}, {h.ssao.p, sizeof(uint16_t)}, {h.deferred.p, sizeof(float4)}, {h.present.p, sizeof(uchar4)},
-      {h.mc.target.depth.p, sizeof(float)}, {h.mc.target.vis.p, sizeof(uint32_t)}, {h.gr.target.depth.p, sizeof(float)}, {h.gr.target.vis.p, sizeof(uint32_t)},
-      {h.rl.vis.p, 1}, {h.ao.counts.p, 1}, {h.mv.image.p, sizeof(float4)},
-      {h.taa.col[h.taa.cur].p, sizeof(float4)}, {h.taa.n[h.taa.cur].p, sizeof(float)},
-      {h.gi.radiance.p, sizeof(float4)}, {h.gi.counts.p, sizeof(uint32_t)}};
-   return read_back(c, out, img[which].first, (size_t)c->W * c->H * img[which].second);
-}
-
-int uh_get_hybrid_frame_stats(uh_ctx* c, UhHybridFrameStats* out) {
-   int st;
-   if (!stats_begin(c, out, sizeof(*out), "uh_get_hybrid_frame_stats: null destination", c && c->hy.counter.p, &st)) return st;
-   const uh_ctx::Hybrid& h = c->hy;
-   for (int k = 0; k < kHybridPasses; k++)
-      if ((st = stage_ms(c, c->hy.stage[k], &out->pass_ms[k]))) return st;
-   if (h.stage[kStSky].ran) HIP_TRY(c, hipMemcpy(&out->sky_pixels, h.sky_counter.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-   out->lights = h.frame_lights;
-   return UH_OK;
-}
-
-int uh_get_hybrid_restir_stats(uh_ctx* c, UhHybridRestirStats* out) {
-   int st;
-   if (!stats_begin(c, out, sizeof(*out), "uh_get_hybrid_restir_stats: null destination", c && c->hy.rl.renders != 0, &st)) return st;
-   const uh_ctx::Hybrid& h = c->hy;
-   if ((st = stage_ms(c, c->hy.stage[kStRestirLights], &out->pass_ms))) return st;
-   uint32_t counters[2] = {0, 0};
-   HIP_TRY(c, hipMemcpy(counters, h.rl.counters.p, sizeof(counters), hipMemcpyDeviceToHost));
-   out->rays = counters[0];
-   out->occluded = counters[1];
-   return UH_OK;
-}
-
-// ---- ray-traced ambient occlusion (utopian_hip.h "UH_HYBRID_RTAO"; rtao.hip) ----
-int uh_rtao_default_params(UhRtaoParams* out) {
-   if (!out) return UH_ERR_INVALID_ARGUMENT;
-   *out = UhRtaoParams{4, 1.0f, 1.0f, 2, 0.9f, 0.05f};
-   return UH_OK;
-}
-
-static const char* rtao_params_refusal(const UhRtaoParams& p) {
-   if (p.samples < 1 || p.samples > 64) return "samples must be 1..64";
-   if (!(p.radius > 0.0f && p.radius <= 10000.0f)) return "radius must be finite, > 0 and <= 10000";
-   if (!(p.strength >= 0.0f && p.strength < INFINITY)) return "strength must be finite and >= 0";
-   if (p.blur_radius > 4) return "blur_radius must be 0..4";
-   if (std::isnan(p.blur_normal_cos) || std::isnan(p.blur_plane)) return "blur_normal_cos and blur_plane must not be NaN";
-   return nullptr;
-}
-
-int uh_set_rtao_params(uh_ctx* c, const UhRtaoParams* params) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!params) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_set_rtao_params: null params");
-   if (const char* why = rtao_params_refusal(*params)) return fail(c, UH_ERR_INVALID_ARGUMENT, std::string("uh_set_rtao_params: ") + why);
-   c->hy.ao.params = *params;
-   return UH_OK;
-}
-
-int uh_get_rtao_stats(uh_ctx* c, UhRtaoStats* out) {
-   int st;
-   if (!stats_begin(c, out, sizeof(*out), "uh_get_rtao_stats: null destination", c && c->hy.ao.renders != 0, &st)) return st;
-   const uh_ctx::Hybrid& h = c->hy;
-   if ((st = stage_ms(c, c->hy.stage[kStRtaoTrace], &out->trace_ms))) return st;
-   if ((st = stage_ms(c, c->hy.stage[kStRtaoFilter], &out->filter_ms))) return st;
-   uint32_t counters[2] = {0, 0};
-   HIP_TRY(c, hipMemcpy(counters, h.ao.counters.p, sizeof(counters), hipMemcpyDeviceToHost));
-   out->pixels = counters[0];
-   out->rays = (uint64_t)counters[0] * h.ao.samples;
-   out->occluded = counters[1];
-   return UH_OK;
-}
-
-int uh_get_rtao_visits(uh_ctx* c, uint64_t* nodes, uint64_t* triangles) {
-   int st;
-   if (c && nodes && triangles) *triangles = 0;  // (*nodes: by stats_begin)
-   if (!stats_begin(c, nodes && triangles ? nodes : nullptr, sizeof(*nodes), "uh_get_rtao_visits: null destination", c && c->hy.ao.renders != 0, &st)) return st;
-   const uh_ctx::Hybrid& h = c->hy;
-   uint64_t visits[2] = {0, 0};
-   HIP_TRY(c, hipMemcpy(visits, h.ao.counters.p + 2, sizeof(visits), hipMemcpyDeviceToHost));
-   *nodes = visits[0];
-   *triangles = visits[1];
-   return UH_OK;
-}
-
-// ---- one-bounce ray-traced diffuse GI (utopian_hip.h "UH_HYBRID_RTGI"; rtgi.hip) ----
-int uh_rtgi_default_params(UhRtgiParams* out) {
-   if (!out) return UH_ERR_INVALID_ARGUMENT;
-   *out = UhRtgiParams{2, 3, 16.0f, 1.0f, 0.9f, 0.05f};
-   return UH_OK;
-}
-
-static const char* rtgi_params_refusal(const UhRtgiParams& p) {
-   if (p.samples < 1 || p.samples > 16) return "samples must be 1..16";
-   if (p.blur_radius > 6) return "blur_radius must be 0..6";
-   if (!(p.max_radiance > 0.0f && p.max_radiance < INFINITY)) return "max_radiance must be finite and > 0";
-   if (!(p.intensity >= 0.0f && p.intensity < INFINITY)) return "intensity must be finite and >= 0";
-   if (std::isnan(p.blur_normal_cos) || std::isnan(p.blur_plane)) return "blur_normal_cos and blur_plane must not be NaN";
-   return nullptr;
-}
-
-int uh_set_rtgi_params(uh_ctx* c, const UhRtgiParams* params) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!params) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_set_rtgi_params: null params");
-   if (const char* why = rtgi_params_refusal(*params)) return fail(c, UH_ERR_INVALID_ARGUMENT, std::string("uh_set_rtgi_params: ") + why);
-   c->hy.gi.params = *params;
-   return UH_OK;
-}
-
-int uh_get_rtgi_stats(uh_ctx* c, UhRtgiStats* out) {
-   int st;
-   if (!stats_begin(c, out, sizeof(*out), "uh_get_rtgi_stats: null destination", c && c->hy.gi.renders != 0, &st)) return st;
-   uh_ctx::Hybrid::Rtgi& g = c->hy.gi;
-   float* const ms[4] = {&out->trace_ms, &out->shadow_ms, &out->filter_ms, &out->composite_ms};
-   for (int k = 0; k < 4; k++)
-      if ((st = stage_ms(c, g.stage[k], ms[k]))) return st;
-   uint32_t counters[3] = {0, 0, 0};
-   HIP_TRY(c, hipMemcpy(counters, g.counters.p, sizeof(counters), hipMemcpyDeviceToHost));
-   out->pixels = counters[0];
-   out->rays = (uint64_t)counters[0] * g.samples;
-   out->shadow_rays = counters[1];
-   out->misses = counters[2];
-   return UH_OK;
-}
-
-int uh_get_motion_stats(uh_ctx* c, UhMotionStats* out) {
-   int st;
-   if (!stats_begin(c, out, sizeof(*out), "uh_get_motion_stats: null destination", c && c->hy.mv.renders != 0, &st)) return st;
-   uh_ctx::Hybrid& h = c->hy;
-   if ((st = stage_ms(c, h.mv.stage[0], &out->motion_ms))) return st;
-   if ((st = stage_ms(c, h.mv.stage[1], &out->snapshot_ms))) return st;
-   std::vector<uint32_t> counts(2 * (size_t)h.mv.blocks);  // a pair per block of the kernel's grid
-   HIP_TRY(c, hipMemcpy(counts.data(), h.mv.counters.p, counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-   for (uint32_t b = 0; b < h.mv.blocks; b++) out->pixels_with += counts[2 * b], out->pixels_without += counts[2 * b + 1];
-   out->meshes_static = h.mv.states[kMotionStatic];
-   out->meshes_rigid = h.mv.states[kMotionRigid];
-   out->meshes_deformed = h.mv.states[kMotionDeformed];
-   out->meshes_none = h.mv.states[kMotionNone];
-   return UH_OK;
-}
-
-// ---- temporal anti-aliasing (utopian_hip.h "temporal anti-aliasing"; taa.hip) ----
-int uh_taa_default_params(UhTaaParams* out) {
-   if (!out) return UH_ERR_INVALID_ARGUMENT;
-   *out = UhTaaParams{UH_TAA_CLAMP, 16, 0.1f, 1.0f};
-   return UH_OK;
-}
-
-static const char* taa_params_refusal(const UhTaaParams& p) {
-   if (p.flags & ~(uint32_t)(UH_TAA_CLAMP | UH_TAA_MOTION)) return "unknown flag bits (UH_TAA_CLAMP, UH_TAA_MOTION)";
-   if (p.max_history < 1) return "max_history must be >= 1";
-   if (!(p.alpha_min >= 0.0f && p.alpha_min <= 1.0f)) return "alpha_min must be in [0, 1]";
-   if (!(p.clamp_gamma >= 0.0f && p.clamp_gamma < INFINITY)) return "clamp_gamma must be finite and >= 0";
-   return nullptr;
-}
-
-int uh_set_taa_params(uh_ctx* c, const UhTaaParams* params) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!params) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_set_taa_params: null params");
-   if (const char* why = taa_params_refusal(*params)) return fail(c, UH_ERR_INVALID_ARGUMENT, std::string("uh_set_taa_params: ") + why);
-   c->hy.taa.params = *params;
-   return UH_OK;
-}
-
-int uh_reset_taa_history(uh_ctx* c) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (c->hy.taa.counters.p) {
-      HIP_TRY(c, hipSetDevice(c->device));
-      if (int st = sync_all(c)) return st;
-   }
-   c->hy.taa.valid = false;
-   return UH_OK;
-}
-
-int uh_get_taa_stats(uh_ctx* c, UhTaaStats* out) {
-   int st;
-   if (!stats_begin(c, out, sizeof(*out), "uh_get_taa_stats: null destination", c && c->hy.taa.renders != 0, &st)) return st;
-   uh_ctx::Hybrid& h = c->hy;
-   if ((st = stage_ms(c, h.taa.stage, &out->taa_ms))) return st;
-   std::vector<uint32_t> counters(h.taa.counters.n);  // a pair per slot, a line apart
-   HIP_TRY(c, hipMemcpy(counters.data(), h.taa.counters.p, counters.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-   for (uint32_t s = 0; s < kTaaCounterSlots; s++)
-      out->history_pixels += counters[(size_t)s * kTaaCounterStride], out->reset_pixels += counters[(size_t)s * kTaaCounterStride + 1];
-   return UH_OK;
-}
-
-// ---- the HDR display chain (utopian_hip.h "HDR display chain"; post.hip) ----
-int uh_post_default_params(UhPostParams* out) {
-   if (!out) return UH_ERR_INVALID_ARGUMENT;
-   *out = UhPostParams{UH_POST_AUTO_EXPOSURE | UH_POST_BLOOM, UH_TONEMAP_ACES, 6, 1.0f, 0.18f, 0.015625f, 64.0f, 0.1f, 0.5f, 0.95f, 1.0f, 0.04f};
-   return UH_OK;
-}
-
-static const char* post_params_refusal(const UhPostParams& p) {
-   const auto exposure_ok = [](float v) { return v > 0.0f && v <= 65536.0f; };  // (a NaN fails both compares)
-   if (p.flags & ~(uint32_t)(UH_POST_AUTO_EXPOSURE | UH_POST_BLOOM)) return "unknown flag bits (UH_POST_AUTO_EXPOSURE, UH_POST_BLOOM)";
-   if (p.tonemap > UH_TONEMAP_ACES) return "tonemap must be 0..2 (UH_TONEMAP_NONE, UH_TONEMAP_REINHARD, UH_TONEMAP_ACES)";
-   if (p.bloom_levels < 1 || p.bloom_levels > kPostMaxLevels) return "bloom_levels must be 1..8";
-   if (!exposure_ok(p.manual_exposure) || !exposure_ok(p.key) || !exposure_ok(p.min_exposure) || !exposure_ok(p.max_exposure))
-      return "manual_exposure, key, min_exposure and max_exposure must be finite and in (0, 65536]";
-   if (p.min_exposure > p.max_exposure) return "min_exposure must not exceed max_exposure";
-   if (!(p.adaptation > 0.0f && p.adaptation <= 1.0f)) return "adaptation must be in (0, 1]";
-   if (!(p.low_percentile >= 0.0f && p.low_percentile < p.high_percentile && p.high_percentile <= 1.0f))
-      return "percentiles must be 0 <= low_percentile < high_percentile <= 1";
-   if (!(p.bloom_threshold >= 0.0f && p.bloom_threshold <= 65536.0f) || !(p.bloom_intensity >= 0.0f && p.bloom_intensity <= 65536.0f))
-      return "bloom_threshold and bloom_intensity must be finite and in [0, 65536]";
-   return nullptr;
-}
-
-int uh_set_post_params(uh_ctx* c, const UhPostParams* params) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!params) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_set_post_params: null params");
-   if (const char* why = post_params_refusal(*params)) return fail(c, UH_ERR_INVALID_ARGUMENT, std::string("uh_set_post_params: ") + why);
-   c->hy.post.params = *params;
-   return UH_OK;
-}
-
-int uh_reset_post_exposure(uh_ctx* c) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   c->hy.post.have_exposure = false;  // a pass already enqueued took the flag with it
-   return UH_OK;
-}
-
-int uh_post_image(uh_ctx* c, const float* rgba32f) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   if (!rgba32f) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_post_image: null image");
-   HIP_TRY(c, hipSetDevice(c->device));
-   uh_ctx::Hybrid::Post& t = c->hy.post;
-   if (int st = hybrid_events(c)) return st;
-   if (int st = post_alloc(c)) return st;
-   const size_t pixels = (size_t)c->W * c->H;
-   if (int st = grow(c, t.input, pixels, "uh_post_image")) return st;
-   if (int st = sync_all(c)) return st;  // an earlier pass may still read the upload buffer
-   HIP_TRY(c, hipMemcpy(t.input.p, rgba32f, pixels * sizeof(float4), hipMemcpyHostToDevice));
-   if (int st = post_run(c, cfg(c), t.input.p)) return st;
-   HIP_TRY(c, hipStreamSynchronize(c->stream));
-   return UH_OK;
-}
-
-int uh_post_level_size(uint32_t W, uint32_t H, uint32_t level, uint32_t* w, uint32_t* h) {
-   if (!w || !h) return UH_ERR_INVALID_ARGUMENT;
-   return post_level_dims(W, H, level, w, h) ? UH_OK : UH_ERR_INVALID_ARGUMENT;
-}
-
-int uh_read_post(uh_ctx* c, int which, int level, void* out) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   const uh_ctx::Hybrid::Post& t = c->hy.post;
-   if (!out) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_post: null destination");
-   if (t.renders == 0) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_post before the first post pass (UH_HYBRID_POST or uh_post_image)");
-   if (which < UH_POST_OUTPUT || which > UH_POST_HISTOGRAM) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_post: image must be 0..3");
-   if (which == UH_POST_OUTPUT || which == UH_POST_HISTOGRAM) {
-      if (level != 0) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_post: post_output and the histogram have level 0 only");
-      if (which == UH_POST_OUTPUT) return read_back(c, out, t.out.p, (size_t)c->W * c->H * sizeof(float4));
-      if (!t.metered) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_post: the last pass took no histogram (UH_POST_AUTO_EXPOSURE was not set)");
-      return read_back(c, out, t.hist_copy.p, kPostBins * sizeof(uint32_t));
-   }
-   if (level < 1 || (uint32_t)level > t.levels)
-      return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_post: a bloom level the last pass did not build (1..UhPostStats::levels)");
-   const float4* img = which == UH_POST_BLOOM_DOWN || (uint32_t)level == t.levels ? t.down[level].p : t.up[level].p;
-   return read_back(c, out, img, post_level_texels(c->W, c->H, (uint32_t)level) * sizeof(float4));
-}
-
-int uh_get_post_stats(uh_ctx* c, UhPostStats* out) {
-   int st;
-   if (!stats_begin(c, out, sizeof(*out), "uh_get_post_stats: null destination", c && c->hy.post.renders != 0, &st)) return st;
-   uh_ctx::Hybrid::Post& t = c->hy.post;
-   PostRecord r;
-   HIP_TRY(c, hipMemcpy(&r, t.rec.p, sizeof(r), hipMemcpyDeviceToHost));
-   out->exposure = r.exposure, out->target_exposure = r.target, out->average_luminance = r.lavg;
-   out->metered_pixels = r.metered, out->bad_pixels = r.bad, out->levels = t.levels;
-   if ((st = stage_ms(c, t.stage[0], &out->meter_ms))) return st;
-   if ((st = stage_ms(c, t.stage[1], &out->bloom_ms))) return st;
-   if ((st = stage_ms(c, t.stage[2], &out->tonemap_ms))) return st;
-   out->renders = t.renders;
-   return UH_OK;
-}
-
-// element i (from 1) of the Halton sequence in base b, less 0.5: the radical inverse in double, rounded to float once and kept below 0.5
-static float halton_centred(uint64_t i, uint32_t b) {
-   double f = 1.0, r = 0.0;
-   for (; i; i /= b) {
-      f /= (double)b;
-      r += f * (double)(i % b);
-   }
-   return std::fmin((float)(r - 0.5), 0.49999997f);
-}
-
-int uh_taa_jitter(uint32_t index, float out[2]) {
-   if (!out) return UH_ERR_INVALID_ARGUMENT;
-   out[0] = halton_centred((uint64_t)index + 1, 2);
-   out[1] = halton_centred((uint64_t)index + 1, 3);
-   return UH_OK;
-}
-
-int uh_get_marching_cubes_stats(uh_ctx* c, UhMarchingCubesStats* out) {
-   int st;
-   if (!stats_begin(c, out, sizeof(*out), "uh_get_marching_cubes_stats: null destination", c && c->hy.mc.renders != 0, &st)) return st;
-   const uh_ctx::Hybrid& h = c->hy;
-   if ((st = stage_ms(c, c->hy.stage[kStMarchingCubes], &out->pass_ms))) return st;
-   out->renders = h.mc.renders;
-   out->triangles = h.mc.tris;
-   out->pieces = h.mc.pieces;
-   HIP_TRY(c, hipMemcpy(&out->covered_pixels, h.mc.target.covered.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-   out->lights = h.mc.lights_used;
-   out->time = h.mc.time;
-   return UH_OK;
-}
-
-int uh_get_gbuffer_raster_stats(uh_ctx* c, UhGbufferRasterStats* out) {
-   int st;
-   if (!stats_begin(c, out, sizeof(*out), "uh_get_gbuffer_raster_stats: null destination", c && c->hy.gr.renders != 0, &st)) return st;
-   const uh_ctx::Hybrid& h = c->hy;
-   if (h.gbuffer_rasterised)  // the G-buffer stage's record is the last rasterised pass's
-      if ((st = stage_ms(c, c->hy.stage[kStGbuffer], &out->pass_ms))) return st;
-   out->renders = h.gr.renders;
-   out->pieces = h.gr.pieces;
-   HIP_TRY(c, hipMemcpy(&out->covered_pixels, h.gr.target.covered.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-   return UH_OK;
-}
-
-int uh_read_environment(uh_ctx* c, int which, int face, int mip, void* out) {
-   if (!c) return UH_ERR_INVALID_ARGUMENT;
-   const uh_ctx::Hybrid& h = c->hy;
-   if (h.env.builds == 0) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_environment before the first call with UH_HYBRID_ENVIRONMENT");
-   if (which == UH_ENV_BRDF_LUT) {
-      if (face != 0 || mip != 0) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_environment: the BRDF LUT has face 0 and mip 0 only");
-      return read_back(c, out, h.env.lut.p, (size_t)kLutSize * kLutSize * sizeof(uint32_t));
-   }
-   if (which < UH_ENV_ENVIRONMENT || which > UH_ENV_SPECULAR) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_environment: map must be 0..3");
-   const int mips = which == UH_ENV_IRRADIANCE ? 1 : (int)kEnvMips;
-   if (face < 0 || face > 5 || mip < 0 || mip >= mips) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_environment: face 0..5, mip 0..7 (irradiance: 0)");
-   const size_t S = kEnvSize >> mip;
-   const float4* base = which == UH_ENV_ENVIRONMENT ? h.env.cube.p : which == UH_ENV_IRRADIANCE ? h.env.irr.p : h.env.spec.p;
-   return read_back(c, out, base + env_mip_offset((uint32_t)mip) + (size_t)face * S * S, S * S * sizeof(float4));
-}
-
-int uh_get_environment_stats(uh_ctx* c, UhEnvironmentStats* out) {
-   int st;
-   if (!stats_begin(c, out, sizeof(*out), "uh_get_environment_stats: null destination", c && c->hy.env.builds != 0, &st)) return st;
-   const uh_ctx::Hybrid& h = c->hy;
-   for (int k = 0; k < 4; k++)
-      if ((st = stage_ms(c, c->hy.stage[kStEnvCube + k], &out->pass_ms[k]))) return st;
-   out->builds = h.env.builds;
-   std::memcpy(out->sun_dir, h.env.sun, sizeof(out->sun_dir));
-   std::memcpy(out->eye, h.env.eye, sizeof(out->eye));
-   return UH_OK;
-}
-
-int uh_get_hybrid_stats(uh_ctx* c, UhHybridStats* out) {
-   int st;
-   if (!stats_begin(c, out, sizeof(*out), "uh_get_hybrid_stats: null destination", c && c->hy.counter.p, &st)) return st;
-   const uh_ctx::Hybrid& h = c->hy;
-   uint32_t metal = 0;
-   if (h.stage[kStReflections].ran) HIP_TRY(c, hipMemcpy(&metal, h.counter.p, sizeof(metal), hipMemcpyDeviceToHost));
-   const uint64_t n = (uint64_t)c->W * c->H;
-   out->rays[0] = h.stage[kStGbuffer].ran && !h.gbuffer_rasterised ? n : 0;  // a rasterised pass casts no ray
-   out->rays[1] = h.stage[kStShadows].ran ? n : 0;
-   out->rays[2] = metal;
-   out->reflection_pixels = metal;
-   const int stages[3] = {kStGbuffer, kStShadows, kStReflections};  // the header's order
-   for (int k = 0; k < 3; k++)
-      if ((st = stage_ms(c, c->hy.stage[stages[k]], &out->pass_ms[k]))) return st;
-   return UH_OK;
-}
-

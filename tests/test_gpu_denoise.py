@@ -252,7 +252,7 @@ def test_refusals_run_nothing_and_leave_the_history():
     refused(v, bad, "reserved")
     with pytest.raises(ValueError, match="0..5"):
         r.gpu.read_denoised(6)
-    fn = r.gpu._denoise_fn("read_denoised", [C.c_int, C.c_void_p])
+    fn = rr.api._bind(r.gpu._lib, "uh_", "read_denoised")
     assert fn(r.gpu._ctx, 6, before["color"].ctypes.data) == 1 and fn(r.gpu._ctx, -1, before["color"].ctypes.data) == 1
     # the history survived all of them: the next call of the camera at rest has history 2
     r.denoise(r.shoot(r.view()), p)

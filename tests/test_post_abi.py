@@ -37,7 +37,7 @@ def test_header_declares_the_bit_the_verbs_and_the_contract():
               "int uh_post_level_size(uint32_t W, uint32_t H, uint32_t level, uint32_t* w, uint32_t* h);", "UH_HYBRID_FRAME = 0x7f"):
         assert s in text, s
     assert "1u << 9" not in text, "bit 9 stays unused"
-    assert "image index must be 0..17" in open(os.path.join(ROOT, "rust-renderer_amd", "csrc", "hybrid_graph.hip")).read(), "uh_read_hybrid keeps its images"
+    assert "image index must be 0..17" in open(os.path.join(ROOT, "rust-renderer_amd", "csrc", "hybrid_verbs.hip")).read(), "uh_read_hybrid keeps its images"
     for verb in VERBS:
         assert verb.replace("uh_", "uh_mgpu_", 1) not in text, verb
     section = text[text.index("---- HDR display chain"):]
