@@ -244,7 +244,7 @@ typedef struct uh_ctx uh_ctx;
  *        triangle total, 8 bytes, back to size its buffers), uh_get_isosurface_update_stats, uh_update_mesh_vertices (device input:
  *        it reads a 4-byte verdict on the caller's buffer back before it takes it), uh_get_mesh_update_stats, uh_read_denoised,
  *        uh_get_denoise_stats, uh_reset_denoise_history, uh_get_rtao_stats, uh_get_rtao_visits, uh_get_motion_stats, uh_reset_taa_history,
- *        uh_get_taa_stats, uh_post_image, uh_read_post, uh_get_post_stats, uh_get_rtgi_stats, uh_destroy;
+ *        uh_get_taa_stats, uh_post_image, uh_read_post, uh_get_post_stats, uh_get_rtgi_stats, uh_get_glossy_stats, uh_destroy;
  *   enqueues like a frame, ordered behind the frames in flight and before those that follow:  uh_rccl_gather_tiles, uh_mgpu_compose;
  *        uh_set_option for "frames_in_flight" and for "time_kernels" 1 -> 0 (the others only change what the NEXT enqueued
  *        frame does: "furnace", "sun_grid*", "camera_grid*", "overlap", "batch_frames", "trace_blocks_per_cu", "count_visits",
@@ -252,8 +252,9 @@ typedef struct uh_ctx uh_ctx;
  *        needs uh_build_acceleration, which waits);
  *   host state only (no device access, nothing to wait for):  uh_add_mesh, uh_add_light, uh_set_instance_transform,
  *        uh_get_num_lights, uh_mesh_info, uh_read_mesh, uh_get_restir_rows, uh_tile_pack_count, uh_set_rtao_params, uh_set_taa_params,
- *        uh_set_post_params, uh_reset_post_exposure, uh_set_rtgi_params (read by the next uh_render_hybrid; the post pair also by the
- *        next uh_post_image), uh_taa_default_params, uh_taa_jitter, uh_post_default_params, uh_post_level_size, uh_rtgi_default_params,
+ *        uh_set_post_params, uh_reset_post_exposure, uh_set_rtgi_params, uh_set_glossy_params (read by the next uh_render_hybrid; the post
+ *        pair also by the next uh_post_image), uh_taa_default_params, uh_taa_jitter, uh_post_default_params, uh_post_level_size,
+ *        uh_rtgi_default_params, uh_glossy_default_params,
  *        uh_last_error
  *        (uh_read_mesh of a mesh that uh_update_isosurface_mesh has made device-resident, or that uh_update_mesh_vertices last updated
  *        from a device pointer, copies it from the device: a blocking copy);
@@ -649,7 +650,7 @@ int uh_mgpu_set_option(uh_mgpu* group, const char* name, int value);
  * UH_HYBRID_RT_REFLECTIONS with view->ibl_enabled == 1 is UH_ERR_INVALID_ARGUMENT - and nothing runs - until the IBL maps (irradiance,
  * specular, BRDF LUT of ibl.rs) have been built with UH_HYBRID_ENVIRONMENT, below; mask bits, UH_ERR_NOT_BUILT and moved instances with
  * view->rebuild_tlas as for uh_render_frame (bits above UH_HYBRID_SHADOW_MAPS, below, are ignored, except UH_HYBRID_MARCHING_CUBES,
- * UH_HYBRID_GBUFFER_RASTER, UH_HYBRID_RESTIR_LIGHTS, UH_HYBRID_RTAO, UH_HYBRID_MOTION, UH_HYBRID_TAA, UH_HYBRID_POST and UH_HYBRID_RTGI).
+ * UH_HYBRID_GBUFFER_RASTER, UH_HYBRID_RESTIR_LIGHTS, UH_HYBRID_RTAO, UH_HYBRID_MOTION, UH_HYBRID_TAA, UH_HYBRID_POST, UH_HYBRID_RTGI and UH_HYBRID_GLOSSY).
  * STREAM ORDER: uh_render_hybrid enqueues like a frame (behind the frames in flight, ahead of those that follow); uh_read_hybrid and
  * uh_get_hybrid_stats wait for all work of the context and are complete on return. The exception is UH_HYBRID_SHADOW_MAPS, below: a
  * call that renders shadow maps BLOCKS the host until the frames in flight and the pass's binning have finished (it reads the
@@ -1423,8 +1424,8 @@ int uh_post_level_size(uint32_t W, uint32_t H, uint32_t level, uint32_t* w, uint
  * deferred_output (and what later passes of the call make of it) and its own two; its rays are counted in UhRtgiStats only, and
  * UhHybridFrameStats keeps its layout and its times. Without the bit every pass, image, statistic and allocation is what it was.
  * No uh_mgpu_ twin.
- * OUT OF SCOPE: point, spot and reservoir lights at the hit; more than one bounce; specular GI; a history of its own (UH_HYBRID_TAA
- * serves); the forward graph.
+ * OUT OF SCOPE: point, spot and reservoir lights at the hit; more than one bounce; specular GI (a pass of its own: UH_HYBRID_GLOSSY,
+ * below); a history of its own (UH_HYBRID_TAA serves); the forward graph.
  * Arithmetic: DESIGN.md section 2, "Ray-traced diffuse GI". */
 enum { UH_HYBRID_RTGI = 1u << 17 };
 enum { UH_HYBRID_GI_RADIANCE = 18 /* RGBA32F: Ef, w = 1 where the pixel cast */, UH_HYBRID_GI_COUNTS = 19 /* 4 x uint8: sunlit, dark, emitter, missed */ };
@@ -1454,6 +1455,88 @@ UH_LAYOUT_ASSERT(sizeof(UhRtgiStats) == 48 && offsetof(UhRtgiStats, rays) == 8 &
 int uh_rtgi_default_params(UhRtgiParams* out); /* needs no GPU: 2, 3, 16.0, 1.0, 0.9, 0.05; UH_ERR_INVALID_ARGUMENT for NULL */
 int uh_set_rtgi_params(uh_ctx* ctx, const UhRtgiParams* params); /* validated here; a refused call leaves the old ones */
 int uh_get_rtgi_stats(uh_ctx* ctx, UhRtgiStats* out);            /* waits; all zero before the first pass */
+
+/* ---- ray-traced glossy reflections for the hybrid frame: the specular half of the indirect light ---------------------------------------
+ * An EXTENSION: the reference's only reflection of the scene is rt_reflections' perfect mirror on material type 1. UH_HYBRID_GLOSSY
+ * (bit 18) adds one pass to uh_render_hybrid directly AFTER the rtgi pass (after the deferred pass when that bit is clear) and BEFORE the
+ * marching-cubes, sky, taa and post passes. It adds roughness-aware specular reflection of the scene's own geometry to deferred_output;
+ * the deferred pass and rt_reflections are untouched. UH_HYBRID_FRAME | UH_HYBRID_RTGI | UH_HYBRID_GLOSSY is the natural call.
+ *   pixels    RTGI's rule first: position texel w != 0 and Nn = normalize(N) finite. Then the material record as deferred.frag forms it
+ *             (index uint(pbr.a); out of range: factors 1, type 0). The pixel casts when it is not (raytracing_supported == 1 and type 1:
+ *             it holds its mirror), r = pbr.g * roughness_factor has r >= 0 && r <= max_roughness (a NaN fails), V = normalize(eye - P)
+ *             is finite and NoV = dot(Nn, V) > 0.
+ *   rays      `samples` per pixel that casts. alpha = r r, a2 = alpha alpha. T, B from Nn by the branch-free frame of Duff et al. 2017.
+ *             The half vector Hw is drawn from the GGX distribution of visible normals (Heitz 2018) with randomPointInUnitDisk of the
+ *             state initRNG(px, py, W, (frameNumber(view) * 64 + s) ^ 0x474C4F53); d = normalize((2 dot(V, Hw)) Hw - V). A sample whose
+ *             NoL = dot(Nn, d) is not > 0 is BELOW: no ray, an all-zero record, counted dark. Else a closest-hit ray from
+ *             offsetRay(P, Nn), tmin 0.001, tmax 10000.
+ *   radiance  L of a cast ray is UH_HYBRID_RTGI's (sky unclamped with exact heights, (1, 1, 1) for type 3 and under "furnace" for a miss,
+ *             shadowed-sun-lit Lambert or dark elsewhere), clamped per channel with this pass's max_radiance.
+ *   weight    the unbiased visible-normal estimator, height-correlated Smith term, Fresnel split off: sv = sqrt((NoV NoV)(1 - a2) + a2),
+ *             sl likewise of NoL, Gw = (NoL (NoV + sv)) / (NoL sv + NoV sl); x = 1 - dot(V, Hw), x5 = ((x x)(x x)) x. The ray's record
+ *             is (Gw L, x5).
+ *   pixel     S = (sum R_s (1 - x5_s)) / samples and Bi = (sum R_s x5_s) / samples, in sample order from the s = 0 term.
+ *   filter    per pixel radius re = (int)(min(r / blur_roughness, 1) * blur_radius); re == 0: Sf = S, Bf = Bi. Else the mean over the
+ *             taps (dx, dy) in [-re, re]^2, dy outer: the centre, and every tap in the frame that cast, has max(|dx|, |dy|) <= its own
+ *             re, dot(Nn_tap, Nn) >= blur_normal_cos and |dot(P_tap - P, Nn)| <= blur_plane.
+ *   composite for every pixel that cast, base, metallic and occlusion as deferred.frag:52-65 forms them: F0 = 0.04 (1 - metallic) +
+ *             base metallic; add = ((F0 Sf + Bf) intensity) occlusion, times (view->ssao_enabled == 1) the ssao texel / 65535;
+ *             deferred_output.rgb += add, alpha untouched, no shadow factor.
+ * PARAMS: uh_set_glossy_params validates and keeps them (a refused call leaves the old ones); the defaults of uh_glossy_default_params:
+ * 1 sample, blur_radius 3, max_roughness 0.6, max_radiance 16.0, intensity 1.0, blur_roughness 0.5, 0.95, 0.05.
+ * UH_ERR_INVALID_ARGUMENT with a message, and nothing runs, in this order after every rule above (UH_HYBRID_RTGI's included): the bit
+ * and view->raytracing_supported != 1; no G-buffer rendered in this call or an earlier one; the bit and view->ibl_enabled == 1 (the IBL
+ * specular term and this pass would both count the sky); the bit without UH_HYBRID_DEFERRED in the same call. UH_ERR_CAPACITY for a
+ * frame of 2^28 pixels or more. UH_ERR_NOT_BUILT before uh_build_acceleration, as without the bit.
+ * READ-BACK (uh_read_hybrid, UH_ERR_INVALID_ARGUMENT before the first glossy pass; all three in G-buffer orientation):
+ * UH_HYBRID_GLOSSY_SCALE and UH_HYBRID_GLOSSY_BIAS, RGBA32F: Sf and Bf, w = 1 where the pixel cast, (0, 0, 0, 0) elsewhere.
+ * UH_HYBRID_GLOSSY_COUNTS, 4 bytes per pixel: sunlit, dark (below samples among them), emitter, missed; they sum to `samples` where the
+ * pixel cast and are 0 elsewhere.
+ * RESOURCES: 73 bytes per pixel (counts, the two images, the two unfiltered means, the pixel queue, the radius byte) and 68 bytes per ray
+ * (its hit record, which becomes its radiance record, its origin and direction, its sun-ray record, its queue word) at the largest
+ * `samples` a pass has run with, allocated by the first pass; freed by uh_destroy. A context that never sets the bit allocates nothing.
+ * STREAM ORDER: as uh_render_hybrid. uh_set_glossy_params is host state, read by the next uh_render_hybrid; uh_get_glossy_stats waits.
+ * ISOLATION: the bit changes no reservoir, accumulation, gbuffer_position, grid, UhStats, RTAO or RTGI state, and no hybrid image but
+ * deferred_output (and what later passes of the call make of it) and its own three. Without the bit every pass, image, statistic and
+ * allocation is what it was.
+ * No uh_mgpu_ twin.
+ * OUT OF SCOPE: replacing rt_reflections or lighting metal pixels; point, spot and reservoir lights at the hit; a second bounce; a
+ * history of its own (UH_HYBRID_TAA serves); the forward graph; moving UH_HYBRID_RTGI onto this pass's kernels.
+ * Arithmetic: DESIGN.md section 2, "Ray-traced glossy reflections". */
+enum { UH_HYBRID_GLOSSY = 1u << 18 };
+enum { UH_HYBRID_GLOSSY_SCALE = 20 /* RGBA32F: Sf, w = 1 where the pixel cast */, UH_HYBRID_GLOSSY_BIAS = 21 /* RGBA32F: Bf, w likewise */,
+       UH_HYBRID_GLOSSY_COUNTS = 22 /* 4 x uint8: sunlit, dark, emitter, missed */ };
+typedef struct UhGlossyParams {
+   uint32_t samples;      /* rays per pixel that casts, 1..16 */
+   uint32_t blur_radius;  /* the filter's largest radius, 0..6; 0 = no filter */
+   float max_roughness;   /* a pixel casts when 0 <= pbr.g * roughness_factor <= this; finite, >= 0 */
+   float max_radiance;    /* the cap of a ray's L per channel; finite, > 0 */
+   float intensity;       /* scales what the composite adds; finite, >= 0 */
+   float blur_roughness;  /* the roughness at which a pixel's radius reaches blur_radius; finite, > 0 */
+   float blur_normal_cos; /* a tap counts when dot(Nn_tap, Nn) >= this; not NaN */
+   float blur_plane;      /* and |dot(P_tap - P, Nn)| <= this (world units); not NaN */
+} UhGlossyParams;
+UH_LAYOUT_ASSERT(sizeof(UhGlossyParams) == 32 && offsetof(UhGlossyParams, blur_radius) == 4 && offsetof(UhGlossyParams, max_roughness) == 8 &&
+                    offsetof(UhGlossyParams, max_radiance) == 12 && offsetof(UhGlossyParams, intensity) == 16 &&
+                    offsetof(UhGlossyParams, blur_roughness) == 20 && offsetof(UhGlossyParams, blur_normal_cos) == 24 &&
+                    offsetof(UhGlossyParams, blur_plane) == 28,
+                 "UhGlossyParams (32 B)");
+/* the last glossy pass: the pixels that cast, the rays cast and the below samples (rays + below == pixels * samples), the sun rays cast
+ * from the hits, the rays that missed, and the hipEvent times of classify + ray generation + closest-hit walk, of the hit shading, of
+ * the sun rays' any-hit walk, of the mean + filter and of the composite. All zero before the first pass. Waits. */
+typedef struct UhGlossyStats {
+   uint64_t pixels, rays, below, shadow_rays, misses;
+   float trace_ms, shade_ms, shadow_ms, filter_ms, composite_ms; /* then 4 bytes of tail padding */
+} UhGlossyStats;
+UH_LAYOUT_ASSERT(sizeof(UhGlossyStats) == 64 && offsetof(UhGlossyStats, rays) == 8 && offsetof(UhGlossyStats, below) == 16 &&
+                    offsetof(UhGlossyStats, shadow_rays) == 24 && offsetof(UhGlossyStats, misses) == 32 &&
+                    offsetof(UhGlossyStats, trace_ms) == 40 && offsetof(UhGlossyStats, shade_ms) == 44 &&
+                    offsetof(UhGlossyStats, shadow_ms) == 48 && offsetof(UhGlossyStats, filter_ms) == 52 &&
+                    offsetof(UhGlossyStats, composite_ms) == 56,
+                 "UhGlossyStats (64 B)");
+int uh_glossy_default_params(UhGlossyParams* out); /* needs no GPU: 1, 3, 0.6, 16.0, 1.0, 0.5, 0.95, 0.05; UH_ERR_INVALID_ARGUMENT for NULL */
+int uh_set_glossy_params(uh_ctx* ctx, const UhGlossyParams* params); /* validated here; a refused call leaves the old ones */
+int uh_get_glossy_stats(uh_ctx* ctx, UhGlossyStats* out);            /* waits; all zero before the first pass */
 
 #ifdef __cplusplus
 }

@@ -329,14 +329,15 @@ class Renderer {
    // one image as bytes: W*H texels of 16 (position, normal, pbr, deferred output, the motion image of UH_HYBRID_MOTION), 4 (albedo, reflections, present output, the
    // marching-cubes and rasterised G-buffer depth floats and draw indices uint32), 2 (SSAO) or 1 (shadows, light visibility, the
    // occluded-ray counts of UH_HYBRID_RTAO) bytes; taa_output of UH_HYBRID_TAA 16, its history length 4; the radiance of UH_HYBRID_RTGI
-   // 16, its four ray counts 4
+   // 16, its four ray counts 4; the scale and bias images of UH_HYBRID_GLOSSY 16 each, its four ray counts 4
    std::vector<uint8_t> read_hybrid(int which) {
       const size_t texel = (which == UH_HYBRID_AO_COUNTS) ? 1
                            : (which == UH_HYBRID_SHADOWS || which == UH_HYBRID_LIGHT_VISIBILITY) ? 1
                            : (which == UH_HYBRID_SSAO_IMAGE) ? 2
                            : (which == UH_HYBRID_ALBEDO || which == UH_HYBRID_REFLECTIONS || which == UH_HYBRID_PRESENT_OUTPUT ||
                               which == UH_HYBRID_DEPTH || which == UH_HYBRID_MARCHING_CUBES_VISIBILITY || which == UH_HYBRID_GBUFFER_DEPTH ||
-                              which == UH_HYBRID_GBUFFER_VISIBILITY || which == UH_HYBRID_TAA_HISTORY || which == UH_HYBRID_GI_COUNTS) ? 4
+                              which == UH_HYBRID_GBUFFER_VISIBILITY || which == UH_HYBRID_TAA_HISTORY || which == UH_HYBRID_GI_COUNTS ||
+                              which == UH_HYBRID_GLOSSY_COUNTS) ? 4
                                                                      : 16;  // (UH_HYBRID_MOTION_IMAGE and UH_HYBRID_TAA_OUTPUT among them)
       static_assert(UH_HYBRID_MOTION_IMAGE == 15, "read_hybrid sizes image 15 as 16-byte texels");
       std::vector<uint8_t> out((size_t)width_ * height_ * texel);
@@ -396,6 +397,19 @@ class Renderer {
    UhRtgiStats rtgi_stats() {
       UhRtgiStats s;
       check(uh_get_rtgi_stats(ctx_, &s), "rtgi_stats");
+      return s;
+   }
+   // ray-traced glossy reflections behind the rtgi pass of render_hybrid (UH_HYBRID_GLOSSY; utopian_hip.h): the params of the calls that
+   // follow, and the last pass's pixels, rays, below samples, sun rays, misses and times
+   static UhGlossyParams default_glossy_params() {
+      UhGlossyParams p;
+      if (uh_glossy_default_params(&p) != UH_OK) throw Error(UH_ERR_INVALID_ARGUMENT, "uh_glossy_default_params");
+      return p;
+   }
+   void set_glossy_params(const UhGlossyParams& params) { check(uh_set_glossy_params(ctx_, &params), "set_glossy_params"); }
+   UhGlossyStats glossy_stats() {
+      UhGlossyStats s;
+      check(uh_get_glossy_stats(ctx_, &s), "glossy_stats");
       return s;
    }
    // motion vectors (UH_HYBRID_GBUFFER | UH_HYBRID_MOTION; utopian_hip.h "motion vectors"): the last motion pass's pixels with and

@@ -41,6 +41,9 @@ from .types import (
     HYBRID_AO_COUNTS,
     HYBRID_GI_COUNTS,
     HYBRID_GI_RADIANCE,
+    HYBRID_GLOSSY_BIAS,
+    HYBRID_GLOSSY_COUNTS,
+    HYBRID_GLOSSY_SCALE,
     HYBRID_DEFERRED_OUTPUT,
     HYBRID_DEPTH,
     HYBRID_GBUFFER_DEPTH,
@@ -90,6 +93,8 @@ from .types import (
     RtaoStats,
     RtgiParams,
     RtgiStats,
+    GlossyParams,
+    GlossyStats,
     Stats,
     TaaParams,
     TaaStats,
@@ -175,6 +180,9 @@ _LIBRARY_VERBS = {
     "rtgi_default_params": [_p(RtgiParams)],
     "set_rtgi_params": [_vp, _p(RtgiParams)],
     "get_rtgi_stats": [_vp, _p(RtgiStats)],
+    "glossy_default_params": [_p(GlossyParams)],
+    "set_glossy_params": [_vp, _p(GlossyParams)],
+    "get_glossy_stats": [_vp, _p(GlossyStats)],
     "get_motion_stats": [_vp, _p(MotionStats)],
     "taa_default_params": [_p(TaaParams)],
     "set_taa_params": [_vp, _p(TaaParams)],
@@ -641,6 +649,8 @@ class Renderer:
     _taa_rendered = False
     # the two images of HYBRID_RTGI: the library refuses them before the first rtgi pass
     _GI_IMAGES = {HYBRID_GI_RADIANCE: (np.float32, 4), HYBRID_GI_COUNTS: (np.uint8, 4)}
+    # the three images of HYBRID_GLOSSY: the library refuses them before the first glossy pass
+    _GLOSSY_IMAGES = {HYBRID_GLOSSY_SCALE: (np.float32, 4), HYBRID_GLOSSY_BIAS: (np.float32, 4), HYBRID_GLOSSY_COUNTS: (np.uint8, 4)}
 
     def read_hybrid(self, which):
         """one image of the hybrid graph: (H, W, 4) float32 position / normal / pbr / deferred output, (H, W, 4) uint8 albedo / reflections /
@@ -650,10 +660,11 @@ class Renderer:
         (H, W) uint8 occluded-ray counts of HYBRID_RTAO, (H, W, 4) float32 motion image of HYBRID_MOTION (previous world position, w = 1
         with a correspondence), once a call with HYBRID_TAA has run (H, W, 4) float32 taa_output and (H, W) float32 history length, and of
         HYBRID_RTGI (H, W, 4) float32 filtered incoming radiance (w = 1 where the pixel cast) and (H, W, 4) uint8 ray counts (sunlit, dark,
-        emitter, missed)"""
-        images = {**self._HYBRID_IMAGES, **(self._TAA_IMAGES if self._taa_rendered else {}), **self._GI_IMAGES}
+        emitter, missed), and of HYBRID_GLOSSY (H, W, 4) float32 filtered scale and bias sums (w = 1 where the pixel cast) and (H, W, 4) uint8
+        ray counts (sunlit, dark, emitter, missed)"""
+        images = {**self._HYBRID_IMAGES, **(self._TAA_IMAGES if self._taa_rendered else {}), **self._GI_IMAGES, **self._GLOSSY_IMAGES}
         return self._read_image(images, self._hybrid_api().read_hybrid, which,
-                                f"hybrid image index {which} (0..15, 18..19, and 16..17 once a render_hybrid call with HYBRID_TAA has run)")
+                                f"hybrid image index {which} (0..15, 18..22, and 16..17 once a render_hybrid call with HYBRID_TAA has run)")
 
     def hybrid_stats(self):
         return self._stats(HybridStats, self._hybrid_api().get_hybrid_stats)
@@ -715,6 +726,18 @@ class Renderer:
     def rtgi_stats(self):
         """UhRtgiStats of the last rtgi pass: pixels, rays, shadow_rays, misses, trace_ms, shadow_ms, filter_ms, composite_ms"""
         return self._stats(RtgiStats, self._hip_only(self._RTGI, "get_rtgi_stats"))
+
+    # -- ray-traced glossy reflections (HYBRID_GLOSSY; include/utopian_hip.h "UH_HYBRID_GLOSSY") ---
+    _GLOSSY = "ray-traced glossy reflections are a per-context verb"
+
+    def set_glossy_params(self, params=None, **fields):
+        """uh_set_glossy_params: `params` (a GlossyParams; the defaults when None) with `fields` set on a copy - the params of the
+        render_hybrid calls with HYBRID_GLOSSY that follow. A refused call raises and leaves the old ones."""
+        return self._set_params(GlossyParams, self._hip_only(self._GLOSSY, "set_glossy_params"), glossy_default_params, params, fields)
+
+    def glossy_stats(self):
+        """UhGlossyStats of the last glossy pass: pixels, rays, below, shadow_rays, misses, trace_ms, shade_ms, shadow_ms, filter_ms, composite_ms"""
+        return self._stats(GlossyStats, self._hip_only(self._GLOSSY, "get_glossy_stats"))
 
     def rtao_visits(self):
         """(node visits, triangle tests) of the last rtao pass's walks, counted while option "count_visits" is 1; else (0, 0)"""
@@ -1056,6 +1079,11 @@ def _default_params(Struct, name):
     if _bind(load_library(), "uh_", name)(C.byref(p)) != 0:
         raise UtopianError(f"uh_{name} failed")
     return p
+
+
+def glossy_default_params():
+    """UhGlossyParams as uh_glossy_default_params fills it (needs no GPU)"""
+    return _default_params(GlossyParams, "glossy_default_params")
 
 
 def rtgi_default_params():

@@ -588,6 +588,25 @@ struct uh_ctx {
          }
       } gi;
 
+      // ray-traced glossy reflections (UH_HYBRID_GLOSSY), allocated by the first pass: the count words, the two images, the unfiltered
+      // sums, the radius bytes, the queue of the pixels that cast and the pass's counters (GlossyDev::counters); rays, orig, dirs, sun_rays
+      // (a record per ray each) and ray_queue (a word per ray) are grown to the largest `samples` a pass has run with. params: the last
+      // uh_set_glossy_params (the defaults before). stage: trace, shade, shadow, filter, composite of the last pass.
+      struct __attribute__((visibility("hidden"))) Glossy {
+         DevBuf<uint32_t> counts, queue, counters, ray_queue;
+         DevBuf<uint8_t> re;
+         DevBuf<float4> scale, bias, mean_s, mean_b, rays, orig, dirs, sun_rays;
+         UhGlossyParams params{1, 3, 0.6f, 16.0f, 1.0f, 0.5f, 0.95f, 0.05f};
+         Stage stage[5];
+         uint32_t renders = 0;
+         template <class F> void images(size_t n, F&& f) { f(counts, n), f(scale, n), f(bias, n), f(mean_s, n), f(mean_b, n), f(re, n), f(queue, n), f(counters, 8); }
+         void destroy() {
+            images(0, ReleaseBuf{});
+            rays.release(), orig.release(), dirs.release(), sun_rays.release(), ray_queue.release();
+            for (Stage& s : stage) s.destroy();
+         }
+      } gl;
+
       // motion vectors (UH_HYBRID_MOTION), allocated by the first call with the bit: the motion image, the pass's counts (pixels with /
       // without a correspondence, a pair per block of the kernel's grid, added up by uh_get_motion_stats), the per-mesh table the
       // kernels read, and the previous-position table (16-byte rows with bases of their own: isosurface meshes, which are never
@@ -662,7 +681,7 @@ struct uh_ctx {
 
       __attribute__((visibility("hidden"))) void destroy() {
          rt_images(0, ReleaseBuf{}), frame_images(0, ReleaseBuf{});
-         env.destroy(), sm.destroy(), gr.destroy(), mc.destroy(), rl.destroy(), ao.destroy(), gi.destroy(), mv.destroy(), taa.destroy(), post.destroy();
+         env.destroy(), sm.destroy(), gr.destroy(), mc.destroy(), rl.destroy(), ao.destroy(), gi.destroy(), gl.destroy(), mv.destroy(), taa.destroy(), post.destroy();
          meshes.release(), vertices.release(), indices.release(), raw_lights.release();
          for (hipEvent_t ev : waits)
             if (ev) (void)hipEventDestroy(ev);

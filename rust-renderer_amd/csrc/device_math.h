@@ -67,6 +67,13 @@ __device__ __forceinline__ V3 random_point_in_unit_sphere(uint32_t& s) {  // ran
       if (dot3(p, p) < 1.0f) return p;
    }
 }
+__device__ __forceinline__ void random_point_in_unit_disk(uint32_t& s, float& x, float& y) {  // random.glsl:48-58
+   for (;;) {
+      const float a = random_float(s), b = random_float(s);
+      x = 2.0f * a - 1.0f, y = 2.0f * b - 1.0f;
+      if (x * x + y * y < 1.0f) return;
+   }
+}
 
 // ---- include/view.glsl -------------------------------------------------------------------
 __device__ __forceinline__ float luminance(V3 c) { return dot3(c, v3(0.2126f, 0.7152f, 0.0722f)); }  // view.glsl:46-50
@@ -482,6 +489,20 @@ __device__ __forceinline__ uint32_t wave_append(uint32_t* counter, bool pred) {
 }
 
 // Wave sum (in 32 bits), then lane 0 adds it to the counter unless it is zero: one atomic per wave. Reached by all lanes of the wave.
+// Several rounds of a wave's appends with one atomic: each round keeps its ballot, wave_reserve takes the slots of all of them (n: their
+// total, wave-uniform; every lane of the wave calls it) and a lane's slot in a round is the base, plus the entries of the rounds before,
+// plus ballot_prefix of the round's ballot.
+__device__ __forceinline__ uint32_t wave_reserve(uint32_t* counter, uint32_t n) {
+   uint32_t base = 0;
+   if (n) {
+      if (lane_id() == 0) base = atomicAdd(counter, n);
+      base = __shfl(base, 0);
+   }
+   return base;
+}
+__device__ __forceinline__ uint32_t ballot_prefix(unsigned long long mask) {
+   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
 template <typename T>
 __device__ __forceinline__ void wave_add(T* counter, uint32_t x) {
    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off);

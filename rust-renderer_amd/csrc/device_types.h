@@ -314,6 +314,31 @@ struct RtgiDev {
 };
 constexpr uint32_t kRtgiSeedXor = 0x52544749u;  // keeps the rays from being the rtao pass's own
 
+// ray-traced glossy reflections of the hybrid frame (UH_HYBRID_GLOSSY; glossy.hip): what its kernels read and write. Sample s of the pixel
+// in queue slot q is ray q * samples + s in `rays`, `orig` and `dirs`; the rays that are cast (not below) are listed in `ray_queue`.
+// counts, rays, sun_rays, queue and counters[0..2] are laid out as RtgiDev's: the sun rays go through k_rtgi_shadow (glossy_sun_view)
+struct GlossyDev {
+   uint32_t* counts;               // UH_HYBRID_GLOSSY_COUNTS: a word per pixel, bytes (low first) sunlit, dark, emitter, missed; added to by words
+   float4* scale;                  // UH_HYBRID_GLOSSY_SCALE: Sf.rgb, w = 1 where the pixel cast, else (0, 0, 0, 0)
+   float4* bias;                   // UH_HYBRID_GLOSSY_BIAS: Bf.rgb, w likewise
+   float4* mean_s;                 // S.rgb and Bi.rgb of the pixels that cast (the filter's input; not written when blur_radius is 0)
+   float4* mean_b;
+   uint8_t* re;                    // the pixel's filter radius, 255 where it did not cast
+   float4* rays;                   // by ray number: the hit record (t, u, v, idx) behind the walk, (Gw L.rgb, x5) behind the shading
+   float4* orig;                   // by ray number: origin.xyz, Gw
+   float4* dirs;                   // by ray number: direction.xyz, x5
+   float4* sun_rays;               // the sun rays queued by the shading: origin.xyz, ray number (bits)
+   uint32_t* ray_queue;            // the numbers of the rays that are cast, compacted
+   uint32_t* queue;                // the pixels that cast, compacted
+   uint32_t* counters;             // [0]: entries of `queue`, [1]: entries of `sun_rays`, [2]: rays that missed, [3]: entries of `ray_queue`, [4]: below samples
+   uint32_t samples;               // UhGlossyParams::samples
+   uint32_t frame_base;            // frameNumber(view) * 64: sample s seeds its state with (frame_base + s) ^ kGlossySeedXor
+   uint32_t blur_radius;
+   uint32_t rt_on;                 // view.raytracing_supported == 1: type-1 pixels hold their mirror
+   float max_roughness, max_radiance, intensity, blur_roughness, blur_normal_cos, blur_plane;
+};
+constexpr uint32_t kGlossySeedXor = 0x474C4F53u;  // keeps the samples from being the rtao or rtgi pass's own
+
 // the denoiser (uh_denoise; denoise.hip): one frame's guides and moments as the next call's history reads them
 struct DenoiseHistory {
    float4* pos;                    // the position texel (w != 0: geometry)

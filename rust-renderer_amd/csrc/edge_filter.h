@@ -1,4 +1,4 @@
-// edge_filter.h — the edge-stopping tile filter of k_rtao_resolve<true> and k_rtgi_filter: a block is a kFilterTileW x kFilterTileH tile
+// edge_filter.h — the edge-stopping tile filter of k_rtao_resolve<true>, k_rtgi_filter and k_glossy_filter: a block is a kFilterTileW x kFilterTileH tile
 // of G-buffer pixels, one lane per pixel, tiles numbered along x first. The tile and its halo (the blur radius r <= kMaxR on every side)
 // of (P, Nn, kPlanes value planes) are staged in LDS once per block; a tap counts when it is the centre or dot(nt, nn) >= normal_cos and
 // |dot(Pt - P, nn)| <= plane. Staging and taps run dy outer, dx inner: the order of the callers' sums, which their tests hold bit for bit.
@@ -71,6 +71,56 @@ struct FilterTile {
             const int i = centre + dy * hw + dx;
             bool counts = dx == 0 && dy == 0;
             if (!counts && valid[i]) {
+               const V3 Pt = v3(rec[0][i], rec[1][i], rec[2][i]), nt = v3(rec[3][i], rec[4][i], rec[5][i]);
+               counts = dot3(nt, nn) >= normal_cos && fabsf(dot3(Pt - P, nn)) <= plane;
+            }
+            if (counts) {
+               tap(i);
+               n++;
+            }
+         }
+      }
+      return n;
+   }
+
+   // The same two for a filter with a validity rule of its own and a radius per lane (k_glossy_filter). stage: casts(g) says whether
+   // pixel g (in the frame) can be a tap - the caller's rule, which implies a position w != 0 and a finite Nn.
+   template <typename Casts, typename Value>
+   __device__ __forceinline__ FilterLane stage(const HybridDev& hd, int r, Casts&& casts, Value&& value) {
+      const FilterLane me = filter_lane(hd, r);
+      const int W = (int)hd.W, H = (int)hd.H, hw = kFilterTileW + 2 * r, hh = kFilterTileH + 2 * r;
+      for (int i = (int)threadIdx.x; i < hw * hh; i += kBlock) {
+         const int gx = me.x0 - r + i % hw, gy = me.y0 - r + i / hw;
+         bool ok = false;
+         if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+            const size_t g = (size_t)gy * W + gx;
+            ok = casts(g);
+            if (ok) {
+               const float4 P4 = hd.pos[g];
+               V3 nn;
+               rtao_normal(hd.nrm[g], nn);
+               rec[0][i] = P4.x, rec[1][i] = P4.y, rec[2][i] = P4.z;
+               rec[3][i] = nn.x, rec[4][i] = nn.y, rec[5][i] = nn.z;
+               value(g, i);
+            }
+         }
+         valid[i] = ok ? 1 : 0;
+      }
+      __syncthreads();
+      return me;
+   }
+   // taps: the tile was staged for radius r, the lane's own radius is re <= r: (dx, dy) in [-re, re]^2; a tap other than the centre
+   // also needs accept(i, max(|dx|, |dy|))
+   template <typename Accept, typename Tap>
+   __device__ __forceinline__ uint32_t taps(int centre, int r, int re, float normal_cos, float plane, Accept&& accept, Tap&& tap) const {
+      const int hw = kFilterTileW + 2 * r;
+      const V3 P = v3(rec[0][centre], rec[1][centre], rec[2][centre]), nn = v3(rec[3][centre], rec[4][centre], rec[5][centre]);
+      uint32_t n = 0;
+      for (int dy = -re; dy <= re; dy++) {
+         for (int dx = -re; dx <= re; dx++) {
+            const int i = centre + dy * hw + dx;
+            bool counts = dx == 0 && dy == 0;
+            if (!counts && valid[i] && accept(i, max(abs(dx), abs(dy)))) {
                const V3 Pt = v3(rec[0][i], rec[1][i], rec[2][i]), nt = v3(rec[3][i], rec[4][i], rec[5][i]);
                counts = dot3(nt, nn) >= normal_cos && fabsf(dot3(Pt - P, nn)) <= plane;
             }

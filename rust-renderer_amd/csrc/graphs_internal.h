@@ -103,6 +103,24 @@ template <class P, class Pass> static int set_params(uh_ctx* c, const P* params,
    return UH_OK;
 }
 
+// ---- glossy.hip ----
+// the glossy pass (UH_HYBRID_GLOSSY), a launcher per timed stage; gl.counters zeroed by the caller. trace: classify (which pixels cast;
+// their images zeroed), ray generation (the below samples are settled, the others queued) and the closest-hit walk into the hit records;
+// shade: the hit records into radiance records, the sun rays queued (k_rtgi_shadow walks them: launch_rtgi_shadow on glossy_sun_view);
+// filter: the per-pixel sums, then the filter when blur_radius is not 0; composite: into deferred_output
+namespace uh {
+void launch_glossy_trace(const LaunchCfg&, const SceneDev&, const HybridDev&, const GlossyDev&);
+void launch_glossy_shade(const LaunchCfg&, const SceneDev&, const HybridDev&, const GlossyDev&);
+void launch_glossy_filter(const LaunchCfg&, const HybridDev&, const GlossyDev&);
+void launch_glossy_composite(const LaunchCfg&, const SceneDev&, const HybridDev&, const HybridFrameDev&, const GlossyDev&);
+// this pass's buffers as k_rtgi_shadow reads them: the sun-ray records, the ray records they zero, the count words, the pixel queue
+inline RtgiDev glossy_sun_view(const GlossyDev& gl) {
+   RtgiDev gi{};
+   gi.counts = gl.counts, gi.rays = gl.rays, gi.sun_rays = gl.sun_rays, gi.queue = gl.queue, gi.counters = gl.counters, gi.samples = gl.samples;
+   return gi;
+}
+}  // namespace uh
+
 // ---- hybrid_graph.hip ----
 int hybrid_events(uh_ctx* c);          // the events of the hybrid stages and of wait_frames_in_flight (first hybrid or forward call)
 int wait_frames_in_flight(uh_ctx* c);  // c->stream (where the graphs run) waits for every other stream of the context

@@ -391,7 +391,7 @@ static int render_gbuffer_raster(uh_ctx* c, const LaunchCfg& lc, const UhViewUni
 struct HybridPlan {
    int code;
    const char* refusal;
-   bool raster, maps, render_maps, restir, rtao, rtgi, mc, motion, rt, taa, post;  // maps: the IBL maps exist for this call's consumers
+   bool raster, maps, render_maps, restir, rtao, rtgi, glossy, mc, motion, rt, taa, post;  // maps: the IBL maps exist for this call's consumers
    bool deferred, frame, env;  // the deferred pass runs; the final frame's images and the IBL maps are needed
    bool first, frame_first;    // the ray-traced images, the final frame's images are allocated by this call (and cleared)
 };
@@ -516,6 +516,26 @@ static HybridPlan hybrid_plan(const uh_ctx& c, const UhViewUniformData& view, ui
       if ((uint64_t)c.W * c.H * 16u >= (1ull << 32))
          return refuse(UH_ERR_CAPACITY, "uh_render_hybrid: UH_HYBRID_RTGI: a frame of 2^28 pixels or more (its rays are numbered in 32 bits)");
    }
+   // glossy reflections: rays drawn around the mirror direction by the pixel's roughness, shaded at their hits, added behind the rtgi pass
+   p.glossy = (mask & UH_HYBRID_GLOSSY) != 0;
+   if (p.glossy) {
+      if (view.raytracing_supported != 1)
+         return refuse(UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_GLOSSY casts rays and view.raytracing_supported is not 1; set it, or clear the bit");
+      if (!(mask & UH_HYBRID_GBUFFER) && !h.gbuffer_done)
+         return refuse(UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_GLOSSY casts its rays from the G-buffer, and no G-buffer has been rendered; set UH_HYBRID_GBUFFER");
+      if (view.ibl_enabled == 1)
+         return refuse(UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_GLOSSY with view.ibl_enabled = 1: the IBL specular term and this pass would both count the sky; "
+                     "set ibl_enabled = 0, or clear the bit");
+      if (!(mask & UH_HYBRID_DEFERRED))
+         return refuse(UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_GLOSSY without UH_HYBRID_DEFERRED in the same call: the pass adds to what the deferred pass "
+                     "writes and has nothing to add to; set UH_HYBRID_DEFERRED");
+      if ((uint64_t)c.W * c.H * 16u >= (1ull << 32))
+         return refuse(UH_ERR_CAPACITY, "uh_render_hybrid: UH_HYBRID_GLOSSY: a frame of 2^28 pixels or more (its rays are numbered in 32 bits)");
+   }
    p.rt = view.raytracing_supported != 0;
    p.deferred = (mask & UH_HYBRID_DEFERRED) != 0;
    p.frame = (mask & (UH_HYBRID_SSAO | UH_HYBRID_DEFERRED | UH_HYBRID_SKY | UH_HYBRID_PRESENT)) || p.mc || p.rtao || p.taa || p.post;
@@ -565,6 +585,22 @@ static int hybrid_prepare(uh_ctx* c, const HybridPlan& p) {
       if (gi.rays.n < rays || gi.sun_rays.n < rays) {
          HIP_TRY(c, hipStreamSynchronize(c->stream));
          for (int st : {grow(c, gi.rays, rays, "uh_render_hybrid: UH_HYBRID_RTGI"), grow(c, gi.sun_rays, rays, "uh_render_hybrid: UH_HYBRID_RTGI")})
+            if (st) return st;
+      }
+   }
+   if (p.glossy) {
+      uh_ctx::Hybrid::Glossy& gl = h.gl;
+      const char* const who = "uh_render_hybrid: UH_HYBRID_GLOSSY";
+      if (!gl.counters.p) {
+         if (int st = stage_create(c, gl.stage, 5)) return st;
+         if (int st = alloc_group(c, [&](auto f) { gl.images(pixels, f); })) return st;
+      }
+      // the per-ray buffers, as the rtgi pass keeps its own
+      const size_t rays = pixels * gl.params.samples;
+      if (gl.rays.n < rays || gl.orig.n < rays || gl.dirs.n < rays || gl.sun_rays.n < rays || gl.ray_queue.n < rays) {
+         HIP_TRY(c, hipStreamSynchronize(c->stream));
+         for (int st : {grow(c, gl.rays, rays, who), grow(c, gl.orig, rays, who), grow(c, gl.dirs, rays, who), grow(c, gl.sun_rays, rays, who),
+                        grow(c, gl.ray_queue, rays, who)})
             if (st) return st;
       }
    }
@@ -634,6 +670,8 @@ static void reset_stage_records(uh_ctx::Hybrid& h, const HybridPlan& p, uint32_t
    if (p.rtao) h.stage[kStRtaoTrace].ran = h.stage[kStRtaoFilter].ran = false;
    if (p.rtgi)
       for (Stage& s : h.gi.stage) s.ran = false;
+   if (p.glossy)
+      for (Stage& s : h.gl.stage) s.ran = false;
 }
 
 // what the passes of one call share
@@ -741,6 +779,29 @@ static int rtgi_pass(uh_ctx* c, const HybridCall& k) {
    return UH_OK;
 }
 
+// the glossy pass behind the rtgi pass (behind deferred_pass without it): classify + ray generation + the closest-hit walk into hit
+// records, the streaming shade (which queues the sun rays), the sun rays' any-hit walk (k_rtgi_shadow on this pass's buffers), the
+// per-pixel sums + filter into the two images, then the composite into deferred_output; a stage each
+static int glossy_pass(uh_ctx* c, const HybridCall& k) {
+   uh_ctx::Hybrid::Glossy& g = c->hy.gl;
+   const UhGlossyParams& p = g.params;
+   const GlossyDev gl{g.counts.p, g.scale.p, g.bias.p, g.mean_s.p, g.mean_b.p, g.re.p, g.rays.p, g.orig.p, g.dirs.p, g.sun_rays.p, g.ray_queue.p, g.queue.p,
+                      g.counters.p, p.samples, k.fp.frame_number * 64u, p.blur_radius, k.fd.rt_on, p.max_roughness, p.max_radiance, p.intensity,
+                      p.blur_roughness, p.blur_normal_cos, p.blur_plane};
+   int st = timed(c, g.stage[0], [&] {
+      HIP_TRY(c, hipMemsetAsync(g.counters.p, 0, g.counters.n * sizeof(uint32_t), c->stream));
+      launch_glossy_trace(k.lc, c->scene, k.hd, gl);
+      return (int)UH_OK;
+   });
+   if (st) return st;
+   if ((st = timed(c, g.stage[1], [&] { launch_glossy_shade(k.lc, c->scene, k.hd, gl); }))) return st;
+   if ((st = timed(c, g.stage[2], [&] { launch_rtgi_shadow(k.lc, c->scene, k.hd, glossy_sun_view(gl)); }))) return st;
+   if ((st = timed(c, g.stage[3], [&] { launch_glossy_filter(k.lc, k.hd, gl); }))) return st;
+   if ((st = timed(c, g.stage[4], [&] { launch_glossy_composite(k.lc, c->scene, k.hd, k.fd, gl); }))) return st;
+   g.renders++;
+   return UH_OK;
+}
+
 // the taa pass between atmosphere_pass and present_pass: deferred_output into the set that is not the history, which then becomes the
 // current one (the ping-pong is the host's: the kernel is enqueued with both pointers)
 static int taa_pass(uh_ctx* c, const HybridCall& k) {
@@ -775,7 +836,7 @@ static int taa_pass(uh_ctx* c, const HybridCall& k) {
 
 // The passes in the order of build_render_graph (mod.rs:91-186, graph.rs:743), each between its stage's two events: setup_shadow_pass's
 // four cascades first, rt_shadows, gbuffer, setup_cubemap_pass, rt_reflections, then the final frame - ssao_pass (not with
-// ssao_enabled != 1, ssao.rs:27; the rtao pass takes its place), deferred_pass, the rtgi pass (an extension), setup_marching_cubes_pass, atmosphere_pass, the taa pass
+// ssao_enabled != 1, ssao.rs:27; the rtao pass takes its place), deferred_pass, the rtgi pass and the glossy pass (extensions), setup_marching_cubes_pass, atmosphere_pass, the taa pass
 // (an extension; present then reads its output), the post pass (an extension; it reads the taa pass's output or deferred_output, and
 // present then reads its own), present_pass
 static int hybrid_passes(uh_ctx* c, const HybridCall& k, uint32_t mask) {
@@ -824,6 +885,7 @@ static int hybrid_passes(uh_ctx* c, const HybridCall& k, uint32_t mask) {
       if (st) return st;
    }
    if (p.rtgi && (st = rtgi_pass(c, k))) return st;
+   if (p.glossy && (st = glossy_pass(c, k))) return st;
    h.frame_lights = h.stage[kStDeferred].ran ? (p.restir ? 2 : view.num_lights + 1) : 0;  // with the reservoir lights: the sun and the reservoir's
    if (p.restir) {
       // a reservoir pass enqueued after this call starts behind the call's reads (the spatial ring comes round to the slot read here)

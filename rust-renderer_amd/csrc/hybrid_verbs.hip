@@ -1,5 +1,5 @@
 // hybrid_verbs.hip - what a caller reads from and sets on the hybrid graph between uh_render_hybrid calls (include/utopian_hip.h): the
-// images and IBL maps (uh_read_hybrid, uh_read_environment), every pass's stats, the params of the rtao, rtgi and taa passes, the
+// images and IBL maps (uh_read_hybrid, uh_read_environment), every pass's stats, the params of the rtao, rtgi, glossy and taa passes, the
 // taa history reset and jitter. Host code over uh_ctx::Hybrid (context_state.h); nothing here touches the pass order
 // (hybrid_graph.hip). The HDR display chain's verbs are in post_graph.hip.
 #include <hip/hip_runtime.h>
@@ -15,12 +15,13 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    const uh_ctx::Hybrid& h = c->hy;
    if (!h.counter.p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid before the first uh_render_hybrid");
-   if (which < 0 || which > UH_HYBRID_GI_COUNTS) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..19");
+   if (which < 0 || which > UH_HYBRID_GLOSSY_COUNTS) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..22");
    const char* const no_frame = "uh_read_hybrid: images 6..8 before the first call with an SSAO, deferred, sky or present bit";
    const char* const no_mc = "uh_read_hybrid: images 9..10 before the first marching-cubes pass";
    const char* const no_gr = "uh_read_hybrid: images 11..12 before the first rasterised G-buffer pass";
    const char* const no_taa = "uh_read_hybrid: images 16..17 before the first taa pass (UH_HYBRID_TAA)";
    const char* const no_gi = "uh_read_hybrid: images 18..19 before the first rtgi pass (UH_HYBRID_RTGI); until then the image index must be 0..17";
+   const char* const no_gl = "uh_read_hybrid: images 20..22 before the first glossy pass (UH_HYBRID_GLOSSY); until then the image index must be 0..19";
    // image k in UH_HYBRID_* image order: its pixels, its bytes per pixel, whether it exists yet and what a read before that is told
    const struct { const void* pixels; size_t bpp; bool ready; const char* refusal; } img[] = {
       {h.pos.p, sizeof(float4), true, nullptr},
@@ -42,8 +43,11 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
       {h.taa.col[h.taa.cur].p, sizeof(float4), h.taa.renders != 0, no_taa},
       {h.taa.n[h.taa.cur].p, sizeof(float), h.taa.renders != 0, no_taa},
       {h.gi.radiance.p, sizeof(float4), h.gi.renders != 0, no_gi},
-      {h.gi.counts.p, sizeof(uint32_t), h.gi.renders != 0, no_gi}};
-   static_assert(sizeof(img) / sizeof(img[0]) == UH_HYBRID_GI_COUNTS + 1, "one row per UH_HYBRID_* image");
+      {h.gi.counts.p, sizeof(uint32_t), h.gi.renders != 0, no_gi},
+      {h.gl.scale.p, sizeof(float4), h.gl.renders != 0, no_gl},
+      {h.gl.bias.p, sizeof(float4), h.gl.renders != 0, no_gl},
+      {h.gl.counts.p, sizeof(uint32_t), h.gl.renders != 0, no_gl}};
+   static_assert(sizeof(img) / sizeof(img[0]) == UH_HYBRID_GLOSSY_COUNTS + 1, "one row per UH_HYBRID_* image");
    if (!img[which].ready) return fail(c, UH_ERR_INVALID_ARGUMENT, img[which].refusal);
    return read_back(c, out, img[which].pixels, (size_t)c->W * c->H * img[which].bpp);
 }
@@ -150,6 +154,45 @@ int uh_get_rtgi_stats(uh_ctx* c, UhRtgiStats* out) {
    out->rays = (uint64_t)counters[0] * g.samples;
    out->shadow_rays = counters[1];
    out->misses = counters[2];
+   return UH_OK;
+}
+
+// ---- ray-traced glossy reflections (utopian_hip.h "UH_HYBRID_GLOSSY"; glossy.hip) ----
+int uh_glossy_default_params(UhGlossyParams* out) {
+   if (!out) return UH_ERR_INVALID_ARGUMENT;
+   *out = UhGlossyParams{1, 3, 0.6f, 16.0f, 1.0f, 0.5f, 0.95f, 0.05f};
+   return UH_OK;
+}
+
+static const char* glossy_params_refusal(const UhGlossyParams& p) {
+   if (p.samples < 1 || p.samples > 16) return "samples must be 1..16";
+   if (p.blur_radius > 6) return "blur_radius must be 0..6";
+   if (!(p.max_roughness >= 0.0f && p.max_roughness < INFINITY)) return "max_roughness must be finite and >= 0";
+   if (!(p.max_radiance > 0.0f && p.max_radiance < INFINITY)) return "max_radiance must be finite and > 0";
+   if (!(p.intensity >= 0.0f && p.intensity < INFINITY)) return "intensity must be finite and >= 0";
+   if (!(p.blur_roughness > 0.0f && p.blur_roughness < INFINITY)) return "blur_roughness must be finite and > 0";
+   if (std::isnan(p.blur_normal_cos) || std::isnan(p.blur_plane)) return "blur_normal_cos and blur_plane must not be NaN";
+   return nullptr;
+}
+
+int uh_set_glossy_params(uh_ctx* c, const UhGlossyParams* params) {
+   return set_params(c, params, "uh_set_glossy_params", glossy_params_refusal, &uh_ctx::Hybrid::gl);
+}
+
+int uh_get_glossy_stats(uh_ctx* c, UhGlossyStats* out) {
+   int st;
+   if (!stats_begin(c, out, sizeof(*out), "uh_get_glossy_stats: null destination", c && c->hy.gl.renders != 0, &st)) return st;
+   uh_ctx::Hybrid::Glossy& g = c->hy.gl;
+   float* const ms[5] = {&out->trace_ms, &out->shade_ms, &out->shadow_ms, &out->filter_ms, &out->composite_ms};
+   for (int k = 0; k < 5; k++)
+      if ((st = stage_ms(c, g.stage[k], ms[k]))) return st;
+   uint32_t counters[5] = {0, 0, 0, 0, 0};
+   HIP_TRY(c, hipMemcpy(counters, g.counters.p, sizeof(counters), hipMemcpyDeviceToHost));
+   out->pixels = counters[0];
+   out->shadow_rays = counters[1];
+   out->misses = counters[2];
+   out->rays = counters[3];
+   out->below = counters[4];
    return UH_OK;
 }
 

@@ -426,6 +426,36 @@ class RtgiStats(C.Structure):
 assert C.sizeof(RtgiStats) == 48 and RtgiStats.misses.offset == 24 and RtgiStats.trace_ms.offset == 32 and RtgiStats.composite_ms.offset == 44
 
 
+# ray-traced glossy reflections of the hybrid frame (an extension; utopian_hip.h "UH_HYBRID_GLOSSY"): the pass behind the rtgi pass and its
+# three images
+HYBRID_GLOSSY = 1 << 18
+HYBRID_GLOSSY_SCALE, HYBRID_GLOSSY_BIAS, HYBRID_GLOSSY_COUNTS = 20, 21, 22
+
+
+class GlossyParams(C.Structure):
+    """UhGlossyParams: rays per pixel that casts (1..16), the filter's largest radius (0..6), the roughness up to which a pixel casts, the
+    cap of a ray's radiance, the scale of what the composite adds, the roughness at which a pixel's radius reaches blur_radius, and a
+    tap's normal and plane thresholds; uh_glossy_default_params fills the defaults"""
+
+    _fields_ = [("samples", C.c_uint32), ("blur_radius", C.c_uint32), ("max_roughness", C.c_float), ("max_radiance", C.c_float),
+                ("intensity", C.c_float), ("blur_roughness", C.c_float), ("blur_normal_cos", C.c_float), ("blur_plane", C.c_float)]
+
+
+assert C.sizeof(GlossyParams) == 32 and [getattr(GlossyParams, n).offset for n, _ in GlossyParams._fields_] == list(range(0, 32, 4))
+
+
+class GlossyStats(C.Structure):
+    """UhGlossyStats: the last glossy pass - the pixels that cast, the rays cast, the below samples, the sun rays cast from the hits, the
+    rays that missed, hipEvent ms of classify + ray generation + closest-hit walk, of the hit shading, of the sun rays' walk, of the
+    sums + filter and of the composite"""
+
+    _fields_ = [("pixels", C.c_uint64), ("rays", C.c_uint64), ("below", C.c_uint64), ("shadow_rays", C.c_uint64), ("misses", C.c_uint64),
+                ("trace_ms", C.c_float), ("shade_ms", C.c_float), ("shadow_ms", C.c_float), ("filter_ms", C.c_float), ("composite_ms", C.c_float)]
+
+
+assert C.sizeof(GlossyStats) == 64 and GlossyStats.misses.offset == 32 and GlossyStats.trace_ms.offset == 40 and GlossyStats.composite_ms.offset == 56
+
+
 # motion vectors for moving geometry (an extension; utopian_hip.h "motion vectors"): a modifier of HYBRID_GBUFFER; bit 9 stays unused
 HYBRID_MOTION = 1 << 14
 HYBRID_MOTION_IMAGE = 15
