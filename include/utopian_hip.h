@@ -244,17 +244,18 @@ typedef struct uh_ctx uh_ctx;
  *        triangle total, 8 bytes, back to size its buffers), uh_get_isosurface_update_stats, uh_update_mesh_vertices (device input:
  *        it reads a 4-byte verdict on the caller's buffer back before it takes it), uh_get_mesh_update_stats, uh_read_denoised,
  *        uh_get_denoise_stats, uh_reset_denoise_history, uh_get_rtao_stats, uh_get_rtao_visits, uh_get_motion_stats, uh_reset_taa_history,
- *        uh_get_taa_stats, uh_post_image, uh_read_post, uh_get_post_stats, uh_get_rtgi_stats, uh_get_glossy_stats, uh_destroy;
+ *        uh_get_taa_stats, uh_post_image, uh_read_post, uh_get_post_stats, uh_get_rtgi_stats, uh_get_glossy_stats, uh_get_fog_stats,
+ *        uh_get_fog_visits, uh_destroy;
  *   enqueues like a frame, ordered behind the frames in flight and before those that follow:  uh_rccl_gather_tiles, uh_mgpu_compose;
  *        uh_set_option for "frames_in_flight" and for "time_kernels" 1 -> 0 (the others only change what the NEXT enqueued
  *        frame does: "furnace", "sun_grid*", "camera_grid*", "overlap", "batch_frames", "trace_blocks_per_cu", "count_visits",
- *        "full_frame_restir", "primary_implicit", "rtao_order", "rtgi_order"; "device_build", "ploc_sah_top" invalidate the tree: the next frame
+ *        "full_frame_restir", "primary_implicit", "rtao_order", "rtgi_order", "fog_order"; "device_build", "ploc_sah_top" invalidate the tree: the next frame
  *        needs uh_build_acceleration, which waits);
  *   host state only (no device access, nothing to wait for):  uh_add_mesh, uh_add_light, uh_set_instance_transform,
  *        uh_get_num_lights, uh_mesh_info, uh_read_mesh, uh_get_restir_rows, uh_tile_pack_count, uh_set_rtao_params, uh_set_taa_params,
- *        uh_set_post_params, uh_reset_post_exposure, uh_set_rtgi_params, uh_set_glossy_params (read by the next uh_render_hybrid; the post
+ *        uh_set_post_params, uh_reset_post_exposure, uh_set_rtgi_params, uh_set_glossy_params, uh_set_fog_params (read by the next uh_render_hybrid; the post
  *        pair also by the next uh_post_image), uh_taa_default_params, uh_taa_jitter, uh_post_default_params, uh_post_level_size,
- *        uh_rtgi_default_params, uh_glossy_default_params,
+ *        uh_rtgi_default_params, uh_glossy_default_params, uh_fog_default_params,
  *        uh_last_error
  *        (uh_read_mesh of a mesh that uh_update_isosurface_mesh has made device-resident, or that uh_update_mesh_vertices last updated
  *        from a device pointer, copies it from the device: a blocking copy);
@@ -650,7 +651,7 @@ int uh_mgpu_set_option(uh_mgpu* group, const char* name, int value);
  * UH_HYBRID_RT_REFLECTIONS with view->ibl_enabled == 1 is UH_ERR_INVALID_ARGUMENT - and nothing runs - until the IBL maps (irradiance,
  * specular, BRDF LUT of ibl.rs) have been built with UH_HYBRID_ENVIRONMENT, below; mask bits, UH_ERR_NOT_BUILT and moved instances with
  * view->rebuild_tlas as for uh_render_frame (bits above UH_HYBRID_SHADOW_MAPS, below, are ignored, except UH_HYBRID_MARCHING_CUBES,
- * UH_HYBRID_GBUFFER_RASTER, UH_HYBRID_RESTIR_LIGHTS, UH_HYBRID_RTAO, UH_HYBRID_MOTION, UH_HYBRID_TAA, UH_HYBRID_POST, UH_HYBRID_RTGI and UH_HYBRID_GLOSSY).
+ * UH_HYBRID_GBUFFER_RASTER, UH_HYBRID_RESTIR_LIGHTS, UH_HYBRID_RTAO, UH_HYBRID_MOTION, UH_HYBRID_TAA, UH_HYBRID_POST, UH_HYBRID_RTGI, UH_HYBRID_GLOSSY and UH_HYBRID_FOG).
  * STREAM ORDER: uh_render_hybrid enqueues like a frame (behind the frames in flight, ahead of those that follow); uh_read_hybrid and
  * uh_get_hybrid_stats wait for all work of the context and are complete on return. The exception is UH_HYBRID_SHADOW_MAPS, below: a
  * call that renders shadow maps BLOCKS the host until the frames in flight and the pass's binning have finished (it reads the
@@ -1537,6 +1538,84 @@ UH_LAYOUT_ASSERT(sizeof(UhGlossyStats) == 64 && offsetof(UhGlossyStats, rays) ==
 int uh_glossy_default_params(UhGlossyParams* out); /* needs no GPU: 1, 3, 0.6, 16.0, 1.0, 0.5, 0.95, 0.05; UH_ERR_INVALID_ARGUMENT for NULL */
 int uh_set_glossy_params(uh_ctx* ctx, const UhGlossyParams* params); /* validated here; a refused call leaves the old ones */
 int uh_get_glossy_stats(uh_ctx* ctx, UhGlossyStats* out);            /* waits; all zero before the first pass */
+
+/* ---- volumetric fog for the hybrid frame: a homogeneous medium with ray-traced sun shafts --------------------------------------------
+ * An EXTENSION: the reference has no participating medium. UH_HYBRID_FOG (bit 19) adds one pass to uh_render_hybrid directly AFTER the
+ * sky pass and BEFORE the taa, post and present passes, so the taa pass integrates the march jitter and the display chain sees the
+ * fogged frame. UH_HYBRID_FRAME | UH_HYBRID_FOG is the natural call. Everything float32 in the order written, nothing fused.
+ *   ray       (o, d) = the sky pass's view ray through the pixel centre. Geometry pixel (position texel w != 0): V = P - o, D0 =
+ *             sqrt(dot(V, V)); it marches when D0 is finite and > 0, with dir = V / D0 and D = min(D0, max_distance); one that does not
+ *             is left exactly as it is, its mask 0 and its terms 0. Sky pixel (w == 0): dir = d, D = max_distance; it always marches.
+ *   samples   dt = D / (float)steps; xi = randomFloat of the state initRNG(px, py, W, (frameNumber(view) * 64) ^ 0x464F4721): one jitter
+ *             per pixel per frame. Sample k is X_k = o + dir * (((float)k + xi) * dt); its ray is an any-hit ray from X_k toward the sun,
+ *             tmin 0.001, tmax 10000, no offsetRay (there is no surface). Bit k of the pixel's mask is set when the ray is not occluded.
+ *   resolve   a = expf(-(density * dt)); p = 1, sum = 0; for k = 0 .. steps - 1: if bit k: sum += p; then p = p * a. Ttot = p and
+ *             F = (1 - a) * sum: the fraction of the sun's scattered light that survives to the eye.
+ *   filter    blur_radius r == 0: Ff = F. Else the mean of F (float32 sum in tap order over the float tap count) over the taps (dx, dy)
+ *             in [-r, r]^2, dy outer: the centre, and every tap in the frame that marched with |D_tap - D| <= blur_depth * D.
+ *   phase     c = dot(sun, dir), g = anisotropy, q = (1 + g g) - (2 g) c, ph = (1 - g g) / ((4 PI) * (q * sqrt(q))), PI of brdf.glsl.
+ *   composite for every pixel that marched: C = deferred_output.rgb, S = ((albedo * rad_sun) * ph) * intensity with the sun radiance
+ *             UH_HYBRID_RTGI takes from the deferred pass's light record 0; out = (C * Ttot + S * Ff) + ambient * (1 - Ttot); alpha
+ *             untouched. Option "furnace" does not change this pass.
+ * PARAMS: uh_set_fog_params validates and keeps them (a refused call leaves the old ones); the defaults of uh_fog_default_params:
+ * 16 steps, blur_radius 2, density 0.02, max_distance 200.0, anisotropy 0.6, intensity 1.0, blur_depth 0.1, albedo (1, 1, 1), ambient
+ * (0.05, 0.06, 0.08).
+ * UH_ERR_INVALID_ARGUMENT with a message, and nothing runs, in this order after every rule above (UH_HYBRID_GLOSSY's included): the bit
+ * and view->raytracing_supported != 1; no G-buffer rendered in this call or an earlier one; the bit without both UH_HYBRID_DEFERRED and
+ * UH_HYBRID_SKY in the same call; the bit together with UH_HYBRID_MARCHING_CUBES in the same call. UH_ERR_CAPACITY for a frame of 2^26
+ * pixels or more (items are numbered in 32 bits at up to 32 per pixel). UH_ERR_NOT_BUILT before uh_build_acceleration, as without the bit.
+ * READ-BACK (uh_read_hybrid, UH_ERR_INVALID_ARGUMENT before the first fog pass; both in G-buffer orientation): UH_HYBRID_FOG_MASK, one
+ * uint32 per pixel; UH_HYBRID_FOG_TERMS, RGBA32F (a, Ttot, F, Ff), all 0 where the pixel did not march.
+ * RESOURCES: 28 bytes per pixel (the mask, the terms, the march length, the pixel queue), allocated by the first pass; freed by
+ * uh_destroy. A context that never sets the bit allocates nothing.
+ * STREAM ORDER: as uh_render_hybrid. uh_set_fog_params is host state, read by the next uh_render_hybrid; uh_get_fog_stats waits.
+ * OPTIONS: "fog_order" 0..2 (default 2) lays the trace kernel's work out (same masks whichever; DESIGN.md section 4 "Volumetric fog"); with
+ * "count_visits" the walks' node visits and triangle tests go to the pass's own counters (uh_get_fog_visits), never to UhStats.
+ * ISOLATION: the bit changes no reservoir, accumulation, grid, UhStats, RTAO, RTGI, GLOSSY, TAA-history or post state beyond what those
+ * passes make of a fogged deferred_output, and no hybrid image but deferred_output and its own two. Without the bit every pass, image,
+ * statistic and allocation is what it was.
+ * No uh_mgpu_ twin.
+ * OUT OF SCOPE: height-dependent or heterogeneous density; point, spot and reservoir lights in the medium; multiple scattering; fog in
+ * rt_reflections, RTGI or GLOSSY rays, or in uh_render_forward; the marching-cubes pass's pixels (hence the refusal); answering these
+ * rays from the path tracer's sun grid (its reach rule is stated for surface points: a follow-up with its own proof); a uh_mgpu_ twin;
+ * a history of its own (UH_HYBRID_TAA serves).
+ * Arithmetic: DESIGN.md section 2, "Volumetric fog". */
+enum { UH_HYBRID_FOG = 1u << 19 };
+enum { UH_HYBRID_FOG_MASK = 23 /* uint32 per pixel, G-buffer orientation: bit k = sample k saw the sun */,
+       UH_HYBRID_FOG_TERMS = 24 /* RGBA32F, G-buffer orientation: (a, Ttot, F, Ff), all 0 where the pixel did not march */ };
+typedef struct UhFogParams {
+   uint32_t steps;        /* samples along a pixel's view ray, 1..32 */
+   uint32_t blur_radius;  /* 0 = no filter; else 1..4: taps dx, dy in [-r, r] */
+   float density;         /* extinction per world unit; finite, >= 0 */
+   float max_distance;    /* march length of a sky pixel and the cap of a geometry pixel's; finite, > 0 */
+   float anisotropy;      /* Henyey-Greenstein g; -0.95..0.95, not NaN */
+   float intensity;       /* scales the sun's in-scattering; finite, >= 0 */
+   float blur_depth;      /* a tap counts when |D_tap - D| <= blur_depth * D; finite, >= 0 */
+   uint32_t reserved;     /* must be 0 */
+   float albedo[3];       /* single-scattering albedo per channel; each finite, 0..1 */
+   float ambient[3];      /* unshadowed fog radiance (sky light in the medium); each finite, >= 0 */
+} UhFogParams;
+UH_LAYOUT_ASSERT(sizeof(UhFogParams) == 56 && offsetof(UhFogParams, blur_radius) == 4 && offsetof(UhFogParams, density) == 8 &&
+                    offsetof(UhFogParams, max_distance) == 12 && offsetof(UhFogParams, anisotropy) == 16 &&
+                    offsetof(UhFogParams, intensity) == 20 && offsetof(UhFogParams, blur_depth) == 24 &&
+                    offsetof(UhFogParams, reserved) == 28 && offsetof(UhFogParams, albedo) == 32 && offsetof(UhFogParams, ambient) == 44,
+                 "UhFogParams (56 B)");
+/* the last fog pass: the pixels that marched, their rays (pixels * steps), the rays that reached the sun, and the hipEvent times of
+ * classify + walk, of resolve + filter and of the composite. All zero before the first pass. Waits. */
+typedef struct UhFogStats {
+   uint64_t pixels, rays, lit;
+   float trace_ms, filter_ms, composite_ms;
+   uint32_t reserved;
+} UhFogStats;
+UH_LAYOUT_ASSERT(sizeof(UhFogStats) == 40 && offsetof(UhFogStats, rays) == 8 && offsetof(UhFogStats, lit) == 16 &&
+                    offsetof(UhFogStats, trace_ms) == 24 && offsetof(UhFogStats, filter_ms) == 28 &&
+                    offsetof(UhFogStats, composite_ms) == 32 && offsetof(UhFogStats, reserved) == 36,
+                 "UhFogStats (40 B)");
+int uh_fog_default_params(UhFogParams* out); /* needs no GPU: 16, 2, 0.02, 200.0, 0.6, 1.0, 0.1, 0, (1, 1, 1), (0.05, 0.06, 0.08); UH_ERR_INVALID_ARGUMENT for NULL */
+int uh_set_fog_params(uh_ctx* ctx, const UhFogParams* params); /* validated here; a refused call leaves the old ones */
+int uh_get_fog_stats(uh_ctx* ctx, UhFogStats* out);            /* waits; all zero before the first pass */
+/* the last fog pass's node visits and triangle tests, counted while option "count_visits" is 1; else 0, 0. Waits. */
+int uh_get_fog_visits(uh_ctx* ctx, uint64_t* nodes, uint64_t* triangles);
 
 #ifdef __cplusplus
 }

@@ -329,7 +329,8 @@ class Renderer {
    // one image as bytes: W*H texels of 16 (position, normal, pbr, deferred output, the motion image of UH_HYBRID_MOTION), 4 (albedo, reflections, present output, the
    // marching-cubes and rasterised G-buffer depth floats and draw indices uint32), 2 (SSAO) or 1 (shadows, light visibility, the
    // occluded-ray counts of UH_HYBRID_RTAO) bytes; taa_output of UH_HYBRID_TAA 16, its history length 4; the radiance of UH_HYBRID_RTGI
-   // 16, its four ray counts 4; the scale and bias images of UH_HYBRID_GLOSSY 16 each, its four ray counts 4
+   // 16, its four ray counts 4; the scale and bias images of UH_HYBRID_GLOSSY 16 each, its four ray counts 4; the mask of UH_HYBRID_FOG 4, its
+   // terms 16
    std::vector<uint8_t> read_hybrid(int which) {
       const size_t texel = (which == UH_HYBRID_AO_COUNTS) ? 1
                            : (which == UH_HYBRID_SHADOWS || which == UH_HYBRID_LIGHT_VISIBILITY) ? 1
@@ -337,7 +338,7 @@ class Renderer {
                            : (which == UH_HYBRID_ALBEDO || which == UH_HYBRID_REFLECTIONS || which == UH_HYBRID_PRESENT_OUTPUT ||
                               which == UH_HYBRID_DEPTH || which == UH_HYBRID_MARCHING_CUBES_VISIBILITY || which == UH_HYBRID_GBUFFER_DEPTH ||
                               which == UH_HYBRID_GBUFFER_VISIBILITY || which == UH_HYBRID_TAA_HISTORY || which == UH_HYBRID_GI_COUNTS ||
-                              which == UH_HYBRID_GLOSSY_COUNTS) ? 4
+                              which == UH_HYBRID_GLOSSY_COUNTS || which == UH_HYBRID_FOG_MASK) ? 4
                                                                      : 16;  // (UH_HYBRID_MOTION_IMAGE and UH_HYBRID_TAA_OUTPUT among them)
       static_assert(UH_HYBRID_MOTION_IMAGE == 15, "read_hybrid sizes image 15 as 16-byte texels");
       std::vector<uint8_t> out((size_t)width_ * height_ * texel);
@@ -411,6 +412,24 @@ class Renderer {
       UhGlossyStats s;
       check(uh_get_glossy_stats(ctx_, &s), "glossy_stats");
       return s;
+   }
+   // volumetric fog behind the sky pass of render_hybrid (UH_HYBRID_FOG; utopian_hip.h): the params of the calls that follow, the last
+   // pass's pixels, rays, lit rays and times, and with option "count_visits" its walks' node visits and triangle tests
+   static UhFogParams default_fog_params() {
+      UhFogParams p;
+      if (uh_fog_default_params(&p) != UH_OK) throw Error(UH_ERR_INVALID_ARGUMENT, "uh_fog_default_params");
+      return p;
+   }
+   void set_fog_params(const UhFogParams& params) { check(uh_set_fog_params(ctx_, &params), "set_fog_params"); }
+   UhFogStats fog_stats() {
+      UhFogStats s;
+      check(uh_get_fog_stats(ctx_, &s), "fog_stats");
+      return s;
+   }
+   std::pair<uint64_t, uint64_t> fog_visits() {
+      uint64_t nodes = 0, tris = 0;
+      check(uh_get_fog_visits(ctx_, &nodes, &tris), "fog_visits");
+      return {nodes, tris};
    }
    // motion vectors (UH_HYBRID_GBUFFER | UH_HYBRID_MOTION; utopian_hip.h "motion vectors"): the last motion pass's pixels with and
    // without a correspondence, its meshes per state, and the times of the motion kernel and of the snapshot behind it

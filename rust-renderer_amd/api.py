@@ -41,6 +41,8 @@ from .types import (
     HYBRID_AO_COUNTS,
     HYBRID_GI_COUNTS,
     HYBRID_GI_RADIANCE,
+    HYBRID_FOG_MASK,
+    HYBRID_FOG_TERMS,
     HYBRID_GLOSSY_BIAS,
     HYBRID_GLOSSY_COUNTS,
     HYBRID_GLOSSY_SCALE,
@@ -93,6 +95,8 @@ from .types import (
     RtaoStats,
     RtgiParams,
     RtgiStats,
+    FogParams,
+    FogStats,
     GlossyParams,
     GlossyStats,
     Stats,
@@ -183,6 +187,10 @@ _LIBRARY_VERBS = {
     "glossy_default_params": [_p(GlossyParams)],
     "set_glossy_params": [_vp, _p(GlossyParams)],
     "get_glossy_stats": [_vp, _p(GlossyStats)],
+    "fog_default_params": [_p(FogParams)],
+    "set_fog_params": [_vp, _p(FogParams)],
+    "get_fog_stats": [_vp, _p(FogStats)],
+    "get_fog_visits": [_vp, _p(_u64), _p(_u64)],
     "get_motion_stats": [_vp, _p(MotionStats)],
     "taa_default_params": [_p(TaaParams)],
     "set_taa_params": [_vp, _p(TaaParams)],
@@ -651,6 +659,8 @@ class Renderer:
     _GI_IMAGES = {HYBRID_GI_RADIANCE: (np.float32, 4), HYBRID_GI_COUNTS: (np.uint8, 4)}
     # the three images of HYBRID_GLOSSY: the library refuses them before the first glossy pass
     _GLOSSY_IMAGES = {HYBRID_GLOSSY_SCALE: (np.float32, 4), HYBRID_GLOSSY_BIAS: (np.float32, 4), HYBRID_GLOSSY_COUNTS: (np.uint8, 4)}
+    # the two images of HYBRID_FOG: the library refuses them before the first fog pass
+    _FOG_IMAGES = {HYBRID_FOG_MASK: (np.uint32, 1), HYBRID_FOG_TERMS: (np.float32, 4)}
 
     def read_hybrid(self, which):
         """one image of the hybrid graph: (H, W, 4) float32 position / normal / pbr / deferred output, (H, W, 4) uint8 albedo / reflections /
@@ -661,10 +671,12 @@ class Renderer:
         with a correspondence), once a call with HYBRID_TAA has run (H, W, 4) float32 taa_output and (H, W) float32 history length, and of
         HYBRID_RTGI (H, W, 4) float32 filtered incoming radiance (w = 1 where the pixel cast) and (H, W, 4) uint8 ray counts (sunlit, dark,
         emitter, missed), and of HYBRID_GLOSSY (H, W, 4) float32 filtered scale and bias sums (w = 1 where the pixel cast) and (H, W, 4) uint8
-        ray counts (sunlit, dark, emitter, missed)"""
-        images = {**self._HYBRID_IMAGES, **(self._TAA_IMAGES if self._taa_rendered else {}), **self._GI_IMAGES, **self._GLOSSY_IMAGES}
+        ray counts (sunlit, dark, emitter, missed), and of HYBRID_FOG (H, W) uint32 masks (bit k: sample k saw the sun) and (H, W, 4) float32
+        terms (a, Ttot, F, Ff; all 0 where the pixel did not march)"""
+        images = {**self._HYBRID_IMAGES, **(self._TAA_IMAGES if self._taa_rendered else {}), **self._GI_IMAGES, **self._GLOSSY_IMAGES,
+                  **self._FOG_IMAGES}
         return self._read_image(images, self._hybrid_api().read_hybrid, which,
-                                f"hybrid image index {which} (0..15, 18..22, and 16..17 once a render_hybrid call with HYBRID_TAA has run)")
+                                f"hybrid image index {which} (0..15, 18..24, and 16..17 once a render_hybrid call with HYBRID_TAA has run)")
 
     def hybrid_stats(self):
         return self._stats(HybridStats, self._hybrid_api().get_hybrid_stats)
@@ -738,6 +750,25 @@ class Renderer:
     def glossy_stats(self):
         """UhGlossyStats of the last glossy pass: pixels, rays, below, shadow_rays, misses, trace_ms, shade_ms, shadow_ms, filter_ms, composite_ms"""
         return self._stats(GlossyStats, self._hip_only(self._GLOSSY, "get_glossy_stats"))
+
+    # -- volumetric fog (HYBRID_FOG; include/utopian_hip.h "UH_HYBRID_FOG") ---
+    _FOG = "volumetric fog is a per-context verb"
+
+    def set_fog_params(self, params=None, **fields):
+        """uh_set_fog_params: `params` (a FogParams; the defaults when None) with `fields` set on a copy - the params of the
+        render_hybrid calls with HYBRID_FOG that follow. A refused call raises and leaves the old ones."""
+        return self._set_params(FogParams, self._hip_only(self._FOG, "set_fog_params"), fog_default_params, params, fields)
+
+    def fog_stats(self):
+        """UhFogStats of the last fog pass: pixels, rays, lit, trace_ms, filter_ms, composite_ms"""
+        return self._stats(FogStats, self._hip_only(self._FOG, "get_fog_stats"))
+
+    def fog_visits(self):
+        """(node visits, triangle tests) of the last fog pass's walks, counted while option "count_visits" is 1; else (0, 0)"""
+        fn = self._hip_only(self._FOG, "get_fog_visits")
+        nodes, tris = C.c_uint64(), C.c_uint64()
+        self._check(fn(self._ctx, C.byref(nodes), C.byref(tris)))
+        return nodes.value, tris.value
 
     def rtao_visits(self):
         """(node visits, triangle tests) of the last rtao pass's walks, counted while option "count_visits" is 1; else (0, 0)"""
@@ -1079,6 +1110,11 @@ def _default_params(Struct, name):
     if _bind(load_library(), "uh_", name)(C.byref(p)) != 0:
         raise UtopianError(f"uh_{name} failed")
     return p
+
+
+def fog_default_params():
+    """UhFogParams as uh_fog_default_params fills it (needs no GPU)"""
+    return _default_params(FogParams, "fog_default_params")
 
 
 def glossy_default_params():

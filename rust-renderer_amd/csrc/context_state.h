@@ -607,6 +607,24 @@ struct uh_ctx {
          }
       } gl;
 
+      // volumetric fog (UH_HYBRID_FOG), allocated by the first pass: the mask words, the terms image, the march lengths, the queue of
+      // the pixels that march and the pass's counters (FogDev::counters). params: the last uh_set_fog_params (the defaults before);
+      // steps: the last pass's. stage: trace, resolve, composite of the last pass.
+      struct __attribute__((visibility("hidden"))) Fog {
+         DevBuf<uint32_t> mask, queue, counters;
+         DevBuf<float4> terms;
+         DevBuf<float> dist;
+         UhFogParams params{16, 2, 0.02f, 200.0f, 0.6f, 1.0f, 0.1f, 0, {1.0f, 1.0f, 1.0f}, {0.05f, 0.06f, 0.08f}};
+         Stage stage[3];
+         uint32_t renders = 0, steps = 0;
+         uint32_t order = 2;                   // option "fog_order" (fog.hip: how the trace kernel's work items are laid out; 2 measured fastest)
+         template <class F> void images(size_t n, F&& f) { f(mask, n), f(terms, n), f(dist, n), f(queue, n), f(counters, 6); }
+         void destroy() {
+            images(0, ReleaseBuf{});
+            for (Stage& s : stage) s.destroy();
+         }
+      } fog;
+
       // motion vectors (UH_HYBRID_MOTION), allocated by the first call with the bit: the motion image, the pass's counts (pixels with /
       // without a correspondence, a pair per block of the kernel's grid, added up by uh_get_motion_stats), the per-mesh table the
       // kernels read, and the previous-position table (16-byte rows with bases of their own: isosurface meshes, which are never
@@ -681,7 +699,7 @@ struct uh_ctx {
 
       __attribute__((visibility("hidden"))) void destroy() {
          rt_images(0, ReleaseBuf{}), frame_images(0, ReleaseBuf{});
-         env.destroy(), sm.destroy(), gr.destroy(), mc.destroy(), rl.destroy(), ao.destroy(), gi.destroy(), gl.destroy(), mv.destroy(), taa.destroy(), post.destroy();
+         env.destroy(), sm.destroy(), gr.destroy(), mc.destroy(), rl.destroy(), ao.destroy(), gi.destroy(), gl.destroy(), fog.destroy(), mv.destroy(), taa.destroy(), post.destroy();
          meshes.release(), vertices.release(), indices.release(), raw_lights.release();
          for (hipEvent_t ev : waits)
             if (ev) (void)hipEventDestroy(ev);

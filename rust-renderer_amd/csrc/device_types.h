@@ -339,6 +339,21 @@ struct GlossyDev {
 };
 constexpr uint32_t kGlossySeedXor = 0x474C4F53u;  // keeps the samples from being the rtao or rtgi pass's own
 
+// volumetric fog of the hybrid frame (UH_HYBRID_FOG; fog.hip): what its kernels read and write
+struct FogDev {
+   uint32_t* mask;                 // UH_HYBRID_FOG_MASK: a word per pixel, bit k = sample k saw the sun; 0 where the pixel did not march
+   float4* terms;                  // UH_HYBRID_FOG_TERMS: (a, Ttot, F, Ff), all 0 where the pixel did not march
+   float* dist;                    // the march length D of a pixel that marched (classify writes it); 0 where it did not
+   uint32_t* queue;                // the pixels that march, compacted
+   uint32_t* counters;             // [0]: entries of `queue`, [1]: lit rays; with count_visits [2..3]: node visits, [4..5]: triangle tests (64 bits each)
+   uint32_t steps;                 // UhFogParams::steps
+   uint32_t frame_seed;            // (frameNumber(view) * 64) ^ kFogSeedXor: the state of a pixel's one jitter xi
+   uint32_t blur_radius;
+   float density, max_distance, anisotropy, intensity, blur_depth;
+   float albedo[3], ambient[3];
+};
+constexpr uint32_t kFogSeedXor = 0x464F4721u;  // keeps the jitter from being another pass's sample
+
 // the denoiser (uh_denoise; denoise.hip): one frame's guides and moments as the next call's history reads them
 struct DenoiseHistory {
    float4* pos;                    // the position texel (w != 0: geometry)
@@ -537,6 +552,14 @@ void launch_rtgi_trace(const LaunchCfg&, const SceneDev&, const HybridDev&, cons
 void launch_rtgi_shadow(const LaunchCfg&, const SceneDev&, const HybridDev&, const RtgiDev&);
 void launch_rtgi_filter(const LaunchCfg&, const HybridDev&, const RtgiDev&);
 void launch_rtgi_composite(const LaunchCfg&, const SceneDev&, const HybridDev&, const HybridFrameDev&, const RtgiDev&);
+// the fog pass (fog.hip), a launcher per timed stage; fg.counters zeroed by the caller. trace: classify (which pixels march; their march
+// length written, their mask zeroed) and the any-hit walk of their samples' sun rays into the masks (order: 0 a pixel's samples are
+// consecutive items, 1 one sample of consecutive queued pixels, 2 an item is a pixel whose lane walks its samples one after the other);
+// LaunchCfg::count_visits: the walks' visits go to fg.counters too. resolve: (a, Ttot, F, Ff) from the masks, Ff through the tile filter
+// when blur_radius > 0; composite: deferred_output.rgb of every pixel that marched
+void launch_fog_trace(const LaunchCfg&, const FrameParams&, const SceneDev&, const HybridDev&, const FogDev&, uint32_t order);
+void launch_fog_resolve(const LaunchCfg&, const HybridDev&, const FogDev&);
+void launch_fog_composite(const LaunchCfg&, const FrameParams&, const HybridDev&, const HybridFrameDev&, const FogDev&);
 // the taa pass (taa.hip): one lane per pixel; fp gives the frame, the matrices of primary_ray and prev_pv; t.counters zeroed by the caller
 void launch_hybrid_taa(const LaunchCfg&, const FrameParams&, const TaaDev&);
 // the three stages of the post pass (post.hip). meter: the histogram (with auto_exposure) and the exposure record; bloom: down[1..levels]

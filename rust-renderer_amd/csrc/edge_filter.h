@@ -1,4 +1,4 @@
-// edge_filter.h — the edge-stopping tile filter of k_rtao_resolve<true>, k_rtgi_filter and k_glossy_filter: a block is a kFilterTileW x kFilterTileH tile
+// edge_filter.h — the edge-stopping tile filter of k_rtao_resolve<true>, k_rtgi_filter, k_glossy_filter and k_fog_resolve<true>: a block is a kFilterTileW x kFilterTileH tile
 // of G-buffer pixels, one lane per pixel, tiles numbered along x first. The tile and its halo (the blur radius r <= kMaxR on every side)
 // of (P, Nn, kPlanes value planes) are staged in LDS once per block; a tap counts when it is the centre or dot(nt, nn) >= normal_cos and
 // |dot(Pt - P, nn)| <= plane. Staging and taps run dy outer, dx inner: the order of the callers' sums, which their tests hold bit for bit.
@@ -84,7 +84,8 @@ struct FilterTile {
    }
 
    // The same two for a filter with a validity rule of its own and a radius per lane (k_glossy_filter). stage: casts(g) says whether
-   // pixel g (in the frame) can be a tap - the caller's rule, which implies a position w != 0 and a finite Nn.
+   // pixel g (in the frame) can be a tap - the caller's rule, which implies a position w != 0 and a finite Nn wherever the P and Nn planes
+   // are read (taps); a filter that reads its value planes alone (taps_depth) may admit any pixel.
    template <typename Casts, typename Value>
    __device__ __forceinline__ FilterLane stage(const HybridDev& hd, int r, Casts&& casts, Value&& value) {
       const FilterLane me = filter_lane(hd, r);
@@ -125,6 +126,25 @@ struct FilterTile {
                counts = dot3(nt, nn) >= normal_cos && fabsf(dot3(Pt - P, nn)) <= plane;
             }
             if (counts) {
+               tap(i);
+               n++;
+            }
+         }
+      }
+      return n;
+   }
+   // taps of a filter whose edge stop is a depth alone (k_fog_resolve: its records are staged by the stage above with a rule that admits
+   // sky pixels, whose P and Nn planes are then not read): (dx, dy) in [-r, r]^2; a tap other than the centre needs a valid record and
+   // |depth[i] - depth[centre]| <= rel * depth[centre], `depth` being one of the value planes
+   template <typename Tap>
+   __device__ __forceinline__ uint32_t taps_depth(int centre, int r, const float* depth, float rel, Tap&& tap) const {
+      const int hw = kFilterTileW + 2 * r;
+      const float D = depth[centre], bound = rel * D;
+      uint32_t n = 0;
+      for (int dy = -r; dy <= r; dy++) {
+         for (int dx = -r; dx <= r; dx++) {
+            const int i = centre + dy * hw + dx;
+            if ((dx == 0 && dy == 0) || (valid[i] && fabsf(depth[i] - D) <= bound)) {
                tap(i);
                n++;
             }

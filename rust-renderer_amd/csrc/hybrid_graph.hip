@@ -391,7 +391,7 @@ static int render_gbuffer_raster(uh_ctx* c, const LaunchCfg& lc, const UhViewUni
 struct HybridPlan {
    int code;
    const char* refusal;
-   bool raster, maps, render_maps, restir, rtao, rtgi, glossy, mc, motion, rt, taa, post;  // maps: the IBL maps exist for this call's consumers
+   bool raster, maps, render_maps, restir, rtao, rtgi, glossy, fog, mc, motion, rt, taa, post;  // maps: the IBL maps exist for this call's consumers
    bool deferred, frame, env;  // the deferred pass runs; the final frame's images and the IBL maps are needed
    bool first, frame_first;    // the ray-traced images, the final frame's images are allocated by this call (and cleared)
 };
@@ -536,6 +536,26 @@ static HybridPlan hybrid_plan(const uh_ctx& c, const UhViewUniformData& view, ui
       if ((uint64_t)c.W * c.H * 16u >= (1ull << 32))
          return refuse(UH_ERR_CAPACITY, "uh_render_hybrid: UH_HYBRID_GLOSSY: a frame of 2^28 pixels or more (its rays are numbered in 32 bits)");
    }
+   // volumetric fog: sun rays from samples along every pixel's view ray, composited behind the sky pass
+   p.fog = (mask & UH_HYBRID_FOG) != 0;
+   if (p.fog) {
+      if (view.raytracing_supported != 1)
+         return refuse(UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_FOG casts sun rays and view.raytracing_supported is not 1; set it, or clear the bit");
+      if (!(mask & UH_HYBRID_GBUFFER) && !h.gbuffer_done)
+         return refuse(UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_FOG marches to the G-buffer's positions, and no G-buffer has been rendered; set UH_HYBRID_GBUFFER");
+      if (!(mask & UH_HYBRID_DEFERRED) || !(mask & UH_HYBRID_SKY))
+         return refuse(UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_FOG without UH_HYBRID_DEFERRED and UH_HYBRID_SKY in the same call: the pass attenuates what "
+                     "those two write and has nothing to attenuate; set both");
+      if (mask & UH_HYBRID_MARCHING_CUBES)
+         return refuse(UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_FOG with UH_HYBRID_MARCHING_CUBES in the same call: the marching-cubes pass's pixels are not "
+                     "in the G-buffer the fog marches to; clear one of the two bits");
+      if ((uint64_t)c.W * c.H * 64u >= (1ull << 32))
+         return refuse(UH_ERR_CAPACITY, "uh_render_hybrid: UH_HYBRID_FOG: a frame of 2^26 pixels or more (its rays are numbered in 32 bits)");
+   }
    p.rt = view.raytracing_supported != 0;
    p.deferred = (mask & UH_HYBRID_DEFERRED) != 0;
    p.frame = (mask & (UH_HYBRID_SSAO | UH_HYBRID_DEFERRED | UH_HYBRID_SKY | UH_HYBRID_PRESENT)) || p.mc || p.rtao || p.taa || p.post;
@@ -603,6 +623,10 @@ static int hybrid_prepare(uh_ctx* c, const HybridPlan& p) {
                         grow(c, gl.ray_queue, rays, who)})
             if (st) return st;
       }
+   }
+   if (p.fog && !h.fog.counters.p) {
+      if (int st = stage_create(c, h.fog.stage, 3)) return st;
+      if (int st = alloc_group(c, [&](auto f) { h.fog.images(pixels, f); })) return st;
    }
    if (p.env)
       if (int st = env_alloc(c)) return st;
@@ -672,6 +696,8 @@ static void reset_stage_records(uh_ctx::Hybrid& h, const HybridPlan& p, uint32_t
       for (Stage& s : h.gi.stage) s.ran = false;
    if (p.glossy)
       for (Stage& s : h.gl.stage) s.ran = false;
+   if (p.fog)
+      for (Stage& s : h.fog.stage) s.ran = false;
 }
 
 // what the passes of one call share
@@ -802,6 +828,29 @@ static int glossy_pass(uh_ctx* c, const HybridCall& k) {
    return UH_OK;
 }
 
+// the fog pass behind atmosphere_pass: classify + the any-hit walk of the samples' sun rays into the bit masks, the resolve / filter into
+// the terms image, then the composite into deferred_output; a stage each
+static int fog_pass(uh_ctx* c, const HybridCall& k) {
+   uh_ctx::Hybrid::Fog& g = c->hy.fog;
+   const UhFogParams& p = g.params;
+   const FogDev fg{g.mask.p, g.terms.p, g.dist.p, g.queue.p, g.counters.p, p.steps, (k.fp.frame_number * 64u) ^ kFogSeedXor, p.blur_radius,
+                   p.density, p.max_distance, p.anisotropy, p.intensity, p.blur_depth, {p.albedo[0], p.albedo[1], p.albedo[2]},
+                   {p.ambient[0], p.ambient[1], p.ambient[2]}};
+   int st = timed(c, g.stage[0], [&] {
+      HIP_TRY(c, hipMemsetAsync(g.counters.p, 0, g.counters.n * sizeof(uint32_t), c->stream));
+      LaunchCfg fc = k.lc;
+      fc.count_visits = c->count_visits;  // into the pass's own counters, never UhStats
+      launch_fog_trace(fc, k.fp, c->scene, k.hd, fg, g.order);
+      return (int)UH_OK;
+   });
+   if (st) return st;
+   if ((st = timed(c, g.stage[1], [&] { launch_fog_resolve(k.lc, k.hd, fg); }))) return st;
+   if ((st = timed(c, g.stage[2], [&] { launch_fog_composite(k.lc, k.fp, k.hd, k.fd, fg); }))) return st;
+   g.steps = p.steps;
+   g.renders++;
+   return UH_OK;
+}
+
 // the taa pass between atmosphere_pass and present_pass: deferred_output into the set that is not the history, which then becomes the
 // current one (the ping-pong is the host's: the kernel is enqueued with both pointers)
 static int taa_pass(uh_ctx* c, const HybridCall& k) {
@@ -836,7 +885,8 @@ static int taa_pass(uh_ctx* c, const HybridCall& k) {
 
 // The passes in the order of build_render_graph (mod.rs:91-186, graph.rs:743), each between its stage's two events: setup_shadow_pass's
 // four cascades first, rt_shadows, gbuffer, setup_cubemap_pass, rt_reflections, then the final frame - ssao_pass (not with
-// ssao_enabled != 1, ssao.rs:27; the rtao pass takes its place), deferred_pass, the rtgi pass and the glossy pass (extensions), setup_marching_cubes_pass, atmosphere_pass, the taa pass
+// ssao_enabled != 1, ssao.rs:27; the rtao pass takes its place), deferred_pass, the rtgi pass and the glossy pass (extensions), setup_marching_cubes_pass, atmosphere_pass, the fog pass (an
+// extension; it attenuates and in-scatters into what the deferred and sky passes wrote), the taa pass
 // (an extension; present then reads its output), the post pass (an extension; it reads the taa pass's output or deferred_output, and
 // present then reads its own), present_pass
 static int hybrid_passes(uh_ctx* c, const HybridCall& k, uint32_t mask) {
@@ -901,6 +951,7 @@ static int hybrid_passes(uh_ctx* c, const HybridCall& k, uint32_t mask) {
       });
       if (st) return st;
    }
+   if (p.fog && (st = fog_pass(c, k))) return st;
    if (p.taa && (st = taa_pass(c, k))) return st;
    HybridFrameDev pd = fd;  // present's source: taa_output when the taa pass ran in this call
    if (p.taa) pd.deferred = h.taa.col[h.taa.cur].p;

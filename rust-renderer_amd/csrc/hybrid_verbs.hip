@@ -1,5 +1,5 @@
 // hybrid_verbs.hip - what a caller reads from and sets on the hybrid graph between uh_render_hybrid calls (include/utopian_hip.h): the
-// images and IBL maps (uh_read_hybrid, uh_read_environment), every pass's stats, the params of the rtao, rtgi, glossy and taa passes, the
+// images and IBL maps (uh_read_hybrid, uh_read_environment), every pass's stats, the params of the rtao, rtgi, glossy, fog and taa passes, the
 // taa history reset and jitter. Host code over uh_ctx::Hybrid (context_state.h); nothing here touches the pass order
 // (hybrid_graph.hip). The HDR display chain's verbs are in post_graph.hip.
 #include <hip/hip_runtime.h>
@@ -15,13 +15,14 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    const uh_ctx::Hybrid& h = c->hy;
    if (!h.counter.p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid before the first uh_render_hybrid");
-   if (which < 0 || which > UH_HYBRID_GLOSSY_COUNTS) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..22");
+   if (which < 0 || which > UH_HYBRID_FOG_TERMS) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..24");
    const char* const no_frame = "uh_read_hybrid: images 6..8 before the first call with an SSAO, deferred, sky or present bit";
    const char* const no_mc = "uh_read_hybrid: images 9..10 before the first marching-cubes pass";
    const char* const no_gr = "uh_read_hybrid: images 11..12 before the first rasterised G-buffer pass";
    const char* const no_taa = "uh_read_hybrid: images 16..17 before the first taa pass (UH_HYBRID_TAA)";
    const char* const no_gi = "uh_read_hybrid: images 18..19 before the first rtgi pass (UH_HYBRID_RTGI); until then the image index must be 0..17";
    const char* const no_gl = "uh_read_hybrid: images 20..22 before the first glossy pass (UH_HYBRID_GLOSSY); until then the image index must be 0..19";
+   const char* const no_fog = "uh_read_hybrid: images 23..24 before the first fog pass (UH_HYBRID_FOG); until then the image index must be 0..22";
    // image k in UH_HYBRID_* image order: its pixels, its bytes per pixel, whether it exists yet and what a read before that is told
    const struct { const void* pixels; size_t bpp; bool ready; const char* refusal; } img[] = {
       {h.pos.p, sizeof(float4), true, nullptr},
@@ -46,8 +47,10 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
       {h.gi.counts.p, sizeof(uint32_t), h.gi.renders != 0, no_gi},
       {h.gl.scale.p, sizeof(float4), h.gl.renders != 0, no_gl},
       {h.gl.bias.p, sizeof(float4), h.gl.renders != 0, no_gl},
-      {h.gl.counts.p, sizeof(uint32_t), h.gl.renders != 0, no_gl}};
-   static_assert(sizeof(img) / sizeof(img[0]) == UH_HYBRID_GLOSSY_COUNTS + 1, "one row per UH_HYBRID_* image");
+      {h.gl.counts.p, sizeof(uint32_t), h.gl.renders != 0, no_gl},
+      {h.fog.mask.p, sizeof(uint32_t), h.fog.renders != 0, no_fog},
+      {h.fog.terms.p, sizeof(float4), h.fog.renders != 0, no_fog}};
+   static_assert(sizeof(img) / sizeof(img[0]) == UH_HYBRID_FOG_TERMS + 1, "one row per UH_HYBRID_* image");
    if (!img[which].ready) return fail(c, UH_ERR_INVALID_ARGUMENT, img[which].refusal);
    return read_back(c, out, img[which].pixels, (size_t)c->W * c->H * img[which].bpp);
 }
@@ -193,6 +196,59 @@ int uh_get_glossy_stats(uh_ctx* c, UhGlossyStats* out) {
    out->misses = counters[2];
    out->rays = counters[3];
    out->below = counters[4];
+   return UH_OK;
+}
+
+// ---- volumetric fog (utopian_hip.h "UH_HYBRID_FOG"; fog.hip) ----
+int uh_fog_default_params(UhFogParams* out) {
+   if (!out) return UH_ERR_INVALID_ARGUMENT;
+   *out = UhFogParams{16, 2, 0.02f, 200.0f, 0.6f, 1.0f, 0.1f, 0, {1.0f, 1.0f, 1.0f}, {0.05f, 0.06f, 0.08f}};
+   return UH_OK;
+}
+
+static const char* fog_params_refusal(const UhFogParams& p) {
+   if (p.steps < 1 || p.steps > 32) return "steps must be 1..32";
+   if (p.blur_radius > 4) return "blur_radius must be 0..4";
+   if (!(p.density >= 0.0f && p.density < INFINITY)) return "density must be finite and >= 0";
+   if (!(p.max_distance > 0.0f && p.max_distance < INFINITY)) return "max_distance must be finite and > 0";
+   if (!(p.anisotropy >= -0.95f && p.anisotropy <= 0.95f)) return "anisotropy must be -0.95..0.95";
+   if (!(p.intensity >= 0.0f && p.intensity < INFINITY)) return "intensity must be finite and >= 0";
+   if (!(p.blur_depth >= 0.0f && p.blur_depth < INFINITY)) return "blur_depth must be finite and >= 0";
+   if (p.reserved != 0) return "reserved must be 0";
+   for (float a : p.albedo)
+      if (!(a >= 0.0f && a <= 1.0f)) return "albedo must be 0..1 in every channel";
+   for (float a : p.ambient)
+      if (!(a >= 0.0f && a < INFINITY)) return "ambient must be finite and >= 0 in every channel";
+   return nullptr;
+}
+
+int uh_set_fog_params(uh_ctx* c, const UhFogParams* params) {
+   return set_params(c, params, "uh_set_fog_params", fog_params_refusal, &uh_ctx::Hybrid::fog);
+}
+
+int uh_get_fog_stats(uh_ctx* c, UhFogStats* out) {
+   int st;
+   if (!stats_begin(c, out, sizeof(*out), "uh_get_fog_stats: null destination", c && c->hy.fog.renders != 0, &st)) return st;
+   uh_ctx::Hybrid::Fog& g = c->hy.fog;
+   float* const ms[3] = {&out->trace_ms, &out->filter_ms, &out->composite_ms};
+   for (int k = 0; k < 3; k++)
+      if ((st = stage_ms(c, g.stage[k], ms[k]))) return st;
+   uint32_t counters[2] = {0, 0};
+   HIP_TRY(c, hipMemcpy(counters, g.counters.p, sizeof(counters), hipMemcpyDeviceToHost));
+   out->pixels = counters[0];
+   out->rays = (uint64_t)counters[0] * g.steps;
+   out->lit = counters[1];
+   return UH_OK;
+}
+
+int uh_get_fog_visits(uh_ctx* c, uint64_t* nodes, uint64_t* triangles) {
+   int st;
+   if (c && nodes && triangles) *triangles = 0;  // (*nodes: by stats_begin)
+   if (!stats_begin(c, nodes && triangles ? nodes : nullptr, sizeof(*nodes), "uh_get_fog_visits: null destination", c && c->hy.fog.renders != 0, &st)) return st;
+   uint64_t visits[2] = {0, 0};
+   HIP_TRY(c, hipMemcpy(visits, c->hy.fog.counters.p + 2, sizeof(visits), hipMemcpyDeviceToHost));
+   *nodes = visits[0];
+   *triangles = visits[1];
    return UH_OK;
 }
 

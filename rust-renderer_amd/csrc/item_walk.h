@@ -1,5 +1,5 @@
 // item_walk.h — the persistent "item walk" the hybrid frame's ray passes share (k_hybrid_shadow, k_hybrid_restir_trace, k_rtao_trace,
-// k_rtgi_trace, k_rtgi_shadow): persistent waves with the LDS refill of traversal.h whose pool carries item numbers alone - items
+// k_rtgi_trace, k_rtgi_shadow, k_glossy_trace, k_fog_trace): persistent waves with the LDS refill of traversal.h whose pool carries item numbers alone - items
 // 0..count or queue[0..count), in static chunks - and the lane that takes an item makes its ray there. The kernels keep their loops:
 //    __shared__ ItemWalkLds s_walk;
 //    Trav t;

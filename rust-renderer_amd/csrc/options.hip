@@ -123,6 +123,13 @@ int uh_set_option(uh_ctx* c, const char* name, int value) {
       if (!range(0, 1)) return bad("must be 0 or 1");
       c->hy.gi.order = (uint32_t)value;
    }
+   else if (n == "fog_order") {
+      // how the fog trace kernel lays out its work (fog.hip; same masks whichever): 0 one sample per item, a pixel's samples together;
+      // 1 one sample per item, one sample index of consecutive pixels together; 2 (default, measured fastest) one pixel per item, its
+      // lane walks the samples
+      if (!range(0, 2)) return bad("must be 0..2");
+      c->hy.fog.order = (uint32_t)value;
+   }
    else if (n == "texture_blocks")
       // 1: the textures added from now on are stored as overlapped blocks, a bilinear footprint in one cache line (texture_layout.h);
       // 0: as 8x8 tiles, or rows. Same images bit for bit: the same four texel words enter the filter

@@ -456,6 +456,36 @@ class GlossyStats(C.Structure):
 assert C.sizeof(GlossyStats) == 64 and GlossyStats.misses.offset == 32 and GlossyStats.trace_ms.offset == 40 and GlossyStats.composite_ms.offset == 56
 
 
+# volumetric fog of the hybrid frame (an extension; utopian_hip.h "UH_HYBRID_FOG"): the pass behind the sky pass and its two images
+HYBRID_FOG = 1 << 19
+HYBRID_FOG_MASK, HYBRID_FOG_TERMS = 23, 24
+
+
+class FogParams(C.Structure):
+    """UhFogParams: samples along a pixel's view ray (1..32), the filter's radius (0..4), the extinction per world unit, the march length
+    of a sky pixel and cap of a geometry pixel's, the Henyey-Greenstein g, the scale of the sun's in-scattering, the filter's relative
+    depth threshold, a reserved word (0), the single-scattering albedo and the unshadowed fog radiance; uh_fog_default_params fills the
+    defaults"""
+
+    _fields_ = [("steps", C.c_uint32), ("blur_radius", C.c_uint32), ("density", C.c_float), ("max_distance", C.c_float),
+                ("anisotropy", C.c_float), ("intensity", C.c_float), ("blur_depth", C.c_float), ("reserved", C.c_uint32),
+                ("albedo", C.c_float * 3), ("ambient", C.c_float * 3)]
+
+
+assert C.sizeof(FogParams) == 56 and [getattr(FogParams, n).offset for n, _ in FogParams._fields_] == [0, 4, 8, 12, 16, 20, 24, 28, 32, 44]
+
+
+class FogStats(C.Structure):
+    """UhFogStats: the last fog pass - the pixels that marched, their rays (pixels * steps), the rays that reached the sun, hipEvent ms of
+    classify + walk, of resolve + filter and of the composite"""
+
+    _fields_ = [("pixels", C.c_uint64), ("rays", C.c_uint64), ("lit", C.c_uint64),
+                ("trace_ms", C.c_float), ("filter_ms", C.c_float), ("composite_ms", C.c_float), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(FogStats) == 40 and FogStats.lit.offset == 16 and FogStats.trace_ms.offset == 24 and FogStats.reserved.offset == 36
+
+
 # motion vectors for moving geometry (an extension; utopian_hip.h "motion vectors"): a modifier of HYBRID_GBUFFER; bit 9 stays unused
 HYBRID_MOTION = 1 << 14
 HYBRID_MOTION_IMAGE = 15
