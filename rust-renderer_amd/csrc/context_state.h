@@ -1,5 +1,5 @@
 // context_state.h - struct uh_ctx and the types it is made of, for the files that implement the context: context.hip (lifetime,
-// the path tracer, read-backs), options.hip (uh_set_option), partition.hip (the tile and band partitions of a multi-GPU frame, the
+// read-backs, stats), frame_loop.hip (the path tracer's frames), options.hip (uh_set_option), partition.hip (the tile and band partitions of a multi-GPU frame, the
 // tile composition), rccl_link.hip (the RCCL link), scene_build.hip (meshes, builders, refit) and the graphs (raster_driver.hip,
 // hybrid_graph.hip, hybrid_verbs.hip, post_graph.hip, forward_graph.hip, denoise_graph.hip; what they share: graphs_internal.h). Private: not installed, not part of
 // the C ABI (include/utopian_hip.h), where uh_ctx stays opaque. The upkeep of the sun and camera grids is grid_cache.hip.
@@ -168,7 +168,7 @@ struct Slot {
    // second stream: shade_miss (pure VALU, touches only paths that left the scene) and the shadow
    // traversals overlap the main stream's shade_hit / next closest-hit traversal
    hipStream_t side = nullptr;
-   hipEvent_t ev_traced = nullptr, ev_missed = nullptr, ev_shaded = nullptr, ev_shadowed = nullptr, ev_side_done = nullptr;
+   hipEvent_t ev_shaded = nullptr, ev_shadowed = nullptr, ev_side_done = nullptr;
    hipEvent_t ev_acc = nullptr;  // recorded after the frame's accumulate / store tail
    hipEvent_t frame_start = nullptr, frame_stop = nullptr;
    DevBuf<float4> rec, radf, pixcol;  // rec: two sets of four path-state planes + the hit plane (device_types.h PathState)
@@ -188,7 +188,7 @@ struct Slot {
    if ((e = (expr)) != hipSuccess) return e
       SLOT_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
       SLOT_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-      for (hipEvent_t* ev : {&ev_traced, &ev_missed, &ev_shaded, &ev_shadowed, &ev_side_done, &ev_acc}) SLOT_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+      for (hipEvent_t* ev : {&ev_shaded, &ev_shadowed, &ev_side_done, &ev_acc}) SLOT_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
       SLOT_TRY(hipEventCreate(&frame_start));
       SLOT_TRY(hipEventCreate(&frame_stop));
       const size_t stagger = kPlaneStaggerBytes;  // 4 KiB + 256 B per array slot
@@ -228,7 +228,7 @@ struct Slot {
       for (auto& q : queues) q.release();
       sun_lit.release();
       control.release();
-      for (hipEvent_t* ev : {&ev_traced, &ev_missed, &ev_shaded, &ev_shadowed, &ev_side_done, &ev_acc, &frame_start, &frame_stop}) {
+      for (hipEvent_t* ev : {&ev_shaded, &ev_shadowed, &ev_side_done, &ev_acc, &frame_start, &frame_stop}) {
          if (*ev) (void)hipEventDestroy(*ev);
          *ev = nullptr;  // (a create() that fails half-way must not leave handles for the next destroy())
       }
@@ -277,9 +277,8 @@ struct SunGridExtras {
    void release() { d_recs.release(), d_coarse.release(); }
 };
 
-// frames of the reservoir passes one uh_render_frames wavefront carries at most, and the ring of spatial buffers that
-// lets the next batch's chains run beside the current wavefront (two batches + the history slot)
-constexpr uint32_t kRestirBatch = 16;
+// the ring of spatial buffers that lets the next batch's reservoir chains (at most kRestirBatch frames, frame_plan.h) run beside
+// the current wavefront (two batches + the history slot)
 constexpr int kSpatialRing = 2 * (int)kRestirBatch + 1;
 
 struct RcclLink;  // rccl_link.hip
@@ -290,7 +289,6 @@ struct uh_ctx {
    uint32_t frames_in_flight = 4;     // slots used round-robin by path-tracing frames (swept: profiles/README.md)
    uint32_t batch_frames = 0;         // frames one uh_render_frames launch chain carries (option "batch_frames"); 0 = auto
    uint32_t next_slot = 0;
-   uint32_t shard_cap = 0;
    hipEvent_t last_acc = nullptr;     // ev_acc of the most recent frame (accumulation order)
    // G-buffer cast + reservoir passes run in call order on their own stream, beside path-tracing frames in flight.
    // spatial_reuse_reservoirs is a RING of kSpatialRing buffers: the path tracer of frame f reads slot `spatial_cur` while
@@ -316,10 +314,7 @@ struct uh_ctx {
    size_t res_stride = 0;  // reservoirs per spatial_reuse buffer: the frame, padded to bands.world equal bands
    hipEvent_t ev_band[kSpatialRing] = {};  // "this context's band of ring slot k is written" (in-process groups pull on it)
    hipEvent_t t_start = nullptr, t_stop = nullptr;  // bracket of the last uh_render_frame call (last_frame_ms)
-   Slot* last_slot = nullptr;
    hipStream_t& stream = slots[0].stream;  // slot 0 also serves every non-frame operation
-   PathState& ps = slots[0].ps;
-   DevBuf<Control>& control = slots[0].control;
    bool overlap_miss = true, overlap_shadow = true;
    uint32_t W = 0, H = 0;
    uint32_t num_cus = 256;
@@ -329,11 +324,10 @@ struct uh_ctx {
    uint32_t closest_blocks_per_cu = 5, shadow_blocks_per_cu = 5;  // (config 2, whose light shadow rays are a third of the frame: 6/5, 5/5, 5/4, 6/4 = 8,230 / 8,266 / 7,997 / 7,950 Mrays/s)
    uint32_t cam_walk_whole = 512;     // option "camera_grid_walk_whole" (sun_grid.h SunGridDev::walk_whole)
    // one frame per call: bounces 1 .. of a lone frame inside one persistent kernel (k_path_fused) instead of four launches per bounce
+   // (when: frame_plan.h plan_sample, with kFusedMaxPaths and the lone frame's kSingleFrameBlocksPerCu)
    bool fused_bounces = true;  // option "fused_bounces"
    bool fused_always = false;  // fused_bounces = -1: also with frames in flight and for frames of any size (tests)
-   static constexpr uint32_t kFusedMaxPaths = 4u << 20;
    uint32_t fused_blocks_per_cu = 4;
-   static constexpr uint32_t kSingleFrameBlocksPerCu = 4;  // the cap on both for a wavefront of one frame (fewer persistent waves reach the end of a small launch's tail sooner: round 4's sweep)
    bool texture_blocks = true;  // option "texture_blocks": how uh_add_texture_rgba8 lays the next textures out
    std::string err;
 
@@ -759,17 +753,21 @@ int fail(uh_ctx* c, int code, const std::string& msg);  // sets uh_last_error (c
                                         std::string(#expr) + ": " + hipGetErrorString(e_));                 \
    } while (0)
 LaunchCfg cfg(uh_ctx* c);
-FrameParams make_params(uh_ctx* c, const UhViewUniformData& v);
-int sync_all(uh_ctx* c);
+// option "time_kernels": the launches between the two are timed as `kind` (EventPair::kind) on `stream` (null: the context's)
+void begin_timed(uh_ctx* c, int kind, hipStream_t stream = nullptr);
+void end_timed(uh_ctx* c, hipStream_t stream = nullptr);
 void drain_timed(uh_ctx* c);  // the pending kernel timings (option "time_kernels") into ms_by_kind; waits for their events
 int read_back(uh_ctx* c, void* dst, const void* src, size_t bytes);
 // paths this rank traces per frame: path ids are dense over the pixels it owns
 inline uint32_t traced_pixels(const uh_ctx* c) { return c->tiles.world > 1 ? c->tiles.n_owned : c->W * c->H; }
-// ---- partition.hip, for context.hip and rccl_link.hip ----
+// ---- frame_loop.hip ----
+FrameParams make_params(uh_ctx* c, const UhViewUniformData& v);
+int sync_all(uh_ctx* c);  // every stream of every slot idle (read-backs, scene rebuilds, stats)
+// ---- partition.hip, for frame_loop.hip and rccl_link.hip ----
 void restir_rows(const uh_ctx* c, UhRestirRows& r);  // rows of this context's reservoir passes (uh_get_restir_rows)
 uint64_t max_pack_pixels(uh_ctx* c);                 // the largest uh_tile_pack_count over the ranks: rank 0's
 int mark_composed(uh_ctx* c);                        // records tiles.ev_compose on the context's stream; it becomes last_acc
-// ---- grid_cache.hip, for context.hip ----
+// ---- grid_cache.hip, for frame_loop.hip and uh_get_stats ----
 // the sun grid for this frame's direction / the camera grid for this call's camera, if there is (or now should be) one: this_frame
 int ensure_sun_grid(uh_ctx* c, const float dir[3]);
 int ensure_camera_grid(uh_ctx* c, const FrameParams& fp, uint32_t batch);

@@ -1,4 +1,4 @@
-// device_types.h — structs passed between the host context (context.hip) and the kernels
+// device_types.h — structs passed between the host context (context.hip, frame_loop.hip) and the kernels
 // (kernels.hip and the other kernel files). Device pointers only; everything here is plain data.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "bvh.h"
+#include "frame_plan.h"
 #include "path_layout.h"
 #include "post_levels.h"
 #include "sun_grid.h"
@@ -104,8 +105,6 @@ struct SceneDev {
    uint32_t num_nodes, num_tris, num_meshes, num_textures, num_lights;
 };
 
-constexpr uint32_t kMaxBatchFrames = 32;
-
 struct FrameParams {
    // A launch chain may carry `batch_frames` consecutive frames of the path-tracing pass as one
    // wavefront: path id = f * (W*H) + pixel. Frames differ only in their RNG frame number and in
@@ -114,7 +113,7 @@ struct FrameParams {
    uint32_t batch_frames;
    uint32_t frame_numbers[kMaxBatchFrames];
    uint32_t total_samples_of[kMaxBatchFrames];
-   // spatial_reuse_reservoirs of each frame of the batch (rgen:98; a ring in the context: context.hip render_batch)
+   // spatial_reuse_reservoirs of each frame of the batch (rgen:98; a ring in the context: frame_loop.hip render_batch)
    const UhReservoir* spatial_of[kMaxBatchFrames];
    float inv_view[16], inv_proj[16], prev_pv[16];
    float sun_dir[3];  // normalize(view.sun_dir), computed on the host with the contract's normalize
@@ -125,11 +124,11 @@ struct FrameParams {
    // k_generate only fills the ray queue with path ids, and every kernel of bounce 0 computes a path's origin, direction,
    // throughput (1) and RNG words from its id (device_math.h primary_state): 48 bytes less written and 96 less read per path
    uint32_t primary_implicit;
-   // option "sun_verdicts" (set per sample pass where the launches are chosen, context.hip enqueue_path_trace): 1 = the sun kernels of
+   // option "sun_verdicts" (set per sample pass where the launches are chosen, frame_plan.h plan_sample): 1 = the sun kernels of
    // this pass leave one verdict bit per ray in PathState::sun_lit and the kernels that read a path's radiance next add its throughput
    // there; 0 = the sun kernels add it themselves (lights enabled, no grid for the bounce, the fused kernel's frames, the option off)
    uint32_t sun_verdicts;
-   // option "slim_state" (set per sample pass beside sun_verdicts, context.hip enqueue_path_trace: sun_verdicts == 1 and one sample per
+   // option "slim_state" (set per sample pass beside sun_verdicts, frame_plan.h plan_sample: sun_verdicts == 1 and one sample per
    // frame): 1 = the pass carries the slim path state (PathState below) - the path id rides with the origin, no id queue is written
    // or read behind bounce 0, throughput and radiance are 24 bytes in 24, and the sun kernels of the last bounce store every surviving
    // path's final radiance (radf[id]) themselves, so k_flush_survivors is not launched; 0 = the four-quad state, the id queues, the flush

@@ -131,7 +131,7 @@ static void add_tri(std::vector<float>& pk, F3 a, F3 b, F3 c) {
 }
 
 static F3 normalised(F3 v) {
-   // the host's normalize(view.sun_dir): v * (1 / sqrt(dot)) in float (context.hip make_params)
+   // the host's normalize(view.sun_dir): v * (1 / sqrt(dot)) in float (frame_loop.hip make_params)
    float d = (v.x * v.x + v.y * v.y) + v.z * v.z;
    float inv = 1.0f / std::sqrt(d);
    return F3{v.x * inv, v.y * inv, v.z * inv};

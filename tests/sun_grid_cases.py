@@ -20,7 +20,7 @@ ALL_SUNS = tuple(SUN)
 
 
 def unit(sun):
-    """the direction as the frame normalises it (context.hip make_params: float32, v * (1 / sqrt(dot)))"""
+    """the direction as the frame normalises it (frame_loop.hip make_params: float32, v * (1 / sqrt(dot)))"""
     v = np.float32(sun)
     d = np.float32(np.float32(v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
     return v * np.float32(np.float32(1.0) / np.sqrt(d, dtype=np.float32))

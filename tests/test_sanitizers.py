@@ -60,6 +60,23 @@ def test_grid_rebuild_policy_under_asan_ubsan(tmp_path):
     assert "GRID CACHE CHECK OK" in r.stdout and "FAIL" not in r.stdout
 
 
+def test_frame_plan_under_asan_ubsan(tmp_path):
+    """csrc/frame_plan.h (product code: what one sample pass of the path tracer is made of, how many frames a wavefront carries, how a
+    call's frames are split - what csrc/frame_loop.hip enqueues follows it) under ASan + UBSan: the plan over the cross product of its
+    inputs against its rules written a second way, the batch sizes of the sizes the benchmark runs, the even split of 1..100 frames
+    (tests/cpp/frame_plan_check.cpp)."""
+    exe = str(tmp_path / "frame_plan_check")
+    csrc = os.path.join(ROOT, "rust-renderer_amd", "csrc")
+    subprocess.run(
+        ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-Wall", "-Wextra", "-I", csrc,
+         "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "frame_plan_check.cpp"), "-o", exe],
+        check=True,
+    )
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert "FRAME PLAN CHECK OK" in r.stdout and "FAIL" not in r.stdout
+
+
 def test_camera_grid_builder_under_asan_ubsan_against_brute_force(tmp_path):
     """csrc/camera_grid.h (product code: the host + device functions the camera grid's kernels run per packet and per cell) under
     ASan + UBSan: for twelve cameras - inside, above, two centimetres above a floor, IN its plane, far outside, narrow and wide fields
