@@ -245,7 +245,7 @@ typedef struct uh_ctx uh_ctx;
  *        it reads a 4-byte verdict on the caller's buffer back before it takes it), uh_get_mesh_update_stats, uh_read_denoised,
  *        uh_get_denoise_stats, uh_reset_denoise_history, uh_get_rtao_stats, uh_get_rtao_visits, uh_get_motion_stats, uh_reset_taa_history,
  *        uh_get_taa_stats, uh_post_image, uh_read_post, uh_get_post_stats, uh_get_rtgi_stats, uh_get_glossy_stats, uh_get_fog_stats,
- *        uh_get_fog_visits, uh_destroy;
+ *        uh_get_fog_visits, uh_get_glass_stats, uh_destroy;
  *   enqueues like a frame, ordered behind the frames in flight and before those that follow:  uh_rccl_gather_tiles, uh_mgpu_compose;
  *        uh_set_option for "frames_in_flight" and for "time_kernels" 1 -> 0 (the others only change what the NEXT enqueued
  *        frame does: "furnace", "sun_grid*", "camera_grid*", "overlap", "batch_frames", "trace_blocks_per_cu", "count_visits",
@@ -253,9 +253,9 @@ typedef struct uh_ctx uh_ctx;
  *        needs uh_build_acceleration, which waits);
  *   host state only (no device access, nothing to wait for):  uh_add_mesh, uh_add_light, uh_set_instance_transform,
  *        uh_get_num_lights, uh_mesh_info, uh_read_mesh, uh_get_restir_rows, uh_tile_pack_count, uh_set_rtao_params, uh_set_taa_params,
- *        uh_set_post_params, uh_reset_post_exposure, uh_set_rtgi_params, uh_set_glossy_params, uh_set_fog_params (read by the next uh_render_hybrid; the post
+ *        uh_set_post_params, uh_reset_post_exposure, uh_set_rtgi_params, uh_set_glossy_params, uh_set_fog_params, uh_set_glass_params (read by the next uh_render_hybrid; the post
  *        pair also by the next uh_post_image), uh_taa_default_params, uh_taa_jitter, uh_post_default_params, uh_post_level_size,
- *        uh_rtgi_default_params, uh_glossy_default_params, uh_fog_default_params,
+ *        uh_rtgi_default_params, uh_glossy_default_params, uh_fog_default_params, uh_glass_default_params,
  *        uh_last_error
  *        (uh_read_mesh of a mesh that uh_update_isosurface_mesh has made device-resident, or that uh_update_mesh_vertices last updated
  *        from a device pointer, copies it from the device: a blocking copy);
@@ -651,7 +651,7 @@ int uh_mgpu_set_option(uh_mgpu* group, const char* name, int value);
  * UH_HYBRID_RT_REFLECTIONS with view->ibl_enabled == 1 is UH_ERR_INVALID_ARGUMENT - and nothing runs - until the IBL maps (irradiance,
  * specular, BRDF LUT of ibl.rs) have been built with UH_HYBRID_ENVIRONMENT, below; mask bits, UH_ERR_NOT_BUILT and moved instances with
  * view->rebuild_tlas as for uh_render_frame (bits above UH_HYBRID_SHADOW_MAPS, below, are ignored, except UH_HYBRID_MARCHING_CUBES,
- * UH_HYBRID_GBUFFER_RASTER, UH_HYBRID_RESTIR_LIGHTS, UH_HYBRID_RTAO, UH_HYBRID_MOTION, UH_HYBRID_TAA, UH_HYBRID_POST, UH_HYBRID_RTGI, UH_HYBRID_GLOSSY and UH_HYBRID_FOG).
+ * UH_HYBRID_GBUFFER_RASTER, UH_HYBRID_RESTIR_LIGHTS, UH_HYBRID_RTAO, UH_HYBRID_MOTION, UH_HYBRID_TAA, UH_HYBRID_POST, UH_HYBRID_RTGI, UH_HYBRID_GLOSSY, UH_HYBRID_FOG and UH_HYBRID_GLASS).
  * STREAM ORDER: uh_render_hybrid enqueues like a frame (behind the frames in flight, ahead of those that follow); uh_read_hybrid and
  * uh_get_hybrid_stats wait for all work of the context and are complete on return. The exception is UH_HYBRID_SHADOW_MAPS, below: a
  * call that renders shadow maps BLOCKS the host until the frames in flight and the pass's binning have finished (it reads the
@@ -1616,6 +1616,78 @@ int uh_set_fog_params(uh_ctx* ctx, const UhFogParams* params); /* validated here
 int uh_get_fog_stats(uh_ctx* ctx, UhFogStats* out);            /* waits; all zero before the first pass */
 /* the last fog pass's node visits and triangle tests, counted while option "count_visits" is 1; else 0, 0. Waits. */
 int uh_get_fog_visits(uh_ctx* ctx, uint64_t* nodes, uint64_t* triangles);
+
+/* ---- ray-traced glass for the hybrid frame: dielectric pixels show what lies behind and before them -----------------------------------
+ * The reference's path tracer renders material type 2 (dielectric) as glass; its hybrid frame shades it as an opaque Cook-Torrance solid.
+ * UH_HYBRID_GLASS (bit 20) adds one pass to uh_render_hybrid directly AFTER the glossy pass (after the rtgi pass, or the deferred pass,
+ * when those bits are clear) and BEFORE the marching-cubes, sky, fog, taa and post passes. For every G-buffer pixel whose material is of
+ * type 2 it follows two deterministic chains of rays - one reflected, one transmitted at the visible surface - and REPLACES
+ * deferred_output.rgb: whatever the deferred, reservoir-light, rtgi and glossy passes wrote on that pixel is overwritten; alpha is
+ * untouched. The pass draws no random numbers. Everything float32 in the order written, nothing fused.
+ *   event     Event(nd, N, ior) is reference.rchit:62-79 without the draw: dnd = dot(nd, N); outward = dnd > 0 ? -N : N; ratio =
+ *             dnd > 0 ? ior : 1 / ior; cos = min(dot(-nd, outward), 1); sin = sqrt(1 - cos cos); cannot = ratio sin > 1; Fr =
+ *             schlick(cos, ratio); R = reflect(nd, outward); T = refract(nd, outward, ratio). N has already been turned toward the ray
+ *             (rchit:35-37), so dnd <= 0 and the ratio is 1 / ior on the way OUT of the glass as well as on the way in. That is the
+ *             reference's behaviour, the path tracer reproduces it, and this pass shows the glass the path tracer shows - not textbook Snell.
+ *   pixels    RTGI's rule first: position texel w != 0 and Nn = normalize(N) finite. The material index uint(pbr.a) is in range and its
+ *             type is 2 (out of range counts as type 0). I = normalize(P - eye) is finite.
+ *   first     Nf = dot(Nn, I) > 0 ? -Nn : Nn; Event(I, Nf, raytrace_properties.y). Chain 0 (reflected): direction R, weight w0 =
+ *             cannot ? 1 : Fr. Chain 1 (transmitted): direction T, weight w1 = 1 - Fr; with `cannot` it is NOT cast: an all-zero record,
+ *             counted dark, flag bit 0. Both start at offsetRay(P, Nf), tmin 0.001, tmax 10000, closest hit; events = 1.
+ *   segment   its end: a miss takes the sky as UH_HYBRID_RTGI does ((1, 1, 1) under "furnace"), counted missed. Type 3: (1, 1, 1), counted
+ *             emitter. Type 2 with events == max_events: the chain is CUT, L = 0, counted dark, its cut flag set; else Nh = the hit's
+ *             world normal turned toward the ray, Event(normalize(d), Nh, the mesh's ior), d' = cannot ? R : T (unnormalised, rgen:61);
+ *             d' not finite or of length 0 cuts the chain as well; else the next segment starts at offsetRay(o + t d, Nh) with
+ *             events + 1. Any other type: UH_HYBRID_RTGI's shadowed-sun-lit Lambert (dark under "furnace"), one any-hit sun ray.
+ *             L is clamped per channel with this pass's max_radiance; the chain's record is w L; an occluded sun ray zeroes it.
+ *   pixel     C = clamp(R_0 + R_1) per channel (NaN, negative and -0 become +0, then the cap); deferred_output.rgb = C * intensity.
+ * PARAMS: uh_set_glass_params validates and keeps them (a refused call leaves the old ones); the defaults of uh_glass_default_params:
+ * max_events 8, max_radiance 16.0, intensity 1.0.
+ * UH_ERR_INVALID_ARGUMENT with a message, and nothing runs, in this order after every rule above: the bit and
+ * view->raytracing_supported != 1; no G-buffer rendered in this call or an earlier one; the bit without UH_HYBRID_DEFERRED in the same
+ * call. UH_ERR_CAPACITY for a frame of 2^27 pixels or more. UH_ERR_NOT_BUILT before uh_build_acceleration, as without the bit.
+ * READ-BACK (uh_read_hybrid, UH_ERR_INVALID_ARGUMENT before the first glass pass; all three in G-buffer orientation):
+ * UH_HYBRID_GLASS_RADIANCE, RGBA32F: (C, 1) where the pixel cast, (0, 0, 0, 0) elsewhere. UH_HYBRID_GLASS_COUNTS, 4 bytes per pixel:
+ * sunlit, dark, emitter, missed; they sum to 2 where the pixel cast. UH_HYBRID_GLASS_EVENTS, 4 bytes per pixel: the events of chain 0,
+ * the events of chain 1 (0 when it was not cast), the flags (bit 0: first-event TIR, bit 1: chain 0 cut, bit 2: chain 1 cut), 0.
+ * RESOURCES: 28 bytes per pixel (counts, the radiance image, the events words, the pixel queue) and 72 bytes per ray (its hit record,
+ * which becomes its radiance record, its origin and direction, its sun-ray record, a word in each of the two round queues), two rays per
+ * pixel: 172 bytes per pixel of the frame, allocated by the first pass; freed by uh_destroy. A context that never sets the bit
+ * allocates nothing. The pass enqueues max_events rounds of walk and bend whose counts stay on the device: no read-back, no wait.
+ * STREAM ORDER: as uh_render_hybrid. uh_set_glass_params is host state, read by the next uh_render_hybrid; uh_get_glass_stats waits.
+ * ISOLATION: the bit changes no reservoir, accumulation, gbuffer_position, grid, UhStats, RTAO, RTGI, glossy or fog state, and no hybrid
+ * image but deferred_output (and what later passes of the call make of it) and its own three. Without the bit every pass, image,
+ * statistic and allocation is what it was.
+ * No uh_mgpu_ twin.
+ * OUT OF SCOPE: a Fresnel split behind the first event; absorption or tint (the reference's glass is vec3(1)); rough transmission; point,
+ * spot and reservoir lights at the hit; fog inside chains; the marching-cubes mesh in chains; the forward graph; teaching the rtgi or
+ * glossy pass to skip glass pixels.
+ * Arithmetic: DESIGN.md section 2, "Ray-traced glass". */
+enum { UH_HYBRID_GLASS = 1u << 20 };
+enum { UH_HYBRID_GLASS_RADIANCE = 25 /* RGBA32F: (C, 1) where the pixel cast */, UH_HYBRID_GLASS_COUNTS = 26 /* 4 x uint8: sunlit, dark, emitter, missed */,
+       UH_HYBRID_GLASS_EVENTS = 27 /* 4 x uint8: events of chain 0, of chain 1, flags, 0 */ };
+typedef struct UhGlassParams {
+   uint32_t max_events; /* the events of a chain, the first included, 1..16: a chain that meets glass with this many behind it is cut */
+   float max_radiance;  /* the cap of a chain's L, and of C, per channel; finite, > 0 */
+   float intensity;     /* scales what the composite writes; finite, >= 0 */
+} UhGlassParams;
+UH_LAYOUT_ASSERT(sizeof(UhGlassParams) == 12 && offsetof(UhGlassParams, max_radiance) == 4 && offsetof(UhGlassParams, intensity) == 8, "UhGlassParams (12 B)");
+/* the last glass pass: the pixels that cast; the chains cast (chains + the first-event TIR pixels == 2 * pixels); the segments walked
+ * (segments == chains + events); the events behind the first; every event, the first included, at which `cannot` held; the chains cut;
+ * the sun rays cast from the ends; the chains that missed; and the hipEvent times of classify + first event + the rounds' closest-hit
+ * walks, of the rounds' bend kernels, of the sun rays' any-hit walk and of the composite. All zero before the first pass. Waits. */
+typedef struct UhGlassStats {
+   uint64_t pixels, chains, segments, events, tir, cut, shadow_rays, misses;
+   float trace_ms, bend_ms, shadow_ms, composite_ms;
+} UhGlassStats;
+UH_LAYOUT_ASSERT(sizeof(UhGlassStats) == 80 && offsetof(UhGlassStats, chains) == 8 && offsetof(UhGlassStats, segments) == 16 &&
+                    offsetof(UhGlassStats, events) == 24 && offsetof(UhGlassStats, tir) == 32 && offsetof(UhGlassStats, cut) == 40 &&
+                    offsetof(UhGlassStats, shadow_rays) == 48 && offsetof(UhGlassStats, misses) == 56 && offsetof(UhGlassStats, trace_ms) == 64 &&
+                    offsetof(UhGlassStats, bend_ms) == 68 && offsetof(UhGlassStats, shadow_ms) == 72 && offsetof(UhGlassStats, composite_ms) == 76,
+                 "UhGlassStats (80 B)");
+int uh_glass_default_params(UhGlassParams* out); /* needs no GPU: 8, 16.0, 1.0; UH_ERR_INVALID_ARGUMENT for NULL */
+int uh_set_glass_params(uh_ctx* ctx, const UhGlassParams* params); /* validated here; a refused call leaves the old ones */
+int uh_get_glass_stats(uh_ctx* ctx, UhGlassStats* out);            /* waits; all zero before the first pass */
 
 #ifdef __cplusplus
 }

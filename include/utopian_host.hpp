@@ -338,7 +338,8 @@ class Renderer {
                            : (which == UH_HYBRID_ALBEDO || which == UH_HYBRID_REFLECTIONS || which == UH_HYBRID_PRESENT_OUTPUT ||
                               which == UH_HYBRID_DEPTH || which == UH_HYBRID_MARCHING_CUBES_VISIBILITY || which == UH_HYBRID_GBUFFER_DEPTH ||
                               which == UH_HYBRID_GBUFFER_VISIBILITY || which == UH_HYBRID_TAA_HISTORY || which == UH_HYBRID_GI_COUNTS ||
-                              which == UH_HYBRID_GLOSSY_COUNTS || which == UH_HYBRID_FOG_MASK) ? 4
+                              which == UH_HYBRID_GLOSSY_COUNTS || which == UH_HYBRID_FOG_MASK || which == UH_HYBRID_GLASS_COUNTS ||
+                              which == UH_HYBRID_GLASS_EVENTS) ? 4
                                                                      : 16;  // (UH_HYBRID_MOTION_IMAGE and UH_HYBRID_TAA_OUTPUT among them)
       static_assert(UH_HYBRID_MOTION_IMAGE == 15, "read_hybrid sizes image 15 as 16-byte texels");
       std::vector<uint8_t> out((size_t)width_ * height_ * texel);
@@ -411,6 +412,20 @@ class Renderer {
    UhGlossyStats glossy_stats() {
       UhGlossyStats s;
       check(uh_get_glossy_stats(ctx_, &s), "glossy_stats");
+      return s;
+   }
+   // ray-traced glass behind the glossy pass of render_hybrid (UH_HYBRID_GLASS; utopian_hip.h): the params of the calls that follow, and the
+   // last pass's pixels, chains, segments, events, TIR events, cut chains, sun rays, misses and times; its images through read_hybrid: the
+   // radiance 16 bytes a texel, the counts and the events 4 each
+   static UhGlassParams default_glass_params() {
+      UhGlassParams p;
+      if (uh_glass_default_params(&p) != UH_OK) throw Error(UH_ERR_INVALID_ARGUMENT, "uh_glass_default_params");
+      return p;
+   }
+   void set_glass_params(const UhGlassParams& params) { check(uh_set_glass_params(ctx_, &params), "set_glass_params"); }
+   UhGlassStats glass_stats() {
+      UhGlassStats s;
+      check(uh_get_glass_stats(ctx_, &s), "glass_stats");
       return s;
    }
    // volumetric fog behind the sky pass of render_hybrid (UH_HYBRID_FOG; utopian_hip.h): the params of the calls that follow, the last

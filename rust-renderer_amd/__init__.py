@@ -10,6 +10,7 @@ from .api import (  # noqa: F401
     default_denoise_params,
     default_view,
     fog_default_params,
+    glass_default_params,
     glossy_default_params,
     hip_versions,
     identity3x4,

@@ -42,6 +42,10 @@ from .types import (
     HYBRID_GI_COUNTS,
     HYBRID_GI_RADIANCE,
     HYBRID_FOG_MASK,
+    HYBRID_GLASS,
+    HYBRID_GLASS_COUNTS,
+    HYBRID_GLASS_EVENTS,
+    HYBRID_GLASS_RADIANCE,
     HYBRID_FOG_TERMS,
     HYBRID_GLOSSY_BIAS,
     HYBRID_GLOSSY_COUNTS,
@@ -97,6 +101,8 @@ from .types import (
     RtgiStats,
     FogParams,
     FogStats,
+    GlassParams,
+    GlassStats,
     GlossyParams,
     GlossyStats,
     Stats,
@@ -191,6 +197,9 @@ _LIBRARY_VERBS = {
     "set_fog_params": [_vp, _p(FogParams)],
     "get_fog_stats": [_vp, _p(FogStats)],
     "get_fog_visits": [_vp, _p(_u64), _p(_u64)],
+    "glass_default_params": [_p(GlassParams)],
+    "set_glass_params": [_vp, _p(GlassParams)],
+    "get_glass_stats": [_vp, _p(GlassStats)],
     "get_motion_stats": [_vp, _p(MotionStats)],
     "taa_default_params": [_p(TaaParams)],
     "set_taa_params": [_vp, _p(TaaParams)],
@@ -633,6 +642,8 @@ class Renderer:
         self._check(api.render_hybrid(self._ctx, C.byref(view), int(mask)))
         if int(mask) & HYBRID_TAA:
             self._taa_rendered = True
+        if int(mask) & HYBRID_GLASS:
+            self._glass_rendered = True
 
     _HYBRID_IMAGES = {
         HYBRID_POSITION: (np.float32, 4),
@@ -661,6 +672,9 @@ class Renderer:
     _GLOSSY_IMAGES = {HYBRID_GLOSSY_SCALE: (np.float32, 4), HYBRID_GLOSSY_BIAS: (np.float32, 4), HYBRID_GLOSSY_COUNTS: (np.uint8, 4)}
     # the two images of HYBRID_FOG: the library refuses them before the first fog pass
     _FOG_IMAGES = {HYBRID_FOG_MASK: (np.uint32, 1), HYBRID_FOG_TERMS: (np.float32, 4)}
+    # the three images of HYBRID_GLASS, which exist once a render_hybrid call with the bit has succeeded on this renderer (_glass_rendered)
+    _GLASS_IMAGES = {HYBRID_GLASS_RADIANCE: (np.float32, 4), HYBRID_GLASS_COUNTS: (np.uint8, 4), HYBRID_GLASS_EVENTS: (np.uint8, 4)}
+    _glass_rendered = False
 
     def read_hybrid(self, which):
         """one image of the hybrid graph: (H, W, 4) float32 position / normal / pbr / deferred output, (H, W, 4) uint8 albedo / reflections /
@@ -672,11 +686,14 @@ class Renderer:
         HYBRID_RTGI (H, W, 4) float32 filtered incoming radiance (w = 1 where the pixel cast) and (H, W, 4) uint8 ray counts (sunlit, dark,
         emitter, missed), and of HYBRID_GLOSSY (H, W, 4) float32 filtered scale and bias sums (w = 1 where the pixel cast) and (H, W, 4) uint8
         ray counts (sunlit, dark, emitter, missed), and of HYBRID_FOG (H, W) uint32 masks (bit k: sample k saw the sun) and (H, W, 4) float32
-        terms (a, Ttot, F, Ff; all 0 where the pixel did not march)"""
+        terms (a, Ttot, F, Ff; all 0 where the pixel did not march), and once a call with HYBRID_GLASS has run (H, W, 4) float32 glass
+        radiance (C, 1 where the pixel cast), (H, W, 4) uint8 chain counts (sunlit, dark, emitter, missed) and (H, W, 4) uint8 events (chain 0,
+        chain 1, flags, 0)"""
         images = {**self._HYBRID_IMAGES, **(self._TAA_IMAGES if self._taa_rendered else {}), **self._GI_IMAGES, **self._GLOSSY_IMAGES,
-                  **self._FOG_IMAGES}
+                  **self._FOG_IMAGES, **(self._GLASS_IMAGES if self._glass_rendered else {})}
         return self._read_image(images, self._hybrid_api().read_hybrid, which,
-                                f"hybrid image index {which} (0..15, 18..24, and 16..17 once a render_hybrid call with HYBRID_TAA has run)")
+                                f"hybrid image index {which} (0..15, 18..24, 16..17 once a render_hybrid call with HYBRID_TAA has run "
+                                f"and 25..27 once one with HYBRID_GLASS has)")
 
     def hybrid_stats(self):
         return self._stats(HybridStats, self._hybrid_api().get_hybrid_stats)
@@ -750,6 +767,19 @@ class Renderer:
     def glossy_stats(self):
         """UhGlossyStats of the last glossy pass: pixels, rays, below, shadow_rays, misses, trace_ms, shade_ms, shadow_ms, filter_ms, composite_ms"""
         return self._stats(GlossyStats, self._hip_only(self._GLOSSY, "get_glossy_stats"))
+
+    # -- ray-traced glass (HYBRID_GLASS; include/utopian_hip.h "UH_HYBRID_GLASS") ---
+    _GLASS = "ray-traced glass is a per-context verb"
+
+    def set_glass_params(self, params=None, **fields):
+        """uh_set_glass_params: `params` (a GlassParams; the defaults when None) with `fields` set on a copy - the params of the
+        render_hybrid calls with HYBRID_GLASS that follow. A refused call raises and leaves the old ones."""
+        return self._set_params(GlassParams, self._hip_only(self._GLASS, "set_glass_params"), glass_default_params, params, fields)
+
+    def glass_stats(self):
+        """UhGlassStats of the last glass pass: pixels, chains, segments, events, tir, cut, shadow_rays, misses, trace_ms, bend_ms, shadow_ms,
+        composite_ms"""
+        return self._stats(GlassStats, self._hip_only(self._GLASS, "get_glass_stats"))
 
     # -- volumetric fog (HYBRID_FOG; include/utopian_hip.h "UH_HYBRID_FOG") ---
     _FOG = "volumetric fog is a per-context verb"
@@ -1110,6 +1140,11 @@ def _default_params(Struct, name):
     if _bind(load_library(), "uh_", name)(C.byref(p)) != 0:
         raise UtopianError(f"uh_{name} failed")
     return p
+
+
+def glass_default_params():
+    """UhGlassParams as uh_glass_default_params fills it (needs no GPU)"""
+    return _default_params(GlassParams, "glass_default_params")
 
 
 def fog_default_params():

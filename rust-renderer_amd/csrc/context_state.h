@@ -619,6 +619,31 @@ struct uh_ctx {
          }
       } fog;
 
+      // ray-traced glass (UH_HYBRID_GLASS), allocated by the first pass: per pixel the count words, the radiance image, the events words and
+      // the queue of the pixels that cast; per ray (two a pixel) the hit / radiance record, origin, direction, sun-ray record and a word in
+      // each of the two round queues; and the pass's counters (GlassDev::counters). params: the last uh_set_glass_params (the defaults
+      // before). trace, bend: a stage per round of the last pass (its first `rounds`; the raygen is in trace[0]); then shadow, composite.
+      struct __attribute__((visibility("hidden"))) Glass {
+         DevBuf<uint32_t> counts, events, queue, counters, ray_queue[2];
+         DevBuf<float4> radiance, rays, orig, dirs, sun_rays;
+         UhGlassParams params{8, 16.0f, 1.0f};
+         Stage trace[kGlassMaxEvents], bend[kGlassMaxEvents], shadow, composite;
+         uint32_t renders = 0, rounds = 0;
+         template <class F> void images(size_t n, F&& f) {
+            f(counts, n), f(events, n), f(radiance, n), f(queue, n), f(rays, 2 * n), f(orig, 2 * n), f(dirs, 2 * n), f(sun_rays, 2 * n), f(ray_queue[0], 2 * n),
+               f(ray_queue[1], 2 * n), f(counters, kGlassCounters);
+         }
+         template <class F> void stages(F&& f) {
+            for (Stage& s : trace) f(s);
+            for (Stage& s : bend) f(s);
+            f(shadow), f(composite);
+         }
+         void destroy() {
+            images(0, ReleaseBuf{});
+            stages([](Stage& s) { s.destroy(); });
+         }
+      } glass;
+
       // motion vectors (UH_HYBRID_MOTION), allocated by the first call with the bit: the motion image, the pass's counts (pixels with /
       // without a correspondence, a pair per block of the kernel's grid, added up by uh_get_motion_stats), the per-mesh table the
       // kernels read, and the previous-position table (16-byte rows with bases of their own: isosurface meshes, which are never
@@ -693,7 +718,7 @@ struct uh_ctx {
 
       __attribute__((visibility("hidden"))) void destroy() {
          rt_images(0, ReleaseBuf{}), frame_images(0, ReleaseBuf{});
-         env.destroy(), sm.destroy(), gr.destroy(), mc.destroy(), rl.destroy(), ao.destroy(), gi.destroy(), gl.destroy(), fog.destroy(), mv.destroy(), taa.destroy(), post.destroy();
+         env.destroy(), sm.destroy(), gr.destroy(), mc.destroy(), rl.destroy(), ao.destroy(), gi.destroy(), gl.destroy(), glass.destroy(), fog.destroy(), mv.destroy(), taa.destroy(), post.destroy();
          meshes.release(), vertices.release(), indices.release(), raw_lights.release();
          for (hipEvent_t ev : waits)
             if (ev) (void)hipEventDestroy(ev);

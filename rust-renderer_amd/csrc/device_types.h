@@ -353,6 +353,30 @@ struct FogDev {
 };
 constexpr uint32_t kFogSeedXor = 0x464F4721u;  // keeps the jitter from being another pass's sample
 
+// ray-traced glass of the hybrid frame (UH_HYBRID_GLASS; glass.hip): what its kernels read and write. Chain c (0 reflected, 1 transmitted)
+// of the pixel in queue slot q is ray q * 2 + c in `rays`, `orig` and `dirs`. Round r walks the rays listed in ray_queue[r & 1], whose
+// count is counters[kGlassRound0 + r], and its bend kernel lists the chains that go on in ray_queue[(r + 1) & 1], counted in
+// counters[kGlassRound0 + r + 1]: no host read-back between rounds. counts, rays, sun_rays, queue and counters[0..2] are laid out as
+// RtgiDev's with samples = 2: the sun rays go through k_rtgi_shadow (glass_sun_view)
+constexpr uint32_t kGlassMaxEvents = 16, kGlassRound0 = 8, kGlassCounters = kGlassRound0 + kGlassMaxEvents + 1;
+static_assert(kGlassRound0 >= 3, "glass_walk_view points GlossyDev::counters three words before a round's counter");
+struct GlassDev {
+   uint32_t* counts;               // UH_HYBRID_GLASS_COUNTS: a word per pixel, bytes (low first) sunlit, dark, emitter, missed; added to by words
+   float4* radiance;               // UH_HYBRID_GLASS_RADIANCE: (C, 1) where the pixel cast, else (0, 0, 0, 0)
+   uint32_t* events;               // UH_HYBRID_GLASS_EVENTS: a word per pixel, byte 0 / 1 the events of chain 0 / 1, byte 2 the flags; added to by words
+   float4* rays;                   // by ray number: the hit record (t, u, v, idx) behind a round's walk, (w L.rgb, 0) once the chain has ended
+   float4* orig;                   // by ray number: the segment's origin.xyz, the chain's weight w
+   float4* dirs;                   // by ray number: the segment's direction.xyz (unnormalised), the chain's events so far (bits)
+   float4* sun_rays;               // the sun rays queued by the bend kernels: origin.xyz, ray number (bits)
+   uint32_t* ray_queue[2];         // the numbers of the rays of a round, compacted; ping-pong
+   uint32_t* queue;                // the pixels that cast, compacted
+   uint32_t* counters;             // [0]: entries of `queue`, [1]: entries of `sun_rays`, [2]: chains that missed,
+                                   // [4]: events at which `cannot` held, [5]: chains cut, [kGlassRound0 + r]: the rays of round r
+   uint32_t max_events;            // UhGlassParams::max_events
+   float max_radiance, intensity;
+};
+constexpr uint32_t kGlassTir = 1u << 16, kGlassCut0 = 1u << 17;  // the flag bits of an events word (chain c cut: kGlassCut0 << c)
+
 // the denoiser (uh_denoise; denoise.hip): one frame's guides and moments as the next call's history reads them
 struct DenoiseHistory {
    float4* pos;                    // the position texel (w != 0: geometry)

@@ -166,6 +166,8 @@ __global__ __launch_bounds__(kBlock) void k_glossy_raygen(SceneDev sc, HybridDev
 // The closest-hit walk over the queued rays, an item walk (item_walk.h) that shades nothing: the lane that takes a ray loads its origin
 // and direction, and when its walk ends it writes the hit record (t, u, v, idx; idx = kEmptyRef for a miss) and is idle for the next
 // refill at once. No lane waits for another and nothing of the shader is live here.
+// The glass pass runs its rounds through this kernel on a view of its own buffers (glass_walk_view, graphs_internal.h) whose `counters`
+// is valid at index 3 ALONE: the kernel must read nothing of gl but ray_queue, counters[3], orig, dirs and rays.
 __global__ __launch_bounds__(kBlock, 5) void k_glossy_trace(SceneDev sc, GlossyDev gl) {
    __shared__ ItemWalkLds s_walk;
    Trav t;
@@ -344,12 +346,18 @@ __global__ __launch_bounds__(kBlock) void k_glossy_composite(SceneDev sc, Hybrid
    fd.deferred[i] = make_float4(d.x + add.x, d.y + add.y, d.z + add.z, d.w);
 }
 
+// the walk alone, over at most `most` queued rays: gl.ray_queue, gl.counters[3], gl.orig and gl.dirs in, gl.rays out (the glass pass runs
+// its rounds through it: glass_walk_view, graphs_internal.h)
+void launch_glossy_walk(const LaunchCfg& c, const SceneDev& sc, const GlossyDev& gl, uint64_t most) {
+   const dim3 grid = persistent_grid(most, c.num_cus * c.closest_blocks_per_cu);
+   k_glossy_trace<<<grid, kBlock, 0, c.stream>>>(sc, gl);
+}
+
 void launch_glossy_trace(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd, const GlossyDev& gl) {
    const uint32_t n = hd.W * hd.H;
    k_glossy_classify<<<stream_grid(c, n), kBlock, 0, c.stream>>>(sc, hd, gl);
    k_glossy_raygen<<<stream_grid(c, n * gl.samples), kBlock, 0, c.stream>>>(sc, hd, gl);
-   const dim3 grid = persistent_grid((uint64_t)n * gl.samples, c.num_cus * c.closest_blocks_per_cu);
-   k_glossy_trace<<<grid, kBlock, 0, c.stream>>>(sc, gl);
+   launch_glossy_walk(c, sc, gl, (uint64_t)n * gl.samples);
 }
 
 void launch_glossy_shade(const LaunchCfg& c, const SceneDev& sc, const HybridDev& hd, const GlossyDev& gl) {

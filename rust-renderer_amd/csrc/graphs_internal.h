@@ -119,6 +119,32 @@ inline RtgiDev glossy_sun_view(const GlossyDev& gl) {
    gi.counts = gl.counts, gi.rays = gl.rays, gi.sun_rays = gl.sun_rays, gi.queue = gl.queue, gi.counters = gl.counters, gi.samples = gl.samples;
    return gi;
 }
+void launch_glossy_walk(const LaunchCfg&, const SceneDev&, const GlossyDev&, uint64_t most);  // k_glossy_trace alone, over at most `most` rays
+}  // namespace uh
+
+// ---- glass.hip ----
+// the glass pass (UH_HYBRID_GLASS); gs.counters zeroed by the caller. raygen: classify (which pixels cast; their images zeroed) and the
+// first event, which queues round 0's rays. A round is launch_glossy_walk on glass_walk_view(gs, round) - k_glossy_trace, unchanged,
+// writing the hit records of the round's queue - and launch_glass_bend(round), which settles the chains that end and lists those that go
+// on for round + 1. Then launch_rtgi_shadow on glass_sun_view and the composite, which replaces deferred_output.rgb.
+namespace uh {
+void launch_glass_raygen(const LaunchCfg&, const SceneDev&, const HybridDev&, const GlassDev&);
+void launch_glass_bend(const LaunchCfg&, const SceneDev&, const HybridDev&, const GlassDev&, uint32_t round);
+void launch_glass_composite(const LaunchCfg&, const HybridDev&, const HybridFrameDev&, const GlassDev&);
+// round `round` of this pass as k_glossy_trace reads it: the round's queue and its count (GlossyDev::counters[3]), origins, directions
+// (their w words are the chain's weight and events: the walk sets its own tmin and tmax), and the hit records out. The view's `counters`
+// is valid at index 3 alone (kGlassRound0 >= 3 keeps the pointer inside the buffer): k_glossy_trace reads no other slot, and says so
+inline GlossyDev glass_walk_view(const GlassDev& gs, uint32_t round) {
+   GlossyDev gl{};
+   gl.rays = gs.rays, gl.orig = gs.orig, gl.dirs = gs.dirs, gl.ray_queue = gs.ray_queue[round & 1u], gl.counters = gs.counters + (kGlassRound0 + round - 3u);
+   return gl;
+}
+// this pass's buffers as k_rtgi_shadow reads them: two chains per queued pixel
+inline RtgiDev glass_sun_view(const GlassDev& gs) {
+   RtgiDev gi{};
+   gi.counts = gs.counts, gi.rays = gs.rays, gi.sun_rays = gs.sun_rays, gi.queue = gs.queue, gi.counters = gs.counters, gi.samples = 2;
+   return gi;
+}
 }  // namespace uh
 
 // ---- hybrid_graph.hip ----

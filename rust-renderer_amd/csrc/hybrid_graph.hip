@@ -391,7 +391,7 @@ static int render_gbuffer_raster(uh_ctx* c, const LaunchCfg& lc, const UhViewUni
 struct HybridPlan {
    int code;
    const char* refusal;
-   bool raster, maps, render_maps, restir, rtao, rtgi, glossy, fog, mc, motion, rt, taa, post;  // maps: the IBL maps exist for this call's consumers
+   bool raster, maps, render_maps, restir, rtao, rtgi, glossy, glass, fog, mc, motion, rt, taa, post;  // maps: the IBL maps exist for this call's consumers
    bool deferred, frame, env;  // the deferred pass runs; the final frame's images and the IBL maps are needed
    bool first, frame_first;    // the ray-traced images, the final frame's images are allocated by this call (and cleared)
 };
@@ -556,6 +556,22 @@ static HybridPlan hybrid_plan(const uh_ctx& c, const UhViewUniformData& view, ui
       if ((uint64_t)c.W * c.H * 64u >= (1ull << 32))
          return refuse(UH_ERR_CAPACITY, "uh_render_hybrid: UH_HYBRID_FOG: a frame of 2^26 pixels or more (its rays are numbered in 32 bits)");
    }
+   // ray-traced glass: two chains of rays per dielectric pixel, which replace what the passes before wrote there
+   p.glass = (mask & UH_HYBRID_GLASS) != 0;
+   if (p.glass) {
+      if (view.raytracing_supported != 1)
+         return refuse(UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_GLASS casts rays and view.raytracing_supported is not 1; set it, or clear the bit");
+      if (!(mask & UH_HYBRID_GBUFFER) && !h.gbuffer_done)
+         return refuse(UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_GLASS casts its rays from the G-buffer, and no G-buffer has been rendered; set UH_HYBRID_GBUFFER");
+      if (!(mask & UH_HYBRID_DEFERRED))
+         return refuse(UH_ERR_INVALID_ARGUMENT,
+                     "uh_render_hybrid: UH_HYBRID_GLASS without UH_HYBRID_DEFERRED in the same call: the pass replaces what the deferred pass "
+                     "writes on dielectric pixels and has nothing to write into; set UH_HYBRID_DEFERRED");
+      if ((uint64_t)c.W * c.H >= (1ull << 27))
+         return refuse(UH_ERR_CAPACITY, "uh_render_hybrid: UH_HYBRID_GLASS: a frame of 2^27 pixels or more (its rays are numbered in 32 bits)");
+   }
    p.rt = view.raytracing_supported != 0;
    p.deferred = (mask & UH_HYBRID_DEFERRED) != 0;
    p.frame = (mask & (UH_HYBRID_SSAO | UH_HYBRID_DEFERRED | UH_HYBRID_SKY | UH_HYBRID_PRESENT)) || p.mc || p.rtao || p.taa || p.post;
@@ -623,6 +639,13 @@ static int hybrid_prepare(uh_ctx* c, const HybridPlan& p) {
                         grow(c, gl.ray_queue, rays, who)})
             if (st) return st;
       }
+   }
+   if (p.glass && !h.glass.counters.p) {
+      uh_ctx::Hybrid::Glass& gs = h.glass;
+      for (int st : {stage_create(c, gs.trace, kGlassMaxEvents), stage_create(c, gs.bend, kGlassMaxEvents), stage_create(c, &gs.shadow, 1),
+                     stage_create(c, &gs.composite, 1)})
+         if (st) return st;
+      if (int st = alloc_group(c, [&](auto f) { gs.images(pixels, f); })) return st;
    }
    if (p.fog && !h.fog.counters.p) {
       if (int st = stage_create(c, h.fog.stage, 3)) return st;
@@ -696,6 +719,7 @@ static void reset_stage_records(uh_ctx::Hybrid& h, const HybridPlan& p, uint32_t
       for (Stage& s : h.gi.stage) s.ran = false;
    if (p.glossy)
       for (Stage& s : h.gl.stage) s.ran = false;
+   if (p.glass) h.glass.stages([](Stage& s) { s.ran = false; });
    if (p.fog)
       for (Stage& s : h.fog.stage) s.ran = false;
 }
@@ -828,6 +852,36 @@ static int glossy_pass(uh_ctx* c, const HybridCall& k) {
    return UH_OK;
 }
 
+// the glass pass behind the glossy pass (behind the rtgi pass or deferred_pass without it): classify + the first event, then max_events
+// rounds of the closest-hit walk and the bend kernel - every kernel takes its count from that round's device counter, the two ray queues
+// swap, nothing is read back and nothing is waited for -, the sun rays' any-hit walk (k_rtgi_shadow on this pass's buffers) and the
+// composite, which replaces deferred_output.rgb on the pixels that cast. A stage per round's walk and bend (trace[0] holds the raygen).
+static int glass_pass(uh_ctx* c, const HybridCall& k) {
+   uh_ctx::Hybrid::Glass& g = c->hy.glass;
+   const UhGlassParams& p = g.params;
+   const GlassDev gs{g.counts.p, g.radiance.p, g.events.p, g.rays.p, g.orig.p, g.dirs.p, g.sun_rays.p, {g.ray_queue[0].p, g.ray_queue[1].p}, g.queue.p,
+                     g.counters.p, p.max_events, p.max_radiance, p.intensity};
+   const uint64_t most = (uint64_t)k.hd.W * k.hd.H * 2u;
+   int st = UH_OK;
+   for (uint32_t round = 0; round < p.max_events; round++) {
+      st = timed(c, g.trace[round], [&] {
+         if (round == 0) {
+            HIP_TRY(c, hipMemsetAsync(g.counters.p, 0, g.counters.n * sizeof(uint32_t), c->stream));
+            launch_glass_raygen(k.lc, c->scene, k.hd, gs);
+         }
+         launch_glossy_walk(k.lc, c->scene, glass_walk_view(gs, round), most);
+         return (int)UH_OK;
+      });
+      if (st) return st;
+      if ((st = timed(c, g.bend[round], [&] { launch_glass_bend(k.lc, c->scene, k.hd, gs, round); }))) return st;
+   }
+   if ((st = timed(c, g.shadow, [&] { launch_rtgi_shadow(k.lc, c->scene, k.hd, glass_sun_view(gs)); }))) return st;
+   if ((st = timed(c, g.composite, [&] { launch_glass_composite(k.lc, k.hd, k.fd, gs); }))) return st;
+   g.rounds = p.max_events;
+   g.renders++;
+   return UH_OK;
+}
+
 // the fog pass behind atmosphere_pass: classify + the any-hit walk of the samples' sun rays into the bit masks, the resolve / filter into
 // the terms image, then the composite into deferred_output; a stage each
 static int fog_pass(uh_ctx* c, const HybridCall& k) {
@@ -885,7 +939,7 @@ static int taa_pass(uh_ctx* c, const HybridCall& k) {
 
 // The passes in the order of build_render_graph (mod.rs:91-186, graph.rs:743), each between its stage's two events: setup_shadow_pass's
 // four cascades first, rt_shadows, gbuffer, setup_cubemap_pass, rt_reflections, then the final frame - ssao_pass (not with
-// ssao_enabled != 1, ssao.rs:27; the rtao pass takes its place), deferred_pass, the rtgi pass and the glossy pass (extensions), setup_marching_cubes_pass, atmosphere_pass, the fog pass (an
+// ssao_enabled != 1, ssao.rs:27; the rtao pass takes its place), deferred_pass, the rtgi, glossy and glass passes (extensions), setup_marching_cubes_pass, atmosphere_pass, the fog pass (an
 // extension; it attenuates and in-scatters into what the deferred and sky passes wrote), the taa pass
 // (an extension; present then reads its output), the post pass (an extension; it reads the taa pass's output or deferred_output, and
 // present then reads its own), present_pass
@@ -936,6 +990,7 @@ static int hybrid_passes(uh_ctx* c, const HybridCall& k, uint32_t mask) {
    }
    if (p.rtgi && (st = rtgi_pass(c, k))) return st;
    if (p.glossy && (st = glossy_pass(c, k))) return st;
+   if (p.glass && (st = glass_pass(c, k))) return st;
    h.frame_lights = h.stage[kStDeferred].ran ? (p.restir ? 2 : view.num_lights + 1) : 0;  // with the reservoir lights: the sun and the reservoir's
    if (p.restir) {
       // a reservoir pass enqueued after this call starts behind the call's reads (the spatial ring comes round to the slot read here)

@@ -1,5 +1,5 @@
 // hybrid_verbs.hip - what a caller reads from and sets on the hybrid graph between uh_render_hybrid calls (include/utopian_hip.h): the
-// images and IBL maps (uh_read_hybrid, uh_read_environment), every pass's stats, the params of the rtao, rtgi, glossy, fog and taa passes, the
+// images and IBL maps (uh_read_hybrid, uh_read_environment), every pass's stats, the params of the rtao, rtgi, glossy, glass, fog and taa passes, the
 // taa history reset and jitter. Host code over uh_ctx::Hybrid (context_state.h); nothing here touches the pass order
 // (hybrid_graph.hip). The HDR display chain's verbs are in post_graph.hip.
 #include <hip/hip_runtime.h>
@@ -15,7 +15,7 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    const uh_ctx::Hybrid& h = c->hy;
    if (!h.counter.p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid before the first uh_render_hybrid");
-   if (which < 0 || which > UH_HYBRID_FOG_TERMS) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..24");
+   if (which < 0 || which > UH_HYBRID_GLASS_EVENTS) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..27");
    const char* const no_frame = "uh_read_hybrid: images 6..8 before the first call with an SSAO, deferred, sky or present bit";
    const char* const no_mc = "uh_read_hybrid: images 9..10 before the first marching-cubes pass";
    const char* const no_gr = "uh_read_hybrid: images 11..12 before the first rasterised G-buffer pass";
@@ -23,6 +23,7 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
    const char* const no_gi = "uh_read_hybrid: images 18..19 before the first rtgi pass (UH_HYBRID_RTGI); until then the image index must be 0..17";
    const char* const no_gl = "uh_read_hybrid: images 20..22 before the first glossy pass (UH_HYBRID_GLOSSY); until then the image index must be 0..19";
    const char* const no_fog = "uh_read_hybrid: images 23..24 before the first fog pass (UH_HYBRID_FOG); until then the image index must be 0..22";
+   const char* const no_glass = "uh_read_hybrid: images 25..27 before the first glass pass (UH_HYBRID_GLASS); until then the image index must be 0..24";
    // image k in UH_HYBRID_* image order: its pixels, its bytes per pixel, whether it exists yet and what a read before that is told
    const struct { const void* pixels; size_t bpp; bool ready; const char* refusal; } img[] = {
       {h.pos.p, sizeof(float4), true, nullptr},
@@ -49,8 +50,11 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
       {h.gl.bias.p, sizeof(float4), h.gl.renders != 0, no_gl},
       {h.gl.counts.p, sizeof(uint32_t), h.gl.renders != 0, no_gl},
       {h.fog.mask.p, sizeof(uint32_t), h.fog.renders != 0, no_fog},
-      {h.fog.terms.p, sizeof(float4), h.fog.renders != 0, no_fog}};
-   static_assert(sizeof(img) / sizeof(img[0]) == UH_HYBRID_FOG_TERMS + 1, "one row per UH_HYBRID_* image");
+      {h.fog.terms.p, sizeof(float4), h.fog.renders != 0, no_fog},
+      {h.glass.radiance.p, sizeof(float4), h.glass.renders != 0, no_glass},
+      {h.glass.counts.p, sizeof(uint32_t), h.glass.renders != 0, no_glass},
+      {h.glass.events.p, sizeof(uint32_t), h.glass.renders != 0, no_glass}};
+   static_assert(sizeof(img) / sizeof(img[0]) == UH_HYBRID_GLASS_EVENTS + 1, "one row per UH_HYBRID_* image");
    if (!img[which].ready) return fail(c, UH_ERR_INVALID_ARGUMENT, img[which].refusal);
    return read_back(c, out, img[which].pixels, (size_t)c->W * c->H * img[which].bpp);
 }
@@ -196,6 +200,50 @@ int uh_get_glossy_stats(uh_ctx* c, UhGlossyStats* out) {
    out->misses = counters[2];
    out->rays = counters[3];
    out->below = counters[4];
+   return UH_OK;
+}
+
+// ---- ray-traced glass (utopian_hip.h "UH_HYBRID_GLASS"; glass.hip) ----
+int uh_glass_default_params(UhGlassParams* out) {
+   if (!out) return UH_ERR_INVALID_ARGUMENT;
+   *out = UhGlassParams{8, 16.0f, 1.0f};
+   return UH_OK;
+}
+
+static const char* glass_params_refusal(const UhGlassParams& p) {
+   if (p.max_events < 1 || p.max_events > kGlassMaxEvents) return "max_events must be 1..16";
+   if (!(p.max_radiance > 0.0f && p.max_radiance < INFINITY)) return "max_radiance must be finite and > 0";
+   if (!(p.intensity >= 0.0f && p.intensity < INFINITY)) return "intensity must be finite and >= 0";
+   return nullptr;
+}
+
+int uh_set_glass_params(uh_ctx* c, const UhGlassParams* params) {
+   return set_params(c, params, "uh_set_glass_params", glass_params_refusal, &uh_ctx::Hybrid::glass);
+}
+
+// chains: the rays of round 0; events: the rays of the rounds behind it (a chain enters round r + 1 by the event at the end of its
+// segment r); segments: the rays of every round
+int uh_get_glass_stats(uh_ctx* c, UhGlassStats* out) {
+   int st;
+   if (!stats_begin(c, out, sizeof(*out), "uh_get_glass_stats: null destination", c && c->hy.glass.renders != 0, &st)) return st;
+   uh_ctx::Hybrid::Glass& g = c->hy.glass;
+   for (uint32_t r = 0; r < g.rounds; r++) {
+      float t = 0.0f, b = 0.0f;
+      if ((st = stage_ms(c, g.trace[r], &t)) || (st = stage_ms(c, g.bend[r], &b))) return st;
+      out->trace_ms += t;
+      out->bend_ms += b;
+   }
+   if ((st = stage_ms(c, g.shadow, &out->shadow_ms)) || (st = stage_ms(c, g.composite, &out->composite_ms))) return st;
+   uint32_t counters[kGlassCounters] = {};
+   HIP_TRY(c, hipMemcpy(counters, g.counters.p, sizeof(counters), hipMemcpyDeviceToHost));
+   out->pixels = counters[0];
+   out->shadow_rays = counters[1];
+   out->misses = counters[2];
+   out->tir = counters[4];
+   out->cut = counters[5];
+   out->chains = counters[kGlassRound0];
+   for (uint32_t r = 1; r <= kGlassMaxEvents; r++) out->events += counters[kGlassRound0 + r];
+   out->segments = out->chains + out->events;
    return UH_OK;
 }
 

@@ -1,4 +1,4 @@
-// kernel_common.h — what the kernel files (kernels.hip, path_fused.hip, restir.hip, tiles.hip, hybrid_kernels.hip, rtao.hip, rtgi.hip, glossy.hip, fog.hip) share
+// kernel_common.h — what the kernel files (kernels.hip, path_fused.hip, restir.hip, tiles.hip, hybrid_kernels.hip, rtao.hip, rtgi.hip, glossy.hip, fog.hip, glass.hip) share
 // besides the device arithmetic: the block size, the launch-grid helpers of their launchers, and four small device functions that kernels
 // of more than one file call (resolve_color: the path tracer's resolve and the tile composition; gbuffer_fetch: the ReSTIR passes and the
 // hybrid passes; rtao_normal: rtao.hip and rtgi.hip; queue_pixels: every classify kernel of the hybrid frame). The hybrid frame's ray

@@ -486,6 +486,35 @@ class FogStats(C.Structure):
 assert C.sizeof(FogStats) == 40 and FogStats.lit.offset == 16 and FogStats.trace_ms.offset == 24 and FogStats.reserved.offset == 36
 
 
+# ray-traced glass of the hybrid frame (utopian_hip.h "UH_HYBRID_GLASS"): the pass behind the glossy pass and its three images
+HYBRID_GLASS = 1 << 20
+HYBRID_GLASS_RADIANCE, HYBRID_GLASS_COUNTS, HYBRID_GLASS_EVENTS = 25, 26, 27
+
+
+class GlassParams(C.Structure):
+    """UhGlassParams: the events of a chain, the first included (1..16), the cap of a chain's radiance and of the pixel's sum, and the
+    scale of what the composite writes; uh_glass_default_params fills the defaults"""
+
+    _fields_ = [("max_events", C.c_uint32), ("max_radiance", C.c_float), ("intensity", C.c_float)]
+
+
+assert C.sizeof(GlassParams) == 12 and [getattr(GlassParams, n).offset for n, _ in GlassParams._fields_] == [0, 4, 8]
+
+
+class GlassStats(C.Structure):
+    """UhGlassStats: the last glass pass - the pixels that cast, the chains cast, the segments walked (chains + events), the events behind
+    the first, the events at which refraction was impossible (the first included), the chains cut, the sun rays cast from the ends, the
+    chains that missed, hipEvent ms of classify + first event + the rounds' walks, of the rounds' bend kernels, of the sun rays' walk
+    and of the composite"""
+
+    _fields_ = [("pixels", C.c_uint64), ("chains", C.c_uint64), ("segments", C.c_uint64), ("events", C.c_uint64), ("tir", C.c_uint64),
+                ("cut", C.c_uint64), ("shadow_rays", C.c_uint64), ("misses", C.c_uint64),
+                ("trace_ms", C.c_float), ("bend_ms", C.c_float), ("shadow_ms", C.c_float), ("composite_ms", C.c_float)]
+
+
+assert C.sizeof(GlassStats) == 80 and GlassStats.misses.offset == 56 and GlassStats.trace_ms.offset == 64 and GlassStats.composite_ms.offset == 76
+
+
 # motion vectors for moving geometry (an extension; utopian_hip.h "motion vectors"): a modifier of HYBRID_GBUFFER; bit 9 stays unused
 HYBRID_MOTION = 1 << 14
 HYBRID_MOTION_IMAGE = 15
