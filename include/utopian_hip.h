@@ -219,7 +219,8 @@ typedef struct UhStats {
    float camera_grid_mean_list; /* entries per occupied pixel */
    uint64_t camera_tree_rays;   /* primary rays the grid handed to the tree walk (pixels with long lists); part of rays[UH_RAY_PRIMARY] */
    uint64_t camera_grid_tris_tested; /* triangle packets tested by the grid walk of the primary rays (option "count_visits") */
-   float camera_grid_ms;        /* summed hipEvent time of the primary rays' launches when they go through the grid (option "time_kernels") */
+   float camera_grid_ms;        /* summed hipEvent time of the primary rays' launches when they go through the grid (option "time_kernels");
+                                   0 for the passes whose first bounce is one kernel (option "fused_primary"): that kernel's time is part of shade_ms */
    float trace_light_ms;        /* summed hipEvent time of the light shadow rays' traversal launches (reference.rgen:106-124; option "time_kernels"); not part of trace_shadow_ms */
    uint64_t sun_covered_rays;   /* sun shadow rays answered by their cell's cover depth alone (option "count_visits") */
    uint64_t sun_grid_bytes;     /* device memory of the sun grid in use: cell records + entry lists + coarse cover + the lists as 64-byte records (when within "sun_grid_inline_max_mb") */
@@ -334,7 +335,7 @@ int uh_trace_any(uh_ctx* ctx, const float* rays, uint32_t n, uint8_t* out_occlud
 /* ---- stats / options ------------------------------------------------------------------- */
 int uh_get_stats(uh_ctx* ctx, UhStats* out);
 int uh_reset_stats(uh_ctx* ctx);
-/* The 27 options (DESIGN.md section 7 has the defaults and what was measured); unknown names return UH_ERR_INVALID_ARGUMENT.
+/* The 33 options (DESIGN.md section 7 has the defaults and what was measured); unknown names return UH_ERR_INVALID_ARGUMENT.
  *  diagnostics   "count_visits" (0/1: UhStats' node / triangle / cover counters), "time_kernels" (0/1: hipEvent time per kernel kind)
  *  results       "full_frame_restir" (0/1; 1 = documented divergence: the reservoir for every pixel instead of the reference's
  *                x > W/2 split), "furnace" (0/1: the reference's FURNACE_TEST build of the miss shader, reference.rmiss:14-28 - a path
@@ -367,7 +368,11 @@ int uh_reset_stats(uh_ctx* ctx);
  *                or for a call of 8 or more frames - go through a per-camera grid of packet lists, one cell per pixel, instead of
  *                the tree; same hit records bit for bit), "camera_grid_max_walk", "camera_grid_walk_whole",
  *                "camera_grid_max_mean_list_x10", "primary_implicit" (0/1, default 1: with that grid in use and one sample per frame,
- *                the primary rays' state is not stored - the kernels of the first bounce compute it from the path id; same images)
+ *                the primary rays' state is not stored - the kernels of the first bounce compute it from the path id; same images),
+ *                "fused_primary" (0/1, default 1: in a pass with that grid, "primary_implicit" and the slim state in effect, none of
+ *                whose pixels hands its ray to the tree, and "count_visits" off, the first bounce is ONE kernel that stands at the
+ *                pixel - primary ray, list walk and hit shading - instead of three that pass ids and hit records through memory;
+ *                0: always the three kernels; same images)
  *  scheduling    "frames_in_flight" (1..8, default 4), "batch_frames" (0 = auto), "overlap" (0/1, default 1: the miss shader and the
  *                shadow traversals on a second stream beside the next bounce's traversal), "trace_blocks_per_cu" (1..8: persistent
  *                grid of the traversal kernels), "fused_bounces" (default 1: a frame that goes alone - uh_render_frame, or a call

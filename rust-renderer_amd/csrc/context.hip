@@ -461,6 +461,8 @@ int uh_trace_any(uh_ctx* c, const float* rays, uint32_t n, uint8_t* out_occluded
    return UH_OK;
 }
 
+// (the kernel times by kind: a pass whose bounce 0 is k_primary_shade - SamplePlan::fused_primary - books it under kind 2, shading, and
+// nothing under kind 3: camera_grid_ms reads 0 for such frames)
 int uh_get_stats(uh_ctx* c, UhStats* out) {
    if (!c || !out) return UH_ERR_INVALID_ARGUMENT;
    HIP_TRY(c, hipSetDevice(c->device));

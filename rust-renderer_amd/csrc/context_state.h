@@ -417,6 +417,7 @@ struct uh_ctx {
    SunGridExtras sun_x;
    bool primary_implicit = true;    // option "primary_implicit" (FrameParams::primary_implicit)
    bool slim_state = true;          // option "slim_state" (FrameParams::slim_state)
+   bool fused_primary = true;       // option "fused_primary" (frame_plan.h SamplePlan::fused_primary)
 
    // the primary rays through a per-camera grid instead of the tree (sun_grid.h "camera grid"; option "camera_grid"), built once the same
    // camera has been asked for in two consecutive frame calls, or at once by a call that carries 8 frames of it (grid_cache.hip ensure_camera_grid)

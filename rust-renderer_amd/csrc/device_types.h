@@ -479,6 +479,8 @@ void launch_trace_camera_grid(const LaunchCfg&, const FrameParams&, const SceneD
                               const SunGridDev&, bool leftovers_possible = true);  // false: the grid's longest list is one its kernel walks itself - no tree-walk launch behind it
 void launch_shade_miss(const LaunchCfg&, const FrameParams&, const PathState&, Control*, DeviceStats*, uint32_t bounce);
 void launch_shade_hit(const LaunchCfg&, const FrameParams&, const SceneDev&, const PathState&, const Images&, Control*, DeviceStats*, uint32_t bounce);
+// bounce 0 in one kernel (frame_plan.h SamplePlan::fused_primary): stands in for launch_generate, launch_trace_camera_grid and launch_shade_hit(0)
+void launch_primary_shade(const LaunchCfg&, const FrameParams&, const SceneDev&, const PathState&, Control*, DeviceStats*, const SunGridDev&);
 // the paths still alive after the last bounce hand their radiance to the per-id array k_finish_sample reads
 // (not launched for a pass with FrameParams::slim_state: its last sun kernels store the radiance themselves)
 void launch_flush_survivors(const LaunchCfg&, const FrameParams&, const PathState&, Control*);

@@ -95,9 +95,12 @@ static int enqueue_path_trace(uh_ctx* c, Slot& s, const FrameParams& frame) {
    FrameParams fp = frame;  // + sun_verdicts and slim_state, which follow the launches chosen per sample
    LaunchCfg lc = cfg(c);
    lc.stream = s.stream;
-   const SampleOptions opt{c->fused_bounces, c->fused_always, c->sun_x.verdicts, c->slim_state, c->overlap_miss, c->overlap_shadow, lc.closest_blocks_per_cu, lc.shadow_blocks_per_cu};
+   const SampleOptions opt{c->fused_bounces, c->fused_always, c->sun_x.verdicts, c->slim_state, c->overlap_miss, c->overlap_shadow, lc.closest_blocks_per_cu, lc.shadow_blocks_per_cu,
+                           c->fused_primary};
+   // (a pixel whose list is longer than the grid kernel walks hands its ray to the tree walk behind it)
+   const bool cam_leftovers = c->cam.max_list_interior > std::max(c->cam.dev.walk_whole, c->cam.dev.max_walk);
    const SampleFacts facts{fp.batch_frames, fp.num_bounces, fp.samples_per_frame, fp.n_owned, s.ps.shard_cap, fp.sun_shadow_enabled == 1, fp.lights_enabled == 1,
-                           c->sun.this_frame, c->cam.this_frame};
+                           c->sun.this_frame, c->cam.this_frame, fp.primary_implicit != 0, c->cam.this_frame && !cam_leftovers, lc.count_visits, fp.owned_pixels != nullptr};
    Control* ctl = s.control.p;
    DeviceStats* st = c->dstats.p;
    // reference.rgen:28: samples of one frame run back to back (the raygen RNG state carries over)
@@ -110,21 +113,28 @@ static int enqueue_path_trace(uh_ctx* c, Slot& s, const FrameParams& frame) {
       fp.sun_verdicts = plan.sun_verdicts ? 1u : 0u;
       fp.slim_state = plan.slim_state ? 1u : 0u;
       HIP_TRY(c, hipMemsetAsync(ctl, 0, sizeof(Control), s.stream));
-      launch_generate(lc, fp, s.ps, ctl, smp);  // (behind the choice of the state: the origin quads it stores carry the id or the RNG word)
+      // (behind the choice of the state: the origin quads it stores carry the id or the RNG word; fused_primary: bounce 0's kernel stands at the pixels itself)
+      if (!plan.fused_primary) launch_generate(lc, fp, s.ps, ctl, smp);
       for (uint32_t b = 0; b < plan.wave_bounces; b++) {
-         begin_timed(c, (b == 0 && plan.grid_primary) ? 3 : 0, s.stream);
-         if (b == 0 && plan.grid_primary) {
-            // no tree walk for the primary rays of a camera at rest (and no launch for one when no pixel's list is too long for the grid kernel)
-            launch_trace_camera_grid(lc, fp, c->scene, s.ps, ctl, st, slot, slot + 1, c->cam.dev, c->cam.max_list_interior > std::max(c->cam.dev.walk_whole, c->cam.dev.max_walk));
-            slot += 2;
-         } else
-            launch_trace_closest(lc, c->scene, s.ps, ctl, st, b, slot++, b == 0 ? UH_RAY_PRIMARY : UH_RAY_BOUNCE);
-         end_timed(c, s.stream);
+         const bool primary_shade = b == 0 && plan.fused_primary;  // bounce 0's walk and shading are one launch, timed as shading (kind 2)
+         if (primary_shade)
+            slot += 2;  // (the cursor slots of the two launches it stands for stay theirs: the later launches keep their numbers)
+         else {
+            begin_timed(c, (b == 0 && plan.grid_primary) ? 3 : 0, s.stream);
+            if (b == 0 && plan.grid_primary) {
+               // no tree walk for the primary rays of a camera at rest (and no launch for one when no pixel's list is too long for the grid kernel)
+               launch_trace_camera_grid(lc, fp, c->scene, s.ps, ctl, st, slot, slot + 1, c->cam.dev, cam_leftovers);
+               slot += 2;
+            } else
+               launch_trace_closest(lc, c->scene, s.ps, ctl, st, b, slot++, b == 0 ? UH_RAY_PRIMARY : UH_RAY_BOUNCE);
+            end_timed(c, s.stream);
+         }
          // shade_hit(b) rewrites ray_o / thr / rad of the paths shadow(b-1) still reads on the side stream, and refills the
          // miss queue shade_miss(b-1) reads there
          if (plan.side_used && b > 0) HIP_TRY(c, hipStreamWaitEvent(s.stream, s.ev_shadowed, 0));
          begin_timed(c, 2, s.stream);
-         launch_shade_hit(lc, fp, c->scene, s.ps, c->im, ctl, st, b);  // also hands the bounce's misses to shade_miss (Q_MISS)
+         if (primary_shade) launch_primary_shade(lc, fp, c->scene, s.ps, ctl, st, c->cam.dev);
+         else launch_shade_hit(lc, fp, c->scene, s.ps, c->im, ctl, st, b);  // either also hands the bounce's misses to shade_miss (Q_MISS)
          if (!c->overlap_miss) launch_shade_miss(lc, fp, s.ps, ctl, st, b);
          end_timed(c, s.stream);
          // shade_miss(b) and the shadow queries of bounce b are independent of trace_closest(b+1) (they only read what

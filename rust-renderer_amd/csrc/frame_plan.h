@@ -21,11 +21,16 @@ constexpr uint32_t kSingleFrameBlocksPerCu = 4;
 struct SampleOptions {  // uh_set_option's, as the context holds them
    bool fused_bounces, fused_always, sun_verdicts, slim_state, overlap_miss, overlap_shadow;
    uint32_t closest_blocks_per_cu, shadow_blocks_per_cu;
+   bool fused_primary = true;  // option "fused_primary"
 };
 struct SampleFacts {  // the frame's
    uint32_t batch_frames, num_bounces, samples_per_frame, n_owned, shard_cap;
    bool sun_shadow_enabled, lights_enabled;  // the view's flags == 1
    bool sun_grid, camera_grid;               // the sun grid / the camera grid serves this frame (CachedGrid::this_frame)
+   bool primary_implicit = false;            // FrameParams::primary_implicit: bounce 0's state is not stored
+   bool camera_lists_walked = false;         // no pixel's list is longer than the camera-grid kernel walks itself: none of its rays goes to the tree
+   bool count_visits = false;                // option "count_visits": the walks count their node and triangle tests
+   bool tile_partition = false;              // the rank traces the pixels of its tiles only (FrameParams::owned_pixels): path ids are not pixels
 };
 struct SamplePlan {
    bool fused;            // bounces 1.. run inside k_path_fused
@@ -39,6 +44,7 @@ struct SamplePlan {
    bool join_side;        // the main stream waits for the side stream's work: before the fused kernel, or with fused_sun0 behind it
    uint32_t wave_bounces; // bounces the wavefront of launches runs
    bool flush;            // launch_flush_survivors runs
+   bool fused_primary;    // bounce 0 is k_primary_shade: no k_generate, no camera-grid launch, no k_shade_hit(0)
 };
 
 // gpu_idle: the frame before this one has left the GPU (the caller asks per sample)
@@ -75,6 +81,12 @@ inline SamplePlan plan_sample(const SampleOptions& o, const SampleFacts& f, bool
    // per-id array the tail reads
    // (slim state: the last bounce's sun kernels stood at those positions with the verdict in hand and stored it themselves)
    p.flush = f.num_bounces > 0 && !p.fused && !p.slim_state;
+   // Bounce 0 in one kernel (option "fused_primary", kernels.hip k_primary_shade): where the three kernels of bounce 0 hand each other
+   // nothing a lane at the pixel cannot compute - the camera grid serves the primary rays and none of them goes to the tree, their
+   // state is implicit, and the slim state wants no id queue behind bounce 0 - and nobody counts the walk's tests. A rank of a tile
+   // partition keeps the three kernels: its runs of 64 ids are not 64 neighbouring pixels, which the one kernel has not been measured
+   // on. The slim state implies sun verdicts, which imply !fused: a lone frame that runs k_path_fused keeps the three kernels in front of it.
+   p.fused_primary = o.fused_primary && p.grid_primary && f.primary_implicit && p.slim_state && f.camera_lists_walked && !f.count_visits && !f.tile_partition;
    return p;
 }
 

@@ -6,16 +6,19 @@
 // compacted queues of path ids:
 //     generate -> [ trace_closest -> shade_miss | shade_hit -> trace_shadow(sun) -> trace_shadow(light) ]*
 //              -> finish_sample
+// Bounce 0 of a pass whose primary rays go through the camera grid with nothing stored (SamplePlan::fused_primary, frame_plan.h) is ONE launch,
+// k_primary_shade, in place of generate -> trace_camera_grid -> shade_hit(0): primary ray, list walk and hit shading at the pixel.
 // Traversal kernels are persistent: a grid that just fills the chip pulls 64-ray batches from a
 // device-side cursor until the queue (whose length only the device knows) is drained.
 // What other kernel files share with these lives in headers: the BVH4 walk (traversal.h), the per-path shading arithmetic
-// (path_shading.h), the sun grid's look-up (grid_walk.h), grids and block size (kernel_common.h). The lone
+// (path_shading.h), the body of the hit shading that k_shade_hit and k_primary_shade share (hit_shading.h), the sun grid's look-up (grid_walk.h), grids and block size (kernel_common.h). The lone
 // frame's fused kernel is path_fused.hip, the ReSTIR passes restir.hip, the multi-GPU tiles tiles.hip, the hybrid passes hybrid_kernels.hip.
 #include <hip/hip_runtime.h>
 
 #include "device_math.h"
 #include "device_types.h"
 #include "grid_walk.h"
+#include "hit_shading.h"
 #include "kernel_common.h"
 #include "path_shading.h"
 #include "traversal.h"
@@ -435,6 +438,33 @@ __global__ __launch_bounds__(kBlock) void k_trace_sun_grid(SceneDev sc, FramePar
 // The 64 rays of a wave are 64 neighbouring pixels: cell records, entries and packets are shared or adjacent - this kernel runs
 // out of the caches where the tree walk of the same rays fetched ~20 records per ray.
 // ------------------------------------------------------------------------------------------
+// the walk of one pixel's list [e, end) by its primary ray (k_trace_camera_grid, k_primary_shade): the closest hit among the list's packets,
+// idx = kEmptyRef for none. sorted: the builder sorted the list by the distance bound, the walk ends where the bound passes the best hit;
+// otherwise (a list longer than max_walk, walked whole under walk_whole) every packet is tested.
+template <bool COUNT>
+__device__ __forceinline__ Hit camera_list_walk(const SunGridDev& g, const float4* __restrict__ tris, uint32_t e, uint32_t end, bool sorted, V3 o, V3 d, uint32_t& n_tris) {
+   Hit best;
+   best.t = 10000.0f;  // rgen:45: tmax
+   best.u = best.v = 0.0f;
+   best.idx = kEmptyRef;
+   best.key = 0xffffffffu;
+   uint2 en = make_uint2(0u, 0u);
+   if (e < end) en = reinterpret_cast<const uint2*>(g.entries)[e];
+   while (e < end) {
+      // sorted by the bound, ascending: from here on no packet can be hit nearer than the best hit (nor tie with it)
+      if (sorted && -__uint_as_float(en.y) > best.t) break;
+      const uint32_t pk = en.x;
+      uint2 nxt = make_uint2(0u, 0u);
+      if (e + 1 < end) nxt = reinterpret_cast<const uint2*>(g.entries)[e + 1];  // in flight with the packet
+      const float4 a = tris[kTriStride16 * (size_t)pk + 0], b = tris[kTriStride16 * (size_t)pk + 1], c = tris[kTriStride16 * (size_t)pk + 2];
+      if (COUNT) n_tris++;
+      tri_compute<false>(a, b, c, pk, o, d, 0.001f, INFINITY, best);
+      en = nxt;
+      e++;
+   }
+   return best;
+}
+
 template <bool COUNT>
 __global__ __launch_bounds__(kBlock) void k_trace_camera_grid(SceneDev sc, FrameParams fp, PathState ps, Control* ctl, DeviceStats* stats, uint32_t cursor_slot, SunGridDev g) {
    const uint32_t lane = lane_id();
@@ -478,26 +508,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_camera_grid(SceneDev sc, Frame
                ro = ld_rec(rec_quad(rec, seg + i, REC_ORIGIN));
                rd = ld_rec(rec_quad(rec, seg + i, REC_DIR));
             }
-            const V3 o = v3(ro.x, ro.y, ro.z), d = v3(rd.x, rd.y, rd.z);
-            Hit best;
-            best.t = 10000.0f;  // rgen:45: tmax
-            best.u = best.v = 0.0f;
-            best.idx = kEmptyRef;
-            best.key = 0xffffffffu;
-            uint2 en = make_uint2(0u, 0u);
-            if (e < end) en = reinterpret_cast<const uint2*>(g.entries)[e];
-            while (e < end) {
-               // sorted by the bound, ascending: from here on no packet can be hit nearer than the best hit (nor tie with it)
-               if (sorted && -__uint_as_float(en.y) > best.t) break;
-               const uint32_t pk = en.x;
-               uint2 nxt = make_uint2(0u, 0u);
-               if (e + 1 < end) nxt = reinterpret_cast<const uint2*>(g.entries)[e + 1];  // in flight with the packet
-               const float4 a = tris[kTriStride16 * (size_t)pk + 0], b = tris[kTriStride16 * (size_t)pk + 1], c = tris[kTriStride16 * (size_t)pk + 2];
-               if (COUNT) n_tris++;
-               tri_compute<false>(a, b, c, pk, o, d, 0.001f, INFINITY, best);
-               en = nxt;
-               e++;
-            }
+            const Hit best = camera_list_walk<COUNT>(g, tris, e, end, sorted, v3(ro.x, ro.y, ro.z), v3(rd.x, rd.y, rd.z), n_tris);
             st_rec(ps.hit + seg + i, make_float4(best.t, best.u, best.v, __uint_as_float(best.idx)));
          }
       }
@@ -643,9 +654,7 @@ __global__ __launch_bounds__(kBlock, kShadeHitBlocks) void k_shade_hit(FramePara
    // kernel ran 86 % TA-busy at 2 % VALU, profiles/r01c_*); LDS serves them at no TA cost
    __shared__ float s_lut[256];
    s_lut[threadIdx.x] = sc.unorm_lut[threadIdx.x];
-   // per-mesh shading records and texture descriptors of the first kLdsMeshes / kLdsTextures entries: every hit
-   // gathers 64 + 24 bytes of them per lane, and the kernel is bound by its gather traffic (texture addresser)
-   constexpr uint32_t kLdsMeshes = 192, kLdsTextures = 64;
+   // the first kLdsMeshes / kLdsTextures per-mesh shading records and texture descriptors (hit_shading.h)
    __shared__ MeshShade s_mesh[kLdsMeshes];
    __shared__ TexInfo s_tex[kLdsTextures];
    const uint32_t n_lds_mesh = sc.num_meshes < kLdsMeshes ? sc.num_meshes : kLdsMeshes;
@@ -672,112 +681,10 @@ __global__ __launch_bounds__(kBlock, kShadeHitBlocks) void k_shade_hit(FramePara
    const uint32_t stride = sx.nb * kBlock;
    const uint32_t rounds = (count + stride - 1) / stride;
    uint32_t n_hits = 0;
-   // one path per lane: `valid` lanes shade their hit; every lane of the wave takes part in the queue appends.
-   // pos: the path's position in this bounce's queue (without the shard segment); its top bit: the path's sun verdict (kSunLitBit)
-   auto shade = [&](uint32_t id, uint32_t pos_lit, float4 hr, bool valid) {
-      const uint32_t pos = pos_lit & ~kSunLitBit;
-      const bool sun_lit = (pos_lit & kSunLitBit) != 0u;
-      const uint32_t pk = __float_as_uint(hr.w);
-      bool scattered = false, want_light = false;
-      uint32_t slot = 0;        // the scattered path's position in the next bounce's queue
-      float4 n_o = make_float4(0, 0, 0, 0), n_d = make_float4(0, 0, 0, 0), n_t = make_float4(0, 0, 0, 0), n_r = make_float4(0, 0, 0, 0);  // the scattered path's new state
-      if (valid) {
-         // every record of the path is requested up front, together with the shading packet (whose index the
-         // classification below already read): one round trip for all of them, then one for the texels.
-         // The path's state: four planes at its queue position (the RNG words ride in the rays' w components); the lanes of a wave
-         // hold hits of nearly consecutive positions, so these are nearly contiguous reads
-         float4 ro, rd, thr4;
-         if (bounce == 0 && fp.primary_implicit) {  // a primary ray's state is not stored (FrameParams::primary_implicit): from its id
-            primary_state(fp, id, ro, rd);
-            thr4 = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-         } else {
-            ro = ld_rec(rec_quad(cur, seg + pos, REC_ORIGIN));
-            rd = ld_rec(rec_quad(cur, seg + pos, REC_DIR));
-            thr4 = ld_rec(rec_quad(cur, seg + pos, REC_THR));
-         }
-         uint2 rng = make_uint2(__float_as_uint(ro.w), __float_as_uint(rd.w));
-         if constexpr (SLIM) {
-            if (bounce != 0) id = rng.x;  // the origin's w is the path id (at bounce 0 the id came from queue[0])
-            rng.x = 0u;                   // (no raygen RNG word in the slim state: nothing of such a pass reads one)
-         }
-         float4 rad4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // radiance so far: zero before the first bounce (not materialised)
-         if (rad_stored(fp, bounce)) rad4 = ld_rad<SLIM>(cur, seg + pos, thr4);  // (the compiler waits for it on the spot: measured level with an unconditional read, which costs 16 bytes per hit at bounce 0)
-         const V3 ray_dir = v3(rd.x, rd.y, rd.z);
-         const float t = hr.x, bu = hr.y, bv = hr.z;
-         const float4* sp = sc.shade + 4 * (size_t)pk;  // pk = hr.w, known since the classification: no wait for hr before these
-         float4 s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3];
-         const uint32_t mesh_index = __float_as_uint(s3.w);
-         // rchit:22-23. The LDS copy is read unconditionally (clamped index, explicit ds_read: device_math.h lds_fetch)
-         // and replaced from global memory for the meshes beyond the LDS table
-         MeshShade ms = lds_fetch(s_mesh + (mesh_index < kLdsMeshes ? mesh_index : kLdsMeshes - 1));
-         if (mesh_index >= n_lds_mesh) ms = sc.meshes[mesh_index];
-         V3 normal;
-         float uu, vv;
-         surface_normal_uv(s0, s1, s2, s3, bu, bv, normal, uu, vv);                    // rchit:30-31, :39
-         // keeps the compiler from sinking the early loads to their first use
-         asm volatile("" : "+v"(rng.x), "+v"(rng.y), "+v"(thr4.x), "+v"(thr4.y), "+v"(thr4.z), "+v"(rad4.x), "+v"(rad4.y), "+v"(rad4.z));
-         if (sun_lit) rad4 = shadow_lit<false>(thr4, rad4);  // rgen:69-78 of the bounce before: its sun ray left a verdict, the records are here
-         const V3 world_normal = world_normal_of(ms, normal, ray_dir);                 // rchit:32-37
-         // where the path goes on from (and its sun ray starts): needs nothing the texels bring
-         V3 origin = v3(ro.x, ro.y, ro.z) + t * ray_dir;                               // rgen:59
-         origin = offset_ray(origin, world_normal);                                    // rgen:60
-         // Does the path go on? Decided by the material type and the side the ray came from (rchit:47-89) - nothing the texels
-         // bring -, so the scattered paths' places in the next bounce's queue are asked for together with the texels: the returning
-         // atomic is in flight with them instead of a round trip of its own after the material evaluation. (Inside the divergent
-         // block: the ballot sees the valid lanes, which are the only ones that can scatter.)
-         scattered = path_scatters(ms, ray_dir, world_normal);
-         const unsigned long long scat_mask = __ballot(scattered);
-         const int scat_leader = __ffsll((long long)scat_mask) - 1;
-         uint32_t scat_base = 0;
-         V3 color = sample_texture_pre(sc, s_lut, ms.diffuse_map, uu, vv, s_tex, n_lds_tex, [&] {  // rchit:40
-            // (the counter's address goes through a register the compiler cannot see into: for a wave-uniform address its atomic
-            // optimiser rewrites the add as a wave reduction with a readfirstlane of the result - and a wait for it - on the spot)
-            typedef __attribute__((address_space(1))) uint32_t* global_u32_t;  // (a pointer of unknown address space would make it a flat atomic, which LDS waits wait for)
-            global_u32_t counter = (global_u32_t)n_next;
-            asm volatile("" : "+v"(counter));
-            if (scattered && (int)lane_id() == scat_leader) scat_base = __hip_atomic_fetch_add(counter, (uint32_t)__popcll(scat_mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-         });
-         color = color * v3(ms.base_color[0], ms.base_color[1], ms.base_color[2]);    // rchit:41
-
-         uint32_t seed = rng.y;
-         const V3 scatter = material_scatter(ms, ray_dir, world_normal, color, seed);  // rchit:47-89
-         rng.y = seed;                                                                 // rchit:91
-         if (scat_leader >= 0) slot = (uint32_t)__builtin_amdgcn_readlane((int)scat_base, scat_leader) + __builtin_amdgcn_mbcnt_hi((uint32_t)(scat_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)scat_mask, 0u));
-
-         V3 thr = v3(thr4.x, thr4.y, thr4.z) * color;                                  // rgen:48
-         if (!scattered) {                                                             // rgen:53-57: the path ends here
-            // its radiance goes to the per-id array k_finish_sample reads, with the raygen's RNG word: the next sample of the
-            // frame starts from it (rgen:28-31)
-            st_stream(ps.radf + id, make_float4(rad4.x + thr.x, rad4.y + thr.y, rad4.z + thr.z, __uint_as_float(rng.x)));
-         } else {
-            float f = 0.0f;
-            int light_index = 0;
-            if constexpr (!SLIM)
-               if (fp.lights_enabled == 1) want_light = select_light(fp, sc, id, rng.x, origin, f, light_index);  // rgen:81-121
-            // the path's state for the next bounce; written below at the position the path gets in the next bounce's queue
-            n_o = make_float4(origin.x, origin.y, origin.z, __uint_as_float(SLIM ? id : rng.x));
-            n_d = make_float4(scatter.x, scatter.y, scatter.z, __uint_as_float(rng.y));  // rgen:61
-            n_t = make_float4(thr.x, thr.y, thr.z, SLIM ? rad4.x : f);
-            n_r = make_float4(rad4.x, rad4.y, rad4.z, __uint_as_float((uint32_t)light_index));  // the radiance travels with the path
-         }
-      }
-      // a wave's scattered paths get consecutive positions: their new state leaves as contiguous stores, and the next bounce's
-      // traversal, sun-ray and shading kernels read it back as streams
-      // the light queue: one round trip - none at all when no lane has an entry
-      uint32_t lslot = 0;
-      if constexpr (!SLIM) lslot = wave_append(n_light, want_light);
-      if (scattered) {
-         if constexpr (!SLIM) st_stream(q_next + slot, id);
-         st_rec(rec_quad(nxt, seg + slot, REC_ORIGIN), n_o);
-         if (bounce + 1 < fp.num_bounces) st_rec(rec_quad(nxt, seg + slot, REC_DIR), n_d);  // (after the last bounce no ray is traced: k_flush_survivors reads radiance and the raygen RNG word)
-         st_rec(rec_quad(nxt, seg + slot, REC_THR), n_t);  // (SLIM: w = radiance.r - a zero nobody reads where the radiance is not materialised)
-         if (rad_stored(fp, bounce + 1)) {
-            if constexpr (SLIM) st_rad_pair(nxt, seg + slot, n_r.y, n_r.z);
-            else st_rec(rec_quad(nxt, seg + slot, REC_RAD), n_r);
-         }
-      }
-      if (want_light) st_stream(q_light + lslot, slot);  // the light ray leaves from the path's new position
-   };
+   // one path per lane (hit_shading.h shade_hit_path: the body k_primary_shade shares): `valid` lanes shade their hit; every lane of the
+   // wave takes part in the queue appends. pos_lit: the position in this bounce's queue (without the shard segment) | kSunLitBit
+   const HitShadeCtx hx{s_lut, s_mesh, s_tex, n_lds_mesh, n_lds_tex, seg, cur, nxt, q_next, n_next, q_light, n_light};
+   auto shade = [&](uint32_t id, uint32_t pos_lit, float4 hr, bool valid) { shade_hit_path<SLIM>(fp, sc, ps, hx, bounce, id, pos_lit, hr, valid); };
    // The bounce's RAY queue holds hits and misses (the traversal kernels build no hit / miss queues). Shading a wave of
    // queue entries as they come leaves the lanes of the misses idle through the whole material evaluation, so the hits
    // are first compacted inside the wave: their ids collect in a per-wave LDS list and are shaded 64 at a time.
@@ -871,6 +778,73 @@ __global__ __launch_bounds__(kBlock, kShadeHitBlocks) void k_shade_hit(FramePara
    if (n_missed) flush_misses(n_missed);
    // closest_hits: per-block sum, one atomic per block (n_hits is wave-uniform)
    if (lane_id() == 0 && n_hits) atomicAdd(&s_hits, n_hits);
+   __syncthreads();
+   if (threadIdx.x == 0 && s_hits) atomicAdd(&stats->closest_hits, (unsigned long long)s_hits);
+}
+
+// ------------------------------------------------------------------------------------------
+// primary_shade - bounce 0 of a pass whose primary rays need nothing stored (SamplePlan::fused_primary: camera grid, primary_implicit,
+// slim state, no pixel handed to the tree): k_generate, k_trace_camera_grid and k_shade_hit(0) in one kernel. A lane stands at its
+// path's pixel: the primary ray from the id (primary_state), the pixel's list (camera_list_walk: k_trace_camera_grid's walk), then a miss
+// goes to bounce 0's Q_MISS as (0, id) - k_shade_miss needs the id alone there - and a hit is shaded where it was found
+// (shade_hit_path: k_shade_hit's body). No id queue, no hit plane, no count of bounce 0's RAY queue: those only carried values from one
+// of the three kernels to the next. One wave per run of 64 consecutive path ids, as k_generate: the run's shard (shard_of_run) is
+// wave-uniform and every append of the wave goes to that shard's counters and segments. 97 % of the primary rays of the benchmark's
+// scenes hit, so the hits are shaded as they lie - no compaction across runs.
+// ------------------------------------------------------------------------------------------
+template <bool SLIM>
+__global__ __launch_bounds__(kBlock, kShadeHitBlocks) void k_primary_shade(FrameParams fp, SceneDev sc, PathState ps, Control* ctl, DeviceStats* stats, SunGridDev g) {
+   static_assert(SLIM, "the plan asks for this kernel under the slim state alone");
+   __shared__ float s_lut[256];
+   s_lut[threadIdx.x] = sc.unorm_lut[threadIdx.x];
+   __shared__ MeshShade s_mesh[kLdsMeshes];
+   __shared__ TexInfo s_tex[kLdsTextures];
+   const uint32_t n_lds_mesh = sc.num_meshes < kLdsMeshes ? sc.num_meshes : kLdsMeshes;
+   const uint32_t n_lds_tex = sc.num_textures < kLdsTextures ? sc.num_textures : kLdsTextures;
+   __shared__ uint32_t s_hits;
+   if (threadIdx.x == 0) s_hits = 0;
+   if (threadIdx.x < n_lds_mesh) s_mesh[threadIdx.x] = sc.meshes[threadIdx.x];
+   if (threadIdx.x < n_lds_tex) s_tex[threadIdx.x] = sc.textures[threadIdx.x];
+   __syncthreads();
+   const uint32_t n = fp.n_owned * fp.batch_frames;  // owned pixels x frames of the batch
+   const uint32_t lane = lane_id();
+   const uint32_t runs = (n + 63) / 64;
+   const float4* __restrict__ tris = sc.tris;
+   uint32_t n_hits = 0, n_tris = 0;  // n_hits: wave-uniform
+   for (uint32_t run = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); run < runs; run += gridDim.x * kWavesPerBlock) {
+      const uint32_t shard = __builtin_amdgcn_readfirstlane(shard_of_run(run));
+      const uint32_t seg = shard * ps.shard_cap;
+      const uint32_t id = run * 64u + lane;
+      const bool own = id < n;
+      float4 ro = make_float4(0, 0, 0, 0), rd = make_float4(0, 0, 0, 0);
+      float4 hr = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kEmptyRef));
+      if (own) {
+         primary_state(fp, id, ro, rd);
+         const uint32_t k = id % fp.n_owned;
+         const uint32_t pix = fp.owned_pixels ? fp.owned_pixels[k] : k;
+         const uint32_t px = pix % fp.W, py = pix / fp.W;
+         const uint32_t cell = (py + 1) * g.nx + (px + 1);
+         const uint32_t e = g.cell_start[cell], end = g.cell_start[cell + 1];
+         // (a list beyond max_walk is not sorted: walked whole. The plan sees to it that none is longer than k_trace_camera_grid would walk.)
+         const Hit best = camera_list_walk<false>(g, tris, e, end, end - e <= g.max_walk, v3(ro.x, ro.y, ro.z), v3(rd.x, rd.y, rd.z), n_tris);
+         hr = make_float4(best.t, best.u, best.v, __uint_as_float(best.idx));
+      }
+      const bool is_hit = __float_as_uint(hr.w) != kEmptyRef;
+      const bool is_miss = own && !is_hit;
+      if (__ballot(is_miss) != 0ull) {  // wave-uniform: every lane of the wave takes part in the append
+         const uint32_t slot = wave_append(&ctl->q_count[qc_index(0, Q_MISS, shard)], is_miss);
+         if (is_miss) st_stream(reinterpret_cast<uint2*>(ps.queue[4]) + seg + slot, make_uint2(0u, id));
+      }
+      const unsigned long long mask = __ballot(is_hit);
+      if (mask == 0ull) continue;
+      const HitShadeCtx hx{s_lut, s_mesh, s_tex, n_lds_mesh, n_lds_tex, seg, ps.set[0], ps.set[1], ps.queue[1] + seg, &ctl->q_count[qc_index(1, Q_RAY, shard)],
+                           ps.queue[2] + seg, &ctl->q_count[qc_index(0, Q_LIGHT, shard)]};
+      shade_hit_path<SLIM, true>(fp, sc, ps, hx, 0u, id, 0u, hr, is_hit, ro, rd);
+      n_hits += (uint32_t)__popcll(mask);
+   }
+   if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&stats->rays[UH_RAY_PRIMARY], (unsigned long long)n);
+   // closest_hits: per-block sum, one atomic per block
+   if (lane == 0 && n_hits) atomicAdd(&s_hits, n_hits);
    __syncthreads();
    if (threadIdx.x == 0 && s_hits) atomicAdd(&stats->closest_hits, (unsigned long long)s_hits);
 }
@@ -1029,6 +1003,10 @@ void launch_shade_miss(const LaunchCfg& c, const FrameParams& fp, const PathStat
 void launch_shade_hit(const LaunchCfg& c, const FrameParams& fp, const SceneDev& sc, const PathState& ps, const Images& im, Control* ctl,
                       DeviceStats* stats, uint32_t bounce) {
    as_constant(fp.slim_state != 0, [&](auto slim) { k_shade_hit<decltype(slim)::value><<<shade_grid(c, fp.W * fp.H), kBlock, 0, c.stream>>>(fp, sc, ps, ctl, stats, bounce); });
+}
+// bounce 0 of a pass with SamplePlan::fused_primary, in place of launch_generate, launch_trace_camera_grid and launch_shade_hit(0)
+void launch_primary_shade(const LaunchCfg& c, const FrameParams& fp, const SceneDev& sc, const PathState& ps, Control* ctl, DeviceStats* stats, const SunGridDev& g) {
+   k_primary_shade<true><<<stream_grid(c, fp.n_owned * fp.batch_frames), kBlock, 0, c.stream>>>(fp, sc, ps, ctl, stats, g);
 }
 // the sun rays of this bounce are the last of a pass with the slim state: they store the surviving paths' radiance themselves
 static bool final_sun_rays(const FrameParams& fp, uint32_t bounce) { return fp.slim_state != 0 && bounce + 1 == fp.num_bounces; }

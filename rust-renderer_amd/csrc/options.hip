@@ -10,7 +10,7 @@ using namespace uh;
 
 extern "C" {
 
-// The options (31): DESIGN.md section 7 has the table with defaults and what was measured. Variants that two rounds of measurements
+// The options (33): DESIGN.md section 7 has the table with defaults and what was measured. Variants that two rounds of measurements
 // left behind (batch traversal kernels, wave-per-tile primary rays, sub-frame interleave, the fused coarse-cover look-up, spatial
 // splits, insertion-based tree optimisation, the host-thread grid build) were removed in round 5 together with their options.
 int uh_set_option(uh_ctx* c, const char* name, int value) {
@@ -104,6 +104,10 @@ int uh_set_option(uh_ctx* c, const char* name, int value) {
       c->cam.cache.invalidate();
    } else if (n == "primary_implicit")
       c->primary_implicit = value != 0;  // 0: bounce 0's state planes are stored by k_generate even when the camera grid is in use
+   else if (n == "fused_primary")
+      // 1: where the plan allows it (frame_plan.h SamplePlan::fused_primary) bounce 0 is one kernel, k_primary_shade; 0: always k_generate,
+      // the camera-grid kernel and k_shade_hit(0). Same images
+      c->fused_primary = value != 0;
    // ---- what the frames compute
    else if (n == "full_frame_restir")
       c->full_frame_restir = value != 0;

@@ -17,8 +17,9 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 def report(d):
     f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
     rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))
-    # the last wavefront: everything from the last k_generate on
-    start = max(i for i, r in enumerate(rows) if "k_generate" in r["Kernel_Name"])
+    # the last wavefront: everything from the last k_generate on - or, where bounce 0 is one kernel (option "fused_primary"), from the
+    # last k_primary_shade on
+    start = max(i for i, r in enumerate(rows) if "k_generate" in r["Kernel_Name"] or "k_primary_shade" in r["Kernel_Name"])
     total = 0.0
     for r in rows[start:]:
         ns = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
