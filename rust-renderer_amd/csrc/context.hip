@@ -3,7 +3,8 @@
 // utopian::Renderer (utopian/src/renderer.rs) and utopian::Raytracing (utopian/src/raytracing.rs) for this path only.
 // struct uh_ctx is context_state.h; the path tracer's frames (uh_render_frame, uh_render_frames) are frame_loop.hip over the plan of
 // frame_plan.h; meshes, the tree builders and the refit are scene_build.hip; the hybrid and the forward graph
-// (uh_render_hybrid, uh_render_forward) are hybrid_graph.hip (its verbs hybrid_verbs.hip, its display chain post_graph.hip) and forward_graph.hip over raster_driver.hip, the denoiser denoise_graph.hip;
+// (uh_render_hybrid, uh_render_forward) are hybrid_graph.hip over the plan of hybrid_plan.h (its ray passes hybrid_ray_passes.hip, its
+// other verbs hybrid_verbs.hip, its display chain post_graph.hip) and forward_graph.hip over raster_driver.hip, the denoiser denoise_graph.hip;
 // the sun and camera grids' upkeep is grid_cache.hip; uh_set_option is options.hip; a frame split over several GPUs - the tile and band
 // partitions, the tile composition - is partition.hip, the RCCL link rccl_link.hip.
 #include <hip/hip_runtime.h>

@@ -1,7 +1,8 @@
 // context_state.h - struct uh_ctx and the types it is made of, for the files that implement the context: context.hip (lifetime,
 // read-backs, stats), frame_loop.hip (the path tracer's frames), options.hip (uh_set_option), partition.hip (the tile and band partitions of a multi-GPU frame, the
 // tile composition), rccl_link.hip (the RCCL link), scene_build.hip (meshes, builders, refit) and the graphs (raster_driver.hip,
-// hybrid_graph.hip, hybrid_verbs.hip, post_graph.hip, forward_graph.hip, denoise_graph.hip; what they share: graphs_internal.h). Private: not installed, not part of
+// hybrid_graph.hip, hybrid_ray_passes.hip, hybrid_verbs.hip, post_graph.hip, forward_graph.hip, denoise_graph.hip; what they share: graphs_internal.h; what a
+// uh_render_hybrid call reads of the context before it runs: hybrid_plan.h). Private: not installed, not part of
 // the C ABI (include/utopian_hip.h), where uh_ctx stays opaque. The upkeep of the sun and camera grids is grid_cache.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -443,7 +444,8 @@ struct uh_ctx {
    // the hybrid graph's passes (uh_render_hybrid): images, the metal-pixel queue and a copy of the scene's meshes as gbuffer.vert
    // reads them, all allocated by the first call. Every feature below names its buffers once, in a visitor f(buffer, length) over
    // n pixels that serves its first-use allocation and its destroy(): a group's last buffer is allocated last, its pointer says
-   // "allocated"; length 0: grown by the pass
+   // "allocated"; length 0: grown by the pass. A feature with timed stages of its own names them likewise, in a visitor stages(f) that
+   // serves their creation (graphs_internal.h first_use), the reset of their records and destroy()
    struct Hybrid {
       DevBuf<float4> pos, nrm, pbr;
       DevBuf<uchar4> alb, refl;
@@ -576,10 +578,13 @@ struct uh_ctx {
          uint32_t renders = 0, samples = 0;
          uint32_t order = 0;                   // option "rtgi_order" (rtgi.hip: how the trace kernel's work items are laid out)
          template <class F> void images(size_t n, F&& f) { f(counts, n), f(radiance, n), f(mean, n), f(queue, n), f(counters, 4); }
+         template <class F> void stages(F&& f) {
+            for (Stage& s : stage) f(s);
+         }
          void destroy() {
             images(0, ReleaseBuf{});
             rays.release(), sun_rays.release();
-            for (Stage& s : stage) s.destroy();
+            stages([](Stage& s) { s.destroy(); });
          }
       } gi;
 
@@ -595,10 +600,13 @@ struct uh_ctx {
          Stage stage[5];
          uint32_t renders = 0;
          template <class F> void images(size_t n, F&& f) { f(counts, n), f(scale, n), f(bias, n), f(mean_s, n), f(mean_b, n), f(re, n), f(queue, n), f(counters, 8); }
+         template <class F> void stages(F&& f) {
+            for (Stage& s : stage) f(s);
+         }
          void destroy() {
             images(0, ReleaseBuf{});
             rays.release(), orig.release(), dirs.release(), sun_rays.release(), ray_queue.release();
-            for (Stage& s : stage) s.destroy();
+            stages([](Stage& s) { s.destroy(); });
          }
       } gl;
 
@@ -614,9 +622,12 @@ struct uh_ctx {
          uint32_t renders = 0, steps = 0;
          uint32_t order = 2;                   // option "fog_order" (fog.hip: how the trace kernel's work items are laid out; 2 measured fastest)
          template <class F> void images(size_t n, F&& f) { f(mask, n), f(terms, n), f(dist, n), f(queue, n), f(counters, 6); }
+         template <class F> void stages(F&& f) {
+            for (Stage& s : stage) f(s);
+         }
          void destroy() {
             images(0, ReleaseBuf{});
-            for (Stage& s : stage) s.destroy();
+            stages([](Stage& s) { s.destroy(); });
          }
       } fog;
 
@@ -663,9 +674,12 @@ struct uh_ctx {
          uint32_t blocks = 0;                  // blocks of the last pass's grid
          bool last = false;                    // the last G-buffer pass enqueued had the bit (uh_denoise with UH_DENOISE_MOTION asks)
          template <class F> void images(size_t n, F&& f) { f(prev, 0), f(table, 0), f(image, n), f(counters, 2 * (size_t)kMaxBlocks); }
+         template <class F> void stages(F&& f) {
+            for (Stage& s : stage) f(s);
+         }
          void destroy() {
             images(0, ReleaseBuf{});
-            for (Stage& s : stage) s.destroy();
+            stages([](Stage& s) { s.destroy(); });
          }
       } mv;
 
@@ -684,9 +698,10 @@ struct uh_ctx {
          bool valid = false;
          uint32_t renders = 0;
          template <class F> void images(size_t n_, F&& f) { f(col[0], n_), f(col[1], n_), f(n[0], n_), f(n[1], n_), f(counters, (size_t)kTaaCounterSlots * kTaaCounterStride); }
+         template <class F> void stages(F&& f) { f(stage); }
          void destroy() {
             images(0, ReleaseBuf{});
-            stage.destroy();
+            stages([](Stage& s) { s.destroy(); });
          }
       } taa;
 
@@ -710,10 +725,13 @@ struct uh_ctx {
             for (uint32_t k = 1; k <= kPostMaxLevels; k++) f(down[k], post_level_texels(W, H, k)), f(up[k], post_level_texels(W, H, k));
             f(hist, (size_t)kPostBins), f(hist_copy, (size_t)kPostBins), f(rec, (size_t)1);
          }
+         template <class F> void stages(F&& f) {
+            for (Stage& s : stage) f(s);
+         }
          void destroy() {
             images(0, 0, ReleaseBuf{});
             input.release();
-            for (Stage& s : stage) s.destroy();
+            stages([](Stage& s) { s.destroy(); });
          }
       } post;
 

@@ -1,6 +1,7 @@
-// graphs_internal.h - what the host files of the graphs share (raster_driver.hip, hybrid_graph.hip, hybrid_verbs.hip, post_graph.hip,
-// forward_graph.hip, denoise_graph.hip): the timed stages, first-use allocation, the preamble of the stats verbs, the params setter and
-// the entry points of one file that another calls. Private, like context_state.h; nothing here is exported.
+// graphs_internal.h - what the host files of the graphs share (raster_driver.hip, hybrid_graph.hip, hybrid_ray_passes.hip, hybrid_verbs.hip,
+// post_graph.hip, forward_graph.hip, denoise_graph.hip): the timed stages, first-use allocation, the preamble of the stats verbs, the
+// params setter, what the passes of one uh_render_hybrid call share (HybridCall, over hybrid_plan.h's plan) and the entry points of one
+// file that another calls. Private, like context_state.h; nothing here is exported.
 #pragma once
 #include <cstring>
 #include <initializer_list>
@@ -8,6 +9,7 @@
 #include <type_traits>
 
 #include "context_state.h"
+#include "hybrid_plan.h"
 
 #pragma GCC visibility push(hidden)
 // ---- the timed stages of the graphs (context_state.h Stage) ----
@@ -67,6 +69,16 @@ template <class Visit> static int alloc_group(uh_ctx* c, Visit visit) {
       return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string("uh_render_hybrid: allocation: ") + hipGetErrorString(e));
    return UH_OK;
 }
+// A pass's first use, when `last` - its group's last buffer - is not there yet: the events of its stages (Pass::stages), then the
+// buffers `images` names (alloc_group)
+template <class Pass, class Images> static int first_use(uh_ctx* c, Pass& pass, const void* last, Images images) {
+   if (last) return UH_OK;
+   int st = UH_OK;
+   pass.stages([&](Stage& s) {
+      if (!st) st = stage_create(c, &s, 1);
+   });
+   return st ? st : alloc_group(c, images);
+}
 // b holds n elements or more: kept when it does, allocated again (its contents lost) when not
 template <class Buf> static int grow(uh_ctx* c, Buf& b, size_t n, const char* prefix) {
    if (b.p && b.n >= n) return UH_OK;
@@ -93,6 +105,12 @@ static bool stats_begin(uh_ctx* c, void* out, size_t bytes, const char* null_mes
 }
 
 // ---- the params verbs of the hybrid passes ----
+// uh_*_default_params of the pass type `Pass`: the params a context holds before the first uh_set_*_params (context_state.h states them once)
+template <class Pass, class P> static int default_params(P* out) {
+   if (!out) return UH_ERR_INVALID_ARGUMENT;
+   *out = Pass{}.params;
+   return UH_OK;
+}
 // uh_set_*_params of the pass `pass` (the member of uh_ctx::Hybrid that holds its `params`): a null context is UH_ERR_INVALID_ARGUMENT; null
 // params, or params in which `refusal` names a fault, that with "<verb>: null params" or "<verb>: <the fault>", the old ones staying.
 template <class P, class Pass> static int set_params(uh_ctx* c, const P* params, const char* verb, const char* (*refusal)(const P&), Pass uh_ctx::Hybrid::*pass) {
@@ -147,6 +165,16 @@ inline RtgiDev glass_sun_view(const GlassDev& gs) {
 }
 }  // namespace uh
 
+// ---- what the passes of one uh_render_hybrid call share ----
+struct HybridCall {
+   const HybridPlan& plan;
+   const UhViewUniformData& view;
+   const FrameParams& fp;
+   const LaunchCfg& lc;
+   const HybridDev& hd;
+   const HybridFrameDev& fd;
+};
+
 // ---- hybrid_graph.hip ----
 int hybrid_events(uh_ctx* c);          // the events of the hybrid stages and of wait_frames_in_flight (first hybrid or forward call)
 int wait_frames_in_flight(uh_ctx* c);  // c->stream (where the graphs run) waits for every other stream of the context
@@ -156,6 +184,23 @@ int hybrid_light_table(uh_ctx* c);     // the uh_add_light table as the lit pass
 // normalised direction, or null for a pass that reads none), and those of the final frame's passes
 HybridDev hybrid_dev(const uh_ctx* c, const UhViewUniformData& view, const float* sun);
 HybridFrameDev hybrid_frame_dev(const uh_ctx* c, const UhViewUniformData& view);
+
+// ---- hybrid_ray_passes.hip ----
+// the passes that cast rays from the G-buffer. *_alloc: the pass's first use (hybrid_prepare, when the plan has the pass); *_run: the pass
+// on c->stream, every stage between its two events (hybrid_passes, in the graph's order)
+int restir_lights_alloc(uh_ctx* c);  // and the light table, and the event behind the call's reads of the reservoirs
+HybridRestirDev restir_lights_dev(const uh_ctx* c, const UhViewUniformData& view);  // what the pass and the deferred pass behind it read
+int restir_lights_run(uh_ctx* c, const HybridCall& k, const HybridRestirDev& rl);
+int rtao_alloc(uh_ctx* c);
+int rtao_run(uh_ctx* c, const HybridCall& k);
+int rtgi_alloc(uh_ctx* c);  // and a record per ray of the params' samples
+int rtgi_run(uh_ctx* c, const HybridCall& k);
+int glossy_alloc(uh_ctx* c);  // and the per-ray buffers of the params' samples
+int glossy_run(uh_ctx* c, const HybridCall& k);
+int glass_alloc(uh_ctx* c);
+int glass_run(uh_ctx* c, const HybridCall& k);
+int fog_alloc(uh_ctx* c);
+int fog_run(uh_ctx* c, const HybridCall& k);
 
 // ---- post_graph.hip ----
 int post_alloc(uh_ctx* c);                                               // the display chain's images, counts and record (first post pass)

@@ -1,7 +1,8 @@
-// hybrid_graph.hip - uh_render_hybrid of include/utopian_hip.h: the plan of a call (which passes run, or why it is refused), first use
-// of what they need and the passes in their order; and what the forward graph and the denoiser share with it: the mesh and light
-// tables, the wait behind the frames in flight and destroy_graphs. The read, stats and params verbs are hybrid_verbs.hip, the HDR display
-// chain post_graph.hip. Host code over uh_ctx::Hybrid (context_state.h); the rasterised passes go through raster_driver.hip.
+// hybrid_graph.hip - uh_render_hybrid of include/utopian_hip.h: the context's facts for the plan of a call (hybrid_plan.h: which passes
+// run, or why it is refused), first use of what they need as a list of calls and the passes in their order; and what the forward graph
+// and the denoiser share with it: the mesh and light tables, the wait behind the frames in flight and destroy_graphs. The passes that
+// cast rays from the G-buffer - first use, run and verbs - are hybrid_ray_passes.hip, the other read, stats and params verbs
+// hybrid_verbs.hip, the HDR display chain post_graph.hip. Host code over uh_ctx::Hybrid (context_state.h); the rasterised passes go through raster_driver.hip.
 // Host-side counterpart of build_render_graph (utopian/src/renderers/mod.rs).
 #include <hip/hip_runtime.h>
 
@@ -294,10 +295,7 @@ static int render_mc_pass(uh_ctx* c, const LaunchCfg& lc, const UhViewUniformDat
 static int motion_prepare(uh_ctx* c, MotionDev& md) {
    uh_ctx::Hybrid& h = c->hy;
    const char* const who = "uh_render_hybrid: motion vectors";
-   if (!h.mv.counters.p) {
-      if (int st = stage_create(c, h.mv.stage, 2)) return st;
-      if (int st = alloc_group(c, [&](auto f) { h.mv.images((size_t)c->W * c->H, f); })) return st;
-   }
+   if (int st = first_use(c, h.mv, h.mv.counters.p, [&](auto f) { h.mv.images((size_t)c->W * c->H, f); })) return st;
    const size_t nm = c->meshes.size();
    if (int st = grow(c, h.mv.table, std::max<size_t>(1, nm), who)) return st;
    h.mv.rows.assign(nm, MotionMesh{});
@@ -385,280 +383,40 @@ static int render_gbuffer_raster(uh_ctx* c, const LaunchCfg& lc, const UhViewUni
 }
 
 // ---- uh_render_hybrid in four steps: plan, prepare, arguments, passes ----
-// What a call does, decided from the context, the view and the mask alone - no HIP call, no state changed: `code` other than UH_OK
-// with the message of the first rule the request breaks (the rules in the order utopian_hip.h gives them), or the passes that run
-// and the first-use groups they need
-struct HybridPlan {
-   int code;
-   const char* refusal;
-   bool raster, maps, render_maps, restir, rtao, rtgi, glossy, glass, fog, mc, motion, rt, taa, post;  // maps: the IBL maps exist for this call's consumers
-   bool deferred, frame, env;  // the deferred pass runs; the final frame's images and the IBL maps are needed
-   bool first, frame_first;    // the ray-traced images, the final frame's images are allocated by this call (and cleared)
-};
-static HybridPlan hybrid_plan(const uh_ctx& c, const UhViewUniformData& view, uint32_t mask) {
+// What hybrid_plan (hybrid_plan.h) decides a call from: the context's facts, read and nothing else
+static HybridFacts hybrid_facts(const uh_ctx& c) {
    const uh_ctx::Hybrid& h = c.hy;
-   HybridPlan p{};
-   const auto refuse = [&p](int code, const char* why) {
-      p.code = code, p.refusal = why;
-      return p;
-   };
-   p.raster = (mask & UH_HYBRID_GBUFFER_RASTER) != 0;
-   if (p.raster && !(mask & UH_HYBRID_GBUFFER))
-      return refuse(UH_ERR_INVALID_ARGUMENT,
-                  "uh_render_hybrid: UH_HYBRID_GBUFFER_RASTER without UH_HYBRID_GBUFFER (the bit chooses how the G-buffer pass runs); set both, "
-                  "or neither");
-   // the IBL maps exist for this call's consumers when an earlier call built them or this one does, before rt_reflections
-   p.maps = h.env.builds > 0 || (mask & UH_HYBRID_ENVIRONMENT);
-   if ((mask & UH_HYBRID_RT_REFLECTIONS) && view.ibl_enabled == 1 && !p.maps)
-      return refuse(UH_ERR_INVALID_ARGUMENT,
-                  "uh_render_hybrid: rt_reflections with view.ibl_enabled = 1 needs the IBL maps (irradiance, specular, BRDF LUT of ibl.rs), "
-                  "which are not part of this library until a call with UH_HYBRID_ENVIRONMENT builds them; set that bit, or ibl_enabled = 0 "
-                  "for the reflection pass's non-IBL branch");
-   p.render_maps = (mask & UH_HYBRID_SHADOW_MAPS) && view.shadows_enabled == 1;
-   if (p.render_maps && !h.sm.params_set)
-      return refuse(UH_ERR_INVALID_ARGUMENT,
-                  "uh_render_hybrid: UH_HYBRID_SHADOW_MAPS before uh_set_shadowmap_params (the cascades of uh_shadow_cascades or the caller's own)");
-   if (mask & UH_HYBRID_DEFERRED) {
-      if (view.shadows_enabled == 1 && !h.sm.size && !p.render_maps)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: the deferred pass with view.shadows_enabled = 1 needs the cascaded shadow maps (shadow.rs), which a call "
-                     "with UH_HYBRID_SHADOW_MAPS renders; set that bit, or shadows_enabled = 0 for the rt_shadows branch");
-      if (view.ibl_enabled == 1 && !p.maps)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: the deferred pass with view.ibl_enabled = 1 needs the IBL maps (irradiance, specular, BRDF LUT of ibl.rs), "
-                     "which a call with UH_HYBRID_ENVIRONMENT builds; set that bit, or ibl_enabled = 0 for the ambient term 0.03 * diffuse * occlusion");
-      if (view.num_lights > c.lights.size())
-         return refuse(UH_ERR_INVALID_ARGUMENT, "uh_render_hybrid: view.num_lights exceeds the lights added with uh_add_light");
-   }
-   if ((mask & UH_HYBRID_SKY) && view.cubemap_enabled == 1 && !p.maps)
-      return refuse(UH_ERR_INVALID_ARGUMENT,
-                  "uh_render_hybrid: the sky pass with view.cubemap_enabled = 1 needs the environment cube (ibl.rs), which a call with "
-                  "UH_HYBRID_ENVIRONMENT builds; set that bit, or cubemap_enabled = 0 for the IntegrateScattering branch");
-   // the reservoir lights: one shadow ray per pixel toward the light of its spatial reservoir, which the deferred pass then adds
-   p.restir = (mask & UH_HYBRID_RESTIR_LIGHTS) != 0;
-   if (p.restir) {
-      if (view.raytracing_supported != 1)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_RESTIR_LIGHTS casts shadow rays and view.raytracing_supported is not 1; set it, or clear the bit");
-      if (!(mask & UH_HYBRID_GBUFFER) && !h.gbuffer_done)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_RESTIR_LIGHTS casts its rays from the G-buffer, and no G-buffer has been rendered; set "
-                     "UH_HYBRID_GBUFFER");
-      if (!c.restir_recorded)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_RESTIR_LIGHTS reads the spatial reservoirs, and no reservoir pass has run on this context; "
-                     "render a frame with UH_PASS_RESTIR (same camera) first");
-      if (c.bands.world > 1)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_RESTIR_LIGHTS needs the whole frame's reservoirs, and a row partition with world > 1 is set "
-                     "(uh_set_restir_partition)");
-   }
-   // ray-traced ambient occlusion takes the SSAO slot: short hemisphere rays from the G-buffer instead of ssao.frag
-   p.rtao = (mask & UH_HYBRID_RTAO) && view.ssao_enabled == 1;
-   if (p.rtao) {
-      if (view.raytracing_supported != 1)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_RTAO casts occlusion rays and view.raytracing_supported is not 1; set it, or clear the bit");
-      if (!(mask & UH_HYBRID_GBUFFER) && !h.gbuffer_done)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_RTAO casts its rays from the G-buffer, and no G-buffer has been rendered; set UH_HYBRID_GBUFFER");
-      if ((uint64_t)c.W * c.H * 64u >= (1ull << 32))
-         return refuse(UH_ERR_CAPACITY, "uh_render_hybrid: UH_HYBRID_RTAO: a frame of 2^26 pixels or more (its rays are numbered in 32 bits)");
-   }
-   // setup_marching_cubes_pass (mod.rs:164): only with the checkbox on
-   p.mc = (mask & UH_HYBRID_MARCHING_CUBES) && view.marching_cubes_enabled == 1;
-   if (p.mc) {
-      if (!(mask & UH_HYBRID_GBUFFER) && !h.gbuffer_done)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: the marching-cubes pass depth-tests against the G-buffer's depth, and no G-buffer has been rendered; "
-                     "set UH_HYBRID_GBUFFER, or marching_cubes_enabled = 0");
-      if (c.meshes.empty())
-         return refuse(UH_ERR_INVALID_ARGUMENT, "uh_render_hybrid: the marching-cubes pass shades with the first mesh's material (mesh_index 0), and the scene has no mesh");
-      if (view.shadows_enabled == 1 && !h.sm.size && !p.render_maps)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: the marching-cubes pass with view.shadows_enabled = 1 needs the cascaded shadow maps (shadow.rs), which a "
-                     "call with UH_HYBRID_SHADOW_MAPS renders; set that bit, or shadows_enabled = 0");
-      if (view.num_lights > c.lights.size())
-         return refuse(UH_ERR_INVALID_ARGUMENT, "uh_render_hybrid: the marching-cubes pass: view.num_lights exceeds the lights added with uh_add_light");
-   }
-   // motion vectors: a modifier of the G-buffer pass, ignored without it
-   p.motion = (mask & UH_HYBRID_MOTION) && (mask & UH_HYBRID_GBUFFER);
-   // temporal anti-aliasing: the resolve between the sky pass and present, over the G-buffer the call leaves
-   p.taa = (mask & UH_HYBRID_TAA) != 0;
-   if (p.taa) {
-      if (!(mask & UH_HYBRID_GBUFFER) && !h.gbuffer_done)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_TAA reprojects the G-buffer's positions, and no G-buffer has been rendered; set UH_HYBRID_GBUFFER");
-      if ((h.taa.params.flags & UH_TAA_MOTION) && !((mask & UH_HYBRID_GBUFFER) ? p.motion : h.mv.last))
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_TAA with UH_TAA_MOTION reads the motion image, and the last G-buffer pass had no UH_HYBRID_MOTION; "
-                     "set UH_HYBRID_GBUFFER | UH_HYBRID_MOTION, or clear the flag (uh_set_taa_params)");
-   }
-   // the HDR display chain: between the taa pass and present, over whatever the call leaves in its source; it refuses nothing
-   p.post = (mask & UH_HYBRID_POST) != 0;
-   // one-bounce diffuse GI: hemisphere rays from the G-buffer, shaded at their hits, added to what the deferred pass of this call wrote
-   p.rtgi = (mask & UH_HYBRID_RTGI) != 0;
-   if (p.rtgi) {
-      if (view.raytracing_supported != 1)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_RTGI casts rays and view.raytracing_supported is not 1; set it, or clear the bit");
-      if (!(mask & UH_HYBRID_GBUFFER) && !h.gbuffer_done)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_RTGI casts its rays from the G-buffer, and no G-buffer has been rendered; set UH_HYBRID_GBUFFER");
-      if (view.ibl_enabled == 1)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_RTGI with view.ibl_enabled = 1: the IBL ambient term and this pass would both count the sky; "
-                     "set ibl_enabled = 0, or clear the bit");
-      if (!(mask & UH_HYBRID_DEFERRED))
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_RTGI without UH_HYBRID_DEFERRED in the same call: the pass adds to what the deferred pass "
-                     "writes and has nothing to add to; set UH_HYBRID_DEFERRED");
-      if ((uint64_t)c.W * c.H * 16u >= (1ull << 32))
-         return refuse(UH_ERR_CAPACITY, "uh_render_hybrid: UH_HYBRID_RTGI: a frame of 2^28 pixels or more (its rays are numbered in 32 bits)");
-   }
-   // glossy reflections: rays drawn around the mirror direction by the pixel's roughness, shaded at their hits, added behind the rtgi pass
-   p.glossy = (mask & UH_HYBRID_GLOSSY) != 0;
-   if (p.glossy) {
-      if (view.raytracing_supported != 1)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_GLOSSY casts rays and view.raytracing_supported is not 1; set it, or clear the bit");
-      if (!(mask & UH_HYBRID_GBUFFER) && !h.gbuffer_done)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_GLOSSY casts its rays from the G-buffer, and no G-buffer has been rendered; set UH_HYBRID_GBUFFER");
-      if (view.ibl_enabled == 1)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_GLOSSY with view.ibl_enabled = 1: the IBL specular term and this pass would both count the sky; "
-                     "set ibl_enabled = 0, or clear the bit");
-      if (!(mask & UH_HYBRID_DEFERRED))
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_GLOSSY without UH_HYBRID_DEFERRED in the same call: the pass adds to what the deferred pass "
-                     "writes and has nothing to add to; set UH_HYBRID_DEFERRED");
-      if ((uint64_t)c.W * c.H * 16u >= (1ull << 32))
-         return refuse(UH_ERR_CAPACITY, "uh_render_hybrid: UH_HYBRID_GLOSSY: a frame of 2^28 pixels or more (its rays are numbered in 32 bits)");
-   }
-   // volumetric fog: sun rays from samples along every pixel's view ray, composited behind the sky pass
-   p.fog = (mask & UH_HYBRID_FOG) != 0;
-   if (p.fog) {
-      if (view.raytracing_supported != 1)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_FOG casts sun rays and view.raytracing_supported is not 1; set it, or clear the bit");
-      if (!(mask & UH_HYBRID_GBUFFER) && !h.gbuffer_done)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_FOG marches to the G-buffer's positions, and no G-buffer has been rendered; set UH_HYBRID_GBUFFER");
-      if (!(mask & UH_HYBRID_DEFERRED) || !(mask & UH_HYBRID_SKY))
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_FOG without UH_HYBRID_DEFERRED and UH_HYBRID_SKY in the same call: the pass attenuates what "
-                     "those two write and has nothing to attenuate; set both");
-      if (mask & UH_HYBRID_MARCHING_CUBES)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_FOG with UH_HYBRID_MARCHING_CUBES in the same call: the marching-cubes pass's pixels are not "
-                     "in the G-buffer the fog marches to; clear one of the two bits");
-      if ((uint64_t)c.W * c.H * 64u >= (1ull << 32))
-         return refuse(UH_ERR_CAPACITY, "uh_render_hybrid: UH_HYBRID_FOG: a frame of 2^26 pixels or more (its rays are numbered in 32 bits)");
-   }
-   // ray-traced glass: two chains of rays per dielectric pixel, which replace what the passes before wrote there
-   p.glass = (mask & UH_HYBRID_GLASS) != 0;
-   if (p.glass) {
-      if (view.raytracing_supported != 1)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_GLASS casts rays and view.raytracing_supported is not 1; set it, or clear the bit");
-      if (!(mask & UH_HYBRID_GBUFFER) && !h.gbuffer_done)
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_GLASS casts its rays from the G-buffer, and no G-buffer has been rendered; set UH_HYBRID_GBUFFER");
-      if (!(mask & UH_HYBRID_DEFERRED))
-         return refuse(UH_ERR_INVALID_ARGUMENT,
-                     "uh_render_hybrid: UH_HYBRID_GLASS without UH_HYBRID_DEFERRED in the same call: the pass replaces what the deferred pass "
-                     "writes on dielectric pixels and has nothing to write into; set UH_HYBRID_DEFERRED");
-      if ((uint64_t)c.W * c.H >= (1ull << 27))
-         return refuse(UH_ERR_CAPACITY, "uh_render_hybrid: UH_HYBRID_GLASS: a frame of 2^27 pixels or more (its rays are numbered in 32 bits)");
-   }
-   p.rt = view.raytracing_supported != 0;
-   p.deferred = (mask & UH_HYBRID_DEFERRED) != 0;
-   p.frame = (mask & (UH_HYBRID_SSAO | UH_HYBRID_DEFERRED | UH_HYBRID_SKY | UH_HYBRID_PRESENT)) || p.mc || p.rtao || p.taa || p.post;
-   p.env = (mask & UH_HYBRID_ENVIRONMENT) != 0;
-   p.first = !h.counter.p;
-   p.frame_first = p.frame && !h.sky_counter.p;
-   return p;
+   HybridFacts f{};
+   f.W = c.W, f.H = c.H, f.world = c.bands.world;
+   f.lights = c.lights.size();
+   f.has_mesh = !c.meshes.empty(), f.restir_recorded = c.restir_recorded;
+   f.maps_built = h.env.builds > 0;
+   f.cascades_set = h.sm.params_set, f.cascades_rendered = h.sm.size != 0;
+   f.gbuffer_done = h.gbuffer_done, f.motion_last = h.mv.last;
+   f.taa_flags = h.taa.params.flags;
+   f.rt_images = h.counter.p != nullptr, f.frame_images = h.sky_counter.p != nullptr;
+   return f;
 }
 
 // First use: the groups the plan asks for, each allocated once (its last buffer says so), and the mesh and light tables
 static int hybrid_prepare(uh_ctx* c, const HybridPlan& p) {
    uh_ctx::Hybrid& h = c->hy;
    const size_t pixels = (size_t)c->W * c->H;
-   if (int st = hybrid_alloc(c)) return st;
-   if (int st = hybrid_tables(c)) return st;
-   if (p.raster && !h.gr.target.covered.p)
-      if (int st = alloc_group(c, [&](auto f) { h.gr.images(pixels, f); })) return st;
-   if (p.frame) {
-      if (int st = hybrid_frame_alloc(c)) return st;
-      if (p.deferred || p.mc)
-         if (int st = hybrid_light_table(c)) return st;
-   }
-   if (p.mc && !h.mc.target.covered.p)
-      if (int st = alloc_group(c, [&](auto f) { h.mc.images(pixels, f); })) return st;
-   if (p.restir) {
-      if (int st = hybrid_light_table(c)) return st;
-      if (!h.rl.read) HIP_TRY(c, hipEventCreateWithFlags(&h.rl.read, hipEventDisableTiming));
-      if (!h.rl.counters.p) {
-         if (int st = alloc_group(c, [&](auto f) { h.rl.images(pixels, f); })) return st;
-         HIP_TRY(c, hipMemsetAsync(h.rl.vis.p, 0, pixels, c->stream));
-         HIP_TRY(c, hipMemsetAsync(h.rl.counters.p, 0, 2 * sizeof(uint32_t), c->stream));
-      }
-   }
-   if (p.rtao && !h.ao.counters.p) {
-      if (int st = alloc_group(c, [&](auto f) { h.ao.images(pixels, f); })) return st;
-      HIP_TRY(c, hipMemsetAsync(h.ao.counts.p, 0, h.ao.counts.n, c->stream));
-   }
-   if (p.rtgi) {
-      uh_ctx::Hybrid::Rtgi& gi = h.gi;
-      if (!gi.counters.p) {
-         if (int st = stage_create(c, gi.stage, 4)) return st;
-         if (int st = alloc_group(c, [&](auto f) { gi.images(pixels, f); })) return st;
-      }
-      // a record per ray: kept while they hold this pass's rays, else allocated again (the stream is waited for first: a pass in flight
-      // may still use the old ones)
-      const size_t rays = pixels * gi.params.samples;
-      if (gi.rays.n < rays || gi.sun_rays.n < rays) {
-         HIP_TRY(c, hipStreamSynchronize(c->stream));
-         for (int st : {grow(c, gi.rays, rays, "uh_render_hybrid: UH_HYBRID_RTGI"), grow(c, gi.sun_rays, rays, "uh_render_hybrid: UH_HYBRID_RTGI")})
-            if (st) return st;
-      }
-   }
-   if (p.glossy) {
-      uh_ctx::Hybrid::Glossy& gl = h.gl;
-      const char* const who = "uh_render_hybrid: UH_HYBRID_GLOSSY";
-      if (!gl.counters.p) {
-         if (int st = stage_create(c, gl.stage, 5)) return st;
-         if (int st = alloc_group(c, [&](auto f) { gl.images(pixels, f); })) return st;
-      }
-      // the per-ray buffers, as the rtgi pass keeps its own
-      const size_t rays = pixels * gl.params.samples;
-      if (gl.rays.n < rays || gl.orig.n < rays || gl.dirs.n < rays || gl.sun_rays.n < rays || gl.ray_queue.n < rays) {
-         HIP_TRY(c, hipStreamSynchronize(c->stream));
-         for (int st : {grow(c, gl.rays, rays, who), grow(c, gl.orig, rays, who), grow(c, gl.dirs, rays, who), grow(c, gl.sun_rays, rays, who),
-                        grow(c, gl.ray_queue, rays, who)})
-            if (st) return st;
-      }
-   }
-   if (p.glass && !h.glass.counters.p) {
-      uh_ctx::Hybrid::Glass& gs = h.glass;
-      for (int st : {stage_create(c, gs.trace, kGlassMaxEvents), stage_create(c, gs.bend, kGlassMaxEvents), stage_create(c, &gs.shadow, 1),
-                     stage_create(c, &gs.composite, 1)})
-         if (st) return st;
-      if (int st = alloc_group(c, [&](auto f) { gs.images(pixels, f); })) return st;
-   }
-   if (p.fog && !h.fog.counters.p) {
-      if (int st = stage_create(c, h.fog.stage, 3)) return st;
-      if (int st = alloc_group(c, [&](auto f) { h.fog.images(pixels, f); })) return st;
-   }
-   if (p.env)
-      if (int st = env_alloc(c)) return st;
-   if (p.taa && !h.taa.counters.p) {
-      if (int st = stage_create(c, &h.taa.stage, 1)) return st;
-      if (int st = alloc_group(c, [&](auto f) { h.taa.images(pixels, f); })) return st;
-   }
-   if (p.post)
-      if (int st = post_alloc(c)) return st;
+   int st = UH_OK;
+   if ((st = hybrid_alloc(c)) || (st = hybrid_tables(c))) return st;
+   if (p.raster && !h.gr.target.covered.p && (st = alloc_group(c, [&](auto f) { h.gr.images(pixels, f); }))) return st;
+   if (p.frame && (st = hybrid_frame_alloc(c))) return st;
+   if (p.frame && (p.deferred || p.mc) && (st = hybrid_light_table(c))) return st;
+   if (p.mc && !h.mc.target.covered.p && (st = alloc_group(c, [&](auto f) { h.mc.images(pixels, f); }))) return st;
+   if (p.restir && (st = restir_lights_alloc(c))) return st;
+   if (p.rtao && (st = rtao_alloc(c))) return st;
+   if (p.rtgi && (st = rtgi_alloc(c))) return st;
+   if (p.glossy && (st = glossy_alloc(c))) return st;
+   if (p.glass && (st = glass_alloc(c))) return st;
+   if (p.fog && (st = fog_alloc(c))) return st;
+   if (p.env && (st = env_alloc(c))) return st;
+   if (p.taa && (st = first_use(c, h.taa, h.taa.counters.p, [&](auto f) { h.taa.images(pixels, f); }))) return st;
+   if (p.post && (st = post_alloc(c))) return st;
    return UH_OK;
 }
 
@@ -713,26 +471,14 @@ static void reset_stage_records(uh_ctx::Hybrid& h, const HybridPlan& p, uint32_t
       for (int k = 0; k < kHybridPasses; k++) h.stage[k].ran = false;
    if (mask & UH_HYBRID_SHADOW_MAPS) h.stage[kStShadowMaps].ran = false;
    if (mask & UH_HYBRID_MARCHING_CUBES) h.stage[kStMarchingCubes].ran = false;
+   const auto not_run = [](Stage& s) { s.ran = false; };
    if (p.restir) h.stage[kStRestirLights].ran = false;
    if (p.rtao) h.stage[kStRtaoTrace].ran = h.stage[kStRtaoFilter].ran = false;
-   if (p.rtgi)
-      for (Stage& s : h.gi.stage) s.ran = false;
-   if (p.glossy)
-      for (Stage& s : h.gl.stage) s.ran = false;
-   if (p.glass) h.glass.stages([](Stage& s) { s.ran = false; });
-   if (p.fog)
-      for (Stage& s : h.fog.stage) s.ran = false;
+   if (p.rtgi) h.gi.stages(not_run);
+   if (p.glossy) h.gl.stages(not_run);
+   if (p.glass) h.glass.stages(not_run);
+   if (p.fog) h.fog.stages(not_run);
 }
-
-// what the passes of one call share
-struct HybridCall {
-   const HybridPlan& plan;
-   const UhViewUniformData& view;
-   const FrameParams& fp;
-   const LaunchCfg& lc;
-   const HybridDev& hd;
-   const HybridFrameDev& fd;
-};
 
 // the G-buffer pass: cast or rasterised, with the motion pass (`plan.motion`) on its hit records and the snapshot behind it
 static int gbuffer_pass(uh_ctx* c, const HybridCall& k) {
@@ -741,7 +487,7 @@ static int gbuffer_pass(uh_ctx* c, const HybridCall& k) {
    MotionDev md{};
    if (motion) {
       h.mv.last = false;  // until this pass and its snapshot are enqueued
-      h.mv.stage[0].ran = h.mv.stage[1].ran = false;
+      h.mv.stages([](Stage& s) { s.ran = false; });
       if (int st = motion_prepare(c, md)) return st;
    }
    // the camera grid when the path tracer's is built for this camera and geometry (read only: the grid's state is the path tracer's)
@@ -786,122 +532,6 @@ static int environment_pass(uh_ctx* c, const HybridCall& k) {
    for (int s = 0; s < 4; s++)
       if (int st = timed(c, h.stage[kStEnvCube + s], [&] { build[s](k.lc, e); })) return st;
    h.env.builds++;
-   return UH_OK;
-}
-
-// the rtao pass in ssao_pass's place: classify + trace into the counts, then the resolve / filter into ssao_output
-static int rtao_pass(uh_ctx* c, const HybridCall& k) {
-   uh_ctx::Hybrid& h = c->hy;
-   const UhRtaoParams& p = h.ao.params;
-   const RtaoDev ao{h.ao.counts.p, h.ao.queue.p, h.ao.counters.p, p.samples, k.fp.frame_number * 64u, p.blur_radius, p.radius, p.strength, p.blur_normal_cos, p.blur_plane};
-   int st = timed(c, h.stage[kStRtaoTrace], [&] {
-      HIP_TRY(c, hipMemsetAsync(h.ao.counters.p, 0, 6 * sizeof(uint32_t), c->stream));
-      LaunchCfg ac = k.lc;
-      ac.count_visits = c->count_visits;  // into the pass's own counters (uh_get_rtao_visits), never UhStats
-      launch_rtao_trace(ac, c->scene, k.hd, ao, h.ao.order);
-      return (int)UH_OK;
-   });
-   if (st) return st;
-   if ((st = timed(c, h.stage[kStRtaoFilter], [&] { launch_rtao_resolve(k.lc, k.hd, ao, h.ssao.p); }))) return st;
-   h.ao.samples = p.samples;
-   h.ao.renders++;
-   return UH_OK;
-}
-
-// the rtgi pass behind deferred_pass: classify + closest-hit walk (which shades the rays and queues the sun rays), the sun rays' any-hit
-// walk, the per-pixel mean + filter into the radiance image, then the composite into deferred_output; a stage each
-static int rtgi_pass(uh_ctx* c, const HybridCall& k) {
-   uh_ctx::Hybrid::Rtgi& g = c->hy.gi;
-   const UhRtgiParams& p = g.params;
-   const RtgiDev gi{g.counts.p, g.radiance.p, g.mean.p, g.rays.p, g.sun_rays.p, g.queue.p, g.counters.p, p.samples, k.fp.frame_number * 64u,
-                    p.blur_radius, p.max_radiance, p.intensity, p.blur_normal_cos, p.blur_plane};
-   int st = timed(c, g.stage[0], [&] {
-      HIP_TRY(c, hipMemsetAsync(g.counters.p, 0, g.counters.n * sizeof(uint32_t), c->stream));
-      launch_rtgi_trace(k.lc, c->scene, k.hd, gi, g.order);
-      return (int)UH_OK;
-   });
-   if (st) return st;
-   if ((st = timed(c, g.stage[1], [&] { launch_rtgi_shadow(k.lc, c->scene, k.hd, gi); }))) return st;
-   if ((st = timed(c, g.stage[2], [&] { launch_rtgi_filter(k.lc, k.hd, gi); }))) return st;
-   if ((st = timed(c, g.stage[3], [&] { launch_rtgi_composite(k.lc, c->scene, k.hd, k.fd, gi); }))) return st;
-   g.samples = p.samples;
-   g.renders++;
-   return UH_OK;
-}
-
-// the glossy pass behind the rtgi pass (behind deferred_pass without it): classify + ray generation + the closest-hit walk into hit
-// records, the streaming shade (which queues the sun rays), the sun rays' any-hit walk (k_rtgi_shadow on this pass's buffers), the
-// per-pixel sums + filter into the two images, then the composite into deferred_output; a stage each
-static int glossy_pass(uh_ctx* c, const HybridCall& k) {
-   uh_ctx::Hybrid::Glossy& g = c->hy.gl;
-   const UhGlossyParams& p = g.params;
-   const GlossyDev gl{g.counts.p, g.scale.p, g.bias.p, g.mean_s.p, g.mean_b.p, g.re.p, g.rays.p, g.orig.p, g.dirs.p, g.sun_rays.p, g.ray_queue.p, g.queue.p,
-                      g.counters.p, p.samples, k.fp.frame_number * 64u, p.blur_radius, k.fd.rt_on, p.max_roughness, p.max_radiance, p.intensity,
-                      p.blur_roughness, p.blur_normal_cos, p.blur_plane};
-   int st = timed(c, g.stage[0], [&] {
-      HIP_TRY(c, hipMemsetAsync(g.counters.p, 0, g.counters.n * sizeof(uint32_t), c->stream));
-      launch_glossy_trace(k.lc, c->scene, k.hd, gl);
-      return (int)UH_OK;
-   });
-   if (st) return st;
-   if ((st = timed(c, g.stage[1], [&] { launch_glossy_shade(k.lc, c->scene, k.hd, gl); }))) return st;
-   if ((st = timed(c, g.stage[2], [&] { launch_rtgi_shadow(k.lc, c->scene, k.hd, glossy_sun_view(gl)); }))) return st;
-   if ((st = timed(c, g.stage[3], [&] { launch_glossy_filter(k.lc, k.hd, gl); }))) return st;
-   if ((st = timed(c, g.stage[4], [&] { launch_glossy_composite(k.lc, c->scene, k.hd, k.fd, gl); }))) return st;
-   g.renders++;
-   return UH_OK;
-}
-
-// the glass pass behind the glossy pass (behind the rtgi pass or deferred_pass without it): classify + the first event, then max_events
-// rounds of the closest-hit walk and the bend kernel - every kernel takes its count from that round's device counter, the two ray queues
-// swap, nothing is read back and nothing is waited for -, the sun rays' any-hit walk (k_rtgi_shadow on this pass's buffers) and the
-// composite, which replaces deferred_output.rgb on the pixels that cast. A stage per round's walk and bend (trace[0] holds the raygen).
-static int glass_pass(uh_ctx* c, const HybridCall& k) {
-   uh_ctx::Hybrid::Glass& g = c->hy.glass;
-   const UhGlassParams& p = g.params;
-   const GlassDev gs{g.counts.p, g.radiance.p, g.events.p, g.rays.p, g.orig.p, g.dirs.p, g.sun_rays.p, {g.ray_queue[0].p, g.ray_queue[1].p}, g.queue.p,
-                     g.counters.p, p.max_events, p.max_radiance, p.intensity};
-   const uint64_t most = (uint64_t)k.hd.W * k.hd.H * 2u;
-   int st = UH_OK;
-   for (uint32_t round = 0; round < p.max_events; round++) {
-      st = timed(c, g.trace[round], [&] {
-         if (round == 0) {
-            HIP_TRY(c, hipMemsetAsync(g.counters.p, 0, g.counters.n * sizeof(uint32_t), c->stream));
-            launch_glass_raygen(k.lc, c->scene, k.hd, gs);
-         }
-         launch_glossy_walk(k.lc, c->scene, glass_walk_view(gs, round), most);
-         return (int)UH_OK;
-      });
-      if (st) return st;
-      if ((st = timed(c, g.bend[round], [&] { launch_glass_bend(k.lc, c->scene, k.hd, gs, round); }))) return st;
-   }
-   if ((st = timed(c, g.shadow, [&] { launch_rtgi_shadow(k.lc, c->scene, k.hd, glass_sun_view(gs)); }))) return st;
-   if ((st = timed(c, g.composite, [&] { launch_glass_composite(k.lc, k.hd, k.fd, gs); }))) return st;
-   g.rounds = p.max_events;
-   g.renders++;
-   return UH_OK;
-}
-
-// the fog pass behind atmosphere_pass: classify + the any-hit walk of the samples' sun rays into the bit masks, the resolve / filter into
-// the terms image, then the composite into deferred_output; a stage each
-static int fog_pass(uh_ctx* c, const HybridCall& k) {
-   uh_ctx::Hybrid::Fog& g = c->hy.fog;
-   const UhFogParams& p = g.params;
-   const FogDev fg{g.mask.p, g.terms.p, g.dist.p, g.queue.p, g.counters.p, p.steps, (k.fp.frame_number * 64u) ^ kFogSeedXor, p.blur_radius,
-                   p.density, p.max_distance, p.anisotropy, p.intensity, p.blur_depth, {p.albedo[0], p.albedo[1], p.albedo[2]},
-                   {p.ambient[0], p.ambient[1], p.ambient[2]}};
-   int st = timed(c, g.stage[0], [&] {
-      HIP_TRY(c, hipMemsetAsync(g.counters.p, 0, g.counters.n * sizeof(uint32_t), c->stream));
-      LaunchCfg fc = k.lc;
-      fc.count_visits = c->count_visits;  // into the pass's own counters, never UhStats
-      launch_fog_trace(fc, k.fp, c->scene, k.hd, fg, g.order);
-      return (int)UH_OK;
-   });
-   if (st) return st;
-   if ((st = timed(c, g.stage[1], [&] { launch_fog_resolve(k.lc, k.hd, fg); }))) return st;
-   if ((st = timed(c, g.stage[2], [&] { launch_fog_composite(k.lc, k.fp, k.hd, k.fd, fg); }))) return st;
-   g.steps = p.steps;
-   g.renders++;
    return UH_OK;
 }
 
@@ -964,20 +594,10 @@ static int hybrid_passes(uh_ctx* c, const HybridCall& k, uint32_t mask) {
       });
       if (st) return st;
    }
-   // restir_lights: the pixels' reservoirs (whatever the last reservoir pass left: read only) and this call's light count
-   const HybridRestirDev rl{h.rl.vis.p, h.rl.queue.p, h.rl.counters.p, c->im.reservoirs[2], h.raw_lights.p,
-                            (uint32_t)std::min<size_t>(view.num_lights, c->lights.size())};
-   if (p.restir) {
-      st = timed(c, h.stage[kStRestirLights], [&] {
-         HIP_TRY(c, hipMemsetAsync(h.rl.counters.p, 0, 2 * sizeof(uint32_t), c->stream));
-         launch_hybrid_restir_lights(lc, k.fp, c->scene, hd, rl);
-         return (int)UH_OK;
-      });
-      if (st) return st;
-      h.rl.renders++;
-   }
+   const HybridRestirDev rl = restir_lights_dev(c, view);
+   if (p.restir && (st = restir_lights_run(c, k, rl))) return st;
    if (p.rtao) {
-      if ((st = rtao_pass(c, k))) return st;
+      if ((st = rtao_run(c, k))) return st;
    } else if ((mask & UH_HYBRID_SSAO) && view.ssao_enabled == 1) {
       if ((st = timed(c, h.stage[kStSsao], [&] { launch_hybrid_ssao(lc, hd, fd); }))) return st;
    }
@@ -988,9 +608,9 @@ static int hybrid_passes(uh_ctx* c, const HybridCall& k, uint32_t mask) {
       });
       if (st) return st;
    }
-   if (p.rtgi && (st = rtgi_pass(c, k))) return st;
-   if (p.glossy && (st = glossy_pass(c, k))) return st;
-   if (p.glass && (st = glass_pass(c, k))) return st;
+   if (p.rtgi && (st = rtgi_run(c, k))) return st;
+   if (p.glossy && (st = glossy_run(c, k))) return st;
+   if (p.glass && (st = glass_run(c, k))) return st;
    h.frame_lights = h.stage[kStDeferred].ran ? (p.restir ? 2 : view.num_lights + 1) : 0;  // with the reservoir lights: the sun and the reservoir's
    if (p.restir) {
       // a reservoir pass enqueued after this call starts behind the call's reads (the spatial ring comes round to the slot read here)
@@ -1006,7 +626,7 @@ static int hybrid_passes(uh_ctx* c, const HybridCall& k, uint32_t mask) {
       });
       if (st) return st;
    }
-   if (p.fog && (st = fog_pass(c, k))) return st;
+   if (p.fog && (st = fog_run(c, k))) return st;
    if (p.taa && (st = taa_pass(c, k))) return st;
    HybridFrameDev pd = fd;  // present's source: taa_output when the taa pass ran in this call
    if (p.taa) pd.deferred = h.taa.col[h.taa.cur].p;
@@ -1022,7 +642,7 @@ static int hybrid_passes(uh_ctx* c, const HybridCall& k, uint32_t mask) {
 int uh_render_hybrid(uh_ctx* c, const UhViewUniformData* view, uint32_t mask) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    if (!view) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_render_hybrid: null view");
-   const HybridPlan plan = hybrid_plan(*c, *view, mask);
+   const HybridPlan plan = hybrid_plan(hybrid_facts(*c), *view, mask);
    if (plan.code != UH_OK) return fail(c, plan.code, plan.refusal);
    if (!c->built && c->topology_valid && view->rebuild_tlas == 1)
       if (int st = uh_refit_acceleration(c)) return st;

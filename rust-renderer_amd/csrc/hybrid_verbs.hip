@@ -1,7 +1,7 @@
 // hybrid_verbs.hip - what a caller reads from and sets on the hybrid graph between uh_render_hybrid calls (include/utopian_hip.h): the
-// images and IBL maps (uh_read_hybrid, uh_read_environment), every pass's stats, the params of the rtao, rtgi, glossy, glass, fog and taa passes, the
-// taa history reset and jitter. Host code over uh_ctx::Hybrid (context_state.h); nothing here touches the pass order
-// (hybrid_graph.hip). The HDR display chain's verbs are in post_graph.hip.
+// images and IBL maps (uh_read_hybrid, uh_read_environment), the frame, hybrid, motion, taa, marching-cubes, raster and environment
+// stats, the taa params, history reset and jitter. Host code over uh_ctx::Hybrid (context_state.h); nothing here touches the pass order
+// (hybrid_graph.hip). The verbs of the passes that cast rays are in hybrid_ray_passes.hip, the HDR display chain's in post_graph.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -70,236 +70,6 @@ int uh_get_hybrid_frame_stats(uh_ctx* c, UhHybridFrameStats* out) {
    return UH_OK;
 }
 
-int uh_get_hybrid_restir_stats(uh_ctx* c, UhHybridRestirStats* out) {
-   int st;
-   if (!stats_begin(c, out, sizeof(*out), "uh_get_hybrid_restir_stats: null destination", c && c->hy.rl.renders != 0, &st)) return st;
-   const uh_ctx::Hybrid& h = c->hy;
-   if ((st = stage_ms(c, c->hy.stage[kStRestirLights], &out->pass_ms))) return st;
-   uint32_t counters[2] = {0, 0};
-   HIP_TRY(c, hipMemcpy(counters, h.rl.counters.p, sizeof(counters), hipMemcpyDeviceToHost));
-   out->rays = counters[0];
-   out->occluded = counters[1];
-   return UH_OK;
-}
-
-// ---- ray-traced ambient occlusion (utopian_hip.h "UH_HYBRID_RTAO"; rtao.hip) ----
-int uh_rtao_default_params(UhRtaoParams* out) {
-   if (!out) return UH_ERR_INVALID_ARGUMENT;
-   *out = UhRtaoParams{4, 1.0f, 1.0f, 2, 0.9f, 0.05f};
-   return UH_OK;
-}
-
-static const char* rtao_params_refusal(const UhRtaoParams& p) {
-   if (p.samples < 1 || p.samples > 64) return "samples must be 1..64";
-   if (!(p.radius > 0.0f && p.radius <= 10000.0f)) return "radius must be finite, > 0 and <= 10000";
-   if (!(p.strength >= 0.0f && p.strength < INFINITY)) return "strength must be finite and >= 0";
-   if (p.blur_radius > 4) return "blur_radius must be 0..4";
-   if (std::isnan(p.blur_normal_cos) || std::isnan(p.blur_plane)) return "blur_normal_cos and blur_plane must not be NaN";
-   return nullptr;
-}
-
-int uh_set_rtao_params(uh_ctx* c, const UhRtaoParams* params) {
-   return set_params(c, params, "uh_set_rtao_params", rtao_params_refusal, &uh_ctx::Hybrid::ao);
-}
-
-int uh_get_rtao_stats(uh_ctx* c, UhRtaoStats* out) {
-   int st;
-   if (!stats_begin(c, out, sizeof(*out), "uh_get_rtao_stats: null destination", c && c->hy.ao.renders != 0, &st)) return st;
-   const uh_ctx::Hybrid& h = c->hy;
-   if ((st = stage_ms(c, c->hy.stage[kStRtaoTrace], &out->trace_ms))) return st;
-   if ((st = stage_ms(c, c->hy.stage[kStRtaoFilter], &out->filter_ms))) return st;
-   uint32_t counters[2] = {0, 0};
-   HIP_TRY(c, hipMemcpy(counters, h.ao.counters.p, sizeof(counters), hipMemcpyDeviceToHost));
-   out->pixels = counters[0];
-   out->rays = (uint64_t)counters[0] * h.ao.samples;
-   out->occluded = counters[1];
-   return UH_OK;
-}
-
-int uh_get_rtao_visits(uh_ctx* c, uint64_t* nodes, uint64_t* triangles) {
-   int st;
-   if (c && nodes && triangles) *triangles = 0;  // (*nodes: by stats_begin)
-   if (!stats_begin(c, nodes && triangles ? nodes : nullptr, sizeof(*nodes), "uh_get_rtao_visits: null destination", c && c->hy.ao.renders != 0, &st)) return st;
-   const uh_ctx::Hybrid& h = c->hy;
-   uint64_t visits[2] = {0, 0};
-   HIP_TRY(c, hipMemcpy(visits, h.ao.counters.p + 2, sizeof(visits), hipMemcpyDeviceToHost));
-   *nodes = visits[0];
-   *triangles = visits[1];
-   return UH_OK;
-}
-
-// ---- one-bounce ray-traced diffuse GI (utopian_hip.h "UH_HYBRID_RTGI"; rtgi.hip) ----
-int uh_rtgi_default_params(UhRtgiParams* out) {
-   if (!out) return UH_ERR_INVALID_ARGUMENT;
-   *out = UhRtgiParams{2, 3, 16.0f, 1.0f, 0.9f, 0.05f};
-   return UH_OK;
-}
-
-static const char* rtgi_params_refusal(const UhRtgiParams& p) {
-   if (p.samples < 1 || p.samples > 16) return "samples must be 1..16";
-   if (p.blur_radius > 6) return "blur_radius must be 0..6";
-   if (!(p.max_radiance > 0.0f && p.max_radiance < INFINITY)) return "max_radiance must be finite and > 0";
-   if (!(p.intensity >= 0.0f && p.intensity < INFINITY)) return "intensity must be finite and >= 0";
-   if (std::isnan(p.blur_normal_cos) || std::isnan(p.blur_plane)) return "blur_normal_cos and blur_plane must not be NaN";
-   return nullptr;
-}
-
-int uh_set_rtgi_params(uh_ctx* c, const UhRtgiParams* params) {
-   return set_params(c, params, "uh_set_rtgi_params", rtgi_params_refusal, &uh_ctx::Hybrid::gi);
-}
-
-int uh_get_rtgi_stats(uh_ctx* c, UhRtgiStats* out) {
-   int st;
-   if (!stats_begin(c, out, sizeof(*out), "uh_get_rtgi_stats: null destination", c && c->hy.gi.renders != 0, &st)) return st;
-   uh_ctx::Hybrid::Rtgi& g = c->hy.gi;
-   float* const ms[4] = {&out->trace_ms, &out->shadow_ms, &out->filter_ms, &out->composite_ms};
-   for (int k = 0; k < 4; k++)
-      if ((st = stage_ms(c, g.stage[k], ms[k]))) return st;
-   uint32_t counters[3] = {0, 0, 0};
-   HIP_TRY(c, hipMemcpy(counters, g.counters.p, sizeof(counters), hipMemcpyDeviceToHost));
-   out->pixels = counters[0];
-   out->rays = (uint64_t)counters[0] * g.samples;
-   out->shadow_rays = counters[1];
-   out->misses = counters[2];
-   return UH_OK;
-}
-
-// ---- ray-traced glossy reflections (utopian_hip.h "UH_HYBRID_GLOSSY"; glossy.hip) ----
-int uh_glossy_default_params(UhGlossyParams* out) {
-   if (!out) return UH_ERR_INVALID_ARGUMENT;
-   *out = UhGlossyParams{1, 3, 0.6f, 16.0f, 1.0f, 0.5f, 0.95f, 0.05f};
-   return UH_OK;
-}
-
-static const char* glossy_params_refusal(const UhGlossyParams& p) {
-   if (p.samples < 1 || p.samples > 16) return "samples must be 1..16";
-   if (p.blur_radius > 6) return "blur_radius must be 0..6";
-   if (!(p.max_roughness >= 0.0f && p.max_roughness < INFINITY)) return "max_roughness must be finite and >= 0";
-   if (!(p.max_radiance > 0.0f && p.max_radiance < INFINITY)) return "max_radiance must be finite and > 0";
-   if (!(p.intensity >= 0.0f && p.intensity < INFINITY)) return "intensity must be finite and >= 0";
-   if (!(p.blur_roughness > 0.0f && p.blur_roughness < INFINITY)) return "blur_roughness must be finite and > 0";
-   if (std::isnan(p.blur_normal_cos) || std::isnan(p.blur_plane)) return "blur_normal_cos and blur_plane must not be NaN";
-   return nullptr;
-}
-
-int uh_set_glossy_params(uh_ctx* c, const UhGlossyParams* params) {
-   return set_params(c, params, "uh_set_glossy_params", glossy_params_refusal, &uh_ctx::Hybrid::gl);
-}
-
-int uh_get_glossy_stats(uh_ctx* c, UhGlossyStats* out) {
-   int st;
-   if (!stats_begin(c, out, sizeof(*out), "uh_get_glossy_stats: null destination", c && c->hy.gl.renders != 0, &st)) return st;
-   uh_ctx::Hybrid::Glossy& g = c->hy.gl;
-   float* const ms[5] = {&out->trace_ms, &out->shade_ms, &out->shadow_ms, &out->filter_ms, &out->composite_ms};
-   for (int k = 0; k < 5; k++)
-      if ((st = stage_ms(c, g.stage[k], ms[k]))) return st;
-   uint32_t counters[5] = {0, 0, 0, 0, 0};
-   HIP_TRY(c, hipMemcpy(counters, g.counters.p, sizeof(counters), hipMemcpyDeviceToHost));
-   out->pixels = counters[0];
-   out->shadow_rays = counters[1];
-   out->misses = counters[2];
-   out->rays = counters[3];
-   out->below = counters[4];
-   return UH_OK;
-}
-
-// ---- ray-traced glass (utopian_hip.h "UH_HYBRID_GLASS"; glass.hip) ----
-int uh_glass_default_params(UhGlassParams* out) {
-   if (!out) return UH_ERR_INVALID_ARGUMENT;
-   *out = UhGlassParams{8, 16.0f, 1.0f};
-   return UH_OK;
-}
-
-static const char* glass_params_refusal(const UhGlassParams& p) {
-   if (p.max_events < 1 || p.max_events > kGlassMaxEvents) return "max_events must be 1..16";
-   if (!(p.max_radiance > 0.0f && p.max_radiance < INFINITY)) return "max_radiance must be finite and > 0";
-   if (!(p.intensity >= 0.0f && p.intensity < INFINITY)) return "intensity must be finite and >= 0";
-   return nullptr;
-}
-
-int uh_set_glass_params(uh_ctx* c, const UhGlassParams* params) {
-   return set_params(c, params, "uh_set_glass_params", glass_params_refusal, &uh_ctx::Hybrid::glass);
-}
-
-// chains: the rays of round 0; events: the rays of the rounds behind it (a chain enters round r + 1 by the event at the end of its
-// segment r); segments: the rays of every round
-int uh_get_glass_stats(uh_ctx* c, UhGlassStats* out) {
-   int st;
-   if (!stats_begin(c, out, sizeof(*out), "uh_get_glass_stats: null destination", c && c->hy.glass.renders != 0, &st)) return st;
-   uh_ctx::Hybrid::Glass& g = c->hy.glass;
-   for (uint32_t r = 0; r < g.rounds; r++) {
-      float t = 0.0f, b = 0.0f;
-      if ((st = stage_ms(c, g.trace[r], &t)) || (st = stage_ms(c, g.bend[r], &b))) return st;
-      out->trace_ms += t;
-      out->bend_ms += b;
-   }
-   if ((st = stage_ms(c, g.shadow, &out->shadow_ms)) || (st = stage_ms(c, g.composite, &out->composite_ms))) return st;
-   uint32_t counters[kGlassCounters] = {};
-   HIP_TRY(c, hipMemcpy(counters, g.counters.p, sizeof(counters), hipMemcpyDeviceToHost));
-   out->pixels = counters[0];
-   out->shadow_rays = counters[1];
-   out->misses = counters[2];
-   out->tir = counters[4];
-   out->cut = counters[5];
-   out->chains = counters[kGlassRound0];
-   for (uint32_t r = 1; r <= kGlassMaxEvents; r++) out->events += counters[kGlassRound0 + r];
-   out->segments = out->chains + out->events;
-   return UH_OK;
-}
-
-// ---- volumetric fog (utopian_hip.h "UH_HYBRID_FOG"; fog.hip) ----
-int uh_fog_default_params(UhFogParams* out) {
-   if (!out) return UH_ERR_INVALID_ARGUMENT;
-   *out = UhFogParams{16, 2, 0.02f, 200.0f, 0.6f, 1.0f, 0.1f, 0, {1.0f, 1.0f, 1.0f}, {0.05f, 0.06f, 0.08f}};
-   return UH_OK;
-}
-
-static const char* fog_params_refusal(const UhFogParams& p) {
-   if (p.steps < 1 || p.steps > 32) return "steps must be 1..32";
-   if (p.blur_radius > 4) return "blur_radius must be 0..4";
-   if (!(p.density >= 0.0f && p.density < INFINITY)) return "density must be finite and >= 0";
-   if (!(p.max_distance > 0.0f && p.max_distance < INFINITY)) return "max_distance must be finite and > 0";
-   if (!(p.anisotropy >= -0.95f && p.anisotropy <= 0.95f)) return "anisotropy must be -0.95..0.95";
-   if (!(p.intensity >= 0.0f && p.intensity < INFINITY)) return "intensity must be finite and >= 0";
-   if (!(p.blur_depth >= 0.0f && p.blur_depth < INFINITY)) return "blur_depth must be finite and >= 0";
-   if (p.reserved != 0) return "reserved must be 0";
-   for (float a : p.albedo)
-      if (!(a >= 0.0f && a <= 1.0f)) return "albedo must be 0..1 in every channel";
-   for (float a : p.ambient)
-      if (!(a >= 0.0f && a < INFINITY)) return "ambient must be finite and >= 0 in every channel";
-   return nullptr;
-}
-
-int uh_set_fog_params(uh_ctx* c, const UhFogParams* params) {
-   return set_params(c, params, "uh_set_fog_params", fog_params_refusal, &uh_ctx::Hybrid::fog);
-}
-
-int uh_get_fog_stats(uh_ctx* c, UhFogStats* out) {
-   int st;
-   if (!stats_begin(c, out, sizeof(*out), "uh_get_fog_stats: null destination", c && c->hy.fog.renders != 0, &st)) return st;
-   uh_ctx::Hybrid::Fog& g = c->hy.fog;
-   float* const ms[3] = {&out->trace_ms, &out->filter_ms, &out->composite_ms};
-   for (int k = 0; k < 3; k++)
-      if ((st = stage_ms(c, g.stage[k], ms[k]))) return st;
-   uint32_t counters[2] = {0, 0};
-   HIP_TRY(c, hipMemcpy(counters, g.counters.p, sizeof(counters), hipMemcpyDeviceToHost));
-   out->pixels = counters[0];
-   out->rays = (uint64_t)counters[0] * g.steps;
-   out->lit = counters[1];
-   return UH_OK;
-}
-
-int uh_get_fog_visits(uh_ctx* c, uint64_t* nodes, uint64_t* triangles) {
-   int st;
-   if (c && nodes && triangles) *triangles = 0;  // (*nodes: by stats_begin)
-   if (!stats_begin(c, nodes && triangles ? nodes : nullptr, sizeof(*nodes), "uh_get_fog_visits: null destination", c && c->hy.fog.renders != 0, &st)) return st;
-   uint64_t visits[2] = {0, 0};
-   HIP_TRY(c, hipMemcpy(visits, c->hy.fog.counters.p + 2, sizeof(visits), hipMemcpyDeviceToHost));
-   *nodes = visits[0];
-   *triangles = visits[1];
-   return UH_OK;
-}
-
 int uh_get_motion_stats(uh_ctx* c, UhMotionStats* out) {
    int st;
    if (!stats_begin(c, out, sizeof(*out), "uh_get_motion_stats: null destination", c && c->hy.mv.renders != 0, &st)) return st;
@@ -317,11 +87,7 @@ int uh_get_motion_stats(uh_ctx* c, UhMotionStats* out) {
 }
 
 // ---- temporal anti-aliasing (utopian_hip.h "temporal anti-aliasing"; taa.hip) ----
-int uh_taa_default_params(UhTaaParams* out) {
-   if (!out) return UH_ERR_INVALID_ARGUMENT;
-   *out = UhTaaParams{UH_TAA_CLAMP, 16, 0.1f, 1.0f};
-   return UH_OK;
-}
+int uh_taa_default_params(UhTaaParams* out) { return default_params<uh_ctx::Hybrid::Taa>(out); }
 
 static const char* taa_params_refusal(const UhTaaParams& p) {
    if (p.flags & ~(uint32_t)(UH_TAA_CLAMP | UH_TAA_MOTION)) return "unknown flag bits (UH_TAA_CLAMP, UH_TAA_MOTION)";

@@ -11,8 +11,7 @@
 int post_alloc(uh_ctx* c) {
    uh_ctx::Hybrid::Post& t = c->hy.post;
    if (t.rec.p) return UH_OK;
-   if (int st = stage_create(c, t.stage, 3)) return st;
-   if (int st = alloc_group(c, [&](auto f) { t.images(c->W, c->H, f); })) return st;
+   if (int st = first_use(c, t, t.rec.p, [&](auto f) { t.images(c->W, c->H, f); })) return st;
    HIP_TRY(c, hipMemsetAsync(t.hist.p, 0, kPostBins * sizeof(uint32_t), c->stream));
    HIP_TRY(c, hipMemsetAsync(t.rec.p, 0, sizeof(PostRecord), c->stream));
    return UH_OK;
@@ -39,7 +38,7 @@ int post_run(uh_ctx* c, const LaunchCfg& lc, const float4* src) {
    pd.manual_exposure = p.manual_exposure, pd.key = p.key, pd.min_exposure = p.min_exposure, pd.max_exposure = p.max_exposure;
    pd.adaptation = p.adaptation, pd.low_percentile = p.low_percentile, pd.high_percentile = p.high_percentile;
    pd.bloom_threshold = p.bloom_threshold, pd.bloom_intensity = p.bloom_intensity;
-   for (Stage& s : t.stage) s.ran = false;
+   t.stages([](Stage& s) { s.ran = false; });
    if (int st = timed(c, t.stage[0], [&] { launch_post_meter(lc, pd); })) return st;
    t.have_exposure = true;  // from here on the record holds this pass's exposure, whatever fails below
    if (pd.levels)

@@ -115,22 +115,26 @@ def test_python_layer():
 
 
 def test_the_refusal_strings():
-    """what uh_render_hybrid and uh_read_hybrid answer, in the order the header states, behind every older rule; and the older strings stay"""
-    graph = open(os.path.join(CSRC, "hybrid_graph.hip")).read()
+    """what uh_render_hybrid and uh_read_hybrid answer, in the order the header states, behind every older rule; and the older strings stay.
+    The plan's rules are text in csrc/hybrid_plan.h (tests/cpp/hybrid_plan_check.cpp asserts their order by behaviour, all 39 of them);
+    "uh_render_hybrid before uh_build_acceleration" is no plan rule and is not searched for here: its place behind every plan rule is
+    test_gpu_hybrid_refusal_order.py::test_every_refusal_comes_before_not_built's, on the GPU. The params strings stand with the glass
+    pass's verbs in csrc/hybrid_ray_passes.hip."""
+    plan = open(os.path.join(CSRC, "hybrid_plan.h")).read()
     order = ["UH_HYBRID_FOG: a frame of 2^26 pixels or more",
              "UH_HYBRID_GLASS casts rays and view.raytracing_supported is not 1",
              "UH_HYBRID_GLASS casts its rays from the G-buffer, and no G-buffer has been rendered",
              "UH_HYBRID_GLASS without UH_HYBRID_DEFERRED in the same call",
-             "UH_HYBRID_GLASS: a frame of 2^27 pixels or more",
-             "uh_render_hybrid before uh_build_acceleration"]
-    at = [graph.index(s) for s in order]
+             "UH_HYBRID_GLASS: a frame of 2^27 pixels or more"]
+    at = [plan.index(s) for s in order]
     assert at == sorted(at), "the refusals stand in this order in the plan"
     verbs = open(os.path.join(CSRC, "hybrid_verbs.hip")).read()
     assert ('"uh_read_hybrid: images 25..27 before the first glass pass (UH_HYBRID_GLASS); until then the image index must be 0..24"') in verbs
     for s in ("must be 0..17", "images 20..22 before the first glossy pass", "images 23..24 before the first fog pass", "image index must be 0..27"):
         assert s in verbs, s
+    passes = open(os.path.join(CSRC, "hybrid_ray_passes.hip")).read()
     for s in ("max_events must be 1..16", "max_radiance must be finite and > 0", "intensity must be finite and >= 0"):
-        assert s in verbs, s
+        assert s in passes, s
 
 
 @pytest.mark.gpu

@@ -12,6 +12,7 @@ pytestmark = pytest.mark.gpu
 W, H = 24, 16
 SHADOWS, GBUFFER, REFL, DEFERRED, SKY = rr.HYBRID_RT_SHADOWS, rr.HYBRID_GBUFFER, rr.HYBRID_RT_REFLECTIONS, rr.HYBRID_DEFERRED, rr.HYBRID_SKY
 RASTER, MAPS, MC, RESTIR, RTAO = rr.HYBRID_GBUFFER_RASTER, rr.HYBRID_SHADOW_MAPS, rr.HYBRID_MARCHING_CUBES, rr.HYBRID_RESTIR_LIGHTS, rr.HYBRID_RTAO
+TAA, RTGI, GLOSSY, FOG, GLASS = rr.HYBRID_TAA, rr.HYBRID_RTGI, rr.HYBRID_GLOSSY, rr.HYBRID_FOG, rr.HYBRID_GLASS
 
 # the rules in the order uh_render_hybrid checks them: how each message begins
 RASTER_ALONE = "uh_render_hybrid: UH_HYBRID_GBUFFER_RASTER without UH_HYBRID_GBUFFER"
@@ -29,6 +30,24 @@ RTAO_GBUFFER = "uh_render_hybrid: UH_HYBRID_RTAO casts its rays from the G-buffe
 MC_GBUFFER = "uh_render_hybrid: the marching-cubes pass depth-tests against the G-buffer's depth, and no G-buffer has been rendered"
 MC_MAPS = "uh_render_hybrid: the marching-cubes pass with view.shadows_enabled = 1 needs the cascaded shadow maps"
 MC_LIGHTS = "uh_render_hybrid: the marching-cubes pass: view.num_lights exceeds the lights added with uh_add_light"
+# (the passes added since, from the list of tests/cpp/hybrid_plan_check.cpp, which holds csrc/hybrid_plan.h to all 39 rules on the CPU: these
+# rows see the context's facts reach the plan through the real entry point)
+TAA_GBUFFER = "uh_render_hybrid: UH_HYBRID_TAA reprojects the G-buffer's positions, and no G-buffer has been rendered"
+RTGI_RT = "uh_render_hybrid: UH_HYBRID_RTGI casts rays and view.raytracing_supported is not 1"
+RTGI_GBUFFER = "uh_render_hybrid: UH_HYBRID_RTGI casts its rays from the G-buffer, and no G-buffer has been rendered"
+RTGI_IBL = "uh_render_hybrid: UH_HYBRID_RTGI with view.ibl_enabled = 1: the IBL ambient term and this pass would both count the sky"
+RTGI_DEFERRED = "uh_render_hybrid: UH_HYBRID_RTGI without UH_HYBRID_DEFERRED in the same call"
+GLOSSY_RT = "uh_render_hybrid: UH_HYBRID_GLOSSY casts rays and view.raytracing_supported is not 1"
+GLOSSY_GBUFFER = "uh_render_hybrid: UH_HYBRID_GLOSSY casts its rays from the G-buffer, and no G-buffer has been rendered"
+GLOSSY_IBL = "uh_render_hybrid: UH_HYBRID_GLOSSY with view.ibl_enabled = 1: the IBL specular term and this pass would both count the sky"
+GLOSSY_DEFERRED = "uh_render_hybrid: UH_HYBRID_GLOSSY without UH_HYBRID_DEFERRED in the same call"
+FOG_RT = "uh_render_hybrid: UH_HYBRID_FOG casts sun rays and view.raytracing_supported is not 1"
+FOG_GBUFFER = "uh_render_hybrid: UH_HYBRID_FOG marches to the G-buffer's positions, and no G-buffer has been rendered"
+FOG_DEFERRED_SKY = "uh_render_hybrid: UH_HYBRID_FOG without UH_HYBRID_DEFERRED and UH_HYBRID_SKY in the same call"
+FOG_MC = "uh_render_hybrid: UH_HYBRID_FOG with UH_HYBRID_MARCHING_CUBES in the same call"
+GLASS_RT = "uh_render_hybrid: UH_HYBRID_GLASS casts rays and view.raytracing_supported is not 1"
+GLASS_GBUFFER = "uh_render_hybrid: UH_HYBRID_GLASS casts its rays from the G-buffer, and no G-buffer has been rendered"
+GLASS_DEFERRED = "uh_render_hybrid: UH_HYBRID_GLASS without UH_HYBRID_DEFERRED in the same call"
 NOT_BUILT = "uh_render_hybrid before uh_build_acceleration"
 
 # (mask, view fields) breaking two rules: the first rule's message; then (mask, view fields) breaking the second alone: its message
@@ -46,6 +65,21 @@ PAIRS = {
     "restir_no_reservoirs/mc_lights": ((RESTIR | GBUFFER | MC, dict(marching_cubes_enabled=1, num_lights=1)), RESTIR_NONE, (GBUFFER | MC, dict(marching_cubes_enabled=1, num_lights=1)), MC_LIGHTS),
     "rtao_gbuffer/mc_gbuffer": ((RTAO | MC, dict(marching_cubes_enabled=1)), RTAO_GBUFFER, (MC, dict(marching_cubes_enabled=1)), MC_GBUFFER),
     "mc_maps/mc_lights": ((GBUFFER | MC, dict(marching_cubes_enabled=1, shadows_enabled=1, num_lights=1)), MC_MAPS, (GBUFFER | MC, dict(marching_cubes_enabled=1, num_lights=1)), MC_LIGHTS),
+    "mc_gbuffer/taa_gbuffer": ((MC | TAA, dict(marching_cubes_enabled=1)), MC_GBUFFER, (TAA, {}), TAA_GBUFFER),
+    "taa_gbuffer/rtgi_raytracing": ((TAA | RTGI, dict(raytracing_supported=0)), TAA_GBUFFER, (RTGI, dict(raytracing_supported=0)), RTGI_RT),
+    "rtgi_raytracing/rtgi_gbuffer": ((RTGI, dict(raytracing_supported=0)), RTGI_RT, (RTGI, {}), RTGI_GBUFFER),
+    "rtgi_gbuffer/rtgi_ibl": ((RTGI, dict(ibl_enabled=1)), RTGI_GBUFFER, (RTGI | GBUFFER, dict(ibl_enabled=1)), RTGI_IBL),
+    "rtgi_ibl/rtgi_deferred": ((RTGI | GBUFFER, dict(ibl_enabled=1)), RTGI_IBL, (RTGI | GBUFFER, {}), RTGI_DEFERRED),
+    "rtgi_deferred/glossy_deferred": ((RTGI | GLOSSY | GBUFFER, {}), RTGI_DEFERRED, (GLOSSY | GBUFFER, {}), GLOSSY_DEFERRED),
+    "glossy_raytracing/glossy_gbuffer": ((GLOSSY, dict(raytracing_supported=0)), GLOSSY_RT, (GLOSSY, {}), GLOSSY_GBUFFER),
+    "glossy_ibl/glossy_deferred": ((GLOSSY | GBUFFER, dict(ibl_enabled=1)), GLOSSY_IBL, (GLOSSY | GBUFFER, {}), GLOSSY_DEFERRED),
+    "glossy_gbuffer/fog_gbuffer": ((GLOSSY | FOG, {}), GLOSSY_GBUFFER, (FOG, {}), FOG_GBUFFER),
+    "fog_raytracing/fog_gbuffer": ((FOG, dict(raytracing_supported=0)), FOG_RT, (FOG, {}), FOG_GBUFFER),
+    "fog_deferred_and_sky/fog_marching_cubes": ((FOG | GBUFFER | DEFERRED | MC, {}), FOG_DEFERRED_SKY, (FOG | GBUFFER | DEFERRED | SKY | MC, {}), FOG_MC),
+    "fog_gbuffer/glass_gbuffer": ((FOG | GLASS, {}), FOG_GBUFFER, (GLASS, {}), GLASS_GBUFFER),
+    "fog_deferred_and_sky/glass_deferred": ((FOG | GLASS | GBUFFER, {}), FOG_DEFERRED_SKY, (GLASS | GBUFFER, {}), GLASS_DEFERRED),
+    "glass_raytracing/glass_gbuffer": ((GLASS, dict(raytracing_supported=0)), GLASS_RT, (GLASS, {}), GLASS_GBUFFER),
+    "glass_gbuffer/glass_deferred": ((GLASS, {}), GLASS_GBUFFER, (GLASS | GBUFFER, {}), GLASS_DEFERRED),
 }
 
 
