@@ -243,7 +243,9 @@ typedef struct uh_ctx uh_ctx;
  *        view->rebuild_tlas), uh_set_tile_partition, uh_set_restir_partition, uh_rccl_attach / uh_rccl_detach, uh_pack_tiles,
  *        uh_unpack_tiles, uh_compose_tiles, uh_resolve_output, uh_add_isosurface_mesh, uh_update_isosurface_mesh (it reads the
  *        triangle total, 8 bytes, back to size its buffers), uh_get_isosurface_update_stats, uh_update_mesh_vertices (device input:
- *        it reads a 4-byte verdict on the caller's buffer back before it takes it), uh_get_mesh_update_stats, uh_read_denoised,
+ *        it reads a 4-byte verdict on the caller's buffer back before it takes it), uh_get_mesh_update_stats, uh_set_mesh_skin,
+ *        uh_set_mesh_morph_targets (both upload into fresh buffers and take the bind pose), uh_pose_mesh (it reads a 4-byte verdict on the
+ *        posed positions back before the mesh takes them), uh_get_pose_stats, uh_read_denoised,
  *        uh_get_denoise_stats, uh_reset_denoise_history, uh_get_rtao_stats, uh_get_rtao_visits, uh_get_motion_stats, uh_reset_taa_history,
  *        uh_get_taa_stats, uh_post_image, uh_read_post, uh_get_post_stats, uh_get_rtgi_stats, uh_get_glossy_stats, uh_get_fog_stats,
  *        uh_get_fog_visits, uh_get_glass_stats, uh_destroy;
@@ -587,6 +589,62 @@ UH_LAYOUT_ASSERT(sizeof(UhMeshUpdateStats) == 32 && offsetof(UhMeshUpdateStats, 
                  "UhMeshUpdateStats (32 B)");
 /* all zero before the first update; waits for the frames in flight like the other stats calls */
 int uh_get_mesh_update_stats(uh_ctx* ctx, UhMeshUpdateStats* out);
+
+/* ---- posed meshes: a skin and / or morph targets on a mesh of uh_add_mesh, posed on the device ------------------------------
+ * An EXTENSION: the reference draws its glTF assets in their bind pose. uh_set_mesh_skin gives mesh `mesh_index` four joint indices
+ * and four weights per vertex (linear blend skinning over `num_joints` joints), uh_set_mesh_morph_targets gives it `num_targets`
+ * morph targets: position deltas, 3 floats per vertex, target-major (target t's deltas are position_deltas[3 * (t * num_vertices + i)
+ * ..]), and optionally normal deltas of the same shape. A mesh may have either or both. Each set verb takes the mesh's CURRENT
+ * vertices as the bind pose (from the device when the host copy is stale after a device update or a pose), keeps its input in device
+ * buffers of the mesh, and replaces what an earlier call of the same verb set; the bind pose is taken anew by every call of either.
+ * Neither changes the geometry: a built context stays built and renders as before.
+ * uh_pose_mesh then writes ALL vertices of the mesh from the bind pose: one kernel (k_pose, pose.hip), its only host input the call's
+ * joint matrices - row-major 3x4, 12 floats each, the layout of uh_set_instance_transform, object space to object space - and morph
+ * weights. num_joints / num_targets must equal what was set, or be 0 with a null pointer for a part the mesh does not have. The
+ * arithmetic is DESIGN.md section 2, "Posed meshes": targets with a weight of exactly zero are skipped, the others added in ascending
+ * order; the blend of the four joint matrices transforms the position, and its upper 3x3 - not the inverse transpose: exact in
+ * direction for rigid and uniformly scaled joints, as in common glTF viewers - the normal and the tangent; the normal is normalised
+ * unless it is zero, the tangent too when a skin transformed it; every other field is the bind record's, bit for bit.
+ * State after a pose: that of uh_update_mesh_vertices(UH_VERTICES_DEVICE) - the context is not built, the host copy is stale,
+ * UhMeshUpdateStats::updates counts it, motion vectors classify the mesh `deformed`; the per-frame protocol is pose,
+ * view->rebuild_tlas = 1, render. A later uh_update_mesh_vertices on the mesh is allowed; the bind pose stays what it was when set.
+ * No vertex data moves between host and device in a pose.
+ * Errors, each UH_ERR_INVALID_ARGUMENT and each leaving everything as it was: a null context, an index out of range, a mesh of
+ * uh_add_isosurface_mesh or one without vertices, num_vertices differing from the mesh's count, num_joints == 0 (or more than 65,536)
+ * or num_targets == 0 in a set verb, a null pointer (normal_deltas may be null), a joint index >= num_joints, a weight that is
+ * negative or not finite, a vertex whose four weights are all zero, a delta that is not finite; in uh_pose_mesh a mesh with neither
+ * part, counts that differ from what was set, a matrix entry or morph weight that is not finite - all checked on the host before
+ * anything is stored -, and a posed position that is not finite: the kernel raises a flag, and the call is refused with the mesh,
+ * the tree and the build state exactly as before (the pose is written into a second vertex buffer that changes places with the
+ * mesh's own only on success). UH_ERR_OUT_OF_MEMORY when a buffer cannot be made.
+ * STREAM ORDER: the four verbs wait for the frames in flight and are complete on return.
+ * RESOURCES: per posed mesh 80 bytes per vertex of bind pose, 24 per vertex of skin, 12 (24 with normals) per vertex and target,
+ * allocated by the set verbs; with the first pose the second vertex buffer (80 per vertex) and the buffers of an updated mesh; per
+ * context the call's parameters (48 bytes per joint, 8 per active target) and two events. All freed by uh_destroy. A context that never
+ * calls these verbs allocates nothing and launches no new kernel.
+ * ISOLATION: no other verb's result changes; uh_update_mesh_vertices runs the code it ran (its tail is now a helper pose shares).
+ * No uh_mgpu_ twin. */
+int uh_set_mesh_skin(uh_ctx* ctx, uint32_t mesh_index, const uint16_t* joints, const float* weights, uint32_t num_vertices, uint32_t num_joints);
+int uh_set_mesh_morph_targets(uh_ctx* ctx, uint32_t mesh_index, const float* position_deltas, const float* normal_deltas, uint32_t num_vertices,
+                              uint32_t num_targets);
+int uh_pose_mesh(uh_ctx* ctx, uint32_t mesh_index, const float* joint_matrices3x4, uint32_t num_joints, const float* morph_weights,
+                 uint32_t num_targets);
+typedef struct UhPoseStats {
+   float pose_ms;               /* hipEvent: k_pose of the last pose */
+   uint32_t poses;              /* so far (refused ones are not counted) */
+   uint32_t vertices;           /* of the last pose */
+   uint32_t joints;             /* of the last pose */
+   uint32_t active_targets;     /* of the last pose: the targets whose weight was not zero */
+   uint32_t staged_joint_limit; /* the largest joint count k_pose keeps in LDS; 0: it never stages - the case: staging measured no
+                                   faster at 64 joints and slower at 1,024 (DESIGN.md section 4 "Posed meshes") */
+   uint64_t device_bytes;       /* bind poses, skins, deltas, second vertex buffers and the call parameters held for posed meshes */
+} UhPoseStats;
+UH_LAYOUT_ASSERT(sizeof(UhPoseStats) == 32 && offsetof(UhPoseStats, poses) == 4 && offsetof(UhPoseStats, vertices) == 8 &&
+                    offsetof(UhPoseStats, joints) == 12 && offsetof(UhPoseStats, active_targets) == 16 &&
+                    offsetof(UhPoseStats, staged_joint_limit) == 20 && offsetof(UhPoseStats, device_bytes) == 24,
+                 "UhPoseStats (32 B)");
+/* all zero before the first pose; waits for the frames in flight like the other stats calls */
+int uh_get_pose_stats(uh_ctx* ctx, UhPoseStats* out);
 
 /* ---- several GPUs behind ONE application process (SURVEY.md section 8b "multi-GPU", 8e) ------------
  * The reference application is a single process with one render thread (prototype/src/main.rs:86-570);

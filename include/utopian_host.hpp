@@ -610,6 +610,24 @@ class Renderer {
       check(uh_get_mesh_update_stats(ctx_, &s), "mesh_update_stats");
       return s;
    }
+   // posed meshes: a skin (four joints and weights per vertex) and / or morph targets (deltas target-major) on a mesh of add_mesh, its
+   // current vertices the bind pose; pose_mesh then writes the mesh's vertices on the device from the call's joint matrices (3x4 row-major,
+   // 12 floats each) and morph weights - null / 0 for a part the mesh does not have - and leaves the state of
+   // update_mesh_vertices(UH_VERTICES_DEVICE): rebuild_tlas() or a frame with view.rebuild_tlas = 1 follows
+   void set_mesh_skin(uint32_t mesh, const uint16_t* joints, const float* weights, uint32_t num_vertices, uint32_t num_joints) {
+      check(uh_set_mesh_skin(ctx_, mesh, joints, weights, num_vertices, num_joints), "set_mesh_skin");
+   }
+   void set_mesh_morph_targets(uint32_t mesh, const float* position_deltas, const float* normal_deltas, uint32_t num_vertices, uint32_t num_targets) {
+      check(uh_set_mesh_morph_targets(ctx_, mesh, position_deltas, normal_deltas, num_vertices, num_targets), "set_mesh_morph_targets");
+   }
+   void pose_mesh(uint32_t mesh, const float* joint_matrices3x4, uint32_t num_joints, const float* morph_weights = nullptr, uint32_t num_targets = 0) {
+      check(uh_pose_mesh(ctx_, mesh, joint_matrices3x4, num_joints, morph_weights, num_targets), "pose_mesh");
+   }
+   UhPoseStats pose_stats() {
+      UhPoseStats s;
+      check(uh_get_pose_stats(ctx_, &s), "pose_stats");
+      return s;
+   }
    // ---- one process per GPU (the reference is single-device: utopian/src/device.rs:45) ----
    // path tracing: tiles t % world == rank; reservoir passes: this rank's band of rows, exchanged over RCCL inside the library
    // (rank 0 makes the id, the launcher hands the 128 bytes to every rank); composition on the root: compose_tiles

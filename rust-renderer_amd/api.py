@@ -77,6 +77,7 @@ from .types import (
     GbufferRasterStats,
     IsosurfaceUpdateStats,
     MeshUpdateStats,
+    PoseStats,
     MotionStats,
     MarchingCubesStats,
     ShadowmapParams,
@@ -177,6 +178,10 @@ _LIBRARY_VERBS = {
     "get_isosurface_update_stats": [_vp, _p(IsosurfaceUpdateStats)],
     "update_mesh_vertices": [_vp, _u32, _vp, _u32, _int],
     "get_mesh_update_stats": [_vp, _p(MeshUpdateStats)],
+    "set_mesh_skin": [_vp, _u32, _vp, _vp, _u32, _u32],
+    "set_mesh_morph_targets": [_vp, _u32, _vp, _vp, _u32, _u32],
+    "pose_mesh": [_vp, _u32, _vp, _u32, _vp, _u32],
+    "get_pose_stats": [_vp, _p(PoseStats)],
     "isosurface_cells": [_vp, _u32, _f32, _f32, _f32, _vp, _vp],
     "mesh_info": [_vp, _u32, _p(_u32), _p(_u32)],
     "read_mesh": [_vp, _u32, _vp, _vp],
@@ -482,6 +487,11 @@ class Renderer:
                 mat.diffuse_map = self.default_diffuse_map()
             w = mesh.transform if transform is None else compose3x4(transform, mesh.transform)
             mesh_ids.append(self.add_mesh(mesh.vertices, mesh.indices, mat, w))
+            if self.backend == "hip":  # a rigged primitive of a glTF (gltf.Animator poses it): the other backends draw the bind pose
+                if getattr(mesh, "skin", None) is not None:
+                    self.set_mesh_skin(mesh_ids[-1], mesh.joints, mesh.weights, len(model.skins[mesh.skin].joints))
+                if getattr(mesh, "morph_positions", None) is not None:
+                    self.set_mesh_morph_targets(mesh_ids[-1], mesh.morph_positions, mesh.morph_normals)
         return mesh_ids
 
     def add_isosurface_mesh(self, resolution, lo, hi, time=0.0, material=None, world3x4=None):
@@ -521,6 +531,37 @@ class Renderer:
     def mesh_update_stats(self):
         """UhMeshUpdateStats (all zero before the first update_mesh_vertices)"""
         return self._stats(MeshUpdateStats, self._uh("get_mesh_update_stats"))
+
+    def set_mesh_skin(self, mesh, joints, weights, num_joints):
+        """uh_set_mesh_skin: `joints` (N, 4) uint16 and `weights` (N, 4) float32 for the N vertices of a mesh of add_mesh, over
+        `num_joints` joints; the mesh's current vertices become the bind pose. The geometry does not change."""
+        joints = np.ascontiguousarray(joints, dtype=np.uint16)
+        weights = np.ascontiguousarray(weights, dtype=np.float32)
+        if joints.ndim != 2 or joints.shape[1] != 4 or weights.shape != joints.shape:
+            raise ValueError("joints and weights are (N, 4) arrays")
+        self._check(self._uh("set_mesh_skin")(self._ctx, int(mesh), joints.ctypes.data, weights.ctypes.data, len(joints), int(num_joints)))
+
+    def set_mesh_morph_targets(self, mesh, position_deltas, normal_deltas=None):
+        """uh_set_mesh_morph_targets: `position_deltas` (T, N, 3) float32 and, optionally, `normal_deltas` of the same shape for the N
+        vertices of a mesh of add_mesh; the mesh's current vertices become the bind pose. The geometry does not change."""
+        dp = np.ascontiguousarray(position_deltas, dtype=np.float32)
+        dn = None if normal_deltas is None else np.ascontiguousarray(normal_deltas, dtype=np.float32)
+        if dp.ndim != 3 or dp.shape[2] != 3 or (dn is not None and dn.shape != dp.shape):
+            raise ValueError("deltas are (T, N, 3) arrays of one shape")
+        self._check(self._uh("set_mesh_morph_targets")(self._ctx, int(mesh), dp.ctypes.data, None if dn is None else dn.ctypes.data, dp.shape[1], dp.shape[0]))
+
+    def pose_mesh(self, mesh, joint_matrices=None, morph_weights=None):
+        """uh_pose_mesh: the mesh's vertices from its bind pose, on the device. `joint_matrices`: (J, 12) or (J, 3, 4) float32, row-major
+        3x4 per joint of the skin; `morph_weights`: (T,) float32; None for a part the mesh does not have. refit_acceleration (or a frame
+        with view.rebuild_tlas = 1) or build_acceleration follows, as after update_mesh_vertices."""
+        jm = None if joint_matrices is None else np.ascontiguousarray(joint_matrices, dtype=np.float32).reshape(-1, 12)
+        mw = None if morph_weights is None else np.ascontiguousarray(morph_weights, dtype=np.float32).reshape(-1)
+        self._check(self._uh("pose_mesh")(self._ctx, int(mesh), None if jm is None else jm.ctypes.data, 0 if jm is None else len(jm),
+                                          None if mw is None else mw.ctypes.data, 0 if mw is None else len(mw)))
+
+    def pose_stats(self):
+        """UhPoseStats (all zero before the first pose_mesh)"""
+        return self._stats(PoseStats, self._uh("get_pose_stats"))
 
     def isosurface_cells(self, resolution, lo, hi, time=0.0):
         """uh_isosurface_cells: per cell of the extraction grid (x fastest) its marching-cubes case index and the triangles it keeps"""

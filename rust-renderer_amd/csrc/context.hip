@@ -234,7 +234,15 @@ void uh_destroy(uh_ctx* c) {
    for (HostMesh& m : c->meshes) {
       if (m.d_verts) (void)hipFree(m.d_verts);
       if (m.d_indices) (void)hipFree(m.d_indices);
+      if (m.pose) {
+         m.pose->release();
+         delete m.pose;
+      }
    }
+   for (hipEvent_t ev : c->pose.ev)
+      if (ev) (void)hipEventDestroy(ev);
+   c->pose.params.release();
+   c->pose.flag.release();
    for (hipEvent_t ev : c->mupd.ev)
       if (ev) (void)hipEventDestroy(ev);
    c->mupd.table.release();

@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -18,6 +19,25 @@
 #include "utopian_hip.h"
 
 using namespace uh;  // (the including files are written inside it)
+
+// what uh_pose_mesh reads of a mesh (pose.hip), all on the device: the bind pose (the mesh's vertices when a set verb was last called),
+// the skin's four joints and weights per vertex, the morph targets' deltas target-major, and the second vertex buffer a pose writes
+// before it changes places with HostMesh::d_verts (made by the first pose)
+struct MeshPose {
+   UhVertex* bind = nullptr;
+   UhVertex* back = nullptr;
+   uint16_t* joints = nullptr;
+   float* weights = nullptr;
+   uint32_t num_joints = 0;   // 0: no skin
+   float* dpos = nullptr;
+   float* dnrm = nullptr;     // null: the targets carry no normal deltas
+   uint32_t num_targets = 0;  // 0: no morph targets
+   void release() {
+      for (void* p : {(void*)bind, (void*)back, (void*)joints, (void*)weights, (void*)dpos, (void*)dnrm})
+         if (p) (void)hipFree(p);
+      *this = MeshPose{};
+   }
+};
 
 struct HostMesh {
    std::vector<UhVertex> vertices;
@@ -42,6 +62,8 @@ struct HostMesh {
    // uploaded by the first update. `indices` stays; `vertices` is stale while !host_valid (the last update took a device pointer)
    bool upd = false;
    uint32_t* d_indices = nullptr;
+   // posed (uh_set_mesh_skin / uh_set_mesh_morph_targets; pose.hip): null until one of them is called, owned by the context
+   struct MeshPose* pose = nullptr;
    bool resident() const { return dev || upd; }
    size_t tris() const { return dev ? dev_tris : indices.size() / 3; }
    size_t num_vertices() const { return dev ? 3 * (size_t)dev_tris : vertices.size(); }
@@ -384,6 +406,16 @@ struct uh_ctx {
       hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // before the gather, between it and the refit, behind the refit
       UhMeshUpdateStats st{};
    } mupd;
+   // uh_pose_mesh (pose.hip): a call's joint matrices and active targets on the device (and the host vector they are copied from), the
+   // flag word of the finite-position check, the events around the kernel and the figures of uh_get_pose_stats; nothing of it exists
+   // before the first pose
+   struct Pose {
+      DevBuf<float> params;
+      std::vector<float> host_params;
+      DevBuf<uint32_t> flag;
+      hipEvent_t ev[2] = {nullptr, nullptr};
+      UhPoseStats st{};
+   } pose;
    float refit_ms = 0.0f;
    DevBuf<TexInfo> d_tex;
    DevBuf<float> d_lut;
@@ -820,6 +852,12 @@ void grid_stats(const uh_ctx* c, UhStats* out);  // the sun_grid_* and camera_gr
 // brackets of UhIsosurfaceUpdateStats::scatter_ms on the context's stream (the mesh tables of device-resident meshes count into it)
 void iso_scatter_begin(uh_ctx* c);
 int iso_scatter_end(uh_ctx* c, bool add);
+// ---- scene_build.hip, for pose.hip ----
+// The tail of every verb that replaces all vertices of a mesh of uh_add_mesh on the device: the mesh's own vertex buffer and its index
+// list on the device (made by the first such call; a refusal leaves the mesh as it was), then serial bumped and the context not built,
+// then write() - it fills m.d_verts or exchanges it for a buffer of the same size that is already filled -, then the host copy marked
+// valid or stale and the update counted (UhMeshUpdateStats::updates). `verb` names the caller in uh_last_error
+int replace_mesh_vertices(uh_ctx* c, HostMesh& m, const char* verb, bool host_valid, const std::function<int()>& write);
 // ---- hybrid_graph.hip, for uh_destroy ----
 void destroy_graphs(uh_ctx* c);  // everything uh_ctx::Hybrid, uh_ctx::Forward and uh_ctx::Denoise own; before the slots' streams go
 #pragma GCC visibility pop

@@ -827,6 +827,41 @@ int uh_get_isosurface_update_stats(uh_ctx* c, UhIsosurfaceUpdateStats* out) {
    return UH_OK;
 }
 
+}  // extern "C"
+
+int replace_mesh_vertices(uh_ctx* c, HostMesh& m, const char* verb, bool host_valid, const std::function<int()>& write) {
+   const size_t num_vertices = m.vertices.size();
+   for (hipEvent_t& ev : c->mupd.ev)  // the refit behind this update times its gather with them
+      if (!ev) HIP_TRY(c, hipEventCreate(&ev));
+   if (!m.upd) {
+      // the mesh's own buffers, and its index list to the device this once; a refusal leaves the mesh as it was
+      UhVertex* dv = nullptr;
+      uint32_t* di = nullptr;
+      const size_t index_bytes = m.indices.size() * sizeof(uint32_t);
+      hipError_t e = hipMalloc((void**)&dv, num_vertices * sizeof(UhVertex));
+      if (e == hipSuccess && index_bytes) e = hipMalloc((void**)&di, index_bytes);
+      if (e == hipSuccess && index_bytes) e = hipMemcpy(di, m.indices.data(), index_bytes, hipMemcpyHostToDevice);
+      if (e != hipSuccess) {
+         if (dv) (void)hipFree(dv);
+         if (di) (void)hipFree(di);
+         return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string(verb) + ": the mesh's device buffers: " + hipGetErrorString(e));
+      }
+      m.d_verts = dv;
+      m.d_indices = di;
+      m.d_capacity = num_vertices;
+      m.upd = true;
+   }
+   // from here on the mesh's geometry is the new one: whatever happens, the context is not built
+   m.serial++;
+   c->built = false;
+   m.host_valid = host_valid;
+   if (int st = write()) return st;
+   c->mupd.st.updates++;
+   return UH_OK;
+}
+
+extern "C" {
+
 int uh_update_mesh_vertices(uh_ctx* c, uint32_t mesh_index, const UhVertex* vertices, uint32_t num_vertices, int where) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    if (mesh_index >= c->meshes.size()) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_update_mesh_vertices: bad mesh index");
@@ -842,8 +877,6 @@ int uh_update_mesh_vertices(uh_ctx* c, uint32_t mesh_index, const UhVertex* vert
    HIP_TRY(c, hipSetDevice(c->device));
    if (int st = sync_all(c)) return st;
    uh_ctx::MeshUpdate& u = c->mupd;
-   for (hipEvent_t& ev : u.ev)
-      if (!ev) HIP_TRY(c, hipEventCreate(&ev));
    if (!num_vertices) {  // nothing to move: the mesh stays where it is
       u.st.updates++;
       return UH_OK;
@@ -859,40 +892,18 @@ int uh_update_mesh_vertices(uh_ctx* c, uint32_t mesh_index, const UhVertex* vert
       HIP_TRY(c, hipStreamSynchronize(c->stream));
       if (flag) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_update_mesh_vertices: vertex position is not finite");
    }
-   if (!m.upd) {
-      // the mesh's own buffers, and its index list to the device this once; a refusal leaves the mesh as it was
-      UhVertex* dv = nullptr;
-      uint32_t* di = nullptr;
-      const size_t index_bytes = m.indices.size() * sizeof(uint32_t);
-      hipError_t e = hipMalloc((void**)&dv, num_vertices * sizeof(UhVertex));
-      if (e == hipSuccess && index_bytes) e = hipMalloc((void**)&di, index_bytes);
-      if (e == hipSuccess && index_bytes) e = hipMemcpy(di, m.indices.data(), index_bytes, hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-         if (dv) (void)hipFree(dv);
-         if (di) (void)hipFree(di);
-         return fail(c, e == hipErrorOutOfMemory ? UH_ERR_OUT_OF_MEMORY : UH_ERR_HIP, std::string("uh_update_mesh_vertices: the mesh's device buffers: ") + hipGetErrorString(e));
-      }
-      m.d_verts = dv;
-      m.d_indices = di;
-      m.d_capacity = num_vertices;
-      m.upd = true;
-   }
-   // from here on the mesh's geometry is the new one: whatever happens, the context is not built
-   m.serial++;
-   c->built = false;
    const size_t bytes = num_vertices * sizeof(UhVertex);
-   if (where == UH_VERTICES_HOST) {
-      std::memcpy(m.vertices.data(), vertices, bytes);
-      m.host_valid = true;
-      HIP_TRY(c, hipMemcpy(m.d_verts, vertices, bytes, hipMemcpyHostToDevice));
-      u.st.host_geometry_bytes += bytes;
-   } else {
-      m.host_valid = false;
-      HIP_TRY(c, hipMemcpyAsync(m.d_verts, vertices, bytes, hipMemcpyDeviceToDevice, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-   }
-   u.st.updates++;
-   return UH_OK;
+   return replace_mesh_vertices(c, m, "uh_update_mesh_vertices", where == UH_VERTICES_HOST, [&]() -> int {
+      if (where == UH_VERTICES_HOST) {
+         std::memcpy(m.vertices.data(), vertices, bytes);
+         HIP_TRY(c, hipMemcpy(m.d_verts, vertices, bytes, hipMemcpyHostToDevice));
+         u.st.host_geometry_bytes += bytes;
+      } else {
+         HIP_TRY(c, hipMemcpyAsync(m.d_verts, vertices, bytes, hipMemcpyDeviceToDevice, c->stream));
+         HIP_TRY(c, hipStreamSynchronize(c->stream));
+      }
+      return UH_OK;
+   });
 }
 
 int uh_get_mesh_update_stats(uh_ctx* c, UhMeshUpdateStats* out) {

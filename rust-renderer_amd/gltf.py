@@ -11,12 +11,17 @@ reference's loader (utopian/src/gltf_loader.rs:47-218):
 * images become RGBA8 (RGB8 is expanded, anything else is the reference's "Unsupported image format!",
   gltf_loader.rs:179-198); PNG is decoded in-repo (image_decode.py), JPEG needs Pillow (optional).
 Buffers may be base64 data URIs or files next to the .gltf.
+Beyond the reference's loader (which draws every asset in its bind pose): skins, morph targets and animation clips. A primitive with
+JOINTS_0 / WEIGHTS_0 or `targets` carries them in the Mesh's optional fields, the Model carries `skins`, `animations` and `nodes`;
+everything the loader returned before is unchanged, a skinned primitive's `transform` included. `Animator` samples a clip with the
+semantics of the glTF 2.0 specification and poses the meshes through Renderer.pose_mesh (include/utopian_hip.h "posed meshes").
 `instance_transform_3x4` applies the scale-rotation-translation round trip of
 Raytracing::fill_instance_array (raytracing.rs:229-248), which drops shear.
 """
 import base64
 import json
 import os
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -27,6 +32,50 @@ from .types import LAMBERTIAN, VERTEX_DTYPE
 f32 = np.float32
 _COMPONENT = {5120: np.int8, 5121: np.uint8, 5122: np.int16, 5123: np.uint16, 5125: np.uint32, 5126: np.float32}
 _NUM = {"SCALAR": 1, "VEC2": 2, "VEC3": 3, "VEC4": 4, "MAT4": 16}
+
+
+@dataclass
+class Node:
+    """a glTF node: its static local transform as TRS (or `matrix`, 4x4 row-major float64, when the file gives one) and its links"""
+    name: str = ""
+    parent: int = None
+    children: list = field(default_factory=list)
+    translation: np.ndarray = None  # (3,) float64
+    rotation: np.ndarray = None     # (4,) float64, xyzw
+    scale: np.ndarray = None        # (3,) float64
+    matrix: np.ndarray = None
+    mesh: int = None
+    skin: int = None
+    weights: np.ndarray = None      # (T,) float64: the node's own morph weights, None when absent
+
+
+@dataclass
+class Skin:
+    joints: list                    # node indices
+    inverse_bind: np.ndarray        # (J, 4, 4) float64, row-major; identities when the file has no inverseBindMatrices
+    skeleton: int = None
+    name: str = ""
+
+
+@dataclass
+class AnimationSampler:
+    times: np.ndarray               # (K,) float64, ascending
+    values: np.ndarray              # (K, C) float64; CUBICSPLINE: (K, 3, C) - in-tangent, value, out-tangent
+    interpolation: str = "LINEAR"
+
+
+@dataclass
+class AnimationChannel:
+    node: int
+    path: str                       # translation | rotation | scale | weights
+    sampler: int
+
+
+@dataclass
+class Animation:
+    name: str = ""
+    samplers: list = field(default_factory=list)
+    channels: list = field(default_factory=list)
 
 
 def _load_uri(uri, base_dir):
@@ -110,18 +159,193 @@ def load_gltf(path):
             if "COLOR_0" in attrs:
                 c = _accessor(gltf, buffers, attrs["COLOR_0"], True)
                 v["color"][:, : c.shape[1]] = c
+            rig = _primitive_rig(gltf, buffers, node, prim, len(pos))
             mat = gltf["materials"][prim["material"]] if "material" in prim else {}
             pbr = mat.get("pbrMetallicRoughness", {})
             tex = pbr.get("baseColorTexture", {}).get("index")
             mesh = Mesh(v, idx, LAMBERTIAN, 0.0, tuple(float(x) for x in pbr.get("baseColorFactor", [1, 1, 1, 1])), tex, transform[:3, :].reshape(12).copy(),
-                        name=mat.get("name", node.get("name", "")), metallic=float(pbr.get("metallicFactor", 1.0)), roughness=float(pbr.get("roughnessFactor", 1.0)))
+                        name=mat.get("name", node.get("name", "")), metallic=float(pbr.get("metallicFactor", 1.0)), roughness=float(pbr.get("roughnessFactor", 1.0)), node=index, **rig)
             model.meshes.append(mesh)
 
     scenes = gltf.get("scenes", [])
     for scene in scenes:
         for n in scene.get("nodes", []):
             load_node(n, np.eye(4, dtype=f32))
+    _load_rig(gltf, buffers, model)
     return model
+
+
+def _primitive_rig(gltf, buffers, node, prim, n):
+    """the optional Mesh fields of a primitive: JOINTS_0 / WEIGHTS_0 (with the node's skin) and the morph targets"""
+    attrs, rig = prim["attributes"], {}
+    if "JOINTS_1" in attrs or "WEIGHTS_1" in attrs:
+        raise NotImplementedError("JOINTS_1 / WEIGHTS_1: more than four influences per vertex")
+    if "JOINTS_0" in attrs and "WEIGHTS_0" in attrs and "skin" in node:
+        rig.update(joints=_accessor(gltf, buffers, attrs["JOINTS_0"]).astype(np.uint16), weights=_accessor(gltf, buffers, attrs["WEIGHTS_0"], True).astype(f32),
+                   skin=int(node["skin"]))
+    targets = prim.get("targets", [])
+    if targets and all("POSITION" in t for t in targets):
+        rig["morph_positions"] = np.stack([_accessor(gltf, buffers, t["POSITION"], True) for t in targets]).astype(f32)
+        if all("NORMAL" in t for t in targets):
+            rig["morph_normals"] = np.stack([_accessor(gltf, buffers, t["NORMAL"], True) for t in targets]).astype(f32)
+        w = gltf["meshes"][node["mesh"]].get("weights")
+        rig["morph_default_weights"] = np.zeros(len(targets), dtype=f32) if w is None else np.array(w, dtype=f32)
+        assert rig["morph_positions"].shape == (len(targets), n, 3)
+    return rig
+
+
+def _load_rig(gltf, buffers, model):
+    """Model.nodes / skins / animations"""
+    for n in gltf.get("nodes", []):
+        node = Node(name=n.get("name", ""), children=list(n.get("children", [])), mesh=n.get("mesh"), skin=n.get("skin"),
+                    translation=np.array(n.get("translation", [0, 0, 0]), dtype=np.float64), rotation=np.array(n.get("rotation", [0, 0, 0, 1]), dtype=np.float64),
+                    scale=np.array(n.get("scale", [1, 1, 1]), dtype=np.float64), weights=None if "weights" not in n else np.array(n["weights"], dtype=np.float64))
+        if "matrix" in n:
+            node.matrix = np.array(n["matrix"], dtype=np.float64).reshape(4, 4).T
+        model.nodes.append(node)
+    for i, node in enumerate(model.nodes):
+        for c in node.children:
+            model.nodes[c].parent = i
+    for s in gltf.get("skins", []):
+        joints = [int(j) for j in s["joints"]]
+        if "inverseBindMatrices" in s:
+            ibm = _accessor(gltf, buffers, s["inverseBindMatrices"], True).astype(np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)  # column-major in the file
+        else:
+            ibm = np.tile(np.eye(4), (len(joints), 1, 1))
+        assert len(ibm) == len(joints)
+        model.skins.append(Skin(joints, np.ascontiguousarray(ibm), s.get("skeleton"), s.get("name", "")))
+    for a in gltf.get("animations", []):
+        anim = Animation(a.get("name", ""))
+        for smp in a.get("samplers", []):
+            times = _accessor(gltf, buffers, smp["input"], True).astype(np.float64).reshape(-1)
+            values = _accessor(gltf, buffers, smp["output"], True).astype(np.float64)
+            anim.samplers.append(AnimationSampler(times, values, smp.get("interpolation", "LINEAR")))
+        for ch in a.get("channels", []):
+            if "node" not in ch["target"]:
+                continue  # (the specification: a channel without a target node is ignored)
+            anim.channels.append(AnimationChannel(int(ch["target"]["node"]), ch["target"]["path"], int(ch["sampler"])))
+        for ch in anim.channels:  # a sampler's output is (keys, components of its channel's path), three per key for CUBICSPLINE
+            smp = anim.samplers[ch.sampler]
+            if smp.values.ndim == 2:
+                k = len(smp.times)
+                smp.values = smp.values.reshape((k, 3, -1) if smp.interpolation == "CUBICSPLINE" else (k, -1))
+        model.animations.append(anim)
+
+
+def _trs(translation, rotation, scale):
+    """T * R * S as a 4x4, float64"""
+    x, y, z, w = rotation
+    m = np.eye(4)
+    m[:3, :3] = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                          [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                          [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]]) * np.asarray(scale)[None, :]
+    m[:3, 3] = translation
+    return m
+
+
+def _slerp(a, b, u):
+    """between unit quaternions on the shortest arc, renormalised"""
+    d = float(np.dot(a, b))
+    if d < 0.0:
+        b, d = -b, -d
+    if d > 0.9995:  # nearly parallel: the sine form loses its digits, the chord is the arc
+        q = a + u * (b - a)
+    else:
+        th = np.arccos(d)
+        q = (np.sin((1 - u) * th) * a + np.sin(u * th) * b) / np.sin(th)
+    return q / np.linalg.norm(q)
+
+
+def sample(sampler, t, rotation=False):
+    """the sampler's value at time t (clamped to its first and last key), float64: LINEAR (slerp for rotations), STEP or CUBICSPLINE.
+    A rotation is a unit quaternion whatever the file's float32 keys add up to: keys are normalised before they are used or blended on the
+    sphere, a spline's result after it is formed (the specification's rule)"""
+    times, values = sampler.times, sampler.values
+    cubic = sampler.interpolation == "CUBICSPLINE"
+    unit = (lambda q: q / np.linalg.norm(q)) if rotation else (lambda v: v.copy())
+    key = (lambda k: unit(values[k, 1])) if cubic else (lambda k: unit(values[k]))
+    t = min(max(float(t), times[0]), times[-1])
+    if len(times) == 1 or t >= times[-1]:
+        return key(len(times) - 1)
+    i = int(np.searchsorted(times, t, side="right")) - 1
+    dt = times[i + 1] - times[i]
+    u = (t - times[i]) / dt
+    if sampler.interpolation == "STEP":
+        return key(i)
+    if cubic:
+        u2, u3 = u * u, u * u * u
+        return unit((2 * u3 - 3 * u2 + 1) * values[i, 1] + dt * (u3 - 2 * u2 + u) * values[i, 2] + (-2 * u3 + 3 * u2) * values[i + 1, 1] + dt * (u3 - u2) * values[i + 1, 0])
+    if rotation:
+        return _slerp(key(i), key(i + 1), u)
+    return values[i] + u * (values[i + 1] - values[i])
+
+
+class Animator:
+    """Poses the rigged meshes of a Model of load_gltf at a time of one of its animation clips, with the semantics of the glTF 2.0
+    specification: channels target a node's translation, rotation, scale or morph weights; a property no channel targets keeps the
+    node's static value; global transforms are parent * local over the whole hierarchy; a skinned mesh's joint matrix k is
+    inverse(G_meshnode) @ G_joint(k) @ inverseBind(k), G_meshnode the rest-pose global transform of the node that carries the mesh -
+    the instance transform the mesh was added with -, so that the renderer's transform times the joint matrix places a vertex where
+    the specification does: at G_joint @ inverseBind @ v, whatever the mesh's node does. Computed in float64, rounded once."""
+
+    def __init__(self, model):
+        self.model = model
+        self.posable = [i for i, m in enumerate(model.meshes) if m.skin is not None or m.morph_positions is not None]
+        self._rest = self.globals(None, 0.0)[0]
+
+    def locals_at(self, animation, t):
+        """([4x4 local transform of every node], {node: morph weights}) at time t of clip `animation` (index, or None: the static scene)"""
+        nodes = self.model.nodes
+        trs = [dict(translation=n.translation, rotation=n.rotation, scale=n.scale) for n in nodes]
+        animated, weights = set(), {}
+        if animation is not None:
+            clip = self.model.animations[animation]
+            for ch in clip.channels:
+                value = sample(clip.samplers[ch.sampler], t, rotation=ch.path == "rotation")
+                if ch.path == "weights":
+                    weights[ch.node] = value
+                else:
+                    trs[ch.node][ch.path] = value
+                    animated.add(ch.node)
+        return [n.matrix if n.matrix is not None and i not in animated else _trs(**trs[i]) for i, n in enumerate(nodes)], weights
+
+    def globals(self, animation, t):
+        local, weights = self.locals_at(animation, t)
+        out = [None] * len(local)
+
+        def visit(i, parent):
+            out[i] = parent @ local[i]
+            for c in self.model.nodes[i].children:
+                visit(c, out[i])
+
+        for i, n in enumerate(self.model.nodes):
+            if n.parent is None:
+                visit(i, np.eye(4))
+        return out, weights
+
+    def pose(self, animation, t):
+        """{index into model.meshes: (joint_matrices (J, 12) float32 | None, morph_weights (T,) float32 | None)} for every skinned or
+        morphed mesh, at time t of clip `animation`"""
+        g, weights = self.globals(animation, t)
+        out = {}
+        for i in self.posable:
+            m = self.model.meshes[i]
+            jm = mw = None
+            if m.skin is not None:
+                skin = self.model.skins[m.skin]
+                to_mesh = np.linalg.inv(self._rest[m.node])
+                jm = np.stack([(to_mesh @ g[j] @ skin.inverse_bind[k])[:3, :].reshape(12) for k, j in enumerate(skin.joints)]).astype(f32)
+            if m.morph_positions is not None:
+                node = self.model.nodes[m.node]
+                w = weights.get(m.node, node.weights if node.weights is not None else m.morph_default_weights)
+                mw = np.asarray(w, dtype=np.float64).astype(f32)
+            out[i] = (jm, mw)
+        return out
+
+    def apply(self, renderer, mesh_ids, animation, t):
+        """poses the meshes `mesh_ids` (what renderer.add_model(model) returned) at time t; a refit or a build has to follow"""
+        for i, (jm, mw) in self.pose(animation, t).items():
+            renderer.pose_mesh(mesh_ids[i], jm, mw)
 
 
 def load_cube():

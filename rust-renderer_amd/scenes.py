@@ -67,6 +67,14 @@ class Mesh:
     name: str = ""
     metallic: float = 1.0   # GpuMaterial.metallic_factor / roughness_factor (renderer.rs:20-36); read by material type PBR only
     roughness: float = 1.0
+    # a rigged primitive of a glTF (gltf.load_gltf; Renderer.add_model hands them to set_mesh_skin / set_mesh_morph_targets): None without
+    joints: np.ndarray = None                 # (N, 4) uint16: JOINTS_0, indices into Model.skins[skin].joints
+    weights: np.ndarray = None                # (N, 4) float32: WEIGHTS_0
+    skin: int = None                          # index into Model.skins
+    morph_positions: np.ndarray = None        # (T, N, 3) float32: targets[].POSITION
+    morph_normals: np.ndarray = None          # (T, N, 3) float32: targets[].NORMAL, None when a target has none
+    morph_default_weights: np.ndarray = None  # (T,) float32: the glTF mesh's `weights` (zeros when absent)
+    node: int = None                          # the glTF node that carries the mesh (index into Model.nodes)
 
     def material_struct(self):
         return make_material(self.material_type, self.material_property, self.base_color, metallic=self.metallic, roughness=self.roughness)
@@ -80,6 +88,10 @@ class Mesh:
 class Model:
     meshes: list = field(default_factory=list)
     textures: list = field(default_factory=list)
+    # of a glTF (gltf.Skin, gltf.Animation, gltf.Node): what gltf.Animator poses the rigged meshes from; empty otherwise
+    skins: list = field(default_factory=list)
+    animations: list = field(default_factory=list)
+    nodes: list = field(default_factory=list)
 
 
 @dataclass

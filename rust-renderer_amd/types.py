@@ -307,6 +307,17 @@ assert C.sizeof(MeshUpdateStats) == 32 and MeshUpdateStats.updates.offset == 8 a
     MeshUpdateStats.host_geometry_bytes.offset == 16 and MeshUpdateStats.device_bytes.offset == 24
 
 
+class PoseStats(C.Structure):
+    """UhPoseStats: uh_pose_mesh so far - hipEvent ms of the last k_pose, the poses, the last one's vertices, joints and active (non-zero)
+    targets, the largest joint count the kernel stages in LDS, and the device memory held for posed meshes"""
+
+    _fields_ = [("pose_ms", C.c_float), ("poses", C.c_uint32), ("vertices", C.c_uint32), ("joints", C.c_uint32), ("active_targets", C.c_uint32),
+                ("staged_joint_limit", C.c_uint32), ("device_bytes", C.c_uint64)]
+
+
+assert C.sizeof(PoseStats) == 32 and PoseStats.poses.offset == 4 and PoseStats.staged_joint_limit.offset == 20 and PoseStats.device_bytes.offset == 24
+
+
 # the hybrid graph's G-buffer pass rasterised (gbuffer.rs, gbuffer.vert / gbuffer.frag): a modifier of HYBRID_GBUFFER
 HYBRID_GBUFFER_RASTER = 1 << 11
 HYBRID_GBUFFER_DEPTH, HYBRID_GBUFFER_VISIBILITY = 11, 12
