@@ -248,17 +248,17 @@ typedef struct uh_ctx uh_ctx;
  *        posed positions back before the mesh takes them), uh_get_pose_stats, uh_read_denoised,
  *        uh_get_denoise_stats, uh_reset_denoise_history, uh_get_rtao_stats, uh_get_rtao_visits, uh_get_motion_stats, uh_reset_taa_history,
  *        uh_get_taa_stats, uh_post_image, uh_read_post, uh_get_post_stats, uh_get_rtgi_stats, uh_get_glossy_stats, uh_get_fog_stats,
- *        uh_get_fog_visits, uh_get_glass_stats, uh_destroy;
+ *        uh_get_fog_visits, uh_get_glass_stats, uh_get_area_light_stats, uh_read_area_emitters, uh_destroy;
  *   enqueues like a frame, ordered behind the frames in flight and before those that follow:  uh_rccl_gather_tiles, uh_mgpu_compose;
  *        uh_set_option for "frames_in_flight" and for "time_kernels" 1 -> 0 (the others only change what the NEXT enqueued
  *        frame does: "furnace", "sun_grid*", "camera_grid*", "overlap", "batch_frames", "trace_blocks_per_cu", "count_visits",
- *        "full_frame_restir", "primary_implicit", "rtao_order", "rtgi_order", "fog_order"; "device_build", "ploc_sah_top" invalidate the tree: the next frame
+ *        "full_frame_restir", "primary_implicit", "rtao_order", "rtgi_order", "fog_order", "area_light_order"; "device_build", "ploc_sah_top" invalidate the tree: the next frame
  *        needs uh_build_acceleration, which waits);
  *   host state only (no device access, nothing to wait for):  uh_add_mesh, uh_add_light, uh_set_instance_transform,
  *        uh_get_num_lights, uh_mesh_info, uh_read_mesh, uh_get_restir_rows, uh_tile_pack_count, uh_set_rtao_params, uh_set_taa_params,
- *        uh_set_post_params, uh_reset_post_exposure, uh_set_rtgi_params, uh_set_glossy_params, uh_set_fog_params, uh_set_glass_params (read by the next uh_render_hybrid; the post
+ *        uh_set_post_params, uh_reset_post_exposure, uh_set_rtgi_params, uh_set_glossy_params, uh_set_fog_params, uh_set_glass_params, uh_set_area_light_params (read by the next uh_render_hybrid; the post
  *        pair also by the next uh_post_image), uh_taa_default_params, uh_taa_jitter, uh_post_default_params, uh_post_level_size,
- *        uh_rtgi_default_params, uh_glossy_default_params, uh_fog_default_params, uh_glass_default_params,
+ *        uh_rtgi_default_params, uh_glossy_default_params, uh_fog_default_params, uh_glass_default_params, uh_area_light_default_params,
  *        uh_last_error
  *        (uh_read_mesh of a mesh that uh_update_isosurface_mesh has made device-resident, or that uh_update_mesh_vertices last updated
  *        from a device pointer, copies it from the device: a blocking copy);
@@ -714,7 +714,7 @@ int uh_mgpu_set_option(uh_mgpu* group, const char* name, int value);
  * UH_HYBRID_RT_REFLECTIONS with view->ibl_enabled == 1 is UH_ERR_INVALID_ARGUMENT - and nothing runs - until the IBL maps (irradiance,
  * specular, BRDF LUT of ibl.rs) have been built with UH_HYBRID_ENVIRONMENT, below; mask bits, UH_ERR_NOT_BUILT and moved instances with
  * view->rebuild_tlas as for uh_render_frame (bits above UH_HYBRID_SHADOW_MAPS, below, are ignored, except UH_HYBRID_MARCHING_CUBES,
- * UH_HYBRID_GBUFFER_RASTER, UH_HYBRID_RESTIR_LIGHTS, UH_HYBRID_RTAO, UH_HYBRID_MOTION, UH_HYBRID_TAA, UH_HYBRID_POST, UH_HYBRID_RTGI, UH_HYBRID_GLOSSY, UH_HYBRID_FOG and UH_HYBRID_GLASS).
+ * UH_HYBRID_GBUFFER_RASTER, UH_HYBRID_RESTIR_LIGHTS, UH_HYBRID_RTAO, UH_HYBRID_MOTION, UH_HYBRID_TAA, UH_HYBRID_POST, UH_HYBRID_RTGI, UH_HYBRID_GLOSSY, UH_HYBRID_FOG and UH_HYBRID_GLASS); UH_HYBRID_AREA_LIGHTS is not ignored either.
  * STREAM ORDER: uh_render_hybrid enqueues like a frame (behind the frames in flight, ahead of those that follow); uh_read_hybrid and
  * uh_get_hybrid_stats wait for all work of the context and are complete on return. The exception is UH_HYBRID_SHADOW_MAPS, below: a
  * call that renders shadow maps BLOCKS the host until the frames in flight and the pass's binning have finished (it reads the
@@ -1751,6 +1751,110 @@ UH_LAYOUT_ASSERT(sizeof(UhGlassStats) == 80 && offsetof(UhGlassStats, chains) ==
 int uh_glass_default_params(UhGlassParams* out); /* needs no GPU: 8, 16.0, 1.0; UH_ERR_INVALID_ARGUMENT for NULL */
 int uh_set_glass_params(uh_ctx* ctx, const UhGlassParams* params); /* validated here; a refused call leaves the old ones */
 int uh_get_glass_stats(uh_ctx* ctx, UhGlassStats* out);            /* waits; all zero before the first pass */
+
+/* ---- emissive meshes as area lights for the hybrid frame: direct light from the scene's own lamps, with soft shadows --------------------
+ * An EXTENSION: the reference's closest-hit shader leaves its fourth material, the diffuse light, a "Todo" (reference.rchit:84-89: the path
+ * ends with white), and its hybrid frame shades such a mesh as an ordinary surface. UH_HYBRID_AREA_LIGHTS (bit 21) adds one pass to
+ * uh_render_hybrid directly AFTER the deferred pass and BEFORE the rtgi pass - and so before the glossy, glass, marching-cubes, sky, fog,
+ * taa, post and present passes: TAA and the display chain see it. UH_HYBRID_FRAME | UH_HYBRID_AREA_LIGHTS is the natural call. The
+ * deferred pass itself is untouched: this pass adds to deferred_output on the pixels that cast and writes the emitters' own pixels.
+ *   emitters  the triangles of every mesh whose raytrace_properties.x == 3, in a table whose order does not depend on the tree: meshes
+ *             in uh_add_mesh order, primitives in index order, slot = base[mesh] + prim. The table is filled on the device from the
+ *             tree's own triangle packets (world-space v0, e1, e2), so it follows uh_set_instance_transform, uh_update_mesh_vertices,
+ *             uh_pose_mesh, uh_update_isosurface_mesh, a refit and a rebuild, host- or device-built, with the same bytes. Ng =
+ *             cross(e1, e2), area = 0.5 * sqrt(dot(Ng, Ng)), a non-finite area counts as 0. Integer weights: with N emitters, b = 31 -
+ *             bit_length(N - 1) and amax = m * 2^x (frexpf) the largest area, q = max(1, trunc(ldexpf(area, b - x))) for area > 0, else
+ *             0; cum the inclusive prefix of q, total = cum[N - 1] <= 2^31. Rebuilt, on the context's stream, by the first pass after a
+ *             build or refit; never otherwise.
+ *   pixels    RTAO's rule first: position texel w != 0 and Nn = normalize(N) finite. Then the material record as deferred.frag forms it
+ *             (index uint(pbr.a), in range): a pixel of type 3, or of type 1 with view->raytracing_supported == 1 (it holds its
+ *             reflection), does not cast. With total == 0 no pixel casts.
+ *   samples   a pixel (px, py) that casts takes `samples` of them; sample s draws from the state initRNG(px, py, W, (frameNumber(view) *
+ *             64 + s) ^ 0x41524541) the 32-bit word r that randomFloat would convert, then u1 and u2 = randomFloat. The emitter i is the
+ *             first slot with cum[i] > ((uint64_t)r * total) >> 32; its point Y = (v0 + u1 e1) + u2 e2 after u1 + u2 > 1 folds both to
+ *             1 - u. With w = Y - P, d2 = dot(w, w), l = w / sqrt(d2), cosL = |dot(Ng, l)| / sqrt(dot(Ng, Ng)) (emitters shine from both
+ *             faces), NdotL = dot(N, l) and G = min((cosL / d2) * ((area * total) / q), max_weight): the sample is AWAY - it adds nothing and
+ *             casts no ray - when d2, NdotL or cosL is not > 0 or G is NaN. Otherwise one any-hit ray from o = offsetRay(P, Nn) toward Y,
+ *             tmin 0.001, tmax 0.999 |Y - o|: a hit makes it OCCLUDED, none (or an empty interval) LIT. A LIT sample brings the two halves
+ *             of deferred.frag's surfaceShading for direction l and radiance Li = (1, 1, 1) * G - the emission every other pass gives type
+ *             3 -: d = kD * (Li * NdotL), without base / PI, and s = specular * (Li * NdotL).
+ *   pixel     D = (d_0 + ... + d_{samples-1}) / (float)samples and Sp likewise, summed in sample order (AWAY and OCCLUDED add +0), then per
+ *             channel min(x > 0 ? x : 0, max_radiance): a NaN is 0, the value is finite and does not depend on the schedule.
+ *   filter    UH_HYBRID_RTGI's, on D and on Sp alike: blur_radius 0 is the identity; r > 0: the mean over the taps (dx, dy) in [-r, r]^2
+ *             (dy outer) that lie in the frame, cast themselves and pass dot(Nn_tap, Nn) >= blur_normal_cos and |dot(P_tap - P, Nn)| <=
+ *             blur_plane; the centre always counts. The base colour is applied after the filter and stays sharp.
+ *   composite for every pixel that cast, with base = pow(albedo, 2.2) * base_color as deferred.frag:61-65 forms it: add = (((base / PI) *
+ *             Df) + Spf) * intensity; deferred_output.rgb += add, alpha untouched. No occlusion, ssao or shadow factor: direct light,
+ *             shadowed by its own rays. A pixel whose position texel has w != 0 and whose material is type 3 gets deferred_output.rgb =
+ *             (1, 1, 1) * intensity when show_emitters == 1 and is left alone when it is 0. Under option "furnace" the pass runs unchanged.
+ * PARAMS: uh_set_area_light_params validates and keeps them for the calls that follow (a refused call leaves the old ones); before the
+ * first call the defaults of uh_area_light_default_params hold: 2 samples, blur_radius 3, show_emitters 1, max_weight 64.0, max_radiance
+ * 16.0, intensity 1.0, 0.9, 0.05.
+ * UH_ERR_INVALID_ARGUMENT with a message, and nothing runs, in this order after every rule above (UH_HYBRID_GLASS's included): the bit and
+ * view->raytracing_supported != 1; no G-buffer rendered in this call or an earlier one; the bit without UH_HYBRID_DEFERRED in the same
+ * call. UH_ERR_CAPACITY for a frame of 2^28 pixels or more, and for more than 2^20 emitter triangles, at the call that sets the bit.
+ * There is no ibl_enabled rule: this is direct light. UH_ERR_NOT_BUILT before uh_build_acceleration, as without the bit. A scene without
+ * emitters, or with degenerate ones alone, is no refusal: no pixel casts, the images are zero and deferred_output stays what it was.
+ * READ-BACK (uh_read_hybrid, UH_ERR_INVALID_ARGUMENT before the first area-light pass; all three in G-buffer orientation):
+ * UH_HYBRID_AREA_DIFFUSE, RGBA32F: Df, w = 1 where the pixel cast, (0, 0, 0, 0) elsewhere. UH_HYBRID_AREA_SPECULAR, RGBA32F: Spf, w
+ * likewise. UH_HYBRID_AREA_COUNTS, 4 bytes per pixel: the samples that were lit, occluded and away, and 0; they sum to `samples` where the
+ * pixel cast and are all 0 elsewhere. uh_read_area_emitters reads the table back.
+ * RESOURCES: 72 bytes per pixel (counts, the two images, their unfiltered means, the queue of the pixels that cast), 64 bytes per sample
+ * (its two records and its ray) at the largest `samples` a pass has run with, and 64 bytes per emitter triangle, allocated by the first
+ * pass; freed by uh_destroy. A context that never sets the bit allocates nothing for it.
+ * STREAM ORDER: as uh_render_hybrid. uh_set_area_light_params is host state, read by the next uh_render_hybrid; uh_get_area_light_stats
+ * and uh_read_area_emitters wait.
+ * ISOLATION: the bit changes no reservoir, accumulation, gbuffer_position, grid, UhStats, RTAO, RTGI, glossy, glass or fog state, and no
+ * hybrid image but deferred_output (and what later passes of the call make of it) and its own three. Without the bit every pass, image,
+ * statistic and allocation is what it was.
+ * No uh_mgpu_ twin.
+ * OPTIONS: "area_light_order" 0 (default) or 1 lays the sample kernel's work out (same images whichever; DESIGN.md section 4 "Area lights").
+ * OUT OF SCOPE: emission other than (1, 1, 1) (textures, strengths); emitters in the path tracer, ReSTIR, the forward graph, or at the
+ * hits of RTGI, GLOSSY, GLASS or FOG rays; mapping glTF emissiveFactor in the loaders; light hierarchies or reservoir resampling of the
+ * picks; a history of its own (UH_HYBRID_TAA serves).
+ * Arithmetic: DESIGN.md section 2, "Area lights". */
+enum { UH_HYBRID_AREA_LIGHTS = 1u << 21 };
+enum { UH_HYBRID_AREA_DIFFUSE = 28 /* RGBA32F: Df, w = 1 where the pixel cast */, UH_HYBRID_AREA_SPECULAR = 29 /* RGBA32F: Spf, w likewise */,
+       UH_HYBRID_AREA_COUNTS = 30 /* 4 x uint8: lit, occluded, away, 0 */ };
+typedef struct UhAreaLightParams {
+   uint32_t samples;       /* samples per pixel that casts, 1..16 */
+   uint32_t blur_radius;   /* 0 = no filter; else 1..6: taps dx, dy in [-r, r] */
+   uint32_t show_emitters; /* 1: a type-3 pixel is written (1, 1, 1) * intensity; 0: it is left alone */
+   float max_weight;       /* the cap of a sample's G = (cosL / d2) / pdf; finite, > 0 */
+   float max_radiance;     /* the cap of D and Sp per channel; finite, > 0 */
+   float intensity;        /* scales what the composite adds and the emitter pixels; finite, >= 0 */
+   float blur_normal_cos;  /* a tap counts when dot(Nn_tap, Nn) >= this; not NaN */
+   float blur_plane;       /* and |dot(P_tap - P, Nn)| <= this (world units); not NaN */
+} UhAreaLightParams;
+UH_LAYOUT_ASSERT(sizeof(UhAreaLightParams) == 32 && offsetof(UhAreaLightParams, blur_radius) == 4 && offsetof(UhAreaLightParams, show_emitters) == 8 &&
+                    offsetof(UhAreaLightParams, max_weight) == 12 && offsetof(UhAreaLightParams, max_radiance) == 16 &&
+                    offsetof(UhAreaLightParams, intensity) == 20 && offsetof(UhAreaLightParams, blur_normal_cos) == 24 &&
+                    offsetof(UhAreaLightParams, blur_plane) == 28,
+                 "UhAreaLightParams (32 B)");
+/* the last area-light pass: the pixels that cast, their samples (pixels * samples), the shadow rays cast (the samples that were not away),
+ * those that were occluded, the emitter pixels; the table's emitter triangles N, its total weight and how often it has been built; and
+ * the hipEvent times of the last table build, of classify + sampling, of the shadow rays' any-hit walk, of the means + filter and of the
+ * composite. All zero before the first pass. Waits for all work of the context. */
+typedef struct UhAreaLightStats {
+   uint64_t pixels, samples, shadow_rays, occluded, emitter_pixels, emitters, total_weight, table_builds;
+   float table_ms, sample_ms, shadow_ms, filter_ms, composite_ms;
+   uint32_t reserved;
+} UhAreaLightStats;
+UH_LAYOUT_ASSERT(sizeof(UhAreaLightStats) == 88 && offsetof(UhAreaLightStats, samples) == 8 && offsetof(UhAreaLightStats, shadow_rays) == 16 &&
+                    offsetof(UhAreaLightStats, occluded) == 24 && offsetof(UhAreaLightStats, emitter_pixels) == 32 &&
+                    offsetof(UhAreaLightStats, emitters) == 40 && offsetof(UhAreaLightStats, total_weight) == 48 &&
+                    offsetof(UhAreaLightStats, table_builds) == 56 && offsetof(UhAreaLightStats, table_ms) == 64 &&
+                    offsetof(UhAreaLightStats, sample_ms) == 68 && offsetof(UhAreaLightStats, shadow_ms) == 72 &&
+                    offsetof(UhAreaLightStats, filter_ms) == 76 && offsetof(UhAreaLightStats, composite_ms) == 80 &&
+                    offsetof(UhAreaLightStats, reserved) == 84,
+                 "UhAreaLightStats (88 B)");
+int uh_area_light_default_params(UhAreaLightParams* out); /* needs no GPU: 2, 3, 1, 64.0, 16.0, 1.0, 0.9, 0.05; UH_ERR_INVALID_ARGUMENT for NULL */
+int uh_set_area_light_params(uh_ctx* ctx, const UhAreaLightParams* params); /* validated here; a refused call leaves the old ones */
+int uh_get_area_light_stats(uh_ctx* ctx, UhAreaLightStats* out);            /* waits; all zero before the first pass */
+/* The emitter table of the last area-light pass, in slot order: the packet keys (mesh << 22 | prim), the areas and the integer weights of
+ * its first min(capacity, N) slots into whichever of the three arrays is not NULL, and N into *count. capacity == 0 returns the count
+ * alone. Waits. UH_ERR_INVALID_ARGUMENT for a NULL count, and before the first pass. */
+int uh_read_area_emitters(uh_ctx* ctx, uint32_t capacity, uint32_t* keys, float* areas, uint32_t* weights, uint32_t* count);
 
 #ifdef __cplusplus
 }

@@ -339,7 +339,7 @@ class Renderer {
                               which == UH_HYBRID_DEPTH || which == UH_HYBRID_MARCHING_CUBES_VISIBILITY || which == UH_HYBRID_GBUFFER_DEPTH ||
                               which == UH_HYBRID_GBUFFER_VISIBILITY || which == UH_HYBRID_TAA_HISTORY || which == UH_HYBRID_GI_COUNTS ||
                               which == UH_HYBRID_GLOSSY_COUNTS || which == UH_HYBRID_FOG_MASK || which == UH_HYBRID_GLASS_COUNTS ||
-                              which == UH_HYBRID_GLASS_EVENTS) ? 4
+                              which == UH_HYBRID_GLASS_EVENTS || which == UH_HYBRID_AREA_COUNTS) ? 4
                                                                      : 16;  // (UH_HYBRID_MOTION_IMAGE and UH_HYBRID_TAA_OUTPUT among them)
       static_assert(UH_HYBRID_MOTION_IMAGE == 15, "read_hybrid sizes image 15 as 16-byte texels");
       std::vector<uint8_t> out((size_t)width_ * height_ * texel);
@@ -427,6 +427,33 @@ class Renderer {
       UhGlassStats s;
       check(uh_get_glass_stats(ctx_, &s), "glass_stats");
       return s;
+   }
+   // emissive meshes as area lights directly behind the deferred pass of render_hybrid (UH_HYBRID_AREA_LIGHTS; utopian_hip.h): the params of
+   // the calls that follow, and the last pass's pixels, samples, shadow rays, emitter table figures and times; its images through
+   // read_hybrid: the two means 16 bytes a texel, the counts 4
+   static UhAreaLightParams default_area_light_params() {
+      UhAreaLightParams p;
+      if (uh_area_light_default_params(&p) != UH_OK) throw Error(UH_ERR_INVALID_ARGUMENT, "uh_area_light_default_params");
+      return p;
+   }
+   void set_area_light_params(const UhAreaLightParams& params) { check(uh_set_area_light_params(ctx_, &params), "set_area_light_params"); }
+   UhAreaLightStats area_light_stats() {
+      UhAreaLightStats s;
+      check(uh_get_area_light_stats(ctx_, &s), "area_light_stats");
+      return s;
+   }
+   // the emitter table of the last area-light pass in slot order: keys (mesh << 22 | prim), areas and integer weights
+   struct AreaEmitters {
+      std::vector<uint32_t> keys;
+      std::vector<float> areas;
+      std::vector<uint32_t> weights;
+   };
+   AreaEmitters read_area_emitters() {
+      uint32_t n = 0;
+      check(uh_read_area_emitters(ctx_, 0, nullptr, nullptr, nullptr, &n), "read_area_emitters");
+      AreaEmitters e{std::vector<uint32_t>(n), std::vector<float>(n), std::vector<uint32_t>(n)};
+      if (n) check(uh_read_area_emitters(ctx_, n, e.keys.data(), e.areas.data(), e.weights.data(), &n), "read_area_emitters");
+      return e;
    }
    // volumetric fog behind the sky pass of render_hybrid (UH_HYBRID_FOG; utopian_hip.h): the params of the calls that follow, the last
    // pass's pixels, rays, lit rays and times, and with option "count_visits" its walks' node visits and triangle tests

@@ -7,6 +7,7 @@ from .api import (  # noqa: F401
     MultiGpuRenderer,
     Renderer,
     UtopianError,
+    area_light_default_params,
     default_denoise_params,
     default_view,
     fog_default_params,

@@ -36,8 +36,14 @@ from .types import (
     ENV_MIPS,
     ENV_SIZE,
     ENV_SPECULAR,
+    AreaLightParams,
+    AreaLightStats,
     HYBRID_ALBEDO,
     HYBRID_ALL,
+    HYBRID_AREA_COUNTS,
+    HYBRID_AREA_DIFFUSE,
+    HYBRID_AREA_LIGHTS,
+    HYBRID_AREA_SPECULAR,
     HYBRID_AO_COUNTS,
     HYBRID_GI_COUNTS,
     HYBRID_GI_RADIANCE,
@@ -205,6 +211,10 @@ _LIBRARY_VERBS = {
     "glass_default_params": [_p(GlassParams)],
     "set_glass_params": [_vp, _p(GlassParams)],
     "get_glass_stats": [_vp, _p(GlassStats)],
+    "area_light_default_params": [_p(AreaLightParams)],
+    "set_area_light_params": [_vp, _p(AreaLightParams)],
+    "get_area_light_stats": [_vp, _p(AreaLightStats)],
+    "read_area_emitters": [_vp, _u32, _vp, _vp, _vp, _p(_u32)],
     "get_motion_stats": [_vp, _p(MotionStats)],
     "taa_default_params": [_p(TaaParams)],
     "set_taa_params": [_vp, _p(TaaParams)],
@@ -685,6 +695,8 @@ class Renderer:
             self._taa_rendered = True
         if int(mask) & HYBRID_GLASS:
             self._glass_rendered = True
+        if int(mask) & HYBRID_AREA_LIGHTS:
+            self._area_rendered = True
 
     _HYBRID_IMAGES = {
         HYBRID_POSITION: (np.float32, 4),
@@ -716,6 +728,9 @@ class Renderer:
     # the three images of HYBRID_GLASS, which exist once a render_hybrid call with the bit has succeeded on this renderer (_glass_rendered)
     _GLASS_IMAGES = {HYBRID_GLASS_RADIANCE: (np.float32, 4), HYBRID_GLASS_COUNTS: (np.uint8, 4), HYBRID_GLASS_EVENTS: (np.uint8, 4)}
     _glass_rendered = False
+    # the three images of HYBRID_AREA_LIGHTS, which exist once a render_hybrid call with the bit has succeeded on this renderer (_area_rendered)
+    _AREA_IMAGES = {HYBRID_AREA_DIFFUSE: (np.float32, 4), HYBRID_AREA_SPECULAR: (np.float32, 4), HYBRID_AREA_COUNTS: (np.uint8, 4)}
+    _area_rendered = False
 
     def read_hybrid(self, which):
         """one image of the hybrid graph: (H, W, 4) float32 position / normal / pbr / deferred output, (H, W, 4) uint8 albedo / reflections /
@@ -729,12 +744,13 @@ class Renderer:
         ray counts (sunlit, dark, emitter, missed), and of HYBRID_FOG (H, W) uint32 masks (bit k: sample k saw the sun) and (H, W, 4) float32
         terms (a, Ttot, F, Ff; all 0 where the pixel did not march), and once a call with HYBRID_GLASS has run (H, W, 4) float32 glass
         radiance (C, 1 where the pixel cast), (H, W, 4) uint8 chain counts (sunlit, dark, emitter, missed) and (H, W, 4) uint8 events (chain 0,
-        chain 1, flags, 0)"""
+        chain 1, flags, 0), and once a call with HYBRID_AREA_LIGHTS has run (H, W, 4) float32 filtered diffuse and specular means of the
+        area lights (w = 1 where the pixel cast) and (H, W, 4) uint8 sample counts (lit, occluded, away, 0)"""
         images = {**self._HYBRID_IMAGES, **(self._TAA_IMAGES if self._taa_rendered else {}), **self._GI_IMAGES, **self._GLOSSY_IMAGES,
-                  **self._FOG_IMAGES, **(self._GLASS_IMAGES if self._glass_rendered else {})}
+                  **self._FOG_IMAGES, **(self._GLASS_IMAGES if self._glass_rendered else {}), **(self._AREA_IMAGES if self._area_rendered else {})}
         return self._read_image(images, self._hybrid_api().read_hybrid, which,
-                                f"hybrid image index {which} (0..15, 18..24, 16..17 once a render_hybrid call with HYBRID_TAA has run "
-                                f"and 25..27 once one with HYBRID_GLASS has)")
+                                f"hybrid image index {which} (0..15, 18..24, 16..17 once a render_hybrid call with HYBRID_TAA has run, "
+                                f"25..27 once one with HYBRID_GLASS has and 28..30 once one with HYBRID_AREA_LIGHTS has)")
 
     def hybrid_stats(self):
         return self._stats(HybridStats, self._hybrid_api().get_hybrid_stats)
@@ -821,6 +837,30 @@ class Renderer:
         """UhGlassStats of the last glass pass: pixels, chains, segments, events, tir, cut, shadow_rays, misses, trace_ms, bend_ms, shadow_ms,
         composite_ms"""
         return self._stats(GlassStats, self._hip_only(self._GLASS, "get_glass_stats"))
+
+    # -- emissive meshes as area lights (HYBRID_AREA_LIGHTS; include/utopian_hip.h "UH_HYBRID_AREA_LIGHTS") ---
+    _AREA = "area lights are a per-context verb"
+
+    def set_area_light_params(self, params=None, **fields):
+        """uh_set_area_light_params: `params` (an AreaLightParams; the defaults when None) with `fields` set on a copy - the params of the
+        render_hybrid calls with HYBRID_AREA_LIGHTS that follow. A refused call raises and leaves the old ones."""
+        return self._set_params(AreaLightParams, self._hip_only(self._AREA, "set_area_light_params"), area_light_default_params, params, fields)
+
+    def area_light_stats(self):
+        """UhAreaLightStats of the last area-light pass: pixels, samples, shadow_rays, occluded, emitter_pixels, emitters, total_weight,
+        table_builds, table_ms, sample_ms, shadow_ms, filter_ms, composite_ms"""
+        return self._stats(AreaLightStats, self._hip_only(self._AREA, "get_area_light_stats"))
+
+    def read_area_emitters(self):
+        """uh_read_area_emitters: the emitter table of the last area-light pass in slot order - keys (N,) uint32 (mesh << 22 | prim),
+        areas (N,) float32 and weights (N,) uint32"""
+        read = self._hip_only(self._AREA, "read_area_emitters")
+        n = C.c_uint32()
+        self._check(read(self._ctx, 0, None, None, None, C.byref(n)))
+        keys, areas, weights = np.zeros(n.value, np.uint32), np.zeros(n.value, np.float32), np.zeros(n.value, np.uint32)
+        if n.value:
+            self._check(read(self._ctx, n.value, keys.ctypes.data, areas.ctypes.data, weights.ctypes.data, C.byref(n)))
+        return keys, areas, weights
 
     # -- volumetric fog (HYBRID_FOG; include/utopian_hip.h "UH_HYBRID_FOG") ---
     _FOG = "volumetric fog is a per-context verb"
@@ -1181,6 +1221,11 @@ def _default_params(Struct, name):
     if _bind(load_library(), "uh_", name)(C.byref(p)) != 0:
         raise UtopianError(f"uh_{name} failed")
     return p
+
+
+def area_light_default_params():
+    """UhAreaLightParams as uh_area_light_default_params fills it (needs no GPU)"""
+    return _default_params(AreaLightParams, "area_light_default_params")
 
 
 def glass_default_params():

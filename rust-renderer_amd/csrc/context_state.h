@@ -688,6 +688,41 @@ struct uh_ctx {
          }
       } glass;
 
+      // emissive meshes as area lights (UH_HYBRID_AREA_LIGHTS), allocated by the first pass: per pixel the count words, the two images,
+      // their unfiltered means and the queue of the pixels that cast; the pass's counters (AreaDev::counters) and the table's two scalars.
+      // rec_d, rec_s (a record per sample each) and rays (two records per sample) are grown to the largest `samples` a pass has run with.
+      // The emitter table (AreaTableDev) is grown to the scene's emitter triangles and filled again when geom != the context's
+      // geom_version - a build or a refit has written the packets since; host_base: the per-mesh first slots as uploaded. params: the
+      // last uh_set_area_light_params (the defaults before); samples: the last pass's. stage: classify + sample, shadow, filter,
+      // composite of the last pass; table: the last table build.
+      struct __attribute__((visibility("hidden"))) AreaLights {
+         DevBuf<uint32_t> counts, queue, counters, amax;
+         DevBuf<unsigned long long> total;
+         DevBuf<float4> diffuse, specular, mean_d, mean_s, rec_d, rec_s, rays;
+         DevBuf<float4> tri;
+         DevBuf<uint32_t> keys, weights, cum, base, chunks;
+         DevBuf<float> areas;
+         std::vector<uint32_t> host_base;
+         UhAreaLightParams params{2, 3, 1, 64.0f, 16.0f, 1.0f, 0.9f, 0.05f};
+         Stage stage[4], table;
+         uint64_t geom = 0;                    // geom_version the table was filled for (0: never)
+         uint32_t emitters = 0, table_builds = 0, renders = 0, samples = 0;
+         uint32_t order = 0;                   // option "area_light_order" (area_lights.hip: how the sample kernel's work items are laid out)
+         template <class F> void images(size_t n, F&& f) {
+            f(counts, n), f(diffuse, n), f(specular, n), f(mean_d, n), f(mean_s, n), f(queue, n), f(amax, 1), f(total, 1), f(counters, 4);
+         }
+         template <class F> void stages(F&& f) {
+            for (Stage& s : stage) f(s);
+            f(table);
+         }
+         void destroy() {
+            images(0, ReleaseBuf{});
+            rec_d.release(), rec_s.release(), rays.release(), tri.release(), keys.release(), weights.release(), cum.release(), base.release(),
+               chunks.release(), areas.release();
+            stages([](Stage& s) { s.destroy(); });
+         }
+      } area;
+
       // motion vectors (UH_HYBRID_MOTION), allocated by the first call with the bit: the motion image, the pass's counts (pixels with /
       // without a correspondence, a pair per block of the kernel's grid, added up by uh_get_motion_stats), the per-mesh table the
       // kernels read, and the previous-position table (16-byte rows with bases of their own: isosurface meshes, which are never
@@ -769,7 +804,7 @@ struct uh_ctx {
 
       __attribute__((visibility("hidden"))) void destroy() {
          rt_images(0, ReleaseBuf{}), frame_images(0, ReleaseBuf{});
-         env.destroy(), sm.destroy(), gr.destroy(), mc.destroy(), rl.destroy(), ao.destroy(), gi.destroy(), gl.destroy(), glass.destroy(), fog.destroy(), mv.destroy(), taa.destroy(), post.destroy();
+         env.destroy(), sm.destroy(), gr.destroy(), mc.destroy(), rl.destroy(), ao.destroy(), gi.destroy(), gl.destroy(), glass.destroy(), area.destroy(), fog.destroy(), mv.destroy(), taa.destroy(), post.destroy();
          meshes.release(), vertices.release(), indices.release(), raw_lights.release();
          for (hipEvent_t ev : waits)
             if (ev) (void)hipEventDestroy(ev);

@@ -336,6 +336,42 @@ struct GlossyDev {
    uint32_t rt_on;                 // view.raytracing_supported == 1: type-1 pixels hold their mirror
    float max_roughness, max_radiance, intensity, blur_roughness, blur_normal_cos, blur_plane;
 };
+// emissive meshes as area lights of the hybrid frame (UH_HYBRID_AREA_LIGHTS; area_lights.hip). The emitter table, n slots in canonical
+// order (slot = base[mesh] + prim), filled from the tree's triangle packets; and what the pass's kernels read and write. Sample s of the
+// pixel in queue slot q is number q * samples + s in rec_d and rec_s; the samples that cast a ray are listed in `rays`
+struct AreaTableDev {
+   float4* tri;                    // 3 per slot: (v0, area), (e1, weight bits), (e2, 0)
+   uint32_t* keys;                 // the packet's key, mesh << kPrimBits | prim
+   float* areas;                   // 0.5 |cross(e1, e2)|, 0 when that is not finite
+   uint32_t* weights;              // q
+   uint32_t* cum;                  // the inclusive prefix of q
+   const uint32_t* base;           // per mesh: its first slot, kNoEmitter for a mesh that is no emitter
+   uint32_t* amax;                 // the bits of the largest area
+   unsigned long long* total;      // cum[n - 1]; 0 without emitters
+   uint32_t n, num_meshes;
+};
+constexpr uint32_t kNoEmitter = 0xffffffffu;
+struct AreaDev {
+   AreaTableDev tab;
+   uint32_t* counts;               // UH_HYBRID_AREA_COUNTS: a word per pixel, bytes (low first) lit, occluded, away, 0; added to by words
+   float4* diffuse;                // UH_HYBRID_AREA_DIFFUSE: Df.rgb, w = 1 where the pixel cast, else (0, 0, 0, 0)
+   float4* specular;               // UH_HYBRID_AREA_SPECULAR: Spf.rgb, w likewise
+   float4* mean_d;                 // D and Sp of the pixels that cast (the filter's input; not written when blur_radius is 0)
+   float4* mean_s;
+   float4* rec_d;                  // d_s and s_s of every sample, by sample number; zero for an AWAY or OCCLUDED one
+   float4* rec_s;
+   float4* rays;                   // 2 per queued shadow ray: (o, sample number bits), (Y, 0)
+   uint32_t* queue;                // the pixels that cast, compacted
+   uint32_t* counters;             // [0]: entries of `queue`, [1]: entries of `rays`, [2]: occluded rays, [3]: emitter pixels
+   uint32_t samples;               // UhAreaLightParams::samples
+   uint32_t frame_base;            // frameNumber(view) * 64: sample s seeds its state with (frame_base + s) ^ kAreaSeedXor
+   uint32_t blur_radius, show_emitters;
+   uint32_t rt_on;                 // view.raytracing_supported == 1: type-1 pixels hold their mirror
+   float max_weight, max_radiance, intensity, blur_normal_cos, blur_plane;
+};
+constexpr uint32_t kAreaSeedXor = 0x41524541u;  // keeps the samples from being another pass's own
+constexpr uint32_t kAreaMaxEmitters = 1u << 20;
+
 constexpr uint32_t kGlossySeedXor = 0x474C4F53u;  // keeps the samples from being the rtao or rtgi pass's own
 
 // volumetric fog of the hybrid frame (UH_HYBRID_FOG; fog.hip): what its kernels read and write

@@ -165,6 +165,20 @@ inline RtgiDev glass_sun_view(const GlassDev& gs) {
 }
 }  // namespace uh
 
+// ---- area_lights.hip ----
+// the area-light pass (UH_HYBRID_AREA_LIGHTS). table: the emitter table from the tree's packets (tab.amax zeroed and tab.base uploaded by
+// the caller; chunks: scan_chunk_count(tab.n) words). Then a launcher per timed stage, al.counters zeroed by the caller - sample: classify
+// (which pixels cast; the images zeroed; the emitters' own pixels written) and the samples, whose shadow rays are queued; shadow: their
+// any-hit walk; filter: the per-pixel means, then the filter when blur_radius is not 0; composite: into deferred_output
+namespace uh {
+uint32_t area_table_chunks(uint32_t n);  // the scan's scratch words for a table of n slots
+void launch_area_table(const LaunchCfg&, const SceneDev&, const AreaTableDev&, uint32_t* chunks);
+void launch_area_sample(const LaunchCfg&, const SceneDev&, const HybridDev&, const HybridFrameDev&, const AreaDev&, uint32_t order);
+void launch_area_shadow(const LaunchCfg&, const SceneDev&, const HybridDev&, const AreaDev&);
+void launch_area_filter(const LaunchCfg&, const HybridDev&, const AreaDev&);
+void launch_area_composite(const LaunchCfg&, const SceneDev&, const HybridDev&, const HybridFrameDev&, const AreaDev&);
+}  // namespace uh
+
 // ---- what the passes of one uh_render_hybrid call share ----
 struct HybridCall {
    const HybridPlan& plan;
@@ -201,6 +215,8 @@ int glass_alloc(uh_ctx* c);
 int glass_run(uh_ctx* c, const HybridCall& k);
 int fog_alloc(uh_ctx* c);
 int fog_run(uh_ctx* c, const HybridCall& k);
+int area_lights_alloc(uh_ctx* c);  // and the per-sample buffers of the params' samples, and the emitter table when the packets have changed
+int area_lights_run(uh_ctx* c, const HybridCall& k);
 
 // ---- post_graph.hip ----
 int post_alloc(uh_ctx* c);                                               // the display chain's images, counts and record (first post pass)

@@ -414,6 +414,7 @@ static int hybrid_prepare(uh_ctx* c, const HybridPlan& p) {
    if (p.glossy && (st = glossy_alloc(c))) return st;
    if (p.glass && (st = glass_alloc(c))) return st;
    if (p.fog && (st = fog_alloc(c))) return st;
+   if (p.area && (st = area_lights_alloc(c))) return st;
    if (p.env && (st = env_alloc(c))) return st;
    if (p.taa && (st = first_use(c, h.taa, h.taa.counters.p, [&](auto f) { h.taa.images(pixels, f); }))) return st;
    if (p.post && (st = post_alloc(c))) return st;
@@ -478,6 +479,8 @@ static void reset_stage_records(uh_ctx::Hybrid& h, const HybridPlan& p, uint32_t
    if (p.glossy) h.gl.stages(not_run);
    if (p.glass) h.glass.stages(not_run);
    if (p.fog) h.fog.stages(not_run);
+   if (p.area)
+      for (Stage& s : h.area.stage) not_run(s);  // (its table stage keeps the last build's time)
 }
 
 // the G-buffer pass: cast or rasterised, with the motion pass (`plan.motion`) on its hit records and the snapshot behind it
@@ -569,7 +572,7 @@ static int taa_pass(uh_ctx* c, const HybridCall& k) {
 
 // The passes in the order of build_render_graph (mod.rs:91-186, graph.rs:743), each between its stage's two events: setup_shadow_pass's
 // four cascades first, rt_shadows, gbuffer, setup_cubemap_pass, rt_reflections, then the final frame - ssao_pass (not with
-// ssao_enabled != 1, ssao.rs:27; the rtao pass takes its place), deferred_pass, the rtgi, glossy and glass passes (extensions), setup_marching_cubes_pass, atmosphere_pass, the fog pass (an
+// ssao_enabled != 1, ssao.rs:27; the rtao pass takes its place), deferred_pass, the area-light, rtgi, glossy and glass passes (extensions), setup_marching_cubes_pass, atmosphere_pass, the fog pass (an
 // extension; it attenuates and in-scatters into what the deferred and sky passes wrote), the taa pass
 // (an extension; present then reads its output), the post pass (an extension; it reads the taa pass's output or deferred_output, and
 // present then reads its own), present_pass
@@ -608,6 +611,7 @@ static int hybrid_passes(uh_ctx* c, const HybridCall& k, uint32_t mask) {
       });
       if (st) return st;
    }
+   if (p.area && (st = area_lights_run(c, k))) return st;
    if (p.rtgi && (st = rtgi_run(c, k))) return st;
    if (p.glossy && (st = glossy_run(c, k))) return st;
    if (p.glass && (st = glass_run(c, k))) return st;

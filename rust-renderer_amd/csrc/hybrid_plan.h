@@ -26,6 +26,7 @@ struct HybridPlan {
    bool raster, maps, render_maps, restir, rtao, rtgi, glossy, glass, fog, mc, motion, rt, taa, post;  // maps: the IBL maps exist for this call's consumers
    bool deferred, frame, env;  // the deferred pass runs; the final frame's images and the IBL maps are needed
    bool first, frame_first;    // the ray-traced images, the final frame's images are allocated by this call (and cleared)
+   bool area;                  // the area-light pass (UH_HYBRID_AREA_LIGHTS) runs, behind the deferred pass
 };
 
 // What a pass that casts rays from the G-buffer asks of a call, in the order it is asked (a null message: not asked): the view's
@@ -84,6 +85,13 @@ constexpr RayPassRules kGlassRules = {
    nullptr, UH_HYBRID_DEFERRED,
    "uh_render_hybrid: UH_HYBRID_GLASS without UH_HYBRID_DEFERRED in the same call: the pass replaces what the deferred pass writes on dielectric pixels and has nothing to write into; set UH_HYBRID_DEFERRED",
    0, nullptr, 32, "uh_render_hybrid: UH_HYBRID_GLASS: a frame of 2^27 pixels or more (its rays are numbered in 32 bits)"};
+constexpr RayPassRules kAreaLightRules = {
+   UH_HYBRID_AREA_LIGHTS,
+   "uh_render_hybrid: UH_HYBRID_AREA_LIGHTS casts shadow rays and view.raytracing_supported is not 1; set it, or clear the bit",
+   "uh_render_hybrid: UH_HYBRID_AREA_LIGHTS casts its rays from the G-buffer, and no G-buffer has been rendered; set UH_HYBRID_GBUFFER",
+   nullptr, UH_HYBRID_DEFERRED,
+   "uh_render_hybrid: UH_HYBRID_AREA_LIGHTS without UH_HYBRID_DEFERRED in the same call: the pass adds to what the deferred pass writes and has nothing to add to; set UH_HYBRID_DEFERRED",
+   0, nullptr, 16, "uh_render_hybrid: UH_HYBRID_AREA_LIGHTS: a frame of 2^28 pixels or more (its samples are numbered in 32 bits)"};
 
 // true when the request breaks one of r's rules: the first of them, in the order above, into p
 inline bool ray_pass_refused(const RayPassRules& r, const HybridFacts& f, const UhViewUniformData& view, uint32_t mask, HybridPlan& p) {
@@ -172,6 +180,9 @@ inline HybridPlan hybrid_plan(const HybridFacts& f, const UhViewUniformData& vie
    // ray-traced glass: two chains of rays per dielectric pixel, which replace what the passes before wrote there
    p.glass = (mask & UH_HYBRID_GLASS) != 0;
    if (p.glass && ray_pass_refused(kGlassRules, f, view, mask, p)) return p;
+   // emissive meshes as area lights: sampled points on the emitters, shadowed by any-hit rays, added directly behind the deferred pass
+   p.area = (mask & UH_HYBRID_AREA_LIGHTS) != 0;
+   if (p.area && ray_pass_refused(kAreaLightRules, f, view, mask, p)) return p;
    p.rt = view.raytracing_supported != 0;
    p.deferred = (mask & UH_HYBRID_DEFERRED) != 0;
    p.frame = (mask & (UH_HYBRID_SSAO | UH_HYBRID_DEFERRED | UH_HYBRID_SKY | UH_HYBRID_PRESENT)) || p.mc || p.rtao || p.taa || p.post;

@@ -1,13 +1,16 @@
 // hybrid_ray_passes.hip - the host side of uh_render_hybrid's passes that cast rays from the G-buffer (include/utopian_hip.h): the
-// reservoir lights, rtao, rtgi, glossy, glass and fog. Per pass its first use (what hybrid_prepare of hybrid_graph.hip calls when the
+// reservoir lights, rtao, rtgi, glossy, glass, area lights and fog. Per pass its first use (what hybrid_prepare of hybrid_graph.hip calls when the
 // plan has the pass), its run between its stages' events (what hybrid_passes calls, in the graph's order) and its verbs - default
 // params, set params, stats, visits. Host code over uh_ctx::Hybrid (context_state.h) that emits no kernel: those are
-// hybrid_kernels.hip, rtao.hip, rtgi.hip, glossy.hip, glass.hip and fog.hip. What a call asks of a pass before it runs is a row of
+// hybrid_kernels.hip, rtao.hip, rtgi.hip, glossy.hip, glass.hip, area_lights.hip and fog.hip. What a call asks of a pass before it runs is a row of
 // hybrid_plan.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <string>
+#include <utility>
+#include <vector>
 
 #include "graphs_internal.h"
 
@@ -342,6 +345,148 @@ int uh_get_glass_stats(uh_ctx* c, UhGlassStats* out) {
    out->chains = counters[kGlassRound0];
    for (uint32_t r = 1; r <= kGlassMaxEvents; r++) out->events += counters[kGlassRound0 + r];
    out->segments = out->chains + out->events;
+   return UH_OK;
+}
+
+// ---- emissive meshes as area lights (utopian_hip.h "UH_HYBRID_AREA_LIGHTS"; area_lights.hip) ----
+static AreaTableDev area_table_dev(const uh_ctx* c) {
+   const uh_ctx::Hybrid::AreaLights& a = c->hy.area;
+   return AreaTableDev{a.tri.p, a.keys.p, a.areas.p, a.weights.p, a.cum.p, a.base.p, a.amax.p, a.total.p, a.emitters, (uint32_t)a.host_base.size()};
+}
+
+// The emitter table for the tree as it stands: nothing when it was filled for this geom_version (every build and refit bumps it, and a
+// mesh's material type changes with uh_add_mesh alone, which asks for a build). Else the emitter meshes' first slots - a host prefix over
+// their triangle counts, in uh_add_mesh order - are uploaded and the table is filled, weighted and scanned on the context's stream.
+static int area_table(uh_ctx* c) {
+   uh_ctx::Hybrid::AreaLights& a = c->hy.area;
+   if (a.geom == c->geom_version) return UH_OK;
+   const char* const who = "uh_render_hybrid: UH_HYBRID_AREA_LIGHTS";
+   std::vector<uint32_t> base(c->meshes.size(), kNoEmitter);
+   uint64_t n = 0;
+   for (size_t i = 0; i < c->meshes.size(); i++) {
+      if (c->meshes[i].material.raytrace_properties[0] != 3.0f) continue;
+      base[i] = (uint32_t)n;
+      n += c->meshes[i].tris();
+      if (n > kAreaMaxEmitters) return fail(c, UH_ERR_CAPACITY, std::string(who) + ": more than 2^20 emitter triangles (the triangles of the meshes of material type 3)");
+   }
+   const size_t slots = std::max<uint64_t>(1, n), nm = std::max<size_t>(1, base.size());
+   if (a.tri.n < 3 * slots || a.base.n < nm) {
+      HIP_TRY(c, hipStreamSynchronize(c->stream));  // a pass in flight may still read the old table
+      for (int st : {grow(c, a.tri, 3 * slots, who), grow(c, a.keys, slots, who), grow(c, a.areas, slots, who), grow(c, a.weights, slots, who),
+                     grow(c, a.cum, slots, who), grow(c, a.chunks, std::max<uint32_t>(1, area_table_chunks((uint32_t)slots)), who), grow(c, a.base, nm, who)})
+         if (st) return st;
+   }
+   a.host_base = std::move(base);
+   a.emitters = (uint32_t)n;
+   const int st = timed(c, a.table, [&] {
+      HIP_TRY(c, hipMemsetAsync(a.amax.p, 0, sizeof(uint32_t), c->stream));
+      HIP_TRY(c, hipMemsetAsync(a.total.p, 0, sizeof(unsigned long long), c->stream));
+      if (n) {
+         // a slot no packet writes (there is none: every triangle has a packet) would be a degenerate emitter
+         HIP_TRY(c, hipMemsetAsync(a.tri.p, 0, 3 * slots * sizeof(float4), c->stream));
+         HIP_TRY(c, hipMemsetAsync(a.keys.p, 0, slots * sizeof(uint32_t), c->stream));
+         HIP_TRY(c, hipMemsetAsync(a.areas.p, 0, slots * sizeof(float), c->stream));
+         HIP_TRY(c, hipMemcpyAsync(a.base.p, a.host_base.data(), a.host_base.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+         launch_area_table(cfg(c), c->scene, area_table_dev(c), a.chunks.p);
+      }
+      return (int)UH_OK;
+   });
+   if (st) return st;
+   a.geom = c->geom_version;
+   a.table_builds++;
+   return UH_OK;
+}
+
+int area_lights_alloc(uh_ctx* c) {
+   uh_ctx::Hybrid::AreaLights& a = c->hy.area;
+   const char* const who = "uh_render_hybrid: UH_HYBRID_AREA_LIGHTS";
+   const size_t pixels = (size_t)c->W * c->H;
+   if (int st = first_use(c, a, a.counters.p, [&](auto f) { a.images(pixels, f); })) return st;
+   // the per-sample buffers, as the rtgi pass keeps its own
+   const size_t samples = pixels * a.params.samples;
+   if (a.rec_d.n < samples || a.rec_s.n < samples || a.rays.n < 2 * samples) {
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      for (int st : {grow(c, a.rec_d, samples, who), grow(c, a.rec_s, samples, who), grow(c, a.rays, 2 * samples, who)})
+         if (st) return st;
+   }
+   return area_table(c);
+}
+
+// the area-light pass directly behind deferred_pass: classify (which writes the emitters' own pixels) + the samples, whose shadow rays are
+// queued, those rays' any-hit walk, the per-pixel means + filter into the two images, then the composite into deferred_output; a stage each
+int area_lights_run(uh_ctx* c, const HybridCall& k) {
+   uh_ctx::Hybrid::AreaLights& a = c->hy.area;
+   const UhAreaLightParams& p = a.params;
+   const AreaDev al{area_table_dev(c), a.counts.p, a.diffuse.p, a.specular.p, a.mean_d.p, a.mean_s.p, a.rec_d.p, a.rec_s.p, a.rays.p, a.queue.p, a.counters.p,
+                    p.samples, k.fp.frame_number * 64u, p.blur_radius, p.show_emitters, k.fd.rt_on, p.max_weight, p.max_radiance, p.intensity,
+                    p.blur_normal_cos, p.blur_plane};
+   int st = timed(c, a.stage[0], [&] {
+      HIP_TRY(c, hipMemsetAsync(a.counters.p, 0, a.counters.n * sizeof(uint32_t), c->stream));
+      launch_area_sample(k.lc, c->scene, k.hd, k.fd, al, a.order);
+      return (int)UH_OK;
+   });
+   if (st) return st;
+   if ((st = timed(c, a.stage[1], [&] { launch_area_shadow(k.lc, c->scene, k.hd, al); }))) return st;
+   if ((st = timed(c, a.stage[2], [&] { launch_area_filter(k.lc, k.hd, al); }))) return st;
+   if ((st = timed(c, a.stage[3], [&] { launch_area_composite(k.lc, c->scene, k.hd, k.fd, al); }))) return st;
+   a.samples = p.samples;
+   a.renders++;
+   return UH_OK;
+}
+
+int uh_area_light_default_params(UhAreaLightParams* out) { return default_params<uh_ctx::Hybrid::AreaLights>(out); }
+
+static const char* area_light_params_refusal(const UhAreaLightParams& p) {
+   if (p.samples < 1 || p.samples > 16) return "samples must be 1..16";
+   if (p.blur_radius > 6) return "blur_radius must be 0..6";
+   if (p.show_emitters > 1) return "show_emitters must be 0 or 1";
+   if (!(p.max_weight > 0.0f && p.max_weight < INFINITY)) return "max_weight must be finite and > 0";
+   if (!(p.max_radiance > 0.0f && p.max_radiance < INFINITY)) return "max_radiance must be finite and > 0";
+   if (!(p.intensity >= 0.0f && p.intensity < INFINITY)) return "intensity must be finite and >= 0";
+   if (std::isnan(p.blur_normal_cos) || std::isnan(p.blur_plane)) return "blur_normal_cos and blur_plane must not be NaN";
+   return nullptr;
+}
+
+int uh_set_area_light_params(uh_ctx* c, const UhAreaLightParams* params) {
+   return set_params(c, params, "uh_set_area_light_params", area_light_params_refusal, &uh_ctx::Hybrid::area);
+}
+
+int uh_get_area_light_stats(uh_ctx* c, UhAreaLightStats* out) {
+   int st;
+   if (!stats_begin(c, out, sizeof(*out), "uh_get_area_light_stats: null destination", c && c->hy.area.renders != 0, &st)) return st;
+   uh_ctx::Hybrid::AreaLights& a = c->hy.area;
+   float* const ms[4] = {&out->sample_ms, &out->shadow_ms, &out->filter_ms, &out->composite_ms};
+   for (int k = 0; k < 4; k++)
+      if ((st = stage_ms(c, a.stage[k], ms[k]))) return st;
+   if ((st = stage_ms(c, a.table, &out->table_ms))) return st;
+   uint32_t counters[4] = {0, 0, 0, 0};
+   unsigned long long total = 0;
+   HIP_TRY(c, hipMemcpy(counters, a.counters.p, sizeof(counters), hipMemcpyDeviceToHost));
+   HIP_TRY(c, hipMemcpy(&total, a.total.p, sizeof(total), hipMemcpyDeviceToHost));
+   out->pixels = counters[0];
+   out->samples = (uint64_t)counters[0] * a.samples;
+   out->shadow_rays = counters[1];
+   out->occluded = counters[2];
+   out->emitter_pixels = counters[3];
+   out->emitters = a.emitters;
+   out->total_weight = total;
+   out->table_builds = a.table_builds;
+   return UH_OK;
+}
+
+int uh_read_area_emitters(uh_ctx* c, uint32_t capacity, uint32_t* keys, float* areas, uint32_t* weights, uint32_t* count) {
+   if (!c) return UH_ERR_INVALID_ARGUMENT;
+   if (!count) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_area_emitters: null count");
+   const uh_ctx::Hybrid::AreaLights& a = c->hy.area;
+   if (!a.renders) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_area_emitters before the first area-light pass (UH_HYBRID_AREA_LIGHTS)");
+   HIP_TRY(c, hipSetDevice(c->device));
+   if (int st = sync_all(c)) return st;
+   *count = a.emitters;
+   const size_t n = std::min(capacity, a.emitters);
+   if (!n) return UH_OK;
+   if (keys) HIP_TRY(c, hipMemcpy(keys, a.keys.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+   if (areas) HIP_TRY(c, hipMemcpy(areas, a.areas.p, n * sizeof(float), hipMemcpyDeviceToHost));
+   if (weights) HIP_TRY(c, hipMemcpy(weights, a.weights.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
    return UH_OK;
 }
 

@@ -134,6 +134,29 @@ __device__ __forceinline__ LightTerm light_term(const HybridLight& hl, const Sur
    t.c = v3(kb.x / kPiBrdf + spec.x, kb.y / kPiBrdf + spec.y, kb.z / kPiBrdf + spec.z);
    return t;
 }
+// The same term for a light that is a direction L and a radiance Li and no record (the area-light pass, area_lights.hip), its two halves
+// kept apart: d = kD * (Li * NdotL), without base / PI - the pass filters d and applies the base colour behind the filter -, and s =
+// specular * (Li * NdotL); NdotL = dot(N, L) as the caller formed it, > 0. The operations of light_term in its order (DESIGN.md
+// section 2, "Area lights").
+struct LightHalves {
+   V3 d, s;
+};
+__device__ __forceinline__ LightHalves light_halves(const SurfaceTerms& s, V3 N, V3 V, V3 L, float NdotL, V3 Li) {
+   const V3 Hv = normalize3(V + L);                                                             // lighting:58
+   const float NdotH = fmaxf(dot3(N, Hv), 0.0f);                                                // brdf:7-14
+   float dn = (NdotH * NdotH) * s.a2m1 + 1.0f;
+   dn = (kPiBrdf * dn) * dn;
+   const float NDF = s.a2 / dn;
+   const float G = (NdotL / (NdotL * s.omk + s.k)) * s.ggxV;                                    // brdf:28-36
+   const float x = fminf(fmaxf(1.0f - fmaxf(dot3(Hv, V), 0.0f), 0.0f), 1.0f);                 // brdf:82-85
+   const float p5 = ((x * x) * (x * x)) * x;
+   const V3 F = s.F0 + (v3(1.0f, 1.0f, 1.0f) - s.F0) * p5;
+   const V3 kD = (v3(1.0f, 1.0f, 1.0f) - F) * s.om;                                             // lighting:66-68
+   const float NG = NDF * G, den2 = s.nv4 * NdotL + 0.0001f;                                    // lighting:70-72
+   const V3 spec = v3((NG * F.x) / den2, (NG * F.y) / den2, (NG * F.z) / den2);
+   const V3 rad = Li * NdotL;                                                                   // lighting:78's radiance * NdotL
+   return LightHalves{kD * rad, spec * rad};
+}
 // summed over the light records of k_hybrid_light_prep (the sun first); the loop is wave-uniform
 __device__ __forceinline__ V3 direct_lighting(const HybridLight* __restrict__ lights, uint32_t count, V3 P, V3 N, V3 V, V3 base, float metallic,
                                               float roughness) {

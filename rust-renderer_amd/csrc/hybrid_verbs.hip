@@ -15,7 +15,7 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
    if (!c) return UH_ERR_INVALID_ARGUMENT;
    const uh_ctx::Hybrid& h = c->hy;
    if (!h.counter.p) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid before the first uh_render_hybrid");
-   if (which < 0 || which > UH_HYBRID_GLASS_EVENTS) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..27");
+   if (which < 0 || which > UH_HYBRID_AREA_COUNTS) return fail(c, UH_ERR_INVALID_ARGUMENT, "uh_read_hybrid: image index must be 0..30");
    const char* const no_frame = "uh_read_hybrid: images 6..8 before the first call with an SSAO, deferred, sky or present bit";
    const char* const no_mc = "uh_read_hybrid: images 9..10 before the first marching-cubes pass";
    const char* const no_gr = "uh_read_hybrid: images 11..12 before the first rasterised G-buffer pass";
@@ -24,6 +24,7 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
    const char* const no_gl = "uh_read_hybrid: images 20..22 before the first glossy pass (UH_HYBRID_GLOSSY); until then the image index must be 0..19";
    const char* const no_fog = "uh_read_hybrid: images 23..24 before the first fog pass (UH_HYBRID_FOG); until then the image index must be 0..22";
    const char* const no_glass = "uh_read_hybrid: images 25..27 before the first glass pass (UH_HYBRID_GLASS); until then the image index must be 0..24";
+   const char* const no_area = "uh_read_hybrid: images 28..30 before the first area-light pass (UH_HYBRID_AREA_LIGHTS); until then the image index must be 0..27";
    // image k in UH_HYBRID_* image order: its pixels, its bytes per pixel, whether it exists yet and what a read before that is told
    const struct { const void* pixels; size_t bpp; bool ready; const char* refusal; } img[] = {
       {h.pos.p, sizeof(float4), true, nullptr},
@@ -53,8 +54,11 @@ int uh_read_hybrid(uh_ctx* c, int which, void* out) {
       {h.fog.terms.p, sizeof(float4), h.fog.renders != 0, no_fog},
       {h.glass.radiance.p, sizeof(float4), h.glass.renders != 0, no_glass},
       {h.glass.counts.p, sizeof(uint32_t), h.glass.renders != 0, no_glass},
-      {h.glass.events.p, sizeof(uint32_t), h.glass.renders != 0, no_glass}};
-   static_assert(sizeof(img) / sizeof(img[0]) == UH_HYBRID_GLASS_EVENTS + 1, "one row per UH_HYBRID_* image");
+      {h.glass.events.p, sizeof(uint32_t), h.glass.renders != 0, no_glass},
+      {h.area.diffuse.p, sizeof(float4), h.area.renders != 0, no_area},
+      {h.area.specular.p, sizeof(float4), h.area.renders != 0, no_area},
+      {h.area.counts.p, sizeof(uint32_t), h.area.renders != 0, no_area}};
+   static_assert(sizeof(img) / sizeof(img[0]) == UH_HYBRID_AREA_COUNTS + 1, "one row per UH_HYBRID_* image");
    if (!img[which].ready) return fail(c, UH_ERR_INVALID_ARGUMENT, img[which].refusal);
    return read_back(c, out, img[which].pixels, (size_t)c->W * c->H * img[which].bpp);
 }

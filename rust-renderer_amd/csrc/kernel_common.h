@@ -1,7 +1,7 @@
-// kernel_common.h — what the kernel files (kernels.hip, path_fused.hip, restir.hip, tiles.hip, hybrid_kernels.hip, rtao.hip, rtgi.hip, glossy.hip, fog.hip, glass.hip) share
+// kernel_common.h — what the kernel files (kernels.hip, path_fused.hip, restir.hip, tiles.hip, hybrid_kernels.hip, rtao.hip, rtgi.hip, glossy.hip, fog.hip, glass.hip, area_lights.hip) share
 // besides the device arithmetic: the block size, the launch-grid helpers of their launchers, and four small device functions that kernels
 // of more than one file call (resolve_color: the path tracer's resolve and the tile composition; gbuffer_fetch: the ReSTIR passes and the
-// hybrid passes; rtao_normal: rtao.hip and rtgi.hip; queue_pixels: every classify kernel of the hybrid frame). The hybrid frame's ray
+// hybrid passes; rtao_normal: rtao.hip, rtgi.hip and area_lights.hip; queue_pixels: every classify kernel of the hybrid frame). The hybrid frame's ray
 // passes share more: their persistent walk is item_walk.h, the tile filter of rtao.hip and rtgi.hip is edge_filter.h.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -127,6 +127,12 @@ int uh_set_option(uh_ctx* c, const char* name, int value) {
       if (!range(0, 1)) return bad("must be 0 or 1");
       c->hy.gi.order = (uint32_t)value;
    }
+   else if (n == "area_light_order") {
+      // how the area-light sample kernel lays out its work (area_lights.hip; same images whichever): 0 (default) a pixel's samples
+      // together; 1 one sample of consecutive pixels together
+      if (!range(0, 1)) return bad("must be 0 or 1");
+      c->hy.area.order = (uint32_t)value;
+   }
    else if (n == "fog_order") {
       // how the fog trace kernel lays out its work (fog.hip; same masks whichever): 0 one sample per item, a pixel's samples together;
       // 1 one sample per item, one sample index of consecutive pixels together; 2 (default, measured fastest) one pixel per item, its

@@ -526,6 +526,39 @@ class GlassStats(C.Structure):
 assert C.sizeof(GlassStats) == 80 and GlassStats.misses.offset == 56 and GlassStats.trace_ms.offset == 64 and GlassStats.composite_ms.offset == 76
 
 
+# emissive meshes as area lights of the hybrid frame (an extension; utopian_hip.h "UH_HYBRID_AREA_LIGHTS"): the pass directly behind the
+# deferred pass and its three images
+HYBRID_AREA_LIGHTS = 1 << 21
+HYBRID_AREA_DIFFUSE, HYBRID_AREA_SPECULAR, HYBRID_AREA_COUNTS = 28, 29, 30
+
+
+class AreaLightParams(C.Structure):
+    """UhAreaLightParams: samples per pixel that casts (1..16), the filter's radius (0 none, else 1..6), whether the emitters' own pixels
+    are written (0 or 1), the cap of a sample's geometry term over its pdf, the cap of a pixel's two means per channel, the scale of what
+    the composite adds, and a tap's normal and plane thresholds; uh_area_light_default_params fills the defaults"""
+
+    _fields_ = [("samples", C.c_uint32), ("blur_radius", C.c_uint32), ("show_emitters", C.c_uint32), ("max_weight", C.c_float),
+                ("max_radiance", C.c_float), ("intensity", C.c_float), ("blur_normal_cos", C.c_float), ("blur_plane", C.c_float)]
+
+
+assert C.sizeof(AreaLightParams) == 32 and [getattr(AreaLightParams, n).offset for n, _ in AreaLightParams._fields_] == list(range(0, 32, 4))
+
+
+class AreaLightStats(C.Structure):
+    """UhAreaLightStats: the last area-light pass - the pixels that cast, their samples, the shadow rays cast, those occluded, the emitter
+    pixels, the table's emitter triangles, its total weight and its builds so far, hipEvent ms of the last table build, of classify +
+    sampling, of the shadow rays' walk, of the means + filter and of the composite"""
+
+    _fields_ = [("pixels", C.c_uint64), ("samples", C.c_uint64), ("shadow_rays", C.c_uint64), ("occluded", C.c_uint64),
+                ("emitter_pixels", C.c_uint64), ("emitters", C.c_uint64), ("total_weight", C.c_uint64), ("table_builds", C.c_uint64),
+                ("table_ms", C.c_float), ("sample_ms", C.c_float), ("shadow_ms", C.c_float), ("filter_ms", C.c_float), ("composite_ms", C.c_float),
+                ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(AreaLightStats) == 88 and AreaLightStats.table_builds.offset == 56 and AreaLightStats.table_ms.offset == 64 and \
+    AreaLightStats.composite_ms.offset == 80
+
+
 # motion vectors for moving geometry (an extension; utopian_hip.h "motion vectors"): a modifier of HYBRID_GBUFFER; bit 9 stays unused
 HYBRID_MOTION = 1 << 14
 HYBRID_MOTION_IMAGE = 15
